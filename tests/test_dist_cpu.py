@@ -280,13 +280,57 @@ def test_bench_launcher_reports_a_dead_rank_and_ends_the_others():
     assert not [x for x in r.stdout.splitlines() if x.strip().startswith("{")]   # no line from a run that lost a rank
 
 
-def test_bench_cfg5_is_a_selectable_config_with_the_batch_knobs():
+def _bench_module():
     import importlib.util
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
+    return mod
+
+
+def test_bench_cfg5_is_a_selectable_config_with_the_batch_knobs():
+    mod = _bench_module()
     a = mod.parse_args(["--config", "cfg5", "--gpus", "8"])
     assert a.config == "cfg5" and a.matrices_per_gpu == 8 and a.gpus == 8   # 8 per GPU, 64 on 8 GPUs (BASELINE.json configs[4])
     assert mod.parse_args([]).config == "cfg3" and mod.parse_args([]).gpus == 1
+
+
+def test_bench_steps_set_the_timed_steps_and_dump_outputs_is_an_option():
+    mod = _bench_module()
+    a = mod.parse_args(["--steps", "3", "--warmup", "0", "--dump-outputs", "out"])
+    assert a.steps == 3 and a.warmup == 0 and a.dump_outputs == "out"
+    assert mod.parse_args([]).dump_outputs is None
+    with pytest.raises(SystemExit):
+        mod.parse_args(["--steps", "0"])   # ms_per_step = elapsed / steps
+
+
+def test_bench_dump_outputs_keeps_to_its_budget_and_samples_the_same_entries_on_every_lane(tmp_path):
+    mod = _bench_module()
+    g = torch.Generator().manual_seed(0)
+    lanes = 3
+    outputs = {"u": [torch.randn(200, 40, dtype=torch.float64, generator=g) for _ in range(lanes)],
+               "z": [torch.randn(40, 300, generator=g) for _ in range(lanes)],
+               "ind": [torch.randperm(300, generator=g) for _ in range(lanes)],
+               "s": [torch.rand(40, dtype=torch.float64, generator=g) for _ in range(lanes)]}
+    budget = 200_000   # u (192 000 bytes) and z (144 000) do not fit their shares, ind (7 200) and s (960) do
+    desc = mod.dump_outputs(str(tmp_path / "a"), outputs, budget)
+    files = {f: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sorted(files) == ["ind.npy", "s.npy", "u.npy", "z.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= budget
+    assert files["s.npy"].dtype == np.float64 and np.array_equal(files["s.npy"], torch.stack(outputs["s"]).numpy())
+    assert files["ind.npy"].dtype == np.float64 and np.array_equal(files["ind.npy"], torch.stack(outputs["ind"]).numpy())
+    assert not desc["s"]["sampled"] and not desc["ind"]["sampled"] and desc["u"]["sampled"] and desc["z"]["sampled"]
+    assert files["u.npy"].dtype == np.float64 and files["z.npy"].dtype == np.float32
+    for name in ("u", "z"):
+        got = files[name + ".npy"]
+        assert got.shape[0] == lanes and 0 < got.shape[1] < outputs[name][0].numel()
+        flat = np.stack([t.reshape(-1).numpy() for t in outputs[name]])
+        # the same entries on every lane: locate lane 0's sample in lane 0's output, then read the others there
+        idx = [int(np.nonzero(flat[0] == v)[0][0]) for v in got[0]]
+        assert idx == sorted(idx) and np.array_equal(got, flat[:, idx])
+    # fixed: a second run over the same outputs writes the same files
+    mod.dump_outputs(str(tmp_path / "b"), outputs, budget)
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "b" / f), files[f])

@@ -2,7 +2,6 @@
 bench.py): what the SVD consumer, the QR + ID consumer and the range finder's QR cost beside the two big products.
     python tools/ablate_pipeline.py [--streams 40] [--rounds 10]"""
 import argparse, ctypes, os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "24")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import rusty_compression_amd as rc

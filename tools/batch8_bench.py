@@ -1,6 +1,5 @@
 """Developer tool: the cfg5 batch of 8 (4096 x 4096 f32, rank-64 column ID) on one GPU; env knobs are read by the library."""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import rusty_compression_amd as rc

@@ -3,7 +3,6 @@ timers (rc_profile_*) on every lane's context during one batch of 8, summed per 
 lone rc_column_id_rank call.  (A rocprofv3 kernel trace serialises these lanes: mean kernels in flight 1.1.)
     python tools/batch_prof.py [lanes]"""
 import ctypes, os, sys, collections
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "24")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import rusty_compression_amd as rc

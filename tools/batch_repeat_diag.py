@@ -1,7 +1,6 @@
 """Developer tool: repeat the cfg5 batch of 8 and compare every factor bit for bit with the one-matrix call; on a mismatch print
 where and by how much (which matrix, C or Z, how many entries, the largest difference, the rows / columns touched)."""
 import os, sys
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import rusty_compression_amd as rc

@@ -12,7 +12,6 @@ import sys
 import time
 
 S_LIST = [int(x) for x in (sys.argv[1:] or ["1", "4", "8", "16", "32"])]
-os.environ.setdefault("GPU_MAX_HW_QUEUES", str(max(S_LIST) + 1))
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402

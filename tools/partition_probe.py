@@ -6,7 +6,6 @@ Work per compression (public entry points only; roughly the consumers of rc_rsvd
   G1: Omega, Y = A Omega                      F1: pivoted QR of Y truncated to k -> range
   G2: B = range^T A                           F2: rc_geqp3(B copy) [cooperative QRCP], rc_compute_svd(B), U = range U_b"""
 import argparse, ctypes, os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "24")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import rusty_compression_amd as rc

@@ -2,7 +2,6 @@
 (RC_QRCP_CHECK=1: a bookkeeping fault becomes an error message instead of a wild gather)."""
 import os, sys, time
 os.environ.setdefault("RC_QRCP_CHECK", "1")
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import rusty_compression_amd as rc

@@ -2,7 +2,6 @@
 lane on the SAME matrix and seed, ROUNDS times; every output of every lane must equal lane 0's eager result bit for bit (the big
 GEMMs of the other lanes are the memory load under which the cooperative QRCP exchanges its columns)."""
 import ctypes, os, sys
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "24")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import rusty_compression_amd as rc
