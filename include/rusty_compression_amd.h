@@ -126,15 +126,15 @@ rc_status rc_graph_destroy(rc_context *ctx, void *graph_exec);
  * could not all become resident in time) and falls back to the lazy scheme; 0 disables it. */
 /* Reproducibility.  Every entry point is deterministic: the same call with the same options on the same context state gives the
  * same bits (no atomics on results, fixed split-K reduction order).  Two settings choose between implementations of the same
- * factorization, and bits are promised PER SETTING, not across them: (i) RC_OPT_CONCURRENCY_HINT decides whether wide products
- * split K (a lone launch) or not (many compressions in flight): results differ by summation order; (ii) a call recorded into a
+ * factorization, and bits are promised PER SETTING, not across them: (i) min(RC_OPT_CONCURRENCY_HINT, RC_OPT_KERNEL_SLOTS) decides
+ * how far wide products split K (a lone launch, a few kernels in flight, many): results differ by summation order; (ii) a call recorded into a
  * hipGraph cannot read scalars back, so general-shape pivoted QRs run the per-step chain there and the blocked panels eagerly:
  * same pivots on the data-determined prefix, factors equal to rounding (tests: test_captured_pivoted_qr_of_a_blocked_eligible_shape…).
  * The cfg3 pipeline (rc_rsvd_id_*) takes the same path eagerly and captured: its replays equal the eager result bit for bit.
  * Environment switches that select between implementations (measurement aids, read once per process) change rounding the same
  * way and are NOT part of the promise: RC_TSQR_FOLD (order of the small factors of the tall-skinny QR), RC_QRCP_CAND_MB (which
  * columns of a blocked panel are updated reflector by reflector and which through the block update: last bits of R12 / Z),
- * RC_GEMM_LANES_TARGET, RC_GEMM_SMALL_TARGET (split-K counts), RC_GEMM_PIPE_* / RC_GEMM_RING (which loop runs a product).
+ * RC_GEMM_LANES_TARGET, RC_GEMM_SLOTS_TARGET, RC_GEMM_SMALL_TARGET (split-K counts), RC_GEMM_PIPE_* / RC_GEMM_RING (which loop runs a product).
  * Schedules that only change WHEN or WHERE the same arithmetic is issued -- RC_WQ_STAGES, RC_QRCP_OPTIMISTIC, RC_BATCH_OPTIMISTIC,
  * RC_QRCP_KEEP_DIRECT, RC_ID_FUSED -- give identical bits (tested for the staged k_wq_coop and the optimistic blocked QRCP). */
 /* RC_OPT_POWER_ITERATION_FIXED (default 0): rc_sample_range_power_iteration_* performs it_count power steps
@@ -150,10 +150,15 @@ rc_status rc_graph_destroy(rc_context *ctx, void *graph_exec);
  * rule and down-dating formulas, about three passes over the trailing matrix per panel instead of two per step.  Reads one
  * small struct back per panel, so it is not used while a hipGraph is being captured.  0 selects the per-step chain. */
 /* RC_OPT_CONCURRENCY_HINT (default 1): how many independent compressions the host keeps in flight on this device (one
- * context + stream each).  A lone GEMM splits its reduction dimension until every CU has a workgroup; with many
- * compressions in flight the other streams fill the chip, and un-split products are cheaper (no partial slabs, no
- * reduction kernel): with a hint >= 8 a product with >= 32 output tiles is not split.  Results are deterministic for a
- * given hint; different hints differ by summation order only. */
+ * context + stream each).  What the library sizes its launches for is min(hint, RC_OPT_KERNEL_SLOTS), the compressions
+ * whose kernels can really run side by side.  With 1 a wide GEMM (>= 8 output tiles) splits its reduction dimension until
+ * every CU has a workgroup (256); with 2..7 a product with >= 32 output tiles splits to 128 workgroups, half the chip, so
+ * that a second product can run beside it; with >= 8 the other streams fill the chip and such a product is not split (no
+ * partial slabs, no reduction kernel).  Results are deterministic for a given min(hint, slots); different values differ
+ * by summation order only. */
+/* RC_OPT_KERNEL_SLOTS (default 4): how many kernels of this process the device runs at once.  Packets of one hardware
+ * queue run in order, so this is the number of hardware queues the process has; 4 is the HIP runtime's default.  The
+ * library does not read the runtime's configuration: a host that runs its process with more queues says so here. */
 /* RC_OPT_COOP_PANEL (default 1): the steps of a blocked-QRCP panel run as ONE cooperative launch with the candidate columns
  * resident in registers (one grid barrier per step instead of two kernel boundaries; the candidates are read and written once
  * per panel) whenever the active rows fit (m - j0 <= 4096 in f32, 3072 in f64) and the candidates fit its 512 waves; a launch
@@ -161,7 +166,7 @@ rc_status rc_graph_destroy(rc_context *ctx, void *graph_exec);
  * kernels take it.  Same pivot rule; the candidates' norms are down-dated with ?laqp2's formula (their columns are kept up to
  * date, so a norm that loses its accuracy is recomputed on the spot instead of ending the panel).  0 = step kernels only. */
 enum { RC_OPT_TALL_SKINNY_FAST_PATH = 1, RC_OPT_WIDE_LAZY_QRCP = 2, RC_OPT_WIDE_COOP_QRCP = 3, RC_OPT_POWER_ITERATION_FIXED = 4, RC_OPT_FORK_BRANCHES = 5,
-       RC_OPT_BLOCKED_QRCP = 6, RC_OPT_CONCURRENCY_HINT = 7, RC_OPT_COOP_PANEL = 8 };
+       RC_OPT_BLOCKED_QRCP = 6, RC_OPT_CONCURRENCY_HINT = 7, RC_OPT_COOP_PANEL = 8, RC_OPT_KERNEL_SLOTS = 9 };
 rc_status rc_set_option(rc_context *ctx, int32_t option, int64_t value);
 /* Health word (read and cleared), OR of: 1 non-positive Cholesky pivot, 2 first CholeskyQR pass too far from orthonormal
  * (both: tall-skinny fast path inside a graph, where no fallback is possible), 4 cooperative short-wide QR could not get

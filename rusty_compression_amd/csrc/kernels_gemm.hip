@@ -579,6 +579,17 @@ static int env_int(const char *name, int dflt) {
     return e ? atoi(e) : dflt;
 }
 
+// Split-K target of a product with >= 32 output tiles, from the compressions whose kernels run side by side
+// (min(RC_OPT_CONCURRENCY_HINT, RC_OPT_KERNEL_SLOTS)): alone it splits to cover the chip (`lone`); with >= 8 in flight the
+// other streams fill the chip and it is not split (`many`); with 2..7 -- the default 4 kernel slots -- it takes half the chip,
+// so that a second product runs beside it.  cfg3 at 4 slots, 44 lanes (profiles/r04_q4_kernel_slots_ab.txt): 256 workgroups
+// 552-560, 128 598-602, 64 529-533, un-split 415-417 compressions/s.
+static int wide_target(const rc_context *c, int many, int lone) {
+    static const int target_slots = env_int("RC_GEMM_SLOTS_TARGET", 128);
+    const int n = c->lanes_in_flight();
+    return n >= 8 ? many : n >= 2 ? target_slots : lone;
+}
+
 // target_wgs / min_ksteps (0 = the defaults below): a bandwidth-bound product asks for more, shorter workgroups
 template <typename T, int ALAY, int BLAY, int BM, int BN, int BK, int WM, int WN, int VEC, int NBUF = 2>
 static void launch_cfg(rc_context *c, GemmArgs<T> g, int target_wgs = 0, int min_ksteps = 0) {
@@ -597,8 +608,7 @@ static void launch_cfg(rc_context *c, GemmArgs<T> g, int target_wgs = 0, int min
     // matrices of the CholeskyQR passes: ONE tile, K = 8192) stops at 32 slabs -- 16 K-tiles per workgroup
     // amortise its prologue / slab write, and the reduction reads 4x less than with 128 slabs
     static const int target_big = env_int("RC_GEMM_TARGET_WGS", 256), target_small = env_int("RC_GEMM_SMALL_TARGET", 32);
-    // with many compressions in flight (RC_OPT_CONCURRENCY_HINT) the other streams fill the chip: wide products stay un-split
-    const int target = target_wgs > 0 ? target_wgs : tiles >= 8 ? (c->opt_lanes >= 8 && tiles >= 32 ? 1 : target_big) : target_small;
+    const int target = target_wgs > 0 ? target_wgs : tiles >= 8 ? (tiles >= 32 ? wide_target(c, 1, target_big) : target_big) : target_small;
     int splits = 1;
     const int64_t ksteps = cdiv(g.K, BK);
     const int min_ks = min_ksteps > 0 ? min_ksteps : (tiles >= 32 ? 16 : 4);
@@ -650,12 +660,12 @@ static void launch_f64q(rc_context *c, GemmArgs<double> g, int target_wgs = 0, i
     // matrices of the CholeskyQR passes: ONE tile, K = 8192) stops at 32 slabs -- 16 K-tiles per workgroup
     // amortise its prologue / slab write, and the reduction reads 4x less than with 128 slabs
     static const int target_big = env_int("RC_GEMM_TARGET_WGS", 256), target_small = env_int("RC_GEMM_SMALL_TARGET", 32);
-    // with many compressions in flight (RC_OPT_CONCURRENCY_HINT) the other streams fill the chip: wide products stay un-split
     // (RC_GEMM_LANES_TARGET=64: ONE K split in flight -- CUs come free twice as often, which shortens the cooperative kernels' wait for
     // co-residency: 1081 against 1073 compressions/s on average over five A/B pairs, inside the run-to-run spread; 128 / 256: neutral /
-    // lower.  The default stays un-split.)
+    // lower.  The default stays un-split.  Measured with 24 kernels of a process in flight.)
     static const int target_lanes = env_int("RC_GEMM_LANES_TARGET", 1);
-    const int target = tiles >= 8 ? (c->opt_lanes >= 8 && tiles >= 32 ? target_lanes : (target_wgs > 0 ? target_wgs : target_big)) : target_small;
+    const int lone = target_wgs > 0 ? target_wgs : target_big;
+    const int target = tiles >= 8 ? (tiles >= 32 ? wide_target(c, target_lanes, lone) : lone) : target_small;
     int splits = 1;
     const int64_t ksteps = cdiv(g.K, BK);
     while (tiles * splits < target && splits < 128 && ksteps / (splits * 2) >= (min_ksteps > 0 ? min_ksteps : (tiles >= 32 ? 16 : 4))) splits *= 2;

@@ -127,6 +127,9 @@ struct rc_context {
     int opt_blocked = 1;    // general shapes: blocked ?laqps panels + GEMM block update (0: per-step Householder chain)
     int opt_coop_panel = 1; // RC_OPT_COOP_PANEL: cooperative register-resident panels of the blocked QRCP
     int opt_lanes = 1;      // RC_OPT_CONCURRENCY_HINT: independent compressions the host keeps in flight on this device
+    int opt_slots = 4;      // RC_OPT_KERNEL_SLOTS: kernels of this process the device runs at once
+    // compressions whose kernels actually run side by side: what every "how much of the chip is mine" decision reads
+    int lanes_in_flight() const { return opt_lanes < opt_slots ? opt_lanes : opt_slots; }
     int *health = nullptr;
     int *health_word();
     unsigned *epoch = nullptr;  // launch counter of the fused Jacobi (keys its producer -> consumer records)
