@@ -24,6 +24,7 @@
 #include "rc_gemm.hpp"
 
 #include <cstdlib>
+#include <type_traits>
 
 namespace rc {
 
@@ -264,33 +265,12 @@ __global__ __launch_bounds__(WM *WN * 64) void k_gemm_mfma(GemmArgs<T> g) {
 // so all 64 result lanes are distinct outputs, rows of C are written in 128-byte segments
 // (ORIENT 0) and the LDS images / pitches are exactly those of the 16x16x4 kernel.
 // ---------------------------------------------------------------------------
-#ifdef RC_GEMM_TIMING
-// diagnostic build (tools/gemm_timing.py): wave 0 of workgroup (0, 0) accumulates s_memtime deltas per phase of the main loop
-__device__ unsigned long long g_gemm_dbg[8];
-#define RC_STAMP(k)                                                                              \
-    {                                                                                            \
-        unsigned long long now_;                                                                 \
-        __builtin_amdgcn_sched_barrier(0);                                                       \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(now_)::"memory");           \
-        __builtin_amdgcn_sched_barrier(0);                                                       \
-        tacc[k] += now_ - tlast;                                                                 \
-        tlast = now_;                                                                            \
-    }
-#else
-#define RC_STAMP(k)
-#endif
-
 // GLDS: the B operand tile goes global -> LDS directly (global_load_lds_dwordx4: no staging registers, no LDS write
 // pass); needs B stored [K][N] with unit N stride (BLAY == 0: every k-row of the tile is BN contiguous doubles, copied
 // as BN / 128 pieces of 1 KiB into the padded LDS row), full tiles, 16-byte aligned rows (checked by the host).
 // GLDS == 2: the A tile as well (A stored [K][M] with unit M stride, ALAY == 1: one 1 KiB piece per k-row for the
 // first 128 columns, plus a masked tail piece when 128 < M <= BM = 136; rows of the tile beyond M keep stale LDS
 // contents, which only reach output rows that are never stored).
-// With BLAY == 1 (B stored [N][K], unit K stride: a tile row is 16 doubles = 128 bytes) one piece covers 8 tile rows, so
-// the LDS image cannot be padded; it is [BN][16] with the eight 16-byte chunks of row n stored at chunk ^ ((n >> 1) & 7)
-// (applied to the per-lane SOURCE address), which keeps the 4 x 16 fragment reads at the two-pass minimum.
-// GLDS == 3: as 2 with THREE LDS buffers: the copies of tile it + 2 are issued before tile it is computed and stay in
-// flight across the barrier (counted s_waitcnt vmcnt, raw LDS-only barrier), so no wave waits for HBM at the barrier.
 template <int ALAY, int BLAY, int BM, int BN, int BK, int WM, int WN, int VEC, int ORIENT, int GLDS = 0>
 __global__ __launch_bounds__(WM *WN * 64) void k_gemm_f64q(GemmArgs<double> g) {
     typedef double T;
@@ -302,10 +282,8 @@ __global__ __launch_bounds__(WM *WN * 64) void k_gemm_f64q(GemmArgs<double> g) {
     static_assert(ORIENT == 0 ? (WR % 4 == 0 && WC % 16 == 0) : (WR % 16 == 0 && WC % 4 == 0), "wave tile shape");
     typedef TileStager<T, ALAY, BM, BK, NT, VEC> StA;
     typedef TileStager<T, BLAY == 1 ? 0 : 1, BN, BK, NT, VEC> StB;
-    constexpr bool SWZ = GLDS != 0 && BLAY == 1;  // swizzled, unpadded B image (see above)
-    constexpr int PA = StA::P, PB = SWZ ? BK : StB::P;
-    constexpr int A_ELEMS = StA::ELEMS, B_ELEMS = SWZ ? BN * BK : StB::ELEMS;
-    static_assert(!SWZ || BK == 16, "swizzled B image: 16-deep tiles");
+    constexpr int PA = StA::P, PB = StB::P;
+    constexpr int A_ELEMS = StA::ELEMS, B_ELEMS = StB::ELEMS;
 
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     T *smem = reinterpret_cast<T *>(smem_raw);
@@ -340,24 +318,10 @@ __global__ __launch_bounds__(WM *WN * 64) void k_gemm_f64q(GemmArgs<double> g) {
     StB sb;
     if (GLDS < 2) sa.init(g.a, m0, kbeg, g.sam, g.sak, tid);
     if (!GLDS) sb.init(g.b, n0, kbeg, g.sbn, g.sbk, tid);
-    static_assert(!GLDS || BLAY == 1 || (BN % 128 == 0 && (BK * (BN / 128)) % (NT / 64) == 0), "direct-to-LDS B tile: shape");
-    static_assert(!GLDS || BLAY == 0 || (BN / 8) % (NT / 64) == 0, "direct-to-LDS B tile (K-contiguous): shape");
+    static_assert(!GLDS || (BLAY == 0 && BN % 128 == 0 && (BK * (BN / 128)) % (NT / 64) == 0), "direct-to-LDS B tile: shape");
     static_assert(GLDS < 2 || (ALAY == 1 && BM >= 128 && BM <= 256 && BK % (NT / 64) == 0), "direct-to-LDS A tile: shape");
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     auto glds_b = [&](int64_t k0, T *bdst) {
-        if constexpr (BLAY == 1) {
-            constexpr int PER_WAVE = (BN / 8) / (NT / 64) > 0 ? (BN / 8) / (NT / 64) : 1;
-#pragma unroll
-            for (int i = 0; i < PER_WAVE; ++i) {
-                const int nb = (wave_u * PER_WAVE + i) * 8;         // eight tile rows per 1 KiB piece
-                const int nrow = nb + (lane >> 3);
-                const int chunk = (lane & 7) ^ ((nrow >> 1) & 7);    // source chunk that lands at position lane & 7
-                const T *src = g.b + (n0 + nrow) * g.sbn + (k0 + 2 * chunk);
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                                 (__attribute__((address_space(3))) void *)(bdst + nb * BK), 16, 0, 0);
-            }
-            return;
-        }
         constexpr int PIECES_ROW = BN >= 128 ? BN / 128 : 1, PER_WAVE = BK * PIECES_ROW / (NT / 64) > 0 ? BK * PIECES_ROW / (NT / 64) : 1;
 #pragma unroll
         for (int i = 0; i < PER_WAVE; ++i) {
@@ -396,37 +360,10 @@ __global__ __launch_bounds__(WM *WN * 64) void k_gemm_f64q(GemmArgs<double> g) {
         if (GLDS < 2) sa.store(smem, tid);
         if (!GLDS) sb.store(smem + A_ELEMS, tid);
     }
-    // copies per wave and tile (GLDS == 3 counts them in s_waitcnt vmcnt)
-    constexpr int GL_PER_TILE = (BK / (NT / 64) > 0 ? BK / (NT / 64) : 1) * (BM > 128 ? 2 : 1) + (BLAY == 1 ? (BN / 8) / (NT / 64) : BK * (BN >= 128 ? BN / 128 : 1) / (NT / 64));
-    if constexpr (GLDS == 3) {
-        static_assert(BM <= 128, "counted waits assume no masked tail piece");
-        if (nk > 1) {
-            glds_a(kbeg + BK, smem + STAGE);
-            glds_b(kbeg + BK, smem + A_ELEMS + STAGE);
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(GL_PER_TILE) : "memory");
-        } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    } else {
-        __syncthreads();
-    }
+    __syncthreads();
     constexpr int AM = ORIENT == 0 ? 4 : 16, BNW = ORIENT == 0 ? 16 : 4;
-#ifdef RC_GEMM_TIMING
-    unsigned long long tacc[5] = {0, 0, 0, 0, 0}, tlast;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tlast)::"memory");
-#endif
-    int buf3 = 0;  // GLDS == 3: it % 3
     for (int64_t it = 0; it < nk; ++it) {
-        const int buf = GLDS == 3 ? buf3 : (int)(it & 1);
-        if constexpr (GLDS == 3) {
-            if (it + 2 < nk) {
-                const int nb = buf3 == 0 ? 2 : buf3 - 1;  // (it + 2) % 3: the buffer read in tile it - 1
-                const int64_t koff = (it + 2) * BK;
-                glds_a(kbeg + koff, smem + nb * STAGE);
-                glds_b(kbeg + koff, smem + A_ELEMS + nb * STAGE);
-            }
-        } else
+        const int buf = (int)(it & 1);
         if (it + 1 < nk) {
             const int64_t koff = (it + 1) * BK;
             if (GLDS >= 2) glds_a(kbeg + koff, smem + (buf ^ 1) * STAGE);
@@ -434,7 +371,6 @@ __global__ __launch_bounds__(WM *WN * 64) void k_gemm_f64q(GemmArgs<double> g) {
             if (GLDS) glds_b(kbeg + koff, smem + A_ELEMS + (buf ^ 1) * STAGE);  // that buffer was last read in tile it - 1
             else sb.load(n0, g.N, kbeg + koff, kend, koff * g.sbk, g.sbn, g.sbk, tid);
         }
-        RC_STAMP(0)
         const T *as = smem + buf * STAGE, *bs = smem + A_ELEMS + buf * STAGE;
         auto load_frags = [&](int ks, T *af, T *bf) {
             const int kk = ks * 4 + lk;
@@ -446,11 +382,9 @@ __global__ __launch_bounds__(WM *WN * 64) void k_gemm_f64q(GemmArgs<double> g) {
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
                 const int nn = wn * WC + j * BNW + lbn;
-                if (SWZ) bf[j] = bs[nn * BK + ((((kk >> 1) ^ ((nn >> 1) & 7)) << 1) | (kk & 1))];
-                else bf[j] = BLAY == 1 ? bs[nn * PB + kk] : bs[kk * PB + nn];
+                bf[j] = BLAY == 1 ? bs[nn * PB + kk] : bs[kk * PB + nn];
             }
         };
-        {
         // (two fragment sets with the next sub-step's reads in flight behind the MFMAs -- possible in the direct-to-LDS
         // instance, which has ~60 registers to spare -- measured 4 % SLOWER than the plain loop)
         // not unrolled: with all BK/4 sub-steps in flight the hoisted fragment loads (4 x 17 f64
@@ -459,37 +393,17 @@ __global__ __launch_bounds__(WM *WN * 64) void k_gemm_f64q(GemmArgs<double> g) {
         for (int ks = 0; ks < BK / 4; ++ks) {
             T af[TM], bf[TN];
             load_frags(ks, af, bf);
-            RC_STAMP(1)
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
                 for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_4x4x4f64(af[i], bf[j], acc[i][j], 0, 0, 0);
-            RC_STAMP(2)
         }
+        if (it + 1 < nk) {
+            if (GLDS < 2) sa.store(smem + (buf ^ 1) * STAGE, tid);
+            if (!GLDS) sb.store(smem + A_ELEMS + (buf ^ 1) * STAGE, tid);
         }
-        if constexpr (GLDS == 3) {
-            // tile it + 1 must have landed; the copies of tile it + 2 (issued above) stay in flight
-            if (it + 2 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(GL_PER_TILE) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            RC_STAMP(3)
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            buf3 = buf3 == 2 ? 0 : buf3 + 1;
-        } else {
-            if (it + 1 < nk) {
-                if (GLDS < 2) sa.store(smem + (buf ^ 1) * STAGE, tid);
-                if (!GLDS) sb.store(smem + A_ELEMS + (buf ^ 1) * STAGE, tid);
-            }
-            RC_STAMP(3)
-            __syncthreads();
-        }
-        RC_STAMP(4)
+        __syncthreads();
     }
-#ifdef RC_GEMM_TIMING
-    if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0 && g.M * g.N * g.K > (1ll << 32)) {
-        for (int k2 = 0; k2 < 5; ++k2) g_gemm_dbg[k2] = tacc[k2];
-        g_gemm_dbg[5] = (unsigned long long)nk;
-    }
-#endif
 
     // ---- epilogue: D lane l = 16*i + 4*b + j ---------------------------------------------
     //   ORIENT 0: row = i (l >> 4),           col = 4*b + j (l & 15)
@@ -590,6 +504,43 @@ static int wide_target(const rc_context *c, int many, int lone) {
     return n >= 8 ? many : n >= 2 ? target_slots : lone;
 }
 
+// The tail shared by launch_cfg and launch_f64q: K split until `target` workgroups exist (each at least min_ksteps K tiles deep;
+// 0 = 16 for a product of >= 32 output tiles, 4 otherwise), the slabs, the product on the tiles x splits grid -- `kern`, unless
+// `pipe` launches it on the pipelined main loop of kernels_gemm_pipe.hip -- and the deterministic slab reduction
+template <typename T, int BK, class Pipe>
+static void launch_split(rc_context *c, GemmArgs<T> g, int target, int min_ksteps, void (*kern)(GemmArgs<T>), int nt, size_t lds,
+                         bool (&attr_set)[64], const char *name, Pipe &&pipe) {
+    const int64_t tiles = (int64_t)g.tiles_m * g.tiles_n;
+    int splits = 1;
+    const int64_t ksteps = cdiv(g.K, BK);
+    const int min_ks = min_ksteps > 0 ? min_ksteps : (tiles >= 32 ? 16 : 4);
+    while (tiles * splits < target && splits < 128 && ksteps / (splits * 2) >= min_ks) splits *= 2;
+    g.kchunk = cdiv(cdiv(g.K, splits), BK) * BK;
+    splits = (int)cdiv(g.K, g.kchunk);
+    if (splits < 1) splits = 1;
+    g.splits = splits;
+    ArenaMark mark(c);
+    if (splits > 1) g.partial = c->alloc<T>((size_t)splits * g.M * g.N);
+    if (lds > 48 * 1024 && !attr_set[c->device & 63]) {
+        RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        attr_set[c->device & 63] = true;
+    }
+    c->last_gemm_kernel = name;
+    if (!pipe(g)) {
+        ProfScope ps(c, "kernel:k_gemm_mfma<%s> M=%lld N=%lld K=%lld", sizeof(T) == 8 ? "f64" : "f32", (long long)g.M, (long long)g.N, (long long)g.K);
+        hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)splits), dim3(nt), lds, c->stream, g);
+    }
+    if (splits > 1) {
+        ProfScope ps(c, "kernel:k_splitk_reduce M=%lld N=%lld splits=%d", (long long)g.M, (long long)g.N, splits);
+        if (g.scm < g.scn && g.N >= 32) {
+            hipLaunchKernelGGL(k_splitk_reduce_t<T>, dim3((unsigned)cdiv(g.N, 32), (unsigned)cdiv(g.M, 32)), dim3(256), 0, c->stream, g);
+        } else {
+            int grid = (int)std::min<int64_t>(cdiv(g.M * g.N, 256), 4096);
+            hipLaunchKernelGGL(k_splitk_reduce<T>, dim3(grid), dim3(256), 0, c->stream, g);
+        }
+    }
+}
+
 // target_wgs / min_ksteps (0 = the defaults below): a bandwidth-bound product asks for more, shorter workgroups
 template <typename T, int ALAY, int BLAY, int BM, int BN, int BK, int WM, int WN, int VEC, int NBUF = 2>
 static void launch_cfg(rc_context *c, GemmArgs<T> g, int target_wgs = 0, int min_ksteps = 0) {
@@ -601,48 +552,16 @@ static void launch_cfg(rc_context *c, GemmArgs<T> g, int target_wgs = 0, int min
     g.tiles_m = (int)cdiv(g.M, BM);
     g.tiles_n = (int)cdiv(g.N, BN);
     const int64_t tiles = (int64_t)g.tiles_m * g.tiles_n;
-    // Split K until the grid covers the 256 CUs about twice (only worth it for deep K; tiny
-    // outputs with a deep reduction -- the n x n Gram matrices of the CholeskyQR passes --
-    // need up to 128 slabs to reach every CU).
     // Split K until the grid covers the chip; a product with very few output tiles (the n x n Gram
     // matrices of the CholeskyQR passes: ONE tile, K = 8192) stops at 32 slabs -- 16 K-tiles per workgroup
     // amortise its prologue / slab write, and the reduction reads 4x less than with 128 slabs
     static const int target_big = env_int("RC_GEMM_TARGET_WGS", 256), target_small = env_int("RC_GEMM_SMALL_TARGET", 32);
     const int target = target_wgs > 0 ? target_wgs : tiles >= 8 ? (tiles >= 32 ? wide_target(c, 1, target_big) : target_big) : target_small;
-    int splits = 1;
-    const int64_t ksteps = cdiv(g.K, BK);
-    const int min_ks = min_ksteps > 0 ? min_ksteps : (tiles >= 32 ? 16 : 4);
-    while (tiles * splits < target && splits < 128 && ksteps / (splits * 2) >= min_ks) splits *= 2;
-    g.kchunk = cdiv(cdiv(g.K, splits), BK) * BK;
-    splits = (int)cdiv(g.K, g.kchunk);
-    if (splits < 1) splits = 1;
-    g.splits = splits;
-    ArenaMark mark(c);
-    if (splits > 1) g.partial = c->alloc<T>((size_t)splits * g.M * g.N);
-    auto kern = k_gemm_mfma<T, ALAY, BLAY, BM, BN, BK, WM, WN, VEC, NBUF>;
     static bool attr_set[64] = {};
-    if (lds > 48 * 1024 && !attr_set[c->device & 63]) {
-        RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set[c->device & 63] = true;
-    }
-    {
-        char nm[128];
-        snprintf(nm, sizeof(nm), "k_gemm_mfma<%s,%d,%d,%d,%d,%d,%d,%d,%d,%d>", sizeof(T) == 8 ? "double" : "float", ALAY, BLAY, BM, BN, BK, WM, WN, VEC, NBUF);
-        c->last_gemm_kernel = nm;
-    }
-    {
-        ProfScope ps(c, "kernel:k_gemm_mfma<%s> M=%lld N=%lld K=%lld", sizeof(T) == 8 ? "f64" : "f32", (long long)g.M, (long long)g.N, (long long)g.K);
-        hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)splits), dim3(NT), lds, c->stream, g);
-    }
-    if (splits > 1) {
-        ProfScope ps(c, "kernel:k_splitk_reduce M=%lld N=%lld splits=%d", (long long)g.M, (long long)g.N, splits);
-        if (g.scm < g.scn && g.N >= 32) {
-            hipLaunchKernelGGL(k_splitk_reduce_t<T>, dim3((unsigned)cdiv(g.N, 32), (unsigned)cdiv(g.M, 32)), dim3(256), 0, c->stream, g);
-        } else {
-            int grid = (int)std::min<int64_t>(cdiv(g.M * g.N, 256), 4096);
-            hipLaunchKernelGGL(k_splitk_reduce<T>, dim3(grid), dim3(256), 0, c->stream, g);
-        }
-    }
+    char nm[128];
+    snprintf(nm, sizeof(nm), "k_gemm_mfma<%s,%d,%d,%d,%d,%d,%d,%d,%d,%d>", sizeof(T) == 8 ? "double" : "float", ALAY, BLAY, BM, BN, BK, WM, WN, VEC, NBUF);
+    launch_split<T, BK>(c, g, target, min_ksteps, k_gemm_mfma<T, ALAY, BLAY, BM, BN, BK, WM, WN, VEC, NBUF>, NT, lds, attr_set, nm,
+                        [](const GemmArgs<T> &) { return false; });
 }
 
 template <int ALAY, int BLAY, int BM, int BN, int BK, int WM, int WN, int VEC, int ORIENT, int GLDS = 0>
@@ -651,14 +570,12 @@ static void launch_f64q(rc_context *c, GemmArgs<double> g, int target_wgs = 0, i
     constexpr int NT = WM * WN * 64;
     typedef TileStager<T, ALAY, BM, BK, NT, VEC> StA;
     typedef TileStager<T, BLAY == 1 ? 0 : 1, BN, BK, NT, VEC> StB;
-    constexpr size_t lds = (GLDS == 3 ? 3 : 2) * (size_t)(StA::ELEMS + (GLDS != 0 && BLAY == 1 ? BN * BK : StB::ELEMS)) * sizeof(T);
+    constexpr size_t lds = 2 * (size_t)(StA::ELEMS + StB::ELEMS) * sizeof(T);
     static_assert(lds <= 160 * 1024, "tile does not fit LDS");
     g.tiles_m = (int)cdiv(g.M, BM);
     g.tiles_n = (int)cdiv(g.N, BN);
     const int64_t tiles = (int64_t)g.tiles_m * g.tiles_n;
-    // Split K until the grid covers the chip; a product with very few output tiles (the n x n Gram
-    // matrices of the CholeskyQR passes: ONE tile, K = 8192) stops at 32 slabs -- 16 K-tiles per workgroup
-    // amortise its prologue / slab write, and the reduction reads 4x less than with 128 slabs
+    // the split targets of launch_cfg, except that target_wgs replaces only the one of a lone wide product
     static const int target_big = env_int("RC_GEMM_TARGET_WGS", 256), target_small = env_int("RC_GEMM_SMALL_TARGET", 32);
     // (RC_GEMM_LANES_TARGET=64: ONE K split in flight -- CUs come free twice as often, which shortens the cooperative kernels' wait for
     // co-residency: 1081 against 1073 compressions/s on average over five A/B pairs, inside the run-to-run spread; 128 / 256: neutral /
@@ -666,148 +583,76 @@ static void launch_f64q(rc_context *c, GemmArgs<double> g, int target_wgs = 0, i
     static const int target_lanes = env_int("RC_GEMM_LANES_TARGET", 1);
     const int lone = target_wgs > 0 ? target_wgs : target_big;
     const int target = tiles >= 8 ? (tiles >= 32 ? wide_target(c, target_lanes, lone) : lone) : target_small;
-    int splits = 1;
-    const int64_t ksteps = cdiv(g.K, BK);
-    while (tiles * splits < target && splits < 128 && ksteps / (splits * 2) >= (min_ksteps > 0 ? min_ksteps : (tiles >= 32 ? 16 : 4))) splits *= 2;
-    g.kchunk = cdiv(cdiv(g.K, splits), BK) * BK;
-    splits = (int)cdiv(g.K, g.kchunk);
-    if (splits < 1) splits = 1;
-    g.splits = splits;
-    ArenaMark mark(c);
-    if (splits > 1) g.partial = c->alloc<T>((size_t)splits * g.M * g.N);
-    auto kern = k_gemm_f64q<ALAY, BLAY, BM, BN, BK, WM, WN, VEC, ORIENT, GLDS>;
     static bool attr_set[64] = {};
-    if (lds > 48 * 1024 && !attr_set[c->device & 63]) {
-        RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set[c->device & 63] = true;
-    }
-    {
-        char nm[128];
-        snprintf(nm, sizeof(nm), "k_gemm_f64q<%d,%d,%d,%d,%d,%d,%d,%d,%d,%d>", ALAY, BLAY, BM, BN, BK, WM, WN, VEC, ORIENT, GLDS);
-        c->last_gemm_kernel = nm;
-    }
+    char nm[128];
+    snprintf(nm, sizeof(nm), "k_gemm_f64q<%d,%d,%d,%d,%d,%d,%d,%d,%d,%d>", ALAY, BLAY, BM, BN, BK, WM, WN, VEC, ORIENT, GLDS);
     // the software-pipelined main loop (kernels_gemm_pipe.hip) where it has an instantiation for this tile shape
-    if (!gemm_f64p_launch(c, g, ALAY, BLAY, BM, BN, BK, WM, WN, ORIENT, VEC == 2)) {
-        ProfScope ps(c, "kernel:k_gemm_mfma<f64> M=%lld N=%lld K=%lld", (long long)g.M, (long long)g.N, (long long)g.K);
-        hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)splits), dim3(NT), lds, c->stream, g);
-    }
-    if (splits > 1) {
-        ProfScope ps(c, "kernel:k_splitk_reduce M=%lld N=%lld splits=%d", (long long)g.M, (long long)g.N, splits);
-        if (g.scm < g.scn && g.N >= 32) {
-            hipLaunchKernelGGL(k_splitk_reduce_t<T>, dim3((unsigned)cdiv(g.N, 32), (unsigned)cdiv(g.M, 32)), dim3(256), 0, c->stream, g);
-        } else {
-            int grid = (int)std::min<int64_t>(cdiv(g.M * g.N, 256), 4096);
-            hipLaunchKernelGGL(k_splitk_reduce<T>, dim3(grid), dim3(256), 0, c->stream, g);
-        }
-    }
+    launch_split<T, BK>(c, g, target, min_ksteps, k_gemm_f64q<ALAY, BLAY, BM, BN, BK, WM, WN, VEC, ORIENT, GLDS>, NT, lds, attr_set, nm,
+                        [&](const GemmArgs<T> &gs) { return gemm_f64p_launch(c, gs, ALAY, BLAY, BM, BN, BK, WM, WN, ORIENT, VEC == 2); });
 }
 
-// f64 shapes on the 4x4x4 MFMA (RC_GEMM_F64X4=0 falls back to the 16x16x4 kernel)
+// f64 shapes on the 4x4x4 MFMA
 template <int ALAY, int BLAY, int VEC>
-static bool launch_shape_f64q(rc_context *c, const GemmArgs<double> &g) {
-    static const int use = env_int("RC_GEMM_F64X4", 1);
-    if (!use) return false;
+static void launch_shape_f64q(rc_context *c, const GemmArgs<double> &g) {
     // Skinny shapes: the narrow dimension is padded to the micro-tile granularity only -- 16 along the
     // "shared" operand's side, 4 along the other (ORIENT picks which) -- so N = 133 costs 136, M = 128 costs 128.
     // (N = 133 through ORIENT 1 / BN = 136 measured slower than BN = 144: 34 B-fragment reads per sub-step.)
-    static const int vn = env_int("RC_GEMM_F64Q_N", 3), vm = env_int("RC_GEMM_F64Q_M", 3), smallk = env_int("RC_GEMM_SMALLK", 1), two_wg = env_int("RC_GEMM_SKETCH_2WG", 0), m32 = env_int("RC_GEMM_F64_M32", 1);
     if (g.M <= 144 && g.N <= 144 && g.M > 80 && g.N > 80) launch_f64q<ALAY, BLAY, 144, 144, 16, 3, 3, VEC, 0>(c, g);
     else if (g.N <= 80) launch_f64q<ALAY, BLAY, 256, 80, 16, 8, 1, VEC, 0>(c, g);
-    else if (g.N <= 128 && vn == 3) launch_f64q<ALAY, BLAY, 256, 128, 16, 8, 1, VEC, 0>(c, g);
-    else if (g.N <= 144) {
-        if (vn == 1) launch_f64q<ALAY, BLAY, 128, 144, 16, 8, 1, VEC, 0>(c, g);
-        else if (vn == 2) launch_f64q<ALAY, BLAY, 128, 144, 16, 4, 1, VEC, 0>(c, g);
-        else launch_f64q<ALAY, BLAY, 256, 144, 16, 8, 1, VEC, 0>(c, g);
-    }
-    else if (g.M <= 32 && g.K >= 512 && m32) {
+    else if (g.N <= 128) launch_f64q<ALAY, BLAY, 256, 128, 16, 8, 1, VEC, 0>(c, g);
+    else if (g.N <= 144) launch_f64q<ALAY, BLAY, 256, 144, 16, 8, 1, VEC, 0>(c, g);
+    else if (g.M <= 32 && g.K >= 512) {
         // the HBM-bound 32-row products of the blocked QRCP's panel ends (Y = V^T A, V^T Q): 32-row tiles instead of 80 and many
         // short workgroups, as for f32 (launch_shape)
         launch_f64q<ALAY, BLAY, 32, 256, 16, 1, 8, VEC, 1>(c, g, 512, 4);
     }
     else if (g.M <= 80) launch_f64q<ALAY, BLAY, 80, 256, 16, 1, 8, VEC, 1>(c, g);
-    else if (g.M <= 136 && g.K <= 160 && smallk && g.N >= 2048) {
+    else if (g.M <= 136 && g.K <= 160 && g.N >= 2048) {
         // shallow products on the dependent chain of a compression (apply R^-1, Q1 Q2, Q U_b, ...: K = 128 / 133): 128-wide
         // tiles = twice the workgroups of the 256-wide instance, for latency rather than efficiency
         if (g.M <= 128) launch_f64q<ALAY, BLAY, 128, 128, 16, 1, 8, VEC, 1>(c, g);
         else launch_f64q<ALAY, BLAY, 136, 128, 16, 2, 4, VEC, 0>(c, g);
     }
-    else if (g.M <= 128 && g.M > 80 && vm == 3 && ALAY == 1 && BLAY == 0 && VEC == 2 && two_wg && g.K % 16 == 0 && g.sam == 1 && g.sbn == 1 && g.N >= 1024) {
-        // the projection on two 4-wave workgroups per CU (128 x 128 tiles, 128 x 32 wave tiles; k_gemm_f64a)
-        launch_f64q<ALAY, BLAY, 128, 128, 16, 1, 4, VEC, 1>(c, g, 512);
-    }
-    else if (g.M <= 128 && vm == 3) {
-        static const int glds = env_int("RC_GEMM_GLDS", 2);  // 0: register staging, 1: B tile direct to LDS, 2: A tile too, 3: + three LDS buffers (no gain measured)
-        const bool direct = glds && BLAY == 0 && VEC == 2 && g.N % 256 == 0 && g.K % 16 == 0 && g.sbn == 1 && g.sbk % 2 == 0 &&
-                            reinterpret_cast<uintptr_t>(g.b) % 16 == 0;
+    else if (g.M <= 128) {
+        // the B tile global -> LDS directly where the operands allow it, and the A tile too for exactly 128 rows of an
+        // M-contiguous A (the projection, when it does not take the ring kernel of kernels_gemm_pipe.hip)
         if constexpr (BLAY == 0 && VEC == 2) {
+            const bool direct = g.N % 256 == 0 && g.K % 16 == 0 && g.sbn == 1 && g.sbk % 2 == 0 && reinterpret_cast<uintptr_t>(g.b) % 16 == 0;
             if constexpr (ALAY == 1) {
-                const bool direct_a = glds >= 2 && g.M == 128 && g.sam == 1 && g.sak % 2 == 0 && reinterpret_cast<uintptr_t>(g.a) % 16 == 0;
-                if (direct && direct_a && glds >= 3) { launch_f64q<ALAY, BLAY, 128, 256, 16, 1, 8, VEC, 1, 3>(c, g); return true; }
-                if (direct && direct_a) { launch_f64q<ALAY, BLAY, 128, 256, 16, 1, 8, VEC, 1, 2>(c, g); return true; }
+                const bool direct_a = g.M == 128 && g.sam == 1 && g.sak % 2 == 0 && reinterpret_cast<uintptr_t>(g.a) % 16 == 0;
+                if (direct && direct_a) { launch_f64q<ALAY, BLAY, 128, 256, 16, 1, 8, VEC, 1, 2>(c, g); return; }
             }
-            if (direct) { launch_f64q<ALAY, BLAY, 128, 256, 16, 1, 8, VEC, 1, 1>(c, g); return true; }
+            if (direct) { launch_f64q<ALAY, BLAY, 128, 256, 16, 1, 8, VEC, 1, 1>(c, g); return; }
         }
         launch_f64q<ALAY, BLAY, 128, 256, 16, 1, 8, VEC, 1>(c, g);
     }
-    else if (g.M <= 136 && g.M > 128 && vm == 3 && ALAY == 1 && BLAY == 1 && VEC == 2 && two_wg && g.N % 128 == 0 && g.K % 16 == 0 && g.sam == 1 && g.sbk == 1) {
-        // the sketch on two 4-wave workgroups per CU (136 x 128 tiles, the same 68 x 64 wave tiles; k_gemm_f64a): each one's
-        // barrier and copy issue hide behind the other's MFMAs; a lone product is split until 512 workgroups exist
-        launch_f64q<ALAY, BLAY, 136, 128, 16, 2, 2, VEC, 0>(c, g, 512);
-    }
-    else if (g.M <= 136 && vm == 3) {  // 68 x 64 wave tiles: 17 + 4 fragment reads per 68 MFMAs
-        static const int glds = env_int("RC_GEMM_GLDS", 2);
-        if constexpr (ALAY == 1 && BLAY == 1 && VEC == 2) {
-            // the sketch (as the transposed problem): A' = Omega^T rows of M doubles, B' = A^T with unit K stride
-            const bool direct = glds >= 2 && g.M > 128 && g.N % 256 == 0 && g.K % 16 == 0 && g.sbk == 1 && g.sbn % 2 == 0 &&
-                                reinterpret_cast<uintptr_t>(g.b) % 16 == 0 && g.sam == 1 && g.sak % 2 == 0 && g.sak >= 128 + 2 * ((g.M - 128 + 1) / 2) &&
-                                reinterpret_cast<uintptr_t>(g.a) % 16 == 0;
-            static const int gs = env_int("RC_GEMM_GLDS_SKETCH", 0);  // measured: 1 (B direct) and 2 (A and B direct) are 1-2 % slower here
-            if (direct && gs == 2) { launch_f64q<ALAY, BLAY, 136, 256, 16, 2, 4, VEC, 0, 2>(c, g); return true; }
-            if (direct && gs == 1) { launch_f64q<ALAY, BLAY, 136, 256, 16, 2, 4, VEC, 0, 1>(c, g); return true; }
-        }
-        launch_f64q<ALAY, BLAY, 136, 256, 16, 2, 4, VEC, 0>(c, g);
-    }
-    else if (g.M <= 144) {
-        if (vm == 1) launch_f64q<ALAY, BLAY, 144, 128, 16, 1, 8, VEC, 1>(c, g);
-        else if (vm == 2) launch_f64q<ALAY, BLAY, 144, 128, 16, 1, 4, VEC, 1>(c, g);
-        else launch_f64q<ALAY, BLAY, 144, 256, 16, 1, 8, VEC, 1>(c, g);
-    }
+    else if (g.M <= 136) launch_f64q<ALAY, BLAY, 136, 256, 16, 2, 4, VEC, 0>(c, g);  // 68 x 64 wave tiles: 17 + 4 fragment reads per 68 MFMAs
+    else if (g.M <= 144) launch_f64q<ALAY, BLAY, 144, 256, 16, 1, 8, VEC, 1>(c, g);
     else launch_f64q<ALAY, BLAY, 128, 128, 16, 2, 2, VEC, 0>(c, g);
-    return true;
 }
-template <typename T, int ALAY, int BLAY, int VEC>
-struct F64Q { static bool run(rc_context *, const GemmArgs<T> &) { return false; } };
-template <int ALAY, int BLAY, int VEC>
-struct F64Q<double, ALAY, BLAY, VEC> { static bool run(rc_context *c, const GemmArgs<double> &g) { return launch_shape_f64q<ALAY, BLAY, VEC>(c, g); } };
 
 template <typename T, int ALAY, int BLAY, int VEC>
 static void launch_shape(rc_context *c, const GemmArgs<T> &g) {
-    if (F64Q<T, ALAY, BLAY, VEC>::run(c, g)) return;
-    // Skinny outputs (the sketch Y = A Omega has N = k + p ~ 69..133; the range
-    // projection B = Q^H A has M = k ~ 64..128) get tiles that cover the short
-    // side once, so the long operand streams from HBM exactly once.
-    static const int vn = env_int("RC_GEMM_SKINNY_N", 0), vm = env_int("RC_GEMM_SKINNY_M", 0), m32 = env_int("RC_GEMM_F32_M32", 2);
-    if (g.M <= 144 && g.N <= 144 && g.M > 80 && g.N > 80) launch_cfg<T, ALAY, BLAY, 144, 144, 16, 3, 3, VEC>(c, g);
-    else if (g.N <= 80) launch_cfg<T, ALAY, BLAY, 128, 80, 16, 4, 1, VEC>(c, g);
-    else if (g.N <= 144) {
-        if (vn == 1) launch_cfg<T, ALAY, BLAY, 128, 144, 16, 4, 1, VEC>(c, g);
-        else launch_cfg<T, ALAY, BLAY, 256, 144, 16, 8, 1, VEC>(c, g);
-    } else if (g.M <= 32 && sizeof(T) == 4 && ALAY == 0 && BLAY == 1 && VEC == 2 && g.K >= 512 && m32) {
-        // Y = V^T A of the blocked QRCP (32 x n x m, both operands K-contiguous, HBM-bound at 32 flops per element of A):
-        // 32-row tiles instead of 80 and many short workgroups (16 K slabs instead of 8) so that enough loads are in flight;
-        // measured on 32 x 4096 x 4096 f32: 76 + 6 us (80-row tiles, 8 slabs) -> 37 + 9 us.  (RC_GEMM_F32_M32=1: 32-deep K tiles,
-        // every row of a tile a whole 128-byte line: 43 + 8 us.)
-        if constexpr (sizeof(T) == 4 && ALAY == 0 && BLAY == 1 && VEC == 2) {
-            // HBM-bound (32 flops per element of A): many short workgroups keep enough loads in flight
-            static const int tw = env_int("RC_GEMM_F32_M32_WGS", 512), mk = env_int("RC_GEMM_F32_M32_MINK", 4);
-            if (m32 == 2) launch_cfg<T, ALAY, BLAY, 32, 128, 16, 1, 4, VEC>(c, g, tw, mk);
-            else launch_cfg<T, ALAY, BLAY, 32, 128, 32, 1, 4, VEC>(c, g, tw, mk);
-        }
-    } else if (g.M <= 80) launch_cfg<T, ALAY, BLAY, 80, 128, 16, 1, 4, VEC>(c, g);
-    else if (g.M <= 144) {
-        if (vm == 1) launch_cfg<T, ALAY, BLAY, 144, 128, 16, 1, 4, VEC>(c, g);
-        else launch_cfg<T, ALAY, BLAY, 144, 256, 16, 1, 8, VEC>(c, g);
-    } else launch_cfg<T, ALAY, BLAY, 128, 128, 16, 2, 2, VEC>(c, g);
+    if constexpr (std::is_same_v<T, double>) {
+        launch_shape_f64q<ALAY, BLAY, VEC>(c, g);
+    } else {
+        // Skinny outputs (the sketch Y = A Omega has N = k + p ~ 69..133; the range
+        // projection B = Q^H A has M = k ~ 64..128) get tiles that cover the short
+        // side once, so the long operand streams from HBM exactly once.
+        constexpr bool panel = ALAY == 0 && BLAY == 1 && VEC == 2;
+        if (g.M <= 144 && g.N <= 144 && g.M > 80 && g.N > 80) launch_cfg<T, ALAY, BLAY, 144, 144, 16, 3, 3, VEC>(c, g);
+        else if (g.N <= 80) launch_cfg<T, ALAY, BLAY, 128, 80, 16, 4, 1, VEC>(c, g);
+        else if (g.N <= 144) launch_cfg<T, ALAY, BLAY, 256, 144, 16, 8, 1, VEC>(c, g);
+        else if (panel && g.M <= 32 && g.K >= 512) {
+            // Y = V^T A of the blocked QRCP (32 x n x m, both operands K-contiguous, HBM-bound at 32 flops per element of A):
+            // 32-row tiles instead of 80 and many short workgroups (16 K slabs instead of 8) so that enough loads are in flight;
+            // measured on 32 x 4096 x 4096 f32: 76 + 6 us (80-row tiles, 8 slabs) -> 37 + 9 us.  (32-deep K tiles, every row of
+            // a tile a whole 128-byte line: 43 + 8 us.)
+            if constexpr (panel) launch_cfg<T, ALAY, BLAY, 32, 128, 16, 1, 4, VEC>(c, g, 512, 4);
+        } else if (g.M <= 80) launch_cfg<T, ALAY, BLAY, 80, 128, 16, 1, 4, VEC>(c, g);
+        else if (g.M <= 144) launch_cfg<T, ALAY, BLAY, 144, 256, 16, 1, 8, VEC>(c, g);
+        else launch_cfg<T, ALAY, BLAY, 128, 128, 16, 2, 2, VEC>(c, g);
+    }
 }
 
 template <typename T, int ALAY, int BLAY>
@@ -819,8 +664,7 @@ static void launch_vec(rc_context *c, const GemmArgs<T> &g) {
     };
     const bool va = ALAY == 0 ? ok(g.a, g.sak, g.sam) : ok(g.a, g.sam, g.sak);
     const bool vb = BLAY == 0 ? ok(g.b, g.sbn, g.sbk) : ok(g.b, g.sbk, g.sbn);
-    static const int allow = env_int("RC_GEMM_VEC", 1);
-    if (va && vb && allow) launch_shape<T, ALAY, BLAY, 2>(c, g);
+    if (va && vb) launch_shape<T, ALAY, BLAY, 2>(c, g);
     else launch_shape<T, ALAY, BLAY, 1>(c, g);
 }
 
@@ -852,8 +696,7 @@ void gemm(rc_context *c, T alpha, Mat<T> a, Mat<T> b, T beta, Mat<T> cm) {
     // f64, skinny N under a long M (the sketch Y = A Omega): run the transposed problem C^T = B^T A^T, so the
     // narrow side becomes M, whose micro-tile granularity is 4 (N = 133 costs 136 instead of 144) and whose
     // tile shapes measured faster; only the view descriptors change
-    static const int swap_ok = env_int("RC_GEMM_SWAP_SKINNY", 1);
-    if (sizeof(T) == 8 && swap_ok && b.cols <= 144 && a.rows > 144) {
+    if (sizeof(T) == 8 && b.cols <= 144 && a.rows > 144) {
         const Mat<T> a2 = b.t(), b2 = a.t();
         a = a2;
         b = b2;
@@ -874,9 +717,6 @@ void gemm(rc_context *c, T alpha, Mat<T> a, Mat<T> b, T beta, Mat<T> cm) {
     }
 }
 
-#ifdef RC_GEMM_TIMING
-extern "C" void rc_debug_gemm_timing(unsigned long long *out) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_gemm_dbg), 8 * sizeof(unsigned long long)); }
-#endif
 template void gemm<double>(rc_context *, double, Mat<double>, Mat<double>, double, Mat<double>);
 template void gemm<float>(rc_context *, float, Mat<float>, Mat<float>, float, Mat<float>);
 

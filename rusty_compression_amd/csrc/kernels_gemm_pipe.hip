@@ -77,7 +77,8 @@ struct PipeStage {
 
 // ALAY: 0 = A is K-contiguous, 1 = A is M-contiguous ; BLAY: 0 = B is N-contiguous, 1 = B is K-contiguous
 // ORIENT 0: A micro tile 4 rows, B micro tile 16 columns ; ORIENT 1: 16 rows / 4 columns (see k_gemm_f64q)
-template <int ALAY, int BLAY, int BM, int BN, int BK, int WM, int WN, int ORIENT, int DBG = 0>
+// (the trailing int is always 0: it only keeps the kernel's name, under which profiles/ records it)
+template <int ALAY, int BLAY, int BM, int BN, int BK, int WM, int WN, int ORIENT, int = 0>
 __global__ __launch_bounds__(WM *WN * 64) void k_gemm_f64p(GemmArgs<double> g) {
     constexpr int NT = WM * WN * 64;
     constexpr int WR = BM / WM, WC = BN / WN;
@@ -159,7 +160,7 @@ __global__ __launch_bounds__(WM *WN * 64) void k_gemm_f64p(GemmArgs<double> g) {
         double *nxt = smem + ((it & 1) ^ 1) * STAGE;
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks) {
-            if (ks == NKS - 2 && !(DBG & 1)) {
+            if (ks == NKS - 2) {
                 // tile it + 1 (in the staging registers since the previous barrier) -> the other buffer; every wave finished
                 // reading that buffer before the previous barrier
                 sa.store(nxt, tid);
@@ -188,12 +189,10 @@ __global__ __launch_bounds__(WM *WN * 64) void k_gemm_f64p(GemmArgs<double> g) {
             __builtin_amdgcn_sched_barrier(0);
             if (ks == NKS - 2) {
                 // the LDS stores above have landed and this wave's reads of `cur` are complete
-                if (!(DBG & 2)) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
                 const int t2 = min(it + 2, nk - 1);
-                if (!(DBG & 1)) {
-                    sa.load(a_rsrc, t2 * a_step);
-                    sb.load(b_rsrc, t2 * b_step);
-                }
+                sa.load(a_rsrc, t2 * a_step);
+                sb.load(b_rsrc, t2 * b_step);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -221,9 +220,8 @@ __global__ __launch_bounds__(WM *WN * 64) void k_gemm_f64p(GemmArgs<double> g) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Direct-to-LDS variant: the operand tiles go global -> LDS with buffer_load_dwordx4 ... lds (no staging registers, no LDS
-// store instructions), one 1 KiB piece per wave instruction.  The copies of tile it + 2 are issued right behind the
-// barrier of tile it and are waited for (vmcnt(0)) only in front of the barrier of tile it + 1: a whole tile in flight.
+// Direct-to-LDS copies (k_gemm_f64r): the operand tiles go global -> LDS with buffer_load_dwordx4 ... lds (no staging registers,
+// no LDS store instructions), one 1 KiB piece per wave instruction.
 // ---------------------------------------------------------------------------------------------------------------------
 typedef __attribute__((address_space(3))) void *lds_ptr_t;
 
@@ -316,140 +314,10 @@ struct DirectK {
     }
 };
 
-// ALAY must be 1 (A row-contiguous).  BLAY 0: B row(N)-contiguous (DirectRows) ; BLAY 1: B K-contiguous (DirectK, ORIENT 0 only)
-template <int BLAY, int BM, int BN, int BK, int WM, int WN, int ORIENT>
-__global__ __launch_bounds__(WM *WN * 64) void k_gemm_f64d(GemmArgs<double> g) {
-    constexpr int NT = WM * WN * 64;
-    constexpr int WR = BM / WM, WC = BN / WN;
-    constexpr int AM = ORIENT == 0 ? 4 : 16, BNW = ORIENT == 0 ? 16 : 4;
-    constexpr int TM = WR / AM, TN = WC / BNW;
-    constexpr int NKS = BK / 4;
-    static_assert(WR % AM == 0 && WC % BNW == 0 && NKS >= 2 && (BLAY == 0 || ORIENT == 0), "tile shape");
-    typedef DirectRows<BM, BK, NT> SA;
-    typedef DirectRows<BN, BK, NT> SBR;
-    typedef DirectK<BN, BK, NT> SBK;
-    constexpr int PA = SA::P, PBR = SBR::P;
-    constexpr int A_ELEMS = SA::ELEMS, STAGE = SA::ELEMS + (BLAY == 0 ? SBR::ELEMS : SBK::ELEMS);
-
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    double *smem = reinterpret_cast<double *>(smem_raw);
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-    const int wm = wave / WN, wn = wave % WN;
-    const int lk = lane >> 4;
-    const int la = ORIENT == 0 ? (lane & 3) : (lane & 15);
-    const int lbn = ORIENT == 0 ? (lane & 15) : (lane & 3);
-
-    const int ntiles = g.tiles_m * g.tiles_n;
-    int bid = blockIdx.x;
-    {
-        const int q = ntiles / 8, r = ntiles % 8, xcd = bid % 8, idx = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
-    const int tile_n = bid % g.tiles_n, tile_m = bid / g.tiles_n;
-    const int64_t m0 = (int64_t)tile_m * BM, n0 = (int64_t)tile_n * BN;
-    const int split = blockIdx.y;
-    const int64_t kbeg = (int64_t)split * g.kchunk;
-    const int64_t kend = min(g.K, kbeg + g.kchunk);
-    const int nk = (int)((kend - kbeg) / BK);  // whole tiles (host-checked), >= 1
-
-    double acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = 0.0;
-
-    SA sa;
-    SBR sbr;
-    SBK sbk;
-    sa.init(g.M - m0, g.sak, lane);
-    if (BLAY == 0) sbr.init(g.N - n0, g.sbk, lane);
-    else sbk.init(g.sbn, lane);
-    const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(g.a + m0 * g.sam + kbeg * g.sak), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(g.b + n0 * g.sbn + kbeg * g.sbk), 0, 0x7fffffff, 0x00020000);
-    const uint32_t a_step = (uint32_t)(BK * g.sak * 8), b_step = (uint32_t)(BK * g.sbk * 8);
-    auto copy_tile = [&](int t, double *stage) {
-        sa.copy(a_rsrc, t * a_step, stage, wave_u);
-        if (BLAY == 0) sbr.copy(b_rsrc, t * b_step, stage + A_ELEMS, wave_u);
-        else sbk.copy(b_rsrc, t * b_step, stage + A_ELEMS, wave_u);
-    };
-
-    // fragment addresses of this lane inside a stage (doubles)
-    const int a_lane = lk * PA + wm * WR + la;
-    auto a_frag = [&](const double *st, int ks, int i) -> double { return st[a_lane + ks * 4 * PA + i * AM]; };
-    // B row-contiguous: [BK][PBR] ; B K-contiguous: swizzled [BN][16], (nn >> 1) & 7 == (lbn >> 1) & 7 (ORIENT 0: nn = 16 * x + lbn)
-    const int b_lane = BLAY == 0 ? lk * PBR + wn * WC + lbn : (wn * WC + lbn) * BK + (lk & 1);
-    const int b_swz = (((lk >> 1) ^ (lbn >> 1)) & 7) * 2;
-    auto b_frag = [&](const double *st, int ks, int j) -> double {
-        if (BLAY == 0) return st[A_ELEMS + b_lane + ks * 4 * PBR + j * BNW];
-        return st[A_ELEMS + b_lane + j * BNW * BK + (b_swz ^ (ks * 4))];
-    };
-
-    // ---- prologue --------------------------------------------------------------------------------------------------------
-    copy_tile(0, smem);
-    copy_tile(min(1, nk - 1), smem + STAGE);
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-    double fa[2][TM], fb[2][TN];
-#pragma unroll
-    for (int j = 0; j < TN; ++j) fb[0][j] = b_frag(smem, 0, j);
-#pragma unroll
-    for (int i = 0; i < TM; ++i) fa[0][i] = a_frag(smem, 0, i);
-
-    for (int it = 0; it < nk; ++it) {
-        double *cur = smem + (it & 1) * STAGE;
-        const double *nxt = smem + ((it & 1) ^ 1) * STAGE;
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) {
-            // the fragments of the next sub-step: same buffer, or sub-step 0 of the other buffer (behind the barrier)
-            const double *fs = ks + 1 < NKS ? cur : nxt;
-            const int nks = ks + 1 < NKS ? ks + 1 : 0;
-            const int pb = ks & 1, qb = pb ^ 1;
-#pragma unroll
-            for (int j = 0; j < TN; ++j) fb[qb][j] = b_frag(fs, nks, j);
-#pragma unroll
-            for (int i = 0; i < TM; ++i) fa[qb][i] = a_frag(fs, nks, i);
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_4x4x4f64(fa[pb][i], fb[pb][j], acc[i][j], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (ks == NKS - 2) {
-                // tile it + 1 has landed in `nxt` (copies issued behind the previous barrier); this wave's reads of `cur` are
-                // complete, so behind the barrier `cur` is free for tile it + 2
-                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-                copy_tile(min(it + 2, nk - 1), cur);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    }
-    // the (redundant) copies of the last iterations must not outlive the workgroup's LDS allocation
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-
-    const int er = ORIENT == 0 ? (lane >> 4) : (((lane >> 2) & 3) * 4 + (lane >> 4));
-    const int ec = ORIENT == 0 ? (lane & 15) : (lane & 3);
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int64_t gm = m0 + wm * WR + i * AM + er;
-            const int64_t gn = n0 + wn * WC + j * BNW + ec;
-            if (gm < g.M && gn < g.N) {
-                const double v = acc[i][j];
-                if (g.splits > 1) {
-                    g.partial[((int64_t)split * g.M + gm) * g.N + gn] = v;
-                } else {
-                    double *cp = g.c + gm * g.scm + gn * g.scn;
-                    *cp = g.beta == 0.0 ? g.alpha * v : g.alpha * v + g.beta * (*cp);
-                }
-            }
-        }
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
-// The sketch shape with a HAND-ORDERED main loop.  Same tiles, copies and barrier placement as k_gemm_f64d (A row-contiguous,
-// B K-contiguous and swizzled, 4-row x 16-column micro tiles, 16-deep K tiles), but every LDS read and MFMA of the loop is an
-// `asm volatile` statement, so the instruction order is the written one and the registers live exactly as long as written:
+// The HAND-ORDERED main loop of k_gemm_f64r (on the sketch: A row-contiguous, B K-contiguous and swizzled, 4-row x 16-column
+// micro tiles, 16-deep K tiles): every LDS read and MFMA of the loop is an `asm volatile` statement, so the instruction order
+// is the written one and the registers live exactly as long as written:
 //   sub-step s:  4 B-fragment reads for s + 1 | for i = 0..TM-1: [wait] 4 MFMAs on A-fragment i, then the read of A-fragment i
 //                for s + 1 INTO THE SAME variable (one rotating A set, B double buffered: 50 fragment registers instead of 84)
 // LDS data return in issue order and 20 reads are always issued between a fragment's read and its use, so `s_waitcnt
@@ -475,140 +343,16 @@ __device__ inline void asm_group(double (&acc)[TM][TN], double (&fa)[TM], const 
     asm_mfma_row<TN>(acc[I], fa[I], fb, std::make_integer_sequence<int, TN>{});
     asm_lds_read<OFF0 + I * ISTRIDE>(fa[I], va);
 }
-template <int TM, int TN, int OFF0, int ISTRIDE, int... I>
-__device__ inline void asm_groups(double (&acc)[TM][TN], double (&fa)[TM], const double (&fb)[TN], uint32_t va, std::integer_sequence<int, I...>) {
-    (asm_group<TM, TN, OFF0, ISTRIDE, I>(acc, fa, fb, va), ...);
-}
-
-// BLAY 1 / ORIENT 0: the sketch (B K-contiguous, swizzled image; 4-row x 16-column micro tiles)
-// BLAY 0 / ORIENT 1: the projection (B N-contiguous, padded image; 16-row x 4-column micro tiles)
-template <int BLAY, int ORIENT, int BM, int BN, int WM, int WN, bool MASKTAIL>
-__global__ __launch_bounds__(WM *WN * 64, 2) void k_gemm_f64a(GemmArgs<double> g) {
-    constexpr int BK = 16;
-    constexpr int NT = WM * WN * 64;
-    constexpr int WR = BM / WM, WC = BN / WN;
-    constexpr int AM = ORIENT == 0 ? 4 : 16, BNW = ORIENT == 0 ? 16 : 4;
-    constexpr int TM = WR / AM, TN = WC / BNW;
-    static_assert((BLAY == 1 && ORIENT == 0) || (BLAY == 0 && ORIENT == 1), "instantiated pairings");
-    static_assert(WR % AM == 0 && WC % BNW == 0 && TM + TN - 1 >= 15, "wave tile shape (and at least 15 reads between a fragment's read and its use)");
-    typedef DirectRows<BM, BK, NT, MASKTAIL> SA;
-    typedef DirectRows<BN, BK, NT> SBR;
-    typedef DirectK<BN, BK, NT> SBK;
-    constexpr int PA = SA::P, PB = SBR::P;
-    constexpr int A_ELEMS = SA::ELEMS, STAGE = SA::ELEMS + (BLAY == 0 ? SBR::ELEMS : SBK::ELEMS);
-
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    double *smem = reinterpret_cast<double *>(smem_raw);
-    const uint32_t lds0 = (uint32_t)reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) char *)smem_raw);
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-    const int wm = wave / WN, wn = wave % WN;
-    const int lk = lane >> 4;
-    const int la = ORIENT == 0 ? (lane & 3) : (lane & 15);
-    const int lbn = ORIENT == 0 ? (lane & 15) : (lane & 3);
-
-    const int ntiles = g.tiles_m * g.tiles_n;
-    int bid = blockIdx.x;
-    {
-        const int q = ntiles / 8, r = ntiles % 8, xcd = bid % 8, idx = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
-    const int tile_n = bid % g.tiles_n, tile_m = bid / g.tiles_n;
-    const int64_t m0 = (int64_t)tile_m * BM, n0 = (int64_t)tile_n * BN;
-    const int split = blockIdx.y;
-    const int64_t kbeg = (int64_t)split * g.kchunk;
-    const int64_t kend = min(g.K, kbeg + g.kchunk);
-    const int nk = (int)((kend - kbeg) / BK);
-
-    double acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = 0.0;
-
-    SA sa;
-    SBR sbr;
-    SBK sbk;
-    sa.init(g.M - m0, g.sak, lane);
-    if (BLAY == 0) sbr.init(g.N - n0, g.sbk, lane);
-    else sbk.init(g.sbn, lane);
-    const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(g.a + m0 * g.sam + kbeg * g.sak), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(g.b + n0 * g.sbn + kbeg * g.sbk), 0, 0x7fffffff, 0x00020000);
-    const uint32_t a_step = (uint32_t)(BK * g.sak * 8), b_step = (uint32_t)(BK * g.sbk * 8);
-    auto copy_tile = [&](int t, double *stage) {
-        sa.copy(a_rsrc, t * a_step, stage, wave_u, lane);
-        if (BLAY == 0) sbr.copy(b_rsrc, t * b_step, stage + A_ELEMS, wave_u, lane);
-        else sbk.copy(b_rsrc, t * b_step, stage + A_ELEMS, wave_u);
-    };
-
-    // LDS byte addresses of this lane's fragments inside stage 0.  A fragment i of sub-step s: + (s * 4 * PA + i * AM) * 8.
-    // B, K-contiguous image: row base + ((chunk pair) ^ 32 s), fragment j + j * 16 rows; N-contiguous image: + (s * 4 * PB + j * BNW) * 8.
-    const uint32_t a_addr = lds0 + (uint32_t)(lk * PA + wm * WR + la) * 8;
-    const uint32_t b_addr = BLAY == 1 ? lds0 + (uint32_t)(A_ELEMS + (wn * WC + lbn) * BK + (lk & 1)) * 8
-                                      : lds0 + (uint32_t)(A_ELEMS + lk * PB + wn * WC + lbn) * 8;
-    const uint32_t swz8 = BLAY == 1 ? (uint32_t)((((lk >> 1) ^ (lbn >> 1)) & 7) * 16) : 0u;
-    constexpr int ISTRIDE = AM * 8, AKS = 4 * PA * 8;
-    constexpr int JSTRIDE = BLAY == 1 ? 16 * BK * 8 : BNW * 8, BKS = BLAY == 1 ? 0 : 4 * PB * 8;
-    auto b_base = [&](uint32_t stage_off, int ks) -> uint32_t { return BLAY == 1 ? b_addr + stage_off + (swz8 ^ (uint32_t)(ks * 32)) : b_addr + stage_off; };
-
-    copy_tile(0, smem);
-    copy_tile(min(1, nk - 1), smem + STAGE);
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-
-    double fa[TM], fb[2][TN];
-    asm_read_b<TN, 0, JSTRIDE>(fb[0], b_base(0, 0), std::make_integer_sequence<int, TN>{});
-    asm_read_a<TM, 0, ISTRIDE>(fa, a_addr, std::make_integer_sequence<int, TM>{});
-
-    for (int it = 0; it < nk; ++it) {
-        const uint32_t cur_off = (uint32_t)((it & 1) * STAGE * 8), nxt_off = (uint32_t)(((it & 1) ^ 1) * STAGE * 8);
-        // sub-steps 0 .. 2: the next fragments come from the same stage; sub-step 3: from sub-step 0 of the other stage
-        {
-            asm_read_b<TN, 1 * BKS, JSTRIDE>(fb[1], b_base(cur_off, 1), std::make_integer_sequence<int, TN>{});
-            asm_groups<TM, TN, 1 * AKS, ISTRIDE>(acc, fa, fb[0], a_addr + cur_off, std::make_integer_sequence<int, TM>{});
-        }
-        {
-            asm_read_b<TN, 2 * BKS, JSTRIDE>(fb[0], b_base(cur_off, 2), std::make_integer_sequence<int, TN>{});
-            asm_groups<TM, TN, 2 * AKS, ISTRIDE>(acc, fa, fb[1], a_addr + cur_off, std::make_integer_sequence<int, TM>{});
-        }
-        {
-            asm_read_b<TN, 3 * BKS, JSTRIDE>(fb[1], b_base(cur_off, 3), std::make_integer_sequence<int, TN>{});
-            asm_groups<TM, TN, 3 * AKS, ISTRIDE>(acc, fa, fb[0], a_addr + cur_off, std::make_integer_sequence<int, TM>{});
-            // tile it + 1 has landed in the other stage; this wave's reads of the current one are complete
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            copy_tile(min(it + 2, nk - 1), smem + (it & 1) * STAGE);
-        }
-        {
-            asm_read_b<TN, 0, JSTRIDE>(fb[0], b_base(nxt_off, 0), std::make_integer_sequence<int, TN>{});
-            asm_groups<TM, TN, 0, ISTRIDE>(acc, fa, fb[1], a_addr + nxt_off, std::make_integer_sequence<int, TM>{});
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // outstanding (redundant) copies and prefetched fragments
-
-    const int er = ORIENT == 0 ? (lane >> 4) : (((lane >> 2) & 3) * 4 + (lane >> 4));
-    const int ec = ORIENT == 0 ? (lane & 15) : (lane & 3);
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int64_t gm = m0 + wm * WR + i * AM + er;
-            const int64_t gn = n0 + wn * WC + j * BNW + ec;
-            if (gm < g.M && gn < g.N) {
-                const double v = acc[i][j];
-                if (g.splits > 1) {
-                    g.partial[((int64_t)split * g.M + gm) * g.N + gn] = v;
-                } else {
-                    double *cp = g.c + gm * g.scm + gn * g.scn;
-                    *cp = g.beta == 0.0 ? g.alpha * v : g.alpha * v + g.beta * (*cp);
-                }
-            }
-        }
+// the TM groups of a sub-step, each followed by after(I) (k_gemm_f64r places its copies there)
+template <int TM, int TN, int OFF0, int ISTRIDE, class F, int... I>
+__device__ inline void asm_groups(double (&acc)[TM][TN], double (&fa)[TM], const double (&fb)[TN], uint32_t va, F &&after, std::integer_sequence<int, I...>) {
+    ((asm_group<TM, TN, OFF0, ISTRIDE, I>(acc, fa, fb, va), after(std::integral_constant<int, I>{})), ...);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// k_gemm_f64r: k_gemm_f64a's hand-ordered loop on a THREE-stage LDS ring (round 3).  What k_gemm_f64a still lost were the phases
-// that are synchronous across the workgroup (ablation, DESIGN.md section 3: copy issue 8 %, barrier 4.5 % of the loop): at the
-// end of sub-step 2 every wave drained its LDS reads (lgkmcnt(0): the stage it had just read was about to be overwritten), met
+// k_gemm_f64r: the hand-ordered loop on a THREE-stage LDS ring (round 3).  What its two-stage form (k_gemm_f64a, since removed)
+// still lost were the phases that are synchronous across the workgroup (ablation, DESIGN.md section 3: copy issue 8 %, barrier
+// 4.5 % of the loop): at the end of sub-step 2 every wave drained its LDS reads (lgkmcnt(0): the stage it had just read was about to be overwritten), met
 // the others, and then all eight waves issued their copies of the next tile at once -- no wave issues an MFMA meanwhile.  Here
 //   * the copies of tile t + 2 go into the stage of tile t - 1, whose last reads every wave completed before it reached the
 //     barrier of tile t: the barrier needs no drain of LDS reads any more -- fragment prefetches stay in flight across it --
@@ -616,22 +360,10 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void k_gemm_f64a(GemmArgs<double> g
 //   * a wave's copies are single instructions INSIDE its MFMA stream (one behind each of the first MFMA groups of a sub-step),
 //     the older half of the workgroup in sub-step 3 and the younger half (waves NW/2 ..: the SIMD partners of the first half)
 //     in sub-step 0 of the next tile, so the issue of one wave's copy is covered by its partner's MFMAs on the same SIMD.
-// Tiles, wave tiles, LDS images, fragment rotation and counted waits are k_gemm_f64a's; one stage more of LDS (154 / 160 KB).
+// Tiles, wave tiles, LDS images, fragment rotation and counted waits are those of the two-stage form; one stage more of LDS
+// (154 / 160 KB).  The trailing int is always 0: it only keeps the kernel's name, under which profiles/ and bench.py find it.
 // ---------------------------------------------------------------------------------------------------------------------
-// DBG (diagnostic instantiations only, -DRC_GEMM_PIPE_DEBUG + RC_GEMM_RING_DBG): 1 = no copies in the loop, 2 = no tile barrier,
-// 4 = no fragment reads / counted waits (the MFMAs run on stale registers), 8 = no MFMAs.  Results are garbage; only the time counts.
-template <int DBG, int TM, int TN, int OFF0, int ISTRIDE, int I>
-__device__ inline void asm_group_d(double (&acc)[TM][TN], double (&fa)[TM], const double (&fb)[TN], uint32_t va) {
-    if constexpr (!(DBG & 4)) asm volatile("s_waitcnt lgkmcnt(15)" ::: "memory");
-    if constexpr (!(DBG & 8)) asm_mfma_row<TN>(acc[I], fa[I], fb, std::make_integer_sequence<int, TN>{});
-    if constexpr (!(DBG & 4)) asm_lds_read<OFF0 + I * ISTRIDE>(fa[I], va);
-}
-template <int DBG, int TM, int TN, int OFF0, int ISTRIDE, class F, int... I>
-__device__ inline void asm_groups_c(double (&acc)[TM][TN], double (&fa)[TM], const double (&fb)[TN], uint32_t va, F &&after, std::integer_sequence<int, I...>) {
-    ((asm_group_d<DBG, TM, TN, OFF0, ISTRIDE, I>(acc, fa, fb, va), after(std::integral_constant<int, I>{})), ...);
-}
-
-template <int BLAY, int ORIENT, int BM, int BN, int WM, int WN, bool MASKTAIL, int DBG = 0>
+template <int BLAY, int ORIENT, int BM, int BN, int WM, int WN, bool MASKTAIL, int = 0>
 __global__ __launch_bounds__(WM *WN * 64, 2) void k_gemm_f64r(GemmArgs<double> g) {
     constexpr int BK = 16, NSTAGE = 3;
     constexpr int NT = WM * WN * 64, NW = WM * WN;
@@ -725,30 +457,30 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void k_gemm_f64r(GemmArgs<double> g
         const int s_nxt = s_cur == NSTAGE - 1 ? 0 : s_cur + 1, s_prv = s_cur == 0 ? NSTAGE - 1 : s_cur - 1;
         const uint32_t cur_off = (uint32_t)(s_cur * STAGE * 8), nxt_off = (uint32_t)(s_nxt * STAGE * 8);
         {   // sub-step 0; younger half: its copies of tile it + 1 (stage free since the barrier of tile it - 1)
-            const bool go = !(DBG & 1) && !early && it + 1 < nk;
+            const bool go = !early && it + 1 < nk;
             double *dst = smem + s_nxt * STAGE;
-            if constexpr (!(DBG & 4)) asm_read_b<TN, 1 * BKS, JSTRIDE>(fb[1], b_base(cur_off, 1), std::make_integer_sequence<int, TN>{});
-            asm_groups_c<DBG, TM, TN, 1 * AKS, ISTRIDE>(acc, fa, fb[0], a_addr + cur_off, [&](auto ic) -> void {
+            asm_read_b<TN, 1 * BKS, JSTRIDE>(fb[1], b_base(cur_off, 1), std::make_integer_sequence<int, TN>{});
+            asm_groups<TM, TN, 1 * AKS, ISTRIDE>(acc, fa, fb[0], a_addr + cur_off, [&](auto ic) -> void {
                 constexpr int I = decltype(ic)::value;
                 if constexpr (I >= 1 && I - 1 < NUNITS) { if (go) copy_unit(I - 1, it + 1, dst); }
             }, std::make_integer_sequence<int, TM>{});
         }
         {
-            if constexpr (!(DBG & 4)) asm_read_b<TN, 2 * BKS, JSTRIDE>(fb[0], b_base(cur_off, 2), std::make_integer_sequence<int, TN>{});
-            asm_groups_c<DBG, TM, TN, 2 * AKS, ISTRIDE>(acc, fa, fb[1], a_addr + cur_off, nothing, std::make_integer_sequence<int, TM>{});
+            asm_read_b<TN, 2 * BKS, JSTRIDE>(fb[0], b_base(cur_off, 2), std::make_integer_sequence<int, TN>{});
+            asm_groups<TM, TN, 2 * AKS, ISTRIDE>(acc, fa, fb[1], a_addr + cur_off, nothing, std::make_integer_sequence<int, TM>{});
         }
         {
-            if constexpr (!(DBG & 4)) asm_read_b<TN, 3 * BKS, JSTRIDE>(fb[1], b_base(cur_off, 3), std::make_integer_sequence<int, TN>{});
-            asm_groups_c<DBG, TM, TN, 3 * AKS, ISTRIDE>(acc, fa, fb[0], a_addr + cur_off, nothing, std::make_integer_sequence<int, TM>{});
+            asm_read_b<TN, 3 * BKS, JSTRIDE>(fb[1], b_base(cur_off, 3), std::make_integer_sequence<int, TN>{});
+            asm_groups<TM, TN, 3 * AKS, ISTRIDE>(acc, fa, fb[0], a_addr + cur_off, nothing, std::make_integer_sequence<int, TM>{});
             // tile it + 1 has landed in its stage (this wave's copies: vmcnt(0); everyone's: the barrier); every wave that passes has
             // finished reading tile it - 1.  The fragment reads for sub-step 3 stay in flight.
-            if constexpr (!(DBG & 2)) asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+            asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
         }
         {   // sub-step 3; older half: its copies of tile it + 2 into the stage of tile it - 1
-            const bool go = !(DBG & 1) && early && it + 2 < nk;
+            const bool go = early && it + 2 < nk;
             double *dst = smem + s_prv * STAGE;
-            if constexpr (!(DBG & 4)) asm_read_b<TN, 0, JSTRIDE>(fb[0], b_base(nxt_off, 0), std::make_integer_sequence<int, TN>{});
-            asm_groups_c<DBG, TM, TN, 0, ISTRIDE>(acc, fa, fb[1], a_addr + nxt_off, [&](auto ic) -> void {
+            asm_read_b<TN, 0, JSTRIDE>(fb[0], b_base(nxt_off, 0), std::make_integer_sequence<int, TN>{});
+            asm_groups<TM, TN, 0, ISTRIDE>(acc, fa, fb[1], a_addr + nxt_off, [&](auto ic) -> void {
                 constexpr int I = decltype(ic)::value;
                 if constexpr (I >= 1 && I - 1 < NUNITS) { if (go) copy_unit(I - 1, it + 2, dst); }
             }, std::make_integer_sequence<int, TM>{});
@@ -777,7 +509,7 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void k_gemm_f64r(GemmArgs<double> g
         }
 }
 
-template <int BLAY, int ORIENT, int BM, int BN, int WM, int WN, bool MASKTAIL, int DBG = 0>
+template <int BLAY, int ORIENT, int BM, int BN, int WM, int WN, bool MASKTAIL>
 static bool launch_r(rc_context *c, const GemmArgs<double> &g) {
     constexpr int NT = WM * WN * 64;
     constexpr size_t lds = 3 * (size_t)(DirectRows<BM, 16, NT, MASKTAIL>::ELEMS + (BLAY == 0 ? DirectRows<BN, 16, NT>::ELEMS : DirectK<BN, 16, NT>::ELEMS)) * sizeof(double);
@@ -787,71 +519,21 @@ static bool launch_r(rc_context *c, const GemmArgs<double> &g) {
     const int64_t a_span = ((int64_t)256 * g.sam + g.kchunk * g.sak + 2) * 8;
     const int64_t b_span = ((int64_t)BN * g.sbn + g.kchunk * g.sbk + 2) * 8;
     if (a_span >= (1ll << 31) || b_span >= (1ll << 31) || g.sak < 0 || g.sbn < 0 || g.sbk < 0) return false;
-    auto kern = k_gemm_f64r<BLAY, ORIENT, BM, BN, WM, WN, MASKTAIL, DBG>;
+    auto kern = k_gemm_f64r<BLAY, ORIENT, BM, BN, WM, WN, MASKTAIL>;
     static bool attr_set[64] = {};
     if (!attr_set[c->device & 63]) {
         RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr_set[c->device & 63] = true;
     }
     char nm[128];
-    snprintf(nm, sizeof(nm), "k_gemm_f64r<%d,%d,%d,%d,%d,%d,%s,%d>", BLAY, ORIENT, BM, BN, WM, WN, MASKTAIL ? "true" : "false", DBG);  // as rocprofv3 prints it
+    snprintf(nm, sizeof(nm), "k_gemm_f64r<%d,%d,%d,%d,%d,%d,%s,0>", BLAY, ORIENT, BM, BN, WM, WN, MASKTAIL ? "true" : "false");  // as rocprofv3 prints it
     c->last_gemm_kernel = nm;
     ProfScope ps(c, "kernel:k_gemm_mfma<f64> M=%lld N=%lld K=%lld", (long long)g.M, (long long)g.N, (long long)g.K);
     hipLaunchKernelGGL(kern, dim3((unsigned)(g.tiles_m * g.tiles_n), (unsigned)g.splits), dim3(NT), lds, c->stream, g);
     return true;
 }
 
-template <int BLAY, int ORIENT, int BM, int BN, int WM, int WN, bool MASKTAIL>
-static bool launch_a(rc_context *c, const GemmArgs<double> &g) {
-    constexpr int NT = WM * WN * 64;
-    constexpr size_t lds = 2 * (size_t)(DirectRows<BM, 16, NT, MASKTAIL>::ELEMS + (BLAY == 0 ? DirectRows<BN, 16, NT>::ELEMS : DirectK<BN, 16, NT>::ELEMS)) * sizeof(double);
-    static_assert(lds <= 160 * 1024, "tile does not fit LDS");
-    if (g.sam != 1) return false;
-    if (BLAY == 0 ? g.sbn != 1 : (g.sbk != 1 || g.N % BN != 0)) return false;
-    const int64_t a_span = ((int64_t)256 * g.sam + g.kchunk * g.sak + 2) * 8;
-    const int64_t b_span = ((int64_t)BN * g.sbn + g.kchunk * g.sbk + 2) * 8;
-    if (a_span >= (1ll << 31) || b_span >= (1ll << 31) || g.sak < 0 || g.sbn < 0 || g.sbk < 0) return false;
-    auto kern = k_gemm_f64a<BLAY, ORIENT, BM, BN, WM, WN, MASKTAIL>;
-    static bool attr_set[64] = {};
-    if (lds > 48 * 1024 && !attr_set[c->device & 63]) {
-        RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set[c->device & 63] = true;
-    }
-    char nm[128];
-    snprintf(nm, sizeof(nm), "k_gemm_f64a<%d,%d,%d,%d,%d,%d,%s>", BLAY, ORIENT, BM, BN, WM, WN, MASKTAIL ? "true" : "false");
-    c->last_gemm_kernel = nm;
-    ProfScope ps(c, "kernel:k_gemm_mfma<f64> M=%lld N=%lld K=%lld", (long long)g.M, (long long)g.N, (long long)g.K);
-    hipLaunchKernelGGL(kern, dim3((unsigned)(g.tiles_m * g.tiles_n), (unsigned)g.splits), dim3(NT), lds, c->stream, g);
-    return true;
-}
-
-template <int BLAY, int BM, int BN, int BK, int WM, int WN, int ORIENT>
-static bool launch_d(rc_context *c, const GemmArgs<double> &g) {
-    constexpr int NT = WM * WN * 64;
-    constexpr size_t lds = 2 * (size_t)(DirectRows<BM, BK, NT>::ELEMS + (BLAY == 0 ? DirectRows<BN, BK, NT>::ELEMS : DirectK<BN, BK, NT>::ELEMS)) * sizeof(double);
-    static_assert(lds <= 160 * 1024, "tile does not fit LDS");
-    // unit row stride of A; B: unit column stride (BLAY 0) or unit K stride with whole tiles of columns (BLAY 1)
-    if (g.sam != 1) return false;
-    if (BLAY == 0 ? g.sbn != 1 : (g.sbk != 1 || g.N % BN != 0)) return false;
-    // 32-bit byte offsets from a workgroup's first element over its whole K chunk
-    const int64_t a_span = ((int64_t)256 * g.sam + g.kchunk * g.sak + 2) * 8;
-    const int64_t b_span = ((int64_t)BN * g.sbn + g.kchunk * g.sbk + 2) * 8;
-    if (a_span >= (1ll << 31) || b_span >= (1ll << 31) || g.sak < 0 || g.sbn < 0 || g.sbk < 0) return false;
-    auto kern = k_gemm_f64d<BLAY, BM, BN, BK, WM, WN, ORIENT>;
-    static bool attr_set[64] = {};
-    if (lds > 48 * 1024 && !attr_set[c->device & 63]) {
-        RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set[c->device & 63] = true;
-    }
-    char nm[128];
-    snprintf(nm, sizeof(nm), "k_gemm_f64d<%d,%d,%d,%d,%d,%d,%d>", BLAY, BM, BN, BK, WM, WN, ORIENT);
-    c->last_gemm_kernel = nm;
-    ProfScope ps(c, "kernel:k_gemm_mfma<f64> M=%lld N=%lld K=%lld", (long long)g.M, (long long)g.N, (long long)g.K);
-    hipLaunchKernelGGL(kern, dim3((unsigned)(g.tiles_m * g.tiles_n), (unsigned)g.splits), dim3(NT), lds, c->stream, g);
-    return true;
-}
-
-template <int ALAY, int BLAY, int BM, int BN, int BK, int WM, int WN, int ORIENT, int DBG = 0>
+template <int ALAY, int BLAY, int BM, int BN, int BK, int WM, int WN, int ORIENT>
 static bool launch_p(rc_context *c, const GemmArgs<double> &g) {
     constexpr int NT = WM * WN * 64;
     typedef PipeStage<ALAY, BM, BK, NT> SA;
@@ -862,7 +544,7 @@ static bool launch_p(rc_context *c, const GemmArgs<double> &g) {
     const int64_t a_span = ((int64_t)BM * g.sam + g.kchunk * g.sak + 2) * 8;
     const int64_t b_span = ((int64_t)BN * g.sbn + g.kchunk * g.sbk + 2) * 8;
     if (a_span >= (1ll << 31) || b_span >= (1ll << 31) || g.sam < 0 || g.sak < 0 || g.sbn < 0 || g.sbk < 0) return false;
-    auto kern = k_gemm_f64p<ALAY, BLAY, BM, BN, BK, WM, WN, ORIENT, DBG>;
+    auto kern = k_gemm_f64p<ALAY, BLAY, BM, BN, BK, WM, WN, ORIENT>;
     static bool attr_set[64] = {};
     if (lds > 48 * 1024 && !attr_set[c->device & 63]) {
         RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -877,61 +559,24 @@ static bool launch_p(rc_context *c, const GemmArgs<double> &g) {
 }
 
 bool gemm_f64p_launch(rc_context *c, const GemmArgs<double> &g, int alay, int blay, int bm, int bn, int bk, int wm, int wn, int orient, bool vec2) {
-    static const int use = [] { const char *e = getenv("RC_GEMM_PIPE"); return e ? atoi(e) : 1; }();
-    if (!use || !vec2 || bk != 16) return false;
+    if (!vec2 || bk != 16) return false;
     // whole K tiles in every split, at least one
     if (g.K % bk != 0 || g.kchunk % bk != 0 || g.K < bk) return false;
+    // the two wide products on the three-stage ring (k_gemm_f64r) where its copies apply: the sketch (as the transposed problem)
+    // and the projection
+    if (alay == 1 && blay == 1 && bm == 136 && bn == 256 && wm == 2 && wn == 4 && orient == 0 && launch_r<1, 0, 136, 256, 2, 4, true>(c, g)) return true;
+    if (alay == 1 && blay == 0 && bm == 128 && bn == 256 && wm == 1 && wn == 8 && orient == 1 && launch_r<0, 1, 128, 256, 1, 8, false>(c, g)) return true;
 #define RC_PIPE_CASE(AL, BL, BM_, BN_, WM_, WN_, OR_)                                                              \
     if (alay == AL && blay == BL && bm == BM_ && bn == BN_ && wm == WM_ && wn == WN_ && orient == OR_)             \
         return launch_p<AL, BL, BM_, BN_, 16, WM_, WN_, OR_>(c, g);
-#ifdef RC_GEMM_PIPE_DEBUG
-    {
-        static const int dbg = [] { const char *e = getenv("RC_GEMM_PIPE_DBG"); return e ? atoi(e) : 0; }();
-        if (alay == 1 && blay == 0 && bm == 128 && bn == 256 && wm == 1 && wn == 8 && orient == 1) {
-            if (dbg == 1) return launch_p<1, 0, 128, 256, 16, 1, 8, 1, 1>(c, g);
-            if (dbg == 2) return launch_p<1, 0, 128, 256, 16, 1, 8, 1, 2>(c, g);
-            if (dbg == 3) return launch_p<1, 0, 128, 256, 16, 1, 8, 1, 3>(c, g);
-        }
-    }
-#endif
-    // RC_GEMM_PIPE_DIRECT: 1 (default) = direct-to-LDS copies where they measured faster (the sketch: 377 -> 358 us; its
-    // register-staged instance spills), 2 = also for the projection (325 us against 321 us register-staged), 0 = never
-    static const int direct = [] { const char *e = getenv("RC_GEMM_PIPE_DIRECT"); return e ? atoi(e) : 1; }();
-    if (direct && alay == 1 && bk == 16) {
-        // hand-ordered main loop (k_gemm_f64a) on two 4-wave workgroups per CU, where kernels_gemm.hip chose 128-column tiles for it
-        static const int wide_asm = [] { const char *e = getenv("RC_GEMM_PIPE_ASM"); return e ? atoi(e) : 1; }();  // 0: the compiler-scheduled loops (k_gemm_f64d / k_gemm_f64p)
-        // three-stage ring with the copies inside the MFMA stream (k_gemm_f64r); RC_GEMM_RING=0: the two-stage k_gemm_f64a
-        static const int ring = [] { const char *e = getenv("RC_GEMM_RING"); return e ? atoi(e) : 1; }();
-#ifdef RC_GEMM_PIPE_DEBUG
-        {
-            static const int rdbg = [] { const char *e = getenv("RC_GEMM_RING_DBG"); return e ? atoi(e) : 0; }();
-            if (rdbg && blay == 1 && bm == 136 && bn == 256 && wm == 2 && wn == 4 && orient == 0) {
-#define RC_RDBG(D) if (rdbg == D) return launch_r<1, 0, 136, 256, 2, 4, true, D>(c, g);
-                RC_RDBG(1) RC_RDBG(2) RC_RDBG(3) RC_RDBG(4) RC_RDBG(7) RC_RDBG(8) RC_RDBG(12) RC_RDBG(5) RC_RDBG(6)
-#undef RC_RDBG
-            }
-        }
-#endif
-        // (RC_GEMM_RING: 1 both products, 2 the sketch only, 3 the projection only)
-        if (wide_asm && (ring == 1 || ring == 2) && blay == 1 && bm == 136 && bn == 256 && wm == 2 && wn == 4 && orient == 0 && launch_r<1, 0, 136, 256, 2, 4, true>(c, g)) return true;
-        if (wide_asm && (ring == 1 || ring == 3) && blay == 0 && bm == 128 && bn == 256 && wm == 1 && wn == 8 && orient == 1 && launch_r<0, 1, 128, 256, 1, 8, false>(c, g)) return true;
-        if (wide_asm && blay == 1 && bm == 136 && bn == 256 && wm == 2 && wn == 4 && orient == 0 && launch_a<1, 0, 136, 256, 2, 4, true>(c, g)) return true;
-        if (wide_asm && blay == 0 && bm == 128 && bn == 256 && wm == 1 && wn == 8 && orient == 1 && launch_a<0, 1, 128, 256, 1, 8, false>(c, g)) return true;
-        if (blay == 1 && bm == 136 && bn == 128 && wm == 2 && wn == 2 && orient == 0 && launch_a<1, 0, 136, 128, 2, 2, true>(c, g)) return true;
-        if (blay == 0 && bm == 128 && bn == 128 && wm == 1 && wn == 4 && orient == 1 && launch_a<0, 1, 128, 128, 1, 4, false>(c, g)) return true;
-        if (blay == 1 && bm == 136 && bn == 256 && wm == 2 && wn == 4 && orient == 0 && launch_d<1, 136, 256, 16, 2, 4, 0>(c, g)) return true;
-        if (direct >= 2 && blay == 0 && bm == 128 && bn == 256 && wm == 1 && wn == 8 && orient == 1 && launch_d<0, 128, 256, 16, 1, 8, 1>(c, g)) return true;
-    }
     // the Gram products of the CholeskyQR passes (Y^T Y: K-contiguous both; Q1^T Q1 on the row-major Q1: M- / N-contiguous): one
     // 144 x 144 tile on 3 x 3 waves, K split over the workgroups -- the compiler-scheduled loop of kernels_gemm.hip spends ~5 us per
-    // K tile on them (load -> LDS -> MFMA in sequence), this one keeps the next tile's loads in flight (RC_GEMM_PIPE_GRAM=0: off)
-    static const int gram = [] { const char *e = getenv("RC_GEMM_PIPE_GRAM"); return e ? atoi(e) : 1; }();
-    if (gram) {
-        RC_PIPE_CASE(0, 1, 144, 144, 3, 3, 0)
-        RC_PIPE_CASE(1, 0, 144, 144, 3, 3, 0)
-    }
+    // K tile on them (load -> LDS -> MFMA in sequence), this one keeps the next tile's loads in flight
+    RC_PIPE_CASE(0, 1, 144, 144, 3, 3, 0)
+    RC_PIPE_CASE(1, 0, 144, 144, 3, 3, 0)
     // (the K = 128 shallow products -- Q = range Q_b, C = Q R11, U = range U_b -- through this loop on 128 x 128 tiles measured
     // neutral to slightly slower in the headline, 1072 / 1083 against 1084 / 1084: eight K tiles do not amortise the prologue)
+    // the sketch and the projection where the ring refuses them (the sketch with N not a multiple of 256; spans of 2 GiB and more)
     RC_PIPE_CASE(1, 1, 136, 256, 2, 4, 0)  // the sketch (transposed problem): 68 x 64 wave tiles
     RC_PIPE_CASE(1, 0, 128, 256, 1, 8, 1)  // the projection: 128 x 32 wave tiles
 #undef RC_PIPE_CASE
@@ -942,12 +587,6 @@ bool gemm_f64p_launch(rc_context *c, const GemmArgs<double> &g, int alay, int bl
 
 namespace rc {
 // (explicit: clang did not emit the host stub of the second instantiation from its use inside the `&&` chain above)
-template __global__ void k_gemm_f64d<1, 136, 256, 16, 2, 4, 0>(GemmArgs<double>);
-template __global__ void k_gemm_f64a<1, 0, 136, 128, 2, 2, true>(GemmArgs<double>);
-template __global__ void k_gemm_f64a<1, 0, 136, 256, 2, 4, true>(GemmArgs<double>);
-template __global__ void k_gemm_f64a<0, 1, 128, 256, 1, 8, false>(GemmArgs<double>);
-template __global__ void k_gemm_f64a<0, 1, 128, 128, 1, 4, false>(GemmArgs<double>);
-template __global__ void k_gemm_f64d<0, 128, 256, 16, 1, 8, 1>(GemmArgs<double>);
 template __global__ void k_gemm_f64r<1, 0, 136, 256, 2, 4, true>(GemmArgs<double>);
 template __global__ void k_gemm_f64r<0, 1, 128, 256, 1, 8, false>(GemmArgs<double>);
 }

@@ -9,6 +9,8 @@ Tolerances (tests/helpers.py TOL): f64 factors <= 1e-10 relative Frobenius,
 singular values <= 1e-12 relative; f32 1e-4 / 1e-5.  Permutation indices are
 compared bit-exactly on the prefix that is determined by the data (helpers.stable_prefix).
 """
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -59,40 +61,126 @@ def test_gemm_all_layouts_and_ragged_shapes(dtype, tol):
     assert rel(npy(rc.conj_matmat(big, y)), big.T.astype(np.float64) @ y) <= tol
 
 
-@pytest.mark.parametrize("opt", ["default", "two_workgroups", "two_stage"])
-def test_f64_gemm_hand_ordered_loops_on_their_shapes(opt):
-    """k_gemm_f64r (round 3, the default: three-stage LDS ring, copies inside the MFMA stream) and k_gemm_f64a (two stages;
-    `two_stage` = RC_GEMM_RING=0, `two_workgroups` = its 2 x 4-wave variant) -- hand-ordered main loops, direct-to-LDS copies,
-    masked tail copy: the shapes that reach their instantiations --
-    129..136 rows over a K-contiguous wide operand (the sketch as the transposed problem) and <= 128 rows over an N-contiguous
-    one (the projection) -- around their preconditions: row counts that clamp, one K tile, K tiles that split, wide / narrow N,
-    plus neighbours that must fall back to the compiler-scheduled kernels (K not a multiple of 16, N not a multiple of the tile)."""
-    import os
-    import subprocess
-    import sys
+def last_gemm_kernel():
+    """The instantiation of the most recent GEMM launch on the default context, as rocprofv3 names it."""
+    from rusty_compression_amd import _lib
 
-    knob = {"two_workgroups": ("RC_GEMM_SKETCH_2WG", "1"), "two_stage": ("RC_GEMM_RING", "0")}.get(opt)
-    if knob and os.environ.get(knob[0]) != knob[1]:
-        # the knobs are read once per process: run this parametrization in a child with it set
-        env = dict(os.environ, **{knob[0]: knob[1]})
-        res = subprocess.run([sys.executable, "-m", "pytest", __file__, "-m", "gpu", "-q", "-x", "-k", "hand_ordered_loops and " + opt], env=env, capture_output=True, text=True, timeout=600)
-        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-1000:]
-        return
+    fn = _lib.lib().rc_last_gemm_kernel_name
+    fn.restype = ctypes.c_char_p
+    fn.argtypes = [ctypes.c_void_p]
+    return fn(_lib.default_context()._h).decode()
+
+
+def gemm_operand(x, layout):
+    """`x` on the device: "C" row-major / "F" column-major with an even leading dimension (16-byte vector staging),
+    "c" row-major with an odd leading dimension (scalar staging)."""
+    r, c = x.shape
+    if layout == "F":
+        t = torch.zeros((c, r + (r & 1)), dtype=torch.from_numpy(x).dtype, device="cuda")[:, :r]
+        t.copy_(torch.from_numpy(np.ascontiguousarray(x.T)))
+        return t.t()
+    ld = c + (c & 1) if layout == "C" else c + 1 - (c & 1)
+    t = torch.zeros((r, ld), dtype=torch.from_numpy(x).dtype, device="cuda")[:, :c]
+    t.copy_(torch.from_numpy(x))
+    return t
+
+
+# Every arm of the GEMM dispatch (kernels_gemm.hip launch_shape_f64q / launch_shape, kernels_gemm_pipe.hip gemm_f64p_launch) with
+# the instantiation it launches: (dtype, layout of A, layout of B, M, N, K, kernel).  "C" A / "F" B: K-contiguous; "F" A: M-contiguous;
+# "C" B: N-contiguous.  f64 products with N <= 144 under M > 144 run as the transposed problem.
+GEMM_DISPATCH = [
+    # f64: the n x n Gram products (pipelined loop for the two CholeskyQR layouts), 144 x 144 tiles otherwise
+    ("f64", "C", "F", 100, 100, 512, "k_gemm_f64p<0,1,144,144,16,3,3,0>"),
+    ("f64", "F", "C", 100, 100, 512, "k_gemm_f64p<1,0,144,144,16,3,3,0>"),
+    ("f64", "C", "C", 100, 100, 512, "k_gemm_f64q<0,0,144,144,16,3,3,2,0,0>"),
+    ("f64", "C", "F", 100, 100, 40, "k_gemm_f64q<0,1,144,144,16,3,3,2,0,0>"),
+    ("f64", "c", "C", 100, 100, 97, "k_gemm_f64q<0,0,144,144,16,3,3,1,0,0>"),
+    # f64 skinny N
+    ("f64", "C", "C", 100, 64, 256, "k_gemm_f64q<0,0,256,80,16,8,1,2,0,0>"),
+    ("f64", "C", "C", 60, 128, 256, "k_gemm_f64q<0,0,256,128,16,8,1,2,0,0>"),
+    ("f64", "C", "C", 60, 136, 256, "k_gemm_f64q<0,0,256,144,16,8,1,2,0,0>"),
+    # f64 skinny M: 32-row panel products, <= 80 rows, shallow K over a wide N
+    ("f64", "C", "C", 32, 512, 1024, "k_gemm_f64q<0,0,32,256,16,1,8,2,1,0>"),
+    ("f64", "C", "C", 64, 512, 256, "k_gemm_f64q<0,0,80,256,16,1,8,2,1,0>"),
+    ("f64", "C", "C", 128, 2048, 128, "k_gemm_f64q<0,0,128,128,16,1,8,2,1,0>"),
+    ("f64", "F", "F", 136, 2048, 128, "k_gemm_f64q<1,1,136,128,16,2,4,2,0,0>"),
+    # f64 <= 128 rows: the projection on the ring kernel; direct-to-LDS B tile; register staging
+    ("f64", "F", "C", 128, 512, 256, "k_gemm_f64r<0,1,128,256,1,8,false,0>"),
+    ("f64", "F", "C", 100, 300, 256, "k_gemm_f64r<0,1,128,256,1,8,false,0>"),
+    ("f64", "C", "C", 128, 512, 256, "k_gemm_f64q<0,0,128,256,16,1,8,2,1,1>"),
+    ("f64", "F", "C", 100, 300, 40, "k_gemm_f64q<1,0,128,256,16,1,8,2,1,0>"),
+    ("f64", "C", "C", 1000, 100, 256, "k_gemm_f64q<1,1,128,256,16,1,8,2,1,0>"),
+    # f64 129 .. 136 rows: the sketch on the ring kernel, the pipelined loop, the plain loop
+    ("f64", "F", "F", 133, 512, 256, "k_gemm_f64r<1,0,136,256,2,4,true,0>"),
+    ("f64", "F", "F", 133, 300, 256, "k_gemm_f64p<1,1,136,256,16,2,4,0>"),
+    ("f64", "F", "F", 133, 512, 40, "k_gemm_f64q<1,1,136,256,16,2,4,2,0,0>"),
+    ("f64", "F", "C", 133, 512, 256, "k_gemm_f64q<1,0,136,256,16,2,4,2,0,0>"),
+    # f64 137 .. 144 rows, and everything larger
+    ("f64", "F", "F", 140, 512, 256, "k_gemm_f64q<1,1,144,256,16,1,8,2,1,0>"),
+    ("f64", "C", "C", 300, 300, 256, "k_gemm_f64q<0,0,128,128,16,2,2,2,0,0>"),
+    # f32
+    ("f32", "C", "C", 100, 100, 256, "k_gemm_mfma<float,0,0,144,144,16,3,3,2,2>"),
+    ("f32", "C", "C", 300, 64, 256, "k_gemm_mfma<float,0,0,128,80,16,4,1,2,2>"),
+    ("f32", "C", "C", 300, 136, 256, "k_gemm_mfma<float,0,0,256,144,16,8,1,2,2>"),
+    ("f32", "C", "F", 32, 512, 1024, "k_gemm_mfma<float,0,1,32,128,16,1,4,2,2>"),
+    ("f32", "C", "C", 32, 512, 1024, "k_gemm_mfma<float,0,0,80,128,16,1,4,2,2>"),
+    ("f32", "C", "C", 64, 512, 256, "k_gemm_mfma<float,0,0,80,128,16,1,4,2,2>"),
+    ("f32", "C", "C", 128, 512, 256, "k_gemm_mfma<float,0,0,144,256,16,1,8,2,2>"),
+    ("f32", "C", "C", 300, 300, 256, "k_gemm_mfma<float,0,0,128,128,16,2,2,2,2>"),
+    ("f32", "c", "C", 300, 300, 255, "k_gemm_mfma<float,0,0,128,128,16,2,2,1,2>"),
+]
+
+
+def test_gemm_dispatch_launches_the_expected_instantiation():
+    rng = np.random.default_rng(4)
+    wrong = []
+    for dt, la, lb, m, n, k, want in GEMM_DISPATCH:
+        dtype, tol = (np.float64, 1e-13) if dt == "f64" else (np.float32, 2e-6)
+        a = rng.standard_normal((m, k)).astype(dtype)
+        b = rng.standard_normal((k, n)).astype(dtype)
+        out = rc.dot(gemm_operand(a, la), gemm_operand(b, lb))
+        got = last_gemm_kernel()
+        if got != want:
+            wrong.append((dt, la, lb, m, n, k, got, want))
+        assert rel(npy(out), a.astype(np.float64) @ b.astype(np.float64)) <= tol, (dt, la, lb, m, n, k)
+    assert not wrong, "\n".join(map(str, wrong))
+
+
+def test_f64_gemm_hand_ordered_loops_on_their_shapes():
+    """k_gemm_f64r (three-stage LDS ring, copies inside the MFMA stream, hand-ordered main loop, direct-to-LDS copies, masked
+    tail copy) on the shapes that reach it -- 129..136 rows over a K-contiguous wide operand (the sketch as the transposed
+    problem) and <= 128 rows over an N-contiguous one (the projection) -- around its preconditions: row counts that clamp, one
+    K tile, K tiles that split, wide / narrow N, plus neighbours that must fall back to k_gemm_f64p / k_gemm_f64q (K not a
+    multiple of 16, N not a multiple of the tile, shallow K over a wide N)."""
     rng = np.random.default_rng(5)
+    sketch_ring = "k_gemm_f64r<1,0,136,256,2,4,true,0>"
+    projection_ring = "k_gemm_f64r<0,1,128,256,1,8,false,0>"
     for m in (129, 133, 136, 128, 97, 130):
         for n in (256, 512, 768, 2048, 300):
             for k in (16, 48, 1024, 2080, 40):
                 a = rng.standard_normal((m, k))
                 b = rng.standard_normal((k, n))
                 ref = a @ b
+                # the ring kernel takes whole 16-deep K tiles; shallow products over a wide N get 128-column tiles instead
+                ring = k % 16 == 0 and not (k <= 160 and n >= 2048)
                 # sketch layout: A stored (k x m) with even leading dimension (M-contiguous), B stored (n x k) (K-contiguous)
                 ta = torch.zeros((k, m + (m & 1)), dtype=torch.float64, device="cuda")[:, :m]
                 ta.copy_(torch.from_numpy(np.ascontiguousarray(a.T)))
                 tb = torch.from_numpy(np.ascontiguousarray(b.T)).cuda()
                 assert rel(npy(rc.dot(ta.t(), tb.t())), ref) <= 1e-13, ("sketch layout", m, n, k)
+                got = last_gemm_kernel()
+                if ring and m > 128 and n % 256 == 0:
+                    assert got == sketch_ring, ("sketch layout", m, n, k, got)
+                else:
+                    assert got.startswith(("k_gemm_f64p<", "k_gemm_f64q<")), ("sketch layout", m, n, k, got)
                 # projection layout: A M-contiguous as above, B stored (k x n) (N-contiguous)
                 tb2 = torch.from_numpy(b).cuda()
                 assert rel(npy(rc.dot(ta.t(), tb2)), ref) <= 1e-13, ("projection layout", m, n, k)
+                got = last_gemm_kernel()
+                if ring and m <= 128:
+                    assert got == projection_ring, ("projection layout", m, n, k, got)
+                else:
+                    assert got.startswith(("k_gemm_f64p<", "k_gemm_f64q<")), ("projection layout", m, n, k, got)
 
 
 def test_gemm_is_deterministic_under_split_k():

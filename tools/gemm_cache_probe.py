@@ -21,6 +21,6 @@ for m in (1024, 2048, 4096, 8192, 16384):
         nm = name.value.decode(); avg = ms.value / max(calls.value, 1)
         if "k_gemm_mfma" in nm:
             fl = 2.0 * m * l * n
-            print(f"m={m:6d} A={m*n*8/2**20:7.0f} MiB  {avg*1e3:8.1f} us  {fl/avg/1e9:6.2f} TF/s  A-stream {m*n*8/avg/1e6:8.1f} GB/s  [{os.environ.get('RC_GEMM_F64X4','1')}]")
+            print(f"m={m:6d} A={m*n*8/2**20:7.0f} MiB  {avg*1e3:8.1f} us  {fl/avg/1e9:6.2f} TF/s  A-stream {m*n*8/avg/1e6:8.1f} GB/s")
     lib.rc_profile_enable(ctx._h, 0)
     del a

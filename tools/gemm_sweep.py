@@ -1,6 +1,6 @@
 """Developer tool: time the two headline GEMM shapes through rc_gemm with the kernel-level
-HIP-event timers.  Tile variants are selected with RC_GEMM_SKINNY_N / RC_GEMM_SKINNY_M /
-RC_GEMM_TARGET_WGS / RC_GEMM_VEC (read once per process)."""
+HIP-event timers.  The split-K targets can be varied with RC_GEMM_TARGET_WGS / RC_GEMM_SMALL_TARGET /
+RC_GEMM_SLOTS_TARGET / RC_GEMM_LANES_TARGET (read once per process)."""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
