@@ -94,7 +94,7 @@ using c32 = std::complex<float>;
 using c64 = std::complex<double>;
 
 template <typename T> struct Api;
-#define RC_API(T, SUF, RSUF)                                                                                            \
+#define RC_API(T, SUF, RSUF, EXTRA)                                                                                          \
     template <> struct Api<T> {                                                                                     \
         static constexpr auto random_gaussian = rc_random_gaussian_##SUF;                                           \
         static constexpr auto matmat = rc_matmat_##SUF;                                                             \
@@ -125,11 +125,15 @@ template <typename T> struct Api;
         static constexpr auto sample_range_power_iteration = rc_sample_range_power_iteration_##SUF;                 \
         static constexpr auto sample_range_adaptive = rc_sample_range_adaptive_##SUF;                               \
         static constexpr auto column_id_rank = rc_column_id_rank_##SUF;                                             \
+        EXTRA                                                                                                       \
     };
-RC_API(double, f64, f64)
-RC_API(float, f32, f32)
-RC_API(c64, c64, f64)
-RC_API(c32, c32, f32)
+// the batched small-matrix column ID exists for real scalars only
+#define RC_API_REAL(SUF) static constexpr auto column_id_rank_batched = rc_column_id_rank_batched_##SUF;
+RC_API(double, f64, f64, RC_API_REAL(f64))
+RC_API(float, f32, f32, RC_API_REAL(f32))
+RC_API(c64, c64, f64, )
+RC_API(c32, c32, f32, )
+#undef RC_API_REAL
 #undef RC_API
 
 // ---- device-resident C-order arrays (the reference's Array2 / Array1<usize>) ----------------------
@@ -525,6 +529,24 @@ ColumnID<T> column_id_rank(const DeviceMatrix<T> &a, int64_t k) {
     const int64_t kk = k < a.nrows() ? (k < a.ncols() ? k : a.ncols()) : (a.nrows() < a.ncols() ? a.nrows() : a.ncols());
     ColumnID<T> out{DeviceMatrix<T>(a.ctx(), a.nrows(), kk), DeviceMatrix<T>(a.ctx(), kk, a.ncols()), DeviceIndex(a.ctx(), (std::size_t)a.ncols())};
     a.ctx().check(Api<T>::column_id_rank(a.ctx().raw(), a.view(), kk, out.c.view(), out.z.view(), out.col_ind.data()));
+    return out;
+}
+// the same unit for `count` small m x n matrices stacked in `a` (count * m rows, n columns) in one stream-ordered call, the rank of
+// each chosen by tol (0: fixed rank k; rc_column_id_rank_batched_*): c is count * m x k, z count * k x n, col_ind count x n
+template <typename T>
+struct BatchedColumnID {
+    DeviceMatrix<T> c, z;
+    DeviceIndex col_ind, ranks;
+};
+template <typename T>
+BatchedColumnID<T> column_id_rank_batched(const DeviceMatrix<T> &a, int32_t count, int64_t k, double tol = 0.0) {
+    const int64_t m = count > 0 ? a.nrows() / count : 0, n = a.ncols();
+    const int64_t kk = k < m ? (k < n ? k : n) : (m < n ? m : n);
+    BatchedColumnID<T> out{DeviceMatrix<T>(a.ctx(), (int64_t)count * m, kk), DeviceMatrix<T>(a.ctx(), (int64_t)count * kk, n),
+                           DeviceIndex(a.ctx(), (std::size_t)count * (std::size_t)n), DeviceIndex(a.ctx(), (std::size_t)count)};
+    a.ctx().check(Api<T>::column_id_rank_batched(a.ctx().raw(), rc_matrix{a.view().data, m, n, n, 1}, m * n, count, k, tol,
+                                                 rc_matrix{out.c.view().data, m, kk, kk, 1}, m * kk, rc_matrix{out.z.view().data, kk, n, n, 1},
+                                                 kk * n, out.col_ind.data(), out.ranks.data()));
     return out;
 }
 template <typename T>

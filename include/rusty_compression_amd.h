@@ -441,6 +441,20 @@ rc_status rc_batch_shard_range(int64_t n_items, int32_t world, int32_t rank, int
  * rc_column_id_rank_*.  Blocking: returns when every factor is in `packed`.  Errors are reported on ctxs[0]. */
 rc_status rc_batch_column_id_f64(rc_context *const *ctxs, int32_t nctx, const rc_matrix *mats, int32_t count, int64_t k, void *packed);
 rc_status rc_batch_column_id_f32(rc_context *const *ctxs, int32_t nctx, const rc_matrix *mats, int32_t count, int64_t k, void *packed);
+/* Many SMALL same-shaped matrices (blocks of a hierarchical matrix / FMM operator) in one stream-ordered call: no host
+ * synchronisation inside, capturable between rc_graph_begin_capture and rc_graph_end_capture.  Matrix i is the view `a` with its
+ * data moved by i * a_batch_stride elements (0 is legal); c (m x k) and z (k x n) likewise with their own batch strides;
+ * col_ind (count x n) and ranks (count) are contiguous; every pointer is a device pointer.  Per matrix the sequence of
+ * rc_column_id_rank_*: truncated pivoted QR with ?geqp3's pivots, k clamped to min(m, n), rank r = the first j < k with
+ * R_jj == 0 or (tol > 0 and |R_jj / R_00| < tol) (src/qr.rs:187-200 as a ratio), else k -- so tol = 0 is fixed rank k, a
+ * matrix of lower exact rank stops at it, an all-zero matrix has rank 0, and where the reference could not compress the rank is k
+ * (no per-matrix error).  ranks[i] = r; col_ind[i, :] is the full permutation (pivots first); C[:, j] = A[:, ind[j]] bit for bit
+ * and Z = [I | R11^-1 R12] P^T for j < r; columns r..k-1 of C and rows r..k-1 of Z are zero.  Matrix i's bits depend on matrix
+ * i alone.  Non-finite input stays inside its matrix's outputs (values unspecified, col_ind still a permutation, 0 <= r <= k).
+ * Domain: 1 <= m, n <= 512, 1 <= k <= 128, 0 <= tol < 1, count >= 0 (0: nothing to do); RC_INVALID_ARGUMENT otherwise, for
+ * wrong c / z shapes, and for an output batch stride smaller than one output view's span.  Workspace: bounded, not by count. */
+rc_status rc_column_id_rank_batched_f64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks);
+rc_status rc_column_id_rank_batched_f32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks);
 
 /* The gather over RCCL (xGMI inside a node).  One process per GPU: rank 0 calls rc_comm_unique_id and hands the 128
  * bytes to the other ranks by whatever means the host has (MPI, a file, torch.distributed), every rank calls

@@ -44,6 +44,32 @@ def column_id_rank(a: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor,
     return c, z, ind
 
 
+def column_id_rank_batched(a: torch.Tensor, k: int, tol: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Column IDs of `count` small same-shaped matrices in one stream-ordered call (rc_column_id_rank_batched_*).
+
+    a: [count, m, n] device tensor, any strides (1 <= m, n <= 512).  k (<= 128) is clamped to min(m, n); the rank of each matrix is
+    the first j < k with R_jj == 0 or |R_jj / R_00| < tol (tol = 0: fixed rank k).  Returns C [count, m, k], Z [count, k, n],
+    ind [count, n] (full permutations, pivots first) and ranks [count]; columns / rows of C / Z past a matrix's rank are zero."""
+    from . import _lib
+    from .types import as_device
+
+    a = as_device(a)
+    if a.dim() != 3:
+        raise AssertionError("expected a [count, m, n] batch")
+    count, m, n = a.shape
+    kk = min(int(k), m, n)
+    c = torch.empty((count, m, kk), dtype=a.dtype, device=a.device)
+    z = torch.empty((count, kk, n), dtype=a.dtype, device=a.device)
+    ind = torch.empty((count, n), dtype=torch.int64, device=a.device)
+    ranks = torch.empty(count, dtype=torch.int64, device=a.device)
+    view = _lib.rc_matrix(a.data_ptr(), m, n, a.stride(1), a.stride(2))
+    _lib.default_context().call(f"rc_column_id_rank_batched_{_lib.suffix(a.dtype)}", view, ctypes.c_int64(a.stride(0)), ctypes.c_int32(count),
+                                ctypes.c_int64(int(k)), ctypes.c_double(float(tol)), _lib.mat(c[0] if count else c.new_empty(m, kk)),
+                                ctypes.c_int64(m * kk), _lib.mat(z[0] if count else z.new_empty(kk, n)), ctypes.c_int64(kk * n),
+                                _lib.i64p(ind), _lib.i64p(ranks))
+    return c, z, ind, ranks
+
+
 def packed_bytes(m: int, n: int, k: int, elem_size: int) -> int:
     """Bytes one matrix's factors take in the packed buffer: C (m x k) | Z (k x n) | pad to 8 | col_ind (n int64)
     (rc_batch_packed_bytes)."""

@@ -98,4 +98,25 @@ __device__ inline double fast_rsqrt(double x) {
 }
 __device__ inline float fast_rsqrt(float x) { return 1.0f / sqrtf(x); }
 
+// ---- ?laqp2 partial-norm down-date ---------------------------------------------------
+// tol3z = sqrt(eps): below it the down-dated norm has lost its digits and is recomputed from the column.  The same constants and
+// the same formula as the down-date of the per-step chain (kernels_qr.hip, k_qr_apply), which keeps its own copy so that its
+// instantiations stay as they were.
+template <typename T> __host__ __device__ constexpr T laqp2_tol3z();
+template <> __host__ __device__ constexpr double laqp2_tol3z<double>() { return 1.0536712127723509e-08; }  // sqrt(2^-53)
+template <> __host__ __device__ constexpr float laqp2_tol3z<float>() { return 2.44140625e-04f; }          // sqrt(2^-24)
+// vn: partial norm of the column before the step (vn1), vn_ref: its norm at the last recompute (vn2), xj: its new row-j entry.
+// Returns true when the norm must be recomputed from rows j+1.. of the updated column; otherwise *vn_new is the down-dated norm.
+template <typename T>
+__device__ inline bool laqp2_downdate(T vn, T vn_ref, T xj, T *vn_new) {
+    T t = fabs(xj) / vn;
+    T temp = (T)1 - t * t;
+    temp = temp > (T)0 ? temp : (T)0;
+    T r = vn / vn_ref;
+    T temp2 = temp * r * r;
+    if (temp2 <= laqp2_tol3z<T>()) return true;
+    *vn_new = vn * sqrt(temp);
+    return false;
+}
+
 }  // namespace rc

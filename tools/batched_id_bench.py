@@ -1,0 +1,112 @@
+#!/usr/bin/env python3
+"""Throughput of the batched small-matrix column ID (rc_column_id_rank_batched_*) against a loop of rc_column_id_rank_* calls.
+
+For each shape: one batched call timed with device events after warm-up (median of --repeats), the same matrices through a
+loop of lone calls on the same stream (the first --loop-count of them: the loop is host-bound and slow, so a subset is timed
+and scaled per matrix), a check that both take the same pivots on the agreed prefix, and the algorithmic bytes (A read once;
+C, Z, col_ind written) over the batched time as a share of HBM bandwidth.  Not used by the tests or by bench.py.
+
+    python tools/batched_id_bench.py [--repeats 5] [--loop-count 64] [--shapes 0,1,2] [--out path.json]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import rusty_compression_amd as rc  # noqa: E402
+from rusty_compression_amd.batch import column_id_rank  # noqa: E402
+from tests.helpers import agreed_pivot_prefix  # noqa: E402
+
+HBM_BYTES_PER_S = 8.0e12  # MI355X HBM3E peak (spec); measured copy ceiling 6.29 TB/s
+SHAPES = [  # (count, m, n, k, tol, dtype)
+    (2048, 512, 256, 32, 0.0, torch.float64),
+    (8192, 256, 256, 32, 0.0, torch.float32),
+    (16384, 128, 128, 64, 1e-8, torch.float64),
+]
+
+
+def timed(fn, repeats):
+    ts = []
+    for _ in range(repeats):
+        b, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        b.record()
+        fn()
+        e.record()
+        e.synchronize()
+        ts.append(b.elapsed_time(e) * 1e-3)
+    return float(np.median(ts)), float(min(ts)), float(max(ts))
+
+
+def decaying_batch(count, m, n, dtype, seed):
+    """A = U diag(logspace(0, -10)) V^T per matrix with Gaussian U, V scaled to unit expected column norms (a decaying spectrum,
+    generated on the device without a batched QR)."""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    r = min(m, n)
+    u = torch.randn(count, m, r, generator=g, device="cuda", dtype=torch.float64) / m ** 0.5
+    v = torch.randn(count, n, r, generator=g, device="cuda", dtype=torch.float64) / n ** 0.5
+    s = torch.logspace(0, -10, r, device="cuda", dtype=torch.float64)
+    return ((u * s) @ v.transpose(1, 2)).to(dtype).contiguous()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--loop-count", type=int, default=64)
+    ap.add_argument("--shapes", default="0,1,2")
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("batched_id_bench: no GPU visible (this tool only measures on the device)")
+    torch.cuda.set_device(0)
+    results = []
+    for si in [int(x) for x in args.shapes.split(",")]:
+        count, m, n, k, tol, dtype = SHAPES[si]
+        a = decaying_batch(count, m, n, dtype, 1234 + si)
+        es = a.element_size()
+        c, z, ind, ranks = rc.column_id_rank_batched(a, k, tol)  # warm-up (code objects, workspace)
+        torch.cuda.synchronize()
+        t_med, t_min, t_max = timed(lambda: rc.column_id_rank_batched(a, k, tol), args.repeats)
+        nl = min(args.loop_count, count)
+        kk = min(k, m, n)
+        column_id_rank(a[0], kk)  # warm-up of the lone path
+
+        def loop():
+            for i in range(nl):
+                column_id_rank(a[i], kk)
+
+        l_med, l_min, l_max = timed(loop, max(1, args.repeats // 2))
+        # pivots: the lone call runs at fixed rank k; compare on the prefix both determine
+        agree = []
+        ind_h, ranks_h = ind.cpu().numpy(), ranks.cpu().numpy()
+        for i in range(min(nl, 8)):
+            _, _, lind = column_id_rank(a[i], kk)
+            an = a[i].double().cpu().numpy()
+            r = int(ranks_h[i])
+            mine = np.linalg.qr(an[:, ind_h[i]], mode="r")[:r]
+            ref = np.linalg.qr(an[:, lind.cpu().numpy()], mode="r")[:r]
+            agree.append(int(agreed_pivot_prefix(ind_h[i], mine, lind.cpu().numpy(), ref, np.dtype(np.float64 if dtype == torch.float64 else np.float32))))
+        bytes_alg = count * ((m * n + m * kk + kk * n) * es + n * 8 + 8)
+        row = dict(count=count, m=m, n=n, k=k, tol=tol, dtype=str(dtype).replace("torch.", ""),
+                   batched_s=t_med, batched_s_min=t_min, batched_s_max=t_max, batched_matrices_per_s=count / t_med,
+                   loop_matrices=nl, loop_s=l_med, loop_matrices_per_s=nl / l_med, speedup=(count / t_med) / (nl / l_med),
+                   ranks_min=int(ranks_h.min()), ranks_max=int(ranks_h.max()), pivots_agreed_prefix=agree,
+                   algorithmic_bytes=bytes_alg, hbm_share=bytes_alg / t_med / HBM_BYTES_PER_S,
+                   bound="not HBM: %.1f %% of the 8 TB/s peak; the k serial Householder steps of each matrix inside its workgroup"
+                   % (100 * bytes_alg / t_med / HBM_BYTES_PER_S))
+        results.append(row)
+        print(json.dumps(row), flush=True)
+        del a, c, z, ind, ranks
+        torch.cuda.empty_cache()
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(results, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
