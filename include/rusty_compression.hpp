@@ -128,7 +128,9 @@ template <typename T> struct Api;
         EXTRA                                                                                                       \
     };
 // the batched small-matrix column ID exists for real scalars only
-#define RC_API_REAL(SUF) static constexpr auto column_id_rank_batched = rc_column_id_rank_batched_##SUF;
+#define RC_API_REAL(SUF)                                                                                            \
+    static constexpr auto column_id_rank_batched = rc_column_id_rank_batched_##SUF;                                 \
+    static constexpr auto two_sided_id_rank_batched = rc_two_sided_id_rank_batched_##SUF;
 RC_API(double, f64, f64, RC_API_REAL(f64))
 RC_API(float, f32, f32, RC_API_REAL(f32))
 RC_API(c64, c64, f64, )
@@ -547,6 +549,26 @@ BatchedColumnID<T> column_id_rank_batched(const DeviceMatrix<T> &a, int32_t coun
     a.ctx().check(Api<T>::column_id_rank_batched(a.ctx().raw(), rc_matrix{a.view().data, m, n, n, 1}, m * n, count, k, tol,
                                                  rc_matrix{out.c.view().data, m, kk, kk, 1}, m * kk, rc_matrix{out.z.view().data, kk, n, n, 1},
                                                  kk * n, out.col_ind.data(), out.ranks.data()));
+    return out;
+}
+// the two-sided ID A ~ C X R of the same batch in one call (rc_two_sided_id_rank_batched_*): c is count * m x k, x count * k x k,
+// r count * k x n, row_ind count x m, col_ind count x n; r and col_ind are column_id_rank_batched's z and col_ind bit for bit
+template <typename T>
+struct BatchedTwoSidedID {
+    DeviceMatrix<T> c, x, r;
+    DeviceIndex row_ind, col_ind, ranks;
+};
+template <typename T>
+BatchedTwoSidedID<T> two_sided_id_rank_batched(const DeviceMatrix<T> &a, int32_t count, int64_t k, double tol = 0.0) {
+    const int64_t m = count > 0 ? a.nrows() / count : 0, n = a.ncols();
+    const int64_t kk = k < m ? (k < n ? k : n) : (m < n ? m : n);
+    BatchedTwoSidedID<T> out{DeviceMatrix<T>(a.ctx(), (int64_t)count * m, kk), DeviceMatrix<T>(a.ctx(), (int64_t)count * kk, kk),
+                             DeviceMatrix<T>(a.ctx(), (int64_t)count * kk, n), DeviceIndex(a.ctx(), (std::size_t)count * (std::size_t)m),
+                             DeviceIndex(a.ctx(), (std::size_t)count * (std::size_t)n), DeviceIndex(a.ctx(), (std::size_t)count)};
+    a.ctx().check(Api<T>::two_sided_id_rank_batched(a.ctx().raw(), rc_matrix{a.view().data, m, n, n, 1}, m * n, count, k, tol,
+                                                    rc_matrix{out.c.view().data, m, kk, kk, 1}, m * kk, rc_matrix{out.x.view().data, kk, kk, kk, 1},
+                                                    kk * kk, rc_matrix{out.r.view().data, kk, n, n, 1}, kk * n, out.row_ind.data(),
+                                                    out.col_ind.data(), out.ranks.data()));
     return out;
 }
 template <typename T>

@@ -455,6 +455,23 @@ rc_status rc_batch_column_id_f32(rc_context *const *ctxs, int32_t nctx, const rc
  * wrong c / z shapes, and for an output batch stride smaller than one output view's span.  Workspace: bounded, not by count. */
 rc_status rc_column_id_rank_batched_f64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks);
 rc_status rc_column_id_rank_batched_f32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks);
+/* The two-sided ID A ~ C X R of the same batch (ColumnIDTraits::two_sided_id after the column ID, src/col_interp_decomp.rs:116-125)
+ * in the same one stream-ordered, capturable call.  Domain, batch layout and checks as rc_column_id_rank_batched_*: k clamped to
+ * min(m, n); c (m x k), x (k x k) and r (k x n) each moved by its own batch stride; row_ind (count x m), col_ind (count x n) and
+ * ranks (count) contiguous; every pointer a device pointer.  Column side: bit for bit rc_column_id_rank_batched_* on the same
+ * input -- ranks[i] = r, col_ind[i, :] the full permutation, r = its Z ([I | R11^-1 R12] P^T on rows < r, rows r..k-1 zero).  Row
+ * side: ?geqp3 pivoting of C^T, C = A[:, col_ind[:r]] read bit for bit from a, with tol = 0 and at most r steps; row_ind[i, :] is
+ * the full row permutation (pivots first), c[:, :r] = Z2^T with Z2 = [I | R11^-1 R12] P2^T the Z of C^T (so c[row_ind[:r], :r] is
+ * exactly the identity), x[:r, :r] = A[row_ind[:r], col_ind[:r]] bit for bit; columns r..k-1 of c and rows and columns r..k-1 of x
+ * are zero.  The row side stops early only on an exactly zero pivot; the columns of c from that step on are then zero (ranks[i]
+ * still r).  r = 0: row_ind[i, :] is the identity and c, x, r are zero.  Per matrix this is rc_column_id_rank_* at rank r followed
+ * by rc_column_id_two_sided_*, except that pivots may differ where the two reduction orders split a near-tie and that X is
+ * gathered from A rather than re-formed as L Q; c x r reconstructs A (the reference TwoSidedID's c, x, r, row_ind, col_ind).
+ * Matrix i's bits depend on matrix i alone.  Non-finite input stays inside its matrix's outputs (values unspecified, row_ind and
+ * col_ind still permutations, 0 <= r <= k).  RC_INVALID_ARGUMENT for an out-of-domain argument, wrong c / x / r shapes, an output
+ * batch stride smaller than one output view's span, or a null pointer.  Workspace: bounded, not by count. */
+rc_status rc_two_sided_id_rank_batched_f64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix c, int64_t c_batch_stride, rc_matrix x, int64_t x_batch_stride, rc_matrix r, int64_t r_batch_stride, int64_t *row_ind, int64_t *col_ind, int64_t *ranks);
+rc_status rc_two_sided_id_rank_batched_f32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix c, int64_t c_batch_stride, rc_matrix x, int64_t x_batch_stride, rc_matrix r, int64_t r_batch_stride, int64_t *row_ind, int64_t *col_ind, int64_t *ranks);
 
 /* The gather over RCCL (xGMI inside a node).  One process per GPU: rank 0 calls rc_comm_unique_id and hands the 128
  * bytes to the other ranks by whatever means the host has (MPI, a file, torch.distributed), every rank calls

@@ -70,6 +70,38 @@ def column_id_rank_batched(a: torch.Tensor, k: int, tol: float = 0.0) -> Tuple[t
     return c, z, ind, ranks
 
 
+def two_sided_id_rank_batched(a: torch.Tensor, k: int, tol: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor,
+                                                                                torch.Tensor]:
+    """Two-sided IDs A ~ C X R of `count` small same-shaped matrices in one stream-ordered call (rc_two_sided_id_rank_batched_*).
+
+    a: [count, m, n] device tensor, any strides (1 <= m, n <= 512).  k (<= 128) is clamped to min(m, n); the rank r of each matrix is
+    that of column_id_rank_batched (R_jj == 0 or |R_jj / R_00| < tol; tol = 0: fixed rank k), whose Z and ind are R and col_ind here
+    bit for bit.  The row side is the row ID of A[:, col_ind[:r]] (ColumnID::two_sided_id).  Returns C [count, m, k], X [count, k, k],
+    R [count, k, n], row_ind [count, m], col_ind [count, n] (full permutations, pivots first) and ranks [count];
+    X[:r, :r] = A[row_ind[:r]][:, col_ind[:r]], and the columns of C, rows of R and rows and columns of X past a matrix's rank are zero."""
+    from . import _lib
+    from .types import as_device
+
+    a = as_device(a)
+    if a.dim() != 3:
+        raise AssertionError("expected a [count, m, n] batch")
+    count, m, n = a.shape
+    kk = min(int(k), m, n)
+    c = torch.empty((count, m, kk), dtype=a.dtype, device=a.device)
+    x = torch.empty((count, kk, kk), dtype=a.dtype, device=a.device)
+    r = torch.empty((count, kk, n), dtype=a.dtype, device=a.device)
+    row_ind = torch.empty((count, m), dtype=torch.int64, device=a.device)
+    col_ind = torch.empty((count, n), dtype=torch.int64, device=a.device)
+    ranks = torch.empty(count, dtype=torch.int64, device=a.device)
+    view = _lib.rc_matrix(a.data_ptr(), m, n, a.stride(1), a.stride(2))
+    _lib.default_context().call(f"rc_two_sided_id_rank_batched_{_lib.suffix(a.dtype)}", view, ctypes.c_int64(a.stride(0)), ctypes.c_int32(count),
+                                ctypes.c_int64(int(k)), ctypes.c_double(float(tol)), _lib.mat(c[0] if count else c.new_empty(m, kk)),
+                                ctypes.c_int64(m * kk), _lib.mat(x[0] if count else x.new_empty(kk, kk)), ctypes.c_int64(kk * kk),
+                                _lib.mat(r[0] if count else r.new_empty(kk, n)), ctypes.c_int64(kk * n), _lib.i64p(row_ind), _lib.i64p(col_ind),
+                                _lib.i64p(ranks))
+    return c, x, r, row_ind, col_ind, ranks
+
+
 def packed_bytes(m: int, n: int, k: int, elem_size: int) -> int:
     """Bytes one matrix's factors take in the packed buffer: C (m x k) | Z (k x n) | pad to 8 | col_ind (n int64)
     (rc_batch_packed_bytes)."""

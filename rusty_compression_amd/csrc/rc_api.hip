@@ -984,31 +984,57 @@ void column_id_rank(rc_context *c, Mat<T> a, int64_t k, Mat<T> cm, Mat<T> z, int
     qr_column_id(c, q, r, col_ind, cm, z);
 }
 
+// the domain of the batched small-matrix kernels (kernels_batched_id.hip); returns k clamped to min(m, n)
+template <typename T>
+int64_t batched_domain(const char *who, const char *larger, const Mat<T> &a, int32_t count, int64_t k, double tol) {
+    const int64_t m = a.rows, n = a.cols;
+    RC_REQUIRE(count >= 0, RC_INVALID_ARGUMENT, "%s: count = %d < 0", who, (int)count);
+    RC_REQUIRE(m >= 1 && m <= 512 && n >= 1 && n <= 512 && k >= 1 && k <= 128, RC_INVALID_ARGUMENT,
+               "%s: needs 1 <= m, n <= 512 and 1 <= k <= 128 (got %lld x %lld, k = %lld); use %s for larger matrices", who, (long long)m, (long long)n,
+               (long long)k, larger);
+    RC_REQUIRE(tol < 1.0 && 0.0 <= tol, RC_INVALID_ARGUMENT, "Require 0 <= tol < 1.0");
+    return std::min(k, std::min(m, n));
+}
+// one output view spans (rows - 1) |rs| + (cols - 1) |cs| + 1 elements; a smaller batch stride would overlap two matrices
+template <typename T>
+void check_batch_stride(const char *who, const char *name, int64_t bs, const Mat<T> &v, int32_t count) {
+    const int64_t span = (v.rows - 1) * std::abs(v.rs) + (v.cols - 1) * std::abs(v.cs) + 1;
+    RC_REQUIRE(count <= 1 || bs >= span, RC_INVALID_ARGUMENT, "%s: %s_batch_stride %lld < %lld overlaps the outputs of two matrices", who, name,
+               (long long)bs, (long long)span);
+}
+
 // the same unit of work for many small same-shaped matrices in one launch, rank chosen per matrix by tol (0: fixed rank k)
 // without a host round trip; one path, stream-ordered, capturable
 template <typename T>
 void column_id_rank_batched(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int64_t k, double tol, Mat<T> cm, int64_t cbs, Mat<T> z, int64_t zbs,
                             int64_t *col_ind, int64_t *ranks) {
     const int64_t m = a.rows, n = a.cols;
-    RC_REQUIRE(count >= 0, RC_INVALID_ARGUMENT, "column_id_rank_batched: count = %d < 0", (int)count);
-    RC_REQUIRE(m >= 1 && m <= 512 && n >= 1 && n <= 512 && k >= 1 && k <= 128, RC_INVALID_ARGUMENT,
-               "column_id_rank_batched: needs 1 <= m, n <= 512 and 1 <= k <= 128 (got %lld x %lld, k = %lld); use rc_column_id_rank_* / "
-               "rc_batch_column_id_* for larger matrices", (long long)m, (long long)n, (long long)k);
-    RC_REQUIRE(tol < 1.0 && 0.0 <= tol, RC_INVALID_ARGUMENT, "Require 0 <= tol < 1.0");
-    k = std::min(k, std::min(m, n));
+    k = batched_domain("column_id_rank_batched", "rc_column_id_rank_* / rc_batch_column_id_*", a, count, k, tol);
     RC_REQUIRE(cm.rows == m && cm.cols == k && z.rows == k && z.cols == n, RC_INVALID_ARGUMENT,
                "column_id_rank_batched: c must be %lld x %lld and z %lld x %lld (k clamped to min(m, n))", (long long)m, (long long)k, (long long)k, (long long)n);
-    // one output view spans (rows - 1) |rs| + (cols - 1) |cs| + 1 elements; a smaller batch stride would overlap two matrices
-    auto span = [](const Mat<T> &v) { return (v.rows - 1) * std::abs(v.rs) + (v.cols - 1) * std::abs(v.cs) + 1; };
-    if (count > 1) {
-        RC_REQUIRE(cbs >= span(cm), RC_INVALID_ARGUMENT, "column_id_rank_batched: c_batch_stride %lld < %lld overlaps the outputs of two matrices",
-                   (long long)cbs, (long long)span(cm));
-        RC_REQUIRE(zbs >= span(z), RC_INVALID_ARGUMENT, "column_id_rank_batched: z_batch_stride %lld < %lld overlaps the outputs of two matrices",
-                   (long long)zbs, (long long)span(z));
-    }
+    check_batch_stride("column_id_rank_batched", "c", cbs, cm, count);
+    check_batch_stride("column_id_rank_batched", "z", zbs, z, count);
     if (count == 0) return;
     RC_REQUIRE(a.p && cm.p && z.p && col_ind && ranks, RC_INVALID_ARGUMENT, "column_id_rank_batched: null pointer");
     batched_column_id(c, a, abs, count, k, tol, cm, cbs, z, zbs, col_ind, ranks);
+}
+
+// the two-sided ID A ~ C X R of the same batch (ColumnID::two_sided_id after the column ID), in the same one launch
+template <typename T>
+void two_sided_id_rank_batched(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int64_t k, double tol, Mat<T> cm, int64_t cbs, Mat<T> x, int64_t xbs,
+                               Mat<T> r, int64_t rbs, int64_t *row_ind, int64_t *col_ind, int64_t *ranks) {
+    const int64_t m = a.rows, n = a.cols;
+    const char *who = "two_sided_id_rank_batched";
+    k = batched_domain(who, "rc_column_id_rank_* + rc_column_id_two_sided_*", a, count, k, tol);
+    RC_REQUIRE(cm.rows == m && cm.cols == k && x.rows == k && x.cols == k && r.rows == k && r.cols == n, RC_INVALID_ARGUMENT,
+               "two_sided_id_rank_batched: c must be %lld x %lld, x %lld x %lld and r %lld x %lld (k clamped to min(m, n))", (long long)m, (long long)k,
+               (long long)k, (long long)k, (long long)k, (long long)n);
+    check_batch_stride(who, "c", cbs, cm, count);
+    check_batch_stride(who, "x", xbs, x, count);
+    check_batch_stride(who, "r", rbs, r, count);
+    if (count == 0) return;
+    RC_REQUIRE(a.p && cm.p && x.p && r.p && row_ind && col_ind && ranks, RC_INVALID_ARGUMENT, "two_sided_id_rank_batched: null pointer");
+    batched_two_sided_id(c, a, abs, count, k, tol, cm, cbs, x, xbs, r, rbs, row_ind, col_ind, ranks);
 }
 
 template <typename T>
@@ -1542,6 +1568,14 @@ rc_status rc_invert_permutation(rc_context *ctx, const int64_t *perm, int64_t n,
         return guarded(ctx, [&] {                                                                                                        \
             column_id_rank_batched<T>(ctx, from_c<T>(a), a_batch_stride, count, k, tol, from_c<T>(c), c_batch_stride, from_c<T>(z),       \
                                       z_batch_stride, col_ind, ranks);                                                                   \
+        });                                                                                                                              \
+    }                                                                                                                                    \
+    rc_status rc_two_sided_id_rank_batched_##SUF(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, \
+                                                 rc_matrix c, int64_t c_batch_stride, rc_matrix x, int64_t x_batch_stride, rc_matrix r,     \
+                                                 int64_t r_batch_stride, int64_t *row_ind, int64_t *col_ind, int64_t *ranks) {              \
+        return guarded(ctx, [&] {                                                                                                        \
+            two_sided_id_rank_batched<T>(ctx, from_c<T>(a), a_batch_stride, count, k, tol, from_c<T>(c), c_batch_stride, from_c<T>(x),    \
+                                         x_batch_stride, from_c<T>(r), r_batch_stride, row_ind, col_ind, ranks);                         \
         });                                                                                                                              \
     }
 

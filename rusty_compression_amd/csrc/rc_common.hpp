@@ -207,6 +207,10 @@ template <typename T> void id_z_from_r(rc_context *c, Mat<T> r, int64_t k, const
 // i * abs, i * cbs, i * zbs elements; col_ind count x n, ranks count (arguments checked by the caller)
 template <typename T> void batched_column_id(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int64_t k, double tol, Mat<T> cm, int64_t cbs, Mat<T> z,
                                              int64_t zbs, int64_t *col_ind, int64_t *ranks);
+// the two-sided ID of the same batch (kernels_batched_id.hip): matrix i is a, cm (m x k), x (k x k), z (k x n) moved by i * abs, i * cbs,
+// i * xbs, i * zbs elements; row_ind count x m, col_ind count x n, ranks count (arguments checked by the caller)
+template <typename T> void batched_two_sided_id(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int64_t k, double tol, Mat<T> cm, int64_t cbs, Mat<T> x,
+                                                int64_t xbs, Mat<T> z, int64_t zbs, int64_t *row_ind, int64_t *col_ind, int64_t *ranks);
 void invert_perm(rc_context *c, const int64_t *perm, int64_t n, int64_t *inv);
 void fill_words(rc_context *c, void *p, size_t bytes, unsigned v);  // every 32-bit word of [p, p + bytes) = v, by a kernel on c->stream (no hipMemset*)
 void iota_i64(rc_context *c, int64_t *p, int64_t n);

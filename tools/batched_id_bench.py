@@ -6,7 +6,11 @@ loop of lone calls on the same stream (the first --loop-count of them: the loop 
 and scaled per matrix), a check that both take the same pivots on the agreed prefix, and the algorithmic bytes (A read once;
 C, Z, col_ind written) over the batched time as a share of HBM bandwidth.  Not used by the tests or by bench.py.
 
-    python tools/batched_id_bench.py [--repeats 5] [--loop-count 64] [--shapes 0,1,2] [--out path.json]
+--two-sided times, on the same shapes and matrices, the batched column ID, the batched two-sided ID
+(rc_two_sided_id_rank_batched_*) and a loop of lone rc_column_id_rank_* + rc_column_id_two_sided_* calls on a subset, and writes
+profiles/batched_two_sided_bench.json unless --out names another file.
+
+    python tools/batched_id_bench.py [--two-sided] [--repeats 5] [--loop-count 64] [--shapes 0,1,2] [--out path.json]
 """
 import argparse
 import json
@@ -54,16 +58,67 @@ def decaying_batch(count, m, n, dtype, seed):
     return ((u * s) @ v.transpose(1, 2)).to(dtype).contiguous()
 
 
+def two_sided_rows(args):
+    """Batched column ID, batched two-sided ID and the loop of lone column ID + two-sided calls, per shape."""
+    results = []
+    for si in [int(x) for x in args.shapes.split(",")]:
+        count, m, n, k, tol, dtype = SHAPES[si]
+        a = decaying_batch(count, m, n, dtype, 1234 + si)
+        kk = min(k, m, n)
+        rc.column_id_rank_batched(a, k, tol)  # warm-up (code objects, workspace)
+        c, x, r, row_ind, col_ind, ranks = rc.two_sided_id_rank_batched(a, k, tol)
+        torch.cuda.synchronize()
+        b_med, b_min, b_max = timed(lambda: rc.column_id_rank_batched(a, k, tol), args.repeats)
+        t_med, t_min, t_max = timed(lambda: rc.two_sided_id_rank_batched(a, k, tol), args.repeats)
+        nl = min(args.loop_count, count)
+        ranks_h = ranks.cpu().numpy()
+
+        def loop():  # the lone chain at each matrix's own rank, as a user of the lone calls would run it
+            for i in range(nl):
+                ci, zi, ind = column_id_rank(a[i], int(ranks_h[i]) or 1)
+                rc.ColumnID(ci, zi, ind).two_sided_id()
+
+        loop()
+        l_med, l_min, l_max = timed(loop, max(1, args.repeats // 2))
+        # row pivots against the lone chain started from the batch's own column ID (identical bits on both sides)
+        agree = []
+        for i in range(min(nl, 8)):
+            ri = int(ranks_h[i])
+            cols = col_ind[i, :ri]
+            lone = rc.ColumnID(a[i][:, cols].contiguous(), r[i, :ri].contiguous(), col_ind[i].clone()).two_sided_id()
+            mine, lrow = row_ind[i].cpu().numpy(), lone.row_ind.cpu().numpy()
+            ct = a[i][:, cols].double().cpu().numpy().T
+            agree.append(int(agreed_pivot_prefix(mine, np.linalg.qr(ct[:, mine], mode="r")[:ri], lrow, np.linalg.qr(ct[:, lrow], mode="r")[:ri],
+                                                 np.dtype(np.float64 if dtype == torch.float64 else np.float32))))
+        row = dict(count=count, m=m, n=n, k=k, tol=tol, dtype=str(dtype).replace("torch.", ""),
+                   column_id_s=b_med, column_id_matrices_per_s=count / b_med,
+                   two_sided_s=t_med, two_sided_s_min=t_min, two_sided_s_max=t_max, two_sided_matrices_per_s=count / t_med,
+                   two_sided_over_column_id=b_med / t_med,
+                   loop_matrices=nl, loop_s=l_med, loop_matrices_per_s=nl / l_med, speedup=(count / t_med) / (nl / l_med),
+                   ranks_min=int(ranks_h.min()), ranks_max=int(ranks_h.max()), row_pivots_agreed_prefix=agree, kk=kk)
+        results.append(row)
+        print(json.dumps(row), flush=True)
+        del a, c, x, r, row_ind, col_ind, ranks
+        torch.cuda.empty_cache()
+    return results
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--loop-count", type=int, default=64)
     ap.add_argument("--shapes", default="0,1,2")
     ap.add_argument("--out", default="")
+    ap.add_argument("--two-sided", action="store_true")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("batched_id_bench: no GPU visible (this tool only measures on the device)")
     torch.cuda.set_device(0)
+    if args.two_sided:
+        results = two_sided_rows(args)
+        with open(args.out or os.path.join(ROOT, "profiles", "batched_two_sided_bench.json"), "w") as f:
+            json.dump(results, f, indent=1)
+        return
     results = []
     for si in [int(x) for x in args.shapes.split(",")]:
         count, m, n, k, tol, dtype = SHAPES[si]
