@@ -1572,36 +1572,7 @@ void qrb_issue(BlockedQrcpJob<T> *J) {
         }
         J->coop_ready = false;  // does not fit this device: step kernels from here on (they redo the selection)
     }
-    // A panel is ~65 dependent launches at ~3.5 us of host time each: replay them from a hipGraph, cached on the context
-    // under everything the launches bake in (the arena hands out the same addresses for the same call sequence, so a
-    // host that compresses many same-shaped matrices replays).  Opt-in (RC_QRCP_GRAPH=1): measured on MI355X the replay does not
-    // beat eager issue -- with 8 matrices in flight the path is bound by the command processor (~3-4 us per kernel over all
-    // streams), not by the host: 1085 matrices/s replayed vs 1207 eager for 8 x (4096 x 4096 f32, k = 64).
-    static const int use_graph = env_int_b("RC_QRCP_GRAPH", 0);
-    // (only for factorizations of a few panels -- the truncated rank-k case: a long one has a different (j0, candidates)
-    // at every panel and would capture each graph for a single use)
-    if (!use_graph || c->prof_on || J->kmax > 4 * kNB) { qrb_issue_launches(J, nbp, cw, grid_a, grid_c); return; }
-    const std::vector<uint64_t> key = {(uint64_t)(uintptr_t)J->w.p, (uint64_t)J->w.cs, (uint64_t)m, (uint64_t)n, (uint64_t)(uintptr_t)J->jpvt, (uint64_t)(uintptr_t)J->tau,
-                                       (uint64_t)(uintptr_t)J->st, (uint64_t)(uintptr_t)J->host_st, (uint64_t)j0, (uint64_t)nbp, (uint64_t)cw, (uint64_t)sizeof(T),
-                                       (uint64_t)(uintptr_t)c->stream};
-    auto it = c->qrb_graphs.find(key);
-    if (it == c->qrb_graphs.end()) {
-        if (c->qrb_graphs.size() >= 64) {  // bounded: a host cycling through many shapes simply re-captures
-            for (auto &kv : c->qrb_graphs) (void)hipGraphExecDestroy(kv.second);
-            c->qrb_graphs.clear();
-        }
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t exec = nullptr;
-        if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); qrb_issue_launches(J, nbp, cw, grid_a, grid_c); return; }
-        bool ok = true;
-        try { qrb_issue_launches(J, nbp, cw, grid_a, grid_c); } catch (const Error &) { ok = false; }
-        if (hipStreamEndCapture(c->stream, &graph) != hipSuccess || !graph) ok = false;
-        if (ok && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) ok = false;
-        if (graph) (void)hipGraphDestroy(graph);
-        if (!ok) { (void)hipGetLastError(); qrb_issue_launches(J, nbp, cw, grid_a, grid_c); return; }
-        it = c->qrb_graphs.emplace(key, exec).first;
-    }
-    RC_HIP(hipGraphLaunch(it->second, c->stream));
+    qrb_issue_launches(J, nbp, cw, grid_a, grid_c);
 }
 
 // to be called after the context's stream has been synchronised since qrb_issue(); true = factorization complete
@@ -1721,8 +1692,8 @@ static bool qrb_finish_with(BlockedQrcpJob<T> *J, QrbState h, bool coop, bool op
 // Needs: cooperative panels for every panel of the job, no T factors kept (no Q wanted), no per-panel diagnostics.
 template <typename T>
 bool qrb_optimistic_possible(BlockedQrcpJob<T> *J) {
-    static const int on = env_int_b("RC_QRCP_OPTIMISTIC", 1), check = env_int_b("RC_QRCP_CHECK", 0), graph = env_int_b("RC_QRCP_GRAPH", 0);
-    if (!on || check || graph || !J->coop_ready || J->keep_t || J->j0 != 0) return false;
+    static const int on = env_int_b("RC_QRCP_OPTIMISTIC", 1), check = env_int_b("RC_QRCP_CHECK", 0);
+    if (!on || check || !J->coop_ready || J->keep_t || J->j0 != 0) return false;
     const int64_t panels = cdivb(J->kmax, kNB);
     if (panels < 1 || panels > 16) return false;
     // every panel must take the cooperative path: rows fit a wave's registers (qrb_issue's own test) at the panel's first row

@@ -16,17 +16,16 @@
 //    registers between the three dot products and the rotation (one LDS read +
 //    one LDS write of the pair per round), reduce with DPP row operations (no
 //    LDS traffic for the reductions) and the 1024-thread workgroup needs ONE
-//    barrier per round.  The right singular vectors are NOT accumulated here:
-//    every rotation (c, s) is appended to a log in HBM (write-only stream).
-//  * k_jacobi_replay_v: V = product of the logged rotations.  Rotations act on
-//    columns, so every ROW of V is independent: one wave per row keeps its row
-//    in LDS and streams the log -- no barrier at all, 128 waves in parallel.
+//    barrier per round.  Every rotation (c, s) is published to a log in HBM
+//    (write-only stream); up to n = 128 a second workgroup of the same launch
+//    accumulates the right singular vectors from it as it is written.
+//  * k_jacobi_replay_v: V = product of the logged rotations for the larger
+//    cores.  Rotations act on columns, so every ROW of V is independent: one
+//    wave per row keeps its row in LDS and streams the log -- no barrier at all.
 //  * k_jacobi_global: fallback for cores that do not fit LDS (n <= 1024),
 //    everything in L2-resident global memory.
 #include "rc_common.hpp"
 #include "rc_device.hpp"
-
-#include <cstdlib>
 
 namespace rc {
 
@@ -55,7 +54,7 @@ __device__ inline void rr_pair(int N, int r, int pi, int &p, int &q) {
 // Always evaluated in f64: with f32 parameters c^2 + s^2 - 1 has a systematic sign, and the thousands of rotations a
 // column goes through inflate the singular values (3e-5 at n = 300).  A tiny angle (|d| >> |h|) is safe: t -> 0.
 template <typename T>
-__device__ inline void jacobi_rotation(T app, T aqq, T apq, T &c, T &s, T *t_out = nullptr) {
+__device__ inline void jacobi_rotation(T app, T aqq, T apq, T &c, T &s) {
     const double d = (double)aqq - (double)app, h = 2.0 * (double)apq;
     const double w = fma(d, d, h * h);
     double ri = __builtin_amdgcn_rsq(w);
@@ -67,7 +66,6 @@ __device__ inline void jacobi_rotation(T app, T aqq, T apq, T &c, T &s, T *t_out
     const double cd = fast_rsqrt(fma(t, t, 1.0));
     c = (T)cd;
     s = (T)(cd * t);
-    if (t_out) *t_out = (T)t;
 }
 
 // one rotation record of the log
@@ -114,11 +112,15 @@ __global__ void k_clear_words(unsigned *p, int n) {
     for (int i = threadIdx.x; i < n; i += blockDim.x) p[i] = 0u;
 }
 
+// Lanes per column pair: one DPP row.
+constexpr int kLPP = 16;
+// Sweep budget of the LDS-resident Jacobi; the fused launch hands the sweep count over in the 8-bit payload of a tagged word.
+constexpr int kMaxSweeps = 30;
+static_assert(kMaxSweeps < 255, "sweep count must fit a tagged word");
+
 // ---------------------------------------------------------------------------
-// LDS-resident one-sided Jacobi.  LPP lanes own one column pair and keep NE = ceil(n / LPP)
-// rows of both columns in registers; with LPP = 4 a 128 x 128 core needs only 4 waves
-// (one per SIMD), which minimises the per-pair overhead (reductions + rotation
-// parameters are paid per wave instruction, not per element).
+// LDS-resident one-sided Jacobi.  16 lanes own one column pair and keep NE = n / 16 rows (rounded up) of both columns in
+// registers; 1024 threads = 64 groups, one per pair slot of a 128 x 128 core.
 //   g      : n x n column-major input (global), destroyed
 //   log    : [max_sweeps][N-1][N/2] rotations (c = 1, s = 0 where none)
 //   sweeps : number of sweeps performed (device scalar out)
@@ -127,25 +129,6 @@ __global__ void k_clear_words(unsigned *p, int n) {
 // ---------------------------------------------------------------------------
 //   fused  : != 0: launched with TWO workgroups; the second one accumulates V from the published records while the first
 //            is still rotating (vsync[0] = number of sweeps once known, vsync[1 + j] = order[j] + 1; both zeroed before)
-// RC_JAC_ABL: timing ablations of the producer's round (diagnostic builds only, tools/jacobi_ablation.sh; results are WRONG):
-// 1 no rotation records, 2 no rcp/rsqrt in the rotation, 4 no write-back, 8 no group reduction, 16 no LDS reads, 32 rotate always
-#ifndef RC_JAC_ABL
-#define RC_JAC_ABL 0
-#endif
-// RC_JAC_TIMING: s_memtime stamps of wave 0 of the producer, summed per phase of the round (diagnostic builds only,
-// tools/jacobi_timing.py; a stamp costs a few hundred cycles and drains the wave's LDS queue)
-#ifdef RC_JAC_TIMING
-__device__ unsigned long long g_jac_dbg[8];
-#define RC_JTICK(k)                                                                      \
-    {                                                                                    \
-        unsigned long long now_;                                                         \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(now_)::"memory");  \
-        jt[k] += now_ - jlast;                                                           \
-        jlast = now_;                                                                    \
-    }
-#else
-#define RC_JTICK(k)
-#endif
 // PROTOCOL INVARIANTS of the fused launch (two workgroups; reviewed against the code in round 3 -- keep list and code in step)
 //  J1  One direction only: workgroup 0 (producer) publishes, workgroup 1 (consumer) reads; the producer never waits for the
 //      consumer, so the two need not be co-resident and the producer's result (U, S) never depends on the consumer.
@@ -160,13 +143,11 @@ __device__ unsigned long long g_jac_dbg[8];
 //      vsync[0] <= s; the producer writes exactly one of the two after sweep s - 1.  Index of a record: (sweep, round, pair slot),
 //      the same expression on both sides (FULL: pair slot = group).
 //  J6  Every consumer spin is bounded (kSpin); on expiry health bit 8 is raised and V is reported incomplete -- never silently wrong.
-//   FULL   : n == LPP * NE and one group per pair slot: no row / column bounds, no slot loop (the round is bound by the
+//   FULL   : n == 16 * NE and one group per pair slot: no row / column bounds, no slot loop (the round is bound by the
 //            number of instructions the 16 waves issue, and the predicates were a quarter of them)
-//   CN     : squared column norms are carried in LDS and updated by the rotation (app -= t apq, aqq += t apq) instead of
-//            being recomputed by every pair in every round; refreshed from the columns at the start of each sweep
-template <typename T, int LPP, int NE, bool FULL, bool CN>
-__global__ __launch_bounds__(LPP == 16 ? 1024 : 512) void k_jacobi_lds(Mat<T> g, Rot<T> *log, int *sweeps_out, Mat<T> uc, T *s, int *order_out, int max_sweeps,
-                                                                       int fused, unsigned *vsync, unsigned long long *chk, unsigned *epoch_p, Mat<T> vc, int *health, int ld) {
+template <typename T, int NE, bool FULL>
+__global__ __launch_bounds__(1024) void k_jacobi_lds(Mat<T> g, Rot<T> *log, int *sweeps_out, Mat<T> uc, T *s, int *order_out, int max_sweeps, int fused,
+                                                  unsigned *vsync, unsigned long long *chk, unsigned *epoch_p, Mat<T> vc, int *health, int ld) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int n = (int)g.rows;
     // ld: column pitch chosen by the host (jacobi_pitch): the two column groups of a 32-lane half read neighbouring columns
@@ -178,7 +159,7 @@ __global__ __launch_bounds__(LPP == 16 ? 1024 : 512) void k_jacobi_lds(Mat<T> g,
     __shared__ int sh_rot_word;
 #define sh_rot sh_rot_word
     const int tid = threadIdx.x, nthr = blockDim.x;
-    const int ll = tid % LPP, grp = tid / LPP, ngrp = nthr / LPP;
+    const int ll = tid % kLPP, grp = tid / kLPP, ngrp = nthr / kLPP;
     const int N = (n + 1) & ~1;
     const int npairs = N / 2;
     const unsigned epoch = fused ? __hip_atomic_load(epoch_p, __ATOMIC_RELAXED, RC_AGENT) & 0xffffffu : 0u;
@@ -225,7 +206,7 @@ __global__ __launch_bounds__(LPP == 16 ? 1024 : 512) void k_jacobi_lds(Mat<T> g,
                         T *vp = V + p * ld, *vq = V + q * ld;
 #pragma unroll
                         for (int e = 0; e < NE; ++e) {
-                            const int i = ll + LPP * e;
+                            const int i = ll + kLPP * e;
                             if (FULL || i < n) {
                                 const T a = vp[i], b = vq[i];
                                 vp[i] = rot.c * a - rot.s * b;
@@ -243,7 +224,7 @@ __global__ __launch_bounds__(LPP == 16 ? 1024 : 512) void k_jacobi_lds(Mat<T> g,
             for (int it = 0; it < kSpin && (enc = tagged_get(vsync + 1 + j, epoch)) == 0u; ++it) __builtin_amdgcn_s_sleep(8);
             if (enc == 0u) { lost = true; continue; }
             const int dst = (int)enc - 1;
-            for (int i = ll; i < n; i += LPP) vc.at(i, dst) = V[j * ld + i];
+            for (int i = ll; i < n; i += kLPP) vc.at(i, dst) = V[j * ld + i];
         }
         if (lost && ll == 0) atomicOr(health, 8);  // the producer never showed up within the spin bound: V is incomplete
         __syncthreads();
@@ -259,30 +240,16 @@ __global__ __launch_bounds__(LPP == 16 ? 1024 : 512) void k_jacobi_lds(Mat<T> g,
     }
     __syncthreads();
 
-#ifdef RC_JAC_TIMING
-    unsigned long long jt[6] = {0, 0, 0, 0, 0, 0}, jlast;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(jlast)::"memory");
-#endif
     int sweep = 0;
     bool converged = false;
     for (; sweep < max_sweeps; ++sweep) {
         if (tid == 0) sh_rot = 0;
-        if (CN) {
-            for (int j = grp; j < n; j += ngrp) {
-                const T *gj = G + j * ld;
-                T acc = 0;
-                for (int i = ll; i < n; i += LPP) acc = fma(gj[i], gj[i], acc);
-                acc = group_sum_dpp<LPP>(acc);
-                if (ll == 0) sig[j] = acc;
-            }
-        }
         __syncthreads();
         // circle-method pair of this group, advanced round by round when the group owns one pair slot (no integer
         // modulo on the per-round critical path): slot 0 pairs N - 1 with r, slot pi pairs (r + pi) with (r - pi) mod N - 1
         const bool one_slot = FULL || npairs <= ngrp;
         int pr = grp % (N - 1), qr = ((N - 1) - grp % (N - 1)) % (N - 1);
         for (int r = 0; r < N - 1; ++r) {
-            RC_JTICK(5)  // barrier + loop control
             for (int pi = grp; pi < npairs; pi += FULL ? (1 << 20) : ngrp) {  // FULL: exactly one trip
                 int p, q;
                 if (one_slot) {
@@ -301,33 +268,23 @@ __global__ __launch_bounds__(LPP == 16 ? 1024 : 512) void k_jacobi_lds(Mat<T> g,
                     T app = 0, aqq = 0, apq = 0;
 #pragma unroll
                     for (int e = 0; e < NE; ++e) {
-                        int i = ll + LPP * e;
-                        if (RC_JAC_ABL & 16) { a[e] = (T)(i + p) * (T)1e-3; b[e] = (T)(i - q) * (T)1e-3; }
-                        else {
+                        int i = ll + kLPP * e;
                         a[e] = (FULL || i < n) ? gp[i] : (T)0;
                         b[e] = (FULL || i < n) ? gq[i] : (T)0;
-                        }
-                        if (!CN) { app = fma(a[e], a[e], app); aqq = fma(b[e], b[e], aqq); }
+                        app = fma(a[e], a[e], app);
+                        aqq = fma(b[e], b[e], aqq);
                         apq = fma(a[e], b[e], apq);
                     }
-                    RC_JTICK(0)  // LDS reads + dot products
-                    if (CN) { app = sig[p]; aqq = sig[q]; apq = group_sum_dpp<LPP>(apq); }
-                    else if (!(RC_JAC_ABL & 8)) { app = group_sum_dpp<LPP>(app); aqq = group_sum_dpp<LPP>(aqq); apq = group_sum_dpp<LPP>(apq); }
-                    RC_JTICK(1)  // group reduction
-                    // rotate iff |apq| > tol * sqrt(app * aqq)   (uniform over the LPP lanes)
-                    if ((RC_JAC_ABL & 32) || apq * apq > tol2 * app * aqq) {
-                        if (RC_JAC_ABL & 2) { rot.c = (T)0.8 + apq * (T)1e-30; rot.s = (T)0.6 + app * (T)1e-30; }
-                        else if (CN) {
-                            T t;
-                            jacobi_rotation(app, aqq, apq, rot.c, rot.s, &t);
-                            if (ll == 0) { sig[p] = app - t * apq; sig[q] = aqq + t * apq; }
-                        } else jacobi_rotation(app, aqq, apq, rot.c, rot.s);
-                        RC_JTICK(2)  // rotation parameters
+                    app = group_sum_dpp<kLPP>(app);
+                    aqq = group_sum_dpp<kLPP>(aqq);
+                    apq = group_sum_dpp<kLPP>(apq);
+                    // rotate iff |apq| > tol * sqrt(app * aqq)   (uniform over the 16 lanes)
+                    if (apq * apq > tol2 * app * aqq) {
+                        jacobi_rotation(app, aqq, apq, rot.c, rot.s);
 #pragma unroll
                         for (int e = 0; e < NE; ++e) {
-                            int i = ll + LPP * e;
-                            if (RC_JAC_ABL & 4) { if (rot.c * a[e] - rot.s * b[e] == (T)123.456 && rot.s * a[e] + rot.c * b[e] == (T)654.321) gp[i] = 0; }
-                            else if (FULL || i < n) {
+                            int i = ll + kLPP * e;
+                            if (FULL || i < n) {
                                 gp[i] = rot.c * a[e] - rot.s * b[e];
                                 gq[i] = rot.s * a[e] + rot.c * b[e];
                             }
@@ -342,27 +299,19 @@ __global__ __launch_bounds__(LPP == 16 ? 1024 : 512) void k_jacobi_lds(Mat<T> g,
                         if (ll == 0 && (apq * apq > tol * (T)0.0625 * app * aqq || rot.s * rot.s > (T)16 * tol)) sh_rot = 2;  // plain store: every writer writes 2
                     }
                 }
-                RC_JTICK(3)  // rotation applied, written back (LDS queue drained by the stamp)
-                if (ll == 0 && !(RC_JAC_ABL & 1)) {
+                if (ll == 0) {
                     if (fused) rot_publish(log + ((size_t)sweep * (N - 1) + r) * npairs + pi, chk + ((size_t)sweep * (N - 1) + r) * npairs + pi, rot, key);
                     else log[((size_t)sweep * (N - 1) + r) * npairs + pi] = rot;
                 }
             }
-            RC_JTICK(4)  // record published
             lds_barrier();  // pairs of one round are disjoint; the next round re-pairs the columns
         }
         const int rotated = sh_rot;
         __syncthreads();
-        if (!(RC_JAC_ABL & 32) && rotated < 2) { ++sweep; converged = true; break; }
+        if (rotated < 2) { ++sweep; converged = true; break; }
     }
     // max_sweeps exhausted with rotations still above the thresholds: reported, never silent (health bit 4, value 16)
-    if (tid == 0 && !converged && !(RC_JAC_ABL & 32) && health) atomicOr(health, 16);
-#ifdef RC_JAC_TIMING
-    if (tid == 0) {
-        for (int k2 = 0; k2 < 6; ++k2) g_jac_dbg[k2] = jt[k2];
-        g_jac_dbg[6] = (unsigned long long)sweep * (N - 1);
-    }
-#endif
+    if (tid == 0 && !converged && health) atomicOr(health, 16);
     if (tid == 0) {
         *sweeps_out = sweep;
         if (fused) tagged_put(vsync, epoch, (unsigned)sweep);
@@ -372,8 +321,8 @@ __global__ __launch_bounds__(LPP == 16 ? 1024 : 512) void k_jacobi_lds(Mat<T> g,
     for (int j = grp; j < n; j += ngrp) {
         const T *gj = G + j * ld;
         T acc = 0;
-        for (int i = ll; i < n; i += LPP) acc += gj[i] * gj[i];
-        acc = group_sum_dpp<LPP>(acc);
+        for (int i = ll; i < n; i += kLPP) acc += gj[i] * gj[i];
+        acc = group_sum_dpp<kLPP>(acc);
         if (ll == 0) sig[j] = sqrt(acc);
     }
     __syncthreads();
@@ -392,321 +341,22 @@ __global__ __launch_bounds__(LPP == 16 ? 1024 : 512) void k_jacobi_lds(Mat<T> g,
         const T sj = sig[j];
         const T inv = sj > (T)0 ? (T)1 / sj : (T)0;
         const T *gj = G + j * ld;
-        for (int i = ll; i < n; i += LPP) uc.at(i, dst) = gj[i] * inv;
+        for (int i = ll; i < n; i += kLPP) uc.at(i, dst) = gj[i] * inv;
     }
 #undef sh_rot
 }
 
 // ---------------------------------------------------------------------------
-// Two-column BLOCK schedule of the fused one-sided Jacobi (round 3; n = 128 = 16 lanes x 8 rows, the core of the headline
-// pipeline).  k_jacobi_lds visits the 8128 column pairs of a sweep in 127 rounds of 64 disjoint pairs: every rotation costs two
-// column loads, two column stores and a share of a workgroup barrier.  Here the columns form 64 blocks of two neighbours; a sweep
-// is ONE round of the 64 intra-block pairs plus a 63-round tournament of the blocks (circle method), and a group of 16 lanes that
-// meets block pair {X, Y} loads its FOUR columns once, rotates the four cross pairs in two phases of two INDEPENDENT rotations --
-// (x0, y0) & (x1, y1), then (x0, y1) & (x1, y0) -- and stores them once: half the LDS traffic and half the barriers per
-// rotation (64 instead of 127 per sweep), and two independent dependent chains per lane to fill the issue slots.  Every pair of
-// columns still meets exactly once per sweep (a cyclic-by-blocks ordering); the rotation, its threshold, the two-part
-// convergence test, the singular-value sort and the record protocol (J1 - J6 above; records indexed (sweep, 64 intra | round,
-// slot, 0..3)) are k_jacobi_lds's.  512 threads = 32 groups = one per block pair.  The consumer workgroup mirrors the schedule on V.
+// V = J_1 J_2 ... applied to I, row by row: one wave per row of V.  Runs for the cores the fused launch of k_jacobi_lds
+// cannot take (more than 64 pair slots), so every lane walks several pair slots of a round.
 // ---------------------------------------------------------------------------
 template <typename T>
-__device__ __forceinline__ void jb2_rotate(T (&a)[8], T (&b)[8], T tol, T tol2, Rot<T> &rot, int ll, int *sh_rot_p) {
-    T app = 0, aqq = 0, apq = 0;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { app = fma(a[e], a[e], app); aqq = fma(b[e], b[e], aqq); apq = fma(a[e], b[e], apq); }
-    app = group_sum_dpp<16>(app);
-    aqq = group_sum_dpp<16>(aqq);
-    apq = group_sum_dpp<16>(apq);
-    rot.c = (T)1;
-    rot.s = (T)0;
-    if (apq * apq > tol2 * app * aqq) {  // uniform over the 16 lanes
-        jacobi_rotation(app, aqq, apq, rot.c, rot.s);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const T x = a[e], y = b[e];
-            a[e] = rot.c * x - rot.s * y;
-            b[e] = rot.s * x + rot.c * y;
-        }
-        if (ll == 0 && (apq * apq > tol * (T)0.0625 * app * aqq || rot.s * rot.s > (T)16 * tol)) *sh_rot_p = 2;  // another sweep is needed (k_jacobi_lds)
-    }
-}
-template <typename T>
-__device__ __forceinline__ void jb2_apply(T (&a)[8], T (&b)[8], Rot<T> rot) {
-    if (rot.s != (T)0) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const T x = a[e], y = b[e];
-            a[e] = rot.c * x - rot.s * y;
-            b[e] = rot.s * x + rot.c * y;
-        }
-    }
-}
-
-template <typename T>
-__global__ __launch_bounds__(512) void k_jacobi_b2(Mat<T> g, Rot<T> *log, int *sweeps_out, Mat<T> uc, T *s, int *order_out, int max_sweeps, unsigned *vsync,
-                                                    unsigned long long *chk, unsigned *epoch_p, Mat<T> vc, int *health, int ld) {
-    constexpr int n = 128, NB = 64, NR = NB - 1, NSLOT = NB / 2, LPP = 16, NE = 8;
-    constexpr int REC = NB + NR * NSLOT * 4;  // records per sweep = 8128 = (n - 1) * n / 2: the log of k_jacobi_lds has the same size
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    T *G = reinterpret_cast<T *>(smem_raw);
-    T *sig = G + (size_t)ld * n;
-    int *order = reinterpret_cast<int *>(sig + n);
-    __shared__ int sh_rot_b2;
-    const int tid = threadIdx.x, nthr = 512;
-    const int ll = tid % LPP, grp = tid / LPP, ngrp = nthr / LPP;  // 32 groups
-    // The two groups of a 32-lane half would both read an even column, then both an odd one: same offset in the bank row (the pitch is
-    // 16 mod 32 elements), a two-way conflict on every access.  Odd groups take the columns of a block in the other order, so one
-    // instruction reads an even and an odd column per half: conflict-free.  The pairs of a phase are the same sets either way --
-    // (x0, y0) & (x1, y1), then (x0, y1) & (x1, y0) -- only their order inside a phase differs, and the consumer uses the same rule.
-    const int sw = grp & 1;
-    const unsigned epoch = __hip_atomic_load(epoch_p, __ATOMIC_RELAXED, RC_AGENT) & 0xffffffu;
-    const unsigned long long key = epoch_key(epoch);
-    // the block pair of this group in tournament round rr: slot 0 pairs block NB - 1 with rr, slot i pairs (rr + i) with (rr - i) mod NR
-    auto blocks_of = [&](int pr, int qr, int &X, int &Y) {
-        X = grp == 0 ? NB - 1 : pr;
-        Y = grp == 0 ? pr : qr;
-        if (X > Y) { const int t = X; X = Y; Y = t; }  // X < Y: every cross pair (x_i, y_j) has x_i < y_j, the (p < q) convention of the rotation
-    };
-    if (blockIdx.x == 1) {
-        // ---- consumer: V = product of the rotations, the producer's schedule ----
-        constexpr int kSpin = 1 << 24;
-        T *V = G;
-        for (int e = tid; e < n * n; e += nthr) {
-            const int i = e % n, j = e / n;
-            V[j * ld + i] = (i == j) ? (T)1 : (T)0;
-        }
-        __syncthreads();
-        bool lost = false;
-        auto fetch = [&](size_t rec) -> Rot<T> {
-            Rot<T> rot{(T)1, (T)0};
-            bool ok = false;
-            for (int it = 0; it < kSpin && !(ok = rot_fetch(log + rec, chk + rec, rot, key)); ++it) __builtin_amdgcn_s_sleep(2);
-            if (!ok) { lost = true; rot.c = (T)1; rot.s = (T)0; }
-            return rot;
-        };
-        for (int sweep = 0;; ++sweep) {
-            if (tid == 0) {  // has the producer started this sweep, or did it finish before it?
-                int fin = 2;
-                for (int it = 0; it < kSpin; ++it) {
-                    const unsigned d = tagged_get(vsync, epoch);
-                    if (d != 0u && (int)d <= sweep) { fin = 1; break; }
-                    Rot<T> r0;
-                    if (sweep < max_sweeps && rot_fetch(log + (size_t)sweep * REC, chk + (size_t)sweep * REC, r0, key)) { fin = 0; break; }
-                    __builtin_amdgcn_s_sleep(8);
-                }
-                sh_rot_b2 = fin;
-            }
-            __syncthreads();
-            const int fin = sh_rot_b2;
-            __syncthreads();
-            if (fin) { lost = lost || fin == 2; break; }
-            const size_t base = (size_t)sweep * REC;
-            for (int h = 0; h < 2; ++h) {  // intra-block pairs
-                const int b = grp + ngrp * h;
-                const Rot<T> rot = fetch(base + b);
-                if (rot.s != (T)0) {
-                    T *vp = V + (2 * b) * ld, *vq = V + (2 * b + 1) * ld;
-                    T a[NE], c2[NE];
-#pragma unroll
-                    for (int e = 0; e < NE; ++e) { a[e] = vp[ll + LPP * e]; c2[e] = vq[ll + LPP * e]; }
-                    jb2_apply(a, c2, rot);
-#pragma unroll
-                    for (int e = 0; e < NE; ++e) { vp[ll + LPP * e] = a[e]; vq[ll + LPP * e] = c2[e]; }
-                }
-            }
-            lds_barrier();
-            int pr = grp % NR, qr = (NR - grp % NR) % NR;
-            for (int rr = 0; rr < NR; ++rr) {
-                int X, Y;
-                blocks_of(pr, qr, X, Y);
-                pr = pr + 1 == NR ? 0 : pr + 1;
-                qr = qr + 1 == NR ? 0 : qr + 1;
-                const size_t rec = base + NB + ((size_t)rr * NSLOT + grp) * 4;
-                const Rot<T> r0 = fetch(rec), r1 = fetch(rec + 1), r2 = fetch(rec + 2), r3 = fetch(rec + 3);
-                if (r0.s != (T)0 || r1.s != (T)0 || r2.s != (T)0 || r3.s != (T)0) {
-                    T *v0 = V + (2 * X + sw) * ld, *v1 = V + (2 * X + 1 - sw) * ld, *v2 = V + (2 * Y + sw) * ld, *v3 = V + (2 * Y + 1 - sw) * ld;
-                    T c0[NE], c1[NE], c2[NE], c3[NE];
-#pragma unroll
-                    for (int e = 0; e < NE; ++e) { const int i = ll + LPP * e; c0[e] = v0[i]; c1[e] = v1[i]; c2[e] = v2[i]; c3[e] = v3[i]; }
-                    jb2_apply(c0, c2, r0);
-                    jb2_apply(c1, c3, r1);
-                    jb2_apply(c0, c3, r2);
-                    jb2_apply(c1, c2, r3);
-#pragma unroll
-                    for (int e = 0; e < NE; ++e) { const int i = ll + LPP * e; v0[i] = c0[e]; v1[i] = c1[e]; v2[i] = c2[e]; v3[i] = c3[e]; }
-                }
-                lds_barrier();
-            }
-        }
-        // columns go out in the sorted order the producer publishes at its very end
-        for (int j = grp; j < n; j += ngrp) {
-            unsigned enc = 0;
-            for (int it = 0; it < kSpin && (enc = tagged_get(vsync + 1 + j, epoch)) == 0u; ++it) __builtin_amdgcn_s_sleep(8);
-            if (enc == 0u) { lost = true; continue; }
-            const int dst = (int)enc - 1;
-            for (int i = ll; i < n; i += LPP) vc.at(i, dst) = V[j * ld + i];
-        }
-        if (lost && ll == 0) atomicOr(health, 8);  // the producer never showed up within the spin bound: V is incomplete
-        __syncthreads();
-        if (tid == 0) __hip_atomic_fetch_add(epoch_p, 1u, __ATOMIC_RELAXED, RC_AGENT);  // the next launch uses a new key
-        return;
-    }
-    // ---- producer ----
-    const T tol = sqrt((T)n) * JEps<T>::eps();
-    const T tol2 = tol * tol;
-    for (int e = tid; e < n * n; e += nthr) {
-        const int i = e % n, j = e / n;
-        G[j * ld + i] = g.p[(int64_t)j * g.cs + i];
-    }
-    __syncthreads();
-    int sweep = 0;
-    bool converged = false;
-    for (; sweep < max_sweeps; ++sweep) {
-        if (tid == 0) sh_rot_b2 = 0;
-        __syncthreads();
-        const size_t base = (size_t)sweep * REC;
-        for (int h = 0; h < 2; ++h) {  // the 64 intra-block pairs (2 b, 2 b + 1)
-            const int b = grp + ngrp * h;
-            T *gp = G + (2 * b) * ld, *gq = G + (2 * b + 1) * ld;
-            T a[NE], c2[NE];
-#pragma unroll
-            for (int e = 0; e < NE; ++e) { a[e] = gp[ll + LPP * e]; c2[e] = gq[ll + LPP * e]; }
-            Rot<T> rot;
-            jb2_rotate(a, c2, tol, tol2, rot, ll, &sh_rot_b2);
-            if (rot.s != (T)0) {
-#pragma unroll
-                for (int e = 0; e < NE; ++e) { gp[ll + LPP * e] = a[e]; gq[ll + LPP * e] = c2[e]; }
-            }
-            if (ll == 0) rot_publish(log + base + b, chk + base + b, rot, key);
-        }
-        lds_barrier();
-        int pr = grp % NR, qr = (NR - grp % NR) % NR;
-        for (int rr = 0; rr < NR; ++rr) {
-            int X, Y;
-            blocks_of(pr, qr, X, Y);
-            pr = pr + 1 == NR ? 0 : pr + 1;
-            qr = qr + 1 == NR ? 0 : qr + 1;
-            T *g0 = G + (2 * X + sw) * ld, *g1 = G + (2 * X + 1 - sw) * ld, *g2 = G + (2 * Y + sw) * ld, *g3 = G + (2 * Y + 1 - sw) * ld;
-            T c0[NE], c1[NE], c2[NE], c3[NE];
-#pragma unroll
-            for (int e = 0; e < NE; ++e) { const int i = ll + LPP * e; c0[e] = g0[i]; c1[e] = g1[i]; c2[e] = g2[i]; c3[e] = g3[i]; }
-            Rot<T> r0, r1, r2, r3;
-            jb2_rotate(c0, c2, tol, tol2, r0, ll, &sh_rot_b2);   // phase 1: (x0, y0) and (x1, y1) are independent
-            jb2_rotate(c1, c3, tol, tol2, r1, ll, &sh_rot_b2);
-            jb2_rotate(c0, c3, tol, tol2, r2, ll, &sh_rot_b2);   // phase 2: (x0, y1) and (x1, y0)
-            jb2_rotate(c1, c2, tol, tol2, r3, ll, &sh_rot_b2);
-            if (r0.s != (T)0 || r1.s != (T)0 || r2.s != (T)0 || r3.s != (T)0) {
-#pragma unroll
-                for (int e = 0; e < NE; ++e) { const int i = ll + LPP * e; g0[i] = c0[e]; g1[i] = c1[e]; g2[i] = c2[e]; g3[i] = c3[e]; }
-            }
-            if (ll == 0) {
-                const size_t rec = base + NB + ((size_t)rr * NSLOT + grp) * 4;
-                rot_publish(log + rec, chk + rec, r0, key);
-                rot_publish(log + rec + 1, chk + rec + 1, r1, key);
-                rot_publish(log + rec + 2, chk + rec + 2, r2, key);
-                rot_publish(log + rec + 3, chk + rec + 3, r3, key);
-            }
-            lds_barrier();  // block pairs of one round are disjoint; the next round re-pairs the blocks
-        }
-        const int rotated = sh_rot_b2;
-        __syncthreads();
-        if (rotated < 2) { ++sweep; converged = true; break; }
-    }
-    if (tid == 0 && !converged && health) atomicOr(health, 16);  // sweep budget exhausted with rotations above the thresholds
-    if (tid == 0) {
-        *sweeps_out = sweep;
-        tagged_put(vsync, epoch, (unsigned)sweep);
-    }
-    // singular values = column norms; stable descending rank sort (gesdd order) -- as k_jacobi_lds
-    for (int j = grp; j < n; j += ngrp) {
-        const T *gj = G + j * ld;
-        T acc = 0;
-        for (int i = ll; i < n; i += LPP) acc += gj[i] * gj[i];
-        acc = group_sum_dpp<LPP>(acc);
-        if (ll == 0) sig[j] = sqrt(acc);
-    }
-    __syncthreads();
-    for (int i = tid; i < n; i += nthr) {
-        int rank = 0;
-        const T si = sig[i];
-        for (int j = 0; j < n; ++j) rank += (sig[j] > si || (sig[j] == si && j < i)) ? 1 : 0;
-        order[i] = rank;
-        order_out[i] = rank;
-        tagged_put(vsync + 1 + i, epoch, (unsigned)(rank + 1));
-        s[rank] = si;
-    }
-    __syncthreads();
-    for (int j = grp; j < n; j += ngrp) {
-        const int dst = order[j];
-        const T sj = sig[j];
-        const T inv = sj > (T)0 ? (T)1 / sj : (T)0;
-        const T *gj = G + j * ld;
-        for (int i = ll; i < n; i += LPP) uc.at(i, dst) = gj[i] * inv;
-    }
-}
-
-// ---------------------------------------------------------------------------
-// V = J_1 J_2 ... applied to I, row by row: one wave per row of V.
-// ---------------------------------------------------------------------------
-template <typename T, int RPW>
 __global__ __launch_bounds__(256) void k_jacobi_replay_v(int n, const Rot<T> *log, const int *sweeps, const int *order, Mat<T> vc) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     T *rows = reinterpret_cast<T *>(smem_raw);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int N = (n + 1) & ~1, npairs = N / 2;
     const int ns = *sweeps;
-    if (npairs <= 64) {
-        // One pair per lane.  A wave carries RPW independent rows through the rounds: the chain of a row is a
-        // dependent LDS read -> FMA -> LDS write per round, so the rows' chains interleave and a quarter of the
-        // waves (and CUs) does the same work in the same time.  The log is one 64-entry line per round, fetched
-        // PF rounds ahead so that the chain does not pay an L2 latency per round.
-        constexpr int PF = 8;
-        const int row0 = (blockIdx.x * 4 + wv) * RPW;
-        if (row0 >= n) return;  // whole wave; no barriers in this kernel
-        T *v = rows + (size_t)wv * RPW * (n + 1);
-#pragma unroll
-        for (int rr = 0; rr < RPW; ++rr)
-            for (int j = lane; j < n; j += 64) v[rr * (n + 1) + j] = (j == row0 + rr) ? (T)1 : (T)0;
-        const int total = ns * (N - 1);
-        const bool has = lane < npairs;
-        // circle-method pair of this lane, advanced round by round (no integer modulo in the chain):
-        // lane 0 pairs N - 1 with r; lane pi pairs (r + pi) mod (N - 1) with (r - pi) mod (N - 1)
-        int pr = lane % (N - 1), qr = ((N - 1) - lane % (N - 1)) % (N - 1);
-        for (int base = 0; base < total; base += PF) {
-            Rot<T> rt[PF];
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                rt[u].c = (T)1;
-                rt[u].s = (T)0;
-                if (has && base + u < total) rt[u] = log[(size_t)(base + u) * npairs + lane];
-            }
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                if (base + u < total) {
-                    int p = lane == 0 ? N - 1 : pr, q = lane == 0 ? pr : qr;  // lane 0: pr runs through r itself
-                    if (p > q) { const int t = p; p = q; q = t; }
-                    pr = pr + 1 == N - 1 ? 0 : pr + 1;
-                    qr = qr + 1 == N - 1 ? 0 : qr + 1;
-                    if (rt[u].s != (T)0) {
-                        T a[RPW], b[RPW];
-#pragma unroll
-                        for (int rr = 0; rr < RPW; ++rr) { a[rr] = v[rr * (n + 1) + p]; b[rr] = v[rr * (n + 1) + q]; }
-#pragma unroll
-                        for (int rr = 0; rr < RPW; ++rr) {
-                            v[rr * (n + 1) + p] = rt[u].c * a[rr] - rt[u].s * b[rr];
-                            v[rr * (n + 1) + q] = rt[u].s * a[rr] + rt[u].c * b[rr];
-                        }
-                    }
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                }
-            }
-        }
-#pragma unroll
-        for (int rr = 0; rr < RPW; ++rr)
-            if (row0 + rr < n)
-                for (int j = lane; j < n; j += 64) vc.at(row0 + rr, order[j]) = v[rr * (n + 1) + j];
-        return;
-    }
     const int row = blockIdx.x * 4 + wv;
     if (row >= n) return;  // whole wave; no barriers in this kernel
     T *v = rows + (size_t)wv * (n + 1);
@@ -853,62 +503,39 @@ static void jacobi_global(rc_context *c, Mat<T> g, Mat<T> v, Mat<T> uc, T *s, Ma
     hipLaunchKernelGGL(k_jacobi_emit<T>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, g, v, sig, order, uc, vc);
 }
 
-template <typename T, int LPP, int NE, bool FULL, bool CN>
-static void launch_lds_impl(rc_context *c, Mat<T> g, Mat<T> uc, T *s, Mat<T> vc, size_t lds, int ld, int max_sweeps) {
+template <typename T, int NE, bool FULL>
+static void launch_lds_impl(rc_context *c, Mat<T> g, Mat<T> uc, T *s, Mat<T> vc, size_t lds, int ld) {
     const int n = (int)g.rows, N = (n + 1) & ~1;
     ArenaMark mark(c);
-    Rot<T> *log = c->alloc<Rot<T>>((size_t)max_sweeps * (N - 1) * (N / 2));
+    Rot<T> *log = c->alloc<Rot<T>>((size_t)kMaxSweeps * (N - 1) * (N / 2));
     int *sweeps = c->alloc<int>(1);
     int *order = c->alloc<int>((size_t)n);
-    auto kern = k_jacobi_lds<T, LPP, NE, FULL, CN>;
+    auto kern = k_jacobi_lds<T, NE, FULL>;
     static bool attr_set[64] = {};
     if (!attr_set[c->device & 63]) {
         RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048));
         attr_set[c->device & 63] = true;
     }
-    // one LPP-lane group per pair, rounded up to whole waves
-    const int threads = std::min(LPP == 16 ? 1024 : 512, std::max(64, (((N / 2) * LPP + 63) / 64) * 64));
+    // one 16-lane group per pair, rounded up to whole waves
+    const int threads = std::min(1024, std::max(64, (((N / 2) * kLPP + 63) / 64) * 64));
     // fused right vectors: a second workgroup applies the rotations to V as they are published (no replay kernel
-    // after the fact); needs one pair slot per group and the padded n of the register tiling
-    static const int fuse_env = [] { const char *e = getenv("RC_JACOBI_FUSED_V"); return e ? atoi(e) : 1; }();
-    const bool fused = fuse_env && (LPP == 16 || LPP == 8) && (N / 2) * LPP <= threads && n <= LPP * NE && n < 255 && max_sweeps < 255;
+    // after the fact); needs one pair slot per group (n <= 128, which also keeps every sorted position + 1 below 255)
+    const bool fused = (N / 2) * kLPP <= threads;
     if (fused) {
         unsigned *vsync = c->alloc<unsigned>((size_t)n + 1);
-        unsigned long long *chk = c->alloc<unsigned long long>((size_t)max_sweeps * (N - 1) * (N / 2));
+        unsigned long long *chk = c->alloc<unsigned long long>((size_t)kMaxSweeps * (N - 1) * (N / 2));
         // The tagged words are cleared before every launch: a word counts as "published" when its upper 24 bits equal the launch's
         // epoch, and workspace memory that is new to the context (first call, arena growth) holds whatever its last owner left --
         // on a context's first launch (epoch 0 until round 2) any small integer there passed for a sweep count or a sorted
         // position, and the consumer wrote V's columns to the wrong places without noticing (seen as one wrong `vt` among 16
         // contexts' first calls).  The epoch itself now starts at a per-context pseudo-random value (rc_context::epoch_word).
-        static const int no_clear = [] { const char *e = getenv("RC_DEBUG_JACOBI_NO_CLEAR"); return e ? atoi(e) : 0; }();  // (diagnostic: the round-2 behaviour)
-        if (!no_clear) hipLaunchKernelGGL(k_clear_words, dim3(1), dim3(256), 0, c->stream, vsync, n + 1);
-        // two-column block schedule (k_jacobi_b2) for the 128-column core: opt-in (RC_JACOBI_BLOCK2=1).  Measured in round 3: the same
-        // 9 sweeps, 1.80 ms against 1.77 ms for the pair-per-round schedule, headline unchanged -- the kernel is bound by the DEPENDENT
-        // chain of a rotation (dot products -> DPP reduction -> rsq / rcp + Newton -> update -> LDS), not by LDS traffic or barriers: a
-        // block round has two dependent phases, so half the rounds carry the same chain length (SVD)
-        static const int block2 = [] { const char *e = getenv("RC_JACOBI_BLOCK2"); return e ? atoi(e) : 0; }();
-        if (block2 && FULL && !CN && LPP == 16 && NE == 8 && n == 128) {
-            auto kb = k_jacobi_b2<T>;
-            static bool attr_b2[64] = {};
-            if (!attr_b2[c->device & 63]) {
-                RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kb), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048));
-                attr_b2[c->device & 63] = true;
-            }
-            hipLaunchKernelGGL(kb, dim3(2), dim3(512), lds, c->stream, g, log, sweeps, uc, s, order, max_sweeps, vsync, chk, c->epoch_word(), vc, c->health_word(), ld);
-        } else
-        hipLaunchKernelGGL(kern, dim3(2), dim3(threads), lds, c->stream, g, log, sweeps, uc, s, order, max_sweeps, 1, vsync, chk, c->epoch_word(), vc, c->health_word(), ld);
+        hipLaunchKernelGGL(k_clear_words, dim3(1), dim3(256), 0, c->stream, vsync, n + 1);
+        hipLaunchKernelGGL(kern, dim3(2), dim3(threads), lds, c->stream, g, log, sweeps, uc, s, order, kMaxSweeps, 1, vsync, chk, c->epoch_word(), vc, c->health_word(), ld);
     } else {
-        hipLaunchKernelGGL(kern, dim3(1), dim3(threads), lds, c->stream, g, log, sweeps, uc, s, order, max_sweeps, 0, (unsigned *)nullptr, (unsigned long long *)nullptr,
+        hipLaunchKernelGGL(kern, dim3(1), dim3(threads), lds, c->stream, g, log, sweeps, uc, s, order, kMaxSweeps, 0, (unsigned *)nullptr, (unsigned long long *)nullptr,
                            (unsigned *)nullptr, vc, c->health_word(), ld);
+        hipLaunchKernelGGL(k_jacobi_replay_v<T>, dim3((unsigned)((n + 3) / 4)), dim3(256), 4 * (size_t)(n + 1) * sizeof(T), c->stream, n, log, sweeps, order, vc);
     }
-    static const int rpw_env = [] { const char *e = getenv("RC_REPLAY_RPW"); return e ? atoi(e) : 1; }();
-    const int rpw = (N / 2 <= 64) ? (rpw_env == 2 || rpw_env == 4 ? rpw_env : 1) : 1;  // rows per wave: 1 measured best (913 vs 903 compressions/s at 4)
-    const size_t lds_v = 4 * (size_t)rpw * (n + 1) * sizeof(T);
-    const dim3 grid((unsigned)((n + 4 * rpw - 1) / (4 * rpw)));
-    if (fused) { /* V is already complete */ }
-    else if (rpw == 4) hipLaunchKernelGGL((k_jacobi_replay_v<T, 4>), grid, dim3(256), lds_v, c->stream, n, log, sweeps, order, vc);
-    else if (rpw == 2) hipLaunchKernelGGL((k_jacobi_replay_v<T, 2>), grid, dim3(256), lds_v, c->stream, n, log, sweeps, order, vc);
-    else hipLaunchKernelGGL((k_jacobi_replay_v<T, 1>), grid, dim3(256), lds_v, c->stream, n, log, sweeps, order, vc);
     if (c->prof_on && !c->capturing) {  // diagnostic: number of sweeps, reported through the profile table
         int h = 0;
         (void)hipMemcpyAsync(&h, sweeps, sizeof(int), hipMemcpyDeviceToHost, c->stream);  // on the context's own stream
@@ -921,26 +548,13 @@ static void launch_lds_impl(rc_context *c, Mat<T> g, Mat<T> uc, T *s, Mat<T> vc,
     }
 }
 
-template <typename T, int LPP, int NE>
-static void launch_lds(rc_context *c, Mat<T> g, Mat<T> uc, T *s, Mat<T> vc, size_t lds, int ld, int max_sweeps) {
-    // the bound-free instance: every lane row and every pair slot is real (n = 32, 64, 128 with 16 lanes per pair)
-    static const int full_env = [] { const char *e = getenv("RC_JACOBI_FULL"); return e ? atoi(e) : 1; }();
-    const int n = (int)g.rows;
-    static const int cn_env = [] { const char *e = getenv("RC_JACOBI_CACHED_NORMS"); return e ? atoi(e) : 0; }();
-    const bool full = full_env && (LPP == 16 || LPP == 8) && n == LPP * NE && (n / 2) * LPP <= (LPP == 16 ? 1024 : 512);
-    if (full && cn_env && LPP == 16) launch_lds_impl<T, LPP, NE, true, true>(c, g, uc, s, vc, lds, ld, max_sweeps);
-    else if (full) launch_lds_impl<T, LPP, NE, true, false>(c, g, uc, s, vc, lds, ld, max_sweeps);
-    else launch_lds_impl<T, LPP, NE, false, false>(c, g, uc, s, vc, lds, ld, max_sweeps);
-}
-
-template <typename T, int LPP>
-static void launch_lds_lpp(rc_context *c, Mat<T> g, Mat<T> uc, T *s, Mat<T> vc, size_t lds, int ld, int max_sweeps) {
-    const int n = (int)g.rows;
-    constexpr int U = 32 / LPP;  // rows per lane at n = 32
-    if (n <= 32) launch_lds<T, LPP, U>(c, g, uc, s, vc, lds, ld, max_sweeps);
-    else if (n <= 64) launch_lds<T, LPP, 2 * U>(c, g, uc, s, vc, lds, ld, max_sweeps);
-    else if (n <= 128) launch_lds<T, LPP, 4 * U>(c, g, uc, s, vc, lds, ld, max_sweeps);
-    else launch_lds<T, LPP, 6 * U>(c, g, uc, s, vc, lds, ld, max_sweeps);  // f32 up to n = 192 (the LDS bound is ~200)
+template <typename T, int NE>
+static void launch_lds(rc_context *c, Mat<T> g, Mat<T> uc, T *s, Mat<T> vc, size_t lds, int ld) {
+    // the bound-free instance: every lane row and every pair slot is real (n = 32, 64, 128); 192 columns would need 1536 threads
+    if constexpr (NE <= 8) {
+        if (g.rows == kLPP * NE) return launch_lds_impl<T, NE, true>(c, g, uc, s, vc, lds, ld);
+    }
+    launch_lds_impl<T, NE, false>(c, g, uc, s, vc, lds, ld);
 }
 
 // ?gesdd returns an orthonormal U also for a rank-deficient matrix; the one-sided Jacobi iteration leaves a ZERO left vector for
@@ -1020,8 +634,7 @@ __global__ __launch_bounds__(1024) void k_complete_left_basis(Mat<T> uc, const T
 
 template <typename T>
 void complete_left_basis(rc_context *c, Mat<T> uc, const T *s) {
-    static const bool on = [] { const char *e = getenv("RC_SVD_COMPLETE_BASIS"); return !e || atoi(e) != 0; }();  // experiments
-    if (!on || uc.rows == 0 || uc.rows != uc.cols || uc.rs != 1) return;
+    if (uc.rows == 0 || uc.rows != uc.cols || uc.rs != 1) return;
     const size_t lds = 2 * (size_t)uc.rows * sizeof(T);
     if (lds > 64 * 1024) return;  // (cores beyond 4096 x 4096 f64 keep the zero vectors)
     hipLaunchKernelGGL(k_complete_left_basis<T>, dim3(1), dim3(1024), lds, c->stream, uc, s);
@@ -1035,33 +648,23 @@ void jacobi_svd(rc_context *c, Mat<T> g, Mat<T> vwork, Mat<T> uc, T *s, Mat<T> v
     const int n = (int)g.rows;
     if (n == 0) return;
     ProfScope ps(c, "op:jacobi_svd n=%lld", (long long)g.rows);
-    static const int max_sweeps_env = [] { const char *e = getenv("RC_JACOBI_MAX_SWEEPS"); return e ? atoi(e) : 30; }();  // experiments only
-    const int max_sweeps = max_sweeps_env;
     // Column pitch in LDS.  A 32-lane half of a wave holds the groups of two neighbouring pair slots, whose columns are
     // neighbours too (p, p + 1 and q, q - 1): with a pitch of 16 elements modulo 32 the two 16-lane groups read opposite
     // halves of the bank row (ds_read_b64: 64 banks, f32 ds_read_b32: 32 banks) -- conflict-free, where the odd pitch n | 1
     // made every such read two-way conflicted.  The padded pitch is used whenever it fits the CU's LDS.
-    static const int pitch_env = [] { const char *e = getenv("RC_JACOBI_PITCH"); return e ? atoi(e) : 1; }();
     const size_t lds_cap = 160 * 1024 - 2048 - 64;
     auto lds_bytes = [&](int pitch) { return ((size_t)pitch * n + n) * sizeof(T) + (size_t)n * sizeof(int) + 64; };
-    static const int lpp = [] { const char *e = getenv("RC_JACOBI_LPP"); return e ? atoi(e) : 16; }();
-    int ld = lpp == 8 ? ((n + 23) / 32) * 32 + 8 : ((n + 15) / 32) * 32 + 16;  // 8 lanes per pair: four groups per half, a quarter row apart
-    if (!pitch_env || lds_bytes(ld) > lds_cap) ld = n | 1;
+    int ld = ((n + 15) / 32) * 32 + 16;
+    if (lds_bytes(ld) > lds_cap) ld = n | 1;
     const size_t lds = lds_bytes(ld);
-    if (lds <= lds_cap && n <= 192) {
-        if (lpp == 4) launch_lds_lpp<T, 4>(c, g, uc, s, vc, lds, ld, max_sweeps);
-        else if (lpp == 8) launch_lds_lpp<T, 8>(c, g, uc, s, vc, lds, ld, max_sweeps);
-        else launch_lds_lpp<T, 16>(c, g, uc, s, vc, lds, ld, max_sweeps);
-    } else {
-        jacobi_global<T>(c, g, vwork, uc, s, vc);
-    }
+    if (lds > lds_cap || n > 192) jacobi_global<T>(c, g, vwork, uc, s, vc);
+    else if (n <= 32) launch_lds<T, 2>(c, g, uc, s, vc, lds, ld);
+    else if (n <= 64) launch_lds<T, 4>(c, g, uc, s, vc, lds, ld);
+    else if (n <= 128) launch_lds<T, 8>(c, g, uc, s, vc, lds, ld);
+    else launch_lds<T, 12>(c, g, uc, s, vc, lds, ld);  // f32 up to n = 192 (the LDS bound is ~200)
 }
 
 template void jacobi_svd<double>(rc_context *, Mat<double>, Mat<double>, Mat<double>, double *, Mat<double>);
 template void jacobi_svd<float>(rc_context *, Mat<float>, Mat<float>, Mat<float>, float *, Mat<float>);
 
 }  // namespace rc
-
-#ifdef RC_JAC_TIMING
-extern "C" void rc_debug_jacobi_timing(unsigned long long *out) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(rc::g_jac_dbg), 8 * sizeof(unsigned long long)); }
-#endif

@@ -147,7 +147,6 @@ unsigned *rc_context::epoch_word() {
                                        (unsigned long long)getpid() * 0xff51afd7ed558ccdull;
         unsigned e0 = (unsigned)(mix >> 29) & 0x7fffffu;  // 23 bits: far from the 24-bit wrap
         if (e0 == 0) e0 = 1;
-        if (const char *dbg = getenv("RC_DEBUG_EPOCH0")) e0 = (unsigned)atoi(dbg);  // (diagnostic: 0 = the round-2 behaviour)
         RC_HIP(hipMemcpy(epoch, &e0, sizeof(unsigned), hipMemcpyHostToDevice));
     }
     return epoch;
@@ -183,8 +182,6 @@ void rc_context::release_all() {
     pinned = nullptr;
     if (sync_ev) (void)hipEventDestroy(sync_ev);
     sync_ev = nullptr;
-    for (auto &kv : qrb_graphs) (void)hipGraphExecDestroy(kv.second);
-    qrb_graphs.clear();
 }
 
 namespace {

@@ -110,8 +110,6 @@ struct rc_context {
     void swap_arena();
     int opt_fork = 0;  // 1: rc_rsvd_id runs its two branches side by side (lower latency; measured LOWER throughput with many graphs in flight)
     hipEvent_t sync_ev = nullptr;       // rc_synchronize_all: one completion event per context
-    // blocked QRCP: the ~65 launches of one panel replayed from a cached hipGraph (keyed by every baked-in pointer / size)
-    std::map<std::vector<uint64_t>, hipGraphExec_t> qrb_graphs;
     void *pinned = nullptr;             // small pinned host buffer for scalar read-backs
     size_t pinned_size = 0;
     int pinned_cursor = 0;              // next free QrbState slot of `pinned` for optimistic blocked-QRCP jobs (kernels_qrblk.hip)
