@@ -217,7 +217,8 @@ rc_status rc_matmat_f32(rc_context *ctx, rc_matrix a, rc_matrix x, rc_matrix y);
 rc_status rc_conj_matmat_f64(rc_context *ctx, rc_matrix a, rc_matrix x, rc_matrix y);
 rc_status rc_conj_matmat_f32(rc_context *ctx, rc_matrix a, rc_matrix x, rc_matrix y);
 /* ndarray `.dot` on two matrices (all call sites listed in SURVEY.md 2b N9):
- * C = alpha * op(A) op(B) + beta * C, op = transpose when the flag is non-zero. */
+ * C = alpha * op(A) op(B) + beta * C, op = transpose when the flag is non-zero.  BLAS semantics: beta = 0 writes C without
+ * reading it (NaN or Inf already in C does not propagate); K = 0 gives C = beta * C; a, b and c are any strided views. */
 rc_status rc_gemm_f64(rc_context *ctx, int32_t trans_a, int32_t trans_b, double alpha, rc_matrix a, rc_matrix b, double beta, rc_matrix c);
 rc_status rc_gemm_f32(rc_context *ctx, int32_t trans_a, int32_t trans_b, float alpha, rc_matrix a, rc_matrix b, float beta, rc_matrix c);
 /* RelDiff (src/types.rs:162-196): host scalar out, synchronous. */
@@ -519,7 +520,8 @@ rc_status rc_rsvd_id_row_sharded_f32(rc_comm *comm, rc_context *ctx, rc_matrix a
  * rc_matrix (strides in complex elements).  Same semantics as the real entry points with A^H wherever they have A^T:
  * conj_matmat is A^H X (src/types.rs:128-132), Q has orthonormal columns in the complex inner product, singular values
  * and norms are real (float / double arguments below), R has a real diagonal (?geqp3), permutation indices as before.
- * rc_gemm_*: trans = 0 none, 1 transpose, 2 conjugate transpose.  rc_random_gaussian_*: element (i, j) takes normals
+ * rc_gemm_*: trans = 0 none, 1 transpose, 2 conjugate transpose; complex alpha / beta with the real entry points' BLAS contract
+ * (beta = 0 never reads C, K = 0 gives C = beta * C).  rc_random_gaussian_*: element (i, j) takes normals
  * 2 (offset + i cols + j) (real part) and the next one (imaginary part) of the Philox stream, the order the reference
  * draws them in (src/random_matrix.rs:136-143).  rc_rsvd_id_c* / rc_batch_column_id_c* are compositions of the calls below with
  * the real entry points' members, layout and "null = skipped" rule (B = Q^H A formed once; not the tuned real hot path);

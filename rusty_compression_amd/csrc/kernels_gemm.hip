@@ -668,6 +668,16 @@ static void launch_vec(rc_context *c, const GemmArgs<T> &g) {
     else launch_shape<T, ALAY, BLAY, 1>(c, g);
 }
 
+// C = beta C (BLAS with an empty inner dimension; beta != 0 -- beta = 0 writes zeros and never reads C)
+template <typename T>
+__global__ __launch_bounds__(256) void k_scale_c(Mat<T> cm, T beta) {
+    const int64_t total = cm.rows * cm.cols;
+    for (int64_t e = blockIdx.x * (int64_t)256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        const int64_t j = e / cm.rows, i = e - j * cm.rows;
+        cm.at(i, j) = beta * cm.at(i, j);
+    }
+}
+
 template <typename T>
 void gemm(rc_context *c, T alpha, Mat<T> a, Mat<T> b, T beta, Mat<T> cm) {
     RC_REQUIRE(a.cols == b.rows && a.rows == cm.rows && b.cols == cm.cols, RC_INVALID_ARGUMENT,
@@ -675,9 +685,9 @@ void gemm(rc_context *c, T alpha, Mat<T> a, Mat<T> b, T beta, Mat<T> cm) {
                (long long)b.rows, (long long)b.cols, (long long)cm.rows, (long long)cm.cols);
     if (cm.empty()) return;
     ArenaMark mark(c);
-    if (a.cols == 0) {  // empty inner dimension: C = beta * C
-        RC_REQUIRE(beta == (T)0, RC_INVALID_ARGUMENT, "gemm: K == 0 with beta != 0 unsupported");
-        fill_zero(c, cm);
+    if (a.cols == 0) {  // empty inner dimension: C = beta * C (as BLAS; the complex path does the same)
+        if (beta == (T)0) fill_zero(c, cm);
+        else if (beta != (T)1) hipLaunchKernelGGL(k_scale_c<T>, dim3((unsigned)std::min<int64_t>(cdiv(cm.rows * cm.cols, 256), 8192)), dim3(256), 0, c->stream, cm, beta);
         return;
     }
     // operands whose neither stride is 1 are packed once (never on the hot path)

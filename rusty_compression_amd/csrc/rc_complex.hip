@@ -573,6 +573,87 @@ __global__ __launch_bounds__(256) void k_c_jacobi_emit(CV<R> g, CV<R> v, const R
     for (int64_t i = lane; i < g.rows; i += 64) uc.at(i, dst) = inv * g.at(i, j);
     for (int64_t i = lane; i < v.rows; i += 64) vc.at(i, dst) = v.at(i, j);
 }
+// ?gesdd returns orthonormal left vectors also for rank-deficient input; k_c_jacobi_emit leaves a ZERO column of uc for every zero
+// singular value.  Complex twin of k_complete_left_basis (kernels_svd.hip), same basis choice: for each zero column, the unit vector
+// with the largest component outside the span of the columns before it, orthogonalised twice against them (classical Gram-Schmidt
+// with conjugated inner products, one re-orthogonalisation) and normalised.  uc: M x n column-major, M >= n (the square core of the
+// QR-first branch or the tall uc of the direct one).  One workgroup; returns at once when the smallest singular value is positive
+// (the values are sorted), which is every full-rank call.
+template <typename R>
+__global__ __launch_bounds__(1024) void k_c_complete_left_basis(CV<R> uc, const R *s) {
+    extern __shared__ __attribute__((aligned(16))) char cb_raw[];
+    cplx<R> *v = reinterpret_cast<cplx<R> *>(cb_raw);  // M
+    cplx<R> *d = v + uc.rows;                             // n: projections
+    __shared__ R red_v[16];
+    __shared__ int red_i[16];
+    __shared__ int sh_p;
+    __shared__ R sh_nrm;
+    const int M = (int)uc.rows, n = (int)uc.cols, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (!(s[n - 1] == (R)0)) return;
+    int z = 0;  // number of positive singular values: columns z .. n-1 are the zero ones
+    for (int j = 0; j < n; ++j) z += s[j] > (R)0 ? 1 : 0;
+    for (int j = z; j < n; ++j) {
+        // residual of every unit vector: 1 - sum_c |U(p, c)|^2 over the columns before j
+        R best = (R)-1;
+        int bp = 0;
+        for (int p = tid; p < M; p += 1024) {
+            R acc = 1;
+            for (int c2 = 0; c2 < j; ++c2) acc -= abs2(uc.at(p, c2));
+            if (acc > best) { best = acc; bp = p; }
+        }
+        const R mx = wave_max_dpp(best);
+        const int cand = wave_min_dpp(best == mx ? bp : 0x7fffffff);
+        if (lane == 0) { red_v[wv] = mx; red_i[wv] = cand; }
+        __syncthreads();
+        if (tid == 0) {
+            R b = red_v[0];
+            int bi = red_i[0];
+            for (int w = 1; w < 16; ++w)
+                if (red_v[w] > b || (red_v[w] == b && red_i[w] < bi)) { b = red_v[w]; bi = red_i[w]; }
+            sh_p = bi;
+        }
+        __syncthreads();
+        const int p = sh_p;
+        for (int i = tid; i < M; i += 1024) v[i] = cplx<R>{i == p ? (R)1 : (R)0, (R)0};
+        __syncthreads();
+        for (int pass = 0; pass < 2; ++pass) {
+            for (int c2 = tid; c2 < j; c2 += 1024) {  // d = U(:, :j)^H v
+                cplx<R> acc{0, 0};
+                for (int i = 0; i < M; ++i) acc = acc + cj(uc.at(i, c2)) * v[i];
+                d[c2] = acc;
+            }
+            __syncthreads();
+            for (int i = tid; i < M; i += 1024) {  // v -= U(:, :j) d
+                cplx<R> acc = v[i];
+                for (int c2 = 0; c2 < j; ++c2) acc = acc - uc.at(i, c2) * d[c2];
+                v[i] = acc;
+            }
+            __syncthreads();
+        }
+        R part = 0;
+        for (int i = tid; i < M; i += 1024) part += abs2(v[i]);
+        part = wsumc(part);
+        if (lane == 0) red_v[wv] = part;
+        __syncthreads();
+        if (tid == 0) {
+            R t = 0;
+            for (int w = 0; w < 16; ++w) t += red_v[w];
+            sh_nrm = sqrt(t);
+        }
+        __syncthreads();
+        const R inv = (R)1 / sh_nrm;
+        for (int i = tid; i < M; i += 1024) uc.at(i, j) = inv * v[i];
+        __threadfence();
+        __syncthreads();
+    }
+}
+template <typename R>
+void c_complete_left_basis(rc_context *c, CV<R> uc, const R *s) {
+    if (uc.empty() || uc.rows < uc.cols || uc.rs != 1) return;
+    const size_t lds = (size_t)(uc.rows + uc.cols) * sizeof(cplx<R>);
+    if (lds > 64 * 1024) return;  // (cores beyond M + n = 4096 c64 keep the zero vectors, as the real kernel does)
+    hipLaunchKernelGGL(k_c_complete_left_basis<R>, dim3(1), dim3(1024), lds, c->stream, uc, s);
+}
 // thin SVD of the TALL column-major g (M x n, M >= n, destroyed): g = uc diag(s) vc^H
 template <typename R>
 void c_jacobi_svd_tall(rc_context *c, CV<R> g, CV<R> uc, R *s, CV<R> vc) {
@@ -600,6 +681,7 @@ void c_jacobi_svd_tall(rc_context *c, CV<R> g, CV<R> uc, R *s, CV<R> vc) {
     hipLaunchKernelGGL(k_c_jacobi_norms<R>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, g, sig);
     hipLaunchKernelGGL(k_c_jacobi_rank<R>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, n, sig, order, s);
     hipLaunchKernelGGL(k_c_jacobi_emit<R>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, g, v, sig, order, uc, vc);
+    c_complete_left_basis(c, uc, s);  // (?gesdd: the left vectors stay orthonormal when singular values are zero; no-op otherwise)
 }
 template <typename R>
 void c_colinv(rc_context *c, CV<R> in, const int64_t *ind, CV<R> out);
