@@ -94,7 +94,7 @@ using c32 = std::complex<float>;
 using c64 = std::complex<double>;
 
 template <typename T> struct Api;
-#define RC_API(T, SUF, RSUF, EXTRA)                                                                                          \
+#define RC_API(T, SUF, RSUF)                                                                                                 \
     template <> struct Api<T> {                                                                                     \
         static constexpr auto random_gaussian = rc_random_gaussian_##SUF;                                           \
         static constexpr auto matmat = rc_matmat_##SUF;                                                             \
@@ -125,17 +125,13 @@ template <typename T> struct Api;
         static constexpr auto sample_range_power_iteration = rc_sample_range_power_iteration_##SUF;                 \
         static constexpr auto sample_range_adaptive = rc_sample_range_adaptive_##SUF;                               \
         static constexpr auto column_id_rank = rc_column_id_rank_##SUF;                                             \
-        EXTRA                                                                                                       \
+        static constexpr auto column_id_rank_batched = rc_column_id_rank_batched_##SUF;                             \
+        static constexpr auto two_sided_id_rank_batched = rc_two_sided_id_rank_batched_##SUF;                       \
     };
-// the batched small-matrix column ID exists for real scalars only
-#define RC_API_REAL(SUF)                                                                                            \
-    static constexpr auto column_id_rank_batched = rc_column_id_rank_batched_##SUF;                                 \
-    static constexpr auto two_sided_id_rank_batched = rc_two_sided_id_rank_batched_##SUF;
-RC_API(double, f64, f64, RC_API_REAL(f64))
-RC_API(float, f32, f32, RC_API_REAL(f32))
-RC_API(c64, c64, f64, )
-RC_API(c32, c32, f32, )
-#undef RC_API_REAL
+RC_API(double, f64, f64)
+RC_API(float, f32, f32)
+RC_API(c64, c64, f64)
+RC_API(c32, c32, f32)
 #undef RC_API
 
 // ---- device-resident C-order arrays (the reference's Array2 / Array1<usize>) ----------------------

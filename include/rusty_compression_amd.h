@@ -453,9 +453,14 @@ rc_status rc_batch_column_id_f32(rc_context *const *ctxs, int32_t nctx, const rc
  * and Z = [I | R11^-1 R12] P^T for j < r; columns r..k-1 of C and rows r..k-1 of Z are zero.  Matrix i's bits depend on matrix
  * i alone.  Non-finite input stays inside its matrix's outputs (values unspecified, col_ind still a permutation, 0 <= r <= k).
  * Domain: 1 <= m, n <= 512, 1 <= k <= 128, 0 <= tol < 1, count >= 0 (0: nothing to do); RC_INVALID_ARGUMENT otherwise, for
- * wrong c / z shapes, and for an output batch stride smaller than one output view's span.  Workspace: bounded, not by count. */
+ * wrong c / z shapes, and for an output batch stride smaller than one output view's span.  Workspace: bounded, not by count.
+ * Complex scalars (c64, c32): the same signature, domain, layout, checks and contract with interleaved (re, im) data, strides and
+ * batch strides in complex elements; the pivots and the rank rule are on the real partial norms and the real R_jj of ?geqp3's
+ * complex Householder QR, and C[:, j] = A[:, ind[j]] bit for bit. */
 rc_status rc_column_id_rank_batched_f64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks);
 rc_status rc_column_id_rank_batched_f32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks);
+rc_status rc_column_id_rank_batched_c64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks);
+rc_status rc_column_id_rank_batched_c32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks);
 /* The two-sided ID A ~ C X R of the same batch (ColumnIDTraits::two_sided_id after the column ID, src/col_interp_decomp.rs:116-125)
  * in the same one stream-ordered, capturable call.  Domain, batch layout and checks as rc_column_id_rank_batched_*: k clamped to
  * min(m, n); c (m x k), x (k x k) and r (k x n) each moved by its own batch stride; row_ind (count x m), col_ind (count x n) and
@@ -470,9 +475,14 @@ rc_status rc_column_id_rank_batched_f32(rc_context *ctx, rc_matrix a, int64_t a_
  * gathered from A rather than re-formed as L Q; c x r reconstructs A (the reference TwoSidedID's c, x, r, row_ind, col_ind).
  * Matrix i's bits depend on matrix i alone.  Non-finite input stays inside its matrix's outputs (values unspecified, row_ind and
  * col_ind still permutations, 0 <= r <= k).  RC_INVALID_ARGUMENT for an out-of-domain argument, wrong c / x / r shapes, an output
- * batch stride smaller than one output view's span, or a null pointer.  Workspace: bounded, not by count. */
+ * batch stride smaller than one output view's span, or a null pointer.  Workspace: bounded, not by count.
+ * Complex scalars (c64, c32): the same signature, domain, layout, checks and contract; the row side factors C^H (the conjugate
+ * transpose, as rc_column_id_two_sided_c* does through its pivoted LQ of C) and c[:, :r] = Z2^H with Z2 the Z of C^H, so that
+ * c[row_ind[:r], :r] is still exactly the identity; x[:r, :r] = A[row_ind[:r], col_ind[:r]] bit for bit (not conjugated). */
 rc_status rc_two_sided_id_rank_batched_f64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix c, int64_t c_batch_stride, rc_matrix x, int64_t x_batch_stride, rc_matrix r, int64_t r_batch_stride, int64_t *row_ind, int64_t *col_ind, int64_t *ranks);
 rc_status rc_two_sided_id_rank_batched_f32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix c, int64_t c_batch_stride, rc_matrix x, int64_t x_batch_stride, rc_matrix r, int64_t r_batch_stride, int64_t *row_ind, int64_t *col_ind, int64_t *ranks);
+rc_status rc_two_sided_id_rank_batched_c64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix c, int64_t c_batch_stride, rc_matrix x, int64_t x_batch_stride, rc_matrix r, int64_t r_batch_stride, int64_t *row_ind, int64_t *col_ind, int64_t *ranks);
+rc_status rc_two_sided_id_rank_batched_c32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix c, int64_t c_batch_stride, rc_matrix x, int64_t x_batch_stride, rc_matrix r, int64_t r_batch_stride, int64_t *row_ind, int64_t *col_ind, int64_t *ranks);
 
 /* The gather over RCCL (xGMI inside a node).  One process per GPU: rank 0 calls rc_comm_unique_id and hands the 128
  * bytes to the other ranks by whatever means the host has (MPI, a file, torch.distributed), every rank calls

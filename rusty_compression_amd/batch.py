@@ -47,13 +47,14 @@ def column_id_rank(a: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor,
 def column_id_rank_batched(a: torch.Tensor, k: int, tol: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """Column IDs of `count` small same-shaped matrices in one stream-ordered call (rc_column_id_rank_batched_*).
 
-    a: [count, m, n] device tensor, any strides (1 <= m, n <= 512).  k (<= 128) is clamped to min(m, n); the rank of each matrix is
-    the first j < k with R_jj == 0 or |R_jj / R_00| < tol (tol = 0: fixed rank k).  Returns C [count, m, k], Z [count, k, n],
+    a: [count, m, n] device tensor of float64, float32, complex128 or complex64, any strides (1 <= m, n <= 512).  k (<= 128) is
+    clamped to min(m, n); the rank of each matrix is the first j < k with R_jj == 0 or |R_jj / R_00| < tol (tol = 0: fixed rank k),
+    with R_jj real also for complex data (?geqp3's complex Householder QR).  Returns C [count, m, k], Z [count, k, n] (a's dtype),
     ind [count, n] (full permutations, pivots first) and ranks [count]; columns / rows of C / Z past a matrix's rank are zero."""
     from . import _lib
     from .types import as_device
 
-    a = as_device(a)
+    a = as_device(a).resolve_conj()  # a lazily conjugated complex view is materialised: the kernels read the stored values
     if a.dim() != 3:
         raise AssertionError("expected a [count, m, n] batch")
     count, m, n = a.shape
@@ -76,13 +77,14 @@ def two_sided_id_rank_batched(a: torch.Tensor, k: int, tol: float = 0.0) -> Tupl
 
     a: [count, m, n] device tensor, any strides (1 <= m, n <= 512).  k (<= 128) is clamped to min(m, n); the rank r of each matrix is
     that of column_id_rank_batched (R_jj == 0 or |R_jj / R_00| < tol; tol = 0: fixed rank k), whose Z and ind are R and col_ind here
-    bit for bit.  The row side is the row ID of A[:, col_ind[:r]] (ColumnID::two_sided_id).  Returns C [count, m, k], X [count, k, k],
+    bit for bit.  The row side is the row ID of A[:, col_ind[:r]] (ColumnID::two_sided_id; for complex data the column ID of its
+    conjugate transpose, C = Z2^H).  Float64, float32, complex128 and complex64.  Returns C [count, m, k], X [count, k, k],
     R [count, k, n], row_ind [count, m], col_ind [count, n] (full permutations, pivots first) and ranks [count];
     X[:r, :r] = A[row_ind[:r]][:, col_ind[:r]], and the columns of C, rows of R and rows and columns of X past a matrix's rank are zero."""
     from . import _lib
     from .types import as_device
 
-    a = as_device(a)
+    a = as_device(a).resolve_conj()  # a lazily conjugated complex view is materialised: the kernels read the stored values
     if a.dim() != 3:
         raise AssertionError("expected a [count, m, n] batch")
     count, m, n = a.shape

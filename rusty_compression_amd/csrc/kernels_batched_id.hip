@@ -335,10 +335,10 @@ __global__ __launch_bounds__(BID_THREADS) void k_batched_two_sided(Mat<T> a, int
     }
 }
 
-constexpr size_t BID_MAX_LDS = 160 * 1024 - 1024;
+}  // namespace
 
 // persistent grid: the resident workgroups of every CU, fewer when the workspace (ws_per bytes per workgroup, 0 in the LDS variants)
-// would pass 256 MiB unless that leaves less than one workgroup per CU; never more than count
+// would pass 256 MiB unless that leaves less than one workgroup per CU; never more than count (shared with kernels_batched_id_c.hip)
 int64_t bid_grid(rc_context *c, const void *kern, size_t lds, size_t ws_per, int32_t count) {
     static int cus_of[64] = {};
     int &cus = cus_of[c->device & 63];
@@ -349,8 +349,6 @@ int64_t bid_grid(rc_context *c, const void *kern, size_t lds, size_t ws_per, int
     if (ws_per) grid = std::min<int64_t>(grid, std::max<int64_t>(cus, (int64_t)((size_t)256 << 20) / (int64_t)ws_per));
     return std::min<int64_t>(grid, count);
 }
-
-}  // namespace
 
 template <typename T>
 void batched_column_id(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int64_t k, double tol, Mat<T> cm, int64_t cbs, Mat<T> z, int64_t zbs,

@@ -1000,26 +1000,25 @@ void check_batch_stride(const char *who, const char *name, int64_t bs, const Mat
                (long long)bs, (long long)span);
 }
 
-// the same unit of work for many small same-shaped matrices in one launch, rank chosen per matrix by tol (0: fixed rank k)
-// without a host round trip; one path, stream-ordered, capturable
+}  // namespace
+
+// the argument checks of the batched calls, shared with the complex entry points (rc_complex.hip) through rc_common.hpp
+namespace rc {
 template <typename T>
-void column_id_rank_batched(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int64_t k, double tol, Mat<T> cm, int64_t cbs, Mat<T> z, int64_t zbs,
-                            int64_t *col_ind, int64_t *ranks) {
+int64_t check_column_id_rank_batched(Mat<T> a, int32_t count, int64_t k, double tol, Mat<T> cm, int64_t cbs, Mat<T> z, int64_t zbs,
+                                     const int64_t *col_ind, const int64_t *ranks) {
     const int64_t m = a.rows, n = a.cols;
     k = batched_domain("column_id_rank_batched", "rc_column_id_rank_* / rc_batch_column_id_*", a, count, k, tol);
     RC_REQUIRE(cm.rows == m && cm.cols == k && z.rows == k && z.cols == n, RC_INVALID_ARGUMENT,
                "column_id_rank_batched: c must be %lld x %lld and z %lld x %lld (k clamped to min(m, n))", (long long)m, (long long)k, (long long)k, (long long)n);
     check_batch_stride("column_id_rank_batched", "c", cbs, cm, count);
     check_batch_stride("column_id_rank_batched", "z", zbs, z, count);
-    if (count == 0) return;
-    RC_REQUIRE(a.p && cm.p && z.p && col_ind && ranks, RC_INVALID_ARGUMENT, "column_id_rank_batched: null pointer");
-    batched_column_id(c, a, abs, count, k, tol, cm, cbs, z, zbs, col_ind, ranks);
+    if (count > 0) RC_REQUIRE(a.p && cm.p && z.p && col_ind && ranks, RC_INVALID_ARGUMENT, "column_id_rank_batched: null pointer");
+    return k;
 }
-
-// the two-sided ID A ~ C X R of the same batch (ColumnID::two_sided_id after the column ID), in the same one launch
 template <typename T>
-void two_sided_id_rank_batched(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int64_t k, double tol, Mat<T> cm, int64_t cbs, Mat<T> x, int64_t xbs,
-                               Mat<T> r, int64_t rbs, int64_t *row_ind, int64_t *col_ind, int64_t *ranks) {
+int64_t check_two_sided_id_rank_batched(Mat<T> a, int32_t count, int64_t k, double tol, Mat<T> cm, int64_t cbs, Mat<T> x, int64_t xbs, Mat<T> r, int64_t rbs,
+                                        const int64_t *row_ind, const int64_t *col_ind, const int64_t *ranks) {
     const int64_t m = a.rows, n = a.cols;
     const char *who = "two_sided_id_rank_batched";
     k = batched_domain(who, "rc_column_id_rank_* + rc_column_id_two_sided_*", a, count, k, tol);
@@ -1029,8 +1028,38 @@ void two_sided_id_rank_batched(rc_context *c, Mat<T> a, int64_t abs, int32_t cou
     check_batch_stride(who, "c", cbs, cm, count);
     check_batch_stride(who, "x", xbs, x, count);
     check_batch_stride(who, "r", rbs, r, count);
+    if (count > 0) RC_REQUIRE(a.p && cm.p && x.p && r.p && row_ind && col_ind && ranks, RC_INVALID_ARGUMENT, "two_sided_id_rank_batched: null pointer");
+    return k;
+}
+template int64_t check_column_id_rank_batched<double>(Mat<double>, int32_t, int64_t, double, Mat<double>, int64_t, Mat<double>, int64_t, const int64_t *,
+                                                      const int64_t *);
+template int64_t check_column_id_rank_batched<float>(Mat<float>, int32_t, int64_t, double, Mat<float>, int64_t, Mat<float>, int64_t, const int64_t *,
+                                                     const int64_t *);
+template int64_t check_two_sided_id_rank_batched<double>(Mat<double>, int32_t, int64_t, double, Mat<double>, int64_t, Mat<double>, int64_t, Mat<double>,
+                                                         int64_t, const int64_t *, const int64_t *, const int64_t *);
+template int64_t check_two_sided_id_rank_batched<float>(Mat<float>, int32_t, int64_t, double, Mat<float>, int64_t, Mat<float>, int64_t, Mat<float>, int64_t,
+                                                        const int64_t *, const int64_t *, const int64_t *);
+
+}  // namespace rc
+
+namespace {
+
+// the same unit of work for many small same-shaped matrices in one launch, rank chosen per matrix by tol (0: fixed rank k)
+// without a host round trip; one path, stream-ordered, capturable
+template <typename T>
+void column_id_rank_batched(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int64_t k, double tol, Mat<T> cm, int64_t cbs, Mat<T> z, int64_t zbs,
+                            int64_t *col_ind, int64_t *ranks) {
+    k = check_column_id_rank_batched(a, count, k, tol, cm, cbs, z, zbs, col_ind, ranks);
     if (count == 0) return;
-    RC_REQUIRE(a.p && cm.p && x.p && r.p && row_ind && col_ind && ranks, RC_INVALID_ARGUMENT, "two_sided_id_rank_batched: null pointer");
+    batched_column_id(c, a, abs, count, k, tol, cm, cbs, z, zbs, col_ind, ranks);
+}
+
+// the two-sided ID A ~ C X R of the same batch (ColumnID::two_sided_id after the column ID), in the same one launch
+template <typename T>
+void two_sided_id_rank_batched(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int64_t k, double tol, Mat<T> cm, int64_t cbs, Mat<T> x, int64_t xbs,
+                               Mat<T> r, int64_t rbs, int64_t *row_ind, int64_t *col_ind, int64_t *ranks) {
+    k = check_two_sided_id_rank_batched(a, count, k, tol, cm, cbs, x, xbs, r, rbs, row_ind, col_ind, ranks);
+    if (count == 0) return;
     batched_two_sided_id(c, a, abs, count, k, tol, cm, cbs, x, xbs, r, rbs, row_ind, col_ind, ranks);
 }
 

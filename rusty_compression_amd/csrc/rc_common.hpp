@@ -209,6 +209,24 @@ template <typename T> void batched_column_id(rc_context *c, Mat<T> a, int64_t ab
 // i * xbs, i * zbs elements; row_ind count x m, col_ind count x n, ranks count (arguments checked by the caller)
 template <typename T> void batched_two_sided_id(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int64_t k, double tol, Mat<T> cm, int64_t cbs, Mat<T> x,
                                                 int64_t xbs, Mat<T> z, int64_t zbs, int64_t *row_ind, int64_t *col_ind, int64_t *ranks);
+// the complex twins (kernels_batched_id_c.hip), R = double (c64) or float (c32): the same layout with interleaved-complex views
+template <typename R> void batched_column_id_c(rc_context *c, const rc_matrix &a, int64_t abs, int32_t count, int64_t k, double tol, const rc_matrix &cm,
+                                               int64_t cbs, const rc_matrix &z, int64_t zbs, int64_t *col_ind, int64_t *ranks);
+template <typename R> void batched_two_sided_id_c(rc_context *c, const rc_matrix &a, int64_t abs, int32_t count, int64_t k, double tol, const rc_matrix &cm,
+                                                  int64_t cbs, const rc_matrix &x, int64_t xbs, const rc_matrix &z, int64_t zbs, int64_t *row_ind,
+                                                  int64_t *col_ind, int64_t *ranks);
+// the argument checks of rc_column_id_rank_batched_* / rc_two_sided_id_rank_batched_* (rc_api.hip), shared by every scalar type: the
+// views carry the shapes and strides (in elements of the scalar type), the pointers only their null-ness.  Return k clamped to
+// min(m, n); the caller returns when count == 0.
+template <typename T> int64_t check_column_id_rank_batched(Mat<T> a, int32_t count, int64_t k, double tol, Mat<T> cm, int64_t cbs, Mat<T> z, int64_t zbs,
+                                                           const int64_t *col_ind, const int64_t *ranks);
+template <typename T> int64_t check_two_sided_id_rank_batched(Mat<T> a, int32_t count, int64_t k, double tol, Mat<T> cm, int64_t cbs, Mat<T> x, int64_t xbs,
+                                                              Mat<T> r, int64_t rbs, const int64_t *row_ind, const int64_t *col_ind, const int64_t *ranks);
+// the batched kernels' dynamic-LDS cap and persistent grid (kernels_batched_id.hip): the resident workgroups of 256 threads on every
+// CU, fewer when the workspace (ws_per bytes per workgroup, 0 in the LDS variants) would pass 256 MiB unless that leaves less than
+// one workgroup per CU; never more than count
+constexpr size_t BID_MAX_LDS = 160 * 1024 - 1024;
+int64_t bid_grid(rc_context *c, const void *kern, size_t lds, size_t ws_per, int32_t count);
 void invert_perm(rc_context *c, const int64_t *perm, int64_t n, int64_t *inv);
 void fill_words(rc_context *c, void *p, size_t bytes, unsigned v);  // every 32-bit word of [p, p + bytes) = v, by a kernel on c->stream (no hipMemset*)
 void iota_i64(rc_context *c, int64_t *p, int64_t n);

@@ -67,6 +67,9 @@ struct CV {
 };
 template <typename R>
 CV<R> view_of(const rc_matrix &m) { return CV<R>{static_cast<cplx<R> *>(m.data), m.rows, m.cols, m.row_stride, m.col_stride}; }
+// the shape, strides and null-ness of a complex operand as the real-typed view the shared argument checks take (never dereferenced)
+template <typename R>
+Mat<R> shape_of(const rc_matrix &m) { return Mat<R>(static_cast<R *>(m.data), m.rows, m.cols, m.row_stride, m.col_stride); }
 template <typename R>
 CV<R> tmp_cm(rc_context *c, int64_t rows, int64_t cols) {
     const int64_t ld = std::max<int64_t>(rows, 1);
@@ -1340,6 +1343,29 @@ extern "C" {
     rc_status rc_batch_column_id_##SUF(rc_context *const *ctxs, int32_t nctx, const rc_matrix *mats, int32_t count, int64_t k, void *packed) { \
         if (!ctxs || nctx < 1 || !ctxs[0]) return RC_INVALID_ARGUMENT;                                                                    \
         return guarded_c(ctxs[0], [&] { c_batch_column_id<R>(ctxs, nctx, mats, count, k, packed); });                                     \
+    }                                                                                                                                     \
+    /* many small complex matrices in one launch (kernels_batched_id_c.hip); the checks of the real entry points on views of the */      \
+    /* same shapes and strides (in complex elements) */                                                                                   \
+    rc_status rc_column_id_rank_batched_##SUF(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, \
+                                              rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind,  \
+                                              int64_t *ranks) {                                                                           \
+        return guarded_c(ctx, [&] {                                                                                                       \
+            k = check_column_id_rank_batched<R>(shape_of<R>(a), count, k, tol, shape_of<R>(c), c_batch_stride, shape_of<R>(z), z_batch_stride, \
+                                                col_ind, ranks);                                                                          \
+            if (count == 0) return;                                                                                                       \
+            batched_column_id_c<R>(ctx, a, a_batch_stride, count, k, tol, c, c_batch_stride, z, z_batch_stride, col_ind, ranks);          \
+        });                                                                                                                               \
+    }                                                                                                                                     \
+    rc_status rc_two_sided_id_rank_batched_##SUF(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, \
+                                                 rc_matrix c, int64_t c_batch_stride, rc_matrix x, int64_t x_batch_stride, rc_matrix r,     \
+                                                 int64_t r_batch_stride, int64_t *row_ind, int64_t *col_ind, int64_t *ranks) {              \
+        return guarded_c(ctx, [&] {                                                                                                       \
+            k = check_two_sided_id_rank_batched<R>(shape_of<R>(a), count, k, tol, shape_of<R>(c), c_batch_stride, shape_of<R>(x),         \
+                                                   x_batch_stride, shape_of<R>(r), r_batch_stride, row_ind, col_ind, ranks);              \
+            if (count == 0) return;                                                                                                       \
+            batched_two_sided_id_c<R>(ctx, a, a_batch_stride, count, k, tol, c, c_batch_stride, x, x_batch_stride, r, r_batch_stride,     \
+                                      row_ind, col_ind, ranks);                                                                           \
+        });                                                                                                                               \
     }
 
 RC_DEFINE_COMPLEX(c64, double, rc_complex64)
