@@ -483,6 +483,23 @@ rc_status rc_two_sided_id_rank_batched_f64(rc_context *ctx, rc_matrix a, int64_t
 rc_status rc_two_sided_id_rank_batched_f32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix c, int64_t c_batch_stride, rc_matrix x, int64_t x_batch_stride, rc_matrix r, int64_t r_batch_stride, int64_t *row_ind, int64_t *col_ind, int64_t *ranks);
 rc_status rc_two_sided_id_rank_batched_c64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix c, int64_t c_batch_stride, rc_matrix x, int64_t x_batch_stride, rc_matrix r, int64_t r_batch_stride, int64_t *row_ind, int64_t *col_ind, int64_t *ranks);
 rc_status rc_two_sided_id_rank_batched_c32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix c, int64_t c_batch_stride, rc_matrix x, int64_t x_batch_stride, rc_matrix r, int64_t r_batch_stride, int64_t *row_ind, int64_t *col_ind, int64_t *ranks);
+/* Truncated SVDs of the same kind of batch (SVD::compute_from followed by compress, src/compute_svd.rs:18-27, src/svd.rs:60-101) in
+ * one stream-ordered, capturable call.  Batch layout as rc_column_id_rank_batched_*: matrix i is `a` moved by i * a_batch_stride
+ * elements (0 is legal); u (m x k) and vt (k x n) each moved by its own batch stride; s (count x p, p = min(m, n)) and ranks (count)
+ * contiguous; every pointer a device pointer.  Domain: 1 <= m, n <= 512, min(m, n) <= 128, 1 <= k <= 128 (clamped to p),
+ * 0 <= tol < 1, count >= 0 (0: nothing to do); RC_INVALID_ARGUMENT otherwise, for wrong u / vt shapes, an output batch stride
+ * smaller than one output view's span, or a null pointer.  Workspace: bounded, not by count.
+ * s[i, :] holds all p singular values of matrix i in descending order (the discarded tail is the truncation error).  Rank r = the
+ * first j < k with s_j == 0 or (tol > 0 and s_j / s_0 < tol), else k: tol = 0 is compress_svd_rank(k), a matrix of lower exact rank
+ * stops at it, an all-zero matrix has rank 0, and where compress_svd_tolerance raises CompressionError the rank is k (no per-matrix
+ * error).  ranks[i] = r; u[:, :r], s[:r], vt[:r, :] are the leading singular triplets; columns r..k-1 of u and rows r..k-1 of vt are
+ * zero.  Signs: the largest-|.| entry of each kept column of u is positive (the first such on a tie), the matching row of vt follows
+ * it (?gesdd leaves them open).  Matrix i's bits depend on matrix i alone: not on count, the neighbours, the input or output
+ * strides, or graph replay against an eager call.  Non-finite input stays inside its matrix's outputs (values unspecified,
+ * 0 <= r <= k).  A matrix whose Jacobi iteration uses up its sweep budget ORs bit 16 into the health word.  Per matrix: pivoted
+ * Householder QR to the p x p factor, one-sided Jacobi on it, U = Q [U_R; 0]; not bit-equal to rc_compute_svd_*, whose QR differs. */
+rc_status rc_svd_rank_batched_f64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix u, int64_t u_batch_stride, double *s, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks);
+rc_status rc_svd_rank_batched_f32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix u, int64_t u_batch_stride, float *s, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks);
 
 /* The gather over RCCL (xGMI inside a node).  One process per GPU: rank 0 calls rc_comm_unique_id and hands the 128
  * bytes to the other ranks by whatever means the host has (MPI, a file, torch.distributed), every rank calls

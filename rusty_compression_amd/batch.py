@@ -104,6 +104,36 @@ def two_sided_id_rank_batched(a: torch.Tensor, k: int, tol: float = 0.0) -> Tupl
     return c, x, r, row_ind, col_ind, ranks
 
 
+def svd_rank_batched(a: torch.Tensor, k: int, tol: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Truncated SVDs of `count` small same-shaped matrices in one stream-ordered call (rc_svd_rank_batched_*).
+
+    a: [count, m, n] device tensor of float64 or float32, any strides (1 <= m, n <= 512, min(m, n) <= 128).  k (<= 128) is clamped to
+    p = min(m, n); the rank of each matrix is the first j < k with s_j == 0 or s_j / s_0 < tol (tol = 0: fixed rank k).  Returns
+    U [count, m, k], S [count, p] (all singular values, descending), Vt [count, k, n] and ranks [count]; the columns of U and rows of
+    Vt past a matrix's rank are zero, and the largest-|.| entry of each kept column of U is positive."""
+    from . import _lib
+    from .types import as_device
+
+    a = as_device(a)
+    if a.dim() != 3:
+        raise AssertionError("expected a [count, m, n] batch")
+    if a.dtype not in (torch.float64, torch.float32):
+        raise TypeError(f"svd_rank_batched: float64 or float32 data expected, got {a.dtype}")
+    count, m, n = a.shape
+    p = min(m, n)
+    kk = min(int(k), p)
+    u = torch.empty((count, m, kk), dtype=a.dtype, device=a.device)
+    s = torch.empty((count, p), dtype=a.dtype, device=a.device)
+    vt = torch.empty((count, kk, n), dtype=a.dtype, device=a.device)
+    ranks = torch.empty(count, dtype=torch.int64, device=a.device)
+    view = _lib.rc_matrix(a.data_ptr(), m, n, a.stride(1), a.stride(2))
+    _lib.default_context().call(f"rc_svd_rank_batched_{_lib.suffix(a.dtype)}", view, ctypes.c_int64(a.stride(0)), ctypes.c_int32(count),
+                                ctypes.c_int64(int(k)), ctypes.c_double(float(tol)), _lib.mat(u[0] if count else u.new_empty(m, kk)),
+                                ctypes.c_int64(m * kk), ctypes.c_void_p(s.data_ptr()), _lib.mat(vt[0] if count else vt.new_empty(kk, n)),
+                                ctypes.c_int64(kk * n), _lib.i64p(ranks))
+    return u, s, vt, ranks
+
+
 def packed_bytes(m: int, n: int, k: int, elem_size: int) -> int:
     """Bytes one matrix's factors take in the packed buffer: C (m x k) | Z (k x n) | pad to 8 | col_ind (n int64)
     (rc_batch_packed_bytes)."""

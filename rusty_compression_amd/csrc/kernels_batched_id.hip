@@ -16,6 +16,9 @@
 // Batched two-sided ID (rc_two_sided_id_rank_batched_*): the same workgroup then takes the row ID of C = A[:, col_ind[:r]] as the
 // column ID of C^T (reference ColumnID::two_sided_id, src/col_interp_decomp.rs:116-125: an LQ of C, then row_id()), through the
 // same three device stages (load + norms, pivoted QR with the stopping rule, Z back substitution).
+//
+// Batched truncated SVD (rc_svd_rank_batched_*): k_batched_svd, the same grid and the same first two stages run to all N steps,
+// then one-sided Jacobi on the transposed triangular factor and U formed from the kept reflectors (see its comment below).
 #include "rc_common.hpp"
 #include "rc_device.hpp"
 
@@ -126,10 +129,13 @@ __device__ __forceinline__ void bid_load(T *W, int ldw, int m, int n, bool lanes
 
 // truncated pivoted QR of the working copy, at most k steps: pivots in jp (?geqp3's rule), R and the Householder vectors in W (LAPACK
 // format, physical column order).  Returns the rank: the first j < k with R_jj == 0 or (tol > 0 and |R_jj / R_00| < tol), else k.
-template <typename T>
-__device__ __forceinline__ int bid_qrcp(T *W, int ldw, int m, int n, int k, double tol, int *jp, T *vn1, T *vn2, T *red, int tid, int wv, int lane) {
+// FULL (the batched SVD): no stopping rule, all k steps are taken (an exactly zero pivot column is a step with H = I) and tau_j goes
+// to taus[j]; returns k.
+template <typename T, bool FULL = false>
+__device__ __forceinline__ int bid_qrcp(T *W, int ldw, int m, int n, int k, double tol, int *jp, T *vn1, T *vn2, T *red, int tid, int wv, int lane,
+                                        T *taus = nullptr) {
     int r = k;
-    T r00 = 0;
+    [[maybe_unused]] T r00 = 0;
     for (int j = 0; j < k; ++j) {
         if (wv == 0) {  // pivot: first maximum of the partial norms; NaN never wins (v > best), no valid index -> j
             T best = (T)-1;
@@ -165,9 +171,13 @@ __device__ __forceinline__ int bid_qrcp(T *W, int ldw, int m, int n, int k, doub
             tj = (beta - alpha) / beta;
             if (tid == 0) col[j] = beta;
         }
-        // R_jj = beta decides the rank (qr.rs:187-200 as a ratio; uniform across the workgroup)
-        if (j == 0) r00 = beta;
-        if (beta == (T)0 || (tol > 0.0 && (double)fabs(beta / r00) < tol)) { r = j; break; }
+        if constexpr (FULL) {
+            if (tid == 0) taus[j] = tj;
+        } else {
+            // R_jj = beta decides the rank (qr.rs:187-200 as a ratio; uniform across the workgroup)
+            if (j == 0) r00 = beta;
+            if (beta == (T)0 || (tol > 0.0 && (double)fabs(beta / r00) < tol)) { r = j; break; }
+        }
         __syncthreads();
         if (j + 1 < n) {
             const int rem = m - j;
@@ -335,6 +345,269 @@ __global__ __launch_bounds__(BID_THREADS) void k_batched_two_sided(Mat<T> a, int
     }
 }
 
+// ---- batched truncated SVD (rc_svd_rank_batched_*) -----------------------------------------------------------------------------
+// Per matrix, in the tall orientation M x N (N = min(m, n); a wide matrix is read through its transposed view): the pivoted QR of
+// bid_qrcp run to N steps (W P = Q R, reflectors kept), one-sided Jacobi on the N x N core G = R^T with the rotations accumulated
+// in J (R^T J = V_R Sigma, so J = U_R), singular values = the column norms of G, then U = Q [J_k; 0] with the k kept columns in
+// registers and V_R = G Sigma^-1, whose rows the pivoted QR permutes: V_W[jp[i], :] = V_R[i, :].  Jacobi on R^T, the rows of the
+// pivoted R, rather than on its columns: R's rows are graded by the pivoting, R^T's columns are then nearly orthogonal and the
+// sweeps converge in a few rounds (Drmac & Veselic's preconditioning); on R's columns the 128 x 128 bench matrices used up the
+// 30-sweep budget.  Everything stays inside one workgroup.
+
+// Jacobi rows per lane of a 16-lane pair group (N <= 16 NE) and rows per lane of a 64-lane U column (M <= 64 NE)
+template <typename T, int NE>
+__device__ __forceinline__ void bsv_round(T *G, int ldg, T *J, int ldj, int N, int p, int q, T tol, T tol2, int ll, int *flag) {
+    T *gp = G + (size_t)p * ldg, *gq = G + (size_t)q * ldg;
+    T a[NE], b[NE];
+    T app = 0, aqq = 0, apq = 0;
+#pragma unroll
+    for (int e = 0; e < NE; ++e) {
+        const int i = ll + 16 * e;
+        a[e] = i < N ? gp[i] : (T)0;
+        b[e] = i < N ? gq[i] : (T)0;
+        app = fma(a[e], a[e], app);
+        aqq = fma(b[e], b[e], aqq);
+        apq = fma(a[e], b[e], apq);
+    }
+    app = group_sum_dpp<16>(app);
+    aqq = group_sum_dpp<16>(aqq);
+    apq = group_sum_dpp<16>(apq);
+    // k_jacobi_lds's test and thresholds: rotate iff |apq| > tol sqrt(app aqq) (uniform over the 16 lanes)
+    if (!(apq * apq > tol2 * app * aqq)) return;
+    T c, s;
+    jacobi_rotation(app, aqq, apq, c, s);
+    T *vp = J + (size_t)p * ldj, *vq = J + (size_t)q * ldj;
+#pragma unroll
+    for (int e = 0; e < NE; ++e) {
+        const int i = ll + 16 * e;
+        if (i < N) {
+            gp[i] = c * a[e] - s * b[e];
+            gq[i] = s * a[e] + c * b[e];
+            const T x = vp[i], y = vq[i];
+            vp[i] = c * x - s * y;
+            vq[i] = s * x + c * y;
+        }
+    }
+    if (ll == 0 && (apq * apq > tol * (T)0.0625 * app * aqq || s * s > (T)16 * tol)) *flag = 2;  // plain store: every writer writes 2
+}
+
+// one-sided Jacobi of the N x N core G (columns ldg apart) with the rotations accumulated in J (ldj); round-robin pairs, 16 lanes per pair, the 16
+// groups of the workgroup walk the N / 2 pair slots of a round.  Returns false when kMaxSweeps ran out before a quiet sweep.
+template <typename T, int NE>
+__device__ __forceinline__ bool bsv_jacobi(T *G, int ldg, T *J, int ldj, int N, int tid, int *flag) {
+    const int ll = tid & 15, grp = tid >> 4;
+    constexpr int NGRP = BID_THREADS / 16;
+    const int N2 = (N + 1) & ~1, npairs = N2 / 2;
+    const T tol = sqrt((T)N) * JEps<T>::eps(), tol2 = tol * tol;
+    for (int sweep = 0; sweep < kMaxSweeps; ++sweep) {
+        if (tid == 0) *flag = 0;
+        __syncthreads();
+        for (int r = 0; r < N2 - 1; ++r) {
+            for (int pi = grp; pi < npairs; pi += NGRP) {
+                int p, q;
+                rr_pair(N2, r, pi, p, q);
+                if (q < N) bsv_round<T, NE>(G, ldg, J, ldj, N, p, q, tol, tol2, ll, flag);  // q == N: the dummy column of an odd N
+            }
+            __syncthreads();  // the pairs of a round are disjoint; the next round re-pairs the columns
+        }
+        const int rotated = *flag;
+        __syncthreads();
+        if (rotated < 2) return true;
+    }
+    return false;
+}
+
+// sign of a column held by one wave (value x[e] at output row orow(e)): -1 when its largest-|.| entry (the first such in output row
+// order) is negative, else +1 (also when every entry is NaN)
+template <typename T, int NE, typename Row>
+__device__ __forceinline__ int bsv_sign(const T (&x)[NE], Row orow) {
+    T mx = 0;
+#pragma unroll
+    for (int e = 0; e < NE; ++e) mx = max(mx, fabs(x[e]));
+    mx = wave_max_dpp(mx);
+    int key = 0x7fffffff;
+#pragma unroll
+    for (int e = 0; e < NE; ++e) {
+        const int o = orow(e);
+        if (o >= 0 && fabs(x[e]) == mx) key = min(key, 2 * o + (x[e] < (T)0 ? 1 : 0));
+    }
+    key = wave_min_dpp(key);
+    return (key != 0x7fffffff && (key & 1)) ? -1 : 1;
+}
+
+// U[:, c] = sgn[c] Q [J[:, srt[c]]; 0] for the kept columns c < r (zero for r <= c < k): one wave per column, the M rows in
+// registers (row lane + 64 e), the N reflectors applied backward, H_j = I - tau_j v_j v_j^T with v_j in W's column jp[j] below row j
+template <typename T, int NE>
+__device__ __forceinline__ void bsv_form_u(const T *W, int ldw, const T *J, int ldj, int M, int N, int k, int r, const int *jp, const T *taus,
+                                           const int *srt, int *sgn, bool sign_here, T *U, int64_t urs, int64_t ucs, int wv, int lane) {
+    for (int c = wv; c < k; c += BID_WAVES) {
+        T *uc = U + (int64_t)c * ucs;
+        if (c >= r) {
+            for (int i = lane; i < M; i += 64) uc[i * urs] = (T)0;
+            continue;
+        }
+        const T *jc = J + (size_t)srt[c] * ldj;
+        T x[NE];
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            const int i = lane + 64 * e;
+            x[e] = i < N ? jc[i] : (T)0;
+        }
+        for (int j = N - 1; j >= 0; --j) {
+            const T tau = taus[j];
+            if (tau == (T)0) continue;  // H_j = I (uniform)
+            const T *vc = W + (size_t)jp[j] * ldw;
+            T v[NE];
+            T dot = 0;
+#pragma unroll
+            for (int e = 0; e < NE; ++e) {
+                const int i = lane + 64 * e;
+                const T vv = vc[i < M ? i : j];  // branch-free: lanes out of range read row j and are masked below
+                v[e] = i > j && i < M ? vv : (i == j ? (T)1 : (T)0);
+                dot = fma(v[e], x[e], dot);
+            }
+            const T f = tau * wave_sum_dpp(dot);
+#pragma unroll
+            for (int e = 0; e < NE; ++e) x[e] = fma(-f, v[e], x[e]);
+        }
+        if (sign_here) {
+            const int s = bsv_sign<T, NE>(x, [&](int e) { const int i = lane + 64 * e; return i < M ? i : -1; });
+            if (lane == 0) sgn[c] = s;
+#pragma unroll
+            for (int e = 0; e < NE; ++e) x[e] = s < 0 ? -x[e] : x[e];
+        } else if (sgn[c] < 0) {
+#pragma unroll
+            for (int e = 0; e < NE; ++e) x[e] = -x[e];
+        }
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            const int i = lane + 64 * e;
+            if (i < M) uc[i * urs] = x[e];
+        }
+    }
+}
+
+// LDS of k_batched_svd: [W: N x (M|1), W_LDS only] G: N x ldg [J: N x ldg, V_LDS only] vn1[N] vn2[N] taus[N] sig[N] red[8]
+// | jp[N] srt[N] sgn[128] flag[4] (ints last: the T arrays stay aligned)
+template <typename T>
+size_t bsv_lds_bytes(int M, int N, int ldg, bool w_lds, bool v_lds) {
+    size_t t = (size_t)N * ldg + 4 * (size_t)N + 8;
+    if (w_lds) t += (size_t)N * (size_t)(M | 1);
+    if (v_lds) t += (size_t)N * ldg;
+    return t * sizeof(T) + (size_t)(2 * N + 128 + 4) * sizeof(int);
+}
+
+// a: m x n input view; uo (M x k) and vo (k x N) are the views the work orientation's U and V^T go to (u and vt for a tall matrix,
+// vt^T and u^T for a wide one), each moved by its own batch stride; s (count x N) and ranks contiguous.  W_LDS / V_LDS: the working
+// copy W / the rotations J (the singular vectors of R) live in LDS, else in the workgroup's workspace slot; the core G is in LDS.
+template <typename T, bool W_LDS, bool V_LDS>
+__global__ __launch_bounds__(BID_THREADS) void k_batched_svd(Mat<T> a, int64_t abs, int count, int k, double tol, Mat<T> uo, int64_t ubs, Mat<T> vo, int64_t vbs,
+                                                             T *__restrict__ s_out, int64_t *__restrict__ ranks, T *__restrict__ ws, int *health, int ldg) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const bool wide = a.rows < a.cols;
+    const int M = (int)(wide ? a.cols : a.rows), N = (int)(wide ? a.rows : a.cols);
+    const int ldw = W_LDS ? (M | 1) : M, ldj = V_LDS ? ldg : N;
+    T *lds = reinterpret_cast<T *>(smem_raw);
+    T *wsb = ws + (size_t)blockIdx.x * ((W_LDS ? 0 : (size_t)M * N) + (V_LDS ? 0 : (size_t)N * N));
+    T *W = W_LDS ? lds : wsb;
+    T *G = lds + (W_LDS ? (size_t)N * ldw : 0);
+    T *J = V_LDS ? G + (size_t)N * ldg : wsb + (W_LDS ? 0 : (size_t)M * N);
+    T *vn1 = G + (size_t)N * ldg + (V_LDS ? (size_t)N * ldg : 0);
+    T *vn2 = vn1 + N, *taus = vn2 + N, *sig = taus + N, *red = sig + N;
+    int *jp = reinterpret_cast<int *>(red + 8);
+    int *srt = jp + N, *sgn = srt + N, *flag = sgn + 128;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    // the input in the work orientation and its fast direction
+    const int64_t ars = wide ? a.cs : a.rs, acs = wide ? a.rs : a.cs;
+
+    for (int b = blockIdx.x; b < count; b += gridDim.x) {
+        const T *__restrict__ A = a.p + (int64_t)b * abs;
+        // ---- QR: W P = Q R, all N steps (exact zero pivots are steps with H = I), taus kept -------------------------------------
+        bid_load(W, ldw, M, N, ars <= acs, [&](int i, int c) { return A[i * ars + c * acs]; }, vn1, vn2, jp, wv, lane);
+        bid_qrcp<T, true>(W, ldw, M, N, N, 0.0, jp, vn1, vn2, red, tid, wv, lane, taus);
+        // ---- core G = R^T (R in pivoted column order: G[:, j] = row j of R) and J = I ------------------------------------------
+        for (int j = wv; j < N; j += BID_WAVES) {
+            for (int i = lane; i < N; i += 64) {
+                G[(size_t)j * ldg + i] = i >= j ? W[(size_t)jp[i] * ldw + j] : (T)0;
+                J[(size_t)j * ldj + i] = i == j ? (T)1 : (T)0;
+            }
+        }
+        __syncthreads();
+        bool conv;
+        if (N <= 16) conv = bsv_jacobi<T, 1>(G, ldg, J, ldj, N, tid, flag);
+        else if (N <= 32) conv = bsv_jacobi<T, 2>(G, ldg, J, ldj, N, tid, flag);
+        else if (N <= 64) conv = bsv_jacobi<T, 4>(G, ldg, J, ldj, N, tid, flag);
+        else conv = bsv_jacobi<T, 8>(G, ldg, J, ldj, N, tid, flag);
+        if (!conv && tid == 0) atomicOr(health, 16);  // the sweep budget ran out: bit 16, as the lone Jacobi reports it
+        // ---- singular values: column norms, sorted descending (a strict total order: NaN last, ties by column) ----------------------
+        for (int j = tid >> 4; j < N; j += BID_THREADS / 16) {
+            const T *gj = G + (size_t)j * ldg;
+            T acc = 0;
+            for (int i = tid & 15; i < N; i += 16) acc = fma(gj[i], gj[i], acc);
+            acc = group_sum_dpp<16>(acc);
+            if ((tid & 15) == 0) sig[j] = sqrt(acc);
+        }
+        __syncthreads();
+        T *sb = s_out + (int64_t)b * N;
+        for (int i = tid; i < N; i += BID_THREADS) {
+            const T ki = sig[i] >= (T)0 ? sig[i] : (T)-1;
+            int pos = 0;
+            for (int j = 0; j < N; ++j) {
+                const T kj = sig[j] >= (T)0 ? sig[j] : (T)-1;
+                pos += (kj > ki || (kj == ki && j < i)) ? 1 : 0;
+            }
+            srt[pos] = i;
+            sb[pos] = sig[i];
+        }
+        __syncthreads();
+        // ---- rank: the first j < k with s_j == 0 or (tol > 0 and s_j / s_0 < tol), else k ---------------------------------------
+        if (tid == 0) {
+            const T s0 = sig[srt[0]];
+            int r = k;
+            for (int j = 0; j < k; ++j) {
+                const T sj = sig[srt[j]];
+                if (sj == (T)0 || (tol > 0.0 && (double)(sj / s0) < tol)) { r = j; break; }
+            }
+            flag[1] = r;
+            ranks[b] = r;
+        }
+        __syncthreads();
+        const int r = flag[1];
+        // ---- signs: the largest-|.| entry of each kept column of the caller's u is positive --------------------------------------
+        // (a wide matrix's u is V = G Sigma^-1: its signs are fixed here, before U is formed; a tall one's in bsv_form_u)
+        if (wide) {
+            for (int c = wv; c < r; c += BID_WAVES) {
+                const T *gc = G + (size_t)srt[c] * ldg;
+                const T sj = sig[srt[c]], inv = sj > (T)0 ? (T)1 / sj : (T)0;
+                T x[2];
+                for (int e = 0; e < 2; ++e) {
+                    const int i = lane + 64 * e;
+                    x[e] = i < N ? gc[i] * inv : (T)0;
+                }
+                const int sg = bsv_sign<T, 2>(x, [&](int e) { const int i = lane + 64 * e; return i < N ? jp[i] : -1; });
+                if (lane == 0) sgn[c] = sg;
+            }
+            __syncthreads();
+        }
+        // ---- U = Q [J_k; 0] straight into the output view -------------------------------------------------------------------------
+        T *Ub = uo.p + (int64_t)b * ubs;
+        if (M <= 64) bsv_form_u<T, 1>(W, ldw, J, ldj, M, N, k, r, jp, taus, srt, sgn, !wide, Ub, uo.rs, uo.cs, wv, lane);
+        else if (M <= 128) bsv_form_u<T, 2>(W, ldw, J, ldj, M, N, k, r, jp, taus, srt, sgn, !wide, Ub, uo.rs, uo.cs, wv, lane);
+        else if (M <= 256) bsv_form_u<T, 4>(W, ldw, J, ldj, M, N, k, r, jp, taus, srt, sgn, !wide, Ub, uo.rs, uo.cs, wv, lane);
+        else bsv_form_u<T, 8>(W, ldw, J, ldj, M, N, k, r, jp, taus, srt, sgn, !wide, Ub, uo.rs, uo.cs, wv, lane);
+        __syncthreads();  // sgn of a tall matrix is written above
+        // ---- V^T: row c of vo is sgn[c] V_W[:, c], V_W[jp[i], c] = V_R[i, c] = G[i, srt[c]] / s_c; rows r..k-1 zero ---------------
+        T *Vb = vo.p + (int64_t)b * vbs;
+        for (int c = wv; c < k; c += BID_WAVES) {
+            const int j0 = c < r ? srt[c] : 0;
+            const T *gc = G + (size_t)j0 * ldg;
+            const T sj = sig[j0], inv = c < r && sj > (T)0 ? (sgn[c] < 0 ? (T)-1 : (T)1) / sj : (T)0;
+            for (int i = lane; i < N; i += 64) Vb[c * vo.rs + (int64_t)jp[i] * vo.cs] = gc[i] * inv;
+        }
+        __syncthreads();  // W, G, J and the small arrays are rewritten by the next matrix
+    }
+}
+
 }  // namespace
 
 // persistent grid: the resident workgroups of every CU, fewer when the workspace (ws_per bytes per workgroup, 0 in the LDS variants)
@@ -396,11 +669,52 @@ void batched_two_sided_id(rc_context *c, Mat<T> a, int64_t abs, int32_t count, i
                        col_ind, ranks, ws);
 }
 
+// where the working copy W (M x N) and V (N x N) live: in LDS when they fit next to the core (W only with V), otherwise in
+// workgroup blockIdx.x's slot of the grid-bounded workspace; the core G always fits (N <= 128: 128 KiB in f64).  The core's column
+// pitch is k_jacobi_lds's conflict-free one (16 modulo 32 elements) whenever the plan fits with it, else N | 1.
+template <typename T>
+void batched_svd(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs, T *s, Mat<T> vt, int64_t vbs,
+                 int64_t *ranks) {
+    const int m = (int)a.rows, n = (int)a.cols;
+    if (count <= 0) return;
+    ProfScope ps(c, "op:batched_svd %dx%d k=%lld count=%d", m, n, (long long)k, (int)count);
+    const bool wide = m < n;
+    const int M = wide ? n : m, N = wide ? m : n;
+    // the first plan that fits: most in LDS first, the padded pitch before the odd one (the last always fits)
+    const int pad = ((N + 15) / 32) * 32 + 16, odd = N | 1;
+    const struct { bool w, v; int ld; } plans[] = {{true, true, pad}, {true, true, odd}, {false, true, pad}, {false, true, odd}, {false, false, pad}, {false, false, odd}};
+    int pi = 0;
+    while (pi < 5 && bsv_lds_bytes<T>(M, N, plans[pi].ld, plans[pi].w, plans[pi].v) > BID_MAX_LDS) ++pi;
+    const bool w_lds = plans[pi].w, v_lds = plans[pi].v;
+    const int ldg = plans[pi].ld;
+    const size_t lds = bsv_lds_bytes<T>(M, N, ldg, w_lds, v_lds);
+    auto kern = w_lds ? k_batched_svd<T, true, true> : v_lds ? k_batched_svd<T, false, true> : k_batched_svd<T, false, false>;
+    static bool attr_set[64] = {};
+    if (!attr_set[c->device & 63]) {
+        for (const void *f : {reinterpret_cast<const void *>(k_batched_svd<T, true, true>), reinterpret_cast<const void *>(k_batched_svd<T, false, true>),
+                              reinterpret_cast<const void *>(k_batched_svd<T, false, false>)})
+            RC_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BID_MAX_LDS));
+        attr_set[c->device & 63] = true;
+    }
+    const size_t per = ((w_lds ? 0 : (size_t)M * N) + (v_lds ? 0 : (size_t)N * N)) * sizeof(T);
+    const int64_t grid = bid_grid(c, reinterpret_cast<const void *>(kern), lds, per, count);
+    T *ws = per ? c->alloc<T>((size_t)grid * per / sizeof(T)) : nullptr;
+    // the work orientation's U (M x k) and V^T (k x N): u and vt, or for a wide matrix vt^T and u^T
+    const Mat<T> uo = wide ? vt.t() : u, vo = wide ? u.t() : vt;
+    const int64_t uobs = wide ? vbs : ubs, vobs = wide ? ubs : vbs;
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BID_THREADS), lds, c->stream, a, abs, (int)count, (int)k, tol, uo, uobs, vo, vobs, s, ranks, ws,
+                       c->health_word(), ldg);
+}
+
 template void batched_column_id<double>(rc_context *, Mat<double>, int64_t, int32_t, int64_t, double, Mat<double>, int64_t, Mat<double>, int64_t, int64_t *, int64_t *);
 template void batched_column_id<float>(rc_context *, Mat<float>, int64_t, int32_t, int64_t, double, Mat<float>, int64_t, Mat<float>, int64_t, int64_t *, int64_t *);
 template void batched_two_sided_id<double>(rc_context *, Mat<double>, int64_t, int32_t, int64_t, double, Mat<double>, int64_t, Mat<double>, int64_t,
                                            Mat<double>, int64_t, int64_t *, int64_t *, int64_t *);
 template void batched_two_sided_id<float>(rc_context *, Mat<float>, int64_t, int32_t, int64_t, double, Mat<float>, int64_t, Mat<float>, int64_t,
                                           Mat<float>, int64_t, int64_t *, int64_t *, int64_t *);
+
+template void batched_svd<double>(rc_context *, Mat<double>, int64_t, int32_t, int64_t, double, Mat<double>, int64_t, double *, Mat<double>, int64_t,
+                                  int64_t *);
+template void batched_svd<float>(rc_context *, Mat<float>, int64_t, int32_t, int64_t, double, Mat<float>, int64_t, float *, Mat<float>, int64_t, int64_t *);
 
 }  // namespace rc

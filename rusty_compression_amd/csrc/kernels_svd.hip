@@ -29,44 +29,12 @@
 
 namespace rc {
 
-template <typename T> struct JEps;
-template <> struct JEps<double> { static __device__ inline double eps() { return 1.1102230246251565e-16; } };
-template <> struct JEps<float> { static __device__ inline float eps() { return 5.9604644775390625e-08f; } };
-
 template <typename T> __device__ inline T dpp_row_sum(T v) { return group_sum_dpp<16>(v); }
 
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also waits for
 // outstanding GLOBAL stores (vmcnt(0)); the rotation-log stores are write-only and
 // must stay in flight across rounds, so the round barrier waits for lgkmcnt alone.
 __device__ inline void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// circle-method pairing: round r of N-1 (N even), pair slot pi of N/2
-__device__ inline void rr_pair(int N, int r, int pi, int &p, int &q) {
-    if (pi == 0) { p = N - 1; q = r; }
-    else { p = (r + pi) % (N - 1); q = (r - pi + (N - 1)) % (N - 1); }
-    if (p > q) { int t = p; p = q; q = t; }
-}
-
-// Rotation that annihilates the (p, q) entry of the Gram matrix: with d = aqq - app, h = 2 apq (zeta = d / h)
-//   t = sign(zeta) / (|zeta| + sqrt(1 + zeta^2)) = sign(d h) |h| / (|d| + sqrt(d^2 + h^2)),   c = 1 / sqrt(1 + t^2),  s = c t
-// -- the second form has one reciprocal less on the round's dependent chain.  t only decides how completely the entry is
-// annihilated, so its reciprocal and root take ONE Newton step (1e-15); c decides the orthogonality of the rotation and keeps two.
-// Always evaluated in f64: with f32 parameters c^2 + s^2 - 1 has a systematic sign, and the thousands of rotations a
-// column goes through inflate the singular values (3e-5 at n = 300).  A tiny angle (|d| >> |h|) is safe: t -> 0.
-template <typename T>
-__device__ inline void jacobi_rotation(T app, T aqq, T apq, T &c, T &s) {
-    const double d = (double)aqq - (double)app, h = 2.0 * (double)apq;
-    const double w = fma(d, d, h * h);
-    double ri = __builtin_amdgcn_rsq(w);
-    ri = ri * fma(-0.5 * w, ri * ri, 1.5);
-    const double den = fabs(d) + w * ri;
-    double rd = __builtin_amdgcn_rcp(den);
-    rd = fma(fma(-den, rd, 1.0), rd, rd);
-    const double t = copysign(fabs(h) * rd, d * h);
-    const double cd = fast_rsqrt(fma(t, t, 1.0));
-    c = (T)cd;
-    s = (T)(cd * t);
-}
 
 // one rotation record of the log
 template <typename T> struct Rot { T c, s; };
@@ -114,8 +82,6 @@ __global__ void k_clear_words(unsigned *p, int n) {
 
 // Lanes per column pair: one DPP row.
 constexpr int kLPP = 16;
-// Sweep budget of the LDS-resident Jacobi; the fused launch hands the sweep count over in the 8-bit payload of a tagged word.
-constexpr int kMaxSweeps = 30;
 static_assert(kMaxSweeps < 255, "sweep count must fit a tagged word");
 
 // ---------------------------------------------------------------------------

@@ -1031,6 +1031,23 @@ int64_t check_two_sided_id_rank_batched(Mat<T> a, int32_t count, int64_t k, doub
     if (count > 0) RC_REQUIRE(a.p && cm.p && x.p && r.p && row_ind && col_ind && ranks, RC_INVALID_ARGUMENT, "two_sided_id_rank_batched: null pointer");
     return k;
 }
+// the batched SVD's checks: the batched IDs' domain plus min(m, n) <= 128 (the core of one workgroup)
+template <typename T>
+int64_t check_svd_rank_batched(Mat<T> a, int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs, const T *s, Mat<T> vt, int64_t vbs,
+                               const int64_t *ranks) {
+    const int64_t m = a.rows, n = a.cols;
+    const char *who = "svd_rank_batched";
+    k = batched_domain(who, "rc_compute_svd_*", a, count, k, tol);
+    RC_REQUIRE(std::min(m, n) <= 128, RC_INVALID_ARGUMENT, "%s: needs min(m, n) <= 128 (got %lld x %lld); use rc_compute_svd_* for larger matrices", who,
+               (long long)m, (long long)n);
+    RC_REQUIRE(u.rows == m && u.cols == k && vt.rows == k && vt.cols == n, RC_INVALID_ARGUMENT,
+               "svd_rank_batched: u must be %lld x %lld and vt %lld x %lld (k clamped to min(m, n))", (long long)m, (long long)k, (long long)k, (long long)n);
+    check_batch_stride(who, "u", ubs, u, count);
+    check_batch_stride(who, "vt", vbs, vt, count);
+    if (count > 0) RC_REQUIRE(a.p && u.p && s && vt.p && ranks, RC_INVALID_ARGUMENT, "svd_rank_batched: null pointer");
+    return k;
+}
+
 template int64_t check_column_id_rank_batched<double>(Mat<double>, int32_t, int64_t, double, Mat<double>, int64_t, Mat<double>, int64_t, const int64_t *,
                                                       const int64_t *);
 template int64_t check_column_id_rank_batched<float>(Mat<float>, int32_t, int64_t, double, Mat<float>, int64_t, Mat<float>, int64_t, const int64_t *,
@@ -1061,6 +1078,15 @@ void two_sided_id_rank_batched(rc_context *c, Mat<T> a, int64_t abs, int32_t cou
     k = check_two_sided_id_rank_batched(a, count, k, tol, cm, cbs, x, xbs, r, rbs, row_ind, col_ind, ranks);
     if (count == 0) return;
     batched_two_sided_id(c, a, abs, count, k, tol, cm, cbs, x, xbs, r, rbs, row_ind, col_ind, ranks);
+}
+
+// truncated SVDs of the same batch (SVD::compute_from -> compress(.) per matrix), rank chosen per matrix on the singular values
+template <typename T>
+void svd_rank_batched(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs, T *s, Mat<T> vt, int64_t vbs,
+                      int64_t *ranks) {
+    k = check_svd_rank_batched(a, count, k, tol, u, ubs, s, vt, vbs, ranks);
+    if (count == 0) return;
+    batched_svd(c, a, abs, count, k, tol, u, ubs, s, vt, vbs, ranks);
 }
 
 template <typename T>
@@ -1602,6 +1628,13 @@ rc_status rc_invert_permutation(rc_context *ctx, const int64_t *perm, int64_t n,
         return guarded(ctx, [&] {                                                                                                        \
             two_sided_id_rank_batched<T>(ctx, from_c<T>(a), a_batch_stride, count, k, tol, from_c<T>(c), c_batch_stride, from_c<T>(x),    \
                                          x_batch_stride, from_c<T>(r), r_batch_stride, row_ind, col_ind, ranks);                         \
+        });                                                                                                                              \
+    }                                                                                                                                    \
+    rc_status rc_svd_rank_batched_##SUF(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol,      \
+                                        rc_matrix u, int64_t u_batch_stride, T *s, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks) { \
+        return guarded(ctx, [&] {                                                                                                        \
+            svd_rank_batched<T>(ctx, from_c<T>(a), a_batch_stride, count, k, tol, from_c<T>(u), u_batch_stride, s, from_c<T>(vt),         \
+                                vt_batch_stride, ranks);                                                                                 \
         });                                                                                                                              \
     }
 

@@ -209,6 +209,10 @@ template <typename T> void batched_column_id(rc_context *c, Mat<T> a, int64_t ab
 // i * xbs, i * zbs elements; row_ind count x m, col_ind count x n, ranks count (arguments checked by the caller)
 template <typename T> void batched_two_sided_id(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int64_t k, double tol, Mat<T> cm, int64_t cbs, Mat<T> x,
                                                 int64_t xbs, Mat<T> z, int64_t zbs, int64_t *row_ind, int64_t *col_ind, int64_t *ranks);
+// truncated SVDs of the same kind of batch (kernels_batched_id.hip): matrix i is a, u (m x k), vt (k x n) moved by i * abs, i * ubs,
+// i * vbs elements; s count x min(m, n), ranks count (arguments checked by the caller)
+template <typename T> void batched_svd(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs, T *s, Mat<T> vt,
+                                       int64_t vbs, int64_t *ranks);
 // the complex twins (kernels_batched_id_c.hip), R = double (c64) or float (c32): the same layout with interleaved-complex views
 template <typename R> void batched_column_id_c(rc_context *c, const rc_matrix &a, int64_t abs, int32_t count, int64_t k, double tol, const rc_matrix &cm,
                                                int64_t cbs, const rc_matrix &z, int64_t zbs, int64_t *col_ind, int64_t *ranks);
