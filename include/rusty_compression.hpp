@@ -94,7 +94,7 @@ using c32 = std::complex<float>;
 using c64 = std::complex<double>;
 
 template <typename T> struct Api;
-#define RC_API(T, SUF, RSUF, REAL_ONLY)  /* REAL_ONLY: RC_KEEP or RC_DROP, the entry points of real scalars only */                 \
+#define RC_API(T, SUF, RSUF)                                                                                      \
     template <> struct Api<T> {                                                                                     \
         static constexpr auto random_gaussian = rc_random_gaussian_##SUF;                                           \
         static constexpr auto matmat = rc_matmat_##SUF;                                                             \
@@ -127,17 +127,13 @@ template <typename T> struct Api;
         static constexpr auto column_id_rank = rc_column_id_rank_##SUF;                                             \
         static constexpr auto column_id_rank_batched = rc_column_id_rank_batched_##SUF;                             \
         static constexpr auto two_sided_id_rank_batched = rc_two_sided_id_rank_batched_##SUF;                       \
-        REAL_ONLY(static constexpr auto svd_rank_batched = rc_svd_rank_batched_##SUF;)                              \
+        static constexpr auto svd_rank_batched = rc_svd_rank_batched_##SUF;                                         \
     };
-#define RC_KEEP(...) __VA_ARGS__
-#define RC_DROP(...)
-RC_API(double, f64, f64, RC_KEEP)
-RC_API(float, f32, f32, RC_KEEP)
-RC_API(c64, c64, f64, RC_DROP)
-RC_API(c32, c32, f32, RC_DROP)
+RC_API(double, f64, f64)
+RC_API(float, f32, f32)
+RC_API(c64, c64, f64)
+RC_API(c32, c32, f32)
 #undef RC_API
-#undef RC_KEEP
-#undef RC_DROP
 
 // ---- device-resident C-order arrays (the reference's Array2 / Array1<usize>) ----------------------
 template <typename T>
@@ -572,12 +568,13 @@ BatchedTwoSidedID<T> two_sided_id_rank_batched(const DeviceMatrix<T> &a, int32_t
                                                     out.col_ind.data(), out.ranks.data()));
     return out;
 }
-// truncated SVDs of the same batch in one call (rc_svd_rank_batched_*, real scalars): u is count * m x k, s count x min(m, n) (all
-// singular values, descending), vt count * k x n; ranks[i] = the kept rank, the rows / columns past it zero
+// truncated SVDs of the same batch in one call (rc_svd_rank_batched_*, every scalar type): u is count * m x k, s count x min(m, n)
+// (all singular values, descending, in the real type), vt count * k x n (V^H for complex scalars); ranks[i] = the kept rank, the
+// rows / columns past it zero
 template <typename T>
 struct BatchedSVD {
     DeviceMatrix<T> u;
-    DeviceBuffer<T> s;
+    DeviceBuffer<typename Scalar<T>::real> s;
     DeviceMatrix<T> vt;
     DeviceIndex ranks;
 };
@@ -585,7 +582,7 @@ template <typename T>
 BatchedSVD<T> svd_rank_batched(const DeviceMatrix<T> &a, int32_t count, int64_t k, double tol = 0.0) {
     const int64_t m = count > 0 ? a.nrows() / count : 0, n = a.ncols(), p = m < n ? m : n;
     const int64_t kk = k < p ? k : p;
-    BatchedSVD<T> out{DeviceMatrix<T>(a.ctx(), (int64_t)count * m, kk), DeviceBuffer<T>(a.ctx(), (std::size_t)count * (std::size_t)p),
+    BatchedSVD<T> out{DeviceMatrix<T>(a.ctx(), (int64_t)count * m, kk), DeviceBuffer<typename Scalar<T>::real>(a.ctx(), (std::size_t)count * (std::size_t)p),
                       DeviceMatrix<T>(a.ctx(), (int64_t)count * kk, n), DeviceIndex(a.ctx(), (std::size_t)count)};
     a.ctx().check(Api<T>::svd_rank_batched(a.ctx().raw(), rc_matrix{a.view().data, m, n, n, 1}, m * n, count, k, tol,
                                            rc_matrix{out.u.view().data, m, kk, kk, 1}, m * kk, out.s.data(), rc_matrix{out.vt.view().data, kk, n, n, 1},

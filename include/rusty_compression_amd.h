@@ -497,9 +497,19 @@ rc_status rc_two_sided_id_rank_batched_c32(rc_context *ctx, rc_matrix a, int64_t
  * it (?gesdd leaves them open).  Matrix i's bits depend on matrix i alone: not on count, the neighbours, the input or output
  * strides, or graph replay against an eager call.  Non-finite input stays inside its matrix's outputs (values unspecified,
  * 0 <= r <= k).  A matrix whose Jacobi iteration uses up its sweep budget ORs bit 16 into the health word.  Per matrix: pivoted
- * Householder QR to the p x p factor, one-sided Jacobi on it, U = Q [U_R; 0]; not bit-equal to rc_compute_svd_*, whose QR differs. */
+ * Householder QR to the p x p factor, one-sided Jacobi on it, U = Q [U_R; 0]; not bit-equal to rc_compute_svd_*, whose QR differs.
+ * Complex scalars (c64, c32): the same signature, domain, layout, checks, rank rule, zero tails and health bit with interleaved
+ * (re, im) data, strides and batch strides in complex elements; s has the real type (double for c64, float for c32).  u is m x k and
+ * vt = V^H (k x n, the conjugate transpose, as in rc_compute_svd_c*), so u[:, :r] diag(s[:r]) vt[:r, :] is the rank-r truncation.
+ * Phases replace the sign rule: in each kept column of u, the first (in row order) of its largest-modulus entries is exactly
+ * (|u_ic|, 0), the column having been multiplied by that unit phase, and the matching row of vt by its inverse (?gesdd leaves the
+ * phase open; with the rule a separated triplet is unique).  conj(A) gives the same s and ranks and the conjugates of u and vt, bit
+ * for bit.  Per matrix: complex pivoted Householder QR to the p x p factor R, one-sided complex Jacobi on R^H, U = Q [U_R; 0]; a wide
+ * matrix is factored through its transpose. */
 rc_status rc_svd_rank_batched_f64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix u, int64_t u_batch_stride, double *s, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks);
 rc_status rc_svd_rank_batched_f32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix u, int64_t u_batch_stride, float *s, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks);
+rc_status rc_svd_rank_batched_c64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix u, int64_t u_batch_stride, double *s, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks);
+rc_status rc_svd_rank_batched_c32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix u, int64_t u_batch_stride, float *s, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks);
 
 /* The gather over RCCL (xGMI inside a node).  One process per GPU: rank 0 calls rc_comm_unique_id and hands the 128
  * bytes to the other ranks by whatever means the host has (MPI, a file, torch.distributed), every rank calls

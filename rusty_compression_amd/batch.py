@@ -110,7 +110,8 @@ def svd_rank_batched(a: torch.Tensor, k: int, tol: float = 0.0) -> Tuple[torch.T
     a: [count, m, n] device tensor of float64 or float32, any strides (1 <= m, n <= 512, min(m, n) <= 128).  k (<= 128) is clamped to
     p = min(m, n); the rank of each matrix is the first j < k with s_j == 0 or s_j / s_0 < tol (tol = 0: fixed rank k).  Returns
     U [count, m, k], S [count, p] (all singular values, descending), Vt [count, k, n] and ranks [count]; the columns of U and rows of
-    Vt past a matrix's rank are zero, and the largest-|.| entry of each kept column of U is positive."""
+    Vt past a matrix's rank are zero, and the largest-|.| entry of each kept column of U is positive.  Complex data (complex128,
+    complex64) goes to svd_rank_batched_complex; this function raises TypeError for it."""
     from . import _lib
     from .types import as_device
 
@@ -124,6 +125,39 @@ def svd_rank_batched(a: torch.Tensor, k: int, tol: float = 0.0) -> Tuple[torch.T
     kk = min(int(k), p)
     u = torch.empty((count, m, kk), dtype=a.dtype, device=a.device)
     s = torch.empty((count, p), dtype=a.dtype, device=a.device)
+    vt = torch.empty((count, kk, n), dtype=a.dtype, device=a.device)
+    ranks = torch.empty(count, dtype=torch.int64, device=a.device)
+    view = _lib.rc_matrix(a.data_ptr(), m, n, a.stride(1), a.stride(2))
+    _lib.default_context().call(f"rc_svd_rank_batched_{_lib.suffix(a.dtype)}", view, ctypes.c_int64(a.stride(0)), ctypes.c_int32(count),
+                                ctypes.c_int64(int(k)), ctypes.c_double(float(tol)), _lib.mat(u[0] if count else u.new_empty(m, kk)),
+                                ctypes.c_int64(m * kk), ctypes.c_void_p(s.data_ptr()), _lib.mat(vt[0] if count else vt.new_empty(kk, n)),
+                                ctypes.c_int64(kk * n), _lib.i64p(ranks))
+    return u, s, vt, ranks
+
+
+def svd_rank_batched_complex(a: torch.Tensor, k: int, tol: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Truncated SVDs of `count` small same-shaped complex matrices in one stream-ordered call (rc_svd_rank_batched_c64 / _c32).
+
+    a: [count, m, n] device tensor of complex128 or complex64, any strides (1 <= m, n <= 512, min(m, n) <= 128); float64 and float32
+    data goes to svd_rank_batched, and this function raises TypeError for it.  The domain, the rank rule and the zero tails are
+    svd_rank_batched's.  Returns U [count, m, k] (complex), S [count, p] (the real dtype: float64 for complex128, float32 for
+    complex64; all p = min(m, n) singular values, descending), Vt [count, k, n] (complex, the conjugate transpose of V, so that
+    U[:, :, :r] S[:, :r] Vt[:, :r, :] is the rank-r truncation) and ranks [count].  Phase rule: in each kept column of U the first of
+    its largest-modulus entries is real and positive, its imaginary part exactly 0; conj(a) gives the conjugated U and Vt bit for bit."""
+    from . import _lib
+    from .types import as_device
+
+    a = as_device(a).resolve_conj()  # a lazily conjugated complex view is materialised: the kernels read the stored values
+    if a.dim() != 3:
+        raise AssertionError("expected a [count, m, n] batch")
+    if a.dtype not in (torch.complex128, torch.complex64):
+        raise TypeError(f"svd_rank_batched_complex: complex128 or complex64 data expected, got {a.dtype}")
+    real = torch.float64 if a.dtype == torch.complex128 else torch.float32
+    count, m, n = a.shape
+    p = min(m, n)
+    kk = min(int(k), p)
+    u = torch.empty((count, m, kk), dtype=a.dtype, device=a.device)
+    s = torch.empty((count, p), dtype=real, device=a.device)
     vt = torch.empty((count, kk, n), dtype=a.dtype, device=a.device)
     ranks = torch.empty(count, dtype=torch.int64, device=a.device)
     view = _lib.rc_matrix(a.data_ptr(), m, n, a.stride(1), a.stride(2))

@@ -1,5 +1,5 @@
-// Batched column and two-sided IDs of many small same-shaped COMPLEX matrices in one launch (rc_column_id_rank_batched_c64 / _c32,
-// rc_two_sided_id_rank_batched_c64 / _c32).
+// Batched column and two-sided IDs and truncated SVDs of many small same-shaped COMPLEX matrices in one launch
+// (rc_column_id_rank_batched_c64 / _c32, rc_two_sided_id_rank_batched_c64 / _c32, rc_svd_rank_batched_c64 / _c32).
 //
 // The structure of kernels_batched_id.hip (one persistent workgroup of 256 threads per matrix, the same three device stages, the same
 // grid and workspace rule, bid_grid) with the complex arithmetic of the lone complex path in rc_complex.hip:
@@ -14,6 +14,9 @@
 //
 // Register budget (every instance must run without scratch): one trailing column in flight per wave in the apply (the real kernels
 // keep two) and 8 x 8 back-substitution tiles (the real kernels use 16 x 16).
+//
+// The truncated SVD (k_batched_svd_c) runs the first two stages to all N steps, then k_batched_svd's complex Jacobi and U forming (see
+// its comment below).
 //
 // Every operation below commutes exactly with negating all imaginary parts (round to nearest is sign-symmetric, and each real part
 // is even, each imaginary part odd in the imaginary inputs), so conj(A) gives the same permutations and ranks and the conjugate
@@ -158,10 +161,13 @@ __device__ __forceinline__ void bic_load(cx<R> *W, int ldw, int m, int n, bool l
 
 // truncated pivoted QR of the working copy, at most k steps: pivots in jp (?geqp3's rule), R and the Householder vectors in W (LAPACK
 // format, physical column order).  Returns the rank: the first j < k with R_jj == 0 or (tol > 0 and |R_jj / R_00| < tol), else k.
-template <typename R>
-__device__ __forceinline__ int bic_qrcp(cx<R> *W, int ldw, int m, int n, int k, double tol, int *jp, R *vn1, R *vn2, R *red, int tid, int wv, int lane) {
+// FULL (the batched SVD): no stopping rule, all k steps are taken (an exactly zero pivot column is a step with H = I) and the complex
+// tau_j goes to taus[j]; returns k.
+template <typename R, bool FULL = false>
+__device__ __forceinline__ int bic_qrcp(cx<R> *W, int ldw, int m, int n, int k, double tol, int *jp, R *vn1, R *vn2, R *red, int tid, int wv, int lane,
+                                        cx<R> *taus = nullptr) {
     int r = k;
-    R r00 = 0;
+    [[maybe_unused]] R r00 = 0;
     for (int j = 0; j < k; ++j) {
         if (wv == 0) {  // pivot: first maximum of the partial norms; NaN never wins (v > best), no valid index -> j
             R best = (R)-1;
@@ -199,9 +205,13 @@ __device__ __forceinline__ int bic_qrcp(cx<R> *W, int ldw, int m, int n, int k, 
             tj = cx<R>{(beta - alpha.re) / beta, -alpha.im / beta};
             if (tid == 0) col[j] = cx<R>{beta, (R)0};
         }
-        // R_jj = beta (real) decides the rank (qr.rs:187-200 as a ratio; uniform across the workgroup)
-        if (j == 0) r00 = beta;
-        if (beta == (R)0 || (tol > 0.0 && (double)fabs(beta / r00) < tol)) { r = j; break; }
+        if constexpr (FULL) {
+            if (tid == 0) taus[j] = tj;
+        } else {
+            // R_jj = beta (real) decides the rank (qr.rs:187-200 as a ratio; uniform across the workgroup)
+            if (j == 0) r00 = beta;
+            if (beta == (R)0 || (tol > 0.0 && (double)fabs(beta / r00) < tol)) { r = j; break; }
+        }
         __syncthreads();
         if (j + 1 < n) {
             const int rem = m - j;
@@ -372,6 +382,336 @@ __global__ __launch_bounds__(BIC_THREADS) void k_batched_two_sided_c(CView<R> a,
     }
 }
 
+
+// ---- batched truncated SVD (rc_svd_rank_batched_c64 / _c32) --------------------------------------------------------------------
+// k_batched_svd's stages with the arithmetic above.  Per matrix, in the tall orientation M x N (N = min(m, n)): the pivoted QR of
+// bic_qrcp run to N steps (W P = Q R with Q = H_0 .. H_{N-1}, the complex tau_j kept), one-sided Jacobi on the N x N core G = R^H
+// (the rows of the graded R, as the real kernel takes R^T) with the rotations accumulated in J: G J = U_G S, so R = J S U_G^H;
+// singular values = the column norms of G, U = Q [J_k; 0] with the k kept columns in registers, and V_W[jp[i], :] = (G S^-1)[i, :].
+// A wide matrix is read through its plain (unconjugated) transposed view: A^T = U' S V'^H gives A = conj(V') S U'^T, so u is the work
+// orientation's V^H written through u^T and vt its U written through vt^T, no conjugation on either side.  A Jacobi step on (g_p, g_q)
+// turns g_q by the phase e^{-i phi} = conj(apq) / |apq| (apq = g_p^H g_q; evaluated in f64 and rounded, as k_c_jacobi_round does),
+// then takes the real rotation of (app, aqq, |apq|).  Everything stays inside one workgroup.
+
+// Jacobi rows per lane of a 16-lane pair group (N <= 16 NE): the complex twin of bsv_round
+template <typename R, int NE>
+__device__ __forceinline__ void bsc_round(cx<R> *G, int ldg, cx<R> *J, int ldj, int N, int p, int q, R tol, R tol2, int ll, int *flag) {
+    cx<R> *gp = G + (size_t)p * ldg, *gq = G + (size_t)q * ldg;
+    cx<R> a[NE], b[NE];
+    R app = 0, aqq = 0, are = 0, aim = 0;  // apq = g_p^H g_q = (are, aim)
+#pragma unroll
+    for (int e = 0; e < NE; ++e) {
+        const int i = ll + 16 * e;
+        a[e] = i < N ? gp[i] : czero<R>();
+        b[e] = i < N ? gq[i] : czero<R>();
+        app = fma(a[e].re, a[e].re, app);
+        app = fma(a[e].im, a[e].im, app);
+        aqq = fma(b[e].re, b[e].re, aqq);
+        aqq = fma(b[e].im, b[e].im, aqq);
+        are = fma(a[e].re, b[e].re, are);
+        are = fma(a[e].im, b[e].im, are);
+        aim = fma(a[e].re, b[e].im, aim);
+        aim = fma(-a[e].im, b[e].re, aim);
+    }
+    app = group_sum_dpp<16>(app);
+    aqq = group_sum_dpp<16>(aqq);
+    are = group_sum_dpp<16>(are);
+    aim = group_sum_dpp<16>(aim);
+    // bsv_round's test with |apq|^2: rotate iff |apq| > tol sqrt(app aqq) (uniform over the 16 lanes)
+    const R h2 = are * are + aim * aim;
+    if (!(h2 > tol2 * app * aqq)) return;
+    const double hd = sqrt((double)are * (double)are + (double)aim * (double)aim), ih = 1.0 / hd;
+    const cx<R> ph{(R)((double)are * ih), (R)(-((double)aim * ih))};  // e^{-i phi}
+    double cd, sd;
+    jacobi_rotation<double>((double)app, (double)aqq, hd, cd, sd);
+    const R c = (R)cd, s = (R)sd;
+    cx<R> *vp = J + (size_t)p * ldj, *vq = J + (size_t)q * ldj;
+#pragma unroll
+    for (int e = 0; e < NE; ++e) {
+        const int i = ll + 16 * e;
+        if (i < N) {
+            const cx<R> bq = cmul(ph, b[e]);
+            gp[i] = cx<R>{c * a[e].re - s * bq.re, c * a[e].im - s * bq.im};
+            gq[i] = cx<R>{s * a[e].re + c * bq.re, s * a[e].im + c * bq.im};
+            const cx<R> x = vp[i], y = cmul(ph, vq[i]);
+            vp[i] = cx<R>{c * x.re - s * y.re, c * x.im - s * y.im};
+            vq[i] = cx<R>{s * x.re + c * y.re, s * x.im + c * y.im};
+        }
+    }
+    if (ll == 0 && (h2 > tol * (R)0.0625 * app * aqq || s * s > (R)16 * tol)) *flag = 2;  // plain store: every writer writes 2
+}
+
+// bsv_jacobi's schedule (round-robin pairs, 16 lanes per pair, one barrier per round, kMaxSweeps) on the complex core.  Returns false
+// when the sweep budget ran out before a quiet sweep.
+template <typename R, int NE>
+__device__ __forceinline__ bool bsc_jacobi(cx<R> *G, int ldg, cx<R> *J, int ldj, int N, int tid, int *flag) {
+    const int ll = tid & 15, grp = tid >> 4;
+    constexpr int NGRP = BIC_THREADS / 16;
+    const int N2 = (N + 1) & ~1, npairs = N2 / 2;
+    const R tol = sqrt((R)N) * JEps<R>::eps(), tol2 = tol * tol;
+    for (int sweep = 0; sweep < kMaxSweeps; ++sweep) {
+        if (tid == 0) *flag = 0;
+        __syncthreads();
+        for (int r = 0; r < N2 - 1; ++r) {
+            for (int pi = grp; pi < npairs; pi += NGRP) {
+                int p, q;
+                rr_pair(N2, r, pi, p, q);
+                if (q < N) bsc_round<R, NE>(G, ldg, J, ldj, N, p, q, tol, tol2, ll, flag);  // q == N: the dummy column of an odd N
+            }
+            __syncthreads();  // the pairs of a round are disjoint; the next round re-pairs the columns
+        }
+        const int rotated = *flag;
+        __syncthreads();
+        if (rotated < 2) return true;
+    }
+    return false;
+}
+
+// the phase rule on a column held by one wave (x[e] at output row orow(e), -1: none): i* = the first output row of the largest
+// |x|^2; the column is multiplied by ph = conj(x_i*) / |x_i*| (f64, rounded) and x_i* becomes exactly (|x_i*|, 0).  Returns ph;
+// (1, 0) with the column unchanged when |x_i*| is not positive and finite (a zero or non-finite column)
+template <typename R, int NE, typename Row>
+__device__ __forceinline__ cx<R> bsc_phase(cx<R> (&x)[NE], Row orow, int lane) {
+    R mx = 0;
+#pragma unroll
+    for (int e = 0; e < NE; ++e)
+        if (orow(e) >= 0) mx = max(mx, abs2(x[e]));
+    mx = wave_max_dpp(mx);
+    int key = 0x7fffffff;
+#pragma unroll
+    for (int e = 0; e < NE; ++e) {
+        const int o = orow(e);
+        if (o >= 0 && abs2(x[e]) == mx) key = min(key, o);
+    }
+    key = wave_min_dpp(key);
+    int who = 0x7fffffff;  // the lane and element holding row key
+#pragma unroll
+    for (int e = 0; e < NE; ++e)
+        if (key != 0x7fffffff && orow(e) == key) who = 64 * e + lane;
+    who = wave_min_dpp(who);
+    if (who == 0x7fffffff) return cone<R>();
+    cx<R> xs = czero<R>();
+#pragma unroll
+    for (int e = 0; e < NE; ++e)
+        if (e == (who >> 6)) xs = cx<R>{read_lane(x[e].re, who & 63), read_lane(x[e].im, who & 63)};
+    const double md = hypot((double)xs.re, (double)xs.im);
+    if (!(md > 0.0 && md <= 1.7976931348623157e308)) return cone<R>();
+    const cx<R> ph{(R)((double)xs.re / md), (R)(-((double)xs.im / md))};
+    const R mr = (R)md;
+#pragma unroll
+    for (int e = 0; e < NE; ++e) x[e] = orow(e) == key ? cx<R>{mr, (R)0} : cmul(x[e], ph);
+    return ph;
+}
+
+// U[:, c] = Q [J[:, srt[c]]; 0] times its phase for the kept columns c < r (zero for r <= c < k): one wave per column, the M rows in
+// registers (row lane + 64 e), the N reflectors applied backward as x -= tau_j v_j (v_j^H x) (Q = H_0 .. H_{N-1}: the factorization
+// applied H_j^H, forming Q applies H_j), v_j in W's column jp[j] below row j.  phase_here: the phase rule is applied to this column
+// and its phase stored in phs[c]; otherwise the column is multiplied by conj(phs[c]).
+template <typename R, int NE>
+__device__ __forceinline__ void bsc_form_u(const cx<R> *W, int ldw, const cx<R> *J, int ldj, int M, int N, int k, int r, const int *jp, const cx<R> *taus,
+                                           const int *srt, cx<R> *phs, bool phase_here, cx<R> *U, int64_t urs, int64_t ucs, int wv, int lane) {
+    for (int c = wv; c < k; c += BIC_WAVES) {
+        cx<R> *uc = U + (int64_t)c * ucs;
+        if (c >= r) {
+            for (int i = lane; i < M; i += 64) uc[i * urs] = czero<R>();
+            continue;
+        }
+        const cx<R> *jc = J + (size_t)srt[c] * ldj;
+        cx<R> x[NE];
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            const int i = lane + 64 * e;
+            x[e] = i < N ? jc[i] : czero<R>();
+        }
+        for (int j = N - 1; j >= 0; --j) {
+            const cx<R> tau = taus[j];
+            if (tau.re == (R)0 && tau.im == (R)0) continue;  // H_j = I (uniform)
+            const cx<R> *vc = W + (size_t)jp[j] * ldw;
+            cx<R> v[NE];
+            R dre = 0, dim = 0;  // v^H x
+#pragma unroll
+            for (int e = 0; e < NE; ++e) {
+                const int i = lane + 64 * e;
+                const cx<R> vv = vc[i < M ? i : j];  // branch-free: lanes out of range read row j and are masked below
+                v[e] = i > j && i < M ? vv : (i == j ? cone<R>() : czero<R>());
+                dre = fma(v[e].re, x[e].re, dre);
+                dre = fma(v[e].im, x[e].im, dre);
+                dim = fma(v[e].re, x[e].im, dim);
+                dim = fma(-v[e].im, x[e].re, dim);
+            }
+            const cx<R> f = cmul(tau, cx<R>{wave_sum_dpp(dre), wave_sum_dpp(dim)});
+#pragma unroll
+            for (int e = 0; e < NE; ++e) {
+                x[e].re = fma(-f.re, v[e].re, x[e].re);
+                x[e].re = fma(f.im, v[e].im, x[e].re);
+                x[e].im = fma(-f.re, v[e].im, x[e].im);
+                x[e].im = fma(-f.im, v[e].re, x[e].im);
+            }
+        }
+        if (phase_here) {
+            const cx<R> ph = bsc_phase<R, NE>(x, [&](int e) { const int i = lane + 64 * e; return i < M ? i : -1; }, lane);
+            if (lane == 0) phs[c] = ph;
+        } else {
+            const cx<R> ph = conj_of(phs[c]);
+#pragma unroll
+            for (int e = 0; e < NE; ++e) x[e] = cmul(x[e], ph);
+        }
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            const int i = lane + 64 * e;
+            if (i < M) uc[i * urs] = x[e];
+        }
+    }
+}
+
+// LDS of k_batched_svd_c: [W: N x (M|1), W_LDS only] [G: N x ldg, G_LDS only] [J: N x ldg, V_LDS only] taus[N] phs[128] complex
+// | vn1[N] vn2[N] sig[N] red[8] real | jp[N] srt[N] flag[4]
+template <typename R>
+size_t bsc_lds_bytes(int M, int N, int ldg, bool w_lds, bool v_lds, bool g_lds) {
+    size_t c = (size_t)N + 128;
+    if (w_lds) c += (size_t)N * (size_t)(M | 1);
+    if (g_lds) c += (size_t)N * ldg;
+    if (v_lds) c += (size_t)N * ldg;
+    return c * sizeof(cx<R>) + ((size_t)3 * N + 8) * sizeof(R) + (size_t)(2 * N + 4) * sizeof(int);
+}
+// complex elements of one workgroup's workspace slot: W (M x N), G (N x ldg), J (N x N), each unless it is in LDS
+__host__ __device__ inline size_t bsc_ws_elems(int M, int N, int ldg, bool w_lds, bool v_lds, bool g_lds) {
+    return (w_lds ? 0 : (size_t)M * N) + (g_lds ? 0 : (size_t)N * ldg) + (v_lds ? 0 : (size_t)N * N);
+}
+
+// a: m x n input view; uo (M x k) and vo (k x N) are the views the work orientation's U and V^H go to (u and vt for a tall matrix,
+// vt^T and u^T for a wide one), each moved by its own batch stride; s (count x N) and ranks contiguous.  W_LDS / G_LDS / V_LDS: the
+// working copy W / the core G / the rotations J live in LDS, else in the workgroup's workspace slot (in that order, ldg = N there).
+template <typename R, bool W_LDS, bool V_LDS, bool G_LDS>
+__global__ __launch_bounds__(BIC_THREADS) void k_batched_svd_c(CView<R> a, int64_t abs, int count, int k, double tol, CView<R> uo, int64_t ubs, CView<R> vo,
+                                                               int64_t vbs, R *__restrict__ s_out, int64_t *__restrict__ ranks, cx<R> *__restrict__ ws,
+                                                               int *health, int ldg) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const bool wide = a.rows < a.cols;
+    const int M = (int)(wide ? a.cols : a.rows), N = (int)(wide ? a.rows : a.cols);
+    const int ldw = W_LDS ? (M | 1) : M, ldj = V_LDS ? ldg : N;
+    cx<R> *lp = reinterpret_cast<cx<R> *>(smem_raw);                                    // next free LDS element
+    cx<R> *wp = ws + (size_t)blockIdx.x * bsc_ws_elems(M, N, ldg, W_LDS, V_LDS, G_LDS);  // next free element of the workspace slot
+    cx<R> *W, *G, *J;
+    if (W_LDS) { W = lp; lp += (size_t)N * ldw; } else { W = wp; wp += (size_t)N * ldw; }
+    if (G_LDS) { G = lp; lp += (size_t)N * ldg; } else { G = wp; wp += (size_t)N * ldg; }
+    if (V_LDS) { J = lp; lp += (size_t)N * ldj; } else { J = wp; }
+    cx<R> *taus = lp, *phs = taus + N;
+    R *vn1 = reinterpret_cast<R *>(phs + 128);
+    R *vn2 = vn1 + N, *sig = vn2 + N, *red = sig + N;
+    int *jp = reinterpret_cast<int *>(red + 8);
+    int *srt = jp + N, *flag = srt + N;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    // the input in the work orientation and its fast direction
+    const int64_t ars = wide ? a.cs : a.rs, acs = wide ? a.rs : a.cs;
+
+    for (int b = blockIdx.x; b < count; b += gridDim.x) {
+        const cx<R> *__restrict__ A = a.p + (int64_t)b * abs;
+        // ---- QR: W P = Q R, all N steps (exact zero pivots are steps with H = I), complex taus kept -------------------------------
+        bic_load(W, ldw, M, N, ars <= acs, [&](int i, int c) { return A[i * ars + c * acs]; }, vn1, vn2, jp, wv, lane);
+        bic_qrcp<R, true>(W, ldw, M, N, N, 0.0, jp, vn1, vn2, red, tid, wv, lane, taus);
+        // ---- core G = R^H (R in pivoted column order: G[:, j] = conj(row j of R)) and J = I -----------------------------------------
+        for (int j = wv; j < N; j += BIC_WAVES) {
+            for (int i = lane; i < N; i += 64) {
+                G[(size_t)j * ldg + i] = i >= j ? conj_of(W[(size_t)jp[i] * ldw + j]) : czero<R>();
+                J[(size_t)j * ldj + i] = i == j ? cone<R>() : czero<R>();
+            }
+        }
+        __syncthreads();
+        bool conv;
+        if (N <= 16) conv = bsc_jacobi<R, 1>(G, ldg, J, ldj, N, tid, flag);
+        else if (N <= 32) conv = bsc_jacobi<R, 2>(G, ldg, J, ldj, N, tid, flag);
+        else if (N <= 64) conv = bsc_jacobi<R, 4>(G, ldg, J, ldj, N, tid, flag);
+        else conv = bsc_jacobi<R, 8>(G, ldg, J, ldj, N, tid, flag);
+        if (!conv && tid == 0) atomicOr(health, 16);  // the sweep budget ran out: bit 16, as the lone Jacobi reports it
+        // ---- singular values: column norms, sorted descending (a strict total order: NaN last, ties by column) ----------------------
+        for (int j = tid >> 4; j < N; j += BIC_THREADS / 16) {
+            const cx<R> *gj = G + (size_t)j * ldg;
+            R acc = 0;
+            for (int i = tid & 15; i < N; i += 16) {
+                acc = fma(gj[i].re, gj[i].re, acc);
+                acc = fma(gj[i].im, gj[i].im, acc);
+            }
+            acc = group_sum_dpp<16>(acc);
+            if ((tid & 15) == 0) sig[j] = sqrt(acc);
+        }
+        __syncthreads();
+        R *sb = s_out + (int64_t)b * N;
+        for (int i = tid; i < N; i += BIC_THREADS) {
+            const R ki = sig[i] >= (R)0 ? sig[i] : (R)-1;
+            int pos = 0;
+            for (int j = 0; j < N; ++j) {
+                const R kj = sig[j] >= (R)0 ? sig[j] : (R)-1;
+                pos += (kj > ki || (kj == ki && j < i)) ? 1 : 0;
+            }
+            srt[pos] = i;
+            sb[pos] = sig[i];
+        }
+        __syncthreads();
+        // ---- rank: the first j < k with s_j == 0 or (tol > 0 and s_j / s_0 < tol), else k ---------------------------------------
+        if (tid == 0) {
+            const R s0 = sig[srt[0]];
+            int r = k;
+            for (int j = 0; j < k; ++j) {
+                const R sj = sig[srt[j]];
+                if (sj == (R)0 || (tol > 0.0 && (double)(sj / s0) < tol)) { r = j; break; }
+            }
+            flag[1] = r;
+            ranks[b] = r;
+        }
+        __syncthreads();
+        const int r = flag[1];
+        cx<R> *Vb = vo.p + (int64_t)b * vbs;
+        // ---- phases on the caller's u.  Wide: u[:, c] is row c of vo, u[jp[i], c] = conj(G[i, srt[c]]) / s_c; its phase is fixed
+        // and the row written here, before U is formed.  Tall: in bsc_form_u. ------------------------------------------------------
+        if (wide) {
+            for (int c = wv; c < k; c += BIC_WAVES) {
+                const int j0 = c < r ? srt[c] : 0;
+                const cx<R> *gc = G + (size_t)j0 * ldg;
+                const R sj = sig[j0], inv = sj > (R)0 ? (R)1 / sj : (R)0;
+                cx<R> x[2];
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    const int i = lane + 64 * e;
+                    const cx<R> g = i < N ? gc[i] : czero<R>();
+                    x[e] = c < r ? cx<R>{g.re * inv, -(g.im * inv)} : czero<R>();
+                }
+                if (c < r) {
+                    const cx<R> ph = bsc_phase<R, 2>(x, [&](int e) { const int i = lane + 64 * e; return i < N ? jp[i] : -1; }, lane);
+                    if (lane == 0) phs[c] = ph;
+                }
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    const int i = lane + 64 * e;
+                    if (i < N) Vb[c * vo.rs + (int64_t)jp[i] * vo.cs] = x[e];
+                }
+            }
+            __syncthreads();
+        }
+        // ---- U = Q [J_k; 0] straight into the output view -------------------------------------------------------------------------
+        cx<R> *Ub = uo.p + (int64_t)b * ubs;
+        if (M <= 64) bsc_form_u<R, 1>(W, ldw, J, ldj, M, N, k, r, jp, taus, srt, phs, !wide, Ub, uo.rs, uo.cs, wv, lane);
+        else if (M <= 128) bsc_form_u<R, 2>(W, ldw, J, ldj, M, N, k, r, jp, taus, srt, phs, !wide, Ub, uo.rs, uo.cs, wv, lane);
+        else if (M <= 256) bsc_form_u<R, 4>(W, ldw, J, ldj, M, N, k, r, jp, taus, srt, phs, !wide, Ub, uo.rs, uo.cs, wv, lane);
+        else bsc_form_u<R, 8>(W, ldw, J, ldj, M, N, k, r, jp, taus, srt, phs, !wide, Ub, uo.rs, uo.cs, wv, lane);
+        if (!wide) {
+            __syncthreads();  // phs is written in bsc_form_u
+            // ---- V^H: row c of vo is conj(V_W[:, c] ph_c), V_W[jp[i], c] = G[i, srt[c]] / s_c; rows r..k-1 zero ----------------------
+            for (int c = wv; c < k; c += BIC_WAVES) {
+                const int j0 = c < r ? srt[c] : 0;
+                const cx<R> *gc = G + (size_t)j0 * ldg;
+                const R sj = sig[j0], inv = sj > (R)0 ? (R)1 / sj : (R)0;
+                const cx<R> ph = c < r ? phs[c] : czero<R>();
+                for (int i = lane; i < N; i += 64) {
+                    const cx<R> t = cmul(gc[i], ph);
+                    Vb[c * vo.rs + (int64_t)jp[i] * vo.cs] = c < r ? cx<R>{t.re * inv, -(t.im * inv)} : czero<R>();
+                }
+            }
+        }
+        __syncthreads();  // W, G, J and the small arrays are rewritten by the next matrix
+    }
+}
+
 }  // namespace
 
 // the real kernels' launch rule (bid_grid, BID_MAX_LDS): LDS variant when the complex working copy fits, else the workspace variant
@@ -422,6 +762,49 @@ void batched_two_sided_id_c(rc_context *c, const rc_matrix &a_, int64_t abs, int
                        col_ind, ranks, ws);
 }
 
+// the real batched SVD's launch rule with a third place for the core: the first plan that fits, most in LDS first, the padded pitch
+// before the odd one; the last keeps W, G and J in the workgroup's slot of the grid-bounded workspace (a 128 x 128 c64 core alone
+// takes 256 KiB, more than BID_MAX_LDS)
+template <typename R>
+void batched_svd_c(rc_context *c, const rc_matrix &a_, int64_t abs, int32_t count, int64_t k, double tol, const rc_matrix &u_, int64_t ubs, R *s,
+                   const rc_matrix &vt_, int64_t vbs, int64_t *ranks) {
+    const CView<R> a = cview<R>(a_), u = cview<R>(u_), vt = cview<R>(vt_);
+    const int m = (int)a.rows, n = (int)a.cols;
+    if (count <= 0) return;
+    ProfScope ps(c, "op:batched_svd<complex> %dx%d k=%lld count=%d", m, n, (long long)k, (int)count);
+    const bool wide = m < n;
+    const int M = wide ? n : m, N = wide ? m : n;
+    const int pad = ((N + 15) / 32) * 32 + 16, odd = N | 1;
+    const struct { bool w, v, g; int ld; } plans[] = {{true, true, true, pad},    {true, true, true, odd},    {false, true, true, pad}, {false, true, true, odd},
+                                                      {false, false, true, pad},  {false, false, true, odd},  {false, false, false, N}};
+    int pi = 0;
+    while (pi < 6 && bsc_lds_bytes<R>(M, N, plans[pi].ld, plans[pi].w, plans[pi].v, plans[pi].g) > BID_MAX_LDS) ++pi;
+    const bool w_lds = plans[pi].w, v_lds = plans[pi].v, g_lds = plans[pi].g;
+    const int ldg = plans[pi].ld;
+    const size_t lds = bsc_lds_bytes<R>(M, N, ldg, w_lds, v_lds, g_lds);
+    auto kern = w_lds   ? k_batched_svd_c<R, true, true, true>
+                : v_lds ? k_batched_svd_c<R, false, true, true>
+                : g_lds ? k_batched_svd_c<R, false, false, true>
+                        : k_batched_svd_c<R, false, false, false>;
+    static bool attr_set[64] = {};
+    if (!attr_set[c->device & 63]) {
+        for (const void *f : {reinterpret_cast<const void *>(k_batched_svd_c<R, true, true, true>), reinterpret_cast<const void *>(k_batched_svd_c<R, false, true, true>),
+                              reinterpret_cast<const void *>(k_batched_svd_c<R, false, false, true>),
+                              reinterpret_cast<const void *>(k_batched_svd_c<R, false, false, false>)})
+            RC_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BID_MAX_LDS));
+        attr_set[c->device & 63] = true;
+    }
+    const size_t per = bsc_ws_elems(M, N, ldg, w_lds, v_lds, g_lds);
+    const int64_t grid = bid_grid(c, reinterpret_cast<const void *>(kern), lds, per * sizeof(cx<R>), count);
+    cx<R> *ws = per ? c->alloc<cx<R>>((size_t)grid * per) : nullptr;
+    // the work orientation's U (M x k) and V^H (k x N): u and vt, or for a wide matrix the plain transposed views vt^T and u^T
+    auto tr = [](const CView<R> &v) { return CView<R>{v.p, v.cols, v.rows, v.cs, v.rs}; };
+    const CView<R> uo = wide ? tr(vt) : u, vo = wide ? tr(u) : vt;
+    const int64_t uobs = wide ? vbs : ubs, vobs = wide ? ubs : vbs;
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BIC_THREADS), lds, c->stream, a, abs, (int)count, (int)k, tol, uo, uobs, vo, vobs, s, ranks, ws,
+                       c->health_word(), ldg);
+}
+
 template void batched_column_id_c<double>(rc_context *, const rc_matrix &, int64_t, int32_t, int64_t, double, const rc_matrix &, int64_t, const rc_matrix &,
                                           int64_t, int64_t *, int64_t *);
 template void batched_column_id_c<float>(rc_context *, const rc_matrix &, int64_t, int32_t, int64_t, double, const rc_matrix &, int64_t, const rc_matrix &,
@@ -430,5 +813,10 @@ template void batched_two_sided_id_c<double>(rc_context *, const rc_matrix &, in
                                              const rc_matrix &, int64_t, const rc_matrix &, int64_t, int64_t *, int64_t *, int64_t *);
 template void batched_two_sided_id_c<float>(rc_context *, const rc_matrix &, int64_t, int32_t, int64_t, double, const rc_matrix &, int64_t,
                                             const rc_matrix &, int64_t, const rc_matrix &, int64_t, int64_t *, int64_t *, int64_t *);
+
+template void batched_svd_c<double>(rc_context *, const rc_matrix &, int64_t, int32_t, int64_t, double, const rc_matrix &, int64_t, double *,
+                                    const rc_matrix &, int64_t, int64_t *);
+template void batched_svd_c<float>(rc_context *, const rc_matrix &, int64_t, int32_t, int64_t, double, const rc_matrix &, int64_t, float *,
+                                   const rc_matrix &, int64_t, int64_t *);
 
 }  // namespace rc

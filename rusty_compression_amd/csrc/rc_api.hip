@@ -1056,6 +1056,9 @@ template int64_t check_two_sided_id_rank_batched<double>(Mat<double>, int32_t, i
                                                          int64_t, const int64_t *, const int64_t *, const int64_t *);
 template int64_t check_two_sided_id_rank_batched<float>(Mat<float>, int32_t, int64_t, double, Mat<float>, int64_t, Mat<float>, int64_t, Mat<float>, int64_t,
                                                         const int64_t *, const int64_t *, const int64_t *);
+template int64_t check_svd_rank_batched<double>(Mat<double>, int32_t, int64_t, double, Mat<double>, int64_t, const double *, Mat<double>, int64_t,
+                                                const int64_t *);
+template int64_t check_svd_rank_batched<float>(Mat<float>, int32_t, int64_t, double, Mat<float>, int64_t, const float *, Mat<float>, int64_t, const int64_t *);
 
 }  // namespace rc
 

@@ -219,13 +219,17 @@ template <typename R> void batched_column_id_c(rc_context *c, const rc_matrix &a
 template <typename R> void batched_two_sided_id_c(rc_context *c, const rc_matrix &a, int64_t abs, int32_t count, int64_t k, double tol, const rc_matrix &cm,
                                                   int64_t cbs, const rc_matrix &x, int64_t xbs, const rc_matrix &z, int64_t zbs, int64_t *row_ind,
                                                   int64_t *col_ind, int64_t *ranks);
-// the argument checks of rc_column_id_rank_batched_* / rc_two_sided_id_rank_batched_* (rc_api.hip), shared by every scalar type: the
+template <typename R> void batched_svd_c(rc_context *c, const rc_matrix &a, int64_t abs, int32_t count, int64_t k, double tol, const rc_matrix &u, int64_t ubs,
+                                         R *s, const rc_matrix &vt, int64_t vbs, int64_t *ranks);
+// the argument checks of rc_column_id_rank_batched_* / rc_two_sided_id_rank_batched_* / rc_svd_rank_batched_* (rc_api.hip), shared by every scalar type: the
 // views carry the shapes and strides (in elements of the scalar type), the pointers only their null-ness.  Return k clamped to
 // min(m, n); the caller returns when count == 0.
 template <typename T> int64_t check_column_id_rank_batched(Mat<T> a, int32_t count, int64_t k, double tol, Mat<T> cm, int64_t cbs, Mat<T> z, int64_t zbs,
                                                            const int64_t *col_ind, const int64_t *ranks);
 template <typename T> int64_t check_two_sided_id_rank_batched(Mat<T> a, int32_t count, int64_t k, double tol, Mat<T> cm, int64_t cbs, Mat<T> x, int64_t xbs,
                                                               Mat<T> r, int64_t rbs, const int64_t *row_ind, const int64_t *col_ind, const int64_t *ranks);
+template <typename T> int64_t check_svd_rank_batched(Mat<T> a, int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs, const T *s, Mat<T> vt, int64_t vbs,
+                                                    const int64_t *ranks);
 // the batched kernels' dynamic-LDS cap and persistent grid (kernels_batched_id.hip): the resident workgroups of 256 threads on every
 // CU, fewer when the workspace (ws_per bytes per workgroup, 0 in the LDS variants) would pass 256 MiB unless that leaves less than
 // one workgroup per CU; never more than count

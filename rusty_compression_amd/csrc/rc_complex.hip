@@ -1366,6 +1366,16 @@ extern "C" {
             batched_two_sided_id_c<R>(ctx, a, a_batch_stride, count, k, tol, c, c_batch_stride, x, x_batch_stride, r, r_batch_stride,     \
                                       row_ind, col_ind, ranks);                                                                           \
         });                                                                                                                               \
+    }                                                                                                                                     \
+    /* singular values in the real type; u (m x k), vt = V^H (k x n) */                                                                   \
+    rc_status rc_svd_rank_batched_##SUF(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol,       \
+                                        rc_matrix u, int64_t u_batch_stride, R *s, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks) { \
+        return guarded_c(ctx, [&] {                                                                                                       \
+            k = check_svd_rank_batched<R>(shape_of<R>(a), count, k, tol, shape_of<R>(u), u_batch_stride, s, shape_of<R>(vt), vt_batch_stride, \
+                                          ranks);                                                                                         \
+            if (count == 0) return;                                                                                                       \
+            batched_svd_c<R>(ctx, a, a_batch_stride, count, k, tol, u, u_batch_stride, s, vt, vt_batch_stride, ranks);                    \
+        });                                                                                                                               \
     }
 
 RC_DEFINE_COMPLEX(c64, double, rc_complex64)
