@@ -125,12 +125,15 @@ rc_status rc_graph_destroy(rc_context *ctx, void *graph_exec);
  * launches); certifies itself like the tall-skinny path (bit 4 of the health word = its workgroups
  * could not all become resident in time) and falls back to the lazy scheme; 0 disables it. */
 /* Reproducibility.  Every entry point is deterministic: the same call with the same options on the same context state gives the
- * same bits (no atomics on results, fixed split-K reduction order).  Two settings choose between implementations of the same
+ * same bits (no atomics on results, fixed split-K reduction order).  Three settings choose between implementations of the same
  * factorization, and bits are promised PER SETTING, not across them: (i) min(RC_OPT_CONCURRENCY_HINT, RC_OPT_KERNEL_SLOTS) decides
  * how far wide products split K (a lone launch, a few kernels in flight, many): results differ by summation order; (ii) a call recorded into a
  * hipGraph cannot read scalars back, so general-shape pivoted QRs run the per-step chain there and the blocked panels eagerly:
  * same pivots on the data-determined prefix, factors equal to rounding (tests: test_captured_pivoted_qr_of_a_blocked_eligible_shape…).
  * The cfg3 pipeline (rc_rsvd_id_*) takes the same path eagerly and captured: its replays equal the eager result bit for bit.
+ * (iii) RC_OPT_FUSED_CONSUMERS selects the order and the launches of the two consumers of B in rc_rsvd_id_*; bits are promised per
+ * setting like the others (today the two settings agree bit for bit -- tests/test_gpu_fused_consumers.py -- because neither
+ * factorization changes its arithmetic, but only the per-setting promise is API).
  * Environment switches that select between implementations (measurement aids, read once per process) change rounding the same
  * way and are NOT part of the promise: RC_TSQR_FOLD (order of the small factors of the tall-skinny QR), RC_QRCP_CAND_MB (which
  * columns of a blocked panel are updated reflector by reflector and which through the block update: last bits of R12 / Z),
@@ -165,8 +168,15 @@ rc_status rc_graph_destroy(rc_context *ctx, void *graph_exec);
  * that cannot run (too many tied candidates, workgroups not co-resident in time) leaves the panel untouched and the step
  * kernels take it.  Same pivot rule; the candidates' norms are down-dated with ?laqp2's formula (their columns are kept up to
  * date, so a norm that loses its accuracy is recomputed on the spot instead of ending the panel).  0 = step kernels only. */
+/* RC_OPT_FUSED_CONSUMERS (default 1): rc_rsvd_id_* with both consumers wanted runs the pivoted QR of B = Q^H A (k x n) and the
+ * Jacobi SVD of the k x k core of B in ONE launch: the tall QR of B^T first, then one kernel whose first workgroups are the
+ * cooperative pivoted QR (one stage over all steps) and whose last two are the Jacobi's producer and consumer, then the tails of
+ * both branches.  The two factorizations are independent, and side by side they hold one of the process's kernel slots for the
+ * longer of the two instead of two slots for the sum.  Taken for f64, k = 128, shapes the cooperative QR and the tall-skinny path
+ * support, RC_OPT_FORK_BRANCHES off and min(RC_OPT_CONCURRENCY_HINT, RC_OPT_KERNEL_SLOTS) < 8; every other call, and 0, run the
+ * pivoted-QR / ID branch first and the SVD branch after it.  Certificates keep their meaning (health bits 1, 2, 4, 8, 16). */
 enum { RC_OPT_TALL_SKINNY_FAST_PATH = 1, RC_OPT_WIDE_LAZY_QRCP = 2, RC_OPT_WIDE_COOP_QRCP = 3, RC_OPT_POWER_ITERATION_FIXED = 4, RC_OPT_FORK_BRANCHES = 5,
-       RC_OPT_BLOCKED_QRCP = 6, RC_OPT_CONCURRENCY_HINT = 7, RC_OPT_COOP_PANEL = 8, RC_OPT_KERNEL_SLOTS = 9 };
+       RC_OPT_BLOCKED_QRCP = 6, RC_OPT_CONCURRENCY_HINT = 7, RC_OPT_COOP_PANEL = 8, RC_OPT_KERNEL_SLOTS = 9, RC_OPT_FUSED_CONSUMERS = 10 };
 rc_status rc_set_option(rc_context *ctx, int32_t option, int64_t value);
 /* Health word (read and cleared), OR of: 1 non-positive Cholesky pivot, 2 first CholeskyQR pass too far from orthonormal
  * (both: tall-skinny fast path inside a graph, where no fallback is possible), 4 cooperative short-wide QR could not get

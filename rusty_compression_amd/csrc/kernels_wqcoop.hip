@@ -33,6 +33,7 @@
 #include "rc_common.hpp"
 #include <cstdlib>
 #include "rc_device.hpp"
+#include "jacobi_lds.hpp"
 
 #include <chrono>
 #include <mutex>
@@ -57,7 +58,6 @@ template <typename T> struct Tol3z;
 template <> struct Tol3z<double> { static __device__ inline double v() { return 1.0536712127723509e-08; } };
 template <> struct Tol3z<float> { static __device__ inline float v() { return 2.44140625e-04f; } };
 
-#define RC_AGENT __HIP_MEMORY_SCOPE_AGENT
 __device__ inline void st_agent(double *p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, RC_AGENT); }
 __device__ inline void st_agent(float *p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, RC_AGENT); }
 __device__ inline void st_agent(long long *p, long long v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, RC_AGENT); }
@@ -144,8 +144,9 @@ struct WqCoopArgs {
 //  I7  The budget taken by the gate (a.units) is released exactly once, by the workgroup whose arrival at sync[0] is the last.
 //  I8  Stages: a later launch reads what the earlier one wrote (wf rows >= row0, pos_out, vn) across a kernel boundary on the same
 //      stream -- no in-kernel protocol; an aborted earlier stage (flag bit 4) makes the later ones return at once.
+// G, wg: number of cooperating workgroups and this one's index among them (the launch may hold other workgroups behind them)
 template <typename T, int NE, int CPG>
-__global__ __launch_bounds__(512, NE <= 4 ? 4 : 2) void k_wq_coop(WqCoopArgs<T> a) {
+__device__ inline void wq_coop_body(const WqCoopArgs<T> &a, const int G, const int wg) {
     constexpr int NG = 64;  // 8-lane groups per workgroup (512 threads: 256 VGPRs per lane, the slab needs 128)
     constexpr int NW = 8;
     constexpr int kNoInt = 0x7fffffff;
@@ -157,7 +158,6 @@ __global__ __launch_bounds__(512, NE <= 4 ? 4 : 2) void k_wq_coop(WqCoopArgs<T> 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l8 = tid & 7, g8 = tid >> 3;
     const int m = (int)a.w.rows, mp = a.mp;
     const int64_t n = a.w.cols;
-    const int G = gridDim.x, wg = blockIdx.x;
     const int c0 = wg * a.cpw;
     const int nloc = (int)((n - c0) < a.cpw ? (n - c0) : a.cpw);
     unsigned *done = a.sync, *abortw = a.sync + 1;
@@ -476,6 +476,24 @@ __global__ __launch_bounds__(512, NE <= 4 ? 4 : 2) void k_wq_coop(WqCoopArgs<T> 
     }
 }
 
+template <typename T, int NE, int CPG>
+__global__ __launch_bounds__(512, NE <= 4 ? 4 : 2) void k_wq_coop(WqCoopArgs<T> a) {
+    wq_coop_body<T, NE, CPG>(a, (int)gridDim.x, (int)blockIdx.x);
+}
+
+// One launch, two roles (f64, 128-row B).  Workgroups 0 .. g - 1 are k_wq_coop<T, 16, 4> run as ONE stage over all steps; workgroups
+// g and g + 1 are producer and consumer of the LDS Jacobi of the 128 x 128 core (jacobi_lds.hpp) on 512 threads, two pair slots per
+// 16-lane group.  The two factorizations are independent consumers of B = Q^H A: side by side they hold one kernel slot of the
+// process for max(duration) instead of two for the sum.  The roles share nothing: I1-I8 hold among the first g workgroups (G = g
+// everywhere in the body), J1-J6 between the last two; the Jacobi workgroups wait for nobody but each other (J1), so the gate's
+// budget covers the first g only.  Registers: the maximum over both roles (the QR's), hence 512 threads; dynamic LDS: the Jacobi's.
+template <typename T>
+__global__ __launch_bounds__(512, 2) void k_wq_jacobi_fused(WqCoopArgs<T> a, JacobiLdsArgs<T> ja, int g) {
+    const int wg = (int)blockIdx.x;
+    if (wg < g) wq_coop_body<T, 16, 4>(a, g, wg);
+    else jacobi_lds_body<T, 8, true, 2>(ja, wg == g + 1);
+}
+
 // ---- host side ---------------------------------------------------------------------------
 static unsigned *coop_semaphore(int device) {
     static std::mutex mu;
@@ -612,6 +630,33 @@ bool wide_coop_supported(int64_t m, int64_t n, int device) {
     return g >= 1 && g <= kCoopMaxWgs && n < (int64_t)1 << 30 && 2u * (unsigned)g <= coop_budget_units(device);
 }
 
+// arguments of one launch over all steps [0, kmax) with ne 8-row blocks per column on g workgroups (a stage narrows row0 / jend and
+// names the hand-over arrays); the protocol's words come from the context's arena
+template <typename T>
+static WqCoopArgs<T> stage_args(rc_context *c, Mat<T> w, Mat<T> wf, int64_t kmax, int64_t *jpvt, T *tau, int *flag, int ne, int g, int cpw) {
+    WqCoopArgs<T> a;
+    a.w = w;
+    a.wf = wf;
+    a.kmax = (int)kmax;
+    a.cpw = cpw;
+    a.jpvt = jpvt;
+    a.tau = tau;
+    a.mp = 8 * ne;
+    a.hdr = c->alloc<unsigned long long>((size_t)2 * g * 5);
+    a.cols = c->alloc<T>((size_t)2 * g * a.mp);
+    a.sync = c->alloc<unsigned>(4);
+    a.sem = coop_semaphore(c->device);
+    a.flag = flag;
+    a.row0 = 0;
+    a.jend = (int)kmax;
+    a.pos_in = nullptr;
+    a.pos_out = nullptr;
+    a.vn = nullptr;
+    // 512 threads x up to 256 VGPRs: one workgroup fills its CU = 2 units; the 4-block layout is held to 128 VGPRs: 1 unit
+    a.units = (ne <= 4 ? 1u : 2u) * (unsigned)g;
+    return a;
+}
+
 // w: m x n column-major input (left untouched); wf: m x n column-major output, the factorization in
 // the format of geqp3_inplace (R on/above the diagonal, the reflector below it in physical column
 // jpvt[j]); flag gets bit 4 when the kernel had to give up (wf, jpvt, tau are then garbage).
@@ -649,26 +694,12 @@ void geqp3_wide_coop(rc_context *c, Mat<T> w, Mat<T> wf, int64_t kmax, int64_t *
                 vn = c->alloc<T>((size_t)2 * n);
             }
         }
-        WqCoopArgs<T> a;
-        a.w = w;
-        a.wf = wf;
-        a.kmax = (int)kmax;
-        a.cpw = cpw;
-        a.jpvt = jpvt;
-        a.tau = tau;
-        a.mp = 8 * ne;
-        a.hdr = c->alloc<unsigned long long>((size_t)2 * g * 5);
-        a.cols = c->alloc<T>((size_t)2 * g * a.mp);
-        a.sync = c->alloc<unsigned>(4);
-        a.sem = coop_semaphore(c->device);
-        a.flag = flag;
+        WqCoopArgs<T> a = stage_args<T>(c, w, wf, kmax, jpvt, tau, flag, ne, g, cpw);
         a.row0 = (int)row0;
         a.jend = (int)jend;
         a.pos_in = first ? nullptr : pos;
         a.pos_out = last ? nullptr : pos;
         a.vn = vn;
-        // 512 threads x up to 256 VGPRs: one workgroup fills its CU = 2 units; the 4-block layout is held to 128 VGPRs: 1 unit
-        a.units = (ne <= 4 ? 1u : 2u) * (unsigned)g;
         coop_gate_launch(c, a.units, a.sync, a.hdr, 2 * g * 5);
 #define RC_COOP(NE_, CPG_) hipLaunchKernelGGL((k_wq_coop<T, NE_, CPG_>), dim3((unsigned)g), dim3(512), 0, c->stream, a)
         if (ne == 4) RC_COOP(4, 8);
@@ -681,6 +712,52 @@ void geqp3_wide_coop(rc_context *c, Mat<T> w, Mat<T> wf, int64_t kmax, int64_t *
     }
 }
 
+// ---- the pivoted QR of B and the Jacobi SVD of the 128 x 128 core in one launch (k_wq_jacobi_fused) ----
+// B: 128 x n with wide_coop_supported; core: 128 x 128 column-major.  f64 only: the f32 instance of k_wq_coop<T, 16, 4> would need
+// its own measurement.
+template <typename T>
+bool wide_coop_jacobi_supported(int64_t m, int64_t n, int device) {
+    if (!std::is_same<T, double>::value) return false;
+    return m == 8 * kLPP && stage_ne(m) == 16 && wide_coop_supported<T>(m, n, device) &&
+           jacobi_lds_bytes<T>((int)m, jacobi_pitch<T>((int)m)) <= kJacobiLdsCap;
+}
+
+// geqp3_wide_coop(w -> wf, jpvt, tau; flag bit 4 when it gave up) and jacobi_svd(core -> uc, s, vc; health bits 8 / 16) at once.
+// The Jacobi's result does not depend on whether the QR certifies.
+template <typename T>
+void geqp3_wide_coop_jacobi(rc_context *c, Mat<T> w, Mat<T> wf, int64_t kmax, int64_t *jpvt, T *tau, int *flag, Mat<T> core, Mat<T> uc, T *s, Mat<T> vc) {
+    const int64_t m = w.rows, n = w.cols;
+    RC_REQUIRE(wf.rs == 1 && wf.rows == m && wf.cols == n, RC_LAYOUT_ERROR, "geqp3_wide_coop_jacobi: column-major output required");
+    RC_REQUIRE(core.rows == m && core.cols == m && core.rs == 1 && uc.rs == 1 && vc.rs == 1, RC_LAYOUT_ERROR, "geqp3_wide_coop_jacobi: square column-major core required");
+    RC_REQUIRE(wide_coop_jacobi_supported<T>(m, n, c->device), RC_INVALID_ARGUMENT, "geqp3_wide_coop_jacobi: unsupported shape");
+    if constexpr (std::is_same<T, double>::value) {
+        kmax = std::min(kmax, std::min(m, n));
+        const int nc = (int)m, N = nc;  // (even)
+        int cpg, cpw, g;
+        stage_shape(16, n, &cpg, &cpw, &g);
+        ProfScope ps(c, "op:geqp3_wide_coop %lldx%lld + jacobi_svd n=%d wgs=%d+2", (long long)m, (long long)n, nc, g);
+        const WqCoopArgs<T> a = stage_args<T>(c, w, wf, kmax, jpvt, tau, flag, 16, g, cpw);
+        const int ld = jacobi_pitch<T>(nc);
+        const size_t lds = jacobi_lds_bytes<T>(nc, ld);
+        const size_t nrec = (size_t)kMaxSweeps * (N - 1) * (N / 2);
+        Rot<T> *log = c->alloc<Rot<T>>(nrec);
+        int *sweeps = c->alloc<int>(1);
+        int *order = c->alloc<int>((size_t)nc);
+        unsigned *vsync = c->alloc<unsigned>((size_t)nc + 1);
+        unsigned long long *chk = c->alloc<unsigned long long>(nrec);
+        const JacobiLdsArgs<T> ja{core, log, sweeps, uc, s, order, kMaxSweeps, 1, vsync, chk, c->epoch_word(), vc, c->health_word(), ld};
+        auto kern = k_wq_jacobi_fused<T>;
+        static bool attr_set[64] = {};
+        if (!attr_set[c->device & 63]) {
+            RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048));
+            attr_set[c->device & 63] = true;
+        }
+        fill_words(c, vsync, ((size_t)nc + 1) * sizeof(unsigned), 0u);  // J4
+        coop_gate_launch(c, a.units, a.sync, a.hdr, 2 * g * 5);
+        hipLaunchKernelGGL(kern, dim3((unsigned)g + 2), dim3(512), lds, c->stream, a, ja, g);
+    }
+}
+
 #ifdef RC_COOP_TIMING
 extern "C" void rc_debug_coop_timing(unsigned long long *out) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_coop_dbg), 8 * sizeof(unsigned long long)); }
 #endif
@@ -688,5 +765,9 @@ template bool wide_coop_supported<double>(int64_t, int64_t, int);
 template bool wide_coop_supported<float>(int64_t, int64_t, int);
 template void geqp3_wide_coop<double>(rc_context *, Mat<double>, Mat<double>, int64_t, int64_t *, double *, int *);
 template void geqp3_wide_coop<float>(rc_context *, Mat<float>, Mat<float>, int64_t, int64_t *, float *, int *);
+template bool wide_coop_jacobi_supported<double>(int64_t, int64_t, int);
+template bool wide_coop_jacobi_supported<float>(int64_t, int64_t, int);
+template void geqp3_wide_coop_jacobi<double>(rc_context *, Mat<double>, Mat<double>, int64_t, int64_t *, double *, int *, Mat<double>, Mat<double>, double *, Mat<double>);
+template void geqp3_wide_coop_jacobi<float>(rc_context *, Mat<float>, Mat<float>, int64_t, int64_t *, float *, int *, Mat<float>, Mat<float>, float *, Mat<float>);
 
 }  // namespace rc

@@ -449,6 +449,35 @@ void lapack_orgqr(rc_context *c, Mat<T> a, const T *tau, int64_t k, Mat<T> q) {
     }
 }
 
+static int tsqr_fold() {
+    static const int fold = [] { const char *e = getenv("RC_TSQR_FOLD"); return e ? atoi(e) : 1; }();
+    return fold;
+}
+
+// The tail of svd_core: from the SVD of the core (uc, s, vc) and the orthogonal factor of the tall QR -- qw, or q1 r2i when it
+// stayed factored -- to the factors of the matrix itself.
+template <typename T>
+void svd_finish(rc_context *c, bool transposed, bool factored, Mat<T> qw, Mat<T> q1, Mat<T> r2i, Mat<T> uc, Mat<T> vc, const T *s, Mat<T> u, Mat<T> vt) {
+    const int64_t r = uc.rows;
+    complete_left_basis(c, uc, s);  // (?gesdd: U stays orthonormal when singular values are zero; no-op otherwise)
+    Mat<T> small;
+    if (factored) {
+        small = tmp_colmajor<T>(c, r, r);
+        gemm<T>(c, 1, r2i, transposed ? vc : uc, 0, small);
+    }
+    if (!transposed) {
+        // a = Q_w R = (Q_w Uc) S Vc^T
+        if (factored) gemm<T>(c, 1, q1, small, 0, u);
+        else gemm<T>(c, 1, qw, uc, 0, u);
+        copy_mat(c, vc.t(), vt);
+    } else {
+        // a = L Q_w^T = Uc S (Q_w Vc)^T
+        copy_mat(c, uc, u);
+        if (factored) gemm<T>(c, 1, small.t(), q1.t(), 0, vt);
+        else gemm<T>(c, 1, vc.t(), qw.t(), 0, vt);
+    }
+}
+
 // ComputeSVD::compute_svd on a working matrix: wt is the TALL orientation
 // (M x r column-major, destroyed), i.e. a itself when m >= n, a^T otherwise.
 template <typename T>
@@ -458,7 +487,7 @@ void svd_core(rc_context *c, Mat<T> wt, bool transposed, Mat<T> u, T *s, Mat<T> 
     Mat<T> core = tmp_colmajor<T>(c, r, r);
     Mat<T> qw, q1, r2i;
     bool done = false;
-    static const int fold = [] { const char *e = getenv("RC_TSQR_FOLD"); return e ? atoi(e) : 1; }();
+    const int fold = tsqr_fold();
     if (c->opt_tsqr && tsqr_supported<T>(M, r)) {
         // tall: core = R ; wide: core = L = R^T  (a = L Q_w^T).  Q_w stays factored (Q1 R2^-1): R2^-1 goes into the small
         // factor that multiplies Q_w below, one pass over the tall matrix less
@@ -483,23 +512,7 @@ void svd_core(rc_context *c, Mat<T> wt, bool transposed, Mat<T> u, T *s, Mat<T> 
     }
     Mat<T> vwork = tmp_colmajor<T>(c, r, r), uc = tmp_colmajor<T>(c, r, r), vc = tmp_colmajor<T>(c, r, r);
     jacobi_svd(c, core, vwork, uc, s, vc);
-    complete_left_basis(c, uc, s);  // (?gesdd: U stays orthonormal when singular values are zero; no-op otherwise)
-    Mat<T> small;
-    if (factored) {
-        small = tmp_colmajor<T>(c, r, r);
-        gemm<T>(c, 1, r2i, transposed ? vc : uc, 0, small);
-    }
-    if (!transposed) {
-        // a = Q_w R = (Q_w Uc) S Vc^T
-        if (factored) gemm<T>(c, 1, q1, small, 0, u);
-        else gemm<T>(c, 1, qw, uc, 0, u);
-        copy_mat(c, vc.t(), vt);
-    } else {
-        // a = L Q_w^T = Uc S (Q_w Vc)^T
-        copy_mat(c, uc, u);
-        if (factored) gemm<T>(c, 1, small.t(), q1.t(), 0, vt);
-        else gemm<T>(c, 1, vc.t(), qw.t(), 0, vt);
-    }
+    svd_finish(c, transposed, factored, qw, q1, r2i, uc, vc, s, u, vt);
 }
 
 // /root/reference/src/compute_svd.rs:18-27
@@ -857,6 +870,68 @@ void rsvd_id(rc_context *c, const OpView<T> &a, int64_t k, int64_t p, Mat<T> ome
     rsvd_id_consumers(c, range, b, o);
 }
 
+// ---- the two consumers with the pivoted QR of B and the Jacobi SVD of the core in ONE launch (RC_OPT_FUSED_CONSUMERS) ----
+// With a few compressions in flight the process's kernel slots are the bound: the Jacobi of the core
+// holds a slot with two workgroups, the cooperative QRCP of B with 32.  Both only depend on B, so they share a launch.  With
+// eight or more side by side the chip is the bound and the staged QRCP (fewer CU-steps) is the right shape: not taken there.
+template <typename T>
+bool fused_consumers_qualify(rc_context *c, int64_t k, int64_t n) {
+    return c->opt_fused_consumers && c->opt_wide_coop && c->opt_tsqr && tsqr_fold() && c->lanes_in_flight() < 8 && tsqr_supported<T>(n, k) &&
+           wide_coop_jacobi_supported<T>(k, n, c->device);
+}
+
+// Order: tall QR of B^T (B^T = Q_w R, B = L Q_w^T; L = R^T is the core), then the fused launch (B -> pivoted QR, L -> its SVD), then the tails of the
+// two branches as rsvd_id_consumers / qrcp_core / svd_core have them: every kernel sees the operands it sees there, so all outputs
+// are the same bits.  Returns false, with B untouched, when the tall QR does not certify (eager calls only): the caller's
+// old order then runs.
+template <typename T>
+bool rsvd_id_consumers_fused(rc_context *c, Mat<T> range, Mat<T> b, const rc_rsvd_id_out &o) {
+    const int64_t m = range.rows, k = b.rows, n = b.cols;
+    ArenaMark mark(c);
+    Mat<T> core = tmp_colmajor<T>(c, k, k);
+    Mat<T> q1 = rowmajor(c->alloc<T>((size_t)n * even_ld(k)), n, k, even_ld(k));
+    Mat<T> r2i = rowmajor(c->alloc<T>((size_t)k * even_ld(k)), k, k, even_ld(k));
+    {
+        ProfScope ps(c, "stage:tall QR of B^T");
+        // tsqr_cholqr2_factored only READS its input (two Gram products and one application into q1): B stays where it lies for
+        // the cooperative QRCP below, and for the old order when this does not certify
+        if (!run_certified(c, [&](int *flag) { tsqr_cholqr2_factored<T>(c, b.t(), q1, r2i, core.t(), flag); })) return false;
+    }
+    Mat<T> uc = tmp_colmajor<T>(c, k, k), vc = tmp_colmajor<T>(c, k, k);
+    Mat<T> qb = tmp_colmajor<T>(c, k, k);
+    Mat<T> r = o.qr_r.data ? from_c<T>(o.qr_r) : tmp_rowmajor<T>(c, k, n);
+    int64_t *ind = o.qr_ind ? o.qr_ind : c->alloc<int64_t>((size_t)n);
+    T *tau = c->alloc<T>((size_t)k);
+    Mat<T> wf = tmp_colmajor<T>(c, k, n);
+    T *s = static_cast<T *>(o.s);
+    bool qr_done;
+    {
+        ProfScope ps(c, "stage:qrcp of B | svd of the core");
+        qr_done = run_certified(c, [&](int *flag) { geqp3_wide_coop_jacobi<T>(c, b, wf, k, ind, tau, flag, core, uc, s, vc); });
+    }
+    {
+        ProfScope ps(c, "stage:qrcp of B + column_id");
+        if (qr_done) {
+            extract_r(c, wf, ind, r);
+            form_q(c, wf, ind, tau, k, qb);
+        } else {
+            // the cooperative workgroups did not all become resident in time (eager calls only).  The SVD of the core stands (it does
+            // not depend on them) and nothing below needs B any more: the pivoted QR takes its other paths on B itself
+            qrcp_core(c, b, k, true, qb, r, ind);
+        }
+        Mat<T> q = o.qr_q.data ? from_c<T>(o.qr_q) : tmp_colmajor<T>(c, m, k);
+        gemm<T>(c, 1, range, qb, 0, q);
+        if (o.id_c.data || o.id_z.data) qr_column_id(c, q, r, ind, from_c<T>(o.id_c), from_c<T>(o.id_z));
+    }
+    {
+        ProfScope ps(c, "stage:svd of B + U=Q Ub");
+        Mat<T> ub = tmp_colmajor<T>(c, k, k);
+        svd_finish(c, /*transposed=*/true, /*factored=*/true, Mat<T>(), q1, r2i, uc, vc, s, ub, from_c<T>(o.vt));
+        gemm<T>(c, 1, range, ub, 0, from_c<T>(o.u));
+    }
+    return true;
+}
+
 // the two consumers of B = range^H A (k x n, destroyed): SVD::compute_from_range_estimate (src/svd.rs:171-183) and
 // QR::compute_from_range_estimate + column_id (src/qr.rs:311-323, :270-309); outputs have range.rows rows
 template <typename T>
@@ -868,6 +943,10 @@ void rsvd_id_consumers(rc_context *c, Mat<T> range, Mat<T> b, const rc_rsvd_id_o
     // the two consumers of B are independent: the ID branch goes to the side stream, the SVD branch stays here.  Side by side
     // (RC_OPT_FORK_BRANCHES) the ID branch works on its own copy of B, taken before the fork (the SVD branch may overwrite B);
     // one after the other the pivoted QR reads B where it lies
+    if (want_id && want_svd && !c->opt_fork && fused_consumers_qualify<T>(c, k, n)) {
+        RC_REQUIRE(!(o.id_c.data || o.id_z.data) || (o.id_c.data && o.id_z.data), RC_INVALID_ARGUMENT, "rsvd_id: id_c and id_z must be given together");
+        if (rsvd_id_consumers_fused(c, range, b, o)) return;
+    }
     Mat<T> wq;
     if (want_id && want_svd && c->opt_fork) {
         wq = tmp_colmajor<T>(c, k, n);
@@ -1336,6 +1415,7 @@ rc_status rc_set_option(rc_context *ctx, int32_t option, int64_t value) {
         case RC_OPT_COOP_PANEL: ctx->opt_coop_panel = value != 0; return RC_OK;
         case RC_OPT_CONCURRENCY_HINT: ctx->opt_lanes = (int)std::max<int64_t>(1, std::min<int64_t>(value, 1024)); return RC_OK;
         case RC_OPT_KERNEL_SLOTS: ctx->opt_slots = (int)std::max<int64_t>(1, std::min<int64_t>(value, 1024)); return RC_OK;
+        case RC_OPT_FUSED_CONSUMERS: ctx->opt_fused_consumers = value != 0; return RC_OK;
         default: ctx->last_error = "unknown option"; return RC_INVALID_ARGUMENT;
     }
 }

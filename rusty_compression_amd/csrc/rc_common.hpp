@@ -126,6 +126,7 @@ struct rc_context {
     int opt_coop_panel = 1; // RC_OPT_COOP_PANEL: cooperative register-resident panels of the blocked QRCP
     int opt_lanes = 1;      // RC_OPT_CONCURRENCY_HINT: independent compressions the host keeps in flight on this device
     int opt_slots = 4;      // RC_OPT_KERNEL_SLOTS: kernels of this process the device runs at once
+    int opt_fused_consumers = 1;  // RC_OPT_FUSED_CONSUMERS: rc_rsvd_id_* runs the pivoted QR of B and the Jacobi SVD of the core in one launch
     // compressions whose kernels actually run side by side: what every "how much of the chip is mine" decision reads
     int lanes_in_flight() const { return opt_lanes < opt_slots ? opt_lanes : opt_slots; }
     int *health = nullptr;
@@ -283,6 +284,10 @@ template <typename T> void geqp3_wide_lazy(rc_context *c, Mat<T> b, int64_t kmax
 // flag gets bit 4 (w is never written) when the workgroups could not all become resident in time
 template <typename T> bool wide_coop_supported(int64_t m, int64_t n, int device);
 template <typename T> void geqp3_wide_coop(rc_context *c, Mat<T> w, Mat<T> wf, int64_t kmax, int64_t *jpvt, T *tau, int *flag);
+// the same factorization and the Jacobi SVD of an independent 128 x 128 core in ONE launch (kernels_wqcoop.hip, k_wq_jacobi_fused)
+template <typename T> bool wide_coop_jacobi_supported(int64_t m, int64_t n, int device);
+template <typename T>
+void geqp3_wide_coop_jacobi(rc_context *c, Mat<T> w, Mat<T> wf, int64_t kmax, int64_t *jpvt, T *tau, int *flag, Mat<T> core, Mat<T> uc, T *s, Mat<T> vc);
 void coop_prepare(int device);
 // device-wide budget of the cooperative kernels, in half compute units (kernels_wqcoop.hip)
 unsigned *coop_semaphore_of(int device);
