@@ -611,8 +611,9 @@ __global__ __launch_bounds__(BID_THREADS) void k_batched_svd(Mat<T> a, int64_t a
 }  // namespace
 
 // persistent grid: the resident workgroups of every CU, fewer when the workspace (ws_per bytes per workgroup, 0 in the LDS variants)
-// would pass 256 MiB unless that leaves less than one workgroup per CU; never more than count (shared with kernels_batched_id_c.hip)
-int64_t bid_grid(rc_context *c, const void *kern, size_t lds, size_t ws_per, int32_t count) {
+// would pass 256 MiB unless that leaves less than one workgroup per CU; never more than count (shared with kernels_batched_id_c.hip).
+// *slots: the grid before that last bound, what a batch of any size can occupy (the slots= field of the profile label)
+int64_t bid_grid(rc_context *c, const void *kern, size_t lds, size_t ws_per, int32_t count, int64_t *slots) {
     static int cus_of[64] = {};
     int &cus = cus_of[c->device & 63];
     if (!cus && (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus <= 0)) cus = 256;
@@ -620,6 +621,7 @@ int64_t bid_grid(rc_context *c, const void *kern, size_t lds, size_t ws_per, int
     RC_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, BID_THREADS, lds));
     int64_t grid = (int64_t)cus * std::max(per_cu, 1);
     if (ws_per) grid = std::min<int64_t>(grid, std::max<int64_t>(cus, (int64_t)((size_t)256 << 20) / (int64_t)ws_per));
+    *slots = grid;
     return std::min<int64_t>(grid, count);
 }
 
@@ -628,7 +630,6 @@ void batched_column_id(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int6
                        int64_t *col_ind, int64_t *ranks) {
     const int m = (int)a.rows, n = (int)a.cols;
     if (count <= 0) return;
-    ProfScope ps(c, "op:batched_column_id %dx%d k=%lld count=%d", m, n, (long long)k, (int)count);
     const size_t lds_in = bid_lds_bytes<T>(m, n, true);
     const bool in_lds = lds_in <= BID_MAX_LDS;
     const size_t lds = in_lds ? lds_in : bid_lds_bytes<T>(m, n, false);
@@ -640,7 +641,10 @@ void batched_column_id(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int6
         attr_set[c->device & 63] = true;
     }
     const size_t per = (size_t)m * (size_t)n * sizeof(T);
-    const int64_t grid = bid_grid(c, reinterpret_cast<const void *>(kern), lds, in_lds ? 0 : per, count);
+    int64_t slots = 0;
+    const int64_t grid = bid_grid(c, reinterpret_cast<const void *>(kern), lds, in_lds ? 0 : per, count, &slots);
+    ProfScope ps(c, "op:batched_column_id %dx%d k=%lld count=%d grid=%lld slots=%lld plan=W:%s", m, n, (long long)k, (int)count, (long long)grid,
+                 (long long)slots, in_lds ? "lds" : "ws");
     T *ws = in_lds ? nullptr : c->alloc<T>((size_t)grid * (size_t)m * (size_t)n);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BID_THREADS), lds, c->stream, a, abs, (int)count, (int)k, tol, cm, cbs, z, zbs, col_ind, ranks, ws);
 }
@@ -651,7 +655,6 @@ void batched_two_sided_id(rc_context *c, Mat<T> a, int64_t abs, int32_t count, i
                           Mat<T> z, int64_t zbs, int64_t *row_ind, int64_t *col_ind, int64_t *ranks) {
     const int m = (int)a.rows, n = (int)a.cols;
     if (count <= 0) return;
-    ProfScope ps(c, "op:batched_two_sided_id %dx%d k=%lld count=%d", m, n, (long long)k, (int)count);
     const size_t lds_in = bts_lds_bytes<T>(m, n, (int)k, true);
     const bool in_lds = lds_in <= BID_MAX_LDS;
     const size_t lds = in_lds ? lds_in : bts_lds_bytes<T>(m, n, (int)k, false);
@@ -663,7 +666,10 @@ void batched_two_sided_id(rc_context *c, Mat<T> a, int64_t abs, int32_t count, i
         attr_set[c->device & 63] = true;
     }
     const size_t per = (size_t)m * (size_t)n * sizeof(T);
-    const int64_t grid = bid_grid(c, reinterpret_cast<const void *>(kern), lds, in_lds ? 0 : per, count);
+    int64_t slots = 0;
+    const int64_t grid = bid_grid(c, reinterpret_cast<const void *>(kern), lds, in_lds ? 0 : per, count, &slots);
+    ProfScope ps(c, "op:batched_two_sided_id %dx%d k=%lld count=%d grid=%lld slots=%lld plan=W:%s", m, n, (long long)k, (int)count, (long long)grid,
+                 (long long)slots, in_lds ? "lds" : "ws");
     T *ws = in_lds ? nullptr : c->alloc<T>((size_t)grid * (size_t)m * (size_t)n);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BID_THREADS), lds, c->stream, a, abs, (int)count, (int)k, tol, cm, cbs, x, xbs, z, zbs, row_ind,
                        col_ind, ranks, ws);
@@ -677,7 +683,6 @@ void batched_svd(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int64_t k,
                  int64_t *ranks) {
     const int m = (int)a.rows, n = (int)a.cols;
     if (count <= 0) return;
-    ProfScope ps(c, "op:batched_svd %dx%d k=%lld count=%d", m, n, (long long)k, (int)count);
     const bool wide = m < n;
     const int M = wide ? n : m, N = wide ? m : n;
     // the first plan that fits: most in LDS first, the padded pitch before the odd one (the last always fits)
@@ -697,7 +702,10 @@ void batched_svd(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int64_t k,
         attr_set[c->device & 63] = true;
     }
     const size_t per = ((w_lds ? 0 : (size_t)M * N) + (v_lds ? 0 : (size_t)N * N)) * sizeof(T);
-    const int64_t grid = bid_grid(c, reinterpret_cast<const void *>(kern), lds, per, count);
+    int64_t slots = 0;
+    const int64_t grid = bid_grid(c, reinterpret_cast<const void *>(kern), lds, per, count, &slots);
+    ProfScope ps(c, "op:batched_svd %dx%d k=%lld count=%d grid=%lld slots=%lld plan=W:%s,V:%s,G:lds,ld=%d", m, n, (long long)k, (int)count, (long long)grid,
+                 (long long)slots, w_lds ? "lds" : "ws", v_lds ? "lds" : "ws", ldg);
     T *ws = per ? c->alloc<T>((size_t)grid * per / sizeof(T)) : nullptr;
     // the work orientation's U (M x k) and V^T (k x N): u and vt, or for a wide matrix vt^T and u^T
     const Mat<T> uo = wide ? vt.t() : u, vo = wide ? u.t() : vt;

@@ -721,7 +721,6 @@ void batched_column_id_c(rc_context *c, const rc_matrix &a_, int64_t abs, int32_
     const CView<R> a = cview<R>(a_), cm = cview<R>(cm_), z = cview<R>(z_);
     const int m = (int)a.rows, n = (int)a.cols;
     if (count <= 0) return;
-    ProfScope ps(c, "op:batched_column_id<complex> %dx%d k=%lld count=%d", m, n, (long long)k, (int)count);
     const size_t lds_in = bic_lds_bytes<R>(m, n, true);
     const bool in_lds = lds_in <= BID_MAX_LDS;
     const size_t lds = in_lds ? lds_in : bic_lds_bytes<R>(m, n, false);
@@ -733,7 +732,10 @@ void batched_column_id_c(rc_context *c, const rc_matrix &a_, int64_t abs, int32_
         attr_set[c->device & 63] = true;
     }
     const size_t per = (size_t)m * (size_t)n * sizeof(cx<R>);
-    const int64_t grid = bid_grid(c, reinterpret_cast<const void *>(kern), lds, in_lds ? 0 : per, count);
+    int64_t slots = 0;
+    const int64_t grid = bid_grid(c, reinterpret_cast<const void *>(kern), lds, in_lds ? 0 : per, count, &slots);
+    ProfScope ps(c, "op:batched_column_id<complex> %dx%d k=%lld count=%d grid=%lld slots=%lld plan=W:%s", m, n, (long long)k, (int)count, (long long)grid,
+                 (long long)slots, in_lds ? "lds" : "ws");
     cx<R> *ws = in_lds ? nullptr : c->alloc<cx<R>>((size_t)grid * (size_t)m * (size_t)n);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BIC_THREADS), lds, c->stream, a, abs, (int)count, (int)k, tol, cm, cbs, z, zbs, col_ind, ranks, ws);
 }
@@ -744,7 +746,6 @@ void batched_two_sided_id_c(rc_context *c, const rc_matrix &a_, int64_t abs, int
     const CView<R> a = cview<R>(a_), cm = cview<R>(cm_), x = cview<R>(x_), z = cview<R>(z_);
     const int m = (int)a.rows, n = (int)a.cols;
     if (count <= 0) return;
-    ProfScope ps(c, "op:batched_two_sided_id<complex> %dx%d k=%lld count=%d", m, n, (long long)k, (int)count);
     const size_t lds_in = btc_lds_bytes<R>(m, n, (int)k, true);
     const bool in_lds = lds_in <= BID_MAX_LDS;
     const size_t lds = in_lds ? lds_in : btc_lds_bytes<R>(m, n, (int)k, false);
@@ -756,7 +757,10 @@ void batched_two_sided_id_c(rc_context *c, const rc_matrix &a_, int64_t abs, int
         attr_set[c->device & 63] = true;
     }
     const size_t per = (size_t)m * (size_t)n * sizeof(cx<R>);
-    const int64_t grid = bid_grid(c, reinterpret_cast<const void *>(kern), lds, in_lds ? 0 : per, count);
+    int64_t slots = 0;
+    const int64_t grid = bid_grid(c, reinterpret_cast<const void *>(kern), lds, in_lds ? 0 : per, count, &slots);
+    ProfScope ps(c, "op:batched_two_sided_id<complex> %dx%d k=%lld count=%d grid=%lld slots=%lld plan=W:%s", m, n, (long long)k, (int)count,
+                 (long long)grid, (long long)slots, in_lds ? "lds" : "ws");
     cx<R> *ws = in_lds ? nullptr : c->alloc<cx<R>>((size_t)grid * (size_t)m * (size_t)n);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BIC_THREADS), lds, c->stream, a, abs, (int)count, (int)k, tol, cm, cbs, x, xbs, z, zbs, row_ind,
                        col_ind, ranks, ws);
@@ -771,7 +775,6 @@ void batched_svd_c(rc_context *c, const rc_matrix &a_, int64_t abs, int32_t coun
     const CView<R> a = cview<R>(a_), u = cview<R>(u_), vt = cview<R>(vt_);
     const int m = (int)a.rows, n = (int)a.cols;
     if (count <= 0) return;
-    ProfScope ps(c, "op:batched_svd<complex> %dx%d k=%lld count=%d", m, n, (long long)k, (int)count);
     const bool wide = m < n;
     const int M = wide ? n : m, N = wide ? m : n;
     const int pad = ((N + 15) / 32) * 32 + 16, odd = N | 1;
@@ -795,7 +798,10 @@ void batched_svd_c(rc_context *c, const rc_matrix &a_, int64_t abs, int32_t coun
         attr_set[c->device & 63] = true;
     }
     const size_t per = bsc_ws_elems(M, N, ldg, w_lds, v_lds, g_lds);
-    const int64_t grid = bid_grid(c, reinterpret_cast<const void *>(kern), lds, per * sizeof(cx<R>), count);
+    int64_t slots = 0;
+    const int64_t grid = bid_grid(c, reinterpret_cast<const void *>(kern), lds, per * sizeof(cx<R>), count, &slots);
+    ProfScope ps(c, "op:batched_svd<complex> %dx%d k=%lld count=%d grid=%lld slots=%lld plan=W:%s,V:%s,G:%s,ld=%d", m, n, (long long)k, (int)count,
+                 (long long)grid, (long long)slots, w_lds ? "lds" : "ws", v_lds ? "lds" : "ws", g_lds ? "lds" : "ws", ldg);
     cx<R> *ws = per ? c->alloc<cx<R>>((size_t)grid * per) : nullptr;
     // the work orientation's U (M x k) and V^H (k x N): u and vt, or for a wide matrix the plain transposed views vt^T and u^T
     auto tr = [](const CView<R> &v) { return CView<R>{v.p, v.cols, v.rows, v.cs, v.rs}; };

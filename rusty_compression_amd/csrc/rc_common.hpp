@@ -233,9 +233,9 @@ template <typename T> int64_t check_svd_rank_batched(Mat<T> a, int32_t count, in
                                                     const int64_t *ranks);
 // the batched kernels' dynamic-LDS cap and persistent grid (kernels_batched_id.hip): the resident workgroups of 256 threads on every
 // CU, fewer when the workspace (ws_per bytes per workgroup, 0 in the LDS variants) would pass 256 MiB unless that leaves less than
-// one workgroup per CU; never more than count
+// one workgroup per CU; never more than count.  *slots receives the grid before that last bound (slots= in the profile label)
 constexpr size_t BID_MAX_LDS = 160 * 1024 - 1024;
-int64_t bid_grid(rc_context *c, const void *kern, size_t lds, size_t ws_per, int32_t count);
+int64_t bid_grid(rc_context *c, const void *kern, size_t lds, size_t ws_per, int32_t count, int64_t *slots);
 void invert_perm(rc_context *c, const int64_t *perm, int64_t n, int64_t *inv);
 void fill_words(rc_context *c, void *p, size_t bytes, unsigned v);  // every 32-bit word of [p, p + bytes) = v, by a kernel on c->stream (no hipMemset*)
 void iota_i64(rc_context *c, int64_t *p, int64_t n);

@@ -105,3 +105,41 @@ def greedy_pivot_slack(a, r, ind, k):
         slack.append((mx - abs(r[j, j])) / mx if mx > 0 else 0.0)
         vn2 = vn2 - r[j] ** 2
     return slack
+
+
+def batched_launch(fn, ctx=None):
+    """Run fn() with the event profile of `ctx` (default: the default context) switched on and return (fn's result, the fields
+    of the single op:batched_* label it recorded):
+        op:batched_svd<complex> 512x128 k=64 count=641 grid=256 slots=256 plan=W:ws,V:ws,G:lds,ld=144
+    -> {"op": "batched_svd<complex>", "m": 512, "n": 128, "k": 64, "count": 641, "grid": 256, "slots": 256, "plan": "W:ws,V:ws,G:lds,ld=144"}.
+    grid is the launched grid, slots the persistent grid before it is bounded by count, plan where the working copy W, the rotations
+    V and the core G live (lds or the workgroup's workspace slot, ws) and the core's column pitch (the IDs have W alone)."""
+    import ctypes
+    import re
+
+    from rusty_compression_amd import _lib
+
+    ctx = ctx or _lib.default_context()
+    lib = _lib.lib()
+    labels = []
+    ctx.check(lib.rc_profile_enable(ctx._h, 1))
+    try:
+        ctx.check(lib.rc_profile_reset(ctx._h))
+        out = fn()
+        cnt = ctypes.c_int32(0)
+        ctx.check(lib.rc_profile_count(ctx._h, ctypes.byref(cnt)))
+        for i in range(cnt.value):
+            name = ctypes.create_string_buffer(192)
+            ms, calls = ctypes.c_double(0), ctypes.c_int64(0)
+            ctx.check(lib.rc_profile_get(ctx._h, i, name, 192, ctypes.byref(ms), ctypes.byref(calls)))
+            if name.value.decode().startswith("op:batched_"):
+                labels.append((name.value.decode(), calls.value))
+    finally:
+        lib.rc_profile_enable(ctx._h, 0)
+        lib.rc_profile_reset(ctx._h)
+    assert len(labels) == 1 and labels[0][1] == 1, labels
+    mt = re.fullmatch(r"op:(batched_\S+) (\d+)x(\d+) k=(\d+) count=(\d+) grid=(\d+) slots=(\d+) plan=(\S+)", labels[0][0])
+    assert mt, labels[0][0]
+    f = dict(zip(("m", "n", "k", "count", "grid", "slots"), map(int, mt.groups()[1:7])))
+    f.update(op=mt.group(1), plan=mt.group(8))
+    return out, f

@@ -13,7 +13,7 @@ import torch
 import rusty_compression_amd as rc
 from oracle import ref_lapack as o
 from rusty_compression_amd import _lib
-from tests.helpers import TOL, golden, npy, sign_normalise
+from tests.helpers import TOL, batched_launch, golden, npy, sign_normalise
 
 pytestmark = pytest.mark.gpu
 
@@ -197,13 +197,14 @@ def test_bits_independent_of_position_neighbours_and_count():
     rng = np.random.default_rng(5)
     m, n, k = 64, 48, 16
     x = decaying(rng, m, n, np.float64)
-    alone = batched(torch.from_numpy(x[None]).cuda(), k, 1e-6)
-    big = torch.from_numpy(rng.standard_normal((2 * 256 + 37, m, n))).cuda()
+    alone, probe = batched_launch(lambda: batched(torch.from_numpy(x[None]).cuda(), k, 1e-6))
+    big = torch.from_numpy(rng.standard_normal((2 * probe["slots"] + 37, m, n))).cuda()  # slots: the persistent grid of this shape
     big[5] *= 1e-3  # different neighbours, among them a tiny one
     for sl in (len(big) // 2, len(big) - 1):
         b = big.clone()
         b[sl] = torch.from_numpy(x)
-        got = batched(b, k, 1e-6)
+        got, lab = batched_launch(lambda: batched(b, k, 1e-6))
+        assert lab["count"] > 2 * lab["grid"]  # both positions are some workgroup's second or third matrix
         for v, w in zip(alone, got):
             assert np.array_equal(v[0], w[sl])
 

@@ -16,7 +16,7 @@ import rusty_compression_amd as rc
 from oracle import ref_lapack as o
 from rusty_compression_amd import _lib
 from rusty_compression_amd.batch import column_id_rank
-from tests.helpers import TOL, agreed_pivot_prefix, is_permutation, npy, rel
+from tests.helpers import TOL, agreed_pivot_prefix, batched_launch, is_permutation, npy, rel
 
 pytestmark = pytest.mark.gpu
 
@@ -203,13 +203,14 @@ def test_bits_independent_of_position_and_neighbours():
     rng = np.random.default_rng(16)
     m, n, k = 64, 48, 16
     a = phased(rng, m, n, C64)
-    alone = two_sided(torch.from_numpy(a[None]).cuda(), k, 1e-6)
-    big = torch.from_numpy(gaussian(rng, (4 * 256 + 37) * m, n, C64).reshape(-1, m, n)).cuda()
+    alone, probe = batched_launch(lambda: two_sided(torch.from_numpy(a[None]).cuda(), k, 1e-6))
+    big = torch.from_numpy(gaussian(rng, (2 * probe["slots"] + 37) * m, n, C64).reshape(-1, m, n)).cuda()  # slots: this shape's persistent grid
     big[5] *= 1e-3  # different neighbours, among them a tiny one
     for s in (len(big) // 2, len(big) - 1):
         b = big.clone()
         b[s] = torch.from_numpy(a)
-        got = two_sided(b, k, 1e-6)
+        got, lab = batched_launch(lambda: two_sided(b, k, 1e-6))
+        assert lab["count"] > 2 * lab["grid"]  # both positions are some workgroup's second or third matrix
         for u, v in zip(alone, got):
             assert np.array_equal(u[0], v[s])
 
