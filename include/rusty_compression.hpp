@@ -128,6 +128,7 @@ template <typename T> struct Api;
         static constexpr auto column_id_rank_batched = rc_column_id_rank_batched_##SUF;                             \
         static constexpr auto two_sided_id_rank_batched = rc_two_sided_id_rank_batched_##SUF;                       \
         static constexpr auto svd_rank_batched = rc_svd_rank_batched_##SUF;                                         \
+        static constexpr auto lowrank_apply_batched = rc_lowrank_apply_batched_##SUF;                               \
     };
 RC_API(double, f64, f64)
 RC_API(float, f32, f32)
@@ -588,6 +589,49 @@ BatchedSVD<T> svd_rank_batched(const DeviceMatrix<T> &a, int32_t count, int64_t 
                                            rc_matrix{out.u.view().data, m, kk, kk, 1}, m * kk, out.s.data(), rc_matrix{out.vt.view().data, kk, n, n, 1},
                                            kk * n, out.ranks.data()));
     return out;
+}
+// apply (b: count * n x nrhs, block i in rows i n .. (i + 1) n - 1) or rebuild (b == nullptr) every block of a batch from its stacked
+// factors in one rank-aware call (rc_lowrank_apply_batched_*; Apply::dot and to_mat, src/col_interp_decomp.rs:63-65, :134-154,
+// src/two_sided_interp_decomp.rs:62-65, :159-170, src/svd.rs:42-55): left is count * m x k, right count * k x n, mid count * k x k or
+// nullptr, s count x s_stride reals or nullptr, ranks count values or nullptr (every rank is k); returns y, count * m x nrhs (or n)
+template <typename T>
+DeviceMatrix<T> lowrank_apply_batched(const DeviceMatrix<T> &left, const DeviceMatrix<T> *mid, const DeviceBuffer<typename Scalar<T>::real> *s,
+                                      const DeviceMatrix<T> &right, const DeviceIndex *ranks, int32_t count, const DeviceMatrix<T> *b) {
+    const int64_t m = count > 0 ? left.nrows() / count : 0, k = left.ncols(), n = right.ncols();
+    const int64_t ncols = b ? b->ncols() : n, p = s && count > 0 ? (int64_t)(s->size() / (std::size_t)count) : 0;
+    DeviceMatrix<T> y(left.ctx(), (int64_t)count * m, ncols);
+    const rc_matrix none{nullptr, 0, 0, 0, 0};
+    left.ctx().check(Api<T>::lowrank_apply_batched(left.ctx().raw(), rc_matrix{left.view().data, m, k, k, 1}, m * k,
+                                                   mid ? rc_matrix{mid->view().data, k, k, k, 1} : none, k * k, s ? s->data() : nullptr, p,
+                                                   rc_matrix{right.view().data, k, n, n, 1}, k * n, ranks ? ranks->data() : nullptr, count,
+                                                   b ? rc_matrix{b->view().data, n, ncols, ncols, 1} : none, n * ncols,
+                                                   rc_matrix{y.view().data, m, ncols, ncols, 1}, m * ncols));
+    return y;
+}
+// Apply::dot and to_mat of the three batched decompositions, each block at its own rank
+template <typename T>
+DeviceMatrix<T> apply_batched(const BatchedColumnID<T> &id, const DeviceMatrix<T> &b) {
+    return lowrank_apply_batched<T>(id.c, nullptr, nullptr, id.z, &id.ranks, (int32_t)id.ranks.size(), &b);
+}
+template <typename T>
+DeviceMatrix<T> to_mat_batched(const BatchedColumnID<T> &id) {
+    return lowrank_apply_batched<T>(id.c, nullptr, nullptr, id.z, &id.ranks, (int32_t)id.ranks.size(), nullptr);
+}
+template <typename T>
+DeviceMatrix<T> apply_batched(const BatchedTwoSidedID<T> &id, const DeviceMatrix<T> &b) {
+    return lowrank_apply_batched<T>(id.c, &id.x, nullptr, id.r, &id.ranks, (int32_t)id.ranks.size(), &b);
+}
+template <typename T>
+DeviceMatrix<T> to_mat_batched(const BatchedTwoSidedID<T> &id) {
+    return lowrank_apply_batched<T>(id.c, &id.x, nullptr, id.r, &id.ranks, (int32_t)id.ranks.size(), nullptr);
+}
+template <typename T>
+DeviceMatrix<T> apply_batched(const BatchedSVD<T> &svd, const DeviceMatrix<T> &b) {
+    return lowrank_apply_batched<T>(svd.u, nullptr, &svd.s, svd.vt, &svd.ranks, (int32_t)svd.ranks.size(), &b);
+}
+template <typename T>
+DeviceMatrix<T> to_mat_batched(const BatchedSVD<T> &svd) {
+    return lowrank_apply_batched<T>(svd.u, nullptr, &svd.s, svd.vt, &svd.ranks, (int32_t)svd.ranks.size(), nullptr);
 }
 template <typename T>
 typename Scalar<T>::real max_col_norm(const DeviceMatrix<T> &y) {  // :184-191

@@ -520,6 +520,35 @@ rc_status rc_svd_rank_batched_f64(rc_context *ctx, rc_matrix a, int64_t a_batch_
 rc_status rc_svd_rank_batched_f32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix u, int64_t u_batch_stride, float *s, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks);
 rc_status rc_svd_rank_batched_c64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix u, int64_t u_batch_stride, double *s, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks);
 rc_status rc_svd_rank_batched_c32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix u, int64_t u_batch_stride, float *s, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks);
+/* Apply, or rebuild, every block of such a batch from its factors in one stream-ordered, capturable call that reads the ranks on the
+ * device: the reference's Apply::dot (vector and matrix) and to_mat of the column ID (src/col_interp_decomp.rs:63-65, :134-154), the
+ * two-sided ID (src/two_sided_interp_decomp.rs:62-65, :159-170) and the SVD (src/svd.rs:42-55) for the outputs of the three batched
+ * calls above.  One entry point covers the three factor forms:
+ *   left  (m x k)  C of the column ID, C of the two-sided ID, U of the SVD
+ *   mid   (k x k)  X of the two-sided ID; mid.data == NULL: none
+ *   s              the SVD's singular values: row i = s + i * s_stride, at least k reals (double for f64 / c64, float for f32 / c32); NULL: none
+ *   right (k x n)  Z, R, Vt
+ *   ranks          count device values; NULL: every rank is k
+ *   b     (n x nrhs) the right-hand sides; b.data == NULL: reconstruct (to_mat)
+ *   y     (m x nrhs), or m x n when reconstructing
+ * Block i of every operand is its view moved by i times its batch stride (0 is legal for the inputs, for example one b shared by all
+ * blocks); any row and column strides; y must not overlap an input; every pointer a device pointer.  With r = ranks[i] clamped to
+ * [0, k] (k without ranks), per block: W = right_i[:r, :] b_i (W = right_i[:r, :] when reconstructing); with s, W = diag(s_i[:r]) W;
+ * with mid, W = mid_i[:r, :r] W; y_i = left_i[:, :r] W; r = 0 gives y_i = 0.  Nothing is conjugated (vt is already V^H).  The
+ * transposed apply A^T x is the same call with left = right^T and right = left^T passed as strided views (rows and columns and their
+ * strides swapped).  Elements of left, mid, s and right at an index >= r are never read: they may hold anything, NaN included, so the
+ * result does not rely on the zero tails the batched calls write.  Block i's bits depend on block i's operands, their row and column
+ * strides and the call's shapes alone: not on count, the neighbours, any batch stride, the grid, or graph replay against an eager call
+ * (each output element is summed in a fixed order).  Domain: 1 <= m, n <= 512, 1 <= k <= 128, nrhs >= 1, count >= 0 (0: nothing to
+ * do).  RC_INVALID_ARGUMENT for an argument outside the domain, inconsistent shapes (left.cols != right.rows, mid not k x k,
+ * b.rows != n, y not m x nrhs, or not m x n when reconstructing), a y batch stride smaller than one view's span, a null left, right or
+ * y pointer with count > 0, or a null ctx.  No host synchronisation, no workspace: the r x nrhs intermediate never leaves the chip.
+ * Complex scalars (c64, c32): the same signature and contract with interleaved (re, im) data, strides and batch strides in complex
+ * elements; s has the real type. */
+rc_status rc_lowrank_apply_batched_f64(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const double *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix b, int64_t b_batch_stride, rc_matrix y, int64_t y_batch_stride);
+rc_status rc_lowrank_apply_batched_f32(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const float *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix b, int64_t b_batch_stride, rc_matrix y, int64_t y_batch_stride);
+rc_status rc_lowrank_apply_batched_c64(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const double *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix b, int64_t b_batch_stride, rc_matrix y, int64_t y_batch_stride);
+rc_status rc_lowrank_apply_batched_c32(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const float *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix b, int64_t b_batch_stride, rc_matrix y, int64_t y_batch_stride);
 
 /* The gather over RCCL (xGMI inside a node).  One process per GPU: rank 0 calls rc_comm_unique_id and hands the 128
  * bytes to the other ranks by whatever means the host has (MPI, a file, torch.distributed), every rank calls

@@ -168,6 +168,83 @@ def svd_rank_batched_complex(a: torch.Tensor, k: int, tol: float = 0.0) -> Tuple
     return u, s, vt, ranks
 
 
+def lowrank_apply_batched(left: torch.Tensor, right: torch.Tensor, b: Optional[torch.Tensor] = None, mid: Optional[torch.Tensor] = None,
+                          s: Optional[torch.Tensor] = None, ranks: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Apply, or rebuild, every block of a batch from its factors in one stream-ordered call (rc_lowrank_apply_batched_*): the
+    reference's Apply::dot and to_mat (src/col_interp_decomp.rs:63-65, :134-154, src/two_sided_interp_decomp.rs:62-65, :159-170,
+    src/svd.rs:42-55) for the outputs of the batched IDs and SVDs.
+
+    left: [count, m, k], right: [count, k, n], mid: [count, k, k] or None, s: [count, p >= k] of the real dtype or None, ranks:
+    [count] int64 or None (every rank is k); device tensors of one scalar type (float64, float32, complex128, complex64), any strides
+    (a stride-0 batch dimension shares one operand).  b: [count, n, nrhs], or [count, n] for vectors, or None to reconstruct.  With
+    r = ranks[i] clamped to [0, k], block i of the result is left[i][:, :r] mid[i][:r, :r] diag(s[i][:r]) right[i][:r] b[i] (absent
+    factors omitted, nothing conjugated); nothing at an index >= r is read.  Returns y: [count, m, nrhs], [count, m] or [count, m, n]."""
+    from . import _lib
+    from .types import as_device
+
+    ops = {"left": left, "right": right, "b": b, "mid": mid}
+    ops = {name: as_device(t).resolve_conj() for name, t in ops.items() if t is not None}  # the kernels read the stored values
+    left, right, b, mid = ops["left"], ops["right"], ops.get("b"), ops.get("mid")
+    for name, t in ops.items():
+        if t.dtype != left.dtype:
+            raise TypeError(f"lowrank_apply_batched: {name} is {t.dtype}, left is {left.dtype}")
+    if left.dim() != 3 or right.dim() != 3 or (mid is not None and mid.dim() != 3) or (b is not None and b.dim() not in (2, 3)):
+        raise AssertionError("expected left [count, m, k], right [count, k, n], mid [count, k, k] and b [count, n, nrhs] or [count, n]")
+    count, m, k = left.shape
+    n = right.shape[2]
+    for name, t in ops.items():
+        if t.shape[0] != count:
+            raise AssertionError(f"lowrank_apply_batched: {name} holds {t.shape[0]} blocks, left {count}")
+    if s is not None:
+        s = as_device(s)
+        if s.dtype != _lib.real_dtype(left.dtype):
+            raise TypeError(f"lowrank_apply_batched: s is {s.dtype}, expected {_lib.real_dtype(left.dtype)}")
+        if s.dim() != 2 or s.shape[0] != count or s.shape[1] < k:
+            raise AssertionError(f"lowrank_apply_batched: s must be [count, p] with p >= k = {k}")
+        if s.stride(1) != 1:
+            s = s.contiguous()
+    if ranks is not None:
+        ranks = as_device(ranks)
+        if ranks.dtype != torch.int64:
+            raise TypeError(f"lowrank_apply_batched: ranks is {ranks.dtype}, expected torch.int64")
+        if ranks.shape != (count,):
+            raise AssertionError("lowrank_apply_batched: ranks must be [count]")
+        ranks = ranks.contiguous()
+    vector = b is not None and b.dim() == 2
+    if vector:
+        b = b.unsqueeze(2)
+    ncols = n if b is None else b.shape[2]
+    y = torch.empty((count, m, ncols), dtype=left.dtype, device=left.device)
+
+    def view(t):  # block 0's view and the batch stride
+        if t is None:
+            return _lib.mat(None), ctypes.c_int64(0)
+        return _lib.rc_matrix(t.data_ptr(), t.shape[1], t.shape[2], t.stride(1), t.stride(2)), ctypes.c_int64(t.stride(0))
+
+    _lib.default_context().call(f"rc_lowrank_apply_batched_{_lib.suffix(left.dtype)}", *view(left), *view(mid),
+                                ctypes.c_void_p(s.data_ptr() if s is not None else None), ctypes.c_int64(s.stride(0) if s is not None else 0),
+                                *view(right), _lib.i64p(ranks), ctypes.c_int32(count), *view(b),
+                                _lib.rc_matrix(y.data_ptr(), m, ncols, ncols, 1), ctypes.c_int64(m * ncols))
+    return y[:, :, 0] if vector else y
+
+
+def column_id_apply_batched(c: torch.Tensor, z: torch.Tensor, ranks: Optional[torch.Tensor], b: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ColumnID dot / to_mat for the outputs of column_id_rank_batched: C[:, :r] Z[:r] b per block, or C[:, :r] Z[:r] with b = None."""
+    return lowrank_apply_batched(c, z, b=b, ranks=ranks)
+
+
+def two_sided_id_apply_batched(c: torch.Tensor, x: torch.Tensor, r: torch.Tensor, ranks: Optional[torch.Tensor],
+                               b: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """TwoSidedID dot / to_mat for the outputs of two_sided_id_rank_batched: C X R b per block at its rank, or C X R with b = None."""
+    return lowrank_apply_batched(c, r, b=b, mid=x, ranks=ranks)
+
+
+def svd_apply_batched(u: torch.Tensor, s: torch.Tensor, vt: torch.Tensor, ranks: Optional[torch.Tensor], b: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """SVD dot / to_mat for the outputs of svd_rank_batched / svd_rank_batched_complex: U diag(s) Vt b per block at its rank, or U diag(s) Vt
+    with b = None; s is the [count, p] tensor those calls return, read with row stride p."""
+    return lowrank_apply_batched(u, vt, b=b, s=s, ranks=ranks)
+
+
 def packed_bytes(m: int, n: int, k: int, elem_size: int) -> int:
     """Bytes one matrix's factors take in the packed buffer: C (m x k) | Z (k x n) | pad to 8 | col_ind (n int64)
     (rc_batch_packed_bytes)."""

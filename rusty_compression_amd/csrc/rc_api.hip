@@ -1127,6 +1127,28 @@ int64_t check_svd_rank_batched(Mat<T> a, int32_t count, int64_t k, double tol, M
     return k;
 }
 
+// rc_lowrank_apply_batched_*: the shapes of the factor chain left (m x k) [mid (k x k)] right (k x n) [b (n x nrhs)] -> y, the batched kernels' domain
+// for m, n, k, and y's batch stride; mid and b take part only when their data pointer is set
+template <typename T>
+void check_lowrank_apply_batched(Mat<T> left, Mat<T> mid, Mat<T> right, int32_t count, Mat<T> b, Mat<T> y, int64_t ybs) {
+    const char *who = "lowrank_apply_batched";
+    const int64_t m = left.rows, k = left.cols, n = right.cols;
+    RC_REQUIRE(count >= 0, RC_INVALID_ARGUMENT, "%s: count = %d < 0", who, (int)count);
+    RC_REQUIRE(m >= 1 && m <= 512 && n >= 1 && n <= 512 && k >= 1 && k <= 128, RC_INVALID_ARGUMENT,
+               "%s: needs 1 <= m, n <= 512 and 1 <= k <= 128 (got left %lld x %lld, right %lld x %lld)", who, (long long)m, (long long)k,
+               (long long)right.rows, (long long)n);
+    RC_REQUIRE(right.rows == k, RC_INVALID_ARGUMENT, "%s: left is %lld x %lld but right has %lld rows", who, (long long)m, (long long)k, (long long)right.rows);
+    RC_REQUIRE(!mid.p || (mid.rows == k && mid.cols == k), RC_INVALID_ARGUMENT, "%s: mid must be %lld x %lld (got %lld x %lld)", who, (long long)k,
+               (long long)k, (long long)mid.rows, (long long)mid.cols);
+    RC_REQUIRE(!b.p || (b.rows == n && b.cols >= 1 && b.cols <= INT32_MAX), RC_INVALID_ARGUMENT, "%s: b must be %lld x nrhs with nrhs >= 1 (got %lld x %lld)",
+               who, (long long)n, (long long)b.rows, (long long)b.cols);
+    const int64_t ncols = b.p ? b.cols : n;
+    RC_REQUIRE(y.rows == m && y.cols == ncols, RC_INVALID_ARGUMENT, "%s: y must be %lld x %lld (got %lld x %lld)", who, (long long)m, (long long)ncols,
+               (long long)y.rows, (long long)y.cols);
+    check_batch_stride(who, "y", ybs, y, count);
+    if (count > 0) RC_REQUIRE(left.p && right.p && y.p, RC_INVALID_ARGUMENT, "%s: null pointer", who);
+}
+
 template int64_t check_column_id_rank_batched<double>(Mat<double>, int32_t, int64_t, double, Mat<double>, int64_t, Mat<double>, int64_t, const int64_t *,
                                                       const int64_t *);
 template int64_t check_column_id_rank_batched<float>(Mat<float>, int32_t, int64_t, double, Mat<float>, int64_t, Mat<float>, int64_t, const int64_t *,
@@ -1138,6 +1160,8 @@ template int64_t check_two_sided_id_rank_batched<float>(Mat<float>, int32_t, int
 template int64_t check_svd_rank_batched<double>(Mat<double>, int32_t, int64_t, double, Mat<double>, int64_t, const double *, Mat<double>, int64_t,
                                                 const int64_t *);
 template int64_t check_svd_rank_batched<float>(Mat<float>, int32_t, int64_t, double, Mat<float>, int64_t, const float *, Mat<float>, int64_t, const int64_t *);
+template void check_lowrank_apply_batched<double>(Mat<double>, Mat<double>, Mat<double>, int32_t, Mat<double>, Mat<double>, int64_t);
+template void check_lowrank_apply_batched<float>(Mat<float>, Mat<float>, Mat<float>, int32_t, Mat<float>, Mat<float>, int64_t);
 
 }  // namespace rc
 
@@ -1169,6 +1193,15 @@ void svd_rank_batched(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int64
     k = check_svd_rank_batched(a, count, k, tol, u, ubs, s, vt, vbs, ranks);
     if (count == 0) return;
     batched_svd(c, a, abs, count, k, tol, u, ubs, s, vt, vbs, ranks);
+}
+
+// apply (b given) or rebuild (b.p == nullptr) every block of a batch from its factors, reading the ranks on the device: one launch, no workspace
+template <typename T>
+void lowrank_apply_batched(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride, Mat<T> right, int64_t rbs,
+                           const int64_t *ranks, int32_t count, Mat<T> b, int64_t bbs, Mat<T> y, int64_t ybs) {
+    check_lowrank_apply_batched(left, mid, right, count, b, y, ybs);
+    if (count == 0) return;
+    batched_lowrank_apply(c, left, lbs, mid, mbs, s, s_stride, right, rbs, ranks, count, b, bbs, y, ybs);
 }
 
 template <typename T>
@@ -1718,6 +1751,14 @@ rc_status rc_invert_permutation(rc_context *ctx, const int64_t *perm, int64_t n,
         return guarded(ctx, [&] {                                                                                                        \
             svd_rank_batched<T>(ctx, from_c<T>(a), a_batch_stride, count, k, tol, from_c<T>(u), u_batch_stride, s, from_c<T>(vt),         \
                                 vt_batch_stride, ranks);                                                                                 \
+        });                                                                                                                              \
+    }                                                                                                                                    \
+    rc_status rc_lowrank_apply_batched_##SUF(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, \
+                                             const T *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, \
+                                             int32_t count, rc_matrix b, int64_t b_batch_stride, rc_matrix y, int64_t y_batch_stride) {  \
+        return guarded(ctx, [&] {                                                                                                        \
+            lowrank_apply_batched<T>(ctx, from_c<T>(left), left_batch_stride, from_c<T>(mid), mid_batch_stride, s, s_stride, from_c<T>(right), \
+                                     right_batch_stride, ranks, count, from_c<T>(b), b_batch_stride, from_c<T>(y), y_batch_stride);     \
         });                                                                                                                              \
     }
 

@@ -231,6 +231,16 @@ template <typename T> int64_t check_two_sided_id_rank_batched(Mat<T> a, int32_t 
                                                               Mat<T> r, int64_t rbs, const int64_t *row_ind, const int64_t *col_ind, const int64_t *ranks);
 template <typename T> int64_t check_svd_rank_batched(Mat<T> a, int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs, const T *s, Mat<T> vt, int64_t vbs,
                                                     const int64_t *ranks);
+// apply or rebuild the factors of such a batch in one rank-aware launch (kernels_batched_apply.hip): block i is left (m x k), mid (k x k, p == nullptr:
+// none), right (k x n), b (n x nrhs, p == nullptr: reconstruct) and y each moved by i times its batch stride, s + i * s_stride its k real scales (nullptr:
+// none), ranks count device values (nullptr: every rank is k); the complex twin takes interleaved-complex views (arguments checked by the caller)
+template <typename T> void batched_lowrank_apply(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride, Mat<T> right,
+                                                 int64_t rbs, const int64_t *ranks, int32_t count, Mat<T> b, int64_t bbs, Mat<T> y, int64_t ybs);
+template <typename R> void batched_lowrank_apply_c(rc_context *c, const rc_matrix &left, int64_t lbs, const rc_matrix &mid, int64_t mbs, const R *s,
+                                                   int64_t s_stride, const rc_matrix &right, int64_t rbs, const int64_t *ranks, int32_t count,
+                                                   const rc_matrix &b, int64_t bbs, const rc_matrix &y, int64_t ybs);
+// the argument checks of rc_lowrank_apply_batched_* (rc_api.hip), shared by every scalar type like the three above; the caller returns when count == 0
+template <typename T> void check_lowrank_apply_batched(Mat<T> left, Mat<T> mid, Mat<T> right, int32_t count, Mat<T> b, Mat<T> y, int64_t ybs);
 // the batched kernels' dynamic-LDS cap and persistent grid (kernels_batched_id.hip): the resident workgroups of 256 threads on every
 // CU, fewer when the workspace (ws_per bytes per workgroup, 0 in the LDS variants) would pass 256 MiB unless that leaves less than
 // one workgroup per CU; never more than count.  *slots receives the grid before that last bound (slots= in the profile label)

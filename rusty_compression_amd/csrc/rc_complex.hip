@@ -1376,6 +1376,18 @@ extern "C" {
             if (count == 0) return;                                                                                                       \
             batched_svd_c<R>(ctx, a, a_batch_stride, count, k, tol, u, u_batch_stride, s, vt, vt_batch_stride, ranks);                    \
         });                                                                                                                               \
+    }                                                                                                                                     \
+    /* apply / rebuild the factors of a batch (kernels_batched_apply.hip): the real entry point's checks on views of the same shapes */   \
+    rc_status rc_lowrank_apply_batched_##SUF(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, \
+                                             const R *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, \
+                                             int32_t count, rc_matrix b, int64_t b_batch_stride, rc_matrix y, int64_t y_batch_stride) {   \
+        return guarded_c(ctx, [&] {                                                                                                       \
+            check_lowrank_apply_batched<R>(shape_of<R>(left), shape_of<R>(mid), shape_of<R>(right), count, shape_of<R>(b), shape_of<R>(y), \
+                                           y_batch_stride);                                                                               \
+            if (count == 0) return;                                                                                                       \
+            batched_lowrank_apply_c<R>(ctx, left, left_batch_stride, mid, mid_batch_stride, s, s_stride, right, right_batch_stride, ranks, \
+                                       count, b, b_batch_stride, y, y_batch_stride);                                                      \
+        });                                                                                                                               \
     }
 
 RC_DEFINE_COMPLEX(c64, double, rc_complex64)
