@@ -549,6 +549,39 @@ rc_status rc_lowrank_apply_batched_f64(rc_context *ctx, rc_matrix left, int64_t 
 rc_status rc_lowrank_apply_batched_f32(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const float *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix b, int64_t b_batch_stride, rc_matrix y, int64_t y_batch_stride);
 rc_status rc_lowrank_apply_batched_c64(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const double *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix b, int64_t b_batch_stride, rc_matrix y, int64_t y_batch_stride);
 rc_status rc_lowrank_apply_batched_c32(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const float *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix b, int64_t b_batch_stride, rc_matrix y, int64_t y_batch_stride);
+/* Recompress every factor pair of such a batch to a truncated SVD without forming the m x n blocks, in one stream-ordered, capturable
+ * call: rounded addition of low-rank blocks (U1 S1 V1^T + U2 S2 V2^T is the pair [U1 U2] diag(s1, s2) [V1^T; V2^T] of inner width
+ * K = k1 + k2), the conversion of a batched column or two-sided ID into an SVD, and re-truncation.  Per block the reference's scheme
+ * of SVD::to_qr and compute_from_range_estimate (src/svd.rs:150-163, :171-): factor the thin factors, take the SVD of the small core,
+ * multiply back; the rank rule is SVDTraits::compress's (src/svd.rs:60-101).  Real scalars only.
+ * Inputs as rc_lowrank_apply_batched_*: left (m x K), mid (K x K; mid.data == NULL: none), s (row i = s + i * s_stride, at least K
+ * reals; NULL: none), right (K x n), in_ranks (count device values; NULL: every inner rank is K).  Block i of every operand is its
+ * view moved by i times its batch stride (0 is legal for the inputs); any row and column strides; every pointer a device pointer.
+ * Outputs as rc_svd_rank_batched_*: u (m x kk) and vt (kk x n) with kk = min(k, K), each moved by its own batch stride; s_out
+ * (count x K) and ranks (count) contiguous.  The outputs must not overlap the inputs or one another.
+ * Per block, with q = in_ranks[i] clamped to [0, K] and A_i = left[:, :q] mid[:q, :q] diag(s[:q]) right[:q, :] (absent factors omitted):
+ *   s_out[i, :q] are the q singular values of A_i in descending order, s_out[i, q:K] is zero;
+ *   ranks[i] = r = the first j < min(kk, q) with s_j == 0 or (tol > 0 and s_j / s_0 < tol), else min(kk, q);
+ *   u[:, :r], vt[:r, :] are the leading singular vectors, columns r..kk-1 of u and rows r..kk-1 of vt are zero;
+ *   signs as rc_svd_rank_batched_*: the first largest-|.| entry of each kept column of u is positive;
+ *   q = 0 gives rank 0 and all-zero outputs.
+ * Elements of left, mid, s and right at an index >= q are never read: they may hold anything, NaN included.  An exactly zero column
+ * of left inside the first q (the zero tails the batched SVD writes, after a concatenation) gives an exactly zero singular value,
+ * so at tol = 0 the rank stops at the number of nonzero columns.  Block i's bits depend on block i's operands, their row and column
+ * strides and the call's shapes alone: not on count, the neighbours, any batch stride, the grid, or graph replay against an eager
+ * call.  Non-finite input stays inside its block's outputs (values unspecified, 0 <= r <= kk).  A block whose Jacobi iteration uses
+ * up its sweep budget ORs bit 16 into the health word.  Accuracy: backward stable with respect to the factors, that is errors of a
+ * few eps ||left_q||_2 ||mid diag(s)||_2 ||right_q||_2, which cancellation between the factors can make large relative to s_0.
+ * Per block: pivoted Householder QR of left[:, :q] and of right[:q, :]^T (q steps each), the q x q core
+ * R_L P_L^T mid diag(s) P_R R_R^T summed in a fixed order, one-sided Jacobi on its transpose, U = Q_L [U_c; 0], V = Q_R [V_c; 0]:
+ * O((m + n) q^2) work instead of the O(m n min(m, n)) of rebuilding the block, and no limit of 128 on min(m, n).
+ * Domain: 1 <= m, n <= 512, 1 <= K <= 128, K <= min(m, n), k >= 1, 0 <= tol < 1, count >= 0 (0: nothing to do).  A pair with
+ * K > min(m, n) is cheaper through rc_lowrank_apply_batched_* (to_mat) followed by rc_svd_rank_batched_*.  RC_INVALID_ARGUMENT for an
+ * argument outside the domain, inconsistent shapes (left.cols != right.rows, mid not K x K, u not m x kk, vt not kk x n), an output
+ * batch stride smaller than one view's span, a null left, right, u, s_out, vt or ranks with count > 0, or a null ctx.  No host
+ * synchronisation; workspace bounded by the grid, not by count. */
+rc_status rc_lowrank_recompress_batched_f64(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const double *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *in_ranks, int32_t count, int64_t k, double tol, rc_matrix u, int64_t u_batch_stride, double *s_out, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks);
+rc_status rc_lowrank_recompress_batched_f32(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const float *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *in_ranks, int32_t count, int64_t k, double tol, rc_matrix u, int64_t u_batch_stride, float *s_out, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks);
 
 /* The gather over RCCL (xGMI inside a node).  One process per GPU: rank 0 calls rc_comm_unique_id and hands the 128
  * bytes to the other ranks by whatever means the host has (MPI, a file, torch.distributed), every rank calls

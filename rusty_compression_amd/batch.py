@@ -245,6 +245,94 @@ def svd_apply_batched(u: torch.Tensor, s: torch.Tensor, vt: torch.Tensor, ranks:
     return lowrank_apply_batched(u, vt, b=b, s=s, ranks=ranks)
 
 
+def lowrank_recompress_batched(left: torch.Tensor, right: torch.Tensor, k: int, tol: float = 0.0, mid: Optional[torch.Tensor] = None,
+                               s: Optional[torch.Tensor] = None,
+                               ranks: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Recompress every factor pair of a batch to a truncated SVD without forming the blocks, in one stream-ordered call
+    (rc_lowrank_recompress_batched_*): the scheme of the reference's SVD::to_qr / compute_from_range_estimate (src/svd.rs:150-163, :171-)
+    with compress's rank rule (src/svd.rs:60-101).
+
+    left: [count, m, K], right: [count, K, n], mid: [count, K, K] or None, s: [count, p >= K] or None, ranks: [count] int64 or None
+    (every inner rank is K); float64 or float32 device tensors, any strides (a stride-0 batch dimension shares one operand);
+    K <= min(m, n), K <= 128, m, n <= 512.  With q = ranks[i] clamped to [0, K], block i is A_i = left[i][:, :q] mid[i][:q, :q]
+    diag(s[i][:q]) right[i][:q] (absent factors omitted; nothing at an index >= q is read).  Returns U [count, m, kk], S [count, K]
+    (the q singular values of A_i, descending, then zeros), Vt [count, kk, n] and the new ranks [count], kk = min(k, K): the rank of a
+    block is the first j < min(kk, q) with s_j == 0 or s_j / s_0 < tol, else min(kk, q); columns of U and rows of Vt past it are zero
+    and the largest-|.| entry of each kept column of U is positive.  Complex data raises TypeError."""
+    from . import _lib
+    from .types import as_device
+
+    ops = {"left": left, "right": right, "mid": mid, "s": s}
+    ops = {name: as_device(t) for name, t in ops.items() if t is not None}
+    left, right, mid, s = ops["left"], ops["right"], ops.get("mid"), ops.get("s")
+    if left.dtype not in (torch.float64, torch.float32):
+        raise TypeError(f"lowrank_recompress_batched: float64 or float32 data expected, got {left.dtype}")
+    for name, t in ops.items():
+        if t.dtype != left.dtype:
+            raise TypeError(f"lowrank_recompress_batched: {name} is {t.dtype}, left is {left.dtype}")
+    if left.dim() != 3 or right.dim() != 3 or (mid is not None and mid.dim() != 3):
+        raise AssertionError("expected left [count, m, K], right [count, K, n] and mid [count, K, K]")
+    count, m, kin = left.shape
+    n = right.shape[2]
+    for name, t in ops.items():
+        if t.shape[0] != count:
+            raise AssertionError(f"lowrank_recompress_batched: {name} holds {t.shape[0]} blocks, left {count}")
+    if s is not None:
+        if s.dim() != 2 or s.shape[1] < kin:
+            raise AssertionError(f"lowrank_recompress_batched: s must be [count, p] with p >= K = {kin}")
+        if s.stride(1) != 1:
+            s = s.contiguous()
+    if ranks is not None:
+        ranks = as_device(ranks)
+        if ranks.dtype != torch.int64:
+            raise TypeError(f"lowrank_recompress_batched: ranks is {ranks.dtype}, expected torch.int64")
+        if ranks.shape != (count,):
+            raise AssertionError("lowrank_recompress_batched: ranks must be [count]")
+        ranks = ranks.contiguous()
+    kk = max(min(int(k), kin), 0)
+    u = torch.empty((count, m, kk), dtype=left.dtype, device=left.device)
+    s_out = torch.empty((count, kin), dtype=left.dtype, device=left.device)
+    vt = torch.empty((count, kk, n), dtype=left.dtype, device=left.device)
+    out_ranks = torch.empty(count, dtype=torch.int64, device=left.device)
+
+    def view(t):  # block 0's view and the batch stride
+        if t is None:
+            return _lib.mat(None), ctypes.c_int64(0)
+        return _lib.rc_matrix(t.data_ptr(), t.shape[1], t.shape[2], t.stride(1), t.stride(2)), ctypes.c_int64(t.stride(0))
+
+    _lib.default_context().call(f"rc_lowrank_recompress_batched_{_lib.suffix(left.dtype)}", *view(left), *view(mid),
+                                ctypes.c_void_p(s.data_ptr() if s is not None else None), ctypes.c_int64(s.stride(0) if s is not None else 0),
+                                *view(right), _lib.i64p(ranks), ctypes.c_int32(count), ctypes.c_int64(int(k)), ctypes.c_double(float(tol)),
+                                _lib.rc_matrix(u.data_ptr(), m, kk, kk, 1), ctypes.c_int64(m * kk), ctypes.c_void_p(s_out.data_ptr()),
+                                _lib.rc_matrix(vt.data_ptr(), kk, n, n, 1), ctypes.c_int64(kk * n), _lib.i64p(out_ranks))
+    return u, s_out, vt, out_ranks
+
+
+def column_id_to_svd_batched(c: torch.Tensor, z: torch.Tensor, ranks: Optional[torch.Tensor], k: int,
+                             tol: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Truncated SVDs of the blocks C[:, :r] Z[:r] held by the outputs of column_id_rank_batched, each at its own rank."""
+    return lowrank_recompress_batched(c, z, k, tol, ranks=ranks)
+
+
+def two_sided_id_to_svd_batched(c: torch.Tensor, x: torch.Tensor, r: torch.Tensor, ranks: Optional[torch.Tensor], k: int,
+                                tol: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Truncated SVDs of the blocks C X R held by the outputs of two_sided_id_rank_batched, each at its own rank."""
+    return lowrank_recompress_batched(c, r, k, tol, mid=x, ranks=ranks)
+
+
+def svd_add_batched(u1: torch.Tensor, s1: torch.Tensor, vt1: torch.Tensor, u2: torch.Tensor, s2: torch.Tensor, vt2: torch.Tensor, k: int,
+                    tol: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Rounded addition of two batches of truncated SVDs (the outputs of svd_rank_batched or of this module's recompressions):
+    block i of the result is the SVD of U1 diag(s1) Vt1 + U2 diag(s2) Vt2, truncated to rank <= k by tol.  The factors are concatenated
+    to inner width K = k1 + k2 (K <= min(m, n), K <= 128) and recompressed; columns of U1, U2 past a block's rank are zero, as the
+    batched SVD writes them, and come out as exactly zero singular values."""
+    k1, k2 = u1.shape[2], u2.shape[2]
+    left = torch.cat([u1, u2], dim=2)
+    right = torch.cat([vt1, vt2], dim=1)
+    s = torch.cat([s1[:, :k1], s2[:, :k2]], dim=1)
+    return lowrank_recompress_batched(left, right, k, tol, s=s)
+
+
 def packed_bytes(m: int, n: int, k: int, elem_size: int) -> int:
     """Bytes one matrix's factors take in the packed buffer: C (m x k) | Z (k x n) | pad to 8 | col_ind (n int64)
     (rc_batch_packed_bytes)."""

@@ -19,6 +19,9 @@
 //
 // Batched truncated SVD (rc_svd_rank_batched_*): k_batched_svd, the same grid and the same first two stages run to all N steps,
 // then one-sided Jacobi on the transposed triangular factor and U formed from the kept reflectors (see its comment below).
+//
+// Batched recompression (rc_lowrank_recompress_batched_*): k_batched_recompress, the same grid and stages on the two thin factors of
+// a low-rank block, the same Jacobi on their small core, both Q's applied by the same reflector routine (see its comment below).
 #include "rc_common.hpp"
 #include "rc_device.hpp"
 
@@ -355,7 +358,9 @@ __global__ __launch_bounds__(BID_THREADS) void k_batched_two_sided(Mat<T> a, int
 // 30-sweep budget.  Everything stays inside one workgroup.
 
 // Jacobi rows per lane of a 16-lane pair group (N <= 16 NE) and rows per lane of a 64-lane U column (M <= 64 NE)
-template <typename T, int NE>
+// WIDE (the recompression): both threshold tests are evaluated in f64, so that in f32 two columns of norm 1e-9 or less, whose
+// app aqq and apq^2 pass the smallest f32 number, are still rotated until they are orthogonal; without it the text is the batched SVD's
+template <typename T, int NE, bool WIDE = false>
 __device__ __forceinline__ void bsv_round(T *G, int ldg, T *J, int ldj, int N, int p, int q, T tol, T tol2, int ll, int *flag) {
     T *gp = G + (size_t)p * ldg, *gq = G + (size_t)q * ldg;
     T a[NE], b[NE];
@@ -373,7 +378,11 @@ __device__ __forceinline__ void bsv_round(T *G, int ldg, T *J, int ldj, int N, i
     aqq = group_sum_dpp<16>(aqq);
     apq = group_sum_dpp<16>(apq);
     // k_jacobi_lds's test and thresholds: rotate iff |apq| > tol sqrt(app aqq) (uniform over the 16 lanes)
-    if (!(apq * apq > tol2 * app * aqq)) return;
+    if constexpr (WIDE) {
+        if (!((double)apq * (double)apq > (double)tol2 * (double)app * (double)aqq)) return;
+    } else {
+        if (!(apq * apq > tol2 * app * aqq)) return;
+    }
     T c, s;
     jacobi_rotation(app, aqq, apq, c, s);
     T *vp = J + (size_t)p * ldj, *vq = J + (size_t)q * ldj;
@@ -388,12 +397,16 @@ __device__ __forceinline__ void bsv_round(T *G, int ldg, T *J, int ldj, int N, i
             vq[i] = s * x + c * y;
         }
     }
-    if (ll == 0 && (apq * apq > tol * (T)0.0625 * app * aqq || s * s > (T)16 * tol)) *flag = 2;  // plain store: every writer writes 2
+    if constexpr (WIDE) {
+        if (ll == 0 && ((double)apq * (double)apq > (double)tol * 0.0625 * (double)app * (double)aqq || s * s > (T)16 * tol)) *flag = 2;
+    } else {
+        if (ll == 0 && (apq * apq > tol * (T)0.0625 * app * aqq || s * s > (T)16 * tol)) *flag = 2;  // plain store: every writer writes 2
+    }
 }
 
 // one-sided Jacobi of the N x N core G (columns ldg apart) with the rotations accumulated in J (ldj); round-robin pairs, 16 lanes per pair, the 16
 // groups of the workgroup walk the N / 2 pair slots of a round.  Returns false when kMaxSweeps ran out before a quiet sweep.
-template <typename T, int NE>
+template <typename T, int NE, bool WIDE = false>
 __device__ __forceinline__ bool bsv_jacobi(T *G, int ldg, T *J, int ldj, int N, int tid, int *flag) {
     const int ll = tid & 15, grp = tid >> 4;
     constexpr int NGRP = BID_THREADS / 16;
@@ -406,7 +419,7 @@ __device__ __forceinline__ bool bsv_jacobi(T *G, int ldg, T *J, int ldj, int N, 
             for (int pi = grp; pi < npairs; pi += NGRP) {
                 int p, q;
                 rr_pair(N2, r, pi, p, q);
-                if (q < N) bsv_round<T, NE>(G, ldg, J, ldj, N, p, q, tol, tol2, ll, flag);  // q == N: the dummy column of an odd N
+                if (q < N) bsv_round<T, NE, WIDE>(G, ldg, J, ldj, N, p, q, tol, tol2, ll, flag);  // q == N: the dummy column of an odd N
             }
             __syncthreads();  // the pairs of a round are disjoint; the next round re-pairs the columns
         }
@@ -608,6 +621,196 @@ __global__ __launch_bounds__(BID_THREADS) void k_batched_svd(Mat<T> a, int64_t a
     }
 }
 
+// ---- batched recompression of low-rank factors (rc_lowrank_recompress_batched_*) -----------------------------------------------
+// Per block, with q = in_ranks[b] clamped to [0, K]: A = left[:, :q] mid[:q, :q] diag(s[:q]) right[:q, :] is never formed.  The two
+// thin factors are factored where they stand, left[:, :q] P_L = Q_L R_L and right[:q, :]^T P_R = Q_R R_R (bid_qrcp to q steps each,
+// reflectors kept), so A = Q_L C Q_R^T with the q x q core C = R_L P_L^T mid diag(s) P_R^T R_R^T; the rest is k_batched_svd on the
+// core: one-sided Jacobi on G = C^T with the rotations in J (C^T J = V_c Sigma, J = U_c), singular values = the column norms of G,
+// U = Q_L [U_c; 0] and V = Q_R [V_c; 0] by backward reflector application straight into the output views.  O((m + n) q^2) work.
+// G = C^T, not C: an exactly zero column of left is pivoted last and is a step with H = I, which leaves a zero row in R_L, hence a
+// zero row of C = a zero column of G, and the rotation test (apq^2 > tol^2 app aqq, false for apq = 0) never touches a zero column:
+// its singular value comes out as exactly 0.
+//
+// The core is formed by two q x q x q products in LDS, one thread per element, summed over the inner index in ascending order:
+//   T1[a, j] = sum_b mid[a, b] s[b] Rr[j, b]   (T1 in J's place: J = I only afterwards)
+//   C[i, j]  = sum_a Rl[i, a] T1[a, j]         (stored as G[i * ldg + j]: column i of G = row i of C)
+// where Rl[:, c] is the upper-triangular column R_L P_L^T keeps for the factor's own column c (rows 0 .. ip[c] of the working copy's
+// column c, ip the inverse of the pivot order), Rr likewise.  The lanes run along j: T1, Wr and G are read and written at consecutive
+// addresses and mid[a, b], Rl[i, a] are one broadcast address per wave.
+
+template <typename T>
+struct BrcArgs {
+    Mat<T> left, mid, right, u, vt;
+    int64_t lbs, mbs, rbs, ubs, vbs, s_stride;
+    const T *s;
+    const int64_t *in_ranks;
+    T *s_out;
+    int64_t *ranks;
+    T *ws;
+    int *health;
+    double tol;
+    int count, k, ldg;
+    bool l_lds, r_lds, v_lds;  // the copy of left / of right^T / the rotations J in LDS (else in the workgroup's workspace slot)
+};
+
+// LDS: [Wl: K x (m|1)] [Wr: K x (n|1)] G: K x ldg [J: K x ldg] vn1[K] vn2[K] taul[K] taur[K] sig[K] red[8]
+// | jpl[K] jpr[K] ipl[K] ipr[K] srt[K] sgn[128] flag[4] (ints last: the T arrays stay aligned)
+template <typename T>
+size_t brc_lds_bytes(int m, int n, int K, int ldg, bool l_lds, bool r_lds, bool v_lds) {
+    size_t t = (size_t)K * ldg + 5 * (size_t)K + 8;
+    if (l_lds) t += (size_t)K * (size_t)(m | 1);
+    if (r_lds) t += (size_t)K * (size_t)(n | 1);
+    if (v_lds) t += (size_t)K * ldg;
+    return t * sizeof(T) + (size_t)(5 * K + 128 + 4) * sizeof(int);
+}
+__host__ __device__ inline size_t brc_ws_elems(int m, int n, int K, bool l_lds, bool r_lds, bool v_lds) {
+    return (l_lds ? 0 : (size_t)m * K) + (r_lds ? 0 : (size_t)n * K) + (v_lds ? 0 : (size_t)K * K);
+}
+
+template <typename T>
+__global__ __launch_bounds__(BID_THREADS) void k_batched_recompress(BrcArgs<T> a) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const int m = (int)a.left.rows, n = (int)a.right.cols, K = (int)a.left.cols;
+    const int kk = a.k < K ? a.k : K, ldg = a.ldg;
+    const int ldl = a.l_lds ? (m | 1) : m, ldr = a.r_lds ? (n | 1) : n, ldj = a.v_lds ? ldg : K;
+    T *lds = reinterpret_cast<T *>(smem_raw);
+    T *wsb = a.ws + (size_t)blockIdx.x * brc_ws_elems(m, n, K, a.l_lds, a.r_lds, a.v_lds);
+    T *Wl = lds, *Wr = lds + (a.l_lds ? (size_t)K * ldl : 0);
+    T *G = Wr + (a.r_lds ? (size_t)K * ldr : 0);
+    T *J = G + (size_t)K * ldg;
+    T *vn1 = J + (a.v_lds ? (size_t)K * ldg : 0);
+    if (!a.l_lds) { Wl = wsb; wsb += (size_t)m * K; }
+    if (!a.r_lds) { Wr = wsb; wsb += (size_t)n * K; }
+    if (!a.v_lds) J = wsb;
+    T *vn2 = vn1 + K, *taul = vn2 + K, *taur = taul + K, *sig = taur + K, *red = sig + K;
+    int *jpl = reinterpret_cast<int *>(red + 8);
+    int *jpr = jpl + K, *ipl = jpr + K, *ipr = ipl + K, *srt = ipr + K, *sgn = srt + K, *flag = sgn + 128;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+
+    for (int b = blockIdx.x; b < a.count; b += gridDim.x) {
+        int q = K;
+        if (a.in_ranks) {
+            const int64_t rv = a.in_ranks[b];
+            q = rv < 0 ? 0 : rv > K ? K : (int)rv;
+        }
+        q = __builtin_amdgcn_readfirstlane(q);  // one value per block, uniform by construction
+        T *sb = a.s_out + (int64_t)b * K;
+        T *Ub = a.u.p + (int64_t)b * a.ubs, *Vb = a.vt.p + (int64_t)b * a.vbs;
+        for (int i = q + tid; i < K; i += BID_THREADS) sb[i] = (T)0;
+        if (q == 0) {  // uniform over the workgroup; no input is read
+            if (tid == 0) a.ranks[b] = 0;
+            for (int c = wv; c < kk; c += BID_WAVES) {
+                for (int i = lane; i < m; i += 64) Ub[i * a.u.rs + c * a.u.cs] = (T)0;
+                for (int i = lane; i < n; i += 64) Vb[c * a.vt.rs + i * a.vt.cs] = (T)0;
+            }
+            continue;
+        }
+        // ---- the two pivoted QRs, q steps each (exact zero pivots are steps with H = I), taus and pivots kept -----------------------
+        const T *__restrict__ L = a.left.p + (int64_t)b * a.lbs;
+        const T *__restrict__ R = a.right.p + (int64_t)b * a.rbs;
+        bid_load(Wl, ldl, m, q, a.left.rs <= a.left.cs, [&](int i, int c) { return L[i * a.left.rs + c * a.left.cs]; }, vn1, vn2, jpl, wv, lane);
+        bid_qrcp<T, true>(Wl, ldl, m, q, q, 0.0, jpl, vn1, vn2, red, tid, wv, lane, taul);
+        bid_load(Wr, ldr, n, q, a.right.cs <= a.right.rs, [&](int i, int c) { return R[c * a.right.rs + i * a.right.cs]; }, vn1, vn2, jpr, wv, lane);
+        bid_qrcp<T, true>(Wr, ldr, n, q, q, 0.0, jpr, vn1, vn2, red, tid, wv, lane, taur);
+        for (int j = tid; j < q; j += BID_THREADS) { ipl[jpl[j]] = j; ipr[jpr[j]] = j; }
+        __syncthreads();
+        // ---- T1 = mid diag(s) Rr^T in J's place ----------------------------------------------------------------------------------------
+        const T *__restrict__ Mb = a.mid.p ? a.mid.p + (int64_t)b * a.mbs : nullptr;
+        const T *__restrict__ Sb = a.s ? a.s + (int64_t)b * a.s_stride : nullptr;
+        for (int idx = tid; idx < q * q; idx += BID_THREADS) {
+            const int ai = idx / q, j = idx - ai * q;
+            T acc;
+            if (Mb) {
+                acc = 0;
+                const T *mr = Mb + (int64_t)ai * a.mid.rs;
+                for (int bb = 0; bb < q; ++bb) {
+                    const T rv = j <= ipr[bb] ? Wr[(size_t)bb * ldr + j] : (T)0;
+                    const T mv = Sb ? mr[(int64_t)bb * a.mid.cs] * Sb[bb] : mr[(int64_t)bb * a.mid.cs];
+                    acc = fma(mv, rv, acc);
+                }
+            } else {
+                const T rv = j <= ipr[ai] ? Wr[(size_t)ai * ldr + j] : (T)0;
+                acc = Sb ? Sb[ai] * rv : rv;
+            }
+            J[(size_t)ai * ldj + j] = acc;
+        }
+        __syncthreads();
+        // ---- G = C^T: G[i * ldg + j] = sum_a Rl[i, a] T1[a, j] ----------------------------------------------------------------------
+        for (int idx = tid; idx < q * q; idx += BID_THREADS) {
+            const int i = idx / q, j = idx - i * q;
+            T acc = 0;
+            for (int aa = 0; aa < q; ++aa) {
+                const T lv = i <= ipl[aa] ? Wl[(size_t)aa * ldl + i] : (T)0;
+                acc = fma(lv, J[(size_t)aa * ldj + j], acc);
+            }
+            G[(size_t)i * ldg + j] = acc;
+        }
+        __syncthreads();
+        for (int idx = tid; idx < q * q; idx += BID_THREADS) {
+            const int j = idx / q, i = idx - j * q;
+            J[(size_t)j * ldj + i] = i == j ? (T)1 : (T)0;
+        }
+        __syncthreads();
+        bool conv;
+        if (q <= 16) conv = bsv_jacobi<T, 1, true>(G, ldg, J, ldj, q, tid, flag);
+        else if (q <= 32) conv = bsv_jacobi<T, 2, true>(G, ldg, J, ldj, q, tid, flag);
+        else if (q <= 64) conv = bsv_jacobi<T, 4, true>(G, ldg, J, ldj, q, tid, flag);
+        else conv = bsv_jacobi<T, 8, true>(G, ldg, J, ldj, q, tid, flag);
+        if (!conv && tid == 0) atomicOr(a.health, 16);  // the sweep budget ran out: bit 16, as the batched SVD reports it
+        // ---- singular values: column norms, sorted descending (a strict total order: NaN last, ties by column) ----------------------
+        for (int j = tid >> 4; j < q; j += BID_THREADS / 16) {
+            const T *gj = G + (size_t)j * ldg;
+            T acc = 0;
+            for (int i = tid & 15; i < q; i += 16) acc = fma(gj[i], gj[i], acc);
+            acc = group_sum_dpp<16>(acc);
+            if ((tid & 15) == 0) sig[j] = sqrt(acc);
+        }
+        __syncthreads();
+        for (int i = tid; i < q; i += BID_THREADS) {
+            const T ki = sig[i] >= (T)0 ? sig[i] : (T)-1;
+            int pos = 0;
+            for (int j = 0; j < q; ++j) {
+                const T kj = sig[j] >= (T)0 ? sig[j] : (T)-1;
+                pos += (kj > ki || (kj == ki && j < i)) ? 1 : 0;
+            }
+            srt[pos] = i;
+            sb[pos] = sig[i];
+        }
+        __syncthreads();
+        // ---- rank: the first j < min(kk, q) with s_j == 0 or (tol > 0 and s_j / s_0 < tol), else min(kk, q) -------------------------
+        if (tid == 0) {
+            const T s0 = sig[srt[0]];
+            const int kq = kk < q ? kk : q;
+            int r = kq;
+            for (int j = 0; j < kq; ++j) {
+                const T sj = sig[srt[j]];
+                if (sj == (T)0 || (a.tol > 0.0 && (double)(sj / s0) < a.tol)) { r = j; break; }
+            }
+            flag[1] = r;
+            a.ranks[b] = r;
+        }
+        __syncthreads();
+        const int r = flag[1];
+        // ---- U = Q_L [J_r; 0] with the signs fixed on its columns ----------------------------------------------------------------------
+        if (m <= 64) bsv_form_u<T, 1>(Wl, ldl, J, ldj, m, q, kk, r, jpl, taul, srt, sgn, true, Ub, a.u.rs, a.u.cs, wv, lane);
+        else if (m <= 128) bsv_form_u<T, 2>(Wl, ldl, J, ldj, m, q, kk, r, jpl, taul, srt, sgn, true, Ub, a.u.rs, a.u.cs, wv, lane);
+        else if (m <= 256) bsv_form_u<T, 4>(Wl, ldl, J, ldj, m, q, kk, r, jpl, taul, srt, sgn, true, Ub, a.u.rs, a.u.cs, wv, lane);
+        else bsv_form_u<T, 8>(Wl, ldl, J, ldj, m, q, kk, r, jpl, taul, srt, sgn, true, Ub, a.u.rs, a.u.cs, wv, lane);
+        // ---- V_c = G Sigma^-1 in place (kept columns), then V = Q_R [V_c; 0] through vt's transposed view, with u's signs ---------------
+        for (int c = wv; c < r; c += BID_WAVES) {
+            T *gc = G + (size_t)srt[c] * ldg;
+            const T sj = sig[srt[c]], inv = sj > (T)0 ? (T)1 / sj : (T)0;
+            for (int i = lane; i < q; i += 64) gc[i] *= inv;
+        }
+        __syncthreads();  // sgn and the scaled columns are read by other waves below
+        if (n <= 64) bsv_form_u<T, 1>(Wr, ldr, G, ldg, n, q, kk, r, jpr, taur, srt, sgn, false, Vb, a.vt.cs, a.vt.rs, wv, lane);
+        else if (n <= 128) bsv_form_u<T, 2>(Wr, ldr, G, ldg, n, q, kk, r, jpr, taur, srt, sgn, false, Vb, a.vt.cs, a.vt.rs, wv, lane);
+        else if (n <= 256) bsv_form_u<T, 4>(Wr, ldr, G, ldg, n, q, kk, r, jpr, taur, srt, sgn, false, Vb, a.vt.cs, a.vt.rs, wv, lane);
+        else bsv_form_u<T, 8>(Wr, ldr, G, ldg, n, q, kk, r, jpr, taur, srt, sgn, false, Vb, a.vt.cs, a.vt.rs, wv, lane);
+        __syncthreads();  // the working copies, G, J and the small arrays are rewritten by the next block
+    }
+}
+
 }  // namespace
 
 // persistent grid: the resident workgroups of every CU, fewer when the workspace (ws_per bytes per workgroup, 0 in the LDS variants)
@@ -713,6 +916,53 @@ void batched_svd(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int64_t k,
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BID_THREADS), lds, c->stream, a, abs, (int)count, (int)k, tol, uo, uobs, vo, vobs, s, ranks, ws,
                        c->health_word(), ldg);
 }
+
+// where the two working copies Wl (m x K), Wr (n x K) and the rotations J (K x K) live: batched_svd's rule, the first plan that fits
+// next to the core (always in LDS), most in LDS first and the padded core pitch before the odd one; a copy that does not fit goes to
+// the workgroup's slot of the grid-bounded workspace, the larger copy first.  One kernel: the plan only moves base pointers and pitches.
+template <typename T>
+void batched_lowrank_recompress(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride, Mat<T> right, int64_t rbs,
+                                const int64_t *in_ranks, int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs, T *s_out, Mat<T> vt, int64_t vbs,
+                                int64_t *ranks) {
+    const int m = (int)left.rows, n = (int)right.cols, K = (int)left.cols;
+    if (count <= 0) return;
+    const int pad = ((K + 15) / 32) * 32 + 16, odd = K | 1;
+    const bool big_l = m >= n;  // the copy that leaves LDS first
+    const struct { bool l, r, v; int ld; } plans[] = {{true, true, true, pad},    {true, true, true, odd},    {!big_l, big_l, true, pad},   {!big_l, big_l, true, odd},
+                                                      {false, false, true, pad}, {false, false, true, odd}, {false, false, false, pad}, {false, false, false, odd}};
+    int pi = 0;
+    while (pi < 7 && brc_lds_bytes<T>(m, n, K, plans[pi].ld, plans[pi].l, plans[pi].r, plans[pi].v) > BID_MAX_LDS) ++pi;
+    const bool l_lds = plans[pi].l, r_lds = plans[pi].r, v_lds = plans[pi].v;
+    const int ldg = plans[pi].ld;
+    const size_t lds = brc_lds_bytes<T>(m, n, K, ldg, l_lds, r_lds, v_lds);
+    RC_REQUIRE(lds <= BID_MAX_LDS, RC_RUNTIME_ERROR, "lowrank_recompress_batched: %zu bytes of LDS", lds);
+    const void *kern = reinterpret_cast<const void *>(k_batched_recompress<T>);
+    static bool attr_set[64] = {};
+    if (!attr_set[c->device & 63]) {
+        RC_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BID_MAX_LDS));
+        attr_set[c->device & 63] = true;
+    }
+    const size_t per = brc_ws_elems(m, n, K, l_lds, r_lds, v_lds) * sizeof(T);
+    int64_t slots = 0;
+    const int64_t grid = bid_grid(c, kern, lds, per, count, &slots);
+    ProfScope ps(c, "op:batched_recompress %dx%d k=%d count=%d grid=%lld slots=%lld plan=L:%s,R:%s,V:%s,G:lds,ld=%d,kk=%d%s%s", m, n, K, (int)count,
+                 (long long)grid, (long long)slots, l_lds ? "lds" : "ws", r_lds ? "lds" : "ws", v_lds ? "lds" : "ws", ldg, (int)std::min<int64_t>(k, K),
+                 mid.p ? ",mid" : "", s ? ",s" : "");
+    BrcArgs<T> a;
+    a.left = left; a.mid = mid; a.right = right; a.u = u; a.vt = vt;
+    a.lbs = lbs; a.mbs = mbs; a.rbs = rbs; a.ubs = ubs; a.vbs = vbs; a.s_stride = s_stride;
+    a.s = s; a.in_ranks = in_ranks; a.s_out = s_out; a.ranks = ranks;
+    a.ws = per ? c->alloc<T>((size_t)grid * per / sizeof(T)) : nullptr;
+    a.health = c->health_word();
+    a.tol = tol; a.count = (int)count; a.k = (int)std::min<int64_t>(k, K); a.ldg = ldg;
+    a.l_lds = l_lds; a.r_lds = r_lds; a.v_lds = v_lds;
+    hipLaunchKernelGGL(k_batched_recompress<T>, dim3((unsigned)grid), dim3(BID_THREADS), lds, c->stream, a);
+}
+
+template void batched_lowrank_recompress<double>(rc_context *, Mat<double>, int64_t, Mat<double>, int64_t, const double *, int64_t, Mat<double>, int64_t,
+                                                 const int64_t *, int32_t, int64_t, double, Mat<double>, int64_t, double *, Mat<double>, int64_t, int64_t *);
+template void batched_lowrank_recompress<float>(rc_context *, Mat<float>, int64_t, Mat<float>, int64_t, const float *, int64_t, Mat<float>, int64_t,
+                                                const int64_t *, int32_t, int64_t, double, Mat<float>, int64_t, float *, Mat<float>, int64_t, int64_t *);
 
 template void batched_column_id<double>(rc_context *, Mat<double>, int64_t, int32_t, int64_t, double, Mat<double>, int64_t, Mat<double>, int64_t, int64_t *, int64_t *);
 template void batched_column_id<float>(rc_context *, Mat<float>, int64_t, int32_t, int64_t, double, Mat<float>, int64_t, Mat<float>, int64_t, int64_t *, int64_t *);

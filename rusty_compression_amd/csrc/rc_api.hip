@@ -1204,6 +1204,35 @@ void lowrank_apply_batched(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, 
     batched_lowrank_apply(c, left, lbs, mid, mbs, s, s_stride, right, rbs, ranks, count, b, bbs, y, ybs);
 }
 
+// recompress every factor pair left (m x K) [mid (K x K)] [diag(s)] right (K x n) of a batch to a truncated SVD of rank <= min(k, K) without forming
+// the m x n blocks (SVD::to_qr / compute_from_range_estimate's scheme, src/svd.rs:150-163, :171-, with compress's rank rule, :60-101): one launch
+template <typename T>
+void lowrank_recompress_batched(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride, Mat<T> right, int64_t rbs,
+                                const int64_t *in_ranks, int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs, T *s_out, Mat<T> vt, int64_t vbs,
+                                int64_t *ranks) {
+    const char *who = "lowrank_recompress_batched";
+    const int64_t m = left.rows, K = left.cols, n = right.cols;
+    RC_REQUIRE(count >= 0, RC_INVALID_ARGUMENT, "%s: count = %d < 0", who, (int)count);
+    RC_REQUIRE(m >= 1 && m <= 512 && n >= 1 && n <= 512 && K >= 1 && K <= 128 && k >= 1, RC_INVALID_ARGUMENT,
+               "%s: needs 1 <= m, n <= 512, inner width 1 <= K <= 128 and k >= 1 (got left %lld x %lld, right %lld x %lld, k = %lld)", who, (long long)m,
+               (long long)K, (long long)right.rows, (long long)n, (long long)k);
+    RC_REQUIRE(right.rows == K, RC_INVALID_ARGUMENT, "%s: left is %lld x %lld but right has %lld rows", who, (long long)m, (long long)K, (long long)right.rows);
+    RC_REQUIRE(K <= std::min(m, n), RC_INVALID_ARGUMENT,
+               "%s: needs K <= min(m, n) (got K = %lld for %lld x %lld blocks); rebuild the blocks with rc_lowrank_apply_batched_* and use rc_svd_rank_batched_*",
+               who, (long long)K, (long long)m, (long long)n);
+    RC_REQUIRE(tol < 1.0 && 0.0 <= tol, RC_INVALID_ARGUMENT, "Require 0 <= tol < 1.0");
+    RC_REQUIRE(!mid.p || (mid.rows == K && mid.cols == K), RC_INVALID_ARGUMENT, "%s: mid must be %lld x %lld (got %lld x %lld)", who, (long long)K,
+               (long long)K, (long long)mid.rows, (long long)mid.cols);
+    const int64_t kk = std::min(k, K);
+    RC_REQUIRE(u.rows == m && u.cols == kk && vt.rows == kk && vt.cols == n, RC_INVALID_ARGUMENT,
+               "%s: u must be %lld x %lld and vt %lld x %lld (k clamped to K)", who, (long long)m, (long long)kk, (long long)kk, (long long)n);
+    check_batch_stride(who, "u", ubs, u, count);
+    check_batch_stride(who, "vt", vbs, vt, count);
+    if (count > 0) RC_REQUIRE(left.p && right.p && u.p && s_out && vt.p && ranks, RC_INVALID_ARGUMENT, "%s: null pointer", who);
+    if (count == 0) return;
+    batched_lowrank_recompress(c, left, lbs, mid, mbs, s, s_stride, right, rbs, in_ranks, count, k, tol, u, ubs, s_out, vt, vbs, ranks);
+}
+
 template <typename T>
 void rank_by_tolerance(rc_context *c, Mat<T> tri, double tol, int64_t *rank) {
     RC_REQUIRE(tol < 1.0 && 0.0 <= tol, RC_INVALID_ARGUMENT, "Require 0 <= tol < 1.0");
@@ -1759,6 +1788,17 @@ rc_status rc_invert_permutation(rc_context *ctx, const int64_t *perm, int64_t n,
         return guarded(ctx, [&] {                                                                                                        \
             lowrank_apply_batched<T>(ctx, from_c<T>(left), left_batch_stride, from_c<T>(mid), mid_batch_stride, s, s_stride, from_c<T>(right), \
                                      right_batch_stride, ranks, count, from_c<T>(b), b_batch_stride, from_c<T>(y), y_batch_stride);     \
+        });                                                                                                                              \
+    }                                                                                                                                    \
+    rc_status rc_lowrank_recompress_batched_##SUF(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid,             \
+                                                  int64_t mid_batch_stride, const T *s, int64_t s_stride, rc_matrix right,               \
+                                                  int64_t right_batch_stride, const int64_t *in_ranks, int32_t count, int64_t k, double tol, \
+                                                  rc_matrix u, int64_t u_batch_stride, T *s_out, rc_matrix vt, int64_t vt_batch_stride,  \
+                                                  int64_t *ranks) {                                                                      \
+        return guarded(ctx, [&] {                                                                                                        \
+            lowrank_recompress_batched<T>(ctx, from_c<T>(left), left_batch_stride, from_c<T>(mid), mid_batch_stride, s, s_stride,        \
+                                          from_c<T>(right), right_batch_stride, in_ranks, count, k, tol, from_c<T>(u), u_batch_stride,   \
+                                          s_out, from_c<T>(vt), vt_batch_stride, ranks);                                                 \
         });                                                                                                                              \
     }
 

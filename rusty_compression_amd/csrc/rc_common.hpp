@@ -241,6 +241,12 @@ template <typename R> void batched_lowrank_apply_c(rc_context *c, const rc_matri
                                                    const rc_matrix &b, int64_t bbs, const rc_matrix &y, int64_t ybs);
 // the argument checks of rc_lowrank_apply_batched_* (rc_api.hip), shared by every scalar type like the three above; the caller returns when count == 0
 template <typename T> void check_lowrank_apply_batched(Mat<T> left, Mat<T> mid, Mat<T> right, int32_t count, Mat<T> b, Mat<T> y, int64_t ybs);
+// recompress the factor pairs of such a batch to truncated SVDs without forming the blocks (kernels_batched_id.hip): block i is left (m x K), mid (K x K,
+// p == nullptr: none), right (K x n), u (m x min(k, K)) and vt (min(k, K) x n) each moved by i times its batch stride, s + i * s_stride its K real scales
+// (nullptr: none), in_ranks count device values (nullptr: every inner rank is K); s_out count x K, ranks count (arguments checked by the caller)
+template <typename T> void batched_lowrank_recompress(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride,
+                                                      Mat<T> right, int64_t rbs, const int64_t *in_ranks, int32_t count, int64_t k, double tol, Mat<T> u,
+                                                      int64_t ubs, T *s_out, Mat<T> vt, int64_t vbs, int64_t *ranks);
 // the batched kernels' dynamic-LDS cap and persistent grid (kernels_batched_id.hip): the resident workgroups of 256 threads on every
 // CU, fewer when the workspace (ws_per bytes per workgroup, 0 in the LDS variants) would pass 256 MiB unless that leaves less than
 // one workgroup per CU; never more than count.  *slots receives the grid before that last bound (slots= in the profile label)
