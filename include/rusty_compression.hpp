@@ -549,6 +549,30 @@ BatchedColumnID<T> column_id_rank_batched(const DeviceMatrix<T> &a, int32_t coun
                                                  kk * n, out.col_ind.data(), out.ranks.data()));
     return out;
 }
+// the one-pass randomized column ID of `count` tall m x n blocks stacked in `a` (rc_sketch_column_id_rank_batched_*): per block the sketch
+// omega a_i (l x n; omega is l x m and shared by the batch) and the column ID of the sketch, C gathered from a_i: the projection of
+// sample_range_by_rank (src/random_sampling.rs) followed by QR::compute_from_range_estimate + column_id (src/qr.rs:311-323).  m <= 65536,
+// n <= 512, l <= 128; k is clamped to min(k, l, n).  The result is a BatchedColumnID, so apply_batched, to_mat_batched and
+// recompress_batched take it; `sketch`, when given, receives the count * l x n sketches.  The C ABI has the entry point for the real
+// scalars only, so it is reached through its own dispatch: Api<c64> and Api<c32> stay complete.
+template <typename T> struct SketchApi;
+template <> struct SketchApi<double> { static constexpr auto sketch_column_id_rank_batched = rc_sketch_column_id_rank_batched_f64; };
+template <> struct SketchApi<float> { static constexpr auto sketch_column_id_rank_batched = rc_sketch_column_id_rank_batched_f32; };
+template <typename T>
+BatchedColumnID<T> column_id_rank_batched(const DeviceMatrix<T> &a, const DeviceMatrix<T> &omega, int32_t count, int64_t k, double tol = 0.0,
+                                          DeviceMatrix<T> *sketch = nullptr) {
+    const Context &ctx = a.ctx();
+    const int64_t m = count > 0 ? a.nrows() / count : 0, n = a.ncols(), l = omega.nrows();
+    const int64_t ln = l < n ? l : n, kk = k < ln ? k : ln;
+    BatchedColumnID<T> out{DeviceMatrix<T>(ctx, (int64_t)count * m, kk), DeviceMatrix<T>(ctx, (int64_t)count * kk, n),
+                           DeviceIndex(ctx, (std::size_t)count * (std::size_t)n), DeviceIndex(ctx, (std::size_t)count)};
+    if (sketch) *sketch = DeviceMatrix<T>(ctx, (int64_t)count * l, n);
+    ctx.check(SketchApi<T>::sketch_column_id_rank_batched(ctx.raw(), rc_matrix{a.view().data, m, n, n, 1}, m * n, omega.view(), 0, count, k, tol,
+                                                          sketch ? rc_matrix{sketch->view().data, l, n, n, 1} : rc_matrix{nullptr, 0, 0, 0, 0}, l * n,
+                                                          rc_matrix{out.c.view().data, m, kk, kk, 1}, m * kk,
+                                                          rc_matrix{out.z.view().data, kk, n, n, 1}, kk * n, out.col_ind.data(), out.ranks.data()));
+    return out;
+}
 // the two-sided ID A ~ C X R of the same batch in one call (rc_two_sided_id_rank_batched_*): c is count * m x k, x count * k x k,
 // r count * k x n, row_ind count x m, col_ind count x n; r and col_ind are column_id_rank_batched's z and col_ind bit for bit
 template <typename T>

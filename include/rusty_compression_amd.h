@@ -582,6 +582,32 @@ rc_status rc_lowrank_apply_batched_c32(rc_context *ctx, rc_matrix left, int64_t 
  * synchronisation; workspace bounded by the grid, not by count. */
 rc_status rc_lowrank_recompress_batched_f64(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const double *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *in_ranks, int32_t count, int64_t k, double tol, rc_matrix u, int64_t u_batch_stride, double *s_out, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks);
 rc_status rc_lowrank_recompress_batched_f32(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const float *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *in_ranks, int32_t count, int64_t k, double tol, rc_matrix u, int64_t u_batch_stride, float *s_out, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks);
+/* The one-pass randomized column ID of every block of a batch, in one stream-ordered, capturable call: the sketch Y_i = omega_i a_i (l x n) of each
+ * tall block a_i (m x n) is formed while a_i streams through the chip once, and the column ID of the small Y_i gives the pivots and Z; C is gathered
+ * from a_i.  Per block this replaces the reference's randomized sequence: the projection of sample_range_by_rank (src/random_sampling.rs), then
+ * QR::compute_from_range_estimate followed by column_id() (src/qr.rs:311-323): with omega = Q^H of a range estimate it is that sequence, with a
+ * Gaussian omega (rc_random_gaussian_*) it is the one-pass randomized ID.  The pivoted QR runs on l rows instead of m, so m is not bounded by what
+ * one workgroup holds.  Real scalars only.
+ * The batch layout is rc_column_id_rank_batched_*'s: block i of every operand is its view moved by i times its batch stride; any row and column
+ * strides; every pointer a device pointer.  a is m x n; omega is l x m (omega_batch_stride = 0 shares one test matrix over the batch, the usual
+ * case; a_batch_stride = 0 is legal too); y is l x n and receives the sketch when y.data is not NULL (y.data == NULL: not written, the other
+ * fields are then ignored); c is m x kk and z is kk x n with kk = min(k, l, n); col_ind (count x n) and ranks (count) are contiguous.  The outputs
+ * must not overlap the inputs or one another.
+ * Per block, with Y_i the sketch as this call computes it (and writes it to y):
+ *   col_ind, ranks and z are what rc_column_id_rank_batched_* returns for the matrix Y_i with the same k and tol, bit for bit: pivots by ?geqp3's
+ *     rule on Y_i, r = the first j < kk with R_jj == 0 or (tol > 0 and |R_jj / R_00| < tol), else kk, z = [I | R11^-1 R12] P^T with rows r..kk-1 zero;
+ *   c[:, j] = a[:, col_ind[j]] bit for bit for j < r, columns r..kk-1 of c are zero, so a_i ~ c z to the accuracy of the sketch.
+ * An element of Y_i is summed in ascending order of the row index of a, in chunks that depend on (l, m, n) alone, by v_mfma_f64_16x16x4_f64 /
+ * v_mfma_f32_16x16x4_f32 (exact f32); nothing is split across workgroups or added by atomics.  The outputs do not depend on whether y is
+ * requested; block i's bits depend on block i's a and omega alone: not on count, the position in the batch, the neighbours, any batch, row or
+ * column stride, the grid, or graph replay against an eager call.  Non-finite input stays inside its block's outputs (values unspecified, col_ind
+ * still a permutation, 0 <= r <= kk).
+ * Domain: 1 <= n <= 512, 1 <= l <= 128, 1 <= m <= 65536, 1 <= k <= 128, 0 <= tol < 1, count >= 0 (0: nothing to do).  RC_INVALID_ARGUMENT for an
+ * argument outside the domain, omega.cols != a.rows, a wrong y, c or z shape, an output batch stride smaller than one view's span when count > 1,
+ * a null a, omega, c, z, col_ind or ranks with count > 0, or a null ctx (rejected before a device is touched).  No host synchronisation;
+ * workspace bounded by the grid, not by count. */
+rc_status rc_sketch_column_id_rank_batched_f64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega, int64_t omega_batch_stride, int32_t count, int64_t k, double tol, rc_matrix y, int64_t y_batch_stride, rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks);
+rc_status rc_sketch_column_id_rank_batched_f32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega, int64_t omega_batch_stride, int32_t count, int64_t k, double tol, rc_matrix y, int64_t y_batch_stride, rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks);
 
 /* The gather over RCCL (xGMI inside a node).  One process per GPU: rank 0 calls rc_comm_unique_id and hands the 128
  * bytes to the other ranks by whatever means the host has (MPI, a file, torch.distributed), every rank calls

@@ -333,6 +333,54 @@ def svd_add_batched(u1: torch.Tensor, s1: torch.Tensor, vt1: torch.Tensor, u2: t
     return lowrank_recompress_batched(left, right, k, tol, s=s)
 
 
+def sketch_column_id_rank_batched(a: torch.Tensor, k: int, tol: float = 0.0, omega: Optional[torch.Tensor] = None, oversampling: int = 8, seed: int = 0,
+                                  return_sketch: bool = False):
+    """One-pass randomized column IDs of `count` tall same-shaped blocks in one stream-ordered call (rc_sketch_column_id_rank_batched_*):
+    per block the sketch Y = omega a (l x n) and the column ID of Y, C gathered from a; the reference's sample_range_by_rank projection
+    (src/random_sampling.rs) followed by QR::compute_from_range_estimate + column_id (src/qr.rs:311-323).
+
+    a: [count, m, n] device tensor of float64 or float32, any strides (m <= 65536, n <= 512).  omega: [l, m] (shared by the batch) or
+    [count, l, m], l <= 128, a's dtype, any strides; None draws one shared Gaussian omega of l = min(k + oversampling, 128) rows with
+    rc_random_gaussian_* at (seed, offset 0), so the result is that of the explicit call with random_gaussian((l, m), Rng(seed)).
+    k (<= 128) is clamped to kk = min(k, l, n).  Returns C [count, m, kk], Z [count, kk, n], ind [count, n], ranks [count] and, with
+    return_sketch, Y [count, l, n]: Z, ind and ranks are column_id_rank_batched(Y, k, tol)'s bit for bit, C[:, :, j] = a[:, :, ind[j]]
+    for j below the block's rank, the rest of C and Z zero.  Complex data and mismatched dtypes raise TypeError."""
+    from . import _lib
+    from .types import as_device
+
+    a = as_device(a)
+    if a.dtype not in (torch.float64, torch.float32):
+        raise TypeError(f"sketch_column_id_rank_batched: float64 or float32 data expected, got {a.dtype}")
+    if a.dim() != 3:
+        raise AssertionError("expected a [count, m, n] batch")
+    count, m, n = a.shape
+    if omega is None:
+        from .random_matrix import Rng, random_gaussian
+
+        omega = random_gaussian((max(min(int(k) + int(oversampling), 128), 1), m), Rng(int(seed)), a.dtype)
+    omega = as_device(omega)
+    if omega.dtype != a.dtype:
+        raise TypeError(f"sketch_column_id_rank_batched: omega is {omega.dtype}, a is {a.dtype}")
+    if omega.dim() not in (2, 3) or (omega.dim() == 3 and omega.shape[0] != count):
+        raise AssertionError("expected omega [l, m] or [count, l, m]")
+    l = omega.shape[-2]
+    obs = omega.stride(0) if omega.dim() == 3 else 0
+    kk = max(min(int(k), l, n), 0)
+    c = torch.empty((count, m, kk), dtype=a.dtype, device=a.device)
+    z = torch.empty((count, kk, n), dtype=a.dtype, device=a.device)
+    ind = torch.empty((count, n), dtype=torch.int64, device=a.device)
+    ranks = torch.empty(count, dtype=torch.int64, device=a.device)
+    y = torch.empty((count, l, n), dtype=a.dtype, device=a.device) if return_sketch else None
+    _lib.default_context().call(f"rc_sketch_column_id_rank_batched_{_lib.suffix(a.dtype)}",
+                                _lib.rc_matrix(a.data_ptr(), m, n, a.stride(1), a.stride(2)), ctypes.c_int64(a.stride(0)),
+                                _lib.rc_matrix(omega.data_ptr(), l, omega.shape[-1], omega.stride(-2), omega.stride(-1)), ctypes.c_int64(obs),
+                                ctypes.c_int32(count), ctypes.c_int64(int(k)), ctypes.c_double(float(tol)),
+                                _lib.rc_matrix(y.data_ptr(), l, n, n, 1) if return_sketch else _lib.mat(None), ctypes.c_int64(l * n),
+                                _lib.rc_matrix(c.data_ptr(), m, kk, kk, 1), ctypes.c_int64(m * kk),
+                                _lib.rc_matrix(z.data_ptr(), kk, n, n, 1), ctypes.c_int64(kk * n), _lib.i64p(ind), _lib.i64p(ranks))
+    return (c, z, ind, ranks, y) if return_sketch else (c, z, ind, ranks)
+
+
 def packed_bytes(m: int, n: int, k: int, elem_size: int) -> int:
     """Bytes one matrix's factors take in the packed buffer: C (m x k) | Z (k x n) | pad to 8 | col_ind (n int64)
     (rc_batch_packed_bytes)."""

@@ -22,8 +22,12 @@
 //
 // Batched recompression (rc_lowrank_recompress_batched_*): k_batched_recompress, the same grid and stages on the two thin factors of
 // a low-rank block, the same Jacobi on their small core, both Q's applied by the same reflector routine (see its comment below).
+//
+// Batched sketched column ID (rc_sketch_column_id_rank_batched_*): k_batched_sketch_id, the same grid; the working copy is the sketch
+// Omega A (l x n, l <= 128) formed by MFMA while A streams through LDS once, then the same stages on l rows (see its comment below).
 #include "rc_common.hpp"
 #include "rc_device.hpp"
+#include "rc_gemm.hpp"
 
 namespace rc {
 
@@ -109,6 +113,18 @@ __device__ __forceinline__ void bid_apply(T *W, int ldw, int m, int n, int j, co
 // ---- the three stages of one factorization, shared by k_batched_id and both phases of k_batched_two_sided ------------------------
 // (m x n below is the matrix being factored: A for a column ID, C^T for the row side of a two-sided ID)
 
+// the initial column norms of the working copy W (m x n, column c at W + c * ldw) and the identity permutation
+template <typename T>
+__device__ __forceinline__ void bid_norms(const T *W, int ldw, int m, int n, T *vn1, T *vn2, int *jp, int wv, int lane) {
+    for (int c = wv; c < n; c += BID_WAVES) {
+        T acc = 0;
+        for (int i = lane; i < m; i += 64) { const T v = W[(size_t)c * ldw + i]; acc += v * v; }
+        acc = wave_sum_dpp(acc);
+        if (lane == 0) { const T nr = sqrt(acc); vn1[c] = nr; vn2[c] = nr; jp[c] = c; }
+    }
+    __syncthreads();
+}
+
 // working copy W[c * ldw + i] = at(i, c), read with the lanes along i (lanes_on_rows) or along c (the input's fast direction),
 // then the initial column norms and the identity permutation
 template <typename T, typename At>
@@ -121,13 +137,7 @@ __device__ __forceinline__ void bid_load(T *W, int ldw, int m, int n, bool lanes
             for (int c = lane; c < n; c += 64) W[(size_t)c * ldw + i] = at(i, c);
     }
     __syncthreads();
-    for (int c = wv; c < n; c += BID_WAVES) {
-        T acc = 0;
-        for (int i = lane; i < m; i += 64) { const T v = W[(size_t)c * ldw + i]; acc += v * v; }
-        acc = wave_sum_dpp(acc);
-        if (lane == 0) { const T nr = sqrt(acc); vn1[c] = nr; vn2[c] = nr; jp[c] = c; }
-    }
-    __syncthreads();
+    bid_norms(W, ldw, m, n, vn1, vn2, jp, wv, lane);
 }
 
 // truncated pivoted QR of the working copy, at most k steps: pivots in jp (?geqp3's rule), R and the Householder vectors in W (LAPACK
@@ -811,6 +821,182 @@ __global__ __launch_bounds__(BID_THREADS) void k_batched_recompress(BrcArgs<T> a
     }
 }
 
+
+// ---- batched sketched column ID (rc_sketch_column_id_rank_batched_*) ------------------------------------------------------------
+// Per block, the reference's randomized path (sample, project, factor the small projected matrix: sample_range_by_rank in
+// src/random_sampling.rs, QR::compute_from_range_estimate + column_id, src/qr.rs:311-323): the sketch Y = Omega A (l x n, l <= 128) is
+// formed straight into the working copy W that bid_qrcp factors, then the stages of k_batched_id run on W with l rows instead of m:
+// pivots, rank and Z are those of the column ID of Y, C is gathered from A.  A is read from HBM once (plus the kept columns for C),
+// so m is bounded by the index range, not by what a workgroup can hold.
+//
+// The sketch.  Column panels of BSI_COLS = 64 columns of Y, one 16-column MFMA tile per wave, all TL = ceil(l / 16) row tiles of the
+// panel in the wave's accumulators (v_mfma_f64_16x16x4_f64 / v_mfma_f32_16x16x4_f32, Acc<T> of rc_gemm.hpp).  The panel's rows of A
+// stream through LDS in chunks of BSI_ROWS = 32 rows beside the matching 32 columns of Omega, which is re-read per panel (from L2).
+// Both chunks are read with the lanes along the operand's smaller stride and keep that index fastest in LDS (pitch 34 along the
+// reduction index, or a pitch of 16 modulo 32 along the other: the fragment reads of either image are bank-conflict free); rows past
+// m, columns past n and rows of Omega past l are zeros in LDS, so the MFMA loop has no edge branch.  An element of Y is summed in
+// ascending row order: chunk after chunk, four rows per MFMA: a function of (l, m, n) and the two constants alone.
+constexpr int BSI_ROWS = 32;   // rows of A (= columns of Omega) per LDS chunk
+constexpr int BSI_COLS = 64;   // columns of Y per panel
+constexpr int BSI_PK = BSI_ROWS + 2;                       // pitch of an image with the reduction index fastest
+constexpr int BSI_PA = 80;                                 // pitch of A's image with the column index fastest (16 mod 32, >= BSI_COLS)
+constexpr int BSI_A_ELEMS = BSI_ROWS * BSI_PA;             // A's chunk image: the larger of the two layouts
+static_assert(BSI_A_ELEMS >= BSI_COLS * BSI_PK && BSI_PA >= BSI_COLS, "A chunk image");
+__host__ __device__ constexpr int bsi_po(int l) {          // pitch of Omega's image with the row index fastest (16 mod 32, >= 16 TL)
+    return (((l + 15) & ~15) & 16) ? ((l + 15) & ~15) : ((l + 15) & ~15) + 16;
+}
+__host__ __device__ constexpr int bsi_o_elems(int l) {     // Omega's chunk image: the larger of the two layouts (16 TL rows x BSI_ROWS)
+    return BSI_ROWS * bsi_po(l) > ((l + 15) & ~15) * BSI_PK ? BSI_ROWS * bsi_po(l) : ((l + 15) & ~15) * BSI_PK;
+}
+// dynamic LDS: [W: n x (l|1), LDS plan only] A chunk [BSI_A_ELEMS] Omega chunk [bsi_o_elems(l)] vn1[n] vn2[n] tile[16 x 17] red[8] | jp[n]
+template <typename T>
+size_t bsi_lds_bytes(int l, int n, bool in_lds) {
+    size_t t = (size_t)BSI_A_ELEMS + (size_t)bsi_o_elems(l) + (size_t)2 * n + BID_NB * (BID_NB + 1) + 8;
+    if (in_lds) t += (size_t)n * (size_t)(l | 1);
+    return t * sizeof(T) + (size_t)n * sizeof(int);
+}
+
+template <typename T>
+struct BsiArgs {
+    Mat<T> a, omega, y, c, z;  // y.p == nullptr: the sketch is not written
+    int64_t abs, obs, ybs, cbs, zbs;
+    int64_t *col_ind, *ranks;
+    T *ws;
+    double tol;
+    int count, kk;
+    bool w_lds;  // the working copy in LDS (else in the workgroup's workspace slot)
+};
+
+// W[c * ldw + i] = Y[i, c] = sum_r Om[i, r] A[r, c] for the l x n sketch of one block (and Y to Yb when it is not null).
+// AR / OR: the lanes of the staging loads run along the rows of a / of omega (the operand's smaller stride), else along its columns;
+// each thread's elements of a chunk are then a fixed step apart in memory and in the LDS image, whose offsets are compile-time constants.
+template <typename T, int TL, bool AR, bool OR>
+__device__ __forceinline__ void bsi_sketch(const BsiArgs<T> &g, const T *__restrict__ A, const T *__restrict__ Om, T *Yb, T *W, int ldw, T *As, T *Os, int tid,
+                                           int wv, int lane) {
+    constexpr int PO = bsi_po(16 * TL);
+    constexpr int A_PER = BSI_ROWS * BSI_COLS / BID_THREADS;    // 8 elements of A per thread and chunk
+    constexpr int O_PER = BSI_ROWS * 16 * TL / BID_THREADS;     // 2 TL elements of Omega
+    constexpr int A_SR = AR ? 1 : BSI_PA, A_SC = AR ? BSI_PK : 1;   // A's image: As[r * A_SR + c * A_SC]
+    constexpr int O_SI = OR ? 1 : BSI_PK, O_SR = OR ? PO : 1;       // Omega's image: Os[i * O_SI + r * O_SR]
+    const int m = (int)g.a.rows, n = (int)g.a.cols, l = (int)g.omega.rows;
+    const int64_t ars = g.a.rs, acs = g.a.cs, ors = g.omega.rs, ocs = g.omega.cs;
+    // this thread's elements of a chunk: A[ar + AR_STEP e, ac + AC_STEP e], Om[oi + 16 (e / 2) or 8 e, orr + 16 (e % 2) or 0]
+    const int ar = AR ? (tid & (BSI_ROWS - 1)) : (tid / BSI_COLS), ac = AR ? (tid / BSI_ROWS) : (tid & (BSI_COLS - 1));
+    constexpr int AR_STEP = AR ? 0 : BID_THREADS / BSI_COLS, AC_STEP = AR ? BID_THREADS / BSI_ROWS : 0;
+    const int oi = OR ? (tid & 15) : (tid / BSI_ROWS), orr = OR ? (tid >> 4) : (tid & (BSI_ROWS - 1));
+    const int r16 = lane & 15, k4 = lane >> 4;
+    T *as_st = As + ar * A_SR + ac * A_SC, *os_st = Os + oi * O_SI + orr * O_SR;
+    const T *as_ld = As + k4 * A_SR + (wv * 16 + r16) * A_SC, *os_ld = Os + r16 * O_SI + k4 * O_SR;
+    for (int c0 = 0; c0 < n; c0 += BSI_COLS) {
+        typename Acc<T>::type acc[TL];
+#pragma unroll
+        for (int i = 0; i < TL; ++i) acc[i] = typename Acc<T>::type{0, 0, 0, 0};
+        for (int m0 = 0; m0 < m; m0 += BSI_ROWS) {
+            T av[A_PER], ov[O_PER];
+            const T *pa = A + (int64_t)(m0 + ar) * ars + (int64_t)(c0 + ac) * acs;
+            const T *po = Om + (int64_t)oi * ors + (int64_t)(m0 + orr) * ocs;
+            // the steps between a thread's elements are uniform; hidden from the optimizer here, every address is the thread's one base plus a
+            // scalar offset (otherwise each of the 8 + 2 TL addresses becomes a loop-carried 64-bit register pair of its own)
+            int64_t sa = AR ? AC_STEP * acs : AR_STEP * ars, so_i = ors, so_r = ocs;
+            asm volatile("" : "+s"(sa), "+s"(so_i), "+s"(so_r));
+#pragma unroll
+            for (int e = 0; e < A_PER; ++e) {
+                const bool ok = m0 + ar + AR_STEP * e < m && c0 + ac + AC_STEP * e < n;
+                av[e] = ok ? pa[e * sa] : (T)0;
+            }
+#pragma unroll
+            for (int e = 0; e < O_PER; ++e) {
+                const int di = OR ? 16 * (e / 2) : 8 * e, dr = OR ? 16 * (e % 2) : 0;
+                const bool ok = oi + di < l && m0 + orr + dr < m;
+                ov[e] = ok ? po[di * so_i + dr * so_r] : (T)0;
+            }
+#pragma unroll
+            for (int e = 0; e < A_PER; ++e) as_st[AR_STEP * e * A_SR + AC_STEP * e * A_SC] = av[e];
+#pragma unroll
+            for (int e = 0; e < O_PER; ++e) {
+                const int di = OR ? 16 * (e / 2) : 8 * e, dr = OR ? 16 * (e % 2) : 0;
+                os_st[di * O_SI + dr * O_SR] = ov[e];
+            }
+            __syncthreads();
+#pragma unroll
+            for (int ks = 0; ks < BSI_ROWS / 4; ++ks) {
+                const T bf = as_ld[ks * 4 * A_SR];
+#pragma unroll
+                for (int i = 0; i < TL; ++i) acc[i] = Acc<T>::mfma(os_ld[i * 16 * O_SI + ks * 4 * O_SR], bf, acc[i]);
+            }
+            __syncthreads();  // the chunk images are rewritten by the next chunk
+        }
+        const int col = c0 + wv * 16 + r16;
+#pragma unroll
+        for (int i = 0; i < TL; ++i)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                const int row = i * 16 + Acc<T>::row(lane, reg);
+                if (row < l && col < n) {
+                    const T v = acc[i][reg];
+                    W[(size_t)col * ldw + row] = v;
+                    if (Yb) Yb[row * g.y.rs + col * g.y.cs] = v;
+                }
+            }
+    }
+    __syncthreads();
+}
+
+template <typename T, bool AR, bool OR>
+__global__ __launch_bounds__(BID_THREADS, 2) void k_batched_sketch_id(BsiArgs<T> g) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const int m = (int)g.a.rows, n = (int)g.a.cols, l = (int)g.omega.rows, kk = g.kk;
+    const int ldw = g.w_lds ? (l | 1) : l;
+    T *lds = reinterpret_cast<T *>(smem_raw);
+    T *W = g.w_lds ? lds : g.ws + (size_t)blockIdx.x * (size_t)l * (size_t)n;
+    T *As = lds + (g.w_lds ? (size_t)n * ldw : 0);
+    T *Os = As + BSI_A_ELEMS;
+    T *vn1 = Os + bsi_o_elems(l);
+    T *vn2 = vn1 + n;
+    T(*tile)[BID_NB + 1] = reinterpret_cast<T(*)[BID_NB + 1]>(vn2 + n);
+    T *red = vn2 + n + BID_NB * (BID_NB + 1);
+    int *jp = reinterpret_cast<int *>(red + 8);
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+
+    for (int b = blockIdx.x; b < g.count; b += gridDim.x) {
+        const T *__restrict__ A = g.a.p + (int64_t)b * g.abs;
+        const T *__restrict__ Om = g.omega.p + (int64_t)b * g.obs;
+        T *Yb = g.y.p ? g.y.p + (int64_t)b * g.ybs : nullptr;
+        // ---- the sketch into W (and y), one instance per number of 16-row tiles so that the accumulators stay in registers ------------
+        switch ((l + 15) >> 4) {
+            case 1: bsi_sketch<T, 1, AR, OR>(g, A, Om, Yb, W, ldw, As, Os, tid, wv, lane); break;
+            case 2: bsi_sketch<T, 2, AR, OR>(g, A, Om, Yb, W, ldw, As, Os, tid, wv, lane); break;
+            case 3: bsi_sketch<T, 3, AR, OR>(g, A, Om, Yb, W, ldw, As, Os, tid, wv, lane); break;
+            case 4: bsi_sketch<T, 4, AR, OR>(g, A, Om, Yb, W, ldw, As, Os, tid, wv, lane); break;
+            case 5: bsi_sketch<T, 5, AR, OR>(g, A, Om, Yb, W, ldw, As, Os, tid, wv, lane); break;
+            case 6: bsi_sketch<T, 6, AR, OR>(g, A, Om, Yb, W, ldw, As, Os, tid, wv, lane); break;
+            case 7: bsi_sketch<T, 7, AR, OR>(g, A, Om, Yb, W, ldw, As, Os, tid, wv, lane); break;
+            default: bsi_sketch<T, 8, AR, OR>(g, A, Om, Yb, W, ldw, As, Os, tid, wv, lane); break;
+        }
+        // ---- the column ID of Y: k_batched_id's stages on l rows ----------------------------------------------------------------------
+        bid_norms(W, ldw, l, n, vn1, vn2, jp, wv, lane);
+        const int r = bid_qrcp(W, ldw, l, n, kk, g.tol, jp, vn1, vn2, red, tid, wv, lane);
+        for (int p = tid; p < n; p += BID_THREADS) g.col_ind[(int64_t)b * n + p] = jp[p];
+        if (tid == 0) g.ranks[b] = r;
+        // C[:, j] = A[:, jp[j]] (zero for j >= r), the lanes along a's smaller stride
+        T *Cb = g.c.p + (int64_t)b * g.cbs;
+        if (g.a.rs <= g.a.cs) {
+            for (int j = wv; j < kk; j += BID_WAVES) {
+                const T *src = A + (int64_t)jp[j] * g.a.cs;
+                for (int i = lane; i < m; i += 64) Cb[i * g.c.rs + j * g.c.cs] = j < r ? src[i * g.a.rs] : (T)0;
+            }
+        } else {
+            const int total = m * kk;  // <= 65536 * 128
+            for (int idx = tid; idx < total; idx += BID_THREADS) {
+                const int i = idx / kk, j = idx - i * kk;
+                Cb[i * g.c.rs + j * g.c.cs] = j < r ? A[i * g.a.rs + (int64_t)jp[j] * g.a.cs] : (T)0;
+            }
+        }
+        bid_z(W, ldw, n, r, kk, jp, tile, g.z.p + (int64_t)b * g.zbs, g.z.rs, g.z.cs, tid);
+        __syncthreads();  // W, jp and the norms are rewritten by the next block
+    }
+}
+
 }  // namespace
 
 // persistent grid: the resident workgroups of every CU, fewer when the workspace (ws_per bytes per workgroup, 0 in the LDS variants)
@@ -958,6 +1144,55 @@ void batched_lowrank_recompress(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> 
     a.l_lds = l_lds; a.r_lds = r_lds; a.v_lds = v_lds;
     hipLaunchKernelGGL(k_batched_recompress<T>, dim3((unsigned)grid), dim3(BID_THREADS), lds, c->stream, a);
 }
+
+// the sketched column ID of a batch: W (l x n) in LDS when it fits next to the chunk images, else in the workgroup's slot of the grid-bounded
+// workspace: the plan only moves W's base pointer and pitch, so it cannot change a block's bits.  Four instances of the kernel, by the
+// index of a and of omega that the staging loads' lanes run along; each element of Y is summed in the same order in all four.
+template <typename T>
+void batched_sketch_column_id(rc_context *c, Mat<T> a, int64_t abs, Mat<T> omega, int64_t obs, int32_t count, int64_t kk, double tol, Mat<T> y, int64_t ybs,
+                              Mat<T> cm, int64_t cbs, Mat<T> z, int64_t zbs, int64_t *col_ind, int64_t *ranks) {
+    const int m = (int)a.rows, n = (int)a.cols, l = (int)omega.rows;
+    if (count <= 0) return;
+    const bool w_lds = bsi_lds_bytes<T>(l, n, true) <= BID_MAX_LDS;
+    const size_t lds = bsi_lds_bytes<T>(l, n, w_lds);
+    // the lanes of the staging loads along the smaller stride of a and of omega (bid_load's rule for a)
+    const bool a_rows = a.rs <= a.cs, o_rows = omega.rs < omega.cs;
+    const void *kerns[4] = {reinterpret_cast<const void *>(k_batched_sketch_id<T, false, false>), reinterpret_cast<const void *>(k_batched_sketch_id<T, false, true>),
+                            reinterpret_cast<const void *>(k_batched_sketch_id<T, true, false>), reinterpret_cast<const void *>(k_batched_sketch_id<T, true, true>)};
+    const void *kern = kerns[(a_rows ? 2 : 0) + (o_rows ? 1 : 0)];
+    // per device, once: the LDS cap, and each instance's scratch bytes per thread for the label (the f64 instances sit at the register bound of two
+    // waves per SIMD, so a compiler that spills more shows up in every profile and in tools/batched_sketch_id_bench.py)
+    static bool attr_set[64] = {};
+    static int scratch_of[64][4] = {};
+    if (!attr_set[c->device & 63]) {
+        for (int i = 0; i < 4; ++i) {
+            RC_HIP(hipFuncSetAttribute(kerns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)BID_MAX_LDS));
+            hipFuncAttributes fa;
+            RC_HIP(hipFuncGetAttributes(&fa, kerns[i]));
+            scratch_of[c->device & 63][i] = (int)fa.localSizeBytes;
+        }
+        attr_set[c->device & 63] = true;
+    }
+    const size_t per = w_lds ? 0 : (size_t)l * (size_t)n * sizeof(T);
+    int64_t slots = 0;
+    const int64_t grid = bid_grid(c, kern, lds, per, count, &slots);
+    ProfScope ps(c, "op:batched_sketch_id %dx%d k=%lld count=%d grid=%lld slots=%lld plan=W:%s,l=%d,rows=%d,cols=%d,scratch=%d", m, n, (long long)kk,
+                 (int)count, (long long)grid, (long long)slots, w_lds ? "lds" : "ws", l, BSI_ROWS, BSI_COLS,
+                 scratch_of[c->device & 63][(a_rows ? 2 : 0) + (o_rows ? 1 : 0)]);
+    BsiArgs<T> g;
+    g.a = a; g.omega = omega; g.y = y; g.c = cm; g.z = z;
+    g.abs = abs; g.obs = obs; g.ybs = ybs; g.cbs = cbs; g.zbs = zbs;
+    g.col_ind = col_ind; g.ranks = ranks;
+    g.ws = per ? c->alloc<T>((size_t)grid * (size_t)l * (size_t)n) : nullptr;
+    g.tol = tol; g.count = (int)count; g.kk = (int)kk; g.w_lds = w_lds;
+    void *args[] = {&g};
+    RC_HIP(hipLaunchKernel(kern, dim3((unsigned)grid), dim3(BID_THREADS), args, lds, c->stream));
+}
+
+template void batched_sketch_column_id<double>(rc_context *, Mat<double>, int64_t, Mat<double>, int64_t, int32_t, int64_t, double, Mat<double>, int64_t, Mat<double>,
+                                               int64_t, Mat<double>, int64_t, int64_t *, int64_t *);
+template void batched_sketch_column_id<float>(rc_context *, Mat<float>, int64_t, Mat<float>, int64_t, int32_t, int64_t, double, Mat<float>, int64_t, Mat<float>,
+                                              int64_t, Mat<float>, int64_t, int64_t *, int64_t *);
 
 template void batched_lowrank_recompress<double>(rc_context *, Mat<double>, int64_t, Mat<double>, int64_t, const double *, int64_t, Mat<double>, int64_t,
                                                  const int64_t *, int32_t, int64_t, double, Mat<double>, int64_t, double *, Mat<double>, int64_t, int64_t *);

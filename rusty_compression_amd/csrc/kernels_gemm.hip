@@ -30,25 +30,6 @@ namespace rc {
 
 static __host__ __device__ inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-typedef double double4_t __attribute__((ext_vector_type(4)));
-typedef float float4_t __attribute__((ext_vector_type(4)));
-typedef double double2_t __attribute__((ext_vector_type(2)));
-typedef float float2_t __attribute__((ext_vector_type(2)));
-
-template <typename T> struct Acc;
-template <> struct Acc<double> {
-    typedef double4_t type;
-    typedef double2_t vec2;
-    static __device__ inline type mfma(double a, double b, type c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
-    static __device__ inline int row(int lane, int reg) { return (lane >> 4) + 4 * reg; }
-};
-template <> struct Acc<float> {
-    typedef float4_t type;
-    typedef float2_t vec2;
-    static __device__ inline type mfma(float a, float b, type c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-    static __device__ inline int row(int lane, int reg) { return 4 * (lane >> 4) + reg; }
-};
-
 // smallest pitch >= n with pitch % 32 == 16 (conflict-free M/N-fastest fragment reads, 16x16x4 MFMA)
 constexpr int pitch16(int n) { return n + ((16 - n % 32) + 32) % 32; }
 // smallest pitch >= n with pitch % 8 == 4 (same for the 4x4x4 f64 MFMA fragments)

@@ -1233,6 +1233,32 @@ void lowrank_recompress_batched(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> 
     batched_lowrank_recompress(c, left, lbs, mid, mbs, s, s_stride, right, rbs, in_ranks, count, k, tol, u, ubs, s_out, vt, vbs, ranks);
 }
 
+// the one-pass randomized column ID of every block of a batch: the sketch y = omega a (l x n) and the column ID of y in one launch, c gathered from a
+// (sample_range_by_rank's projection, src/random_sampling.rs, then QR::compute_from_range_estimate + column_id, src/qr.rs:311-323, per block)
+template <typename T>
+void sketch_column_id_rank_batched(rc_context *c, Mat<T> a, int64_t abs, Mat<T> omega, int64_t obs, int32_t count, int64_t k, double tol, Mat<T> y, int64_t ybs,
+                                   Mat<T> cm, int64_t cbs, Mat<T> z, int64_t zbs, int64_t *col_ind, int64_t *ranks) {
+    const char *who = "sketch_column_id_rank_batched";
+    const int64_t m = a.rows, n = a.cols, l = omega.rows;
+    RC_REQUIRE(count >= 0, RC_INVALID_ARGUMENT, "%s: count = %d < 0", who, (int)count);
+    RC_REQUIRE(m >= 1 && m <= 65536 && n >= 1 && n <= 512 && l >= 1 && l <= 128 && k >= 1 && k <= 128, RC_INVALID_ARGUMENT,
+               "%s: needs 1 <= m <= 65536, 1 <= n <= 512, 1 <= l <= 128 and 1 <= k <= 128 (got a %lld x %lld, omega %lld x %lld, k = %lld)", who, (long long)m,
+               (long long)n, (long long)l, (long long)omega.cols, (long long)k);
+    RC_REQUIRE(omega.cols == m, RC_INVALID_ARGUMENT, "%s: a has %lld rows but omega has %lld columns", who, (long long)m, (long long)omega.cols);
+    RC_REQUIRE(tol < 1.0 && 0.0 <= tol, RC_INVALID_ARGUMENT, "Require 0 <= tol < 1.0");
+    const int64_t kk = std::min(k, std::min(l, n));
+    RC_REQUIRE(cm.rows == m && cm.cols == kk && z.rows == kk && z.cols == n, RC_INVALID_ARGUMENT,
+               "%s: c must be %lld x %lld and z %lld x %lld (k clamped to min(l, n))", who, (long long)m, (long long)kk, (long long)kk, (long long)n);
+    RC_REQUIRE(!y.p || (y.rows == l && y.cols == n), RC_INVALID_ARGUMENT, "%s: y must be %lld x %lld (got %lld x %lld)", who, (long long)l, (long long)n,
+               (long long)y.rows, (long long)y.cols);
+    check_batch_stride(who, "c", cbs, cm, count);
+    check_batch_stride(who, "z", zbs, z, count);
+    if (y.p) check_batch_stride(who, "y", ybs, y, count);
+    if (count > 0) RC_REQUIRE(a.p && omega.p && cm.p && z.p && col_ind && ranks, RC_INVALID_ARGUMENT, "%s: null pointer", who);
+    if (count == 0) return;
+    batched_sketch_column_id(c, a, abs, omega, obs, count, kk, tol, y, ybs, cm, cbs, z, zbs, col_ind, ranks);
+}
+
 template <typename T>
 void rank_by_tolerance(rc_context *c, Mat<T> tri, double tol, int64_t *rank) {
     RC_REQUIRE(tol < 1.0 && 0.0 <= tol, RC_INVALID_ARGUMENT, "Require 0 <= tol < 1.0");
@@ -1799,6 +1825,16 @@ rc_status rc_invert_permutation(rc_context *ctx, const int64_t *perm, int64_t n,
             lowrank_recompress_batched<T>(ctx, from_c<T>(left), left_batch_stride, from_c<T>(mid), mid_batch_stride, s, s_stride,        \
                                           from_c<T>(right), right_batch_stride, in_ranks, count, k, tol, from_c<T>(u), u_batch_stride,   \
                                           s_out, from_c<T>(vt), vt_batch_stride, ranks);                                                 \
+        });                                                                                                                              \
+    }                                                                                                                                    \
+    rc_status rc_sketch_column_id_rank_batched_##SUF(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega,              \
+                                                     int64_t omega_batch_stride, int32_t count, int64_t k, double tol, rc_matrix y,      \
+                                                     int64_t y_batch_stride, rc_matrix c, int64_t c_batch_stride, rc_matrix z,           \
+                                                     int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks) {                         \
+        return guarded(ctx, [&] {                                                                                                        \
+            sketch_column_id_rank_batched<T>(ctx, from_c<T>(a), a_batch_stride, from_c<T>(omega), omega_batch_stride, count, k, tol,     \
+                                             from_c<T>(y), y_batch_stride, from_c<T>(c), c_batch_stride, from_c<T>(z), z_batch_stride,   \
+                                             col_ind, ranks);                                                                            \
         });                                                                                                                              \
     }
 

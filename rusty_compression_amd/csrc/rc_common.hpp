@@ -247,6 +247,11 @@ template <typename T> void check_lowrank_apply_batched(Mat<T> left, Mat<T> mid, 
 template <typename T> void batched_lowrank_recompress(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride,
                                                       Mat<T> right, int64_t rbs, const int64_t *in_ranks, int32_t count, int64_t k, double tol, Mat<T> u,
                                                       int64_t ubs, T *s_out, Mat<T> vt, int64_t vbs, int64_t *ranks);
+// the column ID of the sketch omega a of every block of a batch (kernels_batched_id.hip): block i is a (m x n), omega (l x m, l <= 128), y (l x n,
+// p == nullptr: not written), cm (m x kk) and z (kk x n) each moved by i times its batch stride (0 is legal for a and omega), kk = min(k, l, n) already
+// clamped; col_ind count x n, ranks count (arguments checked by the caller)
+template <typename T> void batched_sketch_column_id(rc_context *c, Mat<T> a, int64_t abs, Mat<T> omega, int64_t obs, int32_t count, int64_t kk, double tol,
+                                                    Mat<T> y, int64_t ybs, Mat<T> cm, int64_t cbs, Mat<T> z, int64_t zbs, int64_t *col_ind, int64_t *ranks);
 // the batched kernels' dynamic-LDS cap and persistent grid (kernels_batched_id.hip): the resident workgroups of 256 threads on every
 // CU, fewer when the workspace (ws_per bytes per workgroup, 0 in the LDS variants) would pass 256 MiB unless that leaves less than
 // one workgroup per CU; never more than count.  *slots receives the grid before that last bound (slots= in the profile label)

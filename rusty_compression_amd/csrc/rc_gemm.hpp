@@ -5,6 +5,28 @@
 
 namespace rc {
 
+// The 16x16x4 MFMA of each real scalar and its accumulator fragment (v_mfma_f64_16x16x4_f64, v_mfma_f32_16x16x4_f32: exact f32), shared with the
+// batched sketch (kernels_batched_id.hip).  A-operand lane l holds A[l&15][l>>4], B-operand lane l holds B[l>>4][l&15]; C/D: col = l&15,
+// row = Acc<T>::row(l, reg).
+typedef double double4_t __attribute__((ext_vector_type(4)));
+typedef float float4_t __attribute__((ext_vector_type(4)));
+typedef double double2_t __attribute__((ext_vector_type(2)));
+typedef float float2_t __attribute__((ext_vector_type(2)));
+
+template <typename T> struct Acc;
+template <> struct Acc<double> {
+    typedef double4_t type;
+    typedef double2_t vec2;
+    static __device__ inline type mfma(double a, double b, type c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
+    static __device__ inline int row(int lane, int reg) { return (lane >> 4) + 4 * reg; }
+};
+template <> struct Acc<float> {
+    typedef float4_t type;
+    typedef float2_t vec2;
+    static __device__ inline type mfma(float a, float b, type c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+    static __device__ inline int row(int lane, int reg) { return 4 * (lane >> 4) + reg; }
+};
+
 template <typename T>
 struct GemmArgs {
     const T *a, *b;
