@@ -724,6 +724,50 @@ BatchedSVD<T> recompress_batched(const BatchedSVD<T> &a, const BatchedSVD<T> &b,
     ctx.synchronize();  // eye, left, right and s are freed on return
     return out;
 }
+// the residual of every block of a batch against its stacked factors in one rank-aware call (rc_lowrank_residual_batched_*): per block the
+// reference's rel_diff_fro(x.to_mat(), a) without the rebuilt block, on the domain of the sketched column ID (m <= 65536, n <= 512, K <= 128).
+// a is count * m x n, the factors as in lowrank_apply_batched.  err[i] = ||a_i - left_i mid_i diag(s_i) right_i||_F at the block's rank,
+// nrm[i] = ||a_i||_F, and with want_residual e (count * m x n) holds the residual blocks (else it is empty).  The C ABI has the entry point
+// for the real scalars only, so it is reached through its own dispatch: Api<c64> and Api<c32> stay complete.
+template <typename T> struct ResidualApi;
+template <> struct ResidualApi<double> { static constexpr auto lowrank_residual_batched = rc_lowrank_residual_batched_f64; };
+template <> struct ResidualApi<float> { static constexpr auto lowrank_residual_batched = rc_lowrank_residual_batched_f32; };
+template <typename T>
+struct BatchedResidual {
+    DeviceBuffer<T> err, nrm;
+    DeviceMatrix<T> e;
+    bool has_e = false;
+};
+template <typename T>
+BatchedResidual<T> lowrank_residual_batched(const DeviceMatrix<T> &a, const DeviceMatrix<T> &left, const DeviceMatrix<T> *mid, const DeviceBuffer<T> *s,
+                                            const DeviceMatrix<T> &right, const DeviceIndex *ranks, int32_t count, bool want_residual = false) {
+    const Context &ctx = a.ctx();
+    const int64_t m = count > 0 ? a.nrows() / count : 0, n = a.ncols(), k = left.ncols();
+    const int64_t p = s && count > 0 ? (int64_t)(s->size() / (std::size_t)count) : 0;
+    BatchedResidual<T> out{DeviceBuffer<T>(ctx, (std::size_t)count), DeviceBuffer<T>(ctx, (std::size_t)count),
+                           want_residual ? DeviceMatrix<T>(ctx, (int64_t)count * m, n) : DeviceMatrix<T>(), want_residual};
+    if (count == 0) return out;  // an empty batch is a no-op (the block shape cannot be read off an empty stack)
+    const rc_matrix none{nullptr, 0, 0, 0, 0};
+    ctx.check(ResidualApi<T>::lowrank_residual_batched(ctx.raw(), rc_matrix{a.view().data, m, n, n, 1}, m * n, rc_matrix{left.view().data, m, k, k, 1},
+                                                       m * k, mid ? rc_matrix{mid->view().data, k, k, k, 1} : none, k * k, s ? s->data() : nullptr, p,
+                                                       rc_matrix{right.view().data, k, n, n, 1}, k * n, ranks ? ranks->data() : nullptr, count,
+                                                       want_residual ? rc_matrix{out.e.view().data, m, n, n, 1} : none, m * n, out.err.data(),
+                                                       out.nrm.data()));
+    return out;
+}
+// the three batched decompositions against the blocks they were computed from, each block at its own rank
+template <typename T>
+BatchedResidual<T> residual_batched(const BatchedColumnID<T> &id, const DeviceMatrix<T> &a, bool want_residual = false) {
+    return lowrank_residual_batched<T>(a, id.c, nullptr, nullptr, id.z, &id.ranks, (int32_t)id.ranks.size(), want_residual);
+}
+template <typename T>
+BatchedResidual<T> residual_batched(const BatchedTwoSidedID<T> &id, const DeviceMatrix<T> &a, bool want_residual = false) {
+    return lowrank_residual_batched<T>(a, id.c, &id.x, nullptr, id.r, &id.ranks, (int32_t)id.ranks.size(), want_residual);
+}
+template <typename T>
+BatchedResidual<T> residual_batched(const BatchedSVD<T> &svd, const DeviceMatrix<T> &a, bool want_residual = false) {
+    return lowrank_residual_batched<T>(a, svd.u, nullptr, &svd.s, svd.vt, &svd.ranks, (int32_t)svd.ranks.size(), want_residual);
+}
 template <typename T>
 typename Scalar<T>::real max_col_norm(const DeviceMatrix<T> &y) {  // :184-191
     typename Scalar<T>::real out = 0;

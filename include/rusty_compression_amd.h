@@ -608,6 +608,36 @@ rc_status rc_lowrank_recompress_batched_f32(rc_context *ctx, rc_matrix left, int
  * workspace bounded by the grid, not by count. */
 rc_status rc_sketch_column_id_rank_batched_f64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega, int64_t omega_batch_stride, int32_t count, int64_t k, double tol, rc_matrix y, int64_t y_batch_stride, rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks);
 rc_status rc_sketch_column_id_rank_batched_f32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega, int64_t omega_batch_stride, int32_t count, int64_t k, double tol, rc_matrix y, int64_t y_batch_stride, rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks);
+/* The certificate of such a batch: the Frobenius norm of what a low-rank factorization leaves of its block, in one stream-ordered, capturable call
+ * that reads the ranks on the device: per block the reference's rel_diff_fro(x.to_mat(), a) (src/lib.rs) without the m x n temporary of to_mat, on
+ * the domain of the sketched column ID, so the output of every batched compressor above is accepted.  Real scalars in this version.
+ * Operands.  The factor operands are exactly those of rc_lowrank_apply_batched_*: left (m x K), mid (K x K; mid.data == NULL: none), s (row i =
+ * s + i * s_stride, at least K reals; NULL: none), right (K x n), ranks (count device values; NULL: every rank is K).  a is m x n.  Block i of
+ * every operand is its view moved by i times its batch stride; a batch stride of 0 is legal for every input; any row and column strides; every
+ * pointer a device pointer.
+ * Per block (absent factors omitted), with r = ranks[i] clamped to [0, K] and Ah_i = left_i[:, :r] mid_i[:r, :r] diag(s_i[:r]) right_i[:r, :]:
+ *   err[i] = ||a_i - Ah_i||_F;
+ *   nrm[i] = ||a_i||_F; nrm == NULL: not written;
+ *   e_i = a_i - Ah_i (m x n) when e.data != NULL; e.data == NULL: not written, the other fields of e are then ignored.
+ * err and nrm are contiguous and of the real type of the call; e must not overlap any input.
+ * Reads.  Elements of left, mid, s and right at an index >= r are never read: they may hold anything, NaN included, so the result does not rely
+ * on the zero tails the batched calls write.
+ * Arithmetic.  An element of Ah is the sum over ascending l, from zero, of left[i, l] W[l, j], four terms per v_mfma_f64_16x16x4_f64 /
+ * v_mfma_f32_16x16x4_f32 (exact f32, no reduced precision).  W = right itself when there is neither mid nor s; otherwise
+ * W = mid[:r, :r] (diag(s[:r]) right[:r, :]) with diag(s) right rounded once per element and the mid product summed in ascending inner index by
+ * plain FMAs.  The residual element is a - Ah, one rounding.  Squares of e and of a are accumulated in f64 for both types, in a fixed order that
+ * depends on (m, n) alone, and the root is rounded to the output type.  There is no scaling: entries below about 1e-154 in magnitude contribute
+ * nothing to err and nrm, and entries above about 1e154 overflow them to inf (e is unaffected).
+ * Consequences.  With r = 0, err[i] and nrm[i] are the same bits and e_i = a_i bit for bit.  For column-ID factors (no mid, no s) column
+ * col_ind[j], j < r, of e is exactly zero: a unit column of z rebuilds the column of c exactly.  Block i's bits depend on block i's operands
+ * and the call's shapes alone: not on count, the position in the batch, the neighbours, any batch, row or column stride, the grid, whether e or
+ * nrm is requested, or graph replay against an eager call.  Non-finite input stays inside its block's err, nrm and e.
+ * Domain: 1 <= m <= 65536, 1 <= n <= 512, 1 <= K <= 128, count >= 0 (0: nothing to do).  RC_INVALID_ARGUMENT for an argument outside the domain,
+ * inconsistent shapes (left.rows != a.rows, left.cols != right.rows, right.cols != a.cols, mid not K x K, e not m x n), an e batch stride smaller
+ * than one view's span when count > 1, a null a, left, right or err with count > 0, or a null ctx (rejected before a device is touched).  No host
+ * synchronisation; workspace bounded by the grid, not by count. */
+rc_status rc_lowrank_residual_batched_f64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const double *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix e, int64_t e_batch_stride, double *err, double *nrm);
+rc_status rc_lowrank_residual_batched_f32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const float *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix e, int64_t e_batch_stride, float *err, float *nrm);
 
 /* The gather over RCCL (xGMI inside a node).  One process per GPU: rank 0 calls rc_comm_unique_id and hands the 128
  * bytes to the other ranks by whatever means the host has (MPI, a file, torch.distributed), every rank calls

@@ -1,0 +1,264 @@
+// Residual norms of a batch of low-rank factorizations against their blocks in one rank-aware launch (rc_lowrank_residual_batched_*).
+//
+// Per block i, with r = ranks[i] clamped to [0, K] (K when there are no ranks) and Ah = left_i[:, :r] mid_i[:r, :r] diag(s_i[:r])
+// right_i[:r, :] (absent factors omitted): err[i] = ||a_i - Ah||_F, nrm[i] = ||a_i||_F and, when asked for, e_i = a_i - Ah: the
+// reference's rel_diff_fro(x.to_mat(), a) for the outputs of every batched compressor, without the m x n temporary of to_mat and for the
+// tall blocks of the sketched column ID (m <= 65536).  Nothing at an index >= r is read.
+//
+// MI355X mapping.  The persistent grid of 256-thread workgroups (bid_grid), one workgroup per block from start to finish, nothing
+// crossing workgroups, no atomics.  Two phases per block:
+//   1. W (r x n), the factor the rebuild multiplies left by, produced only when mid or s is present (without either W is right itself and
+//      the MFMA's B operand is read straight from right in phase 2, zero at an inner index >= r or a column >= n: no image, no workspace).
+//      W0 = diag(s[:r]) right[:r, :], read with the lanes along right's smaller stride; with mid, W1 = mid[:r, :r] W0, one thread per
+//      element, plain FMAs over the ascending inner index.  The image has the column index fastest (pitch BR: 16 modulo 32, the MFMA's B-operand read is then free of bank
+//      conflicts); rows r .. 4 ceil(r / 4) - 1 and columns n .. 64 ceil(n / 64) - 1 are zeros written here, never values of a factor.
+//      The images live in LDS when they fit BID_MAX_LDS next to the chunk images, else in the workgroup's slot of the grid-bounded
+//      workspace (L2 resident: at most 128 x 528 elements, twice with mid); the plan only moves base pointers, so it cannot change a bit.
+//      right (and mid, s) are read from memory once per block.
+//   2. Row chunks of BR_ROWS = 32 rows against the resident W.  left's chunk (32 x 4 ceil(r / 4), zeros past m and past r) is staged
+//      in LDS once per chunk -- left is read from HBM once -- and a's chunk streams through LDS in tiles of BR_COLS = 64 columns,
+//      each element read from HBM once, both with the lanes along the operand's smaller stride (bid_load's rule) and that index
+//      fastest in the image.  Per tile each wave owns a 16-column strip and both 16-row tiles: ceil(r / 4) MFMAs per tile
+//      (v_mfma_f64_16x16x4_f64 / v_mfma_f32_16x16x4_f32, Acc<T> of rc_gemm.hpp) from zero accumulators, then e = a - acc on the a
+//      values read back from LDS in the accumulator layout.  W is re-read ceil(m / 32) times, from LDS or L2.  Rows past m and columns
+//      past n are zeros in LDS: the MFMA loop has no edge branch and, with finite factors, the padding adds +0 to the sums (a factor
+//      that holds inf or NaN makes 0 x inf = NaN there, so that block's err is NaN where inf might be expected: it stays in its block).  When e is requested the tile
+//      goes back into a's image and is stored with the lanes along e's smaller stride.
+// Squares of e and of a are accumulated in f64 by each thread over its 8 elements of every tile, tiles in (row chunk, column tile)
+// order; the 64 lanes are then summed by a butterfly and the four waves as (w0 + w1) + (w2 + w3).  The longest chain of additions a
+// sum passes through is L(m, n) = 8 ceil(m / 32) ceil(n / 64) + 8.  Every order above is a function of (m, n, r) alone, which is what
+// the bit-independence clause of the contract rests on.
+#include <algorithm>
+
+#include "rc_common.hpp"
+#include "rc_device.hpp"
+#include "rc_gemm.hpp"
+
+namespace rc {
+
+namespace {
+
+constexpr int BR_THREADS = 256;
+constexpr int BR_ROWS = 32;  // rows of a and of left per chunk: two 16-row MFMA tiles
+constexpr int BR_COLS = 64;  // columns of a per tile: one 16-column strip per wave
+constexpr int BR_PER = BR_ROWS * BR_COLS / BR_THREADS;  // 8 elements of a tile per thread, staged and computed
+constexpr int BR_PAR = BR_ROWS + 4;   // pitch of a's image with the row index fastest
+constexpr int BR_PLR = BR_ROWS + 16;  // pitch of left's image with the row index fastest (16 modulo 32)
+// pitch of a's image with the column index fastest: the accumulator-layout read has lanes 16 columns x 4 rows, the rows 1 (f64) or 4 (f32) apart
+template <typename T>
+constexpr int br_pac() { return sizeof(T) == 8 ? 80 : 68; }
+template <typename T>
+constexpr int br_a_elems() { return BR_ROWS * br_pac<T>() > BR_COLS * BR_PAR ? BR_ROWS * br_pac<T>() : BR_COLS * BR_PAR; }
+__host__ __device__ constexpr int br_k4(int k) { return (k + 3) & ~3; }
+__host__ __device__ constexpr int br_plk(int k) { return ((k + 31) & ~31) + 4; }  // pitch of left's image with the inner index fastest
+__host__ __device__ constexpr int br_l_elems(int k) { return BR_ROWS * br_plk(k) > br_k4(k) * BR_PLR ? BR_ROWS * br_plk(k) : br_k4(k) * BR_PLR; }
+__host__ __device__ constexpr int br_np(int n) { return (n + BR_COLS - 1) & ~(BR_COLS - 1); }
+__host__ __device__ constexpr int br_pw(int n) { return br_np(n) + 16; }  // pitch of W's image
+__host__ __device__ constexpr size_t br_w_elems(int k, int n, bool has_mid) { return (size_t)(has_mid ? 2 : 1) * br_k4(k) * br_pw(n); }
+
+// dynamic LDS: red[8] (f64) | [W0 [W1, with mid]: K4 x pw(n), LDS plan only] a's tile image | left's chunk image
+template <typename T>
+size_t br_lds_bytes(int k, int n, bool has_mid, bool w_lds) {
+    return 64 + ((w_lds ? br_w_elems(k, n, has_mid) : 0) + (size_t)br_a_elems<T>() + (size_t)br_l_elems(k)) * sizeof(T);
+}
+
+template <typename T>
+struct BrArgs {
+    Mat<T> a, left, mid, right, e;  // mid.p == nullptr: none; e.p == nullptr: the residual is not written
+    int64_t abs, lbs, mbs, rbs, ebs, s_stride;
+    const T *s;
+    const int64_t *ranks;
+    T *err, *nrm, *ws;
+    int count;
+    bool w_lds;   // W's images in LDS (else in the workgroup's workspace slot)
+    bool direct;  // neither mid nor s: W is right itself, read in place
+};
+
+template <typename T>
+__global__ __launch_bounds__(BR_THREADS) void k_batched_residual(BrArgs<T> g) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const int m = (int)g.a.rows, n = (int)g.a.cols, K = (int)g.left.cols;
+    const int np = br_np(n), pw = br_pw(n);
+    const bool has_mid = g.mid.p != nullptr;
+    const size_t wel = (size_t)br_k4(K) * pw;
+    double *red = reinterpret_cast<double *>(smem_raw);
+    T *lds = reinterpret_cast<T *>(smem_raw + 64);
+    T *W0 = g.w_lds ? lds : g.direct ? lds : g.ws + (size_t)blockIdx.x * br_w_elems(K, n, has_mid);  // unused when direct
+    T *W1 = W0 + wel;
+    T *As = lds + (g.w_lds ? br_w_elems(K, n, has_mid) : 0);
+    T *Ls = As + br_a_elems<T>();
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r16 = lane & 15, k4 = lane >> 4;
+    // the lanes of every staging loop run along the operand's smaller stride, and that index is the fastest one of the LDS image
+    const bool a_rows = g.a.rs <= g.a.cs, l_rows = g.left.rs <= g.left.cs, r_rows = g.right.rs <= g.right.cs, e_rows = g.e.rs <= g.e.cs;
+    const int as_sr = a_rows ? 1 : br_pac<T>(), as_sc = a_rows ? BR_PAR : 1;  // As[row * as_sr + col * as_sc]
+    const int ls_sr = l_rows ? 1 : br_plk(K), ls_sk = l_rows ? BR_PLR : 1;    // Ls[row * ls_sr + k * ls_sk]
+    // this thread's BR_PER elements of a tile when staging a (row0 + drow * q, col0 + dcol * q) and when storing e
+    const int a_row0 = a_rows ? (tid & (BR_ROWS - 1)) : (tid / BR_COLS), a_col0 = a_rows ? (tid / BR_ROWS) : (tid & (BR_COLS - 1));
+    const int a_drow = a_rows ? 0 : BR_THREADS / BR_COLS, a_dcol = a_rows ? BR_THREADS / BR_ROWS : 0;
+    const int e_row0 = e_rows ? (tid & (BR_ROWS - 1)) : (tid / BR_COLS), e_col0 = e_rows ? (tid / BR_ROWS) : (tid & (BR_COLS - 1));
+    const int e_drow = e_rows ? 0 : BR_THREADS / BR_COLS, e_dcol = e_rows ? BR_THREADS / BR_ROWS : 0;
+    // and in the accumulator layout: rows i * 16 + Acc<T>::row(lane, reg) of column wv * 16 + r16
+    const T *ls_ld = Ls + r16 * ls_sr + k4 * ls_sk;
+    T *as_acc = As + (wv * 16 + r16) * as_sc;
+
+    for (int b = blockIdx.x; b < g.count; b += gridDim.x) {
+        int r = K;
+        if (g.ranks) {
+            const int64_t rv = g.ranks[b];
+            r = rv < 0 ? 0 : rv > K ? K : (int)rv;
+        }
+        r = __builtin_amdgcn_readfirstlane(r);  // one value per block, uniform by construction: the loop bounds stay in scalar registers
+        const int r4 = br_k4(r);
+        const T *__restrict__ A = g.a.p + (int64_t)b * g.abs;
+        const T *__restrict__ Lf = g.left.p + (int64_t)b * g.lbs;
+        const T *__restrict__ Rt = g.right.p + (int64_t)b * g.rbs;
+        const T *sb = g.s ? g.s + (int64_t)b * g.s_stride : nullptr;
+        T *E = g.e.p ? g.e.p + (int64_t)b * g.ebs : nullptr;
+
+        // ---- phase 1: W0 = diag(s[:r]) right[:r, :], zero rows r .. r4 - 1 and zero columns n .. np - 1 ----------------------------------
+        const int wtot = g.direct ? 0 : r4 * np;  // without mid and s there is nothing to produce
+        for (int idx = tid; idx < wtot; idx += BR_THREADS) {
+            int k, j;
+            if (r_rows) { k = idx % r4; j = idx / r4; } else { j = idx % np; k = idx / np; }
+            T v = (T)0;
+            if (k < r && j < n) {
+                v = Rt[(int64_t)k * g.right.rs + (int64_t)j * g.right.cs];
+                if (sb) v = sb[k] * v;
+            }
+            W0[(size_t)k * pw + j] = v;
+        }
+        if (!g.direct) __syncthreads();  // uniform over the grid
+        const T *Wp = W0;
+        if (has_mid) {  // W1 = mid[:r, :r] W0: the 64 lanes of a wave share the row l (np is a multiple of 64) and read one element of mid
+            const T *__restrict__ Md = g.mid.p + (int64_t)b * g.mbs;
+            for (int idx = tid; idx < wtot; idx += BR_THREADS) {
+                const int j = idx % np, l = idx / np;
+                T acc = (T)0;
+                if (l < r && j < n) {
+                    const T *mr = Md + (int64_t)l * g.mid.rs;
+                    for (int p = 0; p < r; ++p) acc = fma(mr[(int64_t)p * g.mid.cs], W0[(size_t)p * pw + j], acc);
+                }
+                W1[(size_t)l * pw + j] = acc;
+            }
+            __syncthreads();
+            Wp = W1;
+        }
+        const T *w_ld = Wp + (size_t)k4 * pw + wv * 16 + r16;
+
+        // ---- phase 2: row chunks of a and left against W ------------------------------------------------------------------------------
+        double se = 0.0, sa = 0.0;
+        for (int m0 = 0; m0 < m; m0 += BR_ROWS) {
+            const int ltot = BR_ROWS * r4;
+            for (int idx = tid; idx < ltot; idx += BR_THREADS) {
+                int row, k;
+                if (l_rows) { row = idx & (BR_ROWS - 1); k = idx / BR_ROWS; } else { k = idx % r4; row = idx / r4; }
+                const bool ok = m0 + row < m && k < r;
+                Ls[row * ls_sr + k * ls_sk] = ok ? Lf[(int64_t)(m0 + row) * g.left.rs + (int64_t)k * g.left.cs] : (T)0;
+            }
+            for (int c0 = 0; c0 < n; c0 += BR_COLS) {
+                T av[BR_PER];
+#pragma unroll
+                for (int q = 0; q < BR_PER; ++q) {
+                    const int row = a_row0 + a_drow * q, col = a_col0 + a_dcol * q;
+                    const bool ok = m0 + row < m && c0 + col < n;
+                    av[q] = ok ? A[(int64_t)(m0 + row) * g.a.rs + (int64_t)(c0 + col) * g.a.cs] : (T)0;
+                }
+#pragma unroll
+                for (int q = 0; q < BR_PER; ++q) As[(a_row0 + a_drow * q) * as_sr + (a_col0 + a_dcol * q) * as_sc] = av[q];
+                __syncthreads();
+                typename Acc<T>::type acc[2];
+                acc[0] = typename Acc<T>::type{0, 0, 0, 0};
+                acc[1] = typename Acc<T>::type{0, 0, 0, 0};
+                const int bcol = c0 + wv * 16 + r16;
+                for (int ks = 0; ks < r4; ks += 4) {
+                    T bf;
+                    if (g.direct)  // uniform over the grid: right in place, zero past the rank and past n
+                        bf = (ks + k4 < r && bcol < n) ? Rt[(int64_t)(ks + k4) * g.right.rs + (int64_t)bcol * g.right.cs] : (T)0;
+                    else
+                        bf = w_ld[(size_t)ks * pw + c0];
+                    acc[0] = Acc<T>::mfma(ls_ld[ks * ls_sk], bf, acc[0]);
+                    acc[1] = Acc<T>::mfma(ls_ld[16 * ls_sr + ks * ls_sk], bf, acc[1]);
+                }
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int reg = 0; reg < 4; ++reg) {
+                        T *pa = as_acc + (i * 16 + Acc<T>::row(lane, reg)) * as_sr;
+                        const T x = *pa;
+                        const T ev = x - acc[i][reg];
+                        se = fma((double)ev, (double)ev, se);
+                        sa = fma((double)x, (double)x, sa);
+                        if (E) *pa = ev;
+                    }
+                if (E) {  // uniform over the grid
+                    __syncthreads();
+#pragma unroll
+                    for (int q = 0; q < BR_PER; ++q) {
+                        const int row = e_row0 + e_drow * q, col = e_col0 + e_dcol * q;
+                        if (m0 + row < m && c0 + col < n) E[(int64_t)(m0 + row) * g.e.rs + (int64_t)(c0 + col) * g.e.cs] = As[row * as_sr + col * as_sc];
+                    }
+                }
+                __syncthreads();  // a's image is rewritten by the next tile, left's by the next chunk
+            }
+        }
+        // ---- the two sums: 64 lanes by a butterfly, then the four waves ------------------------------------------------------------------
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            se += __shfl_xor(se, off, 64);
+            sa += __shfl_xor(sa, off, 64);
+        }
+        if (lane == 0) {
+            red[wv] = se;
+            red[4 + wv] = sa;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            g.err[b] = (T)sqrt((red[0] + red[1]) + (red[2] + red[3]));
+            if (g.nrm) g.nrm[b] = (T)sqrt((red[4] + red[5]) + (red[6] + red[7]));
+        }
+        __syncthreads();  // red and W's images are rewritten by the next block
+    }
+}
+
+}  // namespace
+
+// W's images in LDS when they fit next to the chunk images, else in the workgroup's slot of the grid-bounded workspace: the plan only
+// moves base pointers, so it cannot change a block's bits; without mid and s there is no image (plan=W:right).  One kernel per scalar
+// type.  attr_set, as in the sibling launchers: a racing first call sets the same attribute twice, which is harmless.
+template <typename T>
+void batched_lowrank_residual(rc_context *c, Mat<T> a, int64_t abs, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride, Mat<T> right,
+                              int64_t rbs, const int64_t *ranks, int32_t count, Mat<T> e, int64_t ebs, T *err, T *nrm) {
+    const int m = (int)a.rows, n = (int)a.cols, K = (int)left.cols;
+    if (count <= 0) return;
+    const bool has_mid = mid.p != nullptr;
+    const bool direct = !has_mid && !s;  // W is right itself: no image
+    const bool w_lds = !direct && br_lds_bytes<T>(K, n, has_mid, true) <= BID_MAX_LDS;
+    const size_t lds = br_lds_bytes<T>(K, n, has_mid, w_lds);
+    RC_REQUIRE(lds <= BID_MAX_LDS, RC_RUNTIME_ERROR, "lowrank_residual_batched: %zu bytes of LDS", lds);
+    const void *kern = reinterpret_cast<const void *>(k_batched_residual<T>);
+    static bool attr_set[64] = {};
+    if (!attr_set[c->device & 63]) {
+        RC_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BID_MAX_LDS));
+        attr_set[c->device & 63] = true;
+    }
+    const size_t per = w_lds || direct ? 0 : br_w_elems(K, n, has_mid) * sizeof(T);
+    int64_t slots = 0;
+    const int64_t grid = bid_grid(c, kern, lds, per, count, &slots);
+    ProfScope ps(c, "op:batched_residual %dx%d k=%d count=%d grid=%lld slots=%lld plan=W:%s,rows=%d,cols=%d%s%s%s%s", m, n, K, (int)count, (long long)grid,
+                 (long long)slots, direct ? "right" : w_lds ? "lds" : "ws", BR_ROWS, BR_COLS, has_mid ? ",mid" : "", s ? ",s" : "", e.p ? ",e" : "", nrm ? ",nrm" : "");
+    BrArgs<T> g;
+    g.a = a; g.left = left; g.mid = mid; g.right = right; g.e = e;
+    g.abs = abs; g.lbs = lbs; g.mbs = mbs; g.rbs = rbs; g.ebs = ebs; g.s_stride = s_stride;
+    g.s = s; g.ranks = ranks; g.err = err; g.nrm = nrm;
+    g.ws = per ? c->alloc<T>((size_t)grid * per / sizeof(T)) : nullptr;
+    g.count = (int)count; g.w_lds = w_lds; g.direct = direct;
+    hipLaunchKernelGGL(k_batched_residual<T>, dim3((unsigned)grid), dim3(BR_THREADS), lds, c->stream, g);
+    RC_HIP(hipGetLastError());
+}
+
+template void batched_lowrank_residual<double>(rc_context *, Mat<double>, int64_t, Mat<double>, int64_t, Mat<double>, int64_t, const double *, int64_t, Mat<double>,
+                                               int64_t, const int64_t *, int32_t, Mat<double>, int64_t, double *, double *);
+template void batched_lowrank_residual<float>(rc_context *, Mat<float>, int64_t, Mat<float>, int64_t, Mat<float>, int64_t, const float *, int64_t, Mat<float>,
+                                              int64_t, const int64_t *, int32_t, Mat<float>, int64_t, float *, float *);
+
+}  // namespace rc

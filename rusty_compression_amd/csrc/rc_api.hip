@@ -1259,6 +1259,32 @@ void sketch_column_id_rank_batched(rc_context *c, Mat<T> a, int64_t abs, Mat<T> 
     batched_sketch_column_id(c, a, abs, omega, obs, count, kk, tol, y, ybs, cm, cbs, z, zbs, col_ind, ranks);
 }
 
+// ||a_i - left_i mid_i diag(s_i) right_i||_F at each block's rank, ||a_i||_F and optionally the residual blocks, for the factors of any batched
+// compressor: the reference's rel_diff_fro(x.to_mat(), a) per block (src/lib.rs), in one launch and on the sketched ID's domain
+template <typename T>
+void lowrank_residual_batched(rc_context *c, Mat<T> a, int64_t abs, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride,
+                              Mat<T> right, int64_t rbs, const int64_t *ranks, int32_t count, Mat<T> e, int64_t ebs, T *err, T *nrm) {
+    const char *who = "lowrank_residual_batched";
+    const int64_t m = a.rows, n = a.cols, K = left.cols;
+    RC_REQUIRE(count >= 0, RC_INVALID_ARGUMENT, "%s: count = %d < 0", who, (int)count);
+    RC_REQUIRE(m >= 1 && m <= 65536 && n >= 1 && n <= 512 && K >= 1 && K <= 128, RC_INVALID_ARGUMENT,
+               "%s: needs 1 <= m <= 65536, 1 <= n <= 512 and 1 <= K <= 128 (got a %lld x %lld, left %lld x %lld)", who, (long long)m, (long long)n,
+               (long long)left.rows, (long long)K);
+    RC_REQUIRE(left.rows == m && right.rows == K && right.cols == n, RC_INVALID_ARGUMENT,
+               "%s: a is %lld x %lld but left is %lld x %lld and right %lld x %lld", who, (long long)m, (long long)n, (long long)left.rows, (long long)K,
+               (long long)right.rows, (long long)right.cols);
+    RC_REQUIRE(!mid.p || (mid.rows == K && mid.cols == K), RC_INVALID_ARGUMENT, "%s: mid must be %lld x %lld (got %lld x %lld)", who, (long long)K,
+               (long long)K, (long long)mid.rows, (long long)mid.cols);
+    if (e.p) {
+        RC_REQUIRE(e.rows == m && e.cols == n, RC_INVALID_ARGUMENT, "%s: e must be %lld x %lld (got %lld x %lld)", who, (long long)m, (long long)n,
+                   (long long)e.rows, (long long)e.cols);
+        check_batch_stride(who, "e", ebs, e, count);
+    }
+    if (count > 0) RC_REQUIRE(a.p && left.p && right.p && err, RC_INVALID_ARGUMENT, "%s: null pointer", who);
+    if (count == 0) return;
+    batched_lowrank_residual(c, a, abs, left, lbs, mid, mbs, s, s_stride, right, rbs, ranks, count, e, ebs, err, nrm);
+}
+
 template <typename T>
 void rank_by_tolerance(rc_context *c, Mat<T> tri, double tol, int64_t *rank) {
     RC_REQUIRE(tol < 1.0 && 0.0 <= tol, RC_INVALID_ARGUMENT, "Require 0 <= tol < 1.0");
@@ -1835,6 +1861,16 @@ rc_status rc_invert_permutation(rc_context *ctx, const int64_t *perm, int64_t n,
             sketch_column_id_rank_batched<T>(ctx, from_c<T>(a), a_batch_stride, from_c<T>(omega), omega_batch_stride, count, k, tol,     \
                                              from_c<T>(y), y_batch_stride, from_c<T>(c), c_batch_stride, from_c<T>(z), z_batch_stride,   \
                                              col_ind, ranks);                                                                            \
+        });                                                                                                                              \
+    }                                                                                                                                    \
+    rc_status rc_lowrank_residual_batched_##SUF(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix left, int64_t left_batch_stride, \
+                                                rc_matrix mid, int64_t mid_batch_stride, const T *s, int64_t s_stride, rc_matrix right,  \
+                                                int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix e,            \
+                                                int64_t e_batch_stride, T *err, T *nrm) {                                                \
+        return guarded(ctx, [&] {                                                                                                        \
+            lowrank_residual_batched<T>(ctx, from_c<T>(a), a_batch_stride, from_c<T>(left), left_batch_stride, from_c<T>(mid),           \
+                                        mid_batch_stride, s, s_stride, from_c<T>(right), right_batch_stride, ranks, count, from_c<T>(e), \
+                                        e_batch_stride, err, nrm);                                                                       \
         });                                                                                                                              \
     }
 

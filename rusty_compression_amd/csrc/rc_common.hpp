@@ -252,6 +252,13 @@ template <typename T> void batched_lowrank_recompress(rc_context *c, Mat<T> left
 // clamped; col_ind count x n, ranks count (arguments checked by the caller)
 template <typename T> void batched_sketch_column_id(rc_context *c, Mat<T> a, int64_t abs, Mat<T> omega, int64_t obs, int32_t count, int64_t kk, double tol,
                                                     Mat<T> y, int64_t ybs, Mat<T> cm, int64_t cbs, Mat<T> z, int64_t zbs, int64_t *col_ind, int64_t *ranks);
+// the residual of such factors against the blocks they approximate, in one rank-aware launch (kernels_batched_residual.hip): block i is a (m x n), left
+// (m x K), mid (K x K, p == nullptr: none), right (K x n) and e (m x n, p == nullptr: not written) each moved by i times its batch stride, s + i * s_stride
+// its K real scales (nullptr: none), ranks count device values (nullptr: every rank is K); err and nrm (nullptr: not written) count values: ||a_i - left
+// mid diag(s) right||_F at the block's rank and ||a_i||_F (arguments checked by the caller)
+template <typename T> void batched_lowrank_residual(rc_context *c, Mat<T> a, int64_t abs, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s,
+                                                    int64_t s_stride, Mat<T> right, int64_t rbs, const int64_t *ranks, int32_t count, Mat<T> e, int64_t ebs,
+                                                    T *err, T *nrm);
 // the batched kernels' dynamic-LDS cap and persistent grid (kernels_batched_id.hip): the resident workgroups of 256 threads on every
 // CU, fewer when the workspace (ws_per bytes per workgroup, 0 in the LDS variants) would pass 256 MiB unless that leaves less than
 // one workgroup per CU; never more than count.  *slots receives the grid before that last bound (slots= in the profile label)
