@@ -727,24 +727,29 @@ BatchedSVD<T> recompress_batched(const BatchedSVD<T> &a, const BatchedSVD<T> &b,
 // the residual of every block of a batch against its stacked factors in one rank-aware call (rc_lowrank_residual_batched_*): per block the
 // reference's rel_diff_fro(x.to_mat(), a) without the rebuilt block, on the domain of the sketched column ID (m <= 65536, n <= 512, K <= 128).
 // a is count * m x n, the factors as in lowrank_apply_batched.  err[i] = ||a_i - left_i mid_i diag(s_i) right_i||_F at the block's rank,
-// nrm[i] = ||a_i||_F, and with want_residual e (count * m x n) holds the residual blocks (else it is empty).  The C ABI has the entry point
-// for the real scalars only, so it is reached through its own dispatch: Api<c64> and Api<c32> stay complete.
+// nrm[i] = ||a_i||_F, and with want_residual e (count * m x n) holds the residual blocks (else it is empty).  Every scalar type: for c64 and c32
+// s, err and nrm are of the real type and nothing is conjugated (vt is V^H, as svd_rank_batched returns it).  The entry point is reached through
+// its own dispatch, like the recompression's: Api<T> keeps the members every scalar type has had from the start.
 template <typename T> struct ResidualApi;
 template <> struct ResidualApi<double> { static constexpr auto lowrank_residual_batched = rc_lowrank_residual_batched_f64; };
 template <> struct ResidualApi<float> { static constexpr auto lowrank_residual_batched = rc_lowrank_residual_batched_f32; };
+template <> struct ResidualApi<c64> { static constexpr auto lowrank_residual_batched = rc_lowrank_residual_batched_c64; };
+template <> struct ResidualApi<c32> { static constexpr auto lowrank_residual_batched = rc_lowrank_residual_batched_c32; };
 template <typename T>
 struct BatchedResidual {
-    DeviceBuffer<T> err, nrm;
+    DeviceBuffer<typename Scalar<T>::real> err, nrm;
     DeviceMatrix<T> e;
     bool has_e = false;
 };
 template <typename T>
-BatchedResidual<T> lowrank_residual_batched(const DeviceMatrix<T> &a, const DeviceMatrix<T> &left, const DeviceMatrix<T> *mid, const DeviceBuffer<T> *s,
-                                            const DeviceMatrix<T> &right, const DeviceIndex *ranks, int32_t count, bool want_residual = false) {
+BatchedResidual<T> lowrank_residual_batched(const DeviceMatrix<T> &a, const DeviceMatrix<T> &left, const DeviceMatrix<T> *mid,
+                                            const DeviceBuffer<typename Scalar<T>::real> *s, const DeviceMatrix<T> &right, const DeviceIndex *ranks,
+                                            int32_t count, bool want_residual = false) {
+    using Real = typename Scalar<T>::real;
     const Context &ctx = a.ctx();
     const int64_t m = count > 0 ? a.nrows() / count : 0, n = a.ncols(), k = left.ncols();
     const int64_t p = s && count > 0 ? (int64_t)(s->size() / (std::size_t)count) : 0;
-    BatchedResidual<T> out{DeviceBuffer<T>(ctx, (std::size_t)count), DeviceBuffer<T>(ctx, (std::size_t)count),
+    BatchedResidual<T> out{DeviceBuffer<Real>(ctx, (std::size_t)count), DeviceBuffer<Real>(ctx, (std::size_t)count),
                            want_residual ? DeviceMatrix<T>(ctx, (int64_t)count * m, n) : DeviceMatrix<T>(), want_residual};
     if (count == 0) return out;  // an empty batch is a no-op (the block shape cannot be read off an empty stack)
     const rc_matrix none{nullptr, 0, 0, 0, 0};

@@ -610,7 +610,9 @@ rc_status rc_sketch_column_id_rank_batched_f64(rc_context *ctx, rc_matrix a, int
 rc_status rc_sketch_column_id_rank_batched_f32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega, int64_t omega_batch_stride, int32_t count, int64_t k, double tol, rc_matrix y, int64_t y_batch_stride, rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks);
 /* The certificate of such a batch: the Frobenius norm of what a low-rank factorization leaves of its block, in one stream-ordered, capturable call
  * that reads the ranks on the device: per block the reference's rel_diff_fro(x.to_mat(), a) (src/lib.rs) without the m x n temporary of to_mat, on
- * the domain of the sketched column ID, so the output of every batched compressor above is accepted.  Real scalars in this version.
+ * the domain of the sketched column ID, so the output of every batched compressor above is accepted.  The _c64 / _c32 forms take interleaved
+ * (re, im) views with strides and batch strides in complex elements; s, err and nrm stay of the real type and nothing is conjugated, as in
+ * rc_lowrank_apply_batched_c* (vt is already V^H, the two-sided c already Z2^H).
  * Operands.  The factor operands are exactly those of rc_lowrank_apply_batched_*: left (m x K), mid (K x K; mid.data == NULL: none), s (row i =
  * s + i * s_stride, at least K reals; NULL: none), right (K x n), ranks (count device values; NULL: every rank is K).  a is m x n.  Block i of
  * every operand is its view moved by i times its batch stride; a batch stride of 0 is legal for every input; any row and column strides; every
@@ -628,6 +630,14 @@ rc_status rc_sketch_column_id_rank_batched_f32(rc_context *ctx, rc_matrix a, int
  * plain FMAs.  The residual element is a - Ah, one rounding.  Squares of e and of a are accumulated in f64 for both types, in a fixed order that
  * depends on (m, n) alone, and the root is rounded to the output type.  There is no scaling: entries below about 1e-154 in magnitude contribute
  * nothing to err and nrm, and entries above about 1e154 overflow them to inf (e is unaffected).
+ * Complex arithmetic.  The same MFMAs on the real and imaginary parts as separate real operands: per element each of Re Ah and Im Ah is one
+ * accumulator chain from zero over ascending l, four terms per instruction, and within a step of four the Re chain takes the products
+ * Re(left) Re(W), then (-Im(left)) Im(W), the Im chain Re(left) Im(W), then Im(left) Re(W); the negation is exact.  diag(s) right is one rounding
+ * per component; the mid product is summed over ascending p from zero by plain FMAs, the four real products of a term in the order
+ * re += Re(mid) Re(W0), re += (-Im(mid)) Im(W0), im += Re(mid) Im(W0), im += Im(mid) Re(W0).  Each component of e is one rounding; the squares of
+ * Re e, Im e (Re a, Im a) enter the f64 sums element by element, re before im.  Hence: conjugating every complex operand leaves err and nrm
+ * bit for bit and conjugates e bit for bit (up to the sign of an exactly cancelled zero); operands whose imaginary parts are all +0 give Re e equal
+ * to the real call's e on the real parts and Im e = 0; the exact zeros of a column ID's kept columns hold as in the real call.
  * Consequences.  With r = 0, err[i] and nrm[i] are the same bits and e_i = a_i bit for bit.  For column-ID factors (no mid, no s) column
  * col_ind[j], j < r, of e is exactly zero: a unit column of z rebuilds the column of c exactly.  Block i's bits depend on block i's operands
  * and the call's shapes alone: not on count, the position in the batch, the neighbours, any batch, row or column stride, the grid, whether e or
@@ -638,6 +648,8 @@ rc_status rc_sketch_column_id_rank_batched_f32(rc_context *ctx, rc_matrix a, int
  * synchronisation; workspace bounded by the grid, not by count. */
 rc_status rc_lowrank_residual_batched_f64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const double *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix e, int64_t e_batch_stride, double *err, double *nrm);
 rc_status rc_lowrank_residual_batched_f32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const float *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix e, int64_t e_batch_stride, float *err, float *nrm);
+rc_status rc_lowrank_residual_batched_c64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const double *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix e, int64_t e_batch_stride, double *err, double *nrm);
+rc_status rc_lowrank_residual_batched_c32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const float *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix e, int64_t e_batch_stride, float *err, float *nrm);
 
 /* The gather over RCCL (xGMI inside a node).  One process per GPU: rank 0 calls rc_comm_unique_id and hands the 128
  * bytes to the other ranks by whatever means the host has (MPI, a file, torch.distributed), every rank calls

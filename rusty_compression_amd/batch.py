@@ -333,48 +333,49 @@ def svd_add_batched(u1: torch.Tensor, s1: torch.Tensor, vt1: torch.Tensor, u2: t
     return lowrank_recompress_batched(left, right, k, tol, s=s)
 
 
-def lowrank_residual_batched(a: torch.Tensor, left: torch.Tensor, right: torch.Tensor, mid: Optional[torch.Tensor] = None, s: Optional[torch.Tensor] = None,
-                             ranks: Optional[torch.Tensor] = None, want_residual: bool = False):
-    """Residual norms of every block of a batch against its low-rank factors in one stream-ordered call (rc_lowrank_residual_batched_*):
-    the reference's rel_diff_fro(x.to_mat(), a) per block (src/lib.rs) without the rebuilt blocks, for the outputs of every batched compressor.
-
-    a: [count, m, n], left: [count, m, K], right: [count, K, n], mid: [count, K, K] or None, s: [count, p >= K] or None, ranks: [count] int64
-    or None (every rank is K); float64 or float32 device tensors of one dtype, any strides (a stride-0 batch dimension shares one operand);
-    m <= 65536, n <= 512, K <= 128.  With r = ranks[i] clamped to [0, K] and Ah_i = left[i][:, :r] mid[i][:r, :r] diag(s[i][:r]) right[i][:r]
-    (absent factors omitted; nothing at an index >= r is read), returns err [count] = ||a_i - Ah_i||_F and nrm [count] = ||a_i||_F, and with
-    want_residual also e [count, m, n] = a_i - Ah_i.  Complex data and mismatched dtypes raise TypeError."""
+def _lowrank_residual_batched(who: str, complex_data: bool, a, left, right, mid, s, ranks, want_residual: bool):
+    """The shared body of lowrank_residual_batched (real dtypes) and lowrank_residual_batched_complex (complex dtypes, real s)."""
     from . import _lib
     from .types import as_device
 
-    ops = {"a": a, "left": left, "right": right, "mid": mid, "s": s}
+    ops = {"a": a, "left": left, "right": right, "mid": mid}
     ops = {name: as_device(t) for name, t in ops.items() if t is not None}
-    a, left, right, mid, s = ops["a"], ops["left"], ops["right"], ops.get("mid"), ops.get("s")
-    if a.dtype not in (torch.float64, torch.float32):
-        raise TypeError(f"lowrank_residual_batched: float64 or float32 data expected, got {a.dtype}")
+    if complex_data:
+        ops = {name: t.resolve_conj() for name, t in ops.items()}  # the kernels read the stored values
+    a, left, right, mid = ops["a"], ops["left"], ops["right"], ops.get("mid")
+    kinds = (torch.complex128, torch.complex64) if complex_data else (torch.float64, torch.float32)
+    if a.dtype not in kinds:
+        raise TypeError(f"{who}: {' or '.join(str(k).replace('torch.', '') for k in kinds)} data expected, got {a.dtype}")
     for name, t in ops.items():
         if t.dtype != a.dtype:
-            raise TypeError(f"lowrank_residual_batched: {name} is {t.dtype}, a is {a.dtype}")
+            raise TypeError(f"{who}: {name} is {t.dtype}, a is {a.dtype}")
+    real = _lib.real_dtype(a.dtype)
+    if s is not None:
+        s = as_device(s)
+        if s.dtype != real:
+            raise TypeError(f"{who}: s is {s.dtype}, expected {real}")
+        ops["s"] = s
     if a.dim() != 3 or left.dim() != 3 or right.dim() != 3 or (mid is not None and mid.dim() != 3):
         raise AssertionError("expected a [count, m, n], left [count, m, K], right [count, K, n] and mid [count, K, K]")
     count, m, n = a.shape
     kin = left.shape[2]
     for name, t in ops.items():
         if t.shape[0] != count:
-            raise AssertionError(f"lowrank_residual_batched: {name} holds {t.shape[0]} blocks, a {count}")
+            raise AssertionError(f"{who}: {name} holds {t.shape[0]} blocks, a {count}")
     if s is not None:
         if s.dim() != 2 or s.shape[1] < kin:
-            raise AssertionError(f"lowrank_residual_batched: s must be [count, p] with p >= K = {kin}")
+            raise AssertionError(f"{who}: s must be [count, p] with p >= K = {kin}")
         if s.stride(1) != 1:
             s = s.contiguous()
     if ranks is not None:
         ranks = as_device(ranks)
         if ranks.dtype != torch.int64:
-            raise TypeError(f"lowrank_residual_batched: ranks is {ranks.dtype}, expected torch.int64")
+            raise TypeError(f"{who}: ranks is {ranks.dtype}, expected torch.int64")
         if ranks.shape != (count,):
-            raise AssertionError("lowrank_residual_batched: ranks must be [count]")
+            raise AssertionError(f"{who}: ranks must be [count]")
         ranks = ranks.contiguous()
-    err = torch.empty(count, dtype=a.dtype, device=a.device)
-    nrm = torch.empty(count, dtype=a.dtype, device=a.device)
+    err = torch.empty(count, dtype=real, device=a.device)
+    nrm = torch.empty(count, dtype=real, device=a.device)
     e = torch.empty((count, m, n), dtype=a.dtype, device=a.device) if want_residual else None
 
     def view(t):  # block 0's view and the batch stride
@@ -387,6 +388,28 @@ def lowrank_residual_batched(a: torch.Tensor, left: torch.Tensor, right: torch.T
                                 *view(right), _lib.i64p(ranks), ctypes.c_int32(count), *view(e), ctypes.c_void_p(err.data_ptr()),
                                 ctypes.c_void_p(nrm.data_ptr()))
     return (err, nrm, e) if want_residual else (err, nrm)
+
+
+def lowrank_residual_batched(a: torch.Tensor, left: torch.Tensor, right: torch.Tensor, mid: Optional[torch.Tensor] = None, s: Optional[torch.Tensor] = None,
+                             ranks: Optional[torch.Tensor] = None, want_residual: bool = False):
+    """Residual norms of every block of a batch against its low-rank factors in one stream-ordered call (rc_lowrank_residual_batched_*):
+    the reference's rel_diff_fro(x.to_mat(), a) per block (src/lib.rs) without the rebuilt blocks, for the outputs of every batched compressor.
+
+    a: [count, m, n], left: [count, m, K], right: [count, K, n], mid: [count, K, K] or None, s: [count, p >= K] or None, ranks: [count] int64
+    or None (every rank is K); float64 or float32 device tensors of one dtype, any strides (a stride-0 batch dimension shares one operand);
+    m <= 65536, n <= 512, K <= 128.  With r = ranks[i] clamped to [0, K] and Ah_i = left[i][:, :r] mid[i][:r, :r] diag(s[i][:r]) right[i][:r]
+    (absent factors omitted; nothing at an index >= r is read), returns err [count] = ||a_i - Ah_i||_F and nrm [count] = ||a_i||_F, and with
+    want_residual also e [count, m, n] = a_i - Ah_i.  Complex data (see lowrank_residual_batched_complex) and mismatched dtypes raise TypeError."""
+    return _lowrank_residual_batched("lowrank_residual_batched", False, a, left, right, mid, s, ranks, want_residual)
+
+
+def lowrank_residual_batched_complex(a: torch.Tensor, left: torch.Tensor, right: torch.Tensor, mid: Optional[torch.Tensor] = None,
+                                     s: Optional[torch.Tensor] = None, ranks: Optional[torch.Tensor] = None, want_residual: bool = False):
+    """lowrank_residual_batched for complex blocks and factors (rc_lowrank_residual_batched_c64 / _c32): a, left, right and mid complex128 or
+    complex64 device tensors of one dtype (lazily conjugated views are materialised), s of the matching real dtype (float64 / float32);
+    real data, mismatched dtypes and a complex s raise TypeError.  Nothing is conjugated: Ah_i = left[i][:, :r] mid[i][:r, :r]
+    diag(s[i][:r]) right[i][:r], so vt is the V^H svd_rank_batched_complex returns.  err and nrm come back in the real dtype, e complex."""
+    return _lowrank_residual_batched("lowrank_residual_batched_complex", True, a, left, right, mid, s, ranks, want_residual)
 
 
 def column_id_residual_batched(a: torch.Tensor, c: torch.Tensor, z: torch.Tensor, ranks: Optional[torch.Tensor], want_residual: bool = False):
@@ -404,6 +427,23 @@ def svd_residual_batched(a: torch.Tensor, u: torch.Tensor, s: torch.Tensor, vt: 
     """||a_i - U diag(s) Vt||_F at the block's rank and ||a_i||_F per block for the outputs of svd_rank_batched and of the recompressions; s is
     the [count, p] tensor those calls return, read with row stride p."""
     return lowrank_residual_batched(a, u, vt, s=s, ranks=ranks, want_residual=want_residual)
+
+
+def column_id_residual_batched_complex(a: torch.Tensor, c: torch.Tensor, z: torch.Tensor, ranks: Optional[torch.Tensor], want_residual: bool = False):
+    """column_id_residual_batched for the complex outputs of column_id_rank_batched."""
+    return lowrank_residual_batched_complex(a, c, z, ranks=ranks, want_residual=want_residual)
+
+
+def two_sided_id_residual_batched_complex(a: torch.Tensor, c: torch.Tensor, x: torch.Tensor, r: torch.Tensor, ranks: Optional[torch.Tensor],
+                                          want_residual: bool = False):
+    """two_sided_id_residual_batched for the complex outputs of two_sided_id_rank_batched."""
+    return lowrank_residual_batched_complex(a, c, r, mid=x, ranks=ranks, want_residual=want_residual)
+
+
+def svd_residual_batched_complex(a: torch.Tensor, u: torch.Tensor, s: torch.Tensor, vt: torch.Tensor, ranks: Optional[torch.Tensor],
+                                 want_residual: bool = False):
+    """svd_residual_batched for the outputs of svd_rank_batched_complex: u and vt (= V^H) complex, s the real [count, p] tensor it returns."""
+    return lowrank_residual_batched_complex(a, u, vt, s=s, ranks=ranks, want_residual=want_residual)
 
 
 def sketch_column_id_rank_batched(a: torch.Tensor, k: int, tol: float = 0.0, omega: Optional[torch.Tensor] = None, oversampling: int = 8, seed: int = 0,

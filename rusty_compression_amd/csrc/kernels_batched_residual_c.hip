@@ -1,0 +1,342 @@
+// Residual norms of a batch of complex low-rank factorizations against their blocks in one rank-aware launch
+// (rc_lowrank_residual_batched_c64 / _c32): the complex twin of kernels_batched_residual.hip on interleaved (re, im) data.
+//
+// Per block i, with r = ranks[i] clamped to [0, K] (K when there are no ranks) and Ah = left_i[:, :r] mid_i[:r, :r] diag(s_i[:r])
+// right_i[:r, :] (absent factors omitted, s real, nothing conjugated: vt is already V^H and the two-sided c already Z2^H, as in
+// rc_lowrank_apply_batched_c*): err[i] = ||a_i - Ah||_F and nrm[i] = ||a_i||_F in the real type R and, when asked for, the complex
+// e_i = a_i - Ah.  Nothing at an index >= r is read.
+//
+// MI355X mapping: that of the real kernel.  The persistent grid of 256-thread workgroups (bid_grid), one workgroup per block from
+// start to finish, nothing crossing workgroups, no atomics.  Two phases per block:
+//   1. W (r x n), produced only when mid or s is present (without either the MFMA's B operand is read straight from right in phase 2,
+//      one complex load per lane feeding both components, zero at an inner index >= r or a column >= n: plan=W:right, no image).
+//      W0 = diag(s[:r]) right[:r, :], one rounding per component; with mid, W1 = mid[:r, :r] W0, one thread per element, plain FMAs
+//      over the ascending inner index p from zero, the four real products of a term in the order
+//          re = fma(mid_re, w_re, re); re = fma(-mid_im, w_im, re); im = fma(mid_re, w_im, im); im = fma(mid_im, w_re, im).
+//      The images hold interleaved complex elements with the column index fastest, pitch np + 16 elements (np = 64 ceil(n / 64)):
+//      the B-operand read (16 consecutive elements per inner index, 4 inner indices) is free of bank conflicts both as 8-byte
+//      elements (32-lane groups, rows 16 modulo 32 elements apart) and as 16-byte elements (the 16-lane groups of ds_read_b128, rows
+//      0 modulo 16 elements apart).  They live in LDS when they fit BID_MAX_LDS next to the chunk images, else in the workgroup's slot
+//      of the grid-bounded workspace; the plan only moves base pointers, so it cannot change a bit.
+//   2. Row chunks of BRC_ROWS = 32 rows against the resident W; left's chunk (32 x 4 ceil(r / 4), zeros past m and past r) is staged
+//      once per chunk and a's chunk streams through LDS in tiles of BRC_COLS = 64 columns, both with the lanes along the operand's
+//      smaller stride and that index fastest in the image.  Per tile each wave owns a 16-column strip and both 16-row tiles.  The
+//      rebuild runs on v_mfma_f64_16x16x4_f64 / v_mfma_f32_16x16x4_f32 (Acc<R> of rc_gemm.hpp) with the real and imaginary parts as
+//      separate real operands: per output element each of Re Ah and Im Ah is one accumulator chain from zero over the ascending
+//      inner index, four terms per instruction, and within a step
+//          Re takes MFMA(L_re, W_re) then MFMA(-L_im, W_im);   Im takes MFMA(L_re, W_im) then MFMA(L_im, W_re)
+//      (the negation is a sign flip in a register: exact).  Each component of e = a - acc is one rounding.  Conjugating every
+//      operand negates the second product of Re's pair twice and every product of Im's chain once, and both MFMAs round a sum and
+//      its negation to opposite values (measured on MI355X for f32 and f64), so err and nrm keep their bits and e comes out
+//      conjugated, except that an Im e cancelled to zero exactly is +0 either way (x - x = +0 in IEEE arithmetic); operands with
+//      +0 imaginary parts add only zeros to Re's chain, which then carries the real kernel's values; a column of right that is a unit vector leaves one non-zero product in the chain and e is exactly zero there.
+//      The 32 accumulator registers of c64 (two tiles x (re, im) x 4 x f64) leave the kernel far from the register limit.
+// Squares of Re e, Im e (and of Re a, Im a) are accumulated in f64 by each thread over its 8 elements of every tile, re before im,
+// tiles in (row chunk, column tile) order; the 64 lanes are then summed by a butterfly and the four waves as (w0 + w1) + (w2 + w3).
+// The longest chain of additions is L_c(m, n) = 16 ceil(m / 32) ceil(n / 64) + 8.  Every order above is a function of (m, n, r)
+// alone, which is what the bit-independence clause of the contract rests on.
+#include <algorithm>
+
+#include "rc_common.hpp"
+#include "rc_device.hpp"
+#include "rc_gemm.hpp"
+
+namespace rc {
+
+namespace {
+
+constexpr int BRC_THREADS = 256;
+constexpr int BRC_ROWS = 32;  // rows of a and of left per chunk: two 16-row MFMA tiles
+constexpr int BRC_COLS = 64;  // columns of a per tile: one 16-column strip per wave
+constexpr int BRC_PER = BRC_ROWS * BRC_COLS / BRC_THREADS;  // 8 complex elements of a tile per thread, staged and computed
+constexpr int BRC_PAR = BRC_ROWS + 2;  // pitch of a's image with the row index fastest (2 modulo 16: no conflict for 16-byte elements)
+
+// an element in the caller's memory (aligned as R) and in the images (aligned as one 8- or 16-byte load)
+template <typename R>
+struct gcx {
+    R re, im;
+};
+template <typename R>
+struct alignas(2 * sizeof(R)) cx {
+    R re, im;
+};
+
+// pitch of left's image with the row index fastest: 16 modulo 32 elements (8-byte elements), 0 modulo 16 (16-byte elements)
+template <typename R>
+__host__ __device__ constexpr int brc_plr() { return sizeof(R) == 8 ? BRC_ROWS : BRC_ROWS + 16; }
+// pitch of a's image with the column index fastest: the accumulator-layout read has lanes 16 columns x 4 rows, the rows 1 (f64) or 4 (f32) apart
+template <typename R>
+__host__ __device__ constexpr int brc_pac() { return sizeof(R) == 8 ? 80 : 68; }
+template <typename R>
+__host__ __device__ constexpr int brc_a_elems() { return BRC_ROWS * brc_pac<R>() > BRC_COLS * BRC_PAR ? BRC_ROWS * brc_pac<R>() : BRC_COLS * BRC_PAR; }
+__host__ __device__ constexpr int brc_k4(int k) { return (k + 3) & ~3; }
+// pitch of left's image with the inner index fastest (2 modulo 32: the A-operand read, 16 rows x 4 inner indices, is free of conflicts)
+__host__ __device__ constexpr int brc_plk(int k) { return ((k + 31) & ~31) + 2; }
+template <typename R>
+__host__ __device__ constexpr int brc_l_elems(int k) {
+    return BRC_ROWS * brc_plk(k) > brc_k4(k) * brc_plr<R>() ? BRC_ROWS * brc_plk(k) : brc_k4(k) * brc_plr<R>();
+}
+__host__ __device__ constexpr int brc_np(int n) { return (n + BRC_COLS - 1) & ~(BRC_COLS - 1); }
+__host__ __device__ constexpr int brc_pw(int n) { return brc_np(n) + 16; }  // pitch of W's image
+__host__ __device__ constexpr size_t brc_w_elems(int k, int n, bool has_mid) { return (size_t)(has_mid ? 2 : 1) * brc_k4(k) * brc_pw(n); }
+
+// dynamic LDS: red[8] (f64) | [W0 [W1, with mid]: K4 x pw(n), LDS plan only] a's tile image | left's chunk image (complex elements)
+template <typename R>
+size_t brc_lds_bytes(int k, int n, bool has_mid, bool w_lds) {
+    return 64 + ((w_lds ? brc_w_elems(k, n, has_mid) : 0) + (size_t)brc_a_elems<R>() + (size_t)brc_l_elems<R>(k)) * sizeof(cx<R>);
+}
+
+// strided view of block 0 of one operand (in complex elements)
+template <typename R>
+struct BrcView {
+    gcx<R> *p;
+    int64_t rs, cs;
+};
+
+template <typename R>
+struct BrcArgs {
+    BrcView<R> a, left, mid, right, e;  // mid.p == nullptr: none; e.p == nullptr: the residual is not written
+    int64_t abs, lbs, mbs, rbs, ebs, s_stride;
+    const R *s;
+    const int64_t *ranks;
+    R *err, *nrm;
+    cx<R> *ws;
+    int m, n, k, count;
+    bool w_lds;   // W's images in LDS (else in the workgroup's workspace slot)
+    bool direct;  // neither mid nor s: W is right itself, read in place
+};
+
+template <typename R>
+__global__ __launch_bounds__(BRC_THREADS) void k_batched_residual_c(BrcArgs<R> g) {
+    using C = cx<R>;
+    using G = gcx<R>;
+    typedef typename Acc<R>::type acc_t;
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const int m = g.m, n = g.n, K = g.k;
+    const int np = brc_np(n), pw = brc_pw(n);
+    const bool has_mid = g.mid.p != nullptr;
+    const size_t wel = (size_t)brc_k4(K) * pw;
+    double *red = reinterpret_cast<double *>(smem_raw);
+    C *lds = reinterpret_cast<C *>(smem_raw + 64);
+    C *W0 = g.w_lds ? lds : g.direct ? lds : g.ws + (size_t)blockIdx.x * brc_w_elems(K, n, has_mid);  // unused when direct
+    C *W1 = W0 + wel;
+    C *As = lds + (g.w_lds ? brc_w_elems(K, n, has_mid) : 0);
+    C *Ls = As + brc_a_elems<R>();
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r16 = lane & 15, k4 = lane >> 4;
+    // the lanes of every staging loop run along the operand's smaller stride, and that index is the fastest one of the LDS image
+    const bool a_rows = g.a.rs <= g.a.cs, l_rows = g.left.rs <= g.left.cs, r_rows = g.right.rs <= g.right.cs, e_rows = g.e.rs <= g.e.cs;
+    const int as_sr = a_rows ? 1 : brc_pac<R>(), as_sc = a_rows ? BRC_PAR : 1;    // As[row * as_sr + col * as_sc]
+    const int ls_sr = l_rows ? 1 : brc_plk(K), ls_sk = l_rows ? brc_plr<R>() : 1;  // Ls[row * ls_sr + k * ls_sk]
+    // this thread's BRC_PER elements of a tile when staging a (row0 + drow * q, col0 + dcol * q) and when storing e
+    const int a_row0 = a_rows ? (tid & (BRC_ROWS - 1)) : (tid / BRC_COLS), a_col0 = a_rows ? (tid / BRC_ROWS) : (tid & (BRC_COLS - 1));
+    const int a_drow = a_rows ? 0 : BRC_THREADS / BRC_COLS, a_dcol = a_rows ? BRC_THREADS / BRC_ROWS : 0;
+    const int e_row0 = e_rows ? (tid & (BRC_ROWS - 1)) : (tid / BRC_COLS), e_col0 = e_rows ? (tid / BRC_ROWS) : (tid & (BRC_COLS - 1));
+    const int e_drow = e_rows ? 0 : BRC_THREADS / BRC_COLS, e_dcol = e_rows ? BRC_THREADS / BRC_ROWS : 0;
+    // and in the accumulator layout: rows i * 16 + Acc<R>::row(lane, reg) of column wv * 16 + r16
+    const C *ls_ld = Ls + r16 * ls_sr + k4 * ls_sk;
+    C *as_acc = As + (wv * 16 + r16) * as_sc;
+    const C czero{(R)0, (R)0};
+
+    for (int b = blockIdx.x; b < g.count; b += gridDim.x) {
+        int r = K;
+        if (g.ranks) {
+            const int64_t rv = g.ranks[b];
+            r = rv < 0 ? 0 : rv > K ? K : (int)rv;
+        }
+        r = __builtin_amdgcn_readfirstlane(r);  // one value per block, uniform by construction: the loop bounds stay in scalar registers
+        const int r4 = brc_k4(r);
+        const G *__restrict__ A = g.a.p + (int64_t)b * g.abs;
+        const G *__restrict__ Lf = g.left.p + (int64_t)b * g.lbs;
+        const G *__restrict__ Rt = g.right.p + (int64_t)b * g.rbs;
+        const R *sb = g.s ? g.s + (int64_t)b * g.s_stride : nullptr;
+        G *E = g.e.p ? g.e.p + (int64_t)b * g.ebs : nullptr;
+
+        // ---- phase 1: W0 = diag(s[:r]) right[:r, :], zero rows r .. r4 - 1 and zero columns n .. np - 1 ----------------------------------
+        const int wtot = g.direct ? 0 : r4 * np;  // without mid and s there is nothing to produce
+        for (int idx = tid; idx < wtot; idx += BRC_THREADS) {
+            int k, j;
+            if (r_rows) { k = idx % r4; j = idx / r4; } else { j = idx % np; k = idx / np; }
+            C v = czero;
+            if (k < r && j < n) {
+                const G x = Rt[(int64_t)k * g.right.rs + (int64_t)j * g.right.cs];
+                v.re = x.re;
+                v.im = x.im;
+                if (sb) {
+                    const R sk = sb[k];
+                    v.re = sk * v.re;
+                    v.im = sk * v.im;
+                }
+            }
+            W0[(size_t)k * pw + j] = v;
+        }
+        if (!g.direct) __syncthreads();  // uniform over the grid
+        const C *Wp = W0;
+        if (has_mid) {  // W1 = mid[:r, :r] W0: the 64 lanes of a wave share the row l (np is a multiple of 64) and read one element of mid
+            const G *__restrict__ Md = g.mid.p + (int64_t)b * g.mbs;
+            for (int idx = tid; idx < wtot; idx += BRC_THREADS) {
+                const int j = idx % np, l = idx / np;
+                C acc = czero;
+                if (l < r && j < n) {
+                    const G *mr = Md + (int64_t)l * g.mid.rs;
+                    for (int p = 0; p < r; ++p) {
+                        const G mv = mr[(int64_t)p * g.mid.cs];
+                        const C w = W0[(size_t)p * pw + j];
+                        acc.re = fma(mv.re, w.re, acc.re);
+                        acc.re = fma(-mv.im, w.im, acc.re);
+                        acc.im = fma(mv.re, w.im, acc.im);
+                        acc.im = fma(mv.im, w.re, acc.im);
+                    }
+                }
+                W1[(size_t)l * pw + j] = acc;
+            }
+            __syncthreads();
+            Wp = W1;
+        }
+        const C *w_ld = Wp + (size_t)k4 * pw + wv * 16 + r16;
+
+        // ---- phase 2: row chunks of a and left against W ------------------------------------------------------------------------------
+        double se = 0.0, sa = 0.0;
+        for (int m0 = 0; m0 < m; m0 += BRC_ROWS) {
+            const int ltot = BRC_ROWS * r4;
+            for (int idx = tid; idx < ltot; idx += BRC_THREADS) {
+                int row, k;
+                if (l_rows) { row = idx & (BRC_ROWS - 1); k = idx / BRC_ROWS; } else { k = idx % r4; row = idx / r4; }
+                C v = czero;
+                if (m0 + row < m && k < r) {
+                    const G x = Lf[(int64_t)(m0 + row) * g.left.rs + (int64_t)k * g.left.cs];
+                    v.re = x.re;
+                    v.im = x.im;
+                }
+                Ls[row * ls_sr + k * ls_sk] = v;
+            }
+            for (int c0 = 0; c0 < n; c0 += BRC_COLS) {
+                G av[BRC_PER];
+#pragma unroll
+                for (int q = 0; q < BRC_PER; ++q) {
+                    const int row = a_row0 + a_drow * q, col = a_col0 + a_dcol * q;
+                    const bool ok = m0 + row < m && c0 + col < n;
+                    av[q] = ok ? A[(int64_t)(m0 + row) * g.a.rs + (int64_t)(c0 + col) * g.a.cs] : G{(R)0, (R)0};
+                }
+#pragma unroll
+                for (int q = 0; q < BRC_PER; ++q) As[(a_row0 + a_drow * q) * as_sr + (a_col0 + a_dcol * q) * as_sc] = C{av[q].re, av[q].im};
+                __syncthreads();
+                acc_t are[2], aim[2];
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    are[i] = acc_t{0, 0, 0, 0};
+                    aim[i] = acc_t{0, 0, 0, 0};
+                }
+                const int bcol = c0 + wv * 16 + r16;
+                for (int ks = 0; ks < r4; ks += 4) {
+                    C bf = czero;
+                    if (g.direct) {  // uniform over the grid: right in place, zero past the rank and past n
+                        if (ks + k4 < r && bcol < n) {
+                            const G x = Rt[(int64_t)(ks + k4) * g.right.rs + (int64_t)bcol * g.right.cs];
+                            bf.re = x.re;
+                            bf.im = x.im;
+                        }
+                    } else {
+                        bf = w_ld[(size_t)ks * pw + c0];
+                    }
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) {
+                        const C lf = ls_ld[i * 16 * ls_sr + ks * ls_sk];
+                        are[i] = Acc<R>::mfma(lf.re, bf.re, are[i]);
+                        are[i] = Acc<R>::mfma(-lf.im, bf.im, are[i]);
+                        aim[i] = Acc<R>::mfma(lf.re, bf.im, aim[i]);
+                        aim[i] = Acc<R>::mfma(lf.im, bf.re, aim[i]);
+                    }
+                }
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int reg = 0; reg < 4; ++reg) {
+                        C *pa = as_acc + (i * 16 + Acc<R>::row(lane, reg)) * as_sr;
+                        const C x = *pa;
+                        const R er = x.re - are[i][reg], ei = x.im - aim[i][reg];
+                        se = fma((double)er, (double)er, se);
+                        se = fma((double)ei, (double)ei, se);
+                        sa = fma((double)x.re, (double)x.re, sa);
+                        sa = fma((double)x.im, (double)x.im, sa);
+                        if (E) *pa = C{er, ei};
+                    }
+                if (E) {  // uniform over the grid
+                    __syncthreads();
+#pragma unroll
+                    for (int q = 0; q < BRC_PER; ++q) {
+                        const int row = e_row0 + e_drow * q, col = e_col0 + e_dcol * q;
+                        if (m0 + row < m && c0 + col < n) {
+                            const C v = As[row * as_sr + col * as_sc];
+                            E[(int64_t)(m0 + row) * g.e.rs + (int64_t)(c0 + col) * g.e.cs] = G{v.re, v.im};
+                        }
+                    }
+                }
+                __syncthreads();  // a's image is rewritten by the next tile, left's by the next chunk
+            }
+        }
+        // ---- the two sums: 64 lanes by a butterfly, then the four waves ------------------------------------------------------------------
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            se += __shfl_xor(se, off, 64);
+            sa += __shfl_xor(sa, off, 64);
+        }
+        if (lane == 0) {
+            red[wv] = se;
+            red[4 + wv] = sa;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            g.err[b] = (R)sqrt((red[0] + red[1]) + (red[2] + red[3]));
+            if (g.nrm) g.nrm[b] = (R)sqrt((red[4] + red[5]) + (red[6] + red[7]));
+        }
+        __syncthreads();  // red and W's images are rewritten by the next block
+    }
+}
+
+template <typename R>
+BrcView<R> brc_view(const rc_matrix &v) { return BrcView<R>{static_cast<gcx<R> *>(v.data), v.row_stride, v.col_stride}; }
+
+}  // namespace
+
+// W's images in LDS when they fit next to the chunk images, else in the workgroup's slot of the grid-bounded workspace: the plan only
+// moves base pointers, so it cannot change a block's bits; without mid and s there is no image (plan=W:right).  One kernel per scalar
+// type.  attr_set, as in the sibling launchers: a racing first call sets the same attribute twice, which is harmless.
+template <typename R>
+void batched_lowrank_residual_c(rc_context *c, const rc_matrix &a, int64_t abs, const rc_matrix &left, int64_t lbs, const rc_matrix &mid, int64_t mbs, const R *s,
+                                int64_t s_stride, const rc_matrix &right, int64_t rbs, const int64_t *ranks, int32_t count, const rc_matrix &e, int64_t ebs,
+                                R *err, R *nrm) {
+    const int m = (int)a.rows, n = (int)a.cols, K = (int)left.cols;
+    if (count <= 0) return;
+    const bool has_mid = mid.data != nullptr;
+    const bool direct = !has_mid && !s;  // W is right itself: no image
+    const bool w_lds = !direct && brc_lds_bytes<R>(K, n, has_mid, true) <= BID_MAX_LDS;
+    const size_t lds = brc_lds_bytes<R>(K, n, has_mid, w_lds);
+    RC_REQUIRE(lds <= BID_MAX_LDS, RC_RUNTIME_ERROR, "lowrank_residual_batched: %zu bytes of LDS", lds);
+    const void *kern = reinterpret_cast<const void *>(k_batched_residual_c<R>);
+    static bool attr_set[64] = {};
+    if (!attr_set[c->device & 63]) {
+        RC_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BID_MAX_LDS));
+        attr_set[c->device & 63] = true;
+    }
+    const size_t per = w_lds || direct ? 0 : brc_w_elems(K, n, has_mid) * sizeof(cx<R>);
+    int64_t slots = 0;
+    const int64_t grid = bid_grid(c, kern, lds, per, count, &slots);
+    ProfScope ps(c, "op:batched_residual<complex> %dx%d k=%d count=%d grid=%lld slots=%lld plan=W:%s,rows=%d,cols=%d%s%s%s%s", m, n, K, (int)count,
+                 (long long)grid, (long long)slots, direct ? "right" : w_lds ? "lds" : "ws", BRC_ROWS, BRC_COLS, has_mid ? ",mid" : "", s ? ",s" : "",
+                 e.data ? ",e" : "", nrm ? ",nrm" : "");
+    BrcArgs<R> g;
+    g.a = brc_view<R>(a); g.left = brc_view<R>(left); g.mid = brc_view<R>(mid); g.right = brc_view<R>(right); g.e = brc_view<R>(e);
+    g.abs = abs; g.lbs = lbs; g.mbs = mbs; g.rbs = rbs; g.ebs = ebs; g.s_stride = s_stride;
+    g.s = s; g.ranks = ranks; g.err = err; g.nrm = nrm;
+    g.ws = per ? c->alloc<cx<R>>((size_t)grid * per / sizeof(cx<R>)) : nullptr;
+    g.m = m; g.n = n; g.k = K; g.count = (int)count; g.w_lds = w_lds; g.direct = direct;
+    hipLaunchKernelGGL(k_batched_residual_c<R>, dim3((unsigned)grid), dim3(BRC_THREADS), lds, c->stream, g);
+    RC_HIP(hipGetLastError());
+}
+
+template void batched_lowrank_residual_c<double>(rc_context *, const rc_matrix &, int64_t, const rc_matrix &, int64_t, const rc_matrix &, int64_t, const double *,
+                                                 int64_t, const rc_matrix &, int64_t, const int64_t *, int32_t, const rc_matrix &, int64_t, double *, double *);
+template void batched_lowrank_residual_c<float>(rc_context *, const rc_matrix &, int64_t, const rc_matrix &, int64_t, const rc_matrix &, int64_t, const float *,
+                                                int64_t, const rc_matrix &, int64_t, const int64_t *, int32_t, const rc_matrix &, int64_t, float *, float *);
+
+}  // namespace rc

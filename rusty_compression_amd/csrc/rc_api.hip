@@ -1149,6 +1149,29 @@ void check_lowrank_apply_batched(Mat<T> left, Mat<T> mid, Mat<T> right, int32_t 
     if (count > 0) RC_REQUIRE(left.p && right.p && y.p, RC_INVALID_ARGUMENT, "%s: null pointer", who);
 }
 
+// rc_lowrank_residual_batched_*: the shapes of a (m x n) against the factor chain left (m x K) [mid (K x K)] right (K x n), the sketched ID's domain
+// for m, n, K, and e's shape and batch stride when it is asked for; mid and e take part only when their data pointer is set
+template <typename T>
+void check_lowrank_residual_batched(Mat<T> a, Mat<T> left, Mat<T> mid, Mat<T> right, int32_t count, Mat<T> e, int64_t ebs, const T *err) {
+    const char *who = "lowrank_residual_batched";
+    const int64_t m = a.rows, n = a.cols, K = left.cols;
+    RC_REQUIRE(count >= 0, RC_INVALID_ARGUMENT, "%s: count = %d < 0", who, (int)count);
+    RC_REQUIRE(m >= 1 && m <= 65536 && n >= 1 && n <= 512 && K >= 1 && K <= 128, RC_INVALID_ARGUMENT,
+               "%s: needs 1 <= m <= 65536, 1 <= n <= 512 and 1 <= K <= 128 (got a %lld x %lld, left %lld x %lld)", who, (long long)m, (long long)n,
+               (long long)left.rows, (long long)K);
+    RC_REQUIRE(left.rows == m && right.rows == K && right.cols == n, RC_INVALID_ARGUMENT,
+               "%s: a is %lld x %lld but left is %lld x %lld and right %lld x %lld", who, (long long)m, (long long)n, (long long)left.rows, (long long)K,
+               (long long)right.rows, (long long)right.cols);
+    RC_REQUIRE(!mid.p || (mid.rows == K && mid.cols == K), RC_INVALID_ARGUMENT, "%s: mid must be %lld x %lld (got %lld x %lld)", who, (long long)K,
+               (long long)K, (long long)mid.rows, (long long)mid.cols);
+    if (e.p) {
+        RC_REQUIRE(e.rows == m && e.cols == n, RC_INVALID_ARGUMENT, "%s: e must be %lld x %lld (got %lld x %lld)", who, (long long)m, (long long)n,
+                   (long long)e.rows, (long long)e.cols);
+        check_batch_stride(who, "e", ebs, e, count);
+    }
+    if (count > 0) RC_REQUIRE(a.p && left.p && right.p && err, RC_INVALID_ARGUMENT, "%s: null pointer", who);
+}
+
 template int64_t check_column_id_rank_batched<double>(Mat<double>, int32_t, int64_t, double, Mat<double>, int64_t, Mat<double>, int64_t, const int64_t *,
                                                       const int64_t *);
 template int64_t check_column_id_rank_batched<float>(Mat<float>, int32_t, int64_t, double, Mat<float>, int64_t, Mat<float>, int64_t, const int64_t *,
@@ -1162,6 +1185,8 @@ template int64_t check_svd_rank_batched<double>(Mat<double>, int32_t, int64_t, d
 template int64_t check_svd_rank_batched<float>(Mat<float>, int32_t, int64_t, double, Mat<float>, int64_t, const float *, Mat<float>, int64_t, const int64_t *);
 template void check_lowrank_apply_batched<double>(Mat<double>, Mat<double>, Mat<double>, int32_t, Mat<double>, Mat<double>, int64_t);
 template void check_lowrank_apply_batched<float>(Mat<float>, Mat<float>, Mat<float>, int32_t, Mat<float>, Mat<float>, int64_t);
+template void check_lowrank_residual_batched<double>(Mat<double>, Mat<double>, Mat<double>, Mat<double>, int32_t, Mat<double>, int64_t, const double *);
+template void check_lowrank_residual_batched<float>(Mat<float>, Mat<float>, Mat<float>, Mat<float>, int32_t, Mat<float>, int64_t, const float *);
 
 }  // namespace rc
 
@@ -1264,23 +1289,7 @@ void sketch_column_id_rank_batched(rc_context *c, Mat<T> a, int64_t abs, Mat<T> 
 template <typename T>
 void lowrank_residual_batched(rc_context *c, Mat<T> a, int64_t abs, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride,
                               Mat<T> right, int64_t rbs, const int64_t *ranks, int32_t count, Mat<T> e, int64_t ebs, T *err, T *nrm) {
-    const char *who = "lowrank_residual_batched";
-    const int64_t m = a.rows, n = a.cols, K = left.cols;
-    RC_REQUIRE(count >= 0, RC_INVALID_ARGUMENT, "%s: count = %d < 0", who, (int)count);
-    RC_REQUIRE(m >= 1 && m <= 65536 && n >= 1 && n <= 512 && K >= 1 && K <= 128, RC_INVALID_ARGUMENT,
-               "%s: needs 1 <= m <= 65536, 1 <= n <= 512 and 1 <= K <= 128 (got a %lld x %lld, left %lld x %lld)", who, (long long)m, (long long)n,
-               (long long)left.rows, (long long)K);
-    RC_REQUIRE(left.rows == m && right.rows == K && right.cols == n, RC_INVALID_ARGUMENT,
-               "%s: a is %lld x %lld but left is %lld x %lld and right %lld x %lld", who, (long long)m, (long long)n, (long long)left.rows, (long long)K,
-               (long long)right.rows, (long long)right.cols);
-    RC_REQUIRE(!mid.p || (mid.rows == K && mid.cols == K), RC_INVALID_ARGUMENT, "%s: mid must be %lld x %lld (got %lld x %lld)", who, (long long)K,
-               (long long)K, (long long)mid.rows, (long long)mid.cols);
-    if (e.p) {
-        RC_REQUIRE(e.rows == m && e.cols == n, RC_INVALID_ARGUMENT, "%s: e must be %lld x %lld (got %lld x %lld)", who, (long long)m, (long long)n,
-                   (long long)e.rows, (long long)e.cols);
-        check_batch_stride(who, "e", ebs, e, count);
-    }
-    if (count > 0) RC_REQUIRE(a.p && left.p && right.p && err, RC_INVALID_ARGUMENT, "%s: null pointer", who);
+    check_lowrank_residual_batched(a, left, mid, right, count, e, ebs, err);
     if (count == 0) return;
     batched_lowrank_residual(c, a, abs, left, lbs, mid, mbs, s, s_stride, right, rbs, ranks, count, e, ebs, err, nrm);
 }

@@ -259,6 +259,13 @@ template <typename T> void batched_sketch_column_id(rc_context *c, Mat<T> a, int
 template <typename T> void batched_lowrank_residual(rc_context *c, Mat<T> a, int64_t abs, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s,
                                                     int64_t s_stride, Mat<T> right, int64_t rbs, const int64_t *ranks, int32_t count, Mat<T> e, int64_t ebs,
                                                     T *err, T *nrm);
+// the complex twin (kernels_batched_residual_c.hip), R = double (c64) or float (c32): interleaved-complex views, strides in complex elements, s, err
+// and nrm real
+template <typename R> void batched_lowrank_residual_c(rc_context *c, const rc_matrix &a, int64_t abs, const rc_matrix &left, int64_t lbs, const rc_matrix &mid,
+                                                      int64_t mbs, const R *s, int64_t s_stride, const rc_matrix &right, int64_t rbs, const int64_t *ranks,
+                                                      int32_t count, const rc_matrix &e, int64_t ebs, R *err, R *nrm);
+// the argument checks of rc_lowrank_residual_batched_* (rc_api.hip), shared by every scalar type like those above; the caller returns when count == 0
+template <typename T> void check_lowrank_residual_batched(Mat<T> a, Mat<T> left, Mat<T> mid, Mat<T> right, int32_t count, Mat<T> e, int64_t ebs, const T *err);
 // the batched kernels' dynamic-LDS cap and persistent grid (kernels_batched_id.hip): the resident workgroups of 256 threads on every
 // CU, fewer when the workspace (ws_per bytes per workgroup, 0 in the LDS variants) would pass 256 MiB unless that leaves less than
 // one workgroup per CU; never more than count.  *slots receives the grid before that last bound (slots= in the profile label)

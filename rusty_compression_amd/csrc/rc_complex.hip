@@ -1388,6 +1388,20 @@ extern "C" {
             batched_lowrank_apply_c<R>(ctx, left, left_batch_stride, mid, mid_batch_stride, s, s_stride, right, right_batch_stride, ranks, \
                                        count, b, b_batch_stride, y, y_batch_stride);                                                      \
         });                                                                                                                               \
+    }                                                                                                                                     \
+    /* residual norms of the factors of a batch against their blocks (kernels_batched_residual_c.hip): the real entry point's checks on */ \
+    /* views of the same shapes; s, err and nrm in the real type */                                                                       \
+    rc_status rc_lowrank_residual_batched_##SUF(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix left, int64_t left_batch_stride, \
+                                                rc_matrix mid, int64_t mid_batch_stride, const R *s, int64_t s_stride, rc_matrix right,   \
+                                                int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix e,             \
+                                                int64_t e_batch_stride, R *err, R *nrm) {                                                 \
+        return guarded_c(ctx, [&] {                                                                                                       \
+            check_lowrank_residual_batched<R>(shape_of<R>(a), shape_of<R>(left), shape_of<R>(mid), shape_of<R>(right), count, shape_of<R>(e), \
+                                              e_batch_stride, err);                                                                       \
+            if (count == 0) return;                                                                                                       \
+            batched_lowrank_residual_c<R>(ctx, a, a_batch_stride, left, left_batch_stride, mid, mid_batch_stride, s, s_stride, right,     \
+                                          right_batch_stride, ranks, count, e, e_batch_stride, err, nrm);                                 \
+        });                                                                                                                               \
     }
 
 RC_DEFINE_COMPLEX(c64, double, rc_complex64)
