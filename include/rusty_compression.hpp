@@ -13,6 +13,7 @@
 //   double err = rel_diff_fro(tid.to_mat(), a);
 #pragma once
 
+#include <algorithm>
 #include <cmath>
 #include <complex>
 #include <cstdint>
@@ -773,6 +774,103 @@ template <typename T>
 BatchedResidual<T> residual_batched(const BatchedSVD<T> &svd, const DeviceMatrix<T> &a, bool want_residual = false) {
     return lowrank_residual_batched<T>(a, svd.u, nullptr, &svd.s, svd.vt, &svd.ranks, (int32_t)svd.ranks.size(), want_residual);
 }
+// The block-sparse operator such a batch describes, applied in one launch (rc_block_operator_apply_*): MatMat / ConjMatMat
+// (src/types.rs:40-101) for a BLR / hierarchical matrix whose blocks the batched calls compressed.  Entry e places block block_ids[e]
+// (ids below count: the low-rank blocks left_i [mid_i] [diag(s_i)] right_i of the stacked factors, as in lowrank_apply_batched; ids from
+// count on: block id - count of the stacked dense m x n blocks) with its top-left corner at (rows[e], cols[e]) of the nrows x ncols
+// matrix.  The operands are borrowed and must outlive the operator; the two block-CSR patterns (by row for A x, by column for A^H x on
+// the swapped, transposed views with the conj flag) are built on the host and owned.  Distinct values of rows must tile [0, nrows) in
+// steps of m and distinct values of cols [0, ncols) in steps of n, so that every product writes every row of its result; within a group
+// the entries are summed in the order given.  mid and s together are rejected: (L M diag(s) R)^T is not the kernel's chain.
+template <typename T> struct BlockOperatorApi;
+template <> struct BlockOperatorApi<double> { static constexpr auto apply = rc_block_operator_apply_f64; static constexpr bool conj = false; };
+template <> struct BlockOperatorApi<float> { static constexpr auto apply = rc_block_operator_apply_f32; static constexpr bool conj = false; };
+template <> struct BlockOperatorApi<c64> { static constexpr auto apply = rc_block_operator_apply_c64; static constexpr bool conj = true; };
+template <> struct BlockOperatorApi<c32> { static constexpr auto apply = rc_block_operator_apply_c32; static constexpr bool conj = true; };
+template <typename T>
+class BlockOperator {
+  public:
+    using Real = typename Scalar<T>::real;
+    BlockOperator(const Context &ctx, int64_t nrows, int64_t ncols, const std::vector<int64_t> &rows, const std::vector<int64_t> &cols,
+                  const std::vector<int64_t> &block_ids, int32_t count, const DeviceMatrix<T> *left, const DeviceMatrix<T> *mid,
+                  const DeviceBuffer<Real> *s, const DeviceMatrix<T> *right, const DeviceIndex *ranks, int32_t dense_count = 0,
+                  const DeviceMatrix<T> *dense = nullptr)
+        : nrows_(nrows), ncols_(ncols), count_(count), dense_count_(dense ? dense_count : 0), left_(left), mid_(mid), right_(right), dense_(dense),
+          s_(s), ranks_(ranks) {
+        if (mid && s) throw AssertionFailed("BlockOperator: mid and s together do not transpose into the kernel's chain");
+        if (!(count > 0 && left && right) && !(dense && dense_count > 0)) throw AssertionFailed("BlockOperator: needs a low-rank or a dense batch");
+        if (rows.size() != cols.size() || rows.size() != block_ids.size()) throw AssertionFailed("BlockOperator: one row, column and id per entry");
+        if (count > 0 && left && right) { m_ = left->nrows() / count; k_ = left->ncols(); n_ = right->ncols(); }
+        else { m_ = dense->nrows() / dense_count; n_ = dense->ncols(); }
+        p_ = s && count > 0 ? (int64_t)(s->size() / (std::size_t)count) : 0;
+        by_row_ = Pattern(ctx, rows, cols, block_ids, m_, nrows);
+        by_col_ = Pattern(ctx, cols, rows, block_ids, n_, ncols);
+    }
+    int64_t nrows() const { return nrows_; }
+    int64_t ncols() const { return ncols_; }
+    void matmat(const Context &ctx, rc_matrix x, rc_matrix y) const { call(ctx, by_row_, false, x, y); }
+    void conj_matmat(const Context &ctx, rc_matrix x, rc_matrix y) const { call(ctx, by_col_, true, x, y); }
+    DeviceMatrix<T> apply(const DeviceMatrix<T> &x) const {
+        DeviceMatrix<T> y(x.ctx(), nrows_, x.ncols());
+        matmat(x.ctx(), x.view(), y.view());
+        return y;
+    }
+    DeviceMatrix<T> conj_apply(const DeviceMatrix<T> &x) const {
+        DeviceMatrix<T> y(x.ctx(), ncols_, x.ncols());
+        conj_matmat(x.ctx(), x.view(), y.view());
+        return y;
+    }
+
+  private:
+    struct Pattern {  // block-CSR on the device: group_ptr, group_row, entry_block, entry_col
+        DeviceIndex ptr, row, block, col;
+        int32_t groups = 0;
+        Pattern() = default;
+        Pattern(const Context &ctx, const std::vector<int64_t> &first, const std::vector<int64_t> &other, const std::vector<int64_t> &ids, int64_t extent,
+                int64_t total) {
+            std::vector<int64_t> heads(first);
+            std::sort(heads.begin(), heads.end());
+            heads.erase(std::unique(heads.begin(), heads.end()), heads.end());
+            bool tiles = !heads.empty() && heads.front() == 0 && heads.back() + extent == total;
+            for (std::size_t g = 1; g < heads.size(); ++g) tiles = tiles && heads[g] - heads[g - 1] == extent;
+            if (!tiles) throw AssertionFailed("BlockOperator: the blocks' first rows (columns) must tile the matrix in steps of the block shape");
+            std::vector<int64_t> hptr(heads.size() + 1, 0), hblock(ids.size()), hcol(ids.size());
+            for (int64_t f : first) ++hptr[(std::size_t)(std::lower_bound(heads.begin(), heads.end(), f) - heads.begin()) + 1];
+            for (std::size_t g = 0; g < heads.size(); ++g) hptr[g + 1] += hptr[g];
+            std::vector<int64_t> next(hptr.begin(), hptr.end() - 1);
+            for (std::size_t e = 0; e < first.size(); ++e) {  // input order inside a group
+                const std::size_t at = (std::size_t)next[(std::size_t)(std::lower_bound(heads.begin(), heads.end(), first[e]) - heads.begin())]++;
+                hblock[at] = ids[e];
+                hcol[at] = other[e];
+            }
+            groups = (int32_t)heads.size();
+            ptr = DeviceIndex(ctx, hptr.size()); ptr.from_host(hptr.data());
+            row = DeviceIndex(ctx, heads.size()); row.from_host(heads.data());
+            block = DeviceIndex(ctx, hblock.size() + 1); block.from_host(pad(hblock).data());
+            col = DeviceIndex(ctx, hcol.size() + 1); col.from_host(pad(hcol).data());
+        }
+        static std::vector<int64_t> pad(std::vector<int64_t> v) { v.push_back(0); return v; }  // never a null pointer, also without entries
+    };
+    static rc_matrix block_view(const DeviceMatrix<T> *a, int64_t r, int64_t c, bool transposed) {
+        if (!a) return rc_matrix{nullptr, 0, 0, 0, 0};
+        return transposed ? rc_matrix{a->view().data, c, r, 1, c} : rc_matrix{a->view().data, r, c, c, 1};
+    }
+    void call(const Context &ctx, const Pattern &pat, bool adjoint, rc_matrix x, rc_matrix y) const {
+        const DeviceMatrix<T> *l = adjoint ? right_ : left_, *r = adjoint ? left_ : right_;
+        const int64_t lr = adjoint ? k_ : m_, lc = adjoint ? n_ : k_, rr = adjoint ? m_ : k_, rcols = adjoint ? k_ : n_;  // stored shapes
+        ctx.check(BlockOperatorApi<T>::apply(ctx.raw(), block_view(l, lr, lc, adjoint), lr * lc, block_view(mid_, k_, k_, adjoint), k_ * k_,
+                                             s_ ? s_->data() : nullptr, p_, block_view(r, rr, rcols, adjoint), rr * rcols,
+                                             ranks_ ? ranks_->data() : nullptr, left_ ? count_ : 0, block_view(dense_, m_, n_, adjoint), m_ * n_,
+                                             dense_count_, pat.ptr.data(), pat.row.data(), pat.groups, pat.block.data(), pat.col.data(), x, y, 0,
+                                             adjoint && BlockOperatorApi<T>::conj ? 1 : 0));
+    }
+    int64_t nrows_, ncols_, m_ = 0, n_ = 0, k_ = 0, p_ = 0;
+    int32_t count_, dense_count_;
+    const DeviceMatrix<T> *left_, *mid_, *right_, *dense_;
+    const DeviceBuffer<Real> *s_;
+    const DeviceIndex *ranks_;
+    Pattern by_row_, by_col_;
+};
 template <typename T>
 typename Scalar<T>::real max_col_norm(const DeviceMatrix<T> &y) {  // :184-191
     typename Scalar<T>::real out = 0;

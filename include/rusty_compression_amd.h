@@ -183,7 +183,8 @@ rc_status rc_set_option(rc_context *ctx, int32_t option, int64_t value);
  * its workgroups resident, 8 the right-vector workgroup of the Jacobi SVD never saw its producer within the spin bound,
  * 16 a Jacobi SVD used up its sweep budget before converging (eager calls as well: the factors are then accurate to the
  * last sweep's rotation angles only), 32 an index handed to a gather (a permutation entry, a column index) was outside the
- * source: the affected outputs are zero instead of whatever a wild address held.  0 = every result stands. */
+ * source: the affected outputs are zero instead of whatever a wild address held, 64 a block id, entry_col or group_row of
+ * rc_block_operator_apply_* was out of range: that entry or group was skipped.  0 = every result stands. */
 rc_status rc_get_health(rc_context *ctx, int32_t *word);
 
 /* Stage / kernel timers: HIP events recorded on the context's stream around the
@@ -650,6 +651,48 @@ rc_status rc_lowrank_residual_batched_f64(rc_context *ctx, rc_matrix a, int64_t 
 rc_status rc_lowrank_residual_batched_f32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const float *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix e, int64_t e_batch_stride, float *err, float *nrm);
 rc_status rc_lowrank_residual_batched_c64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const double *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix e, int64_t e_batch_stride, double *err, double *nrm);
 rc_status rc_lowrank_residual_batched_c32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const float *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix e, int64_t e_batch_stride, float *err, float *nrm);
+/* Apply the block-sparse operator such a batch describes, y = H x, in one stream-ordered, capturable call: the blocks of H are the low-rank
+ * factors of a batch (the operands of rc_lowrank_apply_batched_*, unchanged) and, optionally, a batch of dense near-field blocks of the same
+ * m x n shape, placed by a block-CSR pattern that lives on the device.  It is what the reference's MatMat / ConjMatMat (src/types.rs:40-101)
+ * are for a hierarchical (BLR, H-matrix, FMM) operator whose blocks the batched calls above compressed; the gather of x, the apply and the
+ * scatter-add into y happen in one launch, without atomics on y and without a workspace.
+ * Layout.  Block ids are unified: id < count is low-rank block id (left, mid, s, right and ranks exactly as in rc_lowrank_apply_batched_*,
+ * each view moved by id times its batch stride, 0 legal); count <= id < count + dense_count is block id - count of dense (m x n, moved by
+ * dense_batch_stride; dense.data == NULL: there are none and dense_count is ignored).  Group g owns rows group_row[g] .. group_row[g] + m - 1
+ * of y and consists of the entries group_ptr[g] .. group_ptr[g + 1] - 1, in that order; entry e contributes block entry_block[e] applied to
+ * rows entry_col[e] .. entry_col[e] + n - 1 of x.  group_ptr (groups + 1 values, non-decreasing, indexing entry_block and entry_col, whose
+ * length is not passed: that they cover group_ptr[groups] entries is the caller's contract), group_row (groups), entry_block and entry_col are
+ * device int64 arrays.  x is N x nrhs and y is M x nrhs with any strides; y must not overlap an input.  A block may appear in several
+ * entries and groups, and the x ranges of entries may overlap freely.  The row ranges of two groups must not overlap: if they do, which
+ * group's values those rows hold is unspecified and nothing else is affected.  Rows of y that belong to no group are not touched.
+ * Arithmetic.  Per group and column of x: acc starts at +0; every entry adds its contribution in list order, one rounding per add; the
+ * group's rows of y receive acc, or y_old + acc (one more rounding) when accumulate != 0.  An empty group writes zeros, or leaves y_old when
+ * accumulating.  The contribution of a low-rank entry is, bit for bit, what rc_lowrank_apply_batched_* writes for that block with
+ * b = x[entry_col : entry_col + n, :]: r = ranks[id] clamped to [0, K], nothing at an index >= r is read, r = 0 contributes nothing.  The
+ * contribution of a dense entry is sum_j D[i, j] x[col + j, c] in the summation order of the apply's last product at inner extent n, so for
+ * n <= 128 it equals the low-rank contribution of left = D, right = I_n bit for bit.
+ * conj != 0 (complex types; ignored for f64 / f32): every element of left, mid, right and dense is conjugated as it is loaded; s is real and
+ * x is untouched.  With the transposed views (left = right^T, right = left^T, mid^T, dense^T as strided views) and the pattern grouped by
+ * column instead of by row this is A^H x.  (mid and s together do not transpose into this chain: (L M diag(s) R)^T = R^T diag(s) M^T L^T.)
+ * Bits.  The bits of a group's rows depend on its entries' operands in order, the rows of x they read, which stride of each view is the
+ * smaller, and the block shape: not on groups, the group's position, the other groups, nrhs or the column tile (column c of a 17-column x
+ * equals the same column applied alone), any batch stride, the grid, or graph replay against an eager call.  Non-finite values stay inside the
+ * groups that reference them.
+ * Indices are checked on the device: an entry whose block id is outside [0, count + dense_count) or whose entry_col is outside [0, N - n] is
+ * skipped, a group whose group_row is outside [0, M - m] (or whose group_ptr pair starts below 0) writes nothing, and either case ORs bit 64
+ * into the health word; every other group is unaffected.
+ * Domain: 1 <= m, n <= 512, 1 <= K <= 128, nrhs >= 1, count, dense_count, groups >= 0 (groups == 0: nothing to do).  m, n (and K) are those of
+ * left and right when count > 0 or left.data != NULL, else those of dense.  RC_INVALID_ARGUMENT for an argument outside the domain,
+ * inconsistent shapes (left.cols != right.rows, mid not K x K, dense not m x n, x.cols != y.cols), neither a low-rank nor a dense batch with
+ * groups > 0, a null left or right with count > 0, a null index array, x or y with groups > 0, or a null ctx (rejected before a device is
+ * touched).  No host synchronisation, no workspace: a work unit is (group, tile of columns), its m x tile accumulator stays on the chip and y
+ * is written once.  Parallelism is therefore groups x tiles: an operator with fewer block rows than the device holds workgroups does not fill
+ * it at nrhs = 1 (splitting a group would need a workspace that grows with the entry count).
+ * Complex scalars (c64, c32): interleaved (re, im) data, strides and batch strides in complex elements; s has the real type. */
+rc_status rc_block_operator_apply_f64(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const double *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix dense, int64_t dense_batch_stride, int32_t dense_count, const int64_t *group_ptr, const int64_t *group_row, int32_t groups, const int64_t *entry_block, const int64_t *entry_col, rc_matrix x, rc_matrix y, int32_t accumulate, int32_t conj);
+rc_status rc_block_operator_apply_f32(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const float *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix dense, int64_t dense_batch_stride, int32_t dense_count, const int64_t *group_ptr, const int64_t *group_row, int32_t groups, const int64_t *entry_block, const int64_t *entry_col, rc_matrix x, rc_matrix y, int32_t accumulate, int32_t conj);
+rc_status rc_block_operator_apply_c64(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const double *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix dense, int64_t dense_batch_stride, int32_t dense_count, const int64_t *group_ptr, const int64_t *group_row, int32_t groups, const int64_t *entry_block, const int64_t *entry_col, rc_matrix x, rc_matrix y, int32_t accumulate, int32_t conj);
+rc_status rc_block_operator_apply_c32(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const float *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix dense, int64_t dense_batch_stride, int32_t dense_count, const int64_t *group_ptr, const int64_t *group_row, int32_t groups, const int64_t *entry_block, const int64_t *entry_col, rc_matrix x, rc_matrix y, int32_t accumulate, int32_t conj);
 
 /* The gather over RCCL (xGMI inside a node).  One process per GPU: rank 0 calls rc_comm_unique_id and hands the 128
  * bytes to the other ranks by whatever means the host has (MPI, a file, torch.distributed), every rank calls

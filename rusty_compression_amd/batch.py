@@ -245,6 +245,154 @@ def svd_apply_batched(u: torch.Tensor, s: torch.Tensor, vt: torch.Tensor, ranks:
     return lowrank_apply_batched(u, vt, b=b, s=s, ranks=ranks)
 
 
+def block_csr(rows, cols, block_ids, group_rows=None, group_cols=None):
+    """The block-CSR pattern of rc_block_operator_apply_* and its transposed twin, built on the host with NumPy.
+
+    Entry e of the input places block block_ids[e] with its first row at rows[e] (a row of y) and its first column at cols[e] (a row of
+    x).  Returns (pattern, pattern_t), each a tuple (group_ptr, group_row, entry_block, entry_col) of int64 arrays.  pattern groups the
+    entries by row: one group per distinct value of rows in ascending order, or one per element of group_rows when given (a value of
+    group_rows that no entry has gives an empty group; every entry's row must be listed).  Within a group the entries keep the order
+    of the input, which is the order the kernel sums them in.  pattern_t groups the same entries by column (group_cols likewise), its
+    entry_col holding the rows: with the transposed views of the blocks it is the pattern of A^T x / A^H x."""
+    import numpy as np
+
+    rows, cols, ids = (np.asarray(v, dtype=np.int64).reshape(-1) for v in (rows, cols, block_ids))
+    if not (rows.shape == cols.shape == ids.shape):
+        raise AssertionError("block_csr: rows, cols and block_ids must have one value per entry")
+
+    def grouped(first, other, listed):
+        if listed is None:
+            heads = np.unique(first)
+        else:
+            heads = np.asarray(listed, dtype=np.int64).reshape(-1)
+            if np.unique(heads).size != heads.size:
+                raise AssertionError("block_csr: a group is listed twice")
+        order = np.argsort(heads, kind="stable")
+        pos = np.searchsorted(heads[order], first)
+        if first.size and (np.any(pos >= heads.size) or np.any(heads[order][np.minimum(pos, heads.size - 1)] != first)):
+            raise AssertionError("block_csr: an entry belongs to no listed group")
+        group_of = order[pos] if first.size else pos  # the group of every entry, in the order of `heads`
+        perm = np.argsort(group_of, kind="stable")    # entries by group, input order inside a group
+        ptr = np.zeros(heads.size + 1, dtype=np.int64)
+        np.cumsum(np.bincount(group_of, minlength=heads.size), out=ptr[1:])
+        return ptr, heads.copy(), ids[perm].copy(), other[perm].copy()
+
+    return grouped(rows, cols, group_rows), grouped(cols, rows, group_cols)
+
+
+class _BlockOperatorCall:
+    """The checked operands of rc_block_operator_apply_* on the device, ready to be applied to any x and y (block_operator_apply, the
+    products of operator.BlockLowRankOperator): keeps the tensors alive and builds the argument list of the C call."""
+
+    def __init__(self, who, pattern, left=None, right=None, mid=None, s=None, ranks=None, dense=None):
+        from . import _lib
+        from .types import as_device, as_index
+
+        ops = {"left": left, "right": right, "mid": mid, "dense": dense}
+        ops = {name: as_device(t).resolve_conj() for name, t in ops.items() if t is not None}  # the kernels read the stored values
+        if ("left" in ops) != ("right" in ops):
+            raise AssertionError(f"{who}: left and right come together")
+        if "left" not in ops and "dense" not in ops:
+            raise AssertionError(f"{who}: needs a low-rank batch (left, right), a dense batch, or both")
+        if "left" not in ops and (mid is not None or s is not None or ranks is not None):
+            raise AssertionError(f"{who}: mid, s and ranks belong to a low-rank batch")
+        first = ops["left"] if "left" in ops else ops["dense"]
+        self.dtype = first.dtype
+        for name, t in ops.items():
+            if t.dtype != self.dtype:
+                raise TypeError(f"{who}: {name} is {t.dtype}, expected {self.dtype}")
+            if t.dim() != 3:
+                raise AssertionError(f"{who}: {name} must be a [count, rows, cols] batch")
+        self.left, self.right, self.mid, self.dense = ops.get("left"), ops.get("right"), ops.get("mid"), ops.get("dense")
+        self.count = self.left.shape[0] if self.left is not None else 0
+        for name in ("right", "mid"):
+            if name in ops and ops[name].shape[0] != self.count:
+                raise AssertionError(f"{who}: {name} holds {ops[name].shape[0]} blocks, left {self.count}")
+        self.m, self.n = (self.left.shape[1], self.right.shape[2]) if self.left is not None else self.dense.shape[1:]
+        self.s = self.ranks = None
+        if s is not None:
+            k = self.left.shape[2]
+            s = as_device(s)
+            if s.dtype != _lib.real_dtype(self.dtype):
+                raise TypeError(f"{who}: s is {s.dtype}, expected {_lib.real_dtype(self.dtype)}")
+            if s.dim() != 2 or s.shape[0] != self.count or s.shape[1] < k:
+                raise AssertionError(f"{who}: s must be [count, p] with p >= k = {k}")
+            self.s = s if s.stride(1) == 1 else s.contiguous()
+        if ranks is not None:
+            ranks = as_device(ranks)
+            if ranks.dtype != torch.int64:
+                raise TypeError(f"{who}: ranks is {ranks.dtype}, expected torch.int64")
+            if ranks.shape != (self.count,):
+                raise AssertionError(f"{who}: ranks must be [count]")
+            self.ranks = ranks.contiguous()
+        self.pattern = tuple(as_index(v) for v in pattern)
+        group_ptr, group_row, entry_block, entry_col = self.pattern
+        self.groups = int(group_row.numel())
+        if group_ptr.numel() != self.groups + 1 or entry_block.numel() != entry_col.numel():
+            raise AssertionError(f"{who}: group_ptr needs groups + 1 values, entry_block and entry_col one per entry")
+        self.name = f"rc_block_operator_apply_{_lib.suffix(self.dtype)}"
+
+    def args(self, xv, yv, accumulate=False, conj=False):
+        """The arguments after ctx: xv and yv are rc_matrix views of x (N x nrhs) and y (M x nrhs)."""
+        from . import _lib
+
+        def view(t):  # block 0's view and the batch stride
+            if t is None:
+                return _lib.mat(None), ctypes.c_int64(0)
+            return _lib.rc_matrix(t.data_ptr(), t.shape[1], t.shape[2], t.stride(1), t.stride(2)), ctypes.c_int64(t.stride(0))
+
+        s = self.s
+        group_ptr, group_row, entry_block, entry_col = self.pattern
+        return (*view(self.left), *view(self.mid), ctypes.c_void_p(s.data_ptr() if s is not None else None),
+                ctypes.c_int64(s.stride(0) if s is not None else 0), *view(self.right), _lib.i64p(self.ranks), ctypes.c_int32(self.count),
+                *view(self.dense), ctypes.c_int32(self.dense.shape[0] if self.dense is not None else 0), _lib.i64p(group_ptr), _lib.i64p(group_row),
+                ctypes.c_int32(self.groups), _lib.i64p(entry_block), _lib.i64p(entry_col), xv, yv, ctypes.c_int32(1 if accumulate else 0),
+                ctypes.c_int32(1 if conj else 0))
+
+    def apply(self, x, y=None, rows=None, accumulate=False, conj=False):
+        from . import _lib
+        from .types import as_device
+
+        x = as_device(x).resolve_conj()
+        if x.dtype != self.dtype:
+            raise TypeError(f"{self.name}: x is {x.dtype}, expected {self.dtype}")
+        vector = x.dim() == 1
+        x2 = x.unsqueeze(1) if vector else x
+        if y is None:
+            if rows is None:
+                raise AssertionError("block_operator_apply: give y, or rows (the number of rows of y)")
+            y = torch.zeros((int(rows), x2.shape[1]), dtype=self.dtype, device=x.device)  # rows of no group stay zero
+            out = y[:, 0] if vector else y
+        else:
+            if not (isinstance(y, torch.Tensor) and y.is_cuda and y.dtype == self.dtype and y.dim() == x.dim()):
+                raise AssertionError("block_operator_apply: y must be a device tensor of x's dtype and rank")
+            out = y
+            y = y.unsqueeze(1) if vector else y
+        _lib.default_context().call(self.name, *self.args(_lib.mat(x2), _lib.mat(y), accumulate, conj))
+        return out
+
+
+def block_operator_apply(x: torch.Tensor, group_ptr, group_row, entry_block, entry_col, left: Optional[torch.Tensor] = None,
+                         right: Optional[torch.Tensor] = None, mid: Optional[torch.Tensor] = None, s: Optional[torch.Tensor] = None,
+                         ranks: Optional[torch.Tensor] = None, dense: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None,
+                         rows: Optional[int] = None, accumulate: bool = False, conj: bool = False) -> torch.Tensor:
+    """y = H x for the block-sparse operator whose blocks are a batch of low-rank factors and / or a batch of dense blocks, in one
+    stream-ordered call (rc_block_operator_apply_*): the gather of x, lowrank_apply_batched and the scatter-add into y without
+    atomics and without the two intermediate buffers.
+
+    left [count, m, k], right [count, k, n], mid, s and ranks are the operands of lowrank_apply_batched; dense is [dense_count, m, n]
+    or None.  Block ids 0 .. count - 1 are the low-rank blocks, count .. count + dense_count - 1 the dense ones.  (group_ptr,
+    group_row, entry_block, entry_col) is the block-CSR pattern (block_csr builds it): group g owns rows group_row[g] .. + m - 1 of y
+    and sums, in order, the entries group_ptr[g] .. group_ptr[g + 1] - 1; entry e is block entry_block[e] applied to rows
+    entry_col[e] .. + n - 1 of x.  x is [N, nrhs] or [N].  y ([M, nrhs] or [M], any strides) is written in place when given, else a
+    zero-filled [rows, nrhs] result is returned; rows of no group are not touched.  accumulate adds to y instead of overwriting the
+    groups' rows; conj conjugates the blocks (not x) as they are loaded, a no-op for real data.  The row ranges of two groups must
+    not overlap.  An out-of-range block id, entry_col or group_row is skipped on the device and sets bit 64 of the health word
+    (Context.get_health)."""
+    call = _BlockOperatorCall("block_operator_apply", (group_ptr, group_row, entry_block, entry_col), left, right, mid, s, ranks, dense)
+    return call.apply(x, y=y, rows=rows, accumulate=accumulate, conj=conj)
+
+
 def lowrank_recompress_batched(left: torch.Tensor, right: torch.Tensor, k: int, tol: float = 0.0, mid: Optional[torch.Tensor] = None,
                                s: Optional[torch.Tensor] = None,
                                ranks: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:

@@ -1172,6 +1172,48 @@ void check_lowrank_residual_batched(Mat<T> a, Mat<T> left, Mat<T> mid, Mat<T> ri
     if (count > 0) RC_REQUIRE(a.p && left.p && right.p && err, RC_INVALID_ARGUMENT, "%s: null pointer", who);
 }
 
+// rc_block_operator_apply_*: the block shape m x n (and the inner width K of the low-rank batch, 0 without one) from left / right when there is a
+// low-rank batch, else from dense; the batched kernels' domain for m, n, K; x and y as N x nrhs and M x nrhs.  Indices live on the device and are
+// checked there.
+template <typename T>
+BlockShape check_block_operator_apply(Mat<T> left, Mat<T> mid, Mat<T> right, int32_t count, Mat<T> dense, int32_t *dense_count, const BlockPattern &pat,
+                                      Mat<T> x, Mat<T> y) {
+    const char *who = "block_operator_apply";
+    if (!dense.p) *dense_count = 0;
+    RC_REQUIRE(count >= 0 && *dense_count >= 0 && pat.groups >= 0, RC_INVALID_ARGUMENT, "%s: count = %d, dense_count = %d, groups = %d: none may be negative", who,
+               (int)count, (int)*dense_count, (int)pat.groups);
+    const bool lowrank = count > 0 || left.p;
+    BlockShape sh{0, 0, 0};
+    if (lowrank) {
+        const int64_t m = left.rows, k = left.cols, n = right.cols;
+        RC_REQUIRE(m >= 1 && m <= 512 && n >= 1 && n <= 512 && k >= 1 && k <= 128, RC_INVALID_ARGUMENT,
+                   "%s: needs 1 <= m, n <= 512 and 1 <= K <= 128 (got left %lld x %lld, right %lld x %lld)", who, (long long)m, (long long)k,
+                   (long long)right.rows, (long long)n);
+        RC_REQUIRE(right.rows == k, RC_INVALID_ARGUMENT, "%s: left is %lld x %lld but right has %lld rows", who, (long long)m, (long long)k,
+                   (long long)right.rows);
+        RC_REQUIRE(!mid.p || (mid.rows == k && mid.cols == k), RC_INVALID_ARGUMENT, "%s: mid must be %lld x %lld (got %lld x %lld)", who, (long long)k,
+                   (long long)k, (long long)mid.rows, (long long)mid.cols);
+        RC_REQUIRE(!dense.p || (dense.rows == m && dense.cols == n), RC_INVALID_ARGUMENT, "%s: dense must be %lld x %lld like the low-rank blocks (got %lld x %lld)",
+                   who, (long long)m, (long long)n, (long long)dense.rows, (long long)dense.cols);
+        if (count > 0) RC_REQUIRE(left.p && right.p, RC_INVALID_ARGUMENT, "%s: null pointer (left or right with count > 0)", who);
+        sh = BlockShape{(int)m, (int)n, (int)k};
+    } else if (dense.p) {
+        RC_REQUIRE(dense.rows >= 1 && dense.rows <= 512 && dense.cols >= 1 && dense.cols <= 512, RC_INVALID_ARGUMENT,
+                   "%s: needs 1 <= m, n <= 512 (got dense %lld x %lld)", who, (long long)dense.rows, (long long)dense.cols);
+        sh = BlockShape{(int)dense.rows, (int)dense.cols, 0};
+    } else {
+        RC_REQUIRE(pat.groups == 0, RC_INVALID_ARGUMENT, "%s: neither a low-rank nor a dense batch: the block shape is unknown", who);
+    }
+    RC_REQUIRE(x.cols >= 1 && x.cols <= INT32_MAX && x.rows >= 0, RC_INVALID_ARGUMENT, "%s: x must be N x nrhs with nrhs >= 1 (got %lld x %lld)", who,
+               (long long)x.rows, (long long)x.cols);
+    RC_REQUIRE(y.cols == x.cols && y.rows >= 0, RC_INVALID_ARGUMENT, "%s: y must be M x %lld like x (got %lld x %lld)", who, (long long)x.cols,
+               (long long)y.rows, (long long)y.cols);
+    if (pat.groups > 0)
+        RC_REQUIRE(pat.group_ptr && pat.group_row && pat.entry_block && pat.entry_col && x.p && y.p, RC_INVALID_ARGUMENT,
+                   "%s: null pointer (an index array, x or y with groups > 0)", who);
+    return sh;
+}
+
 template int64_t check_column_id_rank_batched<double>(Mat<double>, int32_t, int64_t, double, Mat<double>, int64_t, Mat<double>, int64_t, const int64_t *,
                                                       const int64_t *);
 template int64_t check_column_id_rank_batched<float>(Mat<float>, int32_t, int64_t, double, Mat<float>, int64_t, Mat<float>, int64_t, const int64_t *,
@@ -1185,6 +1227,10 @@ template int64_t check_svd_rank_batched<double>(Mat<double>, int32_t, int64_t, d
 template int64_t check_svd_rank_batched<float>(Mat<float>, int32_t, int64_t, double, Mat<float>, int64_t, const float *, Mat<float>, int64_t, const int64_t *);
 template void check_lowrank_apply_batched<double>(Mat<double>, Mat<double>, Mat<double>, int32_t, Mat<double>, Mat<double>, int64_t);
 template void check_lowrank_apply_batched<float>(Mat<float>, Mat<float>, Mat<float>, int32_t, Mat<float>, Mat<float>, int64_t);
+template BlockShape check_block_operator_apply<double>(Mat<double>, Mat<double>, Mat<double>, int32_t, Mat<double>, int32_t *, const BlockPattern &, Mat<double>,
+                                                       Mat<double>);
+template BlockShape check_block_operator_apply<float>(Mat<float>, Mat<float>, Mat<float>, int32_t, Mat<float>, int32_t *, const BlockPattern &, Mat<float>,
+                                                      Mat<float>);
 template void check_lowrank_residual_batched<double>(Mat<double>, Mat<double>, Mat<double>, Mat<double>, int32_t, Mat<double>, int64_t, const double *);
 template void check_lowrank_residual_batched<float>(Mat<float>, Mat<float>, Mat<float>, Mat<float>, int32_t, Mat<float>, int64_t, const float *);
 
@@ -1227,6 +1273,16 @@ void lowrank_apply_batched(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, 
     check_lowrank_apply_batched(left, mid, right, count, b, y, ybs);
     if (count == 0) return;
     batched_lowrank_apply(c, left, lbs, mid, mbs, s, s_stride, right, rbs, ranks, count, b, bbs, y, ybs);
+}
+
+// y = H x for the block-sparse operator made of a low-rank batch and a dense batch placed by a block-CSR pattern on the device: one launch, no workspace
+template <typename T>
+void block_operator_apply_checked(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride, Mat<T> right, int64_t rbs,
+                                  const int64_t *ranks, int32_t count, Mat<T> dense, int64_t dbs, int32_t dense_count, const BlockPattern &pat, Mat<T> x,
+                                  Mat<T> y, int32_t accumulate) {
+    const BlockShape sh = check_block_operator_apply(left, mid, right, count, dense, &dense_count, pat, x, y);
+    if (pat.groups == 0) return;
+    block_operator_apply(c, left, lbs, mid, mbs, s, s_stride, right, rbs, ranks, count, dense, dbs, dense_count, pat, sh, x, y, accumulate != 0);
 }
 
 // recompress every factor pair left (m x K) [mid (K x K)] [diag(s)] right (K x n) of a batch to a truncated SVD of rank <= min(k, K) without forming
@@ -1849,6 +1905,20 @@ rc_status rc_invert_permutation(rc_context *ctx, const int64_t *perm, int64_t n,
         return guarded(ctx, [&] {                                                                                                        \
             lowrank_apply_batched<T>(ctx, from_c<T>(left), left_batch_stride, from_c<T>(mid), mid_batch_stride, s, s_stride, from_c<T>(right), \
                                      right_batch_stride, ranks, count, from_c<T>(b), b_batch_stride, from_c<T>(y), y_batch_stride);     \
+        });                                                                                                                              \
+    }                                                                                                                                    \
+    /* conj is ignored: conjugation is the identity on real data */                                                                      \
+    rc_status rc_block_operator_apply_##SUF(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, \
+                                            const T *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, \
+                                            int32_t count, rc_matrix dense, int64_t dense_batch_stride, int32_t dense_count,             \
+                                            const int64_t *group_ptr, const int64_t *group_row, int32_t groups, const int64_t *entry_block, \
+                                            const int64_t *entry_col, rc_matrix x, rc_matrix y, int32_t accumulate, int32_t conj) {      \
+        (void)conj;                                                                                                                      \
+        return guarded(ctx, [&] {                                                                                                        \
+            block_operator_apply_checked<T>(ctx, from_c<T>(left), left_batch_stride, from_c<T>(mid), mid_batch_stride, s, s_stride,      \
+                                            from_c<T>(right), right_batch_stride, ranks, count, from_c<T>(dense), dense_batch_stride,    \
+                                            dense_count, BlockPattern{group_ptr, group_row, entry_block, entry_col, groups}, from_c<T>(x), \
+                                            from_c<T>(y), accumulate);                                                                   \
         });                                                                                                                              \
     }                                                                                                                                    \
     rc_status rc_lowrank_recompress_batched_##SUF(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid,             \

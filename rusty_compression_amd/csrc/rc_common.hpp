@@ -241,6 +241,28 @@ template <typename R> void batched_lowrank_apply_c(rc_context *c, const rc_matri
                                                    const rc_matrix &b, int64_t bbs, const rc_matrix &y, int64_t ybs);
 // the argument checks of rc_lowrank_apply_batched_* (rc_api.hip), shared by every scalar type like the three above; the caller returns when count == 0
 template <typename T> void check_lowrank_apply_batched(Mat<T> left, Mat<T> mid, Mat<T> right, int32_t count, Mat<T> b, Mat<T> y, int64_t ybs);
+// y = H x for the block-sparse operator whose blocks are the factors of such a batch and a batch of dense m x n blocks, placed by a block-CSR
+// pattern on the device (kernels_block_operator.hip, rc_block_operator_apply_*): the low-rank operands as in batched_lowrank_apply, block ids
+// count .. count + dense_count - 1 are dense (p == nullptr: none); shape holds m, n and k (0 without a low-rank batch) as the check returns them;
+// the complex twin takes interleaved-complex views and conjugates the blocks on load when conj is set (arguments checked by the caller)
+struct BlockPattern {
+    const int64_t *group_ptr, *group_row, *entry_block, *entry_col;
+    int32_t groups;
+};
+struct BlockShape {
+    int m, n, k;
+};
+template <typename T> void block_operator_apply(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride, Mat<T> right,
+                                                int64_t rbs, const int64_t *ranks, int32_t count, Mat<T> dense, int64_t dbs, int32_t dense_count,
+                                                const BlockPattern &pat, BlockShape shape, Mat<T> x, Mat<T> y, bool accumulate);
+template <typename R> void block_operator_apply_c(rc_context *c, const rc_matrix &left, int64_t lbs, const rc_matrix &mid, int64_t mbs, const R *s,
+                                                  int64_t s_stride, const rc_matrix &right, int64_t rbs, const int64_t *ranks, int32_t count,
+                                                  const rc_matrix &dense, int64_t dbs, int32_t dense_count, const BlockPattern &pat, BlockShape shape,
+                                                  const rc_matrix &x, const rc_matrix &y, bool accumulate, bool conj);
+// the argument checks of rc_block_operator_apply_* (rc_api.hip), shared by every scalar type; dense_count is zeroed when dense.p == nullptr; the
+// caller returns when pat.groups == 0
+template <typename T> BlockShape check_block_operator_apply(Mat<T> left, Mat<T> mid, Mat<T> right, int32_t count, Mat<T> dense, int32_t *dense_count,
+                                                            const BlockPattern &pat, Mat<T> x, Mat<T> y);
 // recompress the factor pairs of such a batch to truncated SVDs without forming the blocks (kernels_batched_id.hip): block i is left (m x K), mid (K x K,
 // p == nullptr: none), right (K x n), u (m x min(k, K)) and vt (min(k, K) x n) each moved by i times its batch stride, s + i * s_stride its K real scales
 // (nullptr: none), in_ranks count device values (nullptr: every inner rank is K); s_out count x K, ranks count (arguments checked by the caller)

@@ -1389,6 +1389,21 @@ extern "C" {
                                        count, b, b_batch_stride, y, y_batch_stride);                                                      \
         });                                                                                                                               \
     }                                                                                                                                     \
+    /* the block-sparse operator of such a batch (kernels_block_operator.hip): the real entry point's checks on views of the same shapes */ \
+    rc_status rc_block_operator_apply_##SUF(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, \
+                                            const R *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, \
+                                            int32_t count, rc_matrix dense, int64_t dense_batch_stride, int32_t dense_count,              \
+                                            const int64_t *group_ptr, const int64_t *group_row, int32_t groups, const int64_t *entry_block, \
+                                            const int64_t *entry_col, rc_matrix x, rc_matrix y, int32_t accumulate, int32_t conj) {       \
+        return guarded_c(ctx, [&] {                                                                                                       \
+            const BlockPattern pat{group_ptr, group_row, entry_block, entry_col, groups};                                                 \
+            const BlockShape sh = check_block_operator_apply<R>(shape_of<R>(left), shape_of<R>(mid), shape_of<R>(right), count, shape_of<R>(dense), \
+                                                                &dense_count, pat, shape_of<R>(x), shape_of<R>(y));                       \
+            if (groups == 0) return;                                                                                                      \
+            block_operator_apply_c<R>(ctx, left, left_batch_stride, mid, mid_batch_stride, s, s_stride, right, right_batch_stride, ranks, \
+                                      count, dense, dense_batch_stride, dense_count, pat, sh, x, y, accumulate != 0, conj != 0);          \
+        });                                                                                                                               \
+    }                                                                                                                                     \
     /* residual norms of the factors of a batch against their blocks (kernels_batched_residual_c.hip): the real entry point's checks on */ \
     /* views of the same shapes; s, err and nrm in the real type */                                                                       \
     rc_status rc_lowrank_residual_batched_##SUF(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix left, int64_t left_batch_stride, \

@@ -148,6 +148,67 @@ class LowRankOperator(Operator):
         return dot(self.v, conj_matmat(self.u, x))      # V (U^H x)
 
 
+class BlockLowRankOperator(Operator):
+    """A block-sparse (BLR / hierarchical / FMM) matrix whose blocks are a batch of low-rank factors and, optionally, a batch of dense
+    near-field blocks of the same m x n shape, never formed: each product is ONE launch of rc_block_operator_apply_*.
+
+    shape = (M, N).  Entry e places block block_ids[e] with its top-left corner at (rows[e], cols[e]); ids below count are the
+    low-rank blocks, ids from count on the dense ones (batch.block_operator_apply).  Distinct values of rows must be at least m apart
+    and distinct values of cols at least n apart (the rows of two groups must not overlap, in either product); parts of the matrix
+    that no block covers are zero.  Factor forms: (C, Z) as left, right; (C, X, R) as left, mid, right; (U, s, Vt) as left, s, right;
+    ranks as the batched calls return them.  mid and s together are rejected: (L M diag(s) R)^T = R^T diag(s) M^T L^T is not the
+    kernel's chain left mid diag(s) right, so the view-swapped call behind conj_matmat would compute another product.
+
+    matmat(x) = A x uses the pattern grouped by row; conj_matmat(x) = A^H x the pattern grouped by column on the swapped, transposed
+    views (nothing is copied) with the kernel's conj flag.  matmat_raw / conj_matmat_raw are the forms the library's callback table
+    calls (the range finders of rc_*_op_*): they write straight into the library's buffers on the library's context."""
+
+    def __init__(self, shape, rows, cols, block_ids, left=None, right=None, mid=None, s=None, ranks=None, dense=None):
+        from .batch import _BlockOperatorCall, block_csr
+
+        if mid is not None and s is not None:
+            raise AssertionError("BlockLowRankOperator: mid and s together do not transpose into the kernel's chain; fold s into mid or right")
+        self._shape = (int(shape[0]), int(shape[1]))
+        by_row, by_col = block_csr(rows, cols, block_ids)
+        self._fwd = _BlockOperatorCall("BlockLowRankOperator", by_row, left, right, mid, s, ranks, dense)
+        f = self._fwd
+        t = lambda v: None if v is None else v.transpose(1, 2)  # noqa: E731
+        self._adj = _BlockOperatorCall("BlockLowRankOperator", by_col, t(f.right), t(f.left), t(f.mid), f.s, f.ranks, t(f.dense))
+        self.dtype = f.dtype
+        self._conj = self.dtype.is_complex
+        if self._shape[0] < f.m or self._shape[1] < f.n:
+            raise AssertionError(f"BlockLowRankOperator: shape {self._shape} is smaller than one {f.m} x {f.n} block")
+
+        def covered(heads, extent, total):  # do the groups' row ranges tile [0, total)?
+            heads = sorted(int(h) for h in heads)
+            return bool(heads) and heads[0] == 0 and heads[-1] + extent == total and all(b - a == extent for a, b in zip(heads, heads[1:]))
+
+        self._covered = (covered(by_row[1], f.m, self._shape[0]), covered(by_col[1], f.n, self._shape[1]))
+
+    def nrows(self):
+        return self._shape[0]
+
+    def ncols(self):
+        return self._shape[1]
+
+    def _raw(self, call, covered, conj, ctx_h, x: _lib.rc_matrix, y: _lib.rc_matrix):
+        if not covered:  # rows of y that no group owns are zero rows of the operator; the kernel does not touch them
+            view_of(y, self.dtype).zero_()
+        return getattr(_lib.lib(), call.name)(ctypes.c_void_p(ctx_h), *call.args(x, y, False, conj))
+
+    def matmat_raw(self, ctx_h, x, y):
+        return self._raw(self._fwd, self._covered[0], False, ctx_h, x, y)
+
+    def conj_matmat_raw(self, ctx_h, x, y):
+        return self._raw(self._adj, self._covered[1], self._conj, ctx_h, x, y)
+
+    def matmat(self, x):
+        return self._fwd.apply(x, rows=self._shape[0])
+
+    def conj_matmat(self, x):
+        return self._adj.apply(x, rows=self._shape[1], conj=self._conj)
+
+
 def is_operator(op) -> bool:
     return not isinstance(op, torch.Tensor) and all(hasattr(op, f) for f in ("nrows", "ncols", "matmat"))
 
