@@ -237,7 +237,11 @@ rc_status rc_rel_diff_fro_f64(rc_context *ctx, rc_matrix first, rc_matrix second
 rc_status rc_rel_diff_fro_f32(rc_context *ctx, rc_matrix first, rc_matrix second, float *out);
 
 /* --------------------------------------------------------- permutation.rs -- */
-/* invert_permutation_vector (src/permutation.rs:28-38) */
+/* invert_permutation_vector (src/permutation.rs:28-38): inverse[perm[i]] = i.  perm and inverse are device arrays of n entries.
+ * An input that is no permutation is not an error here: inverse starts at -1 everywhere, an entry outside [0, n) is skipped, and a
+ * value that occurs twice leaves one of its positions (which one is not defined).  So every position that no in-range entry names
+ * holds -1, and nothing outside inverse[0 .. n) is written.  The call raises no health bit itself: the gather that consumes a -1
+ * rejects it (bit 32, rc_get_health), which is how the INV modes below and the to_mat / ID calls report such an input. */
 rc_status rc_invert_permutation(rc_context *ctx, const int64_t *perm, int64_t n, int64_t *inverse);
 /* ApplyPermutationToMatrix::apply_permutation (src/permutation.rs:84-144).
  * RC_INVALID_ARGUMENT when perm_len mismatches (the reference asserts). */
@@ -296,10 +300,14 @@ rc_status rc_qr_to_mat_f32(rc_context *ctx, rc_matrix q, rc_matrix r, const int6
 /* LQTraits::to_mat (src/qr.rs:73-77): out = (L with ROWINV permutation) Q. */
 rc_status rc_lq_to_mat_f64(rc_context *ctx, rc_matrix l, rc_matrix q, const int64_t *ind, rc_matrix out);
 rc_status rc_lq_to_mat_f32(rc_context *ctx, rc_matrix l, rc_matrix q, const int64_t *ind, rc_matrix out);
-/* QRTraits::column_id (src/qr.rs:270-309): c: m x k, z: k x n (both branches). */
+/* QRTraits::column_id (src/qr.rs:270-309): c: m x k, z: k x n (both branches).
+ * `ind` (n entries) is the caller's and is checked: an entry outside [0, n) is skipped, a column of z that no in-range entry names is
+ * exactly zero, nothing is written outside z or read outside r, and health bit 32 is raised in either case (a duplicated entry leaves
+ * such a column; the column it names twice holds the result of one of the two positions).  c = q r[:, :k] does not depend on ind. */
 rc_status rc_qr_column_id_f64(rc_context *ctx, rc_matrix q, rc_matrix r, const int64_t *ind, rc_matrix c, rc_matrix z);
 rc_status rc_qr_column_id_f32(rc_context *ctx, rc_matrix q, rc_matrix r, const int64_t *ind, rc_matrix c, rc_matrix z);
-/* LQTraits::row_id (src/qr.rs:363-403): x: m x k, r_rows: k x n. */
+/* LQTraits::row_id (src/qr.rs:363-403): x: m x k, r_rows: k x n.  `ind` (m entries) is checked like rc_qr_column_id's: rows of x
+ * that no in-range entry names are exactly zero, health bit 32. */
 rc_status rc_lq_row_id_f64(rc_context *ctx, rc_matrix l, rc_matrix q, const int64_t *ind, rc_matrix x, rc_matrix r_rows);
 rc_status rc_lq_row_id_f32(rc_context *ctx, rc_matrix l, rc_matrix q, const int64_t *ind, rc_matrix x, rc_matrix r_rows);
 /* QRTraits::compute_from_range_estimate (src/qr.rs:311-323): range m x r', A m x n ->

@@ -660,13 +660,31 @@ void trsm_upper(rc_context *c, Mat<T> t, Mat<T> b) {
 //       GEMMs per panel) only to multiply it back with R11 was a third of the launches of a cfg5 matrix.
 // ---------------------------------------------------------------------------
 // FROM_R: w is the k x n factor R in pivoted order (r(i, p), any strides) instead of the ?geqp3-format matrix
-template <typename T, bool FROM_R>
-__global__ __launch_bounds__(256) void k_id_z(Mat<T> w, const int64_t *jpvt, int64_t k, Mat<T> z) {
+// CHECKED (FROM_R only): jpvt is a caller's array.  inv is its checked inverse (invert_perm: inv[jpvt[p]] = p for the entries in
+// range, -1 where no entry names a column, one of the positions where several do).  Position p writes its column only if it owns
+// it (inv[jpvt[p]] == p): nothing is written outside z, no two threads share a column.  Thread p also looks at DESTINATION column p:
+// named by no entry, it is zeroed and health bit 32 raised -- what gather_cols did with the -1 in qr_column_id's former chain.  An
+// entry out of range or a duplicate always leaves such a column, so the bit covers both.  The arithmetic of an owned column is the
+// unchecked kernel's.
+template <bool CHECKED> struct IdzCheck {};
+template <> struct IdzCheck<true> { const int64_t *inv; int *health; };
+template <typename T, bool FROM_R, bool CHECKED = false>
+__global__ __launch_bounds__(256) void k_id_z(Mat<T> w, const int64_t *jpvt, int64_t k, Mat<T> z, IdzCheck<CHECKED> chk = {}) {
+    static_assert(FROM_R || !CHECKED, "the ?geqp3-format variant only ever sees a jpvt the library wrote");
     constexpr int NB = 16;
     __shared__ T tile[NB][NB + 1];
     const int64_t n = w.cols;
     const int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;  // position in the pivoted order
-    const bool inside = p < n;
+    bool owns = p < n;                                                  // CHECKED: ... and this position is the one writer of its column
+    if constexpr (CHECKED) {
+        if (owns && chk.inv[p] < 0) {
+            for (int64_t i = 0; i < k; ++i) z.at(i, p) = (T)0;
+            atomicOr(chk.health, 32);
+        }
+        const int64_t e = owns ? jpvt[p] : -1;
+        owns = (uint64_t)e < (uint64_t)n && chk.inv[e] == p;            // a thread that owns nothing still loads tiles and meets the barriers
+    }
+    const bool inside = owns;
     const int64_t dc = inside ? jpvt[p] : 0;                            // where column p of [I | R11^-1 R12] goes
     const bool active = inside && p >= k;                               // a right-hand side (the first k columns are the identity)
     const T *bcol = FROM_R ? w.p + (inside ? p : 0) * w.cs : w.p + dc * w.cs;  // R12[:, p] (rows 0 .. k-1 of the physical column)
@@ -734,10 +752,19 @@ void id_z_from_r(rc_context *c, Mat<T> r, int64_t k, const int64_t *ind, Mat<T> 
     ProfScope ps(c, "op:id_z_from_r k=%lld n=%lld", (long long)k, (long long)r.cols);
     hipLaunchKernelGGL((k_id_z<T, true>), dim3((unsigned)cdiv(r.cols, 256)), dim3(256), 0, c->stream, r, ind, k, z);
 }
+// The same for an ind the library did not write (the QR / LQ objects of a caller): inv is invert_perm(ind), n entries
+template <typename T>
+void id_z_from_r_checked(rc_context *c, Mat<T> r, int64_t k, const int64_t *ind, const int64_t *inv, Mat<T> z) {
+    RC_REQUIRE(r.rows == k && z.rows == k && z.cols == r.cols && k <= r.cols, RC_INVALID_ARGUMENT, "id_z_from_r: shape mismatch");
+    if (r.cols == 0 || k == 0) return;
+    ProfScope ps(c, "op:id_z_from_r_checked k=%lld n=%lld", (long long)k, (long long)r.cols);
+    hipLaunchKernelGGL((k_id_z<T, true, true>), dim3((unsigned)cdiv(r.cols, 256)), dim3(256), 0, c->stream, r, ind, k, z, IdzCheck<true>{inv, c->health_word()});
+}
 
 #define RC_INST(T)                                                                                         \
     template void column_id_from_qrcp<T>(rc_context *, Mat<T>, Mat<T>, int64_t, const int64_t *, Mat<T>, Mat<T>); \
     template void id_z_from_r<T>(rc_context *, Mat<T>, int64_t, const int64_t *, Mat<T>);                 \
+    template void id_z_from_r_checked<T>(rc_context *, Mat<T>, int64_t, const int64_t *, const int64_t *, Mat<T>); \
     template void geqp3_inplace<T>(rc_context *, Mat<T>, int64_t, bool, int64_t *, T *, T *);             \
     template void extract_r<T>(rc_context *, Mat<T>, const int64_t *, Mat<T>);                             \
     template void form_q<T>(rc_context *, Mat<T>, const int64_t *, const T *, int64_t, Mat<T>);           \

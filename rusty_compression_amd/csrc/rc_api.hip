@@ -532,8 +532,11 @@ void compute_svd(rc_context *c, Mat<T> a, Mat<T> u, T *s, Mat<T> vt) {
 }
 
 // QRTraits::column_id  (/root/reference/src/qr.rs:270-309)
+// own_ind: `ind` was written by the library in this call (a pivoted QR's output: a permutation by construction).  A caller's
+// `ind` (rc_qr_column_id_*, rc_lq_row_id_*) is checked: entries out of range are skipped, columns of Z no entry names are zero,
+// health bit 32 ("Index arrays").
 template <typename T>
-void qr_column_id(rc_context *c, Mat<T> q, Mat<T> r, const int64_t *ind, Mat<T> cm, Mat<T> z) {
+void qr_column_id(rc_context *c, Mat<T> q, Mat<T> r, const int64_t *ind, Mat<T> cm, Mat<T> z, bool own_ind) {
     const int64_t m = q.rows, k = q.cols, n = r.cols;
     RC_REQUIRE(r.rows == k && cm.rows == m && cm.cols == k && z.rows == k && z.cols == n, RC_INVALID_ARGUMENT,
                "column_id: q %lld x %lld, r %lld x %lld, c %lld x %lld, z %lld x %lld", (long long)m, (long long)k,
@@ -544,7 +547,13 @@ void qr_column_id(rc_context *c, Mat<T> q, Mat<T> r, const int64_t *ind, Mat<T> 
     static const int fused = [] { const char *e = getenv("RC_ID_FUSED"); return e ? atoi(e) : 1; }();
     if (fused && k < n) {
         // Z in ONE launch (k_id_z: the chain below with the same arithmetic, every column written to its final place)
-        id_z_from_r(c, r, k, ind, z);
+        if (own_ind) {
+            id_z_from_r(c, r, k, ind, z);
+        } else {
+            int64_t *inv = c->alloc<int64_t>((size_t)n);
+            invert_perm(c, ind, n, inv);
+            id_z_from_r_checked(c, r, k, ind, inv, z);
+        }
         gemm<T>(c, 1, q, r.sub(0, k, 0, k), 0, cm);
         return;
     }
@@ -568,8 +577,8 @@ void qr_column_id(rc_context *c, Mat<T> q, Mat<T> r, const int64_t *ind, Mat<T> 
 // LQTraits::row_id (/root/reference/src/qr.rs:363-403) is the column ID of the
 // transposed factors: X = Z'^T, R_rows = C'^T with (C', Z') = column_id(Q^T, L^T).
 template <typename T>
-void lq_row_id(rc_context *c, Mat<T> l, Mat<T> q, const int64_t *ind, Mat<T> x, Mat<T> rrows) {
-    qr_column_id(c, q.t(), l.t(), ind, rrows.t(), x.t());
+void lq_row_id(rc_context *c, Mat<T> l, Mat<T> q, const int64_t *ind, Mat<T> x, Mat<T> rrows, bool own_ind) {
+    qr_column_id(c, q.t(), l.t(), ind, rrows.t(), x.t(), own_ind);
 }
 
 // B = range^H A written into `b` (any layout)
@@ -921,7 +930,7 @@ bool rsvd_id_consumers_fused(rc_context *c, Mat<T> range, Mat<T> b, const rc_rsv
         }
         Mat<T> q = o.qr_q.data ? from_c<T>(o.qr_q) : tmp_colmajor<T>(c, m, k);
         gemm<T>(c, 1, range, qb, 0, q);
-        if (o.id_c.data || o.id_z.data) qr_column_id(c, q, r, ind, from_c<T>(o.id_c), from_c<T>(o.id_z));
+        if (o.id_c.data || o.id_z.data) qr_column_id(c, q, r, ind, from_c<T>(o.id_c), from_c<T>(o.id_z), /*own_ind=*/true);
     }
     {
         ProfScope ps(c, "stage:svd of B + U=Q Ub");
@@ -964,7 +973,7 @@ void rsvd_id_consumers(rc_context *c, Mat<T> range, Mat<T> b, const rc_rsvd_id_o
         gemm<T>(c, 1, range, qb, 0, q);
         if (o.id_c.data || o.id_z.data) {
             RC_REQUIRE(o.id_c.data && o.id_z.data, RC_INVALID_ARGUMENT, "rsvd_id: id_c and id_z must be given together");
-            qr_column_id(c, q, r, ind, from_c<T>(o.id_c), from_c<T>(o.id_z));
+            qr_column_id(c, q, r, ind, from_c<T>(o.id_c), from_c<T>(o.id_z), /*own_ind=*/true);
         }
     }
     fork.back();
@@ -1057,7 +1066,7 @@ void column_id_rank(rc_context *c, Mat<T> a, int64_t k, Mat<T> cm, Mat<T> z, int
     Mat<T> q = tmp_colmajor<T>(c, m, k);
     Mat<T> r = tmp_rowmajor<T>(c, k, n);
     qrcp_core(c, w, k, true, q, r, col_ind);
-    qr_column_id(c, q, r, col_ind, cm, z);
+    qr_column_id(c, q, r, col_ind, cm, z, /*own_ind=*/true);
 }
 
 // the domain of the batched small-matrix kernels (kernels_batched_id.hip); returns k clamped to min(m, n)
@@ -1752,10 +1761,10 @@ rc_status rc_invert_permutation(rc_context *ctx, const int64_t *perm, int64_t n,
         });                                                                                                                              \
     }                                                                                                                                    \
     rc_status rc_qr_column_id_##SUF(rc_context *ctx, rc_matrix q, rc_matrix r, const int64_t *ind, rc_matrix c, rc_matrix z) {           \
-        return guarded(ctx, [&] { qr_column_id<T>(ctx, from_c<T>(q), from_c<T>(r), ind, from_c<T>(c), from_c<T>(z)); });                 \
+        return guarded(ctx, [&] { qr_column_id<T>(ctx, from_c<T>(q), from_c<T>(r), ind, from_c<T>(c), from_c<T>(z), /*own_ind=*/false); }); \
     }                                                                                                                                    \
     rc_status rc_lq_row_id_##SUF(rc_context *ctx, rc_matrix l, rc_matrix q, const int64_t *ind, rc_matrix x, rc_matrix rr) {             \
-        return guarded(ctx, [&] { lq_row_id<T>(ctx, from_c<T>(l), from_c<T>(q), ind, from_c<T>(x), from_c<T>(rr)); });                   \
+        return guarded(ctx, [&] { lq_row_id<T>(ctx, from_c<T>(l), from_c<T>(q), ind, from_c<T>(x), from_c<T>(rr), /*own_ind=*/false); }); \
     }                                                                                                                                    \
     rc_status rc_qr_from_range_estimate_##SUF(rc_context *ctx, rc_matrix range, rc_matrix a, rc_matrix q, rc_matrix r, int64_t *ind) {   \
         return guarded(ctx, [&] { qr_from_range<T>(ctx, from_c<T>(range), OpView<T>::of(from_c<T>(a)), from_c<T>(q), from_c<T>(r), ind); }); \
@@ -1792,7 +1801,7 @@ rc_status rc_invert_permutation(rc_context *ctx, const int64_t *perm, int64_t n,
             const int64_t m = C.rows, k = C.cols, kk = std::min(m, k);                                                                   \
             Mat<T> l = tmp_rowmajor<T>(ctx, m, kk), ql = tmp_rowmajor<T>(ctx, kk, k);                                                    \
             pivoted_qr<T>(ctx, C.t(), ql.t(), l.t(), row_ind); /* LQ::compute_from, qr.rs:354-362 */                                     \
-            lq_row_id<T>(ctx, l, ql, row_ind, from_c<T>(c_out), from_c<T>(x));                                                           \
+            lq_row_id<T>(ctx, l, ql, row_ind, from_c<T>(c_out), from_c<T>(x), /*own_ind=*/true);                                         \
         });                                                                                                                              \
     }                                                                                                                                    \
     rc_status rc_row_id_two_sided_##SUF(rc_context *ctx, rc_matrix r, rc_matrix x, rc_matrix r_out, int64_t *col_ind) {                  \
@@ -1801,7 +1810,7 @@ rc_status rc_invert_permutation(rc_context *ctx, const int64_t *perm, int64_t n,
             const int64_t k = R.rows, n = R.cols, kk = std::min(k, n);                                                                   \
             Mat<T> q = tmp_colmajor<T>(ctx, k, kk), rr = tmp_rowmajor<T>(ctx, kk, n);                                                    \
             pivoted_qr<T>(ctx, R, q, rr, col_ind);                                                                                       \
-            qr_column_id<T>(ctx, q, rr, col_ind, from_c<T>(x), from_c<T>(r_out));                                                        \
+            qr_column_id<T>(ctx, q, rr, col_ind, from_c<T>(x), from_c<T>(r_out), /*own_ind=*/true);                                      \
         });                                                                                                                              \
     }                                                                                                                                    \
     rc_status rc_max_col_norm_##SUF(rc_context *ctx, rc_matrix y, T *out) {                                                              \

@@ -202,6 +202,7 @@ template <typename T> void gather_cols(rc_context *c, Mat<T> src, const int64_t 
 // C, Z of the rank-k column ID from the ?geqp3-format factorization w of a (kernels_qr.hip: two launches, no Q)
 template <typename T> void column_id_from_qrcp(rc_context *c, Mat<T> a, Mat<T> w, int64_t k, const int64_t *jpvt, Mat<T> cm, Mat<T> z);
 template <typename T> void id_z_from_r(rc_context *c, Mat<T> r, int64_t k, const int64_t *ind, Mat<T> z);
+template <typename T> void id_z_from_r_checked(rc_context *c, Mat<T> r, int64_t k, const int64_t *ind, const int64_t *inv, Mat<T> z);
 // rank-revealing column IDs of `count` same-shaped small matrices in one launch (kernels_batched_id.hip): matrix i is a, cm, z moved by
 // i * abs, i * cbs, i * zbs elements; col_ind count x n, ranks count (arguments checked by the caller)
 template <typename T> void batched_column_id(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int64_t k, double tol, Mat<T> cm, int64_t cbs, Mat<T> z,
