@@ -658,28 +658,32 @@ template <typename T>
 DeviceMatrix<T> to_mat_batched(const BatchedSVD<T> &svd) {
     return lowrank_apply_batched<T>(svd.u, nullptr, &svd.s, svd.vt, &svd.ranks, (int32_t)svd.ranks.size(), nullptr);
 }
-// recompress every factor pair of a batch to a truncated SVD without forming the blocks (rc_lowrank_recompress_batched_*; the scheme of
-// SVD::to_qr / compute_from_range_estimate, src/svd.rs:150-163, :171-, with compress's rank rule, :60-101).  The C ABI has the entry
-// point for the real scalars only, so it is reached through its own dispatch, declared for double and float: Api<c64> and Api<c32>
-// stay complete.  left is count * m x K, right count * K x n, mid count * K x K or nullptr, s count x s_stride reals or nullptr,
-// ranks count inner ranks or nullptr (every rank is K); K <= min(m, n).  Returns u (count * m x kk), s (count x K: the singular
-// values of each block, then zeros), vt (count * kk x n) and the new ranks, kk = min(k, K).
+// recompress every factor pair of a batch to a truncated SVD without forming the blocks (rc_lowrank_recompress_batched_* for the real
+// scalars, rc_lowrank_recompress_complex_batched_* for c64 and c32; the scheme of SVD::to_qr / compute_from_range_estimate,
+// src/svd.rs:150-163, :171-, with compress's rank rule, :60-101).  The entry point is reached through its own dispatch: the complex
+// pair has a stem of its own (see the C header) and takes tol in the real type of the data.  left is count * m x K, right
+// count * K x n, mid count * K x K or nullptr, s count x s_stride reals or nullptr, ranks count inner ranks or nullptr (every rank is
+// K); K <= min(m, n).  Returns u (count * m x kk), s (count x K, the real type: the singular values of each block, then zeros), vt
+// (count * kk x n; V^H for complex scalars, nothing else is conjugated) and the new ranks, kk = min(k, K).
 template <typename T> struct RecompressApi;
-template <> struct RecompressApi<double> { static constexpr auto lowrank_recompress_batched = rc_lowrank_recompress_batched_f64; };
-template <> struct RecompressApi<float> { static constexpr auto lowrank_recompress_batched = rc_lowrank_recompress_batched_f32; };
+template <> struct RecompressApi<double> { using tol_type = double; static constexpr auto lowrank_recompress_batched = rc_lowrank_recompress_batched_f64; };
+template <> struct RecompressApi<float> { using tol_type = double; static constexpr auto lowrank_recompress_batched = rc_lowrank_recompress_batched_f32; };
+template <> struct RecompressApi<c64> { using tol_type = double; static constexpr auto lowrank_recompress_batched = rc_lowrank_recompress_complex_batched_c64; };
+template <> struct RecompressApi<c32> { using tol_type = float; static constexpr auto lowrank_recompress_batched = rc_lowrank_recompress_complex_batched_c32; };
 template <typename T>
-BatchedSVD<T> recompress_batched(const DeviceMatrix<T> &left, const DeviceMatrix<T> *mid, const DeviceBuffer<T> *s, const DeviceMatrix<T> &right,
-                                 const DeviceIndex *ranks, int32_t count, int64_t k, double tol = 0.0) {
+BatchedSVD<T> recompress_batched(const DeviceMatrix<T> &left, const DeviceMatrix<T> *mid, const DeviceBuffer<typename Scalar<T>::real> *s,
+                                 const DeviceMatrix<T> &right, const DeviceIndex *ranks, int32_t count, int64_t k, double tol = 0.0) {
     const Context &ctx = left.ctx();
     const int64_t m = count > 0 ? left.nrows() / count : 0, kin = left.ncols(), n = right.ncols();
     const int64_t kk = k < kin ? k : kin, p = s && count > 0 ? (int64_t)(s->size() / (std::size_t)count) : 0;
-    BatchedSVD<T> out{DeviceMatrix<T>(ctx, (int64_t)count * m, kk), DeviceBuffer<T>(ctx, (std::size_t)count * (std::size_t)kin),
+    BatchedSVD<T> out{DeviceMatrix<T>(ctx, (int64_t)count * m, kk), DeviceBuffer<typename Scalar<T>::real>(ctx, (std::size_t)count * (std::size_t)kin),
                       DeviceMatrix<T>(ctx, (int64_t)count * kk, n), DeviceIndex(ctx, (std::size_t)count)};
     const rc_matrix none{nullptr, 0, 0, 0, 0};
     ctx.check(RecompressApi<T>::lowrank_recompress_batched(ctx.raw(), rc_matrix{left.view().data, m, kin, kin, 1}, m * kin,
                                                            mid ? rc_matrix{mid->view().data, kin, kin, kin, 1} : none, kin * kin,
                                                            s ? s->data() : nullptr, p, rc_matrix{right.view().data, kin, n, n, 1}, kin * n,
-                                                           ranks ? ranks->data() : nullptr, count, k, tol, rc_matrix{out.u.view().data, m, kk, kk, 1},
+                                                           ranks ? ranks->data() : nullptr, count, k, (typename RecompressApi<T>::tol_type)tol,
+                                                           rc_matrix{out.u.view().data, m, kk, kk, 1},
                                                            m * kk, out.s.data(), rc_matrix{out.vt.view().data, kk, n, n, 1}, kk * n, out.ranks.data()));
     return out;
 }
@@ -694,7 +698,8 @@ BatchedSVD<T> recompress_batched(const BatchedTwoSidedID<T> &id, int64_t k, doub
 }
 // rounded addition: the truncated SVD of a_i + b_i per block, from the factors [U_a U_b] diag(s_a, s_b) [Vt_a; Vt_b] of inner width
 // k_a + k_b (<= min(m, n)).  The three concatenations are batched strided copies on the device (the batched apply with an identity
-// factor copies bit for bit); the zero columns the batched SVD leaves past a block's rank come out as exactly zero singular values.
+// factor copies bit for bit; the real s of complex factors goes through the real apply); the zero columns the batched SVD leaves past a
+// block's rank come out as exactly zero singular values.
 template <typename T>
 BatchedSVD<T> recompress_batched(const BatchedSVD<T> &a, const BatchedSVD<T> &b, int64_t k, double tol = 0.0) {
     const Context &ctx = a.u.ctx();
@@ -706,12 +711,20 @@ BatchedSVD<T> recompress_batched(const BatchedSVD<T> &a, const BatchedSVD<T> &b,
     for (int64_t i = 0; i < ke; ++i) heye[(std::size_t)(i * ke + i)] = (T)1;
     const auto eye = DeviceMatrix<T>::from_host(ctx, heye.data(), ke, ke);
     DeviceMatrix<T> left(ctx, (int64_t)count * m, kin), right(ctx, (int64_t)count * kin, n);
-    DeviceBuffer<T> s(ctx, (std::size_t)count * (std::size_t)kin);
+    using Real = typename Scalar<T>::real;
+    const Real hone = (Real)1;
+    const auto one = DeviceMatrix<Real>::from_host(ctx, &hone, 1, 1);
+    DeviceBuffer<Real> s(ctx, (std::size_t)count * (std::size_t)kin);
     const rc_matrix none{nullptr, 0, 0, 0, 0};
     // dst block (rows x cols, row stride drs, batch stride dbs) = lf (rows x r) rt (r x cols): one of the two is the identity
     auto copy = [&](rc_matrix lf, int64_t lbs, rc_matrix rt, int64_t rbs, T *dst, int64_t drs, int64_t dbs) {
         ctx.check(Api<T>::lowrank_apply_batched(ctx.raw(), lf, lbs, none, 0, nullptr, 0, rt, rbs, nullptr, count, none, 0,
                                                 rc_matrix{dst, lf.rows, rt.cols, drs, 1}, dbs));
+    };
+    auto copy_s = [&](const Real *src, int64_t ks, int64_t ps, Real *dst) {  // dst row (1 x ks of kin) = [1] src row (1 x ks of ps)
+        ctx.check(Api<Real>::lowrank_apply_batched(ctx.raw(), rc_matrix{one.view().data, 1, 1, 1, 1}, 0, none, 0, nullptr, 0,
+                                                   rc_matrix{const_cast<Real *>(src), 1, ks, ps, 1}, ps, nullptr, count, none, 0,
+                                                   rc_matrix{dst, 1, ks, kin, 1}, kin));
     };
     auto id = [&](int64_t r) { return rc_matrix{eye.view().data, r, r, ke, 1}; };
     T *lp = static_cast<T *>(left.view().data), *rp = static_cast<T *>(right.view().data);
@@ -719,10 +732,10 @@ BatchedSVD<T> recompress_batched(const BatchedSVD<T> &a, const BatchedSVD<T> &b,
     copy(rc_matrix{b.u.view().data, m, kb, kb, 1}, m * kb, id(kb), 0, lp + ka, kin, m * kin);
     copy(id(ka), 0, rc_matrix{a.vt.view().data, ka, n, n, 1}, ka * n, rp, n, kin * n);
     copy(id(kb), 0, rc_matrix{b.vt.view().data, kb, n, n, 1}, kb * n, rp + ka * n, n, kin * n);
-    copy(id(1), 0, rc_matrix{a.s.data(), 1, ka, pa, 1}, pa, s.data(), kin, kin);
-    copy(id(1), 0, rc_matrix{b.s.data(), 1, kb, pb, 1}, pb, s.data() + ka, kin, kin);
+    copy_s(a.s.data(), ka, pa, s.data());
+    copy_s(b.s.data(), kb, pb, s.data() + ka);
     auto out = recompress_batched<T>(left, nullptr, &s, right, nullptr, count, k, tol);
-    ctx.synchronize();  // eye, left, right and s are freed on return
+    ctx.synchronize();  // eye, one, left, right and s are freed on return
     return out;
 }
 // the residual of every block of a batch against its stacked factors in one rank-aware call (rc_lowrank_residual_batched_*): per block the

@@ -562,7 +562,8 @@ rc_status rc_lowrank_apply_batched_c32(rc_context *ctx, rc_matrix left, int64_t 
  * call: rounded addition of low-rank blocks (U1 S1 V1^T + U2 S2 V2^T is the pair [U1 U2] diag(s1, s2) [V1^T; V2^T] of inner width
  * K = k1 + k2), the conversion of a batched column or two-sided ID into an SVD, and re-truncation.  Per block the reference's scheme
  * of SVD::to_qr and compute_from_range_estimate (src/svd.rs:150-163, :171-): factor the thin factors, take the SVD of the small core,
- * multiply back; the rank rule is SVDTraits::compress's (src/svd.rs:60-101).  Real scalars only.
+ * multiply back; the rank rule is SVDTraits::compress's (src/svd.rs:60-101).  These two are the real scalars; complex factors go
+ * through rc_lowrank_recompress_complex_batched_c64 / _c32 below.
  * Inputs as rc_lowrank_apply_batched_*: left (m x K), mid (K x K; mid.data == NULL: none), s (row i = s + i * s_stride, at least K
  * reals; NULL: none), right (K x n), in_ranks (count device values; NULL: every inner rank is K).  Block i of every operand is its
  * view moved by i times its batch stride (0 is legal for the inputs); any row and column strides; every pointer a device pointer.
@@ -591,6 +592,21 @@ rc_status rc_lowrank_apply_batched_c32(rc_context *ctx, rc_matrix left, int64_t 
  * synchronisation; workspace bounded by the grid, not by count. */
 rc_status rc_lowrank_recompress_batched_f64(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const double *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *in_ranks, int32_t count, int64_t k, double tol, rc_matrix u, int64_t u_batch_stride, double *s_out, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks);
 rc_status rc_lowrank_recompress_batched_f32(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const float *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *in_ranks, int32_t count, int64_t k, double tol, rc_matrix u, int64_t u_batch_stride, float *s_out, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks);
+/* The same call for complex factors (c64, c32): rc_lowrank_recompress_batched_f64's signature argument for argument and its contract, domain,
+ * checks and error messages, with interleaved (re, im) data and every stride and batch stride in complex elements.  s, s_out and tol have the
+ * real type of the data (double for c64, float for c32): s scales the columns of mid by real numbers, and singular values are real.
+ * A_i = left[:, :q] mid[:q, :q] diag(s[:q]) right[:q, :] with nothing conjugated, as in rc_lowrank_apply_batched_c* and
+ * rc_lowrank_residual_batched_c*; vt = V^H (so A_i ~ u diag(s_out) vt, again with nothing conjugated).  Phases as rc_svd_rank_batched_c*:
+ * in each kept column of u the first entry of largest modulus is real and positive with imaginary part exactly 0, and the matching row of
+ * vt carries the conjugate phase.  Conjugating every complex input gives the conjugates of u and vt and the same s_out and ranks, bit for
+ * bit; inputs whose imaginary parts are all zero give u and vt with imaginary parts exactly zero.  Per block: complex pivoted Householder QR
+ * of left[:, :q] and of the plain transpose right[:q, :]^T, the core R_L P_L^T mid diag(s) P_R R_R^T in complex FMAs of a fixed order,
+ * one-sided Jacobi on its conjugate transpose with the rotation tests evaluated in f64, U = Q_L [U_c; 0], vt = (Q_R [conj(V_c); 0])^T.
+ * The name: the stem is rc_lowrank_recompress_complex_batched_, not rc_lowrank_recompress_batched_ with a c64 / c32 suffix as the other
+ * families spell their complex members, because the real pair was published as "real scalars only" and callers (and the ABI test of that
+ * pair) rely on rc_lowrank_recompress_batched_c64 / _c32 not existing: a build that has this complex call is told apart by its own symbol. */
+rc_status rc_lowrank_recompress_complex_batched_c64(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const double *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *in_ranks, int32_t count, int64_t k, double tol, rc_matrix u, int64_t u_batch_stride, double *s_out, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks);
+rc_status rc_lowrank_recompress_complex_batched_c32(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const float *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *in_ranks, int32_t count, int64_t k, float tol, rc_matrix u, int64_t u_batch_stride, float *s_out, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks);
 /* The one-pass randomized column ID of every block of a batch, in one stream-ordered, capturable call: the sketch Y_i = omega_i a_i (l x n) of each
  * tall block a_i (m x n) is formed while a_i streams through the chip once, and the column ID of the small Y_i gives the pivots and Z; C is gathered
  * from a_i.  Per block this replaces the reference's randomized sequence: the projection of sample_range_by_rank (src/random_sampling.rs), then

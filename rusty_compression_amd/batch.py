@@ -393,6 +393,69 @@ def block_operator_apply(x: torch.Tensor, group_ptr, group_row, entry_block, ent
     return call.apply(x, y=y, rows=rows, accumulate=accumulate, conj=conj)
 
 
+def _lowrank_recompress_batched(who: str, complex_data: bool, left, right, k, tol, mid, s, ranks):
+    """The shared body of lowrank_recompress_batched (real dtypes) and lowrank_recompress_batched_complex (complex dtypes, real s and S)."""
+    from . import _lib
+    from .types import as_device
+
+    ops = {"left": left, "right": right, "mid": mid}
+    ops = {name: as_device(t) for name, t in ops.items() if t is not None}
+    if complex_data:
+        ops = {name: t.resolve_conj() for name, t in ops.items()}  # the kernels read the stored values
+    left, right, mid = ops["left"], ops["right"], ops.get("mid")
+    kinds = (torch.complex128, torch.complex64) if complex_data else (torch.float64, torch.float32)
+    if left.dtype not in kinds:
+        raise TypeError(f"{who}: {' or '.join(str(t).replace('torch.', '') for t in kinds)} data expected, got {left.dtype}")
+    for name, t in ops.items():
+        if t.dtype != left.dtype:
+            raise TypeError(f"{who}: {name} is {t.dtype}, left is {left.dtype}")
+    real = _lib.real_dtype(left.dtype)
+    if s is not None:
+        s = as_device(s)
+        if s.dtype != real:
+            raise TypeError(f"{who}: s is {s.dtype}, expected {real}" if complex_data else f"{who}: s is {s.dtype}, left is {left.dtype}")
+        ops["s"] = s
+    if left.dim() != 3 or right.dim() != 3 or (mid is not None and mid.dim() != 3):
+        raise AssertionError("expected left [count, m, K], right [count, K, n] and mid [count, K, K]")
+    count, m, kin = left.shape
+    n = right.shape[2]
+    for name, t in ops.items():
+        if t.shape[0] != count:
+            raise AssertionError(f"{who}: {name} holds {t.shape[0]} blocks, left {count}")
+    if s is not None:
+        if s.dim() != 2 or s.shape[1] < kin:
+            raise AssertionError(f"{who}: s must be [count, p] with p >= K = {kin}")
+        if s.stride(1) != 1:
+            s = s.contiguous()
+    if ranks is not None:
+        ranks = as_device(ranks)
+        if ranks.dtype != torch.int64:
+            raise TypeError(f"{who}: ranks is {ranks.dtype}, expected torch.int64")
+        if ranks.shape != (count,):
+            raise AssertionError(f"{who}: ranks must be [count]")
+        ranks = ranks.contiguous()
+    kk = max(min(int(k), kin), 0)
+    u = torch.empty((count, m, kk), dtype=left.dtype, device=left.device)
+    s_out = torch.empty((count, kin), dtype=real, device=left.device)
+    vt = torch.empty((count, kk, n), dtype=left.dtype, device=left.device)
+    out_ranks = torch.empty(count, dtype=torch.int64, device=left.device)
+
+    def view(t):  # block 0's view and the batch stride
+        if t is None:
+            return _lib.mat(None), ctypes.c_int64(0)
+        return _lib.rc_matrix(t.data_ptr(), t.shape[1], t.shape[2], t.stride(1), t.stride(2)), ctypes.c_int64(t.stride(0))
+
+    # the complex entry points spell their stem differently (see the header) and take tol in the real type of the data
+    stem = "rc_lowrank_recompress_complex_batched_" if complex_data else "rc_lowrank_recompress_batched_"
+    tol_arg = ctypes.c_float(float(tol)) if left.dtype == torch.complex64 else ctypes.c_double(float(tol))
+    _lib.default_context().call(stem + _lib.suffix(left.dtype), *view(left), *view(mid),
+                                ctypes.c_void_p(s.data_ptr() if s is not None else None), ctypes.c_int64(s.stride(0) if s is not None else 0),
+                                *view(right), _lib.i64p(ranks), ctypes.c_int32(count), ctypes.c_int64(int(k)), tol_arg,
+                                _lib.rc_matrix(u.data_ptr(), m, kk, kk, 1), ctypes.c_int64(m * kk), ctypes.c_void_p(s_out.data_ptr()),
+                                _lib.rc_matrix(vt.data_ptr(), kk, n, n, 1), ctypes.c_int64(kk * n), _lib.i64p(out_ranks))
+    return u, s_out, vt, out_ranks
+
+
 def lowrank_recompress_batched(left: torch.Tensor, right: torch.Tensor, k: int, tol: float = 0.0, mid: Optional[torch.Tensor] = None,
                                s: Optional[torch.Tensor] = None,
                                ranks: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -406,54 +469,21 @@ def lowrank_recompress_batched(left: torch.Tensor, right: torch.Tensor, k: int, 
     diag(s[i][:q]) right[i][:q] (absent factors omitted; nothing at an index >= q is read).  Returns U [count, m, kk], S [count, K]
     (the q singular values of A_i, descending, then zeros), Vt [count, kk, n] and the new ranks [count], kk = min(k, K): the rank of a
     block is the first j < min(kk, q) with s_j == 0 or s_j / s_0 < tol, else min(kk, q); columns of U and rows of Vt past it are zero
-    and the largest-|.| entry of each kept column of U is positive.  Complex data raises TypeError."""
-    from . import _lib
-    from .types import as_device
+    and the largest-|.| entry of each kept column of U is positive.  Complex data raises TypeError (see lowrank_recompress_batched_complex)."""
+    return _lowrank_recompress_batched("lowrank_recompress_batched", False, left, right, k, tol, mid, s, ranks)
 
-    ops = {"left": left, "right": right, "mid": mid, "s": s}
-    ops = {name: as_device(t) for name, t in ops.items() if t is not None}
-    left, right, mid, s = ops["left"], ops["right"], ops.get("mid"), ops.get("s")
-    if left.dtype not in (torch.float64, torch.float32):
-        raise TypeError(f"lowrank_recompress_batched: float64 or float32 data expected, got {left.dtype}")
-    for name, t in ops.items():
-        if t.dtype != left.dtype:
-            raise TypeError(f"lowrank_recompress_batched: {name} is {t.dtype}, left is {left.dtype}")
-    if left.dim() != 3 or right.dim() != 3 or (mid is not None and mid.dim() != 3):
-        raise AssertionError("expected left [count, m, K], right [count, K, n] and mid [count, K, K]")
-    count, m, kin = left.shape
-    n = right.shape[2]
-    for name, t in ops.items():
-        if t.shape[0] != count:
-            raise AssertionError(f"lowrank_recompress_batched: {name} holds {t.shape[0]} blocks, left {count}")
-    if s is not None:
-        if s.dim() != 2 or s.shape[1] < kin:
-            raise AssertionError(f"lowrank_recompress_batched: s must be [count, p] with p >= K = {kin}")
-        if s.stride(1) != 1:
-            s = s.contiguous()
-    if ranks is not None:
-        ranks = as_device(ranks)
-        if ranks.dtype != torch.int64:
-            raise TypeError(f"lowrank_recompress_batched: ranks is {ranks.dtype}, expected torch.int64")
-        if ranks.shape != (count,):
-            raise AssertionError("lowrank_recompress_batched: ranks must be [count]")
-        ranks = ranks.contiguous()
-    kk = max(min(int(k), kin), 0)
-    u = torch.empty((count, m, kk), dtype=left.dtype, device=left.device)
-    s_out = torch.empty((count, kin), dtype=left.dtype, device=left.device)
-    vt = torch.empty((count, kk, n), dtype=left.dtype, device=left.device)
-    out_ranks = torch.empty(count, dtype=torch.int64, device=left.device)
 
-    def view(t):  # block 0's view and the batch stride
-        if t is None:
-            return _lib.mat(None), ctypes.c_int64(0)
-        return _lib.rc_matrix(t.data_ptr(), t.shape[1], t.shape[2], t.stride(1), t.stride(2)), ctypes.c_int64(t.stride(0))
-
-    _lib.default_context().call(f"rc_lowrank_recompress_batched_{_lib.suffix(left.dtype)}", *view(left), *view(mid),
-                                ctypes.c_void_p(s.data_ptr() if s is not None else None), ctypes.c_int64(s.stride(0) if s is not None else 0),
-                                *view(right), _lib.i64p(ranks), ctypes.c_int32(count), ctypes.c_int64(int(k)), ctypes.c_double(float(tol)),
-                                _lib.rc_matrix(u.data_ptr(), m, kk, kk, 1), ctypes.c_int64(m * kk), ctypes.c_void_p(s_out.data_ptr()),
-                                _lib.rc_matrix(vt.data_ptr(), kk, n, n, 1), ctypes.c_int64(kk * n), _lib.i64p(out_ranks))
-    return u, s_out, vt, out_ranks
+def lowrank_recompress_batched_complex(left: torch.Tensor, right: torch.Tensor, k: int, tol: float = 0.0, mid: Optional[torch.Tensor] = None,
+                                       s: Optional[torch.Tensor] = None,
+                                       ranks: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """lowrank_recompress_batched for complex factors (rc_lowrank_recompress_complex_batched_c64 / _c32): left, right and mid complex128 or
+    complex64 device tensors of one dtype (lazily conjugated views are materialised), s of the matching real dtype; real data, mismatched
+    dtypes and a complex s raise TypeError.  Nothing is conjugated: A_i = left[i][:, :q] mid[i][:q, :q] diag(s[i][:q]) right[i][:q].
+    Returns U [count, m, kk] (complex), S [count, K] (the real dtype), Vt [count, kk, n] (complex, the conjugate transpose of V, so that
+    U[:, :, :r] S[:, :r] Vt[:, :r, :] is the rank-r truncation) and the new ranks.  Phase rule of svd_rank_batched_complex: in each kept
+    column of U the first of its largest-modulus entries is real and positive, its imaginary part exactly 0; conjugated inputs give the
+    conjugated U and Vt bit for bit.  For complex64 data tol is rounded to float32."""
+    return _lowrank_recompress_batched("lowrank_recompress_batched_complex", True, left, right, k, tol, mid, s, ranks)
 
 
 def column_id_to_svd_batched(c: torch.Tensor, z: torch.Tensor, ranks: Optional[torch.Tensor], k: int,
@@ -479,6 +509,29 @@ def svd_add_batched(u1: torch.Tensor, s1: torch.Tensor, vt1: torch.Tensor, u2: t
     right = torch.cat([vt1, vt2], dim=1)
     s = torch.cat([s1[:, :k1], s2[:, :k2]], dim=1)
     return lowrank_recompress_batched(left, right, k, tol, s=s)
+
+
+def column_id_to_svd_batched_complex(c: torch.Tensor, z: torch.Tensor, ranks: Optional[torch.Tensor], k: int,
+                                     tol: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """column_id_to_svd_batched for the complex outputs of column_id_rank_batched."""
+    return lowrank_recompress_batched_complex(c, z, k, tol, ranks=ranks)
+
+
+def two_sided_id_to_svd_batched_complex(c: torch.Tensor, x: torch.Tensor, r: torch.Tensor, ranks: Optional[torch.Tensor], k: int,
+                                        tol: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """two_sided_id_to_svd_batched for the complex outputs of two_sided_id_rank_batched."""
+    return lowrank_recompress_batched_complex(c, r, k, tol, mid=x, ranks=ranks)
+
+
+def svd_add_batched_complex(u1: torch.Tensor, s1: torch.Tensor, vt1: torch.Tensor, u2: torch.Tensor, s2: torch.Tensor, vt2: torch.Tensor, k: int,
+                            tol: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """svd_add_batched for the outputs of svd_rank_batched_complex or of the complex recompressions: u and vt (= V^H) complex, s real.
+    Block i of the result is the SVD of U1 diag(s1) Vt1 + U2 diag(s2) Vt2; zero columns of U1, U2 come out as exactly zero singular values."""
+    k1, k2 = u1.shape[2], u2.shape[2]
+    left = torch.cat([u1, u2], dim=2)
+    right = torch.cat([vt1, vt2], dim=1)
+    s = torch.cat([s1[:, :k1], s2[:, :k2]], dim=1)
+    return lowrank_recompress_batched_complex(left, right, k, tol, s=s)
 
 
 def _lowrank_residual_batched(who: str, complex_data: bool, a, left, right, mid, s, ranks, want_residual: bool):

@@ -1,5 +1,6 @@
 // Batched column and two-sided IDs and truncated SVDs of many small same-shaped COMPLEX matrices in one launch
-// (rc_column_id_rank_batched_c64 / _c32, rc_two_sided_id_rank_batched_c64 / _c32, rc_svd_rank_batched_c64 / _c32).
+// (rc_column_id_rank_batched_c64 / _c32, rc_two_sided_id_rank_batched_c64 / _c32, rc_svd_rank_batched_c64 / _c32), and the
+// recompression of complex low-rank factors (rc_lowrank_recompress_complex_batched_c64 / _c32, k_batched_recompress_c below).
 //
 // The structure of kernels_batched_id.hip (one persistent workgroup of 256 threads per matrix, the same three device stages, the same
 // grid and workspace rule, bid_grid) with the complex arithmetic of the lone complex path in rc_complex.hip:
@@ -394,7 +395,10 @@ __global__ __launch_bounds__(BIC_THREADS) void k_batched_two_sided_c(CView<R> a,
 // then takes the real rotation of (app, aqq, |apq|).  Everything stays inside one workgroup.
 
 // Jacobi rows per lane of a 16-lane pair group (N <= 16 NE): the complex twin of bsv_round
-template <typename R, int NE>
+// WIDE (the recompression): both threshold tests are evaluated in f64, as bsv_round's are, so that in c32 two columns of norm 1e-9 or
+// less, whose app aqq and |apq|^2 pass the smallest f32 number, are still rotated until they are orthogonal; without it the text is
+// the batched SVD's
+template <typename R, int NE, bool WIDE = false>
 __device__ __forceinline__ void bsc_round(cx<R> *G, int ldg, cx<R> *J, int ldj, int N, int p, int q, R tol, R tol2, int ll, int *flag) {
     cx<R> *gp = G + (size_t)p * ldg, *gq = G + (size_t)q * ldg;
     cx<R> a[NE], b[NE];
@@ -419,7 +423,11 @@ __device__ __forceinline__ void bsc_round(cx<R> *G, int ldg, cx<R> *J, int ldj, 
     aim = group_sum_dpp<16>(aim);
     // bsv_round's test with |apq|^2: rotate iff |apq| > tol sqrt(app aqq) (uniform over the 16 lanes)
     const R h2 = are * are + aim * aim;
-    if (!(h2 > tol2 * app * aqq)) return;
+    if constexpr (WIDE) {
+        if (!((double)are * (double)are + (double)aim * (double)aim > (double)tol2 * (double)app * (double)aqq)) return;
+    } else {
+        if (!(h2 > tol2 * app * aqq)) return;
+    }
     const double hd = sqrt((double)are * (double)are + (double)aim * (double)aim), ih = 1.0 / hd;
     const cx<R> ph{(R)((double)are * ih), (R)(-((double)aim * ih))};  // e^{-i phi}
     double cd, sd;
@@ -438,12 +446,17 @@ __device__ __forceinline__ void bsc_round(cx<R> *G, int ldg, cx<R> *J, int ldj, 
             vq[i] = cx<R>{s * x.re + c * y.re, s * x.im + c * y.im};
         }
     }
-    if (ll == 0 && (h2 > tol * (R)0.0625 * app * aqq || s * s > (R)16 * tol)) *flag = 2;  // plain store: every writer writes 2
+    if constexpr (WIDE) {
+        if (ll == 0 && ((double)are * (double)are + (double)aim * (double)aim > (double)tol * 0.0625 * (double)app * (double)aqq || s * s > (R)16 * tol))
+            *flag = 2;
+    } else {
+        if (ll == 0 && (h2 > tol * (R)0.0625 * app * aqq || s * s > (R)16 * tol)) *flag = 2;  // plain store: every writer writes 2
+    }
 }
 
 // bsv_jacobi's schedule (round-robin pairs, 16 lanes per pair, one barrier per round, kMaxSweeps) on the complex core.  Returns false
 // when the sweep budget ran out before a quiet sweep.
-template <typename R, int NE>
+template <typename R, int NE, bool WIDE = false>
 __device__ __forceinline__ bool bsc_jacobi(cx<R> *G, int ldg, cx<R> *J, int ldj, int N, int tid, int *flag) {
     const int ll = tid & 15, grp = tid >> 4;
     constexpr int NGRP = BIC_THREADS / 16;
@@ -456,7 +469,7 @@ __device__ __forceinline__ bool bsc_jacobi(cx<R> *G, int ldg, cx<R> *J, int ldj,
             for (int pi = grp; pi < npairs; pi += NGRP) {
                 int p, q;
                 rr_pair(N2, r, pi, p, q);
-                if (q < N) bsc_round<R, NE>(G, ldg, J, ldj, N, p, q, tol, tol2, ll, flag);  // q == N: the dummy column of an odd N
+                if (q < N) bsc_round<R, NE, WIDE>(G, ldg, J, ldj, N, p, q, tol, tol2, ll, flag);  // q == N: the dummy column of an odd N
             }
             __syncthreads();  // the pairs of a round are disjoint; the next round re-pairs the columns
         }
@@ -712,6 +725,221 @@ __global__ __launch_bounds__(BIC_THREADS) void k_batched_svd_c(CView<R> a, int64
     }
 }
 
+// ---- batched recompression of complex low-rank factors (rc_lowrank_recompress_complex_batched_c64 / _c32) ----------------------
+// k_batched_recompress's stages with the arithmetic above.  Per block, with q = in_ranks[b] clamped to [0, K]:
+// A = left[:, :q] mid[:q, :q] diag(s[:q]) right[:q, :] (nothing conjugated, s real) is never formed.  The two thin factors are
+// factored where they stand, left[:, :q] P_L = Q_L R_L and the PLAIN transpose right[:q, :]^T P_R = Q_R R_R (bic_qrcp to q steps
+// each, reflectors and the complex taus kept).  With Rl = R_L P_L^T and Rr = R_R P_R^T:
+//     left = Q_L Rl,  right = Rr^T Q_R^T,  A = Q_L C Q_R^T,  C = Rl mid diag(s) Rr^T   (q x q, no conjugate anywhere).
+// One-sided Jacobi on G = C^H with the rotations in J: G J = V_c Sigma, so C = J Sigma V_c^H and
+//     A = (Q_L J) Sigma (conj(Q_R) V_c)^H:  U = Q_L [J; 0],  vt = V^H = V_c^H Q_R^T = (Q_R conj(V_c))^T.
+// The transpose rather than right^H: vt is then the transposed view of Q_R [conj(V_c); 0], which bsc_form_u writes as it stands once
+// the kept columns of G are conjugated in the 1 / sigma scaling pass; with u's phases, u_c -> u_c ph_c needs vt's row c times
+// conj(ph_c), which is what bsc_form_u(phase_here = false) multiplies by.  Factoring right^H instead would need a conjugating store.
+// G = C^H, not C: an exactly zero column of left is pivoted last and is a step with H = I, which leaves a zero row in R_L, hence a
+// zero row of C = a zero column of G, and the rotation test (false for apq = 0) never touches a zero column: its singular value
+// comes out as exactly 0.
+//
+// The core is formed by two q x q x q products, one thread per element, summed over the inner index in ascending order, each term one
+// complex FMA in a fixed order (re += a.re b.re, re -= a.im b.im, im += a.re b.im, im += a.im b.re):
+//   T1[a, j] = sum_b (mid[a, b] s[b]) Rr[j, b]   (T1 in J's place: J = I only afterwards)
+//   C[i, j]  = sum_a Rl[i, a] T1[a, j]           (stored conjugated as G[i * ldg + j]: column i of G = conj(row i of C))
+// where Rl[:, c] is the upper-triangular column the factorization keeps for the factor's own column c (rows 0 .. ip[c] of the
+// working copy's column c, ip the inverse of the pivot order), Rr likewise.  The lanes run along j: T1, Wr and G are read and
+// written at consecutive addresses and mid[a, b], Rl[i, a] are one broadcast address per wave.
+// The Jacobi's threshold tests are evaluated in f64 (bsc_round's WIDE), as the real recompression's are.
+
+template <typename R>
+struct BrcCArgs {
+    CView<R> left, mid, right, u, vt;
+    int64_t lbs, mbs, rbs, ubs, vbs, s_stride;
+    const R *s;
+    const int64_t *in_ranks;
+    R *s_out;
+    int64_t *ranks;
+    cx<R> *ws;
+    int *health;
+    double tol;
+    int count, k, ldg;
+    bool l_lds, r_lds, v_lds, g_lds;  // the copy of left / of right^T / the rotations J / the core G in LDS (else in the workspace slot)
+};
+
+// LDS: [Wl: K x (m|1)] [Wr: K x (n|1)] [G: K x ldg] [J: K x ldg] (each only when its flag is set) taul[K] taur[K] phs[128] complex
+// | vn1[K] vn2[K] sig[K] red[8] real | jpl[K] jpr[K] ipl[K] ipr[K] srt[K] flag[4]
+template <typename R>
+size_t brcc_lds_bytes(int m, int n, int K, int ldg, bool l_lds, bool r_lds, bool v_lds, bool g_lds) {
+    size_t c = (size_t)2 * K + 128;
+    if (l_lds) c += (size_t)K * (size_t)(m | 1);
+    if (r_lds) c += (size_t)K * (size_t)(n | 1);
+    if (g_lds) c += (size_t)K * ldg;
+    if (v_lds) c += (size_t)K * ldg;
+    return c * sizeof(cx<R>) + ((size_t)3 * K + 8) * sizeof(R) + (size_t)(5 * K + 4) * sizeof(int);
+}
+// complex elements of one workgroup's workspace slot: Wl (m x K), Wr (n x K), G (K x ldg), J (K x K), each unless it is in LDS
+__host__ __device__ inline size_t brcc_ws_elems(int m, int n, int K, int ldg, bool l_lds, bool r_lds, bool v_lds, bool g_lds) {
+    return (l_lds ? 0 : (size_t)m * K) + (r_lds ? 0 : (size_t)n * K) + (g_lds ? 0 : (size_t)K * ldg) + (v_lds ? 0 : (size_t)K * K);
+}
+
+// acc += a b, one complex FMA in the fixed order of the comment above
+template <typename R> __device__ __forceinline__ void cfma(cx<R> a, cx<R> b, cx<R> &acc) {
+    acc.re = fma(a.re, b.re, acc.re);
+    acc.re = fma(-a.im, b.im, acc.re);
+    acc.im = fma(a.re, b.im, acc.im);
+    acc.im = fma(a.im, b.re, acc.im);
+}
+
+template <typename R>
+__global__ __launch_bounds__(BIC_THREADS, 2) void k_batched_recompress_c(BrcCArgs<R> a) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const int m = (int)a.left.rows, n = (int)a.right.cols, K = (int)a.left.cols;
+    const int kk = a.k < K ? a.k : K, ldg = a.ldg;
+    const int ldl = a.l_lds ? (m | 1) : m, ldr = a.r_lds ? (n | 1) : n, ldj = a.v_lds ? ldg : K;
+    cx<R> *lp = reinterpret_cast<cx<R> *>(smem_raw);                                                                // next free LDS element
+    cx<R> *wp = a.ws + (size_t)blockIdx.x * brcc_ws_elems(m, n, K, ldg, a.l_lds, a.r_lds, a.v_lds, a.g_lds);      // next free workspace element
+    cx<R> *Wl, *Wr, *G, *J;
+    if (a.l_lds) { Wl = lp; lp += (size_t)K * ldl; } else { Wl = wp; wp += (size_t)m * K; }
+    if (a.r_lds) { Wr = lp; lp += (size_t)K * ldr; } else { Wr = wp; wp += (size_t)n * K; }
+    if (a.g_lds) { G = lp; lp += (size_t)K * ldg; } else { G = wp; wp += (size_t)K * ldg; }
+    if (a.v_lds) { J = lp; lp += (size_t)K * ldj; } else { J = wp; }
+    cx<R> *taul = lp, *taur = taul + K, *phs = taur + K;
+    R *vn1 = reinterpret_cast<R *>(phs + 128);
+    R *vn2 = vn1 + K, *sig = vn2 + K, *red = sig + K;
+    int *jpl = reinterpret_cast<int *>(red + 8);
+    int *jpr = jpl + K, *ipl = jpr + K, *ipr = ipl + K, *srt = ipr + K, *flag = srt + K;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+
+    for (int b = blockIdx.x; b < a.count; b += gridDim.x) {
+        int q = K;
+        if (a.in_ranks) {
+            const int64_t rv = a.in_ranks[b];
+            q = rv < 0 ? 0 : rv > K ? K : (int)rv;
+        }
+        q = __builtin_amdgcn_readfirstlane(q);  // one value per block, uniform by construction
+        R *sb = a.s_out + (int64_t)b * K;
+        cx<R> *Ub = a.u.p + (int64_t)b * a.ubs, *Vb = a.vt.p + (int64_t)b * a.vbs;
+        for (int i = q + tid; i < K; i += BIC_THREADS) sb[i] = (R)0;
+        if (q == 0) {  // uniform over the workgroup; no input is read
+            if (tid == 0) a.ranks[b] = 0;
+            for (int c = wv; c < kk; c += BIC_WAVES) {
+                for (int i = lane; i < m; i += 64) Ub[i * a.u.rs + c * a.u.cs] = czero<R>();
+                for (int i = lane; i < n; i += 64) Vb[c * a.vt.rs + i * a.vt.cs] = czero<R>();
+            }
+            continue;
+        }
+        // ---- the two pivoted QRs, q steps each (exact zero pivots are steps with H = I), taus and pivots kept -----------------------
+        const cx<R> *__restrict__ L = a.left.p + (int64_t)b * a.lbs;
+        const cx<R> *__restrict__ Rt = a.right.p + (int64_t)b * a.rbs;
+        bic_load(Wl, ldl, m, q, a.left.rs <= a.left.cs, [&](int i, int c) { return L[i * a.left.rs + c * a.left.cs]; }, vn1, vn2, jpl, wv, lane);
+        bic_qrcp<R, true>(Wl, ldl, m, q, q, 0.0, jpl, vn1, vn2, red, tid, wv, lane, taul);
+        bic_load(Wr, ldr, n, q, a.right.cs <= a.right.rs, [&](int i, int c) { return Rt[c * a.right.rs + i * a.right.cs]; }, vn1, vn2, jpr, wv, lane);
+        bic_qrcp<R, true>(Wr, ldr, n, q, q, 0.0, jpr, vn1, vn2, red, tid, wv, lane, taur);
+        for (int j = tid; j < q; j += BIC_THREADS) { ipl[jpl[j]] = j; ipr[jpr[j]] = j; }
+        __syncthreads();
+        // ---- T1 = mid diag(s) Rr^T in J's place ----------------------------------------------------------------------------------------
+        const cx<R> *__restrict__ Mb = a.mid.p ? a.mid.p + (int64_t)b * a.mbs : nullptr;
+        const R *__restrict__ Sb = a.s ? a.s + (int64_t)b * a.s_stride : nullptr;
+        for (int idx = tid; idx < q * q; idx += BIC_THREADS) {
+            const int ai = idx / q, j = idx - ai * q;
+            cx<R> acc;
+            if (Mb) {
+                acc = czero<R>();
+                const cx<R> *mr = Mb + (int64_t)ai * a.mid.rs;
+                for (int bb = 0; bb < q; ++bb) {
+                    const cx<R> rv = j <= ipr[bb] ? Wr[(size_t)bb * ldr + j] : czero<R>();
+                    cx<R> mv = mr[(int64_t)bb * a.mid.cs];
+                    if (Sb) { const R sv = Sb[bb]; mv = cx<R>{mv.re * sv, mv.im * sv}; }
+                    cfma(mv, rv, acc);
+                }
+            } else {
+                const cx<R> rv = j <= ipr[ai] ? Wr[(size_t)ai * ldr + j] : czero<R>();
+                acc = rv;
+                if (Sb) { const R sv = Sb[ai]; acc = cx<R>{sv * rv.re, sv * rv.im}; }
+            }
+            J[(size_t)ai * ldj + j] = acc;
+        }
+        __syncthreads();
+        // ---- G = C^H: G[i * ldg + j] = conj(sum_a Rl[i, a] T1[a, j]) ------------------------------------------------------------------
+        for (int idx = tid; idx < q * q; idx += BIC_THREADS) {
+            const int i = idx / q, j = idx - i * q;
+            cx<R> acc = czero<R>();
+            for (int aa = 0; aa < q; ++aa) {
+                const cx<R> lv = i <= ipl[aa] ? Wl[(size_t)aa * ldl + i] : czero<R>();
+                cfma(lv, J[(size_t)aa * ldj + j], acc);
+            }
+            G[(size_t)i * ldg + j] = conj_of(acc);
+        }
+        __syncthreads();
+        for (int idx = tid; idx < q * q; idx += BIC_THREADS) {
+            const int j = idx / q, i = idx - j * q;
+            J[(size_t)j * ldj + i] = i == j ? cone<R>() : czero<R>();
+        }
+        __syncthreads();
+        bool conv;
+        if (q <= 16) conv = bsc_jacobi<R, 1, true>(G, ldg, J, ldj, q, tid, flag);
+        else if (q <= 32) conv = bsc_jacobi<R, 2, true>(G, ldg, J, ldj, q, tid, flag);
+        else if (q <= 64) conv = bsc_jacobi<R, 4, true>(G, ldg, J, ldj, q, tid, flag);
+        else conv = bsc_jacobi<R, 8, true>(G, ldg, J, ldj, q, tid, flag);
+        if (!conv && tid == 0) atomicOr(a.health, 16);  // the sweep budget ran out: bit 16, as the batched SVD reports it
+        // ---- singular values: column norms, sorted descending (a strict total order: NaN last, ties by column) ----------------------
+        for (int j = tid >> 4; j < q; j += BIC_THREADS / 16) {
+            const cx<R> *gj = G + (size_t)j * ldg;
+            R acc = 0;
+            for (int i = tid & 15; i < q; i += 16) {
+                acc = fma(gj[i].re, gj[i].re, acc);
+                acc = fma(gj[i].im, gj[i].im, acc);
+            }
+            acc = group_sum_dpp<16>(acc);
+            if ((tid & 15) == 0) sig[j] = sqrt(acc);
+        }
+        __syncthreads();
+        for (int i = tid; i < q; i += BIC_THREADS) {
+            const R ki = sig[i] >= (R)0 ? sig[i] : (R)-1;
+            int pos = 0;
+            for (int j = 0; j < q; ++j) {
+                const R kj = sig[j] >= (R)0 ? sig[j] : (R)-1;
+                pos += (kj > ki || (kj == ki && j < i)) ? 1 : 0;
+            }
+            srt[pos] = i;
+            sb[pos] = sig[i];
+        }
+        __syncthreads();
+        // ---- rank: the first j < min(kk, q) with s_j == 0 or (tol > 0 and s_j / s_0 < tol), else min(kk, q) -------------------------
+        if (tid == 0) {
+            const R s0 = sig[srt[0]];
+            const int kq = kk < q ? kk : q;
+            int r = kq;
+            for (int j = 0; j < kq; ++j) {
+                const R sj = sig[srt[j]];
+                if (sj == (R)0 || (a.tol > 0.0 && (double)(sj / s0) < a.tol)) { r = j; break; }
+            }
+            flag[1] = r;
+            a.ranks[b] = r;
+        }
+        __syncthreads();
+        const int r = flag[1];
+        // ---- U = Q_L [J_r; 0] with the phase rule applied to its columns, the phases kept in phs ------------------------------------------
+        if (m <= 64) bsc_form_u<R, 1>(Wl, ldl, J, ldj, m, q, kk, r, jpl, taul, srt, phs, true, Ub, a.u.rs, a.u.cs, wv, lane);
+        else if (m <= 128) bsc_form_u<R, 2>(Wl, ldl, J, ldj, m, q, kk, r, jpl, taul, srt, phs, true, Ub, a.u.rs, a.u.cs, wv, lane);
+        else if (m <= 256) bsc_form_u<R, 4>(Wl, ldl, J, ldj, m, q, kk, r, jpl, taul, srt, phs, true, Ub, a.u.rs, a.u.cs, wv, lane);
+        else bsc_form_u<R, 8>(Wl, ldl, J, ldj, m, q, kk, r, jpl, taul, srt, phs, true, Ub, a.u.rs, a.u.cs, wv, lane);
+        // ---- conj(V_c) = conj(G Sigma^-1) in place (kept columns), then vt^T = Q_R [conj(V_c); 0] conj(ph) through vt's transposed view ---
+        for (int c = wv; c < r; c += BIC_WAVES) {
+            cx<R> *gc = G + (size_t)srt[c] * ldg;
+            const R sj = sig[srt[c]], inv = sj > (R)0 ? (R)1 / sj : (R)0;
+            for (int i = lane; i < q; i += 64) {
+                const cx<R> g = gc[i];
+                gc[i] = cx<R>{g.re * inv, -(g.im * inv)};
+            }
+        }
+        __syncthreads();  // phs and the scaled columns are read by other waves below
+        if (n <= 64) bsc_form_u<R, 1>(Wr, ldr, G, ldg, n, q, kk, r, jpr, taur, srt, phs, false, Vb, a.vt.cs, a.vt.rs, wv, lane);
+        else if (n <= 128) bsc_form_u<R, 2>(Wr, ldr, G, ldg, n, q, kk, r, jpr, taur, srt, phs, false, Vb, a.vt.cs, a.vt.rs, wv, lane);
+        else if (n <= 256) bsc_form_u<R, 4>(Wr, ldr, G, ldg, n, q, kk, r, jpr, taur, srt, phs, false, Vb, a.vt.cs, a.vt.rs, wv, lane);
+        else bsc_form_u<R, 8>(Wr, ldr, G, ldg, n, q, kk, r, jpr, taur, srt, phs, false, Vb, a.vt.cs, a.vt.rs, wv, lane);
+        __syncthreads();  // the working copies, G, J and the small arrays are rewritten by the next block
+    }
+}
+
 }  // namespace
 
 // the real kernels' launch rule (bid_grid, BID_MAX_LDS): LDS variant when the complex working copy fits, else the workspace variant
@@ -811,6 +1039,52 @@ void batched_svd_c(rc_context *c, const rc_matrix &a_, int64_t abs, int32_t coun
                        c->health_word(), ldg);
 }
 
+// where the two working copies Wl (m x K), Wr (n x K), the rotations J and the core G (K x K) live: batched_lowrank_recompress's plan
+// list (most in LDS first, the padded core pitch before the odd one, the larger copy to the workspace first) with the fourth
+// placement batched_svd_c has: a complex core that does not fit in LDS at either pitch (c64, K >= 100) goes to the workgroup's slot
+// of the grid-bounded workspace with everything else, at pitch K.  One kernel: the plan only moves base pointers and pitches, and no
+// sum depends on a pitch, so it cannot change a block's bits.
+template <typename R>
+void batched_lowrank_recompress_c(rc_context *c, const rc_matrix &left_, int64_t lbs, const rc_matrix &mid_, int64_t mbs, const R *s, int64_t s_stride,
+                                  const rc_matrix &right_, int64_t rbs, const int64_t *in_ranks, int32_t count, int64_t k, double tol, const rc_matrix &u_,
+                                  int64_t ubs, R *s_out, const rc_matrix &vt_, int64_t vbs, int64_t *ranks) {
+    const CView<R> left = cview<R>(left_), mid = cview<R>(mid_), right = cview<R>(right_), u = cview<R>(u_), vt = cview<R>(vt_);
+    const int m = (int)left.rows, n = (int)right.cols, K = (int)left.cols;
+    if (count <= 0) return;
+    const int pad = ((K + 15) / 32) * 32 + 16, odd = K | 1;
+    const bool big_l = m >= n;  // the copy that leaves LDS first
+    const struct { bool l, r, v, g; int ld; } plans[] = {{true, true, true, true, pad},      {true, true, true, true, odd},     {!big_l, big_l, true, true, pad},
+                                                         {!big_l, big_l, true, true, odd},   {false, false, true, true, pad},   {false, false, true, true, odd},
+                                                         {false, false, false, true, pad},   {false, false, false, true, odd},  {false, false, false, false, K}};
+    int pi = 0;
+    while (pi < 8 && brcc_lds_bytes<R>(m, n, K, plans[pi].ld, plans[pi].l, plans[pi].r, plans[pi].v, plans[pi].g) > BID_MAX_LDS) ++pi;
+    const bool l_lds = plans[pi].l, r_lds = plans[pi].r, v_lds = plans[pi].v, g_lds = plans[pi].g;
+    const int ldg = plans[pi].ld;
+    const size_t lds = brcc_lds_bytes<R>(m, n, K, ldg, l_lds, r_lds, v_lds, g_lds);
+    RC_REQUIRE(lds <= BID_MAX_LDS, RC_RUNTIME_ERROR, "lowrank_recompress_batched: %zu bytes of LDS", lds);
+    const void *kern = reinterpret_cast<const void *>(k_batched_recompress_c<R>);
+    static bool attr_set[64] = {};
+    if (!attr_set[c->device & 63]) {
+        RC_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BID_MAX_LDS));
+        attr_set[c->device & 63] = true;
+    }
+    const size_t per = brcc_ws_elems(m, n, K, ldg, l_lds, r_lds, v_lds, g_lds);
+    int64_t slots = 0;
+    const int64_t grid = bid_grid(c, kern, lds, per * sizeof(cx<R>), count, &slots);
+    ProfScope ps(c, "op:batched_recompress<complex> %dx%d k=%d count=%d grid=%lld slots=%lld plan=L:%s,R:%s,V:%s,G:%s,ld=%d,kk=%d%s%s", m, n, K, (int)count,
+                 (long long)grid, (long long)slots, l_lds ? "lds" : "ws", r_lds ? "lds" : "ws", v_lds ? "lds" : "ws", g_lds ? "lds" : "ws", ldg,
+                 (int)std::min<int64_t>(k, K), mid.p ? ",mid" : "", s ? ",s" : "");
+    BrcCArgs<R> a;
+    a.left = left; a.mid = mid; a.right = right; a.u = u; a.vt = vt;
+    a.lbs = lbs; a.mbs = mbs; a.rbs = rbs; a.ubs = ubs; a.vbs = vbs; a.s_stride = s_stride;
+    a.s = s; a.in_ranks = in_ranks; a.s_out = s_out; a.ranks = ranks;
+    a.ws = per ? c->alloc<cx<R>>((size_t)grid * per) : nullptr;
+    a.health = c->health_word();
+    a.tol = tol; a.count = (int)count; a.k = (int)std::min<int64_t>(k, K); a.ldg = ldg;
+    a.l_lds = l_lds; a.r_lds = r_lds; a.v_lds = v_lds; a.g_lds = g_lds;
+    hipLaunchKernelGGL(k_batched_recompress_c<R>, dim3((unsigned)grid), dim3(BIC_THREADS), lds, c->stream, a);
+}
+
 template void batched_column_id_c<double>(rc_context *, const rc_matrix &, int64_t, int32_t, int64_t, double, const rc_matrix &, int64_t, const rc_matrix &,
                                           int64_t, int64_t *, int64_t *);
 template void batched_column_id_c<float>(rc_context *, const rc_matrix &, int64_t, int32_t, int64_t, double, const rc_matrix &, int64_t, const rc_matrix &,
@@ -824,5 +1098,12 @@ template void batched_svd_c<double>(rc_context *, const rc_matrix &, int64_t, in
                                     const rc_matrix &, int64_t, int64_t *);
 template void batched_svd_c<float>(rc_context *, const rc_matrix &, int64_t, int32_t, int64_t, double, const rc_matrix &, int64_t, float *,
                                    const rc_matrix &, int64_t, int64_t *);
+
+template void batched_lowrank_recompress_c<double>(rc_context *, const rc_matrix &, int64_t, const rc_matrix &, int64_t, const double *, int64_t,
+                                                   const rc_matrix &, int64_t, const int64_t *, int32_t, int64_t, double, const rc_matrix &, int64_t, double *,
+                                                   const rc_matrix &, int64_t, int64_t *);
+template void batched_lowrank_recompress_c<float>(rc_context *, const rc_matrix &, int64_t, const rc_matrix &, int64_t, const float *, int64_t,
+                                                  const rc_matrix &, int64_t, const int64_t *, int32_t, int64_t, double, const rc_matrix &, int64_t, float *,
+                                                  const rc_matrix &, int64_t, int64_t *);
 
 }  // namespace rc

@@ -1223,6 +1223,32 @@ BlockShape check_block_operator_apply(Mat<T> left, Mat<T> mid, Mat<T> right, int
     return sh;
 }
 
+// rc_lowrank_recompress_batched_* and its complex twin: the shapes of the factor chain left (m x K) [mid (K x K)] right (K x n) against u (m x min(k, K))
+// and vt (min(k, K) x n)
+template <typename T>
+void check_lowrank_recompress_batched(Mat<T> left, Mat<T> mid, Mat<T> right, int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs, const T *s_out,
+                                      Mat<T> vt, int64_t vbs, const int64_t *ranks) {
+    const char *who = "lowrank_recompress_batched";
+    const int64_t m = left.rows, K = left.cols, n = right.cols;
+    RC_REQUIRE(count >= 0, RC_INVALID_ARGUMENT, "%s: count = %d < 0", who, (int)count);
+    RC_REQUIRE(m >= 1 && m <= 512 && n >= 1 && n <= 512 && K >= 1 && K <= 128 && k >= 1, RC_INVALID_ARGUMENT,
+               "%s: needs 1 <= m, n <= 512, inner width 1 <= K <= 128 and k >= 1 (got left %lld x %lld, right %lld x %lld, k = %lld)", who, (long long)m,
+               (long long)K, (long long)right.rows, (long long)n, (long long)k);
+    RC_REQUIRE(right.rows == K, RC_INVALID_ARGUMENT, "%s: left is %lld x %lld but right has %lld rows", who, (long long)m, (long long)K, (long long)right.rows);
+    RC_REQUIRE(K <= std::min(m, n), RC_INVALID_ARGUMENT,
+               "%s: needs K <= min(m, n) (got K = %lld for %lld x %lld blocks); rebuild the blocks with rc_lowrank_apply_batched_* and use rc_svd_rank_batched_*",
+               who, (long long)K, (long long)m, (long long)n);
+    RC_REQUIRE(tol < 1.0 && 0.0 <= tol, RC_INVALID_ARGUMENT, "Require 0 <= tol < 1.0");
+    RC_REQUIRE(!mid.p || (mid.rows == K && mid.cols == K), RC_INVALID_ARGUMENT, "%s: mid must be %lld x %lld (got %lld x %lld)", who, (long long)K,
+               (long long)K, (long long)mid.rows, (long long)mid.cols);
+    const int64_t kk = std::min(k, K);
+    RC_REQUIRE(u.rows == m && u.cols == kk && vt.rows == kk && vt.cols == n, RC_INVALID_ARGUMENT,
+               "%s: u must be %lld x %lld and vt %lld x %lld (k clamped to K)", who, (long long)m, (long long)kk, (long long)kk, (long long)n);
+    check_batch_stride(who, "u", ubs, u, count);
+    check_batch_stride(who, "vt", vbs, vt, count);
+    if (count > 0) RC_REQUIRE(left.p && right.p && u.p && s_out && vt.p && ranks, RC_INVALID_ARGUMENT, "%s: null pointer", who);
+}
+
 template int64_t check_column_id_rank_batched<double>(Mat<double>, int32_t, int64_t, double, Mat<double>, int64_t, Mat<double>, int64_t, const int64_t *,
                                                       const int64_t *);
 template int64_t check_column_id_rank_batched<float>(Mat<float>, int32_t, int64_t, double, Mat<float>, int64_t, Mat<float>, int64_t, const int64_t *,
@@ -1242,6 +1268,10 @@ template BlockShape check_block_operator_apply<float>(Mat<float>, Mat<float>, Ma
                                                       Mat<float>);
 template void check_lowrank_residual_batched<double>(Mat<double>, Mat<double>, Mat<double>, Mat<double>, int32_t, Mat<double>, int64_t, const double *);
 template void check_lowrank_residual_batched<float>(Mat<float>, Mat<float>, Mat<float>, Mat<float>, int32_t, Mat<float>, int64_t, const float *);
+template void check_lowrank_recompress_batched<double>(Mat<double>, Mat<double>, Mat<double>, int32_t, int64_t, double, Mat<double>, int64_t, const double *,
+                                                       Mat<double>, int64_t, const int64_t *);
+template void check_lowrank_recompress_batched<float>(Mat<float>, Mat<float>, Mat<float>, int32_t, int64_t, double, Mat<float>, int64_t, const float *, Mat<float>,
+                                                      int64_t, const int64_t *);
 
 }  // namespace rc
 
@@ -1300,25 +1330,7 @@ template <typename T>
 void lowrank_recompress_batched(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride, Mat<T> right, int64_t rbs,
                                 const int64_t *in_ranks, int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs, T *s_out, Mat<T> vt, int64_t vbs,
                                 int64_t *ranks) {
-    const char *who = "lowrank_recompress_batched";
-    const int64_t m = left.rows, K = left.cols, n = right.cols;
-    RC_REQUIRE(count >= 0, RC_INVALID_ARGUMENT, "%s: count = %d < 0", who, (int)count);
-    RC_REQUIRE(m >= 1 && m <= 512 && n >= 1 && n <= 512 && K >= 1 && K <= 128 && k >= 1, RC_INVALID_ARGUMENT,
-               "%s: needs 1 <= m, n <= 512, inner width 1 <= K <= 128 and k >= 1 (got left %lld x %lld, right %lld x %lld, k = %lld)", who, (long long)m,
-               (long long)K, (long long)right.rows, (long long)n, (long long)k);
-    RC_REQUIRE(right.rows == K, RC_INVALID_ARGUMENT, "%s: left is %lld x %lld but right has %lld rows", who, (long long)m, (long long)K, (long long)right.rows);
-    RC_REQUIRE(K <= std::min(m, n), RC_INVALID_ARGUMENT,
-               "%s: needs K <= min(m, n) (got K = %lld for %lld x %lld blocks); rebuild the blocks with rc_lowrank_apply_batched_* and use rc_svd_rank_batched_*",
-               who, (long long)K, (long long)m, (long long)n);
-    RC_REQUIRE(tol < 1.0 && 0.0 <= tol, RC_INVALID_ARGUMENT, "Require 0 <= tol < 1.0");
-    RC_REQUIRE(!mid.p || (mid.rows == K && mid.cols == K), RC_INVALID_ARGUMENT, "%s: mid must be %lld x %lld (got %lld x %lld)", who, (long long)K,
-               (long long)K, (long long)mid.rows, (long long)mid.cols);
-    const int64_t kk = std::min(k, K);
-    RC_REQUIRE(u.rows == m && u.cols == kk && vt.rows == kk && vt.cols == n, RC_INVALID_ARGUMENT,
-               "%s: u must be %lld x %lld and vt %lld x %lld (k clamped to K)", who, (long long)m, (long long)kk, (long long)kk, (long long)n);
-    check_batch_stride(who, "u", ubs, u, count);
-    check_batch_stride(who, "vt", vbs, vt, count);
-    if (count > 0) RC_REQUIRE(left.p && right.p && u.p && s_out && vt.p && ranks, RC_INVALID_ARGUMENT, "%s: null pointer", who);
+    check_lowrank_recompress_batched(left, mid, right, count, k, tol, u, ubs, s_out, vt, vbs, ranks);
     if (count == 0) return;
     batched_lowrank_recompress(c, left, lbs, mid, mbs, s, s_stride, right, rbs, in_ranks, count, k, tol, u, ubs, s_out, vt, vbs, ranks);
 }

@@ -1417,6 +1417,21 @@ extern "C" {
             batched_lowrank_residual_c<R>(ctx, a, a_batch_stride, left, left_batch_stride, mid, mid_batch_stride, s, s_stride, right,     \
                                           right_batch_stride, ranks, count, e, e_batch_stride, err, nrm);                                 \
         });                                                                                                                               \
+    }                                                                                                                                     \
+    /* recompress the complex factors of a batch to truncated SVDs (kernels_batched_id_c.hip): the real entry point's checks on views */  \
+    /* of the same shapes; s, s_out and tol in the real type, vt = V^H */                                                                 \
+    rc_status rc_lowrank_recompress_complex_batched_##SUF(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid,      \
+                                                          int64_t mid_batch_stride, const R *s, int64_t s_stride, rc_matrix right,        \
+                                                          int64_t right_batch_stride, const int64_t *in_ranks, int32_t count, int64_t k,  \
+                                                          R tol, rc_matrix u, int64_t u_batch_stride, R *s_out, rc_matrix vt,             \
+                                                          int64_t vt_batch_stride, int64_t *ranks) {                                      \
+        return guarded_c(ctx, [&] {                                                                                                       \
+            check_lowrank_recompress_batched<R>(shape_of<R>(left), shape_of<R>(mid), shape_of<R>(right), count, k, (double)tol,           \
+                                                shape_of<R>(u), u_batch_stride, s_out, shape_of<R>(vt), vt_batch_stride, ranks);          \
+            if (count == 0) return;                                                                                                       \
+            batched_lowrank_recompress_c<R>(ctx, left, left_batch_stride, mid, mid_batch_stride, s, s_stride, right, right_batch_stride,  \
+                                            in_ranks, count, k, (double)tol, u, u_batch_stride, s_out, vt, vt_batch_stride, ranks);       \
+        });                                                                                                                               \
     }
 
 RC_DEFINE_COMPLEX(c64, double, rc_complex64)
