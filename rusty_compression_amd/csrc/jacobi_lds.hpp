@@ -147,22 +147,17 @@ __device__ inline bool jacobi_rotation_was_large(T app, T aqq, T apq, T s, T tol
 //  J3  epoch is a per-context device counter, started at a pseudo-random 23-bit value, read by both workgroups at their start and
 //      incremented by the consumer at its very end; launches of one context are stream ordered, so every launch sees a new epoch.
 //  J4  The small hand-over words vsync[0] (number of sweeps) and vsync[1 + j] (sorted position + 1) travel as (epoch << 8) | payload
-//      AND are cleared (k_clear_words / fill_words, same stream, in front) before every launch: payload 0 means "not there yet".
+//      AND are cleared on the same stream in front of every launch (fill_words for k_jacobi_lds; for k_wq_jacobi_fused the gate
+//      kernel of its cooperative role, k_coop_gate, clears them with the header words): payload 0 means "not there yet".
 //  J5  The consumer learns that sweep s exists from the first record of sweep s validating, and that it does not from
 //      vsync[0] <= s; the producer writes exactly one of the two after sweep s - 1.  Index of a record: (sweep, round, pair slot),
-//      the same expression on both sides (FULL: pair slot = group + k * number of groups, k < SLOTS).
+//      the same expression on both sides.
 //  J6  Every consumer spin is bounded (kSpin); on expiry health bit 8 is raised and V is reported incomplete -- never silently wrong.
-//   FULL   : n == 16 * NE and SLOTS pair slots per group: no row / column bounds, no slot loop (the round is bound by the
-//            number of instructions the waves issue, and the predicates were a quarter of them)
-//   SLOTS  : pair slots a group handles per round.  1: the 1024-thread launch of a 128 x 128 core.  2 (FULL only): the same core on
-//            512 threads (32 groups), for the launch whose other workgroups need 256 registers per lane.  The two pairs of a group
-//            are disjoint like all pairs of a round; their loads, dot products and reductions are issued side by side (two
-//            independent chains per wave stand in for the two waves per SIMD that are missing).  Every pair sees the arithmetic
-//            of SLOTS = 1, so u, s, vt are the same bits.
+//   FULL   : n == 16 * NE and one pair slot per group (1024 threads for a 128 x 128 core): no row / column bounds, no slot loop
+//            (the round is bound by the number of instructions the waves issue, and the predicates were a quarter of them)
 //   consumer: this workgroup is the second one of a fused launch
-template <typename T, int NE, bool FULL, int SLOTS>
+template <typename T, int NE, bool FULL>
 __device__ inline void jacobi_lds_body(const JacobiLdsArgs<T> &ja, bool consumer) {
-    static_assert(SLOTS == 1 || (SLOTS == 2 && FULL), "two pair slots per group: bound-free instance only");
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const Mat<T> g = ja.g;
     Rot<T> *log = ja.log;
@@ -184,7 +179,7 @@ __device__ inline void jacobi_lds_body(const JacobiLdsArgs<T> &ja, bool consumer
     const unsigned epoch = fused ? __hip_atomic_load(ja.epoch_p, __ATOMIC_RELAXED, RC_AGENT) & 0xffffffu : 0u;
     const unsigned long long key = epoch_key(epoch);
     if (fused && consumer) {
-        // ---- consumer: V = product of the rotations, columns in LDS, the producer's pairing (SLOTS slots per group) ----
+        // ---- consumer: V = product of the rotations, columns in LDS, the producer's pairing ----
         constexpr int kSpin = 1 << 24;
         const Mat<T> vc = ja.vc;
         T *V = G;
@@ -210,44 +205,27 @@ __device__ inline void jacobi_lds_body(const JacobiLdsArgs<T> &ja, bool consumer
             const int fin = sh_rot;
             __syncthreads();
             if (fin) { lost = fin == 2; break; }
-            int pr[SLOTS], qr[SLOTS];
-#pragma unroll
-            for (int k = 0; k < SLOTS; ++k) {
-                const int pi = grp + k * ngrp;
-                pr[k] = pi % (N - 1);
-                qr[k] = ((N - 1) - pi % (N - 1)) % (N - 1);
-            }
+            int pr = grp % (N - 1), qr = ((N - 1) - grp % (N - 1)) % (N - 1);
             for (int r = 0; r < N - 1; ++r) {
                 if (FULL || grp < npairs) {
-                    int p[SLOTS], q[SLOTS];
-                    Rot<T> rot[SLOTS];
-                    bool ok[SLOTS];
+                    int p = grp == 0 ? N - 1 : pr, q = grp == 0 ? pr : qr;
+                    if (p > q) { const int t = p; p = q; q = t; }
+                    pr = pr + 1 == N - 1 ? 0 : pr + 1;
+                    qr = qr + 1 == N - 1 ? 0 : qr + 1;
+                    Rot<T> rot{(T)1, (T)0};
+                    const size_t rec = ((size_t)sweep * (N - 1) + r) * npairs + grp;
+                    bool ok = false;
+                    for (int it = 0; it < kSpin && !(ok = rot_fetch(log + rec, chk + rec, rot, key)); ++it) __builtin_amdgcn_s_sleep(2);
+                    if (!ok) lost = true;
+                    if (ok && (FULL || q < n) && rot.s != (T)0) {
+                        T *vp = V + p * ld, *vq = V + q * ld;
 #pragma unroll
-                    for (int k = 0; k < SLOTS; ++k) {
-                        const int pi = grp + k * ngrp;
-                        p[k] = pi == 0 ? N - 1 : pr[k];
-                        q[k] = pi == 0 ? pr[k] : qr[k];
-                        if (p[k] > q[k]) { const int t = p[k]; p[k] = q[k]; q[k] = t; }
-                        pr[k] = pr[k] + 1 == N - 1 ? 0 : pr[k] + 1;
-                        qr[k] = qr[k] + 1 == N - 1 ? 0 : qr[k] + 1;
-                        rot[k] = Rot<T>{(T)1, (T)0};
-                        const size_t rec = ((size_t)sweep * (N - 1) + r) * npairs + pi;
-                        ok[k] = false;
-                        for (int it = 0; it < kSpin && !(ok[k] = rot_fetch(log + rec, chk + rec, rot[k], key)); ++it) __builtin_amdgcn_s_sleep(2);
-                        if (!ok[k]) lost = true;
-                    }
-#pragma unroll
-                    for (int k = 0; k < SLOTS; ++k) {
-                        if (ok[k] && (FULL || q[k] < n) && rot[k].s != (T)0) {
-                            T *vp = V + p[k] * ld, *vq = V + q[k] * ld;
-#pragma unroll
-                            for (int e = 0; e < NE; ++e) {
-                                const int i = ll + kLPP * e;
-                                if (FULL || i < n) {
-                                    const T a = vp[i], b = vq[i];
-                                    vp[i] = fma(rot[k].c, a, -(rot[k].s * b));  // (the contraction of jacobi_pair_rotate)
-                                    vq[i] = fma(rot[k].s, a, rot[k].c * b);
-                                }
+                        for (int e = 0; e < NE; ++e) {
+                            const int i = ll + kLPP * e;
+                            if (FULL || i < n) {
+                                const T a = vp[i], b = vq[i];
+                                vp[i] = fma(rot.c, a, -(rot.s * b));  // (the contraction of jacobi_pair_rotate)
+                                vq[i] = fma(rot.s, a, rot.c * b);
                             }
                         }
                     }
@@ -282,109 +260,45 @@ __device__ inline void jacobi_lds_body(const JacobiLdsArgs<T> &ja, bool consumer
     for (; sweep < max_sweeps; ++sweep) {
         if (tid == 0) sh_rot = 0;
         __syncthreads();
-        if constexpr (SLOTS == 1) {
-            // circle-method pair of this group, advanced round by round when the group owns one pair slot (no integer
-            // modulo on the per-round critical path): slot 0 pairs N - 1 with r, slot pi pairs (r + pi) with (r - pi) mod N - 1
-            const bool one_slot = FULL || npairs <= ngrp;
-            int pr = grp % (N - 1), qr = ((N - 1) - grp % (N - 1)) % (N - 1);
-            for (int r = 0; r < N - 1; ++r) {
-                for (int pi = grp; pi < npairs; pi += FULL ? (1 << 20) : ngrp) {  // FULL: exactly one trip
-                    int p, q;
-                    if (one_slot) {
-                        p = grp == 0 ? N - 1 : pr;
-                        q = grp == 0 ? pr : qr;
-                        if (p > q) { const int t = p; p = q; q = t; }
-                        pr = pr + 1 == N - 1 ? 0 : pr + 1;
-                        qr = qr + 1 == N - 1 ? 0 : qr + 1;
-                    } else {
-                        rr_pair(N, r, pi, p, q);
-                    }
-                    Rot<T> rot{(T)1, (T)0};
-                    if (FULL || q < n) {  // p < q; q == n is the dummy column of an odd n
-                        T *gp = G + p * ld, *gq = G + q * ld;
-                        T a[NE], b[NE];
-                        T app, aqq, apq;
-                        jacobi_pair_dots<T, NE, FULL>(gp, gq, ll, n, a, b, app, aqq, apq);
-                        app = group_sum_dpp<kLPP>(app);
-                        aqq = group_sum_dpp<kLPP>(aqq);
-                        apq = group_sum_dpp<kLPP>(apq);
-                        // rotate iff |apq| > tol * sqrt(app * aqq)   (uniform over the 16 lanes)
-                        if (apq * apq > tol2 * app * aqq) {
-                            jacobi_rotation(app, aqq, apq, rot.c, rot.s);
-                            jacobi_pair_rotate<T, NE, FULL>(gp, gq, ll, n, a, b, rot);
-                            // flag 2 = another sweep is needed
-                            if (ll == 0 && jacobi_rotation_was_large(app, aqq, apq, rot.s, tol)) sh_rot = 2;  // plain store: every writer writes 2
-                        }
-                    }
-                    if (ll == 0) {
-                        if (fused) rot_publish(log + ((size_t)sweep * (N - 1) + r) * npairs + pi, chk + ((size_t)sweep * (N - 1) + r) * npairs + pi, rot, key);
-                        else log[((size_t)sweep * (N - 1) + r) * npairs + pi] = rot;
-                    }
-                }
-                lds_barrier();  // pairs of one round are disjoint; the next round re-pairs the columns
-            }
-        } else {
-            // SLOTS pair slots per group (pi = grp + k * ngrp), each advanced round by round as above; phase by phase over the
-            // slots so that the independent chains overlap
-            int pr[SLOTS], qr[SLOTS];
-#pragma unroll
-            for (int k = 0; k < SLOTS; ++k) {
-                const int pi = grp + k * ngrp;
-                pr[k] = pi % (N - 1);
-                qr[k] = ((N - 1) - pi % (N - 1)) % (N - 1);
-            }
-            for (int r = 0; r < N - 1; ++r) {
-                T *gp[SLOTS], *gq[SLOTS];
-                T a[SLOTS][NE], b[SLOTS][NE];
-                T app[SLOTS], aqq[SLOTS], apq[SLOTS];
-                Rot<T> rot[SLOTS];
-                bool turn[SLOTS];
-#pragma unroll
-                for (int k = 0; k < SLOTS; ++k) {
-                    const int pi = grp + k * ngrp;
-                    int p = pi == 0 ? N - 1 : pr[k], q = pi == 0 ? pr[k] : qr[k];
+        // circle-method pair of this group, advanced round by round when the group owns one pair slot (no integer
+        // modulo on the per-round critical path): slot 0 pairs N - 1 with r, slot pi pairs (r + pi) with (r - pi) mod N - 1
+        const bool one_slot = FULL || npairs <= ngrp;
+        int pr = grp % (N - 1), qr = ((N - 1) - grp % (N - 1)) % (N - 1);
+        for (int r = 0; r < N - 1; ++r) {
+            for (int pi = grp; pi < npairs; pi += FULL ? (1 << 20) : ngrp) {  // FULL: exactly one trip
+                int p, q;
+                if (one_slot) {
+                    p = grp == 0 ? N - 1 : pr;
+                    q = grp == 0 ? pr : qr;
                     if (p > q) { const int t = p; p = q; q = t; }
-                    pr[k] = pr[k] + 1 == N - 1 ? 0 : pr[k] + 1;
-                    qr[k] = qr[k] + 1 == N - 1 ? 0 : qr[k] + 1;
-                    gp[k] = G + p * ld;
-                    gq[k] = G + q * ld;
-                    jacobi_pair_dots<T, NE, FULL>(gp[k], gq[k], ll, n, a[k], b[k], app[k], aqq[k], apq[k]);
+                    pr = pr + 1 == N - 1 ? 0 : pr + 1;
+                    qr = qr + 1 == N - 1 ? 0 : qr + 1;
+                } else {
+                    rr_pair(N, r, pi, p, q);
                 }
-#pragma unroll
-                for (int k = 0; k < SLOTS; ++k) {
-                    app[k] = group_sum_dpp<kLPP>(app[k]);
-                    aqq[k] = group_sum_dpp<kLPP>(aqq[k]);
-                    apq[k] = group_sum_dpp<kLPP>(apq[k]);
-                    turn[k] = apq[k] * apq[k] > tol2 * app[k] * aqq[k];  // uniform over the 16 lanes
-                    rot[k] = Rot<T>{(T)1, (T)0};
-                }
-                bool any = false;
-#pragma unroll
-                for (int k = 0; k < SLOTS; ++k) any = any || turn[k];
-                if (any) {
-                    // the rotations of all slots side by side (the parameters of a slot that does not rotate are computed and dropped)
-                    Rot<T> cand[SLOTS];
-#pragma unroll
-                    for (int k = 0; k < SLOTS; ++k) jacobi_rotation(app[k], aqq[k], apq[k], cand[k].c, cand[k].s);
-#pragma unroll
-                    for (int k = 0; k < SLOTS; ++k) {
-                        if (turn[k]) {
-                            rot[k] = cand[k];
-                            jacobi_pair_rotate<T, NE, FULL>(gp[k], gq[k], ll, n, a[k], b[k], rot[k]);
-                            if (ll == 0 && jacobi_rotation_was_large(app[k], aqq[k], apq[k], rot[k].s, tol)) sh_rot = 2;
-                        }
+                Rot<T> rot{(T)1, (T)0};
+                if (FULL || q < n) {  // p < q; q == n is the dummy column of an odd n
+                    T *gp = G + p * ld, *gq = G + q * ld;
+                    T a[NE], b[NE];
+                    T app, aqq, apq;
+                    jacobi_pair_dots<T, NE, FULL>(gp, gq, ll, n, a, b, app, aqq, apq);
+                    app = group_sum_dpp<kLPP>(app);
+                    aqq = group_sum_dpp<kLPP>(aqq);
+                    apq = group_sum_dpp<kLPP>(apq);
+                    // rotate iff |apq| > tol * sqrt(app * aqq)   (uniform over the 16 lanes)
+                    if (apq * apq > tol2 * app * aqq) {
+                        jacobi_rotation(app, aqq, apq, rot.c, rot.s);
+                        jacobi_pair_rotate<T, NE, FULL>(gp, gq, ll, n, a, b, rot);
+                        // flag 2 = another sweep is needed
+                        if (ll == 0 && jacobi_rotation_was_large(app, aqq, apq, rot.s, tol)) sh_rot = 2;  // plain store: every writer writes 2
                     }
                 }
                 if (ll == 0) {
-#pragma unroll
-                    for (int k = 0; k < SLOTS; ++k) {
-                        const size_t rec = ((size_t)sweep * (N - 1) + r) * npairs + grp + k * ngrp;
-                        if (fused) rot_publish(log + rec, chk + rec, rot[k], key);
-                        else log[rec] = rot[k];
-                    }
+                    if (fused) rot_publish(log + ((size_t)sweep * (N - 1) + r) * npairs + pi, chk + ((size_t)sweep * (N - 1) + r) * npairs + pi, rot, key);
+                    else log[((size_t)sweep * (N - 1) + r) * npairs + pi] = rot;
                 }
-                lds_barrier();
             }
+            lds_barrier();  // pairs of one round are disjoint; the next round re-pairs the columns
         }
         const int rotated = sh_rot;
         __syncthreads();

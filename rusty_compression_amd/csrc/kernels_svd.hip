@@ -40,7 +40,7 @@ __global__ void k_clear_words(unsigned *p, int n) {
 // pair slot, workgroup 1 of a fused launch is the consumer.
 template <typename T, int NE, bool FULL>
 __global__ __launch_bounds__(1024) void k_jacobi_lds(JacobiLdsArgs<T> ja) {
-    jacobi_lds_body<T, NE, FULL, 1>(ja, blockIdx.x == 1);
+    jacobi_lds_body<T, NE, FULL>(ja, blockIdx.x == 1);
 }
 
 // ---------------------------------------------------------------------------

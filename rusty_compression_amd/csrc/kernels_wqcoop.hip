@@ -2,7 +2,8 @@
 // the k x n projection B = Q^H A of the range finder, reference call site
 // /root/reference/src/qr.rs:311-323 (QR::compute_from_range_estimate -> ?geqp3 of B).
 //
-// One launch factors the whole matrix.  G workgroups of 512 threads each own a slab of
+// One launch factors the whole matrix.  G workgroups of 512 threads (1024 in the launch shared
+// with the Jacobi SVD, k_wq_jacobi_fused) each own a slab of
 // columns and keep it in REGISTERS for the whole factorization (8 lanes per column, rows
 // interleaved: 8192 x 128 f64 = 8 MB lives in the VGPRs of 32 CUs).  Per Householder step:
 //   A  every workgroup finds its best remaining column (largest partial norm, first position
@@ -72,9 +73,13 @@ __device__ inline unsigned ld_agent(const unsigned *p) { return __hip_atomic_loa
 // words carry the step number they belong to, and a stale word of an earlier launch must not pass.
 // proceed (optional): a device word of the caller; 0 = do not even try (the optimistic issue of the blocked QRCP found one of its
 // assumptions broken: the cooperative kernel behind this gate then leaves through its "the gate gave up" exit, no budget is held)
-__global__ void k_coop_gate(unsigned *sem, unsigned need, unsigned budget, unsigned *sync, unsigned long long *hdr, int hdr_words, const int *proceed) {
+// clr (optional): clr_words more 32-bit words to clear for the kernel behind the gate (the fused launch's Jacobi hand-over words, J4);
+// like the header words they are complete when the gate kernel ends, which is before the kernel behind it on the stream starts
+__global__ void k_coop_gate(unsigned *sem, unsigned need, unsigned budget, unsigned *sync, unsigned long long *hdr, int hdr_words, const int *proceed, unsigned *clr,
+                            int clr_words) {
     if (blockIdx.x != 0) return;
     for (int i = threadIdx.x; i < hdr_words; i += blockDim.x) __hip_atomic_store(hdr + i, 0ull, __ATOMIC_RELAXED, RC_AGENT);
+    for (int i = threadIdx.x; i < clr_words; i += blockDim.x) st_agent(clr + i, 0u);
     if (threadIdx.x != 0) return;
     st_agent(sync + 0, 0u);
     st_agent(sync + 2, 0u);  // (k_qrb_coop's commit counter)
@@ -94,6 +99,14 @@ __global__ void k_coop_gate(unsigned *sem, unsigned need, unsigned budget, unsig
 #ifdef RC_COOP_TIMING
 __device__ unsigned long long g_coop_dbg[8];
 #endif
+
+// This lane's index in its wave, read from the hardware again at every call (two v_mbcnt) instead of kept in a register: see
+// kRereadLane in wq_coop_body.
+__device__ inline int lane_reread() {
+    int l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return l;
+}
 
 template <typename T>
 struct WqCoopArgs {
@@ -136,7 +149,8 @@ struct WqCoopArgs {
 //      stores (s_waitcnt vmcnt(0)) -> workgroup barrier -> wave 0 writes the header.  (The barrier alone does not wait for global
 //      stores on gfx950.)  Column slots are double buffered like the headers (same argument as I2).
 //  I4  Cleared per launch, on the stream, by k_coop_gate in front: all header words (a stale word of an earlier launch at the same
-//      address must not validate), sync[0] (finished counter), sync[2]; sync[1] (abort) is written by the gate last.
+//      address must not validate), sync[0] (finished counter), sync[2]; sync[1] (abort) is written by the gate last.  (For the fused
+//      launch the same gate also clears the Jacobi role's hand-over words: J4 in jacobi_lds.hpp.)
 //  I5  Pivot agreement is computed redundantly from the same 5 x G words by every workgroup with the same instruction sequence,
 //      so all workgroups take the same pivot, bit for bit; the reflector is generated redundantly from the same fetched column.
 //  I6  Every spin is bounded (kSpinLimit); on expiry the abort word is set (agent scope), every workgroup leaves at its next poll,
@@ -144,18 +158,35 @@ struct WqCoopArgs {
 //  I7  The budget taken by the gate (a.units) is released exactly once, by the workgroup whose arrival at sync[0] is the last.
 //  I8  Stages: a later launch reads what the earlier one wrote (wf rows >= row0, pos_out, vn) across a kernel boundary on the same
 //      stream -- no in-kernel protocol; an aborted earlier stage (flag bit 4) makes the later ones return at once.
+// NG 8-lane groups per workgroup (8 NG threads), so a workgroup owns up to NG * CPG columns, column cl of it in group cl % NG, slot
+// cl / NG.  Two layouts are in use, both with 256 columns per workgroup of a 128-row matrix:
+//   NG = 64, CPG = 4 (512 threads, k_wq_coop): 256 VGPRs per lane, the slab needs 128 of them
+//   NG = 128, CPG = 2 (1024 threads, k_wq_jacobi_fused): 128 VGPRs per lane, the slab needs 64
+// A column is 8 lanes with rows l8 + 8 e in either; its dot products, reductions and down-dates are per column and pivot ties are
+// broken by position, so which group, wave or slot holds a column does not reach the bits of wf, jpvt, tau.
 // G, wg: number of cooperating workgroups and this one's index among them (the launch may hold other workgroups behind them)
-template <typename T, int NE, int CPG>
+template <typename T, int NE, int CPG, int NG = 64>
 __device__ inline void wq_coop_body(const WqCoopArgs<T> &a, const int G, const int wg) {
-    constexpr int NG = 64;  // 8-lane groups per workgroup (512 threads: 256 VGPRs per lane, the slab needs 128)
-    constexpr int NW = 8;
+    static_assert(NG % 8 == 0 && NG * 8 <= 1024 && CPG <= 8, "whole waves of 8-lane groups; one norm owner lane per column of a group");
+    constexpr int NW = NG / 8;  // waves per workgroup
     constexpr int kNoInt = 0x7fffffff;
     __shared__ double sh_v[NW];
     __shared__ int sh_p[NW], sh_c[NW], sh_j[NW];
     __shared__ int sh_exit;
     __shared__ int bc[4];
     __shared__ T xw[8 * NE];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l8 = tid & 7, g8 = tid >> 3;
+    // 1024 threads leave a lane 128 VGPRs, 64 of them slab and 32 the reflector.  Left alone, the compiler hoists what the step loop
+    // derives from the thread index (LDS and slot addresses, the write-out addresses) in front of the loops, where these values outlive
+    // every step in registers the lane does not have: they are spilled and reloaded step by step.  So this layout keeps the wave's
+    // number in a scalar register, takes the lane index from the hardware (v_mbcnt) rather than from the thread index, and reads it
+    // AGAIN (lane_reread) where such a value is formed: phase A's LDS slots, phase B's column fetch, the down-date's vote bit, the
+    // write-out of block 0.
+    // (Re-reading it everywhere, or in the reflector's norm loop, makes the compiler spill the slab itself: 240 registers.)
+    constexpr bool kRereadLane = NG > 64;
+    const int wv = kRereadLane ? __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6) : (int)threadIdx.x >> 6;
+    const int lane = kRereadLane ? (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) : (int)threadIdx.x & 63;
+    const int tid = kRereadLane ? wv * 64 + lane : (int)threadIdx.x;
+    const int l8 = kRereadLane ? lane & 7 : tid & 7, g8 = kRereadLane ? wv * 8 + (lane >> 3) : tid >> 3;
     const int m = (int)a.w.rows, mp = a.mp;
     const int64_t n = a.w.cols;
     const int c0 = wg * a.cpw;
@@ -240,14 +271,15 @@ __device__ inline void wq_coop_body(const WqCoopArgs<T> &a, const int G, const i
             const int cmin = wave_min_dpp((speak && best == mx) ? mypos : kNoInt);
             const unsigned long long mask = __ballot(speak && best == mx && mypos == cmin);
             const unsigned long long maskj = __ballot(speak && mypos == j);
-            if (lane == 0) {
+            const int la = kRereadLane ? lane_reread() : lane;
+            if (la == 0) {
                 sh_v[wv] = mask ? mx : -1.0;
                 sh_p[wv] = cmin;
                 sh_c[wv] = -1;
                 sh_j[wv] = -1;
             }
-            if (mask && lane == __ffsll((long long)mask) - 1) sh_c[wv] = mycol;
-            if (maskj && lane == __ffsll((long long)maskj) - 1) sh_j[wv] = mycol;
+            if (mask && la == __ffsll((long long)mask) - 1) sh_c[wv] = mycol;
+            if (maskj && la == __ffsll((long long)maskj) - 1) sh_j[wv] = mycol;
         }
         __syncthreads();
         RC_TICK(0)
@@ -333,7 +365,10 @@ __device__ inline void wq_coop_body(const WqCoopArgs<T> &a, const int G, const i
         const int wcol = bc[0], wslot = bc[1], wpos = bc[2], colj = bc[3];
         // ---- B: fetch the pivot column (complete before its header was posted); each wave then
         //         generates the reflector redundantly (?larfg): identical arithmetic everywhere ----
-        if (tid < mp && row0 + tid >= j && row0 + tid < m) xw[tid] = ld_agent(a.cols + ((size_t)par * G + wslot) * mp + tid);  // xw[i - row0] = row i
+        {
+            const int tb = kRereadLane ? wv * 64 + lane_reread() : tid;
+            if (tb < mp && row0 + tb >= j && row0 + tb < m) xw[tb] = ld_agent(a.cols + ((size_t)par * G + wslot) * mp + tb);  // xw[i - row0] = row i
+        }
         __syncthreads();
         RC_TICK(3)
         T tj = 0, beta, scal = 0;
@@ -407,7 +442,7 @@ __device__ inline void wq_coop_body(const WqCoopArgs<T> &a, const int G, const i
                 temp = temp > (T)0 ? temp : (T)0;
                 const T r = myvn1 / myvn2;
                 const T temp2 = temp * r * r;
-                if (temp2 <= Tol3z<T>::v()) need = 1 << l8;
+                if (temp2 <= Tol3z<T>::v()) need = 1 << (kRereadLane ? lane_reread() & 7 : l8);
                 else myvn1 = myvn1 * sqrt(temp);
             }
             need = group_sum_dpp<8>(need);
@@ -435,7 +470,8 @@ __device__ inline void wq_coop_body(const WqCoopArgs<T> &a, const int G, const i
     // ---- the 8-row block is finished: write it out, shift the register blocks down -------------
 #pragma unroll
     for (int q = 0; q < CPG; ++q) {
-        if (!aborted && pos[q] >= 0 && r0 + l8 < m) a.wf.p[(int64_t)(c0 + g8 + NG * q) * a.wf.cs + r0 + l8] = x[q][0];
+        const int lw = kRereadLane ? lane_reread() : lane, l8w = kRereadLane ? lw & 7 : l8, g8w = kRereadLane ? wv * 8 + (lw >> 3) : g8;
+        if (!aborted && pos[q] >= 0 && r0 + l8w < m) a.wf.p[(int64_t)(c0 + g8w + NG * q) * a.wf.cs + r0 + l8w] = x[q][0];
 #pragma unroll
         for (int e = 0; e + 1 < NE; ++e) x[q][e] = x[q][e + 1];
         x[q][NE - 1] = 0;
@@ -481,17 +517,20 @@ __global__ __launch_bounds__(512, NE <= 4 ? 4 : 2) void k_wq_coop(WqCoopArgs<T> 
     wq_coop_body<T, NE, CPG>(a, (int)gridDim.x, (int)blockIdx.x);
 }
 
-// One launch, two roles (f64, 128-row B).  Workgroups 0 .. g - 1 are k_wq_coop<T, 16, 4> run as ONE stage over all steps; workgroups
-// g and g + 1 are producer and consumer of the LDS Jacobi of the 128 x 128 core (jacobi_lds.hpp) on 512 threads, two pair slots per
-// 16-lane group.  The two factorizations are independent consumers of B = Q^H A: side by side they hold one kernel slot of the
-// process for max(duration) instead of two for the sum.  The roles share nothing: I1-I8 hold among the first g workgroups (G = g
+// One launch, two roles (f64, 128-row B), 1024 threads per workgroup.  Workgroups 0 .. g - 1 are the cooperative pivoted QR run as ONE
+// stage over all steps, two columns per 8-lane group on 128 groups (the 256 columns per workgroup of k_wq_coop<T, 16, 4>, half the
+// slab per lane); workgroups g and g + 1 are producer and consumer of the LDS Jacobi of the 128 x 128 core (jacobi_lds.hpp), one
+// column pair per 16-lane group: the body of k_jacobi_lds<T, 8, true> itself.  The two factorizations are independent consumers of
+// B = Q^H A: side by side they hold one kernel slot of the process for max(duration) instead of two for the sum, and the Jacobi is
+// the longer one, so its layout decides the launch.  The roles share nothing: I1-I8 hold among the first g workgroups (G = g
 // everywhere in the body), J1-J6 between the last two; the Jacobi workgroups wait for nobody but each other (J1), so the gate's
-// budget covers the first g only.  Registers: the maximum over both roles (the QR's), hence 512 threads; dynamic LDS: the Jacobi's.
+// budget covers the first g only.  Registers: 16 waves per CU leave 128 VGPRs per lane, the maximum over both roles is the QR's
+// (64 of slab, 32 of reflector); dynamic LDS: the Jacobi's.
 template <typename T>
-__global__ __launch_bounds__(512, 2) void k_wq_jacobi_fused(WqCoopArgs<T> a, JacobiLdsArgs<T> ja, int g) {
+__global__ __launch_bounds__(1024) void k_wq_jacobi_fused(WqCoopArgs<T> a, JacobiLdsArgs<T> ja, int g) {
     const int wg = (int)blockIdx.x;
-    if (wg < g) wq_coop_body<T, 16, 4>(a, g, wg);
-    else jacobi_lds_body<T, 8, true, 2>(ja, wg == g + 1);
+    if (wg < g) wq_coop_body<T, 16, 2, 128>(a, g, wg);
+    else jacobi_lds_body<T, 8, true>(ja, wg == g + 1);
 }
 
 // ---- host side ---------------------------------------------------------------------------
@@ -603,22 +642,28 @@ unsigned coop_budget_units(int device) {
 }
 
 // one-thread gate in front of a cooperative kernel: takes `need` units of the device-wide budget (released by the cooperative
-// kernel's last workgroup), clears the kernel's header words and its sync words
-void coop_gate_launch(rc_context *c, unsigned need, unsigned *sync, unsigned long long *hdr, int hdr_words, const int *proceed) {
+// kernel's last workgroup), clears the kernel's header words, its sync words and (optionally) clr_words words at clr
+void coop_gate_launch(rc_context *c, unsigned need, unsigned *sync, unsigned long long *hdr, int hdr_words, const int *proceed, unsigned *clr, int clr_words) {
     // (the caller checked need <= budget; the share of this process may have shrunk since -- another process arrived on the device --
     // in which case this launch still goes through once nothing else of this process holds units)
     const unsigned budget = std::max(coop_budget_units(c->device), need);
-    hipLaunchKernelGGL(k_coop_gate, dim3(1), dim3(256), 0, c->stream, coop_semaphore(c->device), need, budget, sync, hdr, hdr_words, proceed);
+    hipLaunchKernelGGL(k_coop_gate, dim3(1), dim3(256), 0, c->stream, coop_semaphore(c->device), need, budget, sync, hdr, hdr_words, proceed, clr, clr_words);
 }
 
 // One stage: NE 8-row blocks per column in registers (the live rows [row0, m) must fit: 8 NE >= m - row0), CPG columns per 8-lane group.
-static void stage_shape(int ne, int64_t n, int *cpg, int *cpw, int *g) {
-    *cpg = ne >= 32 ? 2 : ne >= 16 ? 4 : 8;  // at most 64 matrix elements per lane; a group owns at most 8 columns (one norm owner each)
-    const int64_t cap = 64 * (int64_t)*cpg;
+// n columns over workgroups that hold at most cap each: their number and the (even) share of each
+static void split_columns(int64_t n, int64_t cap, int *cpw, int *g) {
     const int64_t wgs = (n + cap - 1) / cap;
     *g = (int)wgs;
     *cpw = (int)((n + wgs - 1) / wgs);
 }
+static void stage_shape(int ne, int64_t n, int *cpg, int *cpw, int *g) {
+    *cpg = ne >= 32 ? 2 : ne >= 16 ? 4 : 8;  // at most 64 matrix elements per lane; a group owns at most 8 columns (one norm owner each)
+    split_columns(n, 64 * (int64_t)*cpg, cpw, g);  // 64 groups per 512-thread workgroup
+}
+// the fused launch: 128 groups of 2 columns per 1024-thread workgroup -- the 256 columns of stage_shape(16, ...), so g and cpw (and
+// with them the header / column slots and the budget) are those of k_wq_coop<T, 16, 4>
+constexpr int kFusedGroups = 128, kFusedCpg = 2;
 static int stage_ne(int64_t live_rows) { return live_rows <= 32 ? 4 : live_rows <= 64 ? 8 : live_rows <= 128 ? 16 : 32; }
 
 template <typename T>
@@ -653,6 +698,7 @@ static WqCoopArgs<T> stage_args(rc_context *c, Mat<T> w, Mat<T> wf, int64_t kmax
     a.pos_out = nullptr;
     a.vn = nullptr;
     // 512 threads x up to 256 VGPRs: one workgroup fills its CU = 2 units; the 4-block layout is held to 128 VGPRs: 1 unit
+    // (the fused launch's 1024 threads x 128 VGPRs fill a CU just the same: 2 units, ne = 16)
     a.units = (ne <= 4 ? 1u : 2u) * (unsigned)g;
     return a;
 }
@@ -733,8 +779,8 @@ void geqp3_wide_coop_jacobi(rc_context *c, Mat<T> w, Mat<T> wf, int64_t kmax, in
     if constexpr (std::is_same<T, double>::value) {
         kmax = std::min(kmax, std::min(m, n));
         const int nc = (int)m, N = nc;  // (even)
-        int cpg, cpw, g;
-        stage_shape(16, n, &cpg, &cpw, &g);
+        int cpw, g;
+        split_columns(n, (int64_t)kFusedGroups * kFusedCpg, &cpw, &g);
         ProfScope ps(c, "op:geqp3_wide_coop %lldx%lld + jacobi_svd n=%d wgs=%d+2", (long long)m, (long long)n, nc, g);
         const WqCoopArgs<T> a = stage_args<T>(c, w, wf, kmax, jpvt, tau, flag, 16, g, cpw);
         const int ld = jacobi_pitch<T>(nc);
@@ -752,9 +798,8 @@ void geqp3_wide_coop_jacobi(rc_context *c, Mat<T> w, Mat<T> wf, int64_t kmax, in
             RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048));
             attr_set[c->device & 63] = true;
         }
-        fill_words(c, vsync, ((size_t)nc + 1) * sizeof(unsigned), 0u);  // J4
-        coop_gate_launch(c, a.units, a.sync, a.hdr, 2 * g * 5);
-        hipLaunchKernelGGL(kern, dim3((unsigned)g + 2), dim3(512), lds, c->stream, a, ja, g);
+        coop_gate_launch(c, a.units, a.sync, a.hdr, 2 * g * 5, nullptr, vsync, nc + 1);  // (vsync: J4)
+        hipLaunchKernelGGL(kern, dim3((unsigned)g + 2), dim3(8 * kFusedGroups), lds, c->stream, a, ja, g);
     }
 }
 

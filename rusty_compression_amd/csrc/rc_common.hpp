@@ -359,7 +359,9 @@ void coop_prepare(int device);
 // device-wide budget of the cooperative kernels, in half compute units (kernels_wqcoop.hip)
 unsigned *coop_semaphore_of(int device);
 unsigned coop_budget_units(int device);
-void coop_gate_launch(rc_context *c, unsigned need, unsigned *sync, unsigned long long *hdr, int hdr_words, const int *proceed = nullptr);
+// (clr, clr_words: an optional second range of 32-bit words the gate clears for the kernel behind it)
+void coop_gate_launch(rc_context *c, unsigned need, unsigned *sync, unsigned long long *hdr, int hdr_words, const int *proceed = nullptr, unsigned *clr = nullptr,
+                      int clr_words = 0);
 // r(i, p) = (i <= p) ? w(i, jpvt[p]) : 0  for i < r.rows
 template <typename T> void extract_r(rc_context *c, Mat<T> w, const int64_t *jpvt, Mat<T> r);
 // qw (m x kq column-major) = H_0 ... H_{k-1} [I ; 0], reflector j stored in column jpvt[j] of w

@@ -1,7 +1,7 @@
-// The LDS Jacobi of a 128 x 128 f64 core as a lone two-workgroup launch (producer + consumer), in its two thread layouts:
-//   1024 threads, one pair slot per 16-lane group   (k_jacobi_lds of the library)
-//    512 threads, two pair slots per group          (the Jacobi role of k_wq_jacobi_fused)
-// Prints the median launch time of each and whether u, s, v agree bit for bit.  Build: make -C tools/microbench jacobi_lanes
+// The LDS Jacobi of a 128 x 128 f64 core as a lone two-workgroup launch (producer + consumer) of 1024 threads, one column pair per
+// 16-lane group: k_jacobi_lds of the library and the Jacobi role of k_wq_jacobi_fused.  (The 512-thread layout with two pairs per
+// group that this tool compared it with -- +27 % per launch, profiles/r05_fused_ab.txt -- is gone from the library.)
+// Prints the median launch time and whether two launches agree bit for bit.  Build: make -C tools/microbench jacobi_lanes
 #include "../../rusty_compression_amd/csrc/jacobi_lds.hpp"
 
 #include <algorithm>
@@ -17,9 +17,9 @@ using namespace rc;
         if (e_ != hipSuccess) { fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e_)); return 1; } \
     } while (0)
 
-template <int THREADS, int SLOTS>
+template <int THREADS>
 __global__ __launch_bounds__(THREADS) void k_jacobi(JacobiLdsArgs<double> ja) {
-    jacobi_lds_body<double, 8, true, SLOTS>(ja, blockIdx.x == 1);
+    jacobi_lds_body<double, 8, true>(ja, blockIdx.x == 1);
 }
 
 struct Result {
@@ -28,7 +28,7 @@ struct Result {
     int sweeps = 0, health = 0;
 };
 
-template <int THREADS, int SLOTS>
+template <int THREADS>
 static int run(const double *g_dev, Result &out) {
     constexpr int n = 128;
     const size_t nrec = (size_t)kMaxSweeps * (n - 1) * (n / 2);
@@ -52,7 +52,7 @@ static int run(const double *g_dev, Result &out) {
     CHECK(hipMemset(health, 0, 4));
     const int ld = jacobi_pitch<double>(n);
     const size_t lds = jacobi_lds_bytes<double>(n, ld);
-    auto kern = k_jacobi<THREADS, SLOTS>;
+    auto kern = k_jacobi<THREADS>;
     CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048));
     JacobiLdsArgs<double> ja{Mat<double>(const_cast<double *>(g_dev), n, n, 1, n), log, sweeps, Mat<double>(uc, n, n, 1, n), s, order, kMaxSweeps, 1, vsync, chk, epoch,
                              Mat<double>(vc, n, n, 1, n), health, ld};
@@ -100,9 +100,9 @@ int main() {
     CHECK(hipMalloc(&g_dev, n * n * 8));
     CHECK(hipMemcpy(g_dev, g.data(), n * n * 8, hipMemcpyHostToDevice));
     Result a, b;
-    if (run<1024, 1>(g_dev, a) || run<512, 2>(g_dev, b)) return 1;
+    if (run<1024>(g_dev, a) || run<1024>(g_dev, b)) return 1;
     const bool same = !memcmp(a.u.data(), b.u.data(), n * n * 8) && !memcmp(a.v.data(), b.v.data(), n * n * 8) && !memcmp(a.s.data(), b.s.data(), n * 8);
-    printf("{\"n\": %d, \"ms_1024_threads_1_slot\": %.4f, \"ms_512_threads_2_slots\": %.4f, \"sweeps\": [%d, %d], \"health\": [%d, %d], \"u_s_v_bitwise_equal\": %s}\n", n, a.ms,
-           b.ms, a.sweeps, b.sweeps, a.health, b.health, same ? "true" : "false");
+    printf("{\"n\": %d, \"ms_1024_threads\": [%.4f, %.4f], \"sweeps\": [%d, %d], \"health\": [%d, %d], \"u_s_v_bitwise_equal\": %s}\n", n, a.ms, b.ms, a.sweeps,
+           b.sweeps, a.health, b.health, same ? "true" : "false");
     return same && a.health == 0 && b.health == 0 ? 0 : 2;
 }
