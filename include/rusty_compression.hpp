@@ -554,11 +554,14 @@ BatchedColumnID<T> column_id_rank_batched(const DeviceMatrix<T> &a, int32_t coun
 // omega a_i (l x n; omega is l x m and shared by the batch) and the column ID of the sketch, C gathered from a_i: the projection of
 // sample_range_by_rank (src/random_sampling.rs) followed by QR::compute_from_range_estimate + column_id (src/qr.rs:311-323).  m <= 65536,
 // n <= 512, l <= 128; k is clamped to min(k, l, n).  The result is a BatchedColumnID, so apply_batched, to_mat_batched and
-// recompress_batched take it; `sketch`, when given, receives the count * l x n sketches.  The C ABI has the entry point for the real
-// scalars only, so it is reached through its own dispatch: Api<c64> and Api<c32> stay complete.
+// recompress_batched and residual_batched take it; `sketch`, when given, receives the count * l x n sketches.  The complex entry points carry
+// another stem (rc_sketch_column_id_rank_complex_batched_c64 / _c32: omega a with nothing conjugated), so the call is reached through its
+// own dispatch rather than through Api<T>.
 template <typename T> struct SketchApi;
 template <> struct SketchApi<double> { static constexpr auto sketch_column_id_rank_batched = rc_sketch_column_id_rank_batched_f64; };
 template <> struct SketchApi<float> { static constexpr auto sketch_column_id_rank_batched = rc_sketch_column_id_rank_batched_f32; };
+template <> struct SketchApi<c64> { static constexpr auto sketch_column_id_rank_batched = rc_sketch_column_id_rank_complex_batched_c64; };
+template <> struct SketchApi<c32> { static constexpr auto sketch_column_id_rank_batched = rc_sketch_column_id_rank_complex_batched_c32; };
 template <typename T>
 BatchedColumnID<T> column_id_rank_batched(const DeviceMatrix<T> &a, const DeviceMatrix<T> &omega, int32_t count, int64_t k, double tol = 0.0,
                                           DeviceMatrix<T> *sketch = nullptr) {

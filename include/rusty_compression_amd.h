@@ -612,7 +612,7 @@ rc_status rc_lowrank_recompress_complex_batched_c32(rc_context *ctx, rc_matrix l
  * from a_i.  Per block this replaces the reference's randomized sequence: the projection of sample_range_by_rank (src/random_sampling.rs), then
  * QR::compute_from_range_estimate followed by column_id() (src/qr.rs:311-323): with omega = Q^H of a range estimate it is that sequence, with a
  * Gaussian omega (rc_random_gaussian_*) it is the one-pass randomized ID.  The pivoted QR runs on l rows instead of m, so m is not bounded by what
- * one workgroup holds.  Real scalars only.
+ * one workgroup holds.  Real scalars; complex blocks go to rc_sketch_column_id_rank_complex_batched_c64 / _c32 below.
  * The batch layout is rc_column_id_rank_batched_*'s: block i of every operand is its view moved by i times its batch stride; any row and column
  * strides; every pointer a device pointer.  a is m x n; omega is l x m (omega_batch_stride = 0 shares one test matrix over the batch, the usual
  * case; a_batch_stride = 0 is legal too); y is l x n and receives the sketch when y.data is not NULL (y.data == NULL: not written, the other
@@ -633,6 +633,41 @@ rc_status rc_lowrank_recompress_complex_batched_c32(rc_context *ctx, rc_matrix l
  * workspace bounded by the grid, not by count. */
 rc_status rc_sketch_column_id_rank_batched_f64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega, int64_t omega_batch_stride, int32_t count, int64_t k, double tol, rc_matrix y, int64_t y_batch_stride, rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks);
 rc_status rc_sketch_column_id_rank_batched_f32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega, int64_t omega_batch_stride, int32_t count, int64_t k, double tol, rc_matrix y, int64_t y_batch_stride, rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks);
+/* The complex twin of rc_sketch_column_id_rank_batched_*: the one-pass randomized column ID of every complex tall block of a batch, in one
+ * stream-ordered, capturable call: the sketch Y_i = omega_i a_i (l x n) of each block a_i (m x n) is formed while a_i streams through the chip once,
+ * and the column ID of the small Y_i gives the pivots and Z; C is gathered from a_i.  Nothing is conjugated: a caller who wants Q^H a passes
+ * omega = Q^H (with that omega this is sample_range_by_rank's projection, then QR::compute_from_range_estimate + column_id(), src/qr.rs:311-323,
+ * for the reference's c64 / c32 scalars).  The pivoted QR runs on l rows instead of m, so m is not bounded by what one workgroup holds.
+ * Data are interleaved (re, im): _c64 is std::complex<double>, _c32 std::complex<float>; every stride and batch stride is in complex elements and an
+ * element need only be aligned as its real type.  The batch layout is the real call's: block i of every operand is its view moved by i times its
+ * batch stride; any row and column strides; every pointer a device pointer.  a is m x n; omega is l x m (omega_batch_stride = 0 shares one test
+ * matrix over the batch, the usual case; a_batch_stride = 0 is legal too); y is l x n and receives the sketch when y.data is not NULL (y.data ==
+ * NULL: not written, the other fields are then ignored); c is m x kk and z is kk x n with kk = min(k, l, n); col_ind (count x n) and ranks (count)
+ * are contiguous int64.  The outputs must not overlap the inputs or one another.
+ * Per block, with Y_i the sketch as this call computes it (and writes it to y):
+ *   col_ind, ranks and z are what rc_column_id_rank_batched_c64 / _c32 returns for the matrix Y_i with the same k and tol, bit for bit: pivots on the
+ *     real partial norms of ?geqp3's complex Householder QR of Y_i, r = the first j < kk with the real R_jj == 0 or (tol > 0 and |R_jj / R_00| < tol),
+ *     else kk, z = [I | R11^-1 R12] P^T with rows r..kk-1 zero;
+ *   c[:, j] = a[:, col_ind[j]] bit for bit for j < r, columns r..kk-1 of c are zero, so a_i ~ c z to the accuracy of the sketch.
+ * The sketch runs on v_mfma_f64_16x16x4_f64 / v_mfma_f32_16x16x4_f32 with the real and imaginary parts as separate real operands.  Each of Re Y and
+ * Im Y is one accumulator chain per element, from zero over the ascending rows of a, four rows per instruction; within a four-row step Re takes
+ * MFMA(Om_re, A_re) then MFMA(-Om_im, A_im), Im takes MFMA(Om_re, A_im) then MFMA(Om_im, A_re) (the negation is a sign flip in a register);
+ * nothing is split across workgroups or added by atomics.  The outputs do not depend on whether y is requested; block i's bits depend on block i's
+ * a and omega alone: not on count, the position in the batch, the neighbours, any batch, row or column stride, where the working copy lives, the
+ * grid, or graph replay against an eager call.  Two properties follow from that order:
+ *   conjugation: conjugating both a and omega gives the same col_ind and ranks and the elementwise conjugate of y, c and z, bit for bit, except
+ *     that a component that cancels to exactly zero is +0 either way;
+ *   zero imaginary parts: with every imaginary part of a and omega +0, Re y has the bits of rc_sketch_column_id_rank_batched_f64 / _f32's y on the
+ *     real parts and Im y is zero.
+ * Non-finite input stays inside its block's outputs (values unspecified, col_ind still a permutation, 0 <= r <= kk).
+ * Domain: 1 <= n <= 512, 1 <= l <= 128, 1 <= m <= 65536, 1 <= k <= 128, 0 <= tol < 1, count >= 0 (0: nothing to do).  RC_INVALID_ARGUMENT for an
+ * argument outside the domain, omega.cols != a.rows, a wrong y, c or z shape, an output batch stride smaller than one view's span when count > 1,
+ * a null a, omega, c, z, col_ind or ranks with count > 0, or a null ctx (rejected before a device is touched).  No host synchronisation;
+ * workspace bounded by the grid, not by count.
+ * The name: the stem is rc_sketch_column_id_rank_complex_batched_, as rc_lowrank_recompress_complex_batched_ is spelled, because the real pair was
+ * published as "real scalars only" and callers (and the ABI test of that pair) rely on rc_sketch_column_id_rank_batched_c64 / _c32 not existing. */
+rc_status rc_sketch_column_id_rank_complex_batched_c64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega, int64_t omega_batch_stride, int32_t count, int64_t k, double tol, rc_matrix y, int64_t y_batch_stride, rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks);
+rc_status rc_sketch_column_id_rank_complex_batched_c32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega, int64_t omega_batch_stride, int32_t count, int64_t k, double tol, rc_matrix y, int64_t y_batch_stride, rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks);
 /* The certificate of such a batch: the Frobenius norm of what a low-rank factorization leaves of its block, in one stream-ordered, capturable call
  * that reads the ranks on the device: per block the reference's rel_diff_fro(x.to_mat(), a) (src/lib.rs) without the m x n temporary of to_mat, on
  * the domain of the sketched column ID, so the output of every batched compressor above is accepted.  The _c64 / _c32 forms take interleaved

@@ -647,6 +647,48 @@ def svd_residual_batched_complex(a: torch.Tensor, u: torch.Tensor, s: torch.Tens
     return lowrank_residual_batched_complex(a, u, vt, s=s, ranks=ranks, want_residual=want_residual)
 
 
+def _sketch_column_id_rank_batched(who: str, complex_data: bool, a, k, tol, omega, oversampling, seed, return_sketch: bool):
+    """The body of sketch_column_id_rank_batched and sketch_column_id_rank_batched_complex: the checks, the default omega and the call."""
+    from . import _lib
+    from .types import as_device
+
+    a = as_device(a)
+    kinds = (torch.complex128, torch.complex64) if complex_data else (torch.float64, torch.float32)
+    if a.dtype not in kinds:
+        raise TypeError(f"{who}: {'complex128 or complex64' if complex_data else 'float64 or float32'} data expected, got {a.dtype}")
+    if a.dim() != 3:
+        raise AssertionError("expected a [count, m, n] batch")
+    a = a.resolve_conj()  # a lazily conjugated complex view is materialised: the kernels read the stored values
+    count, m, n = a.shape
+    if omega is None:
+        from .random_matrix import Rng, random_gaussian
+
+        omega = random_gaussian((max(min(int(k) + int(oversampling), 128), 1), m), Rng(int(seed)), a.dtype)
+    omega = as_device(omega)
+    if omega.dtype != a.dtype:
+        raise TypeError(f"{who}: omega is {omega.dtype}, a is {a.dtype}")
+    omega = omega.resolve_conj()
+    if omega.dim() not in (2, 3) or (omega.dim() == 3 and omega.shape[0] != count):
+        raise AssertionError("expected omega [l, m] or [count, l, m]")
+    l = omega.shape[-2]
+    obs = omega.stride(0) if omega.dim() == 3 else 0
+    kk = max(min(int(k), l, n), 0)
+    c = torch.empty((count, m, kk), dtype=a.dtype, device=a.device)
+    z = torch.empty((count, kk, n), dtype=a.dtype, device=a.device)
+    ind = torch.empty((count, n), dtype=torch.int64, device=a.device)
+    ranks = torch.empty(count, dtype=torch.int64, device=a.device)
+    y = torch.empty((count, l, n), dtype=a.dtype, device=a.device) if return_sketch else None
+    stem = "rc_sketch_column_id_rank_complex_batched_" if complex_data else "rc_sketch_column_id_rank_batched_"
+    _lib.default_context().call(stem + _lib.suffix(a.dtype),
+                                _lib.rc_matrix(a.data_ptr(), m, n, a.stride(1), a.stride(2)), ctypes.c_int64(a.stride(0)),
+                                _lib.rc_matrix(omega.data_ptr(), l, omega.shape[-1], omega.stride(-2), omega.stride(-1)), ctypes.c_int64(obs),
+                                ctypes.c_int32(count), ctypes.c_int64(int(k)), ctypes.c_double(float(tol)),
+                                _lib.rc_matrix(y.data_ptr(), l, n, n, 1) if return_sketch else _lib.mat(None), ctypes.c_int64(l * n),
+                                _lib.rc_matrix(c.data_ptr(), m, kk, kk, 1), ctypes.c_int64(m * kk),
+                                _lib.rc_matrix(z.data_ptr(), kk, n, n, 1), ctypes.c_int64(kk * n), _lib.i64p(ind), _lib.i64p(ranks))
+    return (c, z, ind, ranks, y) if return_sketch else (c, z, ind, ranks)
+
+
 def sketch_column_id_rank_batched(a: torch.Tensor, k: int, tol: float = 0.0, omega: Optional[torch.Tensor] = None, oversampling: int = 8, seed: int = 0,
                                   return_sketch: bool = False):
     """One-pass randomized column IDs of `count` tall same-shaped blocks in one stream-ordered call (rc_sketch_column_id_rank_batched_*):
@@ -658,41 +700,19 @@ def sketch_column_id_rank_batched(a: torch.Tensor, k: int, tol: float = 0.0, ome
     rc_random_gaussian_* at (seed, offset 0), so the result is that of the explicit call with random_gaussian((l, m), Rng(seed)).
     k (<= 128) is clamped to kk = min(k, l, n).  Returns C [count, m, kk], Z [count, kk, n], ind [count, n], ranks [count] and, with
     return_sketch, Y [count, l, n]: Z, ind and ranks are column_id_rank_batched(Y, k, tol)'s bit for bit, C[:, :, j] = a[:, :, ind[j]]
-    for j below the block's rank, the rest of C and Z zero.  Complex data and mismatched dtypes raise TypeError."""
-    from . import _lib
-    from .types import as_device
+    for j below the block's rank, the rest of C and Z zero.  Complex data (see sketch_column_id_rank_batched_complex) and mismatched
+    dtypes raise TypeError."""
+    return _sketch_column_id_rank_batched("sketch_column_id_rank_batched", False, a, k, tol, omega, oversampling, seed, return_sketch)
 
-    a = as_device(a)
-    if a.dtype not in (torch.float64, torch.float32):
-        raise TypeError(f"sketch_column_id_rank_batched: float64 or float32 data expected, got {a.dtype}")
-    if a.dim() != 3:
-        raise AssertionError("expected a [count, m, n] batch")
-    count, m, n = a.shape
-    if omega is None:
-        from .random_matrix import Rng, random_gaussian
 
-        omega = random_gaussian((max(min(int(k) + int(oversampling), 128), 1), m), Rng(int(seed)), a.dtype)
-    omega = as_device(omega)
-    if omega.dtype != a.dtype:
-        raise TypeError(f"sketch_column_id_rank_batched: omega is {omega.dtype}, a is {a.dtype}")
-    if omega.dim() not in (2, 3) or (omega.dim() == 3 and omega.shape[0] != count):
-        raise AssertionError("expected omega [l, m] or [count, l, m]")
-    l = omega.shape[-2]
-    obs = omega.stride(0) if omega.dim() == 3 else 0
-    kk = max(min(int(k), l, n), 0)
-    c = torch.empty((count, m, kk), dtype=a.dtype, device=a.device)
-    z = torch.empty((count, kk, n), dtype=a.dtype, device=a.device)
-    ind = torch.empty((count, n), dtype=torch.int64, device=a.device)
-    ranks = torch.empty(count, dtype=torch.int64, device=a.device)
-    y = torch.empty((count, l, n), dtype=a.dtype, device=a.device) if return_sketch else None
-    _lib.default_context().call(f"rc_sketch_column_id_rank_batched_{_lib.suffix(a.dtype)}",
-                                _lib.rc_matrix(a.data_ptr(), m, n, a.stride(1), a.stride(2)), ctypes.c_int64(a.stride(0)),
-                                _lib.rc_matrix(omega.data_ptr(), l, omega.shape[-1], omega.stride(-2), omega.stride(-1)), ctypes.c_int64(obs),
-                                ctypes.c_int32(count), ctypes.c_int64(int(k)), ctypes.c_double(float(tol)),
-                                _lib.rc_matrix(y.data_ptr(), l, n, n, 1) if return_sketch else _lib.mat(None), ctypes.c_int64(l * n),
-                                _lib.rc_matrix(c.data_ptr(), m, kk, kk, 1), ctypes.c_int64(m * kk),
-                                _lib.rc_matrix(z.data_ptr(), kk, n, n, 1), ctypes.c_int64(kk * n), _lib.i64p(ind), _lib.i64p(ranks))
-    return (c, z, ind, ranks, y) if return_sketch else (c, z, ind, ranks)
+def sketch_column_id_rank_batched_complex(a: torch.Tensor, k: int, tol: float = 0.0, omega: Optional[torch.Tensor] = None, oversampling: int = 8,
+                                          seed: int = 0, return_sketch: bool = False):
+    """sketch_column_id_rank_batched for complex tall blocks (rc_sketch_column_id_rank_complex_batched_c64 / _c32): a and omega complex128 or
+    complex64 device tensors of one dtype (lazily conjugated views are materialised); real data and mismatched dtypes raise TypeError.
+    Y = omega a with nothing conjugated: a caller who wants Q^H a passes Q^H.  omega=None draws one shared complex Gaussian of
+    l = min(k + oversampling, 128) rows with rc_random_gaussian_c64 / _c32 at (seed, offset 0): random_gaussian((l, m), Rng(seed), a.dtype).
+    Z, ind and ranks are column_id_rank_batched(Y, k, tol)'s on the complex sketch bit for bit."""
+    return _sketch_column_id_rank_batched("sketch_column_id_rank_batched_complex", True, a, k, tol, omega, oversampling, seed, return_sketch)
 
 
 def packed_bytes(m: int, n: int, k: int, elem_size: int) -> int:

@@ -836,18 +836,7 @@ __global__ __launch_bounds__(BID_THREADS) void k_batched_recompress(BrcArgs<T> a
 // reduction index, or a pitch of 16 modulo 32 along the other: the fragment reads of either image are bank-conflict free); rows past
 // m, columns past n and rows of Omega past l are zeros in LDS, so the MFMA loop has no edge branch.  An element of Y is summed in
 // ascending row order: chunk after chunk, four rows per MFMA: a function of (l, m, n) and the two constants alone.
-constexpr int BSI_ROWS = 32;   // rows of A (= columns of Omega) per LDS chunk
-constexpr int BSI_COLS = 64;   // columns of Y per panel
-constexpr int BSI_PK = BSI_ROWS + 2;                       // pitch of an image with the reduction index fastest
-constexpr int BSI_PA = 80;                                 // pitch of A's image with the column index fastest (16 mod 32, >= BSI_COLS)
-constexpr int BSI_A_ELEMS = BSI_ROWS * BSI_PA;             // A's chunk image: the larger of the two layouts
-static_assert(BSI_A_ELEMS >= BSI_COLS * BSI_PK && BSI_PA >= BSI_COLS, "A chunk image");
-__host__ __device__ constexpr int bsi_po(int l) {          // pitch of Omega's image with the row index fastest (16 mod 32, >= 16 TL)
-    return (((l + 15) & ~15) & 16) ? ((l + 15) & ~15) : ((l + 15) & ~15) + 16;
-}
-__host__ __device__ constexpr int bsi_o_elems(int l) {     // Omega's chunk image: the larger of the two layouts (16 TL rows x BSI_ROWS)
-    return BSI_ROWS * bsi_po(l) > ((l + 15) & ~15) * BSI_PK ? BSI_ROWS * bsi_po(l) : ((l + 15) & ~15) * BSI_PK;
-}
+// (BSI_ROWS, BSI_COLS and the pitches of the chunk images are in rc_gemm.hpp, shared with the complex kernel.)
 // dynamic LDS: [W: n x (l|1), LDS plan only] A chunk [BSI_A_ELEMS] Omega chunk [bsi_o_elems(l)] vn1[n] vn2[n] tile[16 x 17] red[8] | jp[n]
 template <typename T>
 size_t bsi_lds_bytes(int l, int n, bool in_lds) {

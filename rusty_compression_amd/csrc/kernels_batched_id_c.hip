@@ -1,6 +1,7 @@
 // Batched column and two-sided IDs and truncated SVDs of many small same-shaped COMPLEX matrices in one launch
 // (rc_column_id_rank_batched_c64 / _c32, rc_two_sided_id_rank_batched_c64 / _c32, rc_svd_rank_batched_c64 / _c32), and the
-// recompression of complex low-rank factors (rc_lowrank_recompress_complex_batched_c64 / _c32, k_batched_recompress_c below).
+// recompression of complex low-rank factors (rc_lowrank_recompress_complex_batched_c64 / _c32, k_batched_recompress_c below) and the sketched
+// column ID of complex tall blocks (rc_sketch_column_id_rank_complex_batched_c64 / _c32, k_batched_sketch_id_c below).
 //
 // The structure of kernels_batched_id.hip (one persistent workgroup of 256 threads per matrix, the same three device stages, the same
 // grid and workspace rule, bid_grid) with the complex arithmetic of the lone complex path in rc_complex.hip:
@@ -24,6 +25,7 @@
 // of every factor, bit for bit.
 #include "rc_common.hpp"
 #include "rc_device.hpp"
+#include "rc_gemm.hpp"
 
 namespace rc {
 
@@ -139,8 +141,20 @@ __device__ __forceinline__ void bic_apply(cx<R> *W, int ldw, int m, int n, int j
 // ---- the three stages of one factorization, shared by k_batched_id_c and both phases of k_batched_two_sided_c -----------------------
 // (m x n below is the matrix being factored: A for a column ID, C^H for the row side of a two-sided ID)
 
+// the initial (real) column norms of the working copy W (m x n, column c at W + c * ldw) and the identity permutation
+template <typename R>
+__device__ __forceinline__ void bic_norms(const cx<R> *W, int ldw, int m, int n, R *vn1, R *vn2, int *jp, int wv, int lane) {
+    for (int c = wv; c < n; c += BIC_WAVES) {
+        R acc = 0;
+        for (int i = lane; i < m; i += 64) acc += abs2(W[(size_t)c * ldw + i]);
+        acc = wave_sum_dpp(acc);
+        if (lane == 0) { const R nr = sqrt(acc); vn1[c] = nr; vn2[c] = nr; jp[c] = c; }
+    }
+    __syncthreads();
+}
+
 // working copy W[c * ldw + i] = at(i, c), read with the lanes along i (lanes_on_rows) or along c (the input's fast direction),
-// then the initial (real) column norms and the identity permutation
+// then the initial column norms and the identity permutation
 template <typename R, typename At>
 __device__ __forceinline__ void bic_load(cx<R> *W, int ldw, int m, int n, bool lanes_on_rows, At at, R *vn1, R *vn2, int *jp, int wv, int lane) {
     if (lanes_on_rows) {
@@ -151,13 +165,7 @@ __device__ __forceinline__ void bic_load(cx<R> *W, int ldw, int m, int n, bool l
             for (int c = lane; c < n; c += 64) W[(size_t)c * ldw + i] = at(i, c);
     }
     __syncthreads();
-    for (int c = wv; c < n; c += BIC_WAVES) {
-        R acc = 0;
-        for (int i = lane; i < m; i += 64) acc += abs2(W[(size_t)c * ldw + i]);
-        acc = wave_sum_dpp(acc);
-        if (lane == 0) { const R nr = sqrt(acc); vn1[c] = nr; vn2[c] = nr; jp[c] = c; }
-    }
-    __syncthreads();
+    bic_norms(W, ldw, m, n, vn1, vn2, jp, wv, lane);
 }
 
 // truncated pivoted QR of the working copy, at most k steps: pivots in jp (?geqp3's rule), R and the Householder vectors in W (LAPACK
@@ -940,6 +948,200 @@ __global__ __launch_bounds__(BIC_THREADS, 2) void k_batched_recompress_c(BrcCArg
     }
 }
 
+// ---- batched sketched column ID of complex tall blocks (rc_sketch_column_id_rank_complex_batched_c64 / _c32) --------------------
+// k_batched_sketch_id's structure (kernels_batched_id.hip) with the stages above: per block the sketch Y = Omega A (l x n, l <= 128, nothing
+// conjugated) is formed straight into the complex working copy W, then bic_norms, bic_qrcp and bic_z<R, false> run on W with l rows: the same
+// routines on the same values as k_batched_id_c given Y, hence its pivots, rank and Z bit for bit; C is gathered from A.
+//
+// The sketch.  Column panels of BSI_COLS = 64 columns of Y, one 16-column MFMA tile per wave, up to BSC_TILES = 4 of the ceil(l / 16) row
+// tiles of the panel in the wave's accumulators, Re and Im apart (v_mfma_f64_16x16x4_f64 / v_mfma_f32_16x16x4_f32, Acc<R> of rc_gemm.hpp, the
+// real and imaginary parts as separate real operands); l > 64 takes a second pass over the panels for row tiles 4 .. 7.  The panel's rows of A stream through LDS in chunks of BSI_ROWS = 32 rows beside the matching 32
+// columns of Omega.  The images are separate re / im planes, each with the layout and pitches of the real kernel's image (rc_gemm.hpp):
+// a fragment read is then a read of R from one plane, exactly the real kernel's access (pitch 34 along the reduction index, or a pitch of
+// 16 modulo 32 along the other: free of bank conflicts), which interleaved elements would turn into reads at twice the stride; the
+// staging stores pay for it with two stores of R per element.  Zeros fill past m, n and l, so the MFMA loop has no edge branch.
+// Per element each of Re Y and Im Y is one accumulator chain from zero over the ascending rows of A, four rows per instruction, and
+// within a step (the order of kernels_batched_residual_c.hip)
+//     Re takes MFMA(Om_re, A_re) then MFMA(-Om_im, A_im);   Im takes MFMA(Om_re, A_im) then MFMA(Om_im, A_re)
+// (the negation is a sign flip in a register: exact): a function of (l, m, n) and the two constants alone.  Conjugating a and omega
+// negates the second product of Re's pair twice and every product of Im's chain once, and the MFMAs round a sum and its negation to
+// opposite values, so Y comes out conjugated bit for bit (an Im cancelled to zero is +0 either way) and the stages above commute with
+// it; with +0 imaginary parts Re's chain gains only zeros and carries the real kernel's values, and Im Y is zero.
+//
+// Registers: two waves per SIMD (256 registers), which is what the pivoted QR after the sketch needs: it is a chain of short dependent steps,
+// and with one workgroup per CU nothing hides their latency (measured: 1.4 to 1.6 times the blocks per second of the one-wave variant that
+// kept all eight row tiles).  Four row tiles are 2 x 4 x 8 accumulator registers in c64 and 8 + 8 staged complex elements
+// (64 registers); a is read a second time when l > 64, Omega's image holds the 64 rows of one pass.  The chunk loop has no scratch access.
+
+// dynamic LDS: [W: n x (l|1) complex, LDS plan only] tile[8 x 9] complex | A chunk re, im [BSI_A_ELEMS each] Omega chunk re, im
+// [bsc_o_elems(l) each] vn1[n] vn2[n] red[8] real | jp[n]
+constexpr int BSC_TILES = 4;  // row tiles of Y in a wave's accumulators at a time: l > 64 takes a second pass over the panel
+__host__ __device__ constexpr int bsc_o_elems(int l) { return bsi_o_elems(l < 16 * BSC_TILES ? l : 16 * BSC_TILES); }  // one plane of Omega's image
+template <typename R>
+size_t bsc_lds_bytes(int l, int n, bool in_lds) {
+    size_t c = (size_t)BIC_NB * (BIC_NB + 1);
+    if (in_lds) c += (size_t)n * (size_t)(l | 1);
+    return c * sizeof(cx<R>) + ((size_t)2 * BSI_A_ELEMS + (size_t)2 * bsc_o_elems(l) + (size_t)2 * n + 8) * sizeof(R) + (size_t)n * sizeof(int);
+}
+
+template <typename R>
+struct BscArgs {
+    CView<R> a, omega, y, c, z;  // y.p == nullptr: the sketch is not written
+    int64_t abs, obs, ybs, cbs, zbs;
+    int64_t *col_ind, *ranks;
+    cx<R> *ws;
+    double tol;
+    int count, kk;
+    bool w_lds;  // the working copy in LDS (else in the workgroup's workspace slot)
+};
+
+// W[c * ldw + i] = Y[i, c] = sum_r Om[i, r] A[r, c] for the TL row tiles of 16 rows from tile t0 on of the l x n sketch of one block (and Y to
+// Yb when it is not null).
+// AR / OR: the lanes of the staging loads run along the rows of a / of omega (the operand's smaller stride), else along its columns;
+// each thread's elements of a chunk are then a fixed step apart in memory and in the LDS planes, whose offsets are compile-time constants.
+template <typename R, int TL, bool AR, bool OR>
+__device__ __forceinline__ void bsc_sketch(const BscArgs<R> &g, const cx<R> *__restrict__ A, const cx<R> *__restrict__ Om, cx<R> *Yb, cx<R> *W, int ldw, R *As,
+                                           R *Os, int oplane, int t0, int tid, int wv, int lane) {
+    constexpr int PO = bsi_po(16 * TL);
+    constexpr int A_PER = BSI_ROWS * BSI_COLS / BIC_THREADS;    // 8 elements of A per thread and chunk
+    constexpr int O_PER = BSI_ROWS * 16 * TL / BIC_THREADS;     // 2 TL elements of Omega
+    constexpr int A_SR = AR ? 1 : BSI_PA, A_SC = AR ? BSI_PK : 1;   // A's planes: As[r * A_SR + c * A_SC] (re), + BSI_A_ELEMS (im)
+    constexpr int O_SI = OR ? 1 : BSI_PK, O_SR = OR ? PO : 1;       // Omega's planes: Os[i * O_SI + r * O_SR] (re), + oplane (im)
+    const int m = (int)g.a.rows, n = (int)g.a.cols, ltot = (int)g.omega.rows;
+    const int l = ltot - 16 * t0 < 16 * TL ? ltot - 16 * t0 : 16 * TL;  // rows of Omega in this pass, from row 16 t0
+    const int64_t ars = g.a.rs, acs = g.a.cs, ors = g.omega.rs, ocs = g.omega.cs;
+    Om += (int64_t)(16 * t0) * ors;
+    // this thread's elements of a chunk: A[ar + AR_STEP e, ac + AC_STEP e], Om[oi + 16 (e / 2) or 8 e, orr + 16 (e % 2) or 0]
+    const int ar = AR ? (tid & (BSI_ROWS - 1)) : (tid / BSI_COLS), ac = AR ? (tid / BSI_ROWS) : (tid & (BSI_COLS - 1));
+    constexpr int AR_STEP = AR ? 0 : BIC_THREADS / BSI_COLS, AC_STEP = AR ? BIC_THREADS / BSI_ROWS : 0;
+    const int oi = OR ? (tid & 15) : (tid / BSI_ROWS), orr = OR ? (tid >> 4) : (tid & (BSI_ROWS - 1));
+    const int r16 = lane & 15, k4 = lane >> 4;
+    R *as_st = As + ar * A_SR + ac * A_SC, *os_st = Os + oi * O_SI + orr * O_SR;
+    const R *as_ld = As + k4 * A_SR + (wv * 16 + r16) * A_SC, *os_ld = Os + r16 * O_SI + k4 * O_SR;
+    for (int c0 = 0; c0 < n; c0 += BSI_COLS) {
+        typename Acc<R>::type are[TL], aim[TL];
+#pragma unroll
+        for (int i = 0; i < TL; ++i) { are[i] = typename Acc<R>::type{0, 0, 0, 0}; aim[i] = typename Acc<R>::type{0, 0, 0, 0}; }
+        // the chunk at rows m0 .. m0 + 31 into this thread's staging registers
+        cx<R> av[A_PER], ov[O_PER];
+        auto fetch = [&](int m0) {
+            const cx<R> *pa = A + (int64_t)(m0 + ar) * ars + (int64_t)(c0 + ac) * acs;
+            const cx<R> *po = Om + (int64_t)oi * ors + (int64_t)(m0 + orr) * ocs;
+            // the steps between a thread's elements are uniform; hidden from the optimizer here, every address is the thread's one base plus a
+            // scalar offset (otherwise each of the 8 + 2 TL addresses becomes a loop-carried 64-bit register pair of its own)
+            int64_t sa = AR ? AC_STEP * acs : AR_STEP * ars, so_i = ors, so_r = ocs;
+            asm volatile("" : "+s"(sa), "+s"(so_i), "+s"(so_r));
+#pragma unroll
+            for (int e = 0; e < A_PER; ++e) {
+                const bool ok = m0 + ar + AR_STEP * e < m && c0 + ac + AC_STEP * e < n;
+                av[e] = ok ? pa[e * sa] : czero<R>();
+            }
+#pragma unroll
+            for (int e = 0; e < O_PER; ++e) {
+                const int di = OR ? 16 * (e / 2) : 8 * e, dr = OR ? 16 * (e % 2) : 0;
+                const bool ok = oi + di < l && m0 + orr + dr < m;
+                ov[e] = ok ? po[di * so_i + dr * so_r] : czero<R>();
+            }
+        };
+        for (int m0 = 0; m0 < m; m0 += BSI_ROWS) {
+            fetch(m0);
+#pragma unroll
+            for (int e = 0; e < A_PER; ++e) {
+                as_st[AR_STEP * e * A_SR + AC_STEP * e * A_SC] = av[e].re;
+                as_st[AR_STEP * e * A_SR + AC_STEP * e * A_SC + BSI_A_ELEMS] = av[e].im;
+            }
+#pragma unroll
+            for (int e = 0; e < O_PER; ++e) {
+                const int di = OR ? 16 * (e / 2) : 8 * e, dr = OR ? 16 * (e % 2) : 0;
+                os_st[di * O_SI + dr * O_SR] = ov[e].re;
+                os_st[di * O_SI + dr * O_SR + oplane] = ov[e].im;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int ks = 0; ks < BSI_ROWS / 4; ++ks) {
+                const R bre = as_ld[ks * 4 * A_SR], bim = as_ld[ks * 4 * A_SR + BSI_A_ELEMS];
+#pragma unroll
+                for (int i = 0; i < TL; ++i) {
+                    const R ore = os_ld[i * 16 * O_SI + ks * 4 * O_SR], oim = os_ld[i * 16 * O_SI + ks * 4 * O_SR + oplane];
+                    are[i] = Acc<R>::mfma(ore, bre, are[i]);
+                    are[i] = Acc<R>::mfma(-oim, bim, are[i]);
+                    aim[i] = Acc<R>::mfma(ore, bim, aim[i]);
+                    aim[i] = Acc<R>::mfma(oim, bre, aim[i]);
+                }
+            }
+            __syncthreads();  // the chunk images are rewritten by the next chunk
+        }
+        const int col = c0 + wv * 16 + r16;
+#pragma unroll
+        for (int i = 0; i < TL; ++i)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                const int row = (t0 + i) * 16 + Acc<R>::row(lane, reg);
+                if (row < ltot && col < n) {
+                    const cx<R> v{are[i][reg], aim[i][reg]};
+                    W[(size_t)col * ldw + row] = v;
+                    if (Yb) Yb[row * g.y.rs + col * g.y.cs] = v;
+                }
+            }
+    }
+    __syncthreads();
+}
+
+template <typename R, bool AR, bool OR>
+__global__ __launch_bounds__(BIC_THREADS, 2) void k_batched_sketch_id_c(BscArgs<R> g) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const int m = (int)g.a.rows, n = (int)g.a.cols, l = (int)g.omega.rows, kk = g.kk;
+    const int ldw = g.w_lds ? (l | 1) : l;
+    const int oplane = bsc_o_elems(l);
+    cx<R> *lds = reinterpret_cast<cx<R> *>(smem_raw);
+    cx<R> *W = g.w_lds ? lds : g.ws + (size_t)blockIdx.x * (size_t)l * (size_t)n;
+    cx<R>(*tile)[BIC_NB + 1] = reinterpret_cast<cx<R>(*)[BIC_NB + 1]>(lds + (g.w_lds ? (size_t)n * ldw : 0));
+    R *As = reinterpret_cast<R *>(lds + (g.w_lds ? (size_t)n * ldw : 0) + BIC_NB * (BIC_NB + 1));
+    R *Os = As + 2 * BSI_A_ELEMS;
+    R *vn1 = Os + 2 * oplane;
+    R *vn2 = vn1 + n;
+    R *red = vn2 + n;
+    int *jp = reinterpret_cast<int *>(red + 8);
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+
+    for (int b = blockIdx.x; b < g.count; b += gridDim.x) {
+        const cx<R> *__restrict__ A = g.a.p + (int64_t)b * g.abs;
+        const cx<R> *__restrict__ Om = g.omega.p + (int64_t)b * g.obs;
+        cx<R> *Yb = g.y.p ? g.y.p + (int64_t)b * g.ybs : nullptr;
+        // ---- the sketch into W (and y), at most BSC_TILES row tiles per pass over the panels, one instance per number of 16-row tiles of a pass ----
+        for (int t0 = 0; 16 * t0 < l; t0 += BSC_TILES) {
+            const int rest = ((l + 15) >> 4) - t0;
+            switch (rest < BSC_TILES ? rest : BSC_TILES) {
+                case 1: bsc_sketch<R, 1, AR, OR>(g, A, Om, Yb, W, ldw, As, Os, oplane, t0, tid, wv, lane); break;
+                case 2: bsc_sketch<R, 2, AR, OR>(g, A, Om, Yb, W, ldw, As, Os, oplane, t0, tid, wv, lane); break;
+                case 3: bsc_sketch<R, 3, AR, OR>(g, A, Om, Yb, W, ldw, As, Os, oplane, t0, tid, wv, lane); break;
+                default: bsc_sketch<R, 4, AR, OR>(g, A, Om, Yb, W, ldw, As, Os, oplane, t0, tid, wv, lane); break;
+            }
+        }
+        // ---- the column ID of Y: k_batched_id_c's stages on l rows --------------------------------------------------------------------
+        bic_norms(W, ldw, l, n, vn1, vn2, jp, wv, lane);
+        const int r = bic_qrcp(W, ldw, l, n, kk, g.tol, jp, vn1, vn2, red, tid, wv, lane);
+        for (int p = tid; p < n; p += BIC_THREADS) g.col_ind[(int64_t)b * n + p] = jp[p];
+        if (tid == 0) g.ranks[b] = r;
+        // C[:, j] = A[:, jp[j]] (zero for j >= r), the lanes along a's smaller stride
+        cx<R> *Cb = g.c.p + (int64_t)b * g.cbs;
+        if (g.a.rs <= g.a.cs) {
+            for (int j = wv; j < kk; j += BIC_WAVES) {
+                const cx<R> *src = A + (int64_t)jp[j] * g.a.cs;
+                for (int i = lane; i < m; i += 64) Cb[i * g.c.rs + j * g.c.cs] = j < r ? src[i * g.a.rs] : czero<R>();
+            }
+        } else {
+            const int total = m * kk;  // <= 65536 * 128
+            for (int idx = tid; idx < total; idx += BIC_THREADS) {
+                const int i = idx / kk, j = idx - i * kk;
+                Cb[i * g.c.rs + j * g.c.cs] = j < r ? A[i * g.a.rs + (int64_t)jp[j] * g.a.cs] : czero<R>();
+            }
+        }
+        bic_z<R, false>(W, ldw, n, r, kk, jp, tile, g.z.p + (int64_t)b * g.zbs, g.z.rs, g.z.cs, tid);
+        __syncthreads();  // W, jp and the norms are rewritten by the next block
+    }
+}
+
 }  // namespace
 
 // the real kernels' launch rule (bid_grid, BID_MAX_LDS): LDS variant when the complex working copy fits, else the workspace variant
@@ -1084,6 +1286,56 @@ void batched_lowrank_recompress_c(rc_context *c, const rc_matrix &left_, int64_t
     a.l_lds = l_lds; a.r_lds = r_lds; a.v_lds = v_lds; a.g_lds = g_lds;
     hipLaunchKernelGGL(k_batched_recompress_c<R>, dim3((unsigned)grid), dim3(BIC_THREADS), lds, c->stream, a);
 }
+
+// the sketched column ID of a batch of complex blocks: W (l x n complex) in LDS when it fits next to the chunk images, else in the workgroup's
+// slot of the grid-bounded workspace: the plan only moves W's base pointer and pitch, so it cannot change a block's bits.  Four instances of the
+// kernel, by the index of a and of omega that the staging loads' lanes run along; each component of Y is summed in the same order in all four.
+template <typename R>
+void batched_sketch_column_id_c(rc_context *c, const rc_matrix &a_, int64_t abs, const rc_matrix &omega_, int64_t obs, int32_t count, int64_t kk, double tol,
+                                const rc_matrix &y_, int64_t ybs, const rc_matrix &cm_, int64_t cbs, const rc_matrix &z_, int64_t zbs, int64_t *col_ind,
+                                int64_t *ranks) {
+    const CView<R> a = cview<R>(a_), omega = cview<R>(omega_), y = cview<R>(y_), cm = cview<R>(cm_), z = cview<R>(z_);
+    const int m = (int)a.rows, n = (int)a.cols, l = (int)omega.rows;
+    if (count <= 0) return;
+    const bool w_lds = bsc_lds_bytes<R>(l, n, true) <= BID_MAX_LDS;
+    const size_t lds = bsc_lds_bytes<R>(l, n, w_lds);
+    // the lanes of the staging loads along the smaller stride of a and of omega (the real call's rule)
+    const bool a_rows = a.rs <= a.cs, o_rows = omega.rs < omega.cs;
+    const void *kerns[4] = {reinterpret_cast<const void *>(k_batched_sketch_id_c<R, false, false>), reinterpret_cast<const void *>(k_batched_sketch_id_c<R, false, true>),
+                            reinterpret_cast<const void *>(k_batched_sketch_id_c<R, true, false>), reinterpret_cast<const void *>(k_batched_sketch_id_c<R, true, true>)};
+    const int which = (a_rows ? 2 : 0) + (o_rows ? 1 : 0);
+    // per device, once: the LDS cap, and each instance's scratch bytes per thread for the label (a compiler that starts to spill shows up in every
+    // profile and in tools/batched_sketch_id_bench.py --complex)
+    static bool attr_set[64] = {};
+    static int scratch_of[64][4] = {};
+    if (!attr_set[c->device & 63]) {
+        for (int i = 0; i < 4; ++i) {
+            RC_HIP(hipFuncSetAttribute(kerns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)BID_MAX_LDS));
+            hipFuncAttributes fa;
+            RC_HIP(hipFuncGetAttributes(&fa, kerns[i]));
+            scratch_of[c->device & 63][i] = (int)fa.localSizeBytes;
+        }
+        attr_set[c->device & 63] = true;
+    }
+    const size_t per = w_lds ? 0 : (size_t)l * (size_t)n * sizeof(cx<R>);
+    int64_t slots = 0;
+    const int64_t grid = bid_grid(c, kerns[which], lds, per, count, &slots);
+    ProfScope ps(c, "op:batched_sketch_id_c %dx%d k=%lld count=%d grid=%lld slots=%lld plan=W:%s,l=%d,rows=%d,cols=%d,scratch=%d", m, n, (long long)kk,
+                 (int)count, (long long)grid, (long long)slots, w_lds ? "lds" : "ws", l, BSI_ROWS, BSI_COLS, scratch_of[c->device & 63][which]);
+    BscArgs<R> g;
+    g.a = a; g.omega = omega; g.y = y; g.c = cm; g.z = z;
+    g.abs = abs; g.obs = obs; g.ybs = ybs; g.cbs = cbs; g.zbs = zbs;
+    g.col_ind = col_ind; g.ranks = ranks;
+    g.ws = per ? c->alloc<cx<R>>((size_t)grid * (size_t)l * (size_t)n) : nullptr;
+    g.tol = tol; g.count = (int)count; g.kk = (int)kk; g.w_lds = w_lds;
+    void *args[] = {&g};
+    RC_HIP(hipLaunchKernel(kerns[which], dim3((unsigned)grid), dim3(BIC_THREADS), args, lds, c->stream));
+}
+
+template void batched_sketch_column_id_c<double>(rc_context *, const rc_matrix &, int64_t, const rc_matrix &, int64_t, int32_t, int64_t, double, const rc_matrix &,
+                                                 int64_t, const rc_matrix &, int64_t, const rc_matrix &, int64_t, int64_t *, int64_t *);
+template void batched_sketch_column_id_c<float>(rc_context *, const rc_matrix &, int64_t, const rc_matrix &, int64_t, int32_t, int64_t, double, const rc_matrix &,
+                                                int64_t, const rc_matrix &, int64_t, const rc_matrix &, int64_t, int64_t *, int64_t *);
 
 template void batched_column_id_c<double>(rc_context *, const rc_matrix &, int64_t, int32_t, int64_t, double, const rc_matrix &, int64_t, const rc_matrix &,
                                           int64_t, int64_t *, int64_t *);

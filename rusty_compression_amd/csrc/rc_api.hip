@@ -1249,6 +1249,30 @@ void check_lowrank_recompress_batched(Mat<T> left, Mat<T> mid, Mat<T> right, int
     if (count > 0) RC_REQUIRE(left.p && right.p && u.p && s_out && vt.p && ranks, RC_INVALID_ARGUMENT, "%s: null pointer", who);
 }
 
+// the argument checks of rc_sketch_column_id_rank_batched_* and rc_sketch_column_id_rank_complex_batched_*: the views carry the shapes and strides (in
+// elements of the scalar type), the pointers only their null-ness.  Returns kk = min(k, l, n).
+template <typename T>
+int64_t check_sketch_column_id_rank_batched(Mat<T> a, Mat<T> omega, int32_t count, int64_t k, double tol, Mat<T> y, int64_t ybs, Mat<T> cm, int64_t cbs,
+                                            Mat<T> z, int64_t zbs, const int64_t *col_ind, const int64_t *ranks) {
+    const char *who = "sketch_column_id_rank_batched";
+    const int64_t m = a.rows, n = a.cols, l = omega.rows;
+    RC_REQUIRE(count >= 0, RC_INVALID_ARGUMENT, "%s: count = %d < 0", who, (int)count);
+    RC_REQUIRE(m >= 1 && m <= 65536 && n >= 1 && n <= 512 && l >= 1 && l <= 128 && k >= 1 && k <= 128, RC_INVALID_ARGUMENT,
+               "%s: needs 1 <= m <= 65536, 1 <= n <= 512, 1 <= l <= 128 and 1 <= k <= 128 (got a %lld x %lld, omega %lld x %lld, k = %lld)", who, (long long)m,
+               (long long)n, (long long)l, (long long)omega.cols, (long long)k);
+    RC_REQUIRE(omega.cols == m, RC_INVALID_ARGUMENT, "%s: a has %lld rows but omega has %lld columns", who, (long long)m, (long long)omega.cols);
+    RC_REQUIRE(tol < 1.0 && 0.0 <= tol, RC_INVALID_ARGUMENT, "Require 0 <= tol < 1.0");
+    const int64_t kk = std::min(k, std::min(l, n));
+    RC_REQUIRE(cm.rows == m && cm.cols == kk && z.rows == kk && z.cols == n, RC_INVALID_ARGUMENT,
+               "%s: c must be %lld x %lld and z %lld x %lld (k clamped to min(l, n))", who, (long long)m, (long long)kk, (long long)kk, (long long)n);
+    RC_REQUIRE(!y.p || (y.rows == l && y.cols == n), RC_INVALID_ARGUMENT, "%s: y must be %lld x %lld (got %lld x %lld)", who, (long long)l, (long long)n,
+               (long long)y.rows, (long long)y.cols);
+    check_batch_stride(who, "c", cbs, cm, count);
+    check_batch_stride(who, "z", zbs, z, count);
+    if (y.p) check_batch_stride(who, "y", ybs, y, count);
+    if (count > 0) RC_REQUIRE(a.p && omega.p && cm.p && z.p && col_ind && ranks, RC_INVALID_ARGUMENT, "%s: null pointer", who);
+    return kk;
+}
 template int64_t check_column_id_rank_batched<double>(Mat<double>, int32_t, int64_t, double, Mat<double>, int64_t, Mat<double>, int64_t, const int64_t *,
                                                       const int64_t *);
 template int64_t check_column_id_rank_batched<float>(Mat<float>, int32_t, int64_t, double, Mat<float>, int64_t, Mat<float>, int64_t, const int64_t *,
@@ -1272,6 +1296,11 @@ template void check_lowrank_recompress_batched<double>(Mat<double>, Mat<double>,
                                                        Mat<double>, int64_t, const int64_t *);
 template void check_lowrank_recompress_batched<float>(Mat<float>, Mat<float>, Mat<float>, int32_t, int64_t, double, Mat<float>, int64_t, const float *, Mat<float>,
                                                       int64_t, const int64_t *);
+
+template int64_t check_sketch_column_id_rank_batched<double>(Mat<double>, Mat<double>, int32_t, int64_t, double, Mat<double>, int64_t, Mat<double>, int64_t,
+                                                             Mat<double>, int64_t, const int64_t *, const int64_t *);
+template int64_t check_sketch_column_id_rank_batched<float>(Mat<float>, Mat<float>, int32_t, int64_t, double, Mat<float>, int64_t, Mat<float>, int64_t,
+                                                            Mat<float>, int64_t, const int64_t *, const int64_t *);
 
 }  // namespace rc
 
@@ -1340,23 +1369,7 @@ void lowrank_recompress_batched(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> 
 template <typename T>
 void sketch_column_id_rank_batched(rc_context *c, Mat<T> a, int64_t abs, Mat<T> omega, int64_t obs, int32_t count, int64_t k, double tol, Mat<T> y, int64_t ybs,
                                    Mat<T> cm, int64_t cbs, Mat<T> z, int64_t zbs, int64_t *col_ind, int64_t *ranks) {
-    const char *who = "sketch_column_id_rank_batched";
-    const int64_t m = a.rows, n = a.cols, l = omega.rows;
-    RC_REQUIRE(count >= 0, RC_INVALID_ARGUMENT, "%s: count = %d < 0", who, (int)count);
-    RC_REQUIRE(m >= 1 && m <= 65536 && n >= 1 && n <= 512 && l >= 1 && l <= 128 && k >= 1 && k <= 128, RC_INVALID_ARGUMENT,
-               "%s: needs 1 <= m <= 65536, 1 <= n <= 512, 1 <= l <= 128 and 1 <= k <= 128 (got a %lld x %lld, omega %lld x %lld, k = %lld)", who, (long long)m,
-               (long long)n, (long long)l, (long long)omega.cols, (long long)k);
-    RC_REQUIRE(omega.cols == m, RC_INVALID_ARGUMENT, "%s: a has %lld rows but omega has %lld columns", who, (long long)m, (long long)omega.cols);
-    RC_REQUIRE(tol < 1.0 && 0.0 <= tol, RC_INVALID_ARGUMENT, "Require 0 <= tol < 1.0");
-    const int64_t kk = std::min(k, std::min(l, n));
-    RC_REQUIRE(cm.rows == m && cm.cols == kk && z.rows == kk && z.cols == n, RC_INVALID_ARGUMENT,
-               "%s: c must be %lld x %lld and z %lld x %lld (k clamped to min(l, n))", who, (long long)m, (long long)kk, (long long)kk, (long long)n);
-    RC_REQUIRE(!y.p || (y.rows == l && y.cols == n), RC_INVALID_ARGUMENT, "%s: y must be %lld x %lld (got %lld x %lld)", who, (long long)l, (long long)n,
-               (long long)y.rows, (long long)y.cols);
-    check_batch_stride(who, "c", cbs, cm, count);
-    check_batch_stride(who, "z", zbs, z, count);
-    if (y.p) check_batch_stride(who, "y", ybs, y, count);
-    if (count > 0) RC_REQUIRE(a.p && omega.p && cm.p && z.p && col_ind && ranks, RC_INVALID_ARGUMENT, "%s: null pointer", who);
+    const int64_t kk = check_sketch_column_id_rank_batched(a, omega, count, k, tol, y, ybs, cm, cbs, z, zbs, col_ind, ranks);
     if (count == 0) return;
     batched_sketch_column_id(c, a, abs, omega, obs, count, kk, tol, y, ybs, cm, cbs, z, zbs, col_ind, ranks);
 }

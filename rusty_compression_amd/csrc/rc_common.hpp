@@ -284,6 +284,14 @@ template <typename T> void check_lowrank_recompress_batched(Mat<T> left, Mat<T> 
 // clamped; col_ind count x n, ranks count (arguments checked by the caller)
 template <typename T> void batched_sketch_column_id(rc_context *c, Mat<T> a, int64_t abs, Mat<T> omega, int64_t obs, int32_t count, int64_t kk, double tol,
                                                     Mat<T> y, int64_t ybs, Mat<T> cm, int64_t cbs, Mat<T> z, int64_t zbs, int64_t *col_ind, int64_t *ranks);
+// the complex twin (kernels_batched_id_c.hip), R = double (c64) or float (c32): interleaved-complex views, strides in complex elements, nothing conjugated
+template <typename R> void batched_sketch_column_id_c(rc_context *c, const rc_matrix &a, int64_t abs, const rc_matrix &omega, int64_t obs, int32_t count,
+                                                      int64_t kk, double tol, const rc_matrix &y, int64_t ybs, const rc_matrix &cm, int64_t cbs,
+                                                      const rc_matrix &z, int64_t zbs, int64_t *col_ind, int64_t *ranks);
+// the argument checks of rc_sketch_column_id_rank_batched_* and rc_sketch_column_id_rank_complex_batched_* (rc_api.hip), shared by every scalar type like
+// those above.  Return kk = min(k, l, n); the caller returns when count == 0.
+template <typename T> int64_t check_sketch_column_id_rank_batched(Mat<T> a, Mat<T> omega, int32_t count, int64_t k, double tol, Mat<T> y, int64_t ybs, Mat<T> cm,
+                                                                  int64_t cbs, Mat<T> z, int64_t zbs, const int64_t *col_ind, const int64_t *ranks);
 // the residual of such factors against the blocks they approximate, in one rank-aware launch (kernels_batched_residual.hip): block i is a (m x n), left
 // (m x K), mid (K x K, p == nullptr: none), right (K x n) and e (m x n, p == nullptr: not written) each moved by i times its batch stride, s + i * s_stride
 // its K real scales (nullptr: none), ranks count device values (nullptr: every rank is K); err and nrm (nullptr: not written) count values: ||a_i - left

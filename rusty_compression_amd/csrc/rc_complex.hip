@@ -1432,6 +1432,21 @@ extern "C" {
             batched_lowrank_recompress_c<R>(ctx, left, left_batch_stride, mid, mid_batch_stride, s, s_stride, right, right_batch_stride,  \
                                             in_ranks, count, k, (double)tol, u, u_batch_stride, s_out, vt, vt_batch_stride, ranks);       \
         });                                                                                                                               \
+    }                                                                                                                                     \
+    /* the sketched column ID of complex tall blocks (kernels_batched_id_c.hip): the real entry point's checks on views of the same */   \
+    /* shapes; y = omega a with nothing conjugated */                                                                                     \
+    rc_status rc_sketch_column_id_rank_complex_batched_##SUF(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega,       \
+                                                             int64_t omega_batch_stride, int32_t count, int64_t k, double tol, rc_matrix y, \
+                                                             int64_t y_batch_stride, rc_matrix c, int64_t c_batch_stride, rc_matrix z,    \
+                                                             int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks) {                  \
+        return guarded_c(ctx, [&] {                                                                                                       \
+            const int64_t kk = check_sketch_column_id_rank_batched<R>(shape_of<R>(a), shape_of<R>(omega), count, k, tol, shape_of<R>(y),  \
+                                                                      y_batch_stride, shape_of<R>(c), c_batch_stride, shape_of<R>(z),     \
+                                                                      z_batch_stride, col_ind, ranks);                                    \
+            if (count == 0) return;                                                                                                       \
+            batched_sketch_column_id_c<R>(ctx, a, a_batch_stride, omega, omega_batch_stride, count, kk, tol, y, y_batch_stride, c,        \
+                                          c_batch_stride, z, z_batch_stride, col_ind, ranks);                                             \
+        });                                                                                                                               \
     }
 
 RC_DEFINE_COMPLEX(c64, double, rc_complex64)

@@ -27,6 +27,21 @@ template <> struct Acc<float> {
     static __device__ inline int row(int lane, int reg) { return 4 * (lane >> 4) + reg; }
 };
 
+// The LDS chunk images of the batched sketch Omega A, shared by its real kernel (kernels_batched_id.hip) and its complex one (kernels_batched_id_c.hip,
+// one image of these pitches per component): BSI_ROWS rows of A beside the matching columns of Omega, column panels of BSI_COLS columns.
+constexpr int BSI_ROWS = 32;   // rows of A (= columns of Omega) per LDS chunk
+constexpr int BSI_COLS = 64;   // columns of Y per panel
+constexpr int BSI_PK = BSI_ROWS + 2;                       // pitch of an image with the reduction index fastest
+constexpr int BSI_PA = 80;                                 // pitch of A's image with the column index fastest (16 mod 32, >= BSI_COLS)
+constexpr int BSI_A_ELEMS = BSI_ROWS * BSI_PA;             // A's chunk image: the larger of the two layouts
+static_assert(BSI_A_ELEMS >= BSI_COLS * BSI_PK && BSI_PA >= BSI_COLS, "A chunk image");
+__host__ __device__ constexpr int bsi_po(int l) {          // pitch of Omega's image with the row index fastest (16 mod 32, >= 16 TL)
+    return (((l + 15) & ~15) & 16) ? ((l + 15) & ~15) : ((l + 15) & ~15) + 16;
+}
+__host__ __device__ constexpr int bsi_o_elems(int l) {     // Omega's chunk image: the larger of the two layouts (16 TL rows x BSI_ROWS)
+    return BSI_ROWS * bsi_po(l) > ((l + 15) & ~15) * BSI_PK ? BSI_ROWS * bsi_po(l) : ((l + 15) & ~15) * BSI_PK;
+}
+
 template <typename T>
 struct GemmArgs {
     const T *a, *b;
