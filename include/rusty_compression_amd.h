@@ -16,7 +16,13 @@
  *    data[i*row_stride + j*col_stride], strides in elements).  Any layout is
  *    accepted (C order, Fortran order, transposed views); inputs are never
  *    modified (reference: every trait method borrows views and returns owned
- *    arrays).  Outputs are caller-allocated.
+ *    arrays).  Outputs are caller-allocated.  "Any layout" holds for outputs as
+ *    it does for inputs: a padded view (odd pitch included), a view that starts
+ *    at any element offset of its allocation (no alignment beyond the scalar's
+ *    own), and a view with both strides non-unit are written like a fresh C-order
+ *    array, and no element outside the view is ever written
+ *    (tests/test_gpu_output_views.py; overlapping views and zero or negative
+ *    strides on outputs are not supported).
  *  - `_f64` / `_f32` select the scalar type (reference macros instantiate
  *    f32/f64/c32/c64; complex is out of scope).
  *  - Index vectors are int64, 0-based, in device memory (reference: usize,
