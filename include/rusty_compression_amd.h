@@ -177,7 +177,9 @@ rc_status rc_graph_destroy(rc_context *ctx, void *graph_exec);
 /* RC_OPT_FUSED_CONSUMERS (default 1): rc_rsvd_id_* with both consumers wanted runs the pivoted QR of B = Q^H A (k x n) and the
  * Jacobi SVD of the k x k core of B in ONE launch: the tall QR of B^T first, then one kernel whose first workgroups are the
  * cooperative pivoted QR (one stage over all steps) and whose last two are the Jacobi's producer and consumer, then the tails of
- * both branches.  The two factorizations are independent, and side by side they hold one of the process's kernel slots for the
+ * both branches: R, the orthogonal factor Q_b of B and the Z of the column ID come out of ONE further launch (they read only the
+ * factored matrix, its pivots and tau, and not each other), and the Jacobi writes the left vectors of the core where U = Q U_b
+ * reads them.  The two factorizations are independent, and side by side they hold one of the process's kernel slots for the
  * longer of the two instead of two slots for the sum.  Taken for f64, k = 128, shapes the cooperative QR and the tall-skinny path
  * support, RC_OPT_FORK_BRANCHES off and min(RC_OPT_CONCURRENCY_HINT, RC_OPT_KERNEL_SLOTS) < 8; every other call, and 0, run the
  * pivoted-QR / ID branch first and the SVD branch after it.  Certificates keep their meaning (health bits 1, 2, 4, 8, 16). */

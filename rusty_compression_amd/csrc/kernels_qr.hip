@@ -351,16 +351,33 @@ void geqp3_inplace(rc_context *c, Mat<T> w, int64_t kmax, bool pivot, int64_t *j
 // R extraction: r(i, p) = (i <= p) ? w(i, jpvt[p]) : 0   (?geqp3 output upper
 // trapezoid in position order; IntoTriangular, pivoted_qr.rs:100-102)
 // ---------------------------------------------------------------------------
+// (wg of nwg workgroups of nthr threads: the kernel below is the whole grid, k_rsvd_id_tails gives a range of its workgroups)
 template <typename T>
-__global__ __launch_bounds__(256) void k_extract_r(Mat<T> w, const int64_t *jpvt, Mat<T> r) {
+__device__ __forceinline__ void extract_r_body(Mat<T> w, const int64_t *jpvt, Mat<T> r, int64_t wg, int64_t nwg, int tid, int nthr) {
     const bool col_fast = (r.cs <= r.rs);
     const int64_t total = r.rows * r.cols;
-    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
-        int64_t i, p;
-        if (col_fast) { i = e / r.cols; p = e - i * r.cols; }
-        else { p = e / r.rows; i = e - p * r.rows; }
-        r.at(i, p) = (i <= p) ? w.p[jpvt[p] * w.cs + i] : (T)0;
+    constexpr int U = 4;  // entries in flight per thread (each is two dependent loads: the pivot, then the entry)
+    const int64_t stride = nwg * nthr;
+    for (int64_t e0 = wg * (int64_t)nthr + tid; e0 < total; e0 += stride * U) {
+        T val[U];
+        T *dst[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t e = e0 + u * stride < total ? e0 + u * stride : e0;
+            int64_t i, p;
+            if (col_fast) { i = e / r.cols; p = e - i * r.cols; }
+            else { p = e / r.rows; i = e - p * r.rows; }
+            dst[u] = &r.at(i, p);
+            val[u] = (i <= p) ? w.p[jpvt[p] * w.cs + i] : (T)0;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (e0 + u * stride < total) *dst[u] = val[u];
     }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void k_extract_r(Mat<T> w, const int64_t *jpvt, Mat<T> r) {
+    extract_r_body<T>(w, jpvt, r, blockIdx.x, gridDim.x, threadIdx.x, blockDim.x);
 }
 template <typename T>
 void extract_r(rc_context *c, Mat<T> w, const int64_t *jpvt, Mat<T> r) {
@@ -441,20 +458,32 @@ __global__ __launch_bounds__(256) void k_form_q_general(Mat<T> w, const int64_t 
 // short matrices (m <= 128, at most 128 columns of Q): ONE workgroup.  All k reflectors are staged in LDS
 // with one bulk load; 8 lanes per output column keep the column in registers, so the k dependent
 // reflector applications cost LDS broadcasts only -- one CU instead of one workgroup per column.
+// As a device function: workgroup wg of the role owns the nthr / 8 output columns from wg * (nthr / 8) on and stages the
+// reflectors in its own LDS (smem_raw); the kernel below is the one-workgroup case.
 template <typename T, int NE>
-__global__ __launch_bounds__(1024) void k_form_q_small(Mat<T> w, const int64_t *jpvt, const T *tau, int k, Mat<T> qw) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+__device__ __forceinline__ void form_q_small_body(Mat<T> w, const int64_t *jpvt, const T *tau, int k, Mat<T> qw, char *smem_raw, int wg, int tid, int nthr) {
     T *V = reinterpret_cast<T *>(smem_raw);  // V[j * 8 * NE + i] = v_j(i): zero above the diagonal, one on it
     T *tl = V + (size_t)k * 8 * NE;
     const int m = (int)w.rows;
     constexpr int LD = 8 * NE;
-    for (int e = threadIdx.x; e < k * LD; e += blockDim.x) {
-        const int j = e / LD, i = e - j * LD;
-        V[e] = (i < j || i >= m) ? (T)0 : (i == j) ? (T)1 : w.p[jpvt[j] * w.cs + i];
+    // only the reflectors the workgroup's columns meet (column cq meets H_j, j <= cq); U loads in flight per thread and round
+    const int kst = min(k, (wg + 1) * (nthr >> 3));
+    constexpr int U = 8;
+    for (int e0 = tid; e0 < kst * LD; e0 += nthr * U) {
+        T val[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int e = e0 + u * nthr;
+            const int j = min(e / LD, kst - 1), i = e & (LD - 1);
+            val[u] = (i < j || i >= m) ? (T)0 : (i == j) ? (T)1 : w.p[jpvt[j] * w.cs + i];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (e0 + u * nthr < kst * LD) V[e0 + u * nthr] = val[u];
     }
-    for (int j = threadIdx.x; j < k; j += blockDim.x) tl[j] = tau[j];
+    for (int j = tid; j < k; j += nthr) tl[j] = tau[j];
     __syncthreads();
-    const int l8 = threadIdx.x & 7, cq = threadIdx.x >> 3;
+    const int l8 = tid & 7, cq = wg * (nthr >> 3) + (tid >> 3);
     if (cq >= qw.cols) return;
     T x[NE];
 #pragma unroll
@@ -481,6 +510,11 @@ __global__ __launch_bounds__(1024) void k_form_q_small(Mat<T> w, const int64_t *
         const int i = l8 + 8 * e;
         if (i < m) out[i] = x[e];
     }
+}
+template <typename T, int NE>
+__global__ __launch_bounds__(1024) void k_form_q_small(Mat<T> w, const int64_t *jpvt, const T *tau, int k, Mat<T> qw) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    form_q_small_body<T, NE>(w, jpvt, tau, k, qw, smem_raw, 0, threadIdx.x, blockDim.x);
 }
 
 // ---- compact-WY form-Q for tall matrices: Q = (I - V T V^T) [I ; 0] as three GEMMs ----
@@ -668,13 +702,17 @@ void trsm_upper(rc_context *c, Mat<T> t, Mat<T> b) {
 // unchecked kernel's.
 template <bool CHECKED> struct IdzCheck {};
 template <> struct IdzCheck<true> { const int64_t *inv; int *health; };
-template <typename T, bool FROM_R, bool CHECKED = false>
-__global__ __launch_bounds__(256) void k_id_z(Mat<T> w, const int64_t *jpvt, int64_t k, Mat<T> z, IdzCheck<CHECKED> chk = {}) {
+constexpr int kIdzNB = 16;  // back-substitution tile
+// Workgroup wg of the role solves the positions wg * nthr .. of the pivoted order; tile is the workgroup's LDS tile.  jtri: where
+// the tile loads of the ?geqp3-format variant read jpvt[0 .. k-1] (the triangle's columns) -- jpvt itself, or a copy in LDS, which
+// takes one of the two dependent global loads off each of the tiles a workgroup stages one after the other.
+template <typename T, bool FROM_R, bool CHECKED>
+__device__ __forceinline__ void id_z_body(Mat<T> w, const int64_t *jpvt, const int64_t *jtri, int64_t k, Mat<T> z, IdzCheck<CHECKED> chk, T (*tile)[kIdzNB + 1], int64_t wg,
+                                          int tid, int nthr) {
     static_assert(FROM_R || !CHECKED, "the ?geqp3-format variant only ever sees a jpvt the library wrote");
-    constexpr int NB = 16;
-    __shared__ T tile[NB][NB + 1];
+    constexpr int NB = kIdzNB;
     const int64_t n = w.cols;
-    const int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;  // position in the pivoted order
+    const int64_t p = wg * (int64_t)nthr + tid;  // position in the pivoted order
     bool owns = p < n;                                                  // CHECKED: ... and this position is the one writer of its column
     if constexpr (CHECKED) {
         if (owns && chk.inv[p] < 0) {
@@ -690,7 +728,7 @@ __global__ __launch_bounds__(256) void k_id_z(Mat<T> w, const int64_t *jpvt, int
     const T *bcol = FROM_R ? w.p + (inside ? p : 0) * w.cs : w.p + dc * w.cs;  // R12[:, p] (rows 0 .. k-1 of the physical column)
     const int64_t brs = FROM_R ? w.rs : 1;
     const int64_t nblk = (k + NB - 1) / NB;
-    const int ti = threadIdx.x / NB, tj = threadIdx.x % NB;
+    const int ti = tid / NB, tj = tid % NB;
     if (inside && p < k)
         for (int64_t i = 0; i < k; ++i) z.at(i, dc) = (i == p) ? (T)1 : (T)0;
     for (int64_t bi = nblk - 1; bi >= 0; --bi) {
@@ -703,7 +741,7 @@ __global__ __launch_bounds__(256) void k_id_z(Mat<T> w, const int64_t *jpvt, int
             __syncthreads();
             {
                 const int64_t i = r0 + ti, l = c0 + tj;
-                tile[ti][tj] = (i < k && l < k && i <= l) ? (FROM_R ? w.at(i, l) : w.p[jpvt[l] * w.cs + i]) : (T)0;
+                tile[ti][tj] = (i < k && l < k && i <= l) ? (FROM_R ? w.at(i, l) : w.p[jtri[l] * w.cs + i]) : (T)0;
             }
             __syncthreads();
             if (bj > bi) {
@@ -731,6 +769,56 @@ __global__ __launch_bounds__(256) void k_id_z(Mat<T> w, const int64_t *jpvt, int
                 if (r0 + ii < k) z.at(r0 + ii, dc) = acc[ii];
         }
     }
+}
+template <typename T, bool FROM_R, bool CHECKED = false>
+__global__ __launch_bounds__(256) void k_id_z(Mat<T> w, const int64_t *jpvt, int64_t k, Mat<T> z, IdzCheck<CHECKED> chk = {}) {
+    __shared__ T tile[kIdzNB][kIdzNB + 1];
+    id_z_body<T, FROM_R, CHECKED>(w, jpvt, jpvt, k, z, chk, tile, blockIdx.x, threadIdx.x, blockDim.x);
+}
+
+// ---------------------------------------------------------------------------
+// The tails of the fused QRCP/Jacobi launch of rsvd_id_consumers_fused in ONE launch: Z, Q_b and R all read only the factored
+// matrix wf, its pivots and tau, and none reads what another writes (Z is solved from wf, not from R: k_id_z<T, false>, the same
+// bits).  Workgroups take a role by blockIdx.x range; the roles exchange nothing (no flags, no atomics, no waits):
+//   [0, nz)            Z role: the body of k_id_z<T, false>, first so that its workgroups (the longest) are dispatched first
+//   [nz, nz + nq)      Q_b role: the body of k_form_q_small<T, NE>, 32 output columns per workgroup, reflectors in its own LDS
+//   [nz + nq, grid)    R role: the body of k_extract_r, grid-stride over its workgroups
+// Dynamic LDS is what the Q_b role needs; the other roles ignore it.
+// ---------------------------------------------------------------------------
+template <typename T, int NE>
+__global__ __launch_bounds__(256) void k_rsvd_id_tails(Mat<T> w, const int64_t *jpvt, const T *tau, int k, Mat<T> z, Mat<T> qw, Mat<T> r, int nz, int nq) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    __shared__ T tile[kIdzNB][kIdzNB + 1];
+    __shared__ int64_t jtri[8 * NE];  // (k <= 8 NE: the rows a column of the Q_b role holds)
+    const int wg = (int)blockIdx.x, tid = (int)threadIdx.x;
+    if (wg < nz) {
+        for (int j = tid; j < k; j += 256) jtri[j] = jpvt[j];
+        __syncthreads();
+        id_z_body<T, false, false>(w, jpvt, jtri, k, z, IdzCheck<false>{}, tile, wg, tid, 256);
+    }
+    else if (wg < nz + nq) form_q_small_body<T, NE>(w, jpvt, tau, k, qw, smem_raw, wg - nz, tid, 256);
+    else extract_r_body<T>(w, jpvt, r, wg - nz - nq, (int64_t)gridDim.x - nz - nq, tid, 256);
+}
+// wf: k x n in the ?geqp3 format (column-major, k steps done), 64 < k <= 128 < n; qb: k x k column-major; r: k x n; z: k x n or
+// empty (then the launch has no Z role)
+template <typename T>
+void rsvd_id_tails(rc_context *c, Mat<T> wf, const int64_t *jpvt, const T *tau, Mat<T> qb, Mat<T> r, Mat<T> z) {
+    const int64_t k = wf.rows, n = wf.cols;
+    RC_REQUIRE(wf.rs == 1 && qb.rs == 1 && qb.rows == k && qb.cols == k && r.rows == k && r.cols == n && k > 64 && k <= 8 * 16 && k < n &&
+                   (z.empty() || (z.rows == k && z.cols == n)),
+               RC_INVALID_ARGUMENT, "rsvd_id_tails: shape mismatch");
+    constexpr int NE = 16, CPW = 256 / 8;
+    const int nz = z.empty() ? 0 : (int)cdiv(n, 256), nq = (int)cdiv(qb.cols, CPW);
+    const int nr = (int)std::min<int64_t>(cdiv(k * n, 256), 192);
+    const size_t lds = ((size_t)k * 8 * NE + (size_t)k) * sizeof(T);
+    ProfScope ps(c, "op:rsvd_id_tails k=%lld n=%lld wgs=%d+%d+%d", (long long)k, (long long)n, nz, nq, nr);
+    auto kern = k_rsvd_id_tails<T, NE>;
+    static bool attr_set[64] = {};
+    if (!attr_set[c->device & 63]) {
+        RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096));
+        attr_set[c->device & 63] = true;
+    }
+    hipLaunchKernelGGL(kern, dim3((unsigned)(nz + nq + nr)), dim3(256), lds, c->stream, wf, jpvt, tau, (int)k, z, qb, r, nz, nq);
 }
 // a: the original m x n matrix (any layout); w: its factorization in the ?geqp3 format (column-major, columns in place, k steps);
 // jpvt: position -> physical column; cm: m x k, z: k x n
@@ -767,6 +855,7 @@ void id_z_from_r_checked(rc_context *c, Mat<T> r, int64_t k, const int64_t *ind,
     template void id_z_from_r_checked<T>(rc_context *, Mat<T>, int64_t, const int64_t *, const int64_t *, Mat<T>); \
     template void geqp3_inplace<T>(rc_context *, Mat<T>, int64_t, bool, int64_t *, T *, T *);             \
     template void extract_r<T>(rc_context *, Mat<T>, const int64_t *, Mat<T>);                             \
+    template void rsvd_id_tails<T>(rc_context *, Mat<T>, const int64_t *, const T *, Mat<T>, Mat<T>, Mat<T>); \
     template void form_q<T>(rc_context *, Mat<T>, const int64_t *, const T *, int64_t, Mat<T>);           \
     template void trsm_upper<T>(rc_context *, Mat<T>, Mat<T>);
 RC_INST(double)

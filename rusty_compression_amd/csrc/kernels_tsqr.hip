@@ -360,8 +360,80 @@ __device__ __forceinline__ void qrcp_small_reflect(T (&x)[NE], const T *vcol, T 
     for (int e = E0; e < NE; ++e) x[e] -= f * v[e];
 }
 
-template <typename T, int NE, int NTHR>
-__global__ __launch_bounds__(NTHR) void k_qrcp_small(Mat<T> rin, int kmax, int pivot, int64_t *jpvt_out, Mat<T> rout, Mat<T> q2) {
+// The same sums without a branch around each load: every lane's loads are issued together (a masked row reads row j and is zeroed
+// by a select), then the products of the live rows are accumulated in qrcp_small_reflect's order, so dot, f and x are its bits.
+// For a group that has a CU to itself: there the step is the NE - E0 LDS round trips the branches put one behind the other,
+// which sixteen waves on one CU hide behind each other and two cannot.
+template <typename T, int NE, int LPP, int E0>
+__device__ __forceinline__ void qrcp_small_reflect_flat(T (&x)[NE], const T *vcol, T tj, int j, int n, int ll) {
+    T v[NE];
+    bool on[NE];
+#pragma unroll
+    for (int e = E0; e < NE; ++e) {
+        const int i = ll + LPP * e;
+        on[e] = i < n && i >= j;
+        v[e] = vcol[on[e] ? i : j];
+    }
+    // (the empty statement uses every loaded value, so no load can be sunk under a branch on its mask again)
+#pragma unroll
+    for (int e = E0; e < NE; ++e) asm volatile("" : "+v"(v[e]));
+#pragma unroll
+    for (int e = E0; e < NE; ++e) v[e] = on[e] ? ((ll + LPP * e == j) ? (T)1 : v[e]) : (T)0;
+    T dot = 0;
+#pragma unroll
+    for (int e = E0; e < NE; ++e) dot = on[e] ? fma(v[e], x[e], dot) : dot;
+    dot = group_sum_dpp<LPP>(dot);
+    const T f = tj * dot;
+#pragma unroll
+    for (int e = E0; e < NE; ++e) x[e] -= f * v[e];
+}
+
+// Column cq of Q2 by one LPP-lane group: apply H_min(cq,kmax-1) ... H_0 to e_cq (A, tau, jp: the factored LDS image, read-only)
+template <typename T, int NE, int LPP, bool FLAT = false>
+__device__ __forceinline__ void qrcp_small_q2_column(const T *A, int ld, int n, int kmax, const T *tau, const int *jp, int cq, int ll, Mat<T> q2) {
+    T x[NE];
+#pragma unroll
+    for (int e = 0; e < NE; ++e) x[e] = (ll + LPP * e == cq) ? (T)1 : (T)0;
+    const int j0 = cq < kmax - 1 ? cq : kmax - 1;
+    T tnext = tau[j0 > 0 ? j0 : 0];
+    int pnext = jp[j0 > 0 ? j0 : 0];
+    for (int j = j0; j >= 0; --j) {
+        const T tj = FLAT ? tnext : tau[j];
+        if (tj == (T)0) {
+            if constexpr (FLAT) { const int jn = j > 0 ? j - 1 : 0; tnext = tau[jn]; pnext = jp[jn]; }
+            continue;
+        }
+        const T *vcol = A + (FLAT ? pnext : jp[j]) * ld;
+        // register blocks that lie entirely above row j hold only zeros of the reflector: the instance that starts at
+        // the largest multiple of four blocks below row j skips them (same sums, the skipped products are exact zeros)
+        const int e0 = j / LPP;
+        if constexpr (FLAT) {
+            // tau and jp of the next step are fetched with this step's reflector, not in front of the next one
+            const int jn = j > 0 ? j - 1 : 0;
+            tnext = tau[jn];
+            pnext = jp[jn];
+            if (NE > 12 && e0 >= 12) qrcp_small_reflect_flat<T, NE, LPP, (NE > 12 ? 12 : 0)>(x, vcol, tj, j, n, ll);
+            else if (NE > 8 && e0 >= 8) qrcp_small_reflect_flat<T, NE, LPP, (NE > 8 ? 8 : 0)>(x, vcol, tj, j, n, ll);
+            else if (NE > 4 && e0 >= 4) qrcp_small_reflect_flat<T, NE, LPP, (NE > 4 ? 4 : 0)>(x, vcol, tj, j, n, ll);
+            else qrcp_small_reflect_flat<T, NE, LPP, 0>(x, vcol, tj, j, n, ll);
+            continue;
+        }
+        if (NE > 12 && e0 >= 12) qrcp_small_reflect<T, NE, LPP, (NE > 12 ? 12 : 0)>(x, vcol, tj, j, n, ll);
+        else if (NE > 8 && e0 >= 8) qrcp_small_reflect<T, NE, LPP, (NE > 8 ? 8 : 0)>(x, vcol, tj, j, n, ll);
+        else if (NE > 4 && e0 >= 4) qrcp_small_reflect<T, NE, LPP, (NE > 4 ? 4 : 0)>(x, vcol, tj, j, n, ll);
+        else qrcp_small_reflect<T, NE, LPP, 0>(x, vcol, tj, j, n, ll);
+    }
+#pragma unroll
+    for (int e = 0; e < NE; ++e) {
+        int i = ll + LPP * e;
+        if (i < n) q2.at(i, cq) = x[e];
+    }
+}
+
+// IMG: the kernel stops after the factorization and writes its LDS image (the factored matrix, the norms, tau, then jp) to img
+// instead of forming Q2; k_qrcp_small_q2 forms Q2 from it on several workgroups.
+template <typename T, int NE, int NTHR, bool IMG = false>
+__global__ __launch_bounds__(NTHR) void k_qrcp_small(Mat<T> rin, int kmax, int pivot, int64_t *jpvt_out, Mat<T> rout, Mat<T> q2, T *img = nullptr) {
     constexpr int LPP = 8;     // lanes per column in the update
     // NTHR threads = NTHR / 8 column groups: 1024 (n <= 144) covers the trailing columns of a step in one or two passes
     constexpr int NGRP = NTHR / LPP;
@@ -445,30 +517,47 @@ __global__ __launch_bounds__(NTHR) void k_qrcp_small(Mat<T> rin, int kmax, int p
             rout.at(i, p) = (i <= p) ? A[jp[p] * ld + i] : (T)0;
         }
     }
-    if (!q2.empty()) {  // column cq of Q2: apply H_min(cq,kmax-1) ... H_0 to e_cq; A is read-only now
-        for (int cq = grp; cq < (int)q2.cols; cq += NGRP) {
-            T x[NE];
-#pragma unroll
-            for (int e = 0; e < NE; ++e) x[e] = (ll + LPP * e == cq) ? (T)1 : (T)0;
-            for (int j = (cq < kmax - 1 ? cq : kmax - 1); j >= 0; --j) {
-                const T tj = tau[j];
-                if (tj == (T)0) continue;
-                const T *vcol = A + jp[j] * ld;
-                // register blocks that lie entirely above row j hold only zeros of the reflector: the instance that starts at
-                // the largest multiple of four blocks below row j skips them (same sums, the skipped products are exact zeros)
-                const int e0 = j / LPP;
-                if (NE > 12 && e0 >= 12) qrcp_small_reflect<T, NE, LPP, (NE > 12 ? 12 : 0)>(x, vcol, tj, j, n, ll);
-                else if (NE > 8 && e0 >= 8) qrcp_small_reflect<T, NE, LPP, (NE > 8 ? 8 : 0)>(x, vcol, tj, j, n, ll);
-                else if (NE > 4 && e0 >= 4) qrcp_small_reflect<T, NE, LPP, (NE > 4 ? 4 : 0)>(x, vcol, tj, j, n, ll);
-                else qrcp_small_reflect<T, NE, LPP, 0>(x, vcol, tj, j, n, ll);
-            }
-#pragma unroll
-            for (int e = 0; e < NE; ++e) {
-                int i = ll + LPP * e;
-                if (i < n) q2.at(i, cq) = x[e];
-            }
-        }
+    if constexpr (IMG) {
+        const int nt = n * ld + 3 * n;  // A, vn1, vn2, tau are contiguous; jp follows as ints
+        for (int e = tid; e < nt; e += NTHR) img[e] = A[e];
+        int *ijp = reinterpret_cast<int *>(img + nt);
+        for (int p = tid; p < n; p += NTHR) ijp[p] = jp[p];
+        return;
     }
+    if (!q2.empty()) {  // column cq of Q2: apply H_min(cq,kmax-1) ... H_0 to e_cq; A is read-only now
+        for (int cq = grp; cq < (int)q2.cols; cq += NGRP) qrcp_small_q2_column<T, NE, LPP>(A, ld, n, kmax, tau, jp, cq, ll, q2);
+    }
+}
+
+// Q2 of k_qrcp_small<T, NE, ., true> on several workgroups: each loads the image into its LDS and forms cpw columns, one 8-lane
+// group per column with the steps of the in-kernel formation in its order (qrcp_small_q2_column, loads issued together).
+// Columns are independent, so a CU holds cpw / 8 waves of them instead of sixteen and the phase is bound by the longest
+// column's dependent chain.
+template <typename T, int NE>
+__global__ __launch_bounds__(1024) void k_qrcp_small_q2(const T *img, int n, int kmax, Mat<T> q2, int cpw) {
+    constexpr int LPP = 8;
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const int ld = n | 1;
+    T *A = reinterpret_cast<T *>(smem_raw);
+    T *tau = A + (size_t)n * ld + 2 * n;
+    int *jp = reinterpret_cast<int *>(tau + n);
+    const int tid = threadIdx.x;
+    const int nt = n * ld + 3 * n;
+    constexpr int U = 8;  // loads in flight per thread and round (the image is 141 KB at n = 133: three rounds)
+    for (int e0 = tid; e0 < nt; e0 += 1024 * U) {
+        T val[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) val[u] = img[min(e0 + 1024 * u, nt - 1)];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (e0 + 1024 * u < nt) A[e0 + 1024 * u] = val[u];
+    }
+    const int *ijp = reinterpret_cast<const int *>(img + nt);
+    for (int p = tid; p < n; p += 1024) jp[p] = ijp[p];
+    __syncthreads();
+    const int ll = tid % LPP, grp = tid / LPP;
+    const int cq = (int)blockIdx.x * cpw + grp;
+    if (grp < cpw && cq < (int)q2.cols) qrcp_small_q2_column<T, NE, LPP, true>(A, ld, n, kmax, tau, jp, cq, ll, q2);
 }
 
 template <typename T>
@@ -486,9 +575,31 @@ void qrcp_small(rc_context *c, Mat<T> rin, int64_t kmax, bool pivot, int64_t *jp
             RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024)); \
             attr_set[c->device & 63] = true;                                                                           \
         }                                                                                                              \
-        hipLaunchKernelGGL(kern, dim3(1), dim3(NT_), lds, c->stream, rin, (int)kmax, pivot ? 1 : 0, jpvt, rout, q2);   \
+        hipLaunchKernelGGL(kern, dim3(1), dim3(NT_), lds, c->stream, rin, (int)kmax, pivot ? 1 : 0, jpvt, rout, q2, (T *)nullptr); \
     } while (0)
     static const int wide = [] { const char *e = getenv("RC_QRCP_SMALL_1024"); return e ? atoi(e) : 1; }();
+    // workgroups of the separate Q2 launch (0: Q2 stays inside k_qrcp_small).  With fewer than 8 compressions side by side the
+    // kernel slots are the bound: Q2's columns are independent and leave the one CU of k_qrcp_small
+    static const int q2_wgs = [] { const char *e = getenv("RC_QRCP_Q2_WGS"); return e ? std::min(std::max(atoi(e), 0), 64) : 8; }();
+    if (n > 64 && n <= 144 && wide && q2_wgs > 0 && !q2.empty() && c->lanes_in_flight() < 8) {
+        ArenaMark mark(c);
+        const size_t nt = (size_t)n * (n | 1) + 3 * (size_t)n;
+        T *img = c->alloc<T>(nt + (size_t)n);  // (n ints behind nt words of T)
+        auto kf = k_qrcp_small<T, 18, 1024, true>;
+        auto kq = k_qrcp_small_q2<T, 18>;
+        static bool attr_set[64] = {};
+        if (!attr_set[c->device & 63]) {
+            RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kf), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
+            RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kq), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
+            attr_set[c->device & 63] = true;
+        }
+        hipLaunchKernelGGL(kf, dim3(1), dim3(1024), lds, c->stream, rin, (int)kmax, pivot ? 1 : 0, jpvt, rout, q2, img);
+        // whole waves of columns per workgroup (8 columns a wave), at most the 128 column groups of a workgroup
+        const int cpw = (int)std::min<int64_t>(cdiv(cdiv(q2.cols, q2_wgs), 8) * 8, 128);
+        ProfScope pq(c, "op:qrcp_small_q2 n=%lld cols=%lld wgs=%d", (long long)n, (long long)q2.cols, (int)cdiv(q2.cols, cpw));
+        hipLaunchKernelGGL(kq, dim3((unsigned)cdiv(q2.cols, cpw)), dim3(1024), lds, c->stream, (const T *)img, (int)n, (int)kmax, q2, cpw);
+        return;
+    }
     if (n <= 64) RC_QS(8, 512);
     else if (n <= 144 && wide) RC_QS(18, 1024);
     else if (n <= 144) RC_QS(18, 512);

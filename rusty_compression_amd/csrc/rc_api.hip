@@ -455,9 +455,11 @@ static int tsqr_fold() {
 }
 
 // The tail of svd_core: from the SVD of the core (uc, s, vc) and the orthogonal factor of the tall QR -- qw, or q1 r2i when it
-// stayed factored -- to the factors of the matrix itself.
+// stayed factored -- to the factors of the matrix itself.  u_in_place (transposed only): the caller had the SVD of the core write
+// uc into u's storage, so u = uc needs no copy.
 template <typename T>
-void svd_finish(rc_context *c, bool transposed, bool factored, Mat<T> qw, Mat<T> q1, Mat<T> r2i, Mat<T> uc, Mat<T> vc, const T *s, Mat<T> u, Mat<T> vt) {
+void svd_finish(rc_context *c, bool transposed, bool factored, Mat<T> qw, Mat<T> q1, Mat<T> r2i, Mat<T> uc, Mat<T> vc, const T *s, Mat<T> u, Mat<T> vt,
+                bool u_in_place = false) {
     const int64_t r = uc.rows;
     complete_left_basis(c, uc, s);  // (?gesdd: U stays orthonormal when singular values are zero; no-op otherwise)
     Mat<T> small;
@@ -472,7 +474,7 @@ void svd_finish(rc_context *c, bool transposed, bool factored, Mat<T> qw, Mat<T>
         copy_mat(c, vc.t(), vt);
     } else {
         // a = L Q_w^T = Uc S (Q_w Vc)^T
-        copy_mat(c, uc, u);
+        if (!u_in_place) copy_mat(c, uc, u);
         if (factored) gemm<T>(c, 1, small.t(), q1.t(), 0, vt);
         else gemm<T>(c, 1, vc.t(), qw.t(), 0, vt);
     }
@@ -531,6 +533,12 @@ void compute_svd(rc_context *c, Mat<T> a, Mat<T> u, T *s, Mat<T> vt) {
     svd_core(c, wt, transposed, u, s, vt);
 }
 
+// Z of a column / row ID in one launch (RC_ID_FUSED)
+static int id_fused() {
+    static const int fused = [] { const char *e = getenv("RC_ID_FUSED"); return e ? atoi(e) : 1; }();
+    return fused;
+}
+
 // QRTraits::column_id  (/root/reference/src/qr.rs:270-309)
 // own_ind: `ind` was written by the library in this call (a pivoted QR's output: a permutation by construction).  A caller's
 // `ind` (rc_qr_column_id_*, rc_lq_row_id_*) is checked: entries out of range are skipped, columns of Z no entry names are zero,
@@ -544,8 +552,7 @@ void qr_column_id(rc_context *c, Mat<T> q, Mat<T> r, const int64_t *ind, Mat<T> 
     RC_REQUIRE(k <= n, RC_INVALID_ARGUMENT, "column_id: rank exceeds the number of columns");
     if (n == 0) return;
     ArenaMark mark(c);
-    static const int fused = [] { const char *e = getenv("RC_ID_FUSED"); return e ? atoi(e) : 1; }();
-    if (fused && k < n) {
+    if (id_fused() && k < n) {
         // Z in ONE launch (k_id_z: the chain below with the same arithmetic, every column written to its final place)
         if (own_ind) {
             id_z_from_r(c, r, k, ind, z);
@@ -906,7 +913,8 @@ bool rsvd_id_consumers_fused(rc_context *c, Mat<T> range, Mat<T> b, const rc_rsv
         // the cooperative QRCP below, and for the old order when this does not certify
         if (!run_certified(c, [&](int *flag) { tsqr_cholqr2_factored<T>(c, b.t(), q1, r2i, core.t(), flag); })) return false;
     }
-    Mat<T> uc = tmp_colmajor<T>(c, k, k), vc = tmp_colmajor<T>(c, k, k);
+    // (ub: the Jacobi writes the left vectors of the core where U = range ub reads them -- no copy in svd_finish)
+    Mat<T> ub = tmp_colmajor<T>(c, k, k), vc = tmp_colmajor<T>(c, k, k);
     Mat<T> qb = tmp_colmajor<T>(c, k, k);
     Mat<T> r = o.qr_r.data ? from_c<T>(o.qr_r) : tmp_rowmajor<T>(c, k, n);
     int64_t *ind = o.qr_ind ? o.qr_ind : c->alloc<int64_t>((size_t)n);
@@ -916,11 +924,20 @@ bool rsvd_id_consumers_fused(rc_context *c, Mat<T> range, Mat<T> b, const rc_rsv
     bool qr_done;
     {
         ProfScope ps(c, "stage:qrcp of B | svd of the core");
-        qr_done = run_certified(c, [&](int *flag) { geqp3_wide_coop_jacobi<T>(c, b, wf, k, ind, tau, flag, core, uc, s, vc); });
+        qr_done = run_certified(c, [&](int *flag) { geqp3_wide_coop_jacobi<T>(c, b, wf, k, ind, tau, flag, core, ub, s, vc); });
     }
     {
         ProfScope ps(c, "stage:qrcp of B + column_id");
-        if (qr_done) {
+        const bool want_cz = o.id_c.data || o.id_z.data;
+        Mat<T> cm = from_c<T>(o.id_c), z = from_c<T>(o.id_z);
+        // R, Q_b and Z read only wf, ind and tau: one launch (k_rsvd_id_tails) in place of extract_r, form_q and id_z_from_r
+        const bool tails = qr_done && k < n && id_fused();
+        if (tails) {
+            if (want_cz)
+                RC_REQUIRE(cm.rows == m && cm.cols == k && z.rows == k && z.cols == n, RC_INVALID_ARGUMENT, "column_id: c %lld x %lld, z %lld x %lld",
+                           (long long)cm.rows, (long long)cm.cols, (long long)z.rows, (long long)z.cols);
+            rsvd_id_tails(c, wf, ind, tau, qb, r, want_cz ? z : Mat<T>());
+        } else if (qr_done) {
             extract_r(c, wf, ind, r);
             form_q(c, wf, ind, tau, k, qb);
         } else {
@@ -930,12 +947,12 @@ bool rsvd_id_consumers_fused(rc_context *c, Mat<T> range, Mat<T> b, const rc_rsv
         }
         Mat<T> q = o.qr_q.data ? from_c<T>(o.qr_q) : tmp_colmajor<T>(c, m, k);
         gemm<T>(c, 1, range, qb, 0, q);
-        if (o.id_c.data || o.id_z.data) qr_column_id(c, q, r, ind, from_c<T>(o.id_c), from_c<T>(o.id_z), /*own_ind=*/true);
+        if (want_cz && tails) gemm<T>(c, 1, q, r.sub(0, k, 0, k), 0, cm);  // C = Q R11, as qr_column_id has it
+        else if (want_cz) qr_column_id(c, q, r, ind, cm, z, /*own_ind=*/true);
     }
     {
         ProfScope ps(c, "stage:svd of B + U=Q Ub");
-        Mat<T> ub = tmp_colmajor<T>(c, k, k);
-        svd_finish(c, /*transposed=*/true, /*factored=*/true, Mat<T>(), q1, r2i, uc, vc, s, ub, from_c<T>(o.vt));
+        svd_finish(c, /*transposed=*/true, /*factored=*/true, Mat<T>(), q1, r2i, ub, vc, s, ub, from_c<T>(o.vt), /*u_in_place=*/true);
         gemm<T>(c, 1, range, ub, 0, from_c<T>(o.u));
     }
     return true;

@@ -372,6 +372,8 @@ void coop_gate_launch(rc_context *c, unsigned need, unsigned *sync, unsigned lon
                       int clr_words = 0);
 // r(i, p) = (i <= p) ? w(i, jpvt[p]) : 0  for i < r.rows
 template <typename T> void extract_r(rc_context *c, Mat<T> w, const int64_t *jpvt, Mat<T> r);
+// R, Q_b and Z (may be empty) from the factored k x n wf of the fused QRCP/Jacobi launch in one launch (kernels_qr.hip)
+template <typename T> void rsvd_id_tails(rc_context *c, Mat<T> wf, const int64_t *jpvt, const T *tau, Mat<T> qb, Mat<T> r, Mat<T> z);
 // qw (m x kq column-major) = H_0 ... H_{k-1} [I ; 0], reflector j stored in column jpvt[j] of w
 template <typename T> void form_q(rc_context *c, Mat<T> w, const int64_t *jpvt, const T *tau, int64_t k, Mat<T> qw);
 // solve T X = B in place; t: k x k upper triangular view (any strides), b: k x nrhs view
