@@ -4,20 +4,17 @@
 // described at the head of kernels_batched_apply.hip; both kernels include this file so that an entry of the operator and a block of
 // the apply are summed by the same code.
 #pragma once
+#include "rc_batched_launch.hpp"
 #include "rc_common.hpp"
+#include "rc_cplx.hpp"
 #include "rc_device.hpp"
 
 namespace rc {
 
 namespace {
 
-constexpr int BA_THREADS = 256;
+constexpr int BA_THREADS = BATCHED_THREADS;
 constexpr int BA_WAVES = BA_THREADS / 64;
-
-template <typename R>
-struct cpx {
-    R re, im;
-};
 
 // element arithmetic shared by the real and the interleaved-complex instances
 template <typename E>
@@ -31,9 +28,9 @@ struct El {
     static __device__ __forceinline__ E conj(E v) { return v; }
 };
 template <typename R>
-struct El<cpx<R>> {
+struct El<cplx<R>> {
     using real = R;
-    using E = cpx<R>;
+    using E = cplx<R>;
     static __device__ __forceinline__ E zero() { return {(R)0, (R)0}; }
     static __device__ __forceinline__ E fma(E a, E b, E acc) {
         acc.re = ::fma(a.re, b.re, acc.re);

@@ -92,36 +92,34 @@ __global__ __launch_bounds__(BA_THREADS) void k_batched_apply(BaArgs<E> a) {
     }
 }
 
-template <typename E, int NBT>
-void ba_launch_nbt(rc_context *c, const BaArgs<E> &a, const char *tag) {
-    const void *kern = reinterpret_cast<const void *>(k_batched_apply<E, NBT>);
-    static bool attr_set[64] = {};
-    if (!attr_set[c->device & 63]) {
-        RC_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BID_MAX_LDS));
-        attr_set[c->device & 63] = true;
-    }
-    const size_t lds = ba_lds_bytes<E>(a.n, a.k, NBT, a.b.p != nullptr, a.mid.p != nullptr);
-    RC_REQUIRE(lds <= BID_MAX_LDS, RC_RUNTIME_ERROR, "lowrank_apply_batched: %zu bytes of LDS", lds);
-    const int64_t ntiles = (a.ncols + NBT - 1) / NBT, nunits = (int64_t)a.count * ntiles;
-    int64_t slots = 0;
-    const int64_t grid = bid_grid(c, kern, lds, 0, (int32_t)std::min<int64_t>(nunits, INT32_MAX), &slots);
-    ProfScope ps(c, "op:batched_apply%s %dx%d k=%d count=%d grid=%lld slots=%lld plan=nb:%d,tiles:%lld,cols:%d,%s%s%s", tag, a.m, a.n, a.k, a.count,
-                 (long long)grid, (long long)slots, NBT, (long long)ntiles, a.ncols, a.b.p ? "apply" : "to_mat", a.mid.p ? ",mid" : "", a.s ? ",s" : "");
-    hipLaunchKernelGGL((k_batched_apply<E, NBT>), dim3((unsigned)grid), dim3(BA_THREADS), lds, c->stream, a);
+// the plan (at: the tile width): the smallest of 1, 4, 8, 16 that covers the columns, at most the scalar type's NB; no workspace.  The
+// bits of an output element do not depend on it (see the head of this file).
+template <typename E>
+BatchedPlan<int> ba_plan(int n, int k, int ncols, bool has_b, bool has_mid) {
+    constexpr int NB = ba_nb<E>();
+    const int nbt = ncols <= 1 ? 1 : ncols <= 4 ? 4 : (NB >= 16 && ncols <= 8) ? 8 : NB;
+    return {nbt, ba_lds_bytes<E>(n, k, nbt, has_b, has_mid), 0};
 }
 
-// the tile width: the smallest of 1, 4, 8, 16 that covers the columns, at most the scalar type's NB.  The bits of an output
-// element do not depend on it (see the head of this file).
+template <typename E, int NBT>
+void ba_launch_nbt(rc_context *c, const BaArgs<E> &a, const char *tag, size_t lds) {
+    const int64_t ntiles = (a.ncols + NBT - 1) / NBT;
+    const auto lch = batched_prepare(c, k_batched_apply<E, NBT>, "lowrank_apply_batched", lds, 0, (int64_t)a.count * ntiles);
+    ProfScope ps(c, "op:batched_apply%s %dx%d k=%d count=%d grid=%lld slots=%lld plan=nb:%d,tiles:%lld,cols:%d,%s%s%s", tag, a.m, a.n, a.k, a.count,
+                 (long long)lch.grid, (long long)lch.slots, NBT, (long long)ntiles, a.ncols, a.b.p ? "apply" : "to_mat", a.mid.p ? ",mid" : "", a.s ? ",s" : "");
+    lch.launch(a);
+}
+
 template <typename E>
 void ba_launch(rc_context *c, const BaArgs<E> &a, const char *tag) {
-    constexpr int NB = ba_nb<E>();
     if (a.count <= 0) return;
-    if (a.ncols <= 1) return ba_launch_nbt<E, 1>(c, a, tag);
-    if (a.ncols <= 4) return ba_launch_nbt<E, 4>(c, a, tag);
-    if constexpr (NB >= 16) {
-        if (a.ncols <= 8) return ba_launch_nbt<E, 8>(c, a, tag);
+    const auto plan = ba_plan<E>(a.n, a.k, a.ncols, a.b.p != nullptr, a.mid.p != nullptr);
+    if (plan.at == 1) return ba_launch_nbt<E, 1>(c, a, tag, plan.lds);
+    if (plan.at == 4) return ba_launch_nbt<E, 4>(c, a, tag, plan.lds);
+    if constexpr (ba_nb<E>() >= 16) {
+        if (plan.at == 8) return ba_launch_nbt<E, 8>(c, a, tag, plan.lds);
     }
-    ba_launch_nbt<E, NB>(c, a, tag);
+    ba_launch_nbt<E, ba_nb<E>()>(c, a, tag, plan.lds);
 }
 
 template <typename E, typename P>
@@ -147,7 +145,7 @@ template <typename R>
 void batched_lowrank_apply_c(rc_context *c, const rc_matrix &left, int64_t lbs, const rc_matrix &mid, int64_t mbs, const R *s, int64_t s_stride,
                              const rc_matrix &right, int64_t rbs, const int64_t *ranks, int32_t count, const rc_matrix &b, int64_t bbs, const rc_matrix &y,
                              int64_t ybs) {
-    using E = cpx<R>;
+    using E = cplx<R>;
     BaArgs<E> a;
     a.left = ba_view<const E>(left.data, left.row_stride, left.col_stride, lbs);
     a.mid = ba_view<const E>(mid.data, mid.row_stride, mid.col_stride, mbs);

@@ -25,6 +25,14 @@
 //
 // Batched sketched column ID (rc_sketch_column_id_rank_batched_*): k_batched_sketch_id, the same grid; the working copy is the sketch
 // Omega A (l x n, l <= 128) formed by MFMA while A streams through LDS once, then the same stages on l rows (see its comment below).
+//
+// The launchers at the end of the file follow rc_batched_launch.hpp: a plan function per entry point, then prepare, label, workspace,
+// launch.  bid_grid and the first-use LDS cap of the whole batched family are defined here.
+#include <map>
+#include <mutex>
+#include <utility>
+
+#include "rc_batched_launch.hpp"
 #include "rc_common.hpp"
 #include "rc_device.hpp"
 #include "rc_gemm.hpp"
@@ -33,7 +41,7 @@ namespace rc {
 
 namespace {
 
-constexpr int BID_THREADS = 256;
+constexpr int BID_THREADS = BATCHED_THREADS;
 constexpr int BID_WAVES = BID_THREADS / 64;
 constexpr int BID_NB = 16;  // back-substitution tile (k_id_z's)
 
@@ -986,11 +994,55 @@ __global__ __launch_bounds__(BID_THREADS, 2) void k_batched_sketch_id(BsiArgs<T>
     }
 }
 
+// ---- the plans: where each launcher's movable buffers live, as pure functions of the shapes (rc_batched_launch.hpp) -------------------------
+
+// column ID: the working copy W (m x n) in LDS when it fits, else in the workgroup's slot of the grid-bounded workspace
+template <typename T>
+BatchedPlan<bool> bid_plan(int m, int n) {
+    return batched_lds_or_ws([&](bool w_lds) { return bid_lds_bytes<T>(m, n, w_lds); }, (size_t)m * (size_t)n * sizeof(T), "column_id_rank_batched");
+}
+
+// two-sided ID: the same rule, LDS or workspace chosen from the larger need of the two phases
+template <typename T>
+BatchedPlan<bool> bts_plan(int m, int n, int k) {
+    return batched_lds_or_ws([&](bool w_lds) { return bts_lds_bytes<T>(m, n, k, w_lds); }, (size_t)m * (size_t)n * sizeof(T), "two_sided_id_rank_batched");
+}
+
+// SVD, M x N the work orientation: the working copy W (M x N) and V (N x N) in LDS when they fit next to the core (W only with V),
+// otherwise in the workgroup's slot; the core G always fits (N <= 128: 128 KiB in f64).  Most in LDS first; the core's column pitch is
+// k_jacobi_lds's conflict-free one (16 modulo 32 elements) whenever the plan fits with it, else N | 1.
+struct BsvPlace { bool w, v; int ld; };
+template <typename T>
+BatchedPlan<BsvPlace> bsv_plan(int m, int n) {
+    const int M = std::max(m, n), N = std::min(m, n);
+    const int pad = ((N + 15) / 32) * 32 + 16, odd = N | 1;
+    const BsvPlace places[] = {{true, true, pad}, {true, true, odd}, {false, true, pad}, {false, true, odd}, {false, false, pad}, {false, false, odd}};
+    return batched_first_fit(places, [&](BsvPlace p) { return bsv_lds_bytes<T>(M, N, p.ld, p.w, p.v); },
+        [&](BsvPlace p) { return ((p.w ? 0 : (size_t)M * N) + (p.v ? 0 : (size_t)N * N)) * sizeof(T); }, "svd_rank_batched");
+}
+
+// recompression: the two working copies Wl (m x K), Wr (n x K) and the rotations J (K x K) by bsv_plan's rule next to the core (always in
+// LDS); a copy that does not fit goes to the workgroup's slot, the larger copy first
+struct BrcPlace { bool l, r, v; int ld; };
+template <typename T>
+BatchedPlan<BrcPlace> brc_plan(int m, int n, int K) {
+    const int pad = ((K + 15) / 32) * 32 + 16, odd = K | 1;
+    const bool big_l = m >= n;  // the copy that leaves LDS first
+    const BrcPlace places[] = {{true, true, true, pad},    {true, true, true, odd},    {!big_l, big_l, true, pad},   {!big_l, big_l, true, odd},
+                               {false, false, true, pad}, {false, false, true, odd}, {false, false, false, pad}, {false, false, false, odd}};
+    return batched_first_fit(places, [&](BrcPlace p) { return brc_lds_bytes<T>(m, n, K, p.ld, p.l, p.r, p.v); },
+        [&](BrcPlace p) { return brc_ws_elems(m, n, K, p.l, p.r, p.v) * sizeof(T); }, "lowrank_recompress_batched");
+}
+
+// sketched column ID: W (l x n) in LDS when it fits next to the chunk images, else in the workgroup's slot
+template <typename T>
+BatchedPlan<bool> bsi_plan(int l, int n) {
+    return batched_lds_or_ws([&](bool w_lds) { return bsi_lds_bytes<T>(l, n, w_lds); }, (size_t)l * (size_t)n * sizeof(T), "sketch_column_id_rank_batched");
+}
+
 }  // namespace
 
-// persistent grid: the resident workgroups of every CU, fewer when the workspace (ws_per bytes per workgroup, 0 in the LDS variants)
-// would pass 256 MiB unless that leaves less than one workgroup per CU; never more than count (shared with kernels_batched_id_c.hip).
-// *slots: the grid before that last bound, what a batch of any size can occupy (the slots= field of the profile label)
+// the persistent grid of the whole batched family (the rule: rc_batched_launch.hpp)
 int64_t bid_grid(rc_context *c, const void *kern, size_t lds, size_t ws_per, int32_t count, int64_t *slots) {
     static int cus_of[64] = {};
     int &cus = cus_of[c->device & 63];
@@ -1003,179 +1055,115 @@ int64_t bid_grid(rc_context *c, const void *kern, size_t lds, size_t ws_per, int
     return std::min<int64_t>(grid, count);
 }
 
+int batched_kernel_cap(int device, const void *kern) {
+    // the calling thread's last answer first: a loop over one entry point takes neither the lock nor the lookup
+    thread_local int last_device = -1, last_scratch = 0;
+    thread_local const void *last_kern = nullptr;
+    if (device == last_device && kern == last_kern) return last_scratch;
+    static std::mutex mu;
+    static std::map<std::pair<int, const void *>, int> scratch_of;
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = scratch_of.find({device, kern});
+    if (it == scratch_of.end()) {
+        RC_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BID_MAX_LDS));
+        hipFuncAttributes fa;
+        RC_HIP(hipFuncGetAttributes(&fa, kern));
+        it = scratch_of.emplace(std::make_pair(device, kern), (int)fa.localSizeBytes).first;
+    }
+    last_device = device; last_kern = kern;
+    return last_scratch = it->second;
+}
+
 template <typename T>
 void batched_column_id(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int64_t k, double tol, Mat<T> cm, int64_t cbs, Mat<T> z, int64_t zbs,
                        int64_t *col_ind, int64_t *ranks) {
     const int m = (int)a.rows, n = (int)a.cols;
     if (count <= 0) return;
-    const size_t lds_in = bid_lds_bytes<T>(m, n, true);
-    const bool in_lds = lds_in <= BID_MAX_LDS;
-    const size_t lds = in_lds ? lds_in : bid_lds_bytes<T>(m, n, false);
-    auto kern = in_lds ? k_batched_id<T, true> : k_batched_id<T, false>;
-    static bool attr_set[64] = {};
-    if (!attr_set[c->device & 63]) {
-        RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_batched_id<T, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BID_MAX_LDS));
-        RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_batched_id<T, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BID_MAX_LDS));
-        attr_set[c->device & 63] = true;
-    }
-    const size_t per = (size_t)m * (size_t)n * sizeof(T);
-    int64_t slots = 0;
-    const int64_t grid = bid_grid(c, reinterpret_cast<const void *>(kern), lds, in_lds ? 0 : per, count, &slots);
-    ProfScope ps(c, "op:batched_column_id %dx%d k=%lld count=%d grid=%lld slots=%lld plan=W:%s", m, n, (long long)k, (int)count, (long long)grid,
-                 (long long)slots, in_lds ? "lds" : "ws");
-    T *ws = in_lds ? nullptr : c->alloc<T>((size_t)grid * (size_t)m * (size_t)n);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BID_THREADS), lds, c->stream, a, abs, (int)count, (int)k, tol, cm, cbs, z, zbs, col_ind, ranks, ws);
+    const auto plan = bid_plan<T>(m, n);
+    const auto lch = batched_prepare(c, plan.at ? k_batched_id<T, true> : k_batched_id<T, false>, "column_id_rank_batched", plan.lds, plan.ws, count);
+    ProfScope ps(c, "op:batched_column_id %dx%d k=%lld count=%d grid=%lld slots=%lld plan=W:%s", m, n, (long long)k, (int)count, (long long)lch.grid,
+                 (long long)lch.slots, plan.at ? "lds" : "ws");
+    lch.launch(a, abs, (int)count, (int)k, tol, cm, cbs, z, zbs, col_ind, ranks, lch.template workspace<T>());
 }
 
-// the same grid and workspace rule; LDS or workspace chosen from the larger need of the two phases
 template <typename T>
 void batched_two_sided_id(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int64_t k, double tol, Mat<T> cm, int64_t cbs, Mat<T> x, int64_t xbs,
                           Mat<T> z, int64_t zbs, int64_t *row_ind, int64_t *col_ind, int64_t *ranks) {
     const int m = (int)a.rows, n = (int)a.cols;
     if (count <= 0) return;
-    const size_t lds_in = bts_lds_bytes<T>(m, n, (int)k, true);
-    const bool in_lds = lds_in <= BID_MAX_LDS;
-    const size_t lds = in_lds ? lds_in : bts_lds_bytes<T>(m, n, (int)k, false);
-    auto kern = in_lds ? k_batched_two_sided<T, true> : k_batched_two_sided<T, false>;
-    static bool attr_set[64] = {};
-    if (!attr_set[c->device & 63]) {
-        RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_batched_two_sided<T, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BID_MAX_LDS));
-        RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_batched_two_sided<T, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BID_MAX_LDS));
-        attr_set[c->device & 63] = true;
-    }
-    const size_t per = (size_t)m * (size_t)n * sizeof(T);
-    int64_t slots = 0;
-    const int64_t grid = bid_grid(c, reinterpret_cast<const void *>(kern), lds, in_lds ? 0 : per, count, &slots);
-    ProfScope ps(c, "op:batched_two_sided_id %dx%d k=%lld count=%d grid=%lld slots=%lld plan=W:%s", m, n, (long long)k, (int)count, (long long)grid,
-                 (long long)slots, in_lds ? "lds" : "ws");
-    T *ws = in_lds ? nullptr : c->alloc<T>((size_t)grid * (size_t)m * (size_t)n);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BID_THREADS), lds, c->stream, a, abs, (int)count, (int)k, tol, cm, cbs, x, xbs, z, zbs, row_ind,
-                       col_ind, ranks, ws);
+    const auto plan = bts_plan<T>(m, n, (int)k);
+    const auto lch = batched_prepare(c, plan.at ? k_batched_two_sided<T, true> : k_batched_two_sided<T, false>, "two_sided_id_rank_batched", plan.lds, plan.ws, count);
+    ProfScope ps(c, "op:batched_two_sided_id %dx%d k=%lld count=%d grid=%lld slots=%lld plan=W:%s", m, n, (long long)k, (int)count, (long long)lch.grid,
+                 (long long)lch.slots, plan.at ? "lds" : "ws");
+    lch.launch(a, abs, (int)count, (int)k, tol, cm, cbs, x, xbs, z, zbs, row_ind, col_ind, ranks, lch.template workspace<T>());
 }
 
-// where the working copy W (M x N) and V (N x N) live: in LDS when they fit next to the core (W only with V), otherwise in
-// workgroup blockIdx.x's slot of the grid-bounded workspace; the core G always fits (N <= 128: 128 KiB in f64).  The core's column
-// pitch is k_jacobi_lds's conflict-free one (16 modulo 32 elements) whenever the plan fits with it, else N | 1.
 template <typename T>
 void batched_svd(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs, T *s, Mat<T> vt, int64_t vbs,
                  int64_t *ranks) {
     const int m = (int)a.rows, n = (int)a.cols;
     if (count <= 0) return;
     const bool wide = m < n;
-    const int M = wide ? n : m, N = wide ? m : n;
-    // the first plan that fits: most in LDS first, the padded pitch before the odd one (the last always fits)
-    const int pad = ((N + 15) / 32) * 32 + 16, odd = N | 1;
-    const struct { bool w, v; int ld; } plans[] = {{true, true, pad}, {true, true, odd}, {false, true, pad}, {false, true, odd}, {false, false, pad}, {false, false, odd}};
-    int pi = 0;
-    while (pi < 5 && bsv_lds_bytes<T>(M, N, plans[pi].ld, plans[pi].w, plans[pi].v) > BID_MAX_LDS) ++pi;
-    const bool w_lds = plans[pi].w, v_lds = plans[pi].v;
-    const int ldg = plans[pi].ld;
-    const size_t lds = bsv_lds_bytes<T>(M, N, ldg, w_lds, v_lds);
-    auto kern = w_lds ? k_batched_svd<T, true, true> : v_lds ? k_batched_svd<T, false, true> : k_batched_svd<T, false, false>;
-    static bool attr_set[64] = {};
-    if (!attr_set[c->device & 63]) {
-        for (const void *f : {reinterpret_cast<const void *>(k_batched_svd<T, true, true>), reinterpret_cast<const void *>(k_batched_svd<T, false, true>),
-                              reinterpret_cast<const void *>(k_batched_svd<T, false, false>)})
-            RC_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BID_MAX_LDS));
-        attr_set[c->device & 63] = true;
-    }
-    const size_t per = ((w_lds ? 0 : (size_t)M * N) + (v_lds ? 0 : (size_t)N * N)) * sizeof(T);
-    int64_t slots = 0;
-    const int64_t grid = bid_grid(c, reinterpret_cast<const void *>(kern), lds, per, count, &slots);
-    ProfScope ps(c, "op:batched_svd %dx%d k=%lld count=%d grid=%lld slots=%lld plan=W:%s,V:%s,G:lds,ld=%d", m, n, (long long)k, (int)count, (long long)grid,
-                 (long long)slots, w_lds ? "lds" : "ws", v_lds ? "lds" : "ws", ldg);
-    T *ws = per ? c->alloc<T>((size_t)grid * per / sizeof(T)) : nullptr;
+    const auto plan = bsv_plan<T>(m, n);
+    const BsvPlace at = plan.at;
+    const auto lch = batched_prepare(c, at.w ? k_batched_svd<T, true, true> : at.v ? k_batched_svd<T, false, true> : k_batched_svd<T, false, false>,
+                                   "svd_rank_batched", plan.lds, plan.ws, count);
+    ProfScope ps(c, "op:batched_svd %dx%d k=%lld count=%d grid=%lld slots=%lld plan=W:%s,V:%s,G:lds,ld=%d", m, n, (long long)k, (int)count,
+                 (long long)lch.grid, (long long)lch.slots, at.w ? "lds" : "ws", at.v ? "lds" : "ws", at.ld);
     // the work orientation's U (M x k) and V^T (k x N): u and vt, or for a wide matrix vt^T and u^T
     const Mat<T> uo = wide ? vt.t() : u, vo = wide ? u.t() : vt;
     const int64_t uobs = wide ? vbs : ubs, vobs = wide ? ubs : vbs;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BID_THREADS), lds, c->stream, a, abs, (int)count, (int)k, tol, uo, uobs, vo, vobs, s, ranks, ws,
-                       c->health_word(), ldg);
+    lch.launch(a, abs, (int)count, (int)k, tol, uo, uobs, vo, vobs, s, ranks, lch.template workspace<T>(), c->health_word(), at.ld);
 }
 
-// where the two working copies Wl (m x K), Wr (n x K) and the rotations J (K x K) live: batched_svd's rule, the first plan that fits
-// next to the core (always in LDS), most in LDS first and the padded core pitch before the odd one; a copy that does not fit goes to
-// the workgroup's slot of the grid-bounded workspace, the larger copy first.  One kernel: the plan only moves base pointers and pitches.
+// One kernel: the plan only moves base pointers and pitches.
 template <typename T>
 void batched_lowrank_recompress(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride, Mat<T> right, int64_t rbs,
                                 const int64_t *in_ranks, int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs, T *s_out, Mat<T> vt, int64_t vbs,
                                 int64_t *ranks) {
     const int m = (int)left.rows, n = (int)right.cols, K = (int)left.cols;
     if (count <= 0) return;
-    const int pad = ((K + 15) / 32) * 32 + 16, odd = K | 1;
-    const bool big_l = m >= n;  // the copy that leaves LDS first
-    const struct { bool l, r, v; int ld; } plans[] = {{true, true, true, pad},    {true, true, true, odd},    {!big_l, big_l, true, pad},   {!big_l, big_l, true, odd},
-                                                      {false, false, true, pad}, {false, false, true, odd}, {false, false, false, pad}, {false, false, false, odd}};
-    int pi = 0;
-    while (pi < 7 && brc_lds_bytes<T>(m, n, K, plans[pi].ld, plans[pi].l, plans[pi].r, plans[pi].v) > BID_MAX_LDS) ++pi;
-    const bool l_lds = plans[pi].l, r_lds = plans[pi].r, v_lds = plans[pi].v;
-    const int ldg = plans[pi].ld;
-    const size_t lds = brc_lds_bytes<T>(m, n, K, ldg, l_lds, r_lds, v_lds);
-    RC_REQUIRE(lds <= BID_MAX_LDS, RC_RUNTIME_ERROR, "lowrank_recompress_batched: %zu bytes of LDS", lds);
-    const void *kern = reinterpret_cast<const void *>(k_batched_recompress<T>);
-    static bool attr_set[64] = {};
-    if (!attr_set[c->device & 63]) {
-        RC_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BID_MAX_LDS));
-        attr_set[c->device & 63] = true;
-    }
-    const size_t per = brc_ws_elems(m, n, K, l_lds, r_lds, v_lds) * sizeof(T);
-    int64_t slots = 0;
-    const int64_t grid = bid_grid(c, kern, lds, per, count, &slots);
+    const auto plan = brc_plan<T>(m, n, K);
+    const BrcPlace at = plan.at;
+    const auto lch = batched_prepare(c, k_batched_recompress<T>, "lowrank_recompress_batched", plan.lds, plan.ws, count);
     ProfScope ps(c, "op:batched_recompress %dx%d k=%d count=%d grid=%lld slots=%lld plan=L:%s,R:%s,V:%s,G:lds,ld=%d,kk=%d%s%s", m, n, K, (int)count,
-                 (long long)grid, (long long)slots, l_lds ? "lds" : "ws", r_lds ? "lds" : "ws", v_lds ? "lds" : "ws", ldg, (int)std::min<int64_t>(k, K),
+                 (long long)lch.grid, (long long)lch.slots, at.l ? "lds" : "ws", at.r ? "lds" : "ws", at.v ? "lds" : "ws", at.ld, (int)std::min<int64_t>(k, K),
                  mid.p ? ",mid" : "", s ? ",s" : "");
     BrcArgs<T> a;
     a.left = left; a.mid = mid; a.right = right; a.u = u; a.vt = vt;
     a.lbs = lbs; a.mbs = mbs; a.rbs = rbs; a.ubs = ubs; a.vbs = vbs; a.s_stride = s_stride;
     a.s = s; a.in_ranks = in_ranks; a.s_out = s_out; a.ranks = ranks;
-    a.ws = per ? c->alloc<T>((size_t)grid * per / sizeof(T)) : nullptr;
+    a.ws = lch.template workspace<T>();
     a.health = c->health_word();
-    a.tol = tol; a.count = (int)count; a.k = (int)std::min<int64_t>(k, K); a.ldg = ldg;
-    a.l_lds = l_lds; a.r_lds = r_lds; a.v_lds = v_lds;
-    hipLaunchKernelGGL(k_batched_recompress<T>, dim3((unsigned)grid), dim3(BID_THREADS), lds, c->stream, a);
+    a.tol = tol; a.count = (int)count; a.k = (int)std::min<int64_t>(k, K); a.ldg = at.ld;
+    a.l_lds = at.l; a.r_lds = at.r; a.v_lds = at.v;
+    lch.launch(a);
 }
 
-// the sketched column ID of a batch: W (l x n) in LDS when it fits next to the chunk images, else in the workgroup's slot of the grid-bounded
-// workspace: the plan only moves W's base pointer and pitch, so it cannot change a block's bits.  Four instances of the kernel, by the
-// index of a and of omega that the staging loads' lanes run along; each element of Y is summed in the same order in all four.
+// The plan only moves W's base pointer and pitch, so it cannot change a block's bits.  Four instances of the kernel, by the index of a and
+// of omega that the staging loads' lanes run along; each element of Y is summed in the same order in all four.  The label carries the
+// launched instance's scratch bytes per thread (the f64 instances sit at the register bound of two waves per SIMD, so a compiler that
+// spills more shows up in every profile and in tools/batched_sketch_id_bench.py).
 template <typename T>
 void batched_sketch_column_id(rc_context *c, Mat<T> a, int64_t abs, Mat<T> omega, int64_t obs, int32_t count, int64_t kk, double tol, Mat<T> y, int64_t ybs,
                               Mat<T> cm, int64_t cbs, Mat<T> z, int64_t zbs, int64_t *col_ind, int64_t *ranks) {
     const int m = (int)a.rows, n = (int)a.cols, l = (int)omega.rows;
     if (count <= 0) return;
-    const bool w_lds = bsi_lds_bytes<T>(l, n, true) <= BID_MAX_LDS;
-    const size_t lds = bsi_lds_bytes<T>(l, n, w_lds);
+    const auto plan = bsi_plan<T>(l, n);
     // the lanes of the staging loads along the smaller stride of a and of omega (bid_load's rule for a)
     const bool a_rows = a.rs <= a.cs, o_rows = omega.rs < omega.cs;
-    const void *kerns[4] = {reinterpret_cast<const void *>(k_batched_sketch_id<T, false, false>), reinterpret_cast<const void *>(k_batched_sketch_id<T, false, true>),
-                            reinterpret_cast<const void *>(k_batched_sketch_id<T, true, false>), reinterpret_cast<const void *>(k_batched_sketch_id<T, true, true>)};
-    const void *kern = kerns[(a_rows ? 2 : 0) + (o_rows ? 1 : 0)];
-    // per device, once: the LDS cap, and each instance's scratch bytes per thread for the label (the f64 instances sit at the register bound of two
-    // waves per SIMD, so a compiler that spills more shows up in every profile and in tools/batched_sketch_id_bench.py)
-    static bool attr_set[64] = {};
-    static int scratch_of[64][4] = {};
-    if (!attr_set[c->device & 63]) {
-        for (int i = 0; i < 4; ++i) {
-            RC_HIP(hipFuncSetAttribute(kerns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)BID_MAX_LDS));
-            hipFuncAttributes fa;
-            RC_HIP(hipFuncGetAttributes(&fa, kerns[i]));
-            scratch_of[c->device & 63][i] = (int)fa.localSizeBytes;
-        }
-        attr_set[c->device & 63] = true;
-    }
-    const size_t per = w_lds ? 0 : (size_t)l * (size_t)n * sizeof(T);
-    int64_t slots = 0;
-    const int64_t grid = bid_grid(c, kern, lds, per, count, &slots);
+    void (*const kerns[4])(BsiArgs<T>) = {k_batched_sketch_id<T, false, false>, k_batched_sketch_id<T, false, true>, k_batched_sketch_id<T, true, false>,
+                                          k_batched_sketch_id<T, true, true>};
+    const auto lch = batched_prepare(c, kerns[(a_rows ? 2 : 0) + (o_rows ? 1 : 0)], "sketch_column_id_rank_batched", plan.lds, plan.ws, count);
     ProfScope ps(c, "op:batched_sketch_id %dx%d k=%lld count=%d grid=%lld slots=%lld plan=W:%s,l=%d,rows=%d,cols=%d,scratch=%d", m, n, (long long)kk,
-                 (int)count, (long long)grid, (long long)slots, w_lds ? "lds" : "ws", l, BSI_ROWS, BSI_COLS,
-                 scratch_of[c->device & 63][(a_rows ? 2 : 0) + (o_rows ? 1 : 0)]);
+                 (int)count, (long long)lch.grid, (long long)lch.slots, plan.at ? "lds" : "ws", l, BSI_ROWS, BSI_COLS, lch.scratch);
     BsiArgs<T> g;
     g.a = a; g.omega = omega; g.y = y; g.c = cm; g.z = z;
     g.abs = abs; g.obs = obs; g.ybs = ybs; g.cbs = cbs; g.zbs = zbs;
     g.col_ind = col_ind; g.ranks = ranks;
-    g.ws = per ? c->alloc<T>((size_t)grid * (size_t)l * (size_t)n) : nullptr;
-    g.tol = tol; g.count = (int)count; g.kk = (int)kk; g.w_lds = w_lds;
-    void *args[] = {&g};
-    RC_HIP(hipLaunchKernel(kern, dim3((unsigned)grid), dim3(BID_THREADS), args, lds, c->stream));
+    g.ws = lch.template workspace<T>();
+    g.tol = tol; g.count = (int)count; g.kk = (int)kk; g.w_lds = plan.at;
+    lch.launch(g);
 }
 
 template void batched_sketch_column_id<double>(rc_context *, Mat<double>, int64_t, Mat<double>, int64_t, int32_t, int64_t, double, Mat<double>, int64_t, Mat<double>,

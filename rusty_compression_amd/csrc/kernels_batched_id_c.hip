@@ -4,8 +4,9 @@
 // column ID of complex tall blocks (rc_sketch_column_id_rank_complex_batched_c64 / _c32, k_batched_sketch_id_c below).
 //
 // The structure of kernels_batched_id.hip (one persistent workgroup of 256 threads per matrix, the same three device stages, the same
-// grid and workspace rule, bid_grid) with the complex arithmetic of the lone complex path in rc_complex.hip:
-//   * interleaved (re, im) data (rc_complex.hip's cplx<R>); the partial norms vn1 / vn2 are real, W and the tile complex;
+// grid and workspace rule, and the launch path of rc_batched_launch.hpp) with the complex arithmetic of the lone complex path in
+// rc_complex.hip:
+//   * interleaved (re, im) data (cplx<R>, CV<R> and their arithmetic: rc_cplx.hpp); the partial norms vn1 / vn2 are real, W and the tile complex;
 //   * ?larfg for complex (k_c_qr_pivot_reflect): beta = -copysign(lapy3(alpha.re, alpha.im, xnorm), alpha.re) is real, tau complex,
 //     the scale 1 / (alpha - beta) by Smith division; H = I only when xnorm == 0 and alpha.im == 0;
 //   * H^H = I - conj(tau) v v^H with the conjugated dot v^H x, then the ?laqp2 down-date with |x_j| (k_c_qr_apply);
@@ -23,7 +24,9 @@
 // Every operation below commutes exactly with negating all imaginary parts (round to nearest is sign-symmetric, and each real part
 // is even, each imaginary part odd in the imaginary inputs), so conj(A) gives the same permutations and ranks and the conjugate
 // of every factor, bit for bit.
+#include "rc_batched_launch.hpp"
 #include "rc_common.hpp"
+#include "rc_cplx.hpp"
 #include "rc_device.hpp"
 #include "rc_gemm.hpp"
 
@@ -31,71 +34,43 @@ namespace rc {
 
 namespace {
 
-constexpr int BIC_THREADS = 256;
+constexpr int BIC_THREADS = BATCHED_THREADS;
 constexpr int BIC_WAVES = BIC_THREADS / 64;
 constexpr int BIC_NB = 8;  // back-substitution tile
-
-template <typename R>
-struct cx {
-    R re, im;
-};
-template <typename R> __device__ __forceinline__ cx<R> cmul(cx<R> a, cx<R> b) { return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
-template <typename R> __device__ __forceinline__ cx<R> csub(cx<R> a, cx<R> b) { return {a.re - b.re, a.im - b.im}; }
-template <typename R> __device__ __forceinline__ cx<R> conj_of(cx<R> a) { return {a.re, -a.im}; }
-template <typename R> __device__ __forceinline__ R abs2(cx<R> a) { return a.re * a.re + a.im * a.im; }
-template <typename R> __device__ __forceinline__ cx<R> cdiv(cx<R> a, cx<R> b) {  // Smith's algorithm (?ladiv), rc_complex.hip's
-    if (fabs(b.re) >= fabs(b.im)) {
-        const R r = b.im / b.re, d = b.re + b.im * r;
-        return {(a.re + a.im * r) / d, (a.im - a.re * r) / d};
-    }
-    const R r = b.re / b.im, d = b.im + b.re * r;
-    return {(a.re * r + a.im) / d, (a.im * r - a.re) / d};
-}
-template <typename R> __device__ __forceinline__ cx<R> czero() { return {(R)0, (R)0}; }
-template <typename R> __device__ __forceinline__ cx<R> cone() { return {(R)1, (R)0}; }
-
-// strided complex view (the rc_matrix of an interleaved-complex operand, strides in complex elements)
-template <typename R>
-struct CView {
-    cx<R> *p;
-    int64_t rows, cols, rs, cs;
-};
-template <typename R>
-CView<R> cview(const rc_matrix &m) { return CView<R>{static_cast<cx<R> *>(m.data), m.rows, m.cols, m.row_stride, m.col_stride}; }
 
 // dynamic LDS: [W: m x ldw complex, LDS variant only] tile[8 x 9] complex | vn1[n] vn2[n] red[8] real | jp[n]
 template <typename R>
 size_t bic_lds_bytes(int m, int n, bool in_lds) {
     size_t c = (size_t)BIC_NB * (BIC_NB + 1);
     if (in_lds) c += (size_t)n * (size_t)(m | 1);
-    return c * sizeof(cx<R>) + ((size_t)2 * n + 8) * sizeof(R) + (size_t)n * sizeof(int);
+    return c * sizeof(cplx<R>) + ((size_t)2 * n + 8) * sizeof(R) + (size_t)n * sizeof(int);
 }
 
 // H_j^H = I - conj(tau) v v^H applied to the trailing columns p = j+1 .. n-1, one wave per column; rows j + lane + 64 e of the column
 // in registers (NE * 64 >= m - j), then the ?laqp2 down-date of the column's partial norm with |x_j|
 template <typename R, int NE>
-__device__ __forceinline__ void bic_apply(cx<R> *W, int ldw, int m, int n, int j, const int *jp, R *vn1, R *vn2, cx<R> tj, int wv, int lane) {
+__device__ __forceinline__ void bic_apply(cplx<R> *W, int ldw, int m, int n, int j, const int *jp, R *vn1, R *vn2, cplx<R> tj, int wv, int lane) {
     const int mrem = m - j;
-    const cx<R> *vc = W + (size_t)jp[j] * ldw + j;
-    cx<R> v[NE];
+    const cplx<R> *vc = W + (size_t)jp[j] * ldw + j;
+    cplx<R> v[NE];
 #pragma unroll
     for (int e = 0; e < NE; ++e) {
         // branch-free: lanes past the end read row j (always valid) and are masked by a select
         const int li = lane + 64 * e;
         const bool ok = li < mrem;
-        const cx<R> vv = vc[ok ? li : 0];
+        const cplx<R> vv = vc[ok ? li : 0];
         v[e] = ok ? (li == 0 ? cone<R>() : vv) : czero<R>();
     }
     const bool reflect = tj.re != (R)0 || tj.im != (R)0;  // tau == 0: H = I
-    const cx<R> ctj = conj_of(tj);
+    const cplx<R> ctj = cj(tj);
     for (int p = j + 1 + wv; p < n; p += BIC_WAVES) {
-        cx<R> *xc = W + (size_t)jp[p] * ldw + j;
-        cx<R> x[NE];
+        cplx<R> *xc = W + (size_t)jp[p] * ldw + j;
+        cplx<R> x[NE];
 #pragma unroll
         for (int e = 0; e < NE; ++e) {
             const int li = lane + 64 * e;
             const bool ok = li < mrem;
-            const cx<R> xv = xc[ok ? li : 0];
+            const cplx<R> xv = xc[ok ? li : 0];
             x[e] = ok ? xv : czero<R>();
         }
         if (reflect) {
@@ -107,7 +82,7 @@ __device__ __forceinline__ void bic_apply(cx<R> *W, int ldw, int m, int n, int j
                 dim = fma(v[e].re, x[e].im, dim);
                 dim = fma(-v[e].im, x[e].re, dim);
             }
-            const cx<R> f = cmul(ctj, cx<R>{wave_sum_dpp(dre), wave_sum_dpp(dim)});
+            const cplx<R> f = ctj * cplx<R>{wave_sum_dpp(dre), wave_sum_dpp(dim)};
 #pragma unroll
             for (int e = 0; e < NE; ++e) {
                 const int li = lane + 64 * e;
@@ -121,7 +96,7 @@ __device__ __forceinline__ void bic_apply(cx<R> *W, int ldw, int m, int n, int j
         const R vn = vn1[p];
         if (vn != (R)0) {
             R nn;
-            const cx<R> x0{read_lane(x[0].re, 0), read_lane(x[0].im, 0)};
+            const cplx<R> x0{read_lane(x[0].re, 0), read_lane(x[0].im, 0)};
             if (laqp2_downdate(vn, vn2[p], (R)hypot(x0.re, x0.im), &nn)) {
                 R ss = 0;
 #pragma unroll
@@ -143,7 +118,7 @@ __device__ __forceinline__ void bic_apply(cx<R> *W, int ldw, int m, int n, int j
 
 // the initial (real) column norms of the working copy W (m x n, column c at W + c * ldw) and the identity permutation
 template <typename R>
-__device__ __forceinline__ void bic_norms(const cx<R> *W, int ldw, int m, int n, R *vn1, R *vn2, int *jp, int wv, int lane) {
+__device__ __forceinline__ void bic_norms(const cplx<R> *W, int ldw, int m, int n, R *vn1, R *vn2, int *jp, int wv, int lane) {
     for (int c = wv; c < n; c += BIC_WAVES) {
         R acc = 0;
         for (int i = lane; i < m; i += 64) acc += abs2(W[(size_t)c * ldw + i]);
@@ -156,7 +131,7 @@ __device__ __forceinline__ void bic_norms(const cx<R> *W, int ldw, int m, int n,
 // working copy W[c * ldw + i] = at(i, c), read with the lanes along i (lanes_on_rows) or along c (the input's fast direction),
 // then the initial column norms and the identity permutation
 template <typename R, typename At>
-__device__ __forceinline__ void bic_load(cx<R> *W, int ldw, int m, int n, bool lanes_on_rows, At at, R *vn1, R *vn2, int *jp, int wv, int lane) {
+__device__ __forceinline__ void bic_load(cplx<R> *W, int ldw, int m, int n, bool lanes_on_rows, At at, R *vn1, R *vn2, int *jp, int wv, int lane) {
     if (lanes_on_rows) {
         for (int c = wv; c < n; c += BIC_WAVES)
             for (int i = lane; i < m; i += 64) W[(size_t)c * ldw + i] = at(i, c);
@@ -173,8 +148,8 @@ __device__ __forceinline__ void bic_load(cx<R> *W, int ldw, int m, int n, bool l
 // FULL (the batched SVD): no stopping rule, all k steps are taken (an exactly zero pivot column is a step with H = I) and the complex
 // tau_j goes to taus[j]; returns k.
 template <typename R, bool FULL = false>
-__device__ __forceinline__ int bic_qrcp(cx<R> *W, int ldw, int m, int n, int k, double tol, int *jp, R *vn1, R *vn2, R *red, int tid, int wv, int lane,
-                                        cx<R> *taus = nullptr) {
+__device__ __forceinline__ int bic_qrcp(cplx<R> *W, int ldw, int m, int n, int k, double tol, int *jp, R *vn1, R *vn2, R *red, int tid, int wv, int lane,
+                                        cplx<R> *taus = nullptr) {
     int r = k;
     [[maybe_unused]] R r00 = 0;
     for (int j = 0; j < k; ++j) {
@@ -196,8 +171,8 @@ __device__ __forceinline__ int bic_qrcp(cx<R> *W, int ldw, int m, int n, int k, 
         }
         __syncthreads();
         // ?larfg for complex on column jp[j], rows j..m-1 (k_c_qr_pivot_reflect's formula)
-        cx<R> *col = W + (size_t)jp[j] * ldw;
-        const cx<R> alpha = col[j];
+        cplx<R> *col = W + (size_t)jp[j] * ldw;
+        const cplx<R> alpha = col[j];
         R acc = 0;
         for (int i = j + 1 + tid; i < m; i += BIC_THREADS) acc += abs2(col[i]);
         acc = wave_sum_dpp(acc);
@@ -206,13 +181,13 @@ __device__ __forceinline__ int bic_qrcp(cx<R> *W, int ldw, int m, int n, int k, 
         const R ssq = (red[0] + red[1]) + (red[2] + red[3]);
         const R xnorm = sqrt(ssq);
         R beta = alpha.re;
-        cx<R> tj = czero<R>();
+        cplx<R> tj = czero<R>();
         if (xnorm != (R)0 || alpha.im != (R)0) {
             beta = -copysign(sqrt(alpha.re * alpha.re + alpha.im * alpha.im + ssq), alpha.re);  // ?lapy3
-            const cx<R> scal = cdiv(cone<R>(), cx<R>{alpha.re - beta, alpha.im});
-            for (int i = j + 1 + tid; i < m; i += BIC_THREADS) col[i] = cmul(col[i], scal);
-            tj = cx<R>{(beta - alpha.re) / beta, -alpha.im / beta};
-            if (tid == 0) col[j] = cx<R>{beta, (R)0};
+            const cplx<R> scal = cdiv(cone<R>(), cplx<R>{alpha.re - beta, alpha.im});
+            for (int i = j + 1 + tid; i < m; i += BIC_THREADS) col[i] = col[i] * scal;
+            tj = cplx<R>{(beta - alpha.re) / beta, -alpha.im / beta};
+            if (tid == 0) col[j] = cplx<R>{beta, (R)0};
         }
         if constexpr (FULL) {
             if (tid == 0) taus[j] = tj;
@@ -238,27 +213,27 @@ __device__ __forceinline__ int bic_qrcp(cx<R> *W, int ldw, int m, int n, int k, 
 // blocked back substitution with k -> r (8 x 8 tiles of R11 staged in LDS, one thread per right-hand side, complex division on the
 // diagonal), each column written straight to its final place
 template <typename R, bool CONJ>
-__device__ __forceinline__ void bic_z(const cx<R> *W, int ldw, int n, int r, int k, const int *jp, cx<R> (*tile)[BIC_NB + 1], cx<R> *Zb, int64_t zrs,
+__device__ __forceinline__ void bic_z(const cplx<R> *W, int ldw, int n, int r, int k, const int *jp, cplx<R> (*tile)[BIC_NB + 1], cplx<R> *Zb, int64_t zrs,
                                       int64_t zcs, int tid) {
     const int nblk = (r + BIC_NB - 1) / BIC_NB;
     const int ti = tid / BIC_NB, tk = tid % BIC_NB;
-    auto out = [](cx<R> v) { return CONJ ? conj_of(v) : v; };  // its own inverse
+    auto out = [](cplx<R> v) { return CONJ ? cj(v) : v; };  // its own inverse
     for (int q0 = 0; q0 < n; q0 += BIC_THREADS) {
         const int p = q0 + tid;  // position in the pivoted order
         const bool inside = p < n;
         const int dc = inside ? jp[p] : 0;  // where column p of [I | R11^-1 R12] goes
         const bool active = inside && p >= r;
-        cx<R> *zc = Zb + (int64_t)dc * zcs;
+        cplx<R> *zc = Zb + (int64_t)dc * zcs;
         if (inside) {
             if (p < r)
                 for (int i = 0; i < k; ++i) zc[i * zrs] = (i == p) ? cone<R>() : czero<R>();
             else
                 for (int i = r; i < k; ++i) zc[i * zrs] = czero<R>();
         }
-        const cx<R> *bcol = W + (size_t)dc * ldw;  // R12[:, p]: rows 0 .. r-1 of the physical column
+        const cplx<R> *bcol = W + (size_t)dc * ldw;  // R12[:, p]: rows 0 .. r-1 of the physical column
         for (int bi = nblk - 1; bi >= 0; --bi) {
             const int r0 = bi * BIC_NB;
-            cx<R> acc[BIC_NB];
+            cplx<R> acc[BIC_NB];
 #pragma unroll
             for (int ii = 0; ii < BIC_NB; ++ii) acc[ii] = (active && r0 + ii < r) ? bcol[r0 + ii] : czero<R>();
             for (int bj = nblk - 1; bj >= bi; --bj) {
@@ -270,20 +245,20 @@ __device__ __forceinline__ void bic_z(const cx<R> *W, int ldw, int n, int r, int
                 }
                 __syncthreads();
                 if (bj > bi) {
-                    cx<R> x[BIC_NB];
+                    cplx<R> x[BIC_NB];
 #pragma unroll
                     for (int jj = 0; jj < BIC_NB; ++jj) x[jj] = (active && c0 + jj < r) ? out(zc[(c0 + jj) * zrs]) : czero<R>();  // own finished block
 #pragma unroll
                     for (int jj = 0; jj < BIC_NB; ++jj)
 #pragma unroll
-                        for (int ii = 0; ii < BIC_NB; ++ii) acc[ii] = csub(acc[ii], cmul(tile[ii][jj], x[jj]));
+                        for (int ii = 0; ii < BIC_NB; ++ii) acc[ii] = acc[ii] - tile[ii][jj] * x[jj];
                 } else {
 #pragma unroll
                     for (int ii = BIC_NB - 1; ii >= 0; --ii) {
                         if (r0 + ii < r) {
                             acc[ii] = cdiv(acc[ii], tile[ii][ii]);
 #pragma unroll
-                            for (int i2 = 0; i2 < ii; ++i2) acc[i2] = csub(acc[i2], cmul(tile[i2][ii], acc[ii]));
+                            for (int i2 = 0; i2 < ii; ++i2) acc[i2] = acc[i2] - tile[i2][ii] * acc[ii];
                         }
                     }
                 }
@@ -298,15 +273,15 @@ __device__ __forceinline__ void bic_z(const cx<R> *W, int ldw, int n, int r, int
 }
 
 template <typename R, bool IN_LDS>
-__global__ __launch_bounds__(BIC_THREADS) void k_batched_id_c(CView<R> a, int64_t abs, int count, int k, double tol, CView<R> cm, int64_t cbs,
-                                                              CView<R> z, int64_t zbs, int64_t *__restrict__ col_ind, int64_t *__restrict__ ranks,
-                                                              cx<R> *__restrict__ ws) {
+__global__ __launch_bounds__(BIC_THREADS) void k_batched_id_c(CV<R> a, int64_t abs, int count, int k, double tol, CV<R> cm, int64_t cbs,
+                                                              CV<R> z, int64_t zbs, int64_t *__restrict__ col_ind, int64_t *__restrict__ ranks,
+                                                              cplx<R> *__restrict__ ws) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int m = (int)a.rows, n = (int)a.cols;
     const int ldw = IN_LDS ? (m | 1) : m;
-    cx<R> *lds = reinterpret_cast<cx<R> *>(smem_raw);
-    cx<R> *W = IN_LDS ? lds : ws + (size_t)blockIdx.x * (size_t)m * (size_t)n;
-    cx<R>(*tile)[BIC_NB + 1] = reinterpret_cast<cx<R>(*)[BIC_NB + 1]>(lds + (IN_LDS ? (size_t)n * ldw : 0));
+    cplx<R> *lds = reinterpret_cast<cplx<R> *>(smem_raw);
+    cplx<R> *W = IN_LDS ? lds : ws + (size_t)blockIdx.x * (size_t)m * (size_t)n;
+    cplx<R>(*tile)[BIC_NB + 1] = reinterpret_cast<cplx<R>(*)[BIC_NB + 1]>(lds + (IN_LDS ? (size_t)n * ldw : 0));
     R *vn1 = reinterpret_cast<R *>(lds + (IN_LDS ? (size_t)n * ldw : 0) + BIC_NB * (BIC_NB + 1));
     R *vn2 = vn1 + n;
     R *red = vn2 + n;
@@ -314,16 +289,16 @@ __global__ __launch_bounds__(BIC_THREADS) void k_batched_id_c(CView<R> a, int64_
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 
     for (int b = blockIdx.x; b < count; b += gridDim.x) {
-        const cx<R> *__restrict__ A = a.p + (int64_t)b * abs;
+        const cplx<R> *__restrict__ A = a.p + (int64_t)b * abs;
         bic_load(W, ldw, m, n, a.rs <= a.cs, [&](int i, int c) { return A[i * a.rs + c * a.cs]; }, vn1, vn2, jp, wv, lane);
         const int r = bic_qrcp(W, ldw, m, n, k, tol, jp, vn1, vn2, red, tid, wv, lane);
 
         // ---- outputs: permutation, rank, C, Z -------------------------------------------------------------------
         for (int p = tid; p < n; p += BIC_THREADS) col_ind[(int64_t)b * n + p] = jp[p];
         if (tid == 0) ranks[b] = r;
-        cx<R> *Cb = cm.p + (int64_t)b * cbs;
+        cplx<R> *Cb = cm.p + (int64_t)b * cbs;
         for (int j = wv; j < k; j += BIC_WAVES) {
-            const cx<R> *src = A + (int64_t)jp[j] * a.cs;
+            const cplx<R> *src = A + (int64_t)jp[j] * a.cs;
             for (int i = lane; i < m; i += 64) Cb[i * cm.rs + j * cm.cs] = j < r ? src[i * a.rs] : czero<R>();
         }
         bic_z<R, false>(W, ldw, n, r, k, jp, tile, z.p + (int64_t)b * zbs, z.rs, z.cs, tid);
@@ -341,22 +316,22 @@ template <typename R>
 size_t btc_lds_bytes(int m, int n, int k, bool in_lds) {
     size_t c = (size_t)BIC_NB * (BIC_NB + 1);
     if (in_lds) c += btc_w_elems(m, n, k);
-    return c * sizeof(cx<R>) + ((size_t)2 * std::max(m, n) + 8) * sizeof(R) + (size_t)(m + n) * sizeof(int);
+    return c * sizeof(cplx<R>) + ((size_t)2 * std::max(m, n) + 8) * sizeof(R) + (size_t)(m + n) * sizeof(int);
 }
 
 // Two-sided ID A ~ C X R per matrix: phase 1 is k_batched_id_c's column ID (R = its Z, col_ind, the rank r); phase 2 is the column
 // ID of C^H = conj(A[:, col_ind[:r]])^T (r x m) at rank r with tol = 0, by the same three stages: its permutation is row_ind and its
 // Z, conjugated and written through c's transposed view, is c = Z2^H; X = A[row_ind[:r], col_ind[:r]] is gathered from the input.
 template <typename R, bool IN_LDS>
-__global__ __launch_bounds__(BIC_THREADS) void k_batched_two_sided_c(CView<R> a, int64_t abs, int count, int k, double tol, CView<R> cm, int64_t cbs,
-                                                                     CView<R> xm, int64_t xbs, CView<R> z, int64_t zbs, int64_t *__restrict__ row_ind,
-                                                                     int64_t *__restrict__ col_ind, int64_t *__restrict__ ranks, cx<R> *__restrict__ ws) {
+__global__ __launch_bounds__(BIC_THREADS) void k_batched_two_sided_c(CV<R> a, int64_t abs, int count, int k, double tol, CV<R> cm, int64_t cbs,
+                                                                     CV<R> xm, int64_t xbs, CV<R> z, int64_t zbs, int64_t *__restrict__ row_ind,
+                                                                     int64_t *__restrict__ col_ind, int64_t *__restrict__ ranks, cplx<R> *__restrict__ ws) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int m = (int)a.rows, n = (int)a.cols, mn = m > n ? m : n;
     const int ldw = IN_LDS ? (m | 1) : m;
-    cx<R> *lds = reinterpret_cast<cx<R> *>(smem_raw);
-    cx<R> *W = IN_LDS ? lds : ws + (size_t)blockIdx.x * (size_t)m * (size_t)n;
-    cx<R>(*tile)[BIC_NB + 1] = reinterpret_cast<cx<R>(*)[BIC_NB + 1]>(lds + (IN_LDS ? btc_w_elems(m, n, k) : 0));
+    cplx<R> *lds = reinterpret_cast<cplx<R> *>(smem_raw);
+    cplx<R> *W = IN_LDS ? lds : ws + (size_t)blockIdx.x * (size_t)m * (size_t)n;
+    cplx<R>(*tile)[BIC_NB + 1] = reinterpret_cast<cplx<R>(*)[BIC_NB + 1]>(lds + (IN_LDS ? btc_w_elems(m, n, k) : 0));
     R *vn1 = reinterpret_cast<R *>(lds + (IN_LDS ? btc_w_elems(m, n, k) : 0) + BIC_NB * (BIC_NB + 1));
     R *vn2 = vn1 + mn;
     R *red = vn2 + mn;
@@ -365,7 +340,7 @@ __global__ __launch_bounds__(BIC_THREADS) void k_batched_two_sided_c(CView<R> a,
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 
     for (int b = blockIdx.x; b < count; b += gridDim.x) {
-        const cx<R> *__restrict__ A = a.p + (int64_t)b * abs;
+        const cplx<R> *__restrict__ A = a.p + (int64_t)b * abs;
         // ---- phase 1: column ID of A -> r (= Z), col_ind, the rank --------------------------------------------------
         bic_load(W, ldw, m, n, a.rs <= a.cs, [&](int i, int c) { return A[i * a.rs + c * a.cs]; }, vn1, vn2, jp, wv, lane);
         const int r = bic_qrcp(W, ldw, m, n, k, tol, jp, vn1, vn2, red, tid, wv, lane);
@@ -376,15 +351,15 @@ __global__ __launch_bounds__(BIC_THREADS) void k_batched_two_sided_c(CView<R> a,
 
         // ---- phase 2: column ID of C^H (r x m), W2[p][i] = conj(A[p, col_ind[i]]) -> c = Z2^H, row_ind ------------------
         const int ldw2 = IN_LDS ? (r | 1) : r;
-        bic_load(W, ldw2, r, m, a.cs < a.rs, [&](int i, int p) { return conj_of(A[p * a.rs + jp[i] * a.cs]); }, vn1, vn2, jp2, wv, lane);
+        bic_load(W, ldw2, r, m, a.cs < a.rs, [&](int i, int p) { return cj(A[p * a.rs + jp[i] * a.cs]); }, vn1, vn2, jp2, wv, lane);
         const int r2 = bic_qrcp(W, ldw2, r, m, r, 0.0, jp2, vn1, vn2, red, tid, wv, lane);  // r2 < r only on an exactly zero pivot
         for (int p = tid; p < m; p += BIC_THREADS) row_ind[(int64_t)b * m + p] = jp2[p];
         bic_z<R, true>(W, ldw2, m, r2, k, jp2, tile, cm.p + (int64_t)b * cbs, cm.cs, cm.rs, tid);  // Z2^H (m x k) through c's transposed view
 
         // ---- X = A[row_ind[:r], col_ind[:r]], rows and columns r..k-1 zero --------------------------------------------------
-        cx<R> *Xb = xm.p + (int64_t)b * xbs;
+        cplx<R> *Xb = xm.p + (int64_t)b * xbs;
         for (int j = wv; j < k; j += BIC_WAVES) {
-            const cx<R> *src = A + (int64_t)jp[j] * a.cs;
+            const cplx<R> *src = A + (int64_t)jp[j] * a.cs;
             for (int i = lane; i < k; i += 64) Xb[i * xm.rs + j * xm.cs] = (i < r && j < r) ? src[jp2[i] * a.rs] : czero<R>();
         }
         __syncthreads();  // W, jp, jp2 and the norms are rewritten by the next matrix
@@ -407,9 +382,9 @@ __global__ __launch_bounds__(BIC_THREADS) void k_batched_two_sided_c(CView<R> a,
 // less, whose app aqq and |apq|^2 pass the smallest f32 number, are still rotated until they are orthogonal; without it the text is
 // the batched SVD's
 template <typename R, int NE, bool WIDE = false>
-__device__ __forceinline__ void bsc_round(cx<R> *G, int ldg, cx<R> *J, int ldj, int N, int p, int q, R tol, R tol2, int ll, int *flag) {
-    cx<R> *gp = G + (size_t)p * ldg, *gq = G + (size_t)q * ldg;
-    cx<R> a[NE], b[NE];
+__device__ __forceinline__ void bsc_round(cplx<R> *G, int ldg, cplx<R> *J, int ldj, int N, int p, int q, R tol, R tol2, int ll, int *flag) {
+    cplx<R> *gp = G + (size_t)p * ldg, *gq = G + (size_t)q * ldg;
+    cplx<R> a[NE], b[NE];
     R app = 0, aqq = 0, are = 0, aim = 0;  // apq = g_p^H g_q = (are, aim)
 #pragma unroll
     for (int e = 0; e < NE; ++e) {
@@ -437,21 +412,21 @@ __device__ __forceinline__ void bsc_round(cx<R> *G, int ldg, cx<R> *J, int ldj, 
         if (!(h2 > tol2 * app * aqq)) return;
     }
     const double hd = sqrt((double)are * (double)are + (double)aim * (double)aim), ih = 1.0 / hd;
-    const cx<R> ph{(R)((double)are * ih), (R)(-((double)aim * ih))};  // e^{-i phi}
+    const cplx<R> ph{(R)((double)are * ih), (R)(-((double)aim * ih))};  // e^{-i phi}
     double cd, sd;
     jacobi_rotation<double>((double)app, (double)aqq, hd, cd, sd);
     const R c = (R)cd, s = (R)sd;
-    cx<R> *vp = J + (size_t)p * ldj, *vq = J + (size_t)q * ldj;
+    cplx<R> *vp = J + (size_t)p * ldj, *vq = J + (size_t)q * ldj;
 #pragma unroll
     for (int e = 0; e < NE; ++e) {
         const int i = ll + 16 * e;
         if (i < N) {
-            const cx<R> bq = cmul(ph, b[e]);
-            gp[i] = cx<R>{c * a[e].re - s * bq.re, c * a[e].im - s * bq.im};
-            gq[i] = cx<R>{s * a[e].re + c * bq.re, s * a[e].im + c * bq.im};
-            const cx<R> x = vp[i], y = cmul(ph, vq[i]);
-            vp[i] = cx<R>{c * x.re - s * y.re, c * x.im - s * y.im};
-            vq[i] = cx<R>{s * x.re + c * y.re, s * x.im + c * y.im};
+            const cplx<R> bq = ph * b[e];
+            gp[i] = cplx<R>{c * a[e].re - s * bq.re, c * a[e].im - s * bq.im};
+            gq[i] = cplx<R>{s * a[e].re + c * bq.re, s * a[e].im + c * bq.im};
+            const cplx<R> x = vp[i], y = ph * vq[i];
+            vp[i] = cplx<R>{c * x.re - s * y.re, c * x.im - s * y.im};
+            vq[i] = cplx<R>{s * x.re + c * y.re, s * x.im + c * y.im};
         }
     }
     if constexpr (WIDE) {
@@ -465,7 +440,7 @@ __device__ __forceinline__ void bsc_round(cx<R> *G, int ldg, cx<R> *J, int ldj, 
 // bsv_jacobi's schedule (round-robin pairs, 16 lanes per pair, one barrier per round, kMaxSweeps) on the complex core.  Returns false
 // when the sweep budget ran out before a quiet sweep.
 template <typename R, int NE, bool WIDE = false>
-__device__ __forceinline__ bool bsc_jacobi(cx<R> *G, int ldg, cx<R> *J, int ldj, int N, int tid, int *flag) {
+__device__ __forceinline__ bool bsc_jacobi(cplx<R> *G, int ldg, cplx<R> *J, int ldj, int N, int tid, int *flag) {
     const int ll = tid & 15, grp = tid >> 4;
     constexpr int NGRP = BIC_THREADS / 16;
     const int N2 = (N + 1) & ~1, npairs = N2 / 2;
@@ -492,7 +467,7 @@ __device__ __forceinline__ bool bsc_jacobi(cx<R> *G, int ldg, cx<R> *J, int ldj,
 // |x|^2; the column is multiplied by ph = conj(x_i*) / |x_i*| (f64, rounded) and x_i* becomes exactly (|x_i*|, 0).  Returns ph;
 // (1, 0) with the column unchanged when |x_i*| is not positive and finite (a zero or non-finite column)
 template <typename R, int NE, typename Row>
-__device__ __forceinline__ cx<R> bsc_phase(cx<R> (&x)[NE], Row orow, int lane) {
+__device__ __forceinline__ cplx<R> bsc_phase(cplx<R> (&x)[NE], Row orow, int lane) {
     R mx = 0;
 #pragma unroll
     for (int e = 0; e < NE; ++e)
@@ -511,16 +486,16 @@ __device__ __forceinline__ cx<R> bsc_phase(cx<R> (&x)[NE], Row orow, int lane) {
         if (key != 0x7fffffff && orow(e) == key) who = 64 * e + lane;
     who = wave_min_dpp(who);
     if (who == 0x7fffffff) return cone<R>();
-    cx<R> xs = czero<R>();
+    cplx<R> xs = czero<R>();
 #pragma unroll
     for (int e = 0; e < NE; ++e)
-        if (e == (who >> 6)) xs = cx<R>{read_lane(x[e].re, who & 63), read_lane(x[e].im, who & 63)};
+        if (e == (who >> 6)) xs = cplx<R>{read_lane(x[e].re, who & 63), read_lane(x[e].im, who & 63)};
     const double md = hypot((double)xs.re, (double)xs.im);
     if (!(md > 0.0 && md <= 1.7976931348623157e308)) return cone<R>();
-    const cx<R> ph{(R)((double)xs.re / md), (R)(-((double)xs.im / md))};
+    const cplx<R> ph{(R)((double)xs.re / md), (R)(-((double)xs.im / md))};
     const R mr = (R)md;
 #pragma unroll
-    for (int e = 0; e < NE; ++e) x[e] = orow(e) == key ? cx<R>{mr, (R)0} : cmul(x[e], ph);
+    for (int e = 0; e < NE; ++e) x[e] = orow(e) == key ? cplx<R>{mr, (R)0} : x[e] * ph;
     return ph;
 }
 
@@ -529,38 +504,38 @@ __device__ __forceinline__ cx<R> bsc_phase(cx<R> (&x)[NE], Row orow, int lane) {
 // applied H_j^H, forming Q applies H_j), v_j in W's column jp[j] below row j.  phase_here: the phase rule is applied to this column
 // and its phase stored in phs[c]; otherwise the column is multiplied by conj(phs[c]).
 template <typename R, int NE>
-__device__ __forceinline__ void bsc_form_u(const cx<R> *W, int ldw, const cx<R> *J, int ldj, int M, int N, int k, int r, const int *jp, const cx<R> *taus,
-                                           const int *srt, cx<R> *phs, bool phase_here, cx<R> *U, int64_t urs, int64_t ucs, int wv, int lane) {
+__device__ __forceinline__ void bsc_form_u(const cplx<R> *W, int ldw, const cplx<R> *J, int ldj, int M, int N, int k, int r, const int *jp, const cplx<R> *taus,
+                                           const int *srt, cplx<R> *phs, bool phase_here, cplx<R> *U, int64_t urs, int64_t ucs, int wv, int lane) {
     for (int c = wv; c < k; c += BIC_WAVES) {
-        cx<R> *uc = U + (int64_t)c * ucs;
+        cplx<R> *uc = U + (int64_t)c * ucs;
         if (c >= r) {
             for (int i = lane; i < M; i += 64) uc[i * urs] = czero<R>();
             continue;
         }
-        const cx<R> *jc = J + (size_t)srt[c] * ldj;
-        cx<R> x[NE];
+        const cplx<R> *jc = J + (size_t)srt[c] * ldj;
+        cplx<R> x[NE];
 #pragma unroll
         for (int e = 0; e < NE; ++e) {
             const int i = lane + 64 * e;
             x[e] = i < N ? jc[i] : czero<R>();
         }
         for (int j = N - 1; j >= 0; --j) {
-            const cx<R> tau = taus[j];
+            const cplx<R> tau = taus[j];
             if (tau.re == (R)0 && tau.im == (R)0) continue;  // H_j = I (uniform)
-            const cx<R> *vc = W + (size_t)jp[j] * ldw;
-            cx<R> v[NE];
+            const cplx<R> *vc = W + (size_t)jp[j] * ldw;
+            cplx<R> v[NE];
             R dre = 0, dim = 0;  // v^H x
 #pragma unroll
             for (int e = 0; e < NE; ++e) {
                 const int i = lane + 64 * e;
-                const cx<R> vv = vc[i < M ? i : j];  // branch-free: lanes out of range read row j and are masked below
+                const cplx<R> vv = vc[i < M ? i : j];  // branch-free: lanes out of range read row j and are masked below
                 v[e] = i > j && i < M ? vv : (i == j ? cone<R>() : czero<R>());
                 dre = fma(v[e].re, x[e].re, dre);
                 dre = fma(v[e].im, x[e].im, dre);
                 dim = fma(v[e].re, x[e].im, dim);
                 dim = fma(-v[e].im, x[e].re, dim);
             }
-            const cx<R> f = cmul(tau, cx<R>{wave_sum_dpp(dre), wave_sum_dpp(dim)});
+            const cplx<R> f = tau * cplx<R>{wave_sum_dpp(dre), wave_sum_dpp(dim)};
 #pragma unroll
             for (int e = 0; e < NE; ++e) {
                 x[e].re = fma(-f.re, v[e].re, x[e].re);
@@ -570,12 +545,12 @@ __device__ __forceinline__ void bsc_form_u(const cx<R> *W, int ldw, const cx<R> 
             }
         }
         if (phase_here) {
-            const cx<R> ph = bsc_phase<R, NE>(x, [&](int e) { const int i = lane + 64 * e; return i < M ? i : -1; }, lane);
+            const cplx<R> ph = bsc_phase<R, NE>(x, [&](int e) { const int i = lane + 64 * e; return i < M ? i : -1; }, lane);
             if (lane == 0) phs[c] = ph;
         } else {
-            const cx<R> ph = conj_of(phs[c]);
+            const cplx<R> ph = cj(phs[c]);
 #pragma unroll
-            for (int e = 0; e < NE; ++e) x[e] = cmul(x[e], ph);
+            for (int e = 0; e < NE; ++e) x[e] = x[e] * ph;
         }
 #pragma unroll
         for (int e = 0; e < NE; ++e) {
@@ -593,7 +568,7 @@ size_t bsc_lds_bytes(int M, int N, int ldg, bool w_lds, bool v_lds, bool g_lds) 
     if (w_lds) c += (size_t)N * (size_t)(M | 1);
     if (g_lds) c += (size_t)N * ldg;
     if (v_lds) c += (size_t)N * ldg;
-    return c * sizeof(cx<R>) + ((size_t)3 * N + 8) * sizeof(R) + (size_t)(2 * N + 4) * sizeof(int);
+    return c * sizeof(cplx<R>) + ((size_t)3 * N + 8) * sizeof(R) + (size_t)(2 * N + 4) * sizeof(int);
 }
 // complex elements of one workgroup's workspace slot: W (M x N), G (N x ldg), J (N x N), each unless it is in LDS
 __host__ __device__ inline size_t bsc_ws_elems(int M, int N, int ldg, bool w_lds, bool v_lds, bool g_lds) {
@@ -604,20 +579,20 @@ __host__ __device__ inline size_t bsc_ws_elems(int M, int N, int ldg, bool w_lds
 // vt^T and u^T for a wide one), each moved by its own batch stride; s (count x N) and ranks contiguous.  W_LDS / G_LDS / V_LDS: the
 // working copy W / the core G / the rotations J live in LDS, else in the workgroup's workspace slot (in that order, ldg = N there).
 template <typename R, bool W_LDS, bool V_LDS, bool G_LDS>
-__global__ __launch_bounds__(BIC_THREADS) void k_batched_svd_c(CView<R> a, int64_t abs, int count, int k, double tol, CView<R> uo, int64_t ubs, CView<R> vo,
-                                                               int64_t vbs, R *__restrict__ s_out, int64_t *__restrict__ ranks, cx<R> *__restrict__ ws,
+__global__ __launch_bounds__(BIC_THREADS) void k_batched_svd_c(CV<R> a, int64_t abs, int count, int k, double tol, CV<R> uo, int64_t ubs, CV<R> vo,
+                                                               int64_t vbs, R *__restrict__ s_out, int64_t *__restrict__ ranks, cplx<R> *__restrict__ ws,
                                                                int *health, int ldg) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const bool wide = a.rows < a.cols;
     const int M = (int)(wide ? a.cols : a.rows), N = (int)(wide ? a.rows : a.cols);
     const int ldw = W_LDS ? (M | 1) : M, ldj = V_LDS ? ldg : N;
-    cx<R> *lp = reinterpret_cast<cx<R> *>(smem_raw);                                    // next free LDS element
-    cx<R> *wp = ws + (size_t)blockIdx.x * bsc_ws_elems(M, N, ldg, W_LDS, V_LDS, G_LDS);  // next free element of the workspace slot
-    cx<R> *W, *G, *J;
+    cplx<R> *lp = reinterpret_cast<cplx<R> *>(smem_raw);                                    // next free LDS element
+    cplx<R> *wp = ws + (size_t)blockIdx.x * bsc_ws_elems(M, N, ldg, W_LDS, V_LDS, G_LDS);  // next free element of the workspace slot
+    cplx<R> *W, *G, *J;
     if (W_LDS) { W = lp; lp += (size_t)N * ldw; } else { W = wp; wp += (size_t)N * ldw; }
     if (G_LDS) { G = lp; lp += (size_t)N * ldg; } else { G = wp; wp += (size_t)N * ldg; }
     if (V_LDS) { J = lp; lp += (size_t)N * ldj; } else { J = wp; }
-    cx<R> *taus = lp, *phs = taus + N;
+    cplx<R> *taus = lp, *phs = taus + N;
     R *vn1 = reinterpret_cast<R *>(phs + 128);
     R *vn2 = vn1 + N, *sig = vn2 + N, *red = sig + N;
     int *jp = reinterpret_cast<int *>(red + 8);
@@ -627,14 +602,14 @@ __global__ __launch_bounds__(BIC_THREADS) void k_batched_svd_c(CView<R> a, int64
     const int64_t ars = wide ? a.cs : a.rs, acs = wide ? a.rs : a.cs;
 
     for (int b = blockIdx.x; b < count; b += gridDim.x) {
-        const cx<R> *__restrict__ A = a.p + (int64_t)b * abs;
+        const cplx<R> *__restrict__ A = a.p + (int64_t)b * abs;
         // ---- QR: W P = Q R, all N steps (exact zero pivots are steps with H = I), complex taus kept -------------------------------
         bic_load(W, ldw, M, N, ars <= acs, [&](int i, int c) { return A[i * ars + c * acs]; }, vn1, vn2, jp, wv, lane);
         bic_qrcp<R, true>(W, ldw, M, N, N, 0.0, jp, vn1, vn2, red, tid, wv, lane, taus);
         // ---- core G = R^H (R in pivoted column order: G[:, j] = conj(row j of R)) and J = I -----------------------------------------
         for (int j = wv; j < N; j += BIC_WAVES) {
             for (int i = lane; i < N; i += 64) {
-                G[(size_t)j * ldg + i] = i >= j ? conj_of(W[(size_t)jp[i] * ldw + j]) : czero<R>();
+                G[(size_t)j * ldg + i] = i >= j ? cj(W[(size_t)jp[i] * ldw + j]) : czero<R>();
                 J[(size_t)j * ldj + i] = i == j ? cone<R>() : czero<R>();
             }
         }
@@ -647,7 +622,7 @@ __global__ __launch_bounds__(BIC_THREADS) void k_batched_svd_c(CView<R> a, int64
         if (!conv && tid == 0) atomicOr(health, 16);  // the sweep budget ran out: bit 16, as the lone Jacobi reports it
         // ---- singular values: column norms, sorted descending (a strict total order: NaN last, ties by column) ----------------------
         for (int j = tid >> 4; j < N; j += BIC_THREADS / 16) {
-            const cx<R> *gj = G + (size_t)j * ldg;
+            const cplx<R> *gj = G + (size_t)j * ldg;
             R acc = 0;
             for (int i = tid & 15; i < N; i += 16) {
                 acc = fma(gj[i].re, gj[i].re, acc);
@@ -682,23 +657,23 @@ __global__ __launch_bounds__(BIC_THREADS) void k_batched_svd_c(CView<R> a, int64
         }
         __syncthreads();
         const int r = flag[1];
-        cx<R> *Vb = vo.p + (int64_t)b * vbs;
+        cplx<R> *Vb = vo.p + (int64_t)b * vbs;
         // ---- phases on the caller's u.  Wide: u[:, c] is row c of vo, u[jp[i], c] = conj(G[i, srt[c]]) / s_c; its phase is fixed
         // and the row written here, before U is formed.  Tall: in bsc_form_u. ------------------------------------------------------
         if (wide) {
             for (int c = wv; c < k; c += BIC_WAVES) {
                 const int j0 = c < r ? srt[c] : 0;
-                const cx<R> *gc = G + (size_t)j0 * ldg;
+                const cplx<R> *gc = G + (size_t)j0 * ldg;
                 const R sj = sig[j0], inv = sj > (R)0 ? (R)1 / sj : (R)0;
-                cx<R> x[2];
+                cplx<R> x[2];
 #pragma unroll
                 for (int e = 0; e < 2; ++e) {
                     const int i = lane + 64 * e;
-                    const cx<R> g = i < N ? gc[i] : czero<R>();
-                    x[e] = c < r ? cx<R>{g.re * inv, -(g.im * inv)} : czero<R>();
+                    const cplx<R> g = i < N ? gc[i] : czero<R>();
+                    x[e] = c < r ? cplx<R>{g.re * inv, -(g.im * inv)} : czero<R>();
                 }
                 if (c < r) {
-                    const cx<R> ph = bsc_phase<R, 2>(x, [&](int e) { const int i = lane + 64 * e; return i < N ? jp[i] : -1; }, lane);
+                    const cplx<R> ph = bsc_phase<R, 2>(x, [&](int e) { const int i = lane + 64 * e; return i < N ? jp[i] : -1; }, lane);
                     if (lane == 0) phs[c] = ph;
                 }
 #pragma unroll
@@ -710,7 +685,7 @@ __global__ __launch_bounds__(BIC_THREADS) void k_batched_svd_c(CView<R> a, int64
             __syncthreads();
         }
         // ---- U = Q [J_k; 0] straight into the output view -------------------------------------------------------------------------
-        cx<R> *Ub = uo.p + (int64_t)b * ubs;
+        cplx<R> *Ub = uo.p + (int64_t)b * ubs;
         if (M <= 64) bsc_form_u<R, 1>(W, ldw, J, ldj, M, N, k, r, jp, taus, srt, phs, !wide, Ub, uo.rs, uo.cs, wv, lane);
         else if (M <= 128) bsc_form_u<R, 2>(W, ldw, J, ldj, M, N, k, r, jp, taus, srt, phs, !wide, Ub, uo.rs, uo.cs, wv, lane);
         else if (M <= 256) bsc_form_u<R, 4>(W, ldw, J, ldj, M, N, k, r, jp, taus, srt, phs, !wide, Ub, uo.rs, uo.cs, wv, lane);
@@ -720,12 +695,12 @@ __global__ __launch_bounds__(BIC_THREADS) void k_batched_svd_c(CView<R> a, int64
             // ---- V^H: row c of vo is conj(V_W[:, c] ph_c), V_W[jp[i], c] = G[i, srt[c]] / s_c; rows r..k-1 zero ----------------------
             for (int c = wv; c < k; c += BIC_WAVES) {
                 const int j0 = c < r ? srt[c] : 0;
-                const cx<R> *gc = G + (size_t)j0 * ldg;
+                const cplx<R> *gc = G + (size_t)j0 * ldg;
                 const R sj = sig[j0], inv = sj > (R)0 ? (R)1 / sj : (R)0;
-                const cx<R> ph = c < r ? phs[c] : czero<R>();
+                const cplx<R> ph = c < r ? phs[c] : czero<R>();
                 for (int i = lane; i < N; i += 64) {
-                    const cx<R> t = cmul(gc[i], ph);
-                    Vb[c * vo.rs + (int64_t)jp[i] * vo.cs] = c < r ? cx<R>{t.re * inv, -(t.im * inv)} : czero<R>();
+                    const cplx<R> t = gc[i] * ph;
+                    Vb[c * vo.rs + (int64_t)jp[i] * vo.cs] = c < r ? cplx<R>{t.re * inv, -(t.im * inv)} : czero<R>();
                 }
             }
         }
@@ -759,13 +734,13 @@ __global__ __launch_bounds__(BIC_THREADS) void k_batched_svd_c(CView<R> a, int64
 
 template <typename R>
 struct BrcCArgs {
-    CView<R> left, mid, right, u, vt;
+    CV<R> left, mid, right, u, vt;
     int64_t lbs, mbs, rbs, ubs, vbs, s_stride;
     const R *s;
     const int64_t *in_ranks;
     R *s_out;
     int64_t *ranks;
-    cx<R> *ws;
+    cplx<R> *ws;
     int *health;
     double tol;
     int count, k, ldg;
@@ -781,19 +756,11 @@ size_t brcc_lds_bytes(int m, int n, int K, int ldg, bool l_lds, bool r_lds, bool
     if (r_lds) c += (size_t)K * (size_t)(n | 1);
     if (g_lds) c += (size_t)K * ldg;
     if (v_lds) c += (size_t)K * ldg;
-    return c * sizeof(cx<R>) + ((size_t)3 * K + 8) * sizeof(R) + (size_t)(5 * K + 4) * sizeof(int);
+    return c * sizeof(cplx<R>) + ((size_t)3 * K + 8) * sizeof(R) + (size_t)(5 * K + 4) * sizeof(int);
 }
 // complex elements of one workgroup's workspace slot: Wl (m x K), Wr (n x K), G (K x ldg), J (K x K), each unless it is in LDS
 __host__ __device__ inline size_t brcc_ws_elems(int m, int n, int K, int ldg, bool l_lds, bool r_lds, bool v_lds, bool g_lds) {
     return (l_lds ? 0 : (size_t)m * K) + (r_lds ? 0 : (size_t)n * K) + (g_lds ? 0 : (size_t)K * ldg) + (v_lds ? 0 : (size_t)K * K);
-}
-
-// acc += a b, one complex FMA in the fixed order of the comment above
-template <typename R> __device__ __forceinline__ void cfma(cx<R> a, cx<R> b, cx<R> &acc) {
-    acc.re = fma(a.re, b.re, acc.re);
-    acc.re = fma(-a.im, b.im, acc.re);
-    acc.im = fma(a.re, b.im, acc.im);
-    acc.im = fma(a.im, b.re, acc.im);
 }
 
 template <typename R>
@@ -802,14 +769,14 @@ __global__ __launch_bounds__(BIC_THREADS, 2) void k_batched_recompress_c(BrcCArg
     const int m = (int)a.left.rows, n = (int)a.right.cols, K = (int)a.left.cols;
     const int kk = a.k < K ? a.k : K, ldg = a.ldg;
     const int ldl = a.l_lds ? (m | 1) : m, ldr = a.r_lds ? (n | 1) : n, ldj = a.v_lds ? ldg : K;
-    cx<R> *lp = reinterpret_cast<cx<R> *>(smem_raw);                                                                // next free LDS element
-    cx<R> *wp = a.ws + (size_t)blockIdx.x * brcc_ws_elems(m, n, K, ldg, a.l_lds, a.r_lds, a.v_lds, a.g_lds);      // next free workspace element
-    cx<R> *Wl, *Wr, *G, *J;
+    cplx<R> *lp = reinterpret_cast<cplx<R> *>(smem_raw);                                                                // next free LDS element
+    cplx<R> *wp = a.ws + (size_t)blockIdx.x * brcc_ws_elems(m, n, K, ldg, a.l_lds, a.r_lds, a.v_lds, a.g_lds);      // next free workspace element
+    cplx<R> *Wl, *Wr, *G, *J;
     if (a.l_lds) { Wl = lp; lp += (size_t)K * ldl; } else { Wl = wp; wp += (size_t)m * K; }
     if (a.r_lds) { Wr = lp; lp += (size_t)K * ldr; } else { Wr = wp; wp += (size_t)n * K; }
     if (a.g_lds) { G = lp; lp += (size_t)K * ldg; } else { G = wp; wp += (size_t)K * ldg; }
     if (a.v_lds) { J = lp; lp += (size_t)K * ldj; } else { J = wp; }
-    cx<R> *taul = lp, *taur = taul + K, *phs = taur + K;
+    cplx<R> *taul = lp, *taur = taul + K, *phs = taur + K;
     R *vn1 = reinterpret_cast<R *>(phs + 128);
     R *vn2 = vn1 + K, *sig = vn2 + K, *red = sig + K;
     int *jpl = reinterpret_cast<int *>(red + 8);
@@ -824,7 +791,7 @@ __global__ __launch_bounds__(BIC_THREADS, 2) void k_batched_recompress_c(BrcCArg
         }
         q = __builtin_amdgcn_readfirstlane(q);  // one value per block, uniform by construction
         R *sb = a.s_out + (int64_t)b * K;
-        cx<R> *Ub = a.u.p + (int64_t)b * a.ubs, *Vb = a.vt.p + (int64_t)b * a.vbs;
+        cplx<R> *Ub = a.u.p + (int64_t)b * a.ubs, *Vb = a.vt.p + (int64_t)b * a.vbs;
         for (int i = q + tid; i < K; i += BIC_THREADS) sb[i] = (R)0;
         if (q == 0) {  // uniform over the workgroup; no input is read
             if (tid == 0) a.ranks[b] = 0;
@@ -835,8 +802,8 @@ __global__ __launch_bounds__(BIC_THREADS, 2) void k_batched_recompress_c(BrcCArg
             continue;
         }
         // ---- the two pivoted QRs, q steps each (exact zero pivots are steps with H = I), taus and pivots kept -----------------------
-        const cx<R> *__restrict__ L = a.left.p + (int64_t)b * a.lbs;
-        const cx<R> *__restrict__ Rt = a.right.p + (int64_t)b * a.rbs;
+        const cplx<R> *__restrict__ L = a.left.p + (int64_t)b * a.lbs;
+        const cplx<R> *__restrict__ Rt = a.right.p + (int64_t)b * a.rbs;
         bic_load(Wl, ldl, m, q, a.left.rs <= a.left.cs, [&](int i, int c) { return L[i * a.left.rs + c * a.left.cs]; }, vn1, vn2, jpl, wv, lane);
         bic_qrcp<R, true>(Wl, ldl, m, q, q, 0.0, jpl, vn1, vn2, red, tid, wv, lane, taul);
         bic_load(Wr, ldr, n, q, a.right.cs <= a.right.rs, [&](int i, int c) { return Rt[c * a.right.rs + i * a.right.cs]; }, vn1, vn2, jpr, wv, lane);
@@ -844,24 +811,24 @@ __global__ __launch_bounds__(BIC_THREADS, 2) void k_batched_recompress_c(BrcCArg
         for (int j = tid; j < q; j += BIC_THREADS) { ipl[jpl[j]] = j; ipr[jpr[j]] = j; }
         __syncthreads();
         // ---- T1 = mid diag(s) Rr^T in J's place ----------------------------------------------------------------------------------------
-        const cx<R> *__restrict__ Mb = a.mid.p ? a.mid.p + (int64_t)b * a.mbs : nullptr;
+        const cplx<R> *__restrict__ Mb = a.mid.p ? a.mid.p + (int64_t)b * a.mbs : nullptr;
         const R *__restrict__ Sb = a.s ? a.s + (int64_t)b * a.s_stride : nullptr;
         for (int idx = tid; idx < q * q; idx += BIC_THREADS) {
             const int ai = idx / q, j = idx - ai * q;
-            cx<R> acc;
+            cplx<R> acc;
             if (Mb) {
                 acc = czero<R>();
-                const cx<R> *mr = Mb + (int64_t)ai * a.mid.rs;
+                const cplx<R> *mr = Mb + (int64_t)ai * a.mid.rs;
                 for (int bb = 0; bb < q; ++bb) {
-                    const cx<R> rv = j <= ipr[bb] ? Wr[(size_t)bb * ldr + j] : czero<R>();
-                    cx<R> mv = mr[(int64_t)bb * a.mid.cs];
-                    if (Sb) { const R sv = Sb[bb]; mv = cx<R>{mv.re * sv, mv.im * sv}; }
+                    const cplx<R> rv = j <= ipr[bb] ? Wr[(size_t)bb * ldr + j] : czero<R>();
+                    cplx<R> mv = mr[(int64_t)bb * a.mid.cs];
+                    if (Sb) { const R sv = Sb[bb]; mv = cplx<R>{mv.re * sv, mv.im * sv}; }
                     cfma(mv, rv, acc);
                 }
             } else {
-                const cx<R> rv = j <= ipr[ai] ? Wr[(size_t)ai * ldr + j] : czero<R>();
+                const cplx<R> rv = j <= ipr[ai] ? Wr[(size_t)ai * ldr + j] : czero<R>();
                 acc = rv;
-                if (Sb) { const R sv = Sb[ai]; acc = cx<R>{sv * rv.re, sv * rv.im}; }
+                if (Sb) { const R sv = Sb[ai]; acc = cplx<R>{sv * rv.re, sv * rv.im}; }
             }
             J[(size_t)ai * ldj + j] = acc;
         }
@@ -869,12 +836,12 @@ __global__ __launch_bounds__(BIC_THREADS, 2) void k_batched_recompress_c(BrcCArg
         // ---- G = C^H: G[i * ldg + j] = conj(sum_a Rl[i, a] T1[a, j]) ------------------------------------------------------------------
         for (int idx = tid; idx < q * q; idx += BIC_THREADS) {
             const int i = idx / q, j = idx - i * q;
-            cx<R> acc = czero<R>();
+            cplx<R> acc = czero<R>();
             for (int aa = 0; aa < q; ++aa) {
-                const cx<R> lv = i <= ipl[aa] ? Wl[(size_t)aa * ldl + i] : czero<R>();
+                const cplx<R> lv = i <= ipl[aa] ? Wl[(size_t)aa * ldl + i] : czero<R>();
                 cfma(lv, J[(size_t)aa * ldj + j], acc);
             }
-            G[(size_t)i * ldg + j] = conj_of(acc);
+            G[(size_t)i * ldg + j] = cj(acc);
         }
         __syncthreads();
         for (int idx = tid; idx < q * q; idx += BIC_THREADS) {
@@ -890,7 +857,7 @@ __global__ __launch_bounds__(BIC_THREADS, 2) void k_batched_recompress_c(BrcCArg
         if (!conv && tid == 0) atomicOr(a.health, 16);  // the sweep budget ran out: bit 16, as the batched SVD reports it
         // ---- singular values: column norms, sorted descending (a strict total order: NaN last, ties by column) ----------------------
         for (int j = tid >> 4; j < q; j += BIC_THREADS / 16) {
-            const cx<R> *gj = G + (size_t)j * ldg;
+            const cplx<R> *gj = G + (size_t)j * ldg;
             R acc = 0;
             for (int i = tid & 15; i < q; i += 16) {
                 acc = fma(gj[i].re, gj[i].re, acc);
@@ -932,11 +899,11 @@ __global__ __launch_bounds__(BIC_THREADS, 2) void k_batched_recompress_c(BrcCArg
         else bsc_form_u<R, 8>(Wl, ldl, J, ldj, m, q, kk, r, jpl, taul, srt, phs, true, Ub, a.u.rs, a.u.cs, wv, lane);
         // ---- conj(V_c) = conj(G Sigma^-1) in place (kept columns), then vt^T = Q_R [conj(V_c); 0] conj(ph) through vt's transposed view ---
         for (int c = wv; c < r; c += BIC_WAVES) {
-            cx<R> *gc = G + (size_t)srt[c] * ldg;
+            cplx<R> *gc = G + (size_t)srt[c] * ldg;
             const R sj = sig[srt[c]], inv = sj > (R)0 ? (R)1 / sj : (R)0;
             for (int i = lane; i < q; i += 64) {
-                const cx<R> g = gc[i];
-                gc[i] = cx<R>{g.re * inv, -(g.im * inv)};
+                const cplx<R> g = gc[i];
+                gc[i] = cplx<R>{g.re * inv, -(g.im * inv)};
             }
         }
         __syncthreads();  // phs and the scaled columns are read by other waves below
@@ -981,15 +948,15 @@ template <typename R>
 size_t bsc_lds_bytes(int l, int n, bool in_lds) {
     size_t c = (size_t)BIC_NB * (BIC_NB + 1);
     if (in_lds) c += (size_t)n * (size_t)(l | 1);
-    return c * sizeof(cx<R>) + ((size_t)2 * BSI_A_ELEMS + (size_t)2 * bsc_o_elems(l) + (size_t)2 * n + 8) * sizeof(R) + (size_t)n * sizeof(int);
+    return c * sizeof(cplx<R>) + ((size_t)2 * BSI_A_ELEMS + (size_t)2 * bsc_o_elems(l) + (size_t)2 * n + 8) * sizeof(R) + (size_t)n * sizeof(int);
 }
 
 template <typename R>
 struct BscArgs {
-    CView<R> a, omega, y, c, z;  // y.p == nullptr: the sketch is not written
+    CV<R> a, omega, y, c, z;  // y.p == nullptr: the sketch is not written
     int64_t abs, obs, ybs, cbs, zbs;
     int64_t *col_ind, *ranks;
-    cx<R> *ws;
+    cplx<R> *ws;
     double tol;
     int count, kk;
     bool w_lds;  // the working copy in LDS (else in the workgroup's workspace slot)
@@ -1000,7 +967,7 @@ struct BscArgs {
 // AR / OR: the lanes of the staging loads run along the rows of a / of omega (the operand's smaller stride), else along its columns;
 // each thread's elements of a chunk are then a fixed step apart in memory and in the LDS planes, whose offsets are compile-time constants.
 template <typename R, int TL, bool AR, bool OR>
-__device__ __forceinline__ void bsc_sketch(const BscArgs<R> &g, const cx<R> *__restrict__ A, const cx<R> *__restrict__ Om, cx<R> *Yb, cx<R> *W, int ldw, R *As,
+__device__ __forceinline__ void bsc_sketch(const BscArgs<R> &g, const cplx<R> *__restrict__ A, const cplx<R> *__restrict__ Om, cplx<R> *Yb, cplx<R> *W, int ldw, R *As,
                                            R *Os, int oplane, int t0, int tid, int wv, int lane) {
     constexpr int PO = bsi_po(16 * TL);
     constexpr int A_PER = BSI_ROWS * BSI_COLS / BIC_THREADS;    // 8 elements of A per thread and chunk
@@ -1023,10 +990,10 @@ __device__ __forceinline__ void bsc_sketch(const BscArgs<R> &g, const cx<R> *__r
 #pragma unroll
         for (int i = 0; i < TL; ++i) { are[i] = typename Acc<R>::type{0, 0, 0, 0}; aim[i] = typename Acc<R>::type{0, 0, 0, 0}; }
         // the chunk at rows m0 .. m0 + 31 into this thread's staging registers
-        cx<R> av[A_PER], ov[O_PER];
+        cplx<R> av[A_PER], ov[O_PER];
         auto fetch = [&](int m0) {
-            const cx<R> *pa = A + (int64_t)(m0 + ar) * ars + (int64_t)(c0 + ac) * acs;
-            const cx<R> *po = Om + (int64_t)oi * ors + (int64_t)(m0 + orr) * ocs;
+            const cplx<R> *pa = A + (int64_t)(m0 + ar) * ars + (int64_t)(c0 + ac) * acs;
+            const cplx<R> *po = Om + (int64_t)oi * ors + (int64_t)(m0 + orr) * ocs;
             // the steps between a thread's elements are uniform; hidden from the optimizer here, every address is the thread's one base plus a
             // scalar offset (otherwise each of the 8 + 2 TL addresses becomes a loop-carried 64-bit register pair of its own)
             int64_t sa = AR ? AC_STEP * acs : AR_STEP * ars, so_i = ors, so_r = ocs;
@@ -1078,7 +1045,7 @@ __device__ __forceinline__ void bsc_sketch(const BscArgs<R> &g, const cx<R> *__r
             for (int reg = 0; reg < 4; ++reg) {
                 const int row = (t0 + i) * 16 + Acc<R>::row(lane, reg);
                 if (row < ltot && col < n) {
-                    const cx<R> v{are[i][reg], aim[i][reg]};
+                    const cplx<R> v{are[i][reg], aim[i][reg]};
                     W[(size_t)col * ldw + row] = v;
                     if (Yb) Yb[row * g.y.rs + col * g.y.cs] = v;
                 }
@@ -1093,9 +1060,9 @@ __global__ __launch_bounds__(BIC_THREADS, 2) void k_batched_sketch_id_c(BscArgs<
     const int m = (int)g.a.rows, n = (int)g.a.cols, l = (int)g.omega.rows, kk = g.kk;
     const int ldw = g.w_lds ? (l | 1) : l;
     const int oplane = bsc_o_elems(l);
-    cx<R> *lds = reinterpret_cast<cx<R> *>(smem_raw);
-    cx<R> *W = g.w_lds ? lds : g.ws + (size_t)blockIdx.x * (size_t)l * (size_t)n;
-    cx<R>(*tile)[BIC_NB + 1] = reinterpret_cast<cx<R>(*)[BIC_NB + 1]>(lds + (g.w_lds ? (size_t)n * ldw : 0));
+    cplx<R> *lds = reinterpret_cast<cplx<R> *>(smem_raw);
+    cplx<R> *W = g.w_lds ? lds : g.ws + (size_t)blockIdx.x * (size_t)l * (size_t)n;
+    cplx<R>(*tile)[BIC_NB + 1] = reinterpret_cast<cplx<R>(*)[BIC_NB + 1]>(lds + (g.w_lds ? (size_t)n * ldw : 0));
     R *As = reinterpret_cast<R *>(lds + (g.w_lds ? (size_t)n * ldw : 0) + BIC_NB * (BIC_NB + 1));
     R *Os = As + 2 * BSI_A_ELEMS;
     R *vn1 = Os + 2 * oplane;
@@ -1105,9 +1072,9 @@ __global__ __launch_bounds__(BIC_THREADS, 2) void k_batched_sketch_id_c(BscArgs<
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 
     for (int b = blockIdx.x; b < g.count; b += gridDim.x) {
-        const cx<R> *__restrict__ A = g.a.p + (int64_t)b * g.abs;
-        const cx<R> *__restrict__ Om = g.omega.p + (int64_t)b * g.obs;
-        cx<R> *Yb = g.y.p ? g.y.p + (int64_t)b * g.ybs : nullptr;
+        const cplx<R> *__restrict__ A = g.a.p + (int64_t)b * g.abs;
+        const cplx<R> *__restrict__ Om = g.omega.p + (int64_t)b * g.obs;
+        cplx<R> *Yb = g.y.p ? g.y.p + (int64_t)b * g.ybs : nullptr;
         // ---- the sketch into W (and y), at most BSC_TILES row tiles per pass over the panels, one instance per number of 16-row tiles of a pass ----
         for (int t0 = 0; 16 * t0 < l; t0 += BSC_TILES) {
             const int rest = ((l + 15) >> 4) - t0;
@@ -1124,10 +1091,10 @@ __global__ __launch_bounds__(BIC_THREADS, 2) void k_batched_sketch_id_c(BscArgs<
         for (int p = tid; p < n; p += BIC_THREADS) g.col_ind[(int64_t)b * n + p] = jp[p];
         if (tid == 0) g.ranks[b] = r;
         // C[:, j] = A[:, jp[j]] (zero for j >= r), the lanes along a's smaller stride
-        cx<R> *Cb = g.c.p + (int64_t)b * g.cbs;
+        cplx<R> *Cb = g.c.p + (int64_t)b * g.cbs;
         if (g.a.rs <= g.a.cs) {
             for (int j = wv; j < kk; j += BIC_WAVES) {
-                const cx<R> *src = A + (int64_t)jp[j] * g.a.cs;
+                const cplx<R> *src = A + (int64_t)jp[j] * g.a.cs;
                 for (int i = lane; i < m; i += 64) Cb[i * g.c.rs + j * g.c.cs] = j < r ? src[i * g.a.rs] : czero<R>();
             }
         } else {
@@ -1142,194 +1109,154 @@ __global__ __launch_bounds__(BIC_THREADS, 2) void k_batched_sketch_id_c(BscArgs<
     }
 }
 
+// ---- the plans: the real launchers' rules (kernels_batched_id.hip) on complex elements, as pure functions of the shapes ---------------------
+
+template <typename R>
+BatchedPlan<bool> bic_plan(int m, int n) {
+    return batched_lds_or_ws([&](bool w_lds) { return bic_lds_bytes<R>(m, n, w_lds); }, (size_t)m * (size_t)n * sizeof(cplx<R>), "column_id_rank_batched");
+}
+
+template <typename R>
+BatchedPlan<bool> btc_plan(int m, int n, int k) {
+    return batched_lds_or_ws([&](bool w_lds) { return btc_lds_bytes<R>(m, n, k, w_lds); }, (size_t)m * (size_t)n * sizeof(cplx<R>), "two_sided_id_rank_batched");
+}
+
+// SVD: bsv_plan's list with a third place for the core; the last keeps W, G and J in the workgroup's slot of the grid-bounded workspace (a
+// 128 x 128 c64 core alone takes 256 KiB, more than BID_MAX_LDS)
+struct BscPlace { bool w, v, g; int ld; };
+template <typename R>
+BatchedPlan<BscPlace> bsc_plan(int m, int n) {
+    const int M = std::max(m, n), N = std::min(m, n);
+    const int pad = ((N + 15) / 32) * 32 + 16, odd = N | 1;
+    const BscPlace places[] = {{true, true, true, pad},    {true, true, true, odd},    {false, true, true, pad}, {false, true, true, odd},
+                               {false, false, true, pad},  {false, false, true, odd},  {false, false, false, N}};
+    return batched_first_fit(places, [&](BscPlace p) { return bsc_lds_bytes<R>(M, N, p.ld, p.w, p.v, p.g); },
+        [&](BscPlace p) { return bsc_ws_elems(M, N, p.ld, p.w, p.v, p.g) * sizeof(cplx<R>); }, "svd_rank_batched");
+}
+
+// recompression: brc_plan's list (most in LDS first, the padded core pitch before the odd one, the larger copy to the workspace first)
+// with the fourth placement bsc_plan has: a complex core that does not fit in LDS at either pitch (c64, K >= 100) goes to the
+// workgroup's slot with everything else, at pitch K
+struct BrccPlace { bool l, r, v, g; int ld; };
+template <typename R>
+BatchedPlan<BrccPlace> brcc_plan(int m, int n, int K) {
+    const int pad = ((K + 15) / 32) * 32 + 16, odd = K | 1;
+    const bool big_l = m >= n;  // the copy that leaves LDS first
+    const BrccPlace places[] = {{true, true, true, true, pad},      {true, true, true, true, odd},     {!big_l, big_l, true, true, pad},
+                                {!big_l, big_l, true, true, odd},   {false, false, true, true, pad},   {false, false, true, true, odd},
+                                {false, false, false, true, pad},   {false, false, false, true, odd},  {false, false, false, false, K}};
+    return batched_first_fit(places, [&](BrccPlace p) { return brcc_lds_bytes<R>(m, n, K, p.ld, p.l, p.r, p.v, p.g); },
+        [&](BrccPlace p) { return brcc_ws_elems(m, n, K, p.ld, p.l, p.r, p.v, p.g) * sizeof(cplx<R>); }, "lowrank_recompress_batched");
+}
+
+// sketched column ID: W (l x n complex) in LDS when it fits next to the chunk images, else in the workgroup's slot
+template <typename R>
+BatchedPlan<bool> bscid_plan(int l, int n) {
+    return batched_lds_or_ws([&](bool w_lds) { return bsc_lds_bytes<R>(l, n, w_lds); }, (size_t)l * (size_t)n * sizeof(cplx<R>), "sketch_column_id_rank_batched");
+}
+
 }  // namespace
 
-// the real kernels' launch rule (bid_grid, BID_MAX_LDS): LDS variant when the complex working copy fits, else the workspace variant
 template <typename R>
 void batched_column_id_c(rc_context *c, const rc_matrix &a_, int64_t abs, int32_t count, int64_t k, double tol, const rc_matrix &cm_, int64_t cbs,
                          const rc_matrix &z_, int64_t zbs, int64_t *col_ind, int64_t *ranks) {
-    const CView<R> a = cview<R>(a_), cm = cview<R>(cm_), z = cview<R>(z_);
+    const CV<R> a = view_of<R>(a_), cm = view_of<R>(cm_), z = view_of<R>(z_);
     const int m = (int)a.rows, n = (int)a.cols;
     if (count <= 0) return;
-    const size_t lds_in = bic_lds_bytes<R>(m, n, true);
-    const bool in_lds = lds_in <= BID_MAX_LDS;
-    const size_t lds = in_lds ? lds_in : bic_lds_bytes<R>(m, n, false);
-    auto kern = in_lds ? k_batched_id_c<R, true> : k_batched_id_c<R, false>;
-    static bool attr_set[64] = {};
-    if (!attr_set[c->device & 63]) {
-        RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_batched_id_c<R, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BID_MAX_LDS));
-        RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_batched_id_c<R, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BID_MAX_LDS));
-        attr_set[c->device & 63] = true;
-    }
-    const size_t per = (size_t)m * (size_t)n * sizeof(cx<R>);
-    int64_t slots = 0;
-    const int64_t grid = bid_grid(c, reinterpret_cast<const void *>(kern), lds, in_lds ? 0 : per, count, &slots);
-    ProfScope ps(c, "op:batched_column_id<complex> %dx%d k=%lld count=%d grid=%lld slots=%lld plan=W:%s", m, n, (long long)k, (int)count, (long long)grid,
-                 (long long)slots, in_lds ? "lds" : "ws");
-    cx<R> *ws = in_lds ? nullptr : c->alloc<cx<R>>((size_t)grid * (size_t)m * (size_t)n);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BIC_THREADS), lds, c->stream, a, abs, (int)count, (int)k, tol, cm, cbs, z, zbs, col_ind, ranks, ws);
+    const auto plan = bic_plan<R>(m, n);
+    const auto lch = batched_prepare(c, plan.at ? k_batched_id_c<R, true> : k_batched_id_c<R, false>, "column_id_rank_batched", plan.lds, plan.ws, count);
+    ProfScope ps(c, "op:batched_column_id<complex> %dx%d k=%lld count=%d grid=%lld slots=%lld plan=W:%s", m, n, (long long)k, (int)count,
+                 (long long)lch.grid, (long long)lch.slots, plan.at ? "lds" : "ws");
+    lch.launch(a, abs, (int)count, (int)k, tol, cm, cbs, z, zbs, col_ind, ranks, lch.template workspace<cplx<R>>());
 }
 
 template <typename R>
 void batched_two_sided_id_c(rc_context *c, const rc_matrix &a_, int64_t abs, int32_t count, int64_t k, double tol, const rc_matrix &cm_, int64_t cbs,
                             const rc_matrix &x_, int64_t xbs, const rc_matrix &z_, int64_t zbs, int64_t *row_ind, int64_t *col_ind, int64_t *ranks) {
-    const CView<R> a = cview<R>(a_), cm = cview<R>(cm_), x = cview<R>(x_), z = cview<R>(z_);
+    const CV<R> a = view_of<R>(a_), cm = view_of<R>(cm_), x = view_of<R>(x_), z = view_of<R>(z_);
     const int m = (int)a.rows, n = (int)a.cols;
     if (count <= 0) return;
-    const size_t lds_in = btc_lds_bytes<R>(m, n, (int)k, true);
-    const bool in_lds = lds_in <= BID_MAX_LDS;
-    const size_t lds = in_lds ? lds_in : btc_lds_bytes<R>(m, n, (int)k, false);
-    auto kern = in_lds ? k_batched_two_sided_c<R, true> : k_batched_two_sided_c<R, false>;
-    static bool attr_set[64] = {};
-    if (!attr_set[c->device & 63]) {
-        RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_batched_two_sided_c<R, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BID_MAX_LDS));
-        RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_batched_two_sided_c<R, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BID_MAX_LDS));
-        attr_set[c->device & 63] = true;
-    }
-    const size_t per = (size_t)m * (size_t)n * sizeof(cx<R>);
-    int64_t slots = 0;
-    const int64_t grid = bid_grid(c, reinterpret_cast<const void *>(kern), lds, in_lds ? 0 : per, count, &slots);
+    const auto plan = btc_plan<R>(m, n, (int)k);
+    const auto lch = batched_prepare(c, plan.at ? k_batched_two_sided_c<R, true> : k_batched_two_sided_c<R, false>, "two_sided_id_rank_batched", plan.lds,
+                                     plan.ws, count);
     ProfScope ps(c, "op:batched_two_sided_id<complex> %dx%d k=%lld count=%d grid=%lld slots=%lld plan=W:%s", m, n, (long long)k, (int)count,
-                 (long long)grid, (long long)slots, in_lds ? "lds" : "ws");
-    cx<R> *ws = in_lds ? nullptr : c->alloc<cx<R>>((size_t)grid * (size_t)m * (size_t)n);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BIC_THREADS), lds, c->stream, a, abs, (int)count, (int)k, tol, cm, cbs, x, xbs, z, zbs, row_ind,
-                       col_ind, ranks, ws);
+                 (long long)lch.grid, (long long)lch.slots, plan.at ? "lds" : "ws");
+    lch.launch(a, abs, (int)count, (int)k, tol, cm, cbs, x, xbs, z, zbs, row_ind, col_ind, ranks, lch.template workspace<cplx<R>>());
 }
 
-// the real batched SVD's launch rule with a third place for the core: the first plan that fits, most in LDS first, the padded pitch
-// before the odd one; the last keeps W, G and J in the workgroup's slot of the grid-bounded workspace (a 128 x 128 c64 core alone
-// takes 256 KiB, more than BID_MAX_LDS)
 template <typename R>
 void batched_svd_c(rc_context *c, const rc_matrix &a_, int64_t abs, int32_t count, int64_t k, double tol, const rc_matrix &u_, int64_t ubs, R *s,
                    const rc_matrix &vt_, int64_t vbs, int64_t *ranks) {
-    const CView<R> a = cview<R>(a_), u = cview<R>(u_), vt = cview<R>(vt_);
+    const CV<R> a = view_of<R>(a_), u = view_of<R>(u_), vt = view_of<R>(vt_);
     const int m = (int)a.rows, n = (int)a.cols;
     if (count <= 0) return;
     const bool wide = m < n;
-    const int M = wide ? n : m, N = wide ? m : n;
-    const int pad = ((N + 15) / 32) * 32 + 16, odd = N | 1;
-    const struct { bool w, v, g; int ld; } plans[] = {{true, true, true, pad},    {true, true, true, odd},    {false, true, true, pad}, {false, true, true, odd},
-                                                      {false, false, true, pad},  {false, false, true, odd},  {false, false, false, N}};
-    int pi = 0;
-    while (pi < 6 && bsc_lds_bytes<R>(M, N, plans[pi].ld, plans[pi].w, plans[pi].v, plans[pi].g) > BID_MAX_LDS) ++pi;
-    const bool w_lds = plans[pi].w, v_lds = plans[pi].v, g_lds = plans[pi].g;
-    const int ldg = plans[pi].ld;
-    const size_t lds = bsc_lds_bytes<R>(M, N, ldg, w_lds, v_lds, g_lds);
-    auto kern = w_lds   ? k_batched_svd_c<R, true, true, true>
-                : v_lds ? k_batched_svd_c<R, false, true, true>
-                : g_lds ? k_batched_svd_c<R, false, false, true>
-                        : k_batched_svd_c<R, false, false, false>;
-    static bool attr_set[64] = {};
-    if (!attr_set[c->device & 63]) {
-        for (const void *f : {reinterpret_cast<const void *>(k_batched_svd_c<R, true, true, true>), reinterpret_cast<const void *>(k_batched_svd_c<R, false, true, true>),
-                              reinterpret_cast<const void *>(k_batched_svd_c<R, false, false, true>),
-                              reinterpret_cast<const void *>(k_batched_svd_c<R, false, false, false>)})
-            RC_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BID_MAX_LDS));
-        attr_set[c->device & 63] = true;
-    }
-    const size_t per = bsc_ws_elems(M, N, ldg, w_lds, v_lds, g_lds);
-    int64_t slots = 0;
-    const int64_t grid = bid_grid(c, reinterpret_cast<const void *>(kern), lds, per * sizeof(cx<R>), count, &slots);
+    const auto plan = bsc_plan<R>(m, n);
+    const BscPlace at = plan.at;
+    const auto lch = batched_prepare(c,
+                                     at.w   ? k_batched_svd_c<R, true, true, true>
+                                     : at.v ? k_batched_svd_c<R, false, true, true>
+                                     : at.g ? k_batched_svd_c<R, false, false, true>
+                                            : k_batched_svd_c<R, false, false, false>,
+                                     "svd_rank_batched", plan.lds, plan.ws, count);
     ProfScope ps(c, "op:batched_svd<complex> %dx%d k=%lld count=%d grid=%lld slots=%lld plan=W:%s,V:%s,G:%s,ld=%d", m, n, (long long)k, (int)count,
-                 (long long)grid, (long long)slots, w_lds ? "lds" : "ws", v_lds ? "lds" : "ws", g_lds ? "lds" : "ws", ldg);
-    cx<R> *ws = per ? c->alloc<cx<R>>((size_t)grid * per) : nullptr;
+                 (long long)lch.grid, (long long)lch.slots, at.w ? "lds" : "ws", at.v ? "lds" : "ws", at.g ? "lds" : "ws", at.ld);
     // the work orientation's U (M x k) and V^H (k x N): u and vt, or for a wide matrix the plain transposed views vt^T and u^T
-    auto tr = [](const CView<R> &v) { return CView<R>{v.p, v.cols, v.rows, v.cs, v.rs}; };
-    const CView<R> uo = wide ? tr(vt) : u, vo = wide ? tr(u) : vt;
+    const CV<R> uo = wide ? vt.t() : u, vo = wide ? u.t() : vt;
     const int64_t uobs = wide ? vbs : ubs, vobs = wide ? ubs : vbs;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BIC_THREADS), lds, c->stream, a, abs, (int)count, (int)k, tol, uo, uobs, vo, vobs, s, ranks, ws,
-                       c->health_word(), ldg);
+    lch.launch(a, abs, (int)count, (int)k, tol, uo, uobs, vo, vobs, s, ranks, lch.template workspace<cplx<R>>(), c->health_word(), at.ld);
 }
 
-// where the two working copies Wl (m x K), Wr (n x K), the rotations J and the core G (K x K) live: batched_lowrank_recompress's plan
-// list (most in LDS first, the padded core pitch before the odd one, the larger copy to the workspace first) with the fourth
-// placement batched_svd_c has: a complex core that does not fit in LDS at either pitch (c64, K >= 100) goes to the workgroup's slot
-// of the grid-bounded workspace with everything else, at pitch K.  One kernel: the plan only moves base pointers and pitches, and no
-// sum depends on a pitch, so it cannot change a block's bits.
+// One kernel: the plan only moves base pointers and pitches, and no sum depends on a pitch, so it cannot change a block's bits.
 template <typename R>
 void batched_lowrank_recompress_c(rc_context *c, const rc_matrix &left_, int64_t lbs, const rc_matrix &mid_, int64_t mbs, const R *s, int64_t s_stride,
                                   const rc_matrix &right_, int64_t rbs, const int64_t *in_ranks, int32_t count, int64_t k, double tol, const rc_matrix &u_,
                                   int64_t ubs, R *s_out, const rc_matrix &vt_, int64_t vbs, int64_t *ranks) {
-    const CView<R> left = cview<R>(left_), mid = cview<R>(mid_), right = cview<R>(right_), u = cview<R>(u_), vt = cview<R>(vt_);
+    const CV<R> left = view_of<R>(left_), mid = view_of<R>(mid_), right = view_of<R>(right_), u = view_of<R>(u_), vt = view_of<R>(vt_);
     const int m = (int)left.rows, n = (int)right.cols, K = (int)left.cols;
     if (count <= 0) return;
-    const int pad = ((K + 15) / 32) * 32 + 16, odd = K | 1;
-    const bool big_l = m >= n;  // the copy that leaves LDS first
-    const struct { bool l, r, v, g; int ld; } plans[] = {{true, true, true, true, pad},      {true, true, true, true, odd},     {!big_l, big_l, true, true, pad},
-                                                         {!big_l, big_l, true, true, odd},   {false, false, true, true, pad},   {false, false, true, true, odd},
-                                                         {false, false, false, true, pad},   {false, false, false, true, odd},  {false, false, false, false, K}};
-    int pi = 0;
-    while (pi < 8 && brcc_lds_bytes<R>(m, n, K, plans[pi].ld, plans[pi].l, plans[pi].r, plans[pi].v, plans[pi].g) > BID_MAX_LDS) ++pi;
-    const bool l_lds = plans[pi].l, r_lds = plans[pi].r, v_lds = plans[pi].v, g_lds = plans[pi].g;
-    const int ldg = plans[pi].ld;
-    const size_t lds = brcc_lds_bytes<R>(m, n, K, ldg, l_lds, r_lds, v_lds, g_lds);
-    RC_REQUIRE(lds <= BID_MAX_LDS, RC_RUNTIME_ERROR, "lowrank_recompress_batched: %zu bytes of LDS", lds);
-    const void *kern = reinterpret_cast<const void *>(k_batched_recompress_c<R>);
-    static bool attr_set[64] = {};
-    if (!attr_set[c->device & 63]) {
-        RC_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BID_MAX_LDS));
-        attr_set[c->device & 63] = true;
-    }
-    const size_t per = brcc_ws_elems(m, n, K, ldg, l_lds, r_lds, v_lds, g_lds);
-    int64_t slots = 0;
-    const int64_t grid = bid_grid(c, kern, lds, per * sizeof(cx<R>), count, &slots);
+    const auto plan = brcc_plan<R>(m, n, K);
+    const BrccPlace at = plan.at;
+    const auto lch = batched_prepare(c, k_batched_recompress_c<R>, "lowrank_recompress_batched", plan.lds, plan.ws, count);
     ProfScope ps(c, "op:batched_recompress<complex> %dx%d k=%d count=%d grid=%lld slots=%lld plan=L:%s,R:%s,V:%s,G:%s,ld=%d,kk=%d%s%s", m, n, K, (int)count,
-                 (long long)grid, (long long)slots, l_lds ? "lds" : "ws", r_lds ? "lds" : "ws", v_lds ? "lds" : "ws", g_lds ? "lds" : "ws", ldg,
+                 (long long)lch.grid, (long long)lch.slots, at.l ? "lds" : "ws", at.r ? "lds" : "ws", at.v ? "lds" : "ws", at.g ? "lds" : "ws", at.ld,
                  (int)std::min<int64_t>(k, K), mid.p ? ",mid" : "", s ? ",s" : "");
     BrcCArgs<R> a;
     a.left = left; a.mid = mid; a.right = right; a.u = u; a.vt = vt;
     a.lbs = lbs; a.mbs = mbs; a.rbs = rbs; a.ubs = ubs; a.vbs = vbs; a.s_stride = s_stride;
     a.s = s; a.in_ranks = in_ranks; a.s_out = s_out; a.ranks = ranks;
-    a.ws = per ? c->alloc<cx<R>>((size_t)grid * per) : nullptr;
+    a.ws = lch.template workspace<cplx<R>>();
     a.health = c->health_word();
-    a.tol = tol; a.count = (int)count; a.k = (int)std::min<int64_t>(k, K); a.ldg = ldg;
-    a.l_lds = l_lds; a.r_lds = r_lds; a.v_lds = v_lds; a.g_lds = g_lds;
-    hipLaunchKernelGGL(k_batched_recompress_c<R>, dim3((unsigned)grid), dim3(BIC_THREADS), lds, c->stream, a);
+    a.tol = tol; a.count = (int)count; a.k = (int)std::min<int64_t>(k, K); a.ldg = at.ld;
+    a.l_lds = at.l; a.r_lds = at.r; a.v_lds = at.v; a.g_lds = at.g;
+    lch.launch(a);
 }
 
-// the sketched column ID of a batch of complex blocks: W (l x n complex) in LDS when it fits next to the chunk images, else in the workgroup's
-// slot of the grid-bounded workspace: the plan only moves W's base pointer and pitch, so it cannot change a block's bits.  Four instances of the
-// kernel, by the index of a and of omega that the staging loads' lanes run along; each component of Y is summed in the same order in all four.
+// The plan only moves W's base pointer and pitch, so it cannot change a block's bits.  Four instances of the kernel, by the index of a and of
+// omega that the staging loads' lanes run along; each component of Y is summed in the same order in all four.  The label carries the launched
+// instance's scratch bytes per thread (a compiler that starts to spill shows up in every profile and in tools/batched_sketch_id_bench.py --complex).
 template <typename R>
 void batched_sketch_column_id_c(rc_context *c, const rc_matrix &a_, int64_t abs, const rc_matrix &omega_, int64_t obs, int32_t count, int64_t kk, double tol,
                                 const rc_matrix &y_, int64_t ybs, const rc_matrix &cm_, int64_t cbs, const rc_matrix &z_, int64_t zbs, int64_t *col_ind,
                                 int64_t *ranks) {
-    const CView<R> a = cview<R>(a_), omega = cview<R>(omega_), y = cview<R>(y_), cm = cview<R>(cm_), z = cview<R>(z_);
+    const CV<R> a = view_of<R>(a_), omega = view_of<R>(omega_), y = view_of<R>(y_), cm = view_of<R>(cm_), z = view_of<R>(z_);
     const int m = (int)a.rows, n = (int)a.cols, l = (int)omega.rows;
     if (count <= 0) return;
-    const bool w_lds = bsc_lds_bytes<R>(l, n, true) <= BID_MAX_LDS;
-    const size_t lds = bsc_lds_bytes<R>(l, n, w_lds);
+    const auto plan = bscid_plan<R>(l, n);
     // the lanes of the staging loads along the smaller stride of a and of omega (the real call's rule)
     const bool a_rows = a.rs <= a.cs, o_rows = omega.rs < omega.cs;
-    const void *kerns[4] = {reinterpret_cast<const void *>(k_batched_sketch_id_c<R, false, false>), reinterpret_cast<const void *>(k_batched_sketch_id_c<R, false, true>),
-                            reinterpret_cast<const void *>(k_batched_sketch_id_c<R, true, false>), reinterpret_cast<const void *>(k_batched_sketch_id_c<R, true, true>)};
-    const int which = (a_rows ? 2 : 0) + (o_rows ? 1 : 0);
-    // per device, once: the LDS cap, and each instance's scratch bytes per thread for the label (a compiler that starts to spill shows up in every
-    // profile and in tools/batched_sketch_id_bench.py --complex)
-    static bool attr_set[64] = {};
-    static int scratch_of[64][4] = {};
-    if (!attr_set[c->device & 63]) {
-        for (int i = 0; i < 4; ++i) {
-            RC_HIP(hipFuncSetAttribute(kerns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)BID_MAX_LDS));
-            hipFuncAttributes fa;
-            RC_HIP(hipFuncGetAttributes(&fa, kerns[i]));
-            scratch_of[c->device & 63][i] = (int)fa.localSizeBytes;
-        }
-        attr_set[c->device & 63] = true;
-    }
-    const size_t per = w_lds ? 0 : (size_t)l * (size_t)n * sizeof(cx<R>);
-    int64_t slots = 0;
-    const int64_t grid = bid_grid(c, kerns[which], lds, per, count, &slots);
+    void (*const kerns[4])(BscArgs<R>) = {k_batched_sketch_id_c<R, false, false>, k_batched_sketch_id_c<R, false, true>, k_batched_sketch_id_c<R, true, false>,
+                                          k_batched_sketch_id_c<R, true, true>};
+    const auto lch = batched_prepare(c, kerns[(a_rows ? 2 : 0) + (o_rows ? 1 : 0)], "sketch_column_id_rank_batched", plan.lds, plan.ws, count);
     ProfScope ps(c, "op:batched_sketch_id_c %dx%d k=%lld count=%d grid=%lld slots=%lld plan=W:%s,l=%d,rows=%d,cols=%d,scratch=%d", m, n, (long long)kk,
-                 (int)count, (long long)grid, (long long)slots, w_lds ? "lds" : "ws", l, BSI_ROWS, BSI_COLS, scratch_of[c->device & 63][which]);
+                 (int)count, (long long)lch.grid, (long long)lch.slots, plan.at ? "lds" : "ws", l, BSI_ROWS, BSI_COLS, lch.scratch);
     BscArgs<R> g;
     g.a = a; g.omega = omega; g.y = y; g.c = cm; g.z = z;
     g.abs = abs; g.obs = obs; g.ybs = ybs; g.cbs = cbs; g.zbs = zbs;
     g.col_ind = col_ind; g.ranks = ranks;
-    g.ws = per ? c->alloc<cx<R>>((size_t)grid * (size_t)l * (size_t)n) : nullptr;
-    g.tol = tol; g.count = (int)count; g.kk = (int)kk; g.w_lds = w_lds;
-    void *args[] = {&g};
-    RC_HIP(hipLaunchKernel(kerns[which], dim3((unsigned)grid), dim3(BIC_THREADS), args, lds, c->stream));
+    g.ws = lch.template workspace<cplx<R>>();
+    g.tol = tol; g.count = (int)count; g.kk = (int)kk; g.w_lds = plan.at;
+    lch.launch(g);
 }
 
 template void batched_sketch_column_id_c<double>(rc_context *, const rc_matrix &, int64_t, const rc_matrix &, int64_t, int32_t, int64_t, double, const rc_matrix &,

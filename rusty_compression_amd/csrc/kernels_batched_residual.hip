@@ -30,6 +30,7 @@
 // the bit-independence clause of the contract rests on.
 #include <algorithm>
 
+#include "rc_batched_launch.hpp"
 #include "rc_common.hpp"
 #include "rc_device.hpp"
 #include "rc_gemm.hpp"
@@ -38,7 +39,7 @@ namespace rc {
 
 namespace {
 
-constexpr int BR_THREADS = 256;
+constexpr int BR_THREADS = BATCHED_THREADS;
 constexpr int BR_ROWS = 32;  // rows of a and of left per chunk: two 16-row MFMA tiles
 constexpr int BR_COLS = 64;  // columns of a per tile: one 16-column strip per wave
 constexpr int BR_PER = BR_ROWS * BR_COLS / BR_THREADS;  // 8 elements of a tile per thread, staged and computed
@@ -220,40 +221,36 @@ __global__ __launch_bounds__(BR_THREADS) void k_batched_residual(BrArgs<T> g) {
     }
 }
 
+// the plan (at: W's images in LDS): in LDS when they fit next to the chunk images, else in the workgroup's slot of the grid-bounded
+// workspace; without mid and s W is right itself: no image, no workspace (plan=W:right)
+template <typename T>
+BatchedPlan<bool> br_plan(int K, int n, bool has_mid, bool has_s) {
+    if (!has_mid && !has_s) return {false, br_lds_bytes<T>(K, n, false, false), 0};
+    return batched_lds_or_ws([&](bool w_lds) { return br_lds_bytes<T>(K, n, has_mid, w_lds); }, br_w_elems(K, n, has_mid) * sizeof(T), "lowrank_residual_batched");
+}
+
 }  // namespace
 
-// W's images in LDS when they fit next to the chunk images, else in the workgroup's slot of the grid-bounded workspace: the plan only
-// moves base pointers, so it cannot change a block's bits; without mid and s there is no image (plan=W:right).  One kernel per scalar
-// type.  attr_set, as in the sibling launchers: a racing first call sets the same attribute twice, which is harmless.
+// The plan only moves base pointers, so it cannot change a block's bits.  One kernel per scalar type.
 template <typename T>
 void batched_lowrank_residual(rc_context *c, Mat<T> a, int64_t abs, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride, Mat<T> right,
                               int64_t rbs, const int64_t *ranks, int32_t count, Mat<T> e, int64_t ebs, T *err, T *nrm) {
     const int m = (int)a.rows, n = (int)a.cols, K = (int)left.cols;
     if (count <= 0) return;
     const bool has_mid = mid.p != nullptr;
-    const bool direct = !has_mid && !s;  // W is right itself: no image
-    const bool w_lds = !direct && br_lds_bytes<T>(K, n, has_mid, true) <= BID_MAX_LDS;
-    const size_t lds = br_lds_bytes<T>(K, n, has_mid, w_lds);
-    RC_REQUIRE(lds <= BID_MAX_LDS, RC_RUNTIME_ERROR, "lowrank_residual_batched: %zu bytes of LDS", lds);
-    const void *kern = reinterpret_cast<const void *>(k_batched_residual<T>);
-    static bool attr_set[64] = {};
-    if (!attr_set[c->device & 63]) {
-        RC_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BID_MAX_LDS));
-        attr_set[c->device & 63] = true;
-    }
-    const size_t per = w_lds || direct ? 0 : br_w_elems(K, n, has_mid) * sizeof(T);
-    int64_t slots = 0;
-    const int64_t grid = bid_grid(c, kern, lds, per, count, &slots);
-    ProfScope ps(c, "op:batched_residual %dx%d k=%d count=%d grid=%lld slots=%lld plan=W:%s,rows=%d,cols=%d%s%s%s%s", m, n, K, (int)count, (long long)grid,
-                 (long long)slots, direct ? "right" : w_lds ? "lds" : "ws", BR_ROWS, BR_COLS, has_mid ? ",mid" : "", s ? ",s" : "", e.p ? ",e" : "", nrm ? ",nrm" : "");
+    const bool direct = !has_mid && !s;
+    const auto plan = br_plan<T>(K, n, has_mid, s != nullptr);
+    const auto lch = batched_prepare(c, k_batched_residual<T>, "lowrank_residual_batched", plan.lds, plan.ws, count);
+    ProfScope ps(c, "op:batched_residual %dx%d k=%d count=%d grid=%lld slots=%lld plan=W:%s,rows=%d,cols=%d%s%s%s%s", m, n, K, (int)count, (long long)lch.grid,
+                 (long long)lch.slots, direct ? "right" : plan.at ? "lds" : "ws", BR_ROWS, BR_COLS, has_mid ? ",mid" : "", s ? ",s" : "", e.p ? ",e" : "",
+                 nrm ? ",nrm" : "");
     BrArgs<T> g;
     g.a = a; g.left = left; g.mid = mid; g.right = right; g.e = e;
     g.abs = abs; g.lbs = lbs; g.mbs = mbs; g.rbs = rbs; g.ebs = ebs; g.s_stride = s_stride;
     g.s = s; g.ranks = ranks; g.err = err; g.nrm = nrm;
-    g.ws = per ? c->alloc<T>((size_t)grid * per / sizeof(T)) : nullptr;
-    g.count = (int)count; g.w_lds = w_lds; g.direct = direct;
-    hipLaunchKernelGGL(k_batched_residual<T>, dim3((unsigned)grid), dim3(BR_THREADS), lds, c->stream, g);
-    RC_HIP(hipGetLastError());
+    g.ws = lch.template workspace<T>();
+    g.count = (int)count; g.w_lds = plan.at; g.direct = direct;
+    lch.launch(g);
 }
 
 template void batched_lowrank_residual<double>(rc_context *, Mat<double>, int64_t, Mat<double>, int64_t, Mat<double>, int64_t, const double *, int64_t, Mat<double>,

@@ -37,7 +37,9 @@
 // alone, which is what the bit-independence clause of the contract rests on.
 #include <algorithm>
 
+#include "rc_batched_launch.hpp"
 #include "rc_common.hpp"
+#include "rc_cplx.hpp"
 #include "rc_device.hpp"
 #include "rc_gemm.hpp"
 
@@ -45,19 +47,16 @@ namespace rc {
 
 namespace {
 
-constexpr int BRC_THREADS = 256;
+constexpr int BRC_THREADS = BATCHED_THREADS;
 constexpr int BRC_ROWS = 32;  // rows of a and of left per chunk: two 16-row MFMA tiles
 constexpr int BRC_COLS = 64;  // columns of a per tile: one 16-column strip per wave
 constexpr int BRC_PER = BRC_ROWS * BRC_COLS / BRC_THREADS;  // 8 complex elements of a tile per thread, staged and computed
 constexpr int BRC_PAR = BRC_ROWS + 2;  // pitch of a's image with the row index fastest (2 modulo 16: no conflict for 16-byte elements)
 
-// an element in the caller's memory (aligned as R) and in the images (aligned as one 8- or 16-byte load)
+// an element of the LDS and workspace images: a cplx<R> over-aligned to one 8- or 16-byte load (the caller's memory holds cplx<R>,
+// aligned as R)
 template <typename R>
-struct gcx {
-    R re, im;
-};
-template <typename R>
-struct alignas(2 * sizeof(R)) cx {
+struct alignas(2 * sizeof(R)) img_cx {
     R re, im;
 };
 
@@ -83,13 +82,13 @@ __host__ __device__ constexpr size_t brc_w_elems(int k, int n, bool has_mid) { r
 // dynamic LDS: red[8] (f64) | [W0 [W1, with mid]: K4 x pw(n), LDS plan only] a's tile image | left's chunk image (complex elements)
 template <typename R>
 size_t brc_lds_bytes(int k, int n, bool has_mid, bool w_lds) {
-    return 64 + ((w_lds ? brc_w_elems(k, n, has_mid) : 0) + (size_t)brc_a_elems<R>() + (size_t)brc_l_elems<R>(k)) * sizeof(cx<R>);
+    return 64 + ((w_lds ? brc_w_elems(k, n, has_mid) : 0) + (size_t)brc_a_elems<R>() + (size_t)brc_l_elems<R>(k)) * sizeof(img_cx<R>);
 }
 
-// strided view of block 0 of one operand (in complex elements)
+// strided view of block 0 of one operand (in complex elements); the shapes travel once, in BrcArgs, not per operand as in CV<R>
 template <typename R>
 struct BrcView {
-    gcx<R> *p;
+    cplx<R> *p;
     int64_t rs, cs;
 };
 
@@ -100,7 +99,7 @@ struct BrcArgs {
     const R *s;
     const int64_t *ranks;
     R *err, *nrm;
-    cx<R> *ws;
+    img_cx<R> *ws;
     int m, n, k, count;
     bool w_lds;   // W's images in LDS (else in the workgroup's workspace slot)
     bool direct;  // neither mid nor s: W is right itself, read in place
@@ -108,8 +107,8 @@ struct BrcArgs {
 
 template <typename R>
 __global__ __launch_bounds__(BRC_THREADS) void k_batched_residual_c(BrcArgs<R> g) {
-    using C = cx<R>;
-    using G = gcx<R>;
+    using C = img_cx<R>;
+    using G = cplx<R>;
     typedef typename Acc<R>::type acc_t;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int m = g.m, n = g.n, K = g.k;
@@ -294,13 +293,19 @@ __global__ __launch_bounds__(BRC_THREADS) void k_batched_residual_c(BrcArgs<R> g
 }
 
 template <typename R>
-BrcView<R> brc_view(const rc_matrix &v) { return BrcView<R>{static_cast<gcx<R> *>(v.data), v.row_stride, v.col_stride}; }
+BrcView<R> brc_view(const rc_matrix &v) { return BrcView<R>{static_cast<cplx<R> *>(v.data), v.row_stride, v.col_stride}; }
+
+// the plan (at: W's images in LDS): the real kernel's rule (br_plan) on the over-aligned image elements
+template <typename R>
+BatchedPlan<bool> brc_plan(int K, int n, bool has_mid, bool has_s) {
+    if (!has_mid && !has_s) return {false, brc_lds_bytes<R>(K, n, false, false), 0};
+    return batched_lds_or_ws([&](bool w_lds) { return brc_lds_bytes<R>(K, n, has_mid, w_lds); }, brc_w_elems(K, n, has_mid) * sizeof(img_cx<R>),
+                             "lowrank_residual_batched");
+}
 
 }  // namespace
 
-// W's images in LDS when they fit next to the chunk images, else in the workgroup's slot of the grid-bounded workspace: the plan only
-// moves base pointers, so it cannot change a block's bits; without mid and s there is no image (plan=W:right).  One kernel per scalar
-// type.  attr_set, as in the sibling launchers: a racing first call sets the same attribute twice, which is harmless.
+// The plan only moves base pointers, so it cannot change a block's bits.  One kernel per scalar type.
 template <typename R>
 void batched_lowrank_residual_c(rc_context *c, const rc_matrix &a, int64_t abs, const rc_matrix &left, int64_t lbs, const rc_matrix &mid, int64_t mbs, const R *s,
                                 int64_t s_stride, const rc_matrix &right, int64_t rbs, const int64_t *ranks, int32_t count, const rc_matrix &e, int64_t ebs,
@@ -308,30 +313,19 @@ void batched_lowrank_residual_c(rc_context *c, const rc_matrix &a, int64_t abs, 
     const int m = (int)a.rows, n = (int)a.cols, K = (int)left.cols;
     if (count <= 0) return;
     const bool has_mid = mid.data != nullptr;
-    const bool direct = !has_mid && !s;  // W is right itself: no image
-    const bool w_lds = !direct && brc_lds_bytes<R>(K, n, has_mid, true) <= BID_MAX_LDS;
-    const size_t lds = brc_lds_bytes<R>(K, n, has_mid, w_lds);
-    RC_REQUIRE(lds <= BID_MAX_LDS, RC_RUNTIME_ERROR, "lowrank_residual_batched: %zu bytes of LDS", lds);
-    const void *kern = reinterpret_cast<const void *>(k_batched_residual_c<R>);
-    static bool attr_set[64] = {};
-    if (!attr_set[c->device & 63]) {
-        RC_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BID_MAX_LDS));
-        attr_set[c->device & 63] = true;
-    }
-    const size_t per = w_lds || direct ? 0 : brc_w_elems(K, n, has_mid) * sizeof(cx<R>);
-    int64_t slots = 0;
-    const int64_t grid = bid_grid(c, kern, lds, per, count, &slots);
+    const bool direct = !has_mid && !s;
+    const auto plan = brc_plan<R>(K, n, has_mid, s != nullptr);
+    const auto lch = batched_prepare(c, k_batched_residual_c<R>, "lowrank_residual_batched", plan.lds, plan.ws, count);
     ProfScope ps(c, "op:batched_residual<complex> %dx%d k=%d count=%d grid=%lld slots=%lld plan=W:%s,rows=%d,cols=%d%s%s%s%s", m, n, K, (int)count,
-                 (long long)grid, (long long)slots, direct ? "right" : w_lds ? "lds" : "ws", BRC_ROWS, BRC_COLS, has_mid ? ",mid" : "", s ? ",s" : "",
+                 (long long)lch.grid, (long long)lch.slots, direct ? "right" : plan.at ? "lds" : "ws", BRC_ROWS, BRC_COLS, has_mid ? ",mid" : "", s ? ",s" : "",
                  e.data ? ",e" : "", nrm ? ",nrm" : "");
     BrcArgs<R> g;
     g.a = brc_view<R>(a); g.left = brc_view<R>(left); g.mid = brc_view<R>(mid); g.right = brc_view<R>(right); g.e = brc_view<R>(e);
     g.abs = abs; g.lbs = lbs; g.mbs = mbs; g.rbs = rbs; g.ebs = ebs; g.s_stride = s_stride;
     g.s = s; g.ranks = ranks; g.err = err; g.nrm = nrm;
-    g.ws = per ? c->alloc<cx<R>>((size_t)grid * per / sizeof(cx<R>)) : nullptr;
-    g.m = m; g.n = n; g.k = K; g.count = (int)count; g.w_lds = w_lds; g.direct = direct;
-    hipLaunchKernelGGL(k_batched_residual_c<R>, dim3((unsigned)grid), dim3(BRC_THREADS), lds, c->stream, g);
-    RC_HIP(hipGetLastError());
+    g.ws = lch.template workspace<img_cx<R>>();
+    g.m = m; g.n = n; g.k = K; g.count = (int)count; g.w_lds = plan.at; g.direct = direct;
+    lch.launch(g);
 }
 
 template void batched_lowrank_residual_c<double>(rc_context *, const rc_matrix &, int64_t, const rc_matrix &, int64_t, const rc_matrix &, int64_t, const double *,

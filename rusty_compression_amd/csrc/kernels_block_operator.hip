@@ -54,7 +54,7 @@ __device__ __forceinline__ R bop_add(R a, R b) {
     return a + b;
 }
 template <typename R>
-__device__ __forceinline__ cpx<R> bop_add(cpx<R> a, cpx<R> b) {
+__device__ __forceinline__ cplx<R> bop_add(cplx<R> a, cplx<R> b) {
 #pragma clang fp contract(off)
     return {a.re + b.re, a.im + b.im};
 }
@@ -144,41 +144,38 @@ __global__ __launch_bounds__(BA_THREADS) void k_block_operator(BopArgs<E> a) {
     }
 }
 
-template <typename E, int NBT, bool CJ>
-void bop_launch_nbt(rc_context *c, const BopArgs<E> &a, const char *tag, bool conj) {
-    const void *kern = reinterpret_cast<const void *>(k_block_operator<E, NBT, CJ>);
-    static bool attr_set[64] = {};
-    if (!attr_set[c->device & 63]) {
-        RC_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BID_MAX_LDS));
-        attr_set[c->device & 63] = true;
-    }
-    const size_t lds = bop_lds_bytes<E>(a.m, a.n, a.k, NBT, a.mid.p != nullptr);
-    RC_REQUIRE(lds <= BID_MAX_LDS, RC_RUNTIME_ERROR, "block_operator_apply: %zu bytes of LDS", lds);
-    const int64_t ntiles = (a.ncols + NBT - 1) / NBT, nunits = (int64_t)a.groups * ntiles;
-    int64_t slots = 0;
-    const int64_t grid = bid_grid(c, kern, lds, 0, (int32_t)std::min<int64_t>(nunits, INT32_MAX), &slots);
-    // entries: the number of entries is group_ptr[groups], which only the device knows
-    ProfScope ps(c, "op:batched_operator_apply%s %dx%d k=%d count=%d grid=%lld slots=%lld plan=nb:%d,tiles:%lld,cols:%d,entries:dev,lr:%d,dense:%d%s%s%s%s", tag,
-                 a.m, a.n, a.k, a.groups, (long long)grid, (long long)slots, NBT, (long long)ntiles, a.ncols, a.count, a.dense_count, a.mid.p ? ",mid" : "",
-                 a.s ? ",s" : "", a.accumulate ? ",acc" : "", conj ? ",conj" : "");
-    hipLaunchKernelGGL((k_block_operator<E, NBT, CJ>), dim3((unsigned)grid), dim3(BA_THREADS), lds, c->stream, a);
+// the plan (at: the tile width): the apply's rule (the smallest of 1, 4, 8, 16 that covers the columns, at most the scalar type's NB),
+// stepped down while the accumulator does not fit beside the apply's buffers (m = n = 512, k = 128 with mid: 16 columns of f64 need
+// 164 352 B of the 162 816); no workspace.  The bits of an output element do not depend on it.
+template <typename E>
+BatchedPlan<int> bop_plan(int m, int n, int k, int ncols, bool has_mid) {
+    constexpr int NB = ba_nb<E>();
+    int nbt = ncols <= 1 ? 1 : ncols <= 4 ? 4 : ncols <= 8 ? 8 : 16;
+    if (nbt > NB) nbt = NB;
+    while (nbt > 1 && bop_lds_bytes<E>(m, n, k, nbt, has_mid) > BID_MAX_LDS) nbt = nbt == 4 ? 1 : nbt / 2;
+    return {nbt, bop_lds_bytes<E>(m, n, k, nbt, has_mid), 0};
 }
 
-// the tile width: the apply's rule (the smallest of 1, 4, 8, 16 that covers the columns, at most the scalar type's NB), stepped down
-// while the accumulator does not fit beside the apply's buffers (m = n = 512, k = 128 with mid: 16 columns of f64 need 164 352 B of the
-// 162 816).  The bits of an output element do not depend on it.
+template <typename E, int NBT, bool CJ>
+void bop_launch_nbt(rc_context *c, const BopArgs<E> &a, const char *tag, bool conj, size_t lds) {
+    const int64_t ntiles = (a.ncols + NBT - 1) / NBT;
+    const auto lch = batched_prepare(c, k_block_operator<E, NBT, CJ>, "block_operator_apply", lds, 0, (int64_t)a.groups * ntiles);
+    // entries: the number of entries is group_ptr[groups], which only the device knows
+    ProfScope ps(c, "op:batched_operator_apply%s %dx%d k=%d count=%d grid=%lld slots=%lld plan=nb:%d,tiles:%lld,cols:%d,entries:dev,lr:%d,dense:%d%s%s%s%s", tag,
+                 a.m, a.n, a.k, a.groups, (long long)lch.grid, (long long)lch.slots, NBT, (long long)ntiles, a.ncols, a.count, a.dense_count,
+                 a.mid.p ? ",mid" : "", a.s ? ",s" : "", a.accumulate ? ",acc" : "", conj ? ",conj" : "");
+    lch.launch(a);
+}
+
 template <typename E, bool CJ>
 void bop_launch(rc_context *c, const BopArgs<E> &a, const char *tag, bool conj) {
-    constexpr int NB = ba_nb<E>();
-    int nbt = a.ncols <= 1 ? 1 : a.ncols <= 4 ? 4 : a.ncols <= 8 ? 8 : 16;
-    if (nbt > NB) nbt = NB;
-    while (nbt > 1 && bop_lds_bytes<E>(a.m, a.n, a.k, nbt, a.mid.p != nullptr) > BID_MAX_LDS) nbt = nbt == 4 ? 1 : nbt / 2;
-    if (nbt == 1) return bop_launch_nbt<E, 1, CJ>(c, a, tag, conj);
-    if (nbt == 4) return bop_launch_nbt<E, 4, CJ>(c, a, tag, conj);
-    if constexpr (NB >= 16) {
-        if (nbt == 16) return bop_launch_nbt<E, 16, CJ>(c, a, tag, conj);
+    const auto plan = bop_plan<E>(a.m, a.n, a.k, a.ncols, a.mid.p != nullptr);
+    if (plan.at == 1) return bop_launch_nbt<E, 1, CJ>(c, a, tag, conj, plan.lds);
+    if (plan.at == 4) return bop_launch_nbt<E, 4, CJ>(c, a, tag, conj, plan.lds);
+    if constexpr (ba_nb<E>() >= 16) {
+        if (plan.at == 16) return bop_launch_nbt<E, 16, CJ>(c, a, tag, conj, plan.lds);
     }
-    bop_launch_nbt<E, 8, CJ>(c, a, tag, conj);
+    bop_launch_nbt<E, 8, CJ>(c, a, tag, conj, plan.lds);
 }
 
 template <typename E, typename P>
@@ -216,7 +213,7 @@ template <typename R>
 void block_operator_apply_c(rc_context *c, const rc_matrix &left, int64_t lbs, const rc_matrix &mid, int64_t mbs, const R *s, int64_t s_stride,
                             const rc_matrix &right, int64_t rbs, const int64_t *ranks, int32_t count, const rc_matrix &dense, int64_t dbs, int32_t dense_count,
                             const BlockPattern &pat, BlockShape shape, const rc_matrix &x, const rc_matrix &y, bool accumulate, bool conj) {
-    using E = cpx<R>;
+    using E = cplx<R>;
     BopArgs<E> a;
     a.left = bop_view<const E>(left.data, left.row_stride, left.col_stride, lbs);
     a.mid = bop_view<const E>(count > 0 ? mid.data : nullptr, mid.row_stride, mid.col_stride, mbs);

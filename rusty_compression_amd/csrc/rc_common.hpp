@@ -306,11 +306,7 @@ template <typename R> void batched_lowrank_residual_c(rc_context *c, const rc_ma
                                                       int32_t count, const rc_matrix &e, int64_t ebs, R *err, R *nrm);
 // the argument checks of rc_lowrank_residual_batched_* (rc_api.hip), shared by every scalar type like those above; the caller returns when count == 0
 template <typename T> void check_lowrank_residual_batched(Mat<T> a, Mat<T> left, Mat<T> mid, Mat<T> right, int32_t count, Mat<T> e, int64_t ebs, const T *err);
-// the batched kernels' dynamic-LDS cap and persistent grid (kernels_batched_id.hip): the resident workgroups of 256 threads on every
-// CU, fewer when the workspace (ws_per bytes per workgroup, 0 in the LDS variants) would pass 256 MiB unless that leaves less than
-// one workgroup per CU; never more than count.  *slots receives the grid before that last bound (slots= in the profile label)
-constexpr size_t BID_MAX_LDS = 160 * 1024 - 1024;
-int64_t bid_grid(rc_context *c, const void *kern, size_t lds, size_t ws_per, int32_t count, int64_t *slots);
+// (the batched kernels' dynamic-LDS cap, persistent grid and launch path: rc_batched_launch.hpp)
 void invert_perm(rc_context *c, const int64_t *perm, int64_t n, int64_t *inv);
 void fill_words(rc_context *c, void *p, size_t bytes, unsigned v);  // every 32-bit word of [p, p + bytes) = v, by a kernel on c->stream (no hipMemset*)
 void iota_i64(rc_context *c, int64_t *p, int64_t n);

@@ -19,6 +19,7 @@
 // These are correct, deterministic and column-parallel, but not tuned like the real-scalar kernels: complex is the
 // breadth row of SURVEY.md 8(f), the measured hot path (BASELINE.json) is real.
 #include "rc_common.hpp"
+#include "rc_cplx.hpp"
 #include "rc_device.hpp"
 
 #include <algorithm>
@@ -28,45 +29,13 @@ using namespace rc;
 
 namespace {
 
-template <typename R>
-struct cplx {
-    R re, im;
-};
-template <typename R> __host__ __device__ inline cplx<R> mk(R a, R b) { return cplx<R>{a, b}; }
-template <typename R> __host__ __device__ inline cplx<R> operator+(cplx<R> a, cplx<R> b) { return {a.re + b.re, a.im + b.im}; }
-template <typename R> __host__ __device__ inline cplx<R> operator-(cplx<R> a, cplx<R> b) { return {a.re - b.re, a.im - b.im}; }
-template <typename R> __host__ __device__ inline cplx<R> operator*(cplx<R> a, cplx<R> b) { return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
-template <typename R> __host__ __device__ inline cplx<R> operator*(R s, cplx<R> a) { return {s * a.re, s * a.im}; }
-template <typename R> __host__ __device__ inline cplx<R> cj(cplx<R> a) { return {a.re, -a.im}; }
-template <typename R> __host__ __device__ inline R abs2(cplx<R> a) { return a.re * a.re + a.im * a.im; }
-template <typename R> __device__ inline R cabs(cplx<R> a) { return hypot(a.re, a.im); }
-template <typename R> __device__ inline cplx<R> cdiv(cplx<R> a, cplx<R> b) {  // Smith's algorithm (?ladiv)
-    if (fabs(b.re) >= fabs(b.im)) {
-        const R r = b.im / b.re, d = b.re + b.im * r;
-        return {(a.re + a.im * r) / d, (a.im - a.re * r) / d};
-    }
-    const R r = b.re / b.im, d = b.im + b.re * r;
-    return {(a.re * r + a.im) / d, (a.im * r - a.re) / d};
-}
-
 static inline int64_t cdivi(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 template <typename R> struct NumC;
 template <> struct NumC<double> { static __host__ __device__ double tol3z() { return 1.0536712127723509e-08; } static __host__ __device__ double eps() { return 1.1102230246251565e-16; } };
 template <> struct NumC<float> { static __host__ __device__ float tol3z() { return 2.44140625e-04f; } static __host__ __device__ float eps() { return 5.9604645e-08f; } };
 
-// strided complex view (mirror of rc_matrix) and the column-major working matrix
-template <typename R>
-struct CV {
-    cplx<R> *p;
-    int64_t rows, cols, rs, cs;
-    __host__ __device__ cplx<R> &at(int64_t i, int64_t j) const { return p[i * rs + j * cs]; }
-    CV sub(int64_t r0, int64_t nr, int64_t c0, int64_t nc) const { return CV{p + r0 * rs + c0 * cs, nr, nc, rs, cs}; }
-    CV t() const { return CV{p, cols, rows, cs, rs}; }
-    bool empty() const { return rows == 0 || cols == 0; }
-};
-template <typename R>
-CV<R> view_of(const rc_matrix &m) { return CV<R>{static_cast<cplx<R> *>(m.data), m.rows, m.cols, m.row_stride, m.col_stride}; }
+// the column-major working matrix (cplx<R>, CV<R> and view_of: rc_cplx.hpp)
 // the shape, strides and null-ness of a complex operand as the real-typed view the shared argument checks take (never dereferenced)
 template <typename R>
 Mat<R> shape_of(const rc_matrix &m) { return Mat<R>(static_cast<R *>(m.data), m.rows, m.cols, m.row_stride, m.col_stride); }

@@ -225,6 +225,23 @@ def test_odd_core_pitch():
             assert check_vectors(u[i], vt[i], ref.u, ref.vt, ref.s, K, np.float64) >= 3
 
 
+@pytest.mark.parametrize("m,n,plan", [(512, 64, "L:ws,R:lds"), (64, 512, "L:lds,R:ws")])
+def test_the_larger_copy_leaves_lds_first(m, n, plan):
+    """f64, K = 64: the copy of the 512-row factor (64 x 513 x 8 B = 257 KiB) cannot share LDS with the core and the rotations (2 x 64 x
+    80 x 8 B = 80 KiB of the 159 KiB cap), the copy of the 64-row factor (64 x 65 x 8 B = 33 KiB) can: the plan moves the larger copy
+    alone to the workspace, whichever side it is on."""
+    rng = np.random.default_rng(24 + m)
+    K = 64
+    blocks = [factors(rng, kind, m, n, K, "both", np.float64) for kind in KINDS]
+    left, right, mid, s = stack(blocks)
+    (u, s_out, vt, ranks), lab = batched_launch(lambda: recompress(left, right, K, 0.0, mid, s))
+    assert lab["plan"] == plan + f",V:lds,G:lds,ld=80,kk={K},mid,s", lab["plan"]
+    for i in range(3):
+        a, sigma = dense(*blocks[i], K)
+        assert ranks[i] == K
+        check_block(a, sigma, u[i], s_out[i], vt[i], K, K, K, np.float64)
+
+
 # ---------------------------------------------------------------- 3. rank-aware
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_inner_ranks_are_honoured_and_tails_are_never_read(dtype):
