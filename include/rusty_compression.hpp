@@ -636,6 +636,56 @@ DeviceMatrix<T> lowrank_apply_batched(const DeviceMatrix<T> &left, const DeviceM
                                                    rc_matrix{y.view().data, m, ncols, ncols, 1}, m * ncols));
     return y;
 }
+// Mixed-precision storage of such a batch: the factors in f32 (c32) under f64 (c64) arithmetic (rc_lowrank_apply_mixed_batched_*,
+// rc_demote_batched_*, rc_promote_batched_*).  T is the compute type, double or c64; Mixed<T>::storage the type the factors are kept in.
+template <typename T> struct Mixed;
+template <> struct Mixed<double> {
+    using storage = float;
+    static constexpr auto lowrank_apply_batched = rc_lowrank_apply_mixed_batched_f64;
+    static constexpr auto demote_batched = rc_demote_batched_f64;
+    static constexpr auto promote_batched = rc_promote_batched_f32;
+};
+template <> struct Mixed<c64> {
+    using storage = c32;
+    static constexpr auto lowrank_apply_batched = rc_lowrank_apply_mixed_batched_c64;
+    static constexpr auto demote_batched = rc_demote_batched_c64;
+    static constexpr auto promote_batched = rc_promote_batched_c32;
+};
+// the storage copy of a stack of count blocks (x is count * rows x cols), rounded to nearest even; overflow, when given, receives per
+// block the number of finite elements that became infinite (count values)
+template <typename T>
+DeviceMatrix<typename Mixed<T>::storage> demote_batched(const DeviceMatrix<T> &x, int32_t count, DeviceIndex *overflow = nullptr) {
+    const int64_t rows = count > 0 ? x.nrows() / count : 0, cols = x.ncols();
+    DeviceMatrix<typename Mixed<T>::storage> out(x.ctx(), x.nrows(), cols);
+    x.ctx().check(Mixed<T>::demote_batched(x.ctx().raw(), rc_matrix{x.view().data, rows, cols, cols, 1}, rows * cols, count,
+                                           rc_matrix{out.view().data, rows, cols, cols, 1}, rows * cols, overflow ? overflow->data() : nullptr));
+    return out;
+}
+// the exact way back
+template <typename T>
+DeviceMatrix<T> promote_batched(const DeviceMatrix<typename Mixed<T>::storage> &x, int32_t count) {
+    const int64_t rows = count > 0 ? x.nrows() / count : 0, cols = x.ncols();
+    DeviceMatrix<T> out(x.ctx(), x.nrows(), cols);
+    x.ctx().check(Mixed<T>::promote_batched(x.ctx().raw(), rc_matrix{x.view().data, rows, cols, cols, 1}, rows * cols, count,
+                                            rc_matrix{out.view().data, rows, cols, cols, 1}, rows * cols));
+    return out;
+}
+// lowrank_apply_batched on factors in storage precision: the bits of lowrank_apply_batched<T> on promoted copies, half the factor bytes
+template <typename T>
+DeviceMatrix<T> lowrank_apply_batched_mixed(const DeviceMatrix<typename Mixed<T>::storage> &left, const DeviceMatrix<typename Mixed<T>::storage> *mid,
+                                            const DeviceBuffer<double> *s, const DeviceMatrix<typename Mixed<T>::storage> &right,
+                                            const DeviceIndex *ranks, int32_t count, const DeviceMatrix<T> *b) {
+    const int64_t m = count > 0 ? left.nrows() / count : 0, k = left.ncols(), n = right.ncols();
+    const int64_t ncols = b ? b->ncols() : n, p = s && count > 0 ? (int64_t)(s->size() / (std::size_t)count) : 0;
+    DeviceMatrix<T> y(left.ctx(), (int64_t)count * m, ncols);
+    const rc_matrix none{nullptr, 0, 0, 0, 0};
+    left.ctx().check(Mixed<T>::lowrank_apply_batched(left.ctx().raw(), rc_matrix{left.view().data, m, k, k, 1}, m * k,
+                                                     mid ? rc_matrix{mid->view().data, k, k, k, 1} : none, k * k, s ? s->data() : nullptr, p,
+                                                     rc_matrix{right.view().data, k, n, n, 1}, k * n, ranks ? ranks->data() : nullptr, count,
+                                                     b ? rc_matrix{b->view().data, n, ncols, ncols, 1} : none, n * ncols,
+                                                     rc_matrix{y.view().data, m, ncols, ncols, 1}, m * ncols));
+    return y;
+}
 // Apply::dot and to_mat of the three batched decompositions, each block at its own rank
 template <typename T>
 DeviceMatrix<T> apply_batched(const BatchedColumnID<T> &id, const DeviceMatrix<T> &b) {
@@ -798,18 +848,22 @@ BatchedResidual<T> residual_batched(const BatchedSVD<T> &svd, const DeviceMatrix
 // the swapped, transposed views with the conj flag) are built on the host and owned.  Distinct values of rows must tile [0, nrows) in
 // steps of m and distinct values of cols [0, ncols) in steps of n, so that every product writes every row of its result; within a group
 // the entries are summed in the order given.  mid and s together are rejected: (L M diag(s) R)^T is not the kernel's chain.
-template <typename T> struct BlockOperatorApi;
+// BlockOperator<T, S> with S = Mixed<T>::storage (MixedBlockOperator<T>) keeps left, mid and right in storage precision
+// (rc_block_operator_apply_mixed_*): dense, s, x and y stay in T, and the products have the bits of BlockOperator<T> on promoted factors.
+template <typename T, typename S = T> struct BlockOperatorApi;
+template <> struct BlockOperatorApi<double, float> { static constexpr auto apply = rc_block_operator_apply_mixed_f64; static constexpr bool conj = false; };
+template <> struct BlockOperatorApi<c64, c32> { static constexpr auto apply = rc_block_operator_apply_mixed_c64; static constexpr bool conj = true; };
 template <> struct BlockOperatorApi<double> { static constexpr auto apply = rc_block_operator_apply_f64; static constexpr bool conj = false; };
 template <> struct BlockOperatorApi<float> { static constexpr auto apply = rc_block_operator_apply_f32; static constexpr bool conj = false; };
 template <> struct BlockOperatorApi<c64> { static constexpr auto apply = rc_block_operator_apply_c64; static constexpr bool conj = true; };
 template <> struct BlockOperatorApi<c32> { static constexpr auto apply = rc_block_operator_apply_c32; static constexpr bool conj = true; };
-template <typename T>
+template <typename T, typename S = T>
 class BlockOperator {
   public:
     using Real = typename Scalar<T>::real;
     BlockOperator(const Context &ctx, int64_t nrows, int64_t ncols, const std::vector<int64_t> &rows, const std::vector<int64_t> &cols,
-                  const std::vector<int64_t> &block_ids, int32_t count, const DeviceMatrix<T> *left, const DeviceMatrix<T> *mid,
-                  const DeviceBuffer<Real> *s, const DeviceMatrix<T> *right, const DeviceIndex *ranks, int32_t dense_count = 0,
+                  const std::vector<int64_t> &block_ids, int32_t count, const DeviceMatrix<S> *left, const DeviceMatrix<S> *mid,
+                  const DeviceBuffer<Real> *s, const DeviceMatrix<S> *right, const DeviceIndex *ranks, int32_t dense_count = 0,
                   const DeviceMatrix<T> *dense = nullptr)
         : nrows_(nrows), ncols_(ncols), count_(count), dense_count_(dense ? dense_count : 0), left_(left), mid_(mid), right_(right), dense_(dense),
           s_(s), ranks_(ranks) {
@@ -867,26 +921,30 @@ class BlockOperator {
         }
         static std::vector<int64_t> pad(std::vector<int64_t> v) { v.push_back(0); return v; }  // never a null pointer, also without entries
     };
-    static rc_matrix block_view(const DeviceMatrix<T> *a, int64_t r, int64_t c, bool transposed) {
+    template <typename E>
+    static rc_matrix block_view(const DeviceMatrix<E> *a, int64_t r, int64_t c, bool transposed) {
         if (!a) return rc_matrix{nullptr, 0, 0, 0, 0};
         return transposed ? rc_matrix{a->view().data, c, r, 1, c} : rc_matrix{a->view().data, r, c, c, 1};
     }
     void call(const Context &ctx, const Pattern &pat, bool adjoint, rc_matrix x, rc_matrix y) const {
-        const DeviceMatrix<T> *l = adjoint ? right_ : left_, *r = adjoint ? left_ : right_;
+        const DeviceMatrix<S> *l = adjoint ? right_ : left_, *r = adjoint ? left_ : right_;
         const int64_t lr = adjoint ? k_ : m_, lc = adjoint ? n_ : k_, rr = adjoint ? m_ : k_, rcols = adjoint ? k_ : n_;  // stored shapes
-        ctx.check(BlockOperatorApi<T>::apply(ctx.raw(), block_view(l, lr, lc, adjoint), lr * lc, block_view(mid_, k_, k_, adjoint), k_ * k_,
+        ctx.check(BlockOperatorApi<T, S>::apply(ctx.raw(), block_view(l, lr, lc, adjoint), lr * lc, block_view(mid_, k_, k_, adjoint), k_ * k_,
                                              s_ ? s_->data() : nullptr, p_, block_view(r, rr, rcols, adjoint), rr * rcols,
                                              ranks_ ? ranks_->data() : nullptr, left_ ? count_ : 0, block_view(dense_, m_, n_, adjoint), m_ * n_,
                                              dense_count_, pat.ptr.data(), pat.row.data(), pat.groups, pat.block.data(), pat.col.data(), x, y, 0,
-                                             adjoint && BlockOperatorApi<T>::conj ? 1 : 0));
+                                             adjoint && BlockOperatorApi<T, S>::conj ? 1 : 0));
     }
     int64_t nrows_, ncols_, m_ = 0, n_ = 0, k_ = 0, p_ = 0;
     int32_t count_, dense_count_;
-    const DeviceMatrix<T> *left_, *mid_, *right_, *dense_;
+    const DeviceMatrix<S> *left_, *mid_, *right_;
+    const DeviceMatrix<T> *dense_;
     const DeviceBuffer<Real> *s_;
     const DeviceIndex *ranks_;
     Pattern by_row_, by_col_;
 };
+template <typename T>
+using MixedBlockOperator = BlockOperator<T, typename Mixed<T>::storage>;
 template <typename T>
 typename Scalar<T>::real max_col_norm(const DeviceMatrix<T> &y) {  // :184-191
     typename Scalar<T>::real out = 0;

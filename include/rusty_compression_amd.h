@@ -760,6 +760,50 @@ rc_status rc_block_operator_apply_f64(rc_context *ctx, rc_matrix left, int64_t l
 rc_status rc_block_operator_apply_f32(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const float *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix dense, int64_t dense_batch_stride, int32_t dense_count, const int64_t *group_ptr, const int64_t *group_row, int32_t groups, const int64_t *entry_block, const int64_t *entry_col, rc_matrix x, rc_matrix y, int32_t accumulate, int32_t conj);
 rc_status rc_block_operator_apply_c64(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const double *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix dense, int64_t dense_batch_stride, int32_t dense_count, const int64_t *group_ptr, const int64_t *group_row, int32_t groups, const int64_t *entry_block, const int64_t *entry_col, rc_matrix x, rc_matrix y, int32_t accumulate, int32_t conj);
 rc_status rc_block_operator_apply_c32(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const float *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix dense, int64_t dense_batch_stride, int32_t dense_count, const int64_t *group_ptr, const int64_t *group_row, int32_t groups, const int64_t *entry_block, const int64_t *entry_col, rc_matrix x, rc_matrix y, int32_t accumulate, int32_t conj);
+/* Mixed-precision storage of a compressed batch: the factors in f32 (c32 for complex blocks), everything else in f64 (c64).  Factors that were
+ * produced to a tolerance of 1e-6 carry no more than 24 bits of information; storing them in the narrow type halves the footprint of the compressed
+ * operator and the bytes its matvec moves, while the vectors, the accumulation and the dense near-field blocks keep full precision.  Below, S is
+ * the storage type and T the compute type: (T, S) = (f64, f32) for the _f64 calls and (c64, c32) for the _c64 calls.
+ *
+ * rc_lowrank_apply_mixed_batched_f64 / _c64 take the arguments of rc_lowrank_apply_batched_f64 / _c64, with left, mid and right views of S data
+ * (their strides and batch strides count elements of S); s stays double, b and y are T, ranks is unchanged.
+ * rc_block_operator_apply_mixed_f64 / _c64 take the arguments of rc_block_operator_apply_f64 / _c64, with left, mid and right of S; dense, x, y
+ * are T and s double: near-field blocks stay in full precision.
+ * Contract.  Every stored element is widened exactly to T as it is loaded (f32 -> f64 is exact; a complex element widens componentwise, and conj
+ * is applied after widening); everything else is the twin's arithmetic in the twin's order.  The result is, bit for bit, what
+ * rc_lowrank_apply_batched_T / rc_block_operator_apply_T writes for the same call on promoted copies of the factors (rc_promote_batched_*).
+ * Hence every clause of the twins carries over unchanged: nothing at an index >= r is read; block i's (a group's) bits do not depend on count, the
+ * neighbours, any batch stride, the column tile, the grid, or graph replay against an eager call; the accumulate and conj flags; health bit 64
+ * for an out-of-range index; the domains 1 <= m, n <= 512, 1 <= K <= 128, nrhs >= 1; the argument checks, their status codes and messages.
+ * Consequence.  Switching a batch from T to S storage changes the result only through the rounding of the stored factors: elementwise by at most
+ * q u32 (1 + 2 u32) E, where q is the number of demoted factors in the chain (2, or 3 with mid), u32 = 2^-24 and
+ * E = |left| |mid| diag(|s|) |right| |b| taken to the rank ((1 + u)^q - 1 <= q u (1 + 2 u) for q <= 3), provided no factor element overflowed or
+ * fell into the f32 subnormal range when it was demoted. */
+rc_status rc_lowrank_apply_mixed_batched_f64(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const double *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix b, int64_t b_batch_stride, rc_matrix y, int64_t y_batch_stride);
+rc_status rc_lowrank_apply_mixed_batched_c64(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const double *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix b, int64_t b_batch_stride, rc_matrix y, int64_t y_batch_stride);
+rc_status rc_block_operator_apply_mixed_f64(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const double *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix dense, int64_t dense_batch_stride, int32_t dense_count, const int64_t *group_ptr, const int64_t *group_row, int32_t groups, const int64_t *entry_block, const int64_t *entry_col, rc_matrix x, rc_matrix y, int32_t accumulate, int32_t conj);
+rc_status rc_block_operator_apply_mixed_c64(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const double *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix dense, int64_t dense_batch_stride, int32_t dense_count, const int64_t *group_ptr, const int64_t *group_row, int32_t groups, const int64_t *entry_block, const int64_t *entry_col, rc_matrix x, rc_matrix y, int32_t accumulate, int32_t conj);
+/* Strided batched conversion between the two types, so that a C, C++ or Rust host can move a factor batch in one stream-ordered, capturable
+ * call: rc_demote_batched_f64 / _c64 convert T -> S (src is f64 / c64, dst f32 / c32), rc_promote_batched_f32 / _c32 convert S -> T (src is
+ * f32 / c32, dst f64 / c64).  Block i is src moved by i * src_batch_stride and dst moved by i * dst_batch_stride, each in elements of its own
+ * type; src and dst have the same rows x cols and any row and column strides; dst must not overlap src.  Demotion is IEEE round-to-nearest-even
+ * per (real or imaginary) component, the bits of NumPy's astype(float32): results that are f32 subnormals, +-0, and finite values beyond the f32
+ * range, which become +-inf, included; NaN stays NaN (payload unspecified).  overflow may be NULL; otherwise it holds count device int64 values and
+ * overflow[i] receives the number of finite source elements of block i whose image is not finite (a complex element is finite when both parts
+ * are); the call writes the value, it does not add to it, and the value is deterministic.  Promotion is exact.  Domain: 1 <= rows, cols <= 65536
+ * (the tall c of the sketched ID included), count >= 0 (0: nothing to do).  RC_INVALID_ARGUMENT for an argument outside the domain, dst not of
+ * src's shape, a dst batch stride smaller than one view's span when count > 1, a null src or dst with count > 0, or a null ctx.  No host
+ * synchronisation, no workspace. */
+rc_status rc_demote_batched_f64(rc_context *ctx, rc_matrix src, int64_t src_batch_stride, int32_t count, rc_matrix dst, int64_t dst_batch_stride, int64_t *overflow);
+rc_status rc_demote_batched_c64(rc_context *ctx, rc_matrix src, int64_t src_batch_stride, int32_t count, rc_matrix dst, int64_t dst_batch_stride, int64_t *overflow);
+rc_status rc_promote_batched_f32(rc_context *ctx, rc_matrix src, int64_t src_batch_stride, int32_t count, rc_matrix dst, int64_t dst_batch_stride);
+rc_status rc_promote_batched_c32(rc_context *ctx, rc_matrix src, int64_t src_batch_stride, int32_t count, rc_matrix dst, int64_t dst_batch_stride);
+/* Reserved: the _f32 members of the three stems above (every _f64 entry point of this header has an _f32 one).  They would be f32 arithmetic over
+ * 16-bit storage, which this library does not build: each returns RC_INVALID_ARGUMENT for every call (and for a null ctx), with a message
+ * that names the _f64 and _c64 calls, and touches no operand. */
+rc_status rc_lowrank_apply_mixed_batched_f32(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const float *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix b, int64_t b_batch_stride, rc_matrix y, int64_t y_batch_stride);
+rc_status rc_block_operator_apply_mixed_f32(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const float *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix dense, int64_t dense_batch_stride, int32_t dense_count, const int64_t *group_ptr, const int64_t *group_row, int32_t groups, const int64_t *entry_block, const int64_t *entry_col, rc_matrix x, rc_matrix y, int32_t accumulate, int32_t conj);
+rc_status rc_demote_batched_f32(rc_context *ctx, rc_matrix src, int64_t src_batch_stride, int32_t count, rc_matrix dst, int64_t dst_batch_stride, int64_t *overflow);
 
 /* The gather over RCCL (xGMI inside a node).  One process per GPU: rank 0 calls rc_comm_unique_id and hands the 128
  * bytes to the other ranks by whatever means the host has (MPI, a file, torch.distributed), every rank calls

@@ -16,11 +16,12 @@ from .batch import (column_id_to_svd_batched_complex, lowrank_recompress_batched
 from .batch import sketch_column_id_rank_batched  # noqa: F401
 from .batch import sketch_column_id_rank_batched_complex  # noqa: F401
 from .batch import block_csr, block_operator_apply  # noqa: F401
+from .batch import block_operator_apply_mixed, demote_batched, lowrank_apply_batched_mixed, promote_batched  # noqa: F401
 from .batch import column_id_residual_batched, lowrank_residual_batched, svd_residual_batched, two_sided_id_residual_batched  # noqa: F401
 from .batch import (column_id_residual_batched_complex, lowrank_residual_batched_complex, svd_residual_batched_complex,  # noqa: F401
                     two_sided_id_residual_batched_complex)
 from .col_interp_decomp import ColumnID  # noqa: F401
-from .operator import BlockLowRankOperator, DenseOperator, LowRankOperator, Operator  # noqa: F401
+from .operator import BlockLowRankOperator, DenseOperator, LowRankOperator, MixedBlockLowRankOperator, Operator  # noqa: F401
 from .permutation import (MatrixPermutationMode, VectorPermutationMode, apply_permutation,  # noqa: F401
                           invert_permutation_vector)
 from .qr import LQ, QR, pivoted_lq, pivoted_qr  # noqa: F401
@@ -43,4 +44,5 @@ __all__ = [
     "RustyCompressionError", "LinalgError", "CompressionError", "LayoutError", "PivotedQRError", "HipRuntimeError",
     "Context", "default_context", "Operator", "DenseOperator", "LowRankOperator", "BlockLowRankOperator",
     "block_csr", "block_operator_apply",
+    "lowrank_apply_batched_mixed", "block_operator_apply_mixed", "demote_batched", "promote_batched", "MixedBlockLowRankOperator",
 ]

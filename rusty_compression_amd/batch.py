@@ -393,6 +393,177 @@ def block_operator_apply(x: torch.Tensor, group_ptr, group_row, entry_block, ent
     return call.apply(x, y=y, rows=rows, accumulate=accumulate, conj=conj)
 
 
+# mixed-precision storage: the factors of a compressed batch in the narrow type, everything else in the wide one
+_MIXED_WIDE = {torch.float32: torch.float64, torch.complex64: torch.complex128}
+_MIXED_STORAGE = {wide: narrow for narrow, wide in _MIXED_WIDE.items()}
+
+
+def _mixed_wide_dtype(who: str, same: str, factors: dict) -> torch.dtype:
+    """The compute dtype of the storage dtype the factors of a mixed call share; TypeError for anything but float32 / complex64 factors."""
+    first = next(iter(factors.values()))
+    for name, t in factors.items():
+        if t.dtype != first.dtype:
+            raise TypeError(f"{who}: {name} is {t.dtype}, the other factors are {first.dtype}")
+    if first.dtype not in _MIXED_WIDE:
+        raise TypeError(f"{who}: the factors must be stored in float32 (with float64 vectors) or complex64 (with complex128 vectors), got "
+                        f"{first.dtype}; use {same} when every operand has one dtype")
+    return _MIXED_WIDE[first.dtype]
+
+
+def _convert_batched(who: str, x: torch.Tensor, table: dict, stem: str, return_overflow: bool):
+    from . import _lib
+    from .types import as_device
+
+    x = as_device(x).resolve_conj()
+    if x.dtype not in table:
+        raise TypeError(f"{who}: x is {x.dtype}, expected one of {sorted(str(d) for d in table)}")
+    if x.dim() != 3:
+        raise AssertionError(f"{who}: expected a [count, rows, cols] batch")
+    count, rows, cols = x.shape
+    out = torch.empty((count, rows, cols), dtype=table[x.dtype], device=x.device)
+    overflow = torch.zeros(count, dtype=torch.int64, device=x.device) if return_overflow else None
+    blank = x.new_empty(rows, cols)  # block 0 of an empty batch: the shapes are still checked
+    args = [_lib.mat(x[0] if count else blank), ctypes.c_int64(x.stride(0)), ctypes.c_int32(count),
+            _lib.mat(out[0] if count else out.new_empty(rows, cols)), ctypes.c_int64(rows * cols)]
+    if stem == "rc_demote_batched":
+        args.append(_lib.i64p(overflow))
+    _lib.default_context().call(f"{stem}_{_lib.suffix(x.dtype)}", *args)
+    return (out, overflow) if return_overflow else out
+
+
+def demote_batched(x: torch.Tensor, return_overflow: bool = False):
+    """The storage copy of a factor batch for the mixed calls (rc_demote_batched_f64 / _c64): x [count, rows, cols] of float64 or
+    complex128, any strides, rounded to nearest even into a fresh contiguous float32 / complex64 tensor, the bits of NumPy's astype.  With
+    return_overflow also an int64 [count] tensor: per block the finite elements that became infinite."""
+    return _convert_batched("demote_batched", x, _MIXED_STORAGE, "rc_demote_batched", return_overflow)
+
+
+def promote_batched(x: torch.Tensor) -> torch.Tensor:
+    """The exact inverse direction (rc_promote_batched_f32 / _c32): x [count, rows, cols] of float32 or complex64 widened into a fresh
+    contiguous float64 / complex128 tensor."""
+    return _convert_batched("promote_batched", x, _MIXED_WIDE, "rc_promote_batched", False)
+
+
+def lowrank_apply_batched_mixed(left: torch.Tensor, right: torch.Tensor, b: Optional[torch.Tensor] = None, mid: Optional[torch.Tensor] = None,
+                                s: Optional[torch.Tensor] = None, ranks: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """lowrank_apply_batched for factors kept in storage precision (rc_lowrank_apply_mixed_batched_f64 / _c64): left, mid and right are
+    float32 with b and s float64, or complex64 with b complex128 and s float64.  Every factor element is widened exactly as it is loaded
+    and the arithmetic is the wide call's, so the result (float64 / complex128, also when reconstructing with b = None) has the bits of
+    lowrank_apply_batched on promote_batched copies of the factors, while the launch reads half the factor bytes.  Shapes, strides, ranks
+    and the returned shapes are lowrank_apply_batched's.  Any other combination of dtypes raises TypeError."""
+    from . import _lib
+    from .types import as_device
+
+    who = "lowrank_apply_batched_mixed"
+    fac = {"left": left, "right": right, "mid": mid}
+    fac = {name: as_device(t).resolve_conj() for name, t in fac.items() if t is not None}  # the kernels read the stored values
+    left, right, mid = fac["left"], fac["right"], fac.get("mid")
+    wide = _mixed_wide_dtype(who, "lowrank_apply_batched", fac)
+    if b is not None:
+        b = as_device(b).resolve_conj()
+        if b.dtype != wide:
+            raise TypeError(f"{who}: b is {b.dtype}, expected {wide} beside {left.dtype} factors")
+    if left.dim() != 3 or right.dim() != 3 or (mid is not None and mid.dim() != 3) or (b is not None and b.dim() not in (2, 3)):
+        raise AssertionError("expected left [count, m, k], right [count, k, n], mid [count, k, k] and b [count, n, nrhs] or [count, n]")
+    count, m, k = left.shape
+    n = right.shape[2]
+    for name, t in {**fac, **({"b": b} if b is not None else {})}.items():
+        if t.shape[0] != count:
+            raise AssertionError(f"{who}: {name} holds {t.shape[0]} blocks, left {count}")
+    if s is not None:
+        s = as_device(s)
+        if s.dtype != torch.float64:
+            raise TypeError(f"{who}: s is {s.dtype}, expected torch.float64")
+        if s.dim() != 2 or s.shape[0] != count or s.shape[1] < k:
+            raise AssertionError(f"{who}: s must be [count, p] with p >= k = {k}")
+        if s.stride(1) != 1:
+            s = s.contiguous()
+    if ranks is not None:
+        ranks = as_device(ranks)
+        if ranks.dtype != torch.int64:
+            raise TypeError(f"{who}: ranks is {ranks.dtype}, expected torch.int64")
+        if ranks.shape != (count,):
+            raise AssertionError(f"{who}: ranks must be [count]")
+        ranks = ranks.contiguous()
+    vector = b is not None and b.dim() == 2
+    if vector:
+        b = b.unsqueeze(2)
+    ncols = n if b is None else b.shape[2]
+    y = torch.empty((count, m, ncols), dtype=wide, device=left.device)
+
+    def view(t):  # block 0's view and the batch stride
+        if t is None:
+            return _lib.mat(None), ctypes.c_int64(0)
+        return _lib.rc_matrix(t.data_ptr(), t.shape[1], t.shape[2], t.stride(1), t.stride(2)), ctypes.c_int64(t.stride(0))
+
+    _lib.default_context().call(f"rc_lowrank_apply_mixed_batched_{_lib.suffix(wide)}", *view(left), *view(mid),
+                                ctypes.c_void_p(s.data_ptr() if s is not None else None), ctypes.c_int64(s.stride(0) if s is not None else 0),
+                                *view(right), _lib.i64p(ranks), ctypes.c_int32(count), *view(b),
+                                _lib.rc_matrix(y.data_ptr(), m, ncols, ncols, 1), ctypes.c_int64(m * ncols))
+    return y[:, :, 0] if vector else y
+
+
+class _MixedBlockOperatorCall(_BlockOperatorCall):
+    """_BlockOperatorCall for rc_block_operator_apply_mixed_*: left, mid and right in the storage dtype, dense, x and y in the wide one (the
+    call's dtype), s float64.  The argument list and apply are the base class's."""
+
+    def __init__(self, who, pattern, left=None, right=None, mid=None, s=None, ranks=None, dense=None):
+        from . import _lib
+        from .types import as_device, as_index
+
+        fac = {"left": left, "right": right, "mid": mid}
+        fac = {name: as_device(t).resolve_conj() for name, t in fac.items() if t is not None}  # the kernels read the stored values
+        if "left" not in fac or "right" not in fac:
+            raise AssertionError(f"{who}: needs a low-rank batch (left, right) in storage precision; a dense-only operator has nothing to demote")
+        self.dtype = _mixed_wide_dtype(who, "block_operator_apply", fac)
+        if dense is not None:
+            dense = as_device(dense).resolve_conj()
+            if dense.dtype != self.dtype:
+                raise TypeError(f"{who}: dense is {dense.dtype}, expected {self.dtype} (near-field blocks stay in full precision)")
+        for name, t in {**fac, **({"dense": dense} if dense is not None else {})}.items():
+            if t.dim() != 3:
+                raise AssertionError(f"{who}: {name} must be a [count, rows, cols] batch")
+        self.left, self.right, self.mid, self.dense = fac["left"], fac["right"], fac.get("mid"), dense
+        self.count = self.left.shape[0]
+        for name in ("right", "mid"):
+            if name in fac and fac[name].shape[0] != self.count:
+                raise AssertionError(f"{who}: {name} holds {fac[name].shape[0]} blocks, left {self.count}")
+        self.m, self.n = self.left.shape[1], self.right.shape[2]
+        self.s = self.ranks = None
+        if s is not None:
+            k = self.left.shape[2]
+            s = as_device(s)
+            if s.dtype != torch.float64:
+                raise TypeError(f"{who}: s is {s.dtype}, expected torch.float64")
+            if s.dim() != 2 or s.shape[0] != self.count or s.shape[1] < k:
+                raise AssertionError(f"{who}: s must be [count, p] with p >= k = {k}")
+            self.s = s if s.stride(1) == 1 else s.contiguous()
+        if ranks is not None:
+            ranks = as_device(ranks)
+            if ranks.dtype != torch.int64:
+                raise TypeError(f"{who}: ranks is {ranks.dtype}, expected torch.int64")
+            if ranks.shape != (self.count,):
+                raise AssertionError(f"{who}: ranks must be [count]")
+            self.ranks = ranks.contiguous()
+        self.pattern = tuple(as_index(v) for v in pattern)
+        group_ptr, group_row, entry_block, entry_col = self.pattern
+        self.groups = int(group_row.numel())
+        if group_ptr.numel() != self.groups + 1 or entry_block.numel() != entry_col.numel():
+            raise AssertionError(f"{who}: group_ptr needs groups + 1 values, entry_block and entry_col one per entry")
+        self.name = f"rc_block_operator_apply_mixed_{_lib.suffix(self.dtype)}"
+
+
+def block_operator_apply_mixed(x: torch.Tensor, group_ptr, group_row, entry_block, entry_col, left: Optional[torch.Tensor] = None,
+                               right: Optional[torch.Tensor] = None, mid: Optional[torch.Tensor] = None, s: Optional[torch.Tensor] = None,
+                               ranks: Optional[torch.Tensor] = None, dense: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None,
+                               rows: Optional[int] = None, accumulate: bool = False, conj: bool = False) -> torch.Tensor:
+    """block_operator_apply for low-rank blocks kept in storage precision (rc_block_operator_apply_mixed_f64 / _c64): left, mid and right
+    are float32 (complex64); dense, x and y are float64 (complex128) and s float64.  The result has the bits of block_operator_apply on
+    promote_batched copies of the factors; every other argument and rule is block_operator_apply's."""
+    call = _MixedBlockOperatorCall("block_operator_apply_mixed", (group_ptr, group_row, entry_block, entry_col), left, right, mid, s, ranks, dense)
+    return call.apply(x, y=y, rows=rows, accumulate=accumulate, conj=conj)
+
+
 def _lowrank_recompress_batched(who: str, complex_data: bool, left, right, k, tol, mid, s, ranks):
     """The shared body of lowrank_recompress_batched (real dtypes) and lowrank_recompress_batched_complex (complex dtypes, real s and S)."""
     from . import _lib

@@ -24,14 +24,18 @@
 // red-fast mapping is bound by its cross-lane sums, about one shuffle per FMA (tools/batched_apply_bench.py).
 //
 // The complex scalars run the same kernel on interleaved (re, im) pairs; nothing is conjugated.
+//
+// Mixed storage (rc_lowrank_apply_mixed_batched_*): S, the type left, mid and right are stored in, is f32 under E = f64 and c32 under c64.
+// An element is widened exactly as it is loaded (ba_widen); LDS, b, y, s, the accumulators, the mapping and the summation trees are those
+// of E, so the result has the bits of the E call on promoted factors while the launch moves half the factor bytes.
 #include "batched_apply.hpp"
 
 namespace rc {
 
 namespace {
 
-template <typename E, int NBT>
-__global__ __launch_bounds__(BA_THREADS) void k_batched_apply(BaArgs<E> a) {
+template <typename E, int NBT, typename S = E>
+__global__ __launch_bounds__(BA_THREADS) void k_batched_apply(BaArgs<E, S> a) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int m = a.m, n = a.n, k = a.k, ncols = a.ncols;
     const int ldn = n | 1, ldk = k | 1;
@@ -61,13 +65,13 @@ __global__ __launch_bounds__(BA_THREADS) void k_batched_apply(BaArgs<E> a) {
             continue;
         }
         // ---- stage 1: W0 = right[:r, :] b, or the tile of right[:r, :] itself -------------------------------------------------------
-        const E *Rt = a.right.p + blk * a.right.bs;
+        const S *Rt = a.right.p + blk * a.right.bs;
         if (a.b.p) {
             ba_load_tile<E, NBT>(Bs, ldn, a.b.p + blk * a.b.bs, a.b.rs, a.b.cs, n, c0, nb, tid);
             __syncthreads();
-            ba_product<E, NBT>(Rt, a.right.rs, a.right.cs, r, n, Bs, ldn, [&](int row, int c, E v) { W0[c * ldk + row] = v; }, tid);
+            ba_product<E, NBT, false, S>(Rt, a.right.rs, a.right.cs, r, n, Bs, ldn, [&](int row, int c, E v) { W0[c * ldk + row] = v; }, tid);
         } else {
-            ba_load_tile<E, NBT>(W0, ldk, Rt, a.right.rs, a.right.cs, r, c0, nb, tid);
+            ba_load_tile<E, NBT, S>(W0, ldk, Rt, a.right.rs, a.right.cs, r, c0, nb, tid);
         }
         __syncthreads();
         // ---- W0 = diag(s[:r]) W0 --------------------------------------------------------------------------------------------------------
@@ -82,12 +86,12 @@ __global__ __launch_bounds__(BA_THREADS) void k_batched_apply(BaArgs<E> a) {
         // ---- W1 = mid[:r, :r] W0 --------------------------------------------------------------------------------------------------------
         const E *Wc = W0;
         if (a.mid.p) {
-            ba_product<E, NBT>(a.mid.p + blk * a.mid.bs, a.mid.rs, a.mid.cs, r, r, W0, ldk, [&](int row, int c, E v) { W1[c * ldk + row] = v; }, tid);
+            ba_product<E, NBT, false, S>(a.mid.p + blk * a.mid.bs, a.mid.rs, a.mid.cs, r, r, W0, ldk, [&](int row, int c, E v) { W1[c * ldk + row] = v; }, tid);
             __syncthreads();
             Wc = W1;
         }
         // ---- y = left[:, :r] W ----------------------------------------------------------------------------------------------------------
-        ba_product<E, NBT>(a.left.p + blk * a.left.bs, a.left.rs, a.left.cs, m, r, Wc, ldk, to_y, tid);
+        ba_product<E, NBT, false, S>(a.left.p + blk * a.left.bs, a.left.rs, a.left.cs, m, r, Wc, ldk, to_y, tid);
         __syncthreads();  // Bs, W0 and W1 are rewritten by the next unit
     }
 }
@@ -101,25 +105,25 @@ BatchedPlan<int> ba_plan(int n, int k, int ncols, bool has_b, bool has_mid) {
     return {nbt, ba_lds_bytes<E>(n, k, nbt, has_b, has_mid), 0};
 }
 
-template <typename E, int NBT>
-void ba_launch_nbt(rc_context *c, const BaArgs<E> &a, const char *tag, size_t lds) {
+template <typename E, int NBT, typename S>
+void ba_launch_nbt(rc_context *c, const BaArgs<E, S> &a, const char *tag, size_t lds) {
     const int64_t ntiles = (a.ncols + NBT - 1) / NBT;
-    const auto lch = batched_prepare(c, k_batched_apply<E, NBT>, "lowrank_apply_batched", lds, 0, (int64_t)a.count * ntiles);
+    const auto lch = batched_prepare(c, k_batched_apply<E, NBT, S>, "lowrank_apply_batched", lds, 0, (int64_t)a.count * ntiles);
     ProfScope ps(c, "op:batched_apply%s %dx%d k=%d count=%d grid=%lld slots=%lld plan=nb:%d,tiles:%lld,cols:%d,%s%s%s", tag, a.m, a.n, a.k, a.count,
                  (long long)lch.grid, (long long)lch.slots, NBT, (long long)ntiles, a.ncols, a.b.p ? "apply" : "to_mat", a.mid.p ? ",mid" : "", a.s ? ",s" : "");
     lch.launch(a);
 }
 
-template <typename E>
-void ba_launch(rc_context *c, const BaArgs<E> &a, const char *tag) {
+template <typename E, typename S>
+void ba_launch(rc_context *c, const BaArgs<E, S> &a, const char *tag) {
     if (a.count <= 0) return;
     const auto plan = ba_plan<E>(a.n, a.k, a.ncols, a.b.p != nullptr, a.mid.p != nullptr);
-    if (plan.at == 1) return ba_launch_nbt<E, 1>(c, a, tag, plan.lds);
-    if (plan.at == 4) return ba_launch_nbt<E, 4>(c, a, tag, plan.lds);
+    if (plan.at == 1) return ba_launch_nbt<E, 1, S>(c, a, tag, plan.lds);
+    if (plan.at == 4) return ba_launch_nbt<E, 4, S>(c, a, tag, plan.lds);
     if constexpr (ba_nb<E>() >= 16) {
-        if (plan.at == 8) return ba_launch_nbt<E, 8>(c, a, tag, plan.lds);
+        if (plan.at == 8) return ba_launch_nbt<E, 8, S>(c, a, tag, plan.lds);
     }
-    ba_launch_nbt<E, ba_nb<E>()>(c, a, tag, plan.lds);
+    ba_launch_nbt<E, ba_nb<E>(), S>(c, a, tag, plan.lds);
 }
 
 template <typename E, typename P>
@@ -138,7 +142,7 @@ void batched_lowrank_apply(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, 
     a.y = ba_view<T>(y.p, y.rs, y.cs, ybs);
     a.s = s; a.s_stride = s_stride; a.ranks = ranks; a.count = count;
     a.m = (int)left.rows; a.n = (int)right.cols; a.k = (int)left.cols; a.ncols = (int)y.cols;
-    ba_launch<T>(c, a, "");
+    ba_launch<T, T>(c, a, "");
 }
 
 template <typename R>
@@ -154,7 +158,30 @@ void batched_lowrank_apply_c(rc_context *c, const rc_matrix &left, int64_t lbs, 
     a.y = ba_view<E>(y.data, y.row_stride, y.col_stride, ybs);
     a.s = s; a.s_stride = s_stride; a.ranks = ranks; a.count = count;
     a.m = (int)left.rows; a.n = (int)right.cols; a.k = (int)left.cols; a.ncols = (int)y.cols;
-    ba_launch<E>(c, a, "<complex>");
+    ba_launch<E, E>(c, a, "<complex>");
+}
+
+// the mixed calls: factor views of S (strides in elements of S), b and y of E, s double
+template <typename E, typename S>
+static void ba_mixed(rc_context *c, const rc_matrix &left, int64_t lbs, const rc_matrix &mid, int64_t mbs, const double *s, int64_t s_stride,
+                     const rc_matrix &right, int64_t rbs, const int64_t *ranks, int32_t count, const rc_matrix &b, int64_t bbs, const rc_matrix &y, int64_t ybs,
+                     const char *tag) {
+    BaArgs<E, S> a;
+    a.left = ba_view<const S>(left.data, left.row_stride, left.col_stride, lbs);
+    a.mid = ba_view<const S>(mid.data, mid.row_stride, mid.col_stride, mbs);
+    a.right = ba_view<const S>(right.data, right.row_stride, right.col_stride, rbs);
+    a.b = ba_view<const E>(b.data, b.row_stride, b.col_stride, bbs);
+    a.y = ba_view<E>(y.data, y.row_stride, y.col_stride, ybs);
+    a.s = s; a.s_stride = s_stride; a.ranks = ranks; a.count = count;
+    a.m = (int)left.rows; a.n = (int)right.cols; a.k = (int)left.cols; a.ncols = (int)y.cols;
+    ba_launch<E, S>(c, a, tag);
+}
+
+void batched_lowrank_apply_mixed(rc_context *c, bool complex_data, const rc_matrix &left, int64_t lbs, const rc_matrix &mid, int64_t mbs, const double *s,
+                                 int64_t s_stride, const rc_matrix &right, int64_t rbs, const int64_t *ranks, int32_t count, const rc_matrix &b, int64_t bbs,
+                                 const rc_matrix &y, int64_t ybs) {
+    if (complex_data) ba_mixed<cplx<double>, cplx<float>>(c, left, lbs, mid, mbs, s, s_stride, right, rbs, ranks, count, b, bbs, y, ybs, "<complex,mixed>");
+    else ba_mixed<double, float>(c, left, lbs, mid, mbs, s, s_stride, right, rbs, ranks, count, b, bbs, y, ybs, "<mixed>");
 }
 
 template void batched_lowrank_apply<double>(rc_context *, Mat<double>, int64_t, Mat<double>, int64_t, const double *, int64_t, Mat<double>, int64_t,

@@ -18,6 +18,9 @@
 // Neither depends on NBT, the tile, the grid or the other groups.  The adds into the accumulator are kept out of reach of FMA contraction.
 //
 // conj (complex instances only): a template flag on ba_product's loads of left, mid, right and dense; s is real and x is untouched.
+//
+// Mixed storage (rc_block_operator_apply_mixed_*): left, mid and right are stored in S (f32 under E = f64, c32 under c64) and widened as
+// ba_product loads them; dense, x, y, s, LDS and every sum stay in E, so the bits are those of the E call on promoted factors.
 #include "batched_apply.hpp"
 
 namespace rc {
@@ -26,9 +29,10 @@ namespace {
 
 constexpr int BOP_BAD_INDEX = 64;  // health bit: a block id, entry_col or group_row out of range
 
-template <typename E>
+template <typename E, typename S = E>
 struct BopArgs {
-    BaView<const E> left, mid, right, dense;  // dense.p == nullptr: no dense blocks
+    BaView<const S> left, mid, right;  // stored in S
+    BaView<const E> dense;             // dense.p == nullptr: no dense blocks
     const typename El<E>::real *s;
     int64_t s_stride;
     const int64_t *ranks;
@@ -59,8 +63,8 @@ __device__ __forceinline__ cplx<R> bop_add(cplx<R> a, cplx<R> b) {
     return {a.re + b.re, a.im + b.im};
 }
 
-template <typename E, int NBT, bool CJ>
-__global__ __launch_bounds__(BA_THREADS) void k_block_operator(BopArgs<E> a) {
+template <typename E, int NBT, bool CJ, typename S = E>
+__global__ __launch_bounds__(BA_THREADS) void k_block_operator(BopArgs<E, S> a) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int m = a.m, n = a.n, k = a.k, ncols = a.ncols;
     const int ldn = n | 1, ldk = k | 1, ldm = m | 1;
@@ -111,7 +115,7 @@ __global__ __launch_bounds__(BA_THREADS) void k_block_operator(BopArgs<E> a) {
                 continue;
             }
             // ---- the apply's chain (k_batched_apply), the last store adding into Acc ----------------------------------------------------
-            ba_product<E, NBT, CJ>(a.right.p + blk * a.right.bs, a.right.rs, a.right.cs, r, n, Bs, ldn, [&](int row, int c, E v) { W0[c * ldk + row] = v; },
+            ba_product<E, NBT, CJ, S>(a.right.p + blk * a.right.bs, a.right.rs, a.right.cs, r, n, Bs, ldn, [&](int row, int c, E v) { W0[c * ldk + row] = v; },
                                    tid);
             __syncthreads();
             if (a.s) {
@@ -124,11 +128,11 @@ __global__ __launch_bounds__(BA_THREADS) void k_block_operator(BopArgs<E> a) {
             }
             const E *Wc = W0;
             if (a.mid.p) {
-                ba_product<E, NBT, CJ>(a.mid.p + blk * a.mid.bs, a.mid.rs, a.mid.cs, r, r, W0, ldk, [&](int row, int c, E v) { W1[c * ldk + row] = v; }, tid);
+                ba_product<E, NBT, CJ, S>(a.mid.p + blk * a.mid.bs, a.mid.rs, a.mid.cs, r, r, W0, ldk, [&](int row, int c, E v) { W1[c * ldk + row] = v; }, tid);
                 __syncthreads();
                 Wc = W1;
             }
-            ba_product<E, NBT, CJ>(a.left.p + blk * a.left.bs, a.left.rs, a.left.cs, m, r, Wc, ldk, to_acc, tid);
+            ba_product<E, NBT, CJ, S>(a.left.p + blk * a.left.bs, a.left.rs, a.left.cs, m, r, Wc, ldk, to_acc, tid);
             __syncthreads();  // Bs, W0 and W1 are rewritten by the next entry, Acc by other threads
         }
         // ---- y[row0 : row0 + m, c0 : c0 + nb] = [y_old +] Acc, lanes along the fast index of y ------------------------------------------
@@ -156,10 +160,10 @@ BatchedPlan<int> bop_plan(int m, int n, int k, int ncols, bool has_mid) {
     return {nbt, bop_lds_bytes<E>(m, n, k, nbt, has_mid), 0};
 }
 
-template <typename E, int NBT, bool CJ>
-void bop_launch_nbt(rc_context *c, const BopArgs<E> &a, const char *tag, bool conj, size_t lds) {
+template <typename E, int NBT, bool CJ, typename S>
+void bop_launch_nbt(rc_context *c, const BopArgs<E, S> &a, const char *tag, bool conj, size_t lds) {
     const int64_t ntiles = (a.ncols + NBT - 1) / NBT;
-    const auto lch = batched_prepare(c, k_block_operator<E, NBT, CJ>, "block_operator_apply", lds, 0, (int64_t)a.groups * ntiles);
+    const auto lch = batched_prepare(c, k_block_operator<E, NBT, CJ, S>, "block_operator_apply", lds, 0, (int64_t)a.groups * ntiles);
     // entries: the number of entries is group_ptr[groups], which only the device knows
     ProfScope ps(c, "op:batched_operator_apply%s %dx%d k=%d count=%d grid=%lld slots=%lld plan=nb:%d,tiles:%lld,cols:%d,entries:dev,lr:%d,dense:%d%s%s%s%s", tag,
                  a.m, a.n, a.k, a.groups, (long long)lch.grid, (long long)lch.slots, NBT, (long long)ntiles, a.ncols, a.count, a.dense_count,
@@ -167,22 +171,22 @@ void bop_launch_nbt(rc_context *c, const BopArgs<E> &a, const char *tag, bool co
     lch.launch(a);
 }
 
-template <typename E, bool CJ>
-void bop_launch(rc_context *c, const BopArgs<E> &a, const char *tag, bool conj) {
+template <typename E, bool CJ, typename S>
+void bop_launch(rc_context *c, const BopArgs<E, S> &a, const char *tag, bool conj) {
     const auto plan = bop_plan<E>(a.m, a.n, a.k, a.ncols, a.mid.p != nullptr);
-    if (plan.at == 1) return bop_launch_nbt<E, 1, CJ>(c, a, tag, conj, plan.lds);
-    if (plan.at == 4) return bop_launch_nbt<E, 4, CJ>(c, a, tag, conj, plan.lds);
+    if (plan.at == 1) return bop_launch_nbt<E, 1, CJ, S>(c, a, tag, conj, plan.lds);
+    if (plan.at == 4) return bop_launch_nbt<E, 4, CJ, S>(c, a, tag, conj, plan.lds);
     if constexpr (ba_nb<E>() >= 16) {
-        if (plan.at == 16) return bop_launch_nbt<E, 16, CJ>(c, a, tag, conj, plan.lds);
+        if (plan.at == 16) return bop_launch_nbt<E, 16, CJ, S>(c, a, tag, conj, plan.lds);
     }
-    bop_launch_nbt<E, 8, CJ>(c, a, tag, conj, plan.lds);
+    bop_launch_nbt<E, 8, CJ, S>(c, a, tag, conj, plan.lds);
 }
 
 template <typename E, typename P>
 BaView<E> bop_view(P *p, int64_t rs, int64_t cs, int64_t bs) { return BaView<E>{reinterpret_cast<E *>(p), rs, cs, bs}; }
 
-template <typename E>
-void bop_pattern(rc_context *c, BopArgs<E> &a, const BlockPattern &pat, BlockShape shape, int32_t count, int32_t dense_count, bool accumulate) {
+template <typename E, typename S>
+void bop_pattern(rc_context *c, BopArgs<E, S> &a, const BlockPattern &pat, BlockShape shape, int32_t count, int32_t dense_count, bool accumulate) {
     a.group_ptr = pat.group_ptr; a.group_row = pat.group_row; a.entry_block = pat.entry_block; a.entry_col = pat.entry_col; a.groups = pat.groups;
     a.count = count; a.dense_count = a.dense.p ? dense_count : 0;
     a.m = shape.m; a.n = shape.n; a.k = shape.k;
@@ -206,7 +210,7 @@ void block_operator_apply(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, i
     a.y = y.p; a.yrs = y.rs; a.ycs = y.cs; a.yrows = y.rows;
     a.ncols = (int)y.cols;
     bop_pattern(c, a, pat, shape, count, dense_count, accumulate);
-    bop_launch<T, false>(c, a, "", false);
+    bop_launch<T, false, T>(c, a, "", false);
 }
 
 template <typename R>
@@ -224,8 +228,41 @@ void block_operator_apply_c(rc_context *c, const rc_matrix &left, int64_t lbs, c
     a.y = static_cast<E *>(y.data); a.yrs = y.row_stride; a.ycs = y.col_stride; a.yrows = y.rows;
     a.ncols = (int)y.cols;
     bop_pattern(c, a, pat, shape, count, dense_count, accumulate);
-    if (conj) bop_launch<E, true>(c, a, "<complex>", true);
-    else bop_launch<E, false>(c, a, "<complex>", false);
+    if (conj) bop_launch<E, true, E>(c, a, "<complex>", true);
+    else bop_launch<E, false, E>(c, a, "<complex>", false);
+}
+
+// the mixed calls: factor views of S (strides in elements of S), dense, x and y of E, s double
+template <typename E, typename S>
+static BopArgs<E, S> bop_mixed_args(rc_context *c, const rc_matrix &left, int64_t lbs, const rc_matrix &mid, int64_t mbs, const double *s, int64_t s_stride,
+                                    const rc_matrix &right, int64_t rbs, const int64_t *ranks, int32_t count, const rc_matrix &dense, int64_t dbs,
+                                    int32_t dense_count, const BlockPattern &pat, BlockShape shape, const rc_matrix &x, const rc_matrix &y, bool accumulate) {
+    BopArgs<E, S> a;
+    a.left = bop_view<const S>(left.data, left.row_stride, left.col_stride, lbs);
+    a.mid = bop_view<const S>(count > 0 ? mid.data : nullptr, mid.row_stride, mid.col_stride, mbs);
+    a.right = bop_view<const S>(right.data, right.row_stride, right.col_stride, rbs);
+    a.dense = bop_view<const E>(dense.data, dense.row_stride, dense.col_stride, dbs);
+    a.s = count > 0 ? s : nullptr; a.s_stride = s_stride; a.ranks = ranks;
+    a.x = static_cast<const E *>(x.data); a.xrs = x.row_stride; a.xcs = x.col_stride; a.xrows = x.rows;
+    a.y = static_cast<E *>(y.data); a.yrs = y.row_stride; a.ycs = y.col_stride; a.yrows = y.rows;
+    a.ncols = (int)y.cols;
+    bop_pattern(c, a, pat, shape, count, dense_count, accumulate);
+    return a;
+}
+
+void block_operator_apply_mixed(rc_context *c, bool complex_data, const rc_matrix &left, int64_t lbs, const rc_matrix &mid, int64_t mbs, const double *s,
+                                int64_t s_stride, const rc_matrix &right, int64_t rbs, const int64_t *ranks, int32_t count, const rc_matrix &dense, int64_t dbs,
+                                int32_t dense_count, const BlockPattern &pat, BlockShape shape, const rc_matrix &x, const rc_matrix &y, bool accumulate, bool conj) {
+    if (!complex_data) {
+        const auto a = bop_mixed_args<double, float>(c, left, lbs, mid, mbs, s, s_stride, right, rbs, ranks, count, dense, dbs, dense_count, pat, shape, x, y,
+                                                     accumulate);
+        return bop_launch<double, false, float>(c, a, "<mixed>", false);
+    }
+    using E = cplx<double>;
+    using S = cplx<float>;
+    const auto a = bop_mixed_args<E, S>(c, left, lbs, mid, mbs, s, s_stride, right, rbs, ranks, count, dense, dbs, dense_count, pat, shape, x, y, accumulate);
+    if (conj) bop_launch<E, true, S>(c, a, "<complex,mixed>", true);
+    else bop_launch<E, false, S>(c, a, "<complex,mixed>", false);
 }
 
 template void block_operator_apply<double>(rc_context *, Mat<double>, int64_t, Mat<double>, int64_t, const double *, int64_t, Mat<double>, int64_t,

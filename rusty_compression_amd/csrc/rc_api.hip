@@ -1290,6 +1290,16 @@ int64_t check_sketch_column_id_rank_batched(Mat<T> a, Mat<T> omega, int32_t coun
     if (count > 0) RC_REQUIRE(a.p && omega.p && cm.p && z.p && col_ind && ranks, RC_INVALID_ARGUMENT, "%s: null pointer", who);
     return kk;
 }
+// rc_demote_batched_* / rc_promote_batched_*: one shape on both sides, the sketched ID's tall domain, and dst's batch stride
+void check_convert_batched(const char *who, const rc_matrix &src, int32_t count, const rc_matrix &dst, int64_t dbs) {
+    RC_REQUIRE(count >= 0, RC_INVALID_ARGUMENT, "%s: count = %d < 0", who, (int)count);
+    RC_REQUIRE(src.rows >= 1 && src.rows <= 65536 && src.cols >= 1 && src.cols <= 65536, RC_INVALID_ARGUMENT,
+               "%s: needs 1 <= rows, cols <= 65536 (got src %lld x %lld)", who, (long long)src.rows, (long long)src.cols);
+    RC_REQUIRE(dst.rows == src.rows && dst.cols == src.cols, RC_INVALID_ARGUMENT, "%s: dst must be %lld x %lld like src (got %lld x %lld)", who,
+               (long long)src.rows, (long long)src.cols, (long long)dst.rows, (long long)dst.cols);
+    check_batch_stride(who, "dst", dbs, from_c<char>(dst), count);
+    if (count > 0) RC_REQUIRE(src.data && dst.data, RC_INVALID_ARGUMENT, "%s: null pointer", who);
+}
 template int64_t check_column_id_rank_batched<double>(Mat<double>, int32_t, int64_t, double, Mat<double>, int64_t, Mat<double>, int64_t, const int64_t *,
                                                       const int64_t *);
 template int64_t check_column_id_rank_batched<float>(Mat<float>, int32_t, int64_t, double, Mat<float>, int64_t, Mat<float>, int64_t, const int64_t *,
@@ -2006,5 +2016,64 @@ rc_status rc_invert_permutation(rc_context *ctx, const int64_t *perm, int64_t n,
 
 RC_DEFINE_TYPED(f64, double)
 RC_DEFINE_TYPED(f32, float)
+
+// f32 storage under f64 arithmetic (kernels_batched_apply.hip, kernels_block_operator.hip): the twins' checks on views of the same shapes
+rc_status rc_lowrank_apply_mixed_batched_f64(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride,
+                                             const double *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks,
+                                             int32_t count, rc_matrix b, int64_t b_batch_stride, rc_matrix y, int64_t y_batch_stride) {
+    return guarded(ctx, [&] {
+        check_lowrank_apply_batched<double>(from_c<double>(left), from_c<double>(mid), from_c<double>(right), count, from_c<double>(b), from_c<double>(y),
+                                            y_batch_stride);
+        if (count == 0) return;
+        batched_lowrank_apply_mixed(ctx, false, left, left_batch_stride, mid, mid_batch_stride, s, s_stride, right, right_batch_stride, ranks, count, b,
+                                    b_batch_stride, y, y_batch_stride);
+    });
+}
+/* conj is ignored: conjugation is the identity on real data */
+rc_status rc_block_operator_apply_mixed_f64(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride,
+                                            const double *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks,
+                                            int32_t count, rc_matrix dense, int64_t dense_batch_stride, int32_t dense_count, const int64_t *group_ptr,
+                                            const int64_t *group_row, int32_t groups, const int64_t *entry_block, const int64_t *entry_col, rc_matrix x,
+                                            rc_matrix y, int32_t accumulate, int32_t conj) {
+    (void)conj;
+    return guarded(ctx, [&] {
+        const BlockPattern pat{group_ptr, group_row, entry_block, entry_col, groups};
+        const BlockShape sh = check_block_operator_apply<double>(from_c<double>(left), from_c<double>(mid), from_c<double>(right), count, from_c<double>(dense),
+                                                                 &dense_count, pat, from_c<double>(x), from_c<double>(y));
+        if (groups == 0) return;
+        block_operator_apply_mixed(ctx, false, left, left_batch_stride, mid, mid_batch_stride, s, s_stride, right, right_batch_stride, ranks, count, dense,
+                                   dense_batch_stride, dense_count, pat, sh, x, y, accumulate != 0, false);
+    });
+}
+rc_status rc_demote_batched_f64(rc_context *ctx, rc_matrix src, int64_t src_batch_stride, int32_t count, rc_matrix dst, int64_t dst_batch_stride,
+                                int64_t *overflow) {
+    return guarded(ctx, [&] {
+        check_convert_batched("demote_batched", src, count, dst, dst_batch_stride);
+        if (count == 0) return;
+        batched_demote(ctx, false, src, src_batch_stride, count, dst, dst_batch_stride, overflow);
+    });
+}
+rc_status rc_promote_batched_f32(rc_context *ctx, rc_matrix src, int64_t src_batch_stride, int32_t count, rc_matrix dst, int64_t dst_batch_stride) {
+    return guarded(ctx, [&] {
+        check_convert_batched("promote_batched", src, count, dst, dst_batch_stride);
+        if (count == 0) return;
+        batched_promote(ctx, false, src, src_batch_stride, count, dst, dst_batch_stride);
+    });
+}
+// The _f32 names of the three stems above are the header's rule that every _f64 entry point has an _f32 one.  They would be f32 arithmetic
+// over 16-bit storage, which this library does not build: declared, exported and always refused, so that a caller finds out at the call.
+static rc_status mixed_f32_not_built(rc_context *ctx, const char *who) {
+    return guarded(ctx, [&] { fail(RC_INVALID_ARGUMENT, "%s: f32 arithmetic over 16-bit storage is not built; the mixed calls are the _f64 and _c64 ones", who); });
+}
+rc_status rc_lowrank_apply_mixed_batched_f32(rc_context *ctx, rc_matrix, int64_t, rc_matrix, int64_t, const float *, int64_t, rc_matrix, int64_t, const int64_t *,
+                                             int32_t, rc_matrix, int64_t, rc_matrix, int64_t) {
+    return mixed_f32_not_built(ctx, "lowrank_apply_mixed_batched_f32");
+}
+rc_status rc_block_operator_apply_mixed_f32(rc_context *ctx, rc_matrix, int64_t, rc_matrix, int64_t, const float *, int64_t, rc_matrix, int64_t, const int64_t *,
+                                            int32_t, rc_matrix, int64_t, int32_t, const int64_t *, const int64_t *, int32_t, const int64_t *, const int64_t *,
+                                            rc_matrix, rc_matrix, int32_t, int32_t) {
+    return mixed_f32_not_built(ctx, "block_operator_apply_mixed_f32");
+}
+rc_status rc_demote_batched_f32(rc_context *ctx, rc_matrix, int64_t, int32_t, rc_matrix, int64_t, int64_t *) { return mixed_f32_not_built(ctx, "demote_batched_f32"); }
 
 }  // extern "C"

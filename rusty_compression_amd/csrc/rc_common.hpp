@@ -264,6 +264,21 @@ template <typename R> void block_operator_apply_c(rc_context *c, const rc_matrix
 // caller returns when pat.groups == 0
 template <typename T> BlockShape check_block_operator_apply(Mat<T> left, Mat<T> mid, Mat<T> right, int32_t count, Mat<T> dense, int32_t *dense_count,
                                                             const BlockPattern &pat, Mat<T> x, Mat<T> y);
+// the mixed-storage forms of the two above (rc_lowrank_apply_mixed_batched_*, rc_block_operator_apply_mixed_*): left, mid and right are views of
+// f32 (c32 when complex_data) data with strides in their own elements, b / dense / x / y are f64 (c64) and s is double; the bits are those of the
+// full-precision call on promoted factors (arguments checked by the caller, on the shapes alone)
+void batched_lowrank_apply_mixed(rc_context *c, bool complex_data, const rc_matrix &left, int64_t lbs, const rc_matrix &mid, int64_t mbs, const double *s,
+                                 int64_t s_stride, const rc_matrix &right, int64_t rbs, const int64_t *ranks, int32_t count, const rc_matrix &b, int64_t bbs,
+                                 const rc_matrix &y, int64_t ybs);
+void block_operator_apply_mixed(rc_context *c, bool complex_data, const rc_matrix &left, int64_t lbs, const rc_matrix &mid, int64_t mbs, const double *s,
+                                int64_t s_stride, const rc_matrix &right, int64_t rbs, const int64_t *ranks, int32_t count, const rc_matrix &dense, int64_t dbs,
+                                int32_t dense_count, const BlockPattern &pat, BlockShape shape, const rc_matrix &x, const rc_matrix &y, bool accumulate, bool conj);
+// strided batched conversion f64 -> f32 (c64 -> c32) and back (kernels_convert.hip): block i is src and dst moved by i times their batch strides;
+// overflow (count device values, nullptr: not counted) receives the finite elements of each block that became non-finite
+void batched_demote(rc_context *c, bool complex_data, const rc_matrix &src, int64_t sbs, int32_t count, const rc_matrix &dst, int64_t dbs, int64_t *overflow);
+void batched_promote(rc_context *c, bool complex_data, const rc_matrix &src, int64_t sbs, int32_t count, const rc_matrix &dst, int64_t dbs);
+// the argument checks of rc_demote_batched_* / rc_promote_batched_* (rc_api.hip); the caller returns when count == 0
+void check_convert_batched(const char *who, const rc_matrix &src, int32_t count, const rc_matrix &dst, int64_t dbs);
 // recompress the factor pairs of such a batch to truncated SVDs without forming the blocks (kernels_batched_id.hip): block i is left (m x K), mid (K x K,
 // p == nullptr: none), right (K x n), u (m x min(k, K)) and vt (min(k, K) x n) each moved by i times its batch stride, s + i * s_stride its K real scales
 // (nullptr: none), in_ranks count device values (nullptr: every inner rank is K); s_out count x K, ranks count (arguments checked by the caller)

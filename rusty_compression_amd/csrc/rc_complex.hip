@@ -1421,4 +1421,46 @@ extern "C" {
 RC_DEFINE_COMPLEX(c64, double, rc_complex64)
 RC_DEFINE_COMPLEX(c32, float, rc_complex32)
 
+// c32 storage under c64 arithmetic (kernels_batched_apply.hip, kernels_block_operator.hip): the twins' checks on views of the same shapes
+rc_status rc_lowrank_apply_mixed_batched_c64(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride,
+                                             const double *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks,
+                                             int32_t count, rc_matrix b, int64_t b_batch_stride, rc_matrix y, int64_t y_batch_stride) {
+    return guarded_c(ctx, [&] {
+        check_lowrank_apply_batched<double>(shape_of<double>(left), shape_of<double>(mid), shape_of<double>(right), count, shape_of<double>(b),
+                                            shape_of<double>(y), y_batch_stride);
+        if (count == 0) return;
+        batched_lowrank_apply_mixed(ctx, true, left, left_batch_stride, mid, mid_batch_stride, s, s_stride, right, right_batch_stride, ranks, count, b,
+                                    b_batch_stride, y, y_batch_stride);
+    });
+}
+rc_status rc_block_operator_apply_mixed_c64(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride,
+                                            const double *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks,
+                                            int32_t count, rc_matrix dense, int64_t dense_batch_stride, int32_t dense_count, const int64_t *group_ptr,
+                                            const int64_t *group_row, int32_t groups, const int64_t *entry_block, const int64_t *entry_col, rc_matrix x,
+                                            rc_matrix y, int32_t accumulate, int32_t conj) {
+    return guarded_c(ctx, [&] {
+        const BlockPattern pat{group_ptr, group_row, entry_block, entry_col, groups};
+        const BlockShape sh = check_block_operator_apply<double>(shape_of<double>(left), shape_of<double>(mid), shape_of<double>(right), count,
+                                                                 shape_of<double>(dense), &dense_count, pat, shape_of<double>(x), shape_of<double>(y));
+        if (groups == 0) return;
+        block_operator_apply_mixed(ctx, true, left, left_batch_stride, mid, mid_batch_stride, s, s_stride, right, right_batch_stride, ranks, count, dense,
+                                   dense_batch_stride, dense_count, pat, sh, x, y, accumulate != 0, conj != 0);
+    });
+}
+rc_status rc_demote_batched_c64(rc_context *ctx, rc_matrix src, int64_t src_batch_stride, int32_t count, rc_matrix dst, int64_t dst_batch_stride,
+                                int64_t *overflow) {
+    return guarded_c(ctx, [&] {
+        check_convert_batched("demote_batched", src, count, dst, dst_batch_stride);
+        if (count == 0) return;
+        batched_demote(ctx, true, src, src_batch_stride, count, dst, dst_batch_stride, overflow);
+    });
+}
+rc_status rc_promote_batched_c32(rc_context *ctx, rc_matrix src, int64_t src_batch_stride, int32_t count, rc_matrix dst, int64_t dst_batch_stride) {
+    return guarded_c(ctx, [&] {
+        check_convert_batched("promote_batched", src, count, dst, dst_batch_stride);
+        if (count == 0) return;
+        batched_promote(ctx, true, src, src_batch_stride, count, dst, dst_batch_stride);
+    });
+}
+
 }  // extern "C"

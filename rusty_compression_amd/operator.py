@@ -209,6 +209,37 @@ class BlockLowRankOperator(Operator):
         return self._adj.apply(x, rows=self._shape[1], conj=self._conj)
 
 
+class MixedBlockLowRankOperator(BlockLowRankOperator):
+    """BlockLowRankOperator with the low-rank factors kept in storage precision: left, mid and right are float32 (complex64), dense is
+    float64 (complex128) and so are dtype, x and y; s is float64.  Each product is one launch of rc_block_operator_apply_mixed_*, which
+    widens a factor element as it is loaded and otherwise runs the full-precision arithmetic: matmat, conj_matmat and the raw forms
+    return the bits of the BlockLowRankOperator built from batch.promote_batched copies of the factors, and read half the factor bytes.
+    The constructor, the pattern rules and the products are BlockLowRankOperator's."""
+
+    def __init__(self, shape, rows, cols, block_ids, left=None, right=None, mid=None, s=None, ranks=None, dense=None):
+        from .batch import _MixedBlockOperatorCall, block_csr
+
+        who = "MixedBlockLowRankOperator"
+        if mid is not None and s is not None:
+            raise AssertionError(f"{who}: mid and s together do not transpose into the kernel's chain; fold s into mid or right")
+        self._shape = (int(shape[0]), int(shape[1]))
+        by_row, by_col = block_csr(rows, cols, block_ids)
+        self._fwd = _MixedBlockOperatorCall(who, by_row, left, right, mid, s, ranks, dense)
+        f = self._fwd
+        t = lambda v: None if v is None else v.transpose(1, 2)  # noqa: E731
+        self._adj = _MixedBlockOperatorCall(who, by_col, t(f.right), t(f.left), t(f.mid), f.s, f.ranks, t(f.dense))
+        self.dtype = f.dtype
+        self._conj = self.dtype.is_complex
+        if self._shape[0] < f.m or self._shape[1] < f.n:
+            raise AssertionError(f"{who}: shape {self._shape} is smaller than one {f.m} x {f.n} block")
+
+        def covered(heads, extent, total):  # do the groups' row ranges tile [0, total)?
+            heads = sorted(int(h) for h in heads)
+            return bool(heads) and heads[0] == 0 and heads[-1] + extent == total and all(b - a == extent for a, b in zip(heads, heads[1:]))
+
+        self._covered = (covered(by_row[1], f.m, self._shape[0]), covered(by_col[1], f.n, self._shape[1]))
+
+
 def is_operator(op) -> bool:
     return not isinstance(op, torch.Tensor) and all(hasattr(op, f) for f in ("nrows", "ncols", "matmat"))
 

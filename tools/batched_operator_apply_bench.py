@@ -16,7 +16,13 @@ The mixed case replaces 10 % of the entries by dense blocks (one torch.bmm more 
 factor and dense block once, the x segment of every entry, y once; the fraction is of the 6.29 TB/s a float4 copy reaches on the
 MI355X.  The plan label of the launch (tile width, grid, slots) is read from the event profile.  Writes profiles/batched_operator_apply_bench.json unless --out names another file.  Not used by the tests or by bench.py.
 
-    python tools/batched_operator_apply_bench.py [--repeats 5] [--cases 0,1,2,3,4] [--out path.json]
+--mixed measures the mixed-storage operator instead (rc_block_operator_apply_mixed_f64 / _c64: low-rank factors kept in f32 / c32,
+dense blocks, x and y in full precision) on cases 0, 1, 3 and 4: the factors are demoted and promoted back, and the full-precision call
+on the promoted factors (the yardstick: this library's unchanged kernel) and the mixed call on the stored ones are timed in the same
+process by the same method and checked to give the same bits.  Bytes as above with the factor elements at their stored size.  Writes
+profiles/batched_operator_apply_mixed_bench.json.
+
+    python tools/batched_operator_apply_bench.py [--repeats 5] [--cases 0,1,2,3,4] [--out path.json] [--mixed]
 """
 import argparse
 import json
@@ -55,14 +61,75 @@ def randn(shape, dtype, gen):
     return torch.randn(shape, generator=gen, device="cuda", dtype=dtype)
 
 
+def main_mixed(args):
+    out_path = args.out or os.path.join(ROOT, "profiles", "batched_operator_apply_mixed_bench.json")
+    results = []
+    for ci in [int(v) for v in (args.cases or "0,1,3,4").split(",")]:
+        groups, per, mn, k, nrhs, dtype, share = CASES[ci]
+        m = n = mn
+        gen = torch.Generator(device="cuda").manual_seed(100 + ci)
+        total = groups * per
+        g_of, j_of = np.repeat(np.arange(groups), per), np.tile(np.arange(per), groups)
+        rows, cols = g_of * m, ((g_of + j_of * 7) % groups) * n
+        is_dense = np.zeros(total, dtype=bool)
+        if share > 0:
+            is_dense[np.random.default_rng(ci).choice(total, int(total * share), replace=False)] = True
+        count, dcount = int((~is_dense).sum()), int(is_dense.sum())
+        ids = np.empty(total, dtype=np.int64)
+        ids[~is_dense], ids[is_dense] = np.arange(count), count + np.arange(dcount)
+        low = [rc.demote_batched(randn((count, m, k), dtype, gen) / k ** 0.5), rc.demote_batched(randn((count, k, n), dtype, gen) / n ** 0.5)]
+        up = [rc.promote_batched(v) for v in low]
+        dense = randn((dcount, m, n), dtype, gen) / n ** 0.5 if dcount else None
+        x = randn((groups * n, nrhs), dtype, gen)
+        y_full, y_mixed = (torch.zeros((groups * m, nrhs), dtype=dtype, device="cuda") for _ in range(2))
+        pattern, _ = rc.block_csr(rows, cols, ids)
+        dev_pattern = tuple(torch.from_numpy(v).cuda() for v in pattern)
+
+        def full():
+            rc.block_operator_apply(x, *dev_pattern, left=up[0], right=up[1], dense=dense, y=y_full)
+
+        def mixed():
+            rc.block_operator_apply_mixed(x, *dev_pattern, left=low[0], right=low[1], dense=dense, y=y_mixed)
+
+        full()
+        _, label = batched_launch(mixed)  # warm-up, and the plan, grid and slots of the launch from the event profile
+        torch.cuda.synchronize()
+        same = bool(torch.equal(y_full, y_mixed))
+        es, ss = up[0].element_size(), low[0].element_size()
+        other = es * (dcount * m * n + total * n * nrhs + groups * m * nrhs)
+        bytes_full, bytes_mixed = es * count * (m * k + k * n) + other, ss * count * (m * k + k * n) + other
+        # full, mixed, full again: the second full run shows how far the yardstick itself moves between two measurements
+        t_full, t_mixed, t_again = timed(full, args.repeats), timed(mixed, args.repeats), timed(full, args.repeats)
+        row = dict(case=ci, groups=groups, entries_per_group=per, m=m, n=n, k=k, nrhs=nrhs, dtype=str(dtype).replace("torch.", ""),
+                   storage=str(low[0].dtype).replace("torch.", ""), dense_entries=dcount, op=label["op"], plan=label["plan"], grid=label["grid"],
+                   slots=label["slots"], bit_equal=same,
+                   full=dict(seconds=t_full[0], min=t_full[1], max=t_full[2], again=t_again[0], bytes=bytes_full, blocks_per_s=total / t_full[0],
+                             share_of_copy_bandwidth=bytes_full / t_full[0] / COPY_BW),
+                   mixed=dict(seconds=t_mixed[0], min=t_mixed[1], max=t_mixed[2], bytes=bytes_mixed, blocks_per_s=total / t_mixed[0],
+                              share_of_copy_bandwidth=bytes_mixed / t_mixed[0] / COPY_BW),
+                   bytes_ratio=bytes_full / bytes_mixed, speedup=t_full[0] / t_mixed[0])
+        print(json.dumps(row), flush=True)
+        results.append(row)
+        del low, up, dense, x, y_full, y_mixed
+        torch.cuda.empty_cache()
+    with open(out_path, "w") as f:
+        json.dump(dict(tool="tools/batched_operator_apply_bench.py --mixed", device=torch.cuda.get_device_name(0), repeats=args.repeats,
+                       copy_bandwidth=COPY_BW, cases=results), f, indent=1)
+        f.write("\n")
+    print("wrote", out_path)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--cases", default=None)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--mixed", action="store_true", help="time the mixed-storage operator against the full-precision call on promoted factors")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("needs an MI355X")
+    if args.mixed:
+        return main_mixed(args)
     out_path = args.out or os.path.join(ROOT, "profiles", "batched_operator_apply_bench.json")
     results = []
     for ci in [int(v) for v in (args.cases or ",".join(str(i) for i in range(len(CASES)))).split(",")]:
