@@ -723,22 +723,41 @@ template <> struct RecompressApi<double> { using tol_type = double; static const
 template <> struct RecompressApi<float> { using tol_type = double; static constexpr auto lowrank_recompress_batched = rc_lowrank_recompress_batched_f32; };
 template <> struct RecompressApi<c64> { using tol_type = double; static constexpr auto lowrank_recompress_batched = rc_lowrank_recompress_complex_batched_c64; };
 template <> struct RecompressApi<c32> { using tol_type = float; static constexpr auto lowrank_recompress_batched = rc_lowrank_recompress_complex_batched_c32; };
-template <typename T>
-BatchedSVD<T> recompress_batched(const DeviceMatrix<T> &left, const DeviceMatrix<T> *mid, const DeviceBuffer<typename Scalar<T>::real> *s,
-                                 const DeviceMatrix<T> &right, const DeviceIndex *ranks, int32_t count, int64_t k, double tol = 0.0) {
+// the real pair for a tall left factor (m <= 65536): rc_lowrank_recompress_tall_batched_*, the same signature and contract
+template <typename T> struct RecompressTallApi;
+template <> struct RecompressTallApi<double> { static constexpr auto lowrank_recompress_batched = rc_lowrank_recompress_tall_batched_f64; };
+template <> struct RecompressTallApi<float> { static constexpr auto lowrank_recompress_batched = rc_lowrank_recompress_tall_batched_f32; };
+// the call both recompress_batched and recompress_tall_batched make, on the entry point `fn` of their dispatch
+template <typename T, typename Tol, typename Fn>
+BatchedSVD<T> recompress_batched_through(Fn fn, const DeviceMatrix<T> &left, const DeviceMatrix<T> *mid, const DeviceBuffer<typename Scalar<T>::real> *s,
+                                         const DeviceMatrix<T> &right, const DeviceIndex *ranks, int32_t count, int64_t k, double tol) {
     const Context &ctx = left.ctx();
     const int64_t m = count > 0 ? left.nrows() / count : 0, kin = left.ncols(), n = right.ncols();
     const int64_t kk = k < kin ? k : kin, p = s && count > 0 ? (int64_t)(s->size() / (std::size_t)count) : 0;
     BatchedSVD<T> out{DeviceMatrix<T>(ctx, (int64_t)count * m, kk), DeviceBuffer<typename Scalar<T>::real>(ctx, (std::size_t)count * (std::size_t)kin),
                       DeviceMatrix<T>(ctx, (int64_t)count * kk, n), DeviceIndex(ctx, (std::size_t)count)};
     const rc_matrix none{nullptr, 0, 0, 0, 0};
-    ctx.check(RecompressApi<T>::lowrank_recompress_batched(ctx.raw(), rc_matrix{left.view().data, m, kin, kin, 1}, m * kin,
-                                                           mid ? rc_matrix{mid->view().data, kin, kin, kin, 1} : none, kin * kin,
-                                                           s ? s->data() : nullptr, p, rc_matrix{right.view().data, kin, n, n, 1}, kin * n,
-                                                           ranks ? ranks->data() : nullptr, count, k, (typename RecompressApi<T>::tol_type)tol,
-                                                           rc_matrix{out.u.view().data, m, kk, kk, 1},
-                                                           m * kk, out.s.data(), rc_matrix{out.vt.view().data, kk, n, n, 1}, kk * n, out.ranks.data()));
+    ctx.check(fn(ctx.raw(), rc_matrix{left.view().data, m, kin, kin, 1}, m * kin, mid ? rc_matrix{mid->view().data, kin, kin, kin, 1} : none, kin * kin,
+                 s ? s->data() : nullptr, p, rc_matrix{right.view().data, kin, n, n, 1}, kin * n, ranks ? ranks->data() : nullptr, count, k, (Tol)tol,
+                 rc_matrix{out.u.view().data, m, kk, kk, 1}, m * kk, out.s.data(), rc_matrix{out.vt.view().data, kk, n, n, 1}, kk * n, out.ranks.data()));
     return out;
+}
+template <typename T>
+BatchedSVD<T> recompress_batched(const DeviceMatrix<T> &left, const DeviceMatrix<T> *mid, const DeviceBuffer<typename Scalar<T>::real> *s,
+                                 const DeviceMatrix<T> &right, const DeviceIndex *ranks, int32_t count, int64_t k, double tol = 0.0) {
+    return recompress_batched_through<T, typename RecompressApi<T>::tol_type>(RecompressApi<T>::lowrank_recompress_batched, left, mid, s, right, ranks, count, k,
+                                                                              tol);
+}
+// the same for factor pairs whose left factor is tall (m <= 65536, n <= 512; double and float): the SVD end of sketch_column_id_rank_batched.
+// For m <= 512 the result is recompress_batched's bit for bit.
+template <typename T>
+BatchedSVD<T> recompress_tall_batched(const DeviceMatrix<T> &left, const DeviceMatrix<T> *mid, const DeviceBuffer<typename Scalar<T>::real> *s,
+                                      const DeviceMatrix<T> &right, const DeviceIndex *ranks, int32_t count, int64_t k, double tol = 0.0) {
+    return recompress_batched_through<T, double>(RecompressTallApi<T>::lowrank_recompress_batched, left, mid, s, right, ranks, count, k, tol);
+}
+template <typename T>
+BatchedSVD<T> recompress_tall_batched(const BatchedColumnID<T> &id, int64_t k, double tol = 0.0) {
+    return recompress_tall_batched<T>(id.c, nullptr, nullptr, id.z, &id.ranks, (int32_t)id.ranks.size(), k, tol);
 }
 // a batched column ID, a batched two-sided ID as truncated SVDs, each block from its own rank
 template <typename T>

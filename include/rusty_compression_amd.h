@@ -600,6 +600,31 @@ rc_status rc_lowrank_apply_batched_c32(rc_context *ctx, rc_matrix left, int64_t 
  * synchronisation; workspace bounded by the grid, not by count. */
 rc_status rc_lowrank_recompress_batched_f64(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const double *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *in_ranks, int32_t count, int64_t k, double tol, rc_matrix u, int64_t u_batch_stride, double *s_out, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks);
 rc_status rc_lowrank_recompress_batched_f32(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const float *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *in_ranks, int32_t count, int64_t k, double tol, rc_matrix u, int64_t u_batch_stride, float *s_out, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks);
+/* The same recompression for factor pairs whose left factor is tall: rc_lowrank_recompress_batched_f64 / _f32's signature argument for
+ * argument and its per-block contract sentence for sentence (q, s_out, the rank rule, zero tails, exact zeros, q = 0, NaN containment, health
+ * bit 16, no host synchronisation, capturable), with the sign rule taken over all m rows of each kept column of u.  This is the SVD end of
+ * rc_sketch_column_id_rank_batched_*: its c (m x kk), z and ranks go in as left, right and in_ranks.
+ * Domain: 1 <= m <= 65536, 1 <= n <= 512, 1 <= K <= 128, K <= min(m, n), k >= 1, 0 <= tol < 1, count >= 0; the checks, status codes and
+ * messages are the pair's above under the name lowrank_recompress_tall_batched.  These two are the real scalars; complex factors are out of
+ * scope, and rc_lowrank_recompress_tall_batched_c64 / _c32 do not exist.
+ * Per block: left[:, :q] is factored by a flat Householder TSQR inside the one workgroup that owns the block.  Stage 0 is the pivoted QR of
+ * rows 0 .. min(m, 512) - 1; every later stage stacks the q x q triangle of the stage before on the next 512 - q rows of left, columns in the
+ * pivot order so far, and runs the same q pivoted steps (so an exactly zero column of left stays exactly zero to the end).  The last triangle
+ * and the cumulative permutation enter the core; right, the core, the Jacobi iteration, the sort and the rank rule are those of the call above.
+ * u is formed by carrying each kept column back through the stages' stored reflectors, chunk of rows by chunk of rows.
+ * Bits: as above (operands, their row and column strides and the call's shapes alone); they equal the bits of the truncated factors passed as
+ * a call of inner width q, and for m <= 512 every output equals rc_lowrank_recompress_batched_*'s on the same arguments bit for bit.
+ * Workspace: a workgroup's slot holds every stage's factored copy, 1 + ceil((m - 512) / (512 - K)) stages of (512 K + 2 K) elements for
+ * m > 512, about 90 MiB at m = 65536, K = 128 in f64.  The grid is bounded so that all slots stay at or below 2 GiB (never below one
+ * workgroup), so very tall, wide-K blocks run on few workgroups; rc_lowrank_recompress_tall_batched_plan reports the numbers.
+ * Wide blocks (a tall right factor) are A^T: call with right^T, mid^T and left^T as strided views (rows and strides swapped, no copy) in the
+ * places of left, mid and right, and pass vt^T as u and u^T as vt.  The sign rule then holds on the columns of V. */
+rc_status rc_lowrank_recompress_tall_batched_f64(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const double *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *in_ranks, int32_t count, int64_t k, double tol, rc_matrix u, int64_t u_batch_stride, double *s_out, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks);
+rc_status rc_lowrank_recompress_tall_batched_f32(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const float *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *in_ranks, int32_t count, int64_t k, double tol, rc_matrix u, int64_t u_batch_stride, float *s_out, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks);
+/* The plan of that call as numbers, host arithmetic only (no context, no device): for blocks of m x n with inner width `inner` and
+ * elements of elem_bytes (8: f64, 4: f32), *stages = the stages of a block of full inner rank, *slot_bytes = one workgroup's workspace slot,
+ * *grid = what the 2 GiB bound leaves of `resident` workgroups.  RC_INVALID_ARGUMENT outside the call's domain or for a null output. */
+rc_status rc_lowrank_recompress_tall_batched_plan(int64_t m, int64_t n, int64_t inner, int32_t elem_bytes, int64_t resident, int64_t *stages, int64_t *slot_bytes, int64_t *grid);
 /* The same call for complex factors (c64, c32): rc_lowrank_recompress_batched_f64's signature argument for argument and its contract, domain,
  * checks and error messages, with interleaved (re, im) data and every stride and batch stride in complex elements.  s, s_out and tol have the
  * real type of the data (double for c64, float for c32): s scales the columns of mid by real numbers, and singular values are real.

@@ -564,8 +564,9 @@ def block_operator_apply_mixed(x: torch.Tensor, group_ptr, group_row, entry_bloc
     return call.apply(x, y=y, rows=rows, accumulate=accumulate, conj=conj)
 
 
-def _lowrank_recompress_batched(who: str, complex_data: bool, left, right, k, tol, mid, s, ranks):
-    """The shared body of lowrank_recompress_batched (real dtypes) and lowrank_recompress_batched_complex (complex dtypes, real s and S)."""
+def _lowrank_recompress_batched(who: str, complex_data: bool, left, right, k, tol, mid, s, ranks, tall: bool = False):
+    """The shared body of lowrank_recompress_batched, lowrank_recompress_tall_batched (real dtypes; tall: the entry points for m <= 65536) and
+    lowrank_recompress_batched_complex (complex dtypes, real s and S)."""
     from . import _lib
     from .types import as_device
 
@@ -617,7 +618,7 @@ def _lowrank_recompress_batched(who: str, complex_data: bool, left, right, k, to
         return _lib.rc_matrix(t.data_ptr(), t.shape[1], t.shape[2], t.stride(1), t.stride(2)), ctypes.c_int64(t.stride(0))
 
     # the complex entry points spell their stem differently (see the header) and take tol in the real type of the data
-    stem = "rc_lowrank_recompress_complex_batched_" if complex_data else "rc_lowrank_recompress_batched_"
+    stem = "rc_lowrank_recompress_complex_batched_" if complex_data else "rc_lowrank_recompress_tall_batched_" if tall else "rc_lowrank_recompress_batched_"
     tol_arg = ctypes.c_float(float(tol)) if left.dtype == torch.complex64 else ctypes.c_double(float(tol))
     _lib.default_context().call(stem + _lib.suffix(left.dtype), *view(left), *view(mid),
                                 ctypes.c_void_p(s.data_ptr() if s is not None else None), ctypes.c_int64(s.stride(0) if s is not None else 0),
@@ -680,6 +681,41 @@ def svd_add_batched(u1: torch.Tensor, s1: torch.Tensor, vt1: torch.Tensor, u2: t
     right = torch.cat([vt1, vt2], dim=1)
     s = torch.cat([s1[:, :k1], s2[:, :k2]], dim=1)
     return lowrank_recompress_batched(left, right, k, tol, s=s)
+
+
+def lowrank_recompress_tall_batched(left: torch.Tensor, right: torch.Tensor, k: int, tol: float = 0.0, mid: Optional[torch.Tensor] = None,
+                                    s: Optional[torch.Tensor] = None,
+                                    ranks: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Recompress every factor pair of a batch whose left factor is tall to a truncated SVD without forming the blocks, in one
+    stream-ordered call (rc_lowrank_recompress_tall_batched_*): lowrank_recompress_batched's scheme with the left factor taken through a
+    flat Householder TSQR in stages of 512 rows inside the launch.
+
+    left: [count, m, K], right: [count, K, n], mid: [count, K, K] or None, s: [count, p >= K] or None, ranks: [count] int64 or None
+    (every inner rank is K); float64 or float32 device tensors, any strides (a stride-0 batch dimension shares one operand);
+    K <= min(m, n), K <= 128, m <= 65536, n <= 512.  With q = ranks[i] clamped to [0, K], block i is A_i = left[i][:, :q] mid[i][:q, :q]
+    diag(s[i][:q]) right[i][:q] (absent factors omitted; nothing at an index >= q is read).  Returns U [count, m, kk], S [count, K]
+    (the q singular values of A_i, descending, then zeros), Vt [count, kk, n] and the new ranks [count], kk = min(k, K): the rank of a
+    block is the first j < min(kk, q) with s_j == 0 or s_j / s_0 < tol, else min(kk, q); columns of U and rows of Vt past it are zero
+    and the largest-|.| entry of each kept column of U, over all m rows, is positive.  For m <= 512 the outputs are
+    lowrank_recompress_batched's bit for bit.  A wide pair (tall right) is the transpose: pass right.mT, mid.mT, left.mT and swap
+    U.mT / Vt.mT.  Complex data raises TypeError (complex tall factors are not supported)."""
+    return _lowrank_recompress_batched("lowrank_recompress_tall_batched", False, left, right, k, tol, mid, s, ranks, tall=True)
+
+
+def column_id_to_svd_tall_batched(c: torch.Tensor, z: torch.Tensor, ranks: Optional[torch.Tensor], k: int,
+                                  tol: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Truncated SVDs of the tall blocks C[:, :r] Z[:r] held by the outputs of sketch_column_id_rank_batched, each at its own rank."""
+    return lowrank_recompress_tall_batched(c, z, k, tol, ranks=ranks)
+
+
+def svd_add_tall_batched(u1: torch.Tensor, s1: torch.Tensor, vt1: torch.Tensor, u2: torch.Tensor, s2: torch.Tensor, vt2: torch.Tensor, k: int,
+                         tol: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """svd_add_batched for tall blocks (m <= 65536): the rounded sum of two batches of truncated SVDs through lowrank_recompress_tall_batched."""
+    k1, k2 = u1.shape[2], u2.shape[2]
+    left = torch.cat([u1, u2], dim=2)
+    right = torch.cat([vt1, vt2], dim=1)
+    s = torch.cat([s1[:, :k1], s2[:, :k2]], dim=1)
+    return lowrank_recompress_tall_batched(left, right, k, tol, s=s)
 
 
 def column_id_to_svd_batched_complex(c: torch.Tensor, z: torch.Tensor, ranks: Optional[torch.Tensor], k: int,
@@ -874,6 +910,16 @@ def sketch_column_id_rank_batched(a: torch.Tensor, k: int, tol: float = 0.0, ome
     for j below the block's rank, the rest of C and Z zero.  Complex data (see sketch_column_id_rank_batched_complex) and mismatched
     dtypes raise TypeError."""
     return _sketch_column_id_rank_batched("sketch_column_id_rank_batched", False, a, k, tol, omega, oversampling, seed, return_sketch)
+
+
+def sketch_svd_rank_batched(a: torch.Tensor, k: int, tol: float = 0.0, omega: Optional[torch.Tensor] = None, oversampling: int = 8,
+                            seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Batched randomized SVDs of `count` tall same-shaped blocks (m <= 65536, n <= 512): the reference's sketch -> factor the small matrix ->
+    SVD path in two launches with no host synchronisation between them, sketch_column_id_rank_batched(a, k, tol, omega, oversampling, seed)
+    followed by column_id_to_svd_tall_batched on its (C, Z, ranks).  Returns (U [count, m, kk], S [count, kk], Vt [count, kk, n], ranks),
+    kk = min(k, l, n): the truncated SVD of each block's one-pass column ID C Z, bit for bit that of the two calls made by hand."""
+    c, z, _, ranks = sketch_column_id_rank_batched(a, k, tol, omega, oversampling, seed)
+    return column_id_to_svd_tall_batched(c, z, ranks, k, tol)
 
 
 def sketch_column_id_rank_batched_complex(a: torch.Tensor, k: int, tol: float = 0.0, omega: Optional[torch.Tensor] = None, oversampling: int = 8,

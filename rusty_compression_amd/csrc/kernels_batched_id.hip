@@ -23,6 +23,9 @@
 // Batched recompression (rc_lowrank_recompress_batched_*): k_batched_recompress, the same grid and stages on the two thin factors of
 // a low-rank block, the same Jacobi on their small core, both Q's applied by the same reflector routine (see its comment below).
 //
+// Tall left factors (rc_lowrank_recompress_tall_batched_*, m <= 65536): k_batched_recompress<T, true>, the same kernel text with the left
+// factor taken through a flat Householder TSQR in stages of 512 rows kept in the workgroup's slot (see "tall left factors" below).
+//
 // Batched sketched column ID (rc_sketch_column_id_rank_batched_*): k_batched_sketch_id, the same grid; the working copy is the sketch
 // Omega A (l x n, l <= 128) formed by MFMA while A streams through LDS once, then the same stages on l rows (see its comment below).
 //
@@ -685,19 +688,167 @@ __host__ __device__ inline size_t brc_ws_elems(int m, int n, int K, bool l_lds, 
     return (l_lds ? 0 : (size_t)m * K) + (r_lds ? 0 : (size_t)n * K) + (v_lds ? 0 : (size_t)K * K);
 }
 
+// ---- tall left factors (rc_lowrank_recompress_tall_batched_*, m <= 65536) ----------------------------------------------------------
+// left[:, :q] is factored by a flat Householder TSQR with stored reflectors, still inside one workgroup.  Stage 0 is the factorization
+// above on rows 0 .. min(m, H) - 1, H = BRT_H = 512 rows (what bid_qrcp and bsv_reflect_back<T, 8> hold).  Stage s >= 1 factors a stack:
+// the upper triangle of the previous stage's R (q rows, zeros below the diagonal) on top of the next min(H - q, rows left) rows of left,
+// the columns in the cumulative pivot order, by the same q pivoted steps; an exactly zero column of left is an exactly zero column of every
+// stack, so it stays a step with H = I and a zero row of the last R.  A stack's column for the factor's column c is stored at physical
+// column c, and jp (position -> physical column) is carried from stage to stage instead of being reset: after the last stage it is the
+// cumulative permutation, and (the last stage's copy, jp) stand where (Wl, jpl) stand in the core products.  The stage height depends on
+// q, not on K: a block's bits are those of a call of inner width q.  Every stage's factored copy, taus and pivots stay in the
+// workgroup's workspace slot (brt_stage_elems each) for the backward pass, brt_form_u.  m <= H is one stage and the kernel above.
+constexpr int BRT_H = 512;
+__host__ __device__ inline int brt_stages(int m, int q) { return m <= BRT_H ? 1 : 1 + (m - BRT_H + (BRT_H - q) - 1) / (BRT_H - q); }
+// one stage in the slot: the copy (H x K, pitch H), taus[K], pivots[K] (ints in elements of T)
+__host__ __device__ inline size_t brt_stage_elems(int K) { return (size_t)BRT_H * K + 2 * (size_t)K; }
+// the slot: the stage copies of the widest inner rank first (m > H; brc_ws_elems' copy of left otherwise), then brc_ws_elems' other parts
+__host__ __device__ inline size_t brt_ws_elems(int m, int n, int K, bool l_lds, bool r_lds, bool v_lds) {
+    if (m <= BRT_H) return brc_ws_elems(m, n, K, l_lds, r_lds, v_lds);
+    return (size_t)brt_stages(m, K) * brt_stage_elems(K) + brc_ws_elems(0, n, K, true, r_lds, v_lds);
+}
+
+// one stage's stack into W (pitch ldw, hs rows): rows 0 .. top - 1 of position p's column are R[0 .. p, p] of the previous stage's copy Wp
+// (the same pitch and physical columns) and zeros, rows top .. hs - 1 are at(i - top, c); then the column norms by position (bid_norms'
+// sums) with jp kept as it is.  top == 0 (stage 0): Wp is not read.
+template <typename T, typename At>
+__device__ __forceinline__ void brt_stack_load(T *W, int ldw, const T *Wp, int top, int hs, int q, bool lanes_on_rows, At at, T *vn1, T *vn2, const int *jp,
+                                               int wv, int lane) {
+    if (top) {
+        for (int p = wv; p < q; p += BID_WAVES) {
+            const size_t col = (size_t)jp[p] * ldw;
+            for (int i = lane; i < top; i += 64) W[col + i] = i <= p ? Wp[col + i] : (T)0;
+        }
+    }
+    const int rows = hs - top;
+    if (lanes_on_rows) {
+        for (int c = wv; c < q; c += BID_WAVES)
+            for (int i = lane; i < rows; i += 64) W[(size_t)c * ldw + top + i] = at(i, c);
+    } else {
+        for (int i = wv; i < rows; i += BID_WAVES)
+            for (int c = lane; c < q; c += 64) W[(size_t)c * ldw + top + i] = at(i, c);
+    }
+    __syncthreads();
+    for (int p = wv; p < q; p += BID_WAVES) {
+        const T *col = W + (size_t)jp[p] * ldw;
+        T acc = 0;
+        for (int i = lane; i < hs; i += 64) { const T v = col[i]; acc += v * v; }
+        acc = wave_sum_dpp(acc);
+        if (lane == 0) { const T nr = sqrt(acc); vn1[p] = nr; vn2[p] = nr; }
+    }
+    __syncthreads();
+}
+
+// x <- H_0 .. H_{N-1} x for a column held by one wave (row lane + 64 e in x[e], M rows): bsv_form_u's reflector loop as a routine of its
+// own, for a column that goes through several factorizations (bsv_form_u keeps its loop: sharing this one changed k_batched_svd's stream)
+template <typename T, int NE>
+__device__ __forceinline__ void bsv_reflect_back(const T *W, int ldw, int M, int N, const int *jp, const T *taus, T (&x)[NE], int lane) {
+    for (int j = N - 1; j >= 0; --j) {
+        const T tau = taus[j];
+        if (tau == (T)0) continue;  // H_j = I (uniform)
+        const T *vc = W + (size_t)jp[j] * ldw;
+        T v[NE];
+        T dot = 0;
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            const int i = lane + 64 * e;
+            const T vv = vc[i < M ? i : j];  // branch-free: lanes out of range read row j and are masked below
+            v[e] = i > j && i < M ? vv : (i == j ? (T)1 : (T)0);
+            dot = fma(v[e], x[e], dot);
+        }
+        const T f = tau * wave_sum_dpp(dot);
+#pragma unroll
+        for (int e = 0; e < NE; ++e) x[e] = fma(-f, v[e], x[e]);
+    }
+}
+
+// U[:, c] = sgn[c] Q_0 [Q_1 [.. Q_{S-1} [J[:, srt[c]]; 0] ..; 0]; 0] for S >= 2 stages at stage0 + s * se: one wave per column carries x (q
+// values) down the stages.  Stage s >= 1 applies its reflectors to [x; 0] (H rows in registers); rows q .. of the result are that chunk's
+// rows of u, rows 0 .. q - 1 replace x; stage 0's result fills rows 0 .. H - 1.  The sign rule runs over all m rows: per chunk the
+// largest |.| and its first row (bsv_sign's key), the larger magnitude wins and on a tie the smaller row, which is the later chunk seen.
+// Stage 0's rows are written with the final sign; the wave then negates the rows it wrote before, each lane its own addresses.
 template <typename T>
+__device__ __forceinline__ void brt_form_u(const T *stage0, size_t se, int S, int K, int q, int m, const T *J, int ldj, int k, int r, const int *srt, int *sgn,
+                                           T *U, int64_t urs, int64_t ucs, int wv, int lane) {
+    constexpr int NE = BRT_H / 64;
+    for (int c = wv; c < k; c += BID_WAVES) {
+        T *uc = U + (int64_t)c * ucs;
+        if (c >= r) {
+            for (int i = lane; i < m; i += 64) uc[i * urs] = (T)0;
+            continue;
+        }
+        const T *jc = J + (size_t)srt[c] * ldj;
+        T x[NE];
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            const int i = lane + 64 * e;
+            x[e] = i < q ? jc[i] : (T)0;
+        }
+        T best = (T)-1;
+        int bkey = 0x7fffffff;
+        for (int s = S - 1; s >= 0; --s) {
+            const T *Ws = stage0 + (size_t)s * se, *ts = Ws + (size_t)BRT_H * K;
+            const int top = s ? q : 0, base = s ? BRT_H + (s - 1) * (BRT_H - q) : 0;
+            const int hs = top + min(BRT_H - top, m - base);
+            bsv_reflect_back<T, NE>(Ws, BRT_H, hs, q, reinterpret_cast<const int *>(ts + K), ts, x, lane);
+            T mx = 0;
+#pragma unroll
+            for (int e = 0; e < NE; ++e) {
+                const int i = lane + 64 * e;
+                if (i >= top && i < hs) mx = max(mx, fabs(x[e]));
+            }
+            mx = wave_max_dpp(mx);
+            int key = 0x7fffffff;
+#pragma unroll
+            for (int e = 0; e < NE; ++e) {
+                const int i = lane + 64 * e;
+                if (i >= top && i < hs && fabs(x[e]) == mx) key = min(key, 2 * (base + i - top) + (x[e] < (T)0 ? 1 : 0));
+            }
+            key = wave_min_dpp(key);
+            if (key != 0x7fffffff && mx >= best) { best = mx; bkey = key; }  // this chunk's rows precede every chunk seen so far
+            if (s) {
+#pragma unroll
+                for (int e = 0; e < NE; ++e) {
+                    const int i = lane + 64 * e;
+                    if (i >= top && i < hs) uc[(int64_t)(base + i - top) * urs] = x[e];
+                    x[e] = i < top ? x[e] : (T)0;
+                }
+            }
+        }
+        const bool neg = bkey != 0x7fffffff && (bkey & 1);
+        if (lane == 0) sgn[c] = neg ? -1 : 1;
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            const int i = lane + 64 * e;
+            uc[(int64_t)i * urs] = neg ? -x[e] : x[e];  // stage 0 of S >= 2 stages holds H rows
+        }
+        if (neg) {
+            for (int s = 1; s < S; ++s) {
+                const int base = BRT_H + (s - 1) * (BRT_H - q), rows = min(BRT_H - q, m - base);
+                for (int i = lane; i < rows; i += 64) {
+                    T *p = uc + (int64_t)(base + i) * urs;
+                    *p = -*p;
+                }
+            }
+        }
+    }
+}
+
+// TALL = false: rc_lowrank_recompress_batched_*.  TALL = true: rc_lowrank_recompress_tall_batched_*, the left factor by stages (see above)
+template <typename T, bool TALL>
 __global__ __launch_bounds__(BID_THREADS) void k_batched_recompress(BrcArgs<T> a) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int m = (int)a.left.rows, n = (int)a.right.cols, K = (int)a.left.cols;
     const int kk = a.k < K ? a.k : K, ldg = a.ldg;
-    const int ldl = a.l_lds ? (m | 1) : m, ldr = a.r_lds ? (n | 1) : n, ldj = a.v_lds ? ldg : K;
+    const bool multi = TALL && m > BRT_H;  // the plan keeps the stage copies out of LDS
+    const int ldl = multi ? BRT_H : a.l_lds ? (m | 1) : m, ldr = a.r_lds ? (n | 1) : n, ldj = a.v_lds ? ldg : K;
     T *lds = reinterpret_cast<T *>(smem_raw);
-    T *wsb = a.ws + (size_t)blockIdx.x * brc_ws_elems(m, n, K, a.l_lds, a.r_lds, a.v_lds);
-    T *Wl = lds, *Wr = lds + (a.l_lds ? (size_t)K * ldl : 0);
+    T *wsb = a.ws + (size_t)blockIdx.x * (TALL ? brt_ws_elems(m, n, K, a.l_lds, a.r_lds, a.v_lds) : brc_ws_elems(m, n, K, a.l_lds, a.r_lds, a.v_lds));
+    T *Wl0 = lds, *Wr = lds + (a.l_lds ? (size_t)K * ldl : 0);
     T *G = Wr + (a.r_lds ? (size_t)K * ldr : 0);
     T *J = G + (size_t)K * ldg;
     T *vn1 = J + (a.v_lds ? (size_t)K * ldg : 0);
-    if (!a.l_lds) { Wl = wsb; wsb += (size_t)m * K; }
+    if (!a.l_lds) { Wl0 = wsb; wsb += multi ? (size_t)brt_stages(m, K) * brt_stage_elems(K) : (size_t)m * K; }
     if (!a.r_lds) { Wr = wsb; wsb += (size_t)n * K; }
     if (!a.v_lds) J = wsb;
     T *vn2 = vn1 + K, *taul = vn2 + K, *taur = taul + K, *sig = taur + K, *red = sig + K;
@@ -726,8 +877,30 @@ __global__ __launch_bounds__(BID_THREADS) void k_batched_recompress(BrcArgs<T> a
         // ---- the two pivoted QRs, q steps each (exact zero pivots are steps with H = I), taus and pivots kept -----------------------
         const T *__restrict__ L = a.left.p + (int64_t)b * a.lbs;
         const T *__restrict__ R = a.right.p + (int64_t)b * a.rbs;
-        bid_load(Wl, ldl, m, q, a.left.rs <= a.left.cs, [&](int i, int c) { return L[i * a.left.rs + c * a.left.cs]; }, vn1, vn2, jpl, wv, lane);
-        bid_qrcp<T, true>(Wl, ldl, m, q, q, 0.0, jpl, vn1, vn2, red, tid, wv, lane, taul);
+        T *Wl = Wl0;  // the copy the core and U read: the last stage's
+        [[maybe_unused]] int S = 1;
+        if constexpr (TALL) {
+            S = brt_stages(m, q);
+            const size_t se = brt_stage_elems(K);
+            for (int j = tid; j < q; j += BID_THREADS) jpl[j] = j;  // ordered before its first read by brt_stack_load's barrier
+            for (int s = 0; s < S; ++s) {
+                const int top = s ? q : 0, base = s ? BRT_H + (s - 1) * (BRT_H - q) : 0;
+                const int hs = top + min(BRT_H - top, m - base);
+                T *Ws = Wl0 + (multi ? (size_t)s * se : 0);
+                T *ts = multi ? Ws + (size_t)BRT_H * K : taul;
+                brt_stack_load(Ws, ldl, Ws - (s ? se : 0), top, hs, q, a.left.rs <= a.left.cs,
+                               [&](int i, int c) { return L[(int64_t)(base + i) * a.left.rs + c * a.left.cs]; }, vn1, vn2, jpl, wv, lane);
+                bid_qrcp<T, true>(Ws, ldl, hs, q, q, 0.0, jpl, vn1, vn2, red, tid, wv, lane, ts);
+                if (multi) {  // the stage's pivots beside its taus; jpl goes on as the next stage's starting order
+                    int *js = reinterpret_cast<int *>(ts + K);
+                    for (int j = tid; j < q; j += BID_THREADS) js[j] = jpl[j];
+                }
+                Wl = Ws;
+            }
+        } else {
+            bid_load(Wl, ldl, m, q, a.left.rs <= a.left.cs, [&](int i, int c) { return L[i * a.left.rs + c * a.left.cs]; }, vn1, vn2, jpl, wv, lane);
+            bid_qrcp<T, true>(Wl, ldl, m, q, q, 0.0, jpl, vn1, vn2, red, tid, wv, lane, taul);
+        }
         bid_load(Wr, ldr, n, q, a.right.cs <= a.right.rs, [&](int i, int c) { return R[c * a.right.rs + i * a.right.cs]; }, vn1, vn2, jpr, wv, lane);
         bid_qrcp<T, true>(Wr, ldr, n, q, q, 0.0, jpr, vn1, vn2, red, tid, wv, lane, taur);
         for (int j = tid; j < q; j += BID_THREADS) { ipl[jpl[j]] = j; ipr[jpr[j]] = j; }
@@ -810,7 +983,8 @@ __global__ __launch_bounds__(BID_THREADS) void k_batched_recompress(BrcArgs<T> a
         __syncthreads();
         const int r = flag[1];
         // ---- U = Q_L [J_r; 0] with the signs fixed on its columns ----------------------------------------------------------------------
-        if (m <= 64) bsv_form_u<T, 1>(Wl, ldl, J, ldj, m, q, kk, r, jpl, taul, srt, sgn, true, Ub, a.u.rs, a.u.cs, wv, lane);
+        if (TALL && S > 1) brt_form_u<T>(Wl0, brt_stage_elems(K), S, K, q, m, J, ldj, kk, r, srt, sgn, Ub, a.u.rs, a.u.cs, wv, lane);
+        else if (m <= 64) bsv_form_u<T, 1>(Wl, ldl, J, ldj, m, q, kk, r, jpl, taul, srt, sgn, true, Ub, a.u.rs, a.u.cs, wv, lane);
         else if (m <= 128) bsv_form_u<T, 2>(Wl, ldl, J, ldj, m, q, kk, r, jpl, taul, srt, sgn, true, Ub, a.u.rs, a.u.cs, wv, lane);
         else if (m <= 256) bsv_form_u<T, 4>(Wl, ldl, J, ldj, m, q, kk, r, jpl, taul, srt, sgn, true, Ub, a.u.rs, a.u.cs, wv, lane);
         else bsv_form_u<T, 8>(Wl, ldl, J, ldj, m, q, kk, r, jpl, taul, srt, sgn, true, Ub, a.u.rs, a.u.cs, wv, lane);
@@ -1034,6 +1208,23 @@ BatchedPlan<BrcPlace> brc_plan(int m, int n, int K) {
         [&](BrcPlace p) { return brc_ws_elems(m, n, K, p.l, p.r, p.v) * sizeof(T); }, "lowrank_recompress_batched");
 }
 
+// tall recompression: m <= BRT_H is brc_plan; above it the stage copies are always in the slot (the copy of left never in LDS), Wr and J
+// by brc_plan's rule, and the slot is brt_ws_elems
+template <typename T>
+BatchedPlan<BrcPlace> brt_plan(int m, int n, int K) {
+    if (m <= BRT_H) return brc_plan<T>(m, n, K);
+    const int pad = ((K + 15) / 32) * 32 + 16, odd = K | 1;
+    const BrcPlace places[] = {{false, true, true, pad}, {false, true, true, odd}, {false, false, true, pad}, {false, false, true, odd},
+                               {false, false, false, pad}, {false, false, false, odd}};
+    return batched_first_fit(places, [&](BrcPlace p) { return brc_lds_bytes<T>(m, n, K, p.ld, p.l, p.r, p.v); },
+        [&](BrcPlace p) { return brt_ws_elems(m, n, K, p.l, p.r, p.v) * sizeof(T); }, "lowrank_recompress_tall_batched");
+}
+// the tall launcher's own bound on the grid: the workspace of all slots stays at or below 2 GiB, never below one workgroup
+constexpr size_t BRT_MAX_WS = (size_t)2 << 30;
+inline int64_t brt_grid_cap(int64_t grid, size_t ws_per) {
+    return ws_per ? std::min<int64_t>(grid, std::max<int64_t>(1, (int64_t)(BRT_MAX_WS / ws_per))) : grid;
+}
+
 // sketched column ID: W (l x n) in LDS when it fits next to the chunk images, else in the workgroup's slot
 template <typename T>
 BatchedPlan<bool> bsi_plan(int l, int n) {
@@ -1116,19 +1307,27 @@ void batched_svd(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int64_t k,
     lch.launch(a, abs, (int)count, (int)k, tol, uo, uobs, vo, vobs, s, ranks, lch.template workspace<T>(), c->health_word(), at.ld);
 }
 
-// One kernel: the plan only moves base pointers and pitches.
-template <typename T>
-void batched_lowrank_recompress(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride, Mat<T> right, int64_t rbs,
-                                const int64_t *in_ranks, int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs, T *s_out, Mat<T> vt, int64_t vbs,
-                                int64_t *ranks) {
+// One kernel per entry point: the plan only moves base pointers and pitches.  TALL (rc_lowrank_recompress_tall_batched_*): the same arguments
+// and, for m <= 512, the same plan and the same work per block.  Above it a slot holds every stage's copy (about 90 MiB at 65536 x 128 in
+// f64), so the grid is bounded a second time, by brt_grid_cap: few workgroups run there.
+template <typename T, bool TALL>
+void brc_launch(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride, Mat<T> right, int64_t rbs, const int64_t *in_ranks,
+                int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs, T *s_out, Mat<T> vt, int64_t vbs, int64_t *ranks) {
     const int m = (int)left.rows, n = (int)right.cols, K = (int)left.cols;
     if (count <= 0) return;
-    const auto plan = brc_plan<T>(m, n, K);
+    const auto plan = TALL ? brt_plan<T>(m, n, K) : brc_plan<T>(m, n, K);
     const BrcPlace at = plan.at;
-    const auto lch = batched_prepare(c, k_batched_recompress<T>, "lowrank_recompress_batched", plan.lds, plan.ws, count);
-    ProfScope ps(c, "op:batched_recompress %dx%d k=%d count=%d grid=%lld slots=%lld plan=L:%s,R:%s,V:%s,G:lds,ld=%d,kk=%d%s%s", m, n, K, (int)count,
-                 (long long)lch.grid, (long long)lch.slots, at.l ? "lds" : "ws", at.r ? "lds" : "ws", at.v ? "lds" : "ws", at.ld, (int)std::min<int64_t>(k, K),
-                 mid.p ? ",mid" : "", s ? ",s" : "");
+    auto lch = batched_prepare(c, k_batched_recompress<T, TALL>, TALL ? "lowrank_recompress_tall_batched" : "lowrank_recompress_batched",
+                               plan.lds, plan.ws, count);
+    char stages[24] = "";
+    if constexpr (TALL) {
+        lch.grid = brt_grid_cap(lch.grid, plan.ws);
+        lch.slots = brt_grid_cap(lch.slots, plan.ws);
+        snprintf(stages, sizeof stages, "stages=%d,", brt_stages(m, K));  // inside plan=: the label keeps the family's fields
+    }
+    ProfScope ps(c, "op:batched_recompress%s %dx%d k=%d count=%d grid=%lld slots=%lld plan=%sL:%s,R:%s,V:%s,G:lds,ld=%d,kk=%d%s%s", TALL ? "_tall" : "", m, n, K,
+                 (int)count, (long long)lch.grid, (long long)lch.slots, stages, at.l ? "lds" : "ws", at.r ? "lds" : "ws", at.v ? "lds" : "ws", at.ld,
+                 (int)std::min<int64_t>(k, K), mid.p ? ",mid" : "", s ? ",s" : "");
     BrcArgs<T> a;
     a.left = left; a.mid = mid; a.right = right; a.u = u; a.vt = vt;
     a.lbs = lbs; a.mbs = mbs; a.rbs = rbs; a.ubs = ubs; a.vbs = vbs; a.s_stride = s_stride;
@@ -1138,6 +1337,27 @@ void batched_lowrank_recompress(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> 
     a.tol = tol; a.count = (int)count; a.k = (int)std::min<int64_t>(k, K); a.ldg = at.ld;
     a.l_lds = at.l; a.r_lds = at.r; a.v_lds = at.v;
     lch.launch(a);
+}
+template <typename T>
+void batched_lowrank_recompress(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride, Mat<T> right, int64_t rbs,
+                                const int64_t *in_ranks, int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs, T *s_out, Mat<T> vt, int64_t vbs,
+                                int64_t *ranks) {
+    brc_launch<T, false>(c, left, lbs, mid, mbs, s, s_stride, right, rbs, in_ranks, count, k, tol, u, ubs, s_out, vt, vbs, ranks);
+}
+template <typename T>
+void batched_lowrank_recompress_tall(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride, Mat<T> right,
+                                     int64_t rbs, const int64_t *in_ranks, int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs, T *s_out, Mat<T> vt,
+                                     int64_t vbs, int64_t *ranks) {
+    brc_launch<T, true>(c, left, lbs, mid, mbs, s, s_stride, right, rbs, in_ranks, count, k, tol, u, ubs, s_out, vt, vbs, ranks);
+}
+
+// the tall launcher's plan as numbers (rc_lowrank_recompress_tall_batched_plan): stages at inner width K, bytes of one slot, and the grid
+// brt_grid_cap leaves of `resident` workgroups
+void batched_lowrank_recompress_tall_plan(int64_t m, int64_t n, int64_t K, bool f64, int64_t resident, int64_t *stages, int64_t *slot_bytes, int64_t *grid) {
+    const size_t ws = f64 ? brt_plan<double>((int)m, (int)n, (int)K).ws : brt_plan<float>((int)m, (int)n, (int)K).ws;
+    *stages = brt_stages((int)m, (int)K);
+    *slot_bytes = (int64_t)ws;
+    *grid = brt_grid_cap(resident, ws);
 }
 
 // The plan only moves W's base pointer and pitch, so it cannot change a block's bits.  Four instances of the kernel, by the index of a and
@@ -1175,6 +1395,10 @@ template void batched_lowrank_recompress<double>(rc_context *, Mat<double>, int6
                                                  const int64_t *, int32_t, int64_t, double, Mat<double>, int64_t, double *, Mat<double>, int64_t, int64_t *);
 template void batched_lowrank_recompress<float>(rc_context *, Mat<float>, int64_t, Mat<float>, int64_t, const float *, int64_t, Mat<float>, int64_t,
                                                 const int64_t *, int32_t, int64_t, double, Mat<float>, int64_t, float *, Mat<float>, int64_t, int64_t *);
+template void batched_lowrank_recompress_tall<double>(rc_context *, Mat<double>, int64_t, Mat<double>, int64_t, const double *, int64_t, Mat<double>, int64_t,
+                                                      const int64_t *, int32_t, int64_t, double, Mat<double>, int64_t, double *, Mat<double>, int64_t, int64_t *);
+template void batched_lowrank_recompress_tall<float>(rc_context *, Mat<float>, int64_t, Mat<float>, int64_t, const float *, int64_t, Mat<float>, int64_t,
+                                                     const int64_t *, int32_t, int64_t, double, Mat<float>, int64_t, float *, Mat<float>, int64_t, int64_t *);
 
 template void batched_column_id<double>(rc_context *, Mat<double>, int64_t, int32_t, int64_t, double, Mat<double>, int64_t, Mat<double>, int64_t, int64_t *, int64_t *);
 template void batched_column_id<float>(rc_context *, Mat<float>, int64_t, int32_t, int64_t, double, Mat<float>, int64_t, Mat<float>, int64_t, int64_t *, int64_t *);

@@ -1244,13 +1244,13 @@ BlockShape check_block_operator_apply(Mat<T> left, Mat<T> mid, Mat<T> right, int
 // and vt (min(k, K) x n)
 template <typename T>
 void check_lowrank_recompress_batched(Mat<T> left, Mat<T> mid, Mat<T> right, int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs, const T *s_out,
-                                      Mat<T> vt, int64_t vbs, const int64_t *ranks) {
-    const char *who = "lowrank_recompress_batched";
+                                      Mat<T> vt, int64_t vbs, const int64_t *ranks, bool tall) {
+    const char *who = tall ? "lowrank_recompress_tall_batched" : "lowrank_recompress_batched";
     const int64_t m = left.rows, K = left.cols, n = right.cols;
     RC_REQUIRE(count >= 0, RC_INVALID_ARGUMENT, "%s: count = %d < 0", who, (int)count);
-    RC_REQUIRE(m >= 1 && m <= 512 && n >= 1 && n <= 512 && K >= 1 && K <= 128 && k >= 1, RC_INVALID_ARGUMENT,
-               "%s: needs 1 <= m, n <= 512, inner width 1 <= K <= 128 and k >= 1 (got left %lld x %lld, right %lld x %lld, k = %lld)", who, (long long)m,
-               (long long)K, (long long)right.rows, (long long)n, (long long)k);
+    RC_REQUIRE(m >= 1 && m <= (tall ? 65536 : 512) && n >= 1 && n <= 512 && K >= 1 && K <= 128 && k >= 1, RC_INVALID_ARGUMENT,
+               "%s: needs 1 <= m%s <= 512, inner width 1 <= K <= 128 and k >= 1 (got left %lld x %lld, right %lld x %lld, k = %lld)", who,
+               tall ? " <= 65536, 1 <= n" : ", n", (long long)m, (long long)K, (long long)right.rows, (long long)n, (long long)k);
     RC_REQUIRE(right.rows == K, RC_INVALID_ARGUMENT, "%s: left is %lld x %lld but right has %lld rows", who, (long long)m, (long long)K, (long long)right.rows);
     RC_REQUIRE(K <= std::min(m, n), RC_INVALID_ARGUMENT,
                "%s: needs K <= min(m, n) (got K = %lld for %lld x %lld blocks); rebuild the blocks with rc_lowrank_apply_batched_* and use rc_svd_rank_batched_*",
@@ -1320,9 +1320,9 @@ template BlockShape check_block_operator_apply<float>(Mat<float>, Mat<float>, Ma
 template void check_lowrank_residual_batched<double>(Mat<double>, Mat<double>, Mat<double>, Mat<double>, int32_t, Mat<double>, int64_t, const double *);
 template void check_lowrank_residual_batched<float>(Mat<float>, Mat<float>, Mat<float>, Mat<float>, int32_t, Mat<float>, int64_t, const float *);
 template void check_lowrank_recompress_batched<double>(Mat<double>, Mat<double>, Mat<double>, int32_t, int64_t, double, Mat<double>, int64_t, const double *,
-                                                       Mat<double>, int64_t, const int64_t *);
+                                                       Mat<double>, int64_t, const int64_t *, bool);
 template void check_lowrank_recompress_batched<float>(Mat<float>, Mat<float>, Mat<float>, int32_t, int64_t, double, Mat<float>, int64_t, const float *, Mat<float>,
-                                                      int64_t, const int64_t *);
+                                                      int64_t, const int64_t *, bool);
 
 template int64_t check_sketch_column_id_rank_batched<double>(Mat<double>, Mat<double>, int32_t, int64_t, double, Mat<double>, int64_t, Mat<double>, int64_t,
                                                              Mat<double>, int64_t, const int64_t *, const int64_t *);
@@ -1389,6 +1389,16 @@ void lowrank_recompress_batched(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> 
     check_lowrank_recompress_batched(left, mid, right, count, k, tol, u, ubs, s_out, vt, vbs, ranks);
     if (count == 0) return;
     batched_lowrank_recompress(c, left, lbs, mid, mbs, s, s_stride, right, rbs, in_ranks, count, k, tol, u, ubs, s_out, vt, vbs, ranks);
+}
+
+// the same for a tall left factor (m <= 65536): the same checks with that bound, the left factor by a flat Householder TSQR inside the launch
+template <typename T>
+void lowrank_recompress_tall_batched(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride, Mat<T> right, int64_t rbs,
+                                     const int64_t *in_ranks, int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs, T *s_out, Mat<T> vt, int64_t vbs,
+                                     int64_t *ranks) {
+    check_lowrank_recompress_batched(left, mid, right, count, k, tol, u, ubs, s_out, vt, vbs, ranks, true);
+    if (count == 0) return;
+    batched_lowrank_recompress_tall(c, left, lbs, mid, mbs, s, s_stride, right, rbs, in_ranks, count, k, tol, u, ubs, s_out, vt, vbs, ranks);
 }
 
 // the one-pass randomized column ID of every block of a batch: the sketch y = omega a (l x n) and the column ID of y in one launch, c gathered from a
@@ -1993,6 +2003,17 @@ rc_status rc_invert_permutation(rc_context *ctx, const int64_t *perm, int64_t n,
                                           s_out, from_c<T>(vt), vt_batch_stride, ranks);                                                 \
         });                                                                                                                              \
     }                                                                                                                                    \
+    rc_status rc_lowrank_recompress_tall_batched_##SUF(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid,        \
+                                                       int64_t mid_batch_stride, const T *s, int64_t s_stride, rc_matrix right,          \
+                                                       int64_t right_batch_stride, const int64_t *in_ranks, int32_t count, int64_t k,    \
+                                                       double tol, rc_matrix u, int64_t u_batch_stride, T *s_out, rc_matrix vt,          \
+                                                       int64_t vt_batch_stride, int64_t *ranks) {                                        \
+        return guarded(ctx, [&] {                                                                                                        \
+            lowrank_recompress_tall_batched<T>(ctx, from_c<T>(left), left_batch_stride, from_c<T>(mid), mid_batch_stride, s, s_stride,   \
+                                               from_c<T>(right), right_batch_stride, in_ranks, count, k, tol, from_c<T>(u),              \
+                                               u_batch_stride, s_out, from_c<T>(vt), vt_batch_stride, ranks);                            \
+        });                                                                                                                              \
+    }                                                                                                                                    \
     rc_status rc_sketch_column_id_rank_batched_##SUF(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega,              \
                                                      int64_t omega_batch_stride, int32_t count, int64_t k, double tol, rc_matrix y,      \
                                                      int64_t y_batch_stride, rc_matrix c, int64_t c_batch_stride, rc_matrix z,           \
@@ -2016,6 +2037,20 @@ rc_status rc_invert_permutation(rc_context *ctx, const int64_t *perm, int64_t n,
 
 RC_DEFINE_TYPED(f64, double)
 RC_DEFINE_TYPED(f32, float)
+
+// the tall recompression's plan as numbers: host arithmetic only, no context, no device
+rc_status rc_lowrank_recompress_tall_batched_plan(int64_t m, int64_t n, int64_t inner, int32_t elem_bytes, int64_t resident, int64_t *stages,
+                                                  int64_t *slot_bytes, int64_t *grid) {
+    if (!(m >= 1 && m <= 65536 && n >= 1 && n <= 512 && inner >= 1 && inner <= 128 && inner <= std::min(m, n)) || (elem_bytes != 4 && elem_bytes != 8) ||
+        resident < 1 || !stages || !slot_bytes || !grid)
+        return RC_INVALID_ARGUMENT;
+    try {
+        batched_lowrank_recompress_tall_plan(m, n, inner, elem_bytes == 8, resident, stages, slot_bytes, grid);
+        return RC_OK;
+    } catch (const Error &e) {
+        return e.code;
+    }
+}
 
 // f32 storage under f64 arithmetic (kernels_batched_apply.hip, kernels_block_operator.hip): the twins' checks on views of the same shapes
 rc_status rc_lowrank_apply_mixed_batched_f64(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride,

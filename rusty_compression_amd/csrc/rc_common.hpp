@@ -285,15 +285,21 @@ void check_convert_batched(const char *who, const rc_matrix &src, int32_t count,
 template <typename T> void batched_lowrank_recompress(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride,
                                                       Mat<T> right, int64_t rbs, const int64_t *in_ranks, int32_t count, int64_t k, double tol, Mat<T> u,
                                                       int64_t ubs, T *s_out, Mat<T> vt, int64_t vbs, int64_t *ranks);
+// the same with a tall left factor (m <= 65536): flat Householder TSQR of left in stages of 512 rows, stored in the workgroup's slot; and its plan
+// as numbers: stages at inner width K, bytes of one slot, the grid its 2 GiB workspace bound leaves of `resident` workgroups
+template <typename T> void batched_lowrank_recompress_tall(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride,
+                                                           Mat<T> right, int64_t rbs, const int64_t *in_ranks, int32_t count, int64_t k, double tol, Mat<T> u,
+                                                           int64_t ubs, T *s_out, Mat<T> vt, int64_t vbs, int64_t *ranks);
+void batched_lowrank_recompress_tall_plan(int64_t m, int64_t n, int64_t K, bool f64, int64_t resident, int64_t *stages, int64_t *slot_bytes, int64_t *grid);
 // the complex twin (kernels_batched_id_c.hip), R = double (c64) or float (c32): interleaved-complex views, strides in complex elements, s and s_out
 // real, vt = V^H
 template <typename R> void batched_lowrank_recompress_c(rc_context *c, const rc_matrix &left, int64_t lbs, const rc_matrix &mid, int64_t mbs, const R *s,
                                                         int64_t s_stride, const rc_matrix &right, int64_t rbs, const int64_t *in_ranks, int32_t count, int64_t k,
                                                         double tol, const rc_matrix &u, int64_t ubs, R *s_out, const rc_matrix &vt, int64_t vbs, int64_t *ranks);
 // the argument checks of rc_lowrank_recompress_batched_* and rc_lowrank_recompress_complex_batched_* (rc_api.hip), shared by every scalar type like those
-// above; the caller returns when count == 0
+// above; the caller returns when count == 0.  tall: rc_lowrank_recompress_tall_batched_*'s name and its bound m <= 65536
 template <typename T> void check_lowrank_recompress_batched(Mat<T> left, Mat<T> mid, Mat<T> right, int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs,
-                                                            const T *s_out, Mat<T> vt, int64_t vbs, const int64_t *ranks);
+                                                            const T *s_out, Mat<T> vt, int64_t vbs, const int64_t *ranks, bool tall = false);
 // the column ID of the sketch omega a of every block of a batch (kernels_batched_id.hip): block i is a (m x n), omega (l x m, l <= 128), y (l x n,
 // p == nullptr: not written), cm (m x kk) and z (kk x n) each moved by i times its batch stride (0 is legal for a and omega), kk = min(k, l, n) already
 // clamped; col_ind count x n, ranks count (arguments checked by the caller)
