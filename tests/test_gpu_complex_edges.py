@@ -16,22 +16,13 @@ import torch
 import rusty_compression_amd as rc
 from oracle import ref_lapack as o
 from rusty_compression_amd import _lib, batch
+from tests.gemm_cases import dev as _dev, gemm as _gemm, tdt as _tdt, view as _view
 from tests.helpers import agreed_pivot_prefix, is_permutation, npy, rel, stable_prefix
 from tests.test_gpu_complex import TOLC
 
 pytestmark = pytest.mark.gpu
 CT = rc.CompressionType
 CDT = [np.complex128, np.complex64]
-TORCH = {np.dtype(np.complex128): torch.complex128, np.dtype(np.complex64): torch.complex64,
-         np.dtype(np.float64): torch.float64, np.dtype(np.float32): torch.float32}
-
-
-def _tdt(dtype):
-    return TORCH[np.dtype(dtype)]
-
-
-def _dev(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).cuda()
 
 
 def _mat(dtype, shape, smin, seed):
@@ -43,36 +34,9 @@ def _orth_cols(u):
     return float(np.abs(u.conj().T @ u - np.eye(u.shape[1])).max()) if u.shape[1] else 0.0
 
 
-def _view(x, kind, fill=None):
-    """x (m x n) as a device view: "C" row-major, "T" the transpose of a contiguous n x m (column-major), "P" a column-major
-    sub-view of a larger buffer with an odd leading dimension.  Returns (view, buffer); the buffer's border holds `fill`."""
-    m, n = x.shape
-    dt = _tdt(x.dtype)
-    if kind == "C":
-        t = _dev(x)
-        return t, t
-    if kind == "T":
-        t = _dev(x.T)
-        return t.t(), t
-    ld = m + 3 if (m + 3) % 2 else m + 4
-    fill = complex(7.0, -3.0) if fill is None else fill
-    buf = torch.full((n + 2, ld), fill if dt.is_complex else fill.real, dtype=dt, device="cuda")
-    buf[1:n + 1, 2:m + 2] = torch.from_numpy(np.ascontiguousarray(x.T)).cuda()
-    v = buf[1:n + 1, 2:m + 2].t()
-    assert v.stride() == (1, ld) and ld % 2 == 1
-    return v, buf
-
-
 # ------------------------------------------------------------------------------------------------ GEMM
 def _op(x, op):
     return x if op == 0 else (x.T if op == 1 else x.conj().T)
-
-
-def _gemm(opa, opb, alpha, a, b, beta, c):
-    dt = c.dtype
-    _lib.default_context().call(f"rc_gemm_{_lib.suffix(dt)}", ctypes.c_int32(opa), ctypes.c_int32(opb), _lib.scalar_arg(dt, alpha),
-                                _lib.mat(a), _lib.mat(b), _lib.scalar_arg(dt, beta), _lib.mat(c))
-    torch.cuda.synchronize()
 
 
 def _gemm_case(dtype, opa, opb, m, k, n, alpha, beta, ckind, rng, tol):

@@ -17,6 +17,7 @@ import torch
 
 import rusty_compression_amd as rc
 from oracle import ref_lapack as o
+from tests.gemm_cases import GEMM_DISPATCH, gemm_operand, last_gemm_kernel
 from tests.helpers import TOL, agreed_pivot_prefix, golden, greedy_pivot_slack, is_permutation, npy, rel, sign_normalise, stable_prefix
 
 pytestmark = pytest.mark.gpu
@@ -59,76 +60,6 @@ def test_gemm_all_layouts_and_ragged_shapes(dtype, tol):
     y = rng.standard_normal((70, 12)).astype(dtype)
     assert rel(npy(rc.matmat(big, x)), big.astype(np.float64) @ x) <= tol
     assert rel(npy(rc.conj_matmat(big, y)), big.T.astype(np.float64) @ y) <= tol
-
-
-def last_gemm_kernel():
-    """The instantiation of the most recent GEMM launch on the default context, as rocprofv3 names it."""
-    from rusty_compression_amd import _lib
-
-    fn = _lib.lib().rc_last_gemm_kernel_name
-    fn.restype = ctypes.c_char_p
-    fn.argtypes = [ctypes.c_void_p]
-    return fn(_lib.default_context()._h).decode()
-
-
-def gemm_operand(x, layout):
-    """`x` on the device: "C" row-major / "F" column-major with an even leading dimension (16-byte vector staging),
-    "c" row-major with an odd leading dimension (scalar staging)."""
-    r, c = x.shape
-    if layout == "F":
-        t = torch.zeros((c, r + (r & 1)), dtype=torch.from_numpy(x).dtype, device="cuda")[:, :r]
-        t.copy_(torch.from_numpy(np.ascontiguousarray(x.T)))
-        return t.t()
-    ld = c + (c & 1) if layout == "C" else c + 1 - (c & 1)
-    t = torch.zeros((r, ld), dtype=torch.from_numpy(x).dtype, device="cuda")[:, :c]
-    t.copy_(torch.from_numpy(x))
-    return t
-
-
-# Every arm of the GEMM dispatch (kernels_gemm.hip launch_shape_f64q / launch_shape, kernels_gemm_pipe.hip gemm_f64p_launch) with
-# the instantiation it launches: (dtype, layout of A, layout of B, M, N, K, kernel).  "C" A / "F" B: K-contiguous; "F" A: M-contiguous;
-# "C" B: N-contiguous.  f64 products with N <= 144 under M > 144 run as the transposed problem.
-GEMM_DISPATCH = [
-    # f64: the n x n Gram products (pipelined loop for the two CholeskyQR layouts), 144 x 144 tiles otherwise
-    ("f64", "C", "F", 100, 100, 512, "k_gemm_f64p<0,1,144,144,16,3,3,0>"),
-    ("f64", "F", "C", 100, 100, 512, "k_gemm_f64p<1,0,144,144,16,3,3,0>"),
-    ("f64", "C", "C", 100, 100, 512, "k_gemm_f64q<0,0,144,144,16,3,3,2,0,0>"),
-    ("f64", "C", "F", 100, 100, 40, "k_gemm_f64q<0,1,144,144,16,3,3,2,0,0>"),
-    ("f64", "c", "C", 100, 100, 97, "k_gemm_f64q<0,0,144,144,16,3,3,1,0,0>"),
-    # f64 skinny N
-    ("f64", "C", "C", 100, 64, 256, "k_gemm_f64q<0,0,256,80,16,8,1,2,0,0>"),
-    ("f64", "C", "C", 60, 128, 256, "k_gemm_f64q<0,0,256,128,16,8,1,2,0,0>"),
-    ("f64", "C", "C", 60, 136, 256, "k_gemm_f64q<0,0,256,144,16,8,1,2,0,0>"),
-    # f64 skinny M: 32-row panel products, <= 80 rows, shallow K over a wide N
-    ("f64", "C", "C", 32, 512, 1024, "k_gemm_f64q<0,0,32,256,16,1,8,2,1,0>"),
-    ("f64", "C", "C", 64, 512, 256, "k_gemm_f64q<0,0,80,256,16,1,8,2,1,0>"),
-    ("f64", "C", "C", 128, 2048, 128, "k_gemm_f64q<0,0,128,128,16,1,8,2,1,0>"),
-    ("f64", "F", "F", 136, 2048, 128, "k_gemm_f64q<1,1,136,128,16,2,4,2,0,0>"),
-    # f64 <= 128 rows: the projection on the ring kernel; direct-to-LDS B tile; register staging
-    ("f64", "F", "C", 128, 512, 256, "k_gemm_f64r<0,1,128,256,1,8,false,0>"),
-    ("f64", "F", "C", 100, 300, 256, "k_gemm_f64r<0,1,128,256,1,8,false,0>"),
-    ("f64", "C", "C", 128, 512, 256, "k_gemm_f64q<0,0,128,256,16,1,8,2,1,1>"),
-    ("f64", "F", "C", 100, 300, 40, "k_gemm_f64q<1,0,128,256,16,1,8,2,1,0>"),
-    ("f64", "C", "C", 1000, 100, 256, "k_gemm_f64q<1,1,128,256,16,1,8,2,1,0>"),
-    # f64 129 .. 136 rows: the sketch on the ring kernel, the pipelined loop, the plain loop
-    ("f64", "F", "F", 133, 512, 256, "k_gemm_f64r<1,0,136,256,2,4,true,0>"),
-    ("f64", "F", "F", 133, 300, 256, "k_gemm_f64p<1,1,136,256,16,2,4,0>"),
-    ("f64", "F", "F", 133, 512, 40, "k_gemm_f64q<1,1,136,256,16,2,4,2,0,0>"),
-    ("f64", "F", "C", 133, 512, 256, "k_gemm_f64q<1,0,136,256,16,2,4,2,0,0>"),
-    # f64 137 .. 144 rows, and everything larger
-    ("f64", "F", "F", 140, 512, 256, "k_gemm_f64q<1,1,144,256,16,1,8,2,1,0>"),
-    ("f64", "C", "C", 300, 300, 256, "k_gemm_f64q<0,0,128,128,16,2,2,2,0,0>"),
-    # f32
-    ("f32", "C", "C", 100, 100, 256, "k_gemm_mfma<float,0,0,144,144,16,3,3,2,2>"),
-    ("f32", "C", "C", 300, 64, 256, "k_gemm_mfma<float,0,0,128,80,16,4,1,2,2>"),
-    ("f32", "C", "C", 300, 136, 256, "k_gemm_mfma<float,0,0,256,144,16,8,1,2,2>"),
-    ("f32", "C", "F", 32, 512, 1024, "k_gemm_mfma<float,0,1,32,128,16,1,4,2,2>"),
-    ("f32", "C", "C", 32, 512, 1024, "k_gemm_mfma<float,0,0,80,128,16,1,4,2,2>"),
-    ("f32", "C", "C", 64, 512, 256, "k_gemm_mfma<float,0,0,80,128,16,1,4,2,2>"),
-    ("f32", "C", "C", 128, 512, 256, "k_gemm_mfma<float,0,0,144,256,16,1,8,2,2>"),
-    ("f32", "C", "C", 300, 300, 256, "k_gemm_mfma<float,0,0,128,128,16,2,2,2,2>"),
-    ("f32", "c", "C", 300, 300, 255, "k_gemm_mfma<float,0,0,128,128,16,2,2,1,2>"),
-]
 
 
 def test_gemm_dispatch_launches_the_expected_instantiation():
