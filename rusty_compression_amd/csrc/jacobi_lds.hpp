@@ -122,17 +122,7 @@ __device__ inline void jacobi_pair_rotate(T *gp, T *gq, int ll, int n, const T (
         }
     }
 }
-// "Another sweep is needed" after a rotation by the angle (c, s) of a pair whose cosine was g.  Such a rotation leaves
-// at most |s| * (largest cosine of this sweep) behind in pairs that were already annihilated, so a sweep
-// may be the last one only if every rotation in it had BOTH a small cosine (g <= sqrt(tol) / 4, 9e-9 in
-// f64) AND a small angle (|s| <= 4 sqrt(tol)): for well separated singular values the second follows
-// from the first (quadratic convergence), for clustered / repeated ones (sigma_p ~ sigma_q: the angle is
-// O(1) however small g is) it does not, and such sweeps are followed by another one until an all-quiet
-// or all-small sweep has been seen
-template <typename T>
-__device__ inline bool jacobi_rotation_was_large(T app, T aqq, T apq, T s, T tol) {
-    return apq * apq > tol * (T)0.0625 * app * aqq || s * s > (T)16 * tol;
-}
+// (the two threshold tests of a pair, jacobi_pair_is_coupled and jacobi_rotation_was_large: rc_device.hpp)
 
 // ---------------------------------------------------------------------------
 // LDS-resident one-sided Jacobi.  16 lanes own one column pair and keep NE = n / 16 rows (rounded up) of both columns in
@@ -286,11 +276,12 @@ __device__ inline void jacobi_lds_body(const JacobiLdsArgs<T> &ja, bool consumer
                     aqq = group_sum_dpp<kLPP>(aqq);
                     apq = group_sum_dpp<kLPP>(apq);
                     // rotate iff |apq| > tol * sqrt(app * aqq)   (uniform over the 16 lanes)
-                    if (apq * apq > tol2 * app * aqq) {
+                    const double apq2 = (double)apq * (double)apq;
+                    if (jacobi_pair_is_coupled(app, aqq, apq2, tol2)) {
                         jacobi_rotation(app, aqq, apq, rot.c, rot.s);
                         jacobi_pair_rotate<T, NE, FULL>(gp, gq, ll, n, a, b, rot);
                         // flag 2 = another sweep is needed
-                        if (ll == 0 && jacobi_rotation_was_large(app, aqq, apq, rot.s, tol)) sh_rot = 2;  // plain store: every writer writes 2
+                        if (ll == 0 && jacobi_rotation_was_large(app, aqq, apq2, rot.s, tol)) sh_rot = 2;  // plain store: every writer writes 2
                     }
                 }
                 if (ll == 0) {

@@ -379,9 +379,9 @@ __global__ __launch_bounds__(BID_THREADS) void k_batched_two_sided(Mat<T> a, int
 // 30-sweep budget.  Everything stays inside one workgroup.
 
 // Jacobi rows per lane of a 16-lane pair group (N <= 16 NE) and rows per lane of a 64-lane U column (M <= 64 NE)
-// WIDE (the recompression): both threshold tests are evaluated in f64, so that in f32 two columns of norm 1e-9 or less, whose
-// app aqq and apq^2 pass the smallest f32 number, are still rotated until they are orthogonal; without it the text is the batched SVD's
-template <typename T, int NE, bool WIDE = false>
+// (both threshold tests are evaluated in f64, so that in f32 two columns of norm 1e-9 or less, whose app aqq and apq^2 pass the
+// smallest f32 number, are still rotated until they are orthogonal: jacobi_pair_is_coupled, rc_device.hpp)
+template <typename T, int NE>
 __device__ __forceinline__ void bsv_round(T *G, int ldg, T *J, int ldj, int N, int p, int q, T tol, T tol2, int ll, int *flag) {
     T *gp = G + (size_t)p * ldg, *gq = G + (size_t)q * ldg;
     T a[NE], b[NE];
@@ -399,11 +399,8 @@ __device__ __forceinline__ void bsv_round(T *G, int ldg, T *J, int ldj, int N, i
     aqq = group_sum_dpp<16>(aqq);
     apq = group_sum_dpp<16>(apq);
     // k_jacobi_lds's test and thresholds: rotate iff |apq| > tol sqrt(app aqq) (uniform over the 16 lanes)
-    if constexpr (WIDE) {
-        if (!((double)apq * (double)apq > (double)tol2 * (double)app * (double)aqq)) return;
-    } else {
-        if (!(apq * apq > tol2 * app * aqq)) return;
-    }
+    const double apq2 = (double)apq * (double)apq;
+    if (!jacobi_pair_is_coupled(app, aqq, apq2, tol2)) return;
     T c, s;
     jacobi_rotation(app, aqq, apq, c, s);
     T *vp = J + (size_t)p * ldj, *vq = J + (size_t)q * ldj;
@@ -418,16 +415,12 @@ __device__ __forceinline__ void bsv_round(T *G, int ldg, T *J, int ldj, int N, i
             vq[i] = s * x + c * y;
         }
     }
-    if constexpr (WIDE) {
-        if (ll == 0 && ((double)apq * (double)apq > (double)tol * 0.0625 * (double)app * (double)aqq || s * s > (T)16 * tol)) *flag = 2;
-    } else {
-        if (ll == 0 && (apq * apq > tol * (T)0.0625 * app * aqq || s * s > (T)16 * tol)) *flag = 2;  // plain store: every writer writes 2
-    }
+    if (ll == 0 && jacobi_rotation_was_large(app, aqq, apq2, s, tol)) *flag = 2;  // plain store: every writer writes 2
 }
 
 // one-sided Jacobi of the N x N core G (columns ldg apart) with the rotations accumulated in J (ldj); round-robin pairs, 16 lanes per pair, the 16
 // groups of the workgroup walk the N / 2 pair slots of a round.  Returns false when kMaxSweeps ran out before a quiet sweep.
-template <typename T, int NE, bool WIDE = false>
+template <typename T, int NE>
 __device__ __forceinline__ bool bsv_jacobi(T *G, int ldg, T *J, int ldj, int N, int tid, int *flag) {
     const int ll = tid & 15, grp = tid >> 4;
     constexpr int NGRP = BID_THREADS / 16;
@@ -440,7 +433,7 @@ __device__ __forceinline__ bool bsv_jacobi(T *G, int ldg, T *J, int ldj, int N, 
             for (int pi = grp; pi < npairs; pi += NGRP) {
                 int p, q;
                 rr_pair(N2, r, pi, p, q);
-                if (q < N) bsv_round<T, NE, WIDE>(G, ldg, J, ldj, N, p, q, tol, tol2, ll, flag);  // q == N: the dummy column of an odd N
+                if (q < N) bsv_round<T, NE>(G, ldg, J, ldj, N, p, q, tol, tol2, ll, flag);  // q == N: the dummy column of an odd N
             }
             __syncthreads();  // the pairs of a round are disjoint; the next round re-pairs the columns
         }
@@ -943,10 +936,10 @@ __global__ __launch_bounds__(BID_THREADS) void k_batched_recompress(BrcArgs<T> a
         }
         __syncthreads();
         bool conv;
-        if (q <= 16) conv = bsv_jacobi<T, 1, true>(G, ldg, J, ldj, q, tid, flag);
-        else if (q <= 32) conv = bsv_jacobi<T, 2, true>(G, ldg, J, ldj, q, tid, flag);
-        else if (q <= 64) conv = bsv_jacobi<T, 4, true>(G, ldg, J, ldj, q, tid, flag);
-        else conv = bsv_jacobi<T, 8, true>(G, ldg, J, ldj, q, tid, flag);
+        if (q <= 16) conv = bsv_jacobi<T, 1>(G, ldg, J, ldj, q, tid, flag);
+        else if (q <= 32) conv = bsv_jacobi<T, 2>(G, ldg, J, ldj, q, tid, flag);
+        else if (q <= 64) conv = bsv_jacobi<T, 4>(G, ldg, J, ldj, q, tid, flag);
+        else conv = bsv_jacobi<T, 8>(G, ldg, J, ldj, q, tid, flag);
         if (!conv && tid == 0) atomicOr(a.health, 16);  // the sweep budget ran out: bit 16, as the batched SVD reports it
         // ---- singular values: column norms, sorted descending (a strict total order: NaN last, ties by column) ----------------------
         for (int j = tid >> 4; j < q; j += BID_THREADS / 16) {

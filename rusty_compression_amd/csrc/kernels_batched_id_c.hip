@@ -378,10 +378,9 @@ __global__ __launch_bounds__(BIC_THREADS) void k_batched_two_sided_c(CV<R> a, in
 // then takes the real rotation of (app, aqq, |apq|).  Everything stays inside one workgroup.
 
 // Jacobi rows per lane of a 16-lane pair group (N <= 16 NE): the complex twin of bsv_round
-// WIDE (the recompression): both threshold tests are evaluated in f64, as bsv_round's are, so that in c32 two columns of norm 1e-9 or
-// less, whose app aqq and |apq|^2 pass the smallest f32 number, are still rotated until they are orthogonal; without it the text is
-// the batched SVD's
-template <typename R, int NE, bool WIDE = false>
+// (both threshold tests are evaluated in f64 on |apq|^2 formed in f64, as bsv_round's are, so that in c32 two columns of norm 1e-9
+// or less, whose app aqq and |apq|^2 pass the smallest f32 number, are still rotated until they are orthogonal)
+template <typename R, int NE>
 __device__ __forceinline__ void bsc_round(cplx<R> *G, int ldg, cplx<R> *J, int ldj, int N, int p, int q, R tol, R tol2, int ll, int *flag) {
     cplx<R> *gp = G + (size_t)p * ldg, *gq = G + (size_t)q * ldg;
     cplx<R> a[NE], b[NE];
@@ -405,13 +404,9 @@ __device__ __forceinline__ void bsc_round(cplx<R> *G, int ldg, cplx<R> *J, int l
     are = group_sum_dpp<16>(are);
     aim = group_sum_dpp<16>(aim);
     // bsv_round's test with |apq|^2: rotate iff |apq| > tol sqrt(app aqq) (uniform over the 16 lanes)
-    const R h2 = are * are + aim * aim;
-    if constexpr (WIDE) {
-        if (!((double)are * (double)are + (double)aim * (double)aim > (double)tol2 * (double)app * (double)aqq)) return;
-    } else {
-        if (!(h2 > tol2 * app * aqq)) return;
-    }
-    const double hd = sqrt((double)are * (double)are + (double)aim * (double)aim), ih = 1.0 / hd;
+    const double h2 = (double)are * (double)are + (double)aim * (double)aim;
+    if (!jacobi_pair_is_coupled(app, aqq, h2, tol2)) return;
+    const double hd = sqrt(h2), ih = 1.0 / hd;
     const cplx<R> ph{(R)((double)are * ih), (R)(-((double)aim * ih))};  // e^{-i phi}
     double cd, sd;
     jacobi_rotation<double>((double)app, (double)aqq, hd, cd, sd);
@@ -429,17 +424,12 @@ __device__ __forceinline__ void bsc_round(cplx<R> *G, int ldg, cplx<R> *J, int l
             vq[i] = cplx<R>{s * x.re + c * y.re, s * x.im + c * y.im};
         }
     }
-    if constexpr (WIDE) {
-        if (ll == 0 && ((double)are * (double)are + (double)aim * (double)aim > (double)tol * 0.0625 * (double)app * (double)aqq || s * s > (R)16 * tol))
-            *flag = 2;
-    } else {
-        if (ll == 0 && (h2 > tol * (R)0.0625 * app * aqq || s * s > (R)16 * tol)) *flag = 2;  // plain store: every writer writes 2
-    }
+    if (ll == 0 && jacobi_rotation_was_large(app, aqq, h2, s, tol)) *flag = 2;  // plain store: every writer writes 2
 }
 
 // bsv_jacobi's schedule (round-robin pairs, 16 lanes per pair, one barrier per round, kMaxSweeps) on the complex core.  Returns false
 // when the sweep budget ran out before a quiet sweep.
-template <typename R, int NE, bool WIDE = false>
+template <typename R, int NE>
 __device__ __forceinline__ bool bsc_jacobi(cplx<R> *G, int ldg, cplx<R> *J, int ldj, int N, int tid, int *flag) {
     const int ll = tid & 15, grp = tid >> 4;
     constexpr int NGRP = BIC_THREADS / 16;
@@ -452,7 +442,7 @@ __device__ __forceinline__ bool bsc_jacobi(cplx<R> *G, int ldg, cplx<R> *J, int 
             for (int pi = grp; pi < npairs; pi += NGRP) {
                 int p, q;
                 rr_pair(N2, r, pi, p, q);
-                if (q < N) bsc_round<R, NE, WIDE>(G, ldg, J, ldj, N, p, q, tol, tol2, ll, flag);  // q == N: the dummy column of an odd N
+                if (q < N) bsc_round<R, NE>(G, ldg, J, ldj, N, p, q, tol, tol2, ll, flag);  // q == N: the dummy column of an odd N
             }
             __syncthreads();  // the pairs of a round are disjoint; the next round re-pairs the columns
         }
@@ -730,7 +720,7 @@ __global__ __launch_bounds__(BIC_THREADS) void k_batched_svd_c(CV<R> a, int64_t 
 // where Rl[:, c] is the upper-triangular column the factorization keeps for the factor's own column c (rows 0 .. ip[c] of the
 // working copy's column c, ip the inverse of the pivot order), Rr likewise.  The lanes run along j: T1, Wr and G are read and
 // written at consecutive addresses and mid[a, b], Rl[i, a] are one broadcast address per wave.
-// The Jacobi's threshold tests are evaluated in f64 (bsc_round's WIDE), as the real recompression's are.
+// The Jacobi's threshold tests are evaluated in f64 (bsc_round), as the real recompression's are.
 
 template <typename R>
 struct BrcCArgs {
@@ -850,10 +840,10 @@ __global__ __launch_bounds__(BIC_THREADS, 2) void k_batched_recompress_c(BrcCArg
         }
         __syncthreads();
         bool conv;
-        if (q <= 16) conv = bsc_jacobi<R, 1, true>(G, ldg, J, ldj, q, tid, flag);
-        else if (q <= 32) conv = bsc_jacobi<R, 2, true>(G, ldg, J, ldj, q, tid, flag);
-        else if (q <= 64) conv = bsc_jacobi<R, 4, true>(G, ldg, J, ldj, q, tid, flag);
-        else conv = bsc_jacobi<R, 8, true>(G, ldg, J, ldj, q, tid, flag);
+        if (q <= 16) conv = bsc_jacobi<R, 1>(G, ldg, J, ldj, q, tid, flag);
+        else if (q <= 32) conv = bsc_jacobi<R, 2>(G, ldg, J, ldj, q, tid, flag);
+        else if (q <= 64) conv = bsc_jacobi<R, 4>(G, ldg, J, ldj, q, tid, flag);
+        else conv = bsc_jacobi<R, 8>(G, ldg, J, ldj, q, tid, flag);
         if (!conv && tid == 0) atomicOr(a.health, 16);  // the sweep budget ran out: bit 16, as the batched SVD reports it
         // ---- singular values: column norms, sorted descending (a strict total order: NaN last, ties by column) ----------------------
         for (int j = tid >> 4; j < q; j += BIC_THREADS / 16) {

@@ -181,8 +181,9 @@ static void jacobi_global(rc_context *c, Mat<T> g, Mat<T> v, Mat<T> uc, T *s, Ma
     fill_words(c, state, 4 * sizeof(int), 0u);
     fill_identity(c, v);
     // outside a graph capture the convergence flag is read back after every sweep; inside one a fixed number
-    // of sweeps is recorded (converged sweeps return immediately)
-    const int max_sweeps = c->capturing ? 16 : 60;
+    // of sweeps is recorded (converged sweeps return immediately): the LDS kernel's budget.  With 16 recorded sweeps a
+    // numerically rank-deficient 142 x 142 core (X Y^T of rank 35: 22 sweeps) came back unconverged, health bit 4 raised
+    const int max_sweeps = c->capturing ? kMaxSweeps : 60;
     const unsigned grid = (unsigned)((N / 2 + 3) / 4);
     for (int sweep = 0; sweep < max_sweeps; ++sweep) {
         for (int r = 0; r < N - 1; ++r) hipLaunchKernelGGL(k_jacobi_round<T>, dim3(grid), dim3(256), 0, c->stream, g, v, r, state);

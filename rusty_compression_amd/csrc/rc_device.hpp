@@ -152,6 +152,27 @@ __device__ inline void jacobi_rotation(T app, T aqq, T apq, T &c, T &s) {
     s = (T)(cd * t);
 }
 
+// The two threshold tests of a column pair, on apq2 = |apq|^2 formed in f64.  Both compare products of squared norms, so both are
+// evaluated in f64 whatever T is (for T = double the casts are no-ops): in f32 two columns of norm 1e-9 or less put
+// tol^2 app aqq below the smallest f32 number and apq^2 next to it, the tests then read "rotate iff apq^2 did not vanish", the sweeps
+// stop with cosines far above tol between the columns of tiny singular values, and G Sigma^-1 is not orthonormal (measured with
+// the tests in f32 on 4^-5 X Y^T and 4^-8 X Y^T of rank n / 4, n = 32 .. 192: max |U^T U - I| = 2e-4 .. 0.59, against 3e-6 in f64).
+//   coupled: rotate iff |apq| > tol sqrt(app aqq)   (tol2 = tol^2)
+template <typename T>
+__device__ __forceinline__ bool jacobi_pair_is_coupled(T app, T aqq, double apq2, T tol2) {
+    return apq2 > (double)tol2 * (double)app * (double)aqq;
+}
+//   "another sweep is needed" after a rotation by the angle (c, s) of a pair whose cosine was g.  Such a rotation leaves at most
+// |s| * (largest cosine of this sweep) behind in pairs that were already annihilated, so a sweep may be the last one only if every
+// rotation in it had BOTH a small cosine (g <= sqrt(tol) / 4, 9e-9 in f64) AND a small angle (|s| <= 4 sqrt(tol)): for well
+// separated singular values the second follows from the first (quadratic convergence), for clustered / repeated ones
+// (sigma_p ~ sigma_q: the angle is O(1) however small g is) it does not, and such sweeps are followed by another one until an
+// all-quiet or all-small sweep has been seen
+template <typename T>
+__device__ __forceinline__ bool jacobi_rotation_was_large(T app, T aqq, double apq2, T s, T tol) {
+    return apq2 > (double)tol * 0.0625 * (double)app * (double)aqq || s * s > (T)16 * tol;
+}
+
 // Sweep budget of the LDS-resident Jacobi; the fused launch of k_jacobi_lds hands the sweep count over in the 8-bit payload of a tagged word.
 constexpr int kMaxSweeps = 30;
 

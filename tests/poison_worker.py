@@ -22,6 +22,9 @@ out = {}
 for shape in ((100, 60), (64, 128), (300, 200)):
     u, s, vt = rc.compute_svd(rc.random_gaussian(shape, rc.Rng(6), torch.float64))
     out[f"svd_{shape[0]}x{shape[1]}"] = dg(s, (u * s) @ vt)
+# (after the three above, whose workspace must stay fresh memory: a 135-column core, the LDS Jacobi with the separate replay of V)
+u, s, vt = rc.compute_svd(rc.random_gaussian((150, 135), rc.Rng(6), torch.float64))
+out["svd_replay_150x135"] = dg(s, (u * s) @ vt)
 a = rc.random_gaussian((4096, 2048), rc.Rng(3), torch.float64)
 q = rc.sample_range_by_rank(a, 96, 5, rc.Rng(4))
 svd = rc.SVD.compute_from_range_estimate(q, a)
