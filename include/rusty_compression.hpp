@@ -723,10 +723,13 @@ template <> struct RecompressApi<double> { using tol_type = double; static const
 template <> struct RecompressApi<float> { using tol_type = double; static constexpr auto lowrank_recompress_batched = rc_lowrank_recompress_batched_f32; };
 template <> struct RecompressApi<c64> { using tol_type = double; static constexpr auto lowrank_recompress_batched = rc_lowrank_recompress_complex_batched_c64; };
 template <> struct RecompressApi<c32> { using tol_type = float; static constexpr auto lowrank_recompress_batched = rc_lowrank_recompress_complex_batched_c32; };
-// the real pair for a tall left factor (m <= 65536): rc_lowrank_recompress_tall_batched_*, the same signature and contract
+// the calls for a tall left factor (m <= 65536): rc_lowrank_recompress_tall_batched_* and rc_lowrank_recompress_tall_complex_batched_*, the same
+// signatures and contracts (tol's type is RecompressApi<T>::tol_type)
 template <typename T> struct RecompressTallApi;
 template <> struct RecompressTallApi<double> { static constexpr auto lowrank_recompress_batched = rc_lowrank_recompress_tall_batched_f64; };
 template <> struct RecompressTallApi<float> { static constexpr auto lowrank_recompress_batched = rc_lowrank_recompress_tall_batched_f32; };
+template <> struct RecompressTallApi<c64> { static constexpr auto lowrank_recompress_batched = rc_lowrank_recompress_tall_complex_batched_c64; };
+template <> struct RecompressTallApi<c32> { static constexpr auto lowrank_recompress_batched = rc_lowrank_recompress_tall_complex_batched_c32; };
 // the call both recompress_batched and recompress_tall_batched make, on the entry point `fn` of their dispatch
 template <typename T, typename Tol, typename Fn>
 BatchedSVD<T> recompress_batched_through(Fn fn, const DeviceMatrix<T> &left, const DeviceMatrix<T> *mid, const DeviceBuffer<typename Scalar<T>::real> *s,
@@ -748,12 +751,13 @@ BatchedSVD<T> recompress_batched(const DeviceMatrix<T> &left, const DeviceMatrix
     return recompress_batched_through<T, typename RecompressApi<T>::tol_type>(RecompressApi<T>::lowrank_recompress_batched, left, mid, s, right, ranks, count, k,
                                                                               tol);
 }
-// the same for factor pairs whose left factor is tall (m <= 65536, n <= 512; double and float): the SVD end of sketch_column_id_rank_batched.
-// For m <= 512 the result is recompress_batched's bit for bit.
+// the same for factor pairs whose left factor is tall (m <= 65536, n <= 512; every scalar type): the SVD end of the sketched
+// column_id_rank_batched.  For m <= 512 the result is recompress_batched's bit for bit.
 template <typename T>
 BatchedSVD<T> recompress_tall_batched(const DeviceMatrix<T> &left, const DeviceMatrix<T> *mid, const DeviceBuffer<typename Scalar<T>::real> *s,
                                       const DeviceMatrix<T> &right, const DeviceIndex *ranks, int32_t count, int64_t k, double tol = 0.0) {
-    return recompress_batched_through<T, double>(RecompressTallApi<T>::lowrank_recompress_batched, left, mid, s, right, ranks, count, k, tol);
+    return recompress_batched_through<T, typename RecompressApi<T>::tol_type>(RecompressTallApi<T>::lowrank_recompress_batched, left, mid, s, right, ranks, count,
+                                                                              k, tol);
 }
 template <typename T>
 BatchedSVD<T> recompress_tall_batched(const BatchedColumnID<T> &id, int64_t k, double tol = 0.0) {

@@ -605,8 +605,8 @@ rc_status rc_lowrank_recompress_batched_f32(rc_context *ctx, rc_matrix left, int
  * bit 16, no host synchronisation, capturable), with the sign rule taken over all m rows of each kept column of u.  This is the SVD end of
  * rc_sketch_column_id_rank_batched_*: its c (m x kk), z and ranks go in as left, right and in_ranks.
  * Domain: 1 <= m <= 65536, 1 <= n <= 512, 1 <= K <= 128, K <= min(m, n), k >= 1, 0 <= tol < 1, count >= 0; the checks, status codes and
- * messages are the pair's above under the name lowrank_recompress_tall_batched.  These two are the real scalars; complex factors are out of
- * scope, and rc_lowrank_recompress_tall_batched_c64 / _c32 do not exist.
+ * messages are the pair's above under the name lowrank_recompress_tall_batched.  These two are the real scalars; complex factors go through
+ * rc_lowrank_recompress_tall_complex_batched_c64 / _c32 below (rc_lowrank_recompress_tall_batched_c64 / _c32 do not exist).
  * Per block: left[:, :q] is factored by a flat Householder TSQR inside the one workgroup that owns the block.  Stage 0 is the pivoted QR of
  * rows 0 .. min(m, 512) - 1; every later stage stacks the q x q triangle of the stage before on the next 512 - q rows of left, columns in the
  * pivot order so far, and runs the same q pivoted steps (so an exactly zero column of left stays exactly zero to the end).  The last triangle
@@ -640,6 +640,31 @@ rc_status rc_lowrank_recompress_tall_batched_plan(int64_t m, int64_t n, int64_t 
  * pair) rely on rc_lowrank_recompress_batched_c64 / _c32 not existing: a build that has this complex call is told apart by its own symbol. */
 rc_status rc_lowrank_recompress_complex_batched_c64(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const double *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *in_ranks, int32_t count, int64_t k, double tol, rc_matrix u, int64_t u_batch_stride, double *s_out, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks);
 rc_status rc_lowrank_recompress_complex_batched_c32(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const float *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *in_ranks, int32_t count, int64_t k, float tol, rc_matrix u, int64_t u_batch_stride, float *s_out, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks);
+/* The complex recompression for factor pairs whose left factor is tall: rc_lowrank_recompress_complex_batched_c64 / _c32's signature argument for
+ * argument (interleaved (re, im) data, strides in complex elements, real s, s_out and tol, float tol for c32) and its per-block contract sentence
+ * for sentence (q, s_out, the rank rule, zero tails, exact zeros, q = 0, NaN containment, health bit 16, conjugation and zero-imaginary-part
+ * symmetry, vt = V^H with nothing conjugated in the product), with the phase rule taken over all m rows of each kept column of u: the first
+ * entry of largest modulus is real and positive with imaginary part exactly 0, whichever 512-row stage holds it.  This is the SVD end of
+ * rc_sketch_column_id_rank_complex_batched_*: its c (m x kk), z and ranks go in as left, right and in_ranks.
+ * Domain: 1 <= m <= 65536, 1 <= n <= 512, 1 <= K <= 128, K <= min(m, n), k >= 1, 0 <= tol < 1, count >= 0; the checks, status codes and
+ * messages are the shared ones under the name lowrank_recompress_tall_complex_batched.
+ * Per block: rc_lowrank_recompress_tall_batched_*'s staged Householder TSQR of left[:, :q] (stages of 512 rows, each later stage the q x q
+ * triangle so far on the next 512 - q rows, pivoted in every stage, complex taus) and its backward pass through the stored reflectors; right,
+ * the core, the Jacobi iteration, the sort and the rank rule are rc_lowrank_recompress_complex_batched_*'s.
+ * Bits: the operands, their row and column strides and the call's shapes alone; those of the truncated factors passed as a call of inner width
+ * q; and for m <= 512 every output equals rc_lowrank_recompress_complex_batched_*'s on the same arguments bit for bit.
+ * Workspace: a slot holds 1 + ceil((m - 512) / (512 - K)) stages of (512 K + 2 K) complex elements for m > 512: 173 MiB at m = 65536, K = 128
+ * in c64 (11 workgroups under the 2 GiB bound), 87 MiB in c32 (23).  Such blocks are served, slowly; the plan query below reports the numbers.
+ * Wide blocks are A^T: since vt = V^H and nothing in the product is conjugated, A^T = vt^T diag(s_out) u^T is again of this form, so call with
+ * right^T, mid^T and left^T as strided views in the places of left, mid and right and pass vt^T as u and u^T as vt: plain transposes of all
+ * three factors, nothing conjugated.  The phase rule then holds on the columns of vt^T.
+ * The name: rc_lowrank_recompress_tall_batched_c64 / _c32 stay absent for the reason given at rc_lowrank_recompress_complex_batched_*. */
+rc_status rc_lowrank_recompress_tall_complex_batched_c64(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const double *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *in_ranks, int32_t count, int64_t k, double tol, rc_matrix u, int64_t u_batch_stride, double *s_out, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks);
+rc_status rc_lowrank_recompress_tall_complex_batched_c32(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const float *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *in_ranks, int32_t count, int64_t k, float tol, rc_matrix u, int64_t u_batch_stride, float *s_out, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks);
+/* The plan of that call as numbers, host arithmetic only (no context, no device): as rc_lowrank_recompress_tall_batched_plan with real_bytes
+ * the size of the real type (8: c64, 4: c32); *slot_bytes counts complex elements of 2 * real_bytes.  RC_INVALID_ARGUMENT outside the call's
+ * domain, for another real_bytes, resident < 1 or a null output. */
+rc_status rc_lowrank_recompress_tall_complex_batched_plan(int64_t m, int64_t n, int64_t inner, int32_t real_bytes, int64_t resident, int64_t *stages, int64_t *slot_bytes, int64_t *grid);
 /* The one-pass randomized column ID of every block of a batch, in one stream-ordered, capturable call: the sketch Y_i = omega_i a_i (l x n) of each
  * tall block a_i (m x n) is formed while a_i streams through the chip once, and the column ID of the small Y_i gives the pivots and Z; C is gathered
  * from a_i.  Per block this replaces the reference's randomized sequence: the projection of sample_range_by_rank (src/random_sampling.rs), then

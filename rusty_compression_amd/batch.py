@@ -565,8 +565,8 @@ def block_operator_apply_mixed(x: torch.Tensor, group_ptr, group_row, entry_bloc
 
 
 def _lowrank_recompress_batched(who: str, complex_data: bool, left, right, k, tol, mid, s, ranks, tall: bool = False):
-    """The shared body of lowrank_recompress_batched, lowrank_recompress_tall_batched (real dtypes; tall: the entry points for m <= 65536) and
-    lowrank_recompress_batched_complex (complex dtypes, real s and S)."""
+    """The shared body of lowrank_recompress_batched, lowrank_recompress_tall_batched (real dtypes; tall: the entry points for m <= 65536),
+    lowrank_recompress_batched_complex and lowrank_recompress_tall_batched_complex (complex dtypes, real s and S)."""
     from . import _lib
     from .types import as_device
 
@@ -618,7 +618,8 @@ def _lowrank_recompress_batched(who: str, complex_data: bool, left, right, k, to
         return _lib.rc_matrix(t.data_ptr(), t.shape[1], t.shape[2], t.stride(1), t.stride(2)), ctypes.c_int64(t.stride(0))
 
     # the complex entry points spell their stem differently (see the header) and take tol in the real type of the data
-    stem = "rc_lowrank_recompress_complex_batched_" if complex_data else "rc_lowrank_recompress_tall_batched_" if tall else "rc_lowrank_recompress_batched_"
+    stem = {(False, False): "rc_lowrank_recompress_batched_", (False, True): "rc_lowrank_recompress_tall_batched_",
+            (True, False): "rc_lowrank_recompress_complex_batched_", (True, True): "rc_lowrank_recompress_tall_complex_batched_"}[(complex_data, tall)]
     tol_arg = ctypes.c_float(float(tol)) if left.dtype == torch.complex64 else ctypes.c_double(float(tol))
     _lib.default_context().call(stem + _lib.suffix(left.dtype), *view(left), *view(mid),
                                 ctypes.c_void_p(s.data_ptr() if s is not None else None), ctypes.c_int64(s.stride(0) if s is not None else 0),
@@ -698,7 +699,7 @@ def lowrank_recompress_tall_batched(left: torch.Tensor, right: torch.Tensor, k: 
     block is the first j < min(kk, q) with s_j == 0 or s_j / s_0 < tol, else min(kk, q); columns of U and rows of Vt past it are zero
     and the largest-|.| entry of each kept column of U, over all m rows, is positive.  For m <= 512 the outputs are
     lowrank_recompress_batched's bit for bit.  A wide pair (tall right) is the transpose: pass right.mT, mid.mT, left.mT and swap
-    U.mT / Vt.mT.  Complex data raises TypeError (complex tall factors are not supported)."""
+    U.mT / Vt.mT.  Complex data raises TypeError (see lowrank_recompress_tall_batched_complex)."""
     return _lowrank_recompress_batched("lowrank_recompress_tall_batched", False, left, right, k, tol, mid, s, ranks, tall=True)
 
 
@@ -716,6 +717,38 @@ def svd_add_tall_batched(u1: torch.Tensor, s1: torch.Tensor, vt1: torch.Tensor, 
     right = torch.cat([vt1, vt2], dim=1)
     s = torch.cat([s1[:, :k1], s2[:, :k2]], dim=1)
     return lowrank_recompress_tall_batched(left, right, k, tol, s=s)
+
+
+def lowrank_recompress_tall_batched_complex(left: torch.Tensor, right: torch.Tensor, k: int, tol: float = 0.0, mid: Optional[torch.Tensor] = None,
+                                            s: Optional[torch.Tensor] = None,
+                                            ranks: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """lowrank_recompress_tall_batched for complex factors (rc_lowrank_recompress_tall_complex_batched_c64 / _c32): the arguments, dtypes and
+    results of lowrank_recompress_batched_complex (left, right and mid complex128 or complex64 of one dtype, lazily conjugated views
+    materialised, s and S real, Vt the conjugate transpose of V, nothing conjugated in the product; real data and mismatched dtypes raise
+    TypeError) with m <= 65536: the left factor goes through the staged Householder TSQR of lowrank_recompress_tall_batched.  In each kept
+    column of U the first of its largest-modulus entries over all m rows is real and positive, its imaginary part exactly 0; conjugated
+    inputs give the conjugated U and Vt bit for bit.  For m <= 512 the outputs are lowrank_recompress_batched_complex's bit for bit.
+    A wide pair (tall right) is the transpose, and because Vt = V^H with nothing conjugated in U S Vt, the recipe is the plain transpose of
+    all three factors: pass right.mT, mid.mT, left.mT and read the block's U as Vt_out.mT and its Vt as U_out.mT (no .conj() anywhere);
+    the phase rule then holds on the rows of the block's Vt."""
+    return _lowrank_recompress_batched("lowrank_recompress_tall_batched_complex", True, left, right, k, tol, mid, s, ranks, tall=True)
+
+
+def column_id_to_svd_tall_batched_complex(c: torch.Tensor, z: torch.Tensor, ranks: Optional[torch.Tensor], k: int,
+                                          tol: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """column_id_to_svd_tall_batched for the complex outputs of sketch_column_id_rank_batched_complex."""
+    return lowrank_recompress_tall_batched_complex(c, z, k, tol, ranks=ranks)
+
+
+def svd_add_tall_batched_complex(u1: torch.Tensor, s1: torch.Tensor, vt1: torch.Tensor, u2: torch.Tensor, s2: torch.Tensor, vt2: torch.Tensor, k: int,
+                                 tol: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """svd_add_batched_complex for tall blocks (m <= 65536): the rounded sum of two batches of complex truncated SVDs through
+    lowrank_recompress_tall_batched_complex."""
+    k1, k2 = u1.shape[2], u2.shape[2]
+    left = torch.cat([u1, u2], dim=2)
+    right = torch.cat([vt1, vt2], dim=1)
+    s = torch.cat([s1[:, :k1], s2[:, :k2]], dim=1)
+    return lowrank_recompress_tall_batched_complex(left, right, k, tol, s=s)
 
 
 def column_id_to_svd_batched_complex(c: torch.Tensor, z: torch.Tensor, ranks: Optional[torch.Tensor], k: int,
@@ -917,7 +950,8 @@ def sketch_svd_rank_batched(a: torch.Tensor, k: int, tol: float = 0.0, omega: Op
     """Batched randomized SVDs of `count` tall same-shaped blocks (m <= 65536, n <= 512): the reference's sketch -> factor the small matrix ->
     SVD path in two launches with no host synchronisation between them, sketch_column_id_rank_batched(a, k, tol, omega, oversampling, seed)
     followed by column_id_to_svd_tall_batched on its (C, Z, ranks).  Returns (U [count, m, kk], S [count, kk], Vt [count, kk, n], ranks),
-    kk = min(k, l, n): the truncated SVD of each block's one-pass column ID C Z, bit for bit that of the two calls made by hand."""
+    kk = min(k, l, n): the truncated SVD of each block's one-pass column ID C Z, bit for bit that of the two calls made by hand.
+    Complex data raises TypeError (see sketch_svd_rank_batched_complex)."""
     c, z, _, ranks = sketch_column_id_rank_batched(a, k, tol, omega, oversampling, seed)
     return column_id_to_svd_tall_batched(c, z, ranks, k, tol)
 
@@ -930,6 +964,15 @@ def sketch_column_id_rank_batched_complex(a: torch.Tensor, k: int, tol: float = 
     l = min(k + oversampling, 128) rows with rc_random_gaussian_c64 / _c32 at (seed, offset 0): random_gaussian((l, m), Rng(seed), a.dtype).
     Z, ind and ranks are column_id_rank_batched(Y, k, tol)'s on the complex sketch bit for bit."""
     return _sketch_column_id_rank_batched("sketch_column_id_rank_batched_complex", True, a, k, tol, omega, oversampling, seed, return_sketch)
+
+
+def sketch_svd_rank_batched_complex(a: torch.Tensor, k: int, tol: float = 0.0, omega: Optional[torch.Tensor] = None, oversampling: int = 8,
+                                    seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """sketch_svd_rank_batched for complex tall blocks: sketch_column_id_rank_batched_complex(a, k, tol, omega, oversampling, seed) followed by
+    column_id_to_svd_tall_batched_complex on its (C, Z, ranks), two launches with no host synchronisation between them.  Returns
+    (U, S real, Vt = V^H, ranks), bit for bit the result of the two calls made by hand."""
+    c, z, _, ranks = sketch_column_id_rank_batched_complex(a, k, tol, omega, oversampling, seed)
+    return column_id_to_svd_tall_batched_complex(c, z, ranks, k, tol)
 
 
 def packed_bytes(m: int, n: int, k: int, elem_size: int) -> int:

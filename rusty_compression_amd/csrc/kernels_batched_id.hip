@@ -691,10 +691,7 @@ __host__ __device__ inline size_t brc_ws_elems(int m, int n, int K, bool l_lds, 
 // cumulative permutation, and (the last stage's copy, jp) stand where (Wl, jpl) stand in the core products.  The stage height depends on
 // q, not on K: a block's bits are those of a call of inner width q.  Every stage's factored copy, taus and pivots stay in the
 // workgroup's workspace slot (brt_stage_elems each) for the backward pass, brt_form_u.  m <= H is one stage and the kernel above.
-constexpr int BRT_H = 512;
-__host__ __device__ inline int brt_stages(int m, int q) { return m <= BRT_H ? 1 : 1 + (m - BRT_H + (BRT_H - q) - 1) / (BRT_H - q); }
-// one stage in the slot: the copy (H x K, pitch H), taus[K], pivots[K] (ints in elements of T)
-__host__ __device__ inline size_t brt_stage_elems(int K) { return (size_t)BRT_H * K + 2 * (size_t)K; }
+// (BRT_H, brt_stages, brt_stage_elems and the grid bound brt_grid_cap are in rc_batched_launch.hpp, shared with the complex kernel.)
 // the slot: the stage copies of the widest inner rank first (m > H; brc_ws_elems' copy of left otherwise), then brc_ws_elems' other parts
 __host__ __device__ inline size_t brt_ws_elems(int m, int n, int K, bool l_lds, bool r_lds, bool v_lds) {
     if (m <= BRT_H) return brc_ws_elems(m, n, K, l_lds, r_lds, v_lds);
@@ -1211,11 +1208,6 @@ BatchedPlan<BrcPlace> brt_plan(int m, int n, int K) {
                                {false, false, false, pad}, {false, false, false, odd}};
     return batched_first_fit(places, [&](BrcPlace p) { return brc_lds_bytes<T>(m, n, K, p.ld, p.l, p.r, p.v); },
         [&](BrcPlace p) { return brt_ws_elems(m, n, K, p.l, p.r, p.v) * sizeof(T); }, "lowrank_recompress_tall_batched");
-}
-// the tall launcher's own bound on the grid: the workspace of all slots stays at or below 2 GiB, never below one workgroup
-constexpr size_t BRT_MAX_WS = (size_t)2 << 30;
-inline int64_t brt_grid_cap(int64_t grid, size_t ws_per) {
-    return ws_per ? std::min<int64_t>(grid, std::max<int64_t>(1, (int64_t)(BRT_MAX_WS / ws_per))) : grid;
 }
 
 // sketched column ID: W (l x n) in LDS when it fits next to the chunk images, else in the workgroup's slot

@@ -1,6 +1,7 @@
 // Batched column and two-sided IDs and truncated SVDs of many small same-shaped COMPLEX matrices in one launch
 // (rc_column_id_rank_batched_c64 / _c32, rc_two_sided_id_rank_batched_c64 / _c32, rc_svd_rank_batched_c64 / _c32), and the
-// recompression of complex low-rank factors (rc_lowrank_recompress_complex_batched_c64 / _c32, k_batched_recompress_c below) and the sketched
+// recompression of complex low-rank factors (rc_lowrank_recompress_complex_batched_c64 / _c32 and, for tall left factors,
+// rc_lowrank_recompress_tall_complex_batched_c64 / _c32: k_batched_recompress_c<R, TALL> below) and the sketched
 // column ID of complex tall blocks (rc_sketch_column_id_rank_complex_batched_c64 / _c32, k_batched_sketch_id_c below).
 //
 // The structure of kernels_batched_id.hip (one persistent workgroup of 256 threads per matrix, the same three device stages, the same
@@ -753,16 +754,191 @@ __host__ __device__ inline size_t brcc_ws_elems(int m, int n, int K, int ldg, bo
     return (l_lds ? 0 : (size_t)m * K) + (r_lds ? 0 : (size_t)n * K) + (g_lds ? 0 : (size_t)K * ldg) + (v_lds ? 0 : (size_t)K * K);
 }
 
+// ---- tall left factors (rc_lowrank_recompress_tall_complex_batched_c64 / _c32, m <= 65536) --------------------------------------------------
+// k_batched_recompress<T, true>'s scheme (kernels_batched_id.hip) on complex elements: left[:, :q] is factored by a flat Householder TSQR with
+// stored reflectors inside the one workgroup.  Stage 0 is bic_qrcp on rows 0 .. min(m, H) - 1, H = BRT_H = 512 rows.  Stage s >= 1 factors a
+// stack: the upper triangle of the previous stage's R (q rows, the real diagonal (beta, 0) as bic_qrcp leaves it, exact zeros below) on top of
+// the next min(H - q, rows left) rows of left, by the same q pivoted steps.  The factor's column c sits at physical column c of every stack and
+// jpl (position -> physical column) is carried from stage to stage, so after the last stage (the last stage's copy, jpl) stand where (Wl, jpl)
+// stand in the core products.  An exactly zero column of left is an exactly zero column of every stack: pivoted last, tau = 0, a zero row of the
+// last R.  The stage height depends on q, not on K: a block's bits are those of a call of inner width q.  Every stage's factored copy, complex
+// taus and pivots stay in the workgroup's slot (brt_stage_elems(K) complex elements each) for the backward pass, brtc_form_u.  m <= H is one
+// stage, which is the kernel below with TALL = false: the launcher sends such shapes to that instance, so the TALL instances only ever see
+// m > H, that is two stages or more at every inner rank.
+__host__ __device__ inline size_t brtc_ws_elems(int m, int n, int K, int ldg, bool l_lds, bool r_lds, bool v_lds, bool g_lds) {
+    if (m <= BRT_H) return brcc_ws_elems(m, n, K, ldg, l_lds, r_lds, v_lds, g_lds);
+    return (size_t)brt_stages(m, K) * brt_stage_elems(K) + brcc_ws_elems(0, n, K, ldg, true, r_lds, v_lds, g_lds);
+}
+
+// one stage's stack into W (pitch ldw, hs rows): rows 0 .. top - 1 of position p's column are R[0 .. p, p] of the previous stage's copy Wp (the
+// same pitch and physical columns) and zeros, rows top .. hs - 1 are at(i - top, c); then the real column norms by position (bic_norms' sums)
+// with jp kept as it is.  top == 0 (stage 0): Wp is not read, and with jp the identity this is bic_load.
+template <typename R, typename At>
+__device__ __forceinline__ void brtc_stack_load(cplx<R> *W, int ldw, const cplx<R> *Wp, int top, int hs, int q, bool lanes_on_rows, At at, R *vn1, R *vn2,
+                                                const int *jp, int wv, int lane) {
+    if (top) {
+        for (int p = wv; p < q; p += BIC_WAVES) {
+            const size_t col = (size_t)jp[p] * ldw;
+            for (int i = lane; i < top; i += 64) W[col + i] = i <= p ? Wp[col + i] : czero<R>();
+        }
+    }
+    const int rows = hs - top;
+    if (lanes_on_rows) {
+        for (int c = wv; c < q; c += BIC_WAVES)
+            for (int i = lane; i < rows; i += 64) W[(size_t)c * ldw + top + i] = at(i, c);
+    } else {
+        for (int i = wv; i < rows; i += BIC_WAVES)
+            for (int c = lane; c < q; c += 64) W[(size_t)c * ldw + top + i] = at(i, c);
+    }
+    __syncthreads();
+    for (int p = wv; p < q; p += BIC_WAVES) {
+        const cplx<R> *col = W + (size_t)jp[p] * ldw;
+        R acc = 0;
+        for (int i = lane; i < hs; i += 64) acc += abs2(col[i]);
+        acc = wave_sum_dpp(acc);
+        if (lane == 0) { const R nr = sqrt(acc); vn1[p] = nr; vn2[p] = nr; }
+    }
+    __syncthreads();
+}
+
+// x <- H_0 .. H_{N-1} x for a column held by one wave (row lane + 64 e in x[e], M rows): bsc_form_u's reflector loop, FMA for FMA, as a routine
+// of its own for a column that goes through several factorizations (bsc_form_u keeps its loop, as bsv_form_u does beside bsv_reflect_back)
+template <typename R, int NE>
+__device__ __forceinline__ void bsc_reflect_back(const cplx<R> *W, int ldw, int M, int N, const int *jp, const cplx<R> *taus, cplx<R> (&x)[NE], int lane) {
+    for (int j = N - 1; j >= 0; --j) {
+        const cplx<R> tau = taus[j];
+        if (tau.re == (R)0 && tau.im == (R)0) continue;  // H_j = I (uniform)
+        const cplx<R> *vc = W + (size_t)jp[j] * ldw;
+        cplx<R> v[NE];
+        R dre = 0, dim = 0;  // v^H x
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            const int i = lane + 64 * e;
+            const cplx<R> vv = vc[i < M ? i : j];  // branch-free: lanes out of range read row j and are masked below
+            v[e] = i > j && i < M ? vv : (i == j ? cone<R>() : czero<R>());
+            dre = fma(v[e].re, x[e].re, dre);
+            dre = fma(v[e].im, x[e].im, dre);
+            dim = fma(v[e].re, x[e].im, dim);
+            dim = fma(-v[e].im, x[e].re, dim);
+        }
+        const cplx<R> f = tau * cplx<R>{wave_sum_dpp(dre), wave_sum_dpp(dim)};
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            x[e].re = fma(-f.re, v[e].re, x[e].re);
+            x[e].re = fma(f.im, v[e].im, x[e].re);
+            x[e].im = fma(-f.re, v[e].im, x[e].im);
+            x[e].im = fma(-f.im, v[e].re, x[e].im);
+        }
+    }
+}
+
+// U[:, c] = ph_c Q_0 [Q_1 [.. Q_{S-1} [J[:, srt[c]]; 0] ..; 0]; 0] for S >= 2 stages at stage0 + s * se: one wave per kept column carries x (q
+// complex values, 8 per lane) down the stages.  Stage s >= 1 applies its reflectors to [x; 0] (H rows in registers); rows q .. of the result are
+// that chunk's rows of u and are written as they are, rows 0 .. q - 1 replace x; stage 0's result fills rows 0 .. H - 1.
+// The phase rule runs over all m rows: per chunk the largest abs2 in the working type and the first output row that attains it (bsc_phase's
+// key); the chunks are visited from the last rows to the first, so a chunk whose maximum is >= the best so far takes over, which makes the
+// winner the first of the largest-modulus entries.  ph = conj(x*) / |x*| as in bsc_phase (f64 hypot, rounded); (1, 0) for a zero or non-finite
+// column.  Stage 0's rows are multiplied by ph in registers before they are written; every chunk written earlier is re-read and multiplied by
+// the lanes that wrote it (the same element of the same lane: no other lane's store is read back).  The pivot entry becomes exactly (|x*|, 0)
+// in whichever chunk holds it.  Every product is operator* of rc_cplx.hpp, so conjugating the inputs conjugates the column bit for bit.
 template <typename R>
-__global__ __launch_bounds__(BIC_THREADS, 2) void k_batched_recompress_c(BrcCArgs<R> a) {
+__device__ __forceinline__ void brtc_form_u(const cplx<R> *stage0, size_t se, int S, int K, int q, int m, const cplx<R> *J, int ldj, int k, int r, const int *srt,
+                                            cplx<R> *phs, cplx<R> *U, int64_t urs, int64_t ucs, int wv, int lane) {
+    constexpr int NE = BRT_H / 64;
+    for (int c = wv; c < k; c += BIC_WAVES) {
+        cplx<R> *uc = U + (int64_t)c * ucs;
+        if (c >= r) {
+            for (int i = lane; i < m; i += 64) uc[i * urs] = czero<R>();
+            continue;
+        }
+        const cplx<R> *jc = J + (size_t)srt[c] * ldj;
+        cplx<R> x[NE];
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            const int i = lane + 64 * e;
+            x[e] = i < q ? jc[i] : czero<R>();
+        }
+        R best = (R)-1;
+        int brow = 0x7fffffff;       // the output row of x*
+        cplx<R> xs = czero<R>();  // x*
+        for (int s = S - 1; s >= 0; --s) {
+            const cplx<R> *Ws = stage0 + (size_t)s * se, *ts = Ws + (size_t)BRT_H * K;
+            const int top = s ? q : 0, base = s ? BRT_H + (s - 1) * (BRT_H - q) : 0;
+            const int hs = top + min(BRT_H - top, m - base);
+            bsc_reflect_back<R, NE>(Ws, BRT_H, hs, q, reinterpret_cast<const int *>(ts + K), ts, x, lane);
+            R mx = 0;
+#pragma unroll
+            for (int e = 0; e < NE; ++e) {
+                const int i = lane + 64 * e;
+                if (i >= top && i < hs) mx = max(mx, abs2(x[e]));
+            }
+            mx = wave_max_dpp(mx);
+            int who = 0x7fffffff;  // 64 e + lane of the chunk's first row of abs2 == mx: rows ascend with 64 e + lane
+#pragma unroll
+            for (int e = 0; e < NE; ++e) {
+                const int i = lane + 64 * e;
+                if (i >= top && i < hs && abs2(x[e]) == mx) who = min(who, i);
+            }
+            who = wave_min_dpp(who);
+            if (who != 0x7fffffff && mx >= best) {  // uniform; this chunk's rows precede every chunk seen so far
+                best = mx;
+                brow = base + who - top;
+#pragma unroll
+                for (int e = 0; e < NE; ++e)
+                    if (e == (who >> 6)) xs = cplx<R>{read_lane(x[e].re, who & 63), read_lane(x[e].im, who & 63)};
+            }
+            if (s) {
+#pragma unroll
+                for (int e = 0; e < NE; ++e) {
+                    const int i = lane + 64 * e;
+                    if (i >= top && i < hs) uc[(int64_t)(base + i - top) * urs] = x[e];
+                    x[e] = i < top ? x[e] : czero<R>();
+                }
+            }
+        }
+        const double md = hypot((double)xs.re, (double)xs.im);
+        const bool turn = brow != 0x7fffffff && md > 0.0 && md <= 1.7976931348623157e308;
+        const cplx<R> ph = turn ? cplx<R>{(R)((double)xs.re / md), (R)(-((double)xs.im / md))} : cone<R>();
+        const cplx<R> piv{(R)md, (R)0};
+        if (lane == 0) phs[c] = ph;
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            const int i = lane + 64 * e;  // stage 0 of S >= 2 stages holds H rows
+            uc[(int64_t)i * urs] = !turn ? x[e] : i == brow ? piv : x[e] * ph;
+        }
+        if (turn) {
+            for (int s = 1; s < S; ++s) {
+                const int base = BRT_H + (s - 1) * (BRT_H - q), hs = q + min(BRT_H - q, m - base);
+#pragma unroll
+                for (int e = 0; e < NE; ++e) {
+                    const int i = lane + 64 * e;
+                    if (i >= q && i < hs) {
+                        cplx<R> *p = uc + (int64_t)(base + i - q) * urs;
+                        *p = base + i - q == brow ? piv : *p * ph;
+                    }
+                }
+            }
+        }
+    }
+}
+
+// TALL = false: rc_lowrank_recompress_complex_batched_*, and rc_lowrank_recompress_tall_complex_batched_* for m <= 512.  TALL = true:
+// rc_lowrank_recompress_tall_complex_batched_* for m > 512, the left factor by stages (see above; the plan keeps the stage copies out of LDS).
+// Two waves per SIMD (256 registers), but for the c64 tall instance, which is built for one wave per SIMD.  It fits 256 registers without
+// scratch, but the code the compiler makes under that bound is slower than what it makes with room to spare: 52.7k against 74.7k blocks/s at
+// 2048 x 2048 x 256, K = 32, and 49.9k against 68.7k at 512 x 8192 x 128, K = 16, at the same grid: the workspace bound leaves
+// one workgroup per CU at those shapes either way, and the kernel is latency-bound per Householder step.
+template <typename R, bool TALL>
+__global__ __launch_bounds__(BIC_THREADS, (TALL && sizeof(R) == 8) ? 1 : 2) void k_batched_recompress_c(BrcCArgs<R> a) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int m = (int)a.left.rows, n = (int)a.right.cols, K = (int)a.left.cols;
     const int kk = a.k < K ? a.k : K, ldg = a.ldg;
-    const int ldl = a.l_lds ? (m | 1) : m, ldr = a.r_lds ? (n | 1) : n, ldj = a.v_lds ? ldg : K;
-    cplx<R> *lp = reinterpret_cast<cplx<R> *>(smem_raw);                                                                // next free LDS element
-    cplx<R> *wp = a.ws + (size_t)blockIdx.x * brcc_ws_elems(m, n, K, ldg, a.l_lds, a.r_lds, a.v_lds, a.g_lds);      // next free workspace element
-    cplx<R> *Wl, *Wr, *G, *J;
-    if (a.l_lds) { Wl = lp; lp += (size_t)K * ldl; } else { Wl = wp; wp += (size_t)m * K; }
+    const int ldl = TALL ? BRT_H : a.l_lds ? (m | 1) : m, ldr = a.r_lds ? (n | 1) : n, ldj = a.v_lds ? ldg : K;
+    cplx<R> *lp = reinterpret_cast<cplx<R> *>(smem_raw);  // next free LDS element
+    cplx<R> *wp = a.ws + (size_t)blockIdx.x * (TALL ? brtc_ws_elems(m, n, K, ldg, a.l_lds, a.r_lds, a.v_lds, a.g_lds)
+                                                    : brcc_ws_elems(m, n, K, ldg, a.l_lds, a.r_lds, a.v_lds, a.g_lds));  // next free workspace element
+    cplx<R> *Wl0, *Wr, *G, *J;
+    if (a.l_lds) { Wl0 = lp; lp += (size_t)K * ldl; } else { Wl0 = wp; wp += TALL ? (size_t)brt_stages(m, K) * brt_stage_elems(K) : (size_t)m * K; }
     if (a.r_lds) { Wr = lp; lp += (size_t)K * ldr; } else { Wr = wp; wp += (size_t)n * K; }
     if (a.g_lds) { G = lp; lp += (size_t)K * ldg; } else { G = wp; wp += (size_t)K * ldg; }
     if (a.v_lds) { J = lp; lp += (size_t)K * ldj; } else { J = wp; }
@@ -794,8 +970,27 @@ __global__ __launch_bounds__(BIC_THREADS, 2) void k_batched_recompress_c(BrcCArg
         // ---- the two pivoted QRs, q steps each (exact zero pivots are steps with H = I), taus and pivots kept -----------------------
         const cplx<R> *__restrict__ L = a.left.p + (int64_t)b * a.lbs;
         const cplx<R> *__restrict__ Rt = a.right.p + (int64_t)b * a.rbs;
-        bic_load(Wl, ldl, m, q, a.left.rs <= a.left.cs, [&](int i, int c) { return L[i * a.left.rs + c * a.left.cs]; }, vn1, vn2, jpl, wv, lane);
-        bic_qrcp<R, true>(Wl, ldl, m, q, q, 0.0, jpl, vn1, vn2, red, tid, wv, lane, taul);
+        cplx<R> *Wl = Wl0;  // the copy the core and U read: the last stage's
+        [[maybe_unused]] int S = 1;
+        if constexpr (TALL) {
+            S = brt_stages(m, q);  // >= 2: m > BRT_H
+            const size_t se = brt_stage_elems(K);
+            for (int j = tid; j < q; j += BIC_THREADS) jpl[j] = j;  // ordered before its first read by brtc_stack_load's barrier
+            for (int s = 0; s < S; ++s) {
+                const int top = s ? q : 0, base = s ? BRT_H + (s - 1) * (BRT_H - q) : 0;
+                const int hs = top + min(BRT_H - top, m - base);
+                cplx<R> *Ws = Wl0 + (size_t)s * se, *ts = Ws + (size_t)BRT_H * K;
+                brtc_stack_load(Ws, ldl, Ws - (s ? se : 0), top, hs, q, a.left.rs <= a.left.cs,
+                                [&](int i, int c) { return L[(int64_t)(base + i) * a.left.rs + c * a.left.cs]; }, vn1, vn2, jpl, wv, lane);
+                bic_qrcp<R, true>(Ws, ldl, hs, q, q, 0.0, jpl, vn1, vn2, red, tid, wv, lane, ts);
+                int *js = reinterpret_cast<int *>(ts + K);  // the stage's pivots beside its taus; jpl goes on as the next stage's starting order
+                for (int j = tid; j < q; j += BIC_THREADS) js[j] = jpl[j];
+                Wl = Ws;
+            }
+        } else {
+            bic_load(Wl, ldl, m, q, a.left.rs <= a.left.cs, [&](int i, int c) { return L[i * a.left.rs + c * a.left.cs]; }, vn1, vn2, jpl, wv, lane);
+            bic_qrcp<R, true>(Wl, ldl, m, q, q, 0.0, jpl, vn1, vn2, red, tid, wv, lane, taul);
+        }
         bic_load(Wr, ldr, n, q, a.right.cs <= a.right.rs, [&](int i, int c) { return Rt[c * a.right.rs + i * a.right.cs]; }, vn1, vn2, jpr, wv, lane);
         bic_qrcp<R, true>(Wr, ldr, n, q, q, 0.0, jpr, vn1, vn2, red, tid, wv, lane, taur);
         for (int j = tid; j < q; j += BIC_THREADS) { ipl[jpl[j]] = j; ipr[jpr[j]] = j; }
@@ -883,7 +1078,8 @@ __global__ __launch_bounds__(BIC_THREADS, 2) void k_batched_recompress_c(BrcCArg
         __syncthreads();
         const int r = flag[1];
         // ---- U = Q_L [J_r; 0] with the phase rule applied to its columns, the phases kept in phs ------------------------------------------
-        if (m <= 64) bsc_form_u<R, 1>(Wl, ldl, J, ldj, m, q, kk, r, jpl, taul, srt, phs, true, Ub, a.u.rs, a.u.cs, wv, lane);
+        if constexpr (TALL) brtc_form_u<R>(Wl0, brt_stage_elems(K), S, K, q, m, J, ldj, kk, r, srt, phs, Ub, a.u.rs, a.u.cs, wv, lane);
+        else if (m <= 64) bsc_form_u<R, 1>(Wl, ldl, J, ldj, m, q, kk, r, jpl, taul, srt, phs, true, Ub, a.u.rs, a.u.cs, wv, lane);
         else if (m <= 128) bsc_form_u<R, 2>(Wl, ldl, J, ldj, m, q, kk, r, jpl, taul, srt, phs, true, Ub, a.u.rs, a.u.cs, wv, lane);
         else if (m <= 256) bsc_form_u<R, 4>(Wl, ldl, J, ldj, m, q, kk, r, jpl, taul, srt, phs, true, Ub, a.u.rs, a.u.cs, wv, lane);
         else bsc_form_u<R, 8>(Wl, ldl, J, ldj, m, q, kk, r, jpl, taul, srt, phs, true, Ub, a.u.rs, a.u.cs, wv, lane);
@@ -1139,6 +1335,19 @@ BatchedPlan<BrccPlace> brcc_plan(int m, int n, int K) {
         [&](BrccPlace p) { return brcc_ws_elems(m, n, K, p.ld, p.l, p.r, p.v, p.g) * sizeof(cplx<R>); }, "lowrank_recompress_batched");
 }
 
+// tall recompression: m <= BRT_H is brcc_plan; above it the stage copies are always in the slot (the copy of left never competes for LDS), Wr,
+// J and G by brcc_plan's rule, and the slot is brtc_ws_elems
+template <typename R>
+BatchedPlan<BrccPlace> brtc_plan(int m, int n, int K) {
+    if (m <= BRT_H) return brcc_plan<R>(m, n, K);
+    const int pad = ((K + 15) / 32) * 32 + 16, odd = K | 1;
+    const BrccPlace places[] = {{false, true, true, true, pad},     {false, true, true, true, odd},    {false, false, true, true, pad},
+                                {false, false, true, true, odd},    {false, false, false, true, pad},  {false, false, false, true, odd},
+                                {false, false, false, false, K}};
+    return batched_first_fit(places, [&](BrccPlace p) { return brcc_lds_bytes<R>(m, n, K, p.ld, p.l, p.r, p.v, p.g); },
+        [&](BrccPlace p) { return brtc_ws_elems(m, n, K, p.ld, p.l, p.r, p.v, p.g) * sizeof(cplx<R>); }, "lowrank_recompress_tall_complex_batched");
+}
+
 // sketched column ID: W (l x n complex) in LDS when it fits next to the chunk images, else in the workgroup's slot
 template <typename R>
 BatchedPlan<bool> bscid_plan(int l, int n) {
@@ -1197,20 +1406,30 @@ void batched_svd_c(rc_context *c, const rc_matrix &a_, int64_t abs, int32_t coun
     lch.launch(a, abs, (int)count, (int)k, tol, uo, uobs, vo, vobs, s, ranks, lch.template workspace<cplx<R>>(), c->health_word(), at.ld);
 }
 
-// One kernel: the plan only moves base pointers and pitches, and no sum depends on a pitch, so it cannot change a block's bits.
-template <typename R>
-void batched_lowrank_recompress_c(rc_context *c, const rc_matrix &left_, int64_t lbs, const rc_matrix &mid_, int64_t mbs, const R *s, int64_t s_stride,
-                                  const rc_matrix &right_, int64_t rbs, const int64_t *in_ranks, int32_t count, int64_t k, double tol, const rc_matrix &u_,
-                                  int64_t ubs, R *s_out, const rc_matrix &vt_, int64_t vbs, int64_t *ranks) {
+// The plan only moves base pointers and pitches, and no sum depends on a pitch, so it cannot change a block's bits.
+// TALL (rc_lowrank_recompress_tall_complex_batched_*): the same arguments and, for m <= 512, the same plan and the same kernel instance, so the
+// same bits at the same rate.  Above it the TALL instance runs and a slot holds every stage's copy (173 MiB at 65536 x 128 in c64), so the grid
+// is bounded a second time, by brt_grid_cap: few workgroups run there.
+template <typename R, bool TALL>
+void brcc_launch(rc_context *c, const rc_matrix &left_, int64_t lbs, const rc_matrix &mid_, int64_t mbs, const R *s, int64_t s_stride, const rc_matrix &right_,
+                 int64_t rbs, const int64_t *in_ranks, int32_t count, int64_t k, double tol, const rc_matrix &u_, int64_t ubs, R *s_out, const rc_matrix &vt_,
+                 int64_t vbs, int64_t *ranks) {
     const CV<R> left = view_of<R>(left_), mid = view_of<R>(mid_), right = view_of<R>(right_), u = view_of<R>(u_), vt = view_of<R>(vt_);
     const int m = (int)left.rows, n = (int)right.cols, K = (int)left.cols;
     if (count <= 0) return;
-    const auto plan = brcc_plan<R>(m, n, K);
+    const auto plan = TALL ? brtc_plan<R>(m, n, K) : brcc_plan<R>(m, n, K);
     const BrccPlace at = plan.at;
-    const auto lch = batched_prepare(c, k_batched_recompress_c<R>, "lowrank_recompress_batched", plan.lds, plan.ws, count);
-    ProfScope ps(c, "op:batched_recompress<complex> %dx%d k=%d count=%d grid=%lld slots=%lld plan=L:%s,R:%s,V:%s,G:%s,ld=%d,kk=%d%s%s", m, n, K, (int)count,
-                 (long long)lch.grid, (long long)lch.slots, at.l ? "lds" : "ws", at.r ? "lds" : "ws", at.v ? "lds" : "ws", at.g ? "lds" : "ws", at.ld,
-                 (int)std::min<int64_t>(k, K), mid.p ? ",mid" : "", s ? ",s" : "");
+    auto lch = batched_prepare(c, TALL && m > BRT_H ? k_batched_recompress_c<R, TALL> : k_batched_recompress_c<R, false>,
+                               TALL ? "lowrank_recompress_tall_complex_batched" : "lowrank_recompress_batched", plan.lds, plan.ws, count);
+    char stages[24] = "";
+    if constexpr (TALL) {
+        lch.grid = brt_grid_cap(lch.grid, plan.ws);
+        lch.slots = brt_grid_cap(lch.slots, plan.ws);
+        snprintf(stages, sizeof stages, "stages=%d,", brt_stages(m, K));  // inside plan=: the label keeps the family's fields
+    }
+    ProfScope ps(c, "op:batched_recompress%s<complex> %dx%d k=%d count=%d grid=%lld slots=%lld plan=%sL:%s,R:%s,V:%s,G:%s,ld=%d,kk=%d%s%s", TALL ? "_tall" : "", m,
+                 n, K, (int)count, (long long)lch.grid, (long long)lch.slots, stages, at.l ? "lds" : "ws", at.r ? "lds" : "ws", at.v ? "lds" : "ws",
+                 at.g ? "lds" : "ws", at.ld, (int)std::min<int64_t>(k, K), mid.p ? ",mid" : "", s ? ",s" : "");
     BrcCArgs<R> a;
     a.left = left; a.mid = mid; a.right = right; a.u = u; a.vt = vt;
     a.lbs = lbs; a.mbs = mbs; a.rbs = rbs; a.ubs = ubs; a.vbs = vbs; a.s_stride = s_stride;
@@ -1220,6 +1439,27 @@ void batched_lowrank_recompress_c(rc_context *c, const rc_matrix &left_, int64_t
     a.tol = tol; a.count = (int)count; a.k = (int)std::min<int64_t>(k, K); a.ldg = at.ld;
     a.l_lds = at.l; a.r_lds = at.r; a.v_lds = at.v; a.g_lds = at.g;
     lch.launch(a);
+}
+template <typename R>
+void batched_lowrank_recompress_c(rc_context *c, const rc_matrix &left, int64_t lbs, const rc_matrix &mid, int64_t mbs, const R *s, int64_t s_stride,
+                                  const rc_matrix &right, int64_t rbs, const int64_t *in_ranks, int32_t count, int64_t k, double tol, const rc_matrix &u,
+                                  int64_t ubs, R *s_out, const rc_matrix &vt, int64_t vbs, int64_t *ranks) {
+    brcc_launch<R, false>(c, left, lbs, mid, mbs, s, s_stride, right, rbs, in_ranks, count, k, tol, u, ubs, s_out, vt, vbs, ranks);
+}
+template <typename R>
+void batched_lowrank_recompress_tall_c(rc_context *c, const rc_matrix &left, int64_t lbs, const rc_matrix &mid, int64_t mbs, const R *s, int64_t s_stride,
+                                       const rc_matrix &right, int64_t rbs, const int64_t *in_ranks, int32_t count, int64_t k, double tol, const rc_matrix &u,
+                                       int64_t ubs, R *s_out, const rc_matrix &vt, int64_t vbs, int64_t *ranks) {
+    brcc_launch<R, true>(c, left, lbs, mid, mbs, s, s_stride, right, rbs, in_ranks, count, k, tol, u, ubs, s_out, vt, vbs, ranks);
+}
+
+// the complex tall launcher's plan as numbers (rc_lowrank_recompress_tall_complex_batched_plan): stages at inner width K, bytes of one slot, and
+// the grid brt_grid_cap leaves of `resident` workgroups
+void batched_lowrank_recompress_tall_c_plan(int64_t m, int64_t n, int64_t K, bool c64, int64_t resident, int64_t *stages, int64_t *slot_bytes, int64_t *grid) {
+    const size_t ws = c64 ? brtc_plan<double>((int)m, (int)n, (int)K).ws : brtc_plan<float>((int)m, (int)n, (int)K).ws;
+    *stages = brt_stages((int)m, (int)K);
+    *slot_bytes = (int64_t)ws;
+    *grid = brt_grid_cap(resident, ws);
 }
 
 // The plan only moves W's base pointer and pitch, so it cannot change a block's bits.  Four instances of the kernel, by the index of a and of
@@ -1274,5 +1514,11 @@ template void batched_lowrank_recompress_c<double>(rc_context *, const rc_matrix
 template void batched_lowrank_recompress_c<float>(rc_context *, const rc_matrix &, int64_t, const rc_matrix &, int64_t, const float *, int64_t,
                                                   const rc_matrix &, int64_t, const int64_t *, int32_t, int64_t, double, const rc_matrix &, int64_t, float *,
                                                   const rc_matrix &, int64_t, int64_t *);
+template void batched_lowrank_recompress_tall_c<double>(rc_context *, const rc_matrix &, int64_t, const rc_matrix &, int64_t, const double *, int64_t,
+                                                        const rc_matrix &, int64_t, const int64_t *, int32_t, int64_t, double, const rc_matrix &, int64_t,
+                                                        double *, const rc_matrix &, int64_t, int64_t *);
+template void batched_lowrank_recompress_tall_c<float>(rc_context *, const rc_matrix &, int64_t, const rc_matrix &, int64_t, const float *, int64_t,
+                                                       const rc_matrix &, int64_t, const int64_t *, int32_t, int64_t, double, const rc_matrix &, int64_t, float *,
+                                                       const rc_matrix &, int64_t, int64_t *);
 
 }  // namespace rc

@@ -1244,8 +1244,8 @@ BlockShape check_block_operator_apply(Mat<T> left, Mat<T> mid, Mat<T> right, int
 // and vt (min(k, K) x n)
 template <typename T>
 void check_lowrank_recompress_batched(Mat<T> left, Mat<T> mid, Mat<T> right, int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs, const T *s_out,
-                                      Mat<T> vt, int64_t vbs, const int64_t *ranks, bool tall) {
-    const char *who = tall ? "lowrank_recompress_tall_batched" : "lowrank_recompress_batched";
+                                      Mat<T> vt, int64_t vbs, const int64_t *ranks, int tall) {
+    const char *who = tall == RC_TALL_COMPLEX ? "lowrank_recompress_tall_complex_batched" : tall ? "lowrank_recompress_tall_batched" : "lowrank_recompress_batched";
     const int64_t m = left.rows, K = left.cols, n = right.cols;
     RC_REQUIRE(count >= 0, RC_INVALID_ARGUMENT, "%s: count = %d < 0", who, (int)count);
     RC_REQUIRE(m >= 1 && m <= (tall ? 65536 : 512) && n >= 1 && n <= 512 && K >= 1 && K <= 128 && k >= 1, RC_INVALID_ARGUMENT,
@@ -1320,9 +1320,9 @@ template BlockShape check_block_operator_apply<float>(Mat<float>, Mat<float>, Ma
 template void check_lowrank_residual_batched<double>(Mat<double>, Mat<double>, Mat<double>, Mat<double>, int32_t, Mat<double>, int64_t, const double *);
 template void check_lowrank_residual_batched<float>(Mat<float>, Mat<float>, Mat<float>, Mat<float>, int32_t, Mat<float>, int64_t, const float *);
 template void check_lowrank_recompress_batched<double>(Mat<double>, Mat<double>, Mat<double>, int32_t, int64_t, double, Mat<double>, int64_t, const double *,
-                                                       Mat<double>, int64_t, const int64_t *, bool);
+                                                       Mat<double>, int64_t, const int64_t *, int);
 template void check_lowrank_recompress_batched<float>(Mat<float>, Mat<float>, Mat<float>, int32_t, int64_t, double, Mat<float>, int64_t, const float *, Mat<float>,
-                                                      int64_t, const int64_t *, bool);
+                                                      int64_t, const int64_t *, int);
 
 template int64_t check_sketch_column_id_rank_batched<double>(Mat<double>, Mat<double>, int32_t, int64_t, double, Mat<double>, int64_t, Mat<double>, int64_t,
                                                              Mat<double>, int64_t, const int64_t *, const int64_t *);
@@ -1396,7 +1396,7 @@ template <typename T>
 void lowrank_recompress_tall_batched(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride, Mat<T> right, int64_t rbs,
                                      const int64_t *in_ranks, int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs, T *s_out, Mat<T> vt, int64_t vbs,
                                      int64_t *ranks) {
-    check_lowrank_recompress_batched(left, mid, right, count, k, tol, u, ubs, s_out, vt, vbs, ranks, true);
+    check_lowrank_recompress_batched(left, mid, right, count, k, tol, u, ubs, s_out, vt, vbs, ranks, RC_TALL);
     if (count == 0) return;
     batched_lowrank_recompress_tall(c, left, lbs, mid, mbs, s, s_stride, right, rbs, in_ranks, count, k, tol, u, ubs, s_out, vt, vbs, ranks);
 }
@@ -2046,6 +2046,20 @@ rc_status rc_lowrank_recompress_tall_batched_plan(int64_t m, int64_t n, int64_t 
         return RC_INVALID_ARGUMENT;
     try {
         batched_lowrank_recompress_tall_plan(m, n, inner, elem_bytes == 8, resident, stages, slot_bytes, grid);
+        return RC_OK;
+    } catch (const Error &e) {
+        return e.code;
+    }
+}
+
+// the complex tall recompression's plan as numbers (real_bytes 8: c64, 4: c32): the same domain, host arithmetic only
+rc_status rc_lowrank_recompress_tall_complex_batched_plan(int64_t m, int64_t n, int64_t inner, int32_t real_bytes, int64_t resident, int64_t *stages,
+                                                          int64_t *slot_bytes, int64_t *grid) {
+    if (!(m >= 1 && m <= 65536 && n >= 1 && n <= 512 && inner >= 1 && inner <= 128 && inner <= std::min(m, n)) || (real_bytes != 4 && real_bytes != 8) ||
+        resident < 1 || !stages || !slot_bytes || !grid)
+        return RC_INVALID_ARGUMENT;
+    try {
+        batched_lowrank_recompress_tall_c_plan(m, n, inner, real_bytes == 8, resident, stages, slot_bytes, grid);
         return RC_OK;
     } catch (const Error &e) {
         return e.code;

@@ -1,4 +1,4 @@
-// The launch path of the persistent batched kernels (host only): every launcher of kernels_batched_id.hip, kernels_batched_id_c.hip,
+// The launch path of the persistent batched kernels (host only, but for the tall recompressions' stage arithmetic): every launcher of kernels_batched_id.hip, kernels_batched_id_c.hip,
 // kernels_batched_apply.hip, kernels_block_operator.hip, kernels_batched_residual.hip and kernels_batched_residual_c.hip goes
 //     plan (a pure function of the shapes, in its own file)  ->  batched_prepare  ->  ProfScope  ->  workspace()  ->  launch(...)
 // so that the LDS cap, the grid rule, the workspace unit (bytes) and the launch check live here once.
@@ -21,6 +21,18 @@ int64_t bid_grid(rc_context *c, const void *kern, size_t lds, size_t ws_per, int
 // BID_MAX_LDS and its scratch bytes per thread are read.  Every call returns the latter; a thread that asks for the kernel it asked for
 // last gets the answer without the lock.
 int batched_kernel_cap(int device, const void *kern);
+
+// the tall recompressions (k_batched_recompress<T, true>, k_batched_recompress_c<R, true>): the stage height of their flat Householder TSQR,
+// the stages of an m-row left factor of inner rank q, one stage in the workgroup's slot in elements of the kernel's scalar (the copy, H x K at
+// pitch H, then taus[K] and pivots[K], the pivots as ints in K elements), and the launchers' own bound on the grid: the workspace of all
+// slots stays at or below 2 GiB, never below one workgroup
+constexpr int BRT_H = 512;
+__host__ __device__ inline int brt_stages(int m, int q) { return m <= BRT_H ? 1 : 1 + (m - BRT_H + (BRT_H - q) - 1) / (BRT_H - q); }
+__host__ __device__ inline size_t brt_stage_elems(int K) { return (size_t)BRT_H * K + 2 * (size_t)K; }
+constexpr size_t BRT_MAX_WS = (size_t)2 << 30;
+inline int64_t brt_grid_cap(int64_t grid, size_t ws_per) {
+    return ws_per ? std::min<int64_t>(grid, std::max<int64_t>(1, (int64_t)(BRT_MAX_WS / ws_per))) : grid;
+}
 
 // a launcher's plan: where its movable buffers live (Place: the launcher's own flags and core pitch), the dynamic LDS and the workspace
 // slot of one workgroup, both in bytes.  Every launcher computes it in a pure function of the shapes, the presence flags and the scalar type.

@@ -296,10 +296,18 @@ void batched_lowrank_recompress_tall_plan(int64_t m, int64_t n, int64_t K, bool 
 template <typename R> void batched_lowrank_recompress_c(rc_context *c, const rc_matrix &left, int64_t lbs, const rc_matrix &mid, int64_t mbs, const R *s,
                                                         int64_t s_stride, const rc_matrix &right, int64_t rbs, const int64_t *in_ranks, int32_t count, int64_t k,
                                                         double tol, const rc_matrix &u, int64_t ubs, R *s_out, const rc_matrix &vt, int64_t vbs, int64_t *ranks);
+// the same with a tall left factor (m <= 65536; k_batched_recompress_c<R, true>), and its plan as numbers like the real one's (c64: else c32)
+template <typename R> void batched_lowrank_recompress_tall_c(rc_context *c, const rc_matrix &left, int64_t lbs, const rc_matrix &mid, int64_t mbs, const R *s,
+                                                             int64_t s_stride, const rc_matrix &right, int64_t rbs, const int64_t *in_ranks, int32_t count,
+                                                             int64_t k, double tol, const rc_matrix &u, int64_t ubs, R *s_out, const rc_matrix &vt, int64_t vbs,
+                                                             int64_t *ranks);
+void batched_lowrank_recompress_tall_c_plan(int64_t m, int64_t n, int64_t K, bool c64, int64_t resident, int64_t *stages, int64_t *slot_bytes, int64_t *grid);
 // the argument checks of rc_lowrank_recompress_batched_* and rc_lowrank_recompress_complex_batched_* (rc_api.hip), shared by every scalar type like those
-// above; the caller returns when count == 0.  tall: rc_lowrank_recompress_tall_batched_*'s name and its bound m <= 65536
+// above; the caller returns when count == 0.  tall: the bound m <= 65536 under rc_lowrank_recompress_tall_batched_*'s name (RC_TALL) or
+// rc_lowrank_recompress_tall_complex_batched_*'s (RC_TALL_COMPLEX)
+enum { RC_NOT_TALL = 0, RC_TALL = 1, RC_TALL_COMPLEX = 2 };
 template <typename T> void check_lowrank_recompress_batched(Mat<T> left, Mat<T> mid, Mat<T> right, int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs,
-                                                            const T *s_out, Mat<T> vt, int64_t vbs, const int64_t *ranks, bool tall = false);
+                                                            const T *s_out, Mat<T> vt, int64_t vbs, const int64_t *ranks, int tall = RC_NOT_TALL);
 // the column ID of the sketch omega a of every block of a batch (kernels_batched_id.hip): block i is a (m x n), omega (l x m, l <= 128), y (l x n,
 // p == nullptr: not written), cm (m x kk) and z (kk x n) each moved by i times its batch stride (0 is legal for a and omega), kk = min(k, l, n) already
 // clamped; col_ind count x n, ranks count (arguments checked by the caller)

@@ -1402,6 +1402,22 @@ extern "C" {
                                             in_ranks, count, k, (double)tol, u, u_batch_stride, s_out, vt, vt_batch_stride, ranks);       \
         });                                                                                                                               \
     }                                                                                                                                     \
+    /* the same for tall left factors (m <= 65536; k_batched_recompress_c<R, true>), the checks under the call's own name */             \
+    rc_status rc_lowrank_recompress_tall_complex_batched_##SUF(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, \
+                                                               int64_t mid_batch_stride, const R *s, int64_t s_stride, rc_matrix right,   \
+                                                               int64_t right_batch_stride, const int64_t *in_ranks, int32_t count,        \
+                                                               int64_t k, R tol, rc_matrix u, int64_t u_batch_stride, R *s_out,           \
+                                                               rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks) {                   \
+        return guarded_c(ctx, [&] {                                                                                                       \
+            check_lowrank_recompress_batched<R>(shape_of<R>(left), shape_of<R>(mid), shape_of<R>(right), count, k, (double)tol,           \
+                                                shape_of<R>(u), u_batch_stride, s_out, shape_of<R>(vt), vt_batch_stride, ranks,           \
+                                                RC_TALL_COMPLEX);                                                                         \
+            if (count == 0) return;                                                                                                       \
+            batched_lowrank_recompress_tall_c<R>(ctx, left, left_batch_stride, mid, mid_batch_stride, s, s_stride, right,                 \
+                                                 right_batch_stride, in_ranks, count, k, (double)tol, u, u_batch_stride, s_out, vt,       \
+                                                 vt_batch_stride, ranks);                                                                 \
+        });                                                                                                                               \
+    }                                                                                                                                     \
     /* the sketched column ID of complex tall blocks (kernels_batched_id_c.hip): the real entry point's checks on views of the same */   \
     /* shapes; y = omega a with nothing conjugated */                                                                                     \
     rc_status rc_sketch_column_id_rank_complex_batched_##SUF(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega,       \

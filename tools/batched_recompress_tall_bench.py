@@ -9,7 +9,12 @@ of --repeats).  The stages and the plan of the launch are read from the event pr
 rc_lowrank_recompress_batched_*: the same work per block, so the ratio of the two times is recorded, with a check that the bits agree.
 Writes profiles/batched_recompress_tall_bench.json unless --out names another file.  Not used by the tests or by bench.py.
 
-    python tools/batched_recompress_tall_bench.py [--repeats 5] [--shapes 0,1,2,3] [--out path.json]
+--complex measures rc_lowrank_recompress_tall_complex_batched_* at the same shapes in c64 / c32 (complex Gaussian factors, the same real s)
+against the complex composition (torch.linalg.qr on complex left, rc_lowrank_recompress_complex_batched_*, torch.bmm), against the real tall
+call at the same shape and precision (the real parts of the same factors), and at m <= 512 against the existing complex call on the same
+arguments; it writes profiles/batched_recompress_tall_complex_bench.json.
+
+    python tools/batched_recompress_tall_bench.py [--complex] [--repeats 5] [--shapes 0,1,2,3] [--out path.json]
 """
 import argparse
 import json
@@ -38,18 +43,26 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--shapes", default=None)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--complex", action="store_true", dest="complex_data")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("needs an MI355X")
-    out_path = args.out or os.path.join(ROOT, "profiles", "batched_recompress_tall_bench.json")
+    cx = args.complex_data
+    out_path = args.out or os.path.join(ROOT, "profiles", "batched_recompress_tall_complex_bench.json" if cx else "batched_recompress_tall_bench.json")
+    tall = rc.lowrank_recompress_tall_batched_complex if cx else rc.lowrank_recompress_tall_batched
+    existing = rc.lowrank_recompress_batched_complex if cx else rc.lowrank_recompress_batched
     results = []
     for si in [int(x) for x in (args.shapes or ",".join(str(i) for i in range(len(SHAPES)))).split(",")]:
         count, m, n, kin, k, dtype = SHAPES[si]
         g = torch.Generator(device="cuda").manual_seed(97531 + si)
-        left = (torch.randn(count, m, kin, generator=g, device="cuda", dtype=torch.float64) / m ** 0.5).to(dtype)
-        right = (torch.randn(count, kin, n, generator=g, device="cuda", dtype=torch.float64) / n ** 0.5).to(dtype)
-        s = torch.logspace(0, -6, kin // 2, device="cuda", dtype=torch.float64).repeat(2).to(dtype).expand(count, kin).contiguous()
-        fn = lambda: rc.lowrank_recompress_tall_batched(left, right, k, 0.0, s=s)  # noqa: E731
+        real_dtype = dtype
+        if cx:  # complex Gaussian columns of unit expected norm; s stays real
+            dtype = torch.complex128 if dtype == torch.float64 else torch.complex64
+        gen = torch.complex128 if cx else torch.float64
+        left = (torch.randn(count, m, kin, generator=g, device="cuda", dtype=gen) / m ** 0.5).to(dtype)
+        right = (torch.randn(count, kin, n, generator=g, device="cuda", dtype=gen) / n ** 0.5).to(dtype)
+        s = torch.logspace(0, -6, kin // 2, device="cuda", dtype=torch.float64).repeat(2).to(real_dtype).expand(count, kin).contiguous()
+        fn = lambda: tall(left, right, k, 0.0, s=s)  # noqa: E731
         (u, sv, vt, ranks), label = batched_launch(fn)  # warm-up (code objects, workspace) and the plan
         torch.cuda.synchronize()
         t_med, t_min, t_max = timed(fn, args.repeats)
@@ -60,18 +73,26 @@ def main():
 
         def composition():
             q, r = torch.linalg.qr(left)
-            cu, cs, cvt, cr = rc.lowrank_recompress_batched(r, right, k, 0.0, s=s)
+            cu, cs, cvt, cr = existing(r, right, k, 0.0, s=s)
             return torch.bmm(q, cu), cs, cvt, cr
 
         cu, cs, cvt, _ = composition()
         torch.cuda.synchronize()
         c_med, c_min, c_max = timed(composition, args.repeats)
-        row.update(composition="torch.linalg.qr + lowrank_recompress_batched + torch.bmm", composition_s=c_med, composition_s_min=c_min, composition_s_max=c_max,
+        row.update(composition="torch.linalg.qr + lowrank_recompress_batched%s + torch.bmm" % ("_complex" if cx else ""), composition_s=c_med, composition_s_min=c_min, composition_s_max=c_max,
                    composition_blocks_per_s=count / c_med, speedup_vs_composition=c_med / t_med,
                    max_abs_sval_diff_vs_composition=float((sv[:, :k] - cs[:, :k]).abs().max()), max_sval=float(cs[:, 0].max()))
         del cu, cs, cvt
+        if cx:  # the real tall call at the same shape and precision
+            rl, rr = left.real.contiguous(), right.real.contiguous()
+            rfn = lambda: rc.lowrank_recompress_tall_batched(rl, rr, k, 0.0, s=s)  # noqa: E731
+            rfn()
+            torch.cuda.synchronize()
+            r_med, r_min, r_max = timed(rfn, args.repeats)
+            row.update(real_tall_s=r_med, real_tall_s_min=r_min, real_tall_s_max=r_max, time_vs_real_tall=t_med / r_med)
+            del rl, rr
         if m <= 512:
-            pfn = lambda: rc.lowrank_recompress_batched(left, right, k, 0.0, s=s)  # noqa: E731
+            pfn = lambda: existing(left, right, k, 0.0, s=s)  # noqa: E731
             (pu, ps, pvt, pr), plabel = batched_launch(pfn)
             torch.cuda.synchronize()
             p_med, p_min, p_max = timed(pfn, args.repeats)
@@ -85,7 +106,7 @@ def main():
         print(json.dumps(row), flush=True)
         del left, right, s, u, sv, vt, ranks
         torch.cuda.empty_cache()
-    out = dict(tool="tools/batched_recompress_tall_bench.py", device=torch.cuda.get_device_name(0), results=results)
+    out = dict(tool="tools/batched_recompress_tall_bench.py" + (" --complex" if cx else ""), device=torch.cuda.get_device_name(0), results=results)
     with open(out_path, "w") as f:
         json.dump(out, f, indent=1)
     print("wrote", out_path)
