@@ -763,6 +763,85 @@ template <typename T>
 BatchedSVD<T> recompress_tall_batched(const BatchedColumnID<T> &id, int64_t k, double tol = 0.0) {
     return recompress_tall_batched<T>(id.c, nullptr, nullptr, id.z, &id.ranks, (int32_t)id.ranks.size(), k, tol);
 }
+// one range step of a power iteration on `count` tall m x n blocks stacked in `a` (rc_sketch_range_step_batched_*, real scalars): per block
+// the sketch omega a_i (l x n), an orthonormal basis q_i (l x n) of its rows and the projection p_i = a_i q_i^T (m x l); q is count * l x n, p
+// count * m x l, ranks[i] the number of nonzero rows of q_i.  `sketch`, when given, receives the count * l x n sketches.  The _view form takes
+// block 0's test matrix as a view and its batch stride (0: shared), so that a strided U^T can be the next omega without a copy.
+template <typename T> struct RangeStepApi;
+template <> struct RangeStepApi<double> {
+    static constexpr auto range_step = rc_sketch_range_step_batched_f64;
+    static constexpr auto sketch_id = rc_sketch_column_id_rank_batched_f64;
+    static constexpr auto recompress_tall = rc_lowrank_recompress_tall_batched_f64;
+};
+template <> struct RangeStepApi<float> {
+    static constexpr auto range_step = rc_sketch_range_step_batched_f32;
+    static constexpr auto sketch_id = rc_sketch_column_id_rank_batched_f32;
+    static constexpr auto recompress_tall = rc_lowrank_recompress_tall_batched_f32;
+};
+template <typename T>
+struct BatchedRangeStep {
+    DeviceMatrix<T> q, p;
+    DeviceIndex ranks;
+};
+template <typename T>
+BatchedRangeStep<T> range_step_batched_view(const DeviceMatrix<T> &a, rc_matrix omega, int64_t omega_batch_stride, int32_t count,
+                                            DeviceMatrix<T> *sketch = nullptr) {
+    const Context &ctx = a.ctx();
+    const int64_t m = count > 0 ? a.nrows() / count : 0, n = a.ncols(), l = omega.rows;
+    BatchedRangeStep<T> out{DeviceMatrix<T>(ctx, (int64_t)count * l, n), DeviceMatrix<T>(ctx, (int64_t)count * m, l), DeviceIndex(ctx, (std::size_t)count)};
+    if (sketch) *sketch = DeviceMatrix<T>(ctx, (int64_t)count * l, n);
+    ctx.check(RangeStepApi<T>::range_step(ctx.raw(), rc_matrix{a.view().data, m, n, n, 1}, m * n, omega, omega_batch_stride, count,
+                                          sketch ? rc_matrix{sketch->view().data, l, n, n, 1} : rc_matrix{nullptr, 0, 0, 0, 0}, l * n,
+                                          rc_matrix{out.q.view().data, l, n, n, 1}, l * n, rc_matrix{out.p.view().data, m, l, l, 1}, m * l,
+                                          out.ranks.data()));
+    return out;
+}
+template <typename T>
+BatchedRangeStep<T> range_step_batched(const DeviceMatrix<T> &a, const DeviceMatrix<T> &omega, int32_t count, DeviceMatrix<T> *sketch = nullptr) {
+    return range_step_batched_view(a, omega.view(), 0, count, sketch);
+}
+// the sketched column_id_rank_batched after `iterations` rounds of power iteration on the shared test matrix omega (l x m), both half-steps
+// orthonormalised as in sample_range_power_iteration (src/random_sampling.rs:131-158): per round the range step, then p orthonormalised by
+// rc_lowrank_recompress_tall_batched_* with right = I at the step's ranks, whose u^T (a strided view) is the next, per-block, omega; two
+// launches per round and one for the ID.  The C calls never synchronise; this mirror owns the intermediate buffers, so it waits once per
+// round before it releases them.  iterations = 0 is column_id_rank_batched(a, omega, ...).
+template <typename T>
+BatchedColumnID<T> column_id_rank_power_batched(const DeviceMatrix<T> &a, const DeviceMatrix<T> &omega, int32_t count, int64_t k, double tol = 0.0,
+                                                int iterations = 1, DeviceMatrix<T> *sketch = nullptr) {
+    if (iterations <= 0) return column_id_rank_batched(a, omega, count, k, tol, sketch);
+    const Context &ctx = a.ctx();
+    const int64_t m = count > 0 ? a.nrows() / count : 0, n = a.ncols(), l = omega.nrows();
+    std::vector<T> heye((std::size_t)(l * l), (T)0);
+    for (int64_t i = 0; i < l; ++i) heye[(std::size_t)(i * l + i)] = (T)1;
+    const DeviceMatrix<T> eye = DeviceMatrix<T>::from_host(ctx, heye.data(), l, l);
+    DeviceMatrix<T> u(ctx, (int64_t)count * m, l), vt(ctx, (int64_t)count * l, l);
+    DeviceBuffer<T> s(ctx, (std::size_t)count * (std::size_t)l);
+    DeviceIndex uranks(ctx, (std::size_t)count);
+    rc_matrix om = omega.view();
+    int64_t obs = 0;
+    for (int it = 0; it < iterations; ++it) {
+        const BatchedRangeStep<T> step = range_step_batched_view(a, om, obs, count);
+        DeviceMatrix<T> un(ctx, (int64_t)count * m, l);
+        ctx.check(RangeStepApi<T>::recompress_tall(ctx.raw(), rc_matrix{step.p.view().data, m, l, l, 1}, m * l, rc_matrix{nullptr, 0, 0, 0, 0}, 0, nullptr, 0,
+                                                   rc_matrix{eye.view().data, l, l, l, 1}, 0, step.ranks.data(), count, l, 0.0,
+                                                   rc_matrix{un.view().data, m, l, l, 1}, m * l, s.data(), rc_matrix{vt.view().data, l, l, l, 1}, l * l,
+                                                   uranks.data()));
+        ctx.synchronize();  // step's buffers and the previous u are released here
+        u = std::move(un);
+        om = rc_matrix{u.view().data, l, m, 1, l};
+        obs = m * l;
+    }
+    const int64_t ln = l < n ? l : n, kk = k < ln ? k : ln;
+    BatchedColumnID<T> out{DeviceMatrix<T>(ctx, (int64_t)count * m, kk), DeviceMatrix<T>(ctx, (int64_t)count * kk, n),
+                           DeviceIndex(ctx, (std::size_t)count * (std::size_t)n), DeviceIndex(ctx, (std::size_t)count)};
+    if (sketch) *sketch = DeviceMatrix<T>(ctx, (int64_t)count * l, n);
+    ctx.check(RangeStepApi<T>::sketch_id(ctx.raw(), rc_matrix{a.view().data, m, n, n, 1}, m * n, om, obs, count, k, tol,
+                                         sketch ? rc_matrix{sketch->view().data, l, n, n, 1} : rc_matrix{nullptr, 0, 0, 0, 0}, l * n,
+                                         rc_matrix{out.c.view().data, m, kk, kk, 1}, m * kk, rc_matrix{out.z.view().data, kk, n, n, 1}, kk * n,
+                                         out.col_ind.data(), out.ranks.data()));
+    ctx.synchronize();  // u, the last omega, is released on return
+    return out;
+}
 // a batched column ID, a batched two-sided ID as truncated SVDs, each block from its own rank
 template <typename T>
 BatchedSVD<T> recompress_batched(const BatchedColumnID<T> &id, int64_t k, double tol = 0.0) {

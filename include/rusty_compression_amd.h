@@ -691,6 +691,24 @@ rc_status rc_lowrank_recompress_tall_complex_batched_plan(int64_t m, int64_t n, 
  * workspace bounded by the grid, not by count. */
 rc_status rc_sketch_column_id_rank_batched_f64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega, int64_t omega_batch_stride, int32_t count, int64_t k, double tol, rc_matrix y, int64_t y_batch_stride, rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks);
 rc_status rc_sketch_column_id_rank_batched_f32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega, int64_t omega_batch_stride, int32_t count, int64_t k, double tol, rc_matrix y, int64_t y_batch_stride, rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks);
+/* One range step of a power iteration on every tall block of a batch, in one stream-ordered, capturable call (the two products of one
+ * round of sample_range_power_iteration, src/random_sampling.rs:131-158, with the orthonormalisation between them).  Per block a_i (m x n)
+ * and test matrix omega_i (l x m): the sketch Y_i = omega_i a_i (l x n), formed exactly as rc_sketch_column_id_rank_batched_* forms it (y,
+ * when requested, equals that call's y bit for bit); q_i (l x n), an orthonormal basis of Y_i's rows from a column-pivoted Householder QR of
+ * Y_i^T: rows 0 .. r-1 are orthonormal and span the rows of Y_i, rows r .. l-1 are exactly zero, where ranks[i] = r is the first step
+ * whose R_jj is exactly zero or not finite (else l; there is no tolerance here, truncation belongs to the call that ends the chain); and
+ * the projection p_i = a_i q_i^T (m x l), whose columns r .. l-1 are exactly zero.  a streams through the chip twice.  To continue a power
+ * iteration, orthonormalise p with rc_lowrank_recompress_tall_batched_* (right = I, k = l, tol = 0, in_ranks = ranks) and pass u^T as the
+ * next omega; rc_lowrank_recompress_tall_batched_*(left = p, right = q, in_ranks = ranks) turns the pair into a truncated SVD of a ~ p q.
+ * Domain: 1 <= n <= 512, 1 <= m <= 65536, 1 <= l <= min(128, m, n), count >= 0.  Any row and column strides on every view; batch
+ * strides of 0 are legal for a and omega (one omega shared by all blocks); y.data == NULL: the sketch is not written, and the other outputs
+ * do not depend on that.  Outputs must not overlap inputs or one another.  Block i's bits depend on block i's a and omega and the
+ * call's shapes alone.  Non-finite input stays inside its block's outputs, with 0 <= ranks[i] <= l.  RC_INVALID_ARGUMENT for an argument
+ * outside the domain, omega.cols != a.rows, a wrong y, q or p shape, an output batch stride smaller than one view's span when count > 1, a
+ * null a, omega, q, p or ranks with count > 0, or a null ctx (rejected before a device is touched).  No host synchronisation; workspace
+ * bounded by the grid, not by count.  Real scalars only. */
+rc_status rc_sketch_range_step_batched_f64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega, int64_t omega_batch_stride, int32_t count, rc_matrix y, int64_t y_batch_stride, rc_matrix q, int64_t q_batch_stride, rc_matrix p, int64_t p_batch_stride, int64_t *ranks);
+rc_status rc_sketch_range_step_batched_f32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega, int64_t omega_batch_stride, int32_t count, rc_matrix y, int64_t y_batch_stride, rc_matrix q, int64_t q_batch_stride, rc_matrix p, int64_t p_batch_stride, int64_t *ranks);
 /* The complex twin of rc_sketch_column_id_rank_batched_*: the one-pass randomized column ID of every complex tall block of a batch, in one
  * stream-ordered, capturable call: the sketch Y_i = omega_i a_i (l x n) of each block a_i (m x n) is formed while a_i streams through the chip once,
  * and the column ID of the small Y_i gives the pivots and Z; C is gathered from a_i.  Nothing is conjugated: a caller who wants Q^H a passes

@@ -975,6 +975,117 @@ def sketch_svd_rank_batched_complex(a: torch.Tensor, k: int, tol: float = 0.0, o
     return column_id_to_svd_tall_batched_complex(c, z, ranks, k, tol)
 
 
+def sketch_range_step_batched(a: torch.Tensor, omega: Optional[torch.Tensor] = None, oversampling: int = 8, k: Optional[int] = None, seed: int = 0,
+                              return_sketch: bool = False):
+    """One range step of a power iteration on `count` tall same-shaped blocks in one stream-ordered call (rc_sketch_range_step_batched_*):
+    per block the sketch Y = omega a (l x n, sketch_column_id_rank_batched's bit for bit), an orthonormal basis Q (l x n) of Y's rows from a
+    column-pivoted Householder QR of Y^T, and the projection P = a Q^T (m x l); the two products of one round of the reference's
+    sample_range_power_iteration (src/random_sampling.rs:131-158) with the orthonormalisation between them.
+
+    a: [count, m, n] device tensor of float64 or float32, any strides (m <= 65536, n <= 512).  omega: [l, m] (shared by the batch) or
+    [count, l, m], l <= min(128, m, n), a's dtype, any strides; None draws the shared Gaussian omega of sketch_column_id_rank_batched(a, k,
+    oversampling=oversampling, seed=seed), l = min(k + oversampling, 128) rows.  Returns Q [count, l, n], P [count, m, l], ranks [count] and,
+    with return_sketch, Y [count, l, n]: rows of Q below a block's rank r are orthonormal, rows of Q and columns of P from r on are exactly
+    zero; r is the first step whose R_jj is exactly zero or not finite, else l (no tolerance: truncation belongs to the call that ends the
+    chain).  Complex data and mismatched dtypes raise TypeError."""
+    from . import _lib
+    from .types import as_device
+
+    who = "sketch_range_step_batched"
+    a = as_device(a)
+    if a.dtype not in (torch.float64, torch.float32):
+        raise TypeError(f"{who}: float64 or float32 data expected, got {a.dtype}")
+    if a.dim() != 3:
+        raise AssertionError("expected a [count, m, n] batch")
+    count, m, n = a.shape
+    if omega is None:
+        from .random_matrix import Rng, random_gaussian
+
+        if k is None:
+            raise AssertionError(f"{who}: k is needed to draw the default omega")
+        omega = random_gaussian((max(min(int(k) + int(oversampling), 128), 1), m), Rng(int(seed)), a.dtype)
+    omega = as_device(omega)
+    if omega.dtype != a.dtype:
+        raise TypeError(f"{who}: omega is {omega.dtype}, a is {a.dtype}")
+    if omega.dim() not in (2, 3) or (omega.dim() == 3 and omega.shape[0] != count):
+        raise AssertionError("expected omega [l, m] or [count, l, m]")
+    l = omega.shape[-2]
+    obs = omega.stride(0) if omega.dim() == 3 else 0
+    q = torch.empty((count, l, n), dtype=a.dtype, device=a.device)
+    p = torch.empty((count, m, l), dtype=a.dtype, device=a.device)
+    ranks = torch.empty(count, dtype=torch.int64, device=a.device)
+    y = torch.empty((count, l, n), dtype=a.dtype, device=a.device) if return_sketch else None
+    _lib.default_context().call("rc_sketch_range_step_batched_" + _lib.suffix(a.dtype),
+                                _lib.rc_matrix(a.data_ptr(), m, n, a.stride(1), a.stride(2)), ctypes.c_int64(a.stride(0)),
+                                _lib.rc_matrix(omega.data_ptr(), l, omega.shape[-1], omega.stride(-2), omega.stride(-1)), ctypes.c_int64(obs),
+                                ctypes.c_int32(count),
+                                _lib.rc_matrix(y.data_ptr(), l, n, n, 1) if return_sketch else _lib.mat(None), ctypes.c_int64(l * n),
+                                _lib.rc_matrix(q.data_ptr(), l, n, n, 1), ctypes.c_int64(l * n),
+                                _lib.rc_matrix(p.data_ptr(), m, l, l, 1), ctypes.c_int64(m * l), _lib.i64p(ranks))
+    return (q, p, ranks, y) if return_sketch else (q, p, ranks)
+
+
+def _power_iteration_batched(a: torch.Tensor, omega: Optional[torch.Tensor], k: int, oversampling: int, seed: int) -> torch.Tensor:
+    """One full power iteration: the range step, then P orthonormalised by the tall recompression with right = I at the step's ranks (zero
+    singular values give exactly zero columns); U^T, a strided view, is the next omega.  Two launches, nothing on the host between them."""
+    _, p, ranks = sketch_range_step_batched(a, omega, oversampling, k, seed)
+    l = p.shape[2]
+    eye = torch.eye(l, dtype=p.dtype, device=p.device).expand(p.shape[0], l, l)
+    u, _, _, _ = lowrank_recompress_tall_batched(p, eye, l, 0.0, ranks=ranks)
+    return u.mT
+
+
+def sketch_power_omega_batched(a: torch.Tensor, k: int, power_iterations: int, omega: Optional[torch.Tensor] = None, oversampling: int = 8,
+                               seed: int = 0) -> torch.Tensor:
+    """The test matrix after `power_iterations` rounds of the reference's sample_range_power_iteration (src/random_sampling.rs:131-158) on every
+    block of a batch, both half-steps orthonormalised: per round sketch_range_step_batched, then lowrank_recompress_tall_batched(p, I, k=l,
+    tol=0, ranks=the step's ranks), whose U^T (a strided view, no copy) is the next omega.  Two launches per round and no host
+    synchronisation.  a, omega, k, oversampling and seed as sketch_range_step_batched.  Returns omega_q [count, l, m], whose rows are
+    orthonormal (exactly zero past a block's rank); with power_iterations = 0 the omega given or drawn is returned unchanged ([l, m] when
+    shared).  Complex data raises TypeError."""
+    from .types import as_device
+
+    a = as_device(a)
+    if a.dtype not in (torch.float64, torch.float32):
+        raise TypeError(f"sketch_power_omega_batched: float64 or float32 data expected, got {a.dtype}")
+    if int(power_iterations) < 0:
+        raise AssertionError("sketch_power_omega_batched: power_iterations must be >= 0")
+    if omega is None:
+        from .random_matrix import Rng, random_gaussian
+
+        omega = random_gaussian((max(min(int(k) + int(oversampling), 128), 1), a.shape[-2]), Rng(int(seed)), a.dtype)
+    for _ in range(int(power_iterations)):
+        omega = _power_iteration_batched(a, omega, k, oversampling, seed)
+    return omega
+
+
+def sketch_column_id_rank_power_batched(a: torch.Tensor, k: int, tol: float = 0.0, power_iterations: int = 1, omega: Optional[torch.Tensor] = None,
+                                        oversampling: int = 8, seed: int = 0, return_sketch: bool = False):
+    """sketch_column_id_rank_batched after `power_iterations` rounds of power iteration on the test matrix: sketch_power_omega_batched(a, k,
+    power_iterations, omega, oversampling, seed), then sketch_column_id_rank_batched(a, k, tol, that omega).  On slowly decaying spectra
+    one round roughly halves the error of the one-pass call; more add little.  The return tuple is sketch_column_id_rank_batched's;
+    power_iterations = 0 is that function on the same arguments, bit for bit.  2 q + 1 launches, no host synchronisation.  The power
+    rounds need l <= min(128, m, n).  Complex data raises TypeError."""
+    if int(power_iterations) == 0:
+        return sketch_column_id_rank_batched(a, k, tol, omega, oversampling, seed, return_sketch)
+    omega_q = sketch_power_omega_batched(a, k, power_iterations, omega, oversampling, seed)
+    return sketch_column_id_rank_batched(a, k, tol, omega_q, oversampling, seed, return_sketch)
+
+
+def sketch_svd_rank_power_batched(a: torch.Tensor, k: int, tol: float = 0.0, power_iterations: int = 1, omega: Optional[torch.Tensor] = None,
+                                  oversampling: int = 8, seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Batched randomized SVDs of tall blocks with power iteration: power_iterations - 1 full rounds (sketch_power_omega_batched), one more
+    range step (Q, P = a Q^T, ranks), then lowrank_recompress_tall_batched(left=P, right=Q, ranks=the step's ranks, k, tol): the
+    reference's svd_from_range_estimate on a ~ (a Q^T) Q.  Returns (U [count, m, kk], S [count, l], Vt [count, kk, n], ranks), kk = min(k, l).
+    power_iterations = 0 delegates to sketch_svd_rank_batched on the same arguments.  2 q launches, no host synchronisation.  Complex data
+    raises TypeError."""
+    if int(power_iterations) == 0:
+        return sketch_svd_rank_batched(a, k, tol, omega, oversampling, seed)
+    omega_q = sketch_power_omega_batched(a, k, int(power_iterations) - 1, omega, oversampling, seed)
+    q, p, ranks = sketch_range_step_batched(a, omega_q, oversampling, k, seed)
+    return lowrank_recompress_tall_batched(p, q, k, tol, ranks=ranks)
+
+
 def packed_bytes(m: int, n: int, k: int, elem_size: int) -> int:
     """Bytes one matrix's factors take in the packed buffer: C (m x k) | Z (k x n) | pad to 8 | col_ind (n int64)
     (rc_batch_packed_bytes)."""

@@ -29,6 +29,9 @@
 // Batched sketched column ID (rc_sketch_column_id_rank_batched_*): k_batched_sketch_id, the same grid; the working copy is the sketch
 // Omega A (l x n, l <= 128) formed by MFMA while A streams through LDS once, then the same stages on l rows (see its comment below).
 //
+// Batched range step (rc_sketch_range_step_batched_*): k_batched_range_step, the same grid; that sketch stored as Y^T, its pivoted QR run to
+// all l steps, Q formed explicitly and the projection A Q^T by the sketch routine on A's transposed view (see its comment below).
+//
 // The launchers at the end of the file follow rc_batched_launch.hpp: a plan function per entry point, then prepare, label, workspace,
 // launch.  bid_grid and the first-use LDS cap of the whole batched family are defined here.
 #include <map>
@@ -1031,7 +1034,10 @@ struct BsiArgs {
 // W[c * ldw + i] = Y[i, c] = sum_r Om[i, r] A[r, c] for the l x n sketch of one block (and Y to Yb when it is not null).
 // AR / OR: the lanes of the staging loads run along the rows of a / of omega (the operand's smaller stride), else along its columns;
 // each thread's elements of a chunk are then a fixed step apart in memory and in the LDS image, whose offsets are compile-time constants.
-template <typename T, int TL, bool AR, bool OR>
+// WM: where the sketch goes besides Yb.  BSI_W_COLS: W[c * ldw + i] as above; BSI_W_ROWS: W[i * ldw + c], the working copy of Y^T
+// (k_batched_range_step's row basis); BSI_W_NONE: W is not written (its projection, whose l x m "sketch" only goes to Yb).
+enum { BSI_W_COLS = 0, BSI_W_ROWS = 1, BSI_W_NONE = 2 };
+template <typename T, int TL, bool AR, bool OR, int WM = BSI_W_COLS>
 __device__ __forceinline__ void bsi_sketch(const BsiArgs<T> &g, const T *__restrict__ A, const T *__restrict__ Om, T *Yb, T *W, int ldw, T *As, T *Os, int tid,
                                            int wv, int lane) {
     constexpr int PO = bsi_po(16 * TL);
@@ -1095,7 +1101,8 @@ __device__ __forceinline__ void bsi_sketch(const BsiArgs<T> &g, const T *__restr
                 const int row = i * 16 + Acc<T>::row(lane, reg);
                 if (row < l && col < n) {
                     const T v = acc[i][reg];
-                    W[(size_t)col * ldw + row] = v;
+                    if constexpr (WM == BSI_W_COLS) W[(size_t)col * ldw + row] = v;
+                    if constexpr (WM == BSI_W_ROWS) W[(size_t)row * ldw + col] = v;
                     if (Yb) Yb[row * g.y.rs + col * g.y.cs] = v;
                 }
             }
@@ -1158,6 +1165,149 @@ __global__ __launch_bounds__(BID_THREADS, 2) void k_batched_sketch_id(BsiArgs<T>
     }
 }
 
+// ---- batched range step (rc_sketch_range_step_batched_*) ------------------------------------------------------------------------------
+// One half-iteration pair of the reference's sample_range_power_iteration (src/random_sampling.rs:131-158) per block, without the second
+// orthonormalisation (rc_lowrank_recompress_tall_batched_* with right = I does that to p): the sketch Y = Omega A by bsi_sketch, the same
+// instances as k_batched_sketch_id but stored as the working copy of Y^T (n x l, column i = row i of Y); the pivoted Householder QR of
+// Y^T by bid_qrcp run to all l steps with the reflectors kept; the rank r, the first step whose R_jj is exactly zero or not finite; Q
+// (l x n) formed explicitly, row c = (H_0 .. H_c e_c)^T for c < r and exactly zero from r on, written to q and, n fastest, to the
+// workgroup's slot; then the projection P^T = Q A^T, which is bsi_sketch once more on the transposed view of A with the slot's Q as the test
+// matrix (the lanes of its staging loads along n) and P^T's only destination the transposed view of p.  So an element of P is one MFMA
+// accumulator chain from zero over ascending column index of A, four columns per instruction, and a zero row of Q is a zero column of P.
+// A streams from HBM twice; Q is re-read per 64-row panel of A from L2, as Omega is per column panel in the sketch.
+// dynamic LDS: [W: l x (n|1), LDS plan only] A chunk [BSI_A_ELEMS] Omega chunk [bsi_o_elems(l)] vn1[l] vn2[l] taus[l] red[8] | jp[l] rk[4]
+// slot: Q [l x n] [W: l x n, workspace plan only]
+template <typename T>
+size_t brs_lds_bytes(int l, int n, bool in_lds) {
+    size_t t = (size_t)BSI_A_ELEMS + (size_t)bsi_o_elems(l) + (size_t)3 * l + 8;
+    if (in_lds) t += (size_t)l * (size_t)(n | 1);
+    return t * sizeof(T) + (size_t)(l + 4) * sizeof(int);
+}
+
+template <typename T>
+struct BrsArgs {
+    Mat<T> a, omega, y, q, p;  // y.p == nullptr: the sketch is not written
+    int64_t abs, obs, ybs, qbs, pbs;
+    int64_t *ranks;
+    T *ws;
+    size_t slot;  // elements of one workgroup's slot
+    int count;
+    bool w_lds;   // the working copy of Y^T in LDS (else behind Q in the slot)
+};
+
+// Q[c, :] = (H_0 .. H_c e_c)^T for c < r, zero for r <= c < l, to Qs[c * n + i] and Qb[c * qrs + i * qcs]: one wave per row of Q, its n
+// entries in registers (entry lane + 64 e), H_j = I - tau_j v_j v_j^T with v_j in W's column jp[j] below row j (bsv_form_u's application)
+template <typename T, int NE>
+__device__ __forceinline__ void brs_form_q(const T *W, int ldw, int n, int l, int r, const int *jp, const T *taus, T *Qs, T *Qb, int64_t qrs, int64_t qcs,
+                                           int wv, int lane) {
+    for (int c = wv; c < l; c += BID_WAVES) {
+        T x[NE];
+#pragma unroll
+        for (int e = 0; e < NE; ++e) x[e] = (c < r && lane + 64 * e == c) ? (T)1 : (T)0;
+        for (int j = c < r ? c : -1; j >= 0; --j) {
+            const T tau = taus[j];
+            if (tau == (T)0) continue;  // H_j = I (uniform)
+            const T *vc = W + (size_t)jp[j] * ldw;
+            T v[NE];
+            T dot = 0;
+#pragma unroll
+            for (int e = 0; e < NE; ++e) {
+                const int i = lane + 64 * e;
+                const T vv = vc[i < n ? i : j];  // branch-free: lanes out of range read row j and are masked below
+                v[e] = i > j && i < n ? vv : (i == j ? (T)1 : (T)0);
+                dot = fma(v[e], x[e], dot);
+            }
+            const T f = tau * wave_sum_dpp(dot);
+#pragma unroll
+            for (int e = 0; e < NE; ++e) x[e] = fma(-f, v[e], x[e]);
+        }
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            const int i = lane + 64 * e;
+            if (i < n) {
+                Qs[(size_t)c * n + i] = x[e];
+                Qb[c * qrs + i * qcs] = x[e];
+            }
+        }
+    }
+}
+
+// bsi_sketch's instance for TL = ceil(l / 16) row tiles
+#define RC_BSI_DISPATCH(AR_, OR_, WM_, ...)                                             \
+    switch ((l + 15) >> 4) {                                                            \
+        case 1: bsi_sketch<T, 1, AR_, OR_, WM_>(__VA_ARGS__); break;                    \
+        case 2: bsi_sketch<T, 2, AR_, OR_, WM_>(__VA_ARGS__); break;                    \
+        case 3: bsi_sketch<T, 3, AR_, OR_, WM_>(__VA_ARGS__); break;                    \
+        case 4: bsi_sketch<T, 4, AR_, OR_, WM_>(__VA_ARGS__); break;                    \
+        case 5: bsi_sketch<T, 5, AR_, OR_, WM_>(__VA_ARGS__); break;                    \
+        case 6: bsi_sketch<T, 6, AR_, OR_, WM_>(__VA_ARGS__); break;                    \
+        case 7: bsi_sketch<T, 7, AR_, OR_, WM_>(__VA_ARGS__); break;                    \
+        default: bsi_sketch<T, 8, AR_, OR_, WM_>(__VA_ARGS__); break;                   \
+    }
+
+template <typename T, bool AR, bool OR>
+__global__ __launch_bounds__(BID_THREADS, 2) void k_batched_range_step(BrsArgs<T> g) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const int m = (int)g.a.rows, n = (int)g.a.cols, l = (int)g.omega.rows;
+    const int ldw = g.w_lds ? (n | 1) : n;
+    T *lds = reinterpret_cast<T *>(smem_raw);
+    T *Qs = g.ws + (size_t)blockIdx.x * g.slot;
+    T *W = g.w_lds ? lds : Qs + (size_t)l * (size_t)n;
+    T *As = lds + (g.w_lds ? (size_t)l * ldw : 0);
+    T *Os = As + BSI_A_ELEMS;
+    T *vn1 = Os + bsi_o_elems(l);
+    T *vn2 = vn1 + l;
+    T *taus = vn2 + l;
+    T *red = taus + l;
+    int *jp = reinterpret_cast<int *>(red + 8);
+    int *rk = jp + l;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+
+    for (int b = blockIdx.x; b < g.count; b += gridDim.x) {
+        const T *__restrict__ A = g.a.p + (int64_t)b * g.abs;
+        const T *__restrict__ Om = g.omega.p + (int64_t)b * g.obs;
+        T *Yb = g.y.p ? g.y.p + (int64_t)b * g.ybs : nullptr;
+        // ---- the sketch, k_batched_sketch_id's, into the working copy of Y^T (and y) -----------------------------------------------------
+        {
+            BsiArgs<T> s;
+            s.a = g.a; s.omega = g.omega; s.y = g.y;
+            // the thread index behind an empty asm: the sketch's per-thread staging offsets (16 instances of them with the projection's) are then
+            // recomputed per block instead of being hoisted out of the block loop and spilled there
+            int t = tid;
+            asm volatile("" : "+v"(t));
+            RC_BSI_DISPATCH(AR, OR, BSI_W_ROWS, s, A, Om, Yb, W, ldw, As, Os, t, t >> 6, t & 63)
+        }
+        // ---- the row basis: Y^T P = Q R to all l steps, the rank from R's diagonal, Q formed from the first r reflectors -----------------
+        bid_norms(W, ldw, n, l, vn1, vn2, jp, wv, lane);
+        if (tid == 0) *rk = l;
+        bid_qrcp<T, true>(W, ldw, n, l, l, 0.0, jp, vn1, vn2, red, tid, wv, lane, taus);
+        if (tid < l) {
+            const T d = W[(size_t)jp[tid] * ldw + tid];
+            if (d == (T)0 || !isfinite(d)) atomicMin(rk, tid);
+        }
+        __syncthreads();
+        const int r = *rk;
+        if (tid == 0) g.ranks[b] = r;
+        T *Qb = g.q.p + (int64_t)b * g.qbs;
+        if (n <= 128) brs_form_q<T, 2>(W, ldw, n, l, r, jp, taus, Qs, Qb, g.q.rs, g.q.cs, wv, lane);
+        else if (n <= 256) brs_form_q<T, 4>(W, ldw, n, l, r, jp, taus, Qs, Qb, g.q.rs, g.q.cs, wv, lane);
+        else brs_form_q<T, 8>(W, ldw, n, l, r, jp, taus, Qs, Qb, g.q.rs, g.q.cs, wv, lane);
+        __syncthreads();  // the slot's Q is read by every wave below
+        // ---- the projection P^T = Q A^T: the sketch of a's transposed view with the slot's Q, into p's transposed view --------------------
+        {
+            BsiArgs<T> s;
+            s.a = Mat<T>(g.a.p, n, m, g.a.cs, g.a.rs);
+            s.omega = Mat<T>(Qs, l, n, n, 1);
+            s.y = Mat<T>(g.p.p, l, m, g.p.cs, g.p.rs);
+            int t = tid;
+            asm volatile("" : "+v"(t));
+            RC_BSI_DISPATCH(!AR, false, BSI_W_NONE, s, A, Qs, g.p.p + (int64_t)b * g.pbs, nullptr, 0, As, Os, t, t >> 6, t & 63)
+        }
+        __syncthreads();  // W, Q, jp and the small arrays are rewritten by the next block
+    }
+}
+#undef RC_BSI_DISPATCH
+
 // ---- the plans: where each launcher's movable buffers live, as pure functions of the shapes (rc_batched_launch.hpp) -------------------------
 
 // column ID: the working copy W (m x n) in LDS when it fits, else in the workgroup's slot of the grid-bounded workspace
@@ -1214,6 +1364,15 @@ BatchedPlan<BrcPlace> brt_plan(int m, int n, int K) {
 template <typename T>
 BatchedPlan<bool> bsi_plan(int l, int n) {
     return batched_lds_or_ws([&](bool w_lds) { return bsi_lds_bytes<T>(l, n, w_lds); }, (size_t)l * (size_t)n * sizeof(T), "sketch_column_id_rank_batched");
+}
+
+// range step: the working copy of Y^T (n x l) in LDS when it fits next to the chunk images, else in the workgroup's slot behind Q, which is
+// always there (the projection reads it through the chunk staging, as the sketch reads omega)
+template <typename T>
+BatchedPlan<bool> brs_plan(int l, int n) {
+    const bool places[] = {true, false};
+    return batched_first_fit(places, [&](bool w_lds) { return brs_lds_bytes<T>(l, n, w_lds); },
+        [&](bool w_lds) { return (size_t)(w_lds ? 1 : 2) * (size_t)l * (size_t)n * sizeof(T); }, "sketch_range_step_batched");
 }
 
 }  // namespace
@@ -1370,6 +1529,36 @@ void batched_sketch_column_id(rc_context *c, Mat<T> a, int64_t abs, Mat<T> omega
     g.tol = tol; g.count = (int)count; g.kk = (int)kk; g.w_lds = plan.at;
     lch.launch(g);
 }
+
+// The plan only moves the working copy's base pointer and pitch, and the four instances (by the index of a and of omega that the sketch's
+// staging loads run along; the projection's run along the other index of a and along n in Q) sum every element in the same order, so
+// neither can change a block's bits.  The label carries the scratch bytes per thread like the sketched ID's.
+template <typename T>
+void batched_sketch_range_step(rc_context *c, Mat<T> a, int64_t abs, Mat<T> omega, int64_t obs, int32_t count, Mat<T> y, int64_t ybs, Mat<T> q, int64_t qbs,
+                               Mat<T> p, int64_t pbs, int64_t *ranks) {
+    const int m = (int)a.rows, n = (int)a.cols, l = (int)omega.rows;
+    if (count <= 0) return;
+    const auto plan = brs_plan<T>(l, n);
+    const bool a_rows = a.rs <= a.cs, o_rows = omega.rs < omega.cs;
+    void (*const kerns[4])(BrsArgs<T>) = {k_batched_range_step<T, false, false>, k_batched_range_step<T, false, true>, k_batched_range_step<T, true, false>,
+                                          k_batched_range_step<T, true, true>};
+    const auto lch = batched_prepare(c, kerns[(a_rows ? 2 : 0) + (o_rows ? 1 : 0)], "sketch_range_step_batched", plan.lds, plan.ws, count);
+    ProfScope ps(c, "op:batched_range_step %dx%d l=%d count=%d grid=%lld slots=%lld plan=W:%s,Q:ws,rows=%d,cols=%d,scratch=%d", m, n, l, (int)count,
+                 (long long)lch.grid, (long long)lch.slots, plan.at ? "lds" : "ws", BSI_ROWS, BSI_COLS, lch.scratch);
+    BrsArgs<T> g;
+    g.a = a; g.omega = omega; g.y = y; g.q = q; g.p = p;
+    g.abs = abs; g.obs = obs; g.ybs = ybs; g.qbs = qbs; g.pbs = pbs;
+    g.ranks = ranks;
+    g.ws = lch.template workspace<T>();
+    g.slot = plan.ws / sizeof(T);
+    g.count = (int)count; g.w_lds = plan.at;
+    lch.launch(g);
+}
+
+template void batched_sketch_range_step<double>(rc_context *, Mat<double>, int64_t, Mat<double>, int64_t, int32_t, Mat<double>, int64_t, Mat<double>, int64_t,
+                                                Mat<double>, int64_t, int64_t *);
+template void batched_sketch_range_step<float>(rc_context *, Mat<float>, int64_t, Mat<float>, int64_t, int32_t, Mat<float>, int64_t, Mat<float>, int64_t,
+                                               Mat<float>, int64_t, int64_t *);
 
 template void batched_sketch_column_id<double>(rc_context *, Mat<double>, int64_t, Mat<double>, int64_t, int32_t, int64_t, double, Mat<double>, int64_t, Mat<double>,
                                                int64_t, Mat<double>, int64_t, int64_t *, int64_t *);

@@ -1411,6 +1411,31 @@ void sketch_column_id_rank_batched(rc_context *c, Mat<T> a, int64_t abs, Mat<T> 
     batched_sketch_column_id(c, a, abs, omega, obs, count, kk, tol, y, ybs, cm, cbs, z, zbs, col_ind, ranks);
 }
 
+// one range step of a power iteration on every block of a batch (sample_range_power_iteration, src/random_sampling.rs:131-158): the sketch y = omega a,
+// an orthonormal basis q of its rows by a pivoted Householder QR of y^T and the projection p = a q^T, in one launch; p is orthonormalised by
+// rc_lowrank_recompress_tall_batched_* with right = I before its transpose is the next omega
+template <typename T>
+void sketch_range_step_batched(rc_context *c, Mat<T> a, int64_t abs, Mat<T> omega, int64_t obs, int32_t count, Mat<T> y, int64_t ybs, Mat<T> q, int64_t qbs,
+                               Mat<T> p, int64_t pbs, int64_t *ranks) {
+    const char *who = "sketch_range_step_batched";
+    const int64_t m = a.rows, n = a.cols, l = omega.rows;
+    RC_REQUIRE(count >= 0, RC_INVALID_ARGUMENT, "%s: count = %d < 0", who, (int)count);
+    RC_REQUIRE(m >= 1 && m <= 65536 && n >= 1 && n <= 512 && l >= 1 && l <= 128 && l <= std::min(m, n), RC_INVALID_ARGUMENT,
+               "%s: needs 1 <= m <= 65536, 1 <= n <= 512 and 1 <= l <= min(128, m, n) (got a %lld x %lld, omega %lld x %lld)", who, (long long)m,
+               (long long)n, (long long)l, (long long)omega.cols);
+    RC_REQUIRE(omega.cols == m, RC_INVALID_ARGUMENT, "%s: a has %lld rows but omega has %lld columns", who, (long long)m, (long long)omega.cols);
+    RC_REQUIRE(!y.p || (y.rows == l && y.cols == n), RC_INVALID_ARGUMENT, "%s: y must be %lld x %lld (got %lld x %lld)", who, (long long)l, (long long)n,
+               (long long)y.rows, (long long)y.cols);
+    RC_REQUIRE(q.rows == l && q.cols == n && p.rows == m && p.cols == l, RC_INVALID_ARGUMENT, "%s: q must be %lld x %lld and p %lld x %lld", who,
+               (long long)l, (long long)n, (long long)m, (long long)l);
+    check_batch_stride(who, "q", qbs, q, count);
+    check_batch_stride(who, "p", pbs, p, count);
+    if (y.p) check_batch_stride(who, "y", ybs, y, count);
+    if (count > 0) RC_REQUIRE(a.p && omega.p && q.p && p.p && ranks, RC_INVALID_ARGUMENT, "%s: null pointer", who);
+    if (count == 0) return;
+    batched_sketch_range_step(c, a, abs, omega, obs, count, y, ybs, q, qbs, p, pbs, ranks);
+}
+
 // ||a_i - left_i mid_i diag(s_i) right_i||_F at each block's rank, ||a_i||_F and optionally the residual blocks, for the factors of any batched
 // compressor: the reference's rel_diff_fro(x.to_mat(), a) per block (src/lib.rs), in one launch and on the sketched ID's domain
 template <typename T>
@@ -2022,6 +2047,14 @@ rc_status rc_invert_permutation(rc_context *ctx, const int64_t *perm, int64_t n,
             sketch_column_id_rank_batched<T>(ctx, from_c<T>(a), a_batch_stride, from_c<T>(omega), omega_batch_stride, count, k, tol,     \
                                              from_c<T>(y), y_batch_stride, from_c<T>(c), c_batch_stride, from_c<T>(z), z_batch_stride,   \
                                              col_ind, ranks);                                                                            \
+        });                                                                                                                              \
+    }                                                                                                                                    \
+    rc_status rc_sketch_range_step_batched_##SUF(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega,                  \
+                                                 int64_t omega_batch_stride, int32_t count, rc_matrix y, int64_t y_batch_stride, rc_matrix q, \
+                                                 int64_t q_batch_stride, rc_matrix p, int64_t p_batch_stride, int64_t *ranks) {          \
+        return guarded(ctx, [&] {                                                                                                        \
+            sketch_range_step_batched<T>(ctx, from_c<T>(a), a_batch_stride, from_c<T>(omega), omega_batch_stride, count, from_c<T>(y),   \
+                                         y_batch_stride, from_c<T>(q), q_batch_stride, from_c<T>(p), p_batch_stride, ranks);             \
         });                                                                                                                              \
     }                                                                                                                                    \
     rc_status rc_lowrank_residual_batched_##SUF(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix left, int64_t left_batch_stride, \

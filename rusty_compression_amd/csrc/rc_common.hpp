@@ -321,6 +321,11 @@ template <typename R> void batched_sketch_column_id_c(rc_context *c, const rc_ma
 // those above.  Return kk = min(k, l, n); the caller returns when count == 0.
 template <typename T> int64_t check_sketch_column_id_rank_batched(Mat<T> a, Mat<T> omega, int32_t count, int64_t k, double tol, Mat<T> y, int64_t ybs, Mat<T> cm,
                                                                   int64_t cbs, Mat<T> z, int64_t zbs, const int64_t *col_ind, const int64_t *ranks);
+// one range step of every block of a batch (kernels_batched_id.hip, k_batched_range_step): the sketch y = omega a (l x n, p == nullptr: not written), an
+// orthonormal basis q (l x n, rows from the block's rank on zero) of its rows and the projection p = a q^T (m x l), each moved by i times its batch
+// stride (0 is legal for a and omega); ranks count (arguments checked by the caller)
+template <typename T> void batched_sketch_range_step(rc_context *c, Mat<T> a, int64_t abs, Mat<T> omega, int64_t obs, int32_t count, Mat<T> y, int64_t ybs,
+                                                     Mat<T> q, int64_t qbs, Mat<T> p, int64_t pbs, int64_t *ranks);
 // the residual of such factors against the blocks they approximate, in one rank-aware launch (kernels_batched_residual.hip): block i is a (m x n), left
 // (m x K), mid (K x K, p == nullptr: none), right (K x n) and e (m x n, p == nullptr: not written) each moved by i times its batch stride, s + i * s_stride
 // its K real scales (nullptr: none), ranks count device values (nullptr: every rank is K); err and nrm (nullptr: not written) count values: ||a_i - left
