@@ -483,7 +483,21 @@ rc_status rc_batch_column_id_f32(rc_context *const *ctxs, int32_t nctx, const rc
  * wrong c / z shapes, and for an output batch stride smaller than one output view's span.  Workspace: bounded, not by count.
  * Complex scalars (c64, c32): the same signature, domain, layout, checks and contract with interleaved (re, im) data, strides and
  * batch strides in complex elements; the pivots and the rank rule are on the real partial norms and the real R_jj of ?geqp3's
- * complex Householder QR, and C[:, j] = A[:, ind[j]] bit for bit. */
+ * complex Householder QR, and C[:, j] = A[:, ind[j]] bit for bit.
+ * Input scale.  Domain: the largest finite modulus of a block lies within [2^-100, 2^100] for f32 / c32 and within [2^-900, 2^900]
+ * for f64 / c64 (a zero block is inside it).  Inside it no column norm and no ?larfg norm is taken as an unscaled sum of squares:
+ * the working copy is brought to a largest real or imaginary part in [1, 2) by an exact power of two, as ?nrm2's scaling keeps
+ * LAPACK's sums inside the range.  Equivariance: the result for 2^e A is the result for A with C, X, s and P (and the sketch Y)
+ * multiplied by 2^e and everything else -- ranks, permutations, Z, R, U, Vt, Q -- unchanged, bit for bit while no input, output or
+ * working quantity leaves the normal range (an entry more than about 2^63 (f32) or 2^511 (f64) below the block's largest has a
+ * subnormal or zero square, as it is below every accuracy of the result).  Outside the domain: values unspecified, but contained in
+ * the block's outputs as for non-finite input (permutations still permutations, 0 <= r <= k); a block with a non-finite entry is
+ * not normalised.  The same paragraph holds for rc_two_sided_id_rank_batched_*, rc_svd_rank_batched_*,
+ * rc_sketch_column_id_rank_batched_* / _complex_batched_* and rc_sketch_range_step_batched_*, which refer to it.  The recompression
+ * (rc_lowrank_recompress_*), apply, residual and dense entry points make no such promise yet; the residual calls state their own.
+ * (The real rc_lowrank_recompress_batched_f64 / _f32 and _tall_batched_f64 / _f32 do load `left` and `right` times exact powers of two
+ * and give s the product back, which is what the power-iterated chains on rc_sketch_range_step_batched_* rest on; mid and s are taken
+ * as they stand, the complex twins are unchanged, and no domain is stated for either yet.) */
 rc_status rc_column_id_rank_batched_f64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks);
 rc_status rc_column_id_rank_batched_f32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks);
 rc_status rc_column_id_rank_batched_c64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks);
@@ -505,7 +519,8 @@ rc_status rc_column_id_rank_batched_c32(rc_context *ctx, rc_matrix a, int64_t a_
  * batch stride smaller than one output view's span, or a null pointer.  Workspace: bounded, not by count.
  * Complex scalars (c64, c32): the same signature, domain, layout, checks and contract; the row side factors C^H (the conjugate
  * transpose, as rc_column_id_two_sided_c* does through its pivoted LQ of C) and c[:, :r] = Z2^H with Z2 the Z of C^H, so that
- * c[row_ind[:r], :r] is still exactly the identity; x[:r, :r] = A[row_ind[:r], col_ind[:r]] bit for bit (not conjugated). */
+ * c[row_ind[:r], :r] is still exactly the identity; x[:r, :r] = A[row_ind[:r], col_ind[:r]] bit for bit (not conjugated).
+ * Input scale: the paragraph of rc_column_id_rank_batched_*, sentence for sentence; of the outputs x alone carries the scale. */
 rc_status rc_two_sided_id_rank_batched_f64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix c, int64_t c_batch_stride, rc_matrix x, int64_t x_batch_stride, rc_matrix r, int64_t r_batch_stride, int64_t *row_ind, int64_t *col_ind, int64_t *ranks);
 rc_status rc_two_sided_id_rank_batched_f32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix c, int64_t c_batch_stride, rc_matrix x, int64_t x_batch_stride, rc_matrix r, int64_t r_batch_stride, int64_t *row_ind, int64_t *col_ind, int64_t *ranks);
 rc_status rc_two_sided_id_rank_batched_c64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix c, int64_t c_batch_stride, rc_matrix x, int64_t x_batch_stride, rc_matrix r, int64_t r_batch_stride, int64_t *row_ind, int64_t *col_ind, int64_t *ranks);
@@ -532,7 +547,8 @@ rc_status rc_two_sided_id_rank_batched_c32(rc_context *ctx, rc_matrix a, int64_t
  * (|u_ic|, 0), the column having been multiplied by that unit phase, and the matching row of vt by its inverse (?gesdd leaves the
  * phase open; with the rule a separated triplet is unique).  conj(A) gives the same s and ranks and the conjugates of u and vt, bit
  * for bit.  Per matrix: complex pivoted Householder QR to the p x p factor R, one-sided complex Jacobi on R^H, U = Q [U_R; 0]; a wide
- * matrix is factored through its transpose. */
+ * matrix is factored through its transpose.
+ * Input scale: the paragraph of rc_column_id_rank_batched_*, sentence for sentence; of the outputs s alone carries the scale. */
 rc_status rc_svd_rank_batched_f64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix u, int64_t u_batch_stride, double *s, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks);
 rc_status rc_svd_rank_batched_f32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix u, int64_t u_batch_stride, float *s, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks);
 rc_status rc_svd_rank_batched_c64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix u, int64_t u_batch_stride, double *s, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks);
@@ -688,7 +704,9 @@ rc_status rc_lowrank_recompress_tall_complex_batched_plan(int64_t m, int64_t n, 
  * Domain: 1 <= n <= 512, 1 <= l <= 128, 1 <= m <= 65536, 1 <= k <= 128, 0 <= tol < 1, count >= 0 (0: nothing to do).  RC_INVALID_ARGUMENT for an
  * argument outside the domain, omega.cols != a.rows, a wrong y, c or z shape, an output batch stride smaller than one view's span when count > 1,
  * a null a, omega, c, z, col_ind or ranks with count > 0, or a null ctx (rejected before a device is touched).  No host synchronisation;
- * workspace bounded by the grid, not by count. */
+ * workspace bounded by the grid, not by count.
+ * Input scale: the paragraph of rc_column_id_rank_batched_*, sentence for sentence, with a the block that carries the scale (omega of
+ * order one): the power of two is taken from the sketch Y_i, and y and c carry the scale. */
 rc_status rc_sketch_column_id_rank_batched_f64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega, int64_t omega_batch_stride, int32_t count, int64_t k, double tol, rc_matrix y, int64_t y_batch_stride, rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks);
 rc_status rc_sketch_column_id_rank_batched_f32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega, int64_t omega_batch_stride, int32_t count, int64_t k, double tol, rc_matrix y, int64_t y_batch_stride, rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks);
 /* One range step of a power iteration on every tall block of a batch, in one stream-ordered, capturable call (the two products of one
@@ -706,7 +724,10 @@ rc_status rc_sketch_column_id_rank_batched_f32(rc_context *ctx, rc_matrix a, int
  * call's shapes alone.  Non-finite input stays inside its block's outputs, with 0 <= ranks[i] <= l.  RC_INVALID_ARGUMENT for an argument
  * outside the domain, omega.cols != a.rows, a wrong y, q or p shape, an output batch stride smaller than one view's span when count > 1, a
  * null a, omega, q, p or ranks with count > 0, or a null ctx (rejected before a device is touched).  No host synchronisation; workspace
- * bounded by the grid, not by count.  Real scalars only. */
+ * bounded by the grid, not by count.  Real scalars only.
+ * Input scale: the paragraph of rc_column_id_rank_batched_*, sentence for sentence, with a the block that carries the scale; y and p
+ * carry it, q and ranks do not.  A chain that hands p to rc_lowrank_recompress_tall_batched_f64 / _f32 keeps the equivariance: that call
+ * loads left and right times exact powers of two (u is unchanged and s carries 2^e when p does). */
 rc_status rc_sketch_range_step_batched_f64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega, int64_t omega_batch_stride, int32_t count, rc_matrix y, int64_t y_batch_stride, rc_matrix q, int64_t q_batch_stride, rc_matrix p, int64_t p_batch_stride, int64_t *ranks);
 rc_status rc_sketch_range_step_batched_f32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega, int64_t omega_batch_stride, int32_t count, rc_matrix y, int64_t y_batch_stride, rc_matrix q, int64_t q_batch_stride, rc_matrix p, int64_t p_batch_stride, int64_t *ranks);
 /* The complex twin of rc_sketch_column_id_rank_batched_*: the one-pass randomized column ID of every complex tall block of a batch, in one
@@ -741,7 +762,8 @@ rc_status rc_sketch_range_step_batched_f32(rc_context *ctx, rc_matrix a, int64_t
  * a null a, omega, c, z, col_ind or ranks with count > 0, or a null ctx (rejected before a device is touched).  No host synchronisation;
  * workspace bounded by the grid, not by count.
  * The name: the stem is rc_sketch_column_id_rank_complex_batched_, as rc_lowrank_recompress_complex_batched_ is spelled, because the real pair was
- * published as "real scalars only" and callers (and the ABI test of that pair) rely on rc_sketch_column_id_rank_batched_c64 / _c32 not existing. */
+ * published as "real scalars only" and callers (and the ABI test of that pair) rely on rc_sketch_column_id_rank_batched_c64 / _c32 not existing.
+ * Input scale: the paragraph of rc_column_id_rank_batched_*, sentence for sentence, as for the real pair. */
 rc_status rc_sketch_column_id_rank_complex_batched_c64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega, int64_t omega_batch_stride, int32_t count, int64_t k, double tol, rc_matrix y, int64_t y_batch_stride, rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks);
 rc_status rc_sketch_column_id_rank_complex_batched_c32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega, int64_t omega_batch_stride, int32_t count, int64_t k, double tol, rc_matrix y, int64_t y_batch_stride, rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks);
 /* The certificate of such a batch: the Frobenius norm of what a low-rank factorization leaves of its block, in one stream-ordered, capturable call

@@ -139,10 +139,9 @@ __device__ __forceinline__ void bid_norms(const T *W, int ldw, int m, int n, T *
     __syncthreads();
 }
 
-// working copy W[c * ldw + i] = at(i, c), read with the lanes along i (lanes_on_rows) or along c (the input's fast direction),
-// then the initial column norms and the identity permutation
+// working copy W[c * ldw + i] = at(i, c), read with the lanes along i (lanes_on_rows) or along c (the input's fast direction)
 template <typename T, typename At>
-__device__ __forceinline__ void bid_load(T *W, int ldw, int m, int n, bool lanes_on_rows, At at, T *vn1, T *vn2, int *jp, int wv, int lane) {
+__device__ __forceinline__ void bid_fill(T *W, int ldw, int m, int n, bool lanes_on_rows, At at, int wv, int lane) {
     if (lanes_on_rows) {
         for (int c = wv; c < n; c += BID_WAVES)
             for (int i = lane; i < m; i += 64) W[(size_t)c * ldw + i] = at(i, c);
@@ -151,7 +150,47 @@ __device__ __forceinline__ void bid_load(T *W, int ldw, int m, int n, bool lanes
             for (int c = lane; c < n; c += 64) W[(size_t)c * ldw + i] = at(i, c);
     }
     __syncthreads();
+}
+
+// the working copy as the caller's entries stand, then the initial column norms and the identity permutation (the recompression kernels)
+template <typename T, typename At>
+__device__ __forceinline__ void bid_load(T *W, int ldw, int m, int n, bool lanes_on_rows, At at, T *vn1, T *vn2, int *jp, int wv, int lane) {
+    bid_fill(W, ldw, m, n, lanes_on_rows, at, wv, lane);
     bid_norms(W, ldw, m, n, vn1, vn2, jp, wv, lane);
+}
+
+// bid_norms on a working copy of any scale: W is first brought to a largest magnitude in [1, 2) by the exact power of two 2^-e
+// (block_pow2_exponent, rc_device.hpp; e = 0 for a zero block and for one with a non-finite entry), so that neither these sums of squares
+// nor those of bid_qrcp and bid_apply leave the normal range.  One more pass over W before the first step, none inside the step loop.
+// Returns e: W holds 2^-e times the block, and only an output that carries the block's scale and is produced from W (the singular values
+// of k_batched_svd) multiplies 2^e back; pivots, ranks, Z, Q, U and V^T carry none, C, X and P are taken from the input itself.
+// stage: four elements no thread reads before the next barrier (red + 4).
+template <typename T>
+__device__ __forceinline__ int bid_norms_pow2(T *W, int ldw, int m, int n, T *vn1, T *vn2, int *jp, T *stage, int wv, int lane) {
+    T mx = 0;
+    for (int c = wv; c < n; c += BID_WAVES)
+        for (int i = lane; i < m; i += 64) mx = max(mx, pow2_key(W[(size_t)c * ldw + i]));
+    const int e = block_pow2_exponent(mx, stage, wv, lane);
+    const T sc = ldexp((T)1, -e);
+    for (int c = wv; c < n; c += BID_WAVES) {  // bid_norms' sums on the scaled entries; a wave rewrites the columns it read above
+        T acc = 0;
+        for (int i = lane; i < m; i += 64) {
+            const T v = W[(size_t)c * ldw + i] * sc;
+            W[(size_t)c * ldw + i] = v;
+            acc += v * v;
+        }
+        acc = wave_sum_dpp(acc);
+        if (lane == 0) { const T nr = sqrt(acc); vn1[c] = nr; vn2[c] = nr; jp[c] = c; }
+    }
+    __syncthreads();
+    return e;
+}
+
+// bid_load for a caller's block of any scale (the IDs and the SVD): the fill, then bid_norms_pow2.  Returns the block's exponent.
+template <typename T, typename At>
+__device__ __forceinline__ int bid_load_pow2(T *W, int ldw, int m, int n, bool lanes_on_rows, At at, T *vn1, T *vn2, int *jp, T *stage, int wv, int lane) {
+    bid_fill(W, ldw, m, n, lanes_on_rows, at, wv, lane);
+    return bid_norms_pow2(W, ldw, m, n, vn1, vn2, jp, stage, wv, lane);
 }
 
 // truncated pivoted QR of the working copy, at most k steps: pivots in jp (?geqp3's rule), R and the Householder vectors in W (LAPACK
@@ -295,7 +334,7 @@ __global__ __launch_bounds__(BID_THREADS) void k_batched_id(Mat<T> a, int64_t ab
 
     for (int b = blockIdx.x; b < count; b += gridDim.x) {
         const T *__restrict__ A = a.p + (int64_t)b * abs;
-        bid_load(W, ldw, m, n, a.rs <= a.cs, [&](int i, int c) { return A[i * a.rs + c * a.cs]; }, vn1, vn2, jp, wv, lane);
+        bid_load_pow2(W, ldw, m, n, a.rs <= a.cs, [&](int i, int c) { return A[i * a.rs + c * a.cs]; }, vn1, vn2, jp, red + 4, wv, lane);
         const int r = bid_qrcp(W, ldw, m, n, k, tol, jp, vn1, vn2, red, tid, wv, lane);
 
         // ---- outputs: permutation, rank, C, Z -------------------------------------------------------------------
@@ -348,7 +387,7 @@ __global__ __launch_bounds__(BID_THREADS) void k_batched_two_sided(Mat<T> a, int
     for (int b = blockIdx.x; b < count; b += gridDim.x) {
         const T *__restrict__ A = a.p + (int64_t)b * abs;
         // ---- phase 1: column ID of A -> r (= Z), col_ind, the rank --------------------------------------------------
-        bid_load(W, ldw, m, n, a.rs <= a.cs, [&](int i, int c) { return A[i * a.rs + c * a.cs]; }, vn1, vn2, jp, wv, lane);
+        bid_load_pow2(W, ldw, m, n, a.rs <= a.cs, [&](int i, int c) { return A[i * a.rs + c * a.cs]; }, vn1, vn2, jp, red + 4, wv, lane);
         const int r = bid_qrcp(W, ldw, m, n, k, tol, jp, vn1, vn2, red, tid, wv, lane);
         for (int p = tid; p < n; p += BID_THREADS) col_ind[(int64_t)b * n + p] = jp[p];
         if (tid == 0) ranks[b] = r;
@@ -357,7 +396,7 @@ __global__ __launch_bounds__(BID_THREADS) void k_batched_two_sided(Mat<T> a, int
 
         // ---- phase 2: column ID of C^T (r x m), W2[p][i] = A[p, col_ind[i]] -> c = Z2^T, row_ind ------------------------
         const int ldw2 = IN_LDS ? (r | 1) : r;
-        bid_load(W, ldw2, r, m, a.cs < a.rs, [&](int i, int p) { return A[p * a.rs + jp[i] * a.cs]; }, vn1, vn2, jp2, wv, lane);
+        bid_load_pow2(W, ldw2, r, m, a.cs < a.rs, [&](int i, int p) { return A[p * a.rs + jp[i] * a.cs]; }, vn1, vn2, jp2, red + 4, wv, lane);
         const int r2 = bid_qrcp(W, ldw2, r, m, r, 0.0, jp2, vn1, vn2, red, tid, wv, lane);  // r2 < r only on an exactly zero pivot
         for (int p = tid; p < m; p += BID_THREADS) row_ind[(int64_t)b * m + p] = jp2[p];
         bid_z(W, ldw2, m, r2, k, jp2, tile, cm.p + (int64_t)b * cbs, cm.cs, cm.rs, tid);  // Z2 (k x m) through c's transposed view
@@ -553,7 +592,7 @@ __global__ __launch_bounds__(BID_THREADS) void k_batched_svd(Mat<T> a, int64_t a
     for (int b = blockIdx.x; b < count; b += gridDim.x) {
         const T *__restrict__ A = a.p + (int64_t)b * abs;
         // ---- QR: W P = Q R, all N steps (exact zero pivots are steps with H = I), taus kept -------------------------------------
-        bid_load(W, ldw, M, N, ars <= acs, [&](int i, int c) { return A[i * ars + c * acs]; }, vn1, vn2, jp, wv, lane);
+        const int e2 = bid_load_pow2(W, ldw, M, N, ars <= acs, [&](int i, int c) { return A[i * ars + c * acs]; }, vn1, vn2, jp, red + 4, wv, lane);
         bid_qrcp<T, true>(W, ldw, M, N, N, 0.0, jp, vn1, vn2, red, tid, wv, lane, taus);
         // ---- core G = R^T (R in pivoted column order: G[:, j] = row j of R) and J = I ------------------------------------------
         for (int j = wv; j < N; j += BID_WAVES) {
@@ -587,7 +626,7 @@ __global__ __launch_bounds__(BID_THREADS) void k_batched_svd(Mat<T> a, int64_t a
                 pos += (kj > ki || (kj == ki && j < i)) ? 1 : 0;
             }
             srt[pos] = i;
-            sb[pos] = sig[i];
+            sb[pos] = ldexp(sig[i], e2);  // W was 2^-e2 times the block: the one output that carries its scale
         }
         __syncthreads();
         // ---- rank: the first j < k with s_j == 0 or (tol > 0 and s_j / s_0 < tol), else k ---------------------------------------
@@ -827,6 +866,23 @@ __device__ __forceinline__ void brt_form_u(const T *stage0, size_t se, int S, in
     }
 }
 
+// The exponent of a factor before it is loaded (block_pow2_exponent over at(i, c), i < rows, c < q, read as bid_fill reads it): the loads
+// below multiply every entry by 2^-e, so that the norms, both cores and the Jacobi run at unit scale as in k_batched_svd, and the
+// singular values take 2^(eL + eR) back.  One more read of the factor (the second one hits L2); with e = 0 (a zero or non-finite
+// factor) every entry is multiplied by 1 and the bits are the unscaled ones.  stage: four elements no thread reads before the next barrier.
+template <typename T, typename At>
+__device__ __forceinline__ int brc_exponent(int rows, int q, bool lanes_on_rows, At at, T *stage, int wv, int lane) {
+    T mx = 0;
+    if (lanes_on_rows) {
+        for (int c = wv; c < q; c += BID_WAVES)
+            for (int i = lane; i < rows; i += 64) mx = max(mx, pow2_key(at(i, c)));
+    } else {
+        for (int i = wv; i < rows; i += BID_WAVES)
+            for (int c = lane; c < q; c += 64) mx = max(mx, pow2_key(at(i, c)));
+    }
+    return block_pow2_exponent(mx, stage, wv, lane);
+}
+
 // TALL = false: rc_lowrank_recompress_batched_*.  TALL = true: rc_lowrank_recompress_tall_batched_*, the left factor by stages (see above)
 template <typename T, bool TALL>
 __global__ __launch_bounds__(BID_THREADS) void k_batched_recompress(BrcArgs<T> a) {
@@ -871,6 +927,10 @@ __global__ __launch_bounds__(BID_THREADS) void k_batched_recompress(BrcArgs<T> a
         const T *__restrict__ L = a.left.p + (int64_t)b * a.lbs;
         const T *__restrict__ R = a.right.p + (int64_t)b * a.rbs;
         T *Wl = Wl0;  // the copy the core and U read: the last stage's
+        // the factors' exponents (red[4..7], then red[0..3]: bid_qrcp writes red only behind the loads' barriers)
+        const int el = brc_exponent(m, q, a.left.rs <= a.left.cs, [&](int i, int c) { return L[(int64_t)i * a.left.rs + c * a.left.cs]; }, red + 4, wv, lane);
+        const int er = brc_exponent(n, q, a.right.cs <= a.right.rs, [&](int i, int c) { return R[c * a.right.rs + i * a.right.cs]; }, red, wv, lane);
+        const T scl = ldexp((T)1, -el), scr = ldexp((T)1, -er);
         [[maybe_unused]] int S = 1;
         if constexpr (TALL) {
             S = brt_stages(m, q);
@@ -882,7 +942,7 @@ __global__ __launch_bounds__(BID_THREADS) void k_batched_recompress(BrcArgs<T> a
                 T *Ws = Wl0 + (multi ? (size_t)s * se : 0);
                 T *ts = multi ? Ws + (size_t)BRT_H * K : taul;
                 brt_stack_load(Ws, ldl, Ws - (s ? se : 0), top, hs, q, a.left.rs <= a.left.cs,
-                               [&](int i, int c) { return L[(int64_t)(base + i) * a.left.rs + c * a.left.cs]; }, vn1, vn2, jpl, wv, lane);
+                               [&](int i, int c) { return L[(int64_t)(base + i) * a.left.rs + c * a.left.cs] * scl; }, vn1, vn2, jpl, wv, lane);
                 bid_qrcp<T, true>(Ws, ldl, hs, q, q, 0.0, jpl, vn1, vn2, red, tid, wv, lane, ts);
                 if (multi) {  // the stage's pivots beside its taus; jpl goes on as the next stage's starting order
                     int *js = reinterpret_cast<int *>(ts + K);
@@ -891,10 +951,10 @@ __global__ __launch_bounds__(BID_THREADS) void k_batched_recompress(BrcArgs<T> a
                 Wl = Ws;
             }
         } else {
-            bid_load(Wl, ldl, m, q, a.left.rs <= a.left.cs, [&](int i, int c) { return L[i * a.left.rs + c * a.left.cs]; }, vn1, vn2, jpl, wv, lane);
+            bid_load(Wl, ldl, m, q, a.left.rs <= a.left.cs, [&](int i, int c) { return L[i * a.left.rs + c * a.left.cs] * scl; }, vn1, vn2, jpl, wv, lane);
             bid_qrcp<T, true>(Wl, ldl, m, q, q, 0.0, jpl, vn1, vn2, red, tid, wv, lane, taul);
         }
-        bid_load(Wr, ldr, n, q, a.right.cs <= a.right.rs, [&](int i, int c) { return R[c * a.right.rs + i * a.right.cs]; }, vn1, vn2, jpr, wv, lane);
+        bid_load(Wr, ldr, n, q, a.right.cs <= a.right.rs, [&](int i, int c) { return R[c * a.right.rs + i * a.right.cs] * scr; }, vn1, vn2, jpr, wv, lane);
         bid_qrcp<T, true>(Wr, ldr, n, q, q, 0.0, jpr, vn1, vn2, red, tid, wv, lane, taur);
         for (int j = tid; j < q; j += BID_THREADS) { ipl[jpl[j]] = j; ipr[jpr[j]] = j; }
         __syncthreads();
@@ -958,7 +1018,7 @@ __global__ __launch_bounds__(BID_THREADS) void k_batched_recompress(BrcArgs<T> a
                 pos += (kj > ki || (kj == ki && j < i)) ? 1 : 0;
             }
             srt[pos] = i;
-            sb[pos] = sig[i];
+            sb[pos] = ldexp(sig[i], el + er);  // the factors were loaded as 2^-el left and 2^-er right
         }
         __syncthreads();
         // ---- rank: the first j < min(kk, q) with s_j == 0 or (tol > 0 and s_j / s_0 < tol), else min(kk, q) -------------------------
@@ -1142,7 +1202,7 @@ __global__ __launch_bounds__(BID_THREADS, 2) void k_batched_sketch_id(BsiArgs<T>
             default: bsi_sketch<T, 8, AR, OR>(g, A, Om, Yb, W, ldw, As, Os, tid, wv, lane); break;
         }
         // ---- the column ID of Y: k_batched_id's stages on l rows ----------------------------------------------------------------------
-        bid_norms(W, ldw, l, n, vn1, vn2, jp, wv, lane);
+        bid_norms_pow2(W, ldw, l, n, vn1, vn2, jp, red + 4, wv, lane);
         const int r = bid_qrcp(W, ldw, l, n, kk, g.tol, jp, vn1, vn2, red, tid, wv, lane);
         for (int p = tid; p < n; p += BID_THREADS) g.col_ind[(int64_t)b * n + p] = jp[p];
         if (tid == 0) g.ranks[b] = r;
@@ -1278,7 +1338,7 @@ __global__ __launch_bounds__(BID_THREADS, 2) void k_batched_range_step(BrsArgs<T
             RC_BSI_DISPATCH(AR, OR, BSI_W_ROWS, s, A, Om, Yb, W, ldw, As, Os, t, t >> 6, t & 63)
         }
         // ---- the row basis: Y^T P = Q R to all l steps, the rank from R's diagonal, Q formed from the first r reflectors -----------------
-        bid_norms(W, ldw, n, l, vn1, vn2, jp, wv, lane);
+        bid_norms_pow2(W, ldw, n, l, vn1, vn2, jp, red + 4, wv, lane);
         if (tid == 0) *rk = l;
         bid_qrcp<T, true>(W, ldw, n, l, l, 0.0, jp, vn1, vn2, red, tid, wv, lane, taus);
         if (tid < l) {

@@ -129,10 +129,9 @@ __device__ __forceinline__ void bic_norms(const cplx<R> *W, int ldw, int m, int 
     __syncthreads();
 }
 
-// working copy W[c * ldw + i] = at(i, c), read with the lanes along i (lanes_on_rows) or along c (the input's fast direction),
-// then the initial column norms and the identity permutation
+// working copy W[c * ldw + i] = at(i, c), read with the lanes along i (lanes_on_rows) or along c (the input's fast direction)
 template <typename R, typename At>
-__device__ __forceinline__ void bic_load(cplx<R> *W, int ldw, int m, int n, bool lanes_on_rows, At at, R *vn1, R *vn2, int *jp, int wv, int lane) {
+__device__ __forceinline__ void bic_fill(cplx<R> *W, int ldw, int m, int n, bool lanes_on_rows, At at, int wv, int lane) {
     if (lanes_on_rows) {
         for (int c = wv; c < n; c += BIC_WAVES)
             for (int i = lane; i < m; i += 64) W[(size_t)c * ldw + i] = at(i, c);
@@ -141,7 +140,49 @@ __device__ __forceinline__ void bic_load(cplx<R> *W, int ldw, int m, int n, bool
             for (int c = lane; c < n; c += 64) W[(size_t)c * ldw + i] = at(i, c);
     }
     __syncthreads();
+}
+
+// the working copy as the caller's entries stand, then the initial column norms and the identity permutation (the recompression kernels)
+template <typename R, typename At>
+__device__ __forceinline__ void bic_load(cplx<R> *W, int ldw, int m, int n, bool lanes_on_rows, At at, R *vn1, R *vn2, int *jp, int wv, int lane) {
+    bic_fill(W, ldw, m, n, lanes_on_rows, at, wv, lane);
     bic_norms(W, ldw, m, n, vn1, vn2, jp, wv, lane);
+}
+
+// bic_norms on a working copy of any scale, bid_norms_pow2's scheme (kernels_batched_id.hip): W is first multiplied by the exact power
+// of two 2^-e that brings its largest real or imaginary part (within sqrt 2 of the largest modulus, and never overflowing) into [1, 2);
+// e = 0 for a zero block and for one with a non-finite part.  Returns e.  stage: four elements no thread reads before the next barrier.
+template <typename R>
+__device__ __forceinline__ int bic_norms_pow2(cplx<R> *W, int ldw, int m, int n, R *vn1, R *vn2, int *jp, R *stage, int wv, int lane) {
+    R mx = 0;
+    for (int c = wv; c < n; c += BIC_WAVES)
+        for (int i = lane; i < m; i += 64) {
+            const cplx<R> v = W[(size_t)c * ldw + i];
+            mx = max(mx, max(pow2_key(v.re), pow2_key(v.im)));
+        }
+    const int e = block_pow2_exponent(mx, stage, wv, lane);
+    const R sc = ldexp((R)1, -e);
+    for (int c = wv; c < n; c += BIC_WAVES) {  // bic_norms' sums on the scaled entries; a wave rewrites the columns it read above
+        R acc = 0;
+        for (int i = lane; i < m; i += 64) {
+            const cplx<R> w = W[(size_t)c * ldw + i];
+            const cplx<R> v{w.re * sc, w.im * sc};
+            W[(size_t)c * ldw + i] = v;
+            acc += abs2(v);
+        }
+        acc = wave_sum_dpp(acc);
+        if (lane == 0) { const R nr = sqrt(acc); vn1[c] = nr; vn2[c] = nr; jp[c] = c; }
+    }
+    __syncthreads();
+    return e;
+}
+
+// bic_load for a caller's block of any scale (the IDs and the SVD): the fill, then bic_norms_pow2.  Returns the block's exponent.
+template <typename R, typename At>
+__device__ __forceinline__ int bic_load_pow2(cplx<R> *W, int ldw, int m, int n, bool lanes_on_rows, At at, R *vn1, R *vn2, int *jp, R *stage, int wv,
+                                             int lane) {
+    bic_fill(W, ldw, m, n, lanes_on_rows, at, wv, lane);
+    return bic_norms_pow2(W, ldw, m, n, vn1, vn2, jp, stage, wv, lane);
 }
 
 // truncated pivoted QR of the working copy, at most k steps: pivots in jp (?geqp3's rule), R and the Householder vectors in W (LAPACK
@@ -291,7 +332,7 @@ __global__ __launch_bounds__(BIC_THREADS) void k_batched_id_c(CV<R> a, int64_t a
 
     for (int b = blockIdx.x; b < count; b += gridDim.x) {
         const cplx<R> *__restrict__ A = a.p + (int64_t)b * abs;
-        bic_load(W, ldw, m, n, a.rs <= a.cs, [&](int i, int c) { return A[i * a.rs + c * a.cs]; }, vn1, vn2, jp, wv, lane);
+        bic_load_pow2(W, ldw, m, n, a.rs <= a.cs, [&](int i, int c) { return A[i * a.rs + c * a.cs]; }, vn1, vn2, jp, red + 4, wv, lane);
         const int r = bic_qrcp(W, ldw, m, n, k, tol, jp, vn1, vn2, red, tid, wv, lane);
 
         // ---- outputs: permutation, rank, C, Z -------------------------------------------------------------------
@@ -343,7 +384,7 @@ __global__ __launch_bounds__(BIC_THREADS) void k_batched_two_sided_c(CV<R> a, in
     for (int b = blockIdx.x; b < count; b += gridDim.x) {
         const cplx<R> *__restrict__ A = a.p + (int64_t)b * abs;
         // ---- phase 1: column ID of A -> r (= Z), col_ind, the rank --------------------------------------------------
-        bic_load(W, ldw, m, n, a.rs <= a.cs, [&](int i, int c) { return A[i * a.rs + c * a.cs]; }, vn1, vn2, jp, wv, lane);
+        bic_load_pow2(W, ldw, m, n, a.rs <= a.cs, [&](int i, int c) { return A[i * a.rs + c * a.cs]; }, vn1, vn2, jp, red + 4, wv, lane);
         const int r = bic_qrcp(W, ldw, m, n, k, tol, jp, vn1, vn2, red, tid, wv, lane);
         for (int p = tid; p < n; p += BIC_THREADS) col_ind[(int64_t)b * n + p] = jp[p];
         if (tid == 0) ranks[b] = r;
@@ -352,7 +393,7 @@ __global__ __launch_bounds__(BIC_THREADS) void k_batched_two_sided_c(CV<R> a, in
 
         // ---- phase 2: column ID of C^H (r x m), W2[p][i] = conj(A[p, col_ind[i]]) -> c = Z2^H, row_ind ------------------
         const int ldw2 = IN_LDS ? (r | 1) : r;
-        bic_load(W, ldw2, r, m, a.cs < a.rs, [&](int i, int p) { return cj(A[p * a.rs + jp[i] * a.cs]); }, vn1, vn2, jp2, wv, lane);
+        bic_load_pow2(W, ldw2, r, m, a.cs < a.rs, [&](int i, int p) { return cj(A[p * a.rs + jp[i] * a.cs]); }, vn1, vn2, jp2, red + 4, wv, lane);
         const int r2 = bic_qrcp(W, ldw2, r, m, r, 0.0, jp2, vn1, vn2, red, tid, wv, lane);  // r2 < r only on an exactly zero pivot
         for (int p = tid; p < m; p += BIC_THREADS) row_ind[(int64_t)b * m + p] = jp2[p];
         bic_z<R, true>(W, ldw2, m, r2, k, jp2, tile, cm.p + (int64_t)b * cbs, cm.cs, cm.rs, tid);  // Z2^H (m x k) through c's transposed view
@@ -595,7 +636,7 @@ __global__ __launch_bounds__(BIC_THREADS) void k_batched_svd_c(CV<R> a, int64_t 
     for (int b = blockIdx.x; b < count; b += gridDim.x) {
         const cplx<R> *__restrict__ A = a.p + (int64_t)b * abs;
         // ---- QR: W P = Q R, all N steps (exact zero pivots are steps with H = I), complex taus kept -------------------------------
-        bic_load(W, ldw, M, N, ars <= acs, [&](int i, int c) { return A[i * ars + c * acs]; }, vn1, vn2, jp, wv, lane);
+        const int e2 = bic_load_pow2(W, ldw, M, N, ars <= acs, [&](int i, int c) { return A[i * ars + c * acs]; }, vn1, vn2, jp, red + 4, wv, lane);
         bic_qrcp<R, true>(W, ldw, M, N, N, 0.0, jp, vn1, vn2, red, tid, wv, lane, taus);
         // ---- core G = R^H (R in pivoted column order: G[:, j] = conj(row j of R)) and J = I -----------------------------------------
         for (int j = wv; j < N; j += BIC_WAVES) {
@@ -632,7 +673,7 @@ __global__ __launch_bounds__(BIC_THREADS) void k_batched_svd_c(CV<R> a, int64_t 
                 pos += (kj > ki || (kj == ki && j < i)) ? 1 : 0;
             }
             srt[pos] = i;
-            sb[pos] = sig[i];
+            sb[pos] = ldexp(sig[i], e2);  // W was 2^-e2 times the block: the one output that carries its scale
         }
         __syncthreads();
         // ---- rank: the first j < k with s_j == 0 or (tol > 0 and s_j / s_0 < tol), else k ---------------------------------------
@@ -1272,7 +1313,7 @@ __global__ __launch_bounds__(BIC_THREADS, 2) void k_batched_sketch_id_c(BscArgs<
             }
         }
         // ---- the column ID of Y: k_batched_id_c's stages on l rows --------------------------------------------------------------------
-        bic_norms(W, ldw, l, n, vn1, vn2, jp, wv, lane);
+        bic_norms_pow2(W, ldw, l, n, vn1, vn2, jp, red + 4, wv, lane);
         const int r = bic_qrcp(W, ldw, l, n, kk, g.tol, jp, vn1, vn2, red, tid, wv, lane);
         for (int p = tid; p < n; p += BIC_THREADS) g.col_ind[(int64_t)b * n + p] = jp[p];
         if (tid == 0) g.ranks[b] = r;

@@ -79,6 +79,31 @@ __device__ inline int wave_min_dpp(int v) {
     return min(min(read_lane(v, 0), read_lane(v, 16)), min(read_lane(v, 32), read_lane(v, 48)));
 }
 
+// ---- power-of-two normalisation of a batched working copy ---------------------------------
+// The batched IDs and SVDs bring their working copy to a largest component magnitude in [1, 2) by an exact power of two, so that the
+// sums of squares of the column norms and of ?larfg neither overflow nor go subnormal for any block inside the stated domain, and the
+// result for 2^e A is bit for bit the result for A (a power of two commutes with every rounding inside the normal range).
+// The key of one component: its magnitude, +inf for NaN and +-inf (max() then never sees a NaN and a non-finite block is recognised)
+template <typename T>
+__device__ inline T pow2_key(T v) {
+    const T a = fabs(v);
+    return a < (T)INFINITY ? a : (T)INFINITY;
+}
+// The block's exponent e = floor(log2(max key)) from every thread's own maximum, for workgroups of four waves: one DPP wave maximum, four
+// values through stage[0..3], one barrier.  A zero block and a block with a non-finite entry take e = 0 (the working copy is then the
+// input, bit for bit).  e is clamped so that 2^-e is a normal number.  Uniform over the workgroup.
+template <typename T>
+__device__ inline int block_pow2_exponent(T mx, T *stage, int wv, int lane) {
+    mx = wave_max_dpp(mx);
+    if (lane == 0) stage[wv] = mx;
+    __syncthreads();
+    mx = max(max(stage[0], stage[1]), max(stage[2], stage[3]));
+    if (mx == (T)0 || !(mx < (T)INFINITY)) return 0;
+    constexpr int lim = sizeof(T) == 8 ? 1022 : 126;
+    const int e = ilogb(mx);
+    return e < -lim ? -lim : (e > lim ? lim : e);
+}
+
 // ---- fast, fully accurate reciprocal / reciprocal square root --------------------------
 // v_rcp_f64 / v_rsq_f64 deliver ~2^-23 relative accuracy; two Newton steps reach the f64
 // rounding level (error <= ~2 ulp) at a fraction of the IEEE division / sqrt expansions.
