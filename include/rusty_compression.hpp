@@ -763,20 +763,43 @@ template <typename T>
 BatchedSVD<T> recompress_tall_batched(const BatchedColumnID<T> &id, int64_t k, double tol = 0.0) {
     return recompress_tall_batched<T>(id.c, nullptr, nullptr, id.z, &id.ranks, (int32_t)id.ranks.size(), k, tol);
 }
-// one range step of a power iteration on `count` tall m x n blocks stacked in `a` (rc_sketch_range_step_batched_*, real scalars): per block
-// the sketch omega a_i (l x n), an orthonormal basis q_i (l x n) of its rows and the projection p_i = a_i q_i^T (m x l); q is count * l x n, p
-// count * m x l, ranks[i] the number of nonzero rows of q_i.  `sketch`, when given, receives the count * l x n sketches.  The _view form takes
-// block 0's test matrix as a view and its batch stride (0: shared), so that a strided U^T can be the next omega without a copy.
+// one range step of a power iteration on `count` tall m x n blocks stacked in `a` (rc_sketch_range_step_batched_* for the real scalars,
+// rc_sketch_range_step_complex_batched_* for c64 and c32): per block the sketch omega a_i (l x n), an orthonormal basis q_i (l x n) of its rows
+// (q_i q_i^H = I) and the projection p_i = a_i q_i^H (m x l); q is count * l x n, p count * m x l, ranks[i] the number of nonzero rows of q_i.
+// `sketch`, when given, receives the count * l x n sketches.  The _view form takes block 0's test matrix as a view and its batch stride
+// (0: shared), so that a strided U^T can be the next omega without a copy.  conj_p (complex scalars; the real calls have nothing to
+// conjugate and ignore it): p receives conj(p_i), whose orthonormal basis from recompress_tall is conj(U), so that its plain transpose is
+// the U^H a power iteration continues with (see the C header).
 template <typename T> struct RangeStepApi;
 template <> struct RangeStepApi<double> {
-    static constexpr auto range_step = rc_sketch_range_step_batched_f64;
+    using tol_type = double;
+    static rc_status range_step(rc_context *ctx, rc_matrix a, int64_t abs, rc_matrix omega, int64_t obs, int32_t count, rc_matrix y, int64_t ybs, rc_matrix q,
+                                int64_t qbs, rc_matrix p, int64_t pbs, int64_t *ranks, int32_t) {
+        return rc_sketch_range_step_batched_f64(ctx, a, abs, omega, obs, count, y, ybs, q, qbs, p, pbs, ranks);
+    }
     static constexpr auto sketch_id = rc_sketch_column_id_rank_batched_f64;
     static constexpr auto recompress_tall = rc_lowrank_recompress_tall_batched_f64;
 };
 template <> struct RangeStepApi<float> {
-    static constexpr auto range_step = rc_sketch_range_step_batched_f32;
+    using tol_type = double;
+    static rc_status range_step(rc_context *ctx, rc_matrix a, int64_t abs, rc_matrix omega, int64_t obs, int32_t count, rc_matrix y, int64_t ybs, rc_matrix q,
+                                int64_t qbs, rc_matrix p, int64_t pbs, int64_t *ranks, int32_t) {
+        return rc_sketch_range_step_batched_f32(ctx, a, abs, omega, obs, count, y, ybs, q, qbs, p, pbs, ranks);
+    }
     static constexpr auto sketch_id = rc_sketch_column_id_rank_batched_f32;
     static constexpr auto recompress_tall = rc_lowrank_recompress_tall_batched_f32;
+};
+template <> struct RangeStepApi<c64> {
+    using tol_type = double;
+    static constexpr auto range_step = rc_sketch_range_step_complex_batched_c64;
+    static constexpr auto sketch_id = rc_sketch_column_id_rank_complex_batched_c64;
+    static constexpr auto recompress_tall = rc_lowrank_recompress_tall_complex_batched_c64;
+};
+template <> struct RangeStepApi<c32> {
+    using tol_type = float;
+    static constexpr auto range_step = rc_sketch_range_step_complex_batched_c32;
+    static constexpr auto sketch_id = rc_sketch_column_id_rank_complex_batched_c32;
+    static constexpr auto recompress_tall = rc_lowrank_recompress_tall_complex_batched_c32;
 };
 template <typename T>
 struct BatchedRangeStep {
@@ -785,7 +808,7 @@ struct BatchedRangeStep {
 };
 template <typename T>
 BatchedRangeStep<T> range_step_batched_view(const DeviceMatrix<T> &a, rc_matrix omega, int64_t omega_batch_stride, int32_t count,
-                                            DeviceMatrix<T> *sketch = nullptr) {
+                                            DeviceMatrix<T> *sketch = nullptr, bool conj_p = false) {
     const Context &ctx = a.ctx();
     const int64_t m = count > 0 ? a.nrows() / count : 0, n = a.ncols(), l = omega.rows;
     BatchedRangeStep<T> out{DeviceMatrix<T>(ctx, (int64_t)count * l, n), DeviceMatrix<T>(ctx, (int64_t)count * m, l), DeviceIndex(ctx, (std::size_t)count)};
@@ -793,16 +816,18 @@ BatchedRangeStep<T> range_step_batched_view(const DeviceMatrix<T> &a, rc_matrix 
     ctx.check(RangeStepApi<T>::range_step(ctx.raw(), rc_matrix{a.view().data, m, n, n, 1}, m * n, omega, omega_batch_stride, count,
                                           sketch ? rc_matrix{sketch->view().data, l, n, n, 1} : rc_matrix{nullptr, 0, 0, 0, 0}, l * n,
                                           rc_matrix{out.q.view().data, l, n, n, 1}, l * n, rc_matrix{out.p.view().data, m, l, l, 1}, m * l,
-                                          out.ranks.data()));
+                                          out.ranks.data(), conj_p ? 1 : 0));
     return out;
 }
 template <typename T>
-BatchedRangeStep<T> range_step_batched(const DeviceMatrix<T> &a, const DeviceMatrix<T> &omega, int32_t count, DeviceMatrix<T> *sketch = nullptr) {
-    return range_step_batched_view(a, omega.view(), 0, count, sketch);
+BatchedRangeStep<T> range_step_batched(const DeviceMatrix<T> &a, const DeviceMatrix<T> &omega, int32_t count, DeviceMatrix<T> *sketch = nullptr,
+                                       bool conj_p = false) {
+    return range_step_batched_view(a, omega.view(), 0, count, sketch, conj_p);
 }
 // the sketched column_id_rank_batched after `iterations` rounds of power iteration on the shared test matrix omega (l x m), both half-steps
-// orthonormalised as in sample_range_power_iteration (src/random_sampling.rs:131-158): per round the range step, then p orthonormalised by
-// rc_lowrank_recompress_tall_batched_* with right = I at the step's ranks, whose u^T (a strided view) is the next, per-block, omega; two
+// orthonormalised as in sample_range_power_iteration (src/random_sampling.rs:131-158): per round the range step (with conj_p, which only the
+// complex scalars act on), then p orthonormalised by rc_lowrank_recompress_tall_batched_* / _tall_complex_batched_* with right = I at the
+// step's ranks, whose u^T (a strided view; U^H of p's basis for complex scalars) is the next, per-block, omega; two
 // launches per round and one for the ID.  The C calls never synchronise; this mirror owns the intermediate buffers, so it waits once per
 // round before it releases them.  iterations = 0 is column_id_rank_batched(a, omega, ...).
 template <typename T>
@@ -815,15 +840,15 @@ BatchedColumnID<T> column_id_rank_power_batched(const DeviceMatrix<T> &a, const 
     for (int64_t i = 0; i < l; ++i) heye[(std::size_t)(i * l + i)] = (T)1;
     const DeviceMatrix<T> eye = DeviceMatrix<T>::from_host(ctx, heye.data(), l, l);
     DeviceMatrix<T> u(ctx, (int64_t)count * m, l), vt(ctx, (int64_t)count * l, l);
-    DeviceBuffer<T> s(ctx, (std::size_t)count * (std::size_t)l);
+    DeviceBuffer<typename Scalar<T>::real> s(ctx, (std::size_t)count * (std::size_t)l);
     DeviceIndex uranks(ctx, (std::size_t)count);
     rc_matrix om = omega.view();
     int64_t obs = 0;
     for (int it = 0; it < iterations; ++it) {
-        const BatchedRangeStep<T> step = range_step_batched_view(a, om, obs, count);
+        const BatchedRangeStep<T> step = range_step_batched_view<T>(a, om, obs, count, nullptr, true);
         DeviceMatrix<T> un(ctx, (int64_t)count * m, l);
         ctx.check(RangeStepApi<T>::recompress_tall(ctx.raw(), rc_matrix{step.p.view().data, m, l, l, 1}, m * l, rc_matrix{nullptr, 0, 0, 0, 0}, 0, nullptr, 0,
-                                                   rc_matrix{eye.view().data, l, l, l, 1}, 0, step.ranks.data(), count, l, 0.0,
+                                                   rc_matrix{eye.view().data, l, l, l, 1}, 0, step.ranks.data(), count, l, (typename RangeStepApi<T>::tol_type)0,
                                                    rc_matrix{un.view().data, m, l, l, 1}, m * l, s.data(), rc_matrix{vt.view().data, l, l, l, 1}, l * l,
                                                    uranks.data()));
         ctx.synchronize();  // step's buffers and the previous u are released here

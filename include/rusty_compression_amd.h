@@ -724,7 +724,7 @@ rc_status rc_sketch_column_id_rank_batched_f32(rc_context *ctx, rc_matrix a, int
  * call's shapes alone.  Non-finite input stays inside its block's outputs, with 0 <= ranks[i] <= l.  RC_INVALID_ARGUMENT for an argument
  * outside the domain, omega.cols != a.rows, a wrong y, q or p shape, an output batch stride smaller than one view's span when count > 1, a
  * null a, omega, q, p or ranks with count > 0, or a null ctx (rejected before a device is touched).  No host synchronisation; workspace
- * bounded by the grid, not by count.  Real scalars only.
+ * bounded by the grid, not by count.  Real scalars; complex blocks go to rc_sketch_range_step_complex_batched_c64 / _c32 below.
  * Input scale: the paragraph of rc_column_id_rank_batched_*, sentence for sentence, with a the block that carries the scale; y and p
  * carry it, q and ranks do not.  A chain that hands p to rc_lowrank_recompress_tall_batched_f64 / _f32 keeps the equivariance: that call
  * loads left and right times exact powers of two (u is unchanged and s carries 2^e when p does). */
@@ -766,6 +766,43 @@ rc_status rc_sketch_range_step_batched_f32(rc_context *ctx, rc_matrix a, int64_t
  * Input scale: the paragraph of rc_column_id_rank_batched_*, sentence for sentence, as for the real pair. */
 rc_status rc_sketch_column_id_rank_complex_batched_c64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega, int64_t omega_batch_stride, int32_t count, int64_t k, double tol, rc_matrix y, int64_t y_batch_stride, rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks);
 rc_status rc_sketch_column_id_rank_complex_batched_c32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega, int64_t omega_batch_stride, int32_t count, int64_t k, double tol, rc_matrix y, int64_t y_batch_stride, rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks);
+/* The complex twin of rc_sketch_range_step_batched_*: one range step of a power iteration on every complex tall block of a batch, in one
+ * stream-ordered, capturable call (the two products of one round of sample_range_power_iteration, src/random_sampling.rs:128-168, for the
+ * reference's c64 / c32 scalars, with the orthonormalisation between them).  The arguments are the real call's, one for one, with a trailing
+ * p_conj; data are interleaved (re, im), every stride and batch stride is in complex elements, and the batch layout is that of
+ * rc_sketch_column_id_rank_complex_batched_*.  Per block a_i (m x n) and test matrix omega_i (l x m):
+ *   y = omega_i a_i (l x n), nothing conjugated, formed exactly as rc_sketch_column_id_rank_complex_batched_* forms it (y, when requested, is
+ *     that call's y bit for bit; y.data == NULL: not written, and the other outputs do not depend on that);
+ *   q (l x n) has orthonormal rows, q q^H = I on its first r rows, which span the rows of y: y = (y q^H) q.  It comes from the column-pivoted
+ *     complex Householder QR of the plain transpose y^T with ?geqp3's conventions (real R_jj): row c of q is (H_0 .. H_c e_c)^T, transposed and
+ *     not conjugated (the QR of y^H would give the same q); rows r .. l-1 are exactly zero;
+ *   ranks[i] = r is the first step whose real R_jj is exactly zero or not finite, else l (there is no tolerance here: truncation belongs to the
+ *     call that ends the chain);
+ *   p (m x l) = a_i q^H when p_conj == 0, so a_i ~ p q with nothing conjugated; columns r .. l-1 are exactly zero.  When p_conj != 0, p
+ *     receives the elementwise conjugate of that: the same bits with the sign of every imaginary part flipped at the store.
+ * Why p_conj: the next test matrix of a power iteration is U^H, U an orthonormal basis of p's columns, and no call here conjugates.  The tall
+ * complex recompression is conjugation-symmetric bit for bit, so orthonormalising conj(p) gives conj(U), whose plain transpose, a strided
+ * view, is U^H: no caller has to conjugate anything and no existing signature changes.  The recipe:
+ *   a round: this call with p_conj = 1, then rc_lowrank_recompress_tall_complex_batched_*(left = p, right = I, k = l, tol = 0, in_ranks =
+ *     ranks), then u^T (swap u's row and column strides) as the next omega;
+ *   the SVD end: this call with p_conj = 0, then rc_lowrank_recompress_tall_complex_batched_*(left = p, right = q, in_ranks = ranks), a
+ *     truncated SVD of a ~ p q; the ID end: rc_sketch_column_id_rank_complex_batched_* with the last round's u^T as omega.
+ * Both products run on the MFMA in the sketched ID's order: an element of y is one accumulator chain pair (Re, Im) from zero over the ascending
+ * rows of a_i, an element of p one such pair over the ascending columns of a_i with conj(q) as the left operand.  a streams through the chip
+ * twice when l <= 64; above that each of the two products takes a second pass over a.  Block i's bits depend on block i's a and omega and on
+ * (l, m, n, p_conj) alone.  Conjugating both a and omega gives the same ranks and the conjugates of y, q and p, bit for bit up to the sign of
+ * exact zeros; with every imaginary part of a and omega +0, Re y has the bits of rc_sketch_range_step_batched_*'s y on the real parts and the
+ * imaginary parts of y, q and p are exactly zero (q and p need not equal the real call's bits).  Non-finite input stays inside its block's
+ * outputs, with 0 <= ranks[i] <= l.
+ * Input scale: the paragraph of rc_column_id_rank_batched_* applies to this call (the working copy of y^T is brought to [1, 2) by an exact
+ * power of two before the QR): y and p carry 2^e, q and ranks do not.  The complex recompressions do not normalise their inputs, so the
+ * equivariance of the chains built on this call with them is not promised.
+ * Domain: 1 <= n <= 512, 1 <= m <= 65536, 1 <= l <= min(128, m, n), count >= 0; batch strides of 0 are legal for a and omega.  Outputs must not
+ * overlap inputs or one another.  RC_INVALID_ARGUMENT as for the real call, under the name sketch_range_step_complex_batched; a null ctx is
+ * rejected before a device is touched.  No host synchronisation; workspace bounded by the grid, not by count.
+ * The name: the _complex_batched_ stem of the family; rc_sketch_range_step_batched_c64 / _c32 stay absent, and callers tell builds apart by that. */
+rc_status rc_sketch_range_step_complex_batched_c64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega, int64_t omega_batch_stride, int32_t count, rc_matrix y, int64_t y_batch_stride, rc_matrix q, int64_t q_batch_stride, rc_matrix p, int64_t p_batch_stride, int64_t *ranks, int32_t p_conj);
+rc_status rc_sketch_range_step_complex_batched_c32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega, int64_t omega_batch_stride, int32_t count, rc_matrix y, int64_t y_batch_stride, rc_matrix q, int64_t q_batch_stride, rc_matrix p, int64_t p_batch_stride, int64_t *ranks, int32_t p_conj);
 /* The certificate of such a batch: the Frobenius norm of what a low-rank factorization leaves of its block, in one stream-ordered, capturable call
  * that reads the ranks on the device: per block the reference's rel_diff_fro(x.to_mat(), a) (src/lib.rs) without the m x n temporary of to_mat, on
  * the domain of the sketched column ID, so the output of every batched compressor above is accepted.  The _c64 / _c32 forms take interleaved

@@ -20,6 +20,8 @@ from .batch import sketch_column_id_rank_batched  # noqa: F401
 from .batch import sketch_column_id_rank_batched_complex  # noqa: F401
 from .batch import (sketch_column_id_rank_power_batched, sketch_power_omega_batched, sketch_range_step_batched,  # noqa: F401
                     sketch_svd_rank_power_batched)
+from .batch import (sketch_column_id_rank_power_batched_complex, sketch_power_omega_batched_complex,  # noqa: F401
+                    sketch_range_step_batched_complex, sketch_svd_rank_power_batched_complex)
 from .batch import block_csr, block_operator_apply  # noqa: F401
 from .batch import block_operator_apply_mixed, demote_batched, lowrank_apply_batched_mixed, promote_batched  # noqa: F401
 from .batch import column_id_residual_batched, lowrank_residual_batched, svd_residual_batched, two_sided_id_residual_batched  # noqa: F401
@@ -50,5 +52,7 @@ __all__ = [
     "Context", "default_context", "Operator", "DenseOperator", "LowRankOperator", "BlockLowRankOperator",
     "block_csr", "block_operator_apply",
     "sketch_range_step_batched", "sketch_power_omega_batched", "sketch_column_id_rank_power_batched", "sketch_svd_rank_power_batched",
+    "sketch_range_step_batched_complex", "sketch_power_omega_batched_complex", "sketch_column_id_rank_power_batched_complex",
+    "sketch_svd_rank_power_batched_complex",
     "lowrank_apply_batched_mixed", "block_operator_apply_mixed", "demote_batched", "promote_batched", "MixedBlockLowRankOperator",
 ]

@@ -20,6 +20,7 @@ from __future__ import annotations
 import ctypes
 from typing import Callable, List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 
@@ -1084,6 +1085,126 @@ def sketch_svd_rank_power_batched(a: torch.Tensor, k: int, tol: float = 0.0, pow
     omega_q = sketch_power_omega_batched(a, k, int(power_iterations) - 1, omega, oversampling, seed)
     q, p, ranks = sketch_range_step_batched(a, omega_q, oversampling, k, seed)
     return lowrank_recompress_tall_batched(p, q, k, tol, ranks=ranks)
+
+
+def _require_complex(who: str, a) -> None:
+    """TypeError for anything but complex128 / complex64 data, raised before a device is asked for."""
+    dtype = a.dtype if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a)).dtype
+    if dtype not in (torch.complex128, torch.complex64):
+        raise TypeError(f"{who}: complex128 or complex64 data expected, got {dtype}")
+
+
+def sketch_range_step_batched_complex(a: torch.Tensor, omega: Optional[torch.Tensor] = None, oversampling: int = 8, k: Optional[int] = None,
+                                      seed: int = 0, return_sketch: bool = False, conj_p: bool = False):
+    """sketch_range_step_batched for complex tall blocks (rc_sketch_range_step_complex_batched_c64 / _c32): a and omega complex128 or complex64
+    device tensors of one dtype (lazily conjugated views are materialised); real data and mismatched dtypes raise TypeError.  Per block
+    Y = omega a (l x n, nothing conjugated, sketch_column_id_rank_batched_complex's bit for bit), Q (l x n) with Q Q^H = I on its first r
+    rows, which span Y's rows, from the column-pivoted complex Householder QR of the plain transpose Y^T, and P = a Q^H (m x l), so
+    a ~ P Q with nothing conjugated.  conj_p=True returns conj(P) instead, the same bits with the sign of every imaginary part flipped at
+    the store: the tall complex recompression of conj(P) gives conj(U), whose plain transpose U^H is the next test matrix of a power
+    iteration, so no conjugation kernel runs anywhere.  omega=None draws the shared complex Gaussian of
+    sketch_column_id_rank_batched_complex(a, k, oversampling=oversampling, seed=seed).  Returns Q [count, l, n], P [count, m, l],
+    ranks [count] and, with return_sketch, Y [count, l, n]; rows of Q and columns of P from a block's rank r on are exactly zero; r is the
+    first step whose real R_jj is exactly zero or not finite, else l."""
+    from . import _lib
+    from .types import as_device
+
+    who = "sketch_range_step_batched_complex"
+    _require_complex(who, a)
+    a = as_device(a)
+    if a.dim() != 3:
+        raise AssertionError("expected a [count, m, n] batch")
+    a = a.resolve_conj()  # a lazily conjugated complex view is materialised: the kernels read the stored values
+    count, m, n = a.shape
+    if omega is None:
+        from .random_matrix import Rng, random_gaussian
+
+        if k is None:
+            raise AssertionError(f"{who}: k is needed to draw the default omega")
+        omega = random_gaussian((max(min(int(k) + int(oversampling), 128), 1), m), Rng(int(seed)), a.dtype)
+    omega = as_device(omega)
+    if omega.dtype != a.dtype:
+        raise TypeError(f"{who}: omega is {omega.dtype}, a is {a.dtype}")
+    omega = omega.resolve_conj()
+    if omega.dim() not in (2, 3) or (omega.dim() == 3 and omega.shape[0] != count):
+        raise AssertionError("expected omega [l, m] or [count, l, m]")
+    l = omega.shape[-2]
+    obs = omega.stride(0) if omega.dim() == 3 else 0
+    q = torch.empty((count, l, n), dtype=a.dtype, device=a.device)
+    p = torch.empty((count, m, l), dtype=a.dtype, device=a.device)
+    ranks = torch.empty(count, dtype=torch.int64, device=a.device)
+    y = torch.empty((count, l, n), dtype=a.dtype, device=a.device) if return_sketch else None
+    _lib.default_context().call("rc_sketch_range_step_complex_batched_" + _lib.suffix(a.dtype),
+                                _lib.rc_matrix(a.data_ptr(), m, n, a.stride(1), a.stride(2)), ctypes.c_int64(a.stride(0)),
+                                _lib.rc_matrix(omega.data_ptr(), l, omega.shape[-1], omega.stride(-2), omega.stride(-1)), ctypes.c_int64(obs),
+                                ctypes.c_int32(count),
+                                _lib.rc_matrix(y.data_ptr(), l, n, n, 1) if return_sketch else _lib.mat(None), ctypes.c_int64(l * n),
+                                _lib.rc_matrix(q.data_ptr(), l, n, n, 1), ctypes.c_int64(l * n),
+                                _lib.rc_matrix(p.data_ptr(), m, l, l, 1), ctypes.c_int64(m * l), _lib.i64p(ranks), ctypes.c_int32(1 if conj_p else 0))
+    return (q, p, ranks, y) if return_sketch else (q, p, ranks)
+
+
+def _power_iteration_batched_complex(a: torch.Tensor, omega: Optional[torch.Tensor], k: int, oversampling: int, seed: int) -> torch.Tensor:
+    """One full power iteration on complex blocks: the range step with conj_p, then conj(P) orthonormalised by the tall complex recompression
+    with right = I at the step's ranks: its U is conj of P's basis, so U^T, a strided view, is that basis' conjugate transpose and the
+    next omega.  Two launches, nothing on the host between them and nothing conjugated by a kernel of its own."""
+    _, p, ranks = sketch_range_step_batched_complex(a, omega, oversampling, k, seed, conj_p=True)
+    l = p.shape[2]
+    eye = torch.eye(l, dtype=p.dtype, device=p.device).expand(p.shape[0], l, l)
+    u, _, _, _ = lowrank_recompress_tall_batched_complex(p, eye, l, 0.0, ranks=ranks)
+    return u.mT
+
+
+def sketch_power_omega_batched_complex(a: torch.Tensor, k: int, power_iterations: int, omega: Optional[torch.Tensor] = None, oversampling: int = 8,
+                                       seed: int = 0) -> torch.Tensor:
+    """sketch_power_omega_batched for complex tall blocks: the test matrix after `power_iterations` rounds of the reference's
+    sample_range_power_iteration (src/random_sampling.rs:128-168, c64 / c32).  Per round sketch_range_step_batched_complex(conj_p=True), then
+    lowrank_recompress_tall_batched_complex(p, I, k=l, tol=0, ranks=the step's ranks), whose u.mT (a strided view, no copy, no conjugation) is
+    U^H of the basis of a Q^H's columns and the next omega.  Two launches per round and no host synchronisation.  Returns omega_q
+    [count, l, m] with orthonormal rows (exactly zero past a block's rank); with power_iterations = 0 the omega given or drawn is returned
+    unchanged ([l, m] when shared).  Real data raises TypeError."""
+    from .types import as_device
+
+    _require_complex("sketch_power_omega_batched_complex", a)
+    a = as_device(a)
+    if int(power_iterations) < 0:
+        raise AssertionError("sketch_power_omega_batched_complex: power_iterations must be >= 0")
+    if omega is None:
+        from .random_matrix import Rng, random_gaussian
+
+        omega = random_gaussian((max(min(int(k) + int(oversampling), 128), 1), a.shape[-2]), Rng(int(seed)), a.dtype)
+    for _ in range(int(power_iterations)):
+        omega = _power_iteration_batched_complex(a, omega, k, oversampling, seed)
+    return omega
+
+
+def sketch_column_id_rank_power_batched_complex(a: torch.Tensor, k: int, tol: float = 0.0, power_iterations: int = 1,
+                                                omega: Optional[torch.Tensor] = None, oversampling: int = 8, seed: int = 0,
+                                                return_sketch: bool = False):
+    """sketch_column_id_rank_power_batched for complex tall blocks: sketch_power_omega_batched_complex(a, k, power_iterations, omega,
+    oversampling, seed), then sketch_column_id_rank_batched_complex(a, k, tol, that omega).  The return tuple is
+    sketch_column_id_rank_batched_complex's; power_iterations = 0 is that function on the same arguments, bit for bit.  2 q + 1 launches,
+    no host synchronisation.  The power rounds need l <= min(128, m, n).  Real data raises TypeError."""
+    _require_complex("sketch_column_id_rank_power_batched_complex", a)
+    if int(power_iterations) == 0:
+        return sketch_column_id_rank_batched_complex(a, k, tol, omega, oversampling, seed, return_sketch)
+    omega_q = sketch_power_omega_batched_complex(a, k, power_iterations, omega, oversampling, seed)
+    return sketch_column_id_rank_batched_complex(a, k, tol, omega_q, oversampling, seed, return_sketch)
+
+
+def sketch_svd_rank_power_batched_complex(a: torch.Tensor, k: int, tol: float = 0.0, power_iterations: int = 1, omega: Optional[torch.Tensor] = None,
+                                          oversampling: int = 8, seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """sketch_svd_rank_power_batched for complex tall blocks: power_iterations - 1 full rounds (sketch_power_omega_batched_complex), one more
+    range step with conj_p=False (Q, P = a Q^H, ranks), then lowrank_recompress_tall_batched_complex(left=P, right=Q, ranks=the step's ranks,
+    k, tol): the reference's svd_from_range_estimate on a ~ (a Q^H) Q.  Returns (U [count, m, kk], S real [count, l], Vt = V^H
+    [count, kk, n], ranks), kk = min(k, l).  power_iterations = 0 delegates to sketch_svd_rank_batched_complex on the same arguments.
+    2 q launches, no host synchronisation.  Real data raises TypeError."""
+    _require_complex("sketch_svd_rank_power_batched_complex", a)
+    if int(power_iterations) == 0:
+        return sketch_svd_rank_batched_complex(a, k, tol, omega, oversampling, seed)
+    omega_q = sketch_power_omega_batched_complex(a, k, int(power_iterations) - 1, omega, oversampling, seed)
+    q, p, ranks = sketch_range_step_batched_complex(a, omega_q, oversampling, k, seed)
+    return lowrank_recompress_tall_batched_complex(p, q, k, tol, ranks=ranks)
 
 
 def packed_bytes(m: int, n: int, k: int, elem_size: int) -> int:

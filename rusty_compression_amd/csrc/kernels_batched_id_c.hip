@@ -2,7 +2,8 @@
 // (rc_column_id_rank_batched_c64 / _c32, rc_two_sided_id_rank_batched_c64 / _c32, rc_svd_rank_batched_c64 / _c32), and the
 // recompression of complex low-rank factors (rc_lowrank_recompress_complex_batched_c64 / _c32 and, for tall left factors,
 // rc_lowrank_recompress_tall_complex_batched_c64 / _c32: k_batched_recompress_c<R, TALL> below) and the sketched
-// column ID of complex tall blocks (rc_sketch_column_id_rank_complex_batched_c64 / _c32, k_batched_sketch_id_c below).
+// column ID of complex tall blocks (rc_sketch_column_id_rank_complex_batched_c64 / _c32, k_batched_sketch_id_c below) and the range step
+// of their power iteration (rc_sketch_range_step_complex_batched_c64 / _c32, k_batched_range_step_c below).
 //
 // The structure of kernels_batched_id.hip (one persistent workgroup of 256 threads per matrix, the same three device stages, the same
 // grid and workspace rule, and the launch path of rc_batched_launch.hpp) with the complex arithmetic of the lone complex path in
@@ -1193,9 +1194,13 @@ struct BscArgs {
 // Yb when it is not null).
 // AR / OR: the lanes of the staging loads run along the rows of a / of omega (the operand's smaller stride), else along its columns;
 // each thread's elements of a chunk are then a fixed step apart in memory and in the LDS planes, whose offsets are compile-time constants.
-template <typename R, int TL, bool AR, bool OR>
+// WM: where the sketch goes besides Yb.  BSC_W_COLS: W[c * ldw + i] as above; BSC_W_ROWS: W[i * ldw + c], the working copy of Y^T
+// (k_batched_range_step_c's row basis); BSC_W_NONE: W is not written (its projection, whose l x m "sketch" only goes to Yb).
+// yconj: Yb receives the conjugate, the sign of the imaginary part flipped at the store (that projection's p_conj); W never does.
+enum { BSC_W_COLS = 0, BSC_W_ROWS = 1, BSC_W_NONE = 2 };
+template <typename R, int TL, bool AR, bool OR, int WM = BSC_W_COLS>
 __device__ __forceinline__ void bsc_sketch(const BscArgs<R> &g, const cplx<R> *__restrict__ A, const cplx<R> *__restrict__ Om, cplx<R> *Yb, cplx<R> *W, int ldw, R *As,
-                                           R *Os, int oplane, int t0, int tid, int wv, int lane) {
+                                           R *Os, int oplane, int t0, int tid, int wv, int lane, bool yconj = false) {
     constexpr int PO = bsi_po(16 * TL);
     constexpr int A_PER = BSI_ROWS * BSI_COLS / BIC_THREADS;    // 8 elements of A per thread and chunk
     constexpr int O_PER = BSI_ROWS * 16 * TL / BIC_THREADS;     // 2 TL elements of Omega
@@ -1273,8 +1278,9 @@ __device__ __forceinline__ void bsc_sketch(const BscArgs<R> &g, const cplx<R> *_
                 const int row = (t0 + i) * 16 + Acc<R>::row(lane, reg);
                 if (row < ltot && col < n) {
                     const cplx<R> v{are[i][reg], aim[i][reg]};
-                    W[(size_t)col * ldw + row] = v;
-                    if (Yb) Yb[row * g.y.rs + col * g.y.cs] = v;
+                    if constexpr (WM == BSC_W_COLS) W[(size_t)col * ldw + row] = v;
+                    if constexpr (WM == BSC_W_ROWS) W[(size_t)row * ldw + col] = v;
+                    if (Yb) Yb[row * g.y.rs + col * g.y.cs] = yconj ? cj(v) : v;
                 }
             }
     }
@@ -1336,6 +1342,140 @@ __global__ __launch_bounds__(BIC_THREADS, 2) void k_batched_sketch_id_c(BscArgs<
     }
 }
 
+// ---- batched range step of complex tall blocks (rc_sketch_range_step_complex_batched_c64 / _c32) -------------------------------------------
+// k_batched_range_step's structure (kernels_batched_id.hip) with the stages above.  Per block: the sketch Y = Omega A (nothing conjugated)
+// by bsc_sketch, k_batched_sketch_id_c's instances and passes, stored as the working copy of the plain transpose Y^T (n x l, column i =
+// row i of Y); bic_norms_pow2 and the pivoted complex Householder QR of Y^T by bic_qrcp<R, true> run to all l steps with the taus kept;
+// the rank r, the first step whose real R_jj is exactly zero or not finite; Q (l x n), row c = (H_0 .. H_c e_c)^T for c < r (transposed,
+// not conjugated: Q Q^H = I, and the QR of Y^H would give the same rows) and exactly zero from r on, written to q and, conjugated and n
+// fastest, to the workgroup's slot; then the projection P^T = conj(Q) A^T, which is bsc_sketch once more on the transposed view of A with
+// the slot's conj(Q) as the test matrix (the lanes of its staging loads along n) and P^T's only destination the transposed view of p.
+// So an element of P = A Q^H is one accumulator chain pair (Re, Im) from zero over ascending column index of A, four columns per
+// instruction in bsc_sketch's order, a zero row of Q is a zero column of P, and p_conj flips the sign of Im P at the store and nowhere else.
+// A streams from HBM twice when l <= 64; above that each of the two products takes a second pass over A for row tiles 4 .. 7, as the
+// sketched ID's does.  conj(Q) is re-read per 64-row panel of A from L2, as Omega is per column panel in the sketch.
+// Conjugating a and omega conjugates Y (above), hence W, Q and the slot bit for bit, and P by the sketch's argument again; with +0
+// imaginary parts every imaginary part below stays zero.
+// dynamic LDS: [W: l x (n|1) complex, LDS plan only] taus[l] complex | A chunk re, im [BSI_A_ELEMS each] Omega chunk re, im
+// [bsc_o_elems(l) each] vn1[l] vn2[l] red[8] real | jp[l] rk[4]
+// slot: conj(Q) [l x n] [W: l x n, workspace plan only]
+template <typename R>
+size_t brsc_lds_bytes(int l, int n, bool in_lds) {
+    size_t c = (size_t)l;
+    if (in_lds) c += (size_t)l * (size_t)(n | 1);
+    return c * sizeof(cplx<R>) + ((size_t)2 * BSI_A_ELEMS + (size_t)2 * bsc_o_elems(l) + (size_t)2 * l + 8) * sizeof(R) + (size_t)(l + 4) * sizeof(int);
+}
+
+template <typename R>
+struct BrscArgs {
+    CV<R> a, omega, y, q, p;  // y.p == nullptr: the sketch is not written
+    int64_t abs, obs, ybs, qbs, pbs;
+    int64_t *ranks;
+    cplx<R> *ws;
+    size_t slot;  // complex elements of one workgroup's slot
+    int count;
+    bool w_lds;   // the working copy of Y^T in LDS (else behind conj(Q) in the slot)
+    bool p_conj;  // p receives conj(a q^H)
+};
+
+// Q[c, :] = (H_0 .. H_c e_c)^T for c < r, zero for r <= c < l, to Qb[c * qrs + i * qcs] and, conjugated, to Qs[c * n + i]: one wave per row
+// of Q, its n entries in registers (entry lane + 64 e), the reflectors by bsc_reflect_back (v_j in W's column jp[j] below row j)
+template <typename R, int NE>
+__device__ __forceinline__ void brsc_form_q(const cplx<R> *W, int ldw, int n, int l, int r, const int *jp, const cplx<R> *taus, cplx<R> *Qs, cplx<R> *Qb, int64_t qrs,
+                                            int64_t qcs, int wv, int lane) {
+    for (int c = wv; c < l; c += BIC_WAVES) {
+        cplx<R> x[NE];
+#pragma unroll
+        for (int e = 0; e < NE; ++e) x[e] = (c < r && lane + 64 * e == c) ? cone<R>() : czero<R>();
+        if (c < r) bsc_reflect_back<R, NE>(W, ldw, n, c + 1, jp, taus, x, lane);
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            const int i = lane + 64 * e;
+            if (i < n) {
+                Qs[(size_t)c * n + i] = cj(x[e]);
+                Qb[c * qrs + i * qcs] = x[e];
+            }
+        }
+    }
+}
+
+// bsc_sketch's passes of at most BSC_TILES row tiles over the l rows of the test matrix, one instance per number of 16-row tiles of a pass
+#define RC_BSC_PASSES(AR_, OR_, WM_, G_, A_, OM_, YB_, W_, LDW_, T_, YC_)                                                                   \
+    for (int t0 = 0; 16 * t0 < l; t0 += BSC_TILES) {                                                                                        \
+        const int rest = ((l + 15) >> 4) - t0;                                                                                              \
+        switch (rest < BSC_TILES ? rest : BSC_TILES) {                                                                                      \
+            case 1: bsc_sketch<R, 1, AR_, OR_, WM_>(G_, A_, OM_, YB_, W_, LDW_, As, Os, oplane, t0, T_, T_ >> 6, T_ & 63, YC_); break;      \
+            case 2: bsc_sketch<R, 2, AR_, OR_, WM_>(G_, A_, OM_, YB_, W_, LDW_, As, Os, oplane, t0, T_, T_ >> 6, T_ & 63, YC_); break;      \
+            case 3: bsc_sketch<R, 3, AR_, OR_, WM_>(G_, A_, OM_, YB_, W_, LDW_, As, Os, oplane, t0, T_, T_ >> 6, T_ & 63, YC_); break;      \
+            default: bsc_sketch<R, 4, AR_, OR_, WM_>(G_, A_, OM_, YB_, W_, LDW_, As, Os, oplane, t0, T_, T_ >> 6, T_ & 63, YC_); break;     \
+        }                                                                                                                                   \
+    }
+
+template <typename R, bool AR, bool OR>
+__global__ __launch_bounds__(BIC_THREADS, 2) void k_batched_range_step_c(BrscArgs<R> g) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const int m = (int)g.a.rows, n = (int)g.a.cols, l = (int)g.omega.rows;
+    const int ldw = g.w_lds ? (n | 1) : n;
+    const int oplane = bsc_o_elems(l);
+    cplx<R> *lds = reinterpret_cast<cplx<R> *>(smem_raw);
+    cplx<R> *Qs = g.ws + (size_t)blockIdx.x * g.slot;
+    cplx<R> *W = g.w_lds ? lds : Qs + (size_t)l * (size_t)n;
+    cplx<R> *taus = lds + (g.w_lds ? (size_t)l * ldw : 0);
+    R *As = reinterpret_cast<R *>(taus + l);
+    R *Os = As + 2 * BSI_A_ELEMS;
+    R *vn1 = Os + 2 * oplane;
+    R *vn2 = vn1 + l;
+    R *red = vn2 + l;
+    int *jp = reinterpret_cast<int *>(red + 8);
+    int *rk = jp + l;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+
+    for (int b = blockIdx.x; b < g.count; b += gridDim.x) {
+        const cplx<R> *__restrict__ A = g.a.p + (int64_t)b * g.abs;
+        const cplx<R> *__restrict__ Om = g.omega.p + (int64_t)b * g.obs;
+        cplx<R> *Yb = g.y.p ? g.y.p + (int64_t)b * g.ybs : nullptr;
+        // ---- the sketch, k_batched_sketch_id_c's, into the working copy of Y^T (and y) -----------------------------------------------------
+        {
+            BscArgs<R> s;
+            s.a = g.a; s.omega = g.omega; s.y = g.y;
+            // the thread index behind an empty asm: the sketch's per-thread staging offsets (8 instances of them with the projection's) are then
+            // recomputed per block instead of being hoisted out of the block loop and spilled there
+            int t = tid;
+            asm volatile("" : "+v"(t));
+            RC_BSC_PASSES(AR, OR, BSC_W_ROWS, s, A, Om, Yb, W, ldw, t, false)
+        }
+        // ---- the row basis: Y^T P = Q R to all l steps, the rank from R's real diagonal, Q formed from the first r reflectors ---------------
+        bic_norms_pow2(W, ldw, n, l, vn1, vn2, jp, red + 4, wv, lane);
+        if (tid == 0) *rk = l;
+        bic_qrcp<R, true>(W, ldw, n, l, l, 0.0, jp, vn1, vn2, red, tid, wv, lane, taus);
+        if (tid < l) {
+            const R d = W[(size_t)jp[tid] * ldw + tid].re;
+            if (d == (R)0 || !isfinite(d)) atomicMin(rk, tid);
+        }
+        __syncthreads();
+        const int r = *rk;
+        if (tid == 0) g.ranks[b] = r;
+        cplx<R> *Qb = g.q.p + (int64_t)b * g.qbs;
+        if (n <= 128) brsc_form_q<R, 2>(W, ldw, n, l, r, jp, taus, Qs, Qb, g.q.rs, g.q.cs, wv, lane);
+        else if (n <= 256) brsc_form_q<R, 4>(W, ldw, n, l, r, jp, taus, Qs, Qb, g.q.rs, g.q.cs, wv, lane);
+        else brsc_form_q<R, 8>(W, ldw, n, l, r, jp, taus, Qs, Qb, g.q.rs, g.q.cs, wv, lane);
+        __syncthreads();  // the slot's conj(Q) is read by every wave below
+        // ---- the projection P^T = conj(Q) A^T: the sketch of a's transposed view with the slot's conj(Q), into p's transposed view -----------
+        {
+            BscArgs<R> s;
+            s.a = CV<R>{g.a.p, n, m, g.a.cs, g.a.rs};
+            s.omega = CV<R>{Qs, l, n, n, 1};
+            s.y = CV<R>{g.p.p, l, m, g.p.cs, g.p.rs};
+            cplx<R> *Pb = g.p.p + (int64_t)b * g.pbs;
+            int t = tid;
+            asm volatile("" : "+v"(t));
+            RC_BSC_PASSES(!AR, false, BSC_W_NONE, s, A, Qs, Pb, nullptr, 0, t, g.p_conj)
+        }
+        __syncthreads();  // W, conj(Q), jp and the small arrays are rewritten by the next block
+    }
+}
+#undef RC_BSC_PASSES
+
 // ---- the plans: the real launchers' rules (kernels_batched_id.hip) on complex elements, as pure functions of the shapes ---------------------
 
 template <typename R>
@@ -1393,6 +1533,15 @@ BatchedPlan<BrccPlace> brtc_plan(int m, int n, int K) {
 template <typename R>
 BatchedPlan<bool> bscid_plan(int l, int n) {
     return batched_lds_or_ws([&](bool w_lds) { return bsc_lds_bytes<R>(l, n, w_lds); }, (size_t)l * (size_t)n * sizeof(cplx<R>), "sketch_column_id_rank_batched");
+}
+
+// range step: the working copy of Y^T (n x l complex) in LDS when it fits next to the two pairs of chunk planes, else in the workgroup's slot
+// behind conj(Q), which is always there (the projection reads it through the chunk staging, as the sketch reads omega)
+template <typename R>
+BatchedPlan<bool> brsc_plan(int l, int n) {
+    const bool places[] = {true, false};
+    return batched_first_fit(places, [&](bool w_lds) { return brsc_lds_bytes<R>(l, n, w_lds); },
+        [&](bool w_lds) { return (size_t)(w_lds ? 1 : 2) * (size_t)l * (size_t)n * sizeof(cplx<R>); }, "sketch_range_step_complex_batched");
 }
 
 }  // namespace
@@ -1529,6 +1678,37 @@ void batched_sketch_column_id_c(rc_context *c, const rc_matrix &a_, int64_t abs,
     g.tol = tol; g.count = (int)count; g.kk = (int)kk; g.w_lds = plan.at;
     lch.launch(g);
 }
+
+// The plan only moves the working copy's base pointer and pitch, and the four instances (by the index of a and of omega that the sketch's
+// staging loads run along; the projection's run along the other index of a and along n in conj(Q)) sum every component in the same order,
+// so neither can change a block's bits.  The label carries the scratch bytes per thread like the sketched ID's.
+template <typename R>
+void batched_sketch_range_step_c(rc_context *c, const rc_matrix &a_, int64_t abs, const rc_matrix &omega_, int64_t obs, int32_t count, const rc_matrix &y_,
+                                 int64_t ybs, const rc_matrix &q_, int64_t qbs, const rc_matrix &p_, int64_t pbs, int64_t *ranks, bool p_conj) {
+    const CV<R> a = view_of<R>(a_), omega = view_of<R>(omega_), y = view_of<R>(y_), q = view_of<R>(q_), p = view_of<R>(p_);
+    const int m = (int)a.rows, n = (int)a.cols, l = (int)omega.rows;
+    if (count <= 0) return;
+    const auto plan = brsc_plan<R>(l, n);
+    const bool a_rows = a.rs <= a.cs, o_rows = omega.rs < omega.cs;
+    void (*const kerns[4])(BrscArgs<R>) = {k_batched_range_step_c<R, false, false>, k_batched_range_step_c<R, false, true>,
+                                           k_batched_range_step_c<R, true, false>, k_batched_range_step_c<R, true, true>};
+    const auto lch = batched_prepare(c, kerns[(a_rows ? 2 : 0) + (o_rows ? 1 : 0)], "sketch_range_step_complex_batched", plan.lds, plan.ws, count);
+    ProfScope ps(c, "op:batched_range_step_c %dx%d l=%d count=%d grid=%lld slots=%lld plan=W:%s,Q:ws,rows=%d,cols=%d,conj=%d,scratch=%d", m, n, l, (int)count,
+                 (long long)lch.grid, (long long)lch.slots, plan.at ? "lds" : "ws", BSI_ROWS, BSI_COLS, p_conj ? 1 : 0, lch.scratch);
+    BrscArgs<R> g;
+    g.a = a; g.omega = omega; g.y = y; g.q = q; g.p = p;
+    g.abs = abs; g.obs = obs; g.ybs = ybs; g.qbs = qbs; g.pbs = pbs;
+    g.ranks = ranks;
+    g.ws = lch.template workspace<cplx<R>>();
+    g.slot = plan.ws / sizeof(cplx<R>);
+    g.count = (int)count; g.w_lds = plan.at; g.p_conj = p_conj;
+    lch.launch(g);
+}
+
+template void batched_sketch_range_step_c<double>(rc_context *, const rc_matrix &, int64_t, const rc_matrix &, int64_t, int32_t, const rc_matrix &, int64_t,
+                                                  const rc_matrix &, int64_t, const rc_matrix &, int64_t, int64_t *, bool);
+template void batched_sketch_range_step_c<float>(rc_context *, const rc_matrix &, int64_t, const rc_matrix &, int64_t, int32_t, const rc_matrix &, int64_t,
+                                                 const rc_matrix &, int64_t, const rc_matrix &, int64_t, int64_t *, bool);
 
 template void batched_sketch_column_id_c<double>(rc_context *, const rc_matrix &, int64_t, const rc_matrix &, int64_t, int32_t, int64_t, double, const rc_matrix &,
                                                  int64_t, const rc_matrix &, int64_t, const rc_matrix &, int64_t, int64_t *, int64_t *);

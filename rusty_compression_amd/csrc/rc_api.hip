@@ -1290,6 +1290,27 @@ int64_t check_sketch_column_id_rank_batched(Mat<T> a, Mat<T> omega, int32_t coun
     if (count > 0) RC_REQUIRE(a.p && omega.p && cm.p && z.p && col_ind && ranks, RC_INVALID_ARGUMENT, "%s: null pointer", who);
     return kk;
 }
+// the argument checks of rc_sketch_range_step_batched_* and, with complex, of rc_sketch_range_step_complex_batched_* under its own name: the views
+// carry the shapes and strides (in elements of the scalar type), the pointers only their null-ness; the caller returns when count == 0
+template <typename T>
+void check_sketch_range_step_batched(Mat<T> a, Mat<T> omega, int32_t count, Mat<T> y, int64_t ybs, Mat<T> q, int64_t qbs, Mat<T> p, int64_t pbs,
+                                     const int64_t *ranks, bool complex) {
+    const char *who = complex ? "sketch_range_step_complex_batched" : "sketch_range_step_batched";
+    const int64_t m = a.rows, n = a.cols, l = omega.rows;
+    RC_REQUIRE(count >= 0, RC_INVALID_ARGUMENT, "%s: count = %d < 0", who, (int)count);
+    RC_REQUIRE(m >= 1 && m <= 65536 && n >= 1 && n <= 512 && l >= 1 && l <= 128 && l <= std::min(m, n), RC_INVALID_ARGUMENT,
+               "%s: needs 1 <= m <= 65536, 1 <= n <= 512 and 1 <= l <= min(128, m, n) (got a %lld x %lld, omega %lld x %lld)", who, (long long)m,
+               (long long)n, (long long)l, (long long)omega.cols);
+    RC_REQUIRE(omega.cols == m, RC_INVALID_ARGUMENT, "%s: a has %lld rows but omega has %lld columns", who, (long long)m, (long long)omega.cols);
+    RC_REQUIRE(!y.p || (y.rows == l && y.cols == n), RC_INVALID_ARGUMENT, "%s: y must be %lld x %lld (got %lld x %lld)", who, (long long)l, (long long)n,
+               (long long)y.rows, (long long)y.cols);
+    RC_REQUIRE(q.rows == l && q.cols == n && p.rows == m && p.cols == l, RC_INVALID_ARGUMENT, "%s: q must be %lld x %lld and p %lld x %lld", who,
+               (long long)l, (long long)n, (long long)m, (long long)l);
+    check_batch_stride(who, "q", qbs, q, count);
+    check_batch_stride(who, "p", pbs, p, count);
+    if (y.p) check_batch_stride(who, "y", ybs, y, count);
+    if (count > 0) RC_REQUIRE(a.p && omega.p && q.p && p.p && ranks, RC_INVALID_ARGUMENT, "%s: null pointer", who);
+}
 // rc_demote_batched_* / rc_promote_batched_*: one shape on both sides, the sketched ID's tall domain, and dst's batch stride
 void check_convert_batched(const char *who, const rc_matrix &src, int32_t count, const rc_matrix &dst, int64_t dbs) {
     RC_REQUIRE(count >= 0, RC_INVALID_ARGUMENT, "%s: count = %d < 0", who, (int)count);
@@ -1328,6 +1349,11 @@ template int64_t check_sketch_column_id_rank_batched<double>(Mat<double>, Mat<do
                                                              Mat<double>, int64_t, const int64_t *, const int64_t *);
 template int64_t check_sketch_column_id_rank_batched<float>(Mat<float>, Mat<float>, int32_t, int64_t, double, Mat<float>, int64_t, Mat<float>, int64_t,
                                                             Mat<float>, int64_t, const int64_t *, const int64_t *);
+
+template void check_sketch_range_step_batched<double>(Mat<double>, Mat<double>, int32_t, Mat<double>, int64_t, Mat<double>, int64_t, Mat<double>, int64_t,
+                                                      const int64_t *, bool);
+template void check_sketch_range_step_batched<float>(Mat<float>, Mat<float>, int32_t, Mat<float>, int64_t, Mat<float>, int64_t, Mat<float>, int64_t,
+                                                     const int64_t *, bool);
 
 }  // namespace rc
 
@@ -1417,21 +1443,7 @@ void sketch_column_id_rank_batched(rc_context *c, Mat<T> a, int64_t abs, Mat<T> 
 template <typename T>
 void sketch_range_step_batched(rc_context *c, Mat<T> a, int64_t abs, Mat<T> omega, int64_t obs, int32_t count, Mat<T> y, int64_t ybs, Mat<T> q, int64_t qbs,
                                Mat<T> p, int64_t pbs, int64_t *ranks) {
-    const char *who = "sketch_range_step_batched";
-    const int64_t m = a.rows, n = a.cols, l = omega.rows;
-    RC_REQUIRE(count >= 0, RC_INVALID_ARGUMENT, "%s: count = %d < 0", who, (int)count);
-    RC_REQUIRE(m >= 1 && m <= 65536 && n >= 1 && n <= 512 && l >= 1 && l <= 128 && l <= std::min(m, n), RC_INVALID_ARGUMENT,
-               "%s: needs 1 <= m <= 65536, 1 <= n <= 512 and 1 <= l <= min(128, m, n) (got a %lld x %lld, omega %lld x %lld)", who, (long long)m,
-               (long long)n, (long long)l, (long long)omega.cols);
-    RC_REQUIRE(omega.cols == m, RC_INVALID_ARGUMENT, "%s: a has %lld rows but omega has %lld columns", who, (long long)m, (long long)omega.cols);
-    RC_REQUIRE(!y.p || (y.rows == l && y.cols == n), RC_INVALID_ARGUMENT, "%s: y must be %lld x %lld (got %lld x %lld)", who, (long long)l, (long long)n,
-               (long long)y.rows, (long long)y.cols);
-    RC_REQUIRE(q.rows == l && q.cols == n && p.rows == m && p.cols == l, RC_INVALID_ARGUMENT, "%s: q must be %lld x %lld and p %lld x %lld", who,
-               (long long)l, (long long)n, (long long)m, (long long)l);
-    check_batch_stride(who, "q", qbs, q, count);
-    check_batch_stride(who, "p", pbs, p, count);
-    if (y.p) check_batch_stride(who, "y", ybs, y, count);
-    if (count > 0) RC_REQUIRE(a.p && omega.p && q.p && p.p && ranks, RC_INVALID_ARGUMENT, "%s: null pointer", who);
+    check_sketch_range_step_batched(a, omega, count, y, ybs, q, qbs, p, pbs, ranks);
     if (count == 0) return;
     batched_sketch_range_step(c, a, abs, omega, obs, count, y, ybs, q, qbs, p, pbs, ranks);
 }

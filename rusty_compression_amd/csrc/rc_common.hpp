@@ -326,6 +326,15 @@ template <typename T> int64_t check_sketch_column_id_rank_batched(Mat<T> a, Mat<
 // stride (0 is legal for a and omega); ranks count (arguments checked by the caller)
 template <typename T> void batched_sketch_range_step(rc_context *c, Mat<T> a, int64_t abs, Mat<T> omega, int64_t obs, int32_t count, Mat<T> y, int64_t ybs,
                                                      Mat<T> q, int64_t qbs, Mat<T> p, int64_t pbs, int64_t *ranks);
+// the complex twin (kernels_batched_id_c.hip, k_batched_range_step_c), R = double (c64) or float (c32): interleaved-complex views, strides in complex
+// elements; y = omega a with nothing conjugated, q q^H = I on its first rank rows, p = a q^H, or its elementwise conjugate when p_conj
+template <typename R> void batched_sketch_range_step_c(rc_context *c, const rc_matrix &a, int64_t abs, const rc_matrix &omega, int64_t obs, int32_t count,
+                                                       const rc_matrix &y, int64_t ybs, const rc_matrix &q, int64_t qbs, const rc_matrix &p, int64_t pbs,
+                                                       int64_t *ranks, bool p_conj);
+// the argument checks of rc_sketch_range_step_batched_* and rc_sketch_range_step_complex_batched_* (rc_api.hip; complex: under the latter's name), shared
+// by every scalar type like those above; the caller returns when count == 0
+template <typename T> void check_sketch_range_step_batched(Mat<T> a, Mat<T> omega, int32_t count, Mat<T> y, int64_t ybs, Mat<T> q, int64_t qbs, Mat<T> p,
+                                                           int64_t pbs, const int64_t *ranks, bool complex = false);
 // the residual of such factors against the blocks they approximate, in one rank-aware launch (kernels_batched_residual.hip): block i is a (m x n), left
 // (m x K), mid (K x K, p == nullptr: none), right (K x n) and e (m x n, p == nullptr: not written) each moved by i times its batch stride, s + i * s_stride
 // its K real scales (nullptr: none), ranks count device values (nullptr: every rank is K); err and nrm (nullptr: not written) count values: ||a_i - left

@@ -1432,6 +1432,20 @@ extern "C" {
             batched_sketch_column_id_c<R>(ctx, a, a_batch_stride, omega, omega_batch_stride, count, kk, tol, y, y_batch_stride, c,        \
                                           c_batch_stride, z, z_batch_stride, col_ind, ranks);                                             \
         });                                                                                                                               \
+    }                                                                                                                                     \
+    /* one range step of a power iteration on complex tall blocks (kernels_batched_id_c.hip): the real entry point's checks on views of */ \
+    /* the same shapes under the call's own name; y = omega a, q q^H = I, p = a q^H or, with p_conj, its conjugate */                     \
+    rc_status rc_sketch_range_step_complex_batched_##SUF(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega,           \
+                                                         int64_t omega_batch_stride, int32_t count, rc_matrix y, int64_t y_batch_stride,  \
+                                                         rc_matrix q, int64_t q_batch_stride, rc_matrix p, int64_t p_batch_stride,        \
+                                                         int64_t *ranks, int32_t p_conj) {                                                \
+        return guarded_c(ctx, [&] {                                                                                                       \
+            check_sketch_range_step_batched<R>(shape_of<R>(a), shape_of<R>(omega), count, shape_of<R>(y), y_batch_stride, shape_of<R>(q), \
+                                               q_batch_stride, shape_of<R>(p), p_batch_stride, ranks, true);                              \
+            if (count == 0) return;                                                                                                       \
+            batched_sketch_range_step_c<R>(ctx, a, a_batch_stride, omega, omega_batch_stride, count, y, y_batch_stride, q,                \
+                                           q_batch_stride, p, p_batch_stride, ranks, p_conj != 0);                                        \
+        });                                                                                                                               \
     }
 
 RC_DEFINE_COMPLEX(c64, double, rc_complex64)

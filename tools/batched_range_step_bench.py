@@ -13,7 +13,13 @@ of --repeats with the spread.  The relative errors ||A - C Z||_F / ||A||_F at ze
 blocks of every shape.  Writes profiles/batched_range_step_bench.json unless --out names another file.  Not used by the tests or by
 bench.py.
 
-    python tools/batched_range_step_bench.py [--repeats 5] [--shapes 0,1,2,3] [--torch-blocks 128] [--out path.json]
+--complex runs the same shapes with complex scalars (c64 / c64 / c32 / c64 in place of f64 / f64 / f32 / f64) through
+rc_sketch_range_step_complex_batched_* and the _complex compositions: complex blocks of the same decaying spectrum, a complex Gaussian
+omega, (t) with complex matmul / linalg.qr / bmm (Q conjugated for the projection), and beside them (r) the real step, round and
+power ID on the real parts at the same shape, timed in the same run (step / round / power complex_over_real_time).  Writes
+profiles/batched_range_step_complex_bench.json and leaves the real output file alone.
+
+    python tools/batched_range_step_bench.py [--complex] [--repeats 5] [--shapes 0,1,2,3] [--torch-blocks 128] [--out path.json]
 """
 import argparse
 import json
@@ -29,7 +35,7 @@ import rusty_compression_amd as rc  # noqa: E402
 from rusty_compression_amd import _lib  # noqa: E402
 from rusty_compression_amd.random_matrix import Rng  # noqa: E402
 from tools.batched_id_bench import decaying_batch, timed  # noqa: E402
-from tools.batched_sketch_id_bench import COPY_BW, SHAPES, rel_err  # noqa: E402
+from tools.batched_sketch_id_bench import COMPLEX_OF, COPY_BW, SHAPES, rel_err  # noqa: E402
 
 
 def profiled(fn):
@@ -63,28 +69,34 @@ def main():
     ap.add_argument("--shapes", default=None)
     ap.add_argument("--torch-blocks", type=int, default=128)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--complex", action="store_true", help="time rc_sketch_range_step_complex_batched_c64 / _c32 on complex blocks of the same shapes")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("needs an MI355X")
-    out_path = args.out or os.path.join(ROOT, "profiles", "batched_range_step_bench.json")
+    out_path = args.out or os.path.join(ROOT, "profiles", "batched_range_step_complex_bench.json" if args.complex else "batched_range_step_bench.json")
+    cx = "_complex" if args.complex else ""
+    one_pass_call, step_call = getattr(rc, "sketch_column_id_rank_batched" + cx), getattr(rc, "sketch_range_step_batched" + cx)
+    power_call, omega_call = getattr(rc, "sketch_column_id_rank_power_batched" + cx), getattr(rc, "sketch_power_omega_batched" + cx)
     results = []
     for si in [int(x) for x in (args.shapes or ",".join(str(i) for i in range(len(SHAPES)))).split(",")]:
         count, m, n, l, k, dtype = SHAPES[si]
+        if args.complex:
+            dtype = COMPLEX_OF[dtype]
         a = decaying_batch(count, m, n, dtype, 2468 + si)
         omega = rc.random_gaussian((l, m), Rng(si), dtype)
         elem = a.element_size()
 
         def one_pass():
-            return rc.sketch_column_id_rank_batched(a, k, 0.0, omega=omega)
+            return one_pass_call(a, k, 0.0, omega=omega)
 
         def step():
-            return rc.sketch_range_step_batched(a, omega)
+            return step_call(a, omega)
 
         def power():
-            return rc.sketch_column_id_rank_power_batched(a, k, 0.0, power_iterations=1, omega=omega)
+            return power_call(a, k, 0.0, power_iterations=1, omega=omega)
 
         def full_round():  # the step and the orthonormalisation of P: what (t) computes
-            return rc.sketch_power_omega_batched(a, k, 1, omega=omega)
+            return omega_call(a, k, 1, omega=omega)
 
         tb = min(args.torch_blocks, count)
         at = a[:tb]
@@ -92,7 +104,7 @@ def main():
         def torch_round():
             y = torch.matmul(omega, at)
             q = torch.linalg.qr(y.mT).Q
-            p = torch.bmm(at, q)
+            p = torch.bmm(at, q.conj() if args.complex else q)  # a Q^H with Q = q^T: a conj(q)
             return torch.linalg.qr(p).Q
 
         (c0, z0, _, _), _ = profiled(one_pass)
@@ -116,11 +128,20 @@ def main():
                    round_s=r_med, round_s_min=r_min, round_s_max=r_max, round_blocks_per_s=count / r_med,
                    round_speedup_vs_torch_round=(t_med / tb) / (r_med / count),
                    err_q0=rel_err(a[:4], c0[:4], z0[:4]), err_q1=rel_err(a[:4], c1[:4], z1[:4]))
+        if args.complex:  # (r) the real calls on the real parts, same shape, same run
+            ar, omr = a.real.contiguous(), omega.real.contiguous()
+            rs_med, _, _ = timed(lambda: rc.sketch_range_step_batched(ar, omr), args.repeats)
+            rr_med, _, _ = timed(lambda: rc.sketch_power_omega_batched(ar, k, 1, omega=omr), args.repeats)
+            rp_med, _, _ = timed(lambda: rc.sketch_column_id_rank_power_batched(ar, k, 0.0, power_iterations=1, omega=omr), args.repeats)
+            row.update(real_step_s=rs_med, real_step_blocks_per_s=count / rs_med, step_complex_over_real_time=s_med / rs_med,
+                       real_round_s=rr_med, real_round_blocks_per_s=count / rr_med, round_complex_over_real_time=r_med / rr_med,
+                       real_power_q1_s=rp_med, real_power_q1_blocks_per_s=count / rp_med, power_q1_complex_over_real_time=p_med / rp_med)
+            del ar, omr
         results.append(row)
         print(json.dumps(row), flush=True)
         del a, omega, at, c0, z0, c1, z1
         torch.cuda.empty_cache()
-    out = dict(tool="tools/batched_range_step_bench.py", device=torch.cuda.get_device_name(0), results=results)
+    out = dict(tool="tools/batched_range_step_bench.py" + (" --complex" if args.complex else ""), device=torch.cuda.get_device_name(0), results=results)
     with open(out_path, "w") as f:
         json.dump(out, f, indent=1)
     print("wrote", out_path)
