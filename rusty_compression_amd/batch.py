@@ -105,27 +105,22 @@ def two_sided_id_rank_batched(a: torch.Tensor, k: int, tol: float = 0.0) -> Tupl
     return c, x, r, row_ind, col_ind, ranks
 
 
-def svd_rank_batched(a: torch.Tensor, k: int, tol: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    """Truncated SVDs of `count` small same-shaped matrices in one stream-ordered call (rc_svd_rank_batched_*).
-
-    a: [count, m, n] device tensor of float64 or float32, any strides (1 <= m, n <= 512, min(m, n) <= 128).  k (<= 128) is clamped to
-    p = min(m, n); the rank of each matrix is the first j < k with s_j == 0 or s_j / s_0 < tol (tol = 0: fixed rank k).  Returns
-    U [count, m, k], S [count, p] (all singular values, descending), Vt [count, k, n] and ranks [count]; the columns of U and rows of
-    Vt past a matrix's rank are zero, and the largest-|.| entry of each kept column of U is positive.  Complex data (complex128,
-    complex64) goes to svd_rank_batched_complex; this function raises TypeError for it."""
+def _svd_rank_batched(who: str, complex_data: bool, a, k, tol):
+    """The body of svd_rank_batched and svd_rank_batched_complex: the checks and the call; S comes back in the real dtype."""
     from . import _lib
     from .types import as_device
 
-    a = as_device(a)
+    a = as_device(a).resolve_conj()  # a lazily conjugated complex view is materialised: the kernels read the stored values
     if a.dim() != 3:
         raise AssertionError("expected a [count, m, n] batch")
-    if a.dtype not in (torch.float64, torch.float32):
-        raise TypeError(f"svd_rank_batched: float64 or float32 data expected, got {a.dtype}")
+    kinds = (torch.complex128, torch.complex64) if complex_data else (torch.float64, torch.float32)
+    if a.dtype not in kinds:
+        raise TypeError(f"{who}: {'complex128 or complex64' if complex_data else 'float64 or float32'} data expected, got {a.dtype}")
     count, m, n = a.shape
     p = min(m, n)
     kk = min(int(k), p)
     u = torch.empty((count, m, kk), dtype=a.dtype, device=a.device)
-    s = torch.empty((count, p), dtype=a.dtype, device=a.device)
+    s = torch.empty((count, p), dtype=_lib.real_dtype(a.dtype), device=a.device)
     vt = torch.empty((count, kk, n), dtype=a.dtype, device=a.device)
     ranks = torch.empty(count, dtype=torch.int64, device=a.device)
     view = _lib.rc_matrix(a.data_ptr(), m, n, a.stride(1), a.stride(2))
@@ -134,6 +129,17 @@ def svd_rank_batched(a: torch.Tensor, k: int, tol: float = 0.0) -> Tuple[torch.T
                                 ctypes.c_int64(m * kk), ctypes.c_void_p(s.data_ptr()), _lib.mat(vt[0] if count else vt.new_empty(kk, n)),
                                 ctypes.c_int64(kk * n), _lib.i64p(ranks))
     return u, s, vt, ranks
+
+
+def svd_rank_batched(a: torch.Tensor, k: int, tol: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Truncated SVDs of `count` small same-shaped matrices in one stream-ordered call (rc_svd_rank_batched_*).
+
+    a: [count, m, n] device tensor of float64 or float32, any strides (1 <= m, n <= 512, min(m, n) <= 128).  k (<= 128) is clamped to
+    p = min(m, n); the rank of each matrix is the first j < k with s_j == 0 or s_j / s_0 < tol (tol = 0: fixed rank k).  Returns
+    U [count, m, k], S [count, p] (all singular values, descending), Vt [count, k, n] and ranks [count]; the columns of U and rows of
+    Vt past a matrix's rank are zero, and the largest-|.| entry of each kept column of U is positive.  Complex data (complex128,
+    complex64) goes to svd_rank_batched_complex; this function raises TypeError for it."""
+    return _svd_rank_batched("svd_rank_batched", False, a, k, tol)
 
 
 def svd_rank_batched_complex(a: torch.Tensor, k: int, tol: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -145,28 +151,7 @@ def svd_rank_batched_complex(a: torch.Tensor, k: int, tol: float = 0.0) -> Tuple
     complex64; all p = min(m, n) singular values, descending), Vt [count, k, n] (complex, the conjugate transpose of V, so that
     U[:, :, :r] S[:, :r] Vt[:, :r, :] is the rank-r truncation) and ranks [count].  Phase rule: in each kept column of U the first of
     its largest-modulus entries is real and positive, its imaginary part exactly 0; conj(a) gives the conjugated U and Vt bit for bit."""
-    from . import _lib
-    from .types import as_device
-
-    a = as_device(a).resolve_conj()  # a lazily conjugated complex view is materialised: the kernels read the stored values
-    if a.dim() != 3:
-        raise AssertionError("expected a [count, m, n] batch")
-    if a.dtype not in (torch.complex128, torch.complex64):
-        raise TypeError(f"svd_rank_batched_complex: complex128 or complex64 data expected, got {a.dtype}")
-    real = torch.float64 if a.dtype == torch.complex128 else torch.float32
-    count, m, n = a.shape
-    p = min(m, n)
-    kk = min(int(k), p)
-    u = torch.empty((count, m, kk), dtype=a.dtype, device=a.device)
-    s = torch.empty((count, p), dtype=real, device=a.device)
-    vt = torch.empty((count, kk, n), dtype=a.dtype, device=a.device)
-    ranks = torch.empty(count, dtype=torch.int64, device=a.device)
-    view = _lib.rc_matrix(a.data_ptr(), m, n, a.stride(1), a.stride(2))
-    _lib.default_context().call(f"rc_svd_rank_batched_{_lib.suffix(a.dtype)}", view, ctypes.c_int64(a.stride(0)), ctypes.c_int32(count),
-                                ctypes.c_int64(int(k)), ctypes.c_double(float(tol)), _lib.mat(u[0] if count else u.new_empty(m, kk)),
-                                ctypes.c_int64(m * kk), ctypes.c_void_p(s.data_ptr()), _lib.mat(vt[0] if count else vt.new_empty(kk, n)),
-                                ctypes.c_int64(kk * n), _lib.i64p(ranks))
-    return u, s, vt, ranks
+    return _svd_rank_batched("svd_rank_batched_complex", True, a, k, tol)
 
 
 def lowrank_apply_batched(left: torch.Tensor, right: torch.Tensor, b: Optional[torch.Tensor] = None, mid: Optional[torch.Tensor] = None,
@@ -976,141 +961,20 @@ def sketch_svd_rank_batched_complex(a: torch.Tensor, k: int, tol: float = 0.0, o
     return column_id_to_svd_tall_batched_complex(c, z, ranks, k, tol)
 
 
-def sketch_range_step_batched(a: torch.Tensor, omega: Optional[torch.Tensor] = None, oversampling: int = 8, k: Optional[int] = None, seed: int = 0,
-                              return_sketch: bool = False):
-    """One range step of a power iteration on `count` tall same-shaped blocks in one stream-ordered call (rc_sketch_range_step_batched_*):
-    per block the sketch Y = omega a (l x n, sketch_column_id_rank_batched's bit for bit), an orthonormal basis Q (l x n) of Y's rows from a
-    column-pivoted Householder QR of Y^T, and the projection P = a Q^T (m x l); the two products of one round of the reference's
-    sample_range_power_iteration (src/random_sampling.rs:131-158) with the orthonormalisation between them.
-
-    a: [count, m, n] device tensor of float64 or float32, any strides (m <= 65536, n <= 512).  omega: [l, m] (shared by the batch) or
-    [count, l, m], l <= min(128, m, n), a's dtype, any strides; None draws the shared Gaussian omega of sketch_column_id_rank_batched(a, k,
-    oversampling=oversampling, seed=seed), l = min(k + oversampling, 128) rows.  Returns Q [count, l, n], P [count, m, l], ranks [count] and,
-    with return_sketch, Y [count, l, n]: rows of Q below a block's rank r are orthonormal, rows of Q and columns of P from r on are exactly
-    zero; r is the first step whose R_jj is exactly zero or not finite, else l (no tolerance: truncation belongs to the call that ends the
-    chain).  Complex data and mismatched dtypes raise TypeError."""
-    from . import _lib
-    from .types import as_device
-
-    who = "sketch_range_step_batched"
-    a = as_device(a)
-    if a.dtype not in (torch.float64, torch.float32):
-        raise TypeError(f"{who}: float64 or float32 data expected, got {a.dtype}")
-    if a.dim() != 3:
-        raise AssertionError("expected a [count, m, n] batch")
-    count, m, n = a.shape
-    if omega is None:
-        from .random_matrix import Rng, random_gaussian
-
-        if k is None:
-            raise AssertionError(f"{who}: k is needed to draw the default omega")
-        omega = random_gaussian((max(min(int(k) + int(oversampling), 128), 1), m), Rng(int(seed)), a.dtype)
-    omega = as_device(omega)
-    if omega.dtype != a.dtype:
-        raise TypeError(f"{who}: omega is {omega.dtype}, a is {a.dtype}")
-    if omega.dim() not in (2, 3) or (omega.dim() == 3 and omega.shape[0] != count):
-        raise AssertionError("expected omega [l, m] or [count, l, m]")
-    l = omega.shape[-2]
-    obs = omega.stride(0) if omega.dim() == 3 else 0
-    q = torch.empty((count, l, n), dtype=a.dtype, device=a.device)
-    p = torch.empty((count, m, l), dtype=a.dtype, device=a.device)
-    ranks = torch.empty(count, dtype=torch.int64, device=a.device)
-    y = torch.empty((count, l, n), dtype=a.dtype, device=a.device) if return_sketch else None
-    _lib.default_context().call("rc_sketch_range_step_batched_" + _lib.suffix(a.dtype),
-                                _lib.rc_matrix(a.data_ptr(), m, n, a.stride(1), a.stride(2)), ctypes.c_int64(a.stride(0)),
-                                _lib.rc_matrix(omega.data_ptr(), l, omega.shape[-1], omega.stride(-2), omega.stride(-1)), ctypes.c_int64(obs),
-                                ctypes.c_int32(count),
-                                _lib.rc_matrix(y.data_ptr(), l, n, n, 1) if return_sketch else _lib.mat(None), ctypes.c_int64(l * n),
-                                _lib.rc_matrix(q.data_ptr(), l, n, n, 1), ctypes.c_int64(l * n),
-                                _lib.rc_matrix(p.data_ptr(), m, l, l, 1), ctypes.c_int64(m * l), _lib.i64p(ranks))
-    return (q, p, ranks, y) if return_sketch else (q, p, ranks)
-
-
-def _power_iteration_batched(a: torch.Tensor, omega: Optional[torch.Tensor], k: int, oversampling: int, seed: int) -> torch.Tensor:
-    """One full power iteration: the range step, then P orthonormalised by the tall recompression with right = I at the step's ranks (zero
-    singular values give exactly zero columns); U^T, a strided view, is the next omega.  Two launches, nothing on the host between them."""
-    _, p, ranks = sketch_range_step_batched(a, omega, oversampling, k, seed)
-    l = p.shape[2]
-    eye = torch.eye(l, dtype=p.dtype, device=p.device).expand(p.shape[0], l, l)
-    u, _, _, _ = lowrank_recompress_tall_batched(p, eye, l, 0.0, ranks=ranks)
-    return u.mT
-
-
-def sketch_power_omega_batched(a: torch.Tensor, k: int, power_iterations: int, omega: Optional[torch.Tensor] = None, oversampling: int = 8,
-                               seed: int = 0) -> torch.Tensor:
-    """The test matrix after `power_iterations` rounds of the reference's sample_range_power_iteration (src/random_sampling.rs:131-158) on every
-    block of a batch, both half-steps orthonormalised: per round sketch_range_step_batched, then lowrank_recompress_tall_batched(p, I, k=l,
-    tol=0, ranks=the step's ranks), whose U^T (a strided view, no copy) is the next omega.  Two launches per round and no host
-    synchronisation.  a, omega, k, oversampling and seed as sketch_range_step_batched.  Returns omega_q [count, l, m], whose rows are
-    orthonormal (exactly zero past a block's rank); with power_iterations = 0 the omega given or drawn is returned unchanged ([l, m] when
-    shared).  Complex data raises TypeError."""
-    from .types import as_device
-
-    a = as_device(a)
-    if a.dtype not in (torch.float64, torch.float32):
-        raise TypeError(f"sketch_power_omega_batched: float64 or float32 data expected, got {a.dtype}")
-    if int(power_iterations) < 0:
-        raise AssertionError("sketch_power_omega_batched: power_iterations must be >= 0")
-    if omega is None:
-        from .random_matrix import Rng, random_gaussian
-
-        omega = random_gaussian((max(min(int(k) + int(oversampling), 128), 1), a.shape[-2]), Rng(int(seed)), a.dtype)
-    for _ in range(int(power_iterations)):
-        omega = _power_iteration_batched(a, omega, k, oversampling, seed)
-    return omega
-
-
-def sketch_column_id_rank_power_batched(a: torch.Tensor, k: int, tol: float = 0.0, power_iterations: int = 1, omega: Optional[torch.Tensor] = None,
-                                        oversampling: int = 8, seed: int = 0, return_sketch: bool = False):
-    """sketch_column_id_rank_batched after `power_iterations` rounds of power iteration on the test matrix: sketch_power_omega_batched(a, k,
-    power_iterations, omega, oversampling, seed), then sketch_column_id_rank_batched(a, k, tol, that omega).  On slowly decaying spectra
-    one round roughly halves the error of the one-pass call; more add little.  The return tuple is sketch_column_id_rank_batched's;
-    power_iterations = 0 is that function on the same arguments, bit for bit.  2 q + 1 launches, no host synchronisation.  The power
-    rounds need l <= min(128, m, n).  Complex data raises TypeError."""
-    if int(power_iterations) == 0:
-        return sketch_column_id_rank_batched(a, k, tol, omega, oversampling, seed, return_sketch)
-    omega_q = sketch_power_omega_batched(a, k, power_iterations, omega, oversampling, seed)
-    return sketch_column_id_rank_batched(a, k, tol, omega_q, oversampling, seed, return_sketch)
-
-
-def sketch_svd_rank_power_batched(a: torch.Tensor, k: int, tol: float = 0.0, power_iterations: int = 1, omega: Optional[torch.Tensor] = None,
-                                  oversampling: int = 8, seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    """Batched randomized SVDs of tall blocks with power iteration: power_iterations - 1 full rounds (sketch_power_omega_batched), one more
-    range step (Q, P = a Q^T, ranks), then lowrank_recompress_tall_batched(left=P, right=Q, ranks=the step's ranks, k, tol): the
-    reference's svd_from_range_estimate on a ~ (a Q^T) Q.  Returns (U [count, m, kk], S [count, l], Vt [count, kk, n], ranks), kk = min(k, l).
-    power_iterations = 0 delegates to sketch_svd_rank_batched on the same arguments.  2 q launches, no host synchronisation.  Complex data
-    raises TypeError."""
-    if int(power_iterations) == 0:
-        return sketch_svd_rank_batched(a, k, tol, omega, oversampling, seed)
-    omega_q = sketch_power_omega_batched(a, k, int(power_iterations) - 1, omega, oversampling, seed)
-    q, p, ranks = sketch_range_step_batched(a, omega_q, oversampling, k, seed)
-    return lowrank_recompress_tall_batched(p, q, k, tol, ranks=ranks)
-
-
-def _require_complex(who: str, a) -> None:
-    """TypeError for anything but complex128 / complex64 data, raised before a device is asked for."""
+def _require_dtype(who: str, complex_data: bool, a) -> None:
+    """TypeError for anything but complex128 / complex64 (complex_data) or float64 / float32 data, raised before a device is asked for."""
     dtype = a.dtype if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a)).dtype
-    if dtype not in (torch.complex128, torch.complex64):
-        raise TypeError(f"{who}: complex128 or complex64 data expected, got {dtype}")
+    if dtype not in ((torch.complex128, torch.complex64) if complex_data else (torch.float64, torch.float32)):
+        raise TypeError(f"{who}: {'complex128 or complex64' if complex_data else 'float64 or float32'} data expected, got {dtype}")
 
 
-def sketch_range_step_batched_complex(a: torch.Tensor, omega: Optional[torch.Tensor] = None, oversampling: int = 8, k: Optional[int] = None,
-                                      seed: int = 0, return_sketch: bool = False, conj_p: bool = False):
-    """sketch_range_step_batched for complex tall blocks (rc_sketch_range_step_complex_batched_c64 / _c32): a and omega complex128 or complex64
-    device tensors of one dtype (lazily conjugated views are materialised); real data and mismatched dtypes raise TypeError.  Per block
-    Y = omega a (l x n, nothing conjugated, sketch_column_id_rank_batched_complex's bit for bit), Q (l x n) with Q Q^H = I on its first r
-    rows, which span Y's rows, from the column-pivoted complex Householder QR of the plain transpose Y^T, and P = a Q^H (m x l), so
-    a ~ P Q with nothing conjugated.  conj_p=True returns conj(P) instead, the same bits with the sign of every imaginary part flipped at
-    the store: the tall complex recompression of conj(P) gives conj(U), whose plain transpose U^H is the next test matrix of a power
-    iteration, so no conjugation kernel runs anywhere.  omega=None draws the shared complex Gaussian of
-    sketch_column_id_rank_batched_complex(a, k, oversampling=oversampling, seed=seed).  Returns Q [count, l, n], P [count, m, l],
-    ranks [count] and, with return_sketch, Y [count, l, n]; rows of Q and columns of P from a block's rank r on are exactly zero; r is the
-    first step whose real R_jj is exactly zero or not finite, else l."""
+def _sketch_range_step_batched(who: str, complex_data: bool, a, omega, oversampling, k, seed, return_sketch: bool, conj_p: bool):
+    """The body of sketch_range_step_batched and sketch_range_step_batched_complex: the checks, the default omega and the call; only the
+    complex entry points take conj_p."""
     from . import _lib
     from .types import as_device
 
-    who = "sketch_range_step_batched_complex"
-    _require_complex(who, a)
+    _require_dtype(who, complex_data, a)
     a = as_device(a)
     if a.dim() != 3:
         raise AssertionError("expected a [count, m, n] batch")
@@ -1134,25 +998,133 @@ def sketch_range_step_batched_complex(a: torch.Tensor, omega: Optional[torch.Ten
     p = torch.empty((count, m, l), dtype=a.dtype, device=a.device)
     ranks = torch.empty(count, dtype=torch.int64, device=a.device)
     y = torch.empty((count, l, n), dtype=a.dtype, device=a.device) if return_sketch else None
-    _lib.default_context().call("rc_sketch_range_step_complex_batched_" + _lib.suffix(a.dtype),
+    stem = "rc_sketch_range_step_complex_batched_" if complex_data else "rc_sketch_range_step_batched_"
+    _lib.default_context().call(stem + _lib.suffix(a.dtype),
                                 _lib.rc_matrix(a.data_ptr(), m, n, a.stride(1), a.stride(2)), ctypes.c_int64(a.stride(0)),
                                 _lib.rc_matrix(omega.data_ptr(), l, omega.shape[-1], omega.stride(-2), omega.stride(-1)), ctypes.c_int64(obs),
                                 ctypes.c_int32(count),
                                 _lib.rc_matrix(y.data_ptr(), l, n, n, 1) if return_sketch else _lib.mat(None), ctypes.c_int64(l * n),
                                 _lib.rc_matrix(q.data_ptr(), l, n, n, 1), ctypes.c_int64(l * n),
-                                _lib.rc_matrix(p.data_ptr(), m, l, l, 1), ctypes.c_int64(m * l), _lib.i64p(ranks), ctypes.c_int32(1 if conj_p else 0))
+                                _lib.rc_matrix(p.data_ptr(), m, l, l, 1), ctypes.c_int64(m * l), _lib.i64p(ranks),
+                                *([ctypes.c_int32(1 if conj_p else 0)] if complex_data else []))
     return (q, p, ranks, y) if return_sketch else (q, p, ranks)
 
 
-def _power_iteration_batched_complex(a: torch.Tensor, omega: Optional[torch.Tensor], k: int, oversampling: int, seed: int) -> torch.Tensor:
-    """One full power iteration on complex blocks: the range step with conj_p, then conj(P) orthonormalised by the tall complex recompression
-    with right = I at the step's ranks: its U is conj of P's basis, so U^T, a strided view, is that basis' conjugate transpose and the
-    next omega.  Two launches, nothing on the host between them and nothing conjugated by a kernel of its own."""
-    _, p, ranks = sketch_range_step_batched_complex(a, omega, oversampling, k, seed, conj_p=True)
+def _power_iteration_batched(complex_data: bool, a, omega, k, oversampling, seed) -> torch.Tensor:
+    """One full power iteration: the range step, then P orthonormalised by the tall recompression with right = I at the step's ranks (zero
+    singular values give exactly zero columns); U^T, a strided view, is the next omega.  On complex blocks the step runs with conj_p: the
+    recompression of conj(P) gives conj of P's basis, so U^T is that basis' conjugate transpose and nothing is conjugated by a kernel of
+    its own.  Two launches, nothing on the host between them."""
+    sfx = "_complex" if complex_data else ""
+    _, p, ranks = _sketch_range_step_batched("sketch_range_step_batched" + sfx, complex_data, a, omega, oversampling, k, seed, False, complex_data)
     l = p.shape[2]
     eye = torch.eye(l, dtype=p.dtype, device=p.device).expand(p.shape[0], l, l)
-    u, _, _, _ = lowrank_recompress_tall_batched_complex(p, eye, l, 0.0, ranks=ranks)
+    u, _, _, _ = _lowrank_recompress_batched("lowrank_recompress_tall_batched" + sfx, complex_data, p, eye, l, 0.0, None, None, ranks, tall=True)
     return u.mT
+
+
+def _sketch_power_omega_batched(who: str, complex_data: bool, a, k, power_iterations, omega, oversampling, seed) -> torch.Tensor:
+    """The body of sketch_power_omega_batched and sketch_power_omega_batched_complex."""
+    from .types import as_device
+
+    _require_dtype(who, complex_data, a)
+    a = as_device(a)
+    if int(power_iterations) < 0:
+        raise AssertionError(f"{who}: power_iterations must be >= 0")
+    if omega is None:
+        from .random_matrix import Rng, random_gaussian
+
+        omega = random_gaussian((max(min(int(k) + int(oversampling), 128), 1), a.shape[-2]), Rng(int(seed)), a.dtype)
+    for _ in range(int(power_iterations)):
+        omega = _power_iteration_batched(complex_data, a, omega, k, oversampling, seed)
+    return omega
+
+
+def _sketch_column_id_rank_power_batched(who: str, complex_data: bool, a, k, tol, power_iterations, omega, oversampling, seed, return_sketch: bool):
+    """The body of sketch_column_id_rank_power_batched and its _complex twin: the power rounds on omega, then the one-pass call.  The complex
+    name refuses real data itself; the real one leaves complex data to the calls below, which refuse it under their own names."""
+    sfx = "_complex" if complex_data else ""
+    if complex_data:
+        _require_dtype(who, True, a)
+    if int(power_iterations) != 0:
+        omega = _sketch_power_omega_batched("sketch_power_omega_batched" + sfx, complex_data, a, k, power_iterations, omega, oversampling, seed)
+    return _sketch_column_id_rank_batched("sketch_column_id_rank_batched" + sfx, complex_data, a, k, tol, omega, oversampling, seed, return_sketch)
+
+
+def _sketch_svd_rank_power_batched(who: str, complex_data: bool, a, k, tol, power_iterations, omega, oversampling, seed):
+    """The body of sketch_svd_rank_power_batched and its _complex twin: all but the last power round on omega, one more range step (P not
+    conjugated), then the tall recompression of (P, Q).  Who refuses data of the other kind: as in _sketch_column_id_rank_power_batched."""
+    sfx = "_complex" if complex_data else ""
+    if complex_data:
+        _require_dtype(who, True, a)
+    if int(power_iterations) == 0:
+        return (sketch_svd_rank_batched_complex if complex_data else sketch_svd_rank_batched)(a, k, tol, omega, oversampling, seed)
+    omega_q = _sketch_power_omega_batched("sketch_power_omega_batched" + sfx, complex_data, a, k, int(power_iterations) - 1, omega, oversampling, seed)
+    q, p, ranks = _sketch_range_step_batched("sketch_range_step_batched" + sfx, complex_data, a, omega_q, oversampling, k, seed, False, False)
+    return _lowrank_recompress_batched("lowrank_recompress_tall_batched" + sfx, complex_data, p, q, k, tol, None, None, ranks, tall=True)
+
+
+def sketch_range_step_batched(a: torch.Tensor, omega: Optional[torch.Tensor] = None, oversampling: int = 8, k: Optional[int] = None, seed: int = 0,
+                              return_sketch: bool = False):
+    """One range step of a power iteration on `count` tall same-shaped blocks in one stream-ordered call (rc_sketch_range_step_batched_*):
+    per block the sketch Y = omega a (l x n, sketch_column_id_rank_batched's bit for bit), an orthonormal basis Q (l x n) of Y's rows from a
+    column-pivoted Householder QR of Y^T, and the projection P = a Q^T (m x l); the two products of one round of the reference's
+    sample_range_power_iteration (src/random_sampling.rs:131-158) with the orthonormalisation between them.
+
+    a: [count, m, n] device tensor of float64 or float32, any strides (m <= 65536, n <= 512).  omega: [l, m] (shared by the batch) or
+    [count, l, m], l <= min(128, m, n), a's dtype, any strides; None draws the shared Gaussian omega of sketch_column_id_rank_batched(a, k,
+    oversampling=oversampling, seed=seed), l = min(k + oversampling, 128) rows.  Returns Q [count, l, n], P [count, m, l], ranks [count] and,
+    with return_sketch, Y [count, l, n]: rows of Q below a block's rank r are orthonormal, rows of Q and columns of P from r on are exactly
+    zero; r is the first step whose R_jj is exactly zero or not finite, else l (no tolerance: truncation belongs to the call that ends the
+    chain).  Complex data and mismatched dtypes raise TypeError."""
+    return _sketch_range_step_batched("sketch_range_step_batched", False, a, omega, oversampling, k, seed, return_sketch, False)
+
+
+def sketch_power_omega_batched(a: torch.Tensor, k: int, power_iterations: int, omega: Optional[torch.Tensor] = None, oversampling: int = 8,
+                               seed: int = 0) -> torch.Tensor:
+    """The test matrix after `power_iterations` rounds of the reference's sample_range_power_iteration (src/random_sampling.rs:131-158) on every
+    block of a batch, both half-steps orthonormalised: per round sketch_range_step_batched, then lowrank_recompress_tall_batched(p, I, k=l,
+    tol=0, ranks=the step's ranks), whose U^T (a strided view, no copy) is the next omega.  Two launches per round and no host
+    synchronisation.  a, omega, k, oversampling and seed as sketch_range_step_batched.  Returns omega_q [count, l, m], whose rows are
+    orthonormal (exactly zero past a block's rank); with power_iterations = 0 the omega given or drawn is returned unchanged ([l, m] when
+    shared).  Complex data raises TypeError."""
+    return _sketch_power_omega_batched("sketch_power_omega_batched", False, a, k, power_iterations, omega, oversampling, seed)
+
+
+def sketch_column_id_rank_power_batched(a: torch.Tensor, k: int, tol: float = 0.0, power_iterations: int = 1, omega: Optional[torch.Tensor] = None,
+                                        oversampling: int = 8, seed: int = 0, return_sketch: bool = False):
+    """sketch_column_id_rank_batched after `power_iterations` rounds of power iteration on the test matrix: sketch_power_omega_batched(a, k,
+    power_iterations, omega, oversampling, seed), then sketch_column_id_rank_batched(a, k, tol, that omega).  On slowly decaying spectra
+    one round roughly halves the error of the one-pass call; more add little.  The return tuple is sketch_column_id_rank_batched's;
+    power_iterations = 0 is that function on the same arguments, bit for bit.  2 q + 1 launches, no host synchronisation.  The power
+    rounds need l <= min(128, m, n).  Complex data raises TypeError."""
+    return _sketch_column_id_rank_power_batched("sketch_column_id_rank_power_batched", False, a, k, tol, power_iterations, omega, oversampling, seed,
+                                                return_sketch)
+
+
+def sketch_svd_rank_power_batched(a: torch.Tensor, k: int, tol: float = 0.0, power_iterations: int = 1, omega: Optional[torch.Tensor] = None,
+                                  oversampling: int = 8, seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Batched randomized SVDs of tall blocks with power iteration: power_iterations - 1 full rounds (sketch_power_omega_batched), one more
+    range step (Q, P = a Q^T, ranks), then lowrank_recompress_tall_batched(left=P, right=Q, ranks=the step's ranks, k, tol): the
+    reference's svd_from_range_estimate on a ~ (a Q^T) Q.  Returns (U [count, m, kk], S [count, l], Vt [count, kk, n], ranks), kk = min(k, l).
+    power_iterations = 0 delegates to sketch_svd_rank_batched on the same arguments.  2 q launches, no host synchronisation.  Complex data
+    raises TypeError."""
+    return _sketch_svd_rank_power_batched("sketch_svd_rank_power_batched", False, a, k, tol, power_iterations, omega, oversampling, seed)
+
+
+def sketch_range_step_batched_complex(a: torch.Tensor, omega: Optional[torch.Tensor] = None, oversampling: int = 8, k: Optional[int] = None,
+                                      seed: int = 0, return_sketch: bool = False, conj_p: bool = False):
+    """sketch_range_step_batched for complex tall blocks (rc_sketch_range_step_complex_batched_c64 / _c32): a and omega complex128 or complex64
+    device tensors of one dtype (lazily conjugated views are materialised); real data and mismatched dtypes raise TypeError.  Per block
+    Y = omega a (l x n, nothing conjugated, sketch_column_id_rank_batched_complex's bit for bit), Q (l x n) with Q Q^H = I on its first r
+    rows, which span Y's rows, from the column-pivoted complex Householder QR of the plain transpose Y^T, and P = a Q^H (m x l), so
+    a ~ P Q with nothing conjugated.  conj_p=True returns conj(P) instead, the same bits with the sign of every imaginary part flipped at
+    the store: the tall complex recompression of conj(P) gives conj(U), whose plain transpose U^H is the next test matrix of a power
+    iteration, so no conjugation kernel runs anywhere.  omega=None draws the shared complex Gaussian of
+    sketch_column_id_rank_batched_complex(a, k, oversampling=oversampling, seed=seed).  Returns Q [count, l, n], P [count, m, l],
+    ranks [count] and, with return_sketch, Y [count, l, n]; rows of Q and columns of P from a block's rank r on are exactly zero; r is the
+    first step whose real R_jj is exactly zero or not finite, else l."""
+    return _sketch_range_step_batched("sketch_range_step_batched_complex", True, a, omega, oversampling, k, seed, return_sketch, conj_p)
 
 
 def sketch_power_omega_batched_complex(a: torch.Tensor, k: int, power_iterations: int, omega: Optional[torch.Tensor] = None, oversampling: int = 8,
@@ -1163,19 +1135,7 @@ def sketch_power_omega_batched_complex(a: torch.Tensor, k: int, power_iterations
     U^H of the basis of a Q^H's columns and the next omega.  Two launches per round and no host synchronisation.  Returns omega_q
     [count, l, m] with orthonormal rows (exactly zero past a block's rank); with power_iterations = 0 the omega given or drawn is returned
     unchanged ([l, m] when shared).  Real data raises TypeError."""
-    from .types import as_device
-
-    _require_complex("sketch_power_omega_batched_complex", a)
-    a = as_device(a)
-    if int(power_iterations) < 0:
-        raise AssertionError("sketch_power_omega_batched_complex: power_iterations must be >= 0")
-    if omega is None:
-        from .random_matrix import Rng, random_gaussian
-
-        omega = random_gaussian((max(min(int(k) + int(oversampling), 128), 1), a.shape[-2]), Rng(int(seed)), a.dtype)
-    for _ in range(int(power_iterations)):
-        omega = _power_iteration_batched_complex(a, omega, k, oversampling, seed)
-    return omega
+    return _sketch_power_omega_batched("sketch_power_omega_batched_complex", True, a, k, power_iterations, omega, oversampling, seed)
 
 
 def sketch_column_id_rank_power_batched_complex(a: torch.Tensor, k: int, tol: float = 0.0, power_iterations: int = 1,
@@ -1185,11 +1145,8 @@ def sketch_column_id_rank_power_batched_complex(a: torch.Tensor, k: int, tol: fl
     oversampling, seed), then sketch_column_id_rank_batched_complex(a, k, tol, that omega).  The return tuple is
     sketch_column_id_rank_batched_complex's; power_iterations = 0 is that function on the same arguments, bit for bit.  2 q + 1 launches,
     no host synchronisation.  The power rounds need l <= min(128, m, n).  Real data raises TypeError."""
-    _require_complex("sketch_column_id_rank_power_batched_complex", a)
-    if int(power_iterations) == 0:
-        return sketch_column_id_rank_batched_complex(a, k, tol, omega, oversampling, seed, return_sketch)
-    omega_q = sketch_power_omega_batched_complex(a, k, power_iterations, omega, oversampling, seed)
-    return sketch_column_id_rank_batched_complex(a, k, tol, omega_q, oversampling, seed, return_sketch)
+    return _sketch_column_id_rank_power_batched("sketch_column_id_rank_power_batched_complex", True, a, k, tol, power_iterations, omega, oversampling,
+                                                seed, return_sketch)
 
 
 def sketch_svd_rank_power_batched_complex(a: torch.Tensor, k: int, tol: float = 0.0, power_iterations: int = 1, omega: Optional[torch.Tensor] = None,
@@ -1199,12 +1156,7 @@ def sketch_svd_rank_power_batched_complex(a: torch.Tensor, k: int, tol: float = 
     k, tol): the reference's svd_from_range_estimate on a ~ (a Q^H) Q.  Returns (U [count, m, kk], S real [count, l], Vt = V^H
     [count, kk, n], ranks), kk = min(k, l).  power_iterations = 0 delegates to sketch_svd_rank_batched_complex on the same arguments.
     2 q launches, no host synchronisation.  Real data raises TypeError."""
-    _require_complex("sketch_svd_rank_power_batched_complex", a)
-    if int(power_iterations) == 0:
-        return sketch_svd_rank_batched_complex(a, k, tol, omega, oversampling, seed)
-    omega_q = sketch_power_omega_batched_complex(a, k, int(power_iterations) - 1, omega, oversampling, seed)
-    q, p, ranks = sketch_range_step_batched_complex(a, omega_q, oversampling, k, seed)
-    return lowrank_recompress_tall_batched_complex(p, q, k, tol, ranks=ranks)
+    return _sketch_svd_rank_power_batched("sketch_svd_rank_power_batched_complex", True, a, k, tol, power_iterations, omega, oversampling, seed)
 
 
 def packed_bytes(m: int, n: int, k: int, elem_size: int) -> int:

@@ -186,52 +186,6 @@ void rc_context::release_all() {
 
 namespace {
 
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        (void)hipGetDevice(&prev);
-        if (prev != dev) (void)hipSetDevice(dev);
-        else prev = -1;
-    }
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-// Entry into a C-ABI call.  The outermost call of a context resets its workspace arena; a call made from INSIDE another one -- an
-// operator callback (rc_operator) that uses the library's own products on the same context -- only marks the arena and releases
-// what it took when it returns, so the temporaries of the call around it (among them the callback's operands) stay where they are.
-struct CallScope {
-    rc_context *c;
-    size_t off = 0;
-    bool outer;
-    explicit CallScope(rc_context *ctx) : c(ctx), outer(ctx->call_depth++ == 0) {
-        if (outer) c->reset_arena();
-        else off = c->arena_off;
-    }
-    ~CallScope() {
-        --c->call_depth;
-        if (!outer) c->arena_off = off;
-    }
-};
-
-template <typename F>
-rc_status guarded(rc_context *ctx, F &&f) {
-    if (!ctx) return RC_INVALID_ARGUMENT;
-    DeviceGuard dg(ctx->device);
-    try {
-        CallScope scope(ctx);
-        f();
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) fail(RC_RUNTIME_ERROR, "kernel launch failed: %s", hipGetErrorString(e));
-        return RC_OK;
-    } catch (const Error &e) {
-        ctx->last_error = e.msg;
-        return e.code;
-    } catch (const std::exception &e) {
-        ctx->last_error = e.what();
-        return RC_RUNTIME_ERROR;
-    }
-}
-
 // small device -> host read-back through the pinned buffer (synchronises the stream)
 template <typename T>
 void read_back(rc_context *c, const T *dev, T *host, size_t n) {
@@ -1086,378 +1040,6 @@ void column_id_rank(rc_context *c, Mat<T> a, int64_t k, Mat<T> cm, Mat<T> z, int
     qr_column_id(c, q, r, col_ind, cm, z, /*own_ind=*/true);
 }
 
-// the domain of the batched small-matrix kernels (kernels_batched_id.hip); returns k clamped to min(m, n)
-template <typename T>
-int64_t batched_domain(const char *who, const char *larger, const Mat<T> &a, int32_t count, int64_t k, double tol) {
-    const int64_t m = a.rows, n = a.cols;
-    RC_REQUIRE(count >= 0, RC_INVALID_ARGUMENT, "%s: count = %d < 0", who, (int)count);
-    RC_REQUIRE(m >= 1 && m <= 512 && n >= 1 && n <= 512 && k >= 1 && k <= 128, RC_INVALID_ARGUMENT,
-               "%s: needs 1 <= m, n <= 512 and 1 <= k <= 128 (got %lld x %lld, k = %lld); use %s for larger matrices", who, (long long)m, (long long)n,
-               (long long)k, larger);
-    RC_REQUIRE(tol < 1.0 && 0.0 <= tol, RC_INVALID_ARGUMENT, "Require 0 <= tol < 1.0");
-    return std::min(k, std::min(m, n));
-}
-// one output view spans (rows - 1) |rs| + (cols - 1) |cs| + 1 elements; a smaller batch stride would overlap two matrices
-template <typename T>
-void check_batch_stride(const char *who, const char *name, int64_t bs, const Mat<T> &v, int32_t count) {
-    const int64_t span = (v.rows - 1) * std::abs(v.rs) + (v.cols - 1) * std::abs(v.cs) + 1;
-    RC_REQUIRE(count <= 1 || bs >= span, RC_INVALID_ARGUMENT, "%s: %s_batch_stride %lld < %lld overlaps the outputs of two matrices", who, name,
-               (long long)bs, (long long)span);
-}
-
-}  // namespace
-
-// the argument checks of the batched calls, shared with the complex entry points (rc_complex.hip) through rc_common.hpp
-namespace rc {
-template <typename T>
-int64_t check_column_id_rank_batched(Mat<T> a, int32_t count, int64_t k, double tol, Mat<T> cm, int64_t cbs, Mat<T> z, int64_t zbs,
-                                     const int64_t *col_ind, const int64_t *ranks) {
-    const int64_t m = a.rows, n = a.cols;
-    k = batched_domain("column_id_rank_batched", "rc_column_id_rank_* / rc_batch_column_id_*", a, count, k, tol);
-    RC_REQUIRE(cm.rows == m && cm.cols == k && z.rows == k && z.cols == n, RC_INVALID_ARGUMENT,
-               "column_id_rank_batched: c must be %lld x %lld and z %lld x %lld (k clamped to min(m, n))", (long long)m, (long long)k, (long long)k, (long long)n);
-    check_batch_stride("column_id_rank_batched", "c", cbs, cm, count);
-    check_batch_stride("column_id_rank_batched", "z", zbs, z, count);
-    if (count > 0) RC_REQUIRE(a.p && cm.p && z.p && col_ind && ranks, RC_INVALID_ARGUMENT, "column_id_rank_batched: null pointer");
-    return k;
-}
-template <typename T>
-int64_t check_two_sided_id_rank_batched(Mat<T> a, int32_t count, int64_t k, double tol, Mat<T> cm, int64_t cbs, Mat<T> x, int64_t xbs, Mat<T> r, int64_t rbs,
-                                        const int64_t *row_ind, const int64_t *col_ind, const int64_t *ranks) {
-    const int64_t m = a.rows, n = a.cols;
-    const char *who = "two_sided_id_rank_batched";
-    k = batched_domain(who, "rc_column_id_rank_* + rc_column_id_two_sided_*", a, count, k, tol);
-    RC_REQUIRE(cm.rows == m && cm.cols == k && x.rows == k && x.cols == k && r.rows == k && r.cols == n, RC_INVALID_ARGUMENT,
-               "two_sided_id_rank_batched: c must be %lld x %lld, x %lld x %lld and r %lld x %lld (k clamped to min(m, n))", (long long)m, (long long)k,
-               (long long)k, (long long)k, (long long)k, (long long)n);
-    check_batch_stride(who, "c", cbs, cm, count);
-    check_batch_stride(who, "x", xbs, x, count);
-    check_batch_stride(who, "r", rbs, r, count);
-    if (count > 0) RC_REQUIRE(a.p && cm.p && x.p && r.p && row_ind && col_ind && ranks, RC_INVALID_ARGUMENT, "two_sided_id_rank_batched: null pointer");
-    return k;
-}
-// the batched SVD's checks: the batched IDs' domain plus min(m, n) <= 128 (the core of one workgroup)
-template <typename T>
-int64_t check_svd_rank_batched(Mat<T> a, int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs, const T *s, Mat<T> vt, int64_t vbs,
-                               const int64_t *ranks) {
-    const int64_t m = a.rows, n = a.cols;
-    const char *who = "svd_rank_batched";
-    k = batched_domain(who, "rc_compute_svd_*", a, count, k, tol);
-    RC_REQUIRE(std::min(m, n) <= 128, RC_INVALID_ARGUMENT, "%s: needs min(m, n) <= 128 (got %lld x %lld); use rc_compute_svd_* for larger matrices", who,
-               (long long)m, (long long)n);
-    RC_REQUIRE(u.rows == m && u.cols == k && vt.rows == k && vt.cols == n, RC_INVALID_ARGUMENT,
-               "svd_rank_batched: u must be %lld x %lld and vt %lld x %lld (k clamped to min(m, n))", (long long)m, (long long)k, (long long)k, (long long)n);
-    check_batch_stride(who, "u", ubs, u, count);
-    check_batch_stride(who, "vt", vbs, vt, count);
-    if (count > 0) RC_REQUIRE(a.p && u.p && s && vt.p && ranks, RC_INVALID_ARGUMENT, "svd_rank_batched: null pointer");
-    return k;
-}
-
-// rc_lowrank_apply_batched_*: the shapes of the factor chain left (m x k) [mid (k x k)] right (k x n) [b (n x nrhs)] -> y, the batched kernels' domain
-// for m, n, k, and y's batch stride; mid and b take part only when their data pointer is set
-template <typename T>
-void check_lowrank_apply_batched(Mat<T> left, Mat<T> mid, Mat<T> right, int32_t count, Mat<T> b, Mat<T> y, int64_t ybs) {
-    const char *who = "lowrank_apply_batched";
-    const int64_t m = left.rows, k = left.cols, n = right.cols;
-    RC_REQUIRE(count >= 0, RC_INVALID_ARGUMENT, "%s: count = %d < 0", who, (int)count);
-    RC_REQUIRE(m >= 1 && m <= 512 && n >= 1 && n <= 512 && k >= 1 && k <= 128, RC_INVALID_ARGUMENT,
-               "%s: needs 1 <= m, n <= 512 and 1 <= k <= 128 (got left %lld x %lld, right %lld x %lld)", who, (long long)m, (long long)k,
-               (long long)right.rows, (long long)n);
-    RC_REQUIRE(right.rows == k, RC_INVALID_ARGUMENT, "%s: left is %lld x %lld but right has %lld rows", who, (long long)m, (long long)k, (long long)right.rows);
-    RC_REQUIRE(!mid.p || (mid.rows == k && mid.cols == k), RC_INVALID_ARGUMENT, "%s: mid must be %lld x %lld (got %lld x %lld)", who, (long long)k,
-               (long long)k, (long long)mid.rows, (long long)mid.cols);
-    RC_REQUIRE(!b.p || (b.rows == n && b.cols >= 1 && b.cols <= INT32_MAX), RC_INVALID_ARGUMENT, "%s: b must be %lld x nrhs with nrhs >= 1 (got %lld x %lld)",
-               who, (long long)n, (long long)b.rows, (long long)b.cols);
-    const int64_t ncols = b.p ? b.cols : n;
-    RC_REQUIRE(y.rows == m && y.cols == ncols, RC_INVALID_ARGUMENT, "%s: y must be %lld x %lld (got %lld x %lld)", who, (long long)m, (long long)ncols,
-               (long long)y.rows, (long long)y.cols);
-    check_batch_stride(who, "y", ybs, y, count);
-    if (count > 0) RC_REQUIRE(left.p && right.p && y.p, RC_INVALID_ARGUMENT, "%s: null pointer", who);
-}
-
-// rc_lowrank_residual_batched_*: the shapes of a (m x n) against the factor chain left (m x K) [mid (K x K)] right (K x n), the sketched ID's domain
-// for m, n, K, and e's shape and batch stride when it is asked for; mid and e take part only when their data pointer is set
-template <typename T>
-void check_lowrank_residual_batched(Mat<T> a, Mat<T> left, Mat<T> mid, Mat<T> right, int32_t count, Mat<T> e, int64_t ebs, const T *err) {
-    const char *who = "lowrank_residual_batched";
-    const int64_t m = a.rows, n = a.cols, K = left.cols;
-    RC_REQUIRE(count >= 0, RC_INVALID_ARGUMENT, "%s: count = %d < 0", who, (int)count);
-    RC_REQUIRE(m >= 1 && m <= 65536 && n >= 1 && n <= 512 && K >= 1 && K <= 128, RC_INVALID_ARGUMENT,
-               "%s: needs 1 <= m <= 65536, 1 <= n <= 512 and 1 <= K <= 128 (got a %lld x %lld, left %lld x %lld)", who, (long long)m, (long long)n,
-               (long long)left.rows, (long long)K);
-    RC_REQUIRE(left.rows == m && right.rows == K && right.cols == n, RC_INVALID_ARGUMENT,
-               "%s: a is %lld x %lld but left is %lld x %lld and right %lld x %lld", who, (long long)m, (long long)n, (long long)left.rows, (long long)K,
-               (long long)right.rows, (long long)right.cols);
-    RC_REQUIRE(!mid.p || (mid.rows == K && mid.cols == K), RC_INVALID_ARGUMENT, "%s: mid must be %lld x %lld (got %lld x %lld)", who, (long long)K,
-               (long long)K, (long long)mid.rows, (long long)mid.cols);
-    if (e.p) {
-        RC_REQUIRE(e.rows == m && e.cols == n, RC_INVALID_ARGUMENT, "%s: e must be %lld x %lld (got %lld x %lld)", who, (long long)m, (long long)n,
-                   (long long)e.rows, (long long)e.cols);
-        check_batch_stride(who, "e", ebs, e, count);
-    }
-    if (count > 0) RC_REQUIRE(a.p && left.p && right.p && err, RC_INVALID_ARGUMENT, "%s: null pointer", who);
-}
-
-// rc_block_operator_apply_*: the block shape m x n (and the inner width K of the low-rank batch, 0 without one) from left / right when there is a
-// low-rank batch, else from dense; the batched kernels' domain for m, n, K; x and y as N x nrhs and M x nrhs.  Indices live on the device and are
-// checked there.
-template <typename T>
-BlockShape check_block_operator_apply(Mat<T> left, Mat<T> mid, Mat<T> right, int32_t count, Mat<T> dense, int32_t *dense_count, const BlockPattern &pat,
-                                      Mat<T> x, Mat<T> y) {
-    const char *who = "block_operator_apply";
-    if (!dense.p) *dense_count = 0;
-    RC_REQUIRE(count >= 0 && *dense_count >= 0 && pat.groups >= 0, RC_INVALID_ARGUMENT, "%s: count = %d, dense_count = %d, groups = %d: none may be negative", who,
-               (int)count, (int)*dense_count, (int)pat.groups);
-    const bool lowrank = count > 0 || left.p;
-    BlockShape sh{0, 0, 0};
-    if (lowrank) {
-        const int64_t m = left.rows, k = left.cols, n = right.cols;
-        RC_REQUIRE(m >= 1 && m <= 512 && n >= 1 && n <= 512 && k >= 1 && k <= 128, RC_INVALID_ARGUMENT,
-                   "%s: needs 1 <= m, n <= 512 and 1 <= K <= 128 (got left %lld x %lld, right %lld x %lld)", who, (long long)m, (long long)k,
-                   (long long)right.rows, (long long)n);
-        RC_REQUIRE(right.rows == k, RC_INVALID_ARGUMENT, "%s: left is %lld x %lld but right has %lld rows", who, (long long)m, (long long)k,
-                   (long long)right.rows);
-        RC_REQUIRE(!mid.p || (mid.rows == k && mid.cols == k), RC_INVALID_ARGUMENT, "%s: mid must be %lld x %lld (got %lld x %lld)", who, (long long)k,
-                   (long long)k, (long long)mid.rows, (long long)mid.cols);
-        RC_REQUIRE(!dense.p || (dense.rows == m && dense.cols == n), RC_INVALID_ARGUMENT, "%s: dense must be %lld x %lld like the low-rank blocks (got %lld x %lld)",
-                   who, (long long)m, (long long)n, (long long)dense.rows, (long long)dense.cols);
-        if (count > 0) RC_REQUIRE(left.p && right.p, RC_INVALID_ARGUMENT, "%s: null pointer (left or right with count > 0)", who);
-        sh = BlockShape{(int)m, (int)n, (int)k};
-    } else if (dense.p) {
-        RC_REQUIRE(dense.rows >= 1 && dense.rows <= 512 && dense.cols >= 1 && dense.cols <= 512, RC_INVALID_ARGUMENT,
-                   "%s: needs 1 <= m, n <= 512 (got dense %lld x %lld)", who, (long long)dense.rows, (long long)dense.cols);
-        sh = BlockShape{(int)dense.rows, (int)dense.cols, 0};
-    } else {
-        RC_REQUIRE(pat.groups == 0, RC_INVALID_ARGUMENT, "%s: neither a low-rank nor a dense batch: the block shape is unknown", who);
-    }
-    RC_REQUIRE(x.cols >= 1 && x.cols <= INT32_MAX && x.rows >= 0, RC_INVALID_ARGUMENT, "%s: x must be N x nrhs with nrhs >= 1 (got %lld x %lld)", who,
-               (long long)x.rows, (long long)x.cols);
-    RC_REQUIRE(y.cols == x.cols && y.rows >= 0, RC_INVALID_ARGUMENT, "%s: y must be M x %lld like x (got %lld x %lld)", who, (long long)x.cols,
-               (long long)y.rows, (long long)y.cols);
-    if (pat.groups > 0)
-        RC_REQUIRE(pat.group_ptr && pat.group_row && pat.entry_block && pat.entry_col && x.p && y.p, RC_INVALID_ARGUMENT,
-                   "%s: null pointer (an index array, x or y with groups > 0)", who);
-    return sh;
-}
-
-// rc_lowrank_recompress_batched_* and its complex twin: the shapes of the factor chain left (m x K) [mid (K x K)] right (K x n) against u (m x min(k, K))
-// and vt (min(k, K) x n)
-template <typename T>
-void check_lowrank_recompress_batched(Mat<T> left, Mat<T> mid, Mat<T> right, int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs, const T *s_out,
-                                      Mat<T> vt, int64_t vbs, const int64_t *ranks, int tall) {
-    const char *who = tall == RC_TALL_COMPLEX ? "lowrank_recompress_tall_complex_batched" : tall ? "lowrank_recompress_tall_batched" : "lowrank_recompress_batched";
-    const int64_t m = left.rows, K = left.cols, n = right.cols;
-    RC_REQUIRE(count >= 0, RC_INVALID_ARGUMENT, "%s: count = %d < 0", who, (int)count);
-    RC_REQUIRE(m >= 1 && m <= (tall ? 65536 : 512) && n >= 1 && n <= 512 && K >= 1 && K <= 128 && k >= 1, RC_INVALID_ARGUMENT,
-               "%s: needs 1 <= m%s <= 512, inner width 1 <= K <= 128 and k >= 1 (got left %lld x %lld, right %lld x %lld, k = %lld)", who,
-               tall ? " <= 65536, 1 <= n" : ", n", (long long)m, (long long)K, (long long)right.rows, (long long)n, (long long)k);
-    RC_REQUIRE(right.rows == K, RC_INVALID_ARGUMENT, "%s: left is %lld x %lld but right has %lld rows", who, (long long)m, (long long)K, (long long)right.rows);
-    RC_REQUIRE(K <= std::min(m, n), RC_INVALID_ARGUMENT,
-               "%s: needs K <= min(m, n) (got K = %lld for %lld x %lld blocks); rebuild the blocks with rc_lowrank_apply_batched_* and use rc_svd_rank_batched_*",
-               who, (long long)K, (long long)m, (long long)n);
-    RC_REQUIRE(tol < 1.0 && 0.0 <= tol, RC_INVALID_ARGUMENT, "Require 0 <= tol < 1.0");
-    RC_REQUIRE(!mid.p || (mid.rows == K && mid.cols == K), RC_INVALID_ARGUMENT, "%s: mid must be %lld x %lld (got %lld x %lld)", who, (long long)K,
-               (long long)K, (long long)mid.rows, (long long)mid.cols);
-    const int64_t kk = std::min(k, K);
-    RC_REQUIRE(u.rows == m && u.cols == kk && vt.rows == kk && vt.cols == n, RC_INVALID_ARGUMENT,
-               "%s: u must be %lld x %lld and vt %lld x %lld (k clamped to K)", who, (long long)m, (long long)kk, (long long)kk, (long long)n);
-    check_batch_stride(who, "u", ubs, u, count);
-    check_batch_stride(who, "vt", vbs, vt, count);
-    if (count > 0) RC_REQUIRE(left.p && right.p && u.p && s_out && vt.p && ranks, RC_INVALID_ARGUMENT, "%s: null pointer", who);
-}
-
-// the argument checks of rc_sketch_column_id_rank_batched_* and rc_sketch_column_id_rank_complex_batched_*: the views carry the shapes and strides (in
-// elements of the scalar type), the pointers only their null-ness.  Returns kk = min(k, l, n).
-template <typename T>
-int64_t check_sketch_column_id_rank_batched(Mat<T> a, Mat<T> omega, int32_t count, int64_t k, double tol, Mat<T> y, int64_t ybs, Mat<T> cm, int64_t cbs,
-                                            Mat<T> z, int64_t zbs, const int64_t *col_ind, const int64_t *ranks) {
-    const char *who = "sketch_column_id_rank_batched";
-    const int64_t m = a.rows, n = a.cols, l = omega.rows;
-    RC_REQUIRE(count >= 0, RC_INVALID_ARGUMENT, "%s: count = %d < 0", who, (int)count);
-    RC_REQUIRE(m >= 1 && m <= 65536 && n >= 1 && n <= 512 && l >= 1 && l <= 128 && k >= 1 && k <= 128, RC_INVALID_ARGUMENT,
-               "%s: needs 1 <= m <= 65536, 1 <= n <= 512, 1 <= l <= 128 and 1 <= k <= 128 (got a %lld x %lld, omega %lld x %lld, k = %lld)", who, (long long)m,
-               (long long)n, (long long)l, (long long)omega.cols, (long long)k);
-    RC_REQUIRE(omega.cols == m, RC_INVALID_ARGUMENT, "%s: a has %lld rows but omega has %lld columns", who, (long long)m, (long long)omega.cols);
-    RC_REQUIRE(tol < 1.0 && 0.0 <= tol, RC_INVALID_ARGUMENT, "Require 0 <= tol < 1.0");
-    const int64_t kk = std::min(k, std::min(l, n));
-    RC_REQUIRE(cm.rows == m && cm.cols == kk && z.rows == kk && z.cols == n, RC_INVALID_ARGUMENT,
-               "%s: c must be %lld x %lld and z %lld x %lld (k clamped to min(l, n))", who, (long long)m, (long long)kk, (long long)kk, (long long)n);
-    RC_REQUIRE(!y.p || (y.rows == l && y.cols == n), RC_INVALID_ARGUMENT, "%s: y must be %lld x %lld (got %lld x %lld)", who, (long long)l, (long long)n,
-               (long long)y.rows, (long long)y.cols);
-    check_batch_stride(who, "c", cbs, cm, count);
-    check_batch_stride(who, "z", zbs, z, count);
-    if (y.p) check_batch_stride(who, "y", ybs, y, count);
-    if (count > 0) RC_REQUIRE(a.p && omega.p && cm.p && z.p && col_ind && ranks, RC_INVALID_ARGUMENT, "%s: null pointer", who);
-    return kk;
-}
-// the argument checks of rc_sketch_range_step_batched_* and, with complex, of rc_sketch_range_step_complex_batched_* under its own name: the views
-// carry the shapes and strides (in elements of the scalar type), the pointers only their null-ness; the caller returns when count == 0
-template <typename T>
-void check_sketch_range_step_batched(Mat<T> a, Mat<T> omega, int32_t count, Mat<T> y, int64_t ybs, Mat<T> q, int64_t qbs, Mat<T> p, int64_t pbs,
-                                     const int64_t *ranks, bool complex) {
-    const char *who = complex ? "sketch_range_step_complex_batched" : "sketch_range_step_batched";
-    const int64_t m = a.rows, n = a.cols, l = omega.rows;
-    RC_REQUIRE(count >= 0, RC_INVALID_ARGUMENT, "%s: count = %d < 0", who, (int)count);
-    RC_REQUIRE(m >= 1 && m <= 65536 && n >= 1 && n <= 512 && l >= 1 && l <= 128 && l <= std::min(m, n), RC_INVALID_ARGUMENT,
-               "%s: needs 1 <= m <= 65536, 1 <= n <= 512 and 1 <= l <= min(128, m, n) (got a %lld x %lld, omega %lld x %lld)", who, (long long)m,
-               (long long)n, (long long)l, (long long)omega.cols);
-    RC_REQUIRE(omega.cols == m, RC_INVALID_ARGUMENT, "%s: a has %lld rows but omega has %lld columns", who, (long long)m, (long long)omega.cols);
-    RC_REQUIRE(!y.p || (y.rows == l && y.cols == n), RC_INVALID_ARGUMENT, "%s: y must be %lld x %lld (got %lld x %lld)", who, (long long)l, (long long)n,
-               (long long)y.rows, (long long)y.cols);
-    RC_REQUIRE(q.rows == l && q.cols == n && p.rows == m && p.cols == l, RC_INVALID_ARGUMENT, "%s: q must be %lld x %lld and p %lld x %lld", who,
-               (long long)l, (long long)n, (long long)m, (long long)l);
-    check_batch_stride(who, "q", qbs, q, count);
-    check_batch_stride(who, "p", pbs, p, count);
-    if (y.p) check_batch_stride(who, "y", ybs, y, count);
-    if (count > 0) RC_REQUIRE(a.p && omega.p && q.p && p.p && ranks, RC_INVALID_ARGUMENT, "%s: null pointer", who);
-}
-// rc_demote_batched_* / rc_promote_batched_*: one shape on both sides, the sketched ID's tall domain, and dst's batch stride
-void check_convert_batched(const char *who, const rc_matrix &src, int32_t count, const rc_matrix &dst, int64_t dbs) {
-    RC_REQUIRE(count >= 0, RC_INVALID_ARGUMENT, "%s: count = %d < 0", who, (int)count);
-    RC_REQUIRE(src.rows >= 1 && src.rows <= 65536 && src.cols >= 1 && src.cols <= 65536, RC_INVALID_ARGUMENT,
-               "%s: needs 1 <= rows, cols <= 65536 (got src %lld x %lld)", who, (long long)src.rows, (long long)src.cols);
-    RC_REQUIRE(dst.rows == src.rows && dst.cols == src.cols, RC_INVALID_ARGUMENT, "%s: dst must be %lld x %lld like src (got %lld x %lld)", who,
-               (long long)src.rows, (long long)src.cols, (long long)dst.rows, (long long)dst.cols);
-    check_batch_stride(who, "dst", dbs, from_c<char>(dst), count);
-    if (count > 0) RC_REQUIRE(src.data && dst.data, RC_INVALID_ARGUMENT, "%s: null pointer", who);
-}
-template int64_t check_column_id_rank_batched<double>(Mat<double>, int32_t, int64_t, double, Mat<double>, int64_t, Mat<double>, int64_t, const int64_t *,
-                                                      const int64_t *);
-template int64_t check_column_id_rank_batched<float>(Mat<float>, int32_t, int64_t, double, Mat<float>, int64_t, Mat<float>, int64_t, const int64_t *,
-                                                     const int64_t *);
-template int64_t check_two_sided_id_rank_batched<double>(Mat<double>, int32_t, int64_t, double, Mat<double>, int64_t, Mat<double>, int64_t, Mat<double>,
-                                                         int64_t, const int64_t *, const int64_t *, const int64_t *);
-template int64_t check_two_sided_id_rank_batched<float>(Mat<float>, int32_t, int64_t, double, Mat<float>, int64_t, Mat<float>, int64_t, Mat<float>, int64_t,
-                                                        const int64_t *, const int64_t *, const int64_t *);
-template int64_t check_svd_rank_batched<double>(Mat<double>, int32_t, int64_t, double, Mat<double>, int64_t, const double *, Mat<double>, int64_t,
-                                                const int64_t *);
-template int64_t check_svd_rank_batched<float>(Mat<float>, int32_t, int64_t, double, Mat<float>, int64_t, const float *, Mat<float>, int64_t, const int64_t *);
-template void check_lowrank_apply_batched<double>(Mat<double>, Mat<double>, Mat<double>, int32_t, Mat<double>, Mat<double>, int64_t);
-template void check_lowrank_apply_batched<float>(Mat<float>, Mat<float>, Mat<float>, int32_t, Mat<float>, Mat<float>, int64_t);
-template BlockShape check_block_operator_apply<double>(Mat<double>, Mat<double>, Mat<double>, int32_t, Mat<double>, int32_t *, const BlockPattern &, Mat<double>,
-                                                       Mat<double>);
-template BlockShape check_block_operator_apply<float>(Mat<float>, Mat<float>, Mat<float>, int32_t, Mat<float>, int32_t *, const BlockPattern &, Mat<float>,
-                                                      Mat<float>);
-template void check_lowrank_residual_batched<double>(Mat<double>, Mat<double>, Mat<double>, Mat<double>, int32_t, Mat<double>, int64_t, const double *);
-template void check_lowrank_residual_batched<float>(Mat<float>, Mat<float>, Mat<float>, Mat<float>, int32_t, Mat<float>, int64_t, const float *);
-template void check_lowrank_recompress_batched<double>(Mat<double>, Mat<double>, Mat<double>, int32_t, int64_t, double, Mat<double>, int64_t, const double *,
-                                                       Mat<double>, int64_t, const int64_t *, int);
-template void check_lowrank_recompress_batched<float>(Mat<float>, Mat<float>, Mat<float>, int32_t, int64_t, double, Mat<float>, int64_t, const float *, Mat<float>,
-                                                      int64_t, const int64_t *, int);
-
-template int64_t check_sketch_column_id_rank_batched<double>(Mat<double>, Mat<double>, int32_t, int64_t, double, Mat<double>, int64_t, Mat<double>, int64_t,
-                                                             Mat<double>, int64_t, const int64_t *, const int64_t *);
-template int64_t check_sketch_column_id_rank_batched<float>(Mat<float>, Mat<float>, int32_t, int64_t, double, Mat<float>, int64_t, Mat<float>, int64_t,
-                                                            Mat<float>, int64_t, const int64_t *, const int64_t *);
-
-template void check_sketch_range_step_batched<double>(Mat<double>, Mat<double>, int32_t, Mat<double>, int64_t, Mat<double>, int64_t, Mat<double>, int64_t,
-                                                      const int64_t *, bool);
-template void check_sketch_range_step_batched<float>(Mat<float>, Mat<float>, int32_t, Mat<float>, int64_t, Mat<float>, int64_t, Mat<float>, int64_t,
-                                                     const int64_t *, bool);
-
-}  // namespace rc
-
-namespace {
-
-// the same unit of work for many small same-shaped matrices in one launch, rank chosen per matrix by tol (0: fixed rank k)
-// without a host round trip; one path, stream-ordered, capturable
-template <typename T>
-void column_id_rank_batched(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int64_t k, double tol, Mat<T> cm, int64_t cbs, Mat<T> z, int64_t zbs,
-                            int64_t *col_ind, int64_t *ranks) {
-    k = check_column_id_rank_batched(a, count, k, tol, cm, cbs, z, zbs, col_ind, ranks);
-    if (count == 0) return;
-    batched_column_id(c, a, abs, count, k, tol, cm, cbs, z, zbs, col_ind, ranks);
-}
-
-// the two-sided ID A ~ C X R of the same batch (ColumnID::two_sided_id after the column ID), in the same one launch
-template <typename T>
-void two_sided_id_rank_batched(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int64_t k, double tol, Mat<T> cm, int64_t cbs, Mat<T> x, int64_t xbs,
-                               Mat<T> r, int64_t rbs, int64_t *row_ind, int64_t *col_ind, int64_t *ranks) {
-    k = check_two_sided_id_rank_batched(a, count, k, tol, cm, cbs, x, xbs, r, rbs, row_ind, col_ind, ranks);
-    if (count == 0) return;
-    batched_two_sided_id(c, a, abs, count, k, tol, cm, cbs, x, xbs, r, rbs, row_ind, col_ind, ranks);
-}
-
-// truncated SVDs of the same batch (SVD::compute_from -> compress(.) per matrix), rank chosen per matrix on the singular values
-template <typename T>
-void svd_rank_batched(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs, T *s, Mat<T> vt, int64_t vbs,
-                      int64_t *ranks) {
-    k = check_svd_rank_batched(a, count, k, tol, u, ubs, s, vt, vbs, ranks);
-    if (count == 0) return;
-    batched_svd(c, a, abs, count, k, tol, u, ubs, s, vt, vbs, ranks);
-}
-
-// apply (b given) or rebuild (b.p == nullptr) every block of a batch from its factors, reading the ranks on the device: one launch, no workspace
-template <typename T>
-void lowrank_apply_batched(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride, Mat<T> right, int64_t rbs,
-                           const int64_t *ranks, int32_t count, Mat<T> b, int64_t bbs, Mat<T> y, int64_t ybs) {
-    check_lowrank_apply_batched(left, mid, right, count, b, y, ybs);
-    if (count == 0) return;
-    batched_lowrank_apply(c, left, lbs, mid, mbs, s, s_stride, right, rbs, ranks, count, b, bbs, y, ybs);
-}
-
-// y = H x for the block-sparse operator made of a low-rank batch and a dense batch placed by a block-CSR pattern on the device: one launch, no workspace
-template <typename T>
-void block_operator_apply_checked(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride, Mat<T> right, int64_t rbs,
-                                  const int64_t *ranks, int32_t count, Mat<T> dense, int64_t dbs, int32_t dense_count, const BlockPattern &pat, Mat<T> x,
-                                  Mat<T> y, int32_t accumulate) {
-    const BlockShape sh = check_block_operator_apply(left, mid, right, count, dense, &dense_count, pat, x, y);
-    if (pat.groups == 0) return;
-    block_operator_apply(c, left, lbs, mid, mbs, s, s_stride, right, rbs, ranks, count, dense, dbs, dense_count, pat, sh, x, y, accumulate != 0);
-}
-
-// recompress every factor pair left (m x K) [mid (K x K)] [diag(s)] right (K x n) of a batch to a truncated SVD of rank <= min(k, K) without forming
-// the m x n blocks (SVD::to_qr / compute_from_range_estimate's scheme, src/svd.rs:150-163, :171-, with compress's rank rule, :60-101): one launch
-template <typename T>
-void lowrank_recompress_batched(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride, Mat<T> right, int64_t rbs,
-                                const int64_t *in_ranks, int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs, T *s_out, Mat<T> vt, int64_t vbs,
-                                int64_t *ranks) {
-    check_lowrank_recompress_batched(left, mid, right, count, k, tol, u, ubs, s_out, vt, vbs, ranks);
-    if (count == 0) return;
-    batched_lowrank_recompress(c, left, lbs, mid, mbs, s, s_stride, right, rbs, in_ranks, count, k, tol, u, ubs, s_out, vt, vbs, ranks);
-}
-
-// the same for a tall left factor (m <= 65536): the same checks with that bound, the left factor by a flat Householder TSQR inside the launch
-template <typename T>
-void lowrank_recompress_tall_batched(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride, Mat<T> right, int64_t rbs,
-                                     const int64_t *in_ranks, int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs, T *s_out, Mat<T> vt, int64_t vbs,
-                                     int64_t *ranks) {
-    check_lowrank_recompress_batched(left, mid, right, count, k, tol, u, ubs, s_out, vt, vbs, ranks, RC_TALL);
-    if (count == 0) return;
-    batched_lowrank_recompress_tall(c, left, lbs, mid, mbs, s, s_stride, right, rbs, in_ranks, count, k, tol, u, ubs, s_out, vt, vbs, ranks);
-}
-
-// the one-pass randomized column ID of every block of a batch: the sketch y = omega a (l x n) and the column ID of y in one launch, c gathered from a
-// (sample_range_by_rank's projection, src/random_sampling.rs, then QR::compute_from_range_estimate + column_id, src/qr.rs:311-323, per block)
-template <typename T>
-void sketch_column_id_rank_batched(rc_context *c, Mat<T> a, int64_t abs, Mat<T> omega, int64_t obs, int32_t count, int64_t k, double tol, Mat<T> y, int64_t ybs,
-                                   Mat<T> cm, int64_t cbs, Mat<T> z, int64_t zbs, int64_t *col_ind, int64_t *ranks) {
-    const int64_t kk = check_sketch_column_id_rank_batched(a, omega, count, k, tol, y, ybs, cm, cbs, z, zbs, col_ind, ranks);
-    if (count == 0) return;
-    batched_sketch_column_id(c, a, abs, omega, obs, count, kk, tol, y, ybs, cm, cbs, z, zbs, col_ind, ranks);
-}
-
-// one range step of a power iteration on every block of a batch (sample_range_power_iteration, src/random_sampling.rs:131-158): the sketch y = omega a,
-// an orthonormal basis q of its rows by a pivoted Householder QR of y^T and the projection p = a q^T, in one launch; p is orthonormalised by
-// rc_lowrank_recompress_tall_batched_* with right = I before its transpose is the next omega
-template <typename T>
-void sketch_range_step_batched(rc_context *c, Mat<T> a, int64_t abs, Mat<T> omega, int64_t obs, int32_t count, Mat<T> y, int64_t ybs, Mat<T> q, int64_t qbs,
-                               Mat<T> p, int64_t pbs, int64_t *ranks) {
-    check_sketch_range_step_batched(a, omega, count, y, ybs, q, qbs, p, pbs, ranks);
-    if (count == 0) return;
-    batched_sketch_range_step(c, a, abs, omega, obs, count, y, ybs, q, qbs, p, pbs, ranks);
-}
-
-// ||a_i - left_i mid_i diag(s_i) right_i||_F at each block's rank, ||a_i||_F and optionally the residual blocks, for the factors of any batched
-// compressor: the reference's rel_diff_fro(x.to_mat(), a) per block (src/lib.rs), in one launch and on the sketched ID's domain
-template <typename T>
-void lowrank_residual_batched(rc_context *c, Mat<T> a, int64_t abs, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride,
-                              Mat<T> right, int64_t rbs, const int64_t *ranks, int32_t count, Mat<T> e, int64_t ebs, T *err, T *nrm) {
-    check_lowrank_residual_batched(a, left, mid, right, count, e, ebs, err);
-    if (count == 0) return;
-    batched_lowrank_residual(c, a, abs, left, lbs, mid, mbs, s, s_stride, right, rbs, ranks, count, e, ebs, err, nrm);
-}
-
 template <typename T>
 void rank_by_tolerance(rc_context *c, Mat<T> tri, double tol, int64_t *rank) {
     RC_REQUIRE(tol < 1.0 && 0.0 <= tol, RC_INVALID_ARGUMENT, "Require 0 <= tol < 1.0");
@@ -1983,191 +1565,9 @@ rc_status rc_invert_permutation(rc_context *ctx, const int64_t *perm, int64_t n,
     }                                                                                                                                    \
     rc_status rc_column_id_rank_##SUF(rc_context *ctx, rc_matrix a, int64_t k, rc_matrix c, rc_matrix z, int64_t *col_ind) {             \
         return guarded(ctx, [&] { column_id_rank<T>(ctx, from_c<T>(a), k, from_c<T>(c), from_c<T>(z), col_ind); });                      \
-    }                                                                                                                                    \
-    rc_status rc_column_id_rank_batched_##SUF(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, \
-                                              rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind,  \
-                                              int64_t *ranks) {                                                                          \
-        return guarded(ctx, [&] {                                                                                                        \
-            column_id_rank_batched<T>(ctx, from_c<T>(a), a_batch_stride, count, k, tol, from_c<T>(c), c_batch_stride, from_c<T>(z),       \
-                                      z_batch_stride, col_ind, ranks);                                                                   \
-        });                                                                                                                              \
-    }                                                                                                                                    \
-    rc_status rc_two_sided_id_rank_batched_##SUF(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, \
-                                                 rc_matrix c, int64_t c_batch_stride, rc_matrix x, int64_t x_batch_stride, rc_matrix r,     \
-                                                 int64_t r_batch_stride, int64_t *row_ind, int64_t *col_ind, int64_t *ranks) {              \
-        return guarded(ctx, [&] {                                                                                                        \
-            two_sided_id_rank_batched<T>(ctx, from_c<T>(a), a_batch_stride, count, k, tol, from_c<T>(c), c_batch_stride, from_c<T>(x),    \
-                                         x_batch_stride, from_c<T>(r), r_batch_stride, row_ind, col_ind, ranks);                         \
-        });                                                                                                                              \
-    }                                                                                                                                    \
-    rc_status rc_svd_rank_batched_##SUF(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol,      \
-                                        rc_matrix u, int64_t u_batch_stride, T *s, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks) { \
-        return guarded(ctx, [&] {                                                                                                        \
-            svd_rank_batched<T>(ctx, from_c<T>(a), a_batch_stride, count, k, tol, from_c<T>(u), u_batch_stride, s, from_c<T>(vt),         \
-                                vt_batch_stride, ranks);                                                                                 \
-        });                                                                                                                              \
-    }                                                                                                                                    \
-    rc_status rc_lowrank_apply_batched_##SUF(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, \
-                                             const T *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, \
-                                             int32_t count, rc_matrix b, int64_t b_batch_stride, rc_matrix y, int64_t y_batch_stride) {  \
-        return guarded(ctx, [&] {                                                                                                        \
-            lowrank_apply_batched<T>(ctx, from_c<T>(left), left_batch_stride, from_c<T>(mid), mid_batch_stride, s, s_stride, from_c<T>(right), \
-                                     right_batch_stride, ranks, count, from_c<T>(b), b_batch_stride, from_c<T>(y), y_batch_stride);     \
-        });                                                                                                                              \
-    }                                                                                                                                    \
-    /* conj is ignored: conjugation is the identity on real data */                                                                      \
-    rc_status rc_block_operator_apply_##SUF(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, \
-                                            const T *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, \
-                                            int32_t count, rc_matrix dense, int64_t dense_batch_stride, int32_t dense_count,             \
-                                            const int64_t *group_ptr, const int64_t *group_row, int32_t groups, const int64_t *entry_block, \
-                                            const int64_t *entry_col, rc_matrix x, rc_matrix y, int32_t accumulate, int32_t conj) {      \
-        (void)conj;                                                                                                                      \
-        return guarded(ctx, [&] {                                                                                                        \
-            block_operator_apply_checked<T>(ctx, from_c<T>(left), left_batch_stride, from_c<T>(mid), mid_batch_stride, s, s_stride,      \
-                                            from_c<T>(right), right_batch_stride, ranks, count, from_c<T>(dense), dense_batch_stride,    \
-                                            dense_count, BlockPattern{group_ptr, group_row, entry_block, entry_col, groups}, from_c<T>(x), \
-                                            from_c<T>(y), accumulate);                                                                   \
-        });                                                                                                                              \
-    }                                                                                                                                    \
-    rc_status rc_lowrank_recompress_batched_##SUF(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid,             \
-                                                  int64_t mid_batch_stride, const T *s, int64_t s_stride, rc_matrix right,               \
-                                                  int64_t right_batch_stride, const int64_t *in_ranks, int32_t count, int64_t k, double tol, \
-                                                  rc_matrix u, int64_t u_batch_stride, T *s_out, rc_matrix vt, int64_t vt_batch_stride,  \
-                                                  int64_t *ranks) {                                                                      \
-        return guarded(ctx, [&] {                                                                                                        \
-            lowrank_recompress_batched<T>(ctx, from_c<T>(left), left_batch_stride, from_c<T>(mid), mid_batch_stride, s, s_stride,        \
-                                          from_c<T>(right), right_batch_stride, in_ranks, count, k, tol, from_c<T>(u), u_batch_stride,   \
-                                          s_out, from_c<T>(vt), vt_batch_stride, ranks);                                                 \
-        });                                                                                                                              \
-    }                                                                                                                                    \
-    rc_status rc_lowrank_recompress_tall_batched_##SUF(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid,        \
-                                                       int64_t mid_batch_stride, const T *s, int64_t s_stride, rc_matrix right,          \
-                                                       int64_t right_batch_stride, const int64_t *in_ranks, int32_t count, int64_t k,    \
-                                                       double tol, rc_matrix u, int64_t u_batch_stride, T *s_out, rc_matrix vt,          \
-                                                       int64_t vt_batch_stride, int64_t *ranks) {                                        \
-        return guarded(ctx, [&] {                                                                                                        \
-            lowrank_recompress_tall_batched<T>(ctx, from_c<T>(left), left_batch_stride, from_c<T>(mid), mid_batch_stride, s, s_stride,   \
-                                               from_c<T>(right), right_batch_stride, in_ranks, count, k, tol, from_c<T>(u),              \
-                                               u_batch_stride, s_out, from_c<T>(vt), vt_batch_stride, ranks);                            \
-        });                                                                                                                              \
-    }                                                                                                                                    \
-    rc_status rc_sketch_column_id_rank_batched_##SUF(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega,              \
-                                                     int64_t omega_batch_stride, int32_t count, int64_t k, double tol, rc_matrix y,      \
-                                                     int64_t y_batch_stride, rc_matrix c, int64_t c_batch_stride, rc_matrix z,           \
-                                                     int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks) {                         \
-        return guarded(ctx, [&] {                                                                                                        \
-            sketch_column_id_rank_batched<T>(ctx, from_c<T>(a), a_batch_stride, from_c<T>(omega), omega_batch_stride, count, k, tol,     \
-                                             from_c<T>(y), y_batch_stride, from_c<T>(c), c_batch_stride, from_c<T>(z), z_batch_stride,   \
-                                             col_ind, ranks);                                                                            \
-        });                                                                                                                              \
-    }                                                                                                                                    \
-    rc_status rc_sketch_range_step_batched_##SUF(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega,                  \
-                                                 int64_t omega_batch_stride, int32_t count, rc_matrix y, int64_t y_batch_stride, rc_matrix q, \
-                                                 int64_t q_batch_stride, rc_matrix p, int64_t p_batch_stride, int64_t *ranks) {          \
-        return guarded(ctx, [&] {                                                                                                        \
-            sketch_range_step_batched<T>(ctx, from_c<T>(a), a_batch_stride, from_c<T>(omega), omega_batch_stride, count, from_c<T>(y),   \
-                                         y_batch_stride, from_c<T>(q), q_batch_stride, from_c<T>(p), p_batch_stride, ranks);             \
-        });                                                                                                                              \
-    }                                                                                                                                    \
-    rc_status rc_lowrank_residual_batched_##SUF(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix left, int64_t left_batch_stride, \
-                                                rc_matrix mid, int64_t mid_batch_stride, const T *s, int64_t s_stride, rc_matrix right,  \
-                                                int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix e,            \
-                                                int64_t e_batch_stride, T *err, T *nrm) {                                                \
-        return guarded(ctx, [&] {                                                                                                        \
-            lowrank_residual_batched<T>(ctx, from_c<T>(a), a_batch_stride, from_c<T>(left), left_batch_stride, from_c<T>(mid),           \
-                                        mid_batch_stride, s, s_stride, from_c<T>(right), right_batch_stride, ranks, count, from_c<T>(e), \
-                                        e_batch_stride, err, nrm);                                                                       \
-        });                                                                                                                              \
     }
 
 RC_DEFINE_TYPED(f64, double)
 RC_DEFINE_TYPED(f32, float)
-
-// the tall recompression's plan as numbers: host arithmetic only, no context, no device
-rc_status rc_lowrank_recompress_tall_batched_plan(int64_t m, int64_t n, int64_t inner, int32_t elem_bytes, int64_t resident, int64_t *stages,
-                                                  int64_t *slot_bytes, int64_t *grid) {
-    if (!(m >= 1 && m <= 65536 && n >= 1 && n <= 512 && inner >= 1 && inner <= 128 && inner <= std::min(m, n)) || (elem_bytes != 4 && elem_bytes != 8) ||
-        resident < 1 || !stages || !slot_bytes || !grid)
-        return RC_INVALID_ARGUMENT;
-    try {
-        batched_lowrank_recompress_tall_plan(m, n, inner, elem_bytes == 8, resident, stages, slot_bytes, grid);
-        return RC_OK;
-    } catch (const Error &e) {
-        return e.code;
-    }
-}
-
-// the complex tall recompression's plan as numbers (real_bytes 8: c64, 4: c32): the same domain, host arithmetic only
-rc_status rc_lowrank_recompress_tall_complex_batched_plan(int64_t m, int64_t n, int64_t inner, int32_t real_bytes, int64_t resident, int64_t *stages,
-                                                          int64_t *slot_bytes, int64_t *grid) {
-    if (!(m >= 1 && m <= 65536 && n >= 1 && n <= 512 && inner >= 1 && inner <= 128 && inner <= std::min(m, n)) || (real_bytes != 4 && real_bytes != 8) ||
-        resident < 1 || !stages || !slot_bytes || !grid)
-        return RC_INVALID_ARGUMENT;
-    try {
-        batched_lowrank_recompress_tall_c_plan(m, n, inner, real_bytes == 8, resident, stages, slot_bytes, grid);
-        return RC_OK;
-    } catch (const Error &e) {
-        return e.code;
-    }
-}
-
-// f32 storage under f64 arithmetic (kernels_batched_apply.hip, kernels_block_operator.hip): the twins' checks on views of the same shapes
-rc_status rc_lowrank_apply_mixed_batched_f64(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride,
-                                             const double *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks,
-                                             int32_t count, rc_matrix b, int64_t b_batch_stride, rc_matrix y, int64_t y_batch_stride) {
-    return guarded(ctx, [&] {
-        check_lowrank_apply_batched<double>(from_c<double>(left), from_c<double>(mid), from_c<double>(right), count, from_c<double>(b), from_c<double>(y),
-                                            y_batch_stride);
-        if (count == 0) return;
-        batched_lowrank_apply_mixed(ctx, false, left, left_batch_stride, mid, mid_batch_stride, s, s_stride, right, right_batch_stride, ranks, count, b,
-                                    b_batch_stride, y, y_batch_stride);
-    });
-}
-/* conj is ignored: conjugation is the identity on real data */
-rc_status rc_block_operator_apply_mixed_f64(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride,
-                                            const double *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks,
-                                            int32_t count, rc_matrix dense, int64_t dense_batch_stride, int32_t dense_count, const int64_t *group_ptr,
-                                            const int64_t *group_row, int32_t groups, const int64_t *entry_block, const int64_t *entry_col, rc_matrix x,
-                                            rc_matrix y, int32_t accumulate, int32_t conj) {
-    (void)conj;
-    return guarded(ctx, [&] {
-        const BlockPattern pat{group_ptr, group_row, entry_block, entry_col, groups};
-        const BlockShape sh = check_block_operator_apply<double>(from_c<double>(left), from_c<double>(mid), from_c<double>(right), count, from_c<double>(dense),
-                                                                 &dense_count, pat, from_c<double>(x), from_c<double>(y));
-        if (groups == 0) return;
-        block_operator_apply_mixed(ctx, false, left, left_batch_stride, mid, mid_batch_stride, s, s_stride, right, right_batch_stride, ranks, count, dense,
-                                   dense_batch_stride, dense_count, pat, sh, x, y, accumulate != 0, false);
-    });
-}
-rc_status rc_demote_batched_f64(rc_context *ctx, rc_matrix src, int64_t src_batch_stride, int32_t count, rc_matrix dst, int64_t dst_batch_stride,
-                                int64_t *overflow) {
-    return guarded(ctx, [&] {
-        check_convert_batched("demote_batched", src, count, dst, dst_batch_stride);
-        if (count == 0) return;
-        batched_demote(ctx, false, src, src_batch_stride, count, dst, dst_batch_stride, overflow);
-    });
-}
-rc_status rc_promote_batched_f32(rc_context *ctx, rc_matrix src, int64_t src_batch_stride, int32_t count, rc_matrix dst, int64_t dst_batch_stride) {
-    return guarded(ctx, [&] {
-        check_convert_batched("promote_batched", src, count, dst, dst_batch_stride);
-        if (count == 0) return;
-        batched_promote(ctx, false, src, src_batch_stride, count, dst, dst_batch_stride);
-    });
-}
-// The _f32 names of the three stems above are the header's rule that every _f64 entry point has an _f32 one.  They would be f32 arithmetic
-// over 16-bit storage, which this library does not build: declared, exported and always refused, so that a caller finds out at the call.
-static rc_status mixed_f32_not_built(rc_context *ctx, const char *who) {
-    return guarded(ctx, [&] { fail(RC_INVALID_ARGUMENT, "%s: f32 arithmetic over 16-bit storage is not built; the mixed calls are the _f64 and _c64 ones", who); });
-}
-rc_status rc_lowrank_apply_mixed_batched_f32(rc_context *ctx, rc_matrix, int64_t, rc_matrix, int64_t, const float *, int64_t, rc_matrix, int64_t, const int64_t *,
-                                             int32_t, rc_matrix, int64_t, rc_matrix, int64_t) {
-    return mixed_f32_not_built(ctx, "lowrank_apply_mixed_batched_f32");
-}
-rc_status rc_block_operator_apply_mixed_f32(rc_context *ctx, rc_matrix, int64_t, rc_matrix, int64_t, const float *, int64_t, rc_matrix, int64_t, const int64_t *,
-                                            int32_t, rc_matrix, int64_t, int32_t, const int64_t *, const int64_t *, int32_t, const int64_t *, const int64_t *,
-                                            rc_matrix, rc_matrix, int32_t, int32_t) {
-    return mixed_f32_not_built(ctx, "block_operator_apply_mixed_f32");
-}
-rc_status rc_demote_batched_f32(rc_context *ctx, rc_matrix, int64_t, int32_t, rc_matrix, int64_t, int64_t *) { return mixed_f32_not_built(ctx, "demote_batched_f32"); }
 
 }  // extern "C"

@@ -36,9 +36,6 @@ template <> struct NumC<double> { static __host__ __device__ double tol3z() { re
 template <> struct NumC<float> { static __host__ __device__ float tol3z() { return 2.44140625e-04f; } static __host__ __device__ float eps() { return 5.9604645e-08f; } };
 
 // the column-major working matrix (cplx<R>, CV<R> and view_of: rc_cplx.hpp)
-// the shape, strides and null-ness of a complex operand as the real-typed view the shared argument checks take (never dereferenced)
-template <typename R>
-Mat<R> shape_of(const rc_matrix &m) { return Mat<R>(static_cast<R *>(m.data), m.rows, m.cols, m.row_stride, m.col_stride); }
 template <typename R>
 CV<R> tmp_cm(rc_context *c, int64_t rows, int64_t cols) {
     const int64_t ld = std::max<int64_t>(rows, 1);
@@ -946,35 +943,6 @@ void c_sample_range_adaptive(rc_context *c, const COp<R> &a, double rel_tol_d, i
     RC_HIP(hipStreamSynchronize(c->stream));
 }
 
-template <typename F>
-rc_status guarded_c(rc_context *ctx, F &&f) {
-    if (!ctx) return RC_INVALID_ARGUMENT;
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    if (prev != ctx->device) (void)hipSetDevice(ctx->device);
-    rc_status st = RC_OK;
-    // (calls nest: an operator callback may use the library on the same context -- only the outermost call resets the arena)
-    struct Scope {
-        rc_context *c; size_t off = 0; bool outer;
-        explicit Scope(rc_context *x) : c(x), outer(x->call_depth++ == 0) { if (outer) c->reset_arena(); else off = c->arena_off; }
-        ~Scope() { --c->call_depth; if (!outer) c->arena_off = off; }
-    };
-    try {
-        Scope scope(ctx);
-        f();
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) fail(RC_RUNTIME_ERROR, "kernel launch failed: %s", hipGetErrorString(e));
-    } catch (const Error &e) {
-        ctx->last_error = e.msg;
-        st = e.code;
-    } catch (const std::exception &e) {
-        ctx->last_error = e.what();
-        st = RC_RUNTIME_ERROR;
-    }
-    if (prev != ctx->device && prev >= 0) (void)hipSetDevice(prev);
-    return st;
-}
-
 template <typename R>
 void c_rank_by_tolerance(rc_context *c, CV<R> tri, double tol, int64_t *rank) {
     RC_REQUIRE(tol < 1.0 && 0.0 <= tol, RC_INVALID_ARGUMENT, "Require 0 <= tol < 1.0");
@@ -1082,22 +1050,22 @@ extern "C" {
 
 #define RC_DEFINE_COMPLEX(SUF, R, CT)                                                                                                     \
     rc_status rc_random_gaussian_##SUF(rc_context *ctx, rc_matrix out, uint64_t seed, uint64_t offset) {                                  \
-        return guarded_c(ctx, [&] { c_gaussian<R>(ctx, view_of<R>(out), seed, offset); });                                                \
+        return guarded(ctx, [&] { c_gaussian<R>(ctx, view_of<R>(out), seed, offset); });                                                  \
     }                                                                                                                                     \
     rc_status rc_matmat_##SUF(rc_context *ctx, rc_matrix a, rc_matrix x, rc_matrix y) {                                                   \
-        return guarded_c(ctx, [&] { c_gemm<R>(ctx, 0, 0, one<R>(), view_of<R>(a), view_of<R>(x), zero<R>(), view_of<R>(y)); });           \
+        return guarded(ctx, [&] { c_gemm<R>(ctx, 0, 0, one<R>(), view_of<R>(a), view_of<R>(x), zero<R>(), view_of<R>(y)); });             \
     }                                                                                                                                     \
     rc_status rc_conj_matmat_##SUF(rc_context *ctx, rc_matrix a, rc_matrix x, rc_matrix y) {                                              \
-        return guarded_c(ctx, [&] { c_gemm<R>(ctx, 2, 0, one<R>(), view_of<R>(a), view_of<R>(x), zero<R>(), view_of<R>(y)); });           \
+        return guarded(ctx, [&] { c_gemm<R>(ctx, 2, 0, one<R>(), view_of<R>(a), view_of<R>(x), zero<R>(), view_of<R>(y)); });             \
     }                                                                                                                                     \
     rc_status rc_gemm_##SUF(rc_context *ctx, int32_t trans_a, int32_t trans_b, CT alpha, rc_matrix a, rc_matrix b, CT beta, rc_matrix c) { \
-        return guarded_c(ctx, [&] {                                                                                                       \
+        return guarded(ctx, [&] {                                                                                                         \
             RC_REQUIRE(trans_a >= 0 && trans_a <= 2 && trans_b >= 0 && trans_b <= 2, RC_INVALID_ARGUMENT, "gemm: op must be 0, 1 or 2");  \
             c_gemm<R>(ctx, trans_a, trans_b, cplx<R>{alpha.re, alpha.im}, view_of<R>(a), view_of<R>(b), cplx<R>{beta.re, beta.im}, view_of<R>(c)); \
         });                                                                                                                               \
     }                                                                                                                                     \
     rc_status rc_rel_diff_fro_##SUF(rc_context *ctx, rc_matrix first, rc_matrix second, R *out) {                                         \
-        return guarded_c(ctx, [&] {                                                                                                       \
+        return guarded(ctx, [&] {                                                                                                         \
             CV<R> A = view_of<R>(first), B = view_of<R>(second);                                                                          \
             RC_REQUIRE(A.rows == B.rows && A.cols == B.cols, RC_INVALID_ARGUMENT, "rel_diff_fro: shape mismatch");                        \
             R *d = ctx->alloc<R>(2);                                                                                                      \
@@ -1108,30 +1076,30 @@ extern "C" {
         });                                                                                                                               \
     }                                                                                                                                     \
     rc_status rc_apply_permutation_matrix_##SUF(rc_context *ctx, int32_t mode, rc_matrix in, const int64_t *perm, int64_t plen, rc_matrix out) { \
-        return guarded_c(ctx, [&] { c_apply_perm<R>(ctx, mode, view_of<R>(in), perm, plen, view_of<R>(out)); });                          \
+        return guarded(ctx, [&] { c_apply_perm<R>(ctx, mode, view_of<R>(in), perm, plen, view_of<R>(out)); });                            \
     }                                                                                                                                     \
     rc_status rc_apply_permutation_vector_##SUF(rc_context *ctx, int32_t mode, rc_matrix in, const int64_t *perm, int64_t plen, rc_matrix out) { \
-        return guarded_c(ctx, [&] {                                                                                                       \
+        return guarded(ctx, [&] {                                                                                                         \
             RC_REQUIRE(mode == RC_VPERM_INV || mode == RC_VPERM_NOINV, RC_INVALID_ARGUMENT, "unknown vector permutation mode");           \
             RC_REQUIRE(in.cols == 1 && out.cols == 1 && plen == in.rows, RC_INVALID_ARGUMENT, "The input vector and the index array must have the same length"); \
             c_apply_perm<R>(ctx, mode == RC_VPERM_INV ? RC_PERM_ROWINV : RC_PERM_ROW, view_of<R>(in), perm, plen, view_of<R>(out));       \
         });                                                                                                                               \
     }                                                                                                                                     \
     rc_status rc_pivoted_qr_##SUF(rc_context *ctx, rc_matrix a, rc_matrix q, rc_matrix r, int64_t *ind) {                                 \
-        return guarded_c(ctx, [&] {                                                                                                       \
+        return guarded(ctx, [&] {                                                                                                         \
             CV<R> A = view_of<R>(a), Q = view_of<R>(q), Rr = view_of<R>(r);                                                               \
             RC_REQUIRE(Q.rows == A.rows && Rr.cols == A.cols && Rr.rows == Q.cols, RC_INVALID_ARGUMENT, "pivoted_qr: output shapes");     \
             c_pivoted_qr<R>(ctx, A, Q, Rr, ind, Q.cols);                                                                                  \
         });                                                                                                                               \
     }                                                                                                                                     \
     rc_status rc_geqp3_##SUF(rc_context *ctx, rc_matrix a, int64_t kmax, int64_t *jpvt, CT *tau) {                                        \
-        return guarded_c(ctx, [&] { c_lapack_geqp3<R>(ctx, view_of<R>(a), kmax, jpvt, reinterpret_cast<cplx<R> *>(tau)); });             \
+        return guarded(ctx, [&] { c_lapack_geqp3<R>(ctx, view_of<R>(a), kmax, jpvt, reinterpret_cast<cplx<R> *>(tau)); });               \
     }                                                                                                                                     \
     rc_status rc_orgqr_##SUF(rc_context *ctx, rc_matrix a, const CT *tau, int64_t k, rc_matrix q) {                                       \
-        return guarded_c(ctx, [&] { c_lapack_ungqr<R>(ctx, view_of<R>(a), reinterpret_cast<const cplx<R> *>(tau), k, view_of<R>(q)); }); \
+        return guarded(ctx, [&] { c_lapack_ungqr<R>(ctx, view_of<R>(a), reinterpret_cast<const cplx<R> *>(tau), k, view_of<R>(q)); });   \
     }                                                                                                                                     \
     rc_status rc_trsm_upper_##SUF(rc_context *ctx, rc_matrix t, rc_matrix b) {                                                            \
-        return guarded_c(ctx, [&] {                                                                                                       \
+        return guarded(ctx, [&] {                                                                                                         \
             CV<R> tt = view_of<R>(t), bb = view_of<R>(b);                                                                                 \
             RC_REQUIRE(tt.rows == tt.cols && tt.rows == bb.rows, RC_INVALID_ARGUMENT, "trsm_upper: t must be k x k, b k x nrhs");        \
             if (bb.empty()) return;                                                                                                       \
@@ -1139,20 +1107,20 @@ extern "C" {
         });                                                                                                                               \
     }                                                                                                                                     \
     rc_status rc_pivoted_lq_##SUF(rc_context *ctx, rc_matrix a, rc_matrix l, rc_matrix q, int64_t *ind) {                                 \
-        return guarded_c(ctx, [&] {                                                                                                       \
+        return guarded(ctx, [&] {                                                                                                         \
             CV<R> A = view_of<R>(a), L = view_of<R>(l), Q = view_of<R>(q);                                                                \
             RC_REQUIRE(L.rows == A.rows && Q.cols == A.cols && Q.rows == L.cols, RC_INVALID_ARGUMENT, "pivoted_lq: output shapes");       \
             c_pivoted_lq<R>(ctx, A, L, Q, ind, L.cols);                                                                                   \
         });                                                                                                                               \
     }                                                                                                                                     \
     rc_status rc_compute_svd_##SUF(rc_context *ctx, rc_matrix a, rc_matrix u, R *s, rc_matrix vt) {                                       \
-        return guarded_c(ctx, [&] { c_compute_svd<R>(ctx, view_of<R>(a), view_of<R>(u), s, view_of<R>(vt)); });                           \
+        return guarded(ctx, [&] { c_compute_svd<R>(ctx, view_of<R>(a), view_of<R>(u), s, view_of<R>(vt)); });                             \
     }                                                                                                                                     \
     rc_status rc_rank_by_tolerance_##SUF(rc_context *ctx, rc_matrix tri, double tol, int64_t *rank) {                                     \
-        return guarded_c(ctx, [&] { c_rank_by_tolerance<R>(ctx, view_of<R>(tri), tol, rank); });                                          \
+        return guarded(ctx, [&] { c_rank_by_tolerance<R>(ctx, view_of<R>(tri), tol, rank); });                                            \
     }                                                                                                                                     \
     rc_status rc_qr_to_mat_##SUF(rc_context *ctx, rc_matrix q, rc_matrix r, const int64_t *ind, rc_matrix out) {                          \
-        return guarded_c(ctx, [&] {                                                                                                       \
+        return guarded(ctx, [&] {                                                                                                         \
             CV<R> Rr = view_of<R>(r);                                                                                                     \
             CV<R> rp = tmp_cm<R>(ctx, Rr.rows, Rr.cols);                                                                                  \
             c_colinv<R>(ctx, Rr, ind, rp);                                                                                                \
@@ -1160,7 +1128,7 @@ extern "C" {
         });                                                                                                                               \
     }                                                                                                                                     \
     rc_status rc_lq_to_mat_##SUF(rc_context *ctx, rc_matrix l, rc_matrix q, const int64_t *ind, rc_matrix out) {                          \
-        return guarded_c(ctx, [&] {                                                                                                       \
+        return guarded(ctx, [&] {                                                                                                         \
             CV<R> L = view_of<R>(l);                                                                                                      \
             CV<R> lp = tmp_cm<R>(ctx, L.rows, L.cols);                                                                                    \
             c_colinv<R>(ctx, L.t(), ind, lp.t());                                                                                         \
@@ -1168,13 +1136,13 @@ extern "C" {
         });                                                                                                                               \
     }                                                                                                                                     \
     rc_status rc_qr_column_id_##SUF(rc_context *ctx, rc_matrix q, rc_matrix r, const int64_t *ind, rc_matrix c, rc_matrix z) {            \
-        return guarded_c(ctx, [&] { c_qr_column_id<R>(ctx, view_of<R>(q), view_of<R>(r), ind, view_of<R>(c), view_of<R>(z)); });          \
+        return guarded(ctx, [&] { c_qr_column_id<R>(ctx, view_of<R>(q), view_of<R>(r), ind, view_of<R>(c), view_of<R>(z)); });            \
     }                                                                                                                                     \
     rc_status rc_lq_row_id_##SUF(rc_context *ctx, rc_matrix l, rc_matrix q, const int64_t *ind, rc_matrix x, rc_matrix rr) {              \
-        return guarded_c(ctx, [&] { c_lq_row_id<R>(ctx, view_of<R>(l), view_of<R>(q), ind, view_of<R>(x), view_of<R>(rr)); });            \
+        return guarded(ctx, [&] { c_lq_row_id<R>(ctx, view_of<R>(l), view_of<R>(q), ind, view_of<R>(x), view_of<R>(rr)); });              \
     }                                                                                                                                     \
     rc_status rc_qr_from_range_estimate_##SUF(rc_context *ctx, rc_matrix range, rc_matrix a, rc_matrix q, rc_matrix r, int64_t *ind) {    \
-        return guarded_c(ctx, [&] {                                                                                                       \
+        return guarded(ctx, [&] {                                                                                                         \
             CV<R> Rg = view_of<R>(range), A = view_of<R>(a), Q = view_of<R>(q), Rr = view_of<R>(r);                                       \
             const int64_t rr = Rg.cols, n = A.cols, k = std::min(rr, n);                                                                  \
             RC_REQUIRE(Rg.rows == A.rows && Q.rows == A.rows && Q.cols == k && Rr.rows == k && Rr.cols == n, RC_INVALID_ARGUMENT, "qr_from_range_estimate: shape mismatch"); \
@@ -1185,7 +1153,7 @@ extern "C" {
         });                                                                                                                               \
     }                                                                                                                                     \
     rc_status rc_svd_to_mat_##SUF(rc_context *ctx, rc_matrix u, const R *s, rc_matrix vt, rc_matrix out) {                                \
-        return guarded_c(ctx, [&] {                                                                                                       \
+        return guarded(ctx, [&] {                                                                                                         \
             CV<R> VT = view_of<R>(vt);                                                                                                    \
             CV<R> sv = tmp_cm<R>(ctx, VT.rows, VT.cols);                                                                                  \
             c_copy<R>(ctx, VT, sv);                                                                                                       \
@@ -1194,7 +1162,7 @@ extern "C" {
         });                                                                                                                               \
     }                                                                                                                                     \
     rc_status rc_svd_to_qr_##SUF(rc_context *ctx, rc_matrix u, const R *s, rc_matrix vt, rc_matrix q, rc_matrix r, int64_t *ind) {        \
-        return guarded_c(ctx, [&] {                                                                                                       \
+        return guarded(ctx, [&] {                                                                                                         \
             CV<R> VT = view_of<R>(vt), Q = view_of<R>(q);                                                                                 \
             const int64_t k = Q.cols;                                                                                                     \
             RC_REQUIRE(k <= std::min(VT.rows, VT.cols), RC_INVALID_ARGUMENT, "svd_to_qr: rank exceeds min(r, n)");                        \
@@ -1206,7 +1174,7 @@ extern "C" {
         });                                                                                                                               \
     }                                                                                                                                     \
     rc_status rc_svd_from_range_estimate_##SUF(rc_context *ctx, rc_matrix range, rc_matrix a, rc_matrix u, R *s, rc_matrix vt) {          \
-        return guarded_c(ctx, [&] {                                                                                                       \
+        return guarded(ctx, [&] {                                                                                                         \
             CV<R> Rg = view_of<R>(range), A = view_of<R>(a), U = view_of<R>(u), VT = view_of<R>(vt);                                      \
             const int64_t rr = Rg.cols, n = A.cols, r = std::min(rr, n);                                                                  \
             RC_REQUIRE(Rg.rows == A.rows && U.rows == A.rows && U.cols == r && VT.rows == r && VT.cols == n, RC_INVALID_ARGUMENT, "svd_from_range_estimate: shape mismatch"); \
@@ -1217,7 +1185,7 @@ extern "C" {
         });                                                                                                                               \
     }                                                                                                                                     \
     rc_status rc_column_id_two_sided_##SUF(rc_context *ctx, rc_matrix c, rc_matrix c_out, rc_matrix x, int64_t *row_ind) {                \
-        return guarded_c(ctx, [&] {                                                                                                       \
+        return guarded(ctx, [&] {                                                                                                         \
             CV<R> C = view_of<R>(c);                                                                                                      \
             const int64_t m = C.rows, k = C.cols, kk = std::min(m, k);                                                                    \
             CV<R> l = tmp_cm<R>(ctx, m, kk), ql = tmp_cm<R>(ctx, kk, k);                                                                  \
@@ -1226,7 +1194,7 @@ extern "C" {
         });                                                                                                                               \
     }                                                                                                                                     \
     rc_status rc_row_id_two_sided_##SUF(rc_context *ctx, rc_matrix r, rc_matrix x, rc_matrix r_out, int64_t *col_ind) {                   \
-        return guarded_c(ctx, [&] {                                                                                                       \
+        return guarded(ctx, [&] {                                                                                                         \
             CV<R> Rr = view_of<R>(r);                                                                                                     \
             const int64_t k = Rr.rows, n = Rr.cols, kk = std::min(k, n);                                                                  \
             CV<R> q = tmp_cm<R>(ctx, k, kk), rr = tmp_cm<R>(ctx, kk, n);                                                                  \
@@ -1235,39 +1203,39 @@ extern "C" {
         });                                                                                                                               \
     }                                                                                                                                     \
     rc_status rc_max_col_norm_##SUF(rc_context *ctx, rc_matrix y, R *out) {                                                               \
-        return guarded_c(ctx, [&] {                                                                                                       \
+        return guarded(ctx, [&] {                                                                                                         \
             R *d = ctx->alloc<R>(1);                                                                                                      \
             c_max_col_norm_dev<R>(ctx, view_of<R>(y), d);                                                                                 \
             read_back_r<R>(ctx, d, out, 1);                                                                                               \
         });                                                                                                                               \
     }                                                                                                                                     \
     rc_status rc_sample_range_by_rank_##SUF(rc_context *ctx, rc_matrix a, int64_t k, int64_t p, rc_matrix omega, uint64_t seed, rc_matrix q) { \
-        return guarded_c(ctx, [&] { c_sample_range_by_rank<R>(ctx, COp<R>::of(view_of<R>(a)), k, p, view_of<R>(omega), seed, view_of<R>(q)); }); \
+        return guarded(ctx, [&] { c_sample_range_by_rank<R>(ctx, COp<R>::of(view_of<R>(a)), k, p, view_of<R>(omega), seed, view_of<R>(q)); });   \
     }                                                                                                                                     \
     rc_status rc_sample_range_power_iteration_##SUF(rc_context *ctx, rc_matrix a, int64_t k, int64_t p, int64_t it, rc_matrix omega, uint64_t seed, rc_matrix q) { \
-        return guarded_c(ctx, [&] { c_sample_range_power<R>(ctx, COp<R>::of(view_of<R>(a)), k, p, it, view_of<R>(omega), seed, view_of<R>(q)); }); \
+        return guarded(ctx, [&] { c_sample_range_power<R>(ctx, COp<R>::of(view_of<R>(a)), k, p, it, view_of<R>(omega), seed, view_of<R>(q)); });   \
     }                                                                                                                                     \
     rc_status rc_sample_range_adaptive_##SUF(rc_context *ctx, rc_matrix a, double rel_tol, int64_t s, rc_matrix omegas, uint64_t seed, rc_matrix q_cap, \
                                              int64_t *rank, int64_t *hist_rank, double *hist_res, int64_t hist_cap, int64_t *hist_len) {  \
-        return guarded_c(ctx, [&] {                                                                                                       \
+        return guarded(ctx, [&] {                                                                                                         \
             c_sample_range_adaptive<R>(ctx, COp<R>::of(view_of<R>(a)), rel_tol, s, view_of<R>(omegas), seed, view_of<R>(q_cap), rank, hist_rank, hist_res, hist_cap, hist_len); \
         });                                                                                                                               \
     }                                                                                                                                     \
     /* the range finders and compute_from_range_estimate over the host's operator callbacks (rc_operator) */                              \
     rc_status rc_sample_range_by_rank_op_##SUF(rc_context *ctx, const rc_operator *op, int64_t k, int64_t p, rc_matrix omega, uint64_t seed, rc_matrix q) { \
-        return guarded_c(ctx, [&] { c_sample_range_by_rank<R>(ctx, COp<R>::of(op), k, p, view_of<R>(omega), seed, view_of<R>(q)); });     \
+        return guarded(ctx, [&] { c_sample_range_by_rank<R>(ctx, COp<R>::of(op), k, p, view_of<R>(omega), seed, view_of<R>(q)); });       \
     }                                                                                                                                     \
     rc_status rc_sample_range_power_iteration_op_##SUF(rc_context *ctx, const rc_operator *op, int64_t k, int64_t p, int64_t it, rc_matrix omega, uint64_t seed, rc_matrix q) { \
-        return guarded_c(ctx, [&] { c_sample_range_power<R>(ctx, COp<R>::of(op), k, p, it, view_of<R>(omega), seed, view_of<R>(q)); });   \
+        return guarded(ctx, [&] { c_sample_range_power<R>(ctx, COp<R>::of(op), k, p, it, view_of<R>(omega), seed, view_of<R>(q)); });     \
     }                                                                                                                                     \
     rc_status rc_sample_range_adaptive_op_##SUF(rc_context *ctx, const rc_operator *op, double rel_tol, int64_t s, rc_matrix omegas, uint64_t seed, rc_matrix q_cap, \
                                                 int64_t *rank, int64_t *hist_rank, double *hist_res, int64_t hist_cap, int64_t *hist_len) { \
-        return guarded_c(ctx, [&] {                                                                                                       \
+        return guarded(ctx, [&] {                                                                                                         \
             c_sample_range_adaptive<R>(ctx, COp<R>::of(op), rel_tol, s, view_of<R>(omegas), seed, view_of<R>(q_cap), rank, hist_rank, hist_res, hist_cap, hist_len); \
         });                                                                                                                               \
     }                                                                                                                                     \
     rc_status rc_qr_from_range_estimate_op_##SUF(rc_context *ctx, rc_matrix range, const rc_operator *op, rc_matrix q, rc_matrix r, int64_t *ind) { \
-        return guarded_c(ctx, [&] {                                                                                                       \
+        return guarded(ctx, [&] {                                                                                                         \
             const COp<R> A = COp<R>::of(op);                                                                                              \
             CV<R> Rg = view_of<R>(range), Q = view_of<R>(q), Rr = view_of<R>(r);                                                          \
             const int64_t rr = Rg.cols, n = A.cols, k = std::min(rr, n);                                                                  \
@@ -1279,7 +1247,7 @@ extern "C" {
         });                                                                                                                               \
     }                                                                                                                                     \
     rc_status rc_svd_from_range_estimate_op_##SUF(rc_context *ctx, rc_matrix range, const rc_operator *op, rc_matrix u, R *s, rc_matrix vt) { \
-        return guarded_c(ctx, [&] {                                                                                                       \
+        return guarded(ctx, [&] {                                                                                                         \
             const COp<R> A = COp<R>::of(op);                                                                                              \
             CV<R> Rg = view_of<R>(range), U = view_of<R>(u), VT = view_of<R>(vt);                                                         \
             const int64_t rr = Rg.cols, n = A.cols, r = std::min(rr, n);                                                                  \
@@ -1291,7 +1259,7 @@ extern "C" {
         });                                                                                                                               \
     }                                                                                                                                     \
     rc_status rc_column_id_rank_##SUF(rc_context *ctx, rc_matrix a, int64_t k, rc_matrix c, rc_matrix z, int64_t *col_ind) {              \
-        return guarded_c(ctx, [&] {                                                                                                       \
+        return guarded(ctx, [&] {                                                                                                         \
             CV<R> A = view_of<R>(a);                                                                                                      \
             const int64_t kk = std::min(k, std::min(A.rows, A.cols));                                                                     \
             CV<R> q = tmp_cm<R>(ctx, A.rows, kk), r = tmp_cm<R>(ctx, kk, A.cols);                                                         \
@@ -1306,191 +1274,15 @@ extern "C" {
     /* the fused rSVD + ID call (same members, same "null = skipped" rule as rc_rsvd_id_f64); B = Q^H A is formed once */                \
     rc_status rc_rsvd_id_##SUF(rc_context *ctx, rc_matrix a, int64_t k, int64_t p, rc_matrix omega, uint64_t seed, const rc_rsvd_id_out *out) { \
         if (!out) return RC_INVALID_ARGUMENT;                                                                                             \
-        return guarded_c(ctx, [&] { c_rsvd_id<R>(ctx, view_of<R>(a), k, p, view_of<R>(omega), seed, *out); });                            \
+        return guarded(ctx, [&] { c_rsvd_id<R>(ctx, view_of<R>(a), k, p, view_of<R>(omega), seed, *out); });                              \
     }                                                                                                                                     \
     /* cfg5's batch for complex matrices: the same packed layout, one rank-k column ID per matrix, round-robin over the contexts */      \
     rc_status rc_batch_column_id_##SUF(rc_context *const *ctxs, int32_t nctx, const rc_matrix *mats, int32_t count, int64_t k, void *packed) { \
         if (!ctxs || nctx < 1 || !ctxs[0]) return RC_INVALID_ARGUMENT;                                                                    \
-        return guarded_c(ctxs[0], [&] { c_batch_column_id<R>(ctxs, nctx, mats, count, k, packed); });                                     \
-    }                                                                                                                                     \
-    /* many small complex matrices in one launch (kernels_batched_id_c.hip); the checks of the real entry points on views of the */      \
-    /* same shapes and strides (in complex elements) */                                                                                   \
-    rc_status rc_column_id_rank_batched_##SUF(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, \
-                                              rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind,  \
-                                              int64_t *ranks) {                                                                           \
-        return guarded_c(ctx, [&] {                                                                                                       \
-            k = check_column_id_rank_batched<R>(shape_of<R>(a), count, k, tol, shape_of<R>(c), c_batch_stride, shape_of<R>(z), z_batch_stride, \
-                                                col_ind, ranks);                                                                          \
-            if (count == 0) return;                                                                                                       \
-            batched_column_id_c<R>(ctx, a, a_batch_stride, count, k, tol, c, c_batch_stride, z, z_batch_stride, col_ind, ranks);          \
-        });                                                                                                                               \
-    }                                                                                                                                     \
-    rc_status rc_two_sided_id_rank_batched_##SUF(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, \
-                                                 rc_matrix c, int64_t c_batch_stride, rc_matrix x, int64_t x_batch_stride, rc_matrix r,     \
-                                                 int64_t r_batch_stride, int64_t *row_ind, int64_t *col_ind, int64_t *ranks) {              \
-        return guarded_c(ctx, [&] {                                                                                                       \
-            k = check_two_sided_id_rank_batched<R>(shape_of<R>(a), count, k, tol, shape_of<R>(c), c_batch_stride, shape_of<R>(x),         \
-                                                   x_batch_stride, shape_of<R>(r), r_batch_stride, row_ind, col_ind, ranks);              \
-            if (count == 0) return;                                                                                                       \
-            batched_two_sided_id_c<R>(ctx, a, a_batch_stride, count, k, tol, c, c_batch_stride, x, x_batch_stride, r, r_batch_stride,     \
-                                      row_ind, col_ind, ranks);                                                                           \
-        });                                                                                                                               \
-    }                                                                                                                                     \
-    /* singular values in the real type; u (m x k), vt = V^H (k x n) */                                                                   \
-    rc_status rc_svd_rank_batched_##SUF(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol,       \
-                                        rc_matrix u, int64_t u_batch_stride, R *s, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks) { \
-        return guarded_c(ctx, [&] {                                                                                                       \
-            k = check_svd_rank_batched<R>(shape_of<R>(a), count, k, tol, shape_of<R>(u), u_batch_stride, s, shape_of<R>(vt), vt_batch_stride, \
-                                          ranks);                                                                                         \
-            if (count == 0) return;                                                                                                       \
-            batched_svd_c<R>(ctx, a, a_batch_stride, count, k, tol, u, u_batch_stride, s, vt, vt_batch_stride, ranks);                    \
-        });                                                                                                                               \
-    }                                                                                                                                     \
-    /* apply / rebuild the factors of a batch (kernels_batched_apply.hip): the real entry point's checks on views of the same shapes */   \
-    rc_status rc_lowrank_apply_batched_##SUF(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, \
-                                             const R *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, \
-                                             int32_t count, rc_matrix b, int64_t b_batch_stride, rc_matrix y, int64_t y_batch_stride) {   \
-        return guarded_c(ctx, [&] {                                                                                                       \
-            check_lowrank_apply_batched<R>(shape_of<R>(left), shape_of<R>(mid), shape_of<R>(right), count, shape_of<R>(b), shape_of<R>(y), \
-                                           y_batch_stride);                                                                               \
-            if (count == 0) return;                                                                                                       \
-            batched_lowrank_apply_c<R>(ctx, left, left_batch_stride, mid, mid_batch_stride, s, s_stride, right, right_batch_stride, ranks, \
-                                       count, b, b_batch_stride, y, y_batch_stride);                                                      \
-        });                                                                                                                               \
-    }                                                                                                                                     \
-    /* the block-sparse operator of such a batch (kernels_block_operator.hip): the real entry point's checks on views of the same shapes */ \
-    rc_status rc_block_operator_apply_##SUF(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, \
-                                            const R *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks, \
-                                            int32_t count, rc_matrix dense, int64_t dense_batch_stride, int32_t dense_count,              \
-                                            const int64_t *group_ptr, const int64_t *group_row, int32_t groups, const int64_t *entry_block, \
-                                            const int64_t *entry_col, rc_matrix x, rc_matrix y, int32_t accumulate, int32_t conj) {       \
-        return guarded_c(ctx, [&] {                                                                                                       \
-            const BlockPattern pat{group_ptr, group_row, entry_block, entry_col, groups};                                                 \
-            const BlockShape sh = check_block_operator_apply<R>(shape_of<R>(left), shape_of<R>(mid), shape_of<R>(right), count, shape_of<R>(dense), \
-                                                                &dense_count, pat, shape_of<R>(x), shape_of<R>(y));                       \
-            if (groups == 0) return;                                                                                                      \
-            block_operator_apply_c<R>(ctx, left, left_batch_stride, mid, mid_batch_stride, s, s_stride, right, right_batch_stride, ranks, \
-                                      count, dense, dense_batch_stride, dense_count, pat, sh, x, y, accumulate != 0, conj != 0);          \
-        });                                                                                                                               \
-    }                                                                                                                                     \
-    /* residual norms of the factors of a batch against their blocks (kernels_batched_residual_c.hip): the real entry point's checks on */ \
-    /* views of the same shapes; s, err and nrm in the real type */                                                                       \
-    rc_status rc_lowrank_residual_batched_##SUF(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix left, int64_t left_batch_stride, \
-                                                rc_matrix mid, int64_t mid_batch_stride, const R *s, int64_t s_stride, rc_matrix right,   \
-                                                int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix e,             \
-                                                int64_t e_batch_stride, R *err, R *nrm) {                                                 \
-        return guarded_c(ctx, [&] {                                                                                                       \
-            check_lowrank_residual_batched<R>(shape_of<R>(a), shape_of<R>(left), shape_of<R>(mid), shape_of<R>(right), count, shape_of<R>(e), \
-                                              e_batch_stride, err);                                                                       \
-            if (count == 0) return;                                                                                                       \
-            batched_lowrank_residual_c<R>(ctx, a, a_batch_stride, left, left_batch_stride, mid, mid_batch_stride, s, s_stride, right,     \
-                                          right_batch_stride, ranks, count, e, e_batch_stride, err, nrm);                                 \
-        });                                                                                                                               \
-    }                                                                                                                                     \
-    /* recompress the complex factors of a batch to truncated SVDs (kernels_batched_id_c.hip): the real entry point's checks on views */  \
-    /* of the same shapes; s, s_out and tol in the real type, vt = V^H */                                                                 \
-    rc_status rc_lowrank_recompress_complex_batched_##SUF(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid,      \
-                                                          int64_t mid_batch_stride, const R *s, int64_t s_stride, rc_matrix right,        \
-                                                          int64_t right_batch_stride, const int64_t *in_ranks, int32_t count, int64_t k,  \
-                                                          R tol, rc_matrix u, int64_t u_batch_stride, R *s_out, rc_matrix vt,             \
-                                                          int64_t vt_batch_stride, int64_t *ranks) {                                      \
-        return guarded_c(ctx, [&] {                                                                                                       \
-            check_lowrank_recompress_batched<R>(shape_of<R>(left), shape_of<R>(mid), shape_of<R>(right), count, k, (double)tol,           \
-                                                shape_of<R>(u), u_batch_stride, s_out, shape_of<R>(vt), vt_batch_stride, ranks);          \
-            if (count == 0) return;                                                                                                       \
-            batched_lowrank_recompress_c<R>(ctx, left, left_batch_stride, mid, mid_batch_stride, s, s_stride, right, right_batch_stride,  \
-                                            in_ranks, count, k, (double)tol, u, u_batch_stride, s_out, vt, vt_batch_stride, ranks);       \
-        });                                                                                                                               \
-    }                                                                                                                                     \
-    /* the same for tall left factors (m <= 65536; k_batched_recompress_c<R, true>), the checks under the call's own name */             \
-    rc_status rc_lowrank_recompress_tall_complex_batched_##SUF(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, \
-                                                               int64_t mid_batch_stride, const R *s, int64_t s_stride, rc_matrix right,   \
-                                                               int64_t right_batch_stride, const int64_t *in_ranks, int32_t count,        \
-                                                               int64_t k, R tol, rc_matrix u, int64_t u_batch_stride, R *s_out,           \
-                                                               rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks) {                   \
-        return guarded_c(ctx, [&] {                                                                                                       \
-            check_lowrank_recompress_batched<R>(shape_of<R>(left), shape_of<R>(mid), shape_of<R>(right), count, k, (double)tol,           \
-                                                shape_of<R>(u), u_batch_stride, s_out, shape_of<R>(vt), vt_batch_stride, ranks,           \
-                                                RC_TALL_COMPLEX);                                                                         \
-            if (count == 0) return;                                                                                                       \
-            batched_lowrank_recompress_tall_c<R>(ctx, left, left_batch_stride, mid, mid_batch_stride, s, s_stride, right,                 \
-                                                 right_batch_stride, in_ranks, count, k, (double)tol, u, u_batch_stride, s_out, vt,       \
-                                                 vt_batch_stride, ranks);                                                                 \
-        });                                                                                                                               \
-    }                                                                                                                                     \
-    /* the sketched column ID of complex tall blocks (kernels_batched_id_c.hip): the real entry point's checks on views of the same */   \
-    /* shapes; y = omega a with nothing conjugated */                                                                                     \
-    rc_status rc_sketch_column_id_rank_complex_batched_##SUF(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega,       \
-                                                             int64_t omega_batch_stride, int32_t count, int64_t k, double tol, rc_matrix y, \
-                                                             int64_t y_batch_stride, rc_matrix c, int64_t c_batch_stride, rc_matrix z,    \
-                                                             int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks) {                  \
-        return guarded_c(ctx, [&] {                                                                                                       \
-            const int64_t kk = check_sketch_column_id_rank_batched<R>(shape_of<R>(a), shape_of<R>(omega), count, k, tol, shape_of<R>(y),  \
-                                                                      y_batch_stride, shape_of<R>(c), c_batch_stride, shape_of<R>(z),     \
-                                                                      z_batch_stride, col_ind, ranks);                                    \
-            if (count == 0) return;                                                                                                       \
-            batched_sketch_column_id_c<R>(ctx, a, a_batch_stride, omega, omega_batch_stride, count, kk, tol, y, y_batch_stride, c,        \
-                                          c_batch_stride, z, z_batch_stride, col_ind, ranks);                                             \
-        });                                                                                                                               \
-    }                                                                                                                                     \
-    /* one range step of a power iteration on complex tall blocks (kernels_batched_id_c.hip): the real entry point's checks on views of */ \
-    /* the same shapes under the call's own name; y = omega a, q q^H = I, p = a q^H or, with p_conj, its conjugate */                     \
-    rc_status rc_sketch_range_step_complex_batched_##SUF(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega,           \
-                                                         int64_t omega_batch_stride, int32_t count, rc_matrix y, int64_t y_batch_stride,  \
-                                                         rc_matrix q, int64_t q_batch_stride, rc_matrix p, int64_t p_batch_stride,        \
-                                                         int64_t *ranks, int32_t p_conj) {                                                \
-        return guarded_c(ctx, [&] {                                                                                                       \
-            check_sketch_range_step_batched<R>(shape_of<R>(a), shape_of<R>(omega), count, shape_of<R>(y), y_batch_stride, shape_of<R>(q), \
-                                               q_batch_stride, shape_of<R>(p), p_batch_stride, ranks, true);                              \
-            if (count == 0) return;                                                                                                       \
-            batched_sketch_range_step_c<R>(ctx, a, a_batch_stride, omega, omega_batch_stride, count, y, y_batch_stride, q,                \
-                                           q_batch_stride, p, p_batch_stride, ranks, p_conj != 0);                                        \
-        });                                                                                                                               \
+        return guarded(ctxs[0], [&] { c_batch_column_id<R>(ctxs, nctx, mats, count, k, packed); });                                       \
     }
 
 RC_DEFINE_COMPLEX(c64, double, rc_complex64)
 RC_DEFINE_COMPLEX(c32, float, rc_complex32)
-
-// c32 storage under c64 arithmetic (kernels_batched_apply.hip, kernels_block_operator.hip): the twins' checks on views of the same shapes
-rc_status rc_lowrank_apply_mixed_batched_c64(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride,
-                                             const double *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks,
-                                             int32_t count, rc_matrix b, int64_t b_batch_stride, rc_matrix y, int64_t y_batch_stride) {
-    return guarded_c(ctx, [&] {
-        check_lowrank_apply_batched<double>(shape_of<double>(left), shape_of<double>(mid), shape_of<double>(right), count, shape_of<double>(b),
-                                            shape_of<double>(y), y_batch_stride);
-        if (count == 0) return;
-        batched_lowrank_apply_mixed(ctx, true, left, left_batch_stride, mid, mid_batch_stride, s, s_stride, right, right_batch_stride, ranks, count, b,
-                                    b_batch_stride, y, y_batch_stride);
-    });
-}
-rc_status rc_block_operator_apply_mixed_c64(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride,
-                                            const double *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *ranks,
-                                            int32_t count, rc_matrix dense, int64_t dense_batch_stride, int32_t dense_count, const int64_t *group_ptr,
-                                            const int64_t *group_row, int32_t groups, const int64_t *entry_block, const int64_t *entry_col, rc_matrix x,
-                                            rc_matrix y, int32_t accumulate, int32_t conj) {
-    return guarded_c(ctx, [&] {
-        const BlockPattern pat{group_ptr, group_row, entry_block, entry_col, groups};
-        const BlockShape sh = check_block_operator_apply<double>(shape_of<double>(left), shape_of<double>(mid), shape_of<double>(right), count,
-                                                                 shape_of<double>(dense), &dense_count, pat, shape_of<double>(x), shape_of<double>(y));
-        if (groups == 0) return;
-        block_operator_apply_mixed(ctx, true, left, left_batch_stride, mid, mid_batch_stride, s, s_stride, right, right_batch_stride, ranks, count, dense,
-                                   dense_batch_stride, dense_count, pat, sh, x, y, accumulate != 0, conj != 0);
-    });
-}
-rc_status rc_demote_batched_c64(rc_context *ctx, rc_matrix src, int64_t src_batch_stride, int32_t count, rc_matrix dst, int64_t dst_batch_stride,
-                                int64_t *overflow) {
-    return guarded_c(ctx, [&] {
-        check_convert_batched("demote_batched", src, count, dst, dst_batch_stride);
-        if (count == 0) return;
-        batched_demote(ctx, true, src, src_batch_stride, count, dst, dst_batch_stride, overflow);
-    });
-}
-rc_status rc_promote_batched_c32(rc_context *ctx, rc_matrix src, int64_t src_batch_stride, int32_t count, rc_matrix dst, int64_t dst_batch_stride) {
-    return guarded_c(ctx, [&] {
-        check_convert_batched("promote_batched", src, count, dst, dst_batch_stride);
-        if (count == 0) return;
-        batched_promote(ctx, true, src, src_batch_stride, count, dst, dst_batch_stride);
-    });
-}
 
 }  // extern "C"
