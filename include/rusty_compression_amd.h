@@ -641,6 +641,35 @@ rc_status rc_lowrank_recompress_tall_batched_f32(rc_context *ctx, rc_matrix left
  * elements of elem_bytes (8: f64, 4: f32), *stages = the stages of a block of full inner rank, *slot_bytes = one workgroup's workspace slot,
  * *grid = what the 2 GiB bound leaves of `resident` workgroups.  RC_INVALID_ARGUMENT outside the call's domain or for a null output. */
 rc_status rc_lowrank_recompress_tall_batched_plan(int64_t m, int64_t n, int64_t inner, int32_t elem_bytes, int64_t resident, int64_t *stages, int64_t *slot_bytes, int64_t *grid);
+/* The same recompression for factor pairs with both factors tall (the large square blocks at the upper levels of a hierarchical matrix, the
+ * pair (P, Q) of a randomized SVD of such a block): rc_lowrank_recompress_tall_batched_f64 / _f32's signature argument for argument, and
+ * rc_lowrank_recompress_batched_*'s per-block contract sentence for sentence (q, s_out, the rank rule, zero tails of u and vt, an exactly zero
+ * column of left[:, :q] giving an exactly zero singular value, q = 0, elements at an index >= q never read, NaN containment, health bit 16,
+ * no host synchronisation, capturable).  The sign rule is the tall call's: the first largest-|.| entry over all m rows of each kept column
+ * of u is positive, and vt takes u's signs.
+ * Domain: 1 <= m, n <= 65536, 1 <= K <= 128, K <= min(m, n), k >= 1, 0 <= tol < 1, count >= 0; the checks, status codes and messages are the
+ * pair's above under the name lowrank_recompress_large_batched.  Real scalars only: rc_lowrank_recompress_large_batched_c64 / _c32 do not
+ * exist.
+ * Per block: for n > 512, right[:q, :]^T (n x q) goes through the tall call's flat Householder TSQR as left[:, :q] does: stage 0 the pivoted
+ * QR of its rows 0 .. 511, every later stage the q x q triangle on the next 512 - q rows in the pivot order so far; the factor's power-of-two
+ * scale is taken over all n columns.  The last triangle and the cumulative permutation enter the core; the core, the Jacobi iteration, the
+ * sort and the rank rule are unchanged.  Each kept row of vt is carried back down the right factor's stages and written once, chunk by
+ * chunk, with the sign already fixed on u.
+ * Bits: a block's bits depend on its operands, their row and column strides and the call's shapes alone, and they equal the bits of the
+ * truncated factors passed as a call of inner width q (the stage heights of both sides depend on q, not on K).  For n <= 512 every output
+ * equals rc_lowrank_recompress_tall_batched_*'s on the same arguments bit for bit, so for m, n <= 512 it equals
+ * rc_lowrank_recompress_batched_*'s too.  No transposition symmetry is promised: the Jacobi iteration runs on the transposed core and the
+ * sign rule is on u, so the call on (right^T, mid^T, left^T) need not give the transposed bits.
+ * Workspace: a workgroup's slot holds the left factor's stage copies (m > 512), then the right factor's (n > 512), then the rotations where
+ * they do not fit in LDS; a side <= 512 follows the tall call's plan, so an n <= 512 call has that plan byte for byte.  The grid is bounded
+ * so that all slots stay at or below 2 GiB (never below one workgroup): at m = n = 65536, K = 128 in f64, two sides of 171 stages of
+ * 526336 bytes leave 11 workgroups; rc_lowrank_recompress_large_batched_plan reports the numbers. */
+rc_status rc_lowrank_recompress_large_batched_f64(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const double *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *in_ranks, int32_t count, int64_t k, double tol, rc_matrix u, int64_t u_batch_stride, double *s_out, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks);
+rc_status rc_lowrank_recompress_large_batched_f32(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const float *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *in_ranks, int32_t count, int64_t k, double tol, rc_matrix u, int64_t u_batch_stride, float *s_out, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks);
+/* The plan of that call as numbers, host arithmetic only (no context, no device): as rc_lowrank_recompress_tall_batched_plan, with the
+ * stages of a block of full inner rank on each side (1 for a side <= 512).  RC_INVALID_ARGUMENT outside the call's domain or for a null
+ * output. */
+rc_status rc_lowrank_recompress_large_batched_plan(int64_t m, int64_t n, int64_t inner, int32_t elem_bytes, int64_t resident, int64_t *stages_left, int64_t *stages_right, int64_t *slot_bytes, int64_t *grid);
 /* The same call for complex factors (c64, c32): rc_lowrank_recompress_batched_f64's signature argument for argument and its contract, domain,
  * checks and error messages, with interleaved (re, im) data and every stride and batch stride in complex elements.  s, s_out and tol have the
  * real type of the data (double for c64, float for c32): s scales the columns of mid by real numbers, and singular values are real.

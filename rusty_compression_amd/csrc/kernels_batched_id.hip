@@ -26,6 +26,9 @@
 // Tall left factors (rc_lowrank_recompress_tall_batched_*, m <= 65536): k_batched_recompress<T, true>, the same kernel text with the left
 // factor taken through a flat Householder TSQR in stages of 512 rows kept in the workgroup's slot (see "tall left factors" below).
 //
+// Both factors tall (rc_lowrank_recompress_large_batched_*, m, n <= 65536): k_batched_recompress<T, true, true>, the right factor through
+// the same stages behind the left factor's in the slot, vt formed down them with u's signs (see "both factors tall" below).
+//
 // Batched sketched column ID (rc_sketch_column_id_rank_batched_*): k_batched_sketch_id, the same grid; the working copy is the sketch
 // Omega A (l x n, l <= 128) formed by MFMA while A streams through LDS once, then the same stages on l rows (see its comment below).
 //
@@ -866,6 +869,55 @@ __device__ __forceinline__ void brt_form_u(const T *stage0, size_t se, int S, in
     }
 }
 
+// ---- both factors tall (rc_lowrank_recompress_large_batched_*, m, n <= 65536) -------------------------------------------------------
+// right[:q, :]^T (n x q) goes through the scheme above when n > H: the same stages, jpr carried from stage to stage, every stage's copy,
+// taus and pivots in the workgroup's slot behind the left factor's part; (the last stage's copy, jpr) stand where (Wr, jpr) stand in T1.
+// n <= H is the tall call itself: the launcher runs k_batched_recompress<T, true> under the tall call's plan, so the bits are that call's.
+// the slot: the left factor's part (stage copies for m > H, brc_ws_elems' copy otherwise), the right factor's stage copies, then J
+__host__ __device__ inline size_t brl_ws_elems(int m, int n, int K, bool l_lds, bool r_lds, bool v_lds) {
+    if (n <= BRT_H) return brt_ws_elems(m, n, K, l_lds, r_lds, v_lds);
+    return brt_ws_elems(m, 0, K, l_lds, true, true) + (size_t)brt_stages(n, K) * brt_stage_elems(K) + (v_lds ? 0 : (size_t)K * K);
+}
+
+// V[:, c] = sgn[c] Q_0 [Q_1 [.. Q_{S-1} [Vc[:, srt[c]]; 0] ..; 0]; 0] for S >= 2 stages of the right factor: brt_form_u with the signs
+// already fixed on u, so every chunk is written once with its sign and no row is visited twice.  V is vt's transposed view (n x k).
+template <typename T>
+__device__ __forceinline__ void brl_form_vt(const T *stage0, size_t se, int S, int K, int q, int n, const T *Vc, int ldv, int k, int r, const int *srt,
+                                            const int *sgn, T *V, int64_t vrs, int64_t vcs, int wv, int lane) {
+    constexpr int NE = BRT_H / 64;
+    for (int c = wv; c < k; c += BID_WAVES) {
+        T *vc = V + (int64_t)c * vcs;
+        if (c >= r) {
+            for (int i = lane; i < n; i += 64) vc[i * vrs] = (T)0;
+            continue;
+        }
+        const T *gc = Vc + (size_t)srt[c] * ldv;
+        const bool neg = sgn[c] < 0;
+        T x[NE];
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            const int i = lane + 64 * e;
+            x[e] = i < q ? gc[i] : (T)0;
+        }
+        for (int s = S - 1; s >= 0; --s) {
+            const T *Ws = stage0 + (size_t)s * se, *ts = Ws + (size_t)BRT_H * K;
+            const int top = s ? q : 0, base = s ? BRT_H + (s - 1) * (BRT_H - q) : 0;
+            const int hs = top + min(BRT_H - top, n - base);
+            bsv_reflect_back<T, NE>(Ws, BRT_H, hs, q, reinterpret_cast<const int *>(ts + K), ts, x, lane);
+            if (s) {
+#pragma unroll
+                for (int e = 0; e < NE; ++e) {
+                    const int i = lane + 64 * e;
+                    if (i >= top && i < hs) vc[(int64_t)(base + i - top) * vrs] = neg ? -x[e] : x[e];
+                    x[e] = i < top ? x[e] : (T)0;
+                }
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < NE; ++e) vc[(int64_t)(lane + 64 * e) * vrs] = neg ? -x[e] : x[e];  // stage 0 of S >= 2 stages holds H rows
+    }
+}
+
 // The exponent of a factor before it is loaded (block_pow2_exponent over at(i, c), i < rows, c < q, read as bid_fill reads it): the loads
 // below multiply every entry by 2^-e, so that the norms, both cores and the Jacobi run at unit scale as in k_batched_svd, and the
 // singular values take 2^(eL + eR) back.  One more read of the factor (the second one hits L2); with e = 0 (a zero or non-finite
@@ -883,22 +935,28 @@ __device__ __forceinline__ int brc_exponent(int rows, int q, bool lanes_on_rows,
     return block_pow2_exponent(mx, stage, wv, lane);
 }
 
-// TALL = false: rc_lowrank_recompress_batched_*.  TALL = true: rc_lowrank_recompress_tall_batched_*, the left factor by stages (see above)
-template <typename T, bool TALL>
+// TALL = false: rc_lowrank_recompress_batched_*.  TALL = true: rc_lowrank_recompress_tall_batched_*, the left factor by stages (see above).
+// LARGE (with TALL): rc_lowrank_recompress_large_batched_* for n > BRT_H, the right factor by stages too (see "both factors tall"); the
+// launcher sends n <= BRT_H to the TALL instance, so this one carries neither the one-stage path of the right factor nor bsv_form_u for vt
+template <typename T, bool TALL, bool LARGE = false>
 __global__ __launch_bounds__(BID_THREADS) void k_batched_recompress(BrcArgs<T> a) {
+    static_assert(TALL || !LARGE, "the large instance is the tall one with a staged right factor");
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int m = (int)a.left.rows, n = (int)a.right.cols, K = (int)a.left.cols;
     const int kk = a.k < K ? a.k : K, ldg = a.ldg;
     const bool multi = TALL && m > BRT_H;  // the plan keeps the stage copies out of LDS
-    const int ldl = multi ? BRT_H : a.l_lds ? (m | 1) : m, ldr = a.r_lds ? (n | 1) : n, ldj = a.v_lds ? ldg : K;
+    constexpr bool rmulti = LARGE;  // likewise for the right factor's: n > BRT_H in that instance
+    const int ldl = multi ? BRT_H : a.l_lds ? (m | 1) : m, ldr = rmulti ? BRT_H : a.r_lds ? (n | 1) : n, ldj = a.v_lds ? ldg : K;
     T *lds = reinterpret_cast<T *>(smem_raw);
-    T *wsb = a.ws + (size_t)blockIdx.x * (TALL ? brt_ws_elems(m, n, K, a.l_lds, a.r_lds, a.v_lds) : brc_ws_elems(m, n, K, a.l_lds, a.r_lds, a.v_lds));
-    T *Wl0 = lds, *Wr = lds + (a.l_lds ? (size_t)K * ldl : 0);
-    T *G = Wr + (a.r_lds ? (size_t)K * ldr : 0);
+    T *wsb = a.ws + (size_t)blockIdx.x * (LARGE  ? brl_ws_elems(m, n, K, a.l_lds, a.r_lds, a.v_lds)
+                                          : TALL ? brt_ws_elems(m, n, K, a.l_lds, a.r_lds, a.v_lds)
+                                                 : brc_ws_elems(m, n, K, a.l_lds, a.r_lds, a.v_lds));
+    T *Wl0 = lds, *Wr0 = lds + (a.l_lds ? (size_t)K * ldl : 0);
+    T *G = Wr0 + (a.r_lds ? (size_t)K * ldr : 0);
     T *J = G + (size_t)K * ldg;
     T *vn1 = J + (a.v_lds ? (size_t)K * ldg : 0);
     if (!a.l_lds) { Wl0 = wsb; wsb += multi ? (size_t)brt_stages(m, K) * brt_stage_elems(K) : (size_t)m * K; }
-    if (!a.r_lds) { Wr = wsb; wsb += (size_t)n * K; }
+    if (!a.r_lds) { Wr0 = wsb; wsb += rmulti ? (size_t)brt_stages(n, K) * brt_stage_elems(K) : (size_t)n * K; }
     if (!a.v_lds) J = wsb;
     T *vn2 = vn1 + K, *taul = vn2 + K, *taur = taul + K, *sig = taur + K, *red = sig + K;
     int *jpl = reinterpret_cast<int *>(red + 8);
@@ -927,6 +985,7 @@ __global__ __launch_bounds__(BID_THREADS) void k_batched_recompress(BrcArgs<T> a
         const T *__restrict__ L = a.left.p + (int64_t)b * a.lbs;
         const T *__restrict__ R = a.right.p + (int64_t)b * a.rbs;
         T *Wl = Wl0;  // the copy the core and U read: the last stage's
+        T *Wr = Wr0;  // likewise for T1
         // the factors' exponents (red[4..7], then red[0..3]: bid_qrcp writes red only behind the loads' barriers)
         const int el = brc_exponent(m, q, a.left.rs <= a.left.cs, [&](int i, int c) { return L[(int64_t)i * a.left.rs + c * a.left.cs]; }, red + 4, wv, lane);
         const int er = brc_exponent(n, q, a.right.cs <= a.right.rs, [&](int i, int c) { return R[c * a.right.rs + i * a.right.cs]; }, red, wv, lane);
@@ -954,8 +1013,27 @@ __global__ __launch_bounds__(BID_THREADS) void k_batched_recompress(BrcArgs<T> a
             bid_load(Wl, ldl, m, q, a.left.rs <= a.left.cs, [&](int i, int c) { return L[i * a.left.rs + c * a.left.cs] * scl; }, vn1, vn2, jpl, wv, lane);
             bid_qrcp<T, true>(Wl, ldl, m, q, q, 0.0, jpl, vn1, vn2, red, tid, wv, lane, taul);
         }
-        bid_load(Wr, ldr, n, q, a.right.cs <= a.right.rs, [&](int i, int c) { return R[c * a.right.rs + i * a.right.cs] * scr; }, vn1, vn2, jpr, wv, lane);
-        bid_qrcp<T, true>(Wr, ldr, n, q, q, 0.0, jpr, vn1, vn2, red, tid, wv, lane, taur);
+        [[maybe_unused]] int Sr = 1;
+        if constexpr (LARGE) {  // the left factor's stage loop on right[:q, :]^T, every stage in the slot
+            Sr = brt_stages(n, q);
+            const size_t se = brt_stage_elems(K);
+            for (int j = tid; j < q; j += BID_THREADS) jpr[j] = j;  // ordered before its first read by brt_stack_load's barrier
+            for (int s = 0; s < Sr; ++s) {
+                const int top = s ? q : 0, base = s ? BRT_H + (s - 1) * (BRT_H - q) : 0;
+                const int hs = top + min(BRT_H - top, n - base);
+                T *Ws = Wr0 + (size_t)s * se;
+                T *ts = Ws + (size_t)BRT_H * K;
+                brt_stack_load(Ws, ldr, Ws - (s ? se : 0), top, hs, q, a.right.cs <= a.right.rs,
+                               [&](int i, int c) { return R[c * a.right.rs + (int64_t)(base + i) * a.right.cs] * scr; }, vn1, vn2, jpr, wv, lane);
+                bid_qrcp<T, true>(Ws, ldr, hs, q, q, 0.0, jpr, vn1, vn2, red, tid, wv, lane, ts);
+                int *js = reinterpret_cast<int *>(ts + K);
+                for (int j = tid; j < q; j += BID_THREADS) js[j] = jpr[j];
+                Wr = Ws;
+            }
+        } else {
+            bid_load(Wr, ldr, n, q, a.right.cs <= a.right.rs, [&](int i, int c) { return R[c * a.right.rs + i * a.right.cs] * scr; }, vn1, vn2, jpr, wv, lane);
+            bid_qrcp<T, true>(Wr, ldr, n, q, q, 0.0, jpr, vn1, vn2, red, tid, wv, lane, taur);
+        }
         for (int j = tid; j < q; j += BID_THREADS) { ipl[jpl[j]] = j; ipr[jpr[j]] = j; }
         __syncthreads();
         // ---- T1 = mid diag(s) Rr^T in J's place ----------------------------------------------------------------------------------------
@@ -1048,7 +1126,8 @@ __global__ __launch_bounds__(BID_THREADS) void k_batched_recompress(BrcArgs<T> a
             for (int i = lane; i < q; i += 64) gc[i] *= inv;
         }
         __syncthreads();  // sgn and the scaled columns are read by other waves below
-        if (n <= 64) bsv_form_u<T, 1>(Wr, ldr, G, ldg, n, q, kk, r, jpr, taur, srt, sgn, false, Vb, a.vt.cs, a.vt.rs, wv, lane);
+        if constexpr (LARGE) brl_form_vt<T>(Wr0, brt_stage_elems(K), Sr, K, q, n, G, ldg, kk, r, srt, sgn, Vb, a.vt.cs, a.vt.rs, wv, lane);
+        else if (n <= 64) bsv_form_u<T, 1>(Wr, ldr, G, ldg, n, q, kk, r, jpr, taur, srt, sgn, false, Vb, a.vt.cs, a.vt.rs, wv, lane);
         else if (n <= 128) bsv_form_u<T, 2>(Wr, ldr, G, ldg, n, q, kk, r, jpr, taur, srt, sgn, false, Vb, a.vt.cs, a.vt.rs, wv, lane);
         else if (n <= 256) bsv_form_u<T, 4>(Wr, ldr, G, ldg, n, q, kk, r, jpr, taur, srt, sgn, false, Vb, a.vt.cs, a.vt.rs, wv, lane);
         else bsv_form_u<T, 8>(Wr, ldr, G, ldg, n, q, kk, r, jpr, taur, srt, sgn, false, Vb, a.vt.cs, a.vt.rs, wv, lane);
@@ -1420,6 +1499,19 @@ BatchedPlan<BrcPlace> brt_plan(int m, int n, int K) {
         [&](BrcPlace p) { return brt_ws_elems(m, n, K, p.l, p.r, p.v) * sizeof(T); }, "lowrank_recompress_tall_batched");
 }
 
+// large recompression: n <= BRT_H is brt_plan (the tall call's plan byte for byte); above it the right factor's stage copies are always in the
+// slot, the left factor's copy by brc_plan's rule for m <= BRT_H and staged above it, J by brc_plan's rule, and the slot is brl_ws_elems
+template <typename T>
+BatchedPlan<BrcPlace> brl_plan(int m, int n, int K) {
+    if (n <= BRT_H) return brt_plan<T>(m, n, K);
+    const int pad = ((K + 15) / 32) * 32 + 16, odd = K | 1;
+    const bool l = m <= BRT_H;  // the only copy that may sit in LDS
+    const BrcPlace places[] = {{l, false, true, pad}, {l, false, true, odd}, {false, false, true, pad}, {false, false, true, odd},
+                               {false, false, false, pad}, {false, false, false, odd}};
+    return batched_first_fit(places, [&](BrcPlace p) { return brc_lds_bytes<T>(m, n, K, p.ld, p.l, p.r, p.v); },
+        [&](BrcPlace p) { return brl_ws_elems(m, n, K, p.l, p.r, p.v) * sizeof(T); }, "lowrank_recompress_large_batched");
+}
+
 // sketched column ID: W (l x n) in LDS when it fits next to the chunk images, else in the workgroup's slot
 template <typename T>
 BatchedPlan<bool> bsi_plan(int l, int n) {
@@ -1513,23 +1605,30 @@ void batched_svd(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int64_t k,
 
 // One kernel per entry point: the plan only moves base pointers and pitches.  TALL (rc_lowrank_recompress_tall_batched_*): the same arguments
 // and, for m <= 512, the same plan and the same work per block.  Above it a slot holds every stage's copy (about 90 MiB at 65536 x 128 in
-// f64), so the grid is bounded a second time, by brt_grid_cap: few workgroups run there.
-template <typename T, bool TALL>
+// f64), so the grid is bounded a second time, by brt_grid_cap: few workgroups run there.  LARGE (rc_lowrank_recompress_large_batched_*): for
+// n <= 512 the tall call's plan; above it the slot holds the right factor's stages too and the same bound applies to the whole slot.
+template <typename T, bool TALL, bool LARGE = false>
 void brc_launch(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride, Mat<T> right, int64_t rbs, const int64_t *in_ranks,
                 int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs, T *s_out, Mat<T> vt, int64_t vbs, int64_t *ranks) {
     const int m = (int)left.rows, n = (int)right.cols, K = (int)left.cols;
     if (count <= 0) return;
-    const auto plan = TALL ? brt_plan<T>(m, n, K) : brc_plan<T>(m, n, K);
+    const auto plan = LARGE ? brl_plan<T>(m, n, K) : TALL ? brt_plan<T>(m, n, K) : brc_plan<T>(m, n, K);
     const BrcPlace at = plan.at;
-    auto lch = batched_prepare(c, k_batched_recompress<T, TALL>, TALL ? "lowrank_recompress_tall_batched" : "lowrank_recompress_batched",
-                               plan.lds, plan.ws, count);
-    char stages[24] = "";
+    // n <= BRT_H under the large call is the tall instance under the tall plan (brl_plan returns it): the same kernel, the same bits
+    void (*const kern)(BrcArgs<T>) = LARGE && n > BRT_H ? k_batched_recompress<T, TALL, LARGE> : k_batched_recompress<T, TALL, false>;
+    auto lch = batched_prepare(c, kern,
+                               LARGE ? "lowrank_recompress_large_batched" : TALL ? "lowrank_recompress_tall_batched" : "lowrank_recompress_batched", plan.lds,
+                               plan.ws, count);
+    char stages[48] = "";
     if constexpr (TALL) {
         lch.grid = brt_grid_cap(lch.grid, plan.ws);
         lch.slots = brt_grid_cap(lch.slots, plan.ws);
-        snprintf(stages, sizeof stages, "stages=%d,", brt_stages(m, K));  // inside plan=: the label keeps the family's fields
+        // inside plan=: the label keeps the family's fields
+        if (LARGE) snprintf(stages, sizeof stages, "stages=%d,rstages=%d,", brt_stages(m, K), brt_stages(n, K));
+        else snprintf(stages, sizeof stages, "stages=%d,", brt_stages(m, K));
     }
-    ProfScope ps(c, "op:batched_recompress%s %dx%d k=%d count=%d grid=%lld slots=%lld plan=%sL:%s,R:%s,V:%s,G:lds,ld=%d,kk=%d%s%s", TALL ? "_tall" : "", m, n, K,
+    ProfScope ps(c, "op:batched_recompress%s %dx%d k=%d count=%d grid=%lld slots=%lld plan=%sL:%s,R:%s,V:%s,G:lds,ld=%d,kk=%d%s%s",
+                 LARGE ? "_large" : TALL ? "_tall" : "", m, n, K,
                  (int)count, (long long)lch.grid, (long long)lch.slots, stages, at.l ? "lds" : "ws", at.r ? "lds" : "ws", at.v ? "lds" : "ws", at.ld,
                  (int)std::min<int64_t>(k, K), mid.p ? ",mid" : "", s ? ",s" : "");
     BrcArgs<T> a;
@@ -1553,6 +1652,24 @@ void batched_lowrank_recompress_tall(rc_context *c, Mat<T> left, int64_t lbs, Ma
                                      int64_t rbs, const int64_t *in_ranks, int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs, T *s_out, Mat<T> vt,
                                      int64_t vbs, int64_t *ranks) {
     brc_launch<T, true>(c, left, lbs, mid, mbs, s, s_stride, right, rbs, in_ranks, count, k, tol, u, ubs, s_out, vt, vbs, ranks);
+}
+
+template <typename T>
+void batched_lowrank_recompress_large(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride, Mat<T> right,
+                                      int64_t rbs, const int64_t *in_ranks, int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs, T *s_out, Mat<T> vt,
+                                      int64_t vbs, int64_t *ranks) {
+    brc_launch<T, true, true>(c, left, lbs, mid, mbs, s, s_stride, right, rbs, in_ranks, count, k, tol, u, ubs, s_out, vt, vbs, ranks);
+}
+
+// the large launcher's plan as numbers (rc_lowrank_recompress_large_batched_plan): the stages of both factors at inner width K, bytes of one
+// slot, and the grid brt_grid_cap leaves of `resident` workgroups
+void batched_lowrank_recompress_large_plan(int64_t m, int64_t n, int64_t K, bool f64, int64_t resident, int64_t *stages_left, int64_t *stages_right,
+                                           int64_t *slot_bytes, int64_t *grid) {
+    const size_t ws = f64 ? brl_plan<double>((int)m, (int)n, (int)K).ws : brl_plan<float>((int)m, (int)n, (int)K).ws;
+    *stages_left = brt_stages((int)m, (int)K);
+    *stages_right = brt_stages((int)n, (int)K);
+    *slot_bytes = (int64_t)ws;
+    *grid = brt_grid_cap(resident, ws);
 }
 
 // the tall launcher's plan as numbers (rc_lowrank_recompress_tall_batched_plan): stages at inner width K, bytes of one slot, and the grid
@@ -1633,6 +1750,11 @@ template void batched_lowrank_recompress_tall<double>(rc_context *, Mat<double>,
                                                       const int64_t *, int32_t, int64_t, double, Mat<double>, int64_t, double *, Mat<double>, int64_t, int64_t *);
 template void batched_lowrank_recompress_tall<float>(rc_context *, Mat<float>, int64_t, Mat<float>, int64_t, const float *, int64_t, Mat<float>, int64_t,
                                                      const int64_t *, int32_t, int64_t, double, Mat<float>, int64_t, float *, Mat<float>, int64_t, int64_t *);
+
+template void batched_lowrank_recompress_large<double>(rc_context *, Mat<double>, int64_t, Mat<double>, int64_t, const double *, int64_t, Mat<double>, int64_t,
+                                                       const int64_t *, int32_t, int64_t, double, Mat<double>, int64_t, double *, Mat<double>, int64_t, int64_t *);
+template void batched_lowrank_recompress_large<float>(rc_context *, Mat<float>, int64_t, Mat<float>, int64_t, const float *, int64_t, Mat<float>, int64_t,
+                                                      const int64_t *, int32_t, int64_t, double, Mat<float>, int64_t, float *, Mat<float>, int64_t, int64_t *);
 
 template void batched_column_id<double>(rc_context *, Mat<double>, int64_t, int32_t, int64_t, double, Mat<double>, int64_t, Mat<double>, int64_t, int64_t *, int64_t *);
 template void batched_column_id<float>(rc_context *, Mat<float>, int64_t, int32_t, int64_t, double, Mat<float>, int64_t, Mat<float>, int64_t, int64_t *, int64_t *);

@@ -97,6 +97,13 @@ template <typename T> void batched_lowrank_recompress_tall(rc_context *c, Mat<T>
                                                            Mat<T> right, int64_t rbs, const int64_t *in_ranks, int32_t count, int64_t k, double tol, Mat<T> u,
                                                            int64_t ubs, T *s_out, Mat<T> vt, int64_t vbs, int64_t *ranks);
 void batched_lowrank_recompress_tall_plan(int64_t m, int64_t n, int64_t K, bool f64, int64_t resident, int64_t *stages, int64_t *slot_bytes, int64_t *grid);
+// the same with both factors tall (m, n <= 65536; k_batched_recompress<T, true, true>): right^T by the same stages behind left's in the slot; n <= 512
+// is the tall call bit for bit.  Its plan as numbers: the stages of both factors at inner width K, bytes of one slot, the grid
+template <typename T> void batched_lowrank_recompress_large(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride,
+                                                            Mat<T> right, int64_t rbs, const int64_t *in_ranks, int32_t count, int64_t k, double tol, Mat<T> u,
+                                                            int64_t ubs, T *s_out, Mat<T> vt, int64_t vbs, int64_t *ranks);
+void batched_lowrank_recompress_large_plan(int64_t m, int64_t n, int64_t K, bool f64, int64_t resident, int64_t *stages_left, int64_t *stages_right,
+                                           int64_t *slot_bytes, int64_t *grid);
 // the complex twin (kernels_batched_id_c.hip), R = double (c64) or float (c32): interleaved-complex views, strides in complex elements, s and s_out
 // real, vt = V^H
 template <typename R> void batched_lowrank_recompress_c(rc_context *c, const rc_matrix &left, int64_t lbs, const rc_matrix &mid, int64_t mbs, const R *s,
@@ -110,8 +117,8 @@ template <typename R> void batched_lowrank_recompress_tall_c(rc_context *c, cons
 void batched_lowrank_recompress_tall_c_plan(int64_t m, int64_t n, int64_t K, bool c64, int64_t resident, int64_t *stages, int64_t *slot_bytes, int64_t *grid);
 // the argument checks of rc_lowrank_recompress_batched_* and rc_lowrank_recompress_complex_batched_* (rc_batched_api.hip), one for every scalar type
 // like those above; the caller returns when count == 0.  tall: the bound m <= 65536 under rc_lowrank_recompress_tall_batched_*'s name (RC_TALL) or
-// rc_lowrank_recompress_tall_complex_batched_*'s (RC_TALL_COMPLEX)
-enum { RC_NOT_TALL = 0, RC_TALL = 1, RC_TALL_COMPLEX = 2 };
+// rc_lowrank_recompress_tall_complex_batched_*'s (RC_TALL_COMPLEX); RC_LARGE: m, n <= 65536 under rc_lowrank_recompress_large_batched_*'s
+enum { RC_NOT_TALL = 0, RC_TALL = 1, RC_TALL_COMPLEX = 2, RC_LARGE = 3 };
 void check_lowrank_recompress_batched(const rc_matrix &left, const rc_matrix &mid, const rc_matrix &right, int32_t count, int64_t k, double tol,
                                       const rc_matrix &u, int64_t ubs, const void *s_out, const rc_matrix &vt, int64_t vbs, const int64_t *ranks,
                                       int tall = RC_NOT_TALL);

@@ -161,12 +161,16 @@ BlockShape check_block_operator_apply(const rc_matrix &left, const rc_matrix &mi
 // and vt (min(k, K) x n)
 void check_lowrank_recompress_batched(const rc_matrix &left, const rc_matrix &mid, const rc_matrix &right, int32_t count, int64_t k, double tol,
                                       const rc_matrix &u, int64_t ubs, const void *s_out, const rc_matrix &vt, int64_t vbs, const int64_t *ranks, int tall) {
-    const char *who = tall == RC_TALL_COMPLEX ? "lowrank_recompress_tall_complex_batched" : tall ? "lowrank_recompress_tall_batched" : "lowrank_recompress_batched";
+    const char *who = tall == RC_LARGE          ? "lowrank_recompress_large_batched"
+                      : tall == RC_TALL_COMPLEX ? "lowrank_recompress_tall_complex_batched"
+                      : tall                    ? "lowrank_recompress_tall_batched"
+                                                : "lowrank_recompress_batched";
     const int64_t m = left.rows, K = left.cols, n = right.cols;
     RC_REQUIRE(count >= 0, RC_INVALID_ARGUMENT, "%s: count = %d < 0", who, (int)count);
-    RC_REQUIRE(m >= 1 && m <= (tall ? 65536 : 512) && n >= 1 && n <= 512 && K >= 1 && K <= 128 && k >= 1, RC_INVALID_ARGUMENT,
-               "%s: needs 1 <= m%s <= 512, inner width 1 <= K <= 128 and k >= 1 (got left %lld x %lld, right %lld x %lld, k = %lld)", who,
-               tall ? " <= 65536, 1 <= n" : ", n", (long long)m, (long long)K, (long long)right.rows, (long long)n, (long long)k);
+    RC_REQUIRE(m >= 1 && m <= (tall ? 65536 : 512) && n >= 1 && n <= (tall == RC_LARGE ? 65536 : 512) && K >= 1 && K <= 128 && k >= 1, RC_INVALID_ARGUMENT,
+               "%s: needs 1 <= m%s, inner width 1 <= K <= 128 and k >= 1 (got left %lld x %lld, right %lld x %lld, k = %lld)", who,
+               tall == RC_LARGE ? ", n <= 65536" : tall ? " <= 65536, 1 <= n <= 512" : ", n <= 512", (long long)m, (long long)K, (long long)right.rows, (long long)n,
+               (long long)k);
     RC_REQUIRE(right.rows == K, RC_INVALID_ARGUMENT, "%s: left is %lld x %lld but right has %lld rows", who, (long long)m, (long long)K, (long long)right.rows);
     RC_REQUIRE(K <= std::min(m, n), RC_INVALID_ARGUMENT,
                "%s: needs K <= min(m, n) (got K = %lld for %lld x %lld blocks); rebuild the blocks with rc_lowrank_apply_batched_* and use rc_svd_rank_batched_*",
@@ -254,6 +258,7 @@ struct Real {
     template <typename... A> static void block_operator(bool, const A &...a) { block_operator_apply<R>(a...); }
     template <typename... A> static void recompress(const A &...a) { batched_lowrank_recompress<R>(a...); }
     template <typename... A> static void recompress_tall(const A &...a) { batched_lowrank_recompress_tall<R>(a...); }
+    template <typename... A> static void recompress_large(const A &...a) { batched_lowrank_recompress_large<R>(a...); }
     template <typename... A> static void sketch_column_id(const A &...a) { batched_sketch_column_id<R>(a...); }
     template <typename... A> static void range_step(bool, const A &...a) { batched_sketch_range_step<R>(a...); }
     template <typename... A> static void residual(const A &...a) { batched_lowrank_residual<R>(a...); }
@@ -299,6 +304,20 @@ rc_status recompress_tall_plan(bool complex, int64_t m, int64_t n, int64_t inner
     try {
         (complex ? batched_lowrank_recompress_tall_c_plan : batched_lowrank_recompress_tall_plan)(m, n, inner, real_bytes == 8, resident, stages, slot_bytes,
                                                                                                   grid);
+        return RC_OK;
+    } catch (const Error &e) {
+        return e.code;
+    }
+}
+
+// the large recompression's plan as numbers, likewise
+rc_status recompress_large_plan(int64_t m, int64_t n, int64_t inner, int32_t elem_bytes, int64_t resident, int64_t *stages_left, int64_t *stages_right,
+                                int64_t *slot_bytes, int64_t *grid) {
+    if (!(m >= 1 && m <= 65536 && n >= 1 && n <= 65536 && inner >= 1 && inner <= 128 && inner <= std::min(m, n)) || (elem_bytes != 4 && elem_bytes != 8) ||
+        resident < 1 || !stages_left || !stages_right || !slot_bytes || !grid)
+        return RC_INVALID_ARGUMENT;
+    try {
+        batched_lowrank_recompress_large_plan(m, n, inner, elem_bytes == 8, resident, stages_left, stages_right, slot_bytes, grid);
         return RC_OK;
     } catch (const Error &e) {
         return e.code;
@@ -445,6 +464,26 @@ RC_DEFINE_BATCHED(f32, float, Real, )
 RC_DEFINE_BATCHED(c64, double, Cplx, complex_)
 RC_DEFINE_BATCHED(c32, float, Cplx, complex_)
 
+// the recompression with both factors tall (m, n <= 65536): the pair's checks with those bounds under the call's own name, both factors by a
+// flat Householder TSQR inside the launch.  Real scalars only, so the stanza stands outside RC_DEFINE_BATCHED.
+#define RC_DEFINE_RECOMPRESS_LARGE(SUF, R)                                                                                                   \
+    rc_status rc_lowrank_recompress_large_batched_##SUF(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid,           \
+                                                        int64_t mid_batch_stride, const R *s, int64_t s_stride, rc_matrix right,             \
+                                                        int64_t right_batch_stride, const int64_t *in_ranks, int32_t count, int64_t k,       \
+                                                        double tol, rc_matrix u, int64_t u_batch_stride, R *s_out, rc_matrix vt,             \
+                                                        int64_t vt_batch_stride, int64_t *ranks) {                                           \
+        return guarded(ctx, [&] {                                                                                                            \
+            check_lowrank_recompress_batched(left, mid, right, count, k, tol, u, u_batch_stride, s_out, vt, vt_batch_stride, ranks,          \
+                                             RC_LARGE);                                                                                      \
+            if (count == 0) return;                                                                                                          \
+            Real<R>::recompress_large(ctx, Real<R>::view(left), left_batch_stride, Real<R>::view(mid), mid_batch_stride, s, s_stride,        \
+                                      Real<R>::view(right), right_batch_stride, in_ranks, count, k, tol, Real<R>::view(u), u_batch_stride,   \
+                                      s_out, Real<R>::view(vt), vt_batch_stride, ranks);                                                     \
+        });                                                                                                                                  \
+    }
+RC_DEFINE_RECOMPRESS_LARGE(f64, double)
+RC_DEFINE_RECOMPRESS_LARGE(f32, float)
+
 #define RC_RANGE_STEP_PARAMS                                                                                                                            \
     rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega, int64_t omega_batch_stride, int32_t count, rc_matrix y, int64_t y_batch_stride, \
         rc_matrix q, int64_t q_batch_stride, rc_matrix p, int64_t p_batch_stride, int64_t *ranks
@@ -461,6 +500,10 @@ rc_status rc_sketch_range_step_complex_batched_c32(RC_RANGE_STEP_PARAMS, int32_t
 rc_status rc_lowrank_recompress_tall_batched_plan(int64_t m, int64_t n, int64_t inner, int32_t elem_bytes, int64_t resident, int64_t *stages,
                                                   int64_t *slot_bytes, int64_t *grid) {
     return recompress_tall_plan(false, m, n, inner, elem_bytes, resident, stages, slot_bytes, grid);
+}
+rc_status rc_lowrank_recompress_large_batched_plan(int64_t m, int64_t n, int64_t inner, int32_t elem_bytes, int64_t resident, int64_t *stages_left,
+                                                   int64_t *stages_right, int64_t *slot_bytes, int64_t *grid) {
+    return recompress_large_plan(m, n, inner, elem_bytes, resident, stages_left, stages_right, slot_bytes, grid);
 }
 // (real_bytes 8: c64, 4: c32)
 rc_status rc_lowrank_recompress_tall_complex_batched_plan(int64_t m, int64_t n, int64_t inner, int32_t real_bytes, int64_t resident, int64_t *stages,
