@@ -35,12 +35,19 @@
 // Batched range step (rc_sketch_range_step_batched_*): k_batched_range_step, the same grid; that sketch stored as Y^T, its pivoted QR run to
 // all l steps, Q formed explicitly and the projection A Q^T by the sketch routine on A's transposed view (see its comment below).
 //
+// The stages that read the same for real and complex elements stand once in batched_stages.hpp, as templates over the element type that
+// this file instantiates for double and float: the fill, the norms and their power-of-two normalisation, the pivoted-QR step loop bid_qrcp,
+// the back substitution bid_z, k_batched_id and k_batched_two_sided with their LDS carve-up, plans and launcher bodies, the Jacobi schedule
+// bsv_jacobi and brt_stack_load.  Here stay the real family's own routines (bid_apply, bsv_round, bsv_sign, the form_u routines, the core
+// products) and the SVD, recompression, sketch and range-step kernels.
+//
 // The launchers at the end of the file follow rc_batched_launch.hpp: a plan function per entry point, then prepare, label, workspace,
 // launch.  bid_grid and the first-use LDS cap of the whole batched family are defined here.
 #include <map>
 #include <mutex>
 #include <utility>
 
+#include "batched_stages.hpp"
 #include "rc_batched_launch.hpp"
 #include "rc_common.hpp"
 #include "rc_device.hpp"
@@ -49,18 +56,6 @@
 namespace rc {
 
 namespace {
-
-constexpr int BID_THREADS = BATCHED_THREADS;
-constexpr int BID_WAVES = BID_THREADS / 64;
-constexpr int BID_NB = 16;  // back-substitution tile (k_id_z's)
-
-// dynamic LDS: [W: m x ldw, LDS variant only] vn1[n] vn2[n] tile[16 x 17] red[8] | jp[n] (ints last: the T arrays stay aligned)
-template <typename T>
-size_t bid_lds_bytes(int m, int n, bool in_lds) {
-    size_t t = (size_t)2 * n + BID_NB * (BID_NB + 1) + 8;
-    if (in_lds) t += (size_t)n * (size_t)(m | 1);
-    return t * sizeof(T) + (size_t)n * sizeof(int);
-}
 
 // H_j applied to the trailing columns p = j+1 .. n-1, one wave per column, two columns per wave in flight; rows j + lane + 64 e
 // of the column in registers (NE * 64 >= m - j), then the ?laqp2 down-date of the column's partial norm
@@ -127,293 +122,6 @@ __device__ __forceinline__ void bid_apply(T *W, int ldw, int m, int n, int j, co
     }
 }
 
-// ---- the three stages of one factorization, shared by k_batched_id and both phases of k_batched_two_sided ------------------------
-// (m x n below is the matrix being factored: A for a column ID, C^T for the row side of a two-sided ID)
-
-// the initial column norms of the working copy W (m x n, column c at W + c * ldw) and the identity permutation
-template <typename T>
-__device__ __forceinline__ void bid_norms(const T *W, int ldw, int m, int n, T *vn1, T *vn2, int *jp, int wv, int lane) {
-    for (int c = wv; c < n; c += BID_WAVES) {
-        T acc = 0;
-        for (int i = lane; i < m; i += 64) { const T v = W[(size_t)c * ldw + i]; acc += v * v; }
-        acc = wave_sum_dpp(acc);
-        if (lane == 0) { const T nr = sqrt(acc); vn1[c] = nr; vn2[c] = nr; jp[c] = c; }
-    }
-    __syncthreads();
-}
-
-// working copy W[c * ldw + i] = at(i, c), read with the lanes along i (lanes_on_rows) or along c (the input's fast direction)
-template <typename T, typename At>
-__device__ __forceinline__ void bid_fill(T *W, int ldw, int m, int n, bool lanes_on_rows, At at, int wv, int lane) {
-    if (lanes_on_rows) {
-        for (int c = wv; c < n; c += BID_WAVES)
-            for (int i = lane; i < m; i += 64) W[(size_t)c * ldw + i] = at(i, c);
-    } else {
-        for (int i = wv; i < m; i += BID_WAVES)
-            for (int c = lane; c < n; c += 64) W[(size_t)c * ldw + i] = at(i, c);
-    }
-    __syncthreads();
-}
-
-// the working copy as the caller's entries stand, then the initial column norms and the identity permutation (the recompression kernels)
-template <typename T, typename At>
-__device__ __forceinline__ void bid_load(T *W, int ldw, int m, int n, bool lanes_on_rows, At at, T *vn1, T *vn2, int *jp, int wv, int lane) {
-    bid_fill(W, ldw, m, n, lanes_on_rows, at, wv, lane);
-    bid_norms(W, ldw, m, n, vn1, vn2, jp, wv, lane);
-}
-
-// bid_norms on a working copy of any scale: W is first brought to a largest magnitude in [1, 2) by the exact power of two 2^-e
-// (block_pow2_exponent, rc_device.hpp; e = 0 for a zero block and for one with a non-finite entry), so that neither these sums of squares
-// nor those of bid_qrcp and bid_apply leave the normal range.  One more pass over W before the first step, none inside the step loop.
-// Returns e: W holds 2^-e times the block, and only an output that carries the block's scale and is produced from W (the singular values
-// of k_batched_svd) multiplies 2^e back; pivots, ranks, Z, Q, U and V^T carry none, C, X and P are taken from the input itself.
-// stage: four elements no thread reads before the next barrier (red + 4).
-template <typename T>
-__device__ __forceinline__ int bid_norms_pow2(T *W, int ldw, int m, int n, T *vn1, T *vn2, int *jp, T *stage, int wv, int lane) {
-    T mx = 0;
-    for (int c = wv; c < n; c += BID_WAVES)
-        for (int i = lane; i < m; i += 64) mx = max(mx, pow2_key(W[(size_t)c * ldw + i]));
-    const int e = block_pow2_exponent(mx, stage, wv, lane);
-    const T sc = ldexp((T)1, -e);
-    for (int c = wv; c < n; c += BID_WAVES) {  // bid_norms' sums on the scaled entries; a wave rewrites the columns it read above
-        T acc = 0;
-        for (int i = lane; i < m; i += 64) {
-            const T v = W[(size_t)c * ldw + i] * sc;
-            W[(size_t)c * ldw + i] = v;
-            acc += v * v;
-        }
-        acc = wave_sum_dpp(acc);
-        if (lane == 0) { const T nr = sqrt(acc); vn1[c] = nr; vn2[c] = nr; jp[c] = c; }
-    }
-    __syncthreads();
-    return e;
-}
-
-// bid_load for a caller's block of any scale (the IDs and the SVD): the fill, then bid_norms_pow2.  Returns the block's exponent.
-template <typename T, typename At>
-__device__ __forceinline__ int bid_load_pow2(T *W, int ldw, int m, int n, bool lanes_on_rows, At at, T *vn1, T *vn2, int *jp, T *stage, int wv, int lane) {
-    bid_fill(W, ldw, m, n, lanes_on_rows, at, wv, lane);
-    return bid_norms_pow2(W, ldw, m, n, vn1, vn2, jp, stage, wv, lane);
-}
-
-// truncated pivoted QR of the working copy, at most k steps: pivots in jp (?geqp3's rule), R and the Householder vectors in W (LAPACK
-// format, physical column order).  Returns the rank: the first j < k with R_jj == 0 or (tol > 0 and |R_jj / R_00| < tol), else k.
-// FULL (the batched SVD): no stopping rule, all k steps are taken (an exactly zero pivot column is a step with H = I) and tau_j goes
-// to taus[j]; returns k.
-template <typename T, bool FULL = false>
-__device__ __forceinline__ int bid_qrcp(T *W, int ldw, int m, int n, int k, double tol, int *jp, T *vn1, T *vn2, T *red, int tid, int wv, int lane,
-                                        T *taus = nullptr) {
-    int r = k;
-    [[maybe_unused]] T r00 = 0;
-    for (int j = 0; j < k; ++j) {
-        if (wv == 0) {  // pivot: first maximum of the partial norms; NaN never wins (v > best), no valid index -> j
-            T best = (T)-1;
-            int bi = 0x7fffffff;
-            for (int p = j + lane; p < n; p += 64) {
-                const T v = fabs(vn1[p]);
-                if (v > best) { best = v; bi = p; }
-            }
-            const T mx = wave_max_dpp(best);
-            const int pv = wave_min_dpp(best == mx ? bi : 0x7fffffff);
-            const int pvt = (pv >= j && pv < n) ? pv : j;
-            if (lane == 0 && pvt != j) {  // dlaqp2: swap the indices, carry the norms of position j to pvt
-                const int t = jp[pvt]; jp[pvt] = jp[j]; jp[j] = t;
-                vn1[pvt] = vn1[j];
-                vn2[pvt] = vn2[j];
-            }
-        }
-        __syncthreads();
-        // ?larfg on column jp[j], rows j..m-1 (k_qr_pivot_reflect's formula)
-        T *col = W + (size_t)jp[j] * ldw;
-        const T alpha = col[j];
-        T acc = 0;
-        for (int i = j + 1 + tid; i < m; i += BID_THREADS) { const T v = col[i]; acc += v * v; }
-        acc = wave_sum_dpp(acc);
-        if (lane == 0) red[wv] = acc;
-        __syncthreads();  // also orders every thread's read of alpha before the write of beta below
-        const T xnorm = sqrt((red[0] + red[1]) + (red[2] + red[3]));
-        T beta = alpha, tj = 0;
-        if (xnorm != (T)0) {
-            beta = -copysign(hypot(alpha, xnorm), alpha);
-            const T scal = (T)1 / (alpha - beta);
-            for (int i = j + 1 + tid; i < m; i += BID_THREADS) col[i] *= scal;
-            tj = (beta - alpha) / beta;
-            if (tid == 0) col[j] = beta;
-        }
-        if constexpr (FULL) {
-            if (tid == 0) taus[j] = tj;
-        } else {
-            // R_jj = beta decides the rank (qr.rs:187-200 as a ratio; uniform across the workgroup)
-            if (j == 0) r00 = beta;
-            if (beta == (T)0 || (tol > 0.0 && (double)fabs(beta / r00) < tol)) { r = j; break; }
-        }
-        __syncthreads();
-        if (j + 1 < n) {
-            const int rem = m - j;
-            if (rem <= 128) bid_apply<T, 2>(W, ldw, m, n, j, jp, vn1, vn2, tj, wv, lane);
-            else if (rem <= 256) bid_apply<T, 4>(W, ldw, m, n, j, jp, vn1, vn2, tj, wv, lane);
-            else bid_apply<T, 8>(W, ldw, m, n, j, jp, vn1, vn2, tj, wv, lane);
-        }
-        __syncthreads();
-    }
-    __syncthreads();
-    return r;
-}
-
-// Z = [I | R11^-1 R12] P^T (k x n, rows r..k-1 zero) into Zb[i * zrs + c * zcs]: k_id_z's blocked back substitution with k -> r
-// (16 x 16 tiles of R11 staged in LDS, one thread per right-hand side), each column written straight to its final place
-template <typename T>
-__device__ __forceinline__ void bid_z(const T *W, int ldw, int n, int r, int k, const int *jp, T (*tile)[BID_NB + 1], T *Zb, int64_t zrs, int64_t zcs, int tid) {
-    const int nblk = (r + BID_NB - 1) / BID_NB;
-    const int ti = tid / BID_NB, tk = tid % BID_NB;
-    for (int q0 = 0; q0 < n; q0 += BID_THREADS) {
-        const int p = q0 + tid;  // position in the pivoted order
-        const bool inside = p < n;
-        const int dc = inside ? jp[p] : 0;  // where column p of [I | R11^-1 R12] goes
-        const bool active = inside && p >= r;
-        T *zc = Zb + (int64_t)dc * zcs;
-        if (inside) {
-            if (p < r)
-                for (int i = 0; i < k; ++i) zc[i * zrs] = (i == p) ? (T)1 : (T)0;
-            else
-                for (int i = r; i < k; ++i) zc[i * zrs] = (T)0;
-        }
-        const T *bcol = W + (size_t)dc * ldw;  // R12[:, p]: rows 0 .. r-1 of the physical column
-        for (int bi = nblk - 1; bi >= 0; --bi) {
-            const int r0 = bi * BID_NB;
-            T acc[BID_NB];
-#pragma unroll
-            for (int ii = 0; ii < BID_NB; ++ii) acc[ii] = (active && r0 + ii < r) ? bcol[r0 + ii] : (T)0;
-            for (int bj = nblk - 1; bj >= bi; --bj) {
-                const int c0 = bj * BID_NB;
-                __syncthreads();
-                {
-                    const int i = r0 + ti, l = c0 + tk;
-                    tile[ti][tk] = (i < r && l < r && i <= l) ? W[(size_t)jp[l] * ldw + i] : (T)0;
-                }
-                __syncthreads();
-                if (bj > bi) {
-                    T x[BID_NB];
-#pragma unroll
-                    for (int jj = 0; jj < BID_NB; ++jj) x[jj] = (active && c0 + jj < r) ? zc[(c0 + jj) * zrs] : (T)0;  // this thread's own finished block
-#pragma unroll
-                    for (int jj = 0; jj < BID_NB; ++jj)
-#pragma unroll
-                        for (int ii = 0; ii < BID_NB; ++ii) acc[ii] -= tile[ii][jj] * x[jj];
-                } else {
-#pragma unroll
-                    for (int ii = BID_NB - 1; ii >= 0; --ii) {
-                        if (r0 + ii < r) {
-                            acc[ii] /= tile[ii][ii];
-#pragma unroll
-                            for (int i2 = 0; i2 < ii; ++i2) acc[i2] -= tile[i2][ii] * acc[ii];
-                        }
-                    }
-                }
-            }
-            if (active) {
-#pragma unroll
-                for (int ii = 0; ii < BID_NB; ++ii)
-                    if (r0 + ii < r) zc[(r0 + ii) * zrs] = acc[ii];
-            }
-        }
-    }
-}
-
-template <typename T, bool IN_LDS>
-__global__ __launch_bounds__(BID_THREADS) void k_batched_id(Mat<T> a, int64_t abs, int count, int k, double tol, Mat<T> cm, int64_t cbs, Mat<T> z,
-                                                            int64_t zbs, int64_t *__restrict__ col_ind, int64_t *__restrict__ ranks, T *__restrict__ ws) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    const int m = (int)a.rows, n = (int)a.cols;
-    const int ldw = IN_LDS ? (m | 1) : m;
-    T *lds = reinterpret_cast<T *>(smem_raw);
-    T *W = IN_LDS ? lds : ws + (size_t)blockIdx.x * (size_t)m * (size_t)n;
-    T *vn1 = lds + (IN_LDS ? (size_t)n * ldw : 0);
-    T *vn2 = vn1 + n;
-    T(*tile)[BID_NB + 1] = reinterpret_cast<T(*)[BID_NB + 1]>(vn2 + n);
-    T *red = vn2 + n + BID_NB * (BID_NB + 1);
-    int *jp = reinterpret_cast<int *>(red + 8);
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-
-    for (int b = blockIdx.x; b < count; b += gridDim.x) {
-        const T *__restrict__ A = a.p + (int64_t)b * abs;
-        bid_load_pow2(W, ldw, m, n, a.rs <= a.cs, [&](int i, int c) { return A[i * a.rs + c * a.cs]; }, vn1, vn2, jp, red + 4, wv, lane);
-        const int r = bid_qrcp(W, ldw, m, n, k, tol, jp, vn1, vn2, red, tid, wv, lane);
-
-        // ---- outputs: permutation, rank, C, Z -------------------------------------------------------------------
-        for (int p = tid; p < n; p += BID_THREADS) col_ind[(int64_t)b * n + p] = jp[p];
-        if (tid == 0) ranks[b] = r;
-        T *Cb = cm.p + (int64_t)b * cbs;
-        for (int j = wv; j < k; j += BID_WAVES) {
-            const T *src = A + (int64_t)jp[j] * a.cs;
-            for (int i = lane; i < m; i += 64) Cb[i * cm.rs + j * cm.cs] = j < r ? src[i * a.rs] : (T)0;
-        }
-        bid_z(W, ldw, n, r, k, jp, tile, z.p + (int64_t)b * zbs, z.rs, z.cs, tid);
-        __syncthreads();  // W, jp and the norms are rewritten by the next matrix
-    }
-}
-
-// dynamic LDS of the two-sided kernel: [W: the larger of phase 1's n x (m|1) and phase 2's m x (k|1), LDS variant only]
-// vn1[max(m, n)] vn2[max(m, n)] tile[16 x 17] red[8] | jp[n] jp2[m]
-__host__ __device__ inline size_t bts_w_elems(int m, int n, int k) {
-    const size_t w1 = (size_t)n * (size_t)(m | 1), w2 = (size_t)m * (size_t)(k | 1);
-    return w1 > w2 ? w1 : w2;
-}
-template <typename T>
-size_t bts_lds_bytes(int m, int n, int k, bool in_lds) {
-    size_t t = (size_t)2 * std::max(m, n) + BID_NB * (BID_NB + 1) + 8;
-    if (in_lds) t += bts_w_elems(m, n, k);
-    return t * sizeof(T) + (size_t)(m + n) * sizeof(int);
-}
-
-// Two-sided ID A ~ C X R per matrix: phase 1 is k_batched_id's column ID (R = its Z, col_ind, the rank r); phase 2 is the column
-// ID of C^T = A[:, col_ind[:r]]^T (r x m) at rank r with tol = 0, by the same three stages: its permutation is row_ind and its Z,
-// written through c's transposed view, is c = Z2^T; X = A[row_ind[:r], col_ind[:r]] is gathered from the input.  In the workspace
-// variant phase 2's m x r copy (ldw = r) fits the m x n slot; the LDS variant reserves the larger of the two phases' needs.
-template <typename T, bool IN_LDS>
-__global__ __launch_bounds__(BID_THREADS) void k_batched_two_sided(Mat<T> a, int64_t abs, int count, int k, double tol, Mat<T> cm, int64_t cbs,
-                                                                   Mat<T> xm, int64_t xbs, Mat<T> z, int64_t zbs, int64_t *__restrict__ row_ind,
-                                                                   int64_t *__restrict__ col_ind, int64_t *__restrict__ ranks, T *__restrict__ ws) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    const int m = (int)a.rows, n = (int)a.cols, mn = m > n ? m : n;
-    const int ldw = IN_LDS ? (m | 1) : m;
-    T *lds = reinterpret_cast<T *>(smem_raw);
-    T *W = IN_LDS ? lds : ws + (size_t)blockIdx.x * (size_t)m * (size_t)n;
-    T *vn1 = lds + (IN_LDS ? bts_w_elems(m, n, k) : 0);
-    T *vn2 = vn1 + mn;
-    T(*tile)[BID_NB + 1] = reinterpret_cast<T(*)[BID_NB + 1]>(vn2 + mn);
-    T *red = vn2 + mn + BID_NB * (BID_NB + 1);
-    int *jp = reinterpret_cast<int *>(red + 8);  // phase 1's column permutation: read until X is gathered
-    int *jp2 = jp + n;                           // phase 2's row permutation
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-
-    for (int b = blockIdx.x; b < count; b += gridDim.x) {
-        const T *__restrict__ A = a.p + (int64_t)b * abs;
-        // ---- phase 1: column ID of A -> r (= Z), col_ind, the rank --------------------------------------------------
-        bid_load_pow2(W, ldw, m, n, a.rs <= a.cs, [&](int i, int c) { return A[i * a.rs + c * a.cs]; }, vn1, vn2, jp, red + 4, wv, lane);
-        const int r = bid_qrcp(W, ldw, m, n, k, tol, jp, vn1, vn2, red, tid, wv, lane);
-        for (int p = tid; p < n; p += BID_THREADS) col_ind[(int64_t)b * n + p] = jp[p];
-        if (tid == 0) ranks[b] = r;
-        bid_z(W, ldw, n, r, k, jp, tile, z.p + (int64_t)b * zbs, z.rs, z.cs, tid);
-        __syncthreads();  // W and the norms are phase 2's from here
-
-        // ---- phase 2: column ID of C^T (r x m), W2[p][i] = A[p, col_ind[i]] -> c = Z2^T, row_ind ------------------------
-        const int ldw2 = IN_LDS ? (r | 1) : r;
-        bid_load_pow2(W, ldw2, r, m, a.cs < a.rs, [&](int i, int p) { return A[p * a.rs + jp[i] * a.cs]; }, vn1, vn2, jp2, red + 4, wv, lane);
-        const int r2 = bid_qrcp(W, ldw2, r, m, r, 0.0, jp2, vn1, vn2, red, tid, wv, lane);  // r2 < r only on an exactly zero pivot
-        for (int p = tid; p < m; p += BID_THREADS) row_ind[(int64_t)b * m + p] = jp2[p];
-        bid_z(W, ldw2, m, r2, k, jp2, tile, cm.p + (int64_t)b * cbs, cm.cs, cm.rs, tid);  // Z2 (k x m) through c's transposed view
-
-        // ---- X = A[row_ind[:r], col_ind[:r]], rows and columns r..k-1 zero --------------------------------------------------
-        T *Xb = xm.p + (int64_t)b * xbs;
-        for (int j = wv; j < k; j += BID_WAVES) {
-            const T *src = A + (int64_t)jp[j] * a.cs;
-            for (int i = lane; i < k; i += 64) Xb[i * xm.rs + j * xm.cs] = (i < r && j < r) ? src[jp2[i] * a.rs] : (T)0;
-        }
-        __syncthreads();  // W, jp, jp2 and the norms are rewritten by the next matrix
-    }
-}
-
 // ---- batched truncated SVD (rc_svd_rank_batched_*) -----------------------------------------------------------------------------
 // Per matrix, in the tall orientation M x N (N = min(m, n); a wide matrix is read through its transposed view): the pivoted QR of
 // bid_qrcp run to N steps (W P = Q R, reflectors kept), one-sided Jacobi on the N x N core G = R^T with the rotations accumulated
@@ -461,32 +169,6 @@ __device__ __forceinline__ void bsv_round(T *G, int ldg, T *J, int ldj, int N, i
         }
     }
     if (ll == 0 && jacobi_rotation_was_large(app, aqq, apq2, s, tol)) *flag = 2;  // plain store: every writer writes 2
-}
-
-// one-sided Jacobi of the N x N core G (columns ldg apart) with the rotations accumulated in J (ldj); round-robin pairs, 16 lanes per pair, the 16
-// groups of the workgroup walk the N / 2 pair slots of a round.  Returns false when kMaxSweeps ran out before a quiet sweep.
-template <typename T, int NE>
-__device__ __forceinline__ bool bsv_jacobi(T *G, int ldg, T *J, int ldj, int N, int tid, int *flag) {
-    const int ll = tid & 15, grp = tid >> 4;
-    constexpr int NGRP = BID_THREADS / 16;
-    const int N2 = (N + 1) & ~1, npairs = N2 / 2;
-    const T tol = sqrt((T)N) * JEps<T>::eps(), tol2 = tol * tol;
-    for (int sweep = 0; sweep < kMaxSweeps; ++sweep) {
-        if (tid == 0) *flag = 0;
-        __syncthreads();
-        for (int r = 0; r < N2 - 1; ++r) {
-            for (int pi = grp; pi < npairs; pi += NGRP) {
-                int p, q;
-                rr_pair(N2, r, pi, p, q);
-                if (q < N) bsv_round<T, NE>(G, ldg, J, ldj, N, p, q, tol, tol2, ll, flag);  // q == N: the dummy column of an odd N
-            }
-            __syncthreads();  // the pairs of a round are disjoint; the next round re-pairs the columns
-        }
-        const int rotated = *flag;
-        __syncthreads();
-        if (rotated < 2) return true;
-    }
-    return false;
 }
 
 // sign of a column held by one wave (value x[e] at output row orow(e)): -1 when its largest-|.| entry (the first such in output row
@@ -741,37 +423,6 @@ __host__ __device__ inline size_t brc_ws_elems(int m, int n, int K, bool l_lds, 
 __host__ __device__ inline size_t brt_ws_elems(int m, int n, int K, bool l_lds, bool r_lds, bool v_lds) {
     if (m <= BRT_H) return brc_ws_elems(m, n, K, l_lds, r_lds, v_lds);
     return (size_t)brt_stages(m, K) * brt_stage_elems(K) + brc_ws_elems(0, n, K, true, r_lds, v_lds);
-}
-
-// one stage's stack into W (pitch ldw, hs rows): rows 0 .. top - 1 of position p's column are R[0 .. p, p] of the previous stage's copy Wp
-// (the same pitch and physical columns) and zeros, rows top .. hs - 1 are at(i - top, c); then the column norms by position (bid_norms'
-// sums) with jp kept as it is.  top == 0 (stage 0): Wp is not read.
-template <typename T, typename At>
-__device__ __forceinline__ void brt_stack_load(T *W, int ldw, const T *Wp, int top, int hs, int q, bool lanes_on_rows, At at, T *vn1, T *vn2, const int *jp,
-                                               int wv, int lane) {
-    if (top) {
-        for (int p = wv; p < q; p += BID_WAVES) {
-            const size_t col = (size_t)jp[p] * ldw;
-            for (int i = lane; i < top; i += 64) W[col + i] = i <= p ? Wp[col + i] : (T)0;
-        }
-    }
-    const int rows = hs - top;
-    if (lanes_on_rows) {
-        for (int c = wv; c < q; c += BID_WAVES)
-            for (int i = lane; i < rows; i += 64) W[(size_t)c * ldw + top + i] = at(i, c);
-    } else {
-        for (int i = wv; i < rows; i += BID_WAVES)
-            for (int c = lane; c < q; c += 64) W[(size_t)c * ldw + top + i] = at(i, c);
-    }
-    __syncthreads();
-    for (int p = wv; p < q; p += BID_WAVES) {
-        const T *col = W + (size_t)jp[p] * ldw;
-        T acc = 0;
-        for (int i = lane; i < hs; i += 64) { const T v = col[i]; acc += v * v; }
-        acc = wave_sum_dpp(acc);
-        if (lane == 0) { const T nr = sqrt(acc); vn1[p] = nr; vn2[p] = nr; }
-    }
-    __syncthreads();
 }
 
 // x <- H_0 .. H_{N-1} x for a column held by one wave (row lane + 64 e in x[e], M rows): bsv_form_u's reflector loop as a routine of its
@@ -1449,18 +1100,6 @@ __global__ __launch_bounds__(BID_THREADS, 2) void k_batched_range_step(BrsArgs<T
 
 // ---- the plans: where each launcher's movable buffers live, as pure functions of the shapes (rc_batched_launch.hpp) -------------------------
 
-// column ID: the working copy W (m x n) in LDS when it fits, else in the workgroup's slot of the grid-bounded workspace
-template <typename T>
-BatchedPlan<bool> bid_plan(int m, int n) {
-    return batched_lds_or_ws([&](bool w_lds) { return bid_lds_bytes<T>(m, n, w_lds); }, (size_t)m * (size_t)n * sizeof(T), "column_id_rank_batched");
-}
-
-// two-sided ID: the same rule, LDS or workspace chosen from the larger need of the two phases
-template <typename T>
-BatchedPlan<bool> bts_plan(int m, int n, int k) {
-    return batched_lds_or_ws([&](bool w_lds) { return bts_lds_bytes<T>(m, n, k, w_lds); }, (size_t)m * (size_t)n * sizeof(T), "two_sided_id_rank_batched");
-}
-
 // SVD, M x N the work orientation: the working copy W (M x N) and V (N x N) in LDS when they fit next to the core (W only with V),
 // otherwise in the workgroup's slot; the core G always fits (N <= 128: 128 KiB in f64).  Most in LDS first; the core's column pitch is
 // k_jacobi_lds's conflict-free one (16 modulo 32 elements) whenever the plan fits with it, else N | 1.
@@ -1561,28 +1200,17 @@ int batched_kernel_cap(int device, const void *kern) {
     return last_scratch = it->second;
 }
 
+// the two IDs: plans, kernels and launcher bodies in batched_stages.hpp, one text for real and complex elements
 template <typename T>
 void batched_column_id(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int64_t k, double tol, Mat<T> cm, int64_t cbs, Mat<T> z, int64_t zbs,
                        int64_t *col_ind, int64_t *ranks) {
-    const int m = (int)a.rows, n = (int)a.cols;
-    if (count <= 0) return;
-    const auto plan = bid_plan<T>(m, n);
-    const auto lch = batched_prepare(c, plan.at ? k_batched_id<T, true> : k_batched_id<T, false>, "column_id_rank_batched", plan.lds, plan.ws, count);
-    ProfScope ps(c, "op:batched_column_id %dx%d k=%lld count=%d grid=%lld slots=%lld plan=W:%s", m, n, (long long)k, (int)count, (long long)lch.grid,
-                 (long long)lch.slots, plan.at ? "lds" : "ws");
-    lch.launch(a, abs, (int)count, (int)k, tol, cm, cbs, z, zbs, col_ind, ranks, lch.template workspace<T>());
+    bid_launch<T>(c, a, abs, count, k, tol, cm, cbs, z, zbs, col_ind, ranks);
 }
 
 template <typename T>
 void batched_two_sided_id(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int64_t k, double tol, Mat<T> cm, int64_t cbs, Mat<T> x, int64_t xbs,
                           Mat<T> z, int64_t zbs, int64_t *row_ind, int64_t *col_ind, int64_t *ranks) {
-    const int m = (int)a.rows, n = (int)a.cols;
-    if (count <= 0) return;
-    const auto plan = bts_plan<T>(m, n, (int)k);
-    const auto lch = batched_prepare(c, plan.at ? k_batched_two_sided<T, true> : k_batched_two_sided<T, false>, "two_sided_id_rank_batched", plan.lds, plan.ws, count);
-    ProfScope ps(c, "op:batched_two_sided_id %dx%d k=%lld count=%d grid=%lld slots=%lld plan=W:%s", m, n, (long long)k, (int)count, (long long)lch.grid,
-                 (long long)lch.slots, plan.at ? "lds" : "ws");
-    lch.launch(a, abs, (int)count, (int)k, tol, cm, cbs, x, xbs, z, zbs, row_ind, col_ind, ranks, lch.template workspace<T>());
+    bts_launch<T>(c, a, abs, count, k, tol, cm, cbs, x, xbs, z, zbs, row_ind, col_ind, ranks);
 }
 
 template <typename T>

@@ -6,8 +6,11 @@
 // of their power iteration (rc_sketch_range_step_complex_batched_c64 / _c32, k_batched_range_step_c below).
 //
 // The structure of kernels_batched_id.hip (one persistent workgroup of 256 threads per matrix, the same three device stages, the same
-// grid and workspace rule, and the launch path of rc_batched_launch.hpp) with the complex arithmetic of the lone complex path in
-// rc_complex.hip:
+// grid and workspace rule, and the launch path of rc_batched_launch.hpp).  The stages that read the same for real and complex elements
+// are that file's too: they stand once in batched_stages.hpp, which this file instantiates for cplx<double> and cplx<float> (the fill,
+// the norms, bid_qrcp, bid_z, k_batched_id and k_batched_two_sided with their plans and launcher bodies, bsv_jacobi, brt_stack_load).
+// Here stay the complex family's own routines (bic_apply, bsc_round, bsc_phase, the form_u routines, the core products) and the SVD,
+// recompression, sketch and range-step kernels.  The arithmetic is that of the lone complex path in rc_complex.hip:
 //   * interleaved (re, im) data (cplx<R>, CV<R> and their arithmetic: rc_cplx.hpp); the partial norms vn1 / vn2 are real, W and the tile complex;
 //   * ?larfg for complex (k_c_qr_pivot_reflect): beta = -copysign(lapy3(alpha.re, alpha.im, xnorm), alpha.re) is real, tau complex,
 //     the scale 1 / (alpha - beta) by Smith division; H = I only when xnorm == 0 and alpha.im == 0;
@@ -26,6 +29,7 @@
 // Every operation below commutes exactly with negating all imaginary parts (round to nearest is sign-symmetric, and each real part
 // is even, each imaginary part odd in the imaginary inputs), so conj(A) gives the same permutations and ranks and the conjugate
 // of every factor, bit for bit.
+#include "batched_stages.hpp"
 #include "rc_batched_launch.hpp"
 #include "rc_common.hpp"
 #include "rc_cplx.hpp"
@@ -35,18 +39,6 @@
 namespace rc {
 
 namespace {
-
-constexpr int BIC_THREADS = BATCHED_THREADS;
-constexpr int BIC_WAVES = BIC_THREADS / 64;
-constexpr int BIC_NB = 8;  // back-substitution tile
-
-// dynamic LDS: [W: m x ldw complex, LDS variant only] tile[8 x 9] complex | vn1[n] vn2[n] red[8] real | jp[n]
-template <typename R>
-size_t bic_lds_bytes(int m, int n, bool in_lds) {
-    size_t c = (size_t)BIC_NB * (BIC_NB + 1);
-    if (in_lds) c += (size_t)n * (size_t)(m | 1);
-    return c * sizeof(cplx<R>) + ((size_t)2 * n + 8) * sizeof(R) + (size_t)n * sizeof(int);
-}
 
 // H_j^H = I - conj(tau) v v^H applied to the trailing columns p = j+1 .. n-1, one wave per column; rows j + lane + 64 e of the column
 // in registers (NE * 64 >= m - j), then the ?laqp2 down-date of the column's partial norm with |x_j|
@@ -65,7 +57,7 @@ __device__ __forceinline__ void bic_apply(cplx<R> *W, int ldw, int m, int n, int
     }
     const bool reflect = tj.re != (R)0 || tj.im != (R)0;  // tau == 0: H = I
     const cplx<R> ctj = cj(tj);
-    for (int p = j + 1 + wv; p < n; p += BIC_WAVES) {
+    for (int p = j + 1 + wv; p < n; p += BID_WAVES) {
         cplx<R> *xc = W + (size_t)jp[p] * ldw + j;
         cplx<R> x[NE];
 #pragma unroll
@@ -115,304 +107,9 @@ __device__ __forceinline__ void bic_apply(cplx<R> *W, int ldw, int m, int n, int
     }
 }
 
-// ---- the three stages of one factorization, shared by k_batched_id_c and both phases of k_batched_two_sided_c -----------------------
-// (m x n below is the matrix being factored: A for a column ID, C^H for the row side of a two-sided ID)
-
-// the initial (real) column norms of the working copy W (m x n, column c at W + c * ldw) and the identity permutation
-template <typename R>
-__device__ __forceinline__ void bic_norms(const cplx<R> *W, int ldw, int m, int n, R *vn1, R *vn2, int *jp, int wv, int lane) {
-    for (int c = wv; c < n; c += BIC_WAVES) {
-        R acc = 0;
-        for (int i = lane; i < m; i += 64) acc += abs2(W[(size_t)c * ldw + i]);
-        acc = wave_sum_dpp(acc);
-        if (lane == 0) { const R nr = sqrt(acc); vn1[c] = nr; vn2[c] = nr; jp[c] = c; }
-    }
-    __syncthreads();
-}
-
-// working copy W[c * ldw + i] = at(i, c), read with the lanes along i (lanes_on_rows) or along c (the input's fast direction)
-template <typename R, typename At>
-__device__ __forceinline__ void bic_fill(cplx<R> *W, int ldw, int m, int n, bool lanes_on_rows, At at, int wv, int lane) {
-    if (lanes_on_rows) {
-        for (int c = wv; c < n; c += BIC_WAVES)
-            for (int i = lane; i < m; i += 64) W[(size_t)c * ldw + i] = at(i, c);
-    } else {
-        for (int i = wv; i < m; i += BIC_WAVES)
-            for (int c = lane; c < n; c += 64) W[(size_t)c * ldw + i] = at(i, c);
-    }
-    __syncthreads();
-}
-
-// the working copy as the caller's entries stand, then the initial column norms and the identity permutation (the recompression kernels)
-template <typename R, typename At>
-__device__ __forceinline__ void bic_load(cplx<R> *W, int ldw, int m, int n, bool lanes_on_rows, At at, R *vn1, R *vn2, int *jp, int wv, int lane) {
-    bic_fill(W, ldw, m, n, lanes_on_rows, at, wv, lane);
-    bic_norms(W, ldw, m, n, vn1, vn2, jp, wv, lane);
-}
-
-// bic_norms on a working copy of any scale, bid_norms_pow2's scheme (kernels_batched_id.hip): W is first multiplied by the exact power
-// of two 2^-e that brings its largest real or imaginary part (within sqrt 2 of the largest modulus, and never overflowing) into [1, 2);
-// e = 0 for a zero block and for one with a non-finite part.  Returns e.  stage: four elements no thread reads before the next barrier.
-template <typename R>
-__device__ __forceinline__ int bic_norms_pow2(cplx<R> *W, int ldw, int m, int n, R *vn1, R *vn2, int *jp, R *stage, int wv, int lane) {
-    R mx = 0;
-    for (int c = wv; c < n; c += BIC_WAVES)
-        for (int i = lane; i < m; i += 64) {
-            const cplx<R> v = W[(size_t)c * ldw + i];
-            mx = max(mx, max(pow2_key(v.re), pow2_key(v.im)));
-        }
-    const int e = block_pow2_exponent(mx, stage, wv, lane);
-    const R sc = ldexp((R)1, -e);
-    for (int c = wv; c < n; c += BIC_WAVES) {  // bic_norms' sums on the scaled entries; a wave rewrites the columns it read above
-        R acc = 0;
-        for (int i = lane; i < m; i += 64) {
-            const cplx<R> w = W[(size_t)c * ldw + i];
-            const cplx<R> v{w.re * sc, w.im * sc};
-            W[(size_t)c * ldw + i] = v;
-            acc += abs2(v);
-        }
-        acc = wave_sum_dpp(acc);
-        if (lane == 0) { const R nr = sqrt(acc); vn1[c] = nr; vn2[c] = nr; jp[c] = c; }
-    }
-    __syncthreads();
-    return e;
-}
-
-// bic_load for a caller's block of any scale (the IDs and the SVD): the fill, then bic_norms_pow2.  Returns the block's exponent.
-template <typename R, typename At>
-__device__ __forceinline__ int bic_load_pow2(cplx<R> *W, int ldw, int m, int n, bool lanes_on_rows, At at, R *vn1, R *vn2, int *jp, R *stage, int wv,
-                                             int lane) {
-    bic_fill(W, ldw, m, n, lanes_on_rows, at, wv, lane);
-    return bic_norms_pow2(W, ldw, m, n, vn1, vn2, jp, stage, wv, lane);
-}
-
-// truncated pivoted QR of the working copy, at most k steps: pivots in jp (?geqp3's rule), R and the Householder vectors in W (LAPACK
-// format, physical column order).  Returns the rank: the first j < k with R_jj == 0 or (tol > 0 and |R_jj / R_00| < tol), else k.
-// FULL (the batched SVD): no stopping rule, all k steps are taken (an exactly zero pivot column is a step with H = I) and the complex
-// tau_j goes to taus[j]; returns k.
-template <typename R, bool FULL = false>
-__device__ __forceinline__ int bic_qrcp(cplx<R> *W, int ldw, int m, int n, int k, double tol, int *jp, R *vn1, R *vn2, R *red, int tid, int wv, int lane,
-                                        cplx<R> *taus = nullptr) {
-    int r = k;
-    [[maybe_unused]] R r00 = 0;
-    for (int j = 0; j < k; ++j) {
-        if (wv == 0) {  // pivot: first maximum of the partial norms; NaN never wins (v > best), no valid index -> j
-            R best = (R)-1;
-            int bi = 0x7fffffff;
-            for (int p = j + lane; p < n; p += 64) {
-                const R v = fabs(vn1[p]);
-                if (v > best) { best = v; bi = p; }
-            }
-            const R mx = wave_max_dpp(best);
-            const int pv = wave_min_dpp(best == mx ? bi : 0x7fffffff);
-            const int pvt = (pv >= j && pv < n) ? pv : j;
-            if (lane == 0 && pvt != j) {  // zlaqp2: swap the indices, carry the norms of position j to pvt
-                const int t = jp[pvt]; jp[pvt] = jp[j]; jp[j] = t;
-                vn1[pvt] = vn1[j];
-                vn2[pvt] = vn2[j];
-            }
-        }
-        __syncthreads();
-        // ?larfg for complex on column jp[j], rows j..m-1 (k_c_qr_pivot_reflect's formula)
-        cplx<R> *col = W + (size_t)jp[j] * ldw;
-        const cplx<R> alpha = col[j];
-        R acc = 0;
-        for (int i = j + 1 + tid; i < m; i += BIC_THREADS) acc += abs2(col[i]);
-        acc = wave_sum_dpp(acc);
-        if (lane == 0) red[wv] = acc;
-        __syncthreads();  // also orders every thread's read of alpha before the write of beta below
-        const R ssq = (red[0] + red[1]) + (red[2] + red[3]);
-        const R xnorm = sqrt(ssq);
-        R beta = alpha.re;
-        cplx<R> tj = czero<R>();
-        if (xnorm != (R)0 || alpha.im != (R)0) {
-            beta = -copysign(sqrt(alpha.re * alpha.re + alpha.im * alpha.im + ssq), alpha.re);  // ?lapy3
-            const cplx<R> scal = cdiv(cone<R>(), cplx<R>{alpha.re - beta, alpha.im});
-            for (int i = j + 1 + tid; i < m; i += BIC_THREADS) col[i] = col[i] * scal;
-            tj = cplx<R>{(beta - alpha.re) / beta, -alpha.im / beta};
-            if (tid == 0) col[j] = cplx<R>{beta, (R)0};
-        }
-        if constexpr (FULL) {
-            if (tid == 0) taus[j] = tj;
-        } else {
-            // R_jj = beta (real) decides the rank (qr.rs:187-200 as a ratio; uniform across the workgroup)
-            if (j == 0) r00 = beta;
-            if (beta == (R)0 || (tol > 0.0 && (double)fabs(beta / r00) < tol)) { r = j; break; }
-        }
-        __syncthreads();
-        if (j + 1 < n) {
-            const int rem = m - j;
-            if (rem <= 128) bic_apply<R, 2>(W, ldw, m, n, j, jp, vn1, vn2, tj, wv, lane);
-            else if (rem <= 256) bic_apply<R, 4>(W, ldw, m, n, j, jp, vn1, vn2, tj, wv, lane);
-            else bic_apply<R, 8>(W, ldw, m, n, j, jp, vn1, vn2, tj, wv, lane);
-        }
-        __syncthreads();
-    }
-    __syncthreads();
-    return r;
-}
-
-// Z = [I | R11^-1 R12] P^T (k x n, rows r..k-1 zero) into Zb[i * zrs + c * zcs], or its conjugate when CONJ (the row side's Z2^H):
-// blocked back substitution with k -> r (8 x 8 tiles of R11 staged in LDS, one thread per right-hand side, complex division on the
-// diagonal), each column written straight to its final place
-template <typename R, bool CONJ>
-__device__ __forceinline__ void bic_z(const cplx<R> *W, int ldw, int n, int r, int k, const int *jp, cplx<R> (*tile)[BIC_NB + 1], cplx<R> *Zb, int64_t zrs,
-                                      int64_t zcs, int tid) {
-    const int nblk = (r + BIC_NB - 1) / BIC_NB;
-    const int ti = tid / BIC_NB, tk = tid % BIC_NB;
-    auto out = [](cplx<R> v) { return CONJ ? cj(v) : v; };  // its own inverse
-    for (int q0 = 0; q0 < n; q0 += BIC_THREADS) {
-        const int p = q0 + tid;  // position in the pivoted order
-        const bool inside = p < n;
-        const int dc = inside ? jp[p] : 0;  // where column p of [I | R11^-1 R12] goes
-        const bool active = inside && p >= r;
-        cplx<R> *zc = Zb + (int64_t)dc * zcs;
-        if (inside) {
-            if (p < r)
-                for (int i = 0; i < k; ++i) zc[i * zrs] = (i == p) ? cone<R>() : czero<R>();
-            else
-                for (int i = r; i < k; ++i) zc[i * zrs] = czero<R>();
-        }
-        const cplx<R> *bcol = W + (size_t)dc * ldw;  // R12[:, p]: rows 0 .. r-1 of the physical column
-        for (int bi = nblk - 1; bi >= 0; --bi) {
-            const int r0 = bi * BIC_NB;
-            cplx<R> acc[BIC_NB];
-#pragma unroll
-            for (int ii = 0; ii < BIC_NB; ++ii) acc[ii] = (active && r0 + ii < r) ? bcol[r0 + ii] : czero<R>();
-            for (int bj = nblk - 1; bj >= bi; --bj) {
-                const int c0 = bj * BIC_NB;
-                __syncthreads();
-                if (ti < BIC_NB) {
-                    const int i = r0 + ti, l = c0 + tk;
-                    tile[ti][tk] = (i < r && l < r && i <= l) ? W[(size_t)jp[l] * ldw + i] : czero<R>();
-                }
-                __syncthreads();
-                if (bj > bi) {
-                    cplx<R> x[BIC_NB];
-#pragma unroll
-                    for (int jj = 0; jj < BIC_NB; ++jj) x[jj] = (active && c0 + jj < r) ? out(zc[(c0 + jj) * zrs]) : czero<R>();  // own finished block
-#pragma unroll
-                    for (int jj = 0; jj < BIC_NB; ++jj)
-#pragma unroll
-                        for (int ii = 0; ii < BIC_NB; ++ii) acc[ii] = acc[ii] - tile[ii][jj] * x[jj];
-                } else {
-#pragma unroll
-                    for (int ii = BIC_NB - 1; ii >= 0; --ii) {
-                        if (r0 + ii < r) {
-                            acc[ii] = cdiv(acc[ii], tile[ii][ii]);
-#pragma unroll
-                            for (int i2 = 0; i2 < ii; ++i2) acc[i2] = acc[i2] - tile[i2][ii] * acc[ii];
-                        }
-                    }
-                }
-            }
-            if (active) {
-#pragma unroll
-                for (int ii = 0; ii < BIC_NB; ++ii)
-                    if (r0 + ii < r) zc[(r0 + ii) * zrs] = out(acc[ii]);
-            }
-        }
-    }
-}
-
-template <typename R, bool IN_LDS>
-__global__ __launch_bounds__(BIC_THREADS) void k_batched_id_c(CV<R> a, int64_t abs, int count, int k, double tol, CV<R> cm, int64_t cbs,
-                                                              CV<R> z, int64_t zbs, int64_t *__restrict__ col_ind, int64_t *__restrict__ ranks,
-                                                              cplx<R> *__restrict__ ws) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    const int m = (int)a.rows, n = (int)a.cols;
-    const int ldw = IN_LDS ? (m | 1) : m;
-    cplx<R> *lds = reinterpret_cast<cplx<R> *>(smem_raw);
-    cplx<R> *W = IN_LDS ? lds : ws + (size_t)blockIdx.x * (size_t)m * (size_t)n;
-    cplx<R>(*tile)[BIC_NB + 1] = reinterpret_cast<cplx<R>(*)[BIC_NB + 1]>(lds + (IN_LDS ? (size_t)n * ldw : 0));
-    R *vn1 = reinterpret_cast<R *>(lds + (IN_LDS ? (size_t)n * ldw : 0) + BIC_NB * (BIC_NB + 1));
-    R *vn2 = vn1 + n;
-    R *red = vn2 + n;
-    int *jp = reinterpret_cast<int *>(red + 8);
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-
-    for (int b = blockIdx.x; b < count; b += gridDim.x) {
-        const cplx<R> *__restrict__ A = a.p + (int64_t)b * abs;
-        bic_load_pow2(W, ldw, m, n, a.rs <= a.cs, [&](int i, int c) { return A[i * a.rs + c * a.cs]; }, vn1, vn2, jp, red + 4, wv, lane);
-        const int r = bic_qrcp(W, ldw, m, n, k, tol, jp, vn1, vn2, red, tid, wv, lane);
-
-        // ---- outputs: permutation, rank, C, Z -------------------------------------------------------------------
-        for (int p = tid; p < n; p += BIC_THREADS) col_ind[(int64_t)b * n + p] = jp[p];
-        if (tid == 0) ranks[b] = r;
-        cplx<R> *Cb = cm.p + (int64_t)b * cbs;
-        for (int j = wv; j < k; j += BIC_WAVES) {
-            const cplx<R> *src = A + (int64_t)jp[j] * a.cs;
-            for (int i = lane; i < m; i += 64) Cb[i * cm.rs + j * cm.cs] = j < r ? src[i * a.rs] : czero<R>();
-        }
-        bic_z<R, false>(W, ldw, n, r, k, jp, tile, z.p + (int64_t)b * zbs, z.rs, z.cs, tid);
-        __syncthreads();  // W, jp and the norms are rewritten by the next matrix
-    }
-}
-
-// dynamic LDS of the two-sided kernel: [W: the larger of phase 1's n x (m|1) and phase 2's m x (k|1), LDS variant only] tile[8 x 9]
-// complex | vn1[max(m, n)] vn2[max(m, n)] red[8] real | jp[n] jp2[m]
-__host__ __device__ inline size_t btc_w_elems(int m, int n, int k) {
-    const size_t w1 = (size_t)n * (size_t)(m | 1), w2 = (size_t)m * (size_t)(k | 1);
-    return w1 > w2 ? w1 : w2;
-}
-template <typename R>
-size_t btc_lds_bytes(int m, int n, int k, bool in_lds) {
-    size_t c = (size_t)BIC_NB * (BIC_NB + 1);
-    if (in_lds) c += btc_w_elems(m, n, k);
-    return c * sizeof(cplx<R>) + ((size_t)2 * std::max(m, n) + 8) * sizeof(R) + (size_t)(m + n) * sizeof(int);
-}
-
-// Two-sided ID A ~ C X R per matrix: phase 1 is k_batched_id_c's column ID (R = its Z, col_ind, the rank r); phase 2 is the column
-// ID of C^H = conj(A[:, col_ind[:r]])^T (r x m) at rank r with tol = 0, by the same three stages: its permutation is row_ind and its
-// Z, conjugated and written through c's transposed view, is c = Z2^H; X = A[row_ind[:r], col_ind[:r]] is gathered from the input.
-template <typename R, bool IN_LDS>
-__global__ __launch_bounds__(BIC_THREADS) void k_batched_two_sided_c(CV<R> a, int64_t abs, int count, int k, double tol, CV<R> cm, int64_t cbs,
-                                                                     CV<R> xm, int64_t xbs, CV<R> z, int64_t zbs, int64_t *__restrict__ row_ind,
-                                                                     int64_t *__restrict__ col_ind, int64_t *__restrict__ ranks, cplx<R> *__restrict__ ws) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    const int m = (int)a.rows, n = (int)a.cols, mn = m > n ? m : n;
-    const int ldw = IN_LDS ? (m | 1) : m;
-    cplx<R> *lds = reinterpret_cast<cplx<R> *>(smem_raw);
-    cplx<R> *W = IN_LDS ? lds : ws + (size_t)blockIdx.x * (size_t)m * (size_t)n;
-    cplx<R>(*tile)[BIC_NB + 1] = reinterpret_cast<cplx<R>(*)[BIC_NB + 1]>(lds + (IN_LDS ? btc_w_elems(m, n, k) : 0));
-    R *vn1 = reinterpret_cast<R *>(lds + (IN_LDS ? btc_w_elems(m, n, k) : 0) + BIC_NB * (BIC_NB + 1));
-    R *vn2 = vn1 + mn;
-    R *red = vn2 + mn;
-    int *jp = reinterpret_cast<int *>(red + 8);  // phase 1's column permutation: read until X is gathered
-    int *jp2 = jp + n;                           // phase 2's row permutation
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-
-    for (int b = blockIdx.x; b < count; b += gridDim.x) {
-        const cplx<R> *__restrict__ A = a.p + (int64_t)b * abs;
-        // ---- phase 1: column ID of A -> r (= Z), col_ind, the rank --------------------------------------------------
-        bic_load_pow2(W, ldw, m, n, a.rs <= a.cs, [&](int i, int c) { return A[i * a.rs + c * a.cs]; }, vn1, vn2, jp, red + 4, wv, lane);
-        const int r = bic_qrcp(W, ldw, m, n, k, tol, jp, vn1, vn2, red, tid, wv, lane);
-        for (int p = tid; p < n; p += BIC_THREADS) col_ind[(int64_t)b * n + p] = jp[p];
-        if (tid == 0) ranks[b] = r;
-        bic_z<R, false>(W, ldw, n, r, k, jp, tile, z.p + (int64_t)b * zbs, z.rs, z.cs, tid);
-        __syncthreads();  // W and the norms are phase 2's from here
-
-        // ---- phase 2: column ID of C^H (r x m), W2[p][i] = conj(A[p, col_ind[i]]) -> c = Z2^H, row_ind ------------------
-        const int ldw2 = IN_LDS ? (r | 1) : r;
-        bic_load_pow2(W, ldw2, r, m, a.cs < a.rs, [&](int i, int p) { return cj(A[p * a.rs + jp[i] * a.cs]); }, vn1, vn2, jp2, red + 4, wv, lane);
-        const int r2 = bic_qrcp(W, ldw2, r, m, r, 0.0, jp2, vn1, vn2, red, tid, wv, lane);  // r2 < r only on an exactly zero pivot
-        for (int p = tid; p < m; p += BIC_THREADS) row_ind[(int64_t)b * m + p] = jp2[p];
-        bic_z<R, true>(W, ldw2, m, r2, k, jp2, tile, cm.p + (int64_t)b * cbs, cm.cs, cm.rs, tid);  // Z2^H (m x k) through c's transposed view
-
-        // ---- X = A[row_ind[:r], col_ind[:r]], rows and columns r..k-1 zero --------------------------------------------------
-        cplx<R> *Xb = xm.p + (int64_t)b * xbs;
-        for (int j = wv; j < k; j += BIC_WAVES) {
-            const cplx<R> *src = A + (int64_t)jp[j] * a.cs;
-            for (int i = lane; i < k; i += 64) Xb[i * xm.rs + j * xm.cs] = (i < r && j < r) ? src[jp2[i] * a.rs] : czero<R>();
-        }
-        __syncthreads();  // W, jp, jp2 and the norms are rewritten by the next matrix
-    }
-}
-
-
 // ---- batched truncated SVD (rc_svd_rank_batched_c64 / _c32) --------------------------------------------------------------------
 // k_batched_svd's stages with the arithmetic above.  Per matrix, in the tall orientation M x N (N = min(m, n)): the pivoted QR of
-// bic_qrcp run to N steps (W P = Q R with Q = H_0 .. H_{N-1}, the complex tau_j kept), one-sided Jacobi on the N x N core G = R^H
+// bid_qrcp run to N steps (W P = Q R with Q = H_0 .. H_{N-1}, the complex tau_j kept), one-sided Jacobi on the N x N core G = R^H
 // (the rows of the graded R, as the real kernel takes R^T) with the rotations accumulated in J: G J = U_G S, so R = J S U_G^H;
 // singular values = the column norms of G, U = Q [J_k; 0] with the k kept columns in registers, and V_W[jp[i], :] = (G S^-1)[i, :].
 // A wide matrix is read through its plain (unconjugated) transposed view: A^T = U' S V'^H gives A = conj(V') S U'^T, so u is the work
@@ -470,32 +167,6 @@ __device__ __forceinline__ void bsc_round(cplx<R> *G, int ldg, cplx<R> *J, int l
     if (ll == 0 && jacobi_rotation_was_large(app, aqq, h2, s, tol)) *flag = 2;  // plain store: every writer writes 2
 }
 
-// bsv_jacobi's schedule (round-robin pairs, 16 lanes per pair, one barrier per round, kMaxSweeps) on the complex core.  Returns false
-// when the sweep budget ran out before a quiet sweep.
-template <typename R, int NE>
-__device__ __forceinline__ bool bsc_jacobi(cplx<R> *G, int ldg, cplx<R> *J, int ldj, int N, int tid, int *flag) {
-    const int ll = tid & 15, grp = tid >> 4;
-    constexpr int NGRP = BIC_THREADS / 16;
-    const int N2 = (N + 1) & ~1, npairs = N2 / 2;
-    const R tol = sqrt((R)N) * JEps<R>::eps(), tol2 = tol * tol;
-    for (int sweep = 0; sweep < kMaxSweeps; ++sweep) {
-        if (tid == 0) *flag = 0;
-        __syncthreads();
-        for (int r = 0; r < N2 - 1; ++r) {
-            for (int pi = grp; pi < npairs; pi += NGRP) {
-                int p, q;
-                rr_pair(N2, r, pi, p, q);
-                if (q < N) bsc_round<R, NE>(G, ldg, J, ldj, N, p, q, tol, tol2, ll, flag);  // q == N: the dummy column of an odd N
-            }
-            __syncthreads();  // the pairs of a round are disjoint; the next round re-pairs the columns
-        }
-        const int rotated = *flag;
-        __syncthreads();
-        if (rotated < 2) return true;
-    }
-    return false;
-}
-
 // the phase rule on a column held by one wave (x[e] at output row orow(e), -1: none): i* = the first output row of the largest
 // |x|^2; the column is multiplied by ph = conj(x_i*) / |x_i*| (f64, rounded) and x_i* becomes exactly (|x_i*|, 0).  Returns ph;
 // (1, 0) with the column unchanged when |x_i*| is not positive and finite (a zero or non-finite column)
@@ -539,7 +210,7 @@ __device__ __forceinline__ cplx<R> bsc_phase(cplx<R> (&x)[NE], Row orow, int lan
 template <typename R, int NE>
 __device__ __forceinline__ void bsc_form_u(const cplx<R> *W, int ldw, const cplx<R> *J, int ldj, int M, int N, int k, int r, const int *jp, const cplx<R> *taus,
                                            const int *srt, cplx<R> *phs, bool phase_here, cplx<R> *U, int64_t urs, int64_t ucs, int wv, int lane) {
-    for (int c = wv; c < k; c += BIC_WAVES) {
+    for (int c = wv; c < k; c += BID_WAVES) {
         cplx<R> *uc = U + (int64_t)c * ucs;
         if (c >= r) {
             for (int i = lane; i < M; i += 64) uc[i * urs] = czero<R>();
@@ -612,7 +283,7 @@ __host__ __device__ inline size_t bsc_ws_elems(int M, int N, int ldg, bool w_lds
 // vt^T and u^T for a wide one), each moved by its own batch stride; s (count x N) and ranks contiguous.  W_LDS / G_LDS / V_LDS: the
 // working copy W / the core G / the rotations J live in LDS, else in the workgroup's workspace slot (in that order, ldg = N there).
 template <typename R, bool W_LDS, bool V_LDS, bool G_LDS>
-__global__ __launch_bounds__(BIC_THREADS) void k_batched_svd_c(CV<R> a, int64_t abs, int count, int k, double tol, CV<R> uo, int64_t ubs, CV<R> vo,
+__global__ __launch_bounds__(BID_THREADS) void k_batched_svd_c(CV<R> a, int64_t abs, int count, int k, double tol, CV<R> uo, int64_t ubs, CV<R> vo,
                                                                int64_t vbs, R *__restrict__ s_out, int64_t *__restrict__ ranks, cplx<R> *__restrict__ ws,
                                                                int *health, int ldg) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -637,10 +308,10 @@ __global__ __launch_bounds__(BIC_THREADS) void k_batched_svd_c(CV<R> a, int64_t 
     for (int b = blockIdx.x; b < count; b += gridDim.x) {
         const cplx<R> *__restrict__ A = a.p + (int64_t)b * abs;
         // ---- QR: W P = Q R, all N steps (exact zero pivots are steps with H = I), complex taus kept -------------------------------
-        const int e2 = bic_load_pow2(W, ldw, M, N, ars <= acs, [&](int i, int c) { return A[i * ars + c * acs]; }, vn1, vn2, jp, red + 4, wv, lane);
-        bic_qrcp<R, true>(W, ldw, M, N, N, 0.0, jp, vn1, vn2, red, tid, wv, lane, taus);
+        const int e2 = bid_load_pow2(W, ldw, M, N, ars <= acs, [&](int i, int c) { return A[i * ars + c * acs]; }, vn1, vn2, jp, red + 4, wv, lane);
+        bid_qrcp<cplx<R>, true>(W, ldw, M, N, N, 0.0, jp, vn1, vn2, red, tid, wv, lane, taus);
         // ---- core G = R^H (R in pivoted column order: G[:, j] = conj(row j of R)) and J = I -----------------------------------------
-        for (int j = wv; j < N; j += BIC_WAVES) {
+        for (int j = wv; j < N; j += BID_WAVES) {
             for (int i = lane; i < N; i += 64) {
                 G[(size_t)j * ldg + i] = i >= j ? cj(W[(size_t)jp[i] * ldw + j]) : czero<R>();
                 J[(size_t)j * ldj + i] = i == j ? cone<R>() : czero<R>();
@@ -648,13 +319,13 @@ __global__ __launch_bounds__(BIC_THREADS) void k_batched_svd_c(CV<R> a, int64_t 
         }
         __syncthreads();
         bool conv;
-        if (N <= 16) conv = bsc_jacobi<R, 1>(G, ldg, J, ldj, N, tid, flag);
-        else if (N <= 32) conv = bsc_jacobi<R, 2>(G, ldg, J, ldj, N, tid, flag);
-        else if (N <= 64) conv = bsc_jacobi<R, 4>(G, ldg, J, ldj, N, tid, flag);
-        else conv = bsc_jacobi<R, 8>(G, ldg, J, ldj, N, tid, flag);
+        if (N <= 16) conv = bsv_jacobi<cplx<R>, 1>(G, ldg, J, ldj, N, tid, flag);
+        else if (N <= 32) conv = bsv_jacobi<cplx<R>, 2>(G, ldg, J, ldj, N, tid, flag);
+        else if (N <= 64) conv = bsv_jacobi<cplx<R>, 4>(G, ldg, J, ldj, N, tid, flag);
+        else conv = bsv_jacobi<cplx<R>, 8>(G, ldg, J, ldj, N, tid, flag);
         if (!conv && tid == 0) atomicOr(health, 16);  // the sweep budget ran out: bit 16, as the lone Jacobi reports it
         // ---- singular values: column norms, sorted descending (a strict total order: NaN last, ties by column) ----------------------
-        for (int j = tid >> 4; j < N; j += BIC_THREADS / 16) {
+        for (int j = tid >> 4; j < N; j += BID_THREADS / 16) {
             const cplx<R> *gj = G + (size_t)j * ldg;
             R acc = 0;
             for (int i = tid & 15; i < N; i += 16) {
@@ -666,7 +337,7 @@ __global__ __launch_bounds__(BIC_THREADS) void k_batched_svd_c(CV<R> a, int64_t 
         }
         __syncthreads();
         R *sb = s_out + (int64_t)b * N;
-        for (int i = tid; i < N; i += BIC_THREADS) {
+        for (int i = tid; i < N; i += BID_THREADS) {
             const R ki = sig[i] >= (R)0 ? sig[i] : (R)-1;
             int pos = 0;
             for (int j = 0; j < N; ++j) {
@@ -694,7 +365,7 @@ __global__ __launch_bounds__(BIC_THREADS) void k_batched_svd_c(CV<R> a, int64_t 
         // ---- phases on the caller's u.  Wide: u[:, c] is row c of vo, u[jp[i], c] = conj(G[i, srt[c]]) / s_c; its phase is fixed
         // and the row written here, before U is formed.  Tall: in bsc_form_u. ------------------------------------------------------
         if (wide) {
-            for (int c = wv; c < k; c += BIC_WAVES) {
+            for (int c = wv; c < k; c += BID_WAVES) {
                 const int j0 = c < r ? srt[c] : 0;
                 const cplx<R> *gc = G + (size_t)j0 * ldg;
                 const R sj = sig[j0], inv = sj > (R)0 ? (R)1 / sj : (R)0;
@@ -726,7 +397,7 @@ __global__ __launch_bounds__(BIC_THREADS) void k_batched_svd_c(CV<R> a, int64_t 
         if (!wide) {
             __syncthreads();  // phs is written in bsc_form_u
             // ---- V^H: row c of vo is conj(V_W[:, c] ph_c), V_W[jp[i], c] = G[i, srt[c]] / s_c; rows r..k-1 zero ----------------------
-            for (int c = wv; c < k; c += BIC_WAVES) {
+            for (int c = wv; c < k; c += BID_WAVES) {
                 const int j0 = c < r ? srt[c] : 0;
                 const cplx<R> *gc = G + (size_t)j0 * ldg;
                 const R sj = sig[j0], inv = sj > (R)0 ? (R)1 / sj : (R)0;
@@ -744,7 +415,7 @@ __global__ __launch_bounds__(BIC_THREADS) void k_batched_svd_c(CV<R> a, int64_t 
 // ---- batched recompression of complex low-rank factors (rc_lowrank_recompress_complex_batched_c64 / _c32) ----------------------
 // k_batched_recompress's stages with the arithmetic above.  Per block, with q = in_ranks[b] clamped to [0, K]:
 // A = left[:, :q] mid[:q, :q] diag(s[:q]) right[:q, :] (nothing conjugated, s real) is never formed.  The two thin factors are
-// factored where they stand, left[:, :q] P_L = Q_L R_L and the PLAIN transpose right[:q, :]^T P_R = Q_R R_R (bic_qrcp to q steps
+// factored where they stand, left[:, :q] P_L = Q_L R_L and the PLAIN transpose right[:q, :]^T P_R = Q_R R_R (bid_qrcp to q steps
 // each, reflectors and the complex taus kept).  With Rl = R_L P_L^T and Rr = R_R P_R^T:
 //     left = Q_L Rl,  right = Rr^T Q_R^T,  A = Q_L C Q_R^T,  C = Rl mid diag(s) Rr^T   (q x q, no conjugate anywhere).
 // One-sided Jacobi on G = C^H with the rotations in J: G J = V_c Sigma, so C = J Sigma V_c^H and
@@ -798,8 +469,8 @@ __host__ __device__ inline size_t brcc_ws_elems(int m, int n, int K, int ldg, bo
 
 // ---- tall left factors (rc_lowrank_recompress_tall_complex_batched_c64 / _c32, m <= 65536) --------------------------------------------------
 // k_batched_recompress<T, true>'s scheme (kernels_batched_id.hip) on complex elements: left[:, :q] is factored by a flat Householder TSQR with
-// stored reflectors inside the one workgroup.  Stage 0 is bic_qrcp on rows 0 .. min(m, H) - 1, H = BRT_H = 512 rows.  Stage s >= 1 factors a
-// stack: the upper triangle of the previous stage's R (q rows, the real diagonal (beta, 0) as bic_qrcp leaves it, exact zeros below) on top of
+// stored reflectors inside the one workgroup.  Stage 0 is bid_qrcp on rows 0 .. min(m, H) - 1, H = BRT_H = 512 rows.  Stage s >= 1 factors a
+// stack: the upper triangle of the previous stage's R (q rows, the real diagonal (beta, 0) as bid_qrcp leaves it, exact zeros below) on top of
 // the next min(H - q, rows left) rows of left, by the same q pivoted steps.  The factor's column c sits at physical column c of every stack and
 // jpl (position -> physical column) is carried from stage to stage, so after the last stage (the last stage's copy, jpl) stand where (Wl, jpl)
 // stand in the core products.  An exactly zero column of left is an exactly zero column of every stack: pivoted last, tau = 0, a zero row of the
@@ -810,37 +481,6 @@ __host__ __device__ inline size_t brcc_ws_elems(int m, int n, int K, int ldg, bo
 __host__ __device__ inline size_t brtc_ws_elems(int m, int n, int K, int ldg, bool l_lds, bool r_lds, bool v_lds, bool g_lds) {
     if (m <= BRT_H) return brcc_ws_elems(m, n, K, ldg, l_lds, r_lds, v_lds, g_lds);
     return (size_t)brt_stages(m, K) * brt_stage_elems(K) + brcc_ws_elems(0, n, K, ldg, true, r_lds, v_lds, g_lds);
-}
-
-// one stage's stack into W (pitch ldw, hs rows): rows 0 .. top - 1 of position p's column are R[0 .. p, p] of the previous stage's copy Wp (the
-// same pitch and physical columns) and zeros, rows top .. hs - 1 are at(i - top, c); then the real column norms by position (bic_norms' sums)
-// with jp kept as it is.  top == 0 (stage 0): Wp is not read, and with jp the identity this is bic_load.
-template <typename R, typename At>
-__device__ __forceinline__ void brtc_stack_load(cplx<R> *W, int ldw, const cplx<R> *Wp, int top, int hs, int q, bool lanes_on_rows, At at, R *vn1, R *vn2,
-                                                const int *jp, int wv, int lane) {
-    if (top) {
-        for (int p = wv; p < q; p += BIC_WAVES) {
-            const size_t col = (size_t)jp[p] * ldw;
-            for (int i = lane; i < top; i += 64) W[col + i] = i <= p ? Wp[col + i] : czero<R>();
-        }
-    }
-    const int rows = hs - top;
-    if (lanes_on_rows) {
-        for (int c = wv; c < q; c += BIC_WAVES)
-            for (int i = lane; i < rows; i += 64) W[(size_t)c * ldw + top + i] = at(i, c);
-    } else {
-        for (int i = wv; i < rows; i += BIC_WAVES)
-            for (int c = lane; c < q; c += 64) W[(size_t)c * ldw + top + i] = at(i, c);
-    }
-    __syncthreads();
-    for (int p = wv; p < q; p += BIC_WAVES) {
-        const cplx<R> *col = W + (size_t)jp[p] * ldw;
-        R acc = 0;
-        for (int i = lane; i < hs; i += 64) acc += abs2(col[i]);
-        acc = wave_sum_dpp(acc);
-        if (lane == 0) { const R nr = sqrt(acc); vn1[p] = nr; vn2[p] = nr; }
-    }
-    __syncthreads();
 }
 
 // x <- H_0 .. H_{N-1} x for a column held by one wave (row lane + 64 e in x[e], M rows): bsc_form_u's reflector loop, FMA for FMA, as a routine
@@ -887,7 +527,7 @@ template <typename R>
 __device__ __forceinline__ void brtc_form_u(const cplx<R> *stage0, size_t se, int S, int K, int q, int m, const cplx<R> *J, int ldj, int k, int r, const int *srt,
                                             cplx<R> *phs, cplx<R> *U, int64_t urs, int64_t ucs, int wv, int lane) {
     constexpr int NE = BRT_H / 64;
-    for (int c = wv; c < k; c += BIC_WAVES) {
+    for (int c = wv; c < k; c += BID_WAVES) {
         cplx<R> *uc = U + (int64_t)c * ucs;
         if (c >= r) {
             for (int i = lane; i < m; i += 64) uc[i * urs] = czero<R>();
@@ -971,7 +611,7 @@ __device__ __forceinline__ void brtc_form_u(const cplx<R> *stage0, size_t se, in
 // 2048 x 2048 x 256, K = 32, and 49.9k against 68.7k at 512 x 8192 x 128, K = 16, at the same grid: the workspace bound leaves
 // one workgroup per CU at those shapes either way, and the kernel is latency-bound per Householder step.
 template <typename R, bool TALL>
-__global__ __launch_bounds__(BIC_THREADS, (TALL && sizeof(R) == 8) ? 1 : 2) void k_batched_recompress_c(BrcCArgs<R> a) {
+__global__ __launch_bounds__(BID_THREADS, (TALL && sizeof(R) == 8) ? 1 : 2) void k_batched_recompress_c(BrcCArgs<R> a) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int m = (int)a.left.rows, n = (int)a.right.cols, K = (int)a.left.cols;
     const int kk = a.k < K ? a.k : K, ldg = a.ldg;
@@ -1000,10 +640,10 @@ __global__ __launch_bounds__(BIC_THREADS, (TALL && sizeof(R) == 8) ? 1 : 2) void
         q = __builtin_amdgcn_readfirstlane(q);  // one value per block, uniform by construction
         R *sb = a.s_out + (int64_t)b * K;
         cplx<R> *Ub = a.u.p + (int64_t)b * a.ubs, *Vb = a.vt.p + (int64_t)b * a.vbs;
-        for (int i = q + tid; i < K; i += BIC_THREADS) sb[i] = (R)0;
+        for (int i = q + tid; i < K; i += BID_THREADS) sb[i] = (R)0;
         if (q == 0) {  // uniform over the workgroup; no input is read
             if (tid == 0) a.ranks[b] = 0;
-            for (int c = wv; c < kk; c += BIC_WAVES) {
+            for (int c = wv; c < kk; c += BID_WAVES) {
                 for (int i = lane; i < m; i += 64) Ub[i * a.u.rs + c * a.u.cs] = czero<R>();
                 for (int i = lane; i < n; i += 64) Vb[c * a.vt.rs + i * a.vt.cs] = czero<R>();
             }
@@ -1017,30 +657,30 @@ __global__ __launch_bounds__(BIC_THREADS, (TALL && sizeof(R) == 8) ? 1 : 2) void
         if constexpr (TALL) {
             S = brt_stages(m, q);  // >= 2: m > BRT_H
             const size_t se = brt_stage_elems(K);
-            for (int j = tid; j < q; j += BIC_THREADS) jpl[j] = j;  // ordered before its first read by brtc_stack_load's barrier
+            for (int j = tid; j < q; j += BID_THREADS) jpl[j] = j;  // ordered before its first read by brt_stack_load's barrier
             for (int s = 0; s < S; ++s) {
                 const int top = s ? q : 0, base = s ? BRT_H + (s - 1) * (BRT_H - q) : 0;
                 const int hs = top + min(BRT_H - top, m - base);
                 cplx<R> *Ws = Wl0 + (size_t)s * se, *ts = Ws + (size_t)BRT_H * K;
-                brtc_stack_load(Ws, ldl, Ws - (s ? se : 0), top, hs, q, a.left.rs <= a.left.cs,
+                brt_stack_load(Ws, ldl, Ws - (s ? se : 0), top, hs, q, a.left.rs <= a.left.cs,
                                 [&](int i, int c) { return L[(int64_t)(base + i) * a.left.rs + c * a.left.cs]; }, vn1, vn2, jpl, wv, lane);
-                bic_qrcp<R, true>(Ws, ldl, hs, q, q, 0.0, jpl, vn1, vn2, red, tid, wv, lane, ts);
+                bid_qrcp<cplx<R>, true>(Ws, ldl, hs, q, q, 0.0, jpl, vn1, vn2, red, tid, wv, lane, ts);
                 int *js = reinterpret_cast<int *>(ts + K);  // the stage's pivots beside its taus; jpl goes on as the next stage's starting order
-                for (int j = tid; j < q; j += BIC_THREADS) js[j] = jpl[j];
+                for (int j = tid; j < q; j += BID_THREADS) js[j] = jpl[j];
                 Wl = Ws;
             }
         } else {
-            bic_load(Wl, ldl, m, q, a.left.rs <= a.left.cs, [&](int i, int c) { return L[i * a.left.rs + c * a.left.cs]; }, vn1, vn2, jpl, wv, lane);
-            bic_qrcp<R, true>(Wl, ldl, m, q, q, 0.0, jpl, vn1, vn2, red, tid, wv, lane, taul);
+            bid_load(Wl, ldl, m, q, a.left.rs <= a.left.cs, [&](int i, int c) { return L[i * a.left.rs + c * a.left.cs]; }, vn1, vn2, jpl, wv, lane);
+            bid_qrcp<cplx<R>, true>(Wl, ldl, m, q, q, 0.0, jpl, vn1, vn2, red, tid, wv, lane, taul);
         }
-        bic_load(Wr, ldr, n, q, a.right.cs <= a.right.rs, [&](int i, int c) { return Rt[c * a.right.rs + i * a.right.cs]; }, vn1, vn2, jpr, wv, lane);
-        bic_qrcp<R, true>(Wr, ldr, n, q, q, 0.0, jpr, vn1, vn2, red, tid, wv, lane, taur);
-        for (int j = tid; j < q; j += BIC_THREADS) { ipl[jpl[j]] = j; ipr[jpr[j]] = j; }
+        bid_load(Wr, ldr, n, q, a.right.cs <= a.right.rs, [&](int i, int c) { return Rt[c * a.right.rs + i * a.right.cs]; }, vn1, vn2, jpr, wv, lane);
+        bid_qrcp<cplx<R>, true>(Wr, ldr, n, q, q, 0.0, jpr, vn1, vn2, red, tid, wv, lane, taur);
+        for (int j = tid; j < q; j += BID_THREADS) { ipl[jpl[j]] = j; ipr[jpr[j]] = j; }
         __syncthreads();
         // ---- T1 = mid diag(s) Rr^T in J's place ----------------------------------------------------------------------------------------
         const cplx<R> *__restrict__ Mb = a.mid.p ? a.mid.p + (int64_t)b * a.mbs : nullptr;
         const R *__restrict__ Sb = a.s ? a.s + (int64_t)b * a.s_stride : nullptr;
-        for (int idx = tid; idx < q * q; idx += BIC_THREADS) {
+        for (int idx = tid; idx < q * q; idx += BID_THREADS) {
             const int ai = idx / q, j = idx - ai * q;
             cplx<R> acc;
             if (Mb) {
@@ -1061,7 +701,7 @@ __global__ __launch_bounds__(BIC_THREADS, (TALL && sizeof(R) == 8) ? 1 : 2) void
         }
         __syncthreads();
         // ---- G = C^H: G[i * ldg + j] = conj(sum_a Rl[i, a] T1[a, j]) ------------------------------------------------------------------
-        for (int idx = tid; idx < q * q; idx += BIC_THREADS) {
+        for (int idx = tid; idx < q * q; idx += BID_THREADS) {
             const int i = idx / q, j = idx - i * q;
             cplx<R> acc = czero<R>();
             for (int aa = 0; aa < q; ++aa) {
@@ -1071,19 +711,19 @@ __global__ __launch_bounds__(BIC_THREADS, (TALL && sizeof(R) == 8) ? 1 : 2) void
             G[(size_t)i * ldg + j] = cj(acc);
         }
         __syncthreads();
-        for (int idx = tid; idx < q * q; idx += BIC_THREADS) {
+        for (int idx = tid; idx < q * q; idx += BID_THREADS) {
             const int j = idx / q, i = idx - j * q;
             J[(size_t)j * ldj + i] = i == j ? cone<R>() : czero<R>();
         }
         __syncthreads();
         bool conv;
-        if (q <= 16) conv = bsc_jacobi<R, 1>(G, ldg, J, ldj, q, tid, flag);
-        else if (q <= 32) conv = bsc_jacobi<R, 2>(G, ldg, J, ldj, q, tid, flag);
-        else if (q <= 64) conv = bsc_jacobi<R, 4>(G, ldg, J, ldj, q, tid, flag);
-        else conv = bsc_jacobi<R, 8>(G, ldg, J, ldj, q, tid, flag);
+        if (q <= 16) conv = bsv_jacobi<cplx<R>, 1>(G, ldg, J, ldj, q, tid, flag);
+        else if (q <= 32) conv = bsv_jacobi<cplx<R>, 2>(G, ldg, J, ldj, q, tid, flag);
+        else if (q <= 64) conv = bsv_jacobi<cplx<R>, 4>(G, ldg, J, ldj, q, tid, flag);
+        else conv = bsv_jacobi<cplx<R>, 8>(G, ldg, J, ldj, q, tid, flag);
         if (!conv && tid == 0) atomicOr(a.health, 16);  // the sweep budget ran out: bit 16, as the batched SVD reports it
         // ---- singular values: column norms, sorted descending (a strict total order: NaN last, ties by column) ----------------------
-        for (int j = tid >> 4; j < q; j += BIC_THREADS / 16) {
+        for (int j = tid >> 4; j < q; j += BID_THREADS / 16) {
             const cplx<R> *gj = G + (size_t)j * ldg;
             R acc = 0;
             for (int i = tid & 15; i < q; i += 16) {
@@ -1094,7 +734,7 @@ __global__ __launch_bounds__(BIC_THREADS, (TALL && sizeof(R) == 8) ? 1 : 2) void
             if ((tid & 15) == 0) sig[j] = sqrt(acc);
         }
         __syncthreads();
-        for (int i = tid; i < q; i += BIC_THREADS) {
+        for (int i = tid; i < q; i += BID_THREADS) {
             const R ki = sig[i] >= (R)0 ? sig[i] : (R)-1;
             int pos = 0;
             for (int j = 0; j < q; ++j) {
@@ -1126,7 +766,7 @@ __global__ __launch_bounds__(BIC_THREADS, (TALL && sizeof(R) == 8) ? 1 : 2) void
         else if (m <= 256) bsc_form_u<R, 4>(Wl, ldl, J, ldj, m, q, kk, r, jpl, taul, srt, phs, true, Ub, a.u.rs, a.u.cs, wv, lane);
         else bsc_form_u<R, 8>(Wl, ldl, J, ldj, m, q, kk, r, jpl, taul, srt, phs, true, Ub, a.u.rs, a.u.cs, wv, lane);
         // ---- conj(V_c) = conj(G Sigma^-1) in place (kept columns), then vt^T = Q_R [conj(V_c); 0] conj(ph) through vt's transposed view ---
-        for (int c = wv; c < r; c += BIC_WAVES) {
+        for (int c = wv; c < r; c += BID_WAVES) {
             cplx<R> *gc = G + (size_t)srt[c] * ldg;
             const R sj = sig[srt[c]], inv = sj > (R)0 ? (R)1 / sj : (R)0;
             for (int i = lane; i < q; i += 64) {
@@ -1145,8 +785,8 @@ __global__ __launch_bounds__(BIC_THREADS, (TALL && sizeof(R) == 8) ? 1 : 2) void
 
 // ---- batched sketched column ID of complex tall blocks (rc_sketch_column_id_rank_complex_batched_c64 / _c32) --------------------
 // k_batched_sketch_id's structure (kernels_batched_id.hip) with the stages above: per block the sketch Y = Omega A (l x n, l <= 128, nothing
-// conjugated) is formed straight into the complex working copy W, then bic_norms, bic_qrcp and bic_z<R, false> run on W with l rows: the same
-// routines on the same values as k_batched_id_c given Y, hence its pivots, rank and Z bit for bit; C is gathered from A.
+// conjugated) is formed straight into the complex working copy W, then bid_norms, bid_qrcp and bid_z run on W with l rows: the same
+// routines on the same values as k_batched_id<cplx<R>> given Y, hence its pivots, rank and Z bit for bit; C is gathered from A.
 //
 // The sketch.  Column panels of BSI_COLS = 64 columns of Y, one 16-column MFMA tile per wave, up to BSC_TILES = 4 of the ceil(l / 16) row
 // tiles of the panel in the wave's accumulators, Re and Im apart (v_mfma_f64_16x16x4_f64 / v_mfma_f32_16x16x4_f32, Acc<R> of rc_gemm.hpp, the
@@ -1202,8 +842,8 @@ template <typename R, int TL, bool AR, bool OR, int WM = BSC_W_COLS>
 __device__ __forceinline__ void bsc_sketch(const BscArgs<R> &g, const cplx<R> *__restrict__ A, const cplx<R> *__restrict__ Om, cplx<R> *Yb, cplx<R> *W, int ldw, R *As,
                                            R *Os, int oplane, int t0, int tid, int wv, int lane, bool yconj = false) {
     constexpr int PO = bsi_po(16 * TL);
-    constexpr int A_PER = BSI_ROWS * BSI_COLS / BIC_THREADS;    // 8 elements of A per thread and chunk
-    constexpr int O_PER = BSI_ROWS * 16 * TL / BIC_THREADS;     // 2 TL elements of Omega
+    constexpr int A_PER = BSI_ROWS * BSI_COLS / BID_THREADS;    // 8 elements of A per thread and chunk
+    constexpr int O_PER = BSI_ROWS * 16 * TL / BID_THREADS;     // 2 TL elements of Omega
     constexpr int A_SR = AR ? 1 : BSI_PA, A_SC = AR ? BSI_PK : 1;   // A's planes: As[r * A_SR + c * A_SC] (re), + BSI_A_ELEMS (im)
     constexpr int O_SI = OR ? 1 : BSI_PK, O_SR = OR ? PO : 1;       // Omega's planes: Os[i * O_SI + r * O_SR] (re), + oplane (im)
     const int m = (int)g.a.rows, n = (int)g.a.cols, ltot = (int)g.omega.rows;
@@ -1212,7 +852,7 @@ __device__ __forceinline__ void bsc_sketch(const BscArgs<R> &g, const cplx<R> *_
     Om += (int64_t)(16 * t0) * ors;
     // this thread's elements of a chunk: A[ar + AR_STEP e, ac + AC_STEP e], Om[oi + 16 (e / 2) or 8 e, orr + 16 (e % 2) or 0]
     const int ar = AR ? (tid & (BSI_ROWS - 1)) : (tid / BSI_COLS), ac = AR ? (tid / BSI_ROWS) : (tid & (BSI_COLS - 1));
-    constexpr int AR_STEP = AR ? 0 : BIC_THREADS / BSI_COLS, AC_STEP = AR ? BIC_THREADS / BSI_ROWS : 0;
+    constexpr int AR_STEP = AR ? 0 : BID_THREADS / BSI_COLS, AC_STEP = AR ? BID_THREADS / BSI_ROWS : 0;
     const int oi = OR ? (tid & 15) : (tid / BSI_ROWS), orr = OR ? (tid >> 4) : (tid & (BSI_ROWS - 1));
     const int r16 = lane & 15, k4 = lane >> 4;
     R *as_st = As + ar * A_SR + ac * A_SC, *os_st = Os + oi * O_SI + orr * O_SR;
@@ -1288,7 +928,7 @@ __device__ __forceinline__ void bsc_sketch(const BscArgs<R> &g, const cplx<R> *_
 }
 
 template <typename R, bool AR, bool OR>
-__global__ __launch_bounds__(BIC_THREADS, 2) void k_batched_sketch_id_c(BscArgs<R> g) {
+__global__ __launch_bounds__(BID_THREADS, 2) void k_batched_sketch_id_c(BscArgs<R> g) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int m = (int)g.a.rows, n = (int)g.a.cols, l = (int)g.omega.rows, kk = g.kk;
     const int ldw = g.w_lds ? (l | 1) : l;
@@ -1318,26 +958,26 @@ __global__ __launch_bounds__(BIC_THREADS, 2) void k_batched_sketch_id_c(BscArgs<
                 default: bsc_sketch<R, 4, AR, OR>(g, A, Om, Yb, W, ldw, As, Os, oplane, t0, tid, wv, lane); break;
             }
         }
-        // ---- the column ID of Y: k_batched_id_c's stages on l rows --------------------------------------------------------------------
-        bic_norms_pow2(W, ldw, l, n, vn1, vn2, jp, red + 4, wv, lane);
-        const int r = bic_qrcp(W, ldw, l, n, kk, g.tol, jp, vn1, vn2, red, tid, wv, lane);
-        for (int p = tid; p < n; p += BIC_THREADS) g.col_ind[(int64_t)b * n + p] = jp[p];
+        // ---- the column ID of Y: k_batched_id's stages on l rows --------------------------------------------------------------------
+        bid_norms_pow2(W, ldw, l, n, vn1, vn2, jp, red + 4, wv, lane);
+        const int r = bid_qrcp(W, ldw, l, n, kk, g.tol, jp, vn1, vn2, red, tid, wv, lane);
+        for (int p = tid; p < n; p += BID_THREADS) g.col_ind[(int64_t)b * n + p] = jp[p];
         if (tid == 0) g.ranks[b] = r;
         // C[:, j] = A[:, jp[j]] (zero for j >= r), the lanes along a's smaller stride
         cplx<R> *Cb = g.c.p + (int64_t)b * g.cbs;
         if (g.a.rs <= g.a.cs) {
-            for (int j = wv; j < kk; j += BIC_WAVES) {
+            for (int j = wv; j < kk; j += BID_WAVES) {
                 const cplx<R> *src = A + (int64_t)jp[j] * g.a.cs;
                 for (int i = lane; i < m; i += 64) Cb[i * g.c.rs + j * g.c.cs] = j < r ? src[i * g.a.rs] : czero<R>();
             }
         } else {
             const int total = m * kk;  // <= 65536 * 128
-            for (int idx = tid; idx < total; idx += BIC_THREADS) {
+            for (int idx = tid; idx < total; idx += BID_THREADS) {
                 const int i = idx / kk, j = idx - i * kk;
                 Cb[i * g.c.rs + j * g.c.cs] = j < r ? A[i * g.a.rs + (int64_t)jp[j] * g.a.cs] : czero<R>();
             }
         }
-        bic_z<R, false>(W, ldw, n, r, kk, jp, tile, g.z.p + (int64_t)b * g.zbs, g.z.rs, g.z.cs, tid);
+        bid_z(W, ldw, n, r, kk, jp, tile, g.z.p + (int64_t)b * g.zbs, g.z.rs, g.z.cs, tid);
         __syncthreads();  // W, jp and the norms are rewritten by the next block
     }
 }
@@ -1345,7 +985,7 @@ __global__ __launch_bounds__(BIC_THREADS, 2) void k_batched_sketch_id_c(BscArgs<
 // ---- batched range step of complex tall blocks (rc_sketch_range_step_complex_batched_c64 / _c32) -------------------------------------------
 // k_batched_range_step's structure (kernels_batched_id.hip) with the stages above.  Per block: the sketch Y = Omega A (nothing conjugated)
 // by bsc_sketch, k_batched_sketch_id_c's instances and passes, stored as the working copy of the plain transpose Y^T (n x l, column i =
-// row i of Y); bic_norms_pow2 and the pivoted complex Householder QR of Y^T by bic_qrcp<R, true> run to all l steps with the taus kept;
+// row i of Y); bid_norms_pow2 and the pivoted complex Householder QR of Y^T by bid_qrcp<cplx<R>, true> run to all l steps with the taus kept;
 // the rank r, the first step whose real R_jj is exactly zero or not finite; Q (l x n), row c = (H_0 .. H_c e_c)^T for c < r (transposed,
 // not conjugated: Q Q^H = I, and the QR of Y^H would give the same rows) and exactly zero from r on, written to q and, conjugated and n
 // fastest, to the workgroup's slot; then the projection P^T = conj(Q) A^T, which is bsc_sketch once more on the transposed view of A with
@@ -1383,7 +1023,7 @@ struct BrscArgs {
 template <typename R, int NE>
 __device__ __forceinline__ void brsc_form_q(const cplx<R> *W, int ldw, int n, int l, int r, const int *jp, const cplx<R> *taus, cplx<R> *Qs, cplx<R> *Qb, int64_t qrs,
                                             int64_t qcs, int wv, int lane) {
-    for (int c = wv; c < l; c += BIC_WAVES) {
+    for (int c = wv; c < l; c += BID_WAVES) {
         cplx<R> x[NE];
 #pragma unroll
         for (int e = 0; e < NE; ++e) x[e] = (c < r && lane + 64 * e == c) ? cone<R>() : czero<R>();
@@ -1412,7 +1052,7 @@ __device__ __forceinline__ void brsc_form_q(const cplx<R> *W, int ldw, int n, in
     }
 
 template <typename R, bool AR, bool OR>
-__global__ __launch_bounds__(BIC_THREADS, 2) void k_batched_range_step_c(BrscArgs<R> g) {
+__global__ __launch_bounds__(BID_THREADS, 2) void k_batched_range_step_c(BrscArgs<R> g) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int m = (int)g.a.rows, n = (int)g.a.cols, l = (int)g.omega.rows;
     const int ldw = g.w_lds ? (n | 1) : n;
@@ -1445,9 +1085,9 @@ __global__ __launch_bounds__(BIC_THREADS, 2) void k_batched_range_step_c(BrscArg
             RC_BSC_PASSES(AR, OR, BSC_W_ROWS, s, A, Om, Yb, W, ldw, t, false)
         }
         // ---- the row basis: Y^T P = Q R to all l steps, the rank from R's real diagonal, Q formed from the first r reflectors ---------------
-        bic_norms_pow2(W, ldw, n, l, vn1, vn2, jp, red + 4, wv, lane);
+        bid_norms_pow2(W, ldw, n, l, vn1, vn2, jp, red + 4, wv, lane);
         if (tid == 0) *rk = l;
-        bic_qrcp<R, true>(W, ldw, n, l, l, 0.0, jp, vn1, vn2, red, tid, wv, lane, taus);
+        bid_qrcp<cplx<R>, true>(W, ldw, n, l, l, 0.0, jp, vn1, vn2, red, tid, wv, lane, taus);
         if (tid < l) {
             const R d = W[(size_t)jp[tid] * ldw + tid].re;
             if (d == (R)0 || !isfinite(d)) atomicMin(rk, tid);
@@ -1477,16 +1117,6 @@ __global__ __launch_bounds__(BIC_THREADS, 2) void k_batched_range_step_c(BrscArg
 #undef RC_BSC_PASSES
 
 // ---- the plans: the real launchers' rules (kernels_batched_id.hip) on complex elements, as pure functions of the shapes ---------------------
-
-template <typename R>
-BatchedPlan<bool> bic_plan(int m, int n) {
-    return batched_lds_or_ws([&](bool w_lds) { return bic_lds_bytes<R>(m, n, w_lds); }, (size_t)m * (size_t)n * sizeof(cplx<R>), "column_id_rank_batched");
-}
-
-template <typename R>
-BatchedPlan<bool> btc_plan(int m, int n, int k) {
-    return batched_lds_or_ws([&](bool w_lds) { return btc_lds_bytes<R>(m, n, k, w_lds); }, (size_t)m * (size_t)n * sizeof(cplx<R>), "two_sided_id_rank_batched");
-}
 
 // SVD: bsv_plan's list with a third place for the core; the last keeps W, G and J in the workgroup's slot of the grid-bounded workspace (a
 // 128 x 128 c64 core alone takes 256 KiB, more than BID_MAX_LDS)
@@ -1550,27 +1180,14 @@ template <typename R>
 void batched_column_id_c(rc_context *c, const rc_matrix &a_, int64_t abs, int32_t count, int64_t k, double tol, const rc_matrix &cm_, int64_t cbs,
                          const rc_matrix &z_, int64_t zbs, int64_t *col_ind, int64_t *ranks) {
     const CV<R> a = view_of<R>(a_), cm = view_of<R>(cm_), z = view_of<R>(z_);
-    const int m = (int)a.rows, n = (int)a.cols;
-    if (count <= 0) return;
-    const auto plan = bic_plan<R>(m, n);
-    const auto lch = batched_prepare(c, plan.at ? k_batched_id_c<R, true> : k_batched_id_c<R, false>, "column_id_rank_batched", plan.lds, plan.ws, count);
-    ProfScope ps(c, "op:batched_column_id<complex> %dx%d k=%lld count=%d grid=%lld slots=%lld plan=W:%s", m, n, (long long)k, (int)count,
-                 (long long)lch.grid, (long long)lch.slots, plan.at ? "lds" : "ws");
-    lch.launch(a, abs, (int)count, (int)k, tol, cm, cbs, z, zbs, col_ind, ranks, lch.template workspace<cplx<R>>());
+    bid_launch<cplx<R>>(c, a, abs, count, k, tol, cm, cbs, z, zbs, col_ind, ranks);
 }
 
 template <typename R>
 void batched_two_sided_id_c(rc_context *c, const rc_matrix &a_, int64_t abs, int32_t count, int64_t k, double tol, const rc_matrix &cm_, int64_t cbs,
                             const rc_matrix &x_, int64_t xbs, const rc_matrix &z_, int64_t zbs, int64_t *row_ind, int64_t *col_ind, int64_t *ranks) {
     const CV<R> a = view_of<R>(a_), cm = view_of<R>(cm_), x = view_of<R>(x_), z = view_of<R>(z_);
-    const int m = (int)a.rows, n = (int)a.cols;
-    if (count <= 0) return;
-    const auto plan = btc_plan<R>(m, n, (int)k);
-    const auto lch = batched_prepare(c, plan.at ? k_batched_two_sided_c<R, true> : k_batched_two_sided_c<R, false>, "two_sided_id_rank_batched", plan.lds,
-                                     plan.ws, count);
-    ProfScope ps(c, "op:batched_two_sided_id<complex> %dx%d k=%lld count=%d grid=%lld slots=%lld plan=W:%s", m, n, (long long)k, (int)count,
-                 (long long)lch.grid, (long long)lch.slots, plan.at ? "lds" : "ws");
-    lch.launch(a, abs, (int)count, (int)k, tol, cm, cbs, x, xbs, z, zbs, row_ind, col_ind, ranks, lch.template workspace<cplx<R>>());
+    bts_launch<cplx<R>>(c, a, abs, count, k, tol, cm, cbs, x, xbs, z, zbs, row_ind, col_ind, ranks);
 }
 
 template <typename R>

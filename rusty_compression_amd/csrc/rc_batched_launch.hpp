@@ -1,7 +1,9 @@
 // The launch path of the persistent batched kernels (host only, but for the tall recompressions' stage arithmetic): every launcher of kernels_batched_id.hip, kernels_batched_id_c.hip,
 // kernels_batched_apply.hip, kernels_block_operator.hip, kernels_batched_residual.hip and kernels_batched_residual_c.hip goes
 //     plan (a pure function of the shapes, in its own file)  ->  batched_prepare  ->  ProfScope  ->  workspace()  ->  launch(...)
-// so that the LDS cap, the grid rule, the workspace unit (bytes) and the launch check live here once.
+// so that the LDS cap, the grid rule, the workspace unit (bytes) and the launch check live here once.  The plans and launcher bodies of the
+// column and two-sided IDs are written once for all four element types in batched_stages.hpp, with the device stages the real and complex
+// kernels share.
 #pragma once
 #include <algorithm>
 

@@ -1,8 +1,9 @@
-// The complex element of every complex kernel (rc_complex.hip, kernels_batched_id_c.hip, batched_apply.hpp and the two kernels built
-// on it, kernels_batched_residual_c.hip) and the strided complex view of an rc_matrix.  Complex data is interleaved (re, im) -- the
+// The complex element of every complex kernel (rc_complex.hip, kernels_batched_id_c.hip, batched_stages.hpp, batched_apply.hpp and the
+// two kernels built on it, kernels_batched_residual_c.hip) and the strided complex view of an rc_matrix.  Complex data is interleaved (re, im) -- the
 // layout of ndarray's Complex<T> / numpy complex -- and aligned as its real type, so a view may start at any element of a caller's array.
 #pragma once
 #include "rc_common.hpp"
+#include "rc_device.hpp"
 
 namespace rc {
 
@@ -38,18 +39,26 @@ template <typename R> __device__ __forceinline__ void cfma(cplx<R> a, cplx<R> b,
     acc.im = fma(a.im, b.re, acc.im);
 }
 
-// strided complex view (mirror of rc_matrix, strides in complex elements)
+// The complex side of the element operations the shared batched stages are written in (batched_stages.hpp, where the real side and the
+// primary elem<E> stand): the real type with zero and one, division (Smith's), the larger pow2_key of the two parts, scaling by a
+// real, and the back substitution's acc -= a b in the complex kernels' spelling.  abs2 and cj above are shared as they are.
+template <typename E> struct elem;
 template <typename R>
-struct CV {
-    cplx<R> *p;
-    int64_t rows, cols, rs, cs;
-    __host__ __device__ cplx<R> &at(int64_t i, int64_t j) const { return p[i * rs + j * cs]; }
-    CV sub(int64_t r0, int64_t nr, int64_t c0, int64_t nc) const { return CV{p + r0 * rs + c0 * cs, nr, nc, rs, cs}; }
-    CV t() const { return CV{p, cols, rows, cs, rs}; }
-    bool empty() const { return rows == 0 || cols == 0; }
+struct elem<cplx<R>> {
+    using real = R;
+    static __host__ __device__ __forceinline__ cplx<R> zero() { return czero<R>(); }
+    static __host__ __device__ __forceinline__ cplx<R> one() { return cone<R>(); }
 };
+template <typename R> __device__ __forceinline__ cplx<R> ediv(cplx<R> a, cplx<R> b) { return cdiv(a, b); }
+template <typename R> __device__ __forceinline__ R pow2_key_max(cplx<R> v) { return max(pow2_key(v.re), pow2_key(v.im)); }
+template <typename R> __device__ __forceinline__ cplx<R> escale(cplx<R> v, R s) { return {v.re * s, v.im * s}; }
+template <typename R> __device__ __forceinline__ void submul(cplx<R> &acc, cplx<R> a, cplx<R> b) { acc = acc - a * b; }
+
+// strided complex view: Mat over the complex element
 template <typename R>
-CV<R> view_of(const rc_matrix &m) { return CV<R>{static_cast<cplx<R> *>(m.data), m.rows, m.cols, m.row_stride, m.col_stride}; }
+using CV = Mat<cplx<R>>;
+template <typename R>
+CV<R> view_of(const rc_matrix &m) { return CV<R>(static_cast<cplx<R> *>(m.data), m.rows, m.cols, m.row_stride, m.col_stride); }
 
 }  // namespace
 
