@@ -186,23 +186,6 @@ void rc_context::release_all() {
 
 namespace {
 
-// small device -> host read-back through the pinned buffer (synchronises the stream)
-template <typename T>
-void read_back(rc_context *c, const T *dev, T *host, size_t n) {
-    size_t bytes = n * sizeof(T);
-    if (c->pinned_size < bytes) {
-        if (c->pinned) RC_HIP(hipHostFree(c->pinned));
-        c->pinned = nullptr;
-        c->pinned_size = 0;
-        size_t want = std::max<size_t>(bytes, 1 << 16);
-        RC_HIP(hipHostMalloc(&c->pinned, want, hipHostMallocDefault));
-        c->pinned_size = want;
-    }
-    RC_HIP(hipMemcpyAsync(c->pinned, dev, bytes, hipMemcpyDeviceToHost, c->stream));
-    RC_HIP(hipStreamSynchronize(c->stream));
-    std::memcpy(host, c->pinned, bytes);
-}
-
 template <typename T>
 Mat<T> tmp_colmajor(rc_context *c, int64_t rows, int64_t cols) {
     int64_t ld = even_ld(std::max<int64_t>(rows, 1));
@@ -542,73 +525,33 @@ void lq_row_id(rc_context *c, Mat<T> l, Mat<T> q, const int64_t *ind, Mat<T> x, 
     qr_column_id(c, q.t(), l.t(), ind, rrows.t(), x.t(), own_ind);
 }
 
-// B = range^H A written into `b` (any layout)
+// MaxColNorm (/root/reference/src/random_sampling.rs:184-191) -> device scalar
 template <typename T>
-void project_dense(rc_context *c, Mat<T> range, Mat<T> a, Mat<T> b) {
-    gemm<T>(c, 1, range.t(), a, 0, b);
-}
-
-// The operator the range finders sample: the reference implements them for ANY `Op: MatMat` / `Op: ConjMatMat`
-// (/root/reference/src/random_sampling.rs:102, :130, :222; trait contract src/types.rs:40-51, :77-81, products :58-71, :88-101).
-// Either a dense device matrix (the rc_*_f64 / _f32 entry points: one MFMA GEMM per product) or the host's callback table
-// (rc_operator, the rc_*_op_* entry points): the compositions below are written once against these three products.
-template <typename T>
-struct OpView {
-    int64_t rows = 0, cols = 0;
-    Mat<T> dense;
-    const rc_operator *cb = nullptr;
-    static OpView of(Mat<T> a) { OpView o; o.rows = a.rows; o.cols = a.cols; o.dense = a; return o; }
-    static OpView of(const rc_operator *op) {
-        RC_REQUIRE(op != nullptr && op->matmat != nullptr && op->rows >= 0 && op->cols >= 0, RC_INVALID_ARGUMENT, "rc_operator: null table / matmat or negative extent");
-        OpView o; o.rows = op->rows; o.cols = op->cols; o.cb = op; return o;
-    }
-    static rc_matrix to_c(Mat<T> m) { rc_matrix r; r.data = m.p; r.rows = m.rows; r.cols = m.cols; r.row_stride = m.rs; r.col_stride = m.cs; return r; }
-    void call(rc_context *c, rc_operator_product_fn fn, const char *what, Mat<T> x, Mat<T> y) const {
-        RC_REQUIRE(fn != nullptr, RC_INVALID_ARGUMENT, "rc_operator: this call needs the operator's %s", what);
-        RC_REQUIRE(!c->capturing, RC_INVALID_ARGUMENT, "rc_operator: callbacks cannot be recorded into a hipGraph");
-        const std::string before = c->last_error;
-        const rc_status st = fn(cb->user, c, to_c(x), to_c(y));
-        if (st != RC_OK) {
-            const std::string inner = c->last_error != before ? c->last_error : std::string();
-            fail(st, "operator callback %s (%lld x %lld -> %lld x %lld) returned status %d%s%s", what, (long long)x.rows, (long long)x.cols,
-                 (long long)y.rows, (long long)y.cols, (int)st, inner.empty() ? "" : ": ", inner.c_str());
-        }
-    }
-    // y (rows x s) = A x
-    void matmat(rc_context *c, Mat<T> x, Mat<T> y) const {
-        RC_REQUIRE(x.rows == cols && y.rows == rows && x.cols == y.cols, RC_INVALID_ARGUMENT, "matmat: shape mismatch");
-        if (cb) call(c, cb->matmat, "matmat", x, y);
-        else gemm<T>(c, 1, dense, x, 0, y);
-    }
-    // y (cols x s) = A^H x
-    void conj_matmat(rc_context *c, Mat<T> x, Mat<T> y) const {
-        RC_REQUIRE(x.rows == rows && y.rows == cols && x.cols == y.cols, RC_INVALID_ARGUMENT, "conj_matmat: shape mismatch");
-        if (cb) call(c, cb->conj_matmat, "conj_matmat", x, y);
-        else gemm<T>(c, 1, dense.t(), x, 0, y);
-    }
-    // b (k x n) = range^H A = (A^H range)^H: for the callbacks the k x n result is handed over as the n x k view of its transpose
-    // (the reference does exactly this: conj_matmat, then .t(), src/qr.rs:316-317, src/svd.rs:175-176)
-    void project(rc_context *c, Mat<T> range, Mat<T> b) const {
-        if (cb) conj_matmat(c, range, b.t());
-        else project_dense(c, range, dense, b);
-    }
-};
-
-// QRTraits::compute_from_range_estimate (/root/reference/src/qr.rs:311-323)
-template <typename T>
-void qr_from_range(rc_context *c, Mat<T> range, const OpView<T> &a, Mat<T> q, Mat<T> r, int64_t *ind) {
-    const int64_t m = a.rows, n = a.cols, rr = range.cols, k = std::min(rr, n);
-    RC_REQUIRE(range.rows == m && q.rows == m && q.cols == k && r.rows == k && r.cols == n, RC_INVALID_ARGUMENT,
-               "qr_from_range_estimate: shape mismatch");
+void max_col_norm_dev(rc_context *c, Mat<T> y, T *out_dev) {
     ArenaMark mark(c);
-    Mat<T> w = tmp_colmajor<T>(c, rr, n);
-    a.project(c, range, w);
-    Mat<T> qb = tmp_colmajor<T>(c, rr, k);
-    qrcp_core(c, w, k, true, qb, r, ind);
-    gemm<T>(c, 1, range, qb, 0, q);
+    T *ss = c->alloc<T>((size_t)std::max<int64_t>(y.cols, 1));
+    col_sumsq(c, y, ss);
+    max_sqrt(c, ss, y.cols, out_dev);
 }
 
-// SVDTraits::compute_from_range_estimate (/root/reference/src/svd.rs:171-183)
+// ---- the real family's spelling of the primitives rc_dense_shared.hpp is written in (OpView, the range finders, qr_from_range,
+// rank_by_tolerance, apply_perm_matrix and their entry points stand there, once for real and complex) ----
+template <typename T>
+Mat<T> tmp_omega(rc_context *c, int64_t rows, int64_t cols) { return tmp_rowmajor<T>(c, rows, cols); }
+template <typename T>
+void product(rc_context *c, int alpha, bool adj_a, Mat<T> a, Mat<T> b, int beta, Mat<T> cm) {
+    gemm<T>(c, (T)alpha, adj_a ? a.t() : a, b, (T)beta, cm);
+}
+template <typename T>
+void qrcp(rc_context *c, Mat<T> w, int64_t k, Mat<T> q, Mat<T> r, int64_t *ind) { qrcp_core(c, w, k, true, q, r, ind); }
+
+}  // namespace
+
+#include "rc_dense_shared.hpp"
+
+namespace {
+
+// SVDTraits::compute_from_range_estimate (/root/reference/src/svd.rs:171-183): the tall or the wide orientation for svd_core
 template <typename T>
 void svd_from_range(rc_context *c, Mat<T> range, const OpView<T> &a, Mat<T> u, T *s, Mat<T> vt) {
     const int64_t m = a.rows, n = a.cols, rr = range.cols, r = std::min(rr, n);
@@ -627,154 +570,6 @@ void svd_from_range(rc_context *c, Mat<T> range, const OpView<T> &a, Mat<T> u, T
         svd_core(c, b, false, ub, s, vt);
     }
     gemm<T>(c, 1, range, ub, 0, u);
-}
-
-// SampleRange::sample_range_by_rank (/root/reference/src/random_sampling.rs:103-118).
-// Only the first k Householder steps influence Q[:, :k], so the factorization stops there.
-template <typename T>
-void sample_range_by_rank(rc_context *c, const OpView<T> &a, int64_t k, int64_t p, Mat<T> omega, uint64_t seed, Mat<T> q) {
-    const int64_t m = a.rows, n = a.cols, l = k + p;
-    RC_REQUIRE(k >= 0 && p >= 0, RC_INVALID_ARGUMENT, "sample_range_by_rank: negative k or p");
-    const int64_t kk = std::min(k, std::min(m, l));
-    RC_REQUIRE(q.rows == m && q.cols == kk, RC_INVALID_ARGUMENT, "sample_range_by_rank: q must be %lld x %lld", (long long)m, (long long)kk);
-    if (kk == 0) return;
-    ArenaMark mark(c);
-    if (omega.p == nullptr) {
-        omega = tmp_rowmajor<T>(c, n, l);
-        fill_gaussian(c, omega, seed, 0);
-    } else {
-        RC_REQUIRE(omega.rows == n && omega.cols == l, RC_INVALID_ARGUMENT, "sample_range_by_rank: omega must be %lld x %lld", (long long)n, (long long)l);
-    }
-    Mat<T> w = tmp_colmajor<T>(c, m, l);
-    a.matmat(c, omega, w);
-    int64_t *ind = c->alloc<int64_t>((size_t)l);
-    qrcp_core(c, w, kk, true, q, Mat<T>(), ind);
-}
-
-// full pivoted QR, Q only (helper of the power iteration)
-template <typename T>
-Mat<T> orth_full(rc_context *c, Mat<T> w) {
-    const int64_t k = std::min(w.rows, w.cols);
-    Mat<T> q = tmp_colmajor<T>(c, w.rows, k);
-    int64_t *ind = c->alloc<int64_t>((size_t)std::max<int64_t>(w.cols, 1));
-    qrcp_core(c, w, k, true, q, Mat<T>(), ind);
-    return q;
-}
-
-// SampleRangePowerIteration (/root/reference/src/random_sampling.rs:131-160).
-// The inner `let op_omega = ...` (:150) shadows the outer binding, so every
-// iteration restarts from A Omega and only the last one is kept: for any
-// it_count >= 1 the result is QRCP(A orth(A^H orth(A Omega)))[:, :k].
-template <typename T>
-void sample_range_power(rc_context *c, const OpView<T> &a, int64_t k, int64_t p, int64_t it_count, Mat<T> omega, uint64_t seed, Mat<T> q) {
-    if (it_count <= 0) { sample_range_by_rank(c, a, k, p, omega, seed, q); return; }
-    const int64_t m = a.rows, n = a.cols, l = k + p;
-    ArenaMark mark(c);
-    if (omega.p == nullptr) {
-        omega = tmp_rowmajor<T>(c, n, l);
-        fill_gaussian(c, omega, seed, 0);
-    } else {
-        RC_REQUIRE(omega.rows == n && omega.cols == l, RC_INVALID_ARGUMENT, "sample_range_power_iteration: omega must be %lld x %lld", (long long)n, (long long)l);
-    }
-    Mat<T> y1 = tmp_colmajor<T>(c, m, l);
-    a.matmat(c, omega, y1);
-    // The reference's loop restarts every iteration from the first product (a shadowed variable), so exactly one
-    // power step survives; RC_OPT_POWER_ITERATION_FIXED = 1 runs the it_count steps the documentation describes.
-    const int64_t steps = c->opt_power_fixed ? it_count : 1;
-    for (int64_t it = 0; it < steps; ++it) {
-        Mat<T> q0 = orth_full(c, y1);                    // m x min(m, l)
-        Mat<T> z = tmp_colmajor<T>(c, n, q0.cols);
-        a.conj_matmat(c, q0, z);
-        Mat<T> wq = orth_full(c, z);                     // n x min(n, q0.cols)
-        y1 = tmp_colmajor<T>(c, m, wq.cols);
-        a.matmat(c, wq, y1);
-    }
-    const int64_t kk = std::min(k, std::min(m, y1.cols));
-    RC_REQUIRE(q.rows == m && q.cols == kk, RC_INVALID_ARGUMENT, "sample_range_power_iteration: q must be %lld x %lld", (long long)m, (long long)kk);
-    int64_t *ind = c->alloc<int64_t>((size_t)std::max<int64_t>(y1.cols, 1));
-    qrcp_core(c, y1, kk, true, q, Mat<T>(), ind);
-}
-
-// MaxColNorm (/root/reference/src/random_sampling.rs:184-191) -> device scalar
-template <typename T>
-void max_col_norm_dev(rc_context *c, Mat<T> y, T *out_dev) {
-    ArenaMark mark(c);
-    T *ss = c->alloc<T>((size_t)std::max<int64_t>(y.cols, 1));
-    col_sumsq(c, y, ss);
-    max_sqrt(c, ss, y.cols, out_dev);
-}
-
-// AdaptiveSampling::sample_range_adaptive (/root/reference/src/random_sampling.rs:223-274)
-template <typename T>
-void sample_range_adaptive(rc_context *c, const OpView<T> &a, double rel_tol_d, int64_t s, Mat<T> omegas, uint64_t seed, Mat<T> qcap,
-                           int64_t *rank_out, int64_t *hist_rank, double *hist_res, int64_t hist_cap, int64_t *hist_len) {
-    const int64_t m = a.rows, n = a.cols, cap = qcap.cols;
-    RC_REQUIRE(s >= 1 && qcap.rows == m, RC_INVALID_ARGUMENT, "sample_range_adaptive: bad sample_size or q buffer");
-    const bool explicit_omega = omegas.p != nullptr;
-    if (explicit_omega) RC_REQUIRE(omegas.rows == n, RC_INVALID_ARGUMENT, "sample_range_adaptive: omegas must have %lld rows", (long long)n);
-    const T tol_factor = (T)(10.0 * std::sqrt(2.0 / 3.14159265358979323846));  // random_sampling.rs:231-234
-    const T rel_tol = (T)rel_tol_d;
-    const int64_t sq = std::min(m, s);  // columns a pivoted QR of an m x s block yields
-
-    int64_t blocks_used = 0;
-    auto next_omega = [&](Mat<T> dst) {
-        if (explicit_omega) {
-            RC_REQUIRE((blocks_used + 1) * s <= omegas.cols, RC_COMPRESSION_ERROR,
-                       "sample_range_adaptive: explicit Omega blocks exhausted after %lld blocks", (long long)blocks_used);
-            copy_mat(c, omegas.sub(0, n, blocks_used * s, s), dst);
-        } else {
-            fill_gaussian(c, dst, seed, (uint64_t)blocks_used * (uint64_t)(n * s));
-        }
-        ++blocks_used;
-    };
-
-    Mat<T> omega = tmp_rowmajor<T>(c, n, s);
-    Mat<T> y = tmp_colmajor<T>(c, m, s);
-    Mat<T> qacc = tmp_colmajor<T>(c, m, cap);
-    Mat<T> bacc = tmp_rowmajor<T>(c, cap, n);
-    Mat<T> t1 = tmp_colmajor<T>(c, cap, s);
-    int64_t *ind = c->alloc<int64_t>((size_t)s);
-    T *scal = c->alloc<T>(1);
-
-    next_omega(omega);
-    a.matmat(c, omega, y);
-    T mc;
-    max_col_norm_dev(c, y, scal);
-    read_back(c, scal, &mc, 1);
-    const T operator_norm = mc * tol_factor;
-    T max_norm = operator_norm;
-    int64_t r = 0, nh = 0;
-    while (max_norm / operator_norm >= rel_tol) {
-        RC_REQUIRE(r + sq <= cap, RC_COMPRESSION_ERROR, "sample_range_adaptive: basis capacity %lld exhausted at rank %lld", (long long)cap, (long long)r);
-        if (r > 0) {  // y -= q (q^H y)
-            Mat<T> qr_ = qacc.sub(0, m, 0, r), tt = t1.sub(0, r, 0, s);
-            gemm<T>(c, 1, qr_.t(), y, 0, tt);
-            gemm<T>(c, -1, qr_, tt, 1, y);
-        }
-        Mat<T> qnew = qacc.sub(0, m, r, sq);
-        qrcp_core(c, y, sq, true, qnew, Mat<T>(), ind);       // pivoted QR of the block (:254)
-        a.project(c, qnew, bacc.sub(r, sq, 0, n));             // b = [b ; (A^H Q_new)^H] (:256-260)
-        r += sq;
-        next_omega(omega);
-        {   // y = A Omega - q (b Omega)  (:265-266)
-            Mat<T> qr_ = qacc.sub(0, m, 0, r), tt = t1.sub(0, r, 0, s);
-            gemm<T>(c, 1, bacc.sub(0, r, 0, n), omega, 0, tt);
-            a.matmat(c, omega, y);
-            gemm<T>(c, -1, qr_, tt, 1, y);
-        }
-        max_col_norm_dev(c, y, scal);
-        read_back(c, scal, &mc, 1);
-        max_norm = mc * tol_factor;
-        if (nh < hist_cap) {
-            if (hist_rank) hist_rank[nh] = r;
-            if (hist_res) hist_res[nh] = (double)(max_norm / operator_norm);
-        }
-        ++nh;
-    }
-    copy_mat(c, qacc.sub(0, m, 0, r), qcap.sub(0, m, 0, r));
-    if (rank_out) *rank_out = r;
-    if (hist_len) *hist_len = std::min(nh, hist_cap);
-    RC_HIP(hipStreamSynchronize(c->stream));
 }
 
 // Fork / join of a side branch onto the context's second stream (created on first use, outside graph capture).
@@ -1009,7 +804,7 @@ void rsvd_id_row_sharded(rc_comm *comm, rc_context *c, Mat<T> a, int64_t k, int6
     {
         ProfScope ps(c, "stage:sharded project B = sum_r range_r^H A_r (all-reduce)");
         if (b.rs != n) fill_words(c, b.p, (size_t)k * (size_t)b.rs * sizeof(T), 0u);
-        project_dense(c, range, a, b);
+        product(c, 1, true, range, a, 0, b);  // B = range^H A
         if (comm) comm_ok(rc_comm_all_reduce_sum(comm, c, b.p, (size_t)k * (size_t)b.rs, (int32_t)sizeof(T)), "all-reduce");
     }
     rsvd_id_consumers(c, range, b, o);
@@ -1041,22 +836,6 @@ void column_id_rank(rc_context *c, Mat<T> a, int64_t k, Mat<T> cm, Mat<T> z, int
 }
 
 template <typename T>
-void rank_by_tolerance(rc_context *c, Mat<T> tri, double tol, int64_t *rank) {
-    RC_REQUIRE(tol < 1.0 && 0.0 <= tol, RC_INVALID_ARGUMENT, "Require 0 <= tol < 1.0");
-    const int64_t len = std::min(tri.rows, tri.cols);
-    RC_REQUIRE(len >= 1, RC_COMPRESSION_ERROR, "rank_by_tolerance: empty factor");
-    ArenaMark mark(c);
-    T *d = c->alloc<T>((size_t)len);
-    copy_mat(c, Mat<T>(tri.p, len, 1, tri.rs + tri.cs, 1), Mat<T>(d, len, 1, 1, 1));
-    std::vector<T> h((size_t)len);
-    read_back(c, d, h.data(), (size_t)len);
-    for (int64_t i = 0; i < len; ++i) {
-        if ((double)std::fabs(h[i] / h[0]) < tol) { *rank = i; return; }  // qr.rs:194
-    }
-    fail(RC_COMPRESSION_ERROR, "Could not compress to desired tolerance");
-}
-
-template <typename T>
 void svd_rank_by_tolerance(rc_context *c, const T *s, int64_t len, double tol, int64_t *rank) {
     RC_REQUIRE(tol < 1.0 && 0.0 <= tol, RC_INVALID_ARGUMENT, "Require 0 <= tol < 1.0");
     RC_REQUIRE(len >= 1, RC_COMPRESSION_ERROR, "svd_rank_by_tolerance: empty spectrum");
@@ -1066,25 +845,6 @@ void svd_rank_by_tolerance(rc_context *c, const T *s, int64_t len, double tol, i
         if ((double)(h[i] / h[0]) < tol) { *rank = i; return; }  // svd.rs:95
     }
     fail(RC_COMPRESSION_ERROR, "Could not compress to desired tolerance");
-}
-
-template <typename T>
-void apply_perm_matrix(rc_context *c, int mode, Mat<T> in, const int64_t *perm, int64_t plen, Mat<T> out) {
-    RC_REQUIRE(in.rows == out.rows && in.cols == out.cols, RC_INVALID_ARGUMENT, "apply_permutation: shape mismatch");
-    ArenaMark mark(c);
-    const bool cols = (mode == RC_PERM_COL || mode == RC_PERM_COLINV);
-    const bool inv = (mode == RC_PERM_COLINV || mode == RC_PERM_ROWINV);
-    RC_REQUIRE(mode >= 0 && mode <= 3, RC_INVALID_ARGUMENT, "apply_permutation: unknown mode %d", mode);
-    if (cols) RC_REQUIRE(plen == in.cols, RC_INVALID_ARGUMENT, "Length of index array and number of columns differ.");
-    else RC_REQUIRE(plen == in.rows, RC_INVALID_ARGUMENT, "Length of index array and number of rows differ.");
-    const int64_t *idx = perm;
-    if (inv) {
-        int64_t *iv = c->alloc<int64_t>((size_t)std::max<int64_t>(plen, 1));
-        invert_perm(c, perm, plen, iv);
-        idx = iv;
-    }
-    if (cols) gather_cols(c, in, idx, out);
-    else gather_cols(c, in.t(), idx, out.t());
 }
 
 }  // namespace
@@ -1383,19 +1143,6 @@ rc_status rc_invert_permutation(rc_context *ctx, const int64_t *perm, int64_t n,
             *out = std::sqrt(h[0]) / std::sqrt(h[1]);                                                                                    \
         });                                                                                                                              \
     }                                                                                                                                    \
-    rc_status rc_apply_permutation_matrix_##SUF(rc_context *ctx, int32_t mode, rc_matrix in, const int64_t *perm, int64_t plen,          \
-                                                rc_matrix out) {                                                                         \
-        return guarded(ctx, [&] { apply_perm_matrix<T>(ctx, mode, from_c<T>(in), perm, plen, from_c<T>(out)); });                        \
-    }                                                                                                                                    \
-    rc_status rc_apply_permutation_vector_##SUF(rc_context *ctx, int32_t mode, rc_matrix in, const int64_t *perm, int64_t plen,          \
-                                                rc_matrix out) {                                                                         \
-        return guarded(ctx, [&] {                                                                                                        \
-            RC_REQUIRE(mode == RC_VPERM_INV || mode == RC_VPERM_NOINV, RC_INVALID_ARGUMENT, "unknown vector permutation mode");          \
-            RC_REQUIRE(in.cols == 1 && out.cols == 1 && plen == in.rows, RC_INVALID_ARGUMENT,                                           \
-                       "The input vector and the index array must have the same length");                                               \
-            apply_perm_matrix<T>(ctx, mode == RC_VPERM_INV ? RC_PERM_ROWINV : RC_PERM_ROW, from_c<T>(in), perm, plen, from_c<T>(out));   \
-        });                                                                                                                              \
-    }                                                                                                                                    \
     rc_status rc_pivoted_qr_##SUF(rc_context *ctx, rc_matrix a, rc_matrix q, rc_matrix r, int64_t *ind) {                                \
         return guarded(ctx, [&] { pivoted_qr<T>(ctx, from_c<T>(a), from_c<T>(q), from_c<T>(r), ind); });                                 \
     }                                                                                                                                    \
@@ -1417,9 +1164,6 @@ rc_status rc_invert_permutation(rc_context *ctx, const int64_t *perm, int64_t n,
     }                                                                                                                                    \
     rc_status rc_compute_svd_##SUF(rc_context *ctx, rc_matrix a, rc_matrix u, T *s, rc_matrix vt) {                                      \
         return guarded(ctx, [&] { compute_svd<T>(ctx, from_c<T>(a), from_c<T>(u), s, from_c<T>(vt)); });                                 \
-    }                                                                                                                                    \
-    rc_status rc_rank_by_tolerance_##SUF(rc_context *ctx, rc_matrix tri, double tol, int64_t *rank) {                                    \
-        return guarded(ctx, [&] { rank_by_tolerance<T>(ctx, from_c<T>(tri), tol, rank); });                                              \
     }                                                                                                                                    \
     rc_status rc_qr_to_mat_##SUF(rc_context *ctx, rc_matrix q, rc_matrix r, const int64_t *ind, rc_matrix out) {                         \
         return guarded(ctx, [&] {                                                                                                        \
@@ -1447,9 +1191,6 @@ rc_status rc_invert_permutation(rc_context *ctx, const int64_t *perm, int64_t n,
     rc_status rc_lq_row_id_##SUF(rc_context *ctx, rc_matrix l, rc_matrix q, const int64_t *ind, rc_matrix x, rc_matrix rr) {             \
         return guarded(ctx, [&] { lq_row_id<T>(ctx, from_c<T>(l), from_c<T>(q), ind, from_c<T>(x), from_c<T>(rr), /*own_ind=*/false); }); \
     }                                                                                                                                    \
-    rc_status rc_qr_from_range_estimate_##SUF(rc_context *ctx, rc_matrix range, rc_matrix a, rc_matrix q, rc_matrix r, int64_t *ind) {   \
-        return guarded(ctx, [&] { qr_from_range<T>(ctx, from_c<T>(range), OpView<T>::of(from_c<T>(a)), from_c<T>(q), from_c<T>(r), ind); }); \
-    }                                                                                                                                    \
     rc_status rc_svd_rank_by_tolerance_##SUF(rc_context *ctx, const T *s, int64_t len, double tol, int64_t *rank) {                      \
         return guarded(ctx, [&] { svd_rank_by_tolerance<T>(ctx, s, len, tol, rank); });                                                  \
     }                                                                                                                                    \
@@ -1473,9 +1214,6 @@ rc_status rc_invert_permutation(rc_context *ctx, const int64_t *perm, int64_t n,
             gemm<T>(ctx, 1, from_c<T>(u), qb, 0, Q);                                                                                     \
         });                                                                                                                              \
     }                                                                                                                                    \
-    rc_status rc_svd_from_range_estimate_##SUF(rc_context *ctx, rc_matrix range, rc_matrix a, rc_matrix u, T *s, rc_matrix vt) {         \
-        return guarded(ctx, [&] { svd_from_range<T>(ctx, from_c<T>(range), OpView<T>::of(from_c<T>(a)), from_c<T>(u), s, from_c<T>(vt)); }); \
-    }                                                                                                                                    \
     rc_status rc_column_id_two_sided_##SUF(rc_context *ctx, rc_matrix c, rc_matrix c_out, rc_matrix x, int64_t *row_ind) {               \
         return guarded(ctx, [&] {                                                                                                        \
             Mat<T> C = from_c<T>(c);                                                                                                     \
@@ -1494,29 +1232,6 @@ rc_status rc_invert_permutation(rc_context *ctx, const int64_t *perm, int64_t n,
             qr_column_id<T>(ctx, q, rr, col_ind, from_c<T>(x), from_c<T>(r_out), /*own_ind=*/true);                                      \
         });                                                                                                                              \
     }                                                                                                                                    \
-    rc_status rc_max_col_norm_##SUF(rc_context *ctx, rc_matrix y, T *out) {                                                              \
-        return guarded(ctx, [&] {                                                                                                        \
-            T *d = ctx->alloc<T>(1);                                                                                                     \
-            max_col_norm_dev<T>(ctx, from_c<T>(y), d);                                                                                   \
-            read_back(ctx, d, out, 1);                                                                                                   \
-        });                                                                                                                              \
-    }                                                                                                                                    \
-    rc_status rc_sample_range_by_rank_##SUF(rc_context *ctx, rc_matrix a, int64_t k, int64_t p, rc_matrix omega, uint64_t seed,          \
-                                            rc_matrix q) {                                                                               \
-        return guarded(ctx, [&] { sample_range_by_rank<T>(ctx, OpView<T>::of(from_c<T>(a)), k, p, from_c<T>(omega), seed, from_c<T>(q)); }); \
-    }                                                                                                                                    \
-    rc_status rc_sample_range_power_iteration_##SUF(rc_context *ctx, rc_matrix a, int64_t k, int64_t p, int64_t it, rc_matrix omega,     \
-                                                    uint64_t seed, rc_matrix q) {                                                        \
-        return guarded(ctx, [&] { sample_range_power<T>(ctx, OpView<T>::of(from_c<T>(a)), k, p, it, from_c<T>(omega), seed, from_c<T>(q)); }); \
-    }                                                                                                                                    \
-    rc_status rc_sample_range_adaptive_##SUF(rc_context *ctx, rc_matrix a, double rel_tol, int64_t s, rc_matrix omegas, uint64_t seed,   \
-                                             rc_matrix q_cap, int64_t *rank, int64_t *hist_rank, double *hist_res, int64_t hist_cap,     \
-                                             int64_t *hist_len) {                                                                        \
-        return guarded(ctx, [&] {                                                                                                        \
-            sample_range_adaptive<T>(ctx, OpView<T>::of(from_c<T>(a)), rel_tol, s, from_c<T>(omegas), seed, from_c<T>(q_cap), rank, hist_rank, \
-                                     hist_res, hist_cap, hist_len);                                                                      \
-        });                                                                                                                              \
-    }                                                                                                                                    \
     rc_status rc_rsvd_id_##SUF(rc_context *ctx, rc_matrix a, int64_t k, int64_t p, rc_matrix omega, uint64_t seed,                       \
                                const rc_rsvd_id_out *out) {                                                                              \
         return guarded(ctx, [&] {                                                                                                        \
@@ -1524,31 +1239,7 @@ rc_status rc_invert_permutation(rc_context *ctx, const int64_t *perm, int64_t n,
             rsvd_id<T>(ctx, OpView<T>::of(from_c<T>(a)), k, p, from_c<T>(omega), seed, *out);                                            \
         });                                                                                                                              \
     }                                                                                                                                    \
-    /* the same compositions over the host's operator callbacks (rc_operator) */                                                         \
-    rc_status rc_sample_range_by_rank_op_##SUF(rc_context *ctx, const rc_operator *op, int64_t k, int64_t p, rc_matrix omega,            \
-                                               uint64_t seed, rc_matrix q) {                                                             \
-        return guarded(ctx, [&] { sample_range_by_rank<T>(ctx, OpView<T>::of(op), k, p, from_c<T>(omega), seed, from_c<T>(q)); });       \
-    }                                                                                                                                    \
-    rc_status rc_sample_range_power_iteration_op_##SUF(rc_context *ctx, const rc_operator *op, int64_t k, int64_t p, int64_t it,         \
-                                                       rc_matrix omega, uint64_t seed, rc_matrix q) {                                    \
-        return guarded(ctx, [&] { sample_range_power<T>(ctx, OpView<T>::of(op), k, p, it, from_c<T>(omega), seed, from_c<T>(q)); });     \
-    }                                                                                                                                    \
-    rc_status rc_sample_range_adaptive_op_##SUF(rc_context *ctx, const rc_operator *op, double rel_tol, int64_t s, rc_matrix omegas,     \
-                                                uint64_t seed, rc_matrix q_cap, int64_t *rank, int64_t *hist_rank, double *hist_res,     \
-                                                int64_t hist_cap, int64_t *hist_len) {                                                   \
-        return guarded(ctx, [&] {                                                                                                        \
-            sample_range_adaptive<T>(ctx, OpView<T>::of(op), rel_tol, s, from_c<T>(omegas), seed, from_c<T>(q_cap), rank, hist_rank,     \
-                                     hist_res, hist_cap, hist_len);                                                                      \
-        });                                                                                                                              \
-    }                                                                                                                                    \
-    rc_status rc_qr_from_range_estimate_op_##SUF(rc_context *ctx, rc_matrix range, const rc_operator *op, rc_matrix q, rc_matrix r,      \
-                                                 int64_t *ind) {                                                                         \
-        return guarded(ctx, [&] { qr_from_range<T>(ctx, from_c<T>(range), OpView<T>::of(op), from_c<T>(q), from_c<T>(r), ind); });       \
-    }                                                                                                                                    \
-    rc_status rc_svd_from_range_estimate_op_##SUF(rc_context *ctx, rc_matrix range, const rc_operator *op, rc_matrix u, T *s,            \
-                                                  rc_matrix vt) {                                                                        \
-        return guarded(ctx, [&] { svd_from_range<T>(ctx, from_c<T>(range), OpView<T>::of(op), from_c<T>(u), s, from_c<T>(vt)); });       \
-    }                                                                                                                                    \
+    /* the same composition over the host's operator callbacks (rc_operator) */                                                          \
     rc_status rc_rsvd_id_op_##SUF(rc_context *ctx, const rc_operator *op, int64_t k, int64_t p, rc_matrix omega, uint64_t seed,          \
                                   const rc_rsvd_id_out *out) {                                                                           \
         return guarded(ctx, [&] {                                                                                                        \
@@ -1569,5 +1260,7 @@ rc_status rc_invert_permutation(rc_context *ctx, const int64_t *perm, int64_t n,
 
 RC_DEFINE_TYPED(f64, double)
 RC_DEFINE_TYPED(f32, float)
+RC_DEFINE_DENSE_SHARED(f64, double, double)
+RC_DEFINE_DENSE_SHARED(f32, float, float)
 
 }  // extern "C"

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -236,6 +237,23 @@ rc_status guarded(rc_context *ctx, F &&f) {
         ctx->last_error = e.what();
         return RC_RUNTIME_ERROR;
     }
+}
+
+// small device -> host read-back through the pinned buffer (synchronises the stream)
+template <typename T>
+void read_back(rc_context *c, const T *dev, T *host, size_t n) {
+    size_t bytes = n * sizeof(T);
+    if (c->pinned_size < bytes) {
+        if (c->pinned) RC_HIP(hipHostFree(c->pinned));
+        c->pinned = nullptr;
+        c->pinned_size = 0;
+        size_t want = std::max<size_t>(bytes, 1 << 16);
+        RC_HIP(hipHostMalloc(&c->pinned, want, hipHostMallocDefault));
+        c->pinned_size = want;
+    }
+    RC_HIP(hipMemcpyAsync(c->pinned, dev, bytes, hipMemcpyDeviceToHost, c->stream));
+    RC_HIP(hipStreamSynchronize(c->stream));
+    std::memcpy(host, c->pinned, bytes);
 }
 
 // ---------------------------------------------------------------------------

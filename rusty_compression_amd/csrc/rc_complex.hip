@@ -35,12 +35,14 @@ template <typename R> struct NumC;
 template <> struct NumC<double> { static __host__ __device__ double tol3z() { return 1.0536712127723509e-08; } static __host__ __device__ double eps() { return 1.1102230246251565e-16; } };
 template <> struct NumC<float> { static __host__ __device__ float tol3z() { return 2.44140625e-04f; } static __host__ __device__ float eps() { return 5.9604645e-08f; } };
 
-// the column-major working matrix (cplx<R>, CV<R> and view_of: rc_cplx.hpp)
-template <typename R>
-CV<R> tmp_cm(rc_context *c, int64_t rows, int64_t cols) {
+// the column-major working matrix (cplx<R>, CV<R> and view_of: rc_cplx.hpp); every temporary of this family has this layout, Omega too
+template <typename E>
+Mat<E> tmp_colmajor(rc_context *c, int64_t rows, int64_t cols) {
     const int64_t ld = std::max<int64_t>(rows, 1);
-    return CV<R>{c->alloc<cplx<R>>((size_t)ld * std::max<int64_t>(cols, 1)), rows, cols, 1, ld};
+    return Mat<E>{c->alloc<E>((size_t)ld * std::max<int64_t>(cols, 1)), rows, cols, 1, ld};
 }
+template <typename E>
+Mat<E> tmp_omega(rc_context *c, int64_t rows, int64_t cols) { return tmp_colmajor<E>(c, rows, cols); }
 
 // ------------------------------------------------------------------------------------------------ elementwise kernels
 template <typename R>
@@ -57,7 +59,7 @@ __global__ __launch_bounds__(256) void k_c_copy(CV<R> src, CV<R> dst, int conj) 
     }
 }
 template <typename R>
-void c_copy(rc_context *c, CV<R> src, CV<R> dst, bool conj = false) {
+void copy_mat(rc_context *c, CV<R> src, CV<R> dst, bool conj = false) {
     RC_REQUIRE(src.rows == dst.rows && src.cols == dst.cols, RC_INVALID_ARGUMENT, "complex copy: shape mismatch");
     if (dst.empty()) return;
     hipLaunchKernelGGL(k_c_copy<R>, dim3((unsigned)std::min<int64_t>(cdivi(dst.rows * dst.cols, 256), 8192)), dim3(256), 0, c->stream, src, dst, conj ? 1 : 0);
@@ -90,7 +92,7 @@ __global__ __launch_bounds__(256) void k_c_gather_cols(CV<R> src, const int64_t 
     }
 }
 template <typename R>
-void c_gather_cols(rc_context *c, CV<R> src, const int64_t *idx, CV<R> dst) {
+void gather_cols(rc_context *c, CV<R> src, const int64_t *idx, CV<R> dst) {
     if (dst.empty()) return;
     hipLaunchKernelGGL(k_c_gather_cols<R>, dim3((unsigned)std::min<int64_t>(cdivi(dst.rows * dst.cols, 256), 8192)), dim3(256), 0, c->stream, src, idx, dst, c->health_word());
 }
@@ -101,14 +103,6 @@ __global__ __launch_bounds__(256) void k_c_scale_rows(const R *s, CV<R> m) {  //
         const int64_t j = e / m.rows, i = e - j * m.rows;
         cplx<R> v = m.at(i, j);
         m.at(i, j) = s[i] * v;
-    }
-}
-template <typename R>
-__global__ __launch_bounds__(256) void k_c_sub(CV<R> y, CV<R> corr) {  // y -= corr
-    const int64_t total = y.rows * y.cols;
-    for (int64_t e = blockIdx.x * (int64_t)256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-        const int64_t j = e / y.rows, i = e - j * y.rows;
-        y.at(i, j) = y.at(i, j) - corr.at(i, j);
     }
 }
 // planes for the 4M product: re / im as real column-major matrices with the same leading dimension
@@ -133,8 +127,6 @@ __global__ __launch_bounds__(256) void k_c_combine(const R *re, const R *im, int
     }
 }
 
-template <typename R>
-__device__ inline R wsumc(R v) { return wave_sum_dpp(v); }
 
 // out[j] = ||a[:, j]||^2 (column-major a), one wave per column
 template <typename R>
@@ -143,7 +135,7 @@ __global__ __launch_bounds__(256) void k_c_col_sumsq(CV<R> a, R *out) {
     for (int64_t j = blockIdx.x * 4 + (threadIdx.x >> 6); j < a.cols; j += (int64_t)gridDim.x * 4) {
         R acc = 0;
         for (int64_t i = lane; i < a.rows; i += 64) acc += abs2(a.at(i, j));
-        acc = wsumc(acc);
+        acc = wave_sum_dpp(acc);
         if (lane == 0) out[j] = acc;
     }
 }
@@ -159,8 +151,8 @@ __global__ __launch_bounds__(1024) void k_c_fro(CV<R> a, CV<R> b, R *out2) {
         d2 += abs2(x - y);
         b2 += abs2(y);
     }
-    d2 = wsumc(d2);
-    b2 = wsumc(b2);
+    d2 = wave_sum_dpp(d2);
+    b2 = wave_sum_dpp(b2);
     if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6] = d2; sh[16 + (threadIdx.x >> 6)] = b2; }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -248,7 +240,7 @@ __global__ __launch_bounds__(1024) void k_c_qr_pivot_reflect(CV<R> w, int64_t j,
     const cplx<R> alpha = col[j];
     R acc = 0;
     for (int64_t i = j + 1 + tid; i < m; i += 1024) acc += abs2(col[i]);
-    acc = wsumc(acc);
+    acc = wave_sum_dpp(acc);
     if (lane == 0) shs[wv] = acc;
     __syncthreads();
     R ssq = 0;
@@ -283,7 +275,7 @@ __global__ __launch_bounds__(256) void k_c_qr_apply(CV<R> w, int64_t j, int pivo
             const cplx<R> vi = i == j ? cplx<R>{(R)1, (R)0} : v[i];
             dot = dot + cj(vi) * x[i];
         }
-        R dr = wsumc(dot.re), di = wsumc(dot.im);
+        R dr = wave_sum_dpp(dot.re), di = wave_sum_dpp(dot.im);
         __syncthreads();
         if (lane == 0) { sh[wv] = dr; sh[4 + wv] = di; }
         __syncthreads();
@@ -306,7 +298,7 @@ __global__ __launch_bounds__(256) void k_c_qr_apply(CV<R> w, int64_t j, int pivo
     if (temp * r * r <= NumC<R>::tol3z()) {
         R ss = 0;
         for (int64_t i = j + 1 + tid; i < m; i += 256) ss += abs2(x[i]);
-        ss = wsumc(ss);
+        ss = wave_sum_dpp(ss);
         __syncthreads();
         if (lane == 0) sh[wv] = ss;
         __syncthreads();
@@ -321,7 +313,7 @@ __global__ __launch_bounds__(256) void k_c_qr_init(CV<R> w, int64_t *jpvt, R *vn
     for (int64_t j = blockIdx.x * 4 + (threadIdx.x >> 6); j < w.cols; j += (int64_t)gridDim.x * 4) {
         R acc = 0;
         for (int64_t i = lane; i < w.rows; i += 64) acc += abs2(w.at(i, j));
-        acc = sqrt(wsumc(acc));
+        acc = sqrt(wave_sum_dpp(acc));
         if (lane == 0) { vn1[j] = acc; vn2[j] = acc; jpvt[j] = j; }
     }
 }
@@ -370,7 +362,7 @@ __global__ __launch_bounds__(256) void k_c_form_q(CV<R> w, const int64_t *jpvt, 
             const cplx<R> vi = i == j ? cplx<R>{(R)1, (R)0} : v[i];
             dot = dot + cj(vi) * x[i];
         }
-        R dr = wsumc(dot.re), di = wsumc(dot.im);
+        R dr = wave_sum_dpp(dot.re), di = wave_sum_dpp(dot.im);
         __syncthreads();
         if (lane == 0) { sh[wv] = dr; sh[4 + wv] = di; }
         __syncthreads();
@@ -401,19 +393,19 @@ void c_pivoted_qr(rc_context *c, CV<R> a, CV<R> q, CV<R> r, int64_t *ind, int64_
     RC_REQUIRE(k <= std::min(m, n), RC_INVALID_ARGUMENT, "pivoted_qr: rank %lld exceeds min(m, n)", (long long)k);
     if (n == 0) return;
     ArenaMark mark(c);
-    CV<R> w = tmp_cm<R>(c, m, n);
-    c_copy(c, a, w);
+    CV<R> w = tmp_colmajor<cplx<R>>(c, m, n);
+    copy_mat(c, a, w);
     cplx<R> *tau = c->alloc<cplx<R>>((size_t)std::max<int64_t>(k, 1));
     c_geqp3(c, w, k, ind, tau);
     if (!r.empty()) {
-        CV<R> rw = tmp_cm<R>(c, r.rows, n);
+        CV<R> rw = tmp_colmajor<cplx<R>>(c, r.rows, n);
         hipLaunchKernelGGL(k_c_extract_r<R>, dim3((unsigned)std::min<int64_t>(cdivi(r.rows * n, 256), 8192)), dim3(256), 0, c->stream, w, ind, rw);
-        c_copy(c, rw, r);
+        copy_mat(c, rw, r);
     }
     if (!q.empty()) {
-        CV<R> qw = tmp_cm<R>(c, m, q.cols);
+        CV<R> qw = tmp_colmajor<cplx<R>>(c, m, q.cols);
         hipLaunchKernelGGL(k_c_form_q<R>, dim3((unsigned)q.cols), dim3(256), 0, c->stream, w, ind, tau, k, qw);
-        c_copy(c, qw, q);
+        copy_mat(c, qw, q);
     }
 }
 
@@ -426,10 +418,10 @@ void c_lapack_geqp3(rc_context *c, CV<R> a, int64_t kmax, int64_t *jpvt, cplx<R>
     if (n == 0) return;
     if (kmax == 0 || m == 0) { iota_i64(c, jpvt, n); return; }
     ArenaMark mark(c);
-    CV<R> w = tmp_cm<R>(c, m, n);
-    c_copy(c, a, w);
+    CV<R> w = tmp_colmajor<cplx<R>>(c, m, n);
+    copy_mat(c, a, w);
     c_geqp3(c, w, kmax, jpvt, tau);
-    c_gather_cols(c, w, jpvt, a);
+    gather_cols(c, w, jpvt, a);
 }
 template <typename R>
 void c_lapack_ungqr(rc_context *c, CV<R> a, const cplx<R> *tau, int64_t k, CV<R> q) {
@@ -441,11 +433,11 @@ void c_lapack_ungqr(rc_context *c, CV<R> a, const cplx<R> *tau, int64_t k, CV<R>
     ArenaMark mark(c);
     int64_t *ident = c->alloc<int64_t>((size_t)k);
     iota_i64(c, ident, k);
-    CV<R> w = tmp_cm<R>(c, m, k), qw = tmp_cm<R>(c, m, k);
+    CV<R> w = tmp_colmajor<cplx<R>>(c, m, k), qw = tmp_colmajor<cplx<R>>(c, m, k);
     CV<R> ak = a; ak.cols = k;
-    c_copy(c, ak, w);
+    copy_mat(c, ak, w);
     hipLaunchKernelGGL(k_c_form_q<R>, dim3((unsigned)k), dim3(256), 0, c->stream, w, ident, tau, k, qw);
-    c_copy(c, qw, q);
+    copy_mat(c, qw, q);
 }
 
 // ------------------------------------------------------------------------------------------------ SVD (one-sided Jacobi)
@@ -474,10 +466,10 @@ __global__ __launch_bounds__(256) void k_c_jacobi_round(CV<R> g, CV<R> v, int r,
         aqq += abs2(b);
         apq = apq + cj(a) * b;
     }
-    app = wsumc(app);
-    aqq = wsumc(aqq);
-    apq.re = wsumc(apq.re);
-    apq.im = wsumc(apq.im);
+    app = wave_sum_dpp(app);
+    aqq = wave_sum_dpp(aqq);
+    apq.re = wave_sum_dpp(apq.re);
+    apq.im = wave_sum_dpp(apq.im);
     const R habs = hypot(apq.re, apq.im);
     const R tol = sqrt((R)M) * NumC<R>::eps();
     if (habs == (R)0 || habs <= tol * sqrt(app) * sqrt(aqq)) return;
@@ -517,7 +509,7 @@ __global__ __launch_bounds__(256) void k_c_jacobi_norms(CV<R> g, R *sig) {
     if (j >= g.cols) return;
     R acc = 0;
     for (int64_t i = lane; i < g.rows; i += 64) acc += abs2(g.at(i, j));
-    acc = wsumc(acc);
+    acc = wave_sum_dpp(acc);
     if (lane == 0) sig[j] = sqrt(acc);
 }
 template <typename R>
@@ -601,7 +593,7 @@ __global__ __launch_bounds__(1024) void k_c_complete_left_basis(CV<R> uc, const 
         }
         R part = 0;
         for (int i = tid; i < M; i += 1024) part += abs2(v[i]);
-        part = wsumc(part);
+        part = wave_sum_dpp(part);
         if (lane == 0) red_v[wv] = part;
         __syncthreads();
         if (tid == 0) {
@@ -632,7 +624,7 @@ void c_jacobi_svd_tall(rc_context *c, CV<R> g, CV<R> uc, R *s, CV<R> vc) {
     int *state = c->alloc<int>(4);
     R *sig = c->alloc<R>((size_t)n);
     int *order = c->alloc<int>((size_t)n);
-    CV<R> v = tmp_cm<R>(c, n, n);
+    CV<R> v = tmp_colmajor<cplx<R>>(c, n, n);
     fill_words(c, state, 4 * sizeof(int), 0u);
     c_fill(c, v, true);
     RC_REQUIRE(!c->capturing, RC_RUNTIME_ERROR, "complex SVD reads its convergence flag back: not capturable");
@@ -666,55 +658,50 @@ void c_compute_svd(rc_context *c, CV<R> a, CV<R> u, R *s, CV<R> vt) {
     const bool qr_first = std::max(m, n) >= 2 * r && r >= 2;
     if (m >= n) {
         if (qr_first) {
-            CV<R> q = tmp_cm<R>(c, m, n), rr = tmp_cm<R>(c, n, n), rp = tmp_cm<R>(c, n, n), ur = tmp_cm<R>(c, n, n), vc = tmp_cm<R>(c, n, n);
+            CV<R> q = tmp_colmajor<cplx<R>>(c, m, n), rr = tmp_colmajor<cplx<R>>(c, n, n), rp = tmp_colmajor<cplx<R>>(c, n, n), ur = tmp_colmajor<cplx<R>>(c, n, n), vc = tmp_colmajor<cplx<R>>(c, n, n);
             int64_t *ind = c->alloc<int64_t>((size_t)n);
             c_pivoted_qr(c, a, q, rr, ind, n);   // a P = q rr
             c_colinv(c, rr, ind, rp);            // rr P^H: a = q (rr P^H)
             c_jacobi_svd_tall(c, rp, ur, s, vc);
             c_gemm<R>(c, 0, 0, one<R>(), q, ur, zero<R>(), u);
-            c_copy(c, vc.t(), vt, true);
+            copy_mat(c, vc.t(), vt, true);
         } else {
-            CV<R> g = tmp_cm<R>(c, m, n), uc = tmp_cm<R>(c, m, n), vc = tmp_cm<R>(c, n, n);
-            c_copy(c, a, g);
+            CV<R> g = tmp_colmajor<cplx<R>>(c, m, n), uc = tmp_colmajor<cplx<R>>(c, m, n), vc = tmp_colmajor<cplx<R>>(c, n, n);
+            copy_mat(c, a, g);
             c_jacobi_svd_tall(c, g, uc, s, vc);
-            c_copy(c, uc, u);
-            c_copy(c, vc.t(), vt, true);  // vt = vc^H
+            copy_mat(c, uc, u);
+            copy_mat(c, vc.t(), vt, true);  // vt = vc^H
         }
     } else {
         // a^H = U' S V'^H  =>  a = V' S U'^H
         if (qr_first) {
-            CV<R> ah = tmp_cm<R>(c, n, m), q = tmp_cm<R>(c, n, m), rr = tmp_cm<R>(c, m, m), rp = tmp_cm<R>(c, m, m), ur = tmp_cm<R>(c, m, m), vc = tmp_cm<R>(c, m, m);
+            CV<R> ah = tmp_colmajor<cplx<R>>(c, n, m), q = tmp_colmajor<cplx<R>>(c, n, m), rr = tmp_colmajor<cplx<R>>(c, m, m), rp = tmp_colmajor<cplx<R>>(c, m, m), ur = tmp_colmajor<cplx<R>>(c, m, m), vc = tmp_colmajor<cplx<R>>(c, m, m);
             int64_t *ind = c->alloc<int64_t>((size_t)m);
-            c_copy(c, a.t(), ah, true);
+            copy_mat(c, a.t(), ah, true);
             c_pivoted_qr(c, ah, q, rr, ind, m);  // a^H P = q rr
             c_colinv(c, rr, ind, rp);
             c_jacobi_svd_tall(c, rp, ur, s, vc); // rr P^H = ur S vc^H  =>  a^H = (q ur) S vc^H  =>  a = vc S (q ur)^H
-            CV<R> qu = tmp_cm<R>(c, n, m);
+            CV<R> qu = tmp_colmajor<cplx<R>>(c, n, m);
             c_gemm<R>(c, 0, 0, one<R>(), q, ur, zero<R>(), qu);
-            c_copy(c, vc, u);
-            c_copy(c, qu.t(), vt, true);
+            copy_mat(c, vc, u);
+            copy_mat(c, qu.t(), vt, true);
         } else {
-            CV<R> g = tmp_cm<R>(c, n, m), uc = tmp_cm<R>(c, n, m), vc = tmp_cm<R>(c, m, m);
-            c_copy(c, a.t(), g, true);
+            CV<R> g = tmp_colmajor<cplx<R>>(c, n, m), uc = tmp_colmajor<cplx<R>>(c, n, m), vc = tmp_colmajor<cplx<R>>(c, m, m);
+            copy_mat(c, a.t(), g, true);
             c_jacobi_svd_tall(c, g, uc, s, vc);
-            c_copy(c, vc, u);
-            c_copy(c, uc.t(), vt, true);
+            copy_mat(c, vc, u);
+            copy_mat(c, uc.t(), vt, true);
         }
     }
 }
 
 // ------------------------------------------------------------------------------------------------ compositions
-template <typename R>
-void read_back_r(rc_context *c, const R *dev, R *host, size_t n) {
-    RC_HIP(hipMemcpyAsync(host, dev, n * sizeof(R), hipMemcpyDeviceToHost, c->stream));
-    RC_HIP(hipStreamSynchronize(c->stream));
-}
 // out = in with columns gathered by the inverse permutation: out[:, i] = in[:, inv[i]]
 template <typename R>
 void c_colinv(rc_context *c, CV<R> in, const int64_t *ind, CV<R> out) {
     int64_t *inv = c->alloc<int64_t>((size_t)std::max<int64_t>(in.cols, 1));
     invert_perm(c, ind, in.cols, inv);
-    c_gather_cols(c, in, inv, out);
+    gather_cols(c, in, inv, out);
 }
 // QRTraits::column_id (src/qr.rs:270-309)
 template <typename R>
@@ -723,259 +710,88 @@ void c_qr_column_id(rc_context *c, CV<R> q, CV<R> r, const int64_t *ind, CV<R> c
     RC_REQUIRE(r.rows == k && cm.rows == m && cm.cols == k && z.rows == k && z.cols == n && k <= n, RC_INVALID_ARGUMENT, "column_id: shapes");
     if (n == 0) return;
     ArenaMark mark(c);
-    CV<R> zt = tmp_cm<R>(c, k, n);
+    CV<R> zt = tmp_colmajor<cplx<R>>(c, k, n);
     if (k == n) {
         c_gemm(c, 0, 0, one<R>(), q, r, zero<R>(), cm);
         c_fill(c, zt, true);
     } else {
         c_fill(c, zt.sub(0, k, 0, k), true);
-        c_copy(c, r.sub(0, k, k, n - k), zt.sub(0, k, k, n - k));
-        CV<R> r11 = tmp_cm<R>(c, k, k);
-        c_copy(c, r.sub(0, k, 0, k), r11);
+        copy_mat(c, r.sub(0, k, k, n - k), zt.sub(0, k, k, n - k));
+        CV<R> r11 = tmp_colmajor<cplx<R>>(c, k, k);
+        copy_mat(c, r.sub(0, k, 0, k), r11);
         hipLaunchKernelGGL(k_c_trsm_upper<R>, dim3((unsigned)cdivi(n - k, 256)), dim3(256), 0, c->stream, r11, zt.sub(0, k, k, n - k));
         c_gemm(c, 0, 0, one<R>(), q, r11, zero<R>(), cm);
     }
-    CV<R> zo = tmp_cm<R>(c, k, n);
+    CV<R> zo = tmp_colmajor<cplx<R>>(c, k, n);
     c_colinv(c, zt, ind, zo);
-    c_copy(c, zo, z);
+    copy_mat(c, zo, z);
 }
 // LQTraits::row_id (src/qr.rs:363-403) = the adjoint of the column ID of (Q^H, L^H)
 template <typename R>
 void c_lq_row_id(rc_context *c, CV<R> l, CV<R> q, const int64_t *ind, CV<R> x, CV<R> rrows) {
     const int64_t m = l.rows, k = l.cols, n = q.cols;
     ArenaMark mark(c);
-    CV<R> qh = tmp_cm<R>(c, n, k), lh = tmp_cm<R>(c, k, m), cp = tmp_cm<R>(c, n, k), zp = tmp_cm<R>(c, k, m);
-    c_copy(c, q.t(), qh, true);
-    c_copy(c, l.t(), lh, true);
+    CV<R> qh = tmp_colmajor<cplx<R>>(c, n, k), lh = tmp_colmajor<cplx<R>>(c, k, m), cp = tmp_colmajor<cplx<R>>(c, n, k), zp = tmp_colmajor<cplx<R>>(c, k, m);
+    copy_mat(c, q.t(), qh, true);
+    copy_mat(c, l.t(), lh, true);
     c_qr_column_id(c, qh, lh, ind, cp, zp);
-    c_copy(c, zp.t(), x, true);      // X = Z'^H   (m x k)
-    c_copy(c, cp.t(), rrows, true);  // R = C'^H   (k x n)
+    copy_mat(c, zp.t(), x, true);      // X = Z'^H   (m x k)
+    copy_mat(c, cp.t(), rrows, true);  // R = C'^H   (k x n)
 }
 // P A = L Q: pivoted QR of A^H, conjugate-transposed back (src/pivoted_qr.rs:32-41)
 template <typename R>
 void c_pivoted_lq(rc_context *c, CV<R> a, CV<R> l, CV<R> q, int64_t *ind, int64_t k) {
     const int64_t m = a.rows, n = a.cols;
     ArenaMark mark(c);
-    CV<R> ah = tmp_cm<R>(c, n, m), qp = tmp_cm<R>(c, n, k), rp = tmp_cm<R>(c, k, m);
-    c_copy(c, a.t(), ah, true);
+    CV<R> ah = tmp_colmajor<cplx<R>>(c, n, m), qp = tmp_colmajor<cplx<R>>(c, n, k), rp = tmp_colmajor<cplx<R>>(c, k, m);
+    copy_mat(c, a.t(), ah, true);
     c_pivoted_qr(c, ah, qp, rp, ind, k);
-    c_copy(c, rp.t(), l, true);
-    c_copy(c, qp.t(), q, true);
+    copy_mat(c, rp.t(), l, true);
+    copy_mat(c, qp.t(), q, true);
 }
 template <typename R>
-void c_gaussian(rc_context *c, CV<R> out, uint64_t seed, uint64_t offset) {
+void fill_gaussian(rc_context *c, CV<R> out, uint64_t seed, uint64_t offset) {
     // element (i, j): re = normal number 2 (i cols + j), im = the next one (src/random_matrix.rs:136-143), row-major order
     if (out.empty()) return;
     ArenaMark mark(c);
     cplx<R> *tmp = c->alloc<cplx<R>>((size_t)out.rows * out.cols);
     fill_gaussian<R>(c, Mat<R>(reinterpret_cast<R *>(tmp), out.rows, 2 * out.cols, 2 * out.cols, 1), seed, 2 * offset);
-    c_copy(c, CV<R>{tmp, out.rows, out.cols, out.cols, 1}, out);
+    copy_mat(c, CV<R>{tmp, out.rows, out.cols, out.cols, 1}, out);
 }
 template <typename R>
-void c_max_col_norm_dev(rc_context *c, CV<R> y, R *out_dev) {
+void max_col_norm_dev(rc_context *c, CV<R> y, R *out_dev) {
     ArenaMark mark(c);
-    CV<R> w = tmp_cm<R>(c, y.rows, y.cols);
-    c_copy(c, y, w);
+    CV<R> w = tmp_colmajor<cplx<R>>(c, y.rows, y.cols);
+    copy_mat(c, y, w);
     R *ss = c->alloc<R>((size_t)std::max<int64_t>(y.cols, 1));
     hipLaunchKernelGGL(k_c_col_sumsq<R>, dim3((unsigned)std::min<int64_t>(cdivi(std::max<int64_t>(y.cols, 1), 4), 8192)), dim3(256), 0, c->stream, w, ss);
     max_sqrt<R>(c, ss, y.cols, out_dev);
 }
-// SampleRange::sample_range_by_rank (src/random_sampling.rs:103-118)
-// The operator the complex range finders sample (the real twin is OpView in rc_api.hip): a dense device matrix or the host's
-// callback table (rc_operator; the views handed over are interleaved-complex rc_matrix descriptors, strides in complex elements).
-// conj_matmat is A^H x (src/types.rs:128-132); the projection B = Q^H A is the conjugate transpose of the callback's A^H Q
-// (the reference: conj_matmat(..).t().map(conj), src/qr.rs:316-317), one conjugating copy.
-template <typename R>
-struct COp {
-    int64_t rows = 0, cols = 0;
-    CV<R> dense{nullptr, 0, 0, 0, 0};
-    const rc_operator *cb = nullptr;
-    static COp of(CV<R> a) { COp o; o.rows = a.rows; o.cols = a.cols; o.dense = a; return o; }
-    static COp of(const rc_operator *op) {
-        RC_REQUIRE(op != nullptr && op->matmat != nullptr && op->rows >= 0 && op->cols >= 0, RC_INVALID_ARGUMENT, "rc_operator: null table / matmat or negative extent");
-        COp o; o.rows = op->rows; o.cols = op->cols; o.cb = op; return o;
-    }
-    static rc_matrix to_c(CV<R> m) { rc_matrix r; r.data = m.p; r.rows = m.rows; r.cols = m.cols; r.row_stride = m.rs; r.col_stride = m.cs; return r; }
-    void call(rc_context *c, rc_operator_product_fn fn, const char *what, CV<R> x, CV<R> y) const {
-        RC_REQUIRE(fn != nullptr, RC_INVALID_ARGUMENT, "rc_operator: this call needs the operator's %s", what);
-        RC_REQUIRE(!c->capturing, RC_INVALID_ARGUMENT, "rc_operator: callbacks cannot be recorded into a hipGraph");
-        const rc_status st = fn(cb->user, c, to_c(x), to_c(y));
-        if (st != RC_OK) fail(st, "operator callback %s (%lld x %lld -> %lld x %lld) returned status %d", what, (long long)x.rows, (long long)x.cols, (long long)y.rows, (long long)y.cols, (int)st);
-    }
-    void matmat(rc_context *c, CV<R> x, CV<R> y) const {
-        RC_REQUIRE(x.rows == cols && y.rows == rows && x.cols == y.cols, RC_INVALID_ARGUMENT, "matmat: shape mismatch");
-        if (cb) call(c, cb->matmat, "matmat", x, y);
-        else c_gemm(c, 0, 0, one<R>(), dense, x, zero<R>(), y);
-    }
-    void conj_matmat(rc_context *c, CV<R> x, CV<R> y) const {
-        RC_REQUIRE(x.rows == rows && y.rows == cols && x.cols == y.cols, RC_INVALID_ARGUMENT, "conj_matmat: shape mismatch");
-        if (cb) call(c, cb->conj_matmat, "conj_matmat", x, y);
-        else c_gemm(c, 2, 0, one<R>(), dense, x, zero<R>(), y);
-    }
-    // b (k x n) = range^H A
-    void project(rc_context *c, CV<R> range, CV<R> b) const {
-        if (!cb) { c_gemm(c, 2, 0, one<R>(), range, dense, zero<R>(), b); return; }
-        ArenaMark mark(c);
-        CV<R> t = tmp_cm<R>(c, cols, range.cols);
-        conj_matmat(c, range, t);
-        c_copy(c, t.t(), b, true);
-    }
-};
 
+// ---- the complex family's spelling of the primitives rc_dense_shared.hpp is written in (OpView, the range finders, qr_from_range,
+// rank_by_tolerance, apply_perm_matrix and their entry points stand there, once for real and complex) ----
 template <typename R>
-void c_sample_range_by_rank(rc_context *c, const COp<R> &a, int64_t k, int64_t p, CV<R> omega, uint64_t seed, CV<R> q) {
-    const int64_t m = a.rows, n = a.cols, l = k + p;
-    RC_REQUIRE(k >= 0 && p >= 0, RC_INVALID_ARGUMENT, "sample_range_by_rank: negative k or p");
-    const int64_t kk = std::min(k, std::min(m, l));
-    RC_REQUIRE(q.rows == m && q.cols == kk, RC_INVALID_ARGUMENT, "sample_range_by_rank: q must be %lld x %lld", (long long)m, (long long)kk);
-    if (kk == 0) return;
-    ArenaMark mark(c);
-    if (omega.p == nullptr) {
-        omega = tmp_cm<R>(c, n, l);
-        c_gaussian(c, omega, seed, 0);
-    } else {
-        RC_REQUIRE(omega.rows == n && omega.cols == l, RC_INVALID_ARGUMENT, "sample_range_by_rank: omega must be %lld x %lld", (long long)n, (long long)l);
-    }
-    CV<R> y = tmp_cm<R>(c, m, l);
-    a.matmat(c, omega, y);
-    int64_t *ind = c->alloc<int64_t>((size_t)l);
-    c_pivoted_qr(c, y, q, CV<R>{nullptr, 0, 0, 0, 0}, ind, kk);
+void product(rc_context *c, int alpha, bool adj_a, CV<R> a, CV<R> b, int beta, CV<R> cm) {
+    c_gemm<R>(c, adj_a ? 2 : 0, 0, cplx<R>{(R)alpha, (R)0}, a, b, cplx<R>{(R)beta, (R)0}, cm);
 }
 template <typename R>
-CV<R> c_orth_full(rc_context *c, CV<R> w) {
-    const int64_t k = std::min(w.rows, w.cols);
-    CV<R> q = tmp_cm<R>(c, w.rows, k);
-    int64_t *ind = c->alloc<int64_t>((size_t)std::max<int64_t>(w.cols, 1));
-    c_pivoted_qr(c, w, q, CV<R>{nullptr, 0, 0, 0, 0}, ind, k);
-    return q;
-}
-// SampleRangePowerIteration (src/random_sampling.rs:131-160) with the reference's single surviving step
-template <typename R>
-void c_sample_range_power(rc_context *c, const COp<R> &a, int64_t k, int64_t p, int64_t it_count, CV<R> omega, uint64_t seed, CV<R> q) {
-    if (it_count <= 0) { c_sample_range_by_rank(c, a, k, p, omega, seed, q); return; }
-    const int64_t m = a.rows, n = a.cols, l = k + p;
-    ArenaMark mark(c);
-    if (omega.p == nullptr) {
-        omega = tmp_cm<R>(c, n, l);
-        c_gaussian(c, omega, seed, 0);
-    } else {
-        RC_REQUIRE(omega.rows == n && omega.cols == l, RC_INVALID_ARGUMENT, "sample_range_power_iteration: omega must be %lld x %lld", (long long)n, (long long)l);
-    }
-    CV<R> y1 = tmp_cm<R>(c, m, l);
-    a.matmat(c, omega, y1);
-    const int64_t steps = c->opt_power_fixed ? it_count : 1;
-    for (int64_t it = 0; it < steps; ++it) {
-        CV<R> q0 = c_orth_full(c, y1);
-        CV<R> z = tmp_cm<R>(c, n, q0.cols);
-        a.conj_matmat(c, q0, z);
-        CV<R> wq = c_orth_full(c, z);
-        y1 = tmp_cm<R>(c, m, wq.cols);
-        a.matmat(c, wq, y1);
-    }
-    const int64_t kk = std::min(k, std::min(m, y1.cols));
-    RC_REQUIRE(q.rows == m && q.cols == kk, RC_INVALID_ARGUMENT, "sample_range_power_iteration: q must be %lld x %lld", (long long)m, (long long)kk);
-    int64_t *ind = c->alloc<int64_t>((size_t)std::max<int64_t>(y1.cols, 1));
-    c_pivoted_qr(c, y1, q, CV<R>{nullptr, 0, 0, 0, 0}, ind, kk);
-}
-// AdaptiveSampling::sample_range_adaptive (src/random_sampling.rs:223-274)
-template <typename R>
-void c_sample_range_adaptive(rc_context *c, const COp<R> &a, double rel_tol_d, int64_t s, CV<R> omegas, uint64_t seed, CV<R> qcap, int64_t *rank_out, int64_t *hist_rank,
-                             double *hist_res, int64_t hist_cap, int64_t *hist_len) {
-    const int64_t m = a.rows, n = a.cols, cap = qcap.cols;
-    RC_REQUIRE(s >= 1 && qcap.rows == m, RC_INVALID_ARGUMENT, "sample_range_adaptive: bad sample_size or q buffer");
-    const bool explicit_omega = omegas.p != nullptr;
-    if (explicit_omega) RC_REQUIRE(omegas.rows == n, RC_INVALID_ARGUMENT, "sample_range_adaptive: omegas must have %lld rows", (long long)n);
-    const R tol_factor = (R)(10.0 * std::sqrt(2.0 / 3.14159265358979323846));
-    const R rel_tol = (R)rel_tol_d;
-    const int64_t sq = std::min(m, s);
-    int64_t blocks_used = 0;
-    CV<R> omega = tmp_cm<R>(c, n, s), y = tmp_cm<R>(c, m, s), qacc = tmp_cm<R>(c, m, cap), bacc = tmp_cm<R>(c, cap, n), t1 = tmp_cm<R>(c, cap, s);
-    int64_t *ind = c->alloc<int64_t>((size_t)s);
-    R *scal = c->alloc<R>(1);
-    auto next_omega = [&]() {
-        if (explicit_omega) {
-            RC_REQUIRE((blocks_used + 1) * s <= omegas.cols, RC_COMPRESSION_ERROR, "sample_range_adaptive: explicit Omega blocks exhausted after %lld blocks", (long long)blocks_used);
-            c_copy(c, omegas.sub(0, n, blocks_used * s, s), omega);
-        } else {
-            c_gaussian(c, omega, seed, (uint64_t)blocks_used * (uint64_t)(n * s));
-        }
-        ++blocks_used;
-    };
-    next_omega();
-    a.matmat(c, omega, y);
-    R mc;
-    c_max_col_norm_dev(c, y, scal);
-    read_back_r(c, scal, &mc, 1);
-    const R operator_norm = mc * tol_factor;
-    R max_norm = operator_norm;
-    int64_t r = 0, nh = 0;
-    const cplx<R> minus_one{(R)-1, (R)0};
-    while (max_norm / operator_norm >= rel_tol) {
-        RC_REQUIRE(r + sq <= cap, RC_COMPRESSION_ERROR, "sample_range_adaptive: basis capacity %lld exhausted at rank %lld", (long long)cap, (long long)r);
-        if (r > 0) {  // y -= q (q^H y)
-            CV<R> qr_ = qacc.sub(0, m, 0, r), tt = t1.sub(0, r, 0, s);
-            c_gemm(c, 2, 0, one<R>(), qr_, y, zero<R>(), tt);
-            c_gemm(c, 0, 0, minus_one, qr_, tt, one<R>(), y);
-        }
-        CV<R> qnew = qacc.sub(0, m, r, sq);
-        c_pivoted_qr(c, y, qnew, CV<R>{nullptr, 0, 0, 0, 0}, ind, sq);
-        a.project(c, qnew, bacc.sub(r, sq, 0, n));  // b = [b ; (A^H Q_new)^H] = Q_new^H A
-        r += sq;
-        next_omega();
-        {
-            CV<R> qr_ = qacc.sub(0, m, 0, r), tt = t1.sub(0, r, 0, s);
-            c_gemm(c, 0, 0, one<R>(), bacc.sub(0, r, 0, n), omega, zero<R>(), tt);
-            a.matmat(c, omega, y);
-            c_gemm(c, 0, 0, minus_one, qr_, tt, one<R>(), y);
-        }
-        c_max_col_norm_dev(c, y, scal);
-        read_back_r(c, scal, &mc, 1);
-        max_norm = mc * tol_factor;
-        if (nh < hist_cap) {
-            if (hist_rank) hist_rank[nh] = r;
-            if (hist_res) hist_res[nh] = (double)(max_norm / operator_norm);
-        }
-        ++nh;
-    }
-    c_copy(c, qacc.sub(0, m, 0, r), qcap.sub(0, m, 0, r));
-    if (rank_out) *rank_out = r;
-    if (hist_len) *hist_len = std::min(nh, hist_cap);
-    RC_HIP(hipStreamSynchronize(c->stream));
-}
+void qrcp(rc_context *c, CV<R> w, int64_t k, CV<R> q, CV<R> r, int64_t *ind) { c_pivoted_qr<R>(c, w, q, r, ind, k); }
 
-template <typename R>
-void c_rank_by_tolerance(rc_context *c, CV<R> tri, double tol, int64_t *rank) {
-    RC_REQUIRE(tol < 1.0 && 0.0 <= tol, RC_INVALID_ARGUMENT, "Require 0 <= tol < 1.0");
-    const int64_t len = std::min(tri.rows, tri.cols);
-    RC_REQUIRE(len >= 1, RC_COMPRESSION_ERROR, "rank_by_tolerance: empty factor");
-    ArenaMark mark(c);
-    cplx<R> *d = c->alloc<cplx<R>>((size_t)len);
-    c_copy(c, CV<R>{tri.p, len, 1, tri.rs + tri.cs, 1}, CV<R>{d, len, 1, 1, len});
-    std::vector<cplx<R>> h((size_t)len);
-    RC_HIP(hipMemcpyAsync(h.data(), d, (size_t)len * sizeof(cplx<R>), hipMemcpyDeviceToHost, c->stream));
-    RC_HIP(hipStreamSynchronize(c->stream));
-    const double d0 = std::hypot((double)h[0].re, (double)h[0].im);
-    for (int64_t i = 0; i < len; ++i)
-        if (std::hypot((double)h[i].re, (double)h[i].im) / d0 < tol) { *rank = i; return; }  // qr.rs:194
-    fail(RC_COMPRESSION_ERROR, "Could not compress to desired tolerance");
-}
+}  // namespace
 
+#include "rc_dense_shared.hpp"
+
+namespace {
+
+// SVDTraits::compute_from_range_estimate (src/svd.rs:171-183)
 template <typename R>
-void c_apply_perm(rc_context *c, int mode, CV<R> in, const int64_t *perm, int64_t plen, CV<R> out) {
-    RC_REQUIRE(in.rows == out.rows && in.cols == out.cols, RC_INVALID_ARGUMENT, "apply_permutation: shape mismatch");
-    RC_REQUIRE(mode >= 0 && mode <= 3, RC_INVALID_ARGUMENT, "apply_permutation: unknown mode %d", mode);
-    ArenaMark mark(c);
-    const bool cols = (mode == RC_PERM_COL || mode == RC_PERM_COLINV), inv = (mode == RC_PERM_COLINV || mode == RC_PERM_ROWINV);
-    if (cols) RC_REQUIRE(plen == in.cols, RC_INVALID_ARGUMENT, "Length of index array and number of columns differ.");
-    else RC_REQUIRE(plen == in.rows, RC_INVALID_ARGUMENT, "Length of index array and number of rows differ.");
-    const int64_t *idx = perm;
-    if (inv) {
-        int64_t *iv = c->alloc<int64_t>((size_t)std::max<int64_t>(plen, 1));
-        invert_perm(c, perm, plen, iv);
-        idx = iv;
-    }
-    if (cols) c_gather_cols(c, in, idx, out);
-    else c_gather_cols(c, in.t(), idx, out.t());
+void svd_from_range(rc_context *c, CV<R> range, const OpView<cplx<R>> &a, CV<R> u, R *s, CV<R> vt) {
+    const int64_t rr = range.cols, n = a.cols, r = std::min(rr, n);
+    RC_REQUIRE(range.rows == a.rows && u.rows == a.rows && u.cols == r && vt.rows == r && vt.cols == n, RC_INVALID_ARGUMENT, "svd_from_range_estimate: shape mismatch");
+    CV<R> b = tmp_colmajor<cplx<R>>(c, rr, n), ub = tmp_colmajor<cplx<R>>(c, rr, r);
+    a.project(c, range, b);
+    c_compute_svd<R>(c, b, ub, s, vt);
+    product(c, 1, false, range, ub, 0, u);
 }
 
 static rc_status c_svd_rank_fwd(rc_context *ctx, const double *s, int64_t len, double tol, int64_t *rank) { return rc_svd_rank_by_tolerance_f64(ctx, s, len, tol, rank); }
@@ -988,20 +804,20 @@ void c_rsvd_id(rc_context *c, CV<R> a, int64_t k, int64_t p, CV<R> omega, uint64
     RC_REQUIRE(k >= 1 && k + p <= m && k <= n, RC_INVALID_ARGUMENT, "rsvd_id: need 1 <= k, k + p <= m, k <= n");
     ArenaMark mark(c);
     CV<R> range = view_of<R>(o.range_q);
-    if (range.p == nullptr) range = tmp_cm<R>(c, m, k);
+    if (range.p == nullptr) range = tmp_colmajor<cplx<R>>(c, m, k);
     RC_REQUIRE(range.rows == m && range.cols == k, RC_INVALID_ARGUMENT, "rsvd_id: range_q must be m x k");
-    c_sample_range_by_rank<R>(c, COp<R>::of(a), k, p, omega, seed, range);
-    CV<R> b = tmp_cm<R>(c, k, n);
+    sample_range_by_rank(c, OpView<cplx<R>>::of(a), k, p, omega, seed, range);
+    CV<R> b = tmp_colmajor<cplx<R>>(c, k, n);
     c_gemm<R>(c, 2, 0, one<R>(), range, a, zero<R>(), b);
     const bool want_id = o.id_c.data || o.id_z.data || o.qr_q.data || o.qr_r.data || o.qr_ind;
     const bool want_svd = o.u.data || o.s || o.vt.data;
     if (want_svd) RC_REQUIRE(o.u.data && o.s && o.vt.data, RC_INVALID_ARGUMENT, "rsvd_id: u, s, vt must be given together");
     if (want_id) {
-        CV<R> qb = tmp_cm<R>(c, k, k);
-        CV<R> r = o.qr_r.data ? view_of<R>(o.qr_r) : tmp_cm<R>(c, k, n);
+        CV<R> qb = tmp_colmajor<cplx<R>>(c, k, k);
+        CV<R> r = o.qr_r.data ? view_of<R>(o.qr_r) : tmp_colmajor<cplx<R>>(c, k, n);
         int64_t *ind = o.qr_ind ? o.qr_ind : c->alloc<int64_t>((size_t)n);
         c_pivoted_qr<R>(c, b, qb, r, ind, k);  // works on its own copy of b
-        CV<R> q = o.qr_q.data ? view_of<R>(o.qr_q) : tmp_cm<R>(c, m, k);
+        CV<R> q = o.qr_q.data ? view_of<R>(o.qr_q) : tmp_colmajor<cplx<R>>(c, m, k);
         c_gemm<R>(c, 0, 0, one<R>(), range, qb, zero<R>(), q);
         if (o.id_c.data || o.id_z.data) {
             RC_REQUIRE(o.id_c.data && o.id_z.data, RC_INVALID_ARGUMENT, "rsvd_id: id_c and id_z must be given together");
@@ -1009,7 +825,7 @@ void c_rsvd_id(rc_context *c, CV<R> a, int64_t k, int64_t p, CV<R> omega, uint64
         }
     }
     if (want_svd) {
-        CV<R> ub = tmp_cm<R>(c, k, k);
+        CV<R> ub = tmp_colmajor<cplx<R>>(c, k, k);
         c_compute_svd<R>(c, b, ub, static_cast<R *>(o.s), view_of<R>(o.vt));
         c_gemm<R>(c, 0, 0, one<R>(), range, ub, zero<R>(), view_of<R>(o.u));
     }
@@ -1036,7 +852,7 @@ void c_batch_column_id(rc_context *const *ctxs, int nctx, const rc_matrix *mats,
         CV<R> cm{cz, m, k, k, 1}, z{cz + (size_t)m * k, k, n, n, 1};
         c->reset_arena();
         ArenaMark mark(c);
-        CV<R> q = tmp_cm<R>(c, m, k), r = tmp_cm<R>(c, k, n);
+        CV<R> q = tmp_colmajor<cplx<R>>(c, m, k), r = tmp_colmajor<cplx<R>>(c, k, n);
         c_pivoted_qr<R>(c, A, q, r, ind, k);
         c_qr_column_id<R>(c, q, r, ind, cm, z);
     }
@@ -1050,7 +866,7 @@ extern "C" {
 
 #define RC_DEFINE_COMPLEX(SUF, R, CT)                                                                                                     \
     rc_status rc_random_gaussian_##SUF(rc_context *ctx, rc_matrix out, uint64_t seed, uint64_t offset) {                                  \
-        return guarded(ctx, [&] { c_gaussian<R>(ctx, view_of<R>(out), seed, offset); });                                                  \
+        return guarded(ctx, [&] { fill_gaussian<R>(ctx, view_of<R>(out), seed, offset); });                                               \
     }                                                                                                                                     \
     rc_status rc_matmat_##SUF(rc_context *ctx, rc_matrix a, rc_matrix x, rc_matrix y) {                                                   \
         return guarded(ctx, [&] { c_gemm<R>(ctx, 0, 0, one<R>(), view_of<R>(a), view_of<R>(x), zero<R>(), view_of<R>(y)); });             \
@@ -1071,18 +887,8 @@ extern "C" {
             R *d = ctx->alloc<R>(2);                                                                                                      \
             hipLaunchKernelGGL(k_c_fro<R>, dim3(1), dim3(1024), 0, ctx->stream, A, B, d);                                                 \
             R h[2];                                                                                                                       \
-            read_back_r<R>(ctx, d, h, 2);                                                                                                 \
+            read_back(ctx, d, h, 2);                                                                                                      \
             *out = std::sqrt(h[0]) / std::sqrt(h[1]);                                                                                     \
-        });                                                                                                                               \
-    }                                                                                                                                     \
-    rc_status rc_apply_permutation_matrix_##SUF(rc_context *ctx, int32_t mode, rc_matrix in, const int64_t *perm, int64_t plen, rc_matrix out) { \
-        return guarded(ctx, [&] { c_apply_perm<R>(ctx, mode, view_of<R>(in), perm, plen, view_of<R>(out)); });                            \
-    }                                                                                                                                     \
-    rc_status rc_apply_permutation_vector_##SUF(rc_context *ctx, int32_t mode, rc_matrix in, const int64_t *perm, int64_t plen, rc_matrix out) { \
-        return guarded(ctx, [&] {                                                                                                         \
-            RC_REQUIRE(mode == RC_VPERM_INV || mode == RC_VPERM_NOINV, RC_INVALID_ARGUMENT, "unknown vector permutation mode");           \
-            RC_REQUIRE(in.cols == 1 && out.cols == 1 && plen == in.rows, RC_INVALID_ARGUMENT, "The input vector and the index array must have the same length"); \
-            c_apply_perm<R>(ctx, mode == RC_VPERM_INV ? RC_PERM_ROWINV : RC_PERM_ROW, view_of<R>(in), perm, plen, view_of<R>(out));       \
         });                                                                                                                               \
     }                                                                                                                                     \
     rc_status rc_pivoted_qr_##SUF(rc_context *ctx, rc_matrix a, rc_matrix q, rc_matrix r, int64_t *ind) {                                 \
@@ -1116,13 +922,10 @@ extern "C" {
     rc_status rc_compute_svd_##SUF(rc_context *ctx, rc_matrix a, rc_matrix u, R *s, rc_matrix vt) {                                       \
         return guarded(ctx, [&] { c_compute_svd<R>(ctx, view_of<R>(a), view_of<R>(u), s, view_of<R>(vt)); });                             \
     }                                                                                                                                     \
-    rc_status rc_rank_by_tolerance_##SUF(rc_context *ctx, rc_matrix tri, double tol, int64_t *rank) {                                     \
-        return guarded(ctx, [&] { c_rank_by_tolerance<R>(ctx, view_of<R>(tri), tol, rank); });                                            \
-    }                                                                                                                                     \
     rc_status rc_qr_to_mat_##SUF(rc_context *ctx, rc_matrix q, rc_matrix r, const int64_t *ind, rc_matrix out) {                          \
         return guarded(ctx, [&] {                                                                                                         \
             CV<R> Rr = view_of<R>(r);                                                                                                     \
-            CV<R> rp = tmp_cm<R>(ctx, Rr.rows, Rr.cols);                                                                                  \
+            CV<R> rp = tmp_colmajor<cplx<R>>(ctx, Rr.rows, Rr.cols);                                                                      \
             c_colinv<R>(ctx, Rr, ind, rp);                                                                                                \
             c_gemm<R>(ctx, 0, 0, one<R>(), view_of<R>(q), rp, zero<R>(), view_of<R>(out));                                                \
         });                                                                                                                               \
@@ -1130,7 +933,7 @@ extern "C" {
     rc_status rc_lq_to_mat_##SUF(rc_context *ctx, rc_matrix l, rc_matrix q, const int64_t *ind, rc_matrix out) {                          \
         return guarded(ctx, [&] {                                                                                                         \
             CV<R> L = view_of<R>(l);                                                                                                      \
-            CV<R> lp = tmp_cm<R>(ctx, L.rows, L.cols);                                                                                    \
+            CV<R> lp = tmp_colmajor<cplx<R>>(ctx, L.rows, L.cols);                                                                        \
             c_colinv<R>(ctx, L.t(), ind, lp.t());                                                                                         \
             c_gemm<R>(ctx, 0, 0, one<R>(), lp, view_of<R>(q), zero<R>(), view_of<R>(out));                                                \
         });                                                                                                                               \
@@ -1141,22 +944,11 @@ extern "C" {
     rc_status rc_lq_row_id_##SUF(rc_context *ctx, rc_matrix l, rc_matrix q, const int64_t *ind, rc_matrix x, rc_matrix rr) {              \
         return guarded(ctx, [&] { c_lq_row_id<R>(ctx, view_of<R>(l), view_of<R>(q), ind, view_of<R>(x), view_of<R>(rr)); });              \
     }                                                                                                                                     \
-    rc_status rc_qr_from_range_estimate_##SUF(rc_context *ctx, rc_matrix range, rc_matrix a, rc_matrix q, rc_matrix r, int64_t *ind) {    \
-        return guarded(ctx, [&] {                                                                                                         \
-            CV<R> Rg = view_of<R>(range), A = view_of<R>(a), Q = view_of<R>(q), Rr = view_of<R>(r);                                       \
-            const int64_t rr = Rg.cols, n = A.cols, k = std::min(rr, n);                                                                  \
-            RC_REQUIRE(Rg.rows == A.rows && Q.rows == A.rows && Q.cols == k && Rr.rows == k && Rr.cols == n, RC_INVALID_ARGUMENT, "qr_from_range_estimate: shape mismatch"); \
-            CV<R> b = tmp_cm<R>(ctx, rr, n), qb = tmp_cm<R>(ctx, rr, k);                                                                  \
-            c_gemm<R>(ctx, 2, 0, one<R>(), Rg, A, zero<R>(), b);                                                                          \
-            c_pivoted_qr<R>(ctx, b, qb, Rr, ind, k);                                                                                      \
-            c_gemm<R>(ctx, 0, 0, one<R>(), Rg, qb, zero<R>(), Q);                                                                         \
-        });                                                                                                                               \
-    }                                                                                                                                     \
     rc_status rc_svd_to_mat_##SUF(rc_context *ctx, rc_matrix u, const R *s, rc_matrix vt, rc_matrix out) {                                \
         return guarded(ctx, [&] {                                                                                                         \
             CV<R> VT = view_of<R>(vt);                                                                                                    \
-            CV<R> sv = tmp_cm<R>(ctx, VT.rows, VT.cols);                                                                                  \
-            c_copy<R>(ctx, VT, sv);                                                                                                       \
+            CV<R> sv = tmp_colmajor<cplx<R>>(ctx, VT.rows, VT.cols);                                                                      \
+            copy_mat<R>(ctx, VT, sv);                                                                                                     \
             if (!sv.empty()) hipLaunchKernelGGL(k_c_scale_rows<R>, dim3((unsigned)std::min<int64_t>(cdivi(sv.rows * sv.cols, 256), 8192)), dim3(256), 0, ctx->stream, s, sv); \
             c_gemm<R>(ctx, 0, 0, one<R>(), view_of<R>(u), sv, zero<R>(), view_of<R>(out));                                                \
         });                                                                                                                               \
@@ -1166,29 +958,18 @@ extern "C" {
             CV<R> VT = view_of<R>(vt), Q = view_of<R>(q);                                                                                 \
             const int64_t k = Q.cols;                                                                                                     \
             RC_REQUIRE(k <= std::min(VT.rows, VT.cols), RC_INVALID_ARGUMENT, "svd_to_qr: rank exceeds min(r, n)");                        \
-            CV<R> w = tmp_cm<R>(ctx, VT.rows, VT.cols), qb = tmp_cm<R>(ctx, VT.rows, k);                                                  \
-            c_copy<R>(ctx, VT, w);                                                                                                        \
+            CV<R> w = tmp_colmajor<cplx<R>>(ctx, VT.rows, VT.cols), qb = tmp_colmajor<cplx<R>>(ctx, VT.rows, k);                          \
+            copy_mat<R>(ctx, VT, w);                                                                                                      \
             if (!w.empty()) hipLaunchKernelGGL(k_c_scale_rows<R>, dim3((unsigned)std::min<int64_t>(cdivi(w.rows * w.cols, 256), 8192)), dim3(256), 0, ctx->stream, s, w); \
             c_pivoted_qr<R>(ctx, w, qb, view_of<R>(r), ind, k);                                                                           \
             c_gemm<R>(ctx, 0, 0, one<R>(), view_of<R>(u), qb, zero<R>(), Q);                                                              \
-        });                                                                                                                               \
-    }                                                                                                                                     \
-    rc_status rc_svd_from_range_estimate_##SUF(rc_context *ctx, rc_matrix range, rc_matrix a, rc_matrix u, R *s, rc_matrix vt) {          \
-        return guarded(ctx, [&] {                                                                                                         \
-            CV<R> Rg = view_of<R>(range), A = view_of<R>(a), U = view_of<R>(u), VT = view_of<R>(vt);                                      \
-            const int64_t rr = Rg.cols, n = A.cols, r = std::min(rr, n);                                                                  \
-            RC_REQUIRE(Rg.rows == A.rows && U.rows == A.rows && U.cols == r && VT.rows == r && VT.cols == n, RC_INVALID_ARGUMENT, "svd_from_range_estimate: shape mismatch"); \
-            CV<R> b = tmp_cm<R>(ctx, rr, n), ub = tmp_cm<R>(ctx, rr, r);                                                                  \
-            c_gemm<R>(ctx, 2, 0, one<R>(), Rg, A, zero<R>(), b);                                                                          \
-            c_compute_svd<R>(ctx, b, ub, s, VT);                                                                                          \
-            c_gemm<R>(ctx, 0, 0, one<R>(), Rg, ub, zero<R>(), U);                                                                         \
         });                                                                                                                               \
     }                                                                                                                                     \
     rc_status rc_column_id_two_sided_##SUF(rc_context *ctx, rc_matrix c, rc_matrix c_out, rc_matrix x, int64_t *row_ind) {                \
         return guarded(ctx, [&] {                                                                                                         \
             CV<R> C = view_of<R>(c);                                                                                                      \
             const int64_t m = C.rows, k = C.cols, kk = std::min(m, k);                                                                    \
-            CV<R> l = tmp_cm<R>(ctx, m, kk), ql = tmp_cm<R>(ctx, kk, k);                                                                  \
+            CV<R> l = tmp_colmajor<cplx<R>>(ctx, m, kk), ql = tmp_colmajor<cplx<R>>(ctx, kk, k);                                          \
             c_pivoted_lq<R>(ctx, C, l, ql, row_ind, kk); /* LQ::compute_from, qr.rs:354-362 */                                            \
             c_lq_row_id<R>(ctx, l, ql, row_ind, view_of<R>(c_out), view_of<R>(x));                                                        \
         });                                                                                                                               \
@@ -1197,72 +978,16 @@ extern "C" {
         return guarded(ctx, [&] {                                                                                                         \
             CV<R> Rr = view_of<R>(r);                                                                                                     \
             const int64_t k = Rr.rows, n = Rr.cols, kk = std::min(k, n);                                                                  \
-            CV<R> q = tmp_cm<R>(ctx, k, kk), rr = tmp_cm<R>(ctx, kk, n);                                                                  \
+            CV<R> q = tmp_colmajor<cplx<R>>(ctx, k, kk), rr = tmp_colmajor<cplx<R>>(ctx, kk, n);                                          \
             c_pivoted_qr<R>(ctx, Rr, q, rr, col_ind, kk);                                                                                 \
             c_qr_column_id<R>(ctx, q, rr, col_ind, view_of<R>(x), view_of<R>(r_out));                                                     \
-        });                                                                                                                               \
-    }                                                                                                                                     \
-    rc_status rc_max_col_norm_##SUF(rc_context *ctx, rc_matrix y, R *out) {                                                               \
-        return guarded(ctx, [&] {                                                                                                         \
-            R *d = ctx->alloc<R>(1);                                                                                                      \
-            c_max_col_norm_dev<R>(ctx, view_of<R>(y), d);                                                                                 \
-            read_back_r<R>(ctx, d, out, 1);                                                                                               \
-        });                                                                                                                               \
-    }                                                                                                                                     \
-    rc_status rc_sample_range_by_rank_##SUF(rc_context *ctx, rc_matrix a, int64_t k, int64_t p, rc_matrix omega, uint64_t seed, rc_matrix q) { \
-        return guarded(ctx, [&] { c_sample_range_by_rank<R>(ctx, COp<R>::of(view_of<R>(a)), k, p, view_of<R>(omega), seed, view_of<R>(q)); });   \
-    }                                                                                                                                     \
-    rc_status rc_sample_range_power_iteration_##SUF(rc_context *ctx, rc_matrix a, int64_t k, int64_t p, int64_t it, rc_matrix omega, uint64_t seed, rc_matrix q) { \
-        return guarded(ctx, [&] { c_sample_range_power<R>(ctx, COp<R>::of(view_of<R>(a)), k, p, it, view_of<R>(omega), seed, view_of<R>(q)); });   \
-    }                                                                                                                                     \
-    rc_status rc_sample_range_adaptive_##SUF(rc_context *ctx, rc_matrix a, double rel_tol, int64_t s, rc_matrix omegas, uint64_t seed, rc_matrix q_cap, \
-                                             int64_t *rank, int64_t *hist_rank, double *hist_res, int64_t hist_cap, int64_t *hist_len) {  \
-        return guarded(ctx, [&] {                                                                                                         \
-            c_sample_range_adaptive<R>(ctx, COp<R>::of(view_of<R>(a)), rel_tol, s, view_of<R>(omegas), seed, view_of<R>(q_cap), rank, hist_rank, hist_res, hist_cap, hist_len); \
-        });                                                                                                                               \
-    }                                                                                                                                     \
-    /* the range finders and compute_from_range_estimate over the host's operator callbacks (rc_operator) */                              \
-    rc_status rc_sample_range_by_rank_op_##SUF(rc_context *ctx, const rc_operator *op, int64_t k, int64_t p, rc_matrix omega, uint64_t seed, rc_matrix q) { \
-        return guarded(ctx, [&] { c_sample_range_by_rank<R>(ctx, COp<R>::of(op), k, p, view_of<R>(omega), seed, view_of<R>(q)); });       \
-    }                                                                                                                                     \
-    rc_status rc_sample_range_power_iteration_op_##SUF(rc_context *ctx, const rc_operator *op, int64_t k, int64_t p, int64_t it, rc_matrix omega, uint64_t seed, rc_matrix q) { \
-        return guarded(ctx, [&] { c_sample_range_power<R>(ctx, COp<R>::of(op), k, p, it, view_of<R>(omega), seed, view_of<R>(q)); });     \
-    }                                                                                                                                     \
-    rc_status rc_sample_range_adaptive_op_##SUF(rc_context *ctx, const rc_operator *op, double rel_tol, int64_t s, rc_matrix omegas, uint64_t seed, rc_matrix q_cap, \
-                                                int64_t *rank, int64_t *hist_rank, double *hist_res, int64_t hist_cap, int64_t *hist_len) { \
-        return guarded(ctx, [&] {                                                                                                         \
-            c_sample_range_adaptive<R>(ctx, COp<R>::of(op), rel_tol, s, view_of<R>(omegas), seed, view_of<R>(q_cap), rank, hist_rank, hist_res, hist_cap, hist_len); \
-        });                                                                                                                               \
-    }                                                                                                                                     \
-    rc_status rc_qr_from_range_estimate_op_##SUF(rc_context *ctx, rc_matrix range, const rc_operator *op, rc_matrix q, rc_matrix r, int64_t *ind) { \
-        return guarded(ctx, [&] {                                                                                                         \
-            const COp<R> A = COp<R>::of(op);                                                                                              \
-            CV<R> Rg = view_of<R>(range), Q = view_of<R>(q), Rr = view_of<R>(r);                                                          \
-            const int64_t rr = Rg.cols, n = A.cols, k = std::min(rr, n);                                                                  \
-            RC_REQUIRE(Rg.rows == A.rows && Q.rows == A.rows && Q.cols == k && Rr.rows == k && Rr.cols == n, RC_INVALID_ARGUMENT, "qr_from_range_estimate: shape mismatch"); \
-            CV<R> b = tmp_cm<R>(ctx, rr, n), qb = tmp_cm<R>(ctx, rr, k);                                                                  \
-            A.project(ctx, Rg, b);                                                                                                        \
-            c_pivoted_qr<R>(ctx, b, qb, Rr, ind, k);                                                                                      \
-            c_gemm<R>(ctx, 0, 0, one<R>(), Rg, qb, zero<R>(), Q);                                                                         \
-        });                                                                                                                               \
-    }                                                                                                                                     \
-    rc_status rc_svd_from_range_estimate_op_##SUF(rc_context *ctx, rc_matrix range, const rc_operator *op, rc_matrix u, R *s, rc_matrix vt) { \
-        return guarded(ctx, [&] {                                                                                                         \
-            const COp<R> A = COp<R>::of(op);                                                                                              \
-            CV<R> Rg = view_of<R>(range), U = view_of<R>(u), VT = view_of<R>(vt);                                                         \
-            const int64_t rr = Rg.cols, n = A.cols, r = std::min(rr, n);                                                                  \
-            RC_REQUIRE(Rg.rows == A.rows && U.rows == A.rows && U.cols == r && VT.rows == r && VT.cols == n, RC_INVALID_ARGUMENT, "svd_from_range_estimate: shape mismatch"); \
-            CV<R> b = tmp_cm<R>(ctx, rr, n), ub = tmp_cm<R>(ctx, rr, r);                                                                  \
-            A.project(ctx, Rg, b);                                                                                                        \
-            c_compute_svd<R>(ctx, b, ub, s, VT);                                                                                          \
-            c_gemm<R>(ctx, 0, 0, one<R>(), Rg, ub, zero<R>(), U);                                                                         \
         });                                                                                                                               \
     }                                                                                                                                     \
     rc_status rc_column_id_rank_##SUF(rc_context *ctx, rc_matrix a, int64_t k, rc_matrix c, rc_matrix z, int64_t *col_ind) {              \
         return guarded(ctx, [&] {                                                                                                         \
             CV<R> A = view_of<R>(a);                                                                                                      \
             const int64_t kk = std::min(k, std::min(A.rows, A.cols));                                                                     \
-            CV<R> q = tmp_cm<R>(ctx, A.rows, kk), r = tmp_cm<R>(ctx, kk, A.cols);                                                         \
+            CV<R> q = tmp_colmajor<cplx<R>>(ctx, A.rows, kk), r = tmp_colmajor<cplx<R>>(ctx, kk, A.cols);                                 \
             c_pivoted_qr<R>(ctx, A, q, r, col_ind, kk);                                                                                   \
             c_qr_column_id<R>(ctx, q, r, col_ind, view_of<R>(c), view_of<R>(z));                                                          \
         });                                                                                                                               \
@@ -1284,5 +1009,7 @@ extern "C" {
 
 RC_DEFINE_COMPLEX(c64, double, rc_complex64)
 RC_DEFINE_COMPLEX(c32, float, rc_complex32)
+RC_DEFINE_DENSE_SHARED(c64, cplx<double>, double)
+RC_DEFINE_DENSE_SHARED(c32, cplx<float>, float)
 
 }  // extern "C"

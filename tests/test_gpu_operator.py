@@ -197,6 +197,53 @@ def test_operator_with_matmat_only_and_error_propagation():
     assert rel(npy(rc.sample_range_by_rank(a, 15, 5, omega)), npy(q)) <= 1e-12
 
 
+@pytest.mark.parametrize("dtype", [np.float64, np.float32, np.complex128, np.complex64])
+def test_failing_library_call_inside_a_callback_reaches_the_caller(dtype):
+    """The status path of the rc_*_op_* entry points (OpView::call, csrc/rc_dense_shared.hpp) is one text for f64, f32, c64 and c32:
+    when a callback's own library call fails on the context it was handed, the entry point returns that call's status and its
+    message names the product AND carries the text the inner call left -- compared with the text the same call leaves when made
+    directly, not with a literal.  The context stays usable: the dense range finder returns the bits it returned before."""
+    m, n, k, p = 48, 32, 6, 2
+    rng = np.random.default_rng(4)
+    is_complex = np.issubdtype(dtype, np.complexfloating)
+
+    def draw(*shape):
+        return (rng.standard_normal(shape) + (1j * rng.standard_normal(shape) if is_complex else 0)).astype(dtype)
+
+    a, omega = torch.from_numpy(draw(m, n)).cuda(), torch.from_numpy(draw(n, k + p)).cuda()
+    lib, ctx, suf = _lib.lib(), _lib.default_context(), _lib.suffix(a.dtype)
+    matmat = getattr(lib, f"rc_matmat_{suf}")
+    q_before = rc.sample_range_by_rank(a, k, p, omega)
+
+    tab = OperatorTable(DenseOperator(a))
+    seen = []
+
+    def failing_matmat(_user, ctx_h, x, y):   # y = A x with x and y swapped: A (m x n) times an m x (k + p) matrix
+        seen.append(matmat(ctypes.c_void_p(ctx_h), _lib.mat(a), y, x))
+        return seen[-1]
+
+    status_fn = type(tab.table.matmat)(failing_matmat)
+    tab.table.matmat = status_fn
+
+    # the same failing call made directly, on a context of its own: OpView::call takes the inner text from a CHANGE of the handed
+    # context's last error, and the message is the same on any context
+    other = _lib.Context()
+    y = torch.empty((m, k + p), dtype=a.dtype, device="cuda")
+    st_direct = matmat(other._h, _lib.mat(a), _lib.mat(y), _lib.mat(omega))
+    inner = lib.rc_last_error_message(other._h)
+    other.close()
+    assert st_direct != _lib.RC_OK and inner
+
+    qbuf = torch.empty((m, k), dtype=a.dtype, device="cuda")
+    st = getattr(lib, f"rc_sample_range_by_rank_op_{suf}")(ctx._h, tab.byref(), ctypes.c_int64(k), ctypes.c_int64(p), _lib.mat(omega), ctypes.c_uint64(0),
+                                                          _lib.mat(qbuf))
+    msg = lib.rc_last_error_message(ctx._h)
+    assert seen == [st_direct] and st == st_direct
+    assert b"matmat" in msg
+    assert inner in msg, (msg, inner)
+    assert torch.equal(rc.sample_range_by_rank(a, k, p, omega), q_before)
+
+
 def test_operator_callbacks_are_rejected_inside_a_graph_capture():
     a = torch.from_numpy(_recipe(256, 192, np.float64)).cuda()
     st_ = torch.cuda.Stream()
