@@ -466,7 +466,14 @@ rc_status rc_batch_shard_range(int64_t n_items, int32_t world, int32_t rank, int
 /* Rank-k column ID of `count` same-shaped device matrices into the packed device buffer `packed`
  * (count * rc_batch_packed_bytes).  The matrices are spread over the nctx contexts (one HIP stream each, same device) and
  * pipelined (each lane is waited for on its own event, first in, first out; idle lanes take the next matrix); results are identical to count calls of
- * rc_column_id_rank_*.  Blocking: returns when every factor is in `packed`.  Errors are reported on ctxs[0]. */
+ * rc_column_id_rank_* on a context with the options of ctxs[0]: shapes the lone call takes off the truncated blocked factorization
+ * (tall-skinny, short-wide, k == n, shapes too small for the panels) run the lone call's own routine on their lane.  Which lane a matrix
+ * runs on depends on the timing, so the contexts must agree: a context on another device than ctxs[0], or one whose RC_OPT_BLOCKED_QRCP,
+ * RC_OPT_COOP_PANEL, RC_OPT_TALL_SKINNY_FAST_PATH, RC_OPT_WIDE_COOP_QRCP or RC_OPT_WIDE_LAZY_QRCP differs from ctxs[0]'s, or whose
+ * min(RC_OPT_CONCURRENCY_HINT, RC_OPT_KERNEL_SLOTS) does (it sizes the launches: bits are promised per value), is rejected with
+ * RC_INVALID_ARGUMENT (the message names the lane) before anything is launched; the complex twins (rc_batch_column_id_c64 / _c32), whose
+ * factorization no option selects, reject a context on another device the same way.  Blocking: returns when every factor is in `packed`.
+ * Errors are reported on ctxs[0]; when the call returns an error the contents of every packed slot are undefined. */
 rc_status rc_batch_column_id_f64(rc_context *const *ctxs, int32_t nctx, const rc_matrix *mats, int32_t count, int64_t k, void *packed);
 rc_status rc_batch_column_id_f32(rc_context *const *ctxs, int32_t nctx, const rc_matrix *mats, int32_t count, int64_t k, void *packed);
 /* Many SMALL same-shaped matrices (blocks of a hierarchical matrix / FMM operator) in one stream-ordered call: no host

@@ -1446,7 +1446,7 @@ struct BlockedQrcpJob {
     // cooperative panels (k_qrb_coop)
     QrbCoopArgs<T> coop;
     bool coop_ready = false, coop_issued = false;
-    bool keep_t = true;  // the panels' T factors are kept for qrb_form_q (false: the caller needs no Q -- column_id_from_qrcp)
+    bool keep_t = false;  // geqp3_blocked with a q_out: the panels' T factors are kept for qrb_form_q (the job's other users form no Q)
     int coop_fallbacks = 0;
     int64_t cw_issued = 0;
     unsigned grid_a = 0, grid_c = 0;
@@ -1789,8 +1789,6 @@ void qrb_form_q(BlockedQrcpJob<T> *J, Mat<T> q) {
 
 template <typename T>
 void qrb_end(BlockedQrcpJob<T> *J) { delete J; }
-template <typename T>
-void qrb_keep_t(BlockedQrcpJob<T> *J, bool keep) { J->keep_t = keep; }
 
 // w: m x n column-major working matrix (overwritten with the ?geqp3 output format: R on and above the
 // diagonal in position order, reflectors below, columns never moved); jpvt: n; tau: kmax
@@ -1832,7 +1830,6 @@ extern "C" void rc_debug_qrc_timing(unsigned long long *out) { (void)hipMemcpyFr
     template bool qrb_finish<T>(BlockedQrcpJob<T> *);                                            \
     template void qrb_form_q<T>(BlockedQrcpJob<T> *, Mat<T>);                                    \
     template void qrb_end<T>(BlockedQrcpJob<T> *);                                               \
-    template void qrb_keep_t<T>(BlockedQrcpJob<T> *, bool);                                      \
     template bool qrb_optimistic_possible<T>(BlockedQrcpJob<T> *);                               \
     template bool qrb_issue_all_optimistic<T>(BlockedQrcpJob<T> *);                              \
     template bool qrb_verify_optimistic<T>(BlockedQrcpJob<T> *);                                 \

@@ -278,8 +278,9 @@ __device__ inline T fast_sqrt_pos(T x) { return x > (T)0 ? x * fast_rsqrt(x) : (
 
 // One Householder step of k_qrcp_small applied to the trailing columns (one LPP-lane group per column, NEJ rows per lane
 // from row j on) + the ?laqp2 norm down-date.  safe != 0: a read past the end of a column stays inside the LDS image (it
-// lands in the next column or in the norm / tau / permutation arrays behind the matrix), so the loads carry no bounds:
-// the reflector entries there are zero, the products are exact zeros and the sums are the same bits as with bounds.
+// lands in the pad row, in the next column or in the norm / tau / permutation arrays behind the matrix, all of which the kernel
+// has written: finite values), so the loads carry no bounds: the reflector entries there are zero, the products are exact zeros
+// and the sums are the same bits as with bounds.
 template <typename T, int NEJ, int LPP>
 __device__ __forceinline__ void qrcp_small_apply(T *A, int ld, int n, int j, int grp, int ll, int ngrp, const int *jp, T *vn1, T *vn2, T tj, int pivot, bool safe) {
     const T *vcol = A + jp[j] * ld;
@@ -453,6 +454,10 @@ __global__ __launch_bounds__(NTHR) void k_qrcp_small(Mat<T> rin, int kmax, int p
         int i = e % n, cc = e / n;
         A[cc * ld + i] = rin.at(i, cc);
     }
+    // the pad row of an even n (ld = n + 1) is read by the unbounded loads of qrcp_small_apply too: whatever the last kernel on this CU
+    // left there -- a NaN or an infinity among it -- times the reflector's zero is a NaN, and the column never becomes a pivot
+    if (ld > n)
+        for (int cc = tid; cc < n; cc += NTHR) A[cc * ld + n] = (T)0;
     __syncthreads();
     for (int p = grp; p < n; p += NGRP) {
         T acc = 0;

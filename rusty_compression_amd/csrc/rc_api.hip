@@ -810,31 +810,6 @@ void rsvd_id_row_sharded(rc_comm *comm, rc_context *c, Mat<T> a, int64_t k, int6
     rsvd_id_consumers(c, range, b, o);
 }
 
-// cfg5 unit: rank-k column ID of a dense matrix through the truncated factorization
-template <typename T>
-void column_id_rank(rc_context *c, Mat<T> a, int64_t k, Mat<T> cm, Mat<T> z, int64_t *col_ind) {
-    const int64_t m = a.rows, n = a.cols;
-    k = std::min(k, std::min(m, n));
-    ArenaMark mark(c);
-    Mat<T> w = tmp_colmajor<T>(c, m, n);
-    copy_mat(c, a, w);
-    static const bool long_way = [] { const char *e = getenv("RC_COLUMN_ID_FORM_Q"); return e && atoi(e) != 0; }();
-    // Fast path: the truncated blocked factorization leaves w in the ?geqp3 format; Z and C come straight from it (column_id_from_qrcp,
-    // kernels_qr.hip: C = Q R11 is the selected columns of A themselves -- no Q is formed).  The other factorization paths
-    // (tall-skinny, short-wide, under capture) return Q and R and go through qr_column_id.
-    if (!long_way && k < n && c->opt_blocked && !c->capturing && geqp3_blocked_supported<T>(m, n, k) &&
-        !(c->opt_tsqr && tsqr_supported<T>(m, n)) && !(c->opt_wide_coop && wide_coop_supported<T>(m, n, c->device)) && !(c->opt_wide_lazy && wide_lazy_supported<T>(m, n))) {
-        T *tau = c->alloc<T>((size_t)std::max<int64_t>(k, 1));
-        geqp3_blocked<T>(c, w, k, col_ind, tau, Mat<T>(), /*restore_from=*/a);
-        column_id_from_qrcp(c, a, w, k, col_ind, cm, z);
-        return;
-    }
-    Mat<T> q = tmp_colmajor<T>(c, m, k);
-    Mat<T> r = tmp_rowmajor<T>(c, k, n);
-    qrcp_core(c, w, k, true, q, r, col_ind);
-    qr_column_id(c, q, r, col_ind, cm, z, /*own_ind=*/true);
-}
-
 template <typename T>
 void svd_rank_by_tolerance(rc_context *c, const T *s, int64_t len, double tol, int64_t *rank) {
     RC_REQUIRE(tol < 1.0 && 0.0 <= tol, RC_INVALID_ARGUMENT, "Require 0 <= tol < 1.0");
@@ -848,6 +823,49 @@ void svd_rank_by_tolerance(rc_context *c, const T *s, int64_t len, double tol, i
 }
 
 }  // namespace
+
+namespace rc {
+
+// Whether the rank-k column ID of an m x n matrix on this context takes the truncated blocked factorization, whose output the ID is
+// read from directly (column_id_from_qrcp).  One predicate for the lone call below and for rc_batch_column_id_* (rc_batch.hip), which
+// promises the lone call's bits: every other shape -- tall-skinny, short-wide, k == n, too small for the panels -- goes through
+// qrcp_core and qr_column_id in both.
+template <typename T>
+bool column_id_blocked_route(rc_context *c, int64_t m, int64_t n, int64_t k) {
+    static const bool long_way = [] { const char *e = getenv("RC_COLUMN_ID_FORM_Q"); return e && atoi(e) != 0; }();
+    return !long_way && k < n && c->opt_blocked && !c->capturing && geqp3_blocked_supported<T>(m, n, k) &&
+           !(c->opt_tsqr && tsqr_supported<T>(m, n)) && !(c->opt_wide_coop && wide_coop_supported<T>(m, n, c->device)) && !(c->opt_wide_lazy && wide_lazy_supported<T>(m, n));
+}
+
+// cfg5 unit: rank-k column ID of a dense matrix through the truncated factorization
+template <typename T>
+void column_id_rank(rc_context *c, Mat<T> a, int64_t k, Mat<T> cm, Mat<T> z, int64_t *col_ind) {
+    const int64_t m = a.rows, n = a.cols;
+    k = std::min(k, std::min(m, n));
+    ArenaMark mark(c);
+    Mat<T> w = tmp_colmajor<T>(c, m, n);
+    copy_mat(c, a, w);
+    // Fast path: the truncated blocked factorization leaves w in the ?geqp3 format; Z and C come straight from it (column_id_from_qrcp,
+    // kernels_qr.hip: C = Q R11 is the selected columns of A themselves -- no Q is formed).  The other factorization paths
+    // (tall-skinny, short-wide, under capture) return Q and R and go through qr_column_id.
+    if (column_id_blocked_route<T>(c, m, n, k)) {
+        T *tau = c->alloc<T>((size_t)std::max<int64_t>(k, 1));
+        geqp3_blocked<T>(c, w, k, col_ind, tau, Mat<T>(), /*restore_from=*/a);
+        column_id_from_qrcp(c, a, w, k, col_ind, cm, z);
+        return;
+    }
+    Mat<T> q = tmp_colmajor<T>(c, m, k);
+    Mat<T> r = tmp_rowmajor<T>(c, k, n);
+    qrcp_core(c, w, k, true, q, r, col_ind);
+    qr_column_id(c, q, r, col_ind, cm, z, /*own_ind=*/true);
+}
+
+template bool column_id_blocked_route<double>(rc_context *, int64_t, int64_t, int64_t);
+template bool column_id_blocked_route<float>(rc_context *, int64_t, int64_t, int64_t);
+template void column_id_rank<double>(rc_context *, Mat<double>, int64_t, Mat<double>, Mat<double>, int64_t *);
+template void column_id_rank<float>(rc_context *, Mat<float>, int64_t, Mat<float>, Mat<float>, int64_t *);
+
+}  // namespace rc
 
 // ===========================================================================
 // extern "C"

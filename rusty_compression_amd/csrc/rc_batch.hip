@@ -49,34 +49,6 @@ Mat<T> tmp_cm(rc_context *c, int64_t rows, int64_t cols) {
     return colmajor(c->alloc<T>((size_t)ld * std::max<int64_t>(cols, 1)), rows, cols, ld);
 }
 
-// column ID from the factorization in the ?geqp3 output format (same steps as column_id_rank in rc_api.hip)
-template <typename T>
-void finish_column_id(rc_context *c, Mat<T> a, Mat<T> w, int64_t k, const T *tau, int64_t *ind, Mat<T> cm, Mat<T> z, BlockedQrcpJob<T> *job) {
-    const int64_t m = w.rows, n = w.cols;
-    // RC_COLUMN_ID_FORM_Q=1: C as the product Q R11 with Q formed from the reflectors (the round-2 path, kept for comparison)
-    static const bool long_way = [] { const char *e = getenv("RC_COLUMN_ID_FORM_Q"); return e && atoi(e) != 0; }();
-    if (!long_way && k < n) { column_id_from_qrcp(c, a, w, k, ind, cm, z); return; }
-    Mat<T> r = rowmajor(c->alloc<T>((size_t)k * even_ld(n)), k, n, even_ld(n));
-    extract_r(c, w, ind, r);
-    Mat<T> q = tmp_cm<T>(c, m, k);
-    if (job) qrb_form_q(job, q);
-    else form_q(c, w, ind, tau, k, q);
-    // QRTraits::column_id (src/qr.rs:270-309): Z = [I | R11^-1 R12] P^T, C = Q R11
-    int64_t *inv = c->alloc<int64_t>((size_t)n);
-    invert_perm(c, ind, n, inv);
-    Mat<T> zt = rowmajor(c->alloc<T>((size_t)k * even_ld(n)), k, n, even_ld(n));
-    if (k == n) {
-        gemm<T>(c, 1, q, r, 0, cm);
-        fill_identity(c, zt);
-    } else {
-        fill_identity(c, zt.sub(0, k, 0, k));
-        copy_mat(c, r.sub(0, k, k, n - k), zt.sub(0, k, k, n - k));
-        trsm_upper(c, r.sub(0, k, 0, k), zt.sub(0, k, k, n - k));
-        gemm<T>(c, 1, q, r.sub(0, k, 0, k), 0, cm);
-    }
-    gather_cols(c, zt, inv, z);
-}
-
 template <typename T>
 void batch_column_id(rc_context *const *ctxs, int nctx, const rc_matrix *mats, int count, int64_t k, void *packed) {
     RC_REQUIRE(nctx >= 1 && count >= 0 && k >= 1, RC_INVALID_ARGUMENT, "batch_column_id: need >= 1 context, k >= 1");
@@ -87,6 +59,21 @@ void batch_column_id(rc_context *const *ctxs, int nctx, const rc_matrix *mats, i
         RC_REQUIRE(mats[i].rows == m && mats[i].cols == n && mats[i].data, RC_INVALID_ARGUMENT, "batch_column_id: all matrices must have the shape of the first");
     RC_REQUIRE(k <= std::min(m, n), RC_INVALID_ARGUMENT, "batch_column_id: rank %lld exceeds min(m, n)", (long long)k);
     for (int l = 0; l < nctx; ++l) RC_REQUIRE(ctxs[l] && !ctxs[l]->capturing, RC_INVALID_ARGUMENT, "batch_column_id: bad context");
+    // which lane a matrix runs on depends on the timing: the lanes must all choose the factorization ctxs[0] chooses, on its device
+    for (int l = 1; l < nctx; ++l) {
+        const rc_context *a = ctxs[0], *b = ctxs[l];
+        RC_REQUIRE(b->device == a->device, RC_INVALID_ARGUMENT, "batch_column_id: context %d is on device %d, context 0 on device %d", l, b->device, a->device);
+        RC_REQUIRE(!b->opt_blocked == !a->opt_blocked && !b->opt_coop_panel == !a->opt_coop_panel && !b->opt_tsqr == !a->opt_tsqr &&
+                       !b->opt_wide_coop == !a->opt_wide_coop && !b->opt_wide_lazy == !a->opt_wide_lazy,
+                   RC_INVALID_ARGUMENT, "batch_column_id: context %d differs from context 0 in an option that selects the factorization (RC_OPT_BLOCKED_QRCP, "
+                   "RC_OPT_COOP_PANEL, RC_OPT_TALL_SKINNY_FAST_PATH, RC_OPT_WIDE_COOP_QRCP, RC_OPT_WIDE_LAZY_QRCP)", l);
+        // (what the launches are sized for: the K splits of the products and the launches of the small pivoted QR follow it, and bits with them)
+        RC_REQUIRE(b->lanes_in_flight() == a->lanes_in_flight(), RC_INVALID_ARGUMENT,
+                   "batch_column_id: context %d sizes its launches for %d compressions in flight, context 0 for %d (min(RC_OPT_CONCURRENCY_HINT, RC_OPT_KERNEL_SLOTS))", l,
+                   b->lanes_in_flight(), a->lanes_in_flight());
+    }
+    // the lone call's route (rc_api.hip): the truncated blocked factorization, pipelined below, or the lone call's own routine on the lane
+    const bool blocked = column_id_blocked_route<T>(ctxs[0], m, n, k);
     const size_t per = rc_batch_packed_bytes(m, n, k, (int32_t)sizeof(T));
     struct Lane {
         rc_context *c = nullptr;
@@ -110,36 +97,38 @@ void batch_column_id(rc_context *const *ctxs, int nctx, const rc_matrix *mats, i
         }
     } cleanup{lanes, ctxs, nctx};
     auto slot = [&](int idx) { return static_cast<char *>(packed) + (size_t)idx * per; };
+    // C, Z and ind of a finished blocked factorization into the matrix's slot: read from the factored working copy, no Q (the lone call's tail)
     auto post = [&](Lane &ln) {
         char *base = slot(ln.idx);
         Mat<T> cm = rowmajor(reinterpret_cast<T *>(base), m, k, k);
         Mat<T> z = rowmajor(reinterpret_cast<T *>(base) + (size_t)m * k, k, n, n);
-        finish_column_id<T>(ln.c, from_c<T>(mats[ln.idx]), ln.w, k, ln.tau, ln.ind, cm, z, ln.job);
+        column_id_from_qrcp(ln.c, from_c<T>(mats[ln.idx]), ln.w, k, ln.ind, cm, z);
         RC_HIP(hipMemcpyAsync(base + align8(((size_t)m * k + (size_t)k * n) * sizeof(T)), ln.ind, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToDevice, ln.c->stream));
     };
-    // set-up of the next matrix on a lane: working copy, then either the first panel of the blocked factorization (true: the
-    // lane has a panel in flight) or, for small shapes, the whole per-step chain (false: nothing to wait for)
+    // set-up of the next matrix on a lane.  Blocked route: working copy and the job of the blocked factorization (true: the caller
+    // issues its first panel and the lane has something to wait for).  Every other route (tall-skinny, short-wide, k == n, shapes the
+    // panels do not take): the lone call's own routine, whole, on the lane's stream into the slot (false: nothing to wait for)
     auto start = [&](Lane &ln, int idx) -> bool {
         ln.idx = idx;
         DeviceGuardB dg(ln.c->device);
         ln.c->reset_arena();
-        ln.w = tmp_cm<T>(ln.c, m, n);
-        ln.tau = ln.c->template alloc<T>((size_t)k);
         // (the permutation is built in a lane-owned buffer; it is copied into the packed slot at the end)
         ln.ind = ln.c->template alloc<int64_t>((size_t)n);
-        copy_mat(ln.c, from_c<T>(mats[ln.idx]), ln.w);  // the reference's F-order working copy (pivoted_qr.rs:28-29)
-        if (ln.c->opt_blocked && geqp3_blocked_supported<T>(m, n, k)) {
-            ln.job = qrb_begin<T>(ln.c, ln.w, k, ln.ind, ln.tau);
-            static const bool long_way = [] { const char *e = getenv("RC_COLUMN_ID_FORM_Q"); return e && atoi(e) != 0; }();
-            qrb_keep_t(ln.job, long_way || k >= n);  // (the ID comes straight from the factored matrix: no Q, no T factors to keep)
-            ln.active = true;
-            return true;
+        if (!blocked) {
+            char *base = slot(idx);
+            Mat<T> cm = rowmajor(reinterpret_cast<T *>(base), m, k, k);
+            Mat<T> z = rowmajor(reinterpret_cast<T *>(base) + (size_t)m * k, k, n, n);
+            column_id_rank<T>(ln.c, from_c<T>(mats[idx]), k, cm, z, ln.ind);
+            RC_HIP(hipMemcpyAsync(base + align8(((size_t)m * k + (size_t)k * n) * sizeof(T)), ln.ind, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToDevice, ln.c->stream));
+            ln.active = false;
+            return false;
         }
-        T *vn = ln.c->template alloc<T>((size_t)(2 * n));
-        geqp3_inplace(ln.c, ln.w, k, true, ln.ind, ln.tau, vn);
-        post(ln);
-        ln.active = false;
-        return false;
+        ln.w = tmp_cm<T>(ln.c, m, n);
+        ln.tau = ln.c->template alloc<T>((size_t)k);
+        copy_mat(ln.c, from_c<T>(mats[ln.idx]), ln.w);  // the reference's F-order working copy (pivoted_qr.rs:28-29)
+        ln.job = qrb_begin<T>(ln.c, ln.w, k, ln.ind, ln.tau);
+        ln.active = true;
+        return true;
     };
     for (int l = 0; l < nctx; ++l) lanes[(size_t)l].c = ctxs[l];
     // Optimistic schedule (default where it applies: blocked factorization on cooperative panels, no Q wanted): EVERY matrix is
@@ -152,9 +141,8 @@ void batch_column_id(rc_context *const *ctxs, int nctx, const rc_matrix *mats, i
     std::vector<int> redo;
     bool optimistic_done = false;
     {
-        static const bool long_way = [] { const char *e = getenv("RC_COLUMN_ID_FORM_Q"); return e && atoi(e) != 0; }();
         static const bool opt_on = [] { const char *e = getenv("RC_BATCH_OPTIMISTIC"); return !(e && atoi(e) == 0); }();
-        if (opt_on && !long_way && k < n && count > 0 && lanes[0].c->opt_blocked && geqp3_blocked_supported<T>(m, n, k)) {
+        if (opt_on && blocked) {
             struct Pending { int idx; const QrbState *log; std::vector<int> nbp; bool broken; };
             std::vector<Pending> pending;
             auto flush = [&] {
@@ -167,6 +155,7 @@ void batch_column_id(rc_context *const *ctxs, int nctx, const rc_matrix *mats, i
                 for (auto &ln : lanes) ln.c->pinned_cursor = 0;
             };
             bool possible = true;
+            int flushes = 0;  // waits in the middle of the pass: a lane ran out of pinned state slots
             static const bool dbg = [] { const char *e = getenv("RC_BATCH_DEBUG"); return e && atoi(e) != 0; }();
             const auto t_begin = std::chrono::steady_clock::now();
             for (auto &ln : lanes) ln.c->pinned_cursor = 0;
@@ -180,12 +169,12 @@ void batch_column_id(rc_context *const *ctxs, int nctx, const rc_matrix *mats, i
                 ln.ind = ln.c->template alloc<int64_t>((size_t)n);
                 copy_mat(ln.c, from_c<T>(mats[idx]), ln.w);
                 ln.job = qrb_begin<T>(ln.c, ln.w, k, ln.ind, ln.tau);
-                qrb_keep_t(ln.job, false);
                 if (!qrb_optimistic_possible(ln.job)) {
                     possible = false;
                 } else {
                     if (!qrb_issue_all_optimistic(ln.job)) {  // no pinned slots left on this lane: wait, check, go on
                         flush();
+                        ++flushes;
                         RC_REQUIRE(qrb_issue_all_optimistic(ln.job), RC_RUNTIME_ERROR, "batch_column_id: no pinned state slots");
                     }
                     Pending pd;
@@ -207,8 +196,11 @@ void batch_column_id(rc_context *const *ctxs, int nctx, const rc_matrix *mats, i
             if (possible) flush();
             if (dbg) {
                 const auto t_end = std::chrono::steady_clock::now();
-                fprintf(stderr, "rc_batch optimistic: %d matrices issued in %.3f ms, waited %.3f ms, %zu to redo\n", count,
-                        std::chrono::duration<double, std::milli>(t_issued - t_begin).count(), std::chrono::duration<double, std::milli>(t_end - t_issued).count(), redo.size());
+                std::string which;  // the matrices to redo, by index
+                for (int i2 : redo) which += " " + std::to_string(i2);
+                fprintf(stderr, "rc_batch optimistic: %d matrices issued in %.3f ms, waited %.3f ms, %zu to redo, %d flushes, redo:%s\n", count,
+                        std::chrono::duration<double, std::milli>(t_issued - t_begin).count(), std::chrono::duration<double, std::milli>(t_end - t_issued).count(), redo.size(), flushes,
+                        which.c_str());
             }
             optimistic_done = true;
         }

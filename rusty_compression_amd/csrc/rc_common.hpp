@@ -302,7 +302,6 @@ template <typename T> struct BlockedQrcpJob;
 template <typename T> BlockedQrcpJob<T> *qrb_begin(rc_context *c, Mat<T> w, int64_t kmax, int64_t *jpvt, T *tau);
 template <typename T> void qrb_issue(BlockedQrcpJob<T> *job);
 template <typename T> bool qrb_finish(BlockedQrcpJob<T> *job);
-template <typename T> void qrb_form_q(BlockedQrcpJob<T> *job, Mat<T> q);  // after completion
 template <typename T> void qrb_end(BlockedQrcpJob<T> *job);
 struct QrbState;
 template <typename T> bool qrb_optimistic_possible(BlockedQrcpJob<T> *job);
@@ -310,7 +309,10 @@ template <typename T> bool qrb_issue_all_optimistic(BlockedQrcpJob<T> *job);   /
 template <typename T> bool qrb_verify_optimistic(BlockedQrcpJob<T> *job);
 template <typename T> bool qrb_verify_optimistic(const QrbState *host_log, const std::vector<int> &nbp_log, bool broken);
 template <typename T> void qrb_optimistic_log(BlockedQrcpJob<T> *job, const QrbState **log, std::vector<int> *nbp_log, bool *broken);
-template <typename T> void qrb_keep_t(BlockedQrcpJob<T> *job, bool keep);  // false: no Q will be formed, the panels' T factors need not be kept
+// the lone rank-k column ID (rc_column_id_rank_*, rc_api.hip) and whether it reads the ID from the truncated blocked factorization
+// (true) or goes through qrcp_core and qr_column_id; rc_batch_column_id_* runs the same routes
+template <typename T> bool column_id_blocked_route(rc_context *c, int64_t m, int64_t n, int64_t k);
+template <typename T> void column_id_rank(rc_context *c, Mat<T> a, int64_t k, Mat<T> cm, Mat<T> z, int64_t *col_ind);
 // short-wide matrices (m <= 256 << n): read-only "lazy" pivoted QR with the explicit m x m factor
 template <typename T> bool wide_lazy_supported(int64_t m, int64_t n);
 template <typename T> void geqp3_wide_lazy(rc_context *c, Mat<T> b, int64_t kmax, int64_t *jpvt, Mat<T> q, Mat<T> r);

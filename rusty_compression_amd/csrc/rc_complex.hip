@@ -841,10 +841,16 @@ void c_batch_column_id(rc_context *const *ctxs, int nctx, const rc_matrix *mats,
     const int64_t m = mats[0].rows, n = mats[0].cols;
     RC_REQUIRE(k <= std::min(m, n), RC_INVALID_ARGUMENT, "batch_column_id: rank exceeds min(m, n)");
     const size_t per = rc_batch_packed_bytes(m, n, k, (int32_t)sizeof(cplx<R>));
-    for (int i = 0; i < count; ++i) {
+    // everything is checked before the first launch (no option selects between complex factorizations: the device is all the lanes must share)
+    for (int i = 0; i < count; ++i)
         RC_REQUIRE(mats[i].rows == m && mats[i].cols == n && mats[i].data, RC_INVALID_ARGUMENT, "batch_column_id: all matrices must have the shape of the first");
+    for (int l = 0; l < nctx; ++l) {
+        RC_REQUIRE(ctxs[l] != nullptr, RC_INVALID_ARGUMENT, "batch_column_id: bad context");
+        RC_REQUIRE(ctxs[l]->device == ctxs[0]->device, RC_INVALID_ARGUMENT, "batch_column_id: context %d is on device %d, context 0 on device %d", l, ctxs[l]->device,
+                   ctxs[0]->device);
+    }
+    for (int i = 0; i < count; ++i) {
         rc_context *c = ctxs[i % nctx];
-        RC_REQUIRE(c != nullptr, RC_INVALID_ARGUMENT, "batch_column_id: bad context");
         char *base = static_cast<char *>(packed) + (size_t)i * per;
         cplx<R> *cz = reinterpret_cast<cplx<R> *>(base);
         int64_t *ind = reinterpret_cast<int64_t *>(base + per - (size_t)n * sizeof(int64_t));
