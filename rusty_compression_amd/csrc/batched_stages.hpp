@@ -460,7 +460,7 @@ __device__ __forceinline__ bool bsv_jacobi(E *G, int ldg, E *J, int ldj, int N, 
     const int ll = tid & 15, grp = tid >> 4;
     constexpr int NGRP = BID_THREADS / 16;
     const int N2 = (N + 1) & ~1, npairs = N2 / 2;
-    const R tol = sqrt((R)N) * JEps<R>::eps(), tol2 = tol * tol;
+    const R tol = sqrt((R)N) * num<R>::eps(), tol2 = tol * tol;
     for (int sweep = 0; sweep < kMaxSweeps; ++sweep) {
         if (tid == 0) *flag = 0;
         __syncthreads();

@@ -236,7 +236,7 @@ __device__ inline void jacobi_lds_body(const JacobiLdsArgs<T> &ja, bool consumer
         if (tid == 0) __hip_atomic_fetch_add(ja.epoch_p, 1u, __ATOMIC_RELAXED, RC_AGENT);  // the next launch uses a new key
         return;
     }
-    const T tol = sqrt((T)n) * JEps<T>::eps();
+    const T tol = sqrt((T)n) * num<T>::eps();
     const T tol2 = tol * tol;
 
     for (int e = tid; e < n * n; e += nthr) {

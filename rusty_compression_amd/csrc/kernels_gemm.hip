@@ -28,7 +28,6 @@
 
 namespace rc {
 
-static __host__ __device__ inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // smallest pitch >= n with pitch % 32 == 16 (conflict-free M/N-fastest fragment reads, 16x16x4 MFMA)
 constexpr int pitch16(int n) { return n + ((16 - n % 32) + 32) % 32; }
@@ -467,11 +466,6 @@ __global__ __launch_bounds__(256) void k_splitk_reduce_t(GemmArgs<T> g) {
             *cp = g.beta == (T)0 ? g.alpha * s : g.alpha * s + g.beta * (*cp);
         }
     }
-}
-
-static int env_int(const char *name, int dflt) {
-    const char *e = getenv(name);
-    return e ? atoi(e) : dflt;
 }
 
 // Split-K target of a product with >= 32 output tiles, from the compressions whose kernels run side by side

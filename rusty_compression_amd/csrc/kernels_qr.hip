@@ -25,16 +25,6 @@
 
 namespace rc {
 
-static __host__ __device__ inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-template <typename T> struct Num;
-template <> struct Num<double> {
-    static __host__ __device__ inline double tol3z() { return 1.0536712127723509e-08; }  // sqrt(2^-53)
-};
-template <> struct Num<float> {
-    static __host__ __device__ inline float tol3z() { return 2.44140625e-04f; }  // sqrt(2^-24)
-};
-
 template <typename T>
 __device__ inline T wsum(T v) {
 #pragma unroll
@@ -199,7 +189,7 @@ __global__ __launch_bounds__(256) void k_qr_apply(Mat<T> w, int64_t j, int pivot
         temp = temp > (T)0 ? temp : (T)0;
         T r = vn / vn2[p];
         T temp2 = temp * r * r;
-        if (temp2 <= Num<T>::tol3z()) {
+        if (temp2 <= num<T>::tol3z()) {
             T ss = 0;
 #pragma unroll
             for (int e = 0; e < MAXE; ++e) {
@@ -262,7 +252,7 @@ __global__ __launch_bounds__(256) void k_qr_apply_short(Mat<T> w, int64_t j, int
                     temp = temp > (T)0 ? temp : (T)0;
                     T r = vn / vn2[p];
                     T temp2 = temp * r * r;
-                    if (temp2 <= Num<T>::tol3z()) {
+                    if (temp2 <= num<T>::tol3z()) {
                         T ss = (i0 > j ? x0[u] * x0[u] : (T)0) + x1[u] * x1[u];
                         ss = wave_sum_dpp(ss);
                         if (lane == 0) { T nn = (j < m - 1) ? sqrt(ss) : (T)0; vn1[p] = nn; vn2[p] = nn; }
@@ -302,7 +292,7 @@ __global__ __launch_bounds__(256) void k_qr_apply_general(Mat<T> w, int64_t j, i
         temp = temp > (T)0 ? temp : (T)0;
         T r = vn / vn2[p];
         T temp2 = temp * r * r;
-        if (temp2 <= Num<T>::tol3z()) {
+        if (temp2 <= num<T>::tol3z()) {
             T ss = 0;
             for (int64_t i = j + 1 + threadIdx.x; i < m; i += 256) { T v = xcol[i]; ss += v * v; }
             ss = group_sum<T, 256>(ss, sh);
@@ -1011,7 +1001,7 @@ __global__ __launch_bounds__(256) void k_wq_row(Mat<T> b, Mat<T> qacc, Mat<T> rp
         temp = temp > (T)0 ? temp : (T)0;
         T r = vn / vn2[p];
         T temp2 = temp * r * r;
-        if (temp2 <= Num<T>::tol3z()) {
+        if (temp2 <= num<T>::tol3z()) {
             // exact trailing norm: || (Qacc^T b_c)[j+1:] ||
             T ssq = 0;
             for (int i2 = (int)j + 1; i2 < m; ++i2) {
@@ -1072,7 +1062,7 @@ __global__ __launch_bounds__(256) void k_wq_row_v2(Mat<T> b, Mat<T> qacc, Mat<T>
         temp = temp > (T)0 ? temp : (T)0;
         T r = vn / vnb;
         T temp2 = temp * r * r;
-        if (temp2 <= Num<T>::tol3z()) {
+        if (temp2 <= num<T>::tol3z()) {
             T ssq = 0;
             for (int i2 = (int)j + 1; i2 < m; ++i2) {
                 const T *qi = qacc.p + (int64_t)i2 * qacc.cs;

@@ -44,24 +44,21 @@
 
 namespace rc {
 
-static __host__ __device__ inline int64_t cdivb(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
 constexpr int kNB = 32;
 
 constexpr int kQrbVtaMaxSplits = 16;  // row chunks of the streaming Y = V^T A (k_qrb_vta): partial slabs summed by k_qrb_finish
-template <typename T> struct NumB;
-template <> struct NumB<double> {
+// the radix-select key of a norm (k_qrb_select): its bit pattern, which orders non-negative values as the values themselves
+template <typename T> struct NormKey;
+template <> struct NormKey<double> {
     typedef unsigned long long key_t;
     static constexpr int kKeyBits = 64;
     static constexpr int kSelBits = 32;
-    static __host__ __device__ inline double tol3z() { return 1.0536712127723509e-08; }  // sqrt(2^-53)
     static __device__ inline key_t key(double v) { return (key_t)__double_as_longlong(fabs(v)); }
 };
-template <> struct NumB<float> {
+template <> struct NormKey<float> {
     typedef unsigned int key_t;
     static constexpr int kKeyBits = 32;
     static constexpr int kSelBits = 24;
-    static __host__ __device__ inline float tol3z() { return 2.44140625e-04f; }  // sqrt(2^-24)
     static __device__ inline key_t key(float v) { return __float_as_uint(fabsf(v)); }
 };
 
@@ -105,7 +102,7 @@ __global__ __launch_bounds__(256) void k_qrb_init(Mat<T> w, int64_t *jpvt, int *
 template <typename T>
 __global__ __launch_bounds__(1024) void k_qrb_select(int n, int j0, int cwant, const int *pos, const T *vn1, int *cand, unsigned char *is_cand,
                                                      QrbState *st, T *tsc, int *cpos0, T *cvn0) {
-    typedef typename NumB<T>::key_t key_t;
+    typedef typename NormKey<T>::key_t key_t;
     __shared__ int hist[256];
     __shared__ int sh_scan[1024];
     __shared__ key_t sh_prefix;
@@ -119,13 +116,13 @@ __global__ __launch_bounds__(1024) void k_qrb_select(int n, int j0, int cwant, c
         key_t mask = 0;
         // the leading kSelBits bits of the norm decide (f32: sign + exponent + 15 mantissa bits, f64: + 20): the candidate
         // set is "every norm >= the bin of the cwant-th largest", i.e. at least cwant columns, ties and near-ties included
-        for (int shift = NumB<T>::kKeyBits - 8; shift >= NumB<T>::kKeyBits - NumB<T>::kSelBits; shift -= 8) {
+        for (int shift = NormKey<T>::kKeyBits - 8; shift >= NormKey<T>::kKeyBits - NormKey<T>::kSelBits; shift -= 8) {
             if (tid < 256) hist[tid] = 0;
             __syncthreads();
             const key_t prefix = sh_prefix;
             for (int c = tid; c < n; c += 1024) {
                 if (pos[c] < j0) continue;
-                const key_t kx = NumB<T>::key(vn1[c]);
+                const key_t kx = NormKey<T>::key(vn1[c]);
                 if ((kx & mask) == prefix) atomicAdd(&hist[(int)((kx >> shift) & 255)], 1);
             }
             __syncthreads();
@@ -168,7 +165,7 @@ __global__ __launch_bounds__(1024) void k_qrb_select(int n, int j0, int cwant, c
     T tmax = 0;
     for (int c = c0; c < c1; ++c) {
         const bool unp = pos[c] >= j0;
-        const bool in = unp && NumB<T>::key(vn1[c]) >= thr;
+        const bool in = unp && NormKey<T>::key(vn1[c]) >= thr;
         is_cand[c] = in ? 1 : 0;
         cnt += in ? 1 : 0;
         if (unp && !in) tmax = max(tmax, fabs(vn1[c]));
@@ -240,7 +237,7 @@ __device__ inline bool qrb_downdate(T a, T &vn, T vnb) {  // ?laqps norm down-da
     temp = ((T)1 + temp) * ((T)1 - temp);
     temp = temp > (T)0 ? temp : (T)0;
     const T r = vn / vnb;
-    if (temp * r * r <= NumB<T>::tol3z()) return true;
+    if (temp * r * r <= num<T>::tol3z()) return true;
     vn *= sqrt(temp);
     return false;
 }
@@ -264,7 +261,7 @@ __global__ __launch_bounds__(256) void k_qrb_step_a(Mat<T> w, int j0, int k, Qrb
     const int ncand = st->ncand;
     const int have_noncand = st->have_noncand;
     const int lsticc = st->lsticc;
-    const T lim = P.tsc[0] * ((T)1 + (T)4 * NumB<T>::tol3z());
+    const T lim = P.tsc[0] * ((T)1 + (T)4 * num<T>::tol3z());
     if (tid < kNB) shpiv[tid] = (tid < k) ? st->piv[tid] : 0;
     constexpr int NPF = 4;
     int pf_p[NPF], pf_c[NPF];
@@ -660,7 +657,7 @@ __global__ __launch_bounds__(256) void k_qrb_finish(Mat<T> w, int j0, int kb, co
                 temp = ((T)1 + temp) * ((T)1 - temp);
                 temp = temp > (T)0 ? temp : (T)0;
                 const T r = vn / vnb;
-                if (temp * r * r <= NumB<T>::tol3z()) lost = true;  // recomputed exactly after the block update
+                if (temp * r * r <= num<T>::tol3z()) lost = true;  // recomputed exactly after the block update
                 else vn *= sqrt(temp);
             }
         }
@@ -779,19 +776,19 @@ static bool qrb_vta_launch(rc_context *, Mat<T>, Mat<T>, int, T *, int64_t, int6
 // returns true and sets *nsplit when the streaming kernel ran (ypart: nsplit slabs of kNB x ldy); false: take the GEMM
 template <>
 bool qrb_vta_launch<float>(rc_context *c, Mat<float> vpp, Mat<float> wsub, int kb, float *ypart, int64_t ldy, int64_t sstride, int *nsplit, const int *ok) {
-    static const int on = [] { const char *e = getenv("RC_QRCP_VTA"); return e ? atoi(e) : 1; }();
+    static const int on = env_int("RC_QRCP_VTA", 1);
     const int64_t rows = wsub.rows, n = wsub.cols;
     if (!on || wsub.rs != 1 || vpp.rs != 1 || rows < 256 || n < 64 || kb > kNB) return false;
     if ((wsub.cs % 4) || (vpp.cs % 4) || (reinterpret_cast<uintptr_t>(wsub.p) % 16) || (reinterpret_cast<uintptr_t>(vpp.p) % 16)) return false;
     // row chunks so that ~1024 waves exist (4 per CU): a chunk is a whole number of 16-row steps
-    const int64_t col_wgs = cdivb(n, 256);
+    const int64_t col_wgs = cdiv(n, 256);
     int splits = (int)std::max<int64_t>(1, std::min<int64_t>(kQrbVtaMaxSplits, 256 / std::max<int64_t>(col_wgs, 1)));
-    int64_t rps = cdivb(cdivb(rows, splits), 16) * 16;
-    splits = (int)cdivb(rows, rps);
+    int64_t rps = cdiv(cdiv(rows, splits), 16) * 16;
+    splits = (int)cdiv(rows, rps);
     ProfScope ps(c, "kernel:k_qrb_vta rows=%lld n=%lld kb=%d splits=%d", (long long)rows, (long long)n, kb, splits);
     hipLaunchKernelGGL(k_qrb_vta, dim3((unsigned)col_wgs, (unsigned)splits), dim3(256), 0, c->stream, vpp.p, vpp.cs, wsub.p, wsub.cs, (int)rows, (int)n, kb, ypart, ldy, sstride,
                        (int)rps, ok);
-    if (splits > 1) hipLaunchKernelGGL(k_qrb_ysum, dim3((unsigned)cdivb((int64_t)kb * n, 256)), dim3(256), 0, c->stream, ypart, ldy, sstride, kb, (int)n, splits, ok);
+    if (splits > 1) hipLaunchKernelGGL(k_qrb_ysum, dim3((unsigned)cdiv((int64_t)kb * n, 256)), dim3(256), 0, c->stream, ypart, ldy, sstride, kb, (int)n, splits, ok);
     *nsplit = 1;  // slab 0 holds Y
     return true;
 }
@@ -941,7 +938,7 @@ __global__ __launch_bounds__(512, WPE) void k_qrb_coop(QrbCoopArgs<T> a) {
     int mypos = __builtin_amdgcn_readfirstlane(have ? a.P.cpos[0][ci] : kNoInt);
     T vn1 = have ? a.P.cvn[ci] : (T)0, vn2 = have ? a.P.vn2[c] : (T)0;
     bool renormed = false;
-    const T lim = a.P.tsc[0] * ((T)1 + (T)4 * NumB<T>::tol3z());
+    const T lim = a.P.tsc[0] * ((T)1 + (T)4 * num<T>::tol3z());
     const int have_noncand = st->have_noncand;
     __syncthreads();
 
@@ -1193,7 +1190,7 @@ __global__ __launch_bounds__(512, WPE) void k_qrb_coop(QrbCoopArgs<T> a) {
                     T temp = (T)1 - t * t;
                     temp = temp > (T)0 ? temp : (T)0;
                     const T r2 = vn1 / vn2;
-                    if (temp * r2 * r2 <= NumB<T>::tol3z()) {
+                    if (temp * r2 * r2 <= num<T>::tol3z()) {
                         T ssl = 0;
 #pragma unroll
                         for (int e = 0; e < NE; ++e)
@@ -1382,14 +1379,15 @@ __global__ __launch_bounds__(256) void k_qrb_check_perm(const int64_t *jpvt, con
     }
 }
 
-static int env_int_b(const char *name, int dflt) {
-    const char *e = getenv(name);
-    return e ? atoi(e) : dflt;
+// RC_QRCP_CHECK: the permutation is validated after every panel (diagnostic; the optimistic issue, which has no panel ends on the host, is off)
+static int qrcp_check() {
+    static const int check = env_int("RC_QRCP_CHECK", 0);
+    return check;
 }
 
 template <typename T>
 bool geqp3_blocked_supported(int64_t m, int64_t n, int64_t kmax) {
-    static const int on = env_int_b("RC_QRCP_BLOCKED", 1);
+    static const int on = env_int("RC_QRCP_BLOCKED", 1);
     return on && m >= 128 && n >= 128 && kmax >= 8 && n < (int64_t)1 << 30 && m < (int64_t)1 << 30;
 }
 
@@ -1450,18 +1448,21 @@ struct BlockedQrcpJob {
     int coop_fallbacks = 0;
     int64_t cw_issued = 0;
     unsigned grid_a = 0, grid_c = 0;
-    // optimistic issue (qrb_issue_all_optimistic): panel p's state goes to host_st[log_base + p]; nbp_log[p] = the steps it was assumed to make
-    bool optimistic = false, opt_broken = false;
+    // optimistic issue (qrb_issue_optimistic): panel p's state goes to its own pinned slot, opt.log[p]
+    bool optimistic = false;
+    QrbOptimistic opt;
     int *opt_ok = nullptr;  // device word: 1 while every assumption of the optimistic issue has held (k_qrb_opt_check clears it)
-    int log_base = 0, log_n = 0;
-    std::vector<int> nbp_log;
+    // where the host reads the state of the panel being issued
+    QrbState *state_slot() const { return optimistic ? const_cast<QrbState *>(opt.log) + opt.panels : host_st; }
 };
+template <typename T>
+void QrbJobDelete<T>::operator()(BlockedQrcpJob<T> *job) const { delete job; }
 
 template <typename T>
-BlockedQrcpJob<T> *qrb_begin(rc_context *c, Mat<T> w, int64_t kmax, int64_t *jpvt, T *tau) {
+QrbJobPtr<T> qrb_begin(rc_context *c, Mat<T> w, int64_t kmax, int64_t *jpvt, T *tau) {
     RC_REQUIRE(w.rs == 1, RC_LAYOUT_ERROR, "geqp3_blocked: working matrix must be column-major");
     RC_REQUIRE(!c->capturing, RC_RUNTIME_ERROR, "geqp3_blocked: reads one scalar back per panel, not capturable");
-    auto *J = new BlockedQrcpJob<T>();
+    QrbJobPtr<T> J(new BlockedQrcpJob<T>());
     J->c = c; J->w = w; J->jpvt = jpvt; J->tau = tau;
     const int64_t m = w.rows, n = w.cols;
     J->m = m; J->n = n;
@@ -1500,18 +1501,18 @@ BlockedQrcpJob<T> *qrb_begin(rc_context *c, Mat<T> w, int64_t kmax, int64_t *jpv
     // whole F rows are read: keep them finite; the strictly lower part of T stays zero (block form-Q multiplies by the full square)
     fill_words(c, J->Fm, ((size_t)n * kNB + (size_t)kNB * kNB) * sizeof(T), 0u);
     J->vec_ok = (w.cs % (16 / (int64_t)sizeof(T)) == 0 && reinterpret_cast<uintptr_t>(w.p) % 16 == 0) ? 1 : 0;
-    hipLaunchKernelGGL(k_qrb_init<T>, dim3((unsigned)std::min<int64_t>(cdivb(n, 4), 8192)), dim3(256), 0, c->stream, w, jpvt, J->pos, J->vn1, J->vn2, J->flag);
+    hipLaunchKernelGGL(k_qrb_init<T>, dim3((unsigned)std::min<int64_t>(cdiv(n, 4), 8192)), dim3(256), 0, c->stream, w, jpvt, J->pos, J->vn1, J->vn2, J->flag);
     // candidate budget: about RC_QRCP_CAND_MB of column data, at least 4 NB columns.  A cooperative panel holds one wave per candidate,
     // so the budget is also its CU demand: 4 MB = 256 candidates = 32 workgroups for 4096 rows of f32 (8 MB until round 3: 64 workgroups;
     // eight lanes' panels did not fit the device budget at once).  Fewer candidates end a panel earlier on flat norm profiles (the tau
     // test; the next panel then asks for more).  Measured, 8 x 4096^2 f32 Gaussian, k = 64, batch of 8: 2450 (8 MB) -> 2690 (5) -> 2820 (4)
     // -> 2940 (3) matrices/s, 1470 at 2 MB (every panel ends early); one matrix 0.91 -> 0.88 ms.  NOTE: R12 / Z differ in the last bits
     // with the candidate count (candidates are updated reflector by reflector, the other columns through the block update).
-    static const int cand_mb = env_int_b("RC_QRCP_CAND_MB", 4);
+    static const int cand_mb = env_int("RC_QRCP_CAND_MB", 4);
     J->cwant = std::max<int64_t>(4 * kNB, ((int64_t)cand_mb << 20) / (int64_t)(sizeof(T) * (size_t)std::max<int64_t>(m, 1)));
     if (cand_mb <= 0) J->cwant = n;  // plain ?laqps
     // cooperative panels: header / candidate slots of up to kCoopWgs workgroups, the recorded v_t^T v_k
-    static const int coop_on = env_int_b("RC_QRCP_COOP", 1);
+    static const int coop_on = env_int("RC_QRCP_COOP", 1);
     if (coop_on && c->opt_coop_panel && cand_mb > 0) {
         QrbCoopArgs<T> &a = J->coop;
         a.w = w;
@@ -1538,7 +1539,7 @@ static void qrb_issue_launches(BlockedQrcpJob<T> *J, int nbp, int64_t cw, unsign
         hipLaunchKernelGGL(k_qrb_step_a<T>, dim3(grid_a), dim3(256), 0, c->stream, J->w, (int)j0, k, J->P);
         hipLaunchKernelGGL(k_qrb_step_c<T>, dim3(grid_c), dim3(256), 0, c->stream, J->w, (int)j0, k, (int)grid_a, J->vec_ok, J->P);
     }
-    RC_HIP(hipMemcpyAsync(J->host_st + (J->optimistic ? J->log_base + J->log_n : 0), J->st, sizeof(QrbState), hipMemcpyDeviceToHost, c->stream));
+    RC_HIP(hipMemcpyAsync(J->state_slot(), J->st, sizeof(QrbState), hipMemcpyDeviceToHost, c->stream));
 }
 
 template <typename T>
@@ -1551,21 +1552,21 @@ void qrb_issue(BlockedQrcpJob<T> *J) {
     // step A: one row slab of the pivot column per workgroup (every workgroup scans all candidate norms: few workgroups
     // when the candidates are many); step C: one workgroup per candidate
     const int64_t cbound = std::min<int64_t>(n - j0, 2 * cw);
-    const unsigned grid_a = (unsigned)std::max<int64_t>(4, std::min<int64_t>(std::min<int64_t>(64, cdivb(m - j0, 64)), 65536 / std::max<int64_t>(cbound, 1)));
+    const unsigned grid_a = (unsigned)std::max<int64_t>(4, std::min<int64_t>(std::min<int64_t>(64, cdiv(m - j0, 64)), 65536 / std::max<int64_t>(cbound, 1)));
     const unsigned grid_c = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cbound, 4096));
     J->grid_a = grid_a; J->grid_c = grid_c; J->cw_issued = cw; J->coop_issued = false;
     // Cooperative panel (one launch for all steps, candidates in registers) when the active rows fit the registers of a
     // wave; fewer candidates are requested than the launch has waves, because ties at the threshold all become candidates
     if (J->coop_ready && J->coop_fallbacks < 4 && m - j0 <= coop_rows_cap<T>() && m - j0 >= 8) {
         const int64_t cw_c = std::min<int64_t>(cw, 8 * kCoopWgs - 32);
-        const int g = (int)std::min<int64_t>(kCoopWgs, cdivb(cw_c + std::max<int64_t>(8, cw_c / 16), 8));
+        const int g = (int)std::min<int64_t>(kCoopWgs, cdiv(cw_c + std::max<int64_t>(8, cw_c / 16), 8));
         hipLaunchKernelGGL(k_qrb_select<T>, dim3(1), dim3(1024), 0, c->stream, (int)n, (int)j0, (int)cw_c, J->pos, J->vn1, J->cand, J->is_cand, J->st, J->tsc, J->P.cpos[0],
                            J->P.cvn);
         QrbCoopArgs<T> a = J->coop;
         a.j0 = (int)j0;
         a.nbp = nbp;
         if (qrb_coop_launch<T>(c, a, g, (int)(m - j0), J->optimistic ? J->opt_ok : nullptr)) {
-            RC_HIP(hipMemcpyAsync(J->host_st + (J->optimistic ? J->log_base + J->log_n : 0), J->st, sizeof(QrbState), hipMemcpyDeviceToHost, c->stream));
+            RC_HIP(hipMemcpyAsync(J->state_slot(), J->st, sizeof(QrbState), hipMemcpyDeviceToHost, c->stream));
             J->coop_issued = true;
             J->cw_issued = cw_c;
             return;
@@ -1608,12 +1609,11 @@ static bool qrb_finish_with(BlockedQrcpJob<T> *J, QrbState h, bool coop, bool op
     const int64_t m = J->m, n = J->n, j0 = J->j0;
     const int kb = h.stopped ? h.kb : J->nbp;
     RC_REQUIRE(kb >= 1 && kb <= J->nbp, RC_PIVOTED_QR_ERROR, "geqp3_blocked: panel at %lld made %d steps", (long long)j0, kb);
-    static const int check = env_int_b("RC_QRCP_CHECK", 0);
-    if (check && !optimistic) {
+    if (qrcp_check() && !optimistic) {
         ArenaMark mk(c);
         int *mark = c->alloc<int>((size_t)n + 4);
         fill_words(c, mark, ((size_t)n + 4) * sizeof(int), 0u);
-        hipLaunchKernelGGL(k_qrb_check_perm, dim3((unsigned)std::min<int64_t>(cdivb(n, 256), 1024)), dim3(256), 0, c->stream, J->jpvt, J->pos, (int)n, mark, mark + n);
+        hipLaunchKernelGGL(k_qrb_check_perm, dim3((unsigned)std::min<int64_t>(cdiv(n, 256), 1024)), dim3(256), 0, c->stream, J->jpvt, J->pos, (int)n, mark, mark + n);
         int bad[3] = {0, 0, 0};
         RC_HIP(hipMemcpyAsync(bad, mark + n, sizeof(bad), hipMemcpyDeviceToHost, c->stream));
         RC_HIP(hipStreamSynchronize(c->stream));
@@ -1628,7 +1628,7 @@ static bool qrb_finish_with(BlockedQrcpJob<T> *J, QrbState h, bool coop, bool op
     const int *okp = optimistic ? J->opt_ok : nullptr;
     Mat<T> w = J->w;
     Mat<T> vpp = Mat<T>(J->vp.p, rows, kb, 1, J->vp.cs);
-    hipLaunchKernelGGL(k_qrb_build_vp<T>, dim3((unsigned)std::min<int64_t>(cdivb(rows, 256), 64), (unsigned)kb), dim3(256), 0, c->stream, w, (int)j0, J->st, vpp, okp);
+    hipLaunchKernelGGL(k_qrb_build_vp<T>, dim3((unsigned)std::min<int64_t>(cdiv(rows, 256), 64), (unsigned)kb), dim3(256), 0, c->stream, w, (int)j0, J->st, vpp, okp);
     int ysplits = 1;
     if (h.have_noncand) {
         // Y = V^T A(j0:m, :) for every column: one read pass; used for the non-candidates only.  f32 with 16-byte aligned columns: the
@@ -1640,23 +1640,23 @@ static bool qrb_finish_with(BlockedQrcpJob<T> *J, QrbState h, bool coop, bool op
         }
     }
     if (coop) hipLaunchKernelGGL(k_qrb_build_t<T>, dim3(1), dim3(1024), 0, c->stream, J->coop.D, J->tau, (int)j0, kb, J->Tm, okp);
-    else hipLaunchKernelGGL(k_qrb_scatter<T>, dim3((unsigned)cdivb(std::max(h.ncand, 1), 256)), dim3(256), 0, c->stream, w, (int)j0, kb, J->P, J->vn1);
-    hipLaunchKernelGGL(k_qrb_finish<T>, dim3((unsigned)cdivb(n, 256)), dim3(256), 0, c->stream, w, (int)j0, kb, J->pos, J->is_cand, J->vn1, J->vn2, J->Fm, J->Y, J->ldy,
+    else hipLaunchKernelGGL(k_qrb_scatter<T>, dim3((unsigned)cdiv(std::max(h.ncand, 1), 256)), dim3(256), 0, c->stream, w, (int)j0, kb, J->P, J->vn1);
+    hipLaunchKernelGGL(k_qrb_finish<T>, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, c->stream, w, (int)j0, kb, J->pos, J->is_cand, J->vn1, J->vn2, J->Fm, J->Y, J->ldy,
                        J->Tm, vpp, J->flag, coop ? 1 : 0, ysplits, (int64_t)kNB * J->ldy, okp);
     if (!last && rows - kb > 0) {
         // block update of everything below the panel, written as the transposed product so that the lanes of the
         // MFMA accumulator run along the column-major matrix' contiguous dimension:
         //   A(j0+kb:m, :)^T -= F(:, 0:kb) V(kb:, 0:kb)^T
-        static const int stream_upd = env_int_b("RC_QRCP_STREAM_UPDATE", 1);
+        static const int stream_upd = env_int("RC_QRCP_STREAM_UPDATE", 1);
         if (stream_upd) {
             // streaming rank-kb update (k_qrb_block_update): rows in strips of 256 * RPT, columns in strips sized for ~4 waves of
             // workgroups on the chip
             constexpr int RPT = sizeof(T) == 8 ? 1 : 2;  // 64 registers of V per lane: four waves per SIMD
             const int64_t ur = rows - kb;
-            const unsigned gx = (unsigned)cdivb(ur, 256 * RPT);
-            static const int upd_wgs = env_int_b("RC_QRCP_UPDATE_WGS", 1024);  // every workgroup re-reads its rows of V: wide column strips amortise it
-            const int cols_per_wg = (int)std::max<int64_t>(8, cdivb(n, std::max<int64_t>(1, upd_wgs / gx)));
-            hipLaunchKernelGGL((k_qrb_block_update<T, RPT>), dim3(gx, (unsigned)cdivb(n, cols_per_wg)), dim3(256), 0, c->stream, w, (int)(j0 + kb), kb, (int)j0, vpp,
+            const unsigned gx = (unsigned)cdiv(ur, 256 * RPT);
+            static const int upd_wgs = env_int("RC_QRCP_UPDATE_WGS", 1024);  // every workgroup re-reads its rows of V: wide column strips amortise it
+            const int cols_per_wg = (int)std::max<int64_t>(8, cdiv(n, std::max<int64_t>(1, upd_wgs / gx)));
+            hipLaunchKernelGGL((k_qrb_block_update<T, RPT>), dim3(gx, (unsigned)cdiv(n, cols_per_wg)), dim3(256), 0, c->stream, w, (int)(j0 + kb), kb, (int)j0, vpp,
                                kb, J->Fm, J->pos, J->is_cand, coop ? 1 : 0, cols_per_wg, okp);
         } else {
             Mat<T> ft = Mat<T>(J->Fm, n, kb, kNB, 1);
@@ -1666,7 +1666,7 @@ static bool qrb_finish_with(BlockedQrcpJob<T> *J, QrbState h, bool coop, bool op
         // unpivoted column is recomputed instead: on matrices with a steadily decaying spectrum all columns drift towards the
         // accuracy threshold together (vn1 / vn2 shrinks at the same rate everywhere), and recomputing them one flag at a
         // time would end a panel after every single step for hundreds of steps (which is what LAPACK's own ?geqp3 does there)
-        hipLaunchKernelGGL(k_qrb_renorm<T>, dim3((unsigned)std::min<int64_t>(cdivb(n, 4), 4096)), dim3(256), 0, c->stream, w, (int)(j0 + kb), h.lsticc, J->pos, J->flag,
+        hipLaunchKernelGGL(k_qrb_renorm<T>, dim3((unsigned)std::min<int64_t>(cdiv(n, 4), 4096)), dim3(256), 0, c->stream, w, (int)(j0 + kb), h.lsticc, J->pos, J->flag,
                            J->vn1, J->vn2, optimistic ? J->st : (const QrbState *)nullptr, okp);
     }
     // a panel that the tau test ended early means the candidate set was too small for this spectrum
@@ -1675,7 +1675,7 @@ static bool qrb_finish_with(BlockedQrcpJob<T> *J, QrbState h, bool coop, bool op
         RC_HIP(hipMemcpyAsync(tsave, J->Tm, (size_t)kNB * kNB * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
         J->panels.push_back({j0, kb, tsave});
     }
-    static const int dbg = env_int_b("RC_QRCP_DEBUG", 0);
+    static const int dbg = env_int("RC_QRCP_DEBUG", 0);
     if (dbg) fprintf(stderr, "qrb panel w=%p j0=%lld kb=%d/%d ncand=%d noncand=%d lsticc=%d stop_tau=%d cwant=%lld coop=%d pad0=%d fallbacks=%d\n", (void *)J->w.p, (long long)j0, kb, J->nbp, h.ncand, h.have_noncand, h.lsticc, h.stop_tau, (long long)J->cwant, coop ? 1 : 0, h.pad0, J->coop_fallbacks);
     if (h.stop_tau && kb < J->nbp) J->cwant = std::min<int64_t>(n, kb < J->nbp / 2 ? J->cwant * 2 : J->cwant * 3 / 2);
     J->j0 += kb;
@@ -1686,16 +1686,16 @@ static bool qrb_finish_with(BlockedQrcpJob<T> *J, QrbState h, bool coop, bool op
 // Optimistic issue.  The host reads a panel's state back only to learn what almost always holds for a truncated factorization
 // of a few panels (cfg5: two): the cooperative launch completed (pad0 == 1) and made all its steps.  Here ALL panels and their
 // panel ends are enqueued back to back on those assumptions, each panel's state is copied to its own pinned slot, and the host
-// checks the slots ONCE afterwards (qrb_verify_optimistic): one wait per factorization instead of one per panel, and in a batch
+// checks the slots ONCE afterwards (QrbOptimistic::verified): one wait per factorization instead of one per panel, and in a batch
 // no wait at all until every matrix has been issued.  A failed check means the working matrix is garbage: the caller restores it
 // from its source and runs the per-panel path (qrb_issue / wait / qrb_finish), which handles every case.
 // Needs: cooperative panels for every panel of the job, no T factors kept (no Q wanted), no per-panel diagnostics.
 template <typename T>
-bool qrb_optimistic_possible(BlockedQrcpJob<T> *J) {
-    static const int on = env_int_b("RC_QRCP_OPTIMISTIC", 1), check = env_int_b("RC_QRCP_CHECK", 0);
-    if (!on || check || !J->coop_ready || J->keep_t || J->j0 != 0) return false;
-    const int64_t panels = cdivb(J->kmax, kNB);
-    if (panels < 1 || panels > 16) return false;
+static bool qrb_optimistic_possible(BlockedQrcpJob<T> *J) {
+    static const int on = env_int("RC_QRCP_OPTIMISTIC", 1);
+    if (!on || qrcp_check() || !J->coop_ready || J->keep_t || J->j0 != 0) return false;
+    const int64_t panels = cdiv(J->kmax, kNB);
+    if (panels < 1 || panels > kQrbOptMaxPanels) return false;
     // every panel must take the cooperative path: rows fit a wave's registers (qrb_issue's own test) at the panel's first row
     const int64_t rows_first = J->m, rows_last = J->m - (panels - 1) * kNB;
     return rows_first <= coop_rows_cap<T>() && rows_last >= 8;
@@ -1709,52 +1709,50 @@ __global__ void k_qrb_opt_check(const QrbState *st, int assumed_kb, int *ok) {
 
 // slots of pinned state this context hands to optimistic jobs before somebody has to wait (rc_batch resets the cursor per call)
 template <typename T>
-bool qrb_issue_all_optimistic(BlockedQrcpJob<T> *J) {
+QrbOptimistic qrb_issue_optimistic(BlockedQrcpJob<T> *J) {
     rc_context *c = J->c;
-    const int panels = (int)cdivb(J->kmax, kNB);
+    QrbOptimistic &o = J->opt;
+    if (!qrb_optimistic_possible(J)) return o;
+    const int panels = (int)cdiv(J->kmax, kNB);
     const int cap = (int)(c->pinned_size / sizeof(QrbState));
-    if (c->pinned_cursor + panels > cap) return false;  // the caller waits, checks what is pending and resets the cursor
+    if (c->pinned_cursor + panels > cap) {  // the caller waits, checks what is pending and resets the cursor
+        o.status = QrbOptimistic::NoSlots;
+        return o;
+    }
     J->optimistic = true;
-    J->log_base = c->pinned_cursor;
-    J->log_n = 0;
+    o.status = QrbOptimistic::Issued;
+    o.log = J->host_st + c->pinned_cursor;
+    o.panels = 0;
     c->pinned_cursor += panels;
     fill_words(c, J->opt_ok, 2 * sizeof(int), 1u);
     for (int p = 0; p < panels; ++p) {
         qrb_issue(J);
         if (!J->coop_issued) {  // (the device budget shrank: the step kernels were enqueued instead -- nothing behind them may run)
             fill_words(c, J->opt_ok, 2 * sizeof(int), 0u);
-            J->opt_broken = true;
-            return true;
+            o.broken = true;
+            return o;
         }
         hipLaunchKernelGGL(k_qrb_opt_check, dim3(1), dim3(64), 0, c->stream, J->st, J->nbp, J->opt_ok);
         J->coop_issued = false;
-        J->nbp_log.push_back(J->nbp);
+        o.nbp[o.panels++] = J->nbp;
         QrbState h;
         memset(&h, 0, sizeof(h));
         h.pad0 = 1;
         h.have_noncand = 1;
-        J->log_n = p + 1;
         if (qrb_finish_with(J, h, true, true)) break;
     }
-    return true;
+    return o;
 }
 
 // after the stream has been waited for: did every assumption hold?
-template <typename T>
-bool qrb_verify_optimistic(const QrbState *host_log, const std::vector<int> &nbp_log, bool broken) {
-    if (broken) return false;
-    for (size_t p = 0; p < nbp_log.size(); ++p) {
-        const QrbState &h = host_log[p];
-        if (h.pad0 != 1) return false;                       // the cooperative launch gave up (time-out, more candidates than waves)
-        if (h.stopped && h.kb != nbp_log[p]) return false;   // the panel ended early (tau test)
+bool QrbOptimistic::verified() const {
+    if (status != Issued || broken) return false;
+    for (int p = 0; p < panels; ++p) {
+        const QrbState &h = log[p];
+        if (h.pad0 != 1) return false;                  // the cooperative launch gave up (time-out, more candidates than waves)
+        if (h.stopped && h.kb != nbp[p]) return false;  // the panel ended early (tau test)
     }
     return true;
-}
-template <typename T>
-bool qrb_verify_optimistic(BlockedQrcpJob<T> *J) { return qrb_verify_optimistic<T>(J->host_st + J->log_base, J->nbp_log, J->opt_broken); }
-template <typename T>
-void qrb_optimistic_log(BlockedQrcpJob<T> *J, const QrbState **log, std::vector<int> *nbp_log, bool *broken) {
-    *log = J->host_st + J->log_base; *nbp_log = J->nbp_log; *broken = J->opt_broken;
 }
 
 // Q(:, 0:kq) = H_0 ... H_{k-1} [I ; 0] from the finished job, panel by panel from the last to the first:
@@ -1778,7 +1776,7 @@ void qrb_form_q(BlockedQrcpJob<T> *J, Mat<T> q) {
         const int kb = pr.kb;
         Mat<T> vpp = Mat<T>(J->vp.p, rows, kb, 1, J->vp.cs);
         // the panel's pivot columns: positions j0 .. j0+kb-1 of jpvt (device) -> build V from them
-        hipLaunchKernelGGL(k_qrb_build_vp_pos<T>, dim3((unsigned)std::min<int64_t>(cdivb(rows, 256), 64), (unsigned)kb), dim3(256), 0, c->stream, J->w, (int)pr.j0, J->jpvt, vpp);
+        hipLaunchKernelGGL(k_qrb_build_vp_pos<T>, dim3((unsigned)std::min<int64_t>(cdiv(rows, 256), 64), (unsigned)kb), dim3(256), 0, c->stream, J->w, (int)pr.j0, J->jpvt, vpp);
         Mat<T> qs = q.sub(pr.j0, rows, pr.j0, ncols);
         Mat<T> w2 = rowmajor(w2p, kb, ncols, even_ld(kq)), w3 = rowmajor(w3p, kb, ncols, even_ld(kq));
         gemm<T>(c, 1, vpp.t(), qs, 0, w2);
@@ -1787,9 +1785,6 @@ void qrb_form_q(BlockedQrcpJob<T> *J, Mat<T> q) {
     }
 }
 
-template <typename T>
-void qrb_end(BlockedQrcpJob<T> *J) { delete J; }
-
 // w: m x n column-major working matrix (overwritten with the ?geqp3 output format: R on and above the
 // diagonal in position order, reflectors below, columns never moved); jpvt: n; tau: kmax
 template <typename T>
@@ -1797,44 +1792,39 @@ void geqp3_blocked(rc_context *c, Mat<T> w, int64_t kmax, int64_t *jpvt, T *tau,
     if (std::min(kmax, std::min(w.rows, w.cols)) <= 0) return;
     ProfScope ps(c, "op:geqp3_blocked %lldx%lld k=%lld", (long long)w.rows, (long long)w.cols, (long long)kmax);
     if (restore_from.p && q_out.empty()) {
-        // all panels enqueued on the usual outcome, ONE wait, then the check (see qrb_issue_all_optimistic)
+        // all panels enqueued on the usual outcome, ONE wait, then the check (see qrb_issue_optimistic)
         ArenaMark mark(c);
-        BlockedQrcpJob<T> *J = qrb_begin<T>(c, w, kmax, jpvt, tau);
-        struct Guard { BlockedQrcpJob<T> *j; ~Guard() { qrb_end(j); } } guard{J};
-        J->keep_t = false;
-        c->pinned_cursor = 0;
-        if (qrb_optimistic_possible(J) && qrb_issue_all_optimistic(J)) {
+        QrbJobPtr<T> job = qrb_begin<T>(c, w, kmax, jpvt, tau);
+        c->reset_pinned_slots();
+        const QrbOptimistic o = qrb_issue_optimistic(job.get());
+        if (o.status == QrbOptimistic::Issued) {
             RC_HIP(hipStreamSynchronize(c->stream));
-            if (qrb_verify_optimistic(J)) return;
+            if (o.verified()) return;
             copy_mat(c, restore_from, w);  // an assumption failed: start over on a fresh copy, panel by panel
         }
     }
     ArenaMark mark(c);
-    BlockedQrcpJob<T> *J = qrb_begin<T>(c, w, kmax, jpvt, tau);
-    struct Guard { BlockedQrcpJob<T> *j; ~Guard() { qrb_end(j); } } guard{J};
-    J->keep_t = !q_out.empty();
+    QrbJobPtr<T> job = qrb_begin<T>(c, w, kmax, jpvt, tau);
+    job->keep_t = !q_out.empty();
     for (;;) {
-        qrb_issue(J);
+        qrb_issue(job.get());
         RC_HIP(hipStreamSynchronize(c->stream));
-        if (qrb_finish(J)) break;
+        if (qrb_finish(job.get())) break;
     }
-    if (!q_out.empty()) qrb_form_q(J, q_out);
+    if (!q_out.empty()) qrb_form_q(job.get(), q_out);
 }
 
 #ifdef RC_QRC_TIMING
 extern "C" void rc_debug_qrc_timing(unsigned long long *out) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_qrc_dbg), 8 * sizeof(unsigned long long)); }
 #endif
-#define RC_INST_JOB(T)                                                                           \
-    template BlockedQrcpJob<T> *qrb_begin<T>(rc_context *, Mat<T>, int64_t, int64_t *, T *);     \
-    template void qrb_issue<T>(BlockedQrcpJob<T> *);                                             \
-    template bool qrb_finish<T>(BlockedQrcpJob<T> *);                                            \
-    template void qrb_form_q<T>(BlockedQrcpJob<T> *, Mat<T>);                                    \
-    template void qrb_end<T>(BlockedQrcpJob<T> *);                                               \
-    template bool qrb_optimistic_possible<T>(BlockedQrcpJob<T> *);                               \
-    template bool qrb_issue_all_optimistic<T>(BlockedQrcpJob<T> *);                              \
-    template bool qrb_verify_optimistic<T>(BlockedQrcpJob<T> *);                                 \
-    template bool qrb_verify_optimistic<T>(const QrbState *, const std::vector<int> &, bool);    \
-    template void qrb_optimistic_log<T>(BlockedQrcpJob<T> *, const QrbState **, std::vector<int> *, bool *);
+// (qrb_form_q has no caller outside this file; instantiated here, its kernels keep their place in the code object)
+#define RC_INST_JOB(T)                                                                    \
+    template struct QrbJobDelete<T>;                                                      \
+    template QrbJobPtr<T> qrb_begin<T>(rc_context *, Mat<T>, int64_t, int64_t *, T *);    \
+    template void qrb_issue<T>(BlockedQrcpJob<T> *);                                      \
+    template bool qrb_finish<T>(BlockedQrcpJob<T> *);                                     \
+    template void qrb_form_q<T>(BlockedQrcpJob<T> *, Mat<T>);                             \
+    template QrbOptimistic qrb_issue_optimistic<T>(BlockedQrcpJob<T> *);
 RC_INST_JOB(double)
 RC_INST_JOB(float)
 #undef RC_INST_JOB

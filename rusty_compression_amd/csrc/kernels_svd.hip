@@ -94,7 +94,7 @@ __global__ __launch_bounds__(256) void k_jacobi_round(Mat<T> g, Mat<T> v, int r,
     int p, q;
     rr_pair(N, r, pi, p, q);
     if (q >= n) return;  // the dummy column of an odd n
-    const T tol = sqrt((T)n) * JEps<T>::eps();
+    const T tol = sqrt((T)n) * num<T>::eps();
     T *gp = g.p + (int64_t)p * g.cs, *gq = g.p + (int64_t)q * g.cs;
     T app = 0, aqq = 0, apq = 0;
     for (int i = lane; i < n; i += 64) {

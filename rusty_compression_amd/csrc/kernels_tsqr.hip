@@ -25,17 +25,10 @@
 
 namespace rc {
 
-static __host__ __device__ inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-template <typename T> struct TNum;
-template <> struct TNum<double> {
-    static __device__ inline double tol3z() { return 1.0536712127723509e-08; }
-    static __device__ inline double tiny() { return 1e-300; }
-};
-template <> struct TNum<float> {
-    static __device__ inline float tol3z() { return 2.44140625e-04f; }
-    static __device__ inline float tiny() { return 1e-30f; }
-};
+// what stands in for a Cholesky pivot that is not positive (the failure is flagged; the arithmetic behind it stays finite)
+template <typename T> __device__ inline T tiny_pivot();
+template <> __device__ inline double tiny_pivot<double>() { return 1e-300; }
+template <> __device__ inline float tiny_pivot<float>() { return 1e-30f; }
 
 template <typename T>
 __device__ inline T wave_sum64(T v) {
@@ -151,7 +144,7 @@ __global__ __launch_bounds__(1024) void k_chol_inv(Mat<T> g, Mat<T> r_out, Mat<T
         T d = rb[j];
         if (!(d > (T)0)) {
             if (tid == 0) atomicOr(flag, 1);
-            d = TNum<T>::tiny();
+            d = tiny_pivot<T>();
         }
         const T invr = fast_rsqrt(d), invd = invr * invr;
         T cv[NT];
@@ -240,7 +233,7 @@ void tsqr_cholqr2_factored(rc_context *c, Mat<T> y, Mat<T> q1, Mat<T> r2i, Mat<T
     gemm<T>(c, 1, y, r1i, 0, q1);
     gemm<T>(c, 1, q1.t(), q1, 0, g);
     // after one pass ||Q1^T Q1 - I|| ~ cond(Y)^2 eps; the second pass is only accurate while that is << 1
-    static const int skip_ok = [] { const char *e = getenv("RC_CHOLQR_SKIP"); return e ? atoi(e) : 1; }();
+    static const int skip_ok = env_int("RC_CHOLQR_SKIP", 1);
     const T skip_tol = skip_ok ? (sizeof(T) == 8 ? (T)2.5e-14 : (T)1e-6) : (T)-1;
     chol_inv<T>(c, g, r2, r2i, true, (T)1e-2, skip_tol, flag);
     gemm<T>(c, 1, r2, r1, 0, r);
@@ -326,7 +319,7 @@ __device__ __forceinline__ void qrcp_small_apply(T *A, int ld, int n, int j, int
                 temp = temp > (T)0 ? temp : (T)0;
                 T rr = vn * fast_rcp(vn2[p]);
                 T temp2 = temp * rr * rr;
-                if (temp2 <= TNum<T>::tol3z()) {
+                if (temp2 <= num<T>::tol3z()) {
                     T ss = 0;
 #pragma unroll
                     for (int e = 0; e < NEJ; ++e) {
@@ -582,10 +575,10 @@ void qrcp_small(rc_context *c, Mat<T> rin, int64_t kmax, bool pivot, int64_t *jp
         }                                                                                                              \
         hipLaunchKernelGGL(kern, dim3(1), dim3(NT_), lds, c->stream, rin, (int)kmax, pivot ? 1 : 0, jpvt, rout, q2, (T *)nullptr); \
     } while (0)
-    static const int wide = [] { const char *e = getenv("RC_QRCP_SMALL_1024"); return e ? atoi(e) : 1; }();
+    static const int wide = env_int("RC_QRCP_SMALL_1024", 1);
     // workgroups of the separate Q2 launch (0: Q2 stays inside k_qrcp_small).  With fewer than 8 compressions side by side the
     // kernel slots are the bound: Q2's columns are independent and leave the one CU of k_qrcp_small
-    static const int q2_wgs = [] { const char *e = getenv("RC_QRCP_Q2_WGS"); return e ? std::min(std::max(atoi(e), 0), 64) : 8; }();
+    static const int q2_wgs = std::min(std::max(env_int("RC_QRCP_Q2_WGS", 8), 0), 64);
     if (n > 64 && n <= 144 && wide && q2_wgs > 0 && !q2.empty() && c->lanes_in_flight() < 8) {
         ArenaMark mark(c);
         const size_t nt = (size_t)n * (n | 1) + 3 * (size_t)n;
@@ -690,6 +683,11 @@ void householder_sign_fix(rc_context *c, Mat<T> q, Mat<T> r) {
     scale_cols_rows<T>(c, q, r, d);
 }
 
+int tsqr_fold() {
+    static const int fold = env_int("RC_TSQR_FOLD", 1);
+    return fold;
+}
+
 // Pivoted (or plain) QR of the tall-skinny y through CholeskyQR2 + small QRCP + sign fix.
 //   q: m x k column-major (may be empty), r: k x n (may be empty), ind: n
 // Q = Q1 (R2^-1 Q2 D): the n x k factor W = R2^-1 Q2 is formed first, the signs D (+-1: exact) come from the top k x k block
@@ -700,7 +698,7 @@ void qrcp_tall_fast(rc_context *c, Mat<T> y, int64_t k, bool pivot, Mat<T> q, Ma
     const int64_t m = y.rows, n = y.cols;
     ProfScope ps(c, "op:qrcp_tall_fast %lldx%lld k=%lld pivot=%d", (long long)m, (long long)n, (long long)k, pivot ? 1 : 0);
     ArenaMark mark(c);
-    static const int fold = [] { const char *e = getenv("RC_TSQR_FOLD"); return e ? atoi(e) : 1; }();
+    const int fold = tsqr_fold();
     Mat<T> q1 = rowmajor(c->alloc<T>((size_t)m * even_ld(n)), m, n, even_ld(n));
     Mat<T> r1 = colmajor(c->alloc<T>((size_t)n * even_ld(n)), n, n, even_ld(n));
     Mat<T> r2i = rowmajor(c->alloc<T>((size_t)n * even_ld(n)), n, n, even_ld(n));

@@ -4,7 +4,6 @@
 
 namespace rc {
 
-static __host__ __device__ inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // ===========================================================================
 // Philox4x32-10 (Salmon et al., SC'11) -- counter-based, so element e of the

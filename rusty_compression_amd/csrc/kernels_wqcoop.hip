@@ -576,7 +576,7 @@ struct DeviceShare {
 };
 
 int live_processes(int device, DeviceShare &ds) {
-    static const bool enabled = [] { const char *e = getenv("RC_COOP_SHARE"); return !(e && atoi(e) == 0); }();
+    static const int enabled = env_int("RC_COOP_SHARE", 1);
     if (!enabled) return 1;
     const auto now = std::chrono::steady_clock::now();
     if (ds.tried && (ds.tab == nullptr || now - ds.stamp < std::chrono::milliseconds(100))) return ds.live;
@@ -633,8 +633,7 @@ unsigned coop_budget_units(int device) {
     if (!b) {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
-        const char *e = getenv("RC_COOP_BUDGET");  // in CUs (experiments)
-        const int v = e ? atoi(e) : 0;
+        static const int v = env_int("RC_COOP_BUDGET", 0);  // in CUs (experiments)
         b = (unsigned)(v >= 32 && v <= cus ? 2 * v : 2 * cus * 3 / 4);
     }
     const int procs = live_processes(device, share[device & 63]);
@@ -720,7 +719,7 @@ void geqp3_wide_coop(rc_context *c, Mat<T> w, Mat<T> wf, int64_t kmax, int64_t *
     const int64_t m = w.rows, n = w.cols;
     kmax = std::min(kmax, std::min(m, n));
     RC_REQUIRE(wide_coop_supported<T>(m, n, c->device), RC_INVALID_ARGUMENT, "geqp3_wide_coop: unsupported shape");
-    static const int staged = [] { const char *e = getenv("RC_WQ_STAGES"); return e ? atoi(e) : 1; }();
+    static const int staged = env_int("RC_WQ_STAGES", 1);
     int *pos = nullptr;
     T *vn = nullptr;
     int64_t row0 = 0;

@@ -45,13 +45,11 @@ __global__ void k_poison_words(unsigned *p, size_t n, unsigned v) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
 }
 static void poison_fresh(void *p, size_t bytes, hipStream_t st) {
-    static const bool on = [] { const char *e = getenv("RC_DEBUG_POISON_WORKSPACE"); return e && atoi(e) != 0; }();
-    if (!on || !p || bytes < 4) return;
-    static const bool verbose = [] { const char *e = getenv("RC_DEBUG_POISON_WORKSPACE"); return e && atoi(e) > 1; }();
-    if (verbose) fprintf(stderr, "poison %p %zu bytes\n", p, bytes);
-    // 1 (2: verbose): every word 3; 3: every word 0xffffffff (a NaN in f32 and f64, -1 as an index)
-    static const unsigned value = [] { const char *e = getenv("RC_DEBUG_POISON_WORKSPACE"); return e && atoi(e) == 3 ? 0xffffffffu : 3u; }();
-    hipLaunchKernelGGL(k_poison_words, dim3(1024), dim3(256), 0, st, static_cast<unsigned *>(p), bytes / 4, value);
+    // 1 (2 and above: verbose): every word 3; 3: every word 0xffffffff (a NaN in f32 and f64, -1 as an index)
+    static const int level = env_int("RC_DEBUG_POISON_WORKSPACE", 0);
+    if (!level || !p || bytes < 4) return;
+    if (level > 1) fprintf(stderr, "poison %p %zu bytes\n", p, bytes);
+    hipLaunchKernelGGL(k_poison_words, dim3(1024), dim3(256), 0, st, static_cast<unsigned *>(p), bytes / 4, level == 3 ? 0xffffffffu : 3u);
 }
 
 static void reset_active_arena(rc_context *c, hipStream_t st) {
@@ -184,6 +182,20 @@ void rc_context::release_all() {
     sync_ev = nullptr;
 }
 
+// Column-major temporaries.  The lone calls' (tmp_colmajor) have an even pitch, which is all the GEMM's 2-element staging loads ask for.
+// The batch's working copy (tmp_colmajor_pitch4, rc_batch.hip) pads the pitch to a multiple of 4 elements: its columns are then 16-byte
+// aligned at every m, which is what the blocked QRCP's vector loads ask for (BlockedQrcpJob::vec_ok in k_qrb_step_c, k_qrb_vta).
+namespace rc {
+template <typename T>
+Mat<T> tmp_colmajor_pitch4(rc_context *c, int64_t rows, int64_t cols) {
+    int64_t ld = even_ld(std::max<int64_t>(rows, 1));
+    if (ld % 4) ld += 4 - ld % 4;
+    return colmajor(c->alloc<T>((size_t)ld * std::max<int64_t>(cols, 1)), rows, cols, ld);
+}
+template Mat<double> tmp_colmajor_pitch4<double>(rc_context *, int64_t, int64_t);
+template Mat<float> tmp_colmajor_pitch4<float>(rc_context *, int64_t, int64_t);
+}  // namespace rc
+
 namespace {
 
 template <typename T>
@@ -223,7 +235,7 @@ __global__ void k_set_word(int *dst, int v) {
 // is captured), 2 = rc_get_health reads and clears through the null stream (pageable hipMemcpy + hipMemset) again -- the two round-2
 // code paths, switchable one at a time so that tools/rsvd_repeat_diag.py shows which of them delivers the byte patterns.
 static int debug_memset_path() {
-    static const int v = [] { const char *e = getenv("RC_DEBUG_MEMSET_PATH"); return e ? atoi(e) : 0; }();
+    static const int v = env_int("RC_DEBUG_MEMSET_PATH", 0);
     return v;
 }
 
@@ -242,6 +254,25 @@ bool run_certified(rc_context *c, F &&fast) {
     return h == 0;
 }
 
+// Q from a ?geqp3-format factorization goes into q where q is column-major with room for whole columns, otherwise into a column-major
+// temporary that is then copied out: q_target names the matrix to form Q in, q_deliver copies it out if it was the temporary.
+template <typename T>
+Mat<T> q_target(rc_context *c, Mat<T> q) {
+    return q.empty() || (q.rs == 1 && q.cs >= q.rows) ? q : tmp_colmajor<T>(c, q.rows, q.cols);
+}
+template <typename T>
+void q_deliver(rc_context *c, Mat<T> qw, Mat<T> q) {
+    if (qw.p != q.p) copy_mat(c, qw, q);
+}
+// q = H_0 ... H_{k-1} [I ; 0], reflector j in column ind[j] of w
+template <typename T>
+void form_q_into(rc_context *c, Mat<T> w, const int64_t *ind, const T *tau, int64_t k, Mat<T> q) {
+    if (q.empty()) return;
+    Mat<T> qw = q_target(c, q);
+    form_q(c, w, ind, tau, k, qw);
+    q_deliver(c, qw, q);
+}
+
 // Pivoted QR of the column-major working matrix w (destroyed).
 //   q: m x k (may be empty to skip), r: k x n (may be empty), ind: n, k <= min(m, n)
 // Tall-skinny inputs take the CholeskyQR2 + LDS-QRCP + sign-fix path (kernels_tsqr.hip) and
@@ -256,7 +287,7 @@ void qrcp_core(rc_context *c, Mat<T> w, int64_t k, bool pivot, Mat<T> q, Mat<T> 
     if (c->opt_tsqr && k >= 1 && tsqr_supported<T>(w.rows, n)) {
         if (run_certified(c, [&](int *flag) { qrcp_tall_fast<T>(c, w, k, pivot, q, r, ind, flag); })) return;
     }
-    static const int direct_ok = [] { const char *e = getenv("RC_QRCP_KEEP_DIRECT"); return e ? atoi(e) : 1; }();
+    static const int direct_ok = env_int("RC_QRCP_KEEP_DIRECT", 1);
     if (keep_w && !(direct_ok && c->opt_wide_coop && pivot && k >= 1 && wide_coop_supported<T>(w.rows, n, c->device))) {
         Mat<T> cp = tmp_colmajor<T>(c, w.rows, n);
         copy_mat(c, w, cp);
@@ -268,15 +299,7 @@ void qrcp_core(rc_context *c, Mat<T> w, int64_t k, bool pivot, Mat<T> q, Mat<T> 
         Mat<T> wf = tmp_colmajor<T>(c, w.rows, n);
         if (run_certified(c, [&](int *flag) { geqp3_wide_coop<T>(c, w, wf, k, ind, tau, flag); })) {
             if (!r.empty()) extract_r(c, wf, ind, r);
-            if (!q.empty()) {
-                if (q.rs == 1 && q.cs >= q.rows) {
-                    form_q(c, wf, ind, tau, k, q);
-                } else {
-                    Mat<T> qw = tmp_colmajor<T>(c, w.rows, q.cols);
-                    form_q(c, wf, ind, tau, k, qw);
-                    copy_mat(c, qw, q);
-                }
-            }
+            form_q_into(c, wf, ind, tau, k, q);
             return;
         }
     }
@@ -292,25 +315,16 @@ void qrcp_core(rc_context *c, Mat<T> w, int64_t k, bool pivot, Mat<T> q, Mat<T> 
     T *tau = c->alloc<T>((size_t)std::max<int64_t>(k, 1));
     if (c->opt_blocked && pivot && !c->capturing && geqp3_blocked_supported<T>(w.rows, n, k)) {
         // blocked ?laqps panels; Q comes out of the same job (block reflectors with the panels' T factors)
-        const bool direct = !q.empty() && q.rs == 1 && q.cs >= q.rows;
-        Mat<T> qw = q.empty() ? Mat<T>() : (direct ? q : tmp_colmajor<T>(c, w.rows, q.cols));
+        Mat<T> qw = q_target(c, q);
         geqp3_blocked<T>(c, w, k, ind, tau, qw);
         if (!r.empty()) extract_r(c, w, ind, r);
-        if (!q.empty() && !direct) copy_mat(c, qw, q);
+        q_deliver(c, qw, q);
         return;
     }
     T *vn = c->alloc<T>((size_t)std::max<int64_t>(2 * n, 1));
     geqp3_inplace(c, w, k, pivot, ind, tau, vn);
     if (!r.empty()) extract_r(c, w, ind, r);
-    if (!q.empty()) {
-        if (q.rs == 1 && q.cs >= q.rows) {
-            form_q(c, w, ind, tau, k, q);
-        } else {
-            Mat<T> qw = tmp_colmajor<T>(c, w.rows, q.cols);
-            form_q(c, w, ind, tau, k, qw);
-            copy_mat(c, qw, q);
-        }
-    }
+    form_q_into(c, w, ind, tau, k, q);
 }
 
 // PivotedQR::pivoted_qr  (/root/reference/src/pivoted_qr.rs:25-31, :81-119)
@@ -377,18 +391,7 @@ void lapack_orgqr(rc_context *c, Mat<T> a, const T *tau, int64_t k, Mat<T> q) {
         copy_mat(c, w, wc);
         w = wc;
     }
-    if (q.rs == 1 && q.cs >= q.rows) {
-        form_q(c, w, ident, tau, k, q);
-    } else {
-        Mat<T> qw = tmp_colmajor<T>(c, m, k);
-        form_q(c, w, ident, tau, k, qw);
-        copy_mat(c, qw, q);
-    }
-}
-
-static int tsqr_fold() {
-    static const int fold = [] { const char *e = getenv("RC_TSQR_FOLD"); return e ? atoi(e) : 1; }();
-    return fold;
+    form_q_into(c, w, ident, tau, k, q);
 }
 
 // The tail of svd_core: from the SVD of the core (uc, s, vc) and the orthogonal factor of the tall QR -- qw, or q1 r2i when it
@@ -472,7 +475,7 @@ void compute_svd(rc_context *c, Mat<T> a, Mat<T> u, T *s, Mat<T> vt) {
 
 // Z of a column / row ID in one launch (RC_ID_FUSED)
 static int id_fused() {
-    static const int fused = [] { const char *e = getenv("RC_ID_FUSED"); return e ? atoi(e) : 1; }();
+    static const int fused = env_int("RC_ID_FUSED", 1);
     return fused;
 }
 
@@ -832,7 +835,7 @@ namespace rc {
 // qrcp_core and qr_column_id in both.
 template <typename T>
 bool column_id_blocked_route(rc_context *c, int64_t m, int64_t n, int64_t k) {
-    static const bool long_way = [] { const char *e = getenv("RC_COLUMN_ID_FORM_Q"); return e && atoi(e) != 0; }();
+    static const int long_way = env_int("RC_COLUMN_ID_FORM_Q", 0);
     return !long_way && k < n && c->opt_blocked && !c->capturing && geqp3_blocked_supported<T>(m, n, k) &&
            !(c->opt_tsqr && tsqr_supported<T>(m, n)) && !(c->opt_wide_coop && wide_coop_supported<T>(m, n, c->device)) && !(c->opt_wide_lazy && wide_lazy_supported<T>(m, n));
 }

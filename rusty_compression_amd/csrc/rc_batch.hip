@@ -30,25 +30,6 @@ using namespace rc;
 
 namespace {
 
-struct DeviceGuardB {
-    int prev = -1;
-    explicit DeviceGuardB(int dev) {
-        (void)hipGetDevice(&prev);
-        if (prev != dev) (void)hipSetDevice(dev);
-        else prev = -1;
-    }
-    ~DeviceGuardB() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-inline size_t align8(size_t x) { return (x + 7) & ~(size_t)7; }
-
-template <typename T>
-Mat<T> tmp_cm(rc_context *c, int64_t rows, int64_t cols) {
-    int64_t ld = even_ld(std::max<int64_t>(rows, 1));
-    if (ld % 4) ld += 4 - ld % 4;  // 16-byte aligned columns: the blocked QRCP's vector loads
-    return colmajor(c->alloc<T>((size_t)ld * std::max<int64_t>(cols, 1)), rows, cols, ld);
-}
-
 template <typename T>
 void batch_column_id(rc_context *const *ctxs, int nctx, const rc_matrix *mats, int count, int64_t k, void *packed) {
     RC_REQUIRE(nctx >= 1 && count >= 0 && k >= 1, RC_INVALID_ARGUMENT, "batch_column_id: need >= 1 context, k >= 1");
@@ -74,208 +55,153 @@ void batch_column_id(rc_context *const *ctxs, int nctx, const rc_matrix *mats, i
     }
     // the lone call's route (rc_api.hip): the truncated blocked factorization, pipelined below, or the lone call's own routine on the lane
     const bool blocked = column_id_blocked_route<T>(ctxs[0], m, n, k);
-    const size_t per = rc_batch_packed_bytes(m, n, k, (int32_t)sizeof(T));
     struct Lane {
         rc_context *c = nullptr;
         int idx = -1;
         Mat<T> w;
-        T *tau = nullptr;
         int64_t *ind = nullptr;
-        BlockedQrcpJob<T> *job = nullptr;
-        bool active = false;
+        QrbJobPtr<T> job;  // non-null while the lane has a blocked factorization in progress
     };
     std::vector<Lane> lanes((size_t)nctx);
-    struct Cleanup {
-        std::vector<Lane> &l;
+    for (int l = 0; l < nctx; ++l) lanes[(size_t)l].c = ctxs[l];
+    // Every lane is quiescent before the jobs go and before the call returns -- also when it unwinds on an error: any lane may still have
+    // work in flight, and the caller frees `packed` and reuses the arenas afterwards.  The lanes own their jobs, so this depends on the
+    // order of declaration: `quiesce` stands AFTER `lanes` and is therefore destroyed (waits) BEFORE them.
+    struct Quiesce {
         rc_context *const *ctxs;
         int nctx;
-        // every lane is quiescent before the jobs go and before the call returns -- also when it unwinds on an error: any lane
-        // may still have work in flight, and the caller frees `packed` and reuses the arenas afterwards
-        ~Cleanup() {
-            (void)rc_synchronize_all(ctxs, (int32_t)nctx);
-            for (auto &x : l) if (x.job) { qrb_end(x.job); x.job = nullptr; }
-        }
-    } cleanup{lanes, ctxs, nctx};
-    auto slot = [&](int idx) { return static_cast<char *>(packed) + (size_t)idx * per; };
-    // C, Z and ind of a finished blocked factorization into the matrix's slot: read from the factored working copy, no Q (the lone call's tail)
-    auto post = [&](Lane &ln) {
-        char *base = slot(ln.idx);
-        Mat<T> cm = rowmajor(reinterpret_cast<T *>(base), m, k, k);
-        Mat<T> z = rowmajor(reinterpret_cast<T *>(base) + (size_t)m * k, k, n, n);
-        column_id_from_qrcp(ln.c, from_c<T>(mats[ln.idx]), ln.w, k, ln.ind, cm, z);
-        RC_HIP(hipMemcpyAsync(base + align8(((size_t)m * k + (size_t)k * n) * sizeof(T)), ln.ind, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToDevice, ln.c->stream));
-    };
-    // set-up of the next matrix on a lane.  Blocked route: working copy and the job of the blocked factorization (true: the caller
-    // issues its first panel and the lane has something to wait for).  Every other route (tall-skinny, short-wide, k == n, shapes the
-    // panels do not take): the lone call's own routine, whole, on the lane's stream into the slot (false: nothing to wait for)
+        ~Quiesce() { (void)rc_synchronize_all(ctxs, (int32_t)nctx); }
+    } quiesce{ctxs, nctx};
+    // Set-up of matrix idx on a lane.  Blocked route: working copy and the job of the blocked factorization (true: the caller issues its
+    // panels and the lane has something to finish).  Every other route (tall-skinny, short-wide, k == n, shapes the panels do not take):
+    // the lone call's own routine, whole, on the lane's stream into the slot (false: nothing left to do)
     auto start = [&](Lane &ln, int idx) -> bool {
         ln.idx = idx;
-        DeviceGuardB dg(ln.c->device);
+        DeviceGuard dg(ln.c->device);
         ln.c->reset_arena();
-        // (the permutation is built in a lane-owned buffer; it is copied into the packed slot at the end)
-        ln.ind = ln.c->template alloc<int64_t>((size_t)n);
         if (!blocked) {
-            char *base = slot(idx);
-            Mat<T> cm = rowmajor(reinterpret_cast<T *>(base), m, k, k);
-            Mat<T> z = rowmajor(reinterpret_cast<T *>(base) + (size_t)m * k, k, n, n);
-            column_id_rank<T>(ln.c, from_c<T>(mats[idx]), k, cm, z, ln.ind);
-            RC_HIP(hipMemcpyAsync(base + align8(((size_t)m * k + (size_t)k * n) * sizeof(T)), ln.ind, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToDevice, ln.c->stream));
-            ln.active = false;
+            const PackedSlot<T> s = packed_slot<T>(packed, idx, m, n, k);
+            // (the permutation is built in a lane-owned buffer; it is copied into the packed slot at the end)
+            ln.ind = ln.c->template alloc<int64_t>((size_t)n);
+            column_id_rank<T>(ln.c, from_c<T>(mats[idx]), k, s.cm, s.z, ln.ind);
+            RC_HIP(hipMemcpyAsync(s.ind, ln.ind, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToDevice, ln.c->stream));
             return false;
         }
-        ln.w = tmp_cm<T>(ln.c, m, n);
-        ln.tau = ln.c->template alloc<T>((size_t)k);
-        copy_mat(ln.c, from_c<T>(mats[ln.idx]), ln.w);  // the reference's F-order working copy (pivoted_qr.rs:28-29)
-        ln.job = qrb_begin<T>(ln.c, ln.w, k, ln.ind, ln.tau);
-        ln.active = true;
+        ln.w = tmp_colmajor_pitch4<T>(ln.c, m, n);
+        T *tau = ln.c->template alloc<T>((size_t)k);
+        ln.ind = ln.c->template alloc<int64_t>((size_t)n);
+        copy_mat(ln.c, from_c<T>(mats[idx]), ln.w);  // the reference's F-order working copy (pivoted_qr.rs:28-29)
+        ln.job = qrb_begin<T>(ln.c, ln.w, k, ln.ind, tau);
         return true;
     };
-    for (int l = 0; l < nctx; ++l) lanes[(size_t)l].c = ctxs[l];
+    // C, Z and ind of a finished blocked factorization into the matrix's slot: read from the factored working copy, no Q (the lone call's
+    // tail).  The job is done with: the lane is free for its next matrix.
+    auto post = [&](Lane &ln) {
+        const PackedSlot<T> s = packed_slot<T>(packed, ln.idx, m, n, k);
+        column_id_from_qrcp(ln.c, from_c<T>(mats[ln.idx]), ln.w, k, ln.ind, s.cm, s.z);
+        RC_HIP(hipMemcpyAsync(s.ind, ln.ind, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToDevice, ln.c->stream));
+        ln.job.reset();
+    };
     // Optimistic schedule (default where it applies: blocked factorization on cooperative panels, no Q wanted): EVERY matrix is
-    // enqueued in full on its lane -- all panels on their usual outcome (qrb_issue_all_optimistic), then C, Z, ind -- with no host
+    // enqueued in full on its lane -- all panels on their usual outcome (qrb_issue_optimistic), then C, Z, ind -- with no host
     // wait in between; one wait for all lanes at the end, then the per-panel states are checked and the (rare) matrices whose
     // assumptions failed are redone through the per-panel pipeline below.  The lanes' chains then overlap on the GPU without the
     // bubbles of a host round trip per panel.  Measured (8 x 4096^2 f32, k = 64): the host issues the 8 matrices in 0.6 ms and waits 2.05 ms --
     // the batch is bound on the GPU, so this schedule by itself is neutral against the pipeline below (2560 matrices/s either way); with 256
     // instead of 512 candidates per panel both reach 2810-2860.
-    std::vector<int> redo;
-    bool optimistic_done = false;
-    {
-        static const bool opt_on = [] { const char *e = getenv("RC_BATCH_OPTIMISTIC"); return !(e && atoi(e) == 0); }();
-        if (opt_on && blocked) {
-            struct Pending { int idx; const QrbState *log; std::vector<int> nbp; bool broken; };
-            std::vector<Pending> pending;
-            auto flush = [&] {
-                std::vector<rc_context *> all;
-                for (auto &ln : lanes) all.push_back(ln.c);
-                RC_REQUIRE(rc_synchronize_all(all.data(), (int32_t)all.size()) == RC_OK, RC_RUNTIME_ERROR, "batch_column_id: wait failed");
-                for (auto &pd : pending)
-                    if (!qrb_verify_optimistic<T>(pd.log, pd.nbp, pd.broken)) redo.push_back(pd.idx);
-                pending.clear();
-                for (auto &ln : lanes) ln.c->pinned_cursor = 0;
-            };
-            bool possible = true;
-            int flushes = 0;  // waits in the middle of the pass: a lane ran out of pinned state slots
-            static const bool dbg = [] { const char *e = getenv("RC_BATCH_DEBUG"); return e && atoi(e) != 0; }();
-            const auto t_begin = std::chrono::steady_clock::now();
-            for (auto &ln : lanes) ln.c->pinned_cursor = 0;
-            for (int idx = 0; idx < count && possible; ++idx) {
-                Lane &ln = lanes[(size_t)(idx % nctx)];
-                DeviceGuardB dg(ln.c->device);
-                ln.idx = idx;
-                ln.c->reset_arena();
-                ln.w = tmp_cm<T>(ln.c, m, n);
-                ln.tau = ln.c->template alloc<T>((size_t)k);
-                ln.ind = ln.c->template alloc<int64_t>((size_t)n);
-                copy_mat(ln.c, from_c<T>(mats[idx]), ln.w);
-                ln.job = qrb_begin<T>(ln.c, ln.w, k, ln.ind, ln.tau);
-                if (!qrb_optimistic_possible(ln.job)) {
-                    possible = false;
-                } else {
-                    if (!qrb_issue_all_optimistic(ln.job)) {  // no pinned slots left on this lane: wait, check, go on
-                        flush();
-                        ++flushes;
-                        RC_REQUIRE(qrb_issue_all_optimistic(ln.job), RC_RUNTIME_ERROR, "batch_column_id: no pinned state slots");
-                    }
-                    Pending pd;
-                    pd.idx = idx;
-                    qrb_optimistic_log(ln.job, &pd.log, &pd.nbp, &pd.broken);
-                    pending.push_back(std::move(pd));
-                    post(ln);
-                }
-                qrb_end(ln.job);
-                ln.job = nullptr;
-                ln.active = false;
-                if (!possible) {  // (first matrix only in practice: all matrices share one shape) -- everything through the pipeline below
-                    flush();
-                    redo.clear();
-                    for (int i2 = 0; i2 < count; ++i2) redo.push_back(i2);
-                }
+    std::vector<int> todo;  // what is left to do through the per-panel schedule: everything, or the matrices the optimistic pass has to redo
+    auto everything = [&] {
+        todo.clear();
+        for (int i2 = 0; i2 < count; ++i2) todo.push_back(i2);
+    };
+    static const int opt_on = env_int("RC_BATCH_OPTIMISTIC", 1), dbg = env_int("RC_BATCH_DEBUG", 0);
+    if (opt_on && blocked) {
+        struct Pending { int idx; QrbOptimistic o; };
+        std::vector<Pending> pending;
+        // all lanes waited for: check what is pending; the pinned slots are free again
+        auto flush = [&] {
+            RC_REQUIRE(rc_synchronize_all(ctxs, (int32_t)nctx) == RC_OK, RC_RUNTIME_ERROR, "batch_column_id: wait failed");
+            for (auto &pd : pending)
+                if (!pd.o.verified()) todo.push_back(pd.idx);
+            pending.clear();
+            for (auto &ln : lanes) ln.c->reset_pinned_slots();
+        };
+        bool possible = true;
+        int flushes = 0;  // waits in the middle of the pass: a lane ran out of pinned state slots
+        const auto t_begin = std::chrono::steady_clock::now();
+        for (auto &ln : lanes) ln.c->reset_pinned_slots();
+        for (int idx = 0; idx < count && possible; ++idx) {
+            Lane &ln = lanes[(size_t)(idx % nctx)];
+            start(ln, idx);
+            QrbOptimistic o = qrb_issue_optimistic(ln.job.get());
+            if (o.status == QrbOptimistic::NoSlots) {  // no pinned slots left on this lane: wait, check, go on
+                flush();
+                ++flushes;
+                o = qrb_issue_optimistic(ln.job.get());
+                RC_REQUIRE(o.status == QrbOptimistic::Issued, RC_RUNTIME_ERROR, "batch_column_id: no pinned state slots");
             }
-            const auto t_issued = std::chrono::steady_clock::now();
-            if (possible) flush();
-            if (dbg) {
-                const auto t_end = std::chrono::steady_clock::now();
-                std::string which;  // the matrices to redo, by index
-                for (int i2 : redo) which += " " + std::to_string(i2);
-                fprintf(stderr, "rc_batch optimistic: %d matrices issued in %.3f ms, waited %.3f ms, %zu to redo, %d flushes, redo:%s\n", count,
-                        std::chrono::duration<double, std::milli>(t_issued - t_begin).count(), std::chrono::duration<double, std::milli>(t_end - t_issued).count(), redo.size(), flushes,
-                        which.c_str());
+            if (o.status == QrbOptimistic::Issued) {
+                pending.push_back({idx, o});
+                post(ln);
+            } else {  // (first matrix only in practice: all matrices share one shape) -- everything through the pipeline below
+                possible = false;
+                ln.job.reset();
+                flush();
+                everything();
             }
-            optimistic_done = true;
         }
+        const auto t_issued = std::chrono::steady_clock::now();
+        if (possible) flush();
+        if (dbg) {
+            const auto t_end = std::chrono::steady_clock::now();
+            std::string which;  // the matrices to redo, by index
+            for (int i2 : todo) which += " " + std::to_string(i2);
+            fprintf(stderr, "rc_batch optimistic: %d matrices issued in %.3f ms, waited %.3f ms, %zu to redo, %d flushes, redo:%s\n", count,
+                    std::chrono::duration<double, std::milli>(t_issued - t_begin).count(), std::chrono::duration<double, std::milli>(t_end - t_issued).count(), todo.size(), flushes,
+                    which.c_str());
+        }
+    } else {
+        everything();
     }
-    // what is left to do through the per-panel schedules: everything, or the matrices the optimistic pass has to redo
-    std::vector<int> todo;
-    if (optimistic_done) todo = redo;
-    else for (int i2 = 0; i2 < count; ++i2) todo.push_back(i2);
-    count = (int)todo.size();
-    auto mat_of = [&](int t) { return todo[(size_t)t]; };
     // Pipeline: every lane carries an event behind its panel; the host serves the lanes in the order their panels were
     // issued (first in, first out): wait for that lane only, enqueue its panel-end kernels and its next panel (or its C, Z,
     // ind and the set-up of the lane's next matrix), go on to the next lane.  The lanes drift apart by the host time of one
     // lane's launches, so the host-bound phases of some matrices (dozens of small launches) run while the latency-bound
     // cooperative panels of the others occupy the GPU, instead of everything waiting for the slowest panel of a round.
-    auto mark = [&](Lane &ln) {
+    // (All lanes are on ctxs[0]'s device, which the entry point's guard has made current.)
+    auto issue = [&](Lane &ln) {
         rc_context *c = ln.c;
+        qrb_issue(ln.job.get());
         if (!c->sync_ev) RC_HIP(hipEventCreateWithFlags(&c->sync_ev, hipEventDisableTiming));
         RC_HIP(hipEventRecord(c->sync_ev, c->stream));
     };
-    int next = 0;
+    size_t next = 0;
     std::deque<int> fifo;
     for (;;) {
-        for (int l = 0; l < nctx && next < count; ++l) {  // idle lanes take the next matrices
+        for (int l = 0; l < nctx && next < todo.size(); ++l) {  // idle lanes take the next matrices
             Lane &ln = lanes[(size_t)l];
-            if (ln.active) continue;
-            if (start(ln, mat_of(next++))) {
-                DeviceGuardB dg(ln.c->device);
-                qrb_issue(ln.job);
-                mark(ln);
+            if (ln.job) continue;
+            if (start(ln, todo[next++])) {
+                issue(ln);
                 fifo.push_back(l);
             }
         }
         if (fifo.empty()) {
-            if (next >= count) break;
+            if (next >= todo.size()) break;
             continue;
         }
         const int l = fifo.front();
         Lane &ln = lanes[(size_t)l];
         fifo.pop_front();
-        DeviceGuardB dg(ln.c->device);
         RC_HIP(hipEventSynchronize(ln.c->sync_ev));
-        if (qrb_finish(ln.job)) {
-            ln.active = false;  // (the lane is handed its next matrix at the top of the loop)
-            post(ln);
-            qrb_end(ln.job);
-            ln.job = nullptr;
+        if (qrb_finish(ln.job.get())) {
+            post(ln);  // (the lane is handed its next matrix at the top of the loop)
         } else {
-            qrb_issue(ln.job);
-            mark(ln);
+            issue(ln);
             fifo.push_back(l);
         }
     }
-    std::vector<rc_context *> all(ctxs, ctxs + nctx);
-    RC_REQUIRE(rc_synchronize_all(all.data(), (int32_t)all.size()) == RC_OK, RC_RUNTIME_ERROR, "batch_column_id: wait failed");
-    for (rc_context *c : all) {
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) fail(RC_RUNTIME_ERROR, "kernel launch failed: %s", hipGetErrorString(e));
-        (void)c;
-    }
-}
-
-template <typename F>
-rc_status guarded_b(rc_context *ctx, F &&f) {
-    if (!ctx) return RC_INVALID_ARGUMENT;
-    try {
-        f();
-        return RC_OK;
-    } catch (const Error &e) {
-        ctx->last_error = e.msg;
-        return e.code;
-    } catch (const std::exception &e) {
-        ctx->last_error = e.what();
-        return RC_RUNTIME_ERROR;
-    }
+    RC_REQUIRE(rc_synchronize_all(ctxs, (int32_t)nctx) == RC_OK, RC_RUNTIME_ERROR, "batch_column_id: wait failed");
 }
 
 // ---------------------------------------------------------------- RCCL, opened at run time
@@ -334,7 +260,8 @@ extern "C" {
 
 size_t rc_batch_packed_bytes(int64_t m, int64_t n, int64_t k, int32_t elem_size) {
     if (m < 0 || n < 0 || k < 0 || elem_size <= 0) return 0;
-    return align8(((size_t)m * (size_t)k + (size_t)k * (size_t)n) * (size_t)elem_size) + (size_t)n * 8;
+    const size_t cz = ((size_t)m * (size_t)k + (size_t)k * (size_t)n) * (size_t)elem_size;  // C and Z; the indices follow 8-byte aligned
+    return ((cz + 7) & ~(size_t)7) + (size_t)n * 8;
 }
 
 rc_status rc_batch_shard_range(int64_t n_items, int32_t world, int32_t rank, int64_t *start, int64_t *count) {
@@ -347,11 +274,11 @@ rc_status rc_batch_shard_range(int64_t n_items, int32_t world, int32_t rank, int
 
 rc_status rc_batch_column_id_f64(rc_context *const *ctxs, int32_t nctx, const rc_matrix *mats, int32_t count, int64_t k, void *packed) {
     if (!ctxs || nctx < 1 || !ctxs[0]) return RC_INVALID_ARGUMENT;
-    return guarded_b(ctxs[0], [&] { batch_column_id<double>(ctxs, nctx, mats, count, k, packed); });
+    return guarded(ctxs[0], [&] { batch_column_id<double>(ctxs, nctx, mats, count, k, packed); });
 }
 rc_status rc_batch_column_id_f32(rc_context *const *ctxs, int32_t nctx, const rc_matrix *mats, int32_t count, int64_t k, void *packed) {
     if (!ctxs || nctx < 1 || !ctxs[0]) return RC_INVALID_ARGUMENT;
-    return guarded_b(ctxs[0], [&] { batch_column_id<float>(ctxs, nctx, mats, count, k, packed); });
+    return guarded(ctxs[0], [&] { batch_column_id<float>(ctxs, nctx, mats, count, k, packed); });
 }
 
 rc_status rc_comm_unique_id(void *id128) {
@@ -371,7 +298,7 @@ rc_status rc_comm_init(rc_comm **comm, int32_t world, int32_t rank, const void *
     if (world < 1 || rank < 0 || rank >= world || !id128) return RC_INVALID_ARGUMENT;
     Rccl *r = rccl();
     if (!r->error.empty()) return RC_RUNTIME_ERROR;
-    DeviceGuardB dg(device);
+    DeviceGuard dg(device);
     ncclUniqueId id;
     std::memcpy(&id, id128, sizeof(id));
     rc_comm *c = new rc_comm();
@@ -398,7 +325,7 @@ rc_status rc_comm_gather(rc_comm *comm, rc_context *ctx, const void *send, void 
         return RC_INVALID_ARGUMENT;
     }
     Rccl *r = rccl();
-    DeviceGuardB dg(comm->device);
+    DeviceGuard dg(comm->device);
     auto chk = [&](ncclResult_t e) {
         if (e == ncclSuccess) return true;
         comm->last_error = r->GetErrorString ? r->GetErrorString(e) : "RCCL error";
@@ -451,7 +378,7 @@ rc_status rc_comm_all_gather(rc_comm *comm, rc_context *ctx, const void *send, v
     if (!comm || !ctx) return RC_INVALID_ARGUMENT;
     if (bytes_per_rank == 0) return RC_OK;
     if (!send || !recv) return RC_INVALID_ARGUMENT;
-    DeviceGuardB dg(comm->device);
+    DeviceGuard dg(comm->device);
     char *own = static_cast<char *>(recv) + (size_t)comm->rank * bytes_per_rank;
     if (comm->world == 1 && !comm->comm) {  // (an RCCL communicator of one rank still goes through ncclAllGather)
         if (own != send && !comm_hip(comm, ctx, hipMemcpyAsync(own, send, bytes_per_rank, hipMemcpyDeviceToDevice, ctx->stream), "all_gather copy")) return RC_RUNTIME_ERROR;
@@ -482,7 +409,7 @@ rc_status rc_comm_all_reduce_sum(rc_comm *comm, rc_context *ctx, void *buf, size
     if (!comm || !ctx || (elem_size != 4 && elem_size != 8)) return RC_INVALID_ARGUMENT;
     if (count == 0 || (comm->world == 1 && !comm->comm)) return RC_OK;
     if (!buf) return RC_INVALID_ARGUMENT;
-    DeviceGuardB dg(comm->device);
+    DeviceGuard dg(comm->device);
     const size_t bytes = count * (size_t)elem_size;
     if (comm->host_reduce) {
         comm->stage_in.resize(bytes);
@@ -506,7 +433,7 @@ rc_status rc_comm_all_reduce_sum(rc_comm *comm, rc_context *ctx, void *buf, size
 rc_status rc_comm_destroy(rc_comm *comm) {
     if (!comm) return RC_OK;
     Rccl *r = rccl();
-    DeviceGuardB dg(comm->device);
+    DeviceGuard dg(comm->device);
     if (comm->comm && r->CommDestroy) (void)r->CommDestroy(comm->comm);
     delete comm;
     return RC_OK;

@@ -9,7 +9,9 @@
 #include <cstdio>
 #include <cstring>
 #include <exception>
+#include <cstdlib>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -43,6 +45,13 @@ inline Mat<T> from_c(const rc_matrix &m) {
 // leading dimensions of internal temporaries are kept even so the GEMM can stage them with
 // 2-element vector loads
 inline int64_t even_ld(int64_t x) { return (x + 1) & ~int64_t(1); }
+__host__ __device__ inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// An integer switch of the process environment ("Environment switches", lists them all).  Every site reads its switch once per
+// process -- `static const int x = env_int("RC_...", d);` -- so no hot path calls getenv and a switch cannot change under a running process.
+inline int env_int(const char *name, int dflt) {
+    const char *e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
 // freshly allocated column-major / row-major views
 template <typename T>
 inline Mat<T> colmajor(T *p, int64_t rows, int64_t cols, int64_t ld) { return Mat<T>(p, rows, cols, 1, ld); }
@@ -115,6 +124,7 @@ struct rc_context {
     void *pinned = nullptr;             // small pinned host buffer for scalar read-backs
     size_t pinned_size = 0;
     int pinned_cursor = 0;              // next free QrbState slot of `pinned` for optimistic blocked-QRCP jobs (kernels_qrblk.hip)
+    void reset_pinned_slots() { pinned_cursor = 0; }  // once nothing issued on this context still writes to a slot
 
     // Tall-skinny factorizations: 1 = CholeskyQR2 fast path with certificate + Householder
     // fallback (default), 0 = always the Householder chain.  `health` is a device word the
@@ -297,22 +307,46 @@ template <typename T> bool geqp3_blocked_supported(int64_t m, int64_t n, int64_t
 // restore_from (optional, only without q_out): the matrix w is a copy of -- enables the optimistic issue (all panels enqueued on the
 // usual outcome, one wait, a check; on a failed check w is restored from it and the per-panel path runs)
 template <typename T> void geqp3_blocked(rc_context *c, Mat<T> w, int64_t kmax, int64_t *jpvt, T *tau, Mat<T> q_out, Mat<T> restore_from = Mat<T>());
-// the same factorization as a resumable job (one host wait per panel): begin -> { issue, <stream synchronised>, finish } ... -> end
+// the same factorization as a resumable job (one host wait per panel): begin -> { issue, <stream synchronised>, finish } ...; the
+// handle owns the job (its buffers are the context's arena: no reset while the job is alive)
 template <typename T> struct BlockedQrcpJob;
-template <typename T> BlockedQrcpJob<T> *qrb_begin(rc_context *c, Mat<T> w, int64_t kmax, int64_t *jpvt, T *tau);
+template <typename T> struct QrbJobDelete { void operator()(BlockedQrcpJob<T> *job) const; };
+template <typename T> using QrbJobPtr = std::unique_ptr<BlockedQrcpJob<T>, QrbJobDelete<T>>;
+template <typename T> QrbJobPtr<T> qrb_begin(rc_context *c, Mat<T> w, int64_t kmax, int64_t *jpvt, T *tau);
 template <typename T> void qrb_issue(BlockedQrcpJob<T> *job);
 template <typename T> bool qrb_finish(BlockedQrcpJob<T> *job);
-template <typename T> void qrb_end(BlockedQrcpJob<T> *job);
-struct QrbState;
-template <typename T> bool qrb_optimistic_possible(BlockedQrcpJob<T> *job);
-template <typename T> bool qrb_issue_all_optimistic(BlockedQrcpJob<T> *job);   // false: no pinned slots left on the context (wait, check what is pending, reset c->pinned_cursor)
-template <typename T> bool qrb_verify_optimistic(BlockedQrcpJob<T> *job);
-template <typename T> bool qrb_verify_optimistic(const QrbState *host_log, const std::vector<int> &nbp_log, bool broken);
-template <typename T> void qrb_optimistic_log(BlockedQrcpJob<T> *job, const QrbState **log, std::vector<int> *nbp_log, bool *broken);
+// Optimistic issue of a fresh job: all panels enqueued on the usual outcome, no wait.  What comes back is a value that outlives the job
+// (the log lies in the context's pinned buffer): once the stream has been waited for, verified() says whether every assumption held.
+constexpr int kQrbOptMaxPanels = 16;
+struct QrbOptimistic {
+    enum Status { NotPossible, NoSlots, Issued } status = NotPossible;  // NoSlots: wait, check what is pending, reset_pinned_slots(), call again
+    const struct QrbState *log = nullptr;  // panel p's state (kernels_qrblk.hip), pinned
+    int panels = 0;                        // panels issued
+    int nbp[kQrbOptMaxPanels] = {};        // the steps panel p was assumed to make
+    bool broken = false;                   // a panel could not be issued as assumed: nothing behind it ran
+    bool verified() const;
+};
+template <typename T> QrbOptimistic qrb_issue_optimistic(BlockedQrcpJob<T> *job);
 // the lone rank-k column ID (rc_column_id_rank_*, rc_api.hip) and whether it reads the ID from the truncated blocked factorization
 // (true) or goes through qrcp_core and qr_column_id; rc_batch_column_id_* runs the same routes
 template <typename T> bool column_id_blocked_route(rc_context *c, int64_t m, int64_t n, int64_t k);
 template <typename T> void column_id_rank(rc_context *c, Mat<T> a, int64_t k, Mat<T> cm, Mat<T> z, int64_t *col_ind);
+// the batch's column-major working copy of an m x n matrix (rc_api.hip, beside tmp_colmajor, which says why their pitches differ)
+template <typename T> Mat<T> tmp_colmajor_pitch4(rc_context *c, int64_t rows, int64_t cols);
+// Slot `idx` of the packed buffer of rc_batch_column_id_* (E: the element type, real or complex): C (m x k) and Z (k x n) row-major, then
+// the n indices at the slot's end.  rc_batch_packed_bytes is the definition of the size, and with it of where the indices begin.
+template <typename E>
+struct PackedSlot {
+    Mat<E> cm, z;
+    int64_t *ind;
+};
+template <typename E>
+inline PackedSlot<E> packed_slot(void *packed, int idx, int64_t m, int64_t n, int64_t k) {
+    const size_t per = rc_batch_packed_bytes(m, n, k, (int32_t)sizeof(E));
+    char *base = static_cast<char *>(packed) + (size_t)idx * per;
+    E *e = reinterpret_cast<E *>(base);
+    return {Mat<E>(e, m, k, k, 1), Mat<E>(e + (size_t)m * k, k, n, n, 1), reinterpret_cast<int64_t *>(base + per - (size_t)n * sizeof(int64_t))};
+}
 // short-wide matrices (m <= 256 << n): read-only "lazy" pivoted QR with the explicit m x m factor
 template <typename T> bool wide_lazy_supported(int64_t m, int64_t n);
 template <typename T> void geqp3_wide_lazy(rc_context *c, Mat<T> b, int64_t kmax, int64_t *jpvt, Mat<T> q, Mat<T> r);
@@ -341,6 +375,7 @@ template <typename T> void form_q(rc_context *c, Mat<T> w, const int64_t *jpvt, 
 template <typename T> void trsm_upper(rc_context *c, Mat<T> t, Mat<T> b);
 // tall-skinny fast path (kernels_tsqr.hip): CholeskyQR2 + LDS-resident QRCP + Householder sign fix
 template <typename T> bool tsqr_supported(int64_t m, int64_t n);
+int tsqr_fold();  // RC_TSQR_FOLD: Q of the CholeskyQR2 stays factored (Q1 R2^-1); one read (kernels_tsqr.hip) for its callers there and in rc_api.hip, which must agree
 template <typename T> void tsqr_cholqr2(rc_context *c, Mat<T> y, Mat<T> q, Mat<T> r, int *flag);
 template <typename T> void tsqr_cholqr2_factored(rc_context *c, Mat<T> y, Mat<T> q1, Mat<T> r2i, Mat<T> r, int *flag);
 template <typename T> void qrcp_small(rc_context *c, Mat<T> rin, int64_t kmax, bool pivot, int64_t *jpvt, Mat<T> rout, Mat<T> q2);

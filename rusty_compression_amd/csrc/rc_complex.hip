@@ -29,12 +29,6 @@ using namespace rc;
 
 namespace {
 
-static inline int64_t cdivi(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-template <typename R> struct NumC;
-template <> struct NumC<double> { static __host__ __device__ double tol3z() { return 1.0536712127723509e-08; } static __host__ __device__ double eps() { return 1.1102230246251565e-16; } };
-template <> struct NumC<float> { static __host__ __device__ float tol3z() { return 2.44140625e-04f; } static __host__ __device__ float eps() { return 5.9604645e-08f; } };
-
 // the column-major working matrix (cplx<R>, CV<R> and view_of: rc_cplx.hpp); every temporary of this family has this layout, Omega too
 template <typename E>
 Mat<E> tmp_colmajor(rc_context *c, int64_t rows, int64_t cols) {
@@ -62,7 +56,7 @@ template <typename R>
 void copy_mat(rc_context *c, CV<R> src, CV<R> dst, bool conj = false) {
     RC_REQUIRE(src.rows == dst.rows && src.cols == dst.cols, RC_INVALID_ARGUMENT, "complex copy: shape mismatch");
     if (dst.empty()) return;
-    hipLaunchKernelGGL(k_c_copy<R>, dim3((unsigned)std::min<int64_t>(cdivi(dst.rows * dst.cols, 256), 8192)), dim3(256), 0, c->stream, src, dst, conj ? 1 : 0);
+    hipLaunchKernelGGL(k_c_copy<R>, dim3((unsigned)std::min<int64_t>(cdiv(dst.rows * dst.cols, 256), 8192)), dim3(256), 0, c->stream, src, dst, conj ? 1 : 0);
 }
 template <typename R>
 __global__ __launch_bounds__(256) void k_c_fill(CV<R> dst, int identity) {
@@ -75,7 +69,7 @@ __global__ __launch_bounds__(256) void k_c_fill(CV<R> dst, int identity) {
 template <typename R>
 void c_fill(rc_context *c, CV<R> dst, bool identity) {
     if (dst.empty()) return;
-    hipLaunchKernelGGL(k_c_fill<R>, dim3((unsigned)std::min<int64_t>(cdivi(dst.rows * dst.cols, 256), 8192)), dim3(256), 0, c->stream, dst, identity ? 1 : 0);
+    hipLaunchKernelGGL(k_c_fill<R>, dim3((unsigned)std::min<int64_t>(cdiv(dst.rows * dst.cols, 256), 8192)), dim3(256), 0, c->stream, dst, identity ? 1 : 0);
 }
 template <typename R>
 __global__ __launch_bounds__(256) void k_c_gather_cols(CV<R> src, const int64_t *idx, CV<R> dst, int *health) {  // dst[:, j] = src[:, idx[j]]
@@ -94,7 +88,7 @@ __global__ __launch_bounds__(256) void k_c_gather_cols(CV<R> src, const int64_t 
 template <typename R>
 void gather_cols(rc_context *c, CV<R> src, const int64_t *idx, CV<R> dst) {
     if (dst.empty()) return;
-    hipLaunchKernelGGL(k_c_gather_cols<R>, dim3((unsigned)std::min<int64_t>(cdivi(dst.rows * dst.cols, 256), 8192)), dim3(256), 0, c->stream, src, idx, dst, c->health_word());
+    hipLaunchKernelGGL(k_c_gather_cols<R>, dim3((unsigned)std::min<int64_t>(cdiv(dst.rows * dst.cols, 256), 8192)), dim3(256), 0, c->stream, src, idx, dst, c->health_word());
 }
 template <typename R>
 __global__ __launch_bounds__(256) void k_c_scale_rows(const R *s, CV<R> m) {  // m[i, :] *= s[i]
@@ -182,12 +176,12 @@ void c_gemm(rc_context *c, int opa, int opb, cplx<R> alpha, CV<R> a, CV<R> b, cp
     if (k == 0) {  // empty inner dimension: C = beta C
         fill_words(c, cr, (size_t)ldc * n * sizeof(R), 0u);
         fill_words(c, ci, (size_t)ldc * n * sizeof(R), 0u);
-        hipLaunchKernelGGL(k_c_combine<R>, dim3((unsigned)std::min<int64_t>(cdivi(m * n, 256), 8192)), dim3(256), 0, c->stream, cr, ci, ldc, alpha, beta, cm);
+        hipLaunchKernelGGL(k_c_combine<R>, dim3((unsigned)std::min<int64_t>(cdiv(m * n, 256), 8192)), dim3(256), 0, c->stream, cr, ci, ldc, alpha, beta, cm);
         return;
     }
     if (k > 0) {
-        hipLaunchKernelGGL(k_c_split<R>, dim3((unsigned)std::min<int64_t>(cdivi(m * k, 256), 8192)), dim3(256), 0, c->stream, a, ar, ai, lda);
-        hipLaunchKernelGGL(k_c_split<R>, dim3((unsigned)std::min<int64_t>(cdivi(k * n, 256), 8192)), dim3(256), 0, c->stream, b, br, bi, ldb);
+        hipLaunchKernelGGL(k_c_split<R>, dim3((unsigned)std::min<int64_t>(cdiv(m * k, 256), 8192)), dim3(256), 0, c->stream, a, ar, ai, lda);
+        hipLaunchKernelGGL(k_c_split<R>, dim3((unsigned)std::min<int64_t>(cdiv(k * n, 256), 8192)), dim3(256), 0, c->stream, b, br, bi, ldb);
     }
     Mat<R> Ar = colmajor(ar, m, k, lda), Ai = colmajor(ai, m, k, lda), Br = colmajor(br, k, n, ldb), Bi = colmajor(bi, k, n, ldb);
     Mat<R> Cr = colmajor(cr, m, n, ldc), Ci = colmajor(ci, m, n, ldc);
@@ -196,7 +190,7 @@ void c_gemm(rc_context *c, int opa, int opb, cplx<R> alpha, CV<R> a, CV<R> b, cp
     gemm<R>(c, -(sa * sb), Ai, Bi, (R)1, Cr);
     gemm<R>(c, sb, Ar, Bi, (R)0, Ci);
     gemm<R>(c, sa, Ai, Br, (R)1, Ci);
-    hipLaunchKernelGGL(k_c_combine<R>, dim3((unsigned)std::min<int64_t>(cdivi(m * n, 256), 8192)), dim3(256), 0, c->stream, cr, ci, ldc, alpha, beta, cm);
+    hipLaunchKernelGGL(k_c_combine<R>, dim3((unsigned)std::min<int64_t>(cdiv(m * n, 256), 8192)), dim3(256), 0, c->stream, cr, ci, ldc, alpha, beta, cm);
 }
 template <typename R> cplx<R> one() { return cplx<R>{(R)1, (R)0}; }
 template <typename R> cplx<R> zero() { return cplx<R>{(R)0, (R)0}; }
@@ -295,7 +289,7 @@ __global__ __launch_bounds__(256) void k_c_qr_apply(CV<R> w, int64_t j, int pivo
     R temp = (R)1 - t * t;
     temp = temp > (R)0 ? temp : (R)0;
     const R r = vn / vn2[p];
-    if (temp * r * r <= NumC<R>::tol3z()) {
+    if (temp * r * r <= num<R>::tol3z()) {
         R ss = 0;
         for (int64_t i = j + 1 + tid; i < m; i += 256) ss += abs2(x[i]);
         ss = wave_sum_dpp(ss);
@@ -326,7 +320,7 @@ void c_geqp3(rc_context *c, CV<R> w, int64_t kmax, int64_t *jpvt, cplx<R> *tau) 
     ProfScope ps(c, "op:geqp3<complex> %lldx%lld k=%lld", (long long)m, (long long)n, (long long)kmax);
     ArenaMark mark(c);
     R *vn1 = c->alloc<R>((size_t)n), *vn2 = c->alloc<R>((size_t)n);
-    hipLaunchKernelGGL(k_c_qr_init<R>, dim3((unsigned)std::min<int64_t>(cdivi(n, 4), 8192)), dim3(256), 0, c->stream, w, jpvt, vn1, vn2);
+    hipLaunchKernelGGL(k_c_qr_init<R>, dim3((unsigned)std::min<int64_t>(cdiv(n, 4), 8192)), dim3(256), 0, c->stream, w, jpvt, vn1, vn2);
     for (int64_t j = 0; j < kmax; ++j) {
         hipLaunchKernelGGL(k_c_qr_pivot_reflect<R>, dim3(1), dim3(1024), 0, c->stream, w, j, 1, jpvt, vn1, vn2, tau);
         if (n - j - 1 > 0) hipLaunchKernelGGL(k_c_qr_apply<R>, dim3((unsigned)(n - j - 1)), dim3(256), 0, c->stream, w, j, 1, jpvt, vn1, vn2, tau);
@@ -399,7 +393,7 @@ void c_pivoted_qr(rc_context *c, CV<R> a, CV<R> q, CV<R> r, int64_t *ind, int64_
     c_geqp3(c, w, k, ind, tau);
     if (!r.empty()) {
         CV<R> rw = tmp_colmajor<cplx<R>>(c, r.rows, n);
-        hipLaunchKernelGGL(k_c_extract_r<R>, dim3((unsigned)std::min<int64_t>(cdivi(r.rows * n, 256), 8192)), dim3(256), 0, c->stream, w, ind, rw);
+        hipLaunchKernelGGL(k_c_extract_r<R>, dim3((unsigned)std::min<int64_t>(cdiv(r.rows * n, 256), 8192)), dim3(256), 0, c->stream, w, ind, rw);
         copy_mat(c, rw, r);
     }
     if (!q.empty()) {
@@ -471,7 +465,7 @@ __global__ __launch_bounds__(256) void k_c_jacobi_round(CV<R> g, CV<R> v, int r,
     apq.re = wave_sum_dpp(apq.re);
     apq.im = wave_sum_dpp(apq.im);
     const R habs = hypot(apq.re, apq.im);
-    const R tol = sqrt((R)M) * NumC<R>::eps();
+    const R tol = sqrt((R)M) * num<R>::eps();
     if (habs == (R)0 || habs <= tol * sqrt(app) * sqrt(aqq)) return;
     // q~ = e^{-i phi} q makes p^H q~ = |apq| real: a real Jacobi rotation between p and q~.
     // The phase and the rotation parameters are evaluated in f64 for both precisions (as in the real kernels): in f32,
@@ -719,7 +713,7 @@ void c_qr_column_id(rc_context *c, CV<R> q, CV<R> r, const int64_t *ind, CV<R> c
         copy_mat(c, r.sub(0, k, k, n - k), zt.sub(0, k, k, n - k));
         CV<R> r11 = tmp_colmajor<cplx<R>>(c, k, k);
         copy_mat(c, r.sub(0, k, 0, k), r11);
-        hipLaunchKernelGGL(k_c_trsm_upper<R>, dim3((unsigned)cdivi(n - k, 256)), dim3(256), 0, c->stream, r11, zt.sub(0, k, k, n - k));
+        hipLaunchKernelGGL(k_c_trsm_upper<R>, dim3((unsigned)cdiv(n - k, 256)), dim3(256), 0, c->stream, r11, zt.sub(0, k, k, n - k));
         c_gemm(c, 0, 0, one<R>(), q, r11, zero<R>(), cm);
     }
     CV<R> zo = tmp_colmajor<cplx<R>>(c, k, n);
@@ -764,7 +758,7 @@ void max_col_norm_dev(rc_context *c, CV<R> y, R *out_dev) {
     CV<R> w = tmp_colmajor<cplx<R>>(c, y.rows, y.cols);
     copy_mat(c, y, w);
     R *ss = c->alloc<R>((size_t)std::max<int64_t>(y.cols, 1));
-    hipLaunchKernelGGL(k_c_col_sumsq<R>, dim3((unsigned)std::min<int64_t>(cdivi(std::max<int64_t>(y.cols, 1), 4), 8192)), dim3(256), 0, c->stream, w, ss);
+    hipLaunchKernelGGL(k_c_col_sumsq<R>, dim3((unsigned)std::min<int64_t>(cdiv(std::max<int64_t>(y.cols, 1), 4), 8192)), dim3(256), 0, c->stream, w, ss);
     max_sqrt<R>(c, ss, y.cols, out_dev);
 }
 
@@ -840,7 +834,6 @@ void c_batch_column_id(rc_context *const *ctxs, int nctx, const rc_matrix *mats,
     RC_REQUIRE(mats != nullptr && packed != nullptr, RC_INVALID_ARGUMENT, "batch_column_id: null argument");
     const int64_t m = mats[0].rows, n = mats[0].cols;
     RC_REQUIRE(k <= std::min(m, n), RC_INVALID_ARGUMENT, "batch_column_id: rank exceeds min(m, n)");
-    const size_t per = rc_batch_packed_bytes(m, n, k, (int32_t)sizeof(cplx<R>));
     // everything is checked before the first launch (no option selects between complex factorizations: the device is all the lanes must share)
     for (int i = 0; i < count; ++i)
         RC_REQUIRE(mats[i].rows == m && mats[i].cols == n && mats[i].data, RC_INVALID_ARGUMENT, "batch_column_id: all matrices must have the shape of the first");
@@ -851,16 +844,13 @@ void c_batch_column_id(rc_context *const *ctxs, int nctx, const rc_matrix *mats,
     }
     for (int i = 0; i < count; ++i) {
         rc_context *c = ctxs[i % nctx];
-        char *base = static_cast<char *>(packed) + (size_t)i * per;
-        cplx<R> *cz = reinterpret_cast<cplx<R> *>(base);
-        int64_t *ind = reinterpret_cast<int64_t *>(base + per - (size_t)n * sizeof(int64_t));
+        const PackedSlot<cplx<R>> s = packed_slot<cplx<R>>(packed, i, m, n, k);  // (the permutation is written straight into the slot)
         CV<R> A = view_of<R>(mats[i]);
-        CV<R> cm{cz, m, k, k, 1}, z{cz + (size_t)m * k, k, n, n, 1};
         c->reset_arena();
         ArenaMark mark(c);
         CV<R> q = tmp_colmajor<cplx<R>>(c, m, k), r = tmp_colmajor<cplx<R>>(c, k, n);
-        c_pivoted_qr<R>(c, A, q, r, ind, k);
-        c_qr_column_id<R>(c, q, r, ind, cm, z);
+        c_pivoted_qr<R>(c, A, q, r, s.ind, k);
+        c_qr_column_id<R>(c, q, r, s.ind, s.cm, s.z);
     }
     for (int l = 0; l < std::min(nctx, count); ++l) RC_HIP(hipStreamSynchronize(ctxs[l]->stream));
 }
@@ -915,7 +905,7 @@ extern "C" {
             CV<R> tt = view_of<R>(t), bb = view_of<R>(b);                                                                                 \
             RC_REQUIRE(tt.rows == tt.cols && tt.rows == bb.rows, RC_INVALID_ARGUMENT, "trsm_upper: t must be k x k, b k x nrhs");        \
             if (bb.empty()) return;                                                                                                       \
-            hipLaunchKernelGGL(k_c_trsm_upper<R>, dim3((unsigned)cdivi(bb.cols, 256)), dim3(256), 0, ctx->stream, tt, bb);                \
+            hipLaunchKernelGGL(k_c_trsm_upper<R>, dim3((unsigned)cdiv(bb.cols, 256)), dim3(256), 0, ctx->stream, tt, bb);                \
         });                                                                                                                               \
     }                                                                                                                                     \
     rc_status rc_pivoted_lq_##SUF(rc_context *ctx, rc_matrix a, rc_matrix l, rc_matrix q, int64_t *ind) {                                 \
@@ -955,7 +945,7 @@ extern "C" {
             CV<R> VT = view_of<R>(vt);                                                                                                    \
             CV<R> sv = tmp_colmajor<cplx<R>>(ctx, VT.rows, VT.cols);                                                                      \
             copy_mat<R>(ctx, VT, sv);                                                                                                     \
-            if (!sv.empty()) hipLaunchKernelGGL(k_c_scale_rows<R>, dim3((unsigned)std::min<int64_t>(cdivi(sv.rows * sv.cols, 256), 8192)), dim3(256), 0, ctx->stream, s, sv); \
+            if (!sv.empty()) hipLaunchKernelGGL(k_c_scale_rows<R>, dim3((unsigned)std::min<int64_t>(cdiv(sv.rows * sv.cols, 256), 8192)), dim3(256), 0, ctx->stream, s, sv); \
             c_gemm<R>(ctx, 0, 0, one<R>(), view_of<R>(u), sv, zero<R>(), view_of<R>(out));                                                \
         });                                                                                                                               \
     }                                                                                                                                     \
@@ -966,7 +956,7 @@ extern "C" {
             RC_REQUIRE(k <= std::min(VT.rows, VT.cols), RC_INVALID_ARGUMENT, "svd_to_qr: rank exceeds min(r, n)");                        \
             CV<R> w = tmp_colmajor<cplx<R>>(ctx, VT.rows, VT.cols), qb = tmp_colmajor<cplx<R>>(ctx, VT.rows, k);                          \
             copy_mat<R>(ctx, VT, w);                                                                                                      \
-            if (!w.empty()) hipLaunchKernelGGL(k_c_scale_rows<R>, dim3((unsigned)std::min<int64_t>(cdivi(w.rows * w.cols, 256), 8192)), dim3(256), 0, ctx->stream, s, w); \
+            if (!w.empty()) hipLaunchKernelGGL(k_c_scale_rows<R>, dim3((unsigned)std::min<int64_t>(cdiv(w.rows * w.cols, 256), 8192)), dim3(256), 0, ctx->stream, s, w); \
             c_pivoted_qr<R>(ctx, w, qb, view_of<R>(r), ind, k);                                                                           \
             c_gemm<R>(ctx, 0, 0, one<R>(), view_of<R>(u), qb, zero<R>(), Q);                                                              \
         });                                                                                                                               \

@@ -123,13 +123,20 @@ __device__ inline double fast_rsqrt(double x) {
 }
 __device__ inline float fast_rsqrt(float x) { return 1.0f / sqrtf(x); }
 
+// ---- the constants of the number formats: eps = the unit roundoff (LAPACK's ?lamch('E')), tol3z = sqrt(eps) ----
+template <typename T> struct num;
+template <> struct num<double> {
+    static __host__ __device__ constexpr double eps() { return 1.1102230246251565e-16; }    // 2^-53
+    static __host__ __device__ constexpr double tol3z() { return 1.0536712127723509e-08; }  // sqrt(2^-53)
+};
+template <> struct num<float> {
+    static __host__ __device__ constexpr float eps() { return 5.9604644775390625e-08f; }  // 2^-24
+    static __host__ __device__ constexpr float tol3z() { return 2.44140625e-04f; }        // sqrt(2^-24)
+};
+
 // ---- ?laqp2 partial-norm down-date ---------------------------------------------------
-// tol3z = sqrt(eps): below it the down-dated norm has lost its digits and is recomputed from the column.  The same constants and
-// the same formula as the down-date of the per-step chain (kernels_qr.hip, k_qr_apply), which keeps its own copy so that its
-// instantiations stay as they were.
-template <typename T> __host__ __device__ constexpr T laqp2_tol3z();
-template <> __host__ __device__ constexpr double laqp2_tol3z<double>() { return 1.0536712127723509e-08; }  // sqrt(2^-53)
-template <> __host__ __device__ constexpr float laqp2_tol3z<float>() { return 2.44140625e-04f; }          // sqrt(2^-24)
+// tol3z: below it the down-dated norm has lost its digits and is recomputed from the column.  The same formula as the down-date of
+// the per-step chain (kernels_qr.hip, k_qr_apply), which keeps its own copy so that its instantiations stay as they were.
 // vn: partial norm of the column before the step (vn1), vn_ref: its norm at the last recompute (vn2), xj: its new row-j entry.
 // Returns true when the norm must be recomputed from rows j+1.. of the updated column; otherwise *vn_new is the down-dated norm.
 template <typename T>
@@ -139,15 +146,12 @@ __device__ inline bool laqp2_downdate(T vn, T vn_ref, T xj, T *vn_new) {
     temp = temp > (T)0 ? temp : (T)0;
     T r = vn / vn_ref;
     T temp2 = temp * r * r;
-    if (temp2 <= laqp2_tol3z<T>()) return true;
+    if (temp2 <= num<T>::tol3z()) return true;
     *vn_new = vn * sqrt(temp);
     return false;
 }
 
 // ---- one-sided (Hestenes) Jacobi: shared by the lone core (kernels_svd.hip) and the batched SVD (kernels_batched_id.hip) ----
-template <typename T> struct JEps;
-template <> struct JEps<double> { static __device__ inline double eps() { return 1.1102230246251565e-16; } };
-template <> struct JEps<float> { static __device__ inline float eps() { return 5.9604644775390625e-08f; } };
 
 // circle-method pairing: round r of N-1 (N even), pair slot pi of N/2
 __device__ inline void rr_pair(int N, int r, int pi, int &p, int &q) {

@@ -1387,7 +1387,7 @@ print("DIGESTS " + " ".join(out))
 
 def test_optimistic_blocked_qrcp_equals_the_panel_by_panel_schedule_bit_for_bit():
     """Round 3: the truncated blocked QRCP enqueues all its panels on their usual outcome and checks the panels' states once
-    (kernels_qrblk.hip, qrb_issue_all_optimistic); a failed check restores the working matrix and runs panel by panel.  Both outcomes
+    (kernels_qrblk.hip, qrb_issue_optimistic); a failed check restores the working matrix and runs panel by panel.  Both outcomes
     -- check holds (Gaussian), check fails (decaying spectrum: the tau test ends panels early) -- and the batch schedule built on it
     must give the bits of the per-panel schedule (RC_QRCP_OPTIMISTIC=0, RC_BATCH_OPTIMISTIC=0)."""
     import os
