@@ -877,6 +877,102 @@ BatchedColumnID<T> column_id_rank_power_batched(const DeviceMatrix<T> &a, const 
     ctx.synchronize();  // u, the last omega, is released on return
     return out;
 }
+// the sketch omega a_i of `count` m x n blocks stacked in `a` and nothing else (rc_sketch_product_batched_f64 / _f32, real scalars only), for
+// blocks of up to 65536 columns: count * l x n, with the bits of the sketch the two calls above form (see the C header).  The _view form takes
+// block 0 of every operand as a view with its batch stride, so that the projection p = a q^T is the same call on transposed views.
+template <typename T> struct SketchProductApi;
+template <> struct SketchProductApi<double> {
+    static constexpr auto product = rc_sketch_product_batched_f64;
+    static constexpr auto recompress_tall = rc_lowrank_recompress_tall_batched_f64;
+};
+template <> struct SketchProductApi<float> {
+    static constexpr auto product = rc_sketch_product_batched_f32;
+    static constexpr auto recompress_tall = rc_lowrank_recompress_tall_batched_f32;
+};
+template <typename T>
+void sketch_product_batched_view(const Context &ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega, int64_t omega_batch_stride, int32_t count,
+                                 rc_matrix y, int64_t y_batch_stride) {
+    ctx.check(SketchProductApi<T>::product(ctx.raw(), a, a_batch_stride, omega, omega_batch_stride, count, y, y_batch_stride));
+}
+template <typename T>
+DeviceMatrix<T> sketch_product_batched(const DeviceMatrix<T> &a, const DeviceMatrix<T> &omega, int32_t count) {
+    const Context &ctx = a.ctx();
+    const int64_t m = count > 0 ? a.nrows() / count : 0, n = a.ncols(), l = omega.nrows();
+    DeviceMatrix<T> y(ctx, (int64_t)count * l, n);
+    sketch_product_batched_view<T>(ctx, rc_matrix{a.view().data, m, n, n, 1}, m * n, omega.view(), 0, count, rc_matrix{y.view().data, l, n, n, 1}, l * n);
+    return y;
+}
+// the l x l identity on the device (the `right` of an orthonormalising tall recompression)
+template <typename T>
+DeviceMatrix<T> device_identity(const Context &ctx, int64_t l) {
+    std::vector<T> heye((std::size_t)(l * l), (T)0);
+    for (int64_t i = 0; i < l; ++i) heye[(std::size_t)(i * l + i)] = (T)1;
+    return DeviceMatrix<T>::from_host(ctx, heye.data(), l, l);
+}
+// range_step_batched for blocks of any width (m, n <= 65536, l <= min(128, m, n); real scalars): n <= 512 is range_step_batched_view; above
+// it three launches: the sketch by sketch_product_batched, its row basis by rc_lowrank_recompress_tall_batched_* on the transposed view of the
+// sketch with right = I, k = l, tol = 0 (u written through the transposed view of q, the ranks that call's), and p = a q^T by the product on
+// transposed views.  The mirror owns the sketch, so it waits once before it releases it.  `identity`, when given, is the l x l identity of a
+// caller that makes several steps (else one is made here).
+template <typename T>
+BatchedRangeStep<T> range_step_large_batched_view(const DeviceMatrix<T> &a, rc_matrix omega, int64_t omega_batch_stride, int32_t count,
+                                                  const DeviceMatrix<T> *identity = nullptr) {
+    const Context &ctx = a.ctx();
+    const int64_t m = count > 0 ? a.nrows() / count : 0, n = a.ncols(), l = omega.rows;
+    if (n <= 512) return range_step_batched_view<T>(a, omega, omega_batch_stride, count);
+    BatchedRangeStep<T> out{DeviceMatrix<T>(ctx, (int64_t)count * l, n), DeviceMatrix<T>(ctx, (int64_t)count * m, l), DeviceIndex(ctx, (std::size_t)count)};
+    DeviceMatrix<T> y(ctx, (int64_t)count * l, n), vt(ctx, (int64_t)count * l, l);
+    DeviceBuffer<T> s(ctx, (std::size_t)count * (std::size_t)l);
+    DeviceMatrix<T> own;
+    if (!identity) own = device_identity<T>(ctx, l);
+    const DeviceMatrix<T> &eye = identity ? *identity : own;
+    const rc_matrix av{a.view().data, m, n, n, 1}, none{nullptr, 0, 0, 0, 0};
+    sketch_product_batched_view<T>(ctx, av, m * n, omega, omega_batch_stride, count, rc_matrix{y.view().data, l, n, n, 1}, l * n);
+    ctx.check(SketchProductApi<T>::recompress_tall(ctx.raw(), rc_matrix{y.view().data, n, l, 1, n}, l * n, none, 0, nullptr, 0,
+                                                   rc_matrix{eye.view().data, l, l, l, 1}, 0, nullptr, count, l, 0.0, rc_matrix{out.q.view().data, n, l, 1, n}, l * n,
+                                                   s.data(), rc_matrix{vt.view().data, l, l, l, 1}, l * l, out.ranks.data()));
+    sketch_product_batched_view<T>(ctx, rc_matrix{a.view().data, n, m, 1, n}, m * n, rc_matrix{out.q.view().data, l, n, n, 1}, l * n, count,
+                                   rc_matrix{out.p.view().data, l, m, 1, l}, m * l);
+    ctx.synchronize();  // y, vt, s and eye are released on return
+    return out;
+}
+template <typename T>
+BatchedRangeStep<T> range_step_large_batched(const DeviceMatrix<T> &a, const DeviceMatrix<T> &omega, int32_t count) {
+    return range_step_large_batched_view<T>(a, omega.view(), 0, count);
+}
+// batched randomized SVDs of blocks of any width with `steps` >= 1 range steps on the shared test matrix omega (l x m): per step
+// range_step_large_batched; between steps p orthonormalised by the tall recompression with right = I at the step's ranks, whose u^T (a
+// strided view) is the next, per-block, omega; then recompress_large_batched(p, q, ranks, k, tol).  n <= 512 takes the same calls with the
+// one-launch range step, as the Python sketch_svd_rank_power_batched does.
+template <typename T>
+BatchedSVD<T> svd_rank_large_batched(const DeviceMatrix<T> &a, const DeviceMatrix<T> &omega, int32_t count, int64_t k, double tol = 0.0, int steps = 1) {
+    const Context &ctx = a.ctx();
+    if (steps < 1) throw std::invalid_argument("svd_rank_large_batched: steps must be >= 1 (the one-pass column ID route needs n <= 512)");
+    const int64_t m = count > 0 ? a.nrows() / count : 0, l = omega.nrows();
+    const DeviceMatrix<T> eye = device_identity<T>(ctx, l);
+    DeviceMatrix<T> u;  // the orthonormalised p of the step before, whose transposed view is the next omega (none before the first step)
+    rc_matrix om = omega.view();
+    int64_t obs = 0;
+    for (int it = 0;; ++it) {
+        const BatchedRangeStep<T> step = range_step_large_batched_view<T>(a, om, obs, count, &eye);
+        if (it + 1 == steps) {
+            BatchedSVD<T> out = recompress_large_batched(step.p, nullptr, nullptr, step.q, &step.ranks, count, k, tol);
+            ctx.synchronize();  // step's buffers and u, the last omega, are released on return
+            return out;
+        }
+        DeviceMatrix<T> un(ctx, (int64_t)count * m, l), vt(ctx, (int64_t)count * l, l);
+        DeviceBuffer<T> s(ctx, (std::size_t)count * (std::size_t)l);
+        DeviceIndex uranks(ctx, (std::size_t)count);
+        ctx.check(SketchProductApi<T>::recompress_tall(ctx.raw(), rc_matrix{step.p.view().data, m, l, l, 1}, m * l, rc_matrix{nullptr, 0, 0, 0, 0}, 0, nullptr, 0,
+                                                       rc_matrix{eye.view().data, l, l, l, 1}, 0, step.ranks.data(), count, l, 0.0,
+                                                       rc_matrix{un.view().data, m, l, l, 1}, m * l, s.data(), rc_matrix{vt.view().data, l, l, l, 1}, l * l,
+                                                       uranks.data()));
+        ctx.synchronize();  // step's buffers, vt, s and the previous u are released here
+        u = std::move(un);
+        om = rc_matrix{u.view().data, l, m, 1, l};
+        obs = m * l;
+    }
+}
 // a batched column ID, a batched two-sided ID as truncated SVDs, each block from its own rank
 template <typename T>
 BatchedSVD<T> recompress_batched(const BatchedColumnID<T> &id, int64_t k, double tol = 0.0) {

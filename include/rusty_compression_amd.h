@@ -766,6 +766,29 @@ rc_status rc_sketch_column_id_rank_batched_f32(rc_context *ctx, rc_matrix a, int
  * loads left and right times exact powers of two (u is unchanged and s carries 2^e when p does). */
 rc_status rc_sketch_range_step_batched_f64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega, int64_t omega_batch_stride, int32_t count, rc_matrix y, int64_t y_batch_stride, rc_matrix q, int64_t q_batch_stride, rc_matrix p, int64_t p_batch_stride, int64_t *ranks);
 rc_status rc_sketch_range_step_batched_f32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega, int64_t omega_batch_stride, int32_t count, rc_matrix y, int64_t y_batch_stride, rc_matrix q, int64_t q_batch_stride, rc_matrix p, int64_t p_batch_stride, int64_t *ranks);
+/* The sketch alone, for blocks of any width: per block Y_i = omega_i a_i (l x n) and nothing else, in one stream-ordered, capturable call.
+ * This is the product the two calls above form inside their launch, without the factorization that bounds their n by what one workgroup
+ * holds: the front end of a randomized SVD of wide or large square blocks (rc_lowrank_recompress_large_batched_* is its back end), and, on
+ * transposed views, its projection.
+ * a is m x n, omega is l x m, y is l x n.  The batch layout is rc_sketch_column_id_rank_batched_*'s: block i of every operand is its view
+ * moved by i times its batch stride; any row and column strides on every view; batch stride 0 is legal for a and omega (one omega shared by
+ * all blocks, the usual case); every pointer a device pointer.  The output must not overlap the inputs.
+ * Bits: an element of Y_i is rc_sketch_column_id_rank_batched_*'s chain exactly: v_mfma_f64_16x16x4_f64 / v_mfma_f32_16x16x4_f32 (exact
+ * f32) over ascending rows of a, from zero, in chunks of 32 rows, four rows per instruction.  So
+ *   (i)  for n <= 512, y equals the y of rc_sketch_column_id_rank_batched_* (and of rc_sketch_range_step_batched_*) bit for bit;
+ *   (ii) for any n, column j of y depends on column j of a, on omega and on m alone: not on n, on which 64-column panel or work unit holds
+ *        the column, on the grid, on count, the position in the batch, the neighbours, any stride, or graph replay against an eager call.
+ * From (i) and transposed views one call computes P = a Q^T: pass a' = a^T (n x m, the strides swapped), omega' = Q (l x n) and
+ * y' = p^T (l x m, a transposed view of the m x l output).  For n <= 512 that p equals rc_sketch_range_step_batched_*'s p bit for bit,
+ * given the same q.  Non-finite input stays inside its block, and inside the columns of y whose columns of a hold it when omega is finite.
+ * Work is split over (block, 64-column panel) units on a persistent grid, so a few large blocks fill the chip; nothing is split along m and
+ * nothing is added by atomics.
+ * Domain: 1 <= m, n <= 65536, 1 <= l <= 128, count >= 0 (0: nothing to do).  RC_INVALID_ARGUMENT for an argument outside the domain,
+ * omega.cols != a.rows, a wrong y shape, a y batch stride smaller than one view's span when count > 1, a null a, omega or y with count > 0,
+ * or a null ctx (rejected before a device is touched).  No host synchronisation, no workspace.  Real scalars only:
+ * rc_sketch_product_batched_c64 / _c32 do not exist. */
+rc_status rc_sketch_product_batched_f64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega, int64_t omega_batch_stride, int32_t count, rc_matrix y, int64_t y_batch_stride);
+rc_status rc_sketch_product_batched_f32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega, int64_t omega_batch_stride, int32_t count, rc_matrix y, int64_t y_batch_stride);
 /* The complex twin of rc_sketch_column_id_rank_batched_*: the one-pass randomized column ID of every complex tall block of a batch, in one
  * stream-ordered, capturable call: the sketch Y_i = omega_i a_i (l x n) of each block a_i (m x n) is formed while a_i streams through the chip once,
  * and the column ID of the small Y_i gives the pivots and Z; C is gathered from a_i.  Nothing is conjugated: a caller who wants Q^H a passes

@@ -15,6 +15,7 @@ from .batch import (column_id_to_svd_batched_complex, lowrank_recompress_batched
                     two_sided_id_to_svd_batched_complex)
 from .batch import column_id_to_svd_tall_batched, lowrank_recompress_tall_batched, sketch_svd_rank_batched, svd_add_tall_batched  # noqa: F401
 from .batch import lowrank_recompress_large_batched, svd_add_large_batched  # noqa: F401
+from .batch import sketch_product_batched, sketch_range_step_large_batched, sketch_svd_rank_large_batched  # noqa: F401
 from .batch import (column_id_to_svd_tall_batched_complex, lowrank_recompress_tall_batched_complex, sketch_svd_rank_batched_complex,  # noqa: F401
                     svd_add_tall_batched_complex)
 from .batch import sketch_column_id_rank_batched  # noqa: F401
@@ -55,5 +56,6 @@ __all__ = [
     "sketch_range_step_batched", "sketch_power_omega_batched", "sketch_column_id_rank_power_batched", "sketch_svd_rank_power_batched",
     "sketch_range_step_batched_complex", "sketch_power_omega_batched_complex", "sketch_column_id_rank_power_batched_complex",
     "sketch_svd_rank_power_batched_complex",
+    "sketch_product_batched", "sketch_range_step_large_batched", "sketch_svd_rank_large_batched",
     "lowrank_apply_batched_mixed", "block_operator_apply_mixed", "demote_batched", "promote_batched", "MixedBlockLowRankOperator",
 ]

@@ -913,6 +913,16 @@ def svd_residual_batched_complex(a: torch.Tensor, u: torch.Tensor, s: torch.Tens
     return lowrank_residual_batched_complex(a, u, vt, s=s, ranks=ranks, want_residual=want_residual)
 
 
+def _default_omega(a, k, oversampling, seed, who):
+    """The shared Gaussian omega every sketched call draws when none is given: l = min(k + oversampling, 128) rows (at least one) of
+    rc_random_gaussian_* at (seed, offset 0), in a's dtype."""
+    from .random_matrix import Rng, random_gaussian
+
+    if k is None:
+        raise AssertionError(f"{who}: k is needed to draw the default omega")
+    return random_gaussian((max(min(int(k) + int(oversampling), 128), 1), a.shape[-2]), Rng(int(seed)), a.dtype)
+
+
 def _sketch_column_id_rank_batched(who: str, complex_data: bool, a, k, tol, omega, oversampling, seed, return_sketch: bool):
     """The body of sketch_column_id_rank_batched and sketch_column_id_rank_batched_complex: the checks, the default omega and the call."""
     from . import _lib
@@ -927,9 +937,7 @@ def _sketch_column_id_rank_batched(who: str, complex_data: bool, a, k, tol, omeg
     a = a.resolve_conj()  # a lazily conjugated complex view is materialised: the kernels read the stored values
     count, m, n = a.shape
     if omega is None:
-        from .random_matrix import Rng, random_gaussian
-
-        omega = random_gaussian((max(min(int(k) + int(oversampling), 128), 1), m), Rng(int(seed)), a.dtype)
+        omega = _default_omega(a, k, oversampling, seed, who)
     omega = as_device(omega)
     if omega.dtype != a.dtype:
         raise TypeError(f"{who}: omega is {omega.dtype}, a is {a.dtype}")
@@ -1021,11 +1029,7 @@ def _sketch_range_step_batched(who: str, complex_data: bool, a, omega, oversampl
     a = a.resolve_conj()  # a lazily conjugated complex view is materialised: the kernels read the stored values
     count, m, n = a.shape
     if omega is None:
-        from .random_matrix import Rng, random_gaussian
-
-        if k is None:
-            raise AssertionError(f"{who}: k is needed to draw the default omega")
-        omega = random_gaussian((max(min(int(k) + int(oversampling), 128), 1), m), Rng(int(seed)), a.dtype)
+        omega = _default_omega(a, k, oversampling, seed, who)
     omega = as_device(omega)
     if omega.dtype != a.dtype:
         raise TypeError(f"{who}: omega is {omega.dtype}, a is {a.dtype}")
@@ -1072,9 +1076,7 @@ def _sketch_power_omega_batched(who: str, complex_data: bool, a, k, power_iterat
     if int(power_iterations) < 0:
         raise AssertionError(f"{who}: power_iterations must be >= 0")
     if omega is None:
-        from .random_matrix import Rng, random_gaussian
-
-        omega = random_gaussian((max(min(int(k) + int(oversampling), 128), 1), a.shape[-2]), Rng(int(seed)), a.dtype)
+        omega = _default_omega(a, k, oversampling, seed, who)
     for _ in range(int(power_iterations)):
         omega = _power_iteration_batched(complex_data, a, omega, k, oversampling, seed)
     return omega
@@ -1150,6 +1152,117 @@ def sketch_svd_rank_power_batched(a: torch.Tensor, k: int, tol: float = 0.0, pow
     power_iterations = 0 delegates to sketch_svd_rank_batched on the same arguments.  2 q launches, no host synchronisation.  Complex data
     raises TypeError."""
     return _sketch_svd_rank_power_batched("sketch_svd_rank_power_batched", False, a, k, tol, power_iterations, omega, oversampling, seed)
+
+
+def sketch_product_batched(a: torch.Tensor, omega: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The sketch Y = omega a of every block of a batch and nothing else, in one stream-ordered call (rc_sketch_product_batched_*): the
+    product sketch_column_id_rank_batched and sketch_range_step_batched form inside their launch, for blocks of any width.
+
+    a: [count, m, n] device tensor of float64 or float32, any strides (m, n <= 65536; a stride-0 batch dimension shares one block).
+    omega: [l, m] (shared by the batch) or [count, l, m], l <= 128, a's dtype, any strides.  out: None, or a [count, l, n] device tensor
+    of a's dtype that receives Y (any strides, for instance the transposed view of a [count, n, l] tensor; it must not overlap a or
+    omega).  Returns Y [count, l, n] (out when given).  An element of Y is one MFMA accumulator chain from zero over ascending rows of
+    a: for n <= 512 Y is sketch_column_id_rank_batched(..., return_sketch=True)'s bit for bit, and for any n a column of Y depends on
+    that column of a, on omega and on m alone.  P = a Q^T is the call on transposed views: sketch_product_batched(a.mT, q, out=p.mT).
+    Complex data and mismatched dtypes raise TypeError."""
+    from . import _lib
+    from .types import as_device
+
+    who = "sketch_product_batched"
+    _require_dtype(who, False, a)
+    a, omega = as_device(a), as_device(omega)
+    if omega.dtype != a.dtype:
+        raise TypeError(f"{who}: omega is {omega.dtype}, a is {a.dtype}")
+    if a.dim() != 3:
+        raise AssertionError("expected a [count, m, n] batch")
+    if omega.dim() not in (2, 3) or (omega.dim() == 3 and omega.shape[0] != a.shape[0]):
+        raise AssertionError("expected omega [l, m] or [count, l, m]")
+    count, m, n = a.shape
+    l = omega.shape[-2]
+    obs = omega.stride(0) if omega.dim() == 3 else 0
+    if out is None:
+        out = torch.empty((count, l, n), dtype=a.dtype, device=a.device)
+    else:
+        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != a.dtype:
+            raise TypeError(f"{who}: out must be a device tensor of a's dtype {a.dtype}")
+        if tuple(out.shape) != (count, l, n):
+            raise AssertionError(f"{who}: out must be [{count}, {l}, {n}], got {list(out.shape)}")
+    _lib.default_context().call("rc_sketch_product_batched_" + _lib.suffix(a.dtype),
+                                _lib.rc_matrix(a.data_ptr(), m, n, a.stride(1), a.stride(2)), ctypes.c_int64(a.stride(0)),
+                                _lib.rc_matrix(omega.data_ptr(), l, omega.shape[-1], omega.stride(-2), omega.stride(-1)), ctypes.c_int64(obs),
+                                ctypes.c_int32(count), _lib.rc_matrix(out.data_ptr(), l, n, out.stride(1), out.stride(2)),
+                                ctypes.c_int64(out.stride(0)))
+    return out
+
+
+_SMALL_N = 512  # the widest block the one-launch range step and sketched ID take
+
+
+def sketch_range_step_large_batched(a: torch.Tensor, omega: Optional[torch.Tensor] = None, oversampling: int = 8, k: Optional[int] = None,
+                                    seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """sketch_range_step_batched for blocks of any width (m, n <= 65536, l <= min(128, m, n)): Q [count, l, n] with orthonormal rows
+    spanning the rows of Y = omega a, P = a Q^T [count, m, l] and the ranks [count]; rows of Q and columns of P from a block's rank on
+    are exactly zero.  a, omega, oversampling, k and seed as sketch_range_step_batched.
+
+    n <= 512 returns sketch_range_step_batched's outputs by calling it.  Above that, three launches with nothing on the host between them:
+    Y = sketch_product_batched(a, omega); the row basis by lowrank_recompress_tall_batched(Y^T, I, k=l, tol=0), whose U^T (a strided
+    view) is Q and whose ranks are the step's (a singular value that is exactly zero ends the rank, where the one-launch step tests the
+    diagonal of R); and P by sketch_product_batched(a^T, Q) into P^T.  Complex data raises TypeError."""
+    who = "sketch_range_step_large_batched"
+    _require_dtype(who, False, a)
+    if a.dim() != 3:
+        raise AssertionError("expected a [count, m, n] batch")
+    if a.shape[2] <= _SMALL_N:
+        return sketch_range_step_batched(a, omega, oversampling, k, seed)
+    from .types import as_device
+
+    a = as_device(a)
+    if omega is None:
+        omega = _default_omega(a, k, oversampling, seed, who)
+    omega = as_device(omega)
+    count, m, n = a.shape
+    l = omega.shape[-2]
+    if l > min(128, m, n):
+        raise AssertionError(f"{who}: needs 1 <= l <= min(128, m, n) (got a {m} x {n}, omega {l} x {omega.shape[-1]})")
+    y = sketch_product_batched(a, omega)
+    eye = torch.eye(l, dtype=a.dtype, device=a.device).expand(count, l, l)
+    u, _, _, ranks = lowrank_recompress_tall_batched(y.mT, eye, l, 0.0)
+    q = u.mT
+    p = torch.empty((count, m, l), dtype=a.dtype, device=a.device)
+    sketch_product_batched(a.mT, q, out=p.mT)
+    return q, p, ranks
+
+
+def sketch_svd_rank_large_batched(a: torch.Tensor, k: int, tol: float = 0.0, power_iterations: int = 1, omega: Optional[torch.Tensor] = None,
+                                  oversampling: int = 8, seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Batched randomized SVDs of blocks of any width (m, n <= 65536): sketch_svd_rank_power_batched's chain with
+    sketch_range_step_large_batched as the step and lowrank_recompress_large_batched at the end.  power_iterations counts range steps as
+    sketch_svd_rank_power_batched counts them and must be >= 1: between steps P is orthonormalised by lowrank_recompress_tall_batched(p, I,
+    k=l, tol=0, ranks=the step's ranks), whose U^T is the next omega; after the last step lowrank_recompress_large_batched(p, q, k, tol,
+    ranks=ranks) gives (U [count, m, kk], S [count, l], Vt [count, kk, n], ranks), kk = min(k, l).  n <= 512 returns
+    sketch_svd_rank_power_batched's result by calling it.  3 q + (q - 1) + 1 launches above that, no host synchronisation.  Complex data
+    raises TypeError."""
+    who = "sketch_svd_rank_large_batched"
+    _require_dtype(who, False, a)
+    if int(power_iterations) < 1:
+        raise AssertionError(f"{who}: power_iterations must be >= 1: without a range step the SVD goes through the one-pass column ID, which needs "
+                             f"n <= {_SMALL_N} (sketch_svd_rank_batched)")
+    if a.dim() != 3:
+        raise AssertionError("expected a [count, m, n] batch")
+    if a.shape[2] <= _SMALL_N:
+        return sketch_svd_rank_power_batched(a, k, tol, power_iterations, omega, oversampling, seed)
+    from .types import as_device
+
+    a = as_device(a)
+    if omega is None:
+        omega = _default_omega(a, k, oversampling, seed, who)
+    for step in range(int(power_iterations)):
+        q, p, ranks = sketch_range_step_large_batched(a, omega)
+        if step + 1 < int(power_iterations):
+            l = p.shape[2]
+            eye = torch.eye(l, dtype=p.dtype, device=p.device).expand(p.shape[0], l, l)
+            omega = lowrank_recompress_tall_batched(p, eye, l, 0.0, ranks=ranks)[0].mT
+    return lowrank_recompress_large_batched(p, q, k, tol, ranks=ranks)
 
 
 def sketch_range_step_batched_complex(a: torch.Tensor, omega: Optional[torch.Tensor] = None, oversampling: int = 8, k: Optional[int] = None,

@@ -955,6 +955,122 @@ __global__ __launch_bounds__(BID_THREADS, 2) void k_batched_sketch_id(BsiArgs<T>
     }
 }
 
+// ---- batched sketch product (rc_sketch_product_batched_*) ----------------------------------------------------------------------------
+// Per block Y = Omega A and nothing else, for n up to 65536: bsi_sketch's panel (BSI_COLS columns of Y, all TL row tiles in the wave's
+// accumulators, A and Omega through LDS in chunks of BSI_ROWS rows, the same images, the same zero padding, the same MFMA sequence from
+// zero over ascending rows of A), so an element of Y has bsi_sketch's bits and column j of Y depends on column j of A, on Omega and on m
+// alone.  What differs is around the chain: a work unit of the persistent grid is one (block, panel) pair, units = count * ceil(n / 64), so
+// a few large blocks fill the chip; and the kernel carries no QR state, so chunk i + 1 of A and Omega is loaded into registers before the
+// MFMAs of chunk i and stored to LDS after them.  Nothing is split along m; no workspace, no atomics.
+// dynamic LDS: A chunk [BSI_A_ELEMS] Omega chunk [bsi_o_elems(l)]
+template <typename T>
+struct BspArgs {
+    Mat<T> a, omega, y;
+    int64_t abs, obs, ybs;
+    int64_t units;  // count * panels
+    int panels;     // ceil(n / BSI_COLS)
+};
+
+// every unit of this workgroup for TL = ceil(l / 16) row tiles; AR / OR as in bsi_sketch.  All in-block offsets are 64-bit: m * n reaches 2^32.
+template <typename T, int TL, bool AR, bool OR>
+__device__ __forceinline__ void bsp_units(const BspArgs<T> &g, T *As, T *Os, int wv) {
+    // the thread index from the wave's number (uniform, a scalar register) and the lane's count under a mask behind an empty asm: the
+    // per-thread staging offsets are then this instance's own, and no vector register stays live across the dispatch (threadIdx.x in v0 was
+    // spilled there: the one f64 instance that fills all 256 registers had 8 bytes of scratch)
+    unsigned all = ~0u;
+    asm volatile("" : "+s"(all));
+    const int lane = (int)__builtin_amdgcn_mbcnt_hi(all, __builtin_amdgcn_mbcnt_lo(all, 0u));
+    const int tid = wv * 64 + lane;
+    constexpr int PO = bsi_po(16 * TL);
+    constexpr int A_PER = BSI_ROWS * BSI_COLS / BID_THREADS;    // 8 elements of A per thread and chunk
+    constexpr int O_PER = BSI_ROWS * 16 * TL / BID_THREADS;     // 2 TL elements of Omega
+    constexpr int A_SR = AR ? 1 : BSI_PA, A_SC = AR ? BSI_PK : 1;   // A's image: As[r * A_SR + c * A_SC]
+    constexpr int O_SI = OR ? 1 : BSI_PK, O_SR = OR ? PO : 1;       // Omega's image: Os[i * O_SI + r * O_SR]
+    const int m = (int)g.a.rows, n = (int)g.a.cols, l = (int)g.omega.rows;
+    const int64_t ars = g.a.rs, acs = g.a.cs, ors = g.omega.rs, ocs = g.omega.cs;
+    const int ar = AR ? (tid & (BSI_ROWS - 1)) : (tid / BSI_COLS), ac = AR ? (tid / BSI_ROWS) : (tid & (BSI_COLS - 1));
+    constexpr int AR_STEP = AR ? 0 : BID_THREADS / BSI_COLS, AC_STEP = AR ? BID_THREADS / BSI_ROWS : 0;
+    const int oi = OR ? (tid & 15) : (tid / BSI_ROWS), orr = OR ? (tid >> 4) : (tid & (BSI_ROWS - 1));
+    const int r16 = lane & 15, k4 = lane >> 4;
+    T *as_st = As + ar * A_SR + ac * A_SC, *os_st = Os + oi * O_SI + orr * O_SR;
+    const T *as_ld = As + k4 * A_SR + (wv * 16 + r16) * A_SC, *os_ld = Os + r16 * O_SI + k4 * O_SR;
+    for (int64_t u = blockIdx.x; u < g.units; u += gridDim.x) {
+        const int64_t b = u / g.panels;
+        const int c0 = (int)(u - b * g.panels) * BSI_COLS;
+        const T *__restrict__ A = g.a.p + b * g.abs;
+        const T *__restrict__ Om = g.omega.p + b * g.obs;
+        T *Yb = g.y.p + b * g.ybs;
+        T av[A_PER], ov[O_PER];
+        // this thread's elements of the chunk at row m0 (bsi_sketch's, with its uniform steps behind an empty asm), zeros past m, n and l
+        auto load = [&](int m0) {
+            const T *pa = A + (int64_t)(m0 + ar) * ars + (int64_t)(c0 + ac) * acs;
+            const T *po = Om + (int64_t)oi * ors + (int64_t)(m0 + orr) * ocs;
+            int64_t sa = AR ? AC_STEP * acs : AR_STEP * ars, so_i = ors, so_r = ocs;
+            asm volatile("" : "+s"(sa), "+s"(so_i), "+s"(so_r));
+#pragma unroll
+            for (int e = 0; e < A_PER; ++e) {
+                const bool ok = m0 + ar + AR_STEP * e < m && c0 + ac + AC_STEP * e < n;
+                av[e] = ok ? pa[e * sa] : (T)0;
+            }
+#pragma unroll
+            for (int e = 0; e < O_PER; ++e) {
+                const int di = OR ? 16 * (e / 2) : 8 * e, dr = OR ? 16 * (e % 2) : 0;
+                const bool ok = oi + di < l && m0 + orr + dr < m;
+                ov[e] = ok ? po[di * so_i + dr * so_r] : (T)0;
+            }
+        };
+        typename Acc<T>::type acc[TL];
+#pragma unroll
+        for (int i = 0; i < TL; ++i) acc[i] = typename Acc<T>::type{0, 0, 0, 0};
+        load(0);
+        for (int m0 = 0; m0 < m; m0 += BSI_ROWS) {
+#pragma unroll
+            for (int e = 0; e < A_PER; ++e) as_st[AR_STEP * e * A_SR + AC_STEP * e * A_SC] = av[e];
+#pragma unroll
+            for (int e = 0; e < O_PER; ++e) {
+                const int di = OR ? 16 * (e / 2) : 8 * e, dr = OR ? 16 * (e % 2) : 0;
+                os_st[di * O_SI + dr * O_SR] = ov[e];
+            }
+            __syncthreads();
+            if (m0 + BSI_ROWS < m) load(m0 + BSI_ROWS);  // in flight during the MFMAs below
+#pragma unroll
+            for (int ks = 0; ks < BSI_ROWS / 4; ++ks) {
+                const T bf = as_ld[ks * 4 * A_SR];
+#pragma unroll
+                for (int i = 0; i < TL; ++i) acc[i] = Acc<T>::mfma(os_ld[i * 16 * O_SI + ks * 4 * O_SR], bf, acc[i]);
+            }
+            __syncthreads();  // the chunk images are rewritten by the next chunk (and by the next unit)
+        }
+        const int col = c0 + wv * 16 + r16;
+#pragma unroll
+        for (int i = 0; i < TL; ++i)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                const int row = i * 16 + Acc<T>::row(lane, reg);
+                if (row < l && col < n) Yb[row * g.y.rs + col * g.y.cs] = acc[i][reg];
+            }
+    }
+}
+
+template <typename T, bool AR, bool OR>
+__global__ __launch_bounds__(BID_THREADS, 2) void k_batched_sketch_product(BspArgs<T> g) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    T *As = reinterpret_cast<T *>(smem_raw);
+    T *Os = As + BSI_A_ELEMS;
+    const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    // one instance per number of 16-row tiles, each with its own unit loop
+    switch (((int)g.omega.rows + 15) >> 4) {
+        case 1: bsp_units<T, 1, AR, OR>(g, As, Os, wv); break;
+        case 2: bsp_units<T, 2, AR, OR>(g, As, Os, wv); break;
+        case 3: bsp_units<T, 3, AR, OR>(g, As, Os, wv); break;
+        case 4: bsp_units<T, 4, AR, OR>(g, As, Os, wv); break;
+        case 5: bsp_units<T, 5, AR, OR>(g, As, Os, wv); break;
+        case 6: bsp_units<T, 6, AR, OR>(g, As, Os, wv); break;
+        case 7: bsp_units<T, 7, AR, OR>(g, As, Os, wv); break;
+        default: bsp_units<T, 8, AR, OR>(g, As, Os, wv); break;
+    }
+}
+
 // ---- batched range step (rc_sketch_range_step_batched_*) ------------------------------------------------------------------------------
 // One half-iteration pair of the reference's sample_range_power_iteration (src/random_sampling.rs:131-158) per block, without the second
 // orthonormalisation (rc_lowrank_recompress_tall_batched_* with right = I does that to p): the sketch Y = Omega A by bsi_sketch, the same
@@ -1359,6 +1475,32 @@ void batched_sketch_range_step(rc_context *c, Mat<T> a, int64_t abs, Mat<T> omeg
     g.count = (int)count; g.w_lds = plan.at;
     lch.launch(g);
 }
+
+// No plan: the two chunk images are the whole LDS and there is no workspace.  The grid is bid_grid's over the (block, panel) units, so it
+// does not move a unit's bits either; the four instances are the sketched ID's.  The label carries the units and the scratch bytes per
+// thread, which are 0 in every instance (accumulators and one staging set in flight: DESIGN.md 7u).
+template <typename T>
+void batched_sketch_product(rc_context *c, Mat<T> a, int64_t abs, Mat<T> omega, int64_t obs, int32_t count, Mat<T> y, int64_t ybs) {
+    const int m = (int)a.rows, n = (int)a.cols, l = (int)omega.rows;
+    if (count <= 0) return;
+    const int panels = (n + BSI_COLS - 1) / BSI_COLS;
+    const int64_t units = (int64_t)count * panels;
+    const size_t lds = ((size_t)BSI_A_ELEMS + (size_t)bsi_o_elems(l)) * sizeof(T);
+    const bool a_rows = a.rs <= a.cs, o_rows = omega.rs < omega.cs;
+    void (*const kerns[4])(BspArgs<T>) = {k_batched_sketch_product<T, false, false>, k_batched_sketch_product<T, false, true>,
+                                          k_batched_sketch_product<T, true, false>, k_batched_sketch_product<T, true, true>};
+    const auto lch = batched_prepare(c, kerns[(a_rows ? 2 : 0) + (o_rows ? 1 : 0)], "sketch_product_batched", lds, 0, units);
+    ProfScope ps(c, "op:batched_sketch_product %dx%d l=%d count=%d grid=%lld slots=%lld plan=units=%lld,rows=%d,cols=%d,scratch=%d", m, n, l, (int)count,
+                 (long long)lch.grid, (long long)lch.slots, (long long)units, BSI_ROWS, BSI_COLS, lch.scratch);
+    BspArgs<T> g;
+    g.a = a; g.omega = omega; g.y = y;
+    g.abs = abs; g.obs = obs; g.ybs = ybs;
+    g.units = units; g.panels = panels;
+    lch.launch(g);
+}
+
+template void batched_sketch_product<double>(rc_context *, Mat<double>, int64_t, Mat<double>, int64_t, int32_t, Mat<double>, int64_t);
+template void batched_sketch_product<float>(rc_context *, Mat<float>, int64_t, Mat<float>, int64_t, int32_t, Mat<float>, int64_t);
 
 template void batched_sketch_range_step<double>(rc_context *, Mat<double>, int64_t, Mat<double>, int64_t, int32_t, Mat<double>, int64_t, Mat<double>, int64_t,
                                                 Mat<double>, int64_t, int64_t *);

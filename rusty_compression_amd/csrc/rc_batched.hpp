@@ -149,6 +149,12 @@ template <typename R> void batched_sketch_range_step_c(rc_context *c, const rc_m
 // name), one for every scalar type like those above; the caller returns when count == 0
 void check_sketch_range_step_batched(const rc_matrix &a, const rc_matrix &omega, int32_t count, const rc_matrix &y, int64_t ybs, const rc_matrix &q,
                                      int64_t qbs, const rc_matrix &p, int64_t pbs, const int64_t *ranks, bool complex = false);
+// the sketch alone, for blocks wide as well as tall (kernels_batched_id.hip, k_batched_sketch_product): y = omega a (l x n, n <= 65536) with the
+// bits of batched_sketch_column_id's y, one (block, 64-column panel) per work unit; block i is a (m x n), omega (l x m) and y each moved by i times
+// its batch stride (0 is legal for a and omega).  Real scalars only (arguments checked by the caller)
+template <typename T> void batched_sketch_product(rc_context *c, Mat<T> a, int64_t abs, Mat<T> omega, int64_t obs, int32_t count, Mat<T> y, int64_t ybs);
+// the argument checks of rc_sketch_product_batched_* (rc_batched_api.hip); the caller returns when count == 0
+void check_sketch_product_batched(const rc_matrix &a, const rc_matrix &omega, int32_t count, const rc_matrix &y, int64_t ybs);
 // the residual of such factors against the blocks they approximate, in one rank-aware launch (kernels_batched_residual.hip): block i is a (m x n), left
 // (m x K), mid (K x K, p == nullptr: none), right (K x n) and e (m x n, p == nullptr: not written) each moved by i times its batch stride, s + i * s_stride
 // its K real scales (nullptr: none), ranks count device values (nullptr: every rank is K); err and nrm (nullptr: not written) count values: ||a_i - left

@@ -227,6 +227,20 @@ void check_sketch_range_step_batched(const rc_matrix &a, const rc_matrix &omega,
     if (y.data) check_batch_stride(who, "y", ybs, y, count);
     if (count > 0) RC_REQUIRE(a.data && omega.data && q.data && p.data && ranks, RC_INVALID_ARGUMENT, "%s: null pointer", who);
 }
+// rc_sketch_product_batched_*: the sketched ID's checks on a, omega and y, with n up to 65536 and y required
+void check_sketch_product_batched(const rc_matrix &a, const rc_matrix &omega, int32_t count, const rc_matrix &y, int64_t ybs) {
+    const char *who = "sketch_product_batched";
+    const int64_t m = a.rows, n = a.cols, l = omega.rows;
+    RC_REQUIRE(count >= 0, RC_INVALID_ARGUMENT, "%s: count = %d < 0", who, (int)count);
+    RC_REQUIRE(m >= 1 && m <= 65536 && n >= 1 && n <= 65536 && l >= 1 && l <= 128, RC_INVALID_ARGUMENT,
+               "%s: needs 1 <= m, n <= 65536 and 1 <= l <= 128 (got a %lld x %lld, omega %lld x %lld)", who, (long long)m, (long long)n, (long long)l,
+               (long long)omega.cols);
+    RC_REQUIRE(omega.cols == m, RC_INVALID_ARGUMENT, "%s: a has %lld rows but omega has %lld columns", who, (long long)m, (long long)omega.cols);
+    RC_REQUIRE(y.rows == l && y.cols == n, RC_INVALID_ARGUMENT, "%s: y must be %lld x %lld (got %lld x %lld)", who, (long long)l, (long long)n,
+               (long long)y.rows, (long long)y.cols);
+    check_batch_stride(who, "y", ybs, y, count);
+    if (count > 0) RC_REQUIRE(a.data && omega.data && y.data, RC_INVALID_ARGUMENT, "%s: null pointer", who);
+}
 // rc_demote_batched_* / rc_promote_batched_*: one shape on both sides, the sketched ID's tall domain, and dst's batch stride
 void check_convert_batched(const char *who, const rc_matrix &src, int32_t count, const rc_matrix &dst, int64_t dbs) {
     RC_REQUIRE(count >= 0, RC_INVALID_ARGUMENT, "%s: count = %d < 0", who, (int)count);
@@ -484,7 +498,22 @@ RC_DEFINE_BATCHED(c32, float, Cplx, complex_)
 RC_DEFINE_RECOMPRESS_LARGE(f64, double)
 RC_DEFINE_RECOMPRESS_LARGE(f32, float)
 
-#define RC_RANGE_STEP_PARAMS                                                                                                                            \
+// the sketch y = omega a of every block of a batch and nothing else, for blocks of up to 65536 columns: the front end of a randomized SVD of
+// wide or square blocks, and, on transposed views, its projection p = a q^T.  Real scalars only, like the large recompression.
+#define RC_DEFINE_SKETCH_PRODUCT(SUF, R)                                                                                                     \
+    rc_status rc_sketch_product_batched_##SUF(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega,                         \
+                                              int64_t omega_batch_stride, int32_t count, rc_matrix y, int64_t y_batch_stride) {              \
+        return guarded(ctx, [&] {                                                                                                            \
+            check_sketch_product_batched(a, omega, count, y, y_batch_stride);                                                                \
+            if (count == 0) return;                                                                                                          \
+            batched_sketch_product<R>(ctx, from_c<R>(a), a_batch_stride, from_c<R>(omega), omega_batch_stride, count, from_c<R>(y),          \
+                                      y_batch_stride);                                                                                       \
+        });                                                                                                                                  \
+    }
+RC_DEFINE_SKETCH_PRODUCT(f64, double)
+RC_DEFINE_SKETCH_PRODUCT(f32, float)
+
+#define RC_RANGE_STEP_PARAMS                                                                                                                           \
     rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega, int64_t omega_batch_stride, int32_t count, rc_matrix y, int64_t y_batch_stride, \
         rc_matrix q, int64_t q_batch_stride, rc_matrix p, int64_t p_batch_stride, int64_t *ranks
 #define RC_RANGE_STEP_ARGS ctx, a, a_batch_stride, omega, omega_batch_stride, count, y, y_batch_stride, q, q_batch_stride, p, p_batch_stride, ranks
