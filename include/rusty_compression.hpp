@@ -763,7 +763,7 @@ template <typename T>
 BatchedSVD<T> recompress_tall_batched(const BatchedColumnID<T> &id, int64_t k, double tol = 0.0) {
     return recompress_tall_batched<T>(id.c, nullptr, nullptr, id.z, &id.ranks, (int32_t)id.ranks.size(), k, tol);
 }
-// the same for factor pairs with both factors tall (m, n <= 65536; rc_lowrank_recompress_large_batched_f64 / _f32, real scalars only): rounded
+// the same for factor pairs with both factors tall (m, n <= 65536; rc_lowrank_recompress_large_batched_f64 / _f32 for the real scalars): rounded
 // addition, ID -> SVD conversion and re-truncation of blocks large on both sides.  For n <= 512 the result is recompress_tall_batched's bit for bit.
 inline BatchedSVD<double> recompress_large_batched(const DeviceMatrix<double> &left, const DeviceMatrix<double> *mid, const DeviceBuffer<double> *s,
                                                    const DeviceMatrix<double> &right, const DeviceIndex *ranks, int32_t count, int64_t k, double tol = 0.0) {
@@ -772,6 +772,16 @@ inline BatchedSVD<double> recompress_large_batched(const DeviceMatrix<double> &l
 inline BatchedSVD<float> recompress_large_batched(const DeviceMatrix<float> &left, const DeviceMatrix<float> *mid, const DeviceBuffer<float> *s,
                                                   const DeviceMatrix<float> &right, const DeviceIndex *ranks, int32_t count, int64_t k, double tol = 0.0) {
     return recompress_batched_through<float, double>(rc_lowrank_recompress_large_batched_f32, left, mid, s, right, ranks, count, k, tol);
+}
+// the complex pair (rc_lowrank_recompress_complex_large_batched_c64 / _c32: "complex" before "large", see the C header): s and the singular
+// values real, vt = V^H, tol in the real type of the data.  For n <= 512 the result is recompress_tall_batched's bit for bit.
+inline BatchedSVD<c64> recompress_large_batched(const DeviceMatrix<c64> &left, const DeviceMatrix<c64> *mid, const DeviceBuffer<double> *s,
+                                                const DeviceMatrix<c64> &right, const DeviceIndex *ranks, int32_t count, int64_t k, double tol = 0.0) {
+    return recompress_batched_through<c64, double>(rc_lowrank_recompress_complex_large_batched_c64, left, mid, s, right, ranks, count, k, tol);
+}
+inline BatchedSVD<c32> recompress_large_batched(const DeviceMatrix<c32> &left, const DeviceMatrix<c32> *mid, const DeviceBuffer<float> *s,
+                                                const DeviceMatrix<c32> &right, const DeviceIndex *ranks, int32_t count, int64_t k, double tol = 0.0) {
+    return recompress_batched_through<c32, float>(rc_lowrank_recompress_complex_large_batched_c32, left, mid, s, right, ranks, count, k, tol);
 }
 // one range step of a power iteration on `count` tall m x n blocks stacked in `a` (rc_sketch_range_step_batched_* for the real scalars,
 // rc_sketch_range_step_complex_batched_* for c64 and c32): per block the sketch omega a_i (l x n), an orthonormal basis q_i (l x n) of its rows

@@ -656,7 +656,7 @@ rc_status rc_lowrank_recompress_tall_batched_plan(int64_t m, int64_t n, int64_t 
  * of u is positive, and vt takes u's signs.
  * Domain: 1 <= m, n <= 65536, 1 <= K <= 128, K <= min(m, n), k >= 1, 0 <= tol < 1, count >= 0; the checks, status codes and messages are the
  * pair's above under the name lowrank_recompress_large_batched.  Real scalars only: rc_lowrank_recompress_large_batched_c64 / _c32 do not
- * exist.
+ * exist; complex pairs go to rc_lowrank_recompress_complex_large_batched_c64 / _c32 below.
  * Per block: for n > 512, right[:q, :]^T (n x q) goes through the tall call's flat Householder TSQR as left[:, :q] does: stage 0 the pivoted
  * QR of its rows 0 .. 511, every later stage the q x q triangle on the next 512 - q rows in the pivot order so far; the factor's power-of-two
  * scale is taken over all n columns.  The last triangle and the cumulative permutation enter the core; the core, the Jacobi iteration, the
@@ -717,6 +717,45 @@ rc_status rc_lowrank_recompress_tall_complex_batched_c32(rc_context *ctx, rc_mat
  * the size of the real type (8: c64, 4: c32); *slot_bytes counts complex elements of 2 * real_bytes.  RC_INVALID_ARGUMENT outside the call's
  * domain, for another real_bytes, resident < 1 or a null output. */
 rc_status rc_lowrank_recompress_tall_complex_batched_plan(int64_t m, int64_t n, int64_t inner, int32_t real_bytes, int64_t resident, int64_t *stages, int64_t *slot_bytes, int64_t *grid);
+/* The complex recompression for factor pairs with both factors tall (the large square blocks at the upper levels of a hierarchical matrix):
+ * rc_lowrank_recompress_tall_complex_batched_c64 / _c32's signature argument for argument (interleaved (re, im) data, strides in complex elements,
+ * real s, s_out and tol, float tol for c32) and its per-block contract sentence for sentence: A_i = left[:, :q] mid[:q, :q] diag(s[:q])
+ * right[:q, :] with nothing conjugated, vt = V^H, the rank rule, s_out zero past q, u and vt zero past the rank, an exactly zero column of
+ * left[:, :q] giving an exactly zero singular value, q = 0 reading no input, elements at an index >= q never read, NaN
+ * containment, health bit 16, conjugation and zero-imaginary-part symmetry, no host synchronisation, capturable.  The phase rule is taken over
+ * all m rows of each kept column of u: the first entry of largest modulus is exactly (|x|, 0), whichever stage holds it; the matching row of
+ * vt carries the conjugate phase over all n columns.
+ * Domain: 1 <= m, n <= 65536, 1 <= K <= 128, K <= min(m, n), k >= 1, 0 <= tol < 1, count >= 0; the checks, status codes and messages are the
+ * shared ones under the name lowrank_recompress_complex_large_batched.
+ * Per block: for n > 512 the plain transpose right[:q, :]^T (n x q) goes through the tall call's staged Householder TSQR as left[:, :q] does
+ * (stage 0 the pivoted QR of its rows 0 .. 511, every later stage the q x q triangle on the next 512 - q rows in the pivot order so far,
+ * complex taus); the last triangle and the cumulative permutation enter the core; the core, the Jacobi iteration, the sort and the rank rule
+ * are unchanged.  Each kept row of vt is carried back down the right factor's stages and written once, chunk by chunk, times the conjugate of
+ * the phase fixed on u.
+ * Zero rows of right: for n > 512 an exactly zero row of right[:q, :] is an exactly zero singular value too (a zero row of the right
+ * factor's R; where that R has fewer nonzero rows than the left factor's, the iteration runs on the core itself instead of its conjugate
+ * transpose, in which those rows are untouched zero columns).  Not promised: for n <= 512 the call is
+ * rc_lowrank_recompress_tall_complex_batched_* bit for bit, which makes no such promise and can return inaccurate singular values for a
+ * zero row of right under a nonzero column of left; nor, for any n, a core whose nonzero columns are dependent for another reason (zero
+ * columns of left and zero rows of right at different indices with no mid, or equal rows of right), where the singular values that
+ * should vanish come out as rounding of sigma and the others can lose accuracy.  Cut left and right at the same indices, as the batched calls' zero tails are.
+ * Bits: the operands, their row and column strides and the call's shapes alone; those of the truncated factors passed as a call of inner width
+ * q (the stage heights of both sides depend on q, not on K); and for n <= 512 every output equals
+ * rc_lowrank_recompress_tall_complex_batched_*'s on the same arguments bit for bit.  No transposition symmetry is promised.
+ * Workspace: a workgroup's slot holds the left factor's stage copies (m > 512), then the right factor's (n > 512), then the core and the
+ * rotations where they do not fit in LDS; an n <= 512 call has the tall complex call's plan byte for byte.  The grid is bounded so that all
+ * slots stay at or below 2 GiB (never below one workgroup): at m = n = 65536, K = 128 in c64, two sides of 171 stages of 1052672 bytes leave
+ * 5 workgroups; the plan query below reports the numbers.
+ * The name: "complex" stands before "large", unlike rc_lowrank_recompress_tall_complex_batched_*.  The real pair was published as "real
+ * scalars only" with both spellings a twin might have taken, the real stem with a c64 / c32 suffix and ..._large_complex_batched_*, named as
+ * absent, and callers (and the ABI test of that pair) rely on that: neither is declared or exported, and a build that has this call is told
+ * apart by its own symbol. */
+rc_status rc_lowrank_recompress_complex_large_batched_c64(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const double *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *in_ranks, int32_t count, int64_t k, double tol, rc_matrix u, int64_t u_batch_stride, double *s_out, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks);
+rc_status rc_lowrank_recompress_complex_large_batched_c32(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const float *s, int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *in_ranks, int32_t count, int64_t k, float tol, rc_matrix u, int64_t u_batch_stride, float *s_out, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks);
+/* The plan of that call as numbers, host arithmetic only (no context, no device): as rc_lowrank_recompress_large_batched_plan with real_bytes
+ * the size of the real type (8: c64, 4: c32); *slot_bytes counts complex elements of 2 * real_bytes.  RC_INVALID_ARGUMENT outside the call's
+ * domain, for another real_bytes, resident < 1 or a null output. */
+rc_status rc_lowrank_recompress_complex_large_batched_plan(int64_t m, int64_t n, int64_t inner, int32_t real_bytes, int64_t resident, int64_t *stages_left, int64_t *stages_right, int64_t *slot_bytes, int64_t *grid);
 /* The one-pass randomized column ID of every block of a batch, in one stream-ordered, capturable call: the sketch Y_i = omega_i a_i (l x n) of each
  * tall block a_i (m x n) is formed while a_i streams through the chip once, and the column ID of the small Y_i gives the pivots and Z; C is gathered
  * from a_i.  Per block this replaces the reference's randomized sequence: the projection of sample_range_by_rank (src/random_sampling.rs), then

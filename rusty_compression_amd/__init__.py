@@ -15,6 +15,7 @@ from .batch import (column_id_to_svd_batched_complex, lowrank_recompress_batched
                     two_sided_id_to_svd_batched_complex)
 from .batch import column_id_to_svd_tall_batched, lowrank_recompress_tall_batched, sketch_svd_rank_batched, svd_add_tall_batched  # noqa: F401
 from .batch import lowrank_recompress_large_batched, svd_add_large_batched  # noqa: F401
+from .batch import lowrank_recompress_large_batched_complex, svd_add_large_batched_complex  # noqa: F401
 from .batch import sketch_product_batched, sketch_range_step_large_batched, sketch_svd_rank_large_batched  # noqa: F401
 from .batch import (column_id_to_svd_tall_batched_complex, lowrank_recompress_tall_batched_complex, sketch_svd_rank_batched_complex,  # noqa: F401
                     svd_add_tall_batched_complex)
@@ -49,7 +50,7 @@ __all__ = [
     "MatrixPermutationMode", "VectorPermutationMode", "apply_permutation", "invert_permutation_vector",
     "random_gaussian", "random_bits_u32", "random_orthogonal_matrix", "random_approximate_low_rank_matrix",
     "sample_range_by_rank", "sample_range_power_iteration", "sample_range_adaptive", "max_col_norm",
-    "matmat", "conj_matmat", "dot", "rel_diff_fro", "rel_diff_l2", "pivoted_qr", "pivoted_lq", "compute_svd", "column_id_rank_batched", "two_sided_id_rank_batched", "svd_rank_batched", "svd_rank_batched_complex", "lowrank_apply_batched", "column_id_apply_batched", "two_sided_id_apply_batched", "svd_apply_batched", "lowrank_recompress_batched", "column_id_to_svd_batched", "two_sided_id_to_svd_batched", "svd_add_batched", "lowrank_recompress_batched_complex", "column_id_to_svd_batched_complex", "two_sided_id_to_svd_batched_complex", "svd_add_batched_complex", "lowrank_recompress_tall_batched", "column_id_to_svd_tall_batched", "svd_add_tall_batched", "lowrank_recompress_large_batched", "svd_add_large_batched", "sketch_svd_rank_batched", "lowrank_recompress_tall_batched_complex", "column_id_to_svd_tall_batched_complex", "svd_add_tall_batched_complex", "sketch_svd_rank_batched_complex", "sketch_column_id_rank_batched", "sketch_column_id_rank_batched_complex", "lowrank_residual_batched", "column_id_residual_batched", "two_sided_id_residual_batched", "svd_residual_batched", "lowrank_residual_batched_complex", "column_id_residual_batched_complex", "two_sided_id_residual_batched_complex", "svd_residual_batched_complex", "geqp3", "orgqr", "trsm_upper",
+    "matmat", "conj_matmat", "dot", "rel_diff_fro", "rel_diff_l2", "pivoted_qr", "pivoted_lq", "compute_svd", "column_id_rank_batched", "two_sided_id_rank_batched", "svd_rank_batched", "svd_rank_batched_complex", "lowrank_apply_batched", "column_id_apply_batched", "two_sided_id_apply_batched", "svd_apply_batched", "lowrank_recompress_batched", "column_id_to_svd_batched", "two_sided_id_to_svd_batched", "svd_add_batched", "lowrank_recompress_batched_complex", "column_id_to_svd_batched_complex", "two_sided_id_to_svd_batched_complex", "svd_add_batched_complex", "lowrank_recompress_tall_batched", "column_id_to_svd_tall_batched", "svd_add_tall_batched", "lowrank_recompress_large_batched", "svd_add_large_batched", "lowrank_recompress_large_batched_complex", "svd_add_large_batched_complex", "sketch_svd_rank_batched", "lowrank_recompress_tall_batched_complex", "column_id_to_svd_tall_batched_complex", "svd_add_tall_batched_complex", "sketch_svd_rank_batched_complex", "sketch_column_id_rank_batched", "sketch_column_id_rank_batched_complex", "lowrank_residual_batched", "column_id_residual_batched", "two_sided_id_residual_batched", "svd_residual_batched", "lowrank_residual_batched_complex", "column_id_residual_batched_complex", "two_sided_id_residual_batched_complex", "svd_residual_batched_complex", "geqp3", "orgqr", "trsm_upper",
     "RustyCompressionError", "LinalgError", "CompressionError", "LayoutError", "PivotedQRError", "HipRuntimeError",
     "Context", "default_context", "Operator", "DenseOperator", "LowRankOperator", "BlockLowRankOperator",
     "block_csr", "block_operator_apply",

@@ -552,8 +552,8 @@ def block_operator_apply_mixed(x: torch.Tensor, group_ptr, group_row, entry_bloc
 
 def _lowrank_recompress_batched(who: str, complex_data: bool, left, right, k, tol, mid, s, ranks, tall=False):
     """The shared body of lowrank_recompress_batched, lowrank_recompress_tall_batched, lowrank_recompress_large_batched (real dtypes; tall:
-    False, True for the entry points with m <= 65536, or "large" for those with m, n <= 65536), lowrank_recompress_batched_complex and
-    lowrank_recompress_tall_batched_complex (complex dtypes, real s and S; there is no complex large call)."""
+    False, True for the entry points with m <= 65536, or "large" for those with m, n <= 65536), lowrank_recompress_batched_complex,
+    lowrank_recompress_tall_batched_complex and lowrank_recompress_large_batched_complex (complex dtypes, real s and S, the same values of tall)."""
     from . import _lib
     from .types import as_device
 
@@ -607,7 +607,8 @@ def _lowrank_recompress_batched(who: str, complex_data: bool, left, right, k, to
     # the complex entry points spell their stem differently (see the header) and take tol in the real type of the data
     stem = {(False, False): "rc_lowrank_recompress_batched_", (False, True): "rc_lowrank_recompress_tall_batched_",
             (False, "large"): "rc_lowrank_recompress_large_batched_", (True, False): "rc_lowrank_recompress_complex_batched_",
-            (True, True): "rc_lowrank_recompress_tall_complex_batched_"}[(complex_data, tall)]
+            (True, True): "rc_lowrank_recompress_tall_complex_batched_",
+            (True, "large"): "rc_lowrank_recompress_complex_large_batched_"}[(complex_data, tall)]
     tol_arg = ctypes.c_float(float(tol)) if left.dtype == torch.complex64 else ctypes.c_double(float(tol))
     _lib.default_context().call(stem + _lib.suffix(left.dtype), *view(left), *view(mid),
                                 ctypes.c_void_p(s.data_ptr() if s is not None else None), ctypes.c_int64(s.stride(0) if s is not None else 0),
@@ -717,7 +718,8 @@ def lowrank_recompress_large_batched(left: torch.Tensor, right: torch.Tensor, k:
     The arguments and results are lowrank_recompress_tall_batched's with m, n <= 65536 (K <= min(m, n), K <= 128): U [count, m, kk],
     S [count, K], Vt [count, kk, n] and the new ranks; the largest-|.| entry of each kept column of U, over all m rows, is positive and Vt
     takes U's signs.  For n <= 512 the outputs are lowrank_recompress_tall_batched's bit for bit; a block's bits are those of its truncated
-    factors passed at inner width q.  No transposition symmetry is promised.  Real dtypes only: complex data raises TypeError."""
+    factors passed at inner width q.  No transposition symmetry is promised.  Real dtypes only: complex data raises TypeError (see
+    lowrank_recompress_large_batched_complex)."""
     return _lowrank_recompress_batched("lowrank_recompress_large_batched", False, left, right, k, tol, mid, s, ranks, tall="large")
 
 
@@ -728,6 +730,12 @@ def svd_add_large_batched(u1: torch.Tensor, s1: torch.Tensor, vt1: torch.Tensor,
     lowrank_recompress_large_batched.  ranks1 / ranks2 ([count] int64, optional): the ranks of the two addends; columns of U1, U2, entries of
     s1, s2 and rows of Vt1, Vt2 past them are zeroed before the concatenation (without them the zero tails the batched calls write are relied
     on, as in svd_add_batched)."""
+    left, right, s = _svd_add_large_operands(u1, s1, vt1, u2, s2, vt2, ranks1, ranks2)
+    return lowrank_recompress_large_batched(left, right, k, tol, s=s)
+
+
+def _svd_add_large_operands(u1, s1, vt1, u2, s2, vt2, ranks1, ranks2):
+    """The concatenated factors of svd_add_large_batched and its complex twin, cut at ranks1 / ranks2 where given."""
     k1, k2 = u1.shape[2], u2.shape[2]
 
     def cut(u, s, vt, ranks, kx):  # on the device, no host synchronisation; what lies past a rank may be anything, NaN included
@@ -735,14 +743,15 @@ def svd_add_large_batched(u1: torch.Tensor, s1: torch.Tensor, vt1: torch.Tensor,
             return u, s, vt
         keep = torch.arange(kx, device=s.device)[None, :] < ranks[:, None]
         zero = torch.zeros((), dtype=u.dtype, device=u.device)
-        return torch.where(keep[:, None, :], u, zero), torch.where(keep, s[:, :kx], zero), torch.where(keep[:, :, None], vt, zero)
+        szero = torch.zeros((), dtype=s.dtype, device=s.device)  # s is real where u is complex
+        return torch.where(keep[:, None, :], u, zero), torch.where(keep, s[:, :kx], szero), torch.where(keep[:, :, None], vt, zero)
 
     u1, s1, vt1 = cut(u1, s1, vt1, ranks1, k1)
     u2, s2, vt2 = cut(u2, s2, vt2, ranks2, k2)
     left = torch.cat([u1, u2], dim=2)
     right = torch.cat([vt1, vt2], dim=1)
     s = torch.cat([s1[:, :k1], s2[:, :k2]], dim=1)
-    return lowrank_recompress_large_batched(left, right, k, tol, s=s)
+    return left, right, s
 
 
 def lowrank_recompress_tall_batched_complex(left: torch.Tensor, right: torch.Tensor, k: int, tol: float = 0.0, mid: Optional[torch.Tensor] = None,
@@ -758,6 +767,28 @@ def lowrank_recompress_tall_batched_complex(left: torch.Tensor, right: torch.Ten
     all three factors: pass right.mT, mid.mT, left.mT and read the block's U as Vt_out.mT and its Vt as U_out.mT (no .conj() anywhere);
     the phase rule then holds on the rows of the block's Vt."""
     return _lowrank_recompress_batched("lowrank_recompress_tall_batched_complex", True, left, right, k, tol, mid, s, ranks, tall=True)
+
+
+def lowrank_recompress_large_batched_complex(left: torch.Tensor, right: torch.Tensor, k: int, tol: float = 0.0, mid: Optional[torch.Tensor] = None,
+                                             s: Optional[torch.Tensor] = None,
+                                             ranks: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """lowrank_recompress_large_batched for complex factors (rc_lowrank_recompress_complex_large_batched_c64 / _c32): the arguments, dtypes and
+    results of lowrank_recompress_tall_batched_complex (left, right and mid complex128 or complex64 of one dtype, lazily conjugated views
+    materialised, s and S real, Vt the conjugate transpose of V, nothing conjugated in the product; real data and mismatched dtypes raise
+    TypeError) with m, n <= 65536: the plain transpose of right goes through the same staged Householder TSQR as left.  In each kept column
+    of U the first of its largest-modulus entries over all m rows is real and positive, its imaginary part exactly 0, and the matching row
+    of Vt carries the conjugate phase; conjugated inputs give the conjugated U and Vt bit for bit.  For n <= 512 the outputs are
+    lowrank_recompress_tall_batched_complex's bit for bit; a block's bits are those of its truncated factors passed at inner width q."""
+    return _lowrank_recompress_batched("lowrank_recompress_large_batched_complex", True, left, right, k, tol, mid, s, ranks, tall="large")
+
+
+def svd_add_large_batched_complex(u1: torch.Tensor, s1: torch.Tensor, vt1: torch.Tensor, u2: torch.Tensor, s2: torch.Tensor, vt2: torch.Tensor, k: int,
+                                  tol: float = 0.0, ranks1: Optional[torch.Tensor] = None,
+                                  ranks2: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """svd_add_large_batched for complex truncated SVDs (U, Vt complex, s real; Vt = V^H, nothing conjugated in U diag(s) Vt), through
+    lowrank_recompress_large_batched_complex, with the same ranks1 / ranks2 cut."""
+    left, right, s = _svd_add_large_operands(u1, s1, vt1, u2, s2, vt2, ranks1, ranks2)
+    return lowrank_recompress_large_batched_complex(left, right, k, tol, s=s)
 
 
 def column_id_to_svd_tall_batched_complex(c: torch.Tensor, z: torch.Tensor, ranks: Optional[torch.Tensor], k: int,

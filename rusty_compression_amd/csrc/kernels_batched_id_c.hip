@@ -1,7 +1,8 @@
 // Batched column and two-sided IDs and truncated SVDs of many small same-shaped COMPLEX matrices in one launch
 // (rc_column_id_rank_batched_c64 / _c32, rc_two_sided_id_rank_batched_c64 / _c32, rc_svd_rank_batched_c64 / _c32), and the
 // recompression of complex low-rank factors (rc_lowrank_recompress_complex_batched_c64 / _c32 and, for tall left factors,
-// rc_lowrank_recompress_tall_complex_batched_c64 / _c32: k_batched_recompress_c<R, TALL> below) and the sketched
+// rc_lowrank_recompress_tall_complex_batched_c64 / _c32, for two tall factors rc_lowrank_recompress_complex_large_batched_c64 / _c32:
+// k_batched_recompress_c<R, TALL, LARGE> below) and the sketched
 // column ID of complex tall blocks (rc_sketch_column_id_rank_complex_batched_c64 / _c32, k_batched_sketch_id_c below) and the range step
 // of their power iteration (rc_sketch_range_step_complex_batched_c64 / _c32, k_batched_range_step_c below).
 //
@@ -604,24 +605,86 @@ __device__ __forceinline__ void brtc_form_u(const cplx<R> *stage0, size_t se, in
     }
 }
 
+// ---- both factors tall (rc_lowrank_recompress_complex_large_batched_c64 / _c32, m, n <= 65536) -------------------------------------------------
+// k_batched_recompress<T, true, true>'s scheme (kernels_batched_id.hip) on complex elements: for n > H the plain transpose right[:q, :]^T (n x q)
+// goes through the stages above, jpr carried from stage to stage, every stage's copy, complex taus and pivots in the workgroup's slot behind the
+// left factor's part; (the last stage's copy, jpr) stand where (Wr, jpr) stand in T1.  An exactly zero row of right is a zero column of every
+// stack: pivoted last, tau = 0.  n <= H is the tall complex call itself: the launcher runs its instances under brtc_plan, so the bits are that
+// call's.  The slot: the left factor's part (stage copies for m > H, brcc_ws_elems' copy otherwise), the right factor's stage copies, then G and
+// J wherever they are not in LDS.
+__host__ __device__ inline size_t brlc_ws_elems(int m, int n, int K, int ldg, bool l_lds, bool r_lds, bool v_lds, bool g_lds) {
+    if (n <= BRT_H) return brtc_ws_elems(m, n, K, ldg, l_lds, r_lds, v_lds, g_lds);
+    return brtc_ws_elems(m, 0, K, ldg, l_lds, true, true, true) + (size_t)brt_stages(n, K) * brt_stage_elems(K) + (g_lds ? 0 : (size_t)K * ldg) +
+           (v_lds ? 0 : (size_t)K * K);
+}
+
+// vt^T[:, c] = conj(ph_c) Q_0 [Q_1 [.. Q_{S-1} [Vc[:, srt[c]]; 0] ..; 0]; 0] for S >= 2 stages of the right factor, Vc the kept columns of G already
+// conjugated and scaled: brtc_form_u with the phases already fixed on u, so every chunk is written once, multiplied by conj(phs[c]) with operator*
+// of rc_cplx.hpp (the product bsc_form_u(phase_here = false) uses: conjugating the inputs conjugates the row bit for bit), and no row is visited
+// twice.  V is vt's transposed view (n x k); rows r .. k - 1 of vt are zero over all n columns.
+template <typename R>
+__device__ __forceinline__ void brlc_form_vt(const cplx<R> *stage0, size_t se, int S, int K, int q, int n, const cplx<R> *Vc, int ldv, int k, int r, const int *srt,
+                                             const cplx<R> *phs, cplx<R> *V, int64_t vrs, int64_t vcs, int wv, int lane) {
+    constexpr int NE = BRT_H / 64;
+    for (int c = wv; c < k; c += BID_WAVES) {
+        cplx<R> *vc = V + (int64_t)c * vcs;
+        if (c >= r) {
+            for (int i = lane; i < n; i += 64) vc[i * vrs] = czero<R>();
+            continue;
+        }
+        const cplx<R> *gc = Vc + (size_t)srt[c] * ldv;
+        const cplx<R> ph = cj(phs[c]);
+        cplx<R> x[NE];
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            const int i = lane + 64 * e;
+            x[e] = i < q ? gc[i] : czero<R>();
+        }
+        for (int s = S - 1; s >= 0; --s) {
+            const cplx<R> *Ws = stage0 + (size_t)s * se, *ts = Ws + (size_t)BRT_H * K;
+            const int top = s ? q : 0, base = s ? BRT_H + (s - 1) * (BRT_H - q) : 0;
+            const int hs = top + min(BRT_H - top, n - base);
+            bsc_reflect_back<R, NE>(Ws, BRT_H, hs, q, reinterpret_cast<const int *>(ts + K), ts, x, lane);
+            if (s) {
+#pragma unroll
+                for (int e = 0; e < NE; ++e) {
+                    const int i = lane + 64 * e;
+                    if (i >= top && i < hs) vc[(int64_t)(base + i - top) * vrs] = x[e] * ph;
+                    x[e] = i < top ? x[e] : czero<R>();
+                }
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < NE; ++e) vc[(int64_t)(lane + 64 * e) * vrs] = x[e] * ph;  // stage 0 of S >= 2 stages holds H rows
+    }
+}
+
 // TALL = false: rc_lowrank_recompress_complex_batched_*, and rc_lowrank_recompress_tall_complex_batched_* for m <= 512.  TALL = true:
 // rc_lowrank_recompress_tall_complex_batched_* for m > 512, the left factor by stages (see above; the plan keeps the stage copies out of LDS).
 // Two waves per SIMD (256 registers), but for the c64 tall instance, which is built for one wave per SIMD.  It fits 256 registers without
 // scratch, but the code the compiler makes under that bound is slower than what it makes with room to spare: 52.7k against 74.7k blocks/s at
 // 2048 x 2048 x 256, K = 32, and 49.9k against 68.7k at 512 x 8192 x 128, K = 16, at the same grid: the workspace bound leaves
 // one workgroup per CU at those shapes either way, and the kernel is latency-bound per Householder step.
-template <typename R, bool TALL>
-__global__ __launch_bounds__(BID_THREADS, (TALL && sizeof(R) == 8) ? 1 : 2) void k_batched_recompress_c(BrcCArgs<R> a) {
+// LARGE (with TALL): rc_lowrank_recompress_complex_large_batched_* for n > 512, the right factor by stages too (see "both factors tall"), the left
+// one by stages for m > 512 and as one stage below.  The launcher sends n <= 512 to the two instances above, so this one carries neither the
+// one-stage path of the right factor nor bsc_form_u for vt.  Both of its instances are built for one wave per SIMD: the c64 one for the reason
+// above, and the c32 one because it carries both left paths and spills three registers under the bound of two waves (12 bytes of scratch per
+// thread; none with room), while its slot (both factors' stages) leaves one workgroup per CU at the shapes it is for either way.
+template <typename R, bool TALL, bool LARGE = false>
+__global__ __launch_bounds__(BID_THREADS, ((TALL && sizeof(R) == 8) || LARGE) ? 1 : 2) void k_batched_recompress_c(BrcCArgs<R> a) {
+    static_assert(TALL || !LARGE, "the large instance is the tall one with a staged right factor");
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int m = (int)a.left.rows, n = (int)a.right.cols, K = (int)a.left.cols;
     const int kk = a.k < K ? a.k : K, ldg = a.ldg;
-    const int ldl = TALL ? BRT_H : a.l_lds ? (m | 1) : m, ldr = a.r_lds ? (n | 1) : n, ldj = a.v_lds ? ldg : K;
+    const bool multi = LARGE ? m > BRT_H : TALL;  // the left factor by stages, its copies in the slot (a constant but in the large instance)
+    const int ldl = multi ? BRT_H : a.l_lds ? (m | 1) : m, ldr = LARGE ? BRT_H : a.r_lds ? (n | 1) : n, ldj = a.v_lds ? ldg : K;
     cplx<R> *lp = reinterpret_cast<cplx<R> *>(smem_raw);  // next free LDS element
-    cplx<R> *wp = a.ws + (size_t)blockIdx.x * (TALL ? brtc_ws_elems(m, n, K, ldg, a.l_lds, a.r_lds, a.v_lds, a.g_lds)
-                                                    : brcc_ws_elems(m, n, K, ldg, a.l_lds, a.r_lds, a.v_lds, a.g_lds));  // next free workspace element
-    cplx<R> *Wl0, *Wr, *G, *J;
-    if (a.l_lds) { Wl0 = lp; lp += (size_t)K * ldl; } else { Wl0 = wp; wp += TALL ? (size_t)brt_stages(m, K) * brt_stage_elems(K) : (size_t)m * K; }
-    if (a.r_lds) { Wr = lp; lp += (size_t)K * ldr; } else { Wr = wp; wp += (size_t)n * K; }
+    cplx<R> *wp = a.ws + (size_t)blockIdx.x * (LARGE  ? brlc_ws_elems(m, n, K, ldg, a.l_lds, a.r_lds, a.v_lds, a.g_lds)
+                                               : TALL ? brtc_ws_elems(m, n, K, ldg, a.l_lds, a.r_lds, a.v_lds, a.g_lds)
+                                                      : brcc_ws_elems(m, n, K, ldg, a.l_lds, a.r_lds, a.v_lds, a.g_lds));  // next free workspace element
+    cplx<R> *Wl0, *Wr0, *G, *J;
+    if (a.l_lds) { Wl0 = lp; lp += (size_t)K * ldl; } else { Wl0 = wp; wp += multi ? (size_t)brt_stages(m, K) * brt_stage_elems(K) : (size_t)m * K; }
+    if (a.r_lds) { Wr0 = lp; lp += (size_t)K * ldr; } else { Wr0 = wp; wp += LARGE ? (size_t)brt_stages(n, K) * brt_stage_elems(K) : (size_t)n * K; }
     if (a.g_lds) { G = lp; lp += (size_t)K * ldg; } else { G = wp; wp += (size_t)K * ldg; }
     if (a.v_lds) { J = lp; lp += (size_t)K * ldj; } else { J = wp; }
     cplx<R> *taul = lp, *taur = taul + K, *phs = taur + K;
@@ -653,8 +716,9 @@ __global__ __launch_bounds__(BID_THREADS, (TALL && sizeof(R) == 8) ? 1 : 2) void
         const cplx<R> *__restrict__ L = a.left.p + (int64_t)b * a.lbs;
         const cplx<R> *__restrict__ Rt = a.right.p + (int64_t)b * a.rbs;
         cplx<R> *Wl = Wl0;  // the copy the core and U read: the last stage's
+        cplx<R> *Wr = Wr0;  // likewise for T1 (set per block: a workgroup's next block starts at stage 0 again)
         [[maybe_unused]] int S = 1;
-        if constexpr (TALL) {
+        if (multi) {
             S = brt_stages(m, q);  // >= 2: m > BRT_H
             const size_t se = brt_stage_elems(K);
             for (int j = tid; j < q; j += BID_THREADS) jpl[j] = j;  // ordered before its first read by brt_stack_load's barrier
@@ -673,10 +737,38 @@ __global__ __launch_bounds__(BID_THREADS, (TALL && sizeof(R) == 8) ? 1 : 2) void
             bid_load(Wl, ldl, m, q, a.left.rs <= a.left.cs, [&](int i, int c) { return L[i * a.left.rs + c * a.left.cs]; }, vn1, vn2, jpl, wv, lane);
             bid_qrcp<cplx<R>, true>(Wl, ldl, m, q, q, 0.0, jpl, vn1, vn2, red, tid, wv, lane, taul);
         }
-        bid_load(Wr, ldr, n, q, a.right.cs <= a.right.rs, [&](int i, int c) { return Rt[c * a.right.rs + i * a.right.cs]; }, vn1, vn2, jpr, wv, lane);
-        bid_qrcp<cplx<R>, true>(Wr, ldr, n, q, q, 0.0, jpr, vn1, vn2, red, tid, wv, lane, taur);
+        [[maybe_unused]] int Sr = 1;
+        if constexpr (LARGE) {  // the left factor's stage loop on right[:q, :]^T, every stage in the slot
+            Sr = brt_stages(n, q);  // >= 2: n > BRT_H
+            const size_t se = brt_stage_elems(K);
+            for (int j = tid; j < q; j += BID_THREADS) jpr[j] = j;  // ordered before its first read by brt_stack_load's barrier
+            for (int s = 0; s < Sr; ++s) {
+                const int top = s ? q : 0, base = s ? BRT_H + (s - 1) * (BRT_H - q) : 0;
+                const int hs = top + min(BRT_H - top, n - base);
+                cplx<R> *Ws = Wr0 + (size_t)s * se, *ts = Ws + (size_t)BRT_H * K;
+                brt_stack_load(Ws, ldr, Ws - (s ? se : 0), top, hs, q, a.right.cs <= a.right.rs,
+                                [&](int i, int c) { return Rt[c * a.right.rs + (int64_t)(base + i) * a.right.cs]; }, vn1, vn2, jpr, wv, lane);
+                bid_qrcp<cplx<R>, true>(Ws, ldr, hs, q, q, 0.0, jpr, vn1, vn2, red, tid, wv, lane, ts);
+                int *js = reinterpret_cast<int *>(ts + K);
+                for (int j = tid; j < q; j += BID_THREADS) js[j] = jpr[j];
+                Wr = Ws;
+            }
+        } else {
+            bid_load(Wr, ldr, n, q, a.right.cs <= a.right.rs, [&](int i, int c) { return Rt[c * a.right.rs + i * a.right.cs]; }, vn1, vn2, jpr, wv, lane);
+            bid_qrcp<cplx<R>, true>(Wr, ldr, n, q, q, 0.0, jpr, vn1, vn2, red, tid, wv, lane, taur);
+        }
         for (int j = tid; j < q; j += BID_THREADS) { ipl[jpl[j]] = j; ipr[jpr[j]] = j; }
+        if constexpr (LARGE) {
+            if (tid == 0) { flag[2] = 0; flag[3] = 0; }
+        }
         __syncthreads();
+        if constexpr (LARGE) {  // the nonzero rows of R_L and of R_R (exact zero pivots come last and leave a zero diagonal): see the core below
+            for (int j = tid; j < q; j += BID_THREADS) {
+                const cplx<R> dl = Wl[(size_t)jpl[j] * ldl + j], dr = Wr[(size_t)jpr[j] * ldr + j];
+                if (!(dl.re == (R)0 && dl.im == (R)0)) atomicAdd(&flag[2], 1);
+                if (!(dr.re == (R)0 && dr.im == (R)0)) atomicAdd(&flag[3], 1);
+            }
+        }
         // ---- T1 = mid diag(s) Rr^T in J's place ----------------------------------------------------------------------------------------
         const cplx<R> *__restrict__ Mb = a.mid.p ? a.mid.p + (int64_t)b * a.mbs : nullptr;
         const R *__restrict__ Sb = a.s ? a.s + (int64_t)b * a.s_stride : nullptr;
@@ -701,6 +793,13 @@ __global__ __launch_bounds__(BID_THREADS, (TALL && sizeof(R) == 8) ? 1 : 2) void
         }
         __syncthreads();
         // ---- G = C^H: G[i * ldg + j] = conj(sum_a Rl[i, a] T1[a, j]) ------------------------------------------------------------------
+        // The large instance turns the core when right has fewer nonzero rows of R than left (exactly zero rows of right[:q, :] under
+        // nonzero columns of left): G = C^H would then hold q columns in fewer dimensions, dependent columns, on which the iteration is
+        // inaccurate.  It runs on G = C instead: the zero rows of R_R are zero columns of C, which no rotation touches, so they are
+        // exactly zero singular values as zero columns of left are, and the remaining columns are as many as R_R has rows.  With
+        // C J = U_c Sigma: U = Q_L [U_c; 0] from the scaled columns of G, vt^T = Q_R [conj(J); 0]: the two operands change places below.
+        [[maybe_unused]] bool turned = false;  // a constant in every instance but the large one
+        if constexpr (LARGE) turned = flag[3] < flag[2];  // uniform: read behind the barrier above, rewritten behind the block's last one
         for (int idx = tid; idx < q * q; idx += BID_THREADS) {
             const int i = idx / q, j = idx - i * q;
             cplx<R> acc = czero<R>();
@@ -708,7 +807,12 @@ __global__ __launch_bounds__(BID_THREADS, (TALL && sizeof(R) == 8) ? 1 : 2) void
                 const cplx<R> lv = i <= ipl[aa] ? Wl[(size_t)aa * ldl + i] : czero<R>();
                 cfma(lv, J[(size_t)aa * ldj + j], acc);
             }
-            G[(size_t)i * ldg + j] = cj(acc);
+            if constexpr (LARGE) {
+                if (turned) G[(size_t)j * ldg + i] = acc;
+                else G[(size_t)i * ldg + j] = cj(acc);
+            } else {
+                G[(size_t)i * ldg + j] = cj(acc);
+            }
         }
         __syncthreads();
         for (int idx = tid; idx < q * q; idx += BID_THREADS) {
@@ -760,22 +864,49 @@ __global__ __launch_bounds__(BID_THREADS, (TALL && sizeof(R) == 8) ? 1 : 2) void
         __syncthreads();
         const int r = flag[1];
         // ---- U = Q_L [J_r; 0] with the phase rule applied to its columns, the phases kept in phs ------------------------------------------
-        if constexpr (TALL) brtc_form_u<R>(Wl0, brt_stage_elems(K), S, K, q, m, J, ldj, kk, r, srt, phs, Ub, a.u.rs, a.u.cs, wv, lane);
-        else if (m <= 64) bsc_form_u<R, 1>(Wl, ldl, J, ldj, m, q, kk, r, jpl, taul, srt, phs, true, Ub, a.u.rs, a.u.cs, wv, lane);
-        else if (m <= 128) bsc_form_u<R, 2>(Wl, ldl, J, ldj, m, q, kk, r, jpl, taul, srt, phs, true, Ub, a.u.rs, a.u.cs, wv, lane);
-        else if (m <= 256) bsc_form_u<R, 4>(Wl, ldl, J, ldj, m, q, kk, r, jpl, taul, srt, phs, true, Ub, a.u.rs, a.u.cs, wv, lane);
-        else bsc_form_u<R, 8>(Wl, ldl, J, ldj, m, q, kk, r, jpl, taul, srt, phs, true, Ub, a.u.rs, a.u.cs, wv, lane);
+        if constexpr (LARGE) {
+            const cplx<R> *Uc = J;  // the core's left vectors
+            int ldc = ldj;
+            if (turned) {  // U_c = G Sigma^-1 and conj(J) in place (kept columns), before either is read
+                for (int c = wv; c < r; c += BID_WAVES) {
+                    cplx<R> *gc = G + (size_t)srt[c] * ldg, *jc = J + (size_t)srt[c] * ldj;
+                    const R sj = sig[srt[c]], inv = sj > (R)0 ? (R)1 / sj : (R)0;
+                    for (int i = lane; i < q; i += 64) {
+                        const cplx<R> g = gc[i];
+                        gc[i] = cplx<R>{g.re * inv, g.im * inv};
+                        jc[i] = cj(jc[i]);
+                    }
+                }
+                __syncthreads();
+                Uc = G;
+                ldc = ldg;
+            }
+            if (multi) brtc_form_u<R>(Wl0, brt_stage_elems(K), S, K, q, m, Uc, ldc, kk, r, srt, phs, Ub, a.u.rs, a.u.cs, wv, lane);
+            else if (m <= 64) bsc_form_u<R, 1>(Wl, ldl, Uc, ldc, m, q, kk, r, jpl, taul, srt, phs, true, Ub, a.u.rs, a.u.cs, wv, lane);
+            else if (m <= 128) bsc_form_u<R, 2>(Wl, ldl, Uc, ldc, m, q, kk, r, jpl, taul, srt, phs, true, Ub, a.u.rs, a.u.cs, wv, lane);
+            else if (m <= 256) bsc_form_u<R, 4>(Wl, ldl, Uc, ldc, m, q, kk, r, jpl, taul, srt, phs, true, Ub, a.u.rs, a.u.cs, wv, lane);
+            else bsc_form_u<R, 8>(Wl, ldl, Uc, ldc, m, q, kk, r, jpl, taul, srt, phs, true, Ub, a.u.rs, a.u.cs, wv, lane);
+        } else {
+            if (multi) brtc_form_u<R>(Wl0, brt_stage_elems(K), S, K, q, m, J, ldj, kk, r, srt, phs, Ub, a.u.rs, a.u.cs, wv, lane);
+            else if (m <= 64) bsc_form_u<R, 1>(Wl, ldl, J, ldj, m, q, kk, r, jpl, taul, srt, phs, true, Ub, a.u.rs, a.u.cs, wv, lane);
+            else if (m <= 128) bsc_form_u<R, 2>(Wl, ldl, J, ldj, m, q, kk, r, jpl, taul, srt, phs, true, Ub, a.u.rs, a.u.cs, wv, lane);
+            else if (m <= 256) bsc_form_u<R, 4>(Wl, ldl, J, ldj, m, q, kk, r, jpl, taul, srt, phs, true, Ub, a.u.rs, a.u.cs, wv, lane);
+            else bsc_form_u<R, 8>(Wl, ldl, J, ldj, m, q, kk, r, jpl, taul, srt, phs, true, Ub, a.u.rs, a.u.cs, wv, lane);
+        }
         // ---- conj(V_c) = conj(G Sigma^-1) in place (kept columns), then vt^T = Q_R [conj(V_c); 0] conj(ph) through vt's transposed view ---
-        for (int c = wv; c < r; c += BID_WAVES) {
-            cplx<R> *gc = G + (size_t)srt[c] * ldg;
-            const R sj = sig[srt[c]], inv = sj > (R)0 ? (R)1 / sj : (R)0;
-            for (int i = lane; i < q; i += 64) {
-                const cplx<R> g = gc[i];
-                gc[i] = cplx<R>{g.re * inv, -(g.im * inv)};
+        if (!turned) {  // (false in every instance but the large one)
+            for (int c = wv; c < r; c += BID_WAVES) {
+                cplx<R> *gc = G + (size_t)srt[c] * ldg;
+                const R sj = sig[srt[c]], inv = sj > (R)0 ? (R)1 / sj : (R)0;
+                for (int i = lane; i < q; i += 64) {
+                    const cplx<R> g = gc[i];
+                    gc[i] = cplx<R>{g.re * inv, -(g.im * inv)};
+                }
             }
         }
         __syncthreads();  // phs and the scaled columns are read by other waves below
-        if (n <= 64) bsc_form_u<R, 1>(Wr, ldr, G, ldg, n, q, kk, r, jpr, taur, srt, phs, false, Vb, a.vt.cs, a.vt.rs, wv, lane);
+        if constexpr (LARGE) brlc_form_vt<R>(Wr0, brt_stage_elems(K), Sr, K, q, n, turned ? J : G, turned ? ldj : ldg, kk, r, srt, phs, Vb, a.vt.cs, a.vt.rs, wv, lane);
+        else if (n <= 64) bsc_form_u<R, 1>(Wr, ldr, G, ldg, n, q, kk, r, jpr, taur, srt, phs, false, Vb, a.vt.cs, a.vt.rs, wv, lane);
         else if (n <= 128) bsc_form_u<R, 2>(Wr, ldr, G, ldg, n, q, kk, r, jpr, taur, srt, phs, false, Vb, a.vt.cs, a.vt.rs, wv, lane);
         else if (n <= 256) bsc_form_u<R, 4>(Wr, ldr, G, ldg, n, q, kk, r, jpr, taur, srt, phs, false, Vb, a.vt.cs, a.vt.rs, wv, lane);
         else bsc_form_u<R, 8>(Wr, ldr, G, ldg, n, q, kk, r, jpr, taur, srt, phs, false, Vb, a.vt.cs, a.vt.rs, wv, lane);
@@ -1159,6 +1290,21 @@ BatchedPlan<BrccPlace> brtc_plan(int m, int n, int K) {
         [&](BrccPlace p) { return brtc_ws_elems(m, n, K, p.ld, p.l, p.r, p.v, p.g) * sizeof(cplx<R>); }, "lowrank_recompress_tall_complex_batched");
 }
 
+// large recompression: n <= BRT_H is brtc_plan (the tall complex call's plan byte for byte); above it the right factor's stage copies are always
+// in the slot, the left factor's copy by brcc_plan's rule for m <= BRT_H and staged above it, J and G by brcc_plan's rule, and the slot is
+// brlc_ws_elems
+template <typename R>
+BatchedPlan<BrccPlace> brlc_plan(int m, int n, int K) {
+    if (n <= BRT_H) return brtc_plan<R>(m, n, K);
+    const int pad = ((K + 15) / 32) * 32 + 16, odd = K | 1;
+    const bool l = m <= BRT_H;  // the only copy that may sit in LDS (for m > BRT_H the first two places repeat the next two: first fit skips nothing)
+    const BrccPlace places[] = {{l, false, true, true, pad},       {l, false, true, true, odd},      {false, false, true, true, pad},
+                                {false, false, true, true, odd},   {false, false, false, true, pad}, {false, false, false, true, odd},
+                                {false, false, false, false, K}};
+    return batched_first_fit(places, [&](BrccPlace p) { return brcc_lds_bytes<R>(m, n, K, p.ld, p.l, p.r, p.v, p.g); },
+        [&](BrccPlace p) { return brlc_ws_elems(m, n, K, p.ld, p.l, p.r, p.v, p.g) * sizeof(cplx<R>); }, "lowrank_recompress_complex_large_batched");
+}
+
 // sketched column ID: W (l x n complex) in LDS when it fits next to the chunk images, else in the workgroup's slot
 template <typename R>
 BatchedPlan<bool> bscid_plan(int l, int n) {
@@ -1216,27 +1362,37 @@ void batched_svd_c(rc_context *c, const rc_matrix &a_, int64_t abs, int32_t coun
 // The plan only moves base pointers and pitches, and no sum depends on a pitch, so it cannot change a block's bits.
 // TALL (rc_lowrank_recompress_tall_complex_batched_*): the same arguments and, for m <= 512, the same plan and the same kernel instance, so the
 // same bits at the same rate.  Above it the TALL instance runs and a slot holds every stage's copy (173 MiB at 65536 x 128 in c64), so the grid
-// is bounded a second time, by brt_grid_cap: few workgroups run there.
-template <typename R, bool TALL>
+// is bounded a second time, by brt_grid_cap: few workgroups run there.  LARGE (rc_lowrank_recompress_complex_large_batched_*): for n <= 512 the
+// tall complex call's plan and instances (brlc_plan returns that plan), so its bits at its rate; above it the LARGE instance, the slot holds the
+// right factor's stages too and the same bound applies to the whole slot.
+template <typename R, bool TALL, bool LARGE = false>
 void brcc_launch(rc_context *c, const rc_matrix &left_, int64_t lbs, const rc_matrix &mid_, int64_t mbs, const R *s, int64_t s_stride, const rc_matrix &right_,
                  int64_t rbs, const int64_t *in_ranks, int32_t count, int64_t k, double tol, const rc_matrix &u_, int64_t ubs, R *s_out, const rc_matrix &vt_,
                  int64_t vbs, int64_t *ranks) {
     const CV<R> left = view_of<R>(left_), mid = view_of<R>(mid_), right = view_of<R>(right_), u = view_of<R>(u_), vt = view_of<R>(vt_);
     const int m = (int)left.rows, n = (int)right.cols, K = (int)left.cols;
     if (count <= 0) return;
-    const auto plan = TALL ? brtc_plan<R>(m, n, K) : brcc_plan<R>(m, n, K);
+    const auto plan = LARGE ? brlc_plan<R>(m, n, K) : TALL ? brtc_plan<R>(m, n, K) : brcc_plan<R>(m, n, K);
     const BrccPlace at = plan.at;
-    auto lch = batched_prepare(c, TALL && m > BRT_H ? k_batched_recompress_c<R, TALL> : k_batched_recompress_c<R, false>,
-                               TALL ? "lowrank_recompress_tall_complex_batched" : "lowrank_recompress_batched", plan.lds, plan.ws, count);
-    char stages[24] = "";
+    void (*const kern)(BrcCArgs<R>) = LARGE && n > BRT_H       ? k_batched_recompress_c<R, TALL, LARGE>
+                                      : TALL && m > BRT_H ? k_batched_recompress_c<R, TALL>
+                                                          : k_batched_recompress_c<R, false>;
+    auto lch = batched_prepare(c, kern,
+                               LARGE  ? "lowrank_recompress_complex_large_batched"
+                               : TALL ? "lowrank_recompress_tall_complex_batched"
+                                      : "lowrank_recompress_batched",
+                               plan.lds, plan.ws, count);
+    char stages[48] = "";
     if constexpr (TALL) {
         lch.grid = brt_grid_cap(lch.grid, plan.ws);
         lch.slots = brt_grid_cap(lch.slots, plan.ws);
-        snprintf(stages, sizeof stages, "stages=%d,", brt_stages(m, K));  // inside plan=: the label keeps the family's fields
+        // inside plan=: the label keeps the family's fields
+        if (LARGE) snprintf(stages, sizeof stages, "stages=%d,rstages=%d,", brt_stages(m, K), brt_stages(n, K));
+        else snprintf(stages, sizeof stages, "stages=%d,", brt_stages(m, K));
     }
-    ProfScope ps(c, "op:batched_recompress%s<complex> %dx%d k=%d count=%d grid=%lld slots=%lld plan=%sL:%s,R:%s,V:%s,G:%s,ld=%d,kk=%d%s%s", TALL ? "_tall" : "", m,
-                 n, K, (int)count, (long long)lch.grid, (long long)lch.slots, stages, at.l ? "lds" : "ws", at.r ? "lds" : "ws", at.v ? "lds" : "ws",
-                 at.g ? "lds" : "ws", at.ld, (int)std::min<int64_t>(k, K), mid.p ? ",mid" : "", s ? ",s" : "");
+    ProfScope ps(c, "op:batched_recompress%s<complex> %dx%d k=%d count=%d grid=%lld slots=%lld plan=%sL:%s,R:%s,V:%s,G:%s,ld=%d,kk=%d%s%s",
+                 LARGE ? "_large" : TALL ? "_tall" : "", m, n, K, (int)count, (long long)lch.grid, (long long)lch.slots, stages, at.l ? "lds" : "ws",
+                 at.r ? "lds" : "ws", at.v ? "lds" : "ws", at.g ? "lds" : "ws", at.ld, (int)std::min<int64_t>(k, K), mid.p ? ",mid" : "", s ? ",s" : "");
     BrcCArgs<R> a;
     a.left = left; a.mid = mid; a.right = right; a.u = u; a.vt = vt;
     a.lbs = lbs; a.mbs = mbs; a.rbs = rbs; a.ubs = ubs; a.vbs = vbs; a.s_stride = s_stride;
@@ -1258,6 +1414,24 @@ void batched_lowrank_recompress_tall_c(rc_context *c, const rc_matrix &left, int
                                        const rc_matrix &right, int64_t rbs, const int64_t *in_ranks, int32_t count, int64_t k, double tol, const rc_matrix &u,
                                        int64_t ubs, R *s_out, const rc_matrix &vt, int64_t vbs, int64_t *ranks) {
     brcc_launch<R, true>(c, left, lbs, mid, mbs, s, s_stride, right, rbs, in_ranks, count, k, tol, u, ubs, s_out, vt, vbs, ranks);
+}
+
+template <typename R>
+void batched_lowrank_recompress_large_c(rc_context *c, const rc_matrix &left, int64_t lbs, const rc_matrix &mid, int64_t mbs, const R *s, int64_t s_stride,
+                                        const rc_matrix &right, int64_t rbs, const int64_t *in_ranks, int32_t count, int64_t k, double tol, const rc_matrix &u,
+                                        int64_t ubs, R *s_out, const rc_matrix &vt, int64_t vbs, int64_t *ranks) {
+    brcc_launch<R, true, true>(c, left, lbs, mid, mbs, s, s_stride, right, rbs, in_ranks, count, k, tol, u, ubs, s_out, vt, vbs, ranks);
+}
+
+// the complex large launcher's plan as numbers (rc_lowrank_recompress_complex_large_batched_plan): the stages of both factors at inner width K,
+// bytes of one slot, and the grid brt_grid_cap leaves of `resident` workgroups
+void batched_lowrank_recompress_large_c_plan(int64_t m, int64_t n, int64_t K, bool c64, int64_t resident, int64_t *stages_left, int64_t *stages_right,
+                                             int64_t *slot_bytes, int64_t *grid) {
+    const size_t ws = c64 ? brlc_plan<double>((int)m, (int)n, (int)K).ws : brlc_plan<float>((int)m, (int)n, (int)K).ws;
+    *stages_left = brt_stages((int)m, (int)K);
+    *stages_right = brt_stages((int)n, (int)K);
+    *slot_bytes = (int64_t)ws;
+    *grid = brt_grid_cap(resident, ws);
 }
 
 // the complex tall launcher's plan as numbers (rc_lowrank_recompress_tall_complex_batched_plan): stages at inner width K, bytes of one slot, and
@@ -1358,5 +1532,11 @@ template void batched_lowrank_recompress_tall_c<double>(rc_context *, const rc_m
 template void batched_lowrank_recompress_tall_c<float>(rc_context *, const rc_matrix &, int64_t, const rc_matrix &, int64_t, const float *, int64_t,
                                                        const rc_matrix &, int64_t, const int64_t *, int32_t, int64_t, double, const rc_matrix &, int64_t, float *,
                                                        const rc_matrix &, int64_t, int64_t *);
+template void batched_lowrank_recompress_large_c<double>(rc_context *, const rc_matrix &, int64_t, const rc_matrix &, int64_t, const double *, int64_t,
+                                                         const rc_matrix &, int64_t, const int64_t *, int32_t, int64_t, double, const rc_matrix &, int64_t,
+                                                         double *, const rc_matrix &, int64_t, int64_t *);
+template void batched_lowrank_recompress_large_c<float>(rc_context *, const rc_matrix &, int64_t, const rc_matrix &, int64_t, const float *, int64_t,
+                                                        const rc_matrix &, int64_t, const int64_t *, int32_t, int64_t, double, const rc_matrix &, int64_t, float *,
+                                                        const rc_matrix &, int64_t, int64_t *);
 
 }  // namespace rc

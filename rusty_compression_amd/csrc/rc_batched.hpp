@@ -115,10 +115,19 @@ template <typename R> void batched_lowrank_recompress_tall_c(rc_context *c, cons
                                                              int64_t k, double tol, const rc_matrix &u, int64_t ubs, R *s_out, const rc_matrix &vt, int64_t vbs,
                                                              int64_t *ranks);
 void batched_lowrank_recompress_tall_c_plan(int64_t m, int64_t n, int64_t K, bool c64, int64_t resident, int64_t *stages, int64_t *slot_bytes, int64_t *grid);
+// the same with both factors tall (m, n <= 65536; k_batched_recompress_c<R, true, true>): right^T by the same stages behind left's in the slot;
+// n <= 512 is the tall complex call bit for bit.  Its plan as numbers like the real large one's (c64: else c32)
+template <typename R> void batched_lowrank_recompress_large_c(rc_context *c, const rc_matrix &left, int64_t lbs, const rc_matrix &mid, int64_t mbs, const R *s,
+                                                              int64_t s_stride, const rc_matrix &right, int64_t rbs, const int64_t *in_ranks, int32_t count,
+                                                              int64_t k, double tol, const rc_matrix &u, int64_t ubs, R *s_out, const rc_matrix &vt, int64_t vbs,
+                                                              int64_t *ranks);
+void batched_lowrank_recompress_large_c_plan(int64_t m, int64_t n, int64_t K, bool c64, int64_t resident, int64_t *stages_left, int64_t *stages_right,
+                                             int64_t *slot_bytes, int64_t *grid);
 // the argument checks of rc_lowrank_recompress_batched_* and rc_lowrank_recompress_complex_batched_* (rc_batched_api.hip), one for every scalar type
 // like those above; the caller returns when count == 0.  tall: the bound m <= 65536 under rc_lowrank_recompress_tall_batched_*'s name (RC_TALL) or
-// rc_lowrank_recompress_tall_complex_batched_*'s (RC_TALL_COMPLEX); RC_LARGE: m, n <= 65536 under rc_lowrank_recompress_large_batched_*'s
-enum { RC_NOT_TALL = 0, RC_TALL = 1, RC_TALL_COMPLEX = 2, RC_LARGE = 3 };
+// rc_lowrank_recompress_tall_complex_batched_*'s (RC_TALL_COMPLEX); RC_LARGE: m, n <= 65536 under rc_lowrank_recompress_large_batched_*'s, and
+// RC_LARGE_COMPLEX the same under rc_lowrank_recompress_complex_large_batched_*'s
+enum { RC_NOT_TALL = 0, RC_TALL = 1, RC_TALL_COMPLEX = 2, RC_LARGE = 3, RC_LARGE_COMPLEX = 4 };
 void check_lowrank_recompress_batched(const rc_matrix &left, const rc_matrix &mid, const rc_matrix &right, int32_t count, int64_t k, double tol,
                                       const rc_matrix &u, int64_t ubs, const void *s_out, const rc_matrix &vt, int64_t vbs, const int64_t *ranks,
                                       int tall = RC_NOT_TALL);

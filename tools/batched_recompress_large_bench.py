@@ -18,7 +18,13 @@ At n <= 512 the same arguments also go through rc_lowrank_recompress_tall_batche
 is recorded, with a check that the bits agree.  Writes profiles/batched_recompress_large_bench.json unless --out names another file.  Not used
 by the tests or by bench.py.
 
-    python tools/batched_recompress_large_bench.py [--repeats 5] [--shapes 0,1,2,3] [--out path.json]
+--complex measures rc_lowrank_recompress_complex_large_batched_c64 / _c32 at the same shapes with complex factors (c64 where the real rows
+are f64, c32 where f32) and writes profiles/batched_recompress_large_complex_bench.json.  Per both-tall shape: the in-library composition in
+its complex form (two rc_lowrank_recompress_tall_complex_batched_* calls with right = I, rc_svd_rank_batched_c64 / _c32 on the core, three
+torch.bmm) and the real large call on the real parts of the same factors, in the same process, with the ratio of the two times.  At n <= 512:
+the ratio to rc_lowrank_recompress_tall_complex_batched_*, with the check of the bits.
+
+    python tools/batched_recompress_large_bench.py [--complex] [--repeats 5] [--shapes 0,1,2,3] [--out path.json]
 """
 import argparse
 import json
@@ -42,6 +48,7 @@ SHAPES = [  # (count, m, n, K, k, dtype)
     (2048, 2048, 256, 32, 16, torch.float64),
 ]
 QR_LIMIT_S = 60.0
+COMPLEX_OF = {torch.float64: torch.complex128, torch.float32: torch.complex64}
 
 
 def spread(prefix, t):
@@ -49,14 +56,88 @@ def spread(prefix, t):
     return {prefix + "_s": med, prefix + "_s_min": lo, prefix + "_s_max": hi}
 
 
+def main_complex(args):
+    """The rows of --complex (see the module docstring)."""
+    out_path = args.out or os.path.join(ROOT, "profiles", "batched_recompress_large_complex_bench.json")
+    results = []
+    for si in [int(x) for x in (args.shapes or ",".join(str(i) for i in range(len(SHAPES)))).split(",")]:
+        count, m, n, kin, k, rdtype = SHAPES[si]
+        dtype = COMPLEX_OF[rdtype]
+        g = torch.Generator(device="cuda").manual_seed(86420 + si)
+        left = (torch.randn(count, m, kin, generator=g, device="cuda", dtype=torch.complex128) / m ** 0.5).to(dtype)
+        right = (torch.randn(count, kin, n, generator=g, device="cuda", dtype=torch.complex128) / n ** 0.5).to(dtype)
+        s = torch.logspace(0, -6, kin // 2, device="cuda", dtype=torch.float64).repeat(2).to(rdtype).expand(count, kin).contiguous()
+        fn = lambda: rc.lowrank_recompress_large_batched_complex(left, right, k, 0.0, s=s)  # noqa: E731
+        (u, sv, vt, ranks), label = batched_launch(fn)  # warm-up (code objects, workspace) and the plan
+        torch.cuda.synchronize()
+        t_large = timed(fn, args.repeats)
+        plan = label["plan"].split(",")
+        row = dict(count=count, m=m, n=n, K=kin, k=k, dtype=str(dtype).replace("torch.", ""), stages=int(plan[0].split("=")[1]),
+                   rstages=int(plan[1].split("=")[1]), plan=",".join(plan[2:]), grid=label["grid"], slots=label["slots"],
+                   **spread("recompress_large", t_large), blocks_per_s=count / t_large[0])
+        print(json.dumps(row), flush=True)
+
+        # the real large call on the real parts of the same factors, from the same process
+        rl, rr = left.real.contiguous(), right.real.contiguous()
+        rfn = lambda: rc.lowrank_recompress_large_batched(rl, rr, k, 0.0, s=s)  # noqa: E731
+        rfn()
+        torch.cuda.synchronize()
+        t_real = timed(rfn, args.repeats)
+        row.update(**spread("real_large_call", t_real), real_large_call_blocks_per_s=count / t_real[0], time_vs_real_large_call=t_large[0] / t_real[0])
+        del rl, rr
+
+        if n > 512:
+            eye = torch.eye(kin, device="cuda", dtype=dtype).expand(count, kin, kin)
+            right_t = right.mT  # n x K as a strided view, the plain transpose: no copy, nothing conjugated
+
+            def in_library():
+                ul, sl, vl, _ = rc.lowrank_recompress_tall_batched_complex(left, eye, kin)       # left = ul diag(sl) vl
+                ur, sr, vr, _ = rc.lowrank_recompress_tall_batched_complex(right_t, eye, kin)    # right = vr^T diag(sr) ur^T
+                core = torch.bmm(sl[:, :, None] * vl * s[:, None, :], vr.mT * sr[:, None, :])
+                cu, cs, cvt, cr = rc.svd_rank_batched_complex(core, k)
+                return torch.bmm(ul, cu), cs, torch.bmm(cvt, ur.mT), cr
+
+            _, cs, _, _ = in_library()
+            torch.cuda.synchronize()
+            t_lib = timed(in_library, args.repeats)
+            row.update(in_library_composition="2 x lowrank_recompress_tall_batched_complex (right = I) + svd_rank_batched_complex + 3 x torch.bmm",
+                       **spread("in_library", t_lib), in_library_blocks_per_s=count / t_lib[0], speedup_vs_in_library=t_lib[0] / t_large[0],
+                       faster_than_in_library_beyond_spread=bool(t_lib[0] - t_large[0] > (t_lib[2] - t_lib[1]) + (t_large[2] - t_large[1])),
+                       max_abs_sval_diff_vs_in_library=float((sv[:, :k] - cs[:, :k]).abs().max()), max_sval=float(cs[:, 0].max()))
+            del cs, eye
+        else:
+            pfn = lambda: rc.lowrank_recompress_tall_batched_complex(left, right, k, 0.0, s=s)  # noqa: E731
+            (pu, ps, pvt, pr), plabel = batched_launch(pfn)
+            torch.cuda.synchronize()
+            t_tall = timed(pfn, args.repeats)
+            t_again = timed(fn, args.repeats)  # the large call again, after the tall one: the same cache state on both sides
+            same = all(torch.equal(a, b) for a, b in zip((u, sv, vt, ranks), (pu, ps, pvt, pr)))
+            row.update(tall_call_plan=plabel["plan"], **spread("tall_call", t_tall), **spread("recompress_large_again", t_again),
+                       rate_vs_tall_call=t_tall[0] / t_again[0], same_bits_as_tall_call=bool(same))
+            if not same:
+                raise SystemExit("the bits differ from rc_lowrank_recompress_tall_complex_batched_*'s at n <= 512")
+            del pu, ps, pvt, pr
+        results.append(row)
+        print(json.dumps(row), flush=True)
+        del left, right, s, u, sv, vt, ranks
+        torch.cuda.empty_cache()
+    out = dict(tool="tools/batched_recompress_large_bench.py --complex", device=torch.cuda.get_device_name(0), repeats=args.repeats, results=results)
+    with open(out_path, "w") as f:
+        json.dump(out, f, indent=1)
+    print("wrote", out_path)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--complex", action="store_true", help="the complex twin, rc_lowrank_recompress_complex_large_batched_*")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--shapes", default=None)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("needs an MI355X")
+    if args.complex:
+        return main_complex(args)
     out_path = args.out or os.path.join(ROOT, "profiles", "batched_recompress_large_bench.json")
     results = []
     for si in [int(x) for x in (args.shapes or ",".join(str(i) for i in range(len(SHAPES)))).split(",")]:
