@@ -500,11 +500,17 @@ rc_status rc_batch_column_id_f32(rc_context *const *ctxs, int32_t nctx, const rc
  * subnormal or zero square, as it is below every accuracy of the result).  Outside the domain: values unspecified, but contained in
  * the block's outputs as for non-finite input (permutations still permutations, 0 <= r <= k); a block with a non-finite entry is
  * not normalised.  The same paragraph holds for rc_two_sided_id_rank_batched_*, rc_svd_rank_batched_*,
- * rc_sketch_column_id_rank_batched_* / _complex_batched_* and rc_sketch_range_step_batched_*, which refer to it.  The recompression
- * (rc_lowrank_recompress_*), apply, residual and dense entry points make no such promise yet; the residual calls state their own.
- * (The real rc_lowrank_recompress_batched_f64 / _f32 and _tall_batched_f64 / _f32 do load `left` and `right` times exact powers of two
- * and give s the product back, which is what the power-iterated chains on rc_sketch_range_step_batched_* rest on; mid and s are taken
- * as they stand, the complex twins are unchanged, and no domain is stated for either yet.) */
+ * rc_sketch_column_id_rank_batched_* / _complex_batched_* and rc_sketch_range_step_batched_*, which refer to it.
+ * The recompressions (every rc_lowrank_recompress_*batched_* entry point, real and complex) are inside it, per operand: each of left,
+ * mid, s and right that is present has its largest real or imaginary part in the range above, and so has the sum of their exponents,
+ * which is the exponent s_out is written with.  Each operand is loaded times the exact power of two that brings that part to [1, 2);
+ * the QRs, the core, the iteration and the rank rule run on the normalised copies and s_out takes the product of the four powers
+ * back.  Scaling any operand by 2^e scales s_out by 2^e and leaves u, vt and ranks unchanged, bit for bit under the condition above;
+ * so does a set with every operand extreme and a product at unit scale (left and mid times 2^e, s and right times 2^-e).
+ * rc_lowrank_residual_batched_* is inside it for err and nrm, which carry 2^e with a and the factors' product (see its Arithmetic
+ * paragraph; e is plain arithmetic and carries 2^e exactly).  Still outside, the caller's: the apply and dense entry points, and the
+ * intermediate products of the residual's rebuild, diag(s) right and mid (diag(s) right), which are formed as the operands stand
+ * and overflow or vanish for a split-scale factor set whose product would be in range. */
 rc_status rc_column_id_rank_batched_f64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks);
 rc_status rc_column_id_rank_batched_f32(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks);
 rc_status rc_column_id_rank_batched_c64(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind, int64_t *ranks);
@@ -893,8 +899,8 @@ rc_status rc_sketch_column_id_rank_complex_batched_c32(rc_context *ctx, rc_matri
  * imaginary parts of y, q and p are exactly zero (q and p need not equal the real call's bits).  Non-finite input stays inside its block's
  * outputs, with 0 <= ranks[i] <= l.
  * Input scale: the paragraph of rc_column_id_rank_batched_* applies to this call (the working copy of y^T is brought to [1, 2) by an exact
- * power of two before the QR): y and p carry 2^e, q and ranks do not.  The complex recompressions do not normalise their inputs, so the
- * equivariance of the chains built on this call with them is not promised.
+ * power of two before the QR): y and p carry 2^e, q and ranks do not.  The complex recompressions normalise their operands as the real
+ * ones do, so the chains built on this call with them are equivariant in the same way.
  * Domain: 1 <= n <= 512, 1 <= m <= 65536, 1 <= l <= min(128, m, n), count >= 0; batch strides of 0 are legal for a and omega.  Outputs must not
  * overlap inputs or one another.  RC_INVALID_ARGUMENT as for the real call, under the name sketch_range_step_complex_batched; a null ctx is
  * rejected before a device is touched.  No host synchronisation; workspace bounded by the grid, not by count.
@@ -921,8 +927,12 @@ rc_status rc_sketch_range_step_complex_batched_c32(rc_context *ctx, rc_matrix a,
  * v_mfma_f32_16x16x4_f32 (exact f32, no reduced precision).  W = right itself when there is neither mid nor s; otherwise
  * W = mid[:r, :r] (diag(s[:r]) right[:r, :]) with diag(s) right rounded once per element and the mid product summed in ascending inner index by
  * plain FMAs.  The residual element is a - Ah, one rounding.  Squares of e and of a are accumulated in f64 for both types, in a fixed order that
- * depends on (m, n) alone, and the root is rounded to the output type.  There is no scaling: entries below about 1e-154 in magnitude contribute
- * nothing to err and nrm, and entries above about 1e154 overflow them to inf (e is unaffected).
+ * depends on (m, n) alone, and the root is rounded to the output type.  Scaling, f64 / c64: the three accumulators of LAPACK 3.10's ?lassq.  A
+ * component of magnitude in [2^-511, 2^486) is squared as it stands, a larger one times 2^-538, a smaller one times 2^537; the three sums run
+ * apart in the same fixed order and are combined once per block, so neither err nor nrm overflows or vanishes while the norm itself is a normal
+ * number, and a block with every component in the middle range keeps the bits of the single sum.  A block that straddles a threshold is summed
+ * in another grouping than its scaled copy: err and nrm of 2^e a are 2^e times those of a to rounding, not bit for bit.  f32 / c32: the single f64
+ * sum, which the square of an f32 component (2^-298 .. 2^256) cannot leave.  e is unaffected.
  * Complex arithmetic.  The same MFMAs on the real and imaginary parts as separate real operands: per element each of Re Ah and Im Ah is one
  * accumulator chain from zero over ascending l, four terms per instruction, and within a step of four the Re chain takes the products
  * Re(left) Re(W), then (-Im(left)) Im(W), the Im chain Re(left) Im(W), then Im(left) Re(W); the negation is exact.  diag(s) right is one rounding

@@ -631,7 +631,13 @@ def lowrank_recompress_batched(left: torch.Tensor, right: torch.Tensor, k: int, 
     diag(s[i][:q]) right[i][:q] (absent factors omitted; nothing at an index >= q is read).  Returns U [count, m, kk], S [count, K]
     (the q singular values of A_i, descending, then zeros), Vt [count, kk, n] and the new ranks [count], kk = min(k, K): the rank of a
     block is the first j < min(kk, q) with s_j == 0 or s_j / s_0 < tol, else min(kk, q); columns of U and rows of Vt past it are zero
-    and the largest-|.| entry of each kept column of U is positive.  Complex data raises TypeError (see lowrank_recompress_batched_complex)."""
+    and the largest-|.| entry of each kept column of U is positive.  Complex data raises TypeError (see lowrank_recompress_batched_complex).
+
+    Input scale (this call and every other recompression of this module, real and complex): each operand present may have its largest
+    component anywhere in [2^-100, 2^100] (float32 / complex64) or [2^-900, 2^900] (float64 / complex128), and so may the sum of the
+    operands' exponents.  Every operand is normalised by an exact power of two on loading and S takes the product back: scaling an operand
+    by 2^e scales S by 2^e and leaves U, Vt and the ranks unchanged bit for bit, so the C of a column ID, the X of a two-sided ID and the
+    s of an SVD of a block at 2^e recompress as those of the unit-scale block."""
     return _lowrank_recompress_batched("lowrank_recompress_batched", False, left, right, k, tol, mid, s, ranks)
 
 
@@ -897,7 +903,12 @@ def lowrank_residual_batched(a: torch.Tensor, left: torch.Tensor, right: torch.T
     or None (every rank is K); float64 or float32 device tensors of one dtype, any strides (a stride-0 batch dimension shares one operand);
     m <= 65536, n <= 512, K <= 128.  With r = ranks[i] clamped to [0, K] and Ah_i = left[i][:, :r] mid[i][:r, :r] diag(s[i][:r]) right[i][:r]
     (absent factors omitted; nothing at an index >= r is read), returns err [count] = ||a_i - Ah_i||_F and nrm [count] = ||a_i||_F, and with
-    want_residual also e [count, m, n] = a_i - Ah_i.  Complex data (see lowrank_residual_batched_complex) and mismatched dtypes raise TypeError."""
+    want_residual also e [count, m, n] = a_i - Ah_i.  Complex data (see lowrank_residual_batched_complex) and mismatched dtypes raise TypeError.
+
+    Input scale: err and nrm neither overflow nor vanish for blocks with entries anywhere in the range of the batched compressors (2^+-900
+    in float64 / complex128: the squares are binned as LAPACK's ?lassq bins them; float32 / complex64 squares are taken in float64).  The
+    rebuild's intermediate products diag(s) right and mid (diag(s) right) are formed as the operands stand: a factor set whose
+    intermediates leave the range although its product does not stays the caller's to rescale."""
     return _lowrank_residual_batched("lowrank_residual_batched", False, a, left, right, mid, s, ranks, want_residual)
 
 

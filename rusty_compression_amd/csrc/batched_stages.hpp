@@ -482,6 +482,31 @@ __device__ __forceinline__ bool bsv_jacobi(E *G, int ldg, E *J, int ldj, int N, 
     return false;
 }
 
+// ---- the exponent of an operand of the recompressions --------------------------------------------------------------------------------------
+// The exponent of an operand before it is loaded (block_pow2_exponent over at(i, c), i < rows, c < q, read as bid_fill reads it; for complex
+// elements over the larger of the two parts): the loads multiply every entry by 2^-e, so that the norms, both cores and the Jacobi run at
+// unit scale as in k_batched_svd, and the singular values take 2^(eL + eM + eS + eR) back, one exponent per operand (left, mid, s, right).
+// One more read of the operand (the second one hits L2); with e = 0 (a zero or non-finite operand) every entry is multiplied by 1 and the
+// bits are the unscaled ones.  stage: four elements no thread reads before the next barrier.
+template <typename R, typename At>
+__device__ __forceinline__ int brc_exponent(int rows, int q, bool lanes_on_rows, At at, R *stage, int wv, int lane) {
+    R mx = 0;
+    if (lanes_on_rows) {
+        for (int c = wv; c < q; c += BID_WAVES)
+            for (int i = lane; i < rows; i += 64) mx = max(mx, pow2_key_max(at(i, c)));
+    } else {
+        // lanes along c: a wave takes 64 / qs rows per pass, qs the power of two >= min(q, 64), so that a narrow factor keeps every lane
+        // loading (a maximum does not depend on the order it is taken in)
+        int qs = 1;
+        while (qs < q && qs < 64) qs <<= 1;
+        const int rpw = 64 / qs, lr = lane / qs, lc = lane - lr * qs;
+#pragma unroll 4
+        for (int i = wv * rpw + lr; i < rows; i += BID_WAVES * rpw)
+            for (int c = lc; c < q; c += qs) mx = max(mx, pow2_key_max(at(i, c)));
+    }
+    return __builtin_amdgcn_readfirstlane(block_pow2_exponent(mx, stage, wv, lane));  // uniform by construction: kept in a scalar register
+}
+
 // ---- the stack load of the tall recompressions --------------------------------------------------------------------------------------------
 // one stage's stack into W (pitch ldw, hs rows): rows 0 .. top - 1 of position p's column are R[0 .. p, p] of the previous stage's copy Wp
 // (the same pitch and physical columns) and zeros, rows top .. hs - 1 are at(i - top, c); then the real column norms by position (bid_norms'

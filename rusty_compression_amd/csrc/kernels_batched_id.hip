@@ -569,23 +569,7 @@ __device__ __forceinline__ void brl_form_vt(const T *stage0, size_t se, int S, i
     }
 }
 
-// The exponent of a factor before it is loaded (block_pow2_exponent over at(i, c), i < rows, c < q, read as bid_fill reads it): the loads
-// below multiply every entry by 2^-e, so that the norms, both cores and the Jacobi run at unit scale as in k_batched_svd, and the
-// singular values take 2^(eL + eR) back.  One more read of the factor (the second one hits L2); with e = 0 (a zero or non-finite
-// factor) every entry is multiplied by 1 and the bits are the unscaled ones.  stage: four elements no thread reads before the next barrier.
-template <typename T, typename At>
-__device__ __forceinline__ int brc_exponent(int rows, int q, bool lanes_on_rows, At at, T *stage, int wv, int lane) {
-    T mx = 0;
-    if (lanes_on_rows) {
-        for (int c = wv; c < q; c += BID_WAVES)
-            for (int i = lane; i < rows; i += 64) mx = max(mx, pow2_key(at(i, c)));
-    } else {
-        for (int i = wv; i < rows; i += BID_WAVES)
-            for (int c = lane; c < q; c += 64) mx = max(mx, pow2_key(at(i, c)));
-    }
-    return block_pow2_exponent(mx, stage, wv, lane);
-}
-
+// (brc_exponent, the exponent of an operand before it is loaded, is in batched_stages.hpp, shared with the complex kernel.)
 // TALL = false: rc_lowrank_recompress_batched_*.  TALL = true: rc_lowrank_recompress_tall_batched_*, the left factor by stages (see above).
 // LARGE (with TALL): rc_lowrank_recompress_large_batched_* for n > BRT_H, the right factor by stages too (see "both factors tall"); the
 // launcher sends n <= BRT_H to the TALL instance, so this one carries neither the one-stage path of the right factor nor bsv_form_u for vt
@@ -640,7 +624,13 @@ __global__ __launch_bounds__(BID_THREADS) void k_batched_recompress(BrcArgs<T> a
         // the factors' exponents (red[4..7], then red[0..3]: bid_qrcp writes red only behind the loads' barriers)
         const int el = brc_exponent(m, q, a.left.rs <= a.left.cs, [&](int i, int c) { return L[(int64_t)i * a.left.rs + c * a.left.cs]; }, red + 4, wv, lane);
         const int er = brc_exponent(n, q, a.right.cs <= a.right.rs, [&](int i, int c) { return R[c * a.right.rs + i * a.right.cs]; }, red, wv, lane);
-        const T scl = ldexp((T)1, -el), scr = ldexp((T)1, -er);
+        // mid's and s's (q x q and q elements): they enter T1 times 2^-em and 2^-es, so an X or an s that carries a block's scale meets the
+        // normalised factors at unit scale as well, and a factor set with every operand extreme and a unit-scale product stays in range
+        const T *__restrict__ Mb = a.mid.p ? a.mid.p + (int64_t)b * a.mbs : nullptr;
+        const T *__restrict__ Sb = a.s ? a.s + (int64_t)b * a.s_stride : nullptr;
+        const int em = Mb ? brc_exponent(q, q, a.mid.rs <= a.mid.cs, [&](int i, int c) { return Mb[(int64_t)i * a.mid.rs + c * a.mid.cs]; }, red + 4, wv, lane) : 0;
+        const int es = Sb ? brc_exponent(q, 1, true, [&](int i, int) { return Sb[i]; }, red, wv, lane) : 0;
+        const T scl = ldexp((T)1, -el), scr = ldexp((T)1, -er), scm = ldexp((T)1, -em), scs = ldexp((T)1, -es);
         [[maybe_unused]] int S = 1;
         if constexpr (TALL) {
             S = brt_stages(m, q);
@@ -688,8 +678,6 @@ __global__ __launch_bounds__(BID_THREADS) void k_batched_recompress(BrcArgs<T> a
         for (int j = tid; j < q; j += BID_THREADS) { ipl[jpl[j]] = j; ipr[jpr[j]] = j; }
         __syncthreads();
         // ---- T1 = mid diag(s) Rr^T in J's place ----------------------------------------------------------------------------------------
-        const T *__restrict__ Mb = a.mid.p ? a.mid.p + (int64_t)b * a.mbs : nullptr;
-        const T *__restrict__ Sb = a.s ? a.s + (int64_t)b * a.s_stride : nullptr;
         for (int idx = tid; idx < q * q; idx += BID_THREADS) {
             const int ai = idx / q, j = idx - ai * q;
             T acc;
@@ -698,12 +686,12 @@ __global__ __launch_bounds__(BID_THREADS) void k_batched_recompress(BrcArgs<T> a
                 const T *mr = Mb + (int64_t)ai * a.mid.rs;
                 for (int bb = 0; bb < q; ++bb) {
                     const T rv = j <= ipr[bb] ? Wr[(size_t)bb * ldr + j] : (T)0;
-                    const T mv = Sb ? mr[(int64_t)bb * a.mid.cs] * Sb[bb] : mr[(int64_t)bb * a.mid.cs];
+                    const T mv = Sb ? (mr[(int64_t)bb * a.mid.cs] * scm) * (Sb[bb] * scs) : mr[(int64_t)bb * a.mid.cs] * scm;
                     acc = fma(mv, rv, acc);
                 }
             } else {
                 const T rv = j <= ipr[ai] ? Wr[(size_t)ai * ldr + j] : (T)0;
-                acc = Sb ? Sb[ai] * rv : rv;
+                acc = Sb ? (Sb[ai] * scs) * rv : rv;
             }
             J[(size_t)ai * ldj + j] = acc;
         }
@@ -747,7 +735,7 @@ __global__ __launch_bounds__(BID_THREADS) void k_batched_recompress(BrcArgs<T> a
                 pos += (kj > ki || (kj == ki && j < i)) ? 1 : 0;
             }
             srt[pos] = i;
-            sb[pos] = ldexp(sig[i], el + er);  // the factors were loaded as 2^-el left and 2^-er right
+            sb[pos] = ldexp(sig[i], el + er + em + es);  // the operands entered as 2^-el left, 2^-em mid, 2^-es s and 2^-er right
         }
         __syncthreads();
         // ---- rank: the first j < min(kk, q) with s_j == 0 or (tol > 0 and s_j / s_0 < tol), else min(kk, q) -------------------------

@@ -670,6 +670,8 @@ __device__ __forceinline__ void brlc_form_vt(const cplx<R> *stage0, size_t se, i
 // one-stage path of the right factor nor bsc_form_u for vt.  Both of its instances are built for one wave per SIMD: the c64 one for the reason
 // above, and the c32 one because it carries both left paths and spills three registers under the bound of two waves (12 bytes of scratch per
 // thread; none with room), while its slot (both factors' stages) leaves one workgroup per CU at the shapes it is for either way.
+// With the operands' exponents and scales the c32 tall instance spills 12 bytes per lane under its bound of two waves (measured 1.02 of its
+// former time at 1024 x 512, K = 64), and the c64 tall instance, without scratch, measures 1.4 - 1.5 of its former time: DESIGN.md 7r-2.
 template <typename R, bool TALL, bool LARGE = false>
 __global__ __launch_bounds__(BID_THREADS, ((TALL && sizeof(R) == 8) || LARGE) ? 1 : 2) void k_batched_recompress_c(BrcCArgs<R> a) {
     static_assert(TALL || !LARGE, "the large instance is the tall one with a staged right factor");
@@ -717,7 +719,13 @@ __global__ __launch_bounds__(BID_THREADS, ((TALL && sizeof(R) == 8) || LARGE) ? 
         const cplx<R> *__restrict__ Rt = a.right.p + (int64_t)b * a.rbs;
         cplx<R> *Wl = Wl0;  // the copy the core and U read: the last stage's
         cplx<R> *Wr = Wr0;  // likewise for T1 (set per block: a workgroup's next block starts at stage 0 again)
+        // the operands' exponents, as in k_batched_recompress (red[4..7] and red[0..3] in turn: bid_qrcp writes red only behind the loads'
+        // barriers): every operand enters at unit scale and the singular values take 2^(el + em + es + er) back.  mid's and s's are taken
+        // behind the two QRs, where they are first needed (red is free again behind the barrier there)
+        const int el = brc_exponent(m, q, a.left.rs <= a.left.cs, [&](int i, int c) { return L[(int64_t)i * a.left.rs + c * a.left.cs]; }, red + 4, wv, lane);
+        const int er = brc_exponent(n, q, a.right.cs <= a.right.rs, [&](int i, int c) { return Rt[c * a.right.rs + (int64_t)i * a.right.cs]; }, red, wv, lane);
         [[maybe_unused]] int S = 1;
+        const R scl = ldexp((R)1, -el);  // each scale is made where it is used
         if (multi) {
             S = brt_stages(m, q);  // >= 2: m > BRT_H
             const size_t se = brt_stage_elems(K);
@@ -727,17 +735,18 @@ __global__ __launch_bounds__(BID_THREADS, ((TALL && sizeof(R) == 8) || LARGE) ? 
                 const int hs = top + min(BRT_H - top, m - base);
                 cplx<R> *Ws = Wl0 + (size_t)s * se, *ts = Ws + (size_t)BRT_H * K;
                 brt_stack_load(Ws, ldl, Ws - (s ? se : 0), top, hs, q, a.left.rs <= a.left.cs,
-                                [&](int i, int c) { return L[(int64_t)(base + i) * a.left.rs + c * a.left.cs]; }, vn1, vn2, jpl, wv, lane);
+                                [&](int i, int c) { return escale(L[(int64_t)(base + i) * a.left.rs + c * a.left.cs], scl); }, vn1, vn2, jpl, wv, lane);
                 bid_qrcp<cplx<R>, true>(Ws, ldl, hs, q, q, 0.0, jpl, vn1, vn2, red, tid, wv, lane, ts);
                 int *js = reinterpret_cast<int *>(ts + K);  // the stage's pivots beside its taus; jpl goes on as the next stage's starting order
                 for (int j = tid; j < q; j += BID_THREADS) js[j] = jpl[j];
                 Wl = Ws;
             }
         } else {
-            bid_load(Wl, ldl, m, q, a.left.rs <= a.left.cs, [&](int i, int c) { return L[i * a.left.rs + c * a.left.cs]; }, vn1, vn2, jpl, wv, lane);
+            bid_load(Wl, ldl, m, q, a.left.rs <= a.left.cs, [&](int i, int c) { return escale(L[i * a.left.rs + c * a.left.cs], scl); }, vn1, vn2, jpl, wv, lane);
             bid_qrcp<cplx<R>, true>(Wl, ldl, m, q, q, 0.0, jpl, vn1, vn2, red, tid, wv, lane, taul);
         }
         [[maybe_unused]] int Sr = 1;
+        const R scr = ldexp((R)1, -er);
         if constexpr (LARGE) {  // the left factor's stage loop on right[:q, :]^T, every stage in the slot
             Sr = brt_stages(n, q);  // >= 2: n > BRT_H
             const size_t se = brt_stage_elems(K);
@@ -747,14 +756,14 @@ __global__ __launch_bounds__(BID_THREADS, ((TALL && sizeof(R) == 8) || LARGE) ? 
                 const int hs = top + min(BRT_H - top, n - base);
                 cplx<R> *Ws = Wr0 + (size_t)s * se, *ts = Ws + (size_t)BRT_H * K;
                 brt_stack_load(Ws, ldr, Ws - (s ? se : 0), top, hs, q, a.right.cs <= a.right.rs,
-                                [&](int i, int c) { return Rt[c * a.right.rs + (int64_t)(base + i) * a.right.cs]; }, vn1, vn2, jpr, wv, lane);
+                                [&](int i, int c) { return escale(Rt[c * a.right.rs + (int64_t)(base + i) * a.right.cs], scr); }, vn1, vn2, jpr, wv, lane);
                 bid_qrcp<cplx<R>, true>(Ws, ldr, hs, q, q, 0.0, jpr, vn1, vn2, red, tid, wv, lane, ts);
                 int *js = reinterpret_cast<int *>(ts + K);
                 for (int j = tid; j < q; j += BID_THREADS) js[j] = jpr[j];
                 Wr = Ws;
             }
         } else {
-            bid_load(Wr, ldr, n, q, a.right.cs <= a.right.rs, [&](int i, int c) { return Rt[c * a.right.rs + i * a.right.cs]; }, vn1, vn2, jpr, wv, lane);
+            bid_load(Wr, ldr, n, q, a.right.cs <= a.right.rs, [&](int i, int c) { return escale(Rt[c * a.right.rs + i * a.right.cs], scr); }, vn1, vn2, jpr, wv, lane);
             bid_qrcp<cplx<R>, true>(Wr, ldr, n, q, q, 0.0, jpr, vn1, vn2, red, tid, wv, lane, taur);
         }
         for (int j = tid; j < q; j += BID_THREADS) { ipl[jpl[j]] = j; ipr[jpr[j]] = j; }
@@ -772,6 +781,9 @@ __global__ __launch_bounds__(BID_THREADS, ((TALL && sizeof(R) == 8) || LARGE) ? 
         // ---- T1 = mid diag(s) Rr^T in J's place ----------------------------------------------------------------------------------------
         const cplx<R> *__restrict__ Mb = a.mid.p ? a.mid.p + (int64_t)b * a.mbs : nullptr;
         const R *__restrict__ Sb = a.s ? a.s + (int64_t)b * a.s_stride : nullptr;
+        const int em = Mb ? brc_exponent(q, q, a.mid.rs <= a.mid.cs, [&](int i, int c) { return Mb[(int64_t)i * a.mid.rs + c * a.mid.cs]; }, red + 4, wv, lane) : 0;
+        const int es = Sb ? brc_exponent(q, 1, true, [&](int i, int) { return Sb[i]; }, red, wv, lane) : 0;
+        const R scm = ldexp((R)1, -em), scs = ldexp((R)1, -es);
         for (int idx = tid; idx < q * q; idx += BID_THREADS) {
             const int ai = idx / q, j = idx - ai * q;
             cplx<R> acc;
@@ -780,14 +792,14 @@ __global__ __launch_bounds__(BID_THREADS, ((TALL && sizeof(R) == 8) || LARGE) ? 
                 const cplx<R> *mr = Mb + (int64_t)ai * a.mid.rs;
                 for (int bb = 0; bb < q; ++bb) {
                     const cplx<R> rv = j <= ipr[bb] ? Wr[(size_t)bb * ldr + j] : czero<R>();
-                    cplx<R> mv = mr[(int64_t)bb * a.mid.cs];
-                    if (Sb) { const R sv = Sb[bb]; mv = cplx<R>{mv.re * sv, mv.im * sv}; }
+                    cplx<R> mv = escale(mr[(int64_t)bb * a.mid.cs], scm);
+                    if (Sb) { const R sv = Sb[bb] * scs; mv = cplx<R>{mv.re * sv, mv.im * sv}; }
                     cfma(mv, rv, acc);
                 }
             } else {
                 const cplx<R> rv = j <= ipr[ai] ? Wr[(size_t)ai * ldr + j] : czero<R>();
                 acc = rv;
-                if (Sb) { const R sv = Sb[ai]; acc = cplx<R>{sv * rv.re, sv * rv.im}; }
+                if (Sb) { const R sv = Sb[ai] * scs; acc = cplx<R>{sv * rv.re, sv * rv.im}; }
             }
             J[(size_t)ai * ldj + j] = acc;
         }
@@ -846,7 +858,7 @@ __global__ __launch_bounds__(BID_THREADS, ((TALL && sizeof(R) == 8) || LARGE) ? 
                 pos += (kj > ki || (kj == ki && j < i)) ? 1 : 0;
             }
             srt[pos] = i;
-            sb[pos] = sig[i];
+            sb[pos] = ldexp(sig[i], el + er + em + es);  // the operands entered as 2^-el left, 2^-em mid, 2^-es s and 2^-er right
         }
         __syncthreads();
         // ---- rank: the first j < min(kk, q) with s_j == 0 or (tol > 0 and s_j / s_0 < tol), else min(kk, q) -------------------------

@@ -28,6 +28,10 @@
 // order; the 64 lanes are then summed by a butterfly and the four waves as (w0 + w1) + (w2 + w3).  The longest chain of additions a
 // sum passes through is L(m, n) = 8 ceil(m / 32) ceil(n / 64) + 8.  Every order above is a function of (m, n, r) alone, which is what
 // the bit-independence clause of the contract rests on.
+// Scale (f64): a thread watches the exponent fields of the 8 elements it squares in a tile (ssq_watch, rc_device.hpp); while all lie in
+// [2^-511, 2^486) the two sums above are the whole story, bit for bit.  A tile with a component outside takes its squares back and bins them
+// as ?lassq does (ssq_add: med, big times 2^-538, sml times 2^537), each bin summed over the lanes and waves in the order above and the
+// three combined once per block (ssq_norm).  The f32 instance keeps the single f64 sums: an f32 square cannot leave the f64 range.
 #include <algorithm>
 
 #include "rc_batched_launch.hpp"
@@ -77,6 +81,9 @@ struct BrArgs {
 
 template <typename T>
 __global__ __launch_bounds__(BR_THREADS) void k_batched_residual(BrArgs<T> g) {
+    // f64 squares leave the range inside the domain of the compressors: ?lassq's three accumulators (rc_device.hpp).  f32 keeps the single
+    // f64 accumulator: the square of an f32 component lies in [2^-298, 2^256] and cannot overflow or vanish there.
+    constexpr bool WIDE = sizeof(T) == 8;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int m = (int)g.a.rows, n = (int)g.a.cols, K = (int)g.left.cols;
     const int np = br_np(n), pw = br_pw(n);
@@ -147,7 +154,7 @@ __global__ __launch_bounds__(BR_THREADS) void k_batched_residual(BrArgs<T> g) {
         const T *w_ld = Wp + (size_t)k4 * pw + wv * 16 + r16;
 
         // ---- phase 2: row chunks of a and left against W ------------------------------------------------------------------------------
-        double se = 0.0, sa = 0.0;
+        SumSq3 se{0.0, 0.0, 0.0}, sa{0.0, 0.0, 0.0};  // f32: med alone
         for (int m0 = 0; m0 < m; m0 += BR_ROWS) {
             const int ltot = BR_ROWS * r4;
             for (int idx = tid; idx < ltot; idx += BR_THREADS) {
@@ -168,6 +175,8 @@ __global__ __launch_bounds__(BR_THREADS) void k_batched_residual(BrArgs<T> g) {
                 for (int q = 0; q < BR_PER; ++q) As[(a_row0 + a_drow * q) * as_sr + (a_col0 + a_dcol * q) * as_sc] = av[q];
                 __syncthreads();
                 typename Acc<T>::type acc[2];
+                [[maybe_unused]] const double se0 = se.med, sa0 = sa.med;
+                [[maybe_unused]] unsigned emx = 0u, emn = ~0u;
                 acc[0] = typename Acc<T>::type{0, 0, 0, 0};
                 acc[1] = typename Acc<T>::type{0, 0, 0, 0};
                 const int bcol = c0 + wv * 16 + r16;
@@ -187,10 +196,43 @@ __global__ __launch_bounds__(BR_THREADS) void k_batched_residual(BrArgs<T> g) {
                         T *pa = as_acc + (i * 16 + Acc<T>::row(lane, reg)) * as_sr;
                         const T x = *pa;
                         const T ev = x - acc[i][reg];
-                        se = fma((double)ev, (double)ev, se);
-                        sa = fma((double)x, (double)x, sa);
-                        if (E) *pa = ev;
+                        se.med = fma((double)ev, (double)ev, se.med);
+                        sa.med = fma((double)x, (double)x, sa.med);
+                        if constexpr (WIDE) {
+                            ssq_watch(emx, emn, ev);
+                            ssq_watch(emx, emn, x);
+                        } else {
+                            if (E) *pa = ev;
+                        }
                     }
+                if constexpr (WIDE) {
+                    // a component of this thread's 8 elements out of the plain range: the tile's squares are taken back and binned.
+                    // a's image still holds x (e is stored behind this), and x - acc is the same rounding as above
+                    if (!ssq_all_plain(emx, emn)) {
+                        se.med = se0;
+                        sa.med = sa0;
+#pragma unroll
+                        for (int i = 0; i < 2; ++i)
+#pragma unroll
+                            for (int reg = 0; reg < 4; ++reg) {
+                                T x = as_acc[(i * 16 + Acc<T>::row(lane, reg)) * as_sr];
+                                asm volatile("" : "+v"(x));  // read again, not kept: eight more live residuals cost a wave per SIMD
+                                ssq_add(se, x - acc[i][reg]);
+                                ssq_add(sa, x);
+                            }
+                    }
+                    if (E) {
+#pragma unroll
+                        for (int i = 0; i < 2; ++i)
+#pragma unroll
+                            for (int reg = 0; reg < 4; ++reg) {
+                                T *pa = as_acc + (i * 16 + Acc<T>::row(lane, reg)) * as_sr;
+                                T x = *pa;
+                                asm volatile("" : "+v"(x));  // likewise
+                                *pa = x - acc[i][reg];
+                            }
+                    }
+                }
                 if (E) {  // uniform over the grid
                     __syncthreads();
 #pragma unroll
@@ -205,17 +247,36 @@ __global__ __launch_bounds__(BR_THREADS) void k_batched_residual(BrArgs<T> g) {
         // ---- the two sums: 64 lanes by a butterfly, then the four waves ------------------------------------------------------------------
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) {
-            se += __shfl_xor(se, off, 64);
-            sa += __shfl_xor(sa, off, 64);
+            se.med += __shfl_xor(se.med, off, 64);
+            sa.med += __shfl_xor(sa.med, off, 64);
+            if constexpr (WIDE) {
+                se.big += __shfl_xor(se.big, off, 64);
+                se.sml += __shfl_xor(se.sml, off, 64);
+                sa.big += __shfl_xor(sa.big, off, 64);
+                sa.sml += __shfl_xor(sa.sml, off, 64);
+            }
         }
+        [[maybe_unused]] double *red2 = reinterpret_cast<double *>(As);  // a's image is free behind the last tile's barrier
         if (lane == 0) {
-            red[wv] = se;
-            red[4 + wv] = sa;
+            red[wv] = se.med;
+            red[4 + wv] = sa.med;
+            if constexpr (WIDE) {
+                red2[wv] = se.big;
+                red2[4 + wv] = se.sml;
+                red2[8 + wv] = sa.big;
+                red2[12 + wv] = sa.sml;
+            }
         }
         __syncthreads();
         if (tid == 0) {
-            g.err[b] = (T)sqrt((red[0] + red[1]) + (red[2] + red[3]));
-            if (g.nrm) g.nrm[b] = (T)sqrt((red[4] + red[5]) + (red[6] + red[7]));
+            if constexpr (WIDE) {
+                g.err[b] = (T)ssq_norm((red[0] + red[1]) + (red[2] + red[3]), (red2[0] + red2[1]) + (red2[2] + red2[3]), (red2[4] + red2[5]) + (red2[6] + red2[7]));
+                if (g.nrm)
+                    g.nrm[b] = (T)ssq_norm((red[4] + red[5]) + (red[6] + red[7]), (red2[8] + red2[9]) + (red2[10] + red2[11]), (red2[12] + red2[13]) + (red2[14] + red2[15]));
+            } else {
+                g.err[b] = (T)sqrt((red[0] + red[1]) + (red[2] + red[3]));
+                if (g.nrm) g.nrm[b] = (T)sqrt((red[4] + red[5]) + (red[6] + red[7]));
+            }
         }
         __syncthreads();  // red and W's images are rewritten by the next block
     }

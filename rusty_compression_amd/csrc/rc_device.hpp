@@ -104,6 +104,56 @@ __device__ inline int block_pow2_exponent(T mx, T *stage, int wv, int lane) {
     return e < -lim ? -lim : (e > lim ? lim : e);
 }
 
+// ---- sums of squares over the whole f64 range: the three accumulators of LAPACK 3.10's ?lassq ----
+// A component with magnitude in [2^-511, 2^486) is squared as it stands (med: the plain sum), a larger one after a multiplication by
+// 2^-538 (big), a smaller one after a multiplication by 2^537 (sml): no square overflows or goes subnormal, and 2^32 of them still sum
+// inside the range.  The constants are ?lassq's tsml, tbig, sbig and ssml for f64.  NaN goes into med and stays NaN, +-inf into big.
+// The bins are summed apart, each in the caller's fixed order, and combined once (ssq_norm).
+constexpr double SSQ_TSML = 0x1p-511, SSQ_TBIG = 0x1p486, SSQ_SSML = 0x1p537, SSQ_SBIG = 0x1p-538;
+struct SumSq3 {
+    double med, big, sml;
+};
+__device__ __forceinline__ void ssq_add(SumSq3 &s, double v) {
+    const double a = fabs(v);
+    if (a >= SSQ_TBIG) {
+        const double t = v * SSQ_SBIG;
+        s.big = fma(t, t, s.big);
+    } else if (a < SSQ_TSML) {
+        const double t = v * SSQ_SSML;
+        s.sml = fma(t, t, s.sml);
+    } else {
+        s.med = fma(v, v, s.med);
+    }
+}
+// The watch that lets a caller keep the single accumulator on plain data: the largest exponent field of the components seen and the
+// smallest one minus 1, a zero field (zero, or a subnormal, whose square vanishes against any block of the domain) left out by the
+// wrap-around.  ssq_all_plain: every component seen lies in [2^-511, 2^486) (fields 512 .. 1508) or has a zero field; then the plain
+// sum is the med bin, bit for bit, and big and sml take nothing.  NaN and +-inf (field 2047) are not plain.
+__device__ __forceinline__ void ssq_watch(unsigned &emx, unsigned &emn, double v) {
+    const unsigned e = ((unsigned)__double2hiint(v) >> 20) & 0x7ffu;
+    emx = max(emx, e);
+    emn = min(emn, e - 1u);
+}
+__device__ __forceinline__ bool ssq_all_plain(unsigned emx, unsigned emn) { return emx < 1509u && emn >= 511u; }
+// sqrt of the sum the three bins stand for, ?lassq's combination followed by ?nrm2's: with nothing in big and sml it is sqrt(med), the
+// single accumulator's result bit for bit.  Roundings on top of the bins' own sums: at most 5 (two sqrt, a division, 1 + q^2, a product).
+__device__ inline double ssq_norm(double med, double big, double sml) {
+    if (med != med) return med;
+    if (big > 0.0) {
+        if (med > 0.0) big += (med * SSQ_SBIG) * SSQ_SBIG;
+        return sqrt(big) * 0x1p538;
+    }
+    if (sml > 0.0) {
+        if (med > 0.0) {
+            const double x = sqrt(med), y = sqrt(sml) * 0x1p-537;
+            const double lo = x < y ? x : y, hi = x < y ? y : x, q = lo / hi;
+            return hi * sqrt(fma(q, q, 1.0));
+        }
+        return sqrt(sml) * 0x1p-537;
+    }
+    return sqrt(med);
+}
+
 // ---- fast, fully accurate reciprocal / reciprocal square root --------------------------
 // v_rcp_f64 / v_rsq_f64 deliver ~2^-23 relative accuracy; two Newton steps reach the f64
 // rounding level (error <= ~2 ulp) at a fraction of the IEEE division / sqrt expansions.

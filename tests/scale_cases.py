@@ -13,21 +13,29 @@ for a, bit for bit (LAPACK meets this: test_scale_cases_cpu.py).
 Exponents: the outer ones keep every input, every output and ||A||_F inside the normal range at the shapes used; the middle magnitudes
 sit where the squares of the entries start to overflow (2^62, 2^510) or go subnormal (2^-64, 2^-512).
 Kinds: Gaussian; singular values 1 .. 1e-3 (the modest decay keeps the smallest kept singular value times 2^-90 normal in f32); an exact
-rank-EXACT_RANK product, which the tolerance of the calls (TOLS) must cut at that rank."""
+rank-EXACT_RANK product, which the tolerance of the calls (TOLS) must cut at that rank.
+
+The calls that consume those outputs (second half of this file): a recompression case is a unit-scale (left, right, mid, s) and a carrier
+that says which operand takes 2^e (CARRIERS), a residual case a unit-scale block with its factors where `a` and one factor take 2^e
+(RESIDUAL_CARRIER); check_recompress and check_residual descale exactly and hand over to the families' own checkers and bounds."""
 import numpy as np
 import scipy.linalg
 
 from oracle import ref_lapack as o
 from tests import test_gpu_batched_id as bid
 from tests import test_gpu_batched_id_complex as bidc
+from tests import residual_ref as rr
+from tests import residual_ref_complex as rrc
 from tests import test_gpu_batched_range_step as brs
+from tests import test_gpu_batched_recompress as brc
+from tests import test_gpu_batched_recompress_complex as brcc
 from tests import test_gpu_batched_sketch_id as bsi
 from tests import test_gpu_batched_sketch_id_complex as bsic
 from tests import test_gpu_batched_svd as bsv
 from tests import test_gpu_batched_svd_complex as bsvc
 from tests import test_gpu_batched_two_sided_id as bts
 from tests import test_gpu_batched_two_sided_id_complex as btsc
-from tests.helpers import is_permutation, stable_prefix
+from tests.helpers import is_permutation, sign_normalise, stable_prefix
 
 E32 = (-90, -64, -40, 0, 40, 62, 90)
 E64 = (-900, -512, -300, 0, 300, 510, 900)
@@ -237,3 +245,206 @@ def check_range_step(a, om, e, q, p, r, y, dtype):
     assert span <= brs.QR_MARGIN * lspan + floor, (span, lspan)
     a64, q64 = a.astype(np.float64), q.astype(np.float64)
     assert np.all(np.abs(p1.astype(np.float64) - a64 @ q64.T) <= cst * (n + 4) * u * (np.abs(a64) @ np.abs(q64.T)))
+
+
+# ------------------------------------------------------------------------------------------------ recompression: cases and checker
+# which operand of left mid diag(s) right carries 2^e, and the mode (tests/test_gpu_batched_recompress.py's MODES) it runs in:
+#   left:  what a column ID's C carries;  mid: a two-sided ID's X;  s: an SVD's s;
+#   split: left and mid times 2^e, s and right times 2^-e: every operand is extreme and the product is at unit scale, so a kernel that
+#          normalises some operands and not others goes wrong here.
+CARRIERS = {"left": "none", "mid": "mid", "s": "s", "split": "both"}
+RECOMPRESS_KINDS = ("gauss", "spectrum")
+# (m, n, K) per family, from the families' own lists: the smallest LDS plans and a workspace plan; two stages of the left factor; both
+# factors staged
+RECOMPRESS_SHAPES = {"small": [(33, 17, 17), (200, 96, 40), (512, 512, 128)], "tall": [(513, 40, 8), (1100, 130, 128)],
+                     "large": [(513, 600, 8), (300, 2100, 64)]}
+
+
+def recompress_kinds(carrier, dtype):
+    """The kinds a dtype runs.  The spectrum kind's singular values go down to 2^-30 and, computed from factors rounded to f32, below
+    (1e-11 at K = 128); its left = Q diag(2^-j) has entries down to 2^-50.  2^-90 takes both below the smallest normal f32 number, where
+    a power of two no longer commutes with the rounding: f32 / c32 run the Gaussian kind alone, f64 / c64 both."""
+    return ("gauss",) if real_of(dtype) == np.dtype(np.float32) else RECOMPRESS_KINDS
+
+
+def carry(factors, carrier, e):
+    """The unit-scale (left, right, mid, s) with the carrier's operands times 2^+-e, exactly."""
+    left, right, mid, s = factors
+    if carrier == "left":
+        return scale(left, e), right, mid, s
+    if carrier == "mid":
+        return left, right, scale(mid, e), s
+    if carrier == "s":
+        return left, right, mid, scale(s, e)
+    assert carrier == "split"
+    return scale(left, e), scale(right, -e), scale(mid, e), scale(s, -e)
+
+
+def net_exponent(carrier, e):
+    """The exponent the product, and with it s_out, carries."""
+    return 0 if carrier == "split" else e
+
+
+_RECOMPRESS = {}
+
+
+def recompress_batch(shape, dtype, carrier):
+    """(units, cells, operands, refs): the unit factors per kind, the (kind index, e) of each entry, the four stacked operands (None where
+    the mode has none) and per kind (a, sigma, oracle SVD) of the unit-scale dense product (made once, never changed)."""
+    key = (tuple(shape), np.dtype(dtype), carrier)
+    if key not in _RECOMPRESS:
+        m, n, K = shape
+        mod = brcc if is_complex(dtype) else brc
+        rng = np.random.default_rng(31000 + 1000 * m + 10 * n + K + list(CARRIERS).index(carrier) + (5 if is_complex(dtype) else 0))
+        kinds_ = recompress_kinds(carrier, dtype)
+        units = [mod.factors(rng, kind, m, n, K, CARRIERS[carrier], dtype) for kind in kinds_]
+        cells = [(i, e) for i in range(len(kinds_)) for e in exponents(dtype)]
+        operands = mod.stack([carry(units[i], carrier, e) for i, e in cells])
+        refs = []
+        for f in units:
+            a, sigma = mod.dense(*f, K)
+            refs.append((a, sigma, o.SVD.compute_from(a)))
+        for arr in [x for f in units for x in f] + list(operands):
+            if arr is not None:
+                arr.setflags(write=False)
+        _RECOMPRESS[key] = (units, cells, operands, refs)
+    return _RECOMPRESS[key]
+
+
+def check_recompress(ref, carrier, e, u, s_out, vt, r, kk, dtype, unit_out):
+    """One entry of a recompression batch run on carry(unit factors, carrier, e): s_out descaled by the net exponent, exactly, then the
+    family's check_block against the unit-scale dense product (ref = (a, sigma, its oracle SVD); the bounds are that file's TOL and nothing
+    new), then u, vt and the rank, and the descaled s_out, against the e = 0 entry of the same batch (unit_out = (u, s_out, vt, rank)) bit
+    for bit: each operand is multiplied by an exact power of two before any rounding, so the working copies are identical."""
+    mod = brcc if is_complex(dtype) else brc
+    a, sigma, oracle = ref
+    assert np.all(np.isfinite(u)) and np.all(np.isfinite(vt)) and np.all(np.isfinite(s_out))
+    s1 = descale(s_out, net_exponent(carrier, e))
+    mod.check_block(a, sigma, u, s1, vt, int(r), s_out.shape[0], kk, dtype, oracle)
+    assert_same_as_unit(("u", "s", "vt", "ranks"), unit_out, (u, s1, vt, r))
+
+
+def host_recompress(left, right, mid, s, dtype, plain_norms=False):
+    """The recompression in the working precision on the host: every operand normalised by the exact power of two of its largest
+    component (as the kernels do), scipy's pivoted QR of left and of right^T (no conjugate), the core Rl mid diag(s) Rr^T, numpy's SVD of
+    it, the batched sign / phase rule, and s_out = 2^(el + em + es + er) times the core's singular values.
+    plain_norms: the planted model.  The same route, but the singular values are taken as the kernels took them before mid and s (for
+    complex data: any operand) were normalised: the square roots of plain sums of squares, in the working type, of the columns of the
+    rotated core at the scale the operands left it with.  Returns (u, s_out, vt, r) with r = K."""
+    dt = np.dtype(dtype)
+    rd = real_of(dt)
+
+    def expo(x):
+        if x is None:
+            return 0
+        mx = float(max(np.abs(x.real).max(), np.abs(x.imag).max())) if is_complex(x.dtype) else float(np.abs(x).max())
+        return int(np.floor(np.log2(mx))) if mx > 0 and np.isfinite(mx) else 0
+
+    el, er, em, es = expo(left), expo(right), expo(mid), expo(s)
+    lf, rt = scale(left, -el), scale(right, -er)
+    K = lf.shape[1]
+    ql, rl, pl = scipy.linalg.qr(lf, mode="economic", pivoting=True)
+    qr_, rr_, pr = scipy.linalg.qr(rt.T, mode="economic", pivoting=True)
+    rl_full, rr_full = np.zeros_like(rl), np.zeros_like(rr_)
+    rl_full[:, pl], rr_full[:, pr] = rl, rr_
+    core = np.eye(K, dtype=dt) if mid is None else scale(mid, -em)
+    if s is not None:
+        core = core * scale(s, -es)[None, :]
+    c = rl_full @ core @ rr_full.T
+    assert c.dtype == dt and ql.dtype == dt and qr_.dtype == dt
+    uc, sv, vh = np.linalg.svd(c)
+    if plain_norms:
+        with np.errstate(all="ignore"):
+            gv = scale((c @ vh.conj().T).astype(dt), el + er + em + es)
+            s_out = np.sqrt(np.sum((gv * gv.conj()).real.astype(rd), axis=0, dtype=rd))
+    else:
+        s_out = np.ldexp(sv.astype(rd), el + er + em + es)
+    u, vt = (ql @ uc).astype(dt), (vh @ qr_.T).astype(dt)
+    if is_complex(dt):
+        for j in range(K):
+            i = int(np.argmax(np.abs(u[:, j])))
+            mag = np.abs(u[i, j])
+            if mag > 0 and np.isfinite(mag):
+                ph = np.conj(u[i, j]) / mag
+                u[:, j] *= ph
+                u[i, j] = mag
+                vt[j] *= np.conj(ph)
+    else:
+        u, vt = sign_normalise(u, vt)
+    return u, s_out, vt, K
+
+
+# ------------------------------------------------------------------------------------------------ residual norms: cases and checker
+# mode of tests/residual_ref.py -> the factor that carries 2^e beside a, as a compressor returns it: C of a column ID, s of an SVD, X of a
+# two-sided ID.  The rebuild then runs at 2^e from its last product on and no intermediate leaves the range (a split-scale set whose
+# diag(s) right or mid W0 overflows stays the caller's).
+RESIDUAL_CARRIER = {"none": "left", "s": "s", "both": "mid"}
+RESIDUAL_SHAPES = [(33, 65, 17), (257, 130, 40)]
+RESIDUAL_KINDS = ("gauss", "wide_core")
+
+_RESIDUAL = {}
+
+
+def residual_batch(shape, dtype, mode):
+    """(units, cells, stacked): per kind the unit-scale dict(a, left, right, mid, s) of residual_ref(_complex).gaussian_factors, the
+    (kind index, e) of each entry, and the stacked operands with a and the mode's carrier times 2^e (made once, never changed)."""
+    key = (tuple(shape), np.dtype(dtype), mode)
+    if key not in _RESIDUAL:
+        m, n, K = shape
+        ref = rrc if is_complex(dtype) else rr
+        rng = np.random.default_rng(47000 + 1000 * m + 10 * n + K + len(mode) + (5 if is_complex(dtype) else 0))
+        units = [ref.gaussian_factors(rng, m, n, K, dtype, mode, wide_core=(kind == "wide_core")) for kind in RESIDUAL_KINDS]
+        cells = [(i, e) for i in range(len(units)) for e in exponents(dtype)]
+        car = RESIDUAL_CARRIER[mode]
+        stacked = {}
+        for name in ("a", "left", "right", "mid", "s"):
+            if units[0][name] is None:
+                stacked[name] = None
+            else:
+                stacked[name] = np.stack([scale(units[i][name], e) if name in ("a", car) else units[i][name] for i, e in cells])
+                stacked[name].setflags(write=False)
+        _RESIDUAL[key] = (units, cells, stacked)
+    return _RESIDUAL[key]
+
+
+def check_residual(f, e, err, nrm, e_out, unit_e_out, dtype):
+    """One entry of a residual batch run on 2^e a and the carrier times 2^e: err, nrm and e descaled exactly, then residual_ref.bound
+    against residual_ref.reference on the unit operands f (the complex twins for complex data).  The bound's 16 roundings of slack beside
+    the chain length cover the three-bin accumulation: each bin is summed over a sub-chain of the single accumulator's chain, and the
+    combination adds at most 5 roundings (two roots, a quotient, 1 + q^2, a product), or 3 (two scalings and a sum) and a root.
+    e is unchanged arithmetic: bit for bit 2^e times the unit entry's (unit_e_out; None when the residual was not asked for).  err and nrm
+    need not be: a block whose entries straddle a threshold of the scaled accumulation sums in another grouping."""
+    ref = rrc if is_complex(dtype) else rr
+    m, n = f["a"].shape
+    K = f["left"].shape[1]
+    assert np.isfinite(err) and np.isfinite(nrm)
+    err1, nrm1 = float(descale(err, e)), float(descale(nrm, e))
+    _, e_ref = ref.reference(f["a"], f["left"], f["right"], f["mid"], f["s"], K)
+    B, err_bound, nrm_bound = ref.bound(f["a"], f["left"], f["right"], f["mid"], f["s"], K, dtype, ref.chain_length(m, n))
+    wide = np.complex128 if is_complex(dtype) else np.float64
+    assert abs(err1 - float(np.linalg.norm(e_ref))) <= err_bound, (err1, float(np.linalg.norm(e_ref)), err_bound)
+    assert abs(nrm1 - float(np.linalg.norm(f["a"].astype(wide)))) <= nrm_bound, (nrm1, float(np.linalg.norm(f["a"].astype(wide))), nrm_bound)
+    if e_out is not None:
+        e1 = descale(e_out, e)
+        assert np.all(np.abs(e1.astype(wide) - e_ref) <= B)
+        assert same_bits(e1, unit_e_out), "e is not 2^e times the unit entry's"
+
+
+def lassq_norm(x):
+    """||x||_F of f64 / c128 data by the three accumulators of LAPACK 3.10's ?lassq, in f64: the host model of the kernels' accumulation."""
+    v = np.asarray(x)
+    v = np.concatenate([v.real.ravel(), v.imag.ravel()]) if is_complex(v.dtype) else v.ravel()
+    v = v.astype(np.float64)
+    av = np.abs(v)
+    tsml, tbig, ssml, sbig = 2.0 ** -511, 2.0 ** 486, 2.0 ** 537, 2.0 ** -538
+    big, sml = v[av >= tbig] * sbig, v[(av < tsml)] * ssml
+    med = v[(av >= tsml) & (av < tbig)]
+    abig, asml, amed = float(np.sum(big * big)), float(np.sum(sml * sml)), float(np.sum(med * med))
+    if abig > 0:
+        return np.sqrt(abig + (amed * sbig) * sbig) / sbig
+    if asml > 0:
+        if amed > 0:
+            lo, hi = sorted((np.sqrt(amed), np.sqrt(asml) / ssml))
+            return hi * np.sqrt(1 + (lo / hi) ** 2)
+        return np.sqrt(asml) / ssml
+    return np.sqrt(amed)

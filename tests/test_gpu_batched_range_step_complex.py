@@ -387,8 +387,8 @@ def test_non_finite_input_stays_in_its_block(dtype):
 @pytest.mark.parametrize("m,n,l", sc.STEP_SHAPES)
 def test_range_step_at_every_scale(m, n, l, dtype):
     """2^e a gives y and p times 2^e and q and ranks unchanged, bit for bit, at the exponents of the complex sketched ID's far-scale tests
-    (tests/scale_cases.py: three kinds of block at seven exponents in one batch).  The step only: the complex recompressions do not
-    normalise their inputs, so the chains are not covered."""
+    (tests/scale_cases.py: three kinds of block at seven exponents in one batch).  The step only: the chains built on it are held to the
+    same exponents in tests/test_gpu_batched_scales.py."""
     units, cells, stacked = sc.batch((m, n), dtype)
     om = sc.omega((m, n), l, dtype)
     for conj_p in (False, True):

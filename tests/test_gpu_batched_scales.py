@@ -22,6 +22,7 @@ import torch
 import rusty_compression_amd as rc
 from rusty_compression_amd import _lib
 from tests import range_step_ref as ref
+from tests import range_step_ref_complex as refc
 from tests import scale_cases as sc
 from tests import test_gpu_batched_sketch_id as bsi
 from tests import test_gpu_batched_sketch_id_complex as bsic
@@ -49,14 +50,14 @@ def tol_of(dtype):
     return sc.TOLS[sc.real_of(dtype)]
 
 
-def for_every_cell(cells, check):
+def for_every_cell(cells, check, kinds=sc.KINDS):
     """check(index, kind index, e) on every cell; one failure message that lists every failing (kind, e)."""
     failed = []
     for idx, (i, e) in enumerate(cells):
         try:
             check(idx, i, e)
         except AssertionError as err:
-            failed.append((sc.KINDS[i], e, str(err).splitlines()[0][:160] if str(err) else "assert"))
+            failed.append((kinds[i], e, str(err).splitlines()[0][:160] if str(err) else "assert"))
     assert not failed, f"{len(failed)} of {len(cells)} cells failed: {failed}"
 
 
@@ -187,57 +188,63 @@ _HOST = {}
 
 
 def host_model(which, shape, l, i, dtype):
-    """(error, rank) of the f64 host model of tests/range_step_ref.py on unit matrix i with the same omega (made once)."""
+    """(error, rank) of the f64 host model of tests/range_step_ref.py (complex data: the c128 one of tests/range_step_ref_complex.py) on unit
+    matrix i with the same omega (made once)."""
     key = (which, shape, l, i, np.dtype(dtype))
     if key not in _HOST:
         a, om = sc.batch(shape, dtype)[0][i], sc.omega(shape, l, dtype)
-        fn = ref.column_id_power if which == "id" else ref.svd_power
+        mod = refc if sc.is_complex(dtype) else ref
+        fn = mod.column_id_power if which == "id" else mod.svd_power
         _HOST[key] = fn(a, om, l, tol_of(dtype), 1)[:2]
     return _HOST[key]
 
 
-@pytest.mark.parametrize("dtype", REAL)
+@pytest.mark.parametrize("dtype", ALL)
 @pytest.mark.parametrize("m,n,l", sc.SKETCH_SHAPES)
 def test_power_iterated_sketched_id_at_every_scale(m, n, l, dtype):
-    """One round of power iteration, then the sketched ID.  The round orthonormalises P = a Q^T, which carries the block's scale, by
-    rc_lowrank_recompress_tall_batched_*: that kernel loads its two factors times exact powers of two (brc_exponent), so the basis of the
-    round, and with it every output, is the unit-scale one bit for bit."""
+    """One round of power iteration, then the sketched ID.  The round orthonormalises P = a Q^T (complex: a Q^H), which carries the block's
+    scale, by the tall recompression: that kernel loads its operands times exact powers of two (brc_exponent), the complex one as the real
+    one, so the basis of the round, and with it every output, is the unit-scale one bit for bit."""
     units, cells, stacked = sc.batch((m, n), dtype)
     om = sc.omega((m, n), l, dtype)
-    c, z, ind, ranks = call(rc.sketch_column_id_rank_power_batched, tt(stacked), l, tol_of(dtype), power_iterations=1, omega=tt(om))
+    wide = np.complex128 if sc.is_complex(dtype) else np.float64
+    fn = rc.sketch_column_id_rank_power_batched_complex if sc.is_complex(dtype) else rc.sketch_column_id_rank_power_batched
+    c, z, ind, ranks = call(fn, tt(stacked), l, tol_of(dtype), power_iterations=1, omega=tt(om))
 
     def check(idx, i, e):
         r = int(ranks[idx])
         oerr, orank = host_model("id", (m, n), l, i, dtype)
         assert r == orank == expected_rank((m, n), i, l)
         assert sc.same_bits(c[idx][:, :r], stacked[idx][:, ind[idx][:r]]) and not np.any(c[idx][:, r:]) and not np.any(z[idx][r:])
-        a64 = units[i].astype(np.float64)
-        err = np.linalg.norm(a64 - sc.descale(c[idx], e)[:, :r].astype(np.float64) @ z[idx][:r].astype(np.float64)) / np.linalg.norm(a64)
-        assert err <= 1.5 * oerr + 100 * np.finfo(dtype).eps, (err, oerr)
+        a64 = units[i].astype(wide)
+        err = np.linalg.norm(a64 - sc.descale(c[idx], e)[:, :r].astype(wide) @ z[idx][:r].astype(wide)) / np.linalg.norm(a64)
+        assert err <= 1.5 * oerr + 100 * np.finfo(sc.real_of(dtype)).eps, (err, oerr)
         u = sc.unit_cell(cells, i)
         sc.assert_same_as_unit(("c", "z", "ind", "ranks"), (c[u], z[u], ind[u], ranks[u]), (sc.descale(c[idx], e), z[idx], ind[idx], ranks[idx]), r)
 
     for_every_cell(cells, check)
 
 
-@pytest.mark.parametrize("dtype", REAL)
+@pytest.mark.parametrize("dtype", ALL)
 @pytest.mark.parametrize("m,n,l", sc.SKETCH_SHAPES)
 def test_power_iterated_sketched_svd_at_every_scale(m, n, l, dtype):
     """One range step, then the tall recompression of (P, Q): s carries the scale, U and Vt are the unit-scale ones bit for bit."""
     units, cells, stacked = sc.batch((m, n), dtype)
     om = sc.omega((m, n), l, dtype)
-    u, s, vt, ranks = call(rc.sketch_svd_rank_power_batched, tt(stacked), l, tol_of(dtype), power_iterations=1, omega=tt(om))
+    wide = np.complex128 if sc.is_complex(dtype) else np.float64
+    fn = rc.sketch_svd_rank_power_batched_complex if sc.is_complex(dtype) else rc.sketch_svd_rank_power_batched
+    u, s, vt, ranks = call(fn, tt(stacked), l, tol_of(dtype), power_iterations=1, omega=tt(om))
 
     def check(idx, i, e):
         r = int(ranks[idx])
         oerr, orank = host_model("svd", (m, n), l, i, dtype)
         assert r == orank == expected_rank((m, n), i, l)
-        u0, s0, vt0 = u[idx][:, :r].astype(np.float64), sc.descale(s[idx], e)[:r].astype(np.float64), vt[idx][:r].astype(np.float64)
-        assert max(np.abs(u0.T @ u0 - np.eye(r)).max(), np.abs(vt0 @ vt0.T - np.eye(r)).max()) <= 4 * TOL[np.dtype(dtype)]["orth"]
+        u0, s0, vt0 = u[idx][:, :r].astype(wide), sc.descale(s[idx], e)[:r].astype(np.float64), vt[idx][:r].astype(wide)
+        assert max(np.abs(u0.conj().T @ u0 - np.eye(r)).max(), np.abs(vt0 @ vt0.conj().T - np.eye(r)).max()) <= 4 * TOL[sc.real_of(dtype)]["orth"]
         assert np.all(np.diff(s0) <= 0) and s0[-1] > 0
-        a64 = units[i].astype(np.float64)
+        a64 = units[i].astype(wide)
         err = np.linalg.norm(a64 - (u0 * s0) @ vt0) / np.linalg.norm(a64)
-        assert err <= 1.5 * oerr + 100 * np.finfo(dtype).eps, (err, oerr)
+        assert err <= 1.5 * oerr + 100 * np.finfo(sc.real_of(dtype)).eps, (err, oerr)
         j = sc.unit_cell(cells, i)
         sc.assert_same_as_unit(("u", "s", "vt", "ranks"), (u[j], s[j], vt[j], ranks[j]), (u[idx], sc.descale(s[idx], e), vt[idx], ranks[idx]))
 
