@@ -3,16 +3,16 @@
 // Each of the two translation units instantiates them for its own two element types; nothing here is exported.
 //
 // What stands here once: the fill, the column norms and their power-of-two normalisation, the step loop of the pivoted QR (bid_qrcp), the
-// blocked back substitution for Z (bid_z), the column-ID and two-sided kernels with the carve-up of their LDS (bid_carve), their plans and
-// launcher bodies, the Jacobi sweep schedule (bsv_jacobi) and the stack load of the tall recompressions (brt_stack_load).  The per-element
-// operations they are written in: elem<E> (real type, zero, one), abs2, cj (the identity on reals), ediv, pow2_key_max, escale and
+// blocked back substitution for Z (bid_z), the column-ID and two-sided kernels with the carve-up of their LDS (bid_carve) and their plans,
+// the Jacobi sweep schedule (bsv_jacobi) and the stack load of the tall recompressions (brt_stack_load).  The launcher bodies of both
+// families stand in batched_launchers.hpp.  The per-element operations they are written in: elem<E> (zero, one), abs2, cj (the identity on reals), ediv, pow2_key_max, escale and
 // submul -- the real ones below, the complex ones in rc_cplx.hpp.
 //
 // What stays per family, in the two .hip files, because its arithmetic or its register budget differs: the trailing update bid_apply /
 // bic_apply (two columns in flight per wave for real, one for complex), the Jacobi rounds bsv_round / bsc_round, bsv_sign / bsc_phase, the
 // form_u routines, *_reflect_back, brt_form_u / brtc_form_u / brl_form_vt, the core products, the bodies of the SVD and recompression
 // kernels (their LDS and workspace placement differs by the complex G flag) with the sort of their singular values, the sketch and
-// range-step kernels with their MFMA staging, and the plans bsv / bsc, brc / brcc, brt / brtc, brl and the sketch plans.  The two
+// range-step kernels with their MFMA staging.  The two
 // reflector formulas (?larfg) stand side by side inside bid_qrcp, and the shared loops call bid_apply / bic_apply and bsv_round /
 // bsc_round directly, each under `if constexpr` on the element type.
 //
@@ -42,11 +42,9 @@ constexpr int BIC_NB = 8;   // of the complex kernels (their register budget: ev
 // ---- the element operations, real side ---------------------------------------------------------------------------------------------
 template <typename E>
 struct elem {
-    using real = E;
     static __host__ __device__ __forceinline__ E zero() { return (E)0; }
     static __host__ __device__ __forceinline__ E one() { return (E)1; }
 };
-template <typename E> using real_t = typename elem<E>::real;
 template <typename E> constexpr bool is_real_elem = std::is_same<E, real_t<E>>::value;
 template <typename E> constexpr int z_tile = is_real_elem<E> ? BID_NB : BIC_NB;
 template <typename T> __device__ __forceinline__ T abs2(T v) { return v * v; }
@@ -425,30 +423,7 @@ BatchedPlan<bool> bts_plan(int m, int n, int k) {
                              (size_t)m * (size_t)n * sizeof(E), "two_sided_id_rank_batched");
 }
 
-// and the bodies of their launchers (the exported wrappers are batched_column_id<T> / batched_column_id_c<R> and the two-sided pair)
-template <typename E>
-void bid_launch(rc_context *c, Mat<E> a, int64_t abs, int32_t count, int64_t k, double tol, Mat<E> cm, int64_t cbs, Mat<E> z, int64_t zbs, int64_t *col_ind,
-                int64_t *ranks) {
-    const int m = (int)a.rows, n = (int)a.cols;
-    if (count <= 0) return;
-    const auto plan = bid_plan<E>(m, n);
-    const auto lch = batched_prepare(c, plan.at ? k_batched_id<E, true> : k_batched_id<E, false>, "column_id_rank_batched", plan.lds, plan.ws, count);
-    ProfScope ps(c, "op:batched_column_id%s %dx%d k=%lld count=%d grid=%lld slots=%lld plan=W:%s", is_real_elem<E> ? "" : "<complex>", m, n, (long long)k,
-                 (int)count, (long long)lch.grid, (long long)lch.slots, plan.at ? "lds" : "ws");
-    lch.launch(a, abs, (int)count, (int)k, tol, cm, cbs, z, zbs, col_ind, ranks, lch.template workspace<E>());
-}
-template <typename E>
-void bts_launch(rc_context *c, Mat<E> a, int64_t abs, int32_t count, int64_t k, double tol, Mat<E> cm, int64_t cbs, Mat<E> x, int64_t xbs, Mat<E> z, int64_t zbs,
-                int64_t *row_ind, int64_t *col_ind, int64_t *ranks) {
-    const int m = (int)a.rows, n = (int)a.cols;
-    if (count <= 0) return;
-    const auto plan = bts_plan<E>(m, n, (int)k);
-    const auto lch = batched_prepare(c, plan.at ? k_batched_two_sided<E, true> : k_batched_two_sided<E, false>, "two_sided_id_rank_batched", plan.lds, plan.ws,
-                                     count);
-    ProfScope ps(c, "op:batched_two_sided_id%s %dx%d k=%lld count=%d grid=%lld slots=%lld plan=W:%s", is_real_elem<E> ? "" : "<complex>", m, n, (long long)k,
-                 (int)count, (long long)lch.grid, (long long)lch.slots, plan.at ? "lds" : "ws");
-    lch.launch(a, abs, (int)count, (int)k, tol, cm, cbs, x, xbs, z, zbs, row_ind, col_ind, ranks, lch.template workspace<E>());
-}
+// (the bodies of their launchers: batched_launchers.hpp)
 
 // ---- the Jacobi sweep schedule of the SVD and recompression kernels ---------------------------------------------------------------------
 // one-sided Jacobi of the N x N core G (columns ldg apart) with the rotations accumulated in J (ldj); round-robin pairs, 16 lanes per pair (N <= 16 NE

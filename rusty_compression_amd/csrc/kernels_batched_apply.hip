@@ -131,34 +131,18 @@ BaView<E> ba_view(P *p, int64_t rs, int64_t cs, int64_t bs) { return BaView<E>{r
 
 }  // namespace
 
-template <typename T>
-void batched_lowrank_apply(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride, Mat<T> right, int64_t rbs,
-                           const int64_t *ranks, int32_t count, Mat<T> b, int64_t bbs, Mat<T> y, int64_t ybs) {
-    BaArgs<T> a;
-    a.left = ba_view<const T>(left.p, left.rs, left.cs, lbs);
-    a.mid = ba_view<const T>(mid.p, mid.rs, mid.cs, mbs);
-    a.right = ba_view<const T>(right.p, right.rs, right.cs, rbs);
-    a.b = ba_view<const T>(b.p, b.rs, b.cs, bbs);
-    a.y = ba_view<T>(y.p, y.rs, y.cs, ybs);
-    a.s = s; a.s_stride = s_stride; a.ranks = ranks; a.count = count;
-    a.m = (int)left.rows; a.n = (int)right.cols; a.k = (int)left.cols; a.ncols = (int)y.cols;
-    ba_launch<T, T>(c, a, "");
-}
-
-template <typename R>
-void batched_lowrank_apply_c(rc_context *c, const rc_matrix &left, int64_t lbs, const rc_matrix &mid, int64_t mbs, const R *s, int64_t s_stride,
-                             const rc_matrix &right, int64_t rbs, const int64_t *ranks, int32_t count, const rc_matrix &b, int64_t bbs, const rc_matrix &y,
-                             int64_t ybs) {
-    using E = cplx<R>;
+template <typename E>
+void batched_lowrank_apply(rc_context *c, Mat<E> left, int64_t lbs, Mat<E> mid, int64_t mbs, const real_t<E> *s, int64_t s_stride, Mat<E> right, int64_t rbs,
+                           const int64_t *ranks, int32_t count, Mat<E> b, int64_t bbs, Mat<E> y, int64_t ybs) {
     BaArgs<E> a;
-    a.left = ba_view<const E>(left.data, left.row_stride, left.col_stride, lbs);
-    a.mid = ba_view<const E>(mid.data, mid.row_stride, mid.col_stride, mbs);
-    a.right = ba_view<const E>(right.data, right.row_stride, right.col_stride, rbs);
-    a.b = ba_view<const E>(b.data, b.row_stride, b.col_stride, bbs);
-    a.y = ba_view<E>(y.data, y.row_stride, y.col_stride, ybs);
+    a.left = ba_view<const E>(left.p, left.rs, left.cs, lbs);
+    a.mid = ba_view<const E>(mid.p, mid.rs, mid.cs, mbs);
+    a.right = ba_view<const E>(right.p, right.rs, right.cs, rbs);
+    a.b = ba_view<const E>(b.p, b.rs, b.cs, bbs);
+    a.y = ba_view<E>(y.p, y.rs, y.cs, ybs);
     a.s = s; a.s_stride = s_stride; a.ranks = ranks; a.count = count;
     a.m = (int)left.rows; a.n = (int)right.cols; a.k = (int)left.cols; a.ncols = (int)y.cols;
-    ba_launch<E, E>(c, a, "<complex>");
+    ba_launch<E, E>(c, a, std::is_same<E, real_t<E>>::value ? "" : "<complex>");
 }
 
 // the mixed calls: factor views of S (strides in elements of S), b and y of E, s double
@@ -184,13 +168,12 @@ void batched_lowrank_apply_mixed(rc_context *c, bool complex_data, const rc_matr
     else ba_mixed<double, float>(c, left, lbs, mid, mbs, s, s_stride, right, rbs, ranks, count, b, bbs, y, ybs, "<mixed>");
 }
 
-template void batched_lowrank_apply<double>(rc_context *, Mat<double>, int64_t, Mat<double>, int64_t, const double *, int64_t, Mat<double>, int64_t,
-                                            const int64_t *, int32_t, Mat<double>, int64_t, Mat<double>, int64_t);
-template void batched_lowrank_apply<float>(rc_context *, Mat<float>, int64_t, Mat<float>, int64_t, const float *, int64_t, Mat<float>, int64_t,
-                                           const int64_t *, int32_t, Mat<float>, int64_t, Mat<float>, int64_t);
-template void batched_lowrank_apply_c<double>(rc_context *, const rc_matrix &, int64_t, const rc_matrix &, int64_t, const double *, int64_t,
-                                              const rc_matrix &, int64_t, const int64_t *, int32_t, const rc_matrix &, int64_t, const rc_matrix &, int64_t);
-template void batched_lowrank_apply_c<float>(rc_context *, const rc_matrix &, int64_t, const rc_matrix &, int64_t, const float *, int64_t,
-                                             const rc_matrix &, int64_t, const int64_t *, int32_t, const rc_matrix &, int64_t, const rc_matrix &, int64_t);
+#define RC_INSTANTIATE_APPLY(E)                                                                                                             \
+    template void batched_lowrank_apply<E>(rc_context *, Mat<E>, int64_t, Mat<E>, int64_t, const real_t<E> *, int64_t, Mat<E>, int64_t, const int64_t *, \
+                                           int32_t, Mat<E>, int64_t, Mat<E>, int64_t);
+RC_INSTANTIATE_APPLY(double)
+RC_INSTANTIATE_APPLY(float)
+RC_INSTANTIATE_APPLY(cplx<double>)
+RC_INSTANTIATE_APPLY(cplx<float>)
 
 }  // namespace rc

@@ -37,16 +37,19 @@
 //
 // The stages that read the same for real and complex elements stand once in batched_stages.hpp, as templates over the element type that
 // this file instantiates for double and float: the fill, the norms and their power-of-two normalisation, the pivoted-QR step loop bid_qrcp,
-// the back substitution bid_z, k_batched_id and k_batched_two_sided with their LDS carve-up, plans and launcher bodies, the Jacobi schedule
+// the back substitution bid_z, k_batched_id and k_batched_two_sided with their LDS carve-up and plans, the Jacobi schedule
 // bsv_jacobi and brt_stack_load.  Here stay the real family's own routines (bid_apply, bsv_round, bsv_sign, the form_u routines, the core
 // products) and the SVD, recompression, sketch and range-step kernels.
 //
-// The launchers at the end of the file follow rc_batched_launch.hpp: a plan function per entry point, then prepare, label, workspace,
-// launch.  bid_grid and the first-use LDS cap of the whole batched family are defined here.
+// The launchers follow rc_batched_launch.hpp: a plan function per entry point, then prepare, label, workspace, launch.  All but the sketch
+// product's are written once for all four element types in batched_launchers.hpp; the file ends with what they take from this family
+// (RealFamily: the Args structs, the LDS and workspace sizes and the instance to launch) and their instantiation for double and float.
+// bid_grid and the first-use LDS cap of the whole batched family are defined here.
 #include <map>
 #include <mutex>
 #include <utility>
 
+#include "batched_launchers.hpp"
 #include "batched_stages.hpp"
 #include "rc_batched_launch.hpp"
 #include "rc_common.hpp"
@@ -1202,75 +1205,43 @@ __global__ __launch_bounds__(BID_THREADS, 2) void k_batched_range_step(BrsArgs<T
 }
 #undef RC_BSI_DISPATCH
 
-// ---- the plans: where each launcher's movable buffers live, as pure functions of the shapes (rc_batched_launch.hpp) -------------------------
-
-// SVD, M x N the work orientation: the working copy W (M x N) and V (N x N) in LDS when they fit next to the core (W only with V),
-// otherwise in the workgroup's slot; the core G always fits (N <= 128: 128 KiB in f64).  Most in LDS first; the core's column pitch is
-// k_jacobi_lds's conflict-free one (16 modulo 32 elements) whenever the plan fits with it, else N | 1.
-struct BsvPlace { bool w, v; int ld; };
+// ---- what the shared plans and launchers take from this family (batched_launchers.hpp) ------------------------------------------------------
 template <typename T>
-BatchedPlan<BsvPlace> bsv_plan(int m, int n) {
-    const int M = std::max(m, n), N = std::min(m, n);
-    const int pad = ((N + 15) / 32) * 32 + 16, odd = N | 1;
-    const BsvPlace places[] = {{true, true, pad}, {true, true, odd}, {false, true, pad}, {false, true, odd}, {false, false, pad}, {false, false, odd}};
-    return batched_first_fit(places, [&](BsvPlace p) { return bsv_lds_bytes<T>(M, N, p.ld, p.w, p.v); },
-        [&](BsvPlace p) { return ((p.w ? 0 : (size_t)M * N) + (p.v ? 0 : (size_t)N * N)) * sizeof(T); }, "svd_rank_batched");
-}
-
-// recompression: the two working copies Wl (m x K), Wr (n x K) and the rotations J (K x K) by bsv_plan's rule next to the core (always in
-// LDS); a copy that does not fit goes to the workgroup's slot, the larger copy first
-struct BrcPlace { bool l, r, v; int ld; };
-template <typename T>
-BatchedPlan<BrcPlace> brc_plan(int m, int n, int K) {
-    const int pad = ((K + 15) / 32) * 32 + 16, odd = K | 1;
-    const bool big_l = m >= n;  // the copy that leaves LDS first
-    const BrcPlace places[] = {{true, true, true, pad},    {true, true, true, odd},    {!big_l, big_l, true, pad},   {!big_l, big_l, true, odd},
-                               {false, false, true, pad}, {false, false, true, odd}, {false, false, false, pad}, {false, false, false, odd}};
-    return batched_first_fit(places, [&](BrcPlace p) { return brc_lds_bytes<T>(m, n, K, p.ld, p.l, p.r, p.v); },
-        [&](BrcPlace p) { return brc_ws_elems(m, n, K, p.l, p.r, p.v) * sizeof(T); }, "lowrank_recompress_batched");
-}
-
-// tall recompression: m <= BRT_H is brc_plan; above it the stage copies are always in the slot (the copy of left never in LDS), Wr and J
-// by brc_plan's rule, and the slot is brt_ws_elems
-template <typename T>
-BatchedPlan<BrcPlace> brt_plan(int m, int n, int K) {
-    if (m <= BRT_H) return brc_plan<T>(m, n, K);
-    const int pad = ((K + 15) / 32) * 32 + 16, odd = K | 1;
-    const BrcPlace places[] = {{false, true, true, pad}, {false, true, true, odd}, {false, false, true, pad}, {false, false, true, odd},
-                               {false, false, false, pad}, {false, false, false, odd}};
-    return batched_first_fit(places, [&](BrcPlace p) { return brc_lds_bytes<T>(m, n, K, p.ld, p.l, p.r, p.v); },
-        [&](BrcPlace p) { return brt_ws_elems(m, n, K, p.l, p.r, p.v) * sizeof(T); }, "lowrank_recompress_tall_batched");
-}
-
-// large recompression: n <= BRT_H is brt_plan (the tall call's plan byte for byte); above it the right factor's stage copies are always in the
-// slot, the left factor's copy by brc_plan's rule for m <= BRT_H and staged above it, J by brc_plan's rule, and the slot is brl_ws_elems
-template <typename T>
-BatchedPlan<BrcPlace> brl_plan(int m, int n, int K) {
-    if (n <= BRT_H) return brt_plan<T>(m, n, K);
-    const int pad = ((K + 15) / 32) * 32 + 16, odd = K | 1;
-    const bool l = m <= BRT_H;  // the only copy that may sit in LDS
-    const BrcPlace places[] = {{l, false, true, pad}, {l, false, true, odd}, {false, false, true, pad}, {false, false, true, odd},
-                               {false, false, false, pad}, {false, false, false, odd}};
-    return batched_first_fit(places, [&](BrcPlace p) { return brc_lds_bytes<T>(m, n, K, p.ld, p.l, p.r, p.v); },
-        [&](BrcPlace p) { return brl_ws_elems(m, n, K, p.l, p.r, p.v) * sizeof(T); }, "lowrank_recompress_large_batched");
-}
-
-// sketched column ID: W (l x n) in LDS when it fits next to the chunk images, else in the workgroup's slot
-template <typename T>
-BatchedPlan<bool> bsi_plan(int l, int n) {
-    return batched_lds_or_ws([&](bool w_lds) { return bsi_lds_bytes<T>(l, n, w_lds); }, (size_t)l * (size_t)n * sizeof(T), "sketch_column_id_rank_batched");
-}
-
-// range step: the working copy of Y^T (n x l) in LDS when it fits next to the chunk images, else in the workgroup's slot behind Q, which is
-// always there (the projection reads it through the chunk staging, as the sketch reads omega)
-template <typename T>
-BatchedPlan<bool> brs_plan(int l, int n) {
-    const bool places[] = {true, false};
-    return batched_first_fit(places, [&](bool w_lds) { return brs_lds_bytes<T>(l, n, w_lds); },
-        [&](bool w_lds) { return (size_t)(w_lds ? 1 : 2) * (size_t)l * (size_t)n * sizeof(T); }, "sketch_range_step_batched");
-}
+struct RealFamily {
+    using RecompressArgs = BrcArgs<T>;
+    using SketchIdArgs = BsiArgs<T>;
+    using RangeStepArgs = BrsArgs<T>;
+    static size_t svd_lds_bytes(int M, int N, BsvPlace p) { return bsv_lds_bytes<T>(M, N, p.ld, p.w, p.v); }
+    static size_t svd_ws_elems(int M, int N, BsvPlace p) { return (p.w ? 0 : (size_t)M * N) + (p.v ? 0 : (size_t)N * N); }
+    static auto svd_kernel(BsvPlace p) { return p.w ? k_batched_svd<T, true, true> : p.v ? k_batched_svd<T, false, true> : k_batched_svd<T, false, false>; }
+    static size_t recompress_lds_bytes(int m, int n, int K, BrcPlace p) { return brc_lds_bytes<T>(m, n, K, p.ld, p.l, p.r, p.v); }
+    static size_t recompress_ws_elems(int form, int m, int n, int K, BrcPlace p) {
+        return form == BRC_LARGE ? brl_ws_elems(m, n, K, p.l, p.r, p.v) : form == BRC_TALL ? brt_ws_elems(m, n, K, p.l, p.r, p.v) : brc_ws_elems(m, n, K, p.l, p.r, p.v);
+    }
+    // n <= BRT_H under the large call is the tall instance under the tall plan (brc_plan returns it): the same kernel, the same bits
+    template <int FORM>
+    static auto recompress_kernel(int, int n) {
+        constexpr bool TALL = FORM != BRC_SMALL, LARGE = FORM == BRC_LARGE;
+        return LARGE && n > BRT_H ? k_batched_recompress<T, TALL, LARGE> : k_batched_recompress<T, TALL, false>;
+    }
+    static size_t sketch_id_lds_bytes(int l, int n, bool w_lds) { return bsi_lds_bytes<T>(l, n, w_lds); }
+    static auto sketch_id_kernel(bool a_rows, bool o_rows) {
+        void (*const kerns[4])(BsiArgs<T>) = {k_batched_sketch_id<T, false, false>, k_batched_sketch_id<T, false, true>, k_batched_sketch_id<T, true, false>,
+                                              k_batched_sketch_id<T, true, true>};
+        return kerns[(a_rows ? 2 : 0) + (o_rows ? 1 : 0)];
+    }
+    static size_t range_step_lds_bytes(int l, int n, bool w_lds) { return brs_lds_bytes<T>(l, n, w_lds); }
+    static auto range_step_kernel(bool a_rows, bool o_rows) {
+        void (*const kerns[4])(BrsArgs<T>) = {k_batched_range_step<T, false, false>, k_batched_range_step<T, false, true>, k_batched_range_step<T, true, false>,
+                                              k_batched_range_step<T, true, true>};
+        return kerns[(a_rows ? 2 : 0) + (o_rows ? 1 : 0)];
+    }
+};
 
 }  // namespace
+
+template <> struct BatchedFamily<double> : RealFamily<double> {};
+template <> struct BatchedFamily<float> : RealFamily<float> {};
 
 // the persistent grid of the whole batched family (the rule: rc_batched_launch.hpp)
 int64_t bid_grid(rc_context *c, const void *kern, size_t lds, size_t ws_per, int32_t count, int64_t *slots) {
@@ -1304,165 +1275,7 @@ int batched_kernel_cap(int device, const void *kern) {
     return last_scratch = it->second;
 }
 
-// the two IDs: plans, kernels and launcher bodies in batched_stages.hpp, one text for real and complex elements
-template <typename T>
-void batched_column_id(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int64_t k, double tol, Mat<T> cm, int64_t cbs, Mat<T> z, int64_t zbs,
-                       int64_t *col_ind, int64_t *ranks) {
-    bid_launch<T>(c, a, abs, count, k, tol, cm, cbs, z, zbs, col_ind, ranks);
-}
-
-template <typename T>
-void batched_two_sided_id(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int64_t k, double tol, Mat<T> cm, int64_t cbs, Mat<T> x, int64_t xbs,
-                          Mat<T> z, int64_t zbs, int64_t *row_ind, int64_t *col_ind, int64_t *ranks) {
-    bts_launch<T>(c, a, abs, count, k, tol, cm, cbs, x, xbs, z, zbs, row_ind, col_ind, ranks);
-}
-
-template <typename T>
-void batched_svd(rc_context *c, Mat<T> a, int64_t abs, int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs, T *s, Mat<T> vt, int64_t vbs,
-                 int64_t *ranks) {
-    const int m = (int)a.rows, n = (int)a.cols;
-    if (count <= 0) return;
-    const bool wide = m < n;
-    const auto plan = bsv_plan<T>(m, n);
-    const BsvPlace at = plan.at;
-    const auto lch = batched_prepare(c, at.w ? k_batched_svd<T, true, true> : at.v ? k_batched_svd<T, false, true> : k_batched_svd<T, false, false>,
-                                   "svd_rank_batched", plan.lds, plan.ws, count);
-    ProfScope ps(c, "op:batched_svd %dx%d k=%lld count=%d grid=%lld slots=%lld plan=W:%s,V:%s,G:lds,ld=%d", m, n, (long long)k, (int)count,
-                 (long long)lch.grid, (long long)lch.slots, at.w ? "lds" : "ws", at.v ? "lds" : "ws", at.ld);
-    // the work orientation's U (M x k) and V^T (k x N): u and vt, or for a wide matrix vt^T and u^T
-    const Mat<T> uo = wide ? vt.t() : u, vo = wide ? u.t() : vt;
-    const int64_t uobs = wide ? vbs : ubs, vobs = wide ? ubs : vbs;
-    lch.launch(a, abs, (int)count, (int)k, tol, uo, uobs, vo, vobs, s, ranks, lch.template workspace<T>(), c->health_word(), at.ld);
-}
-
-// One kernel per entry point: the plan only moves base pointers and pitches.  TALL (rc_lowrank_recompress_tall_batched_*): the same arguments
-// and, for m <= 512, the same plan and the same work per block.  Above it a slot holds every stage's copy (about 90 MiB at 65536 x 128 in
-// f64), so the grid is bounded a second time, by brt_grid_cap: few workgroups run there.  LARGE (rc_lowrank_recompress_large_batched_*): for
-// n <= 512 the tall call's plan; above it the slot holds the right factor's stages too and the same bound applies to the whole slot.
-template <typename T, bool TALL, bool LARGE = false>
-void brc_launch(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride, Mat<T> right, int64_t rbs, const int64_t *in_ranks,
-                int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs, T *s_out, Mat<T> vt, int64_t vbs, int64_t *ranks) {
-    const int m = (int)left.rows, n = (int)right.cols, K = (int)left.cols;
-    if (count <= 0) return;
-    const auto plan = LARGE ? brl_plan<T>(m, n, K) : TALL ? brt_plan<T>(m, n, K) : brc_plan<T>(m, n, K);
-    const BrcPlace at = plan.at;
-    // n <= BRT_H under the large call is the tall instance under the tall plan (brl_plan returns it): the same kernel, the same bits
-    void (*const kern)(BrcArgs<T>) = LARGE && n > BRT_H ? k_batched_recompress<T, TALL, LARGE> : k_batched_recompress<T, TALL, false>;
-    auto lch = batched_prepare(c, kern,
-                               LARGE ? "lowrank_recompress_large_batched" : TALL ? "lowrank_recompress_tall_batched" : "lowrank_recompress_batched", plan.lds,
-                               plan.ws, count);
-    char stages[48] = "";
-    if constexpr (TALL) {
-        lch.grid = brt_grid_cap(lch.grid, plan.ws);
-        lch.slots = brt_grid_cap(lch.slots, plan.ws);
-        // inside plan=: the label keeps the family's fields
-        if (LARGE) snprintf(stages, sizeof stages, "stages=%d,rstages=%d,", brt_stages(m, K), brt_stages(n, K));
-        else snprintf(stages, sizeof stages, "stages=%d,", brt_stages(m, K));
-    }
-    ProfScope ps(c, "op:batched_recompress%s %dx%d k=%d count=%d grid=%lld slots=%lld plan=%sL:%s,R:%s,V:%s,G:lds,ld=%d,kk=%d%s%s",
-                 LARGE ? "_large" : TALL ? "_tall" : "", m, n, K,
-                 (int)count, (long long)lch.grid, (long long)lch.slots, stages, at.l ? "lds" : "ws", at.r ? "lds" : "ws", at.v ? "lds" : "ws", at.ld,
-                 (int)std::min<int64_t>(k, K), mid.p ? ",mid" : "", s ? ",s" : "");
-    BrcArgs<T> a;
-    a.left = left; a.mid = mid; a.right = right; a.u = u; a.vt = vt;
-    a.lbs = lbs; a.mbs = mbs; a.rbs = rbs; a.ubs = ubs; a.vbs = vbs; a.s_stride = s_stride;
-    a.s = s; a.in_ranks = in_ranks; a.s_out = s_out; a.ranks = ranks;
-    a.ws = lch.template workspace<T>();
-    a.health = c->health_word();
-    a.tol = tol; a.count = (int)count; a.k = (int)std::min<int64_t>(k, K); a.ldg = at.ld;
-    a.l_lds = at.l; a.r_lds = at.r; a.v_lds = at.v;
-    lch.launch(a);
-}
-template <typename T>
-void batched_lowrank_recompress(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride, Mat<T> right, int64_t rbs,
-                                const int64_t *in_ranks, int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs, T *s_out, Mat<T> vt, int64_t vbs,
-                                int64_t *ranks) {
-    brc_launch<T, false>(c, left, lbs, mid, mbs, s, s_stride, right, rbs, in_ranks, count, k, tol, u, ubs, s_out, vt, vbs, ranks);
-}
-template <typename T>
-void batched_lowrank_recompress_tall(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride, Mat<T> right,
-                                     int64_t rbs, const int64_t *in_ranks, int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs, T *s_out, Mat<T> vt,
-                                     int64_t vbs, int64_t *ranks) {
-    brc_launch<T, true>(c, left, lbs, mid, mbs, s, s_stride, right, rbs, in_ranks, count, k, tol, u, ubs, s_out, vt, vbs, ranks);
-}
-
-template <typename T>
-void batched_lowrank_recompress_large(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride, Mat<T> right,
-                                      int64_t rbs, const int64_t *in_ranks, int32_t count, int64_t k, double tol, Mat<T> u, int64_t ubs, T *s_out, Mat<T> vt,
-                                      int64_t vbs, int64_t *ranks) {
-    brc_launch<T, true, true>(c, left, lbs, mid, mbs, s, s_stride, right, rbs, in_ranks, count, k, tol, u, ubs, s_out, vt, vbs, ranks);
-}
-
-// the large launcher's plan as numbers (rc_lowrank_recompress_large_batched_plan): the stages of both factors at inner width K, bytes of one
-// slot, and the grid brt_grid_cap leaves of `resident` workgroups
-void batched_lowrank_recompress_large_plan(int64_t m, int64_t n, int64_t K, bool f64, int64_t resident, int64_t *stages_left, int64_t *stages_right,
-                                           int64_t *slot_bytes, int64_t *grid) {
-    const size_t ws = f64 ? brl_plan<double>((int)m, (int)n, (int)K).ws : brl_plan<float>((int)m, (int)n, (int)K).ws;
-    *stages_left = brt_stages((int)m, (int)K);
-    *stages_right = brt_stages((int)n, (int)K);
-    *slot_bytes = (int64_t)ws;
-    *grid = brt_grid_cap(resident, ws);
-}
-
-// the tall launcher's plan as numbers (rc_lowrank_recompress_tall_batched_plan): stages at inner width K, bytes of one slot, and the grid
-// brt_grid_cap leaves of `resident` workgroups
-void batched_lowrank_recompress_tall_plan(int64_t m, int64_t n, int64_t K, bool f64, int64_t resident, int64_t *stages, int64_t *slot_bytes, int64_t *grid) {
-    const size_t ws = f64 ? brt_plan<double>((int)m, (int)n, (int)K).ws : brt_plan<float>((int)m, (int)n, (int)K).ws;
-    *stages = brt_stages((int)m, (int)K);
-    *slot_bytes = (int64_t)ws;
-    *grid = brt_grid_cap(resident, ws);
-}
-
-// The plan only moves W's base pointer and pitch, so it cannot change a block's bits.  Four instances of the kernel, by the index of a and
-// of omega that the staging loads' lanes run along; each element of Y is summed in the same order in all four.  The label carries the
-// launched instance's scratch bytes per thread (the f64 instances sit at the register bound of two waves per SIMD, so a compiler that
-// spills more shows up in every profile and in tools/batched_sketch_id_bench.py).
-template <typename T>
-void batched_sketch_column_id(rc_context *c, Mat<T> a, int64_t abs, Mat<T> omega, int64_t obs, int32_t count, int64_t kk, double tol, Mat<T> y, int64_t ybs,
-                              Mat<T> cm, int64_t cbs, Mat<T> z, int64_t zbs, int64_t *col_ind, int64_t *ranks) {
-    const int m = (int)a.rows, n = (int)a.cols, l = (int)omega.rows;
-    if (count <= 0) return;
-    const auto plan = bsi_plan<T>(l, n);
-    // the lanes of the staging loads along the smaller stride of a and of omega (bid_load's rule for a)
-    const bool a_rows = a.rs <= a.cs, o_rows = omega.rs < omega.cs;
-    void (*const kerns[4])(BsiArgs<T>) = {k_batched_sketch_id<T, false, false>, k_batched_sketch_id<T, false, true>, k_batched_sketch_id<T, true, false>,
-                                          k_batched_sketch_id<T, true, true>};
-    const auto lch = batched_prepare(c, kerns[(a_rows ? 2 : 0) + (o_rows ? 1 : 0)], "sketch_column_id_rank_batched", plan.lds, plan.ws, count);
-    ProfScope ps(c, "op:batched_sketch_id %dx%d k=%lld count=%d grid=%lld slots=%lld plan=W:%s,l=%d,rows=%d,cols=%d,scratch=%d", m, n, (long long)kk,
-                 (int)count, (long long)lch.grid, (long long)lch.slots, plan.at ? "lds" : "ws", l, BSI_ROWS, BSI_COLS, lch.scratch);
-    BsiArgs<T> g;
-    g.a = a; g.omega = omega; g.y = y; g.c = cm; g.z = z;
-    g.abs = abs; g.obs = obs; g.ybs = ybs; g.cbs = cbs; g.zbs = zbs;
-    g.col_ind = col_ind; g.ranks = ranks;
-    g.ws = lch.template workspace<T>();
-    g.tol = tol; g.count = (int)count; g.kk = (int)kk; g.w_lds = plan.at;
-    lch.launch(g);
-}
-
-// The plan only moves the working copy's base pointer and pitch, and the four instances (by the index of a and of omega that the sketch's
-// staging loads run along; the projection's run along the other index of a and along n in Q) sum every element in the same order, so
-// neither can change a block's bits.  The label carries the scratch bytes per thread like the sketched ID's.
-template <typename T>
-void batched_sketch_range_step(rc_context *c, Mat<T> a, int64_t abs, Mat<T> omega, int64_t obs, int32_t count, Mat<T> y, int64_t ybs, Mat<T> q, int64_t qbs,
-                               Mat<T> p, int64_t pbs, int64_t *ranks) {
-    const int m = (int)a.rows, n = (int)a.cols, l = (int)omega.rows;
-    if (count <= 0) return;
-    const auto plan = brs_plan<T>(l, n);
-    const bool a_rows = a.rs <= a.cs, o_rows = omega.rs < omega.cs;
-    void (*const kerns[4])(BrsArgs<T>) = {k_batched_range_step<T, false, false>, k_batched_range_step<T, false, true>, k_batched_range_step<T, true, false>,
-                                          k_batched_range_step<T, true, true>};
-    const auto lch = batched_prepare(c, kerns[(a_rows ? 2 : 0) + (o_rows ? 1 : 0)], "sketch_range_step_batched", plan.lds, plan.ws, count);
-    ProfScope ps(c, "op:batched_range_step %dx%d l=%d count=%d grid=%lld slots=%lld plan=W:%s,Q:ws,rows=%d,cols=%d,scratch=%d", m, n, l, (int)count,
-                 (long long)lch.grid, (long long)lch.slots, plan.at ? "lds" : "ws", BSI_ROWS, BSI_COLS, lch.scratch);
-    BrsArgs<T> g;
-    g.a = a; g.omega = omega; g.y = y; g.q = q; g.p = p;
-    g.abs = abs; g.obs = obs; g.ybs = ybs; g.qbs = qbs; g.pbs = pbs;
-    g.ranks = ranks;
-    g.ws = lch.template workspace<T>();
-    g.slot = plan.ws / sizeof(T);
-    g.count = (int)count; g.w_lds = plan.at;
-    lch.launch(g);
-}
+// (the launchers of the two IDs, the SVD, the recompressions, the sketched column ID and the range step: batched_launchers.hpp)
 
 // No plan: the two chunk images are the whole LDS and there is no workspace.  The grid is bid_grid's over the (block, panel) units, so it
 // does not move a unit's bits either; the four instances are the sketched ID's.  The label carries the units and the scratch bytes per
@@ -1490,39 +1303,8 @@ void batched_sketch_product(rc_context *c, Mat<T> a, int64_t abs, Mat<T> omega, 
 template void batched_sketch_product<double>(rc_context *, Mat<double>, int64_t, Mat<double>, int64_t, int32_t, Mat<double>, int64_t);
 template void batched_sketch_product<float>(rc_context *, Mat<float>, int64_t, Mat<float>, int64_t, int32_t, Mat<float>, int64_t);
 
-template void batched_sketch_range_step<double>(rc_context *, Mat<double>, int64_t, Mat<double>, int64_t, int32_t, Mat<double>, int64_t, Mat<double>, int64_t,
-                                                Mat<double>, int64_t, int64_t *);
-template void batched_sketch_range_step<float>(rc_context *, Mat<float>, int64_t, Mat<float>, int64_t, int32_t, Mat<float>, int64_t, Mat<float>, int64_t,
-                                               Mat<float>, int64_t, int64_t *);
-
-template void batched_sketch_column_id<double>(rc_context *, Mat<double>, int64_t, Mat<double>, int64_t, int32_t, int64_t, double, Mat<double>, int64_t, Mat<double>,
-                                               int64_t, Mat<double>, int64_t, int64_t *, int64_t *);
-template void batched_sketch_column_id<float>(rc_context *, Mat<float>, int64_t, Mat<float>, int64_t, int32_t, int64_t, double, Mat<float>, int64_t, Mat<float>,
-                                              int64_t, Mat<float>, int64_t, int64_t *, int64_t *);
-
-template void batched_lowrank_recompress<double>(rc_context *, Mat<double>, int64_t, Mat<double>, int64_t, const double *, int64_t, Mat<double>, int64_t,
-                                                 const int64_t *, int32_t, int64_t, double, Mat<double>, int64_t, double *, Mat<double>, int64_t, int64_t *);
-template void batched_lowrank_recompress<float>(rc_context *, Mat<float>, int64_t, Mat<float>, int64_t, const float *, int64_t, Mat<float>, int64_t,
-                                                const int64_t *, int32_t, int64_t, double, Mat<float>, int64_t, float *, Mat<float>, int64_t, int64_t *);
-template void batched_lowrank_recompress_tall<double>(rc_context *, Mat<double>, int64_t, Mat<double>, int64_t, const double *, int64_t, Mat<double>, int64_t,
-                                                      const int64_t *, int32_t, int64_t, double, Mat<double>, int64_t, double *, Mat<double>, int64_t, int64_t *);
-template void batched_lowrank_recompress_tall<float>(rc_context *, Mat<float>, int64_t, Mat<float>, int64_t, const float *, int64_t, Mat<float>, int64_t,
-                                                     const int64_t *, int32_t, int64_t, double, Mat<float>, int64_t, float *, Mat<float>, int64_t, int64_t *);
-
-template void batched_lowrank_recompress_large<double>(rc_context *, Mat<double>, int64_t, Mat<double>, int64_t, const double *, int64_t, Mat<double>, int64_t,
-                                                       const int64_t *, int32_t, int64_t, double, Mat<double>, int64_t, double *, Mat<double>, int64_t, int64_t *);
-template void batched_lowrank_recompress_large<float>(rc_context *, Mat<float>, int64_t, Mat<float>, int64_t, const float *, int64_t, Mat<float>, int64_t,
-                                                      const int64_t *, int32_t, int64_t, double, Mat<float>, int64_t, float *, Mat<float>, int64_t, int64_t *);
-
-template void batched_column_id<double>(rc_context *, Mat<double>, int64_t, int32_t, int64_t, double, Mat<double>, int64_t, Mat<double>, int64_t, int64_t *, int64_t *);
-template void batched_column_id<float>(rc_context *, Mat<float>, int64_t, int32_t, int64_t, double, Mat<float>, int64_t, Mat<float>, int64_t, int64_t *, int64_t *);
-template void batched_two_sided_id<double>(rc_context *, Mat<double>, int64_t, int32_t, int64_t, double, Mat<double>, int64_t, Mat<double>, int64_t,
-                                           Mat<double>, int64_t, int64_t *, int64_t *, int64_t *);
-template void batched_two_sided_id<float>(rc_context *, Mat<float>, int64_t, int32_t, int64_t, double, Mat<float>, int64_t, Mat<float>, int64_t,
-                                          Mat<float>, int64_t, int64_t *, int64_t *, int64_t *);
-
-template void batched_svd<double>(rc_context *, Mat<double>, int64_t, int32_t, int64_t, double, Mat<double>, int64_t, double *, Mat<double>, int64_t,
-                                  int64_t *);
-template void batched_svd<float>(rc_context *, Mat<float>, int64_t, int32_t, int64_t, double, Mat<float>, int64_t, float *, Mat<float>, int64_t, int64_t *);
+RC_INSTANTIATE_BATCHED_SKETCH(double, float)
+RC_INSTANTIATE_BATCHED_RECOMPRESS(double, float)
+RC_INSTANTIATE_BATCHED_ID_SVD(double, float)
 
 }  // namespace rc

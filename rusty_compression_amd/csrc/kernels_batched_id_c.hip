@@ -9,9 +9,11 @@
 // The structure of kernels_batched_id.hip (one persistent workgroup of 256 threads per matrix, the same three device stages, the same
 // grid and workspace rule, and the launch path of rc_batched_launch.hpp).  The stages that read the same for real and complex elements
 // are that file's too: they stand once in batched_stages.hpp, which this file instantiates for cplx<double> and cplx<float> (the fill,
-// the norms, bid_qrcp, bid_z, k_batched_id and k_batched_two_sided with their plans and launcher bodies, bsv_jacobi, brt_stack_load).
+// the norms, bid_qrcp, bid_z, k_batched_id and k_batched_two_sided with their plans, bsv_jacobi, brt_stack_load).
 // Here stay the complex family's own routines (bic_apply, bsc_round, bsc_phase, the form_u routines, the core products) and the SVD,
-// recompression, sketch and range-step kernels.  The arithmetic is that of the lone complex path in rc_complex.hip:
+// recompression, sketch and range-step kernels.  No plan and no launcher body stands here: they are written once for all four element
+// types in batched_launchers.hpp, and the file ends with what they take from this family (ComplexFamily: the Args structs, the LDS and
+// workspace sizes and the instance to launch) and their instantiation for cplx<double> and cplx<float>.  The arithmetic is that of the lone complex path in rc_complex.hip:
 //   * interleaved (re, im) data (cplx<R>, CV<R> and their arithmetic: rc_cplx.hpp); the partial norms vn1 / vn2 are real, W and the tile complex;
 //   * ?larfg for complex (k_c_qr_pivot_reflect): beta = -copysign(lapy3(alpha.re, alpha.im, xnorm), alpha.re) is real, tau complex,
 //     the scale 1 / (alpha - beta) by Smith division; H = I only when xnorm == 0 and alpha.im == 0;
@@ -30,6 +32,7 @@
 // Every operation below commutes exactly with negating all imaginary parts (round to nearest is sign-symmetric, and each real part
 // is even, each imaginary part odd in the imaginary inputs), so conj(A) gives the same permutations and ranks and the conjugate
 // of every factor, bit for bit.
+#include "batched_launchers.hpp"
 #include "batched_stages.hpp"
 #include "rc_batched_launch.hpp"
 #include "rc_common.hpp"
@@ -1259,296 +1262,56 @@ __global__ __launch_bounds__(BID_THREADS, 2) void k_batched_range_step_c(BrscArg
 }
 #undef RC_BSC_PASSES
 
-// ---- the plans: the real launchers' rules (kernels_batched_id.hip) on complex elements, as pure functions of the shapes ---------------------
-
-// SVD: bsv_plan's list with a third place for the core; the last keeps W, G and J in the workgroup's slot of the grid-bounded workspace (a
-// 128 x 128 c64 core alone takes 256 KiB, more than BID_MAX_LDS)
-struct BscPlace { bool w, v, g; int ld; };
+// ---- what the shared plans and launchers take from this family (batched_launchers.hpp) ------------------------------------------------------
 template <typename R>
-BatchedPlan<BscPlace> bsc_plan(int m, int n) {
-    const int M = std::max(m, n), N = std::min(m, n);
-    const int pad = ((N + 15) / 32) * 32 + 16, odd = N | 1;
-    const BscPlace places[] = {{true, true, true, pad},    {true, true, true, odd},    {false, true, true, pad}, {false, true, true, odd},
-                               {false, false, true, pad},  {false, false, true, odd},  {false, false, false, N}};
-    return batched_first_fit(places, [&](BscPlace p) { return bsc_lds_bytes<R>(M, N, p.ld, p.w, p.v, p.g); },
-        [&](BscPlace p) { return bsc_ws_elems(M, N, p.ld, p.w, p.v, p.g) * sizeof(cplx<R>); }, "svd_rank_batched");
-}
-
-// recompression: brc_plan's list (most in LDS first, the padded core pitch before the odd one, the larger copy to the workspace first)
-// with the fourth placement bsc_plan has: a complex core that does not fit in LDS at either pitch (c64, K >= 100) goes to the
-// workgroup's slot with everything else, at pitch K
-struct BrccPlace { bool l, r, v, g; int ld; };
-template <typename R>
-BatchedPlan<BrccPlace> brcc_plan(int m, int n, int K) {
-    const int pad = ((K + 15) / 32) * 32 + 16, odd = K | 1;
-    const bool big_l = m >= n;  // the copy that leaves LDS first
-    const BrccPlace places[] = {{true, true, true, true, pad},      {true, true, true, true, odd},     {!big_l, big_l, true, true, pad},
-                                {!big_l, big_l, true, true, odd},   {false, false, true, true, pad},   {false, false, true, true, odd},
-                                {false, false, false, true, pad},   {false, false, false, true, odd},  {false, false, false, false, K}};
-    return batched_first_fit(places, [&](BrccPlace p) { return brcc_lds_bytes<R>(m, n, K, p.ld, p.l, p.r, p.v, p.g); },
-        [&](BrccPlace p) { return brcc_ws_elems(m, n, K, p.ld, p.l, p.r, p.v, p.g) * sizeof(cplx<R>); }, "lowrank_recompress_batched");
-}
-
-// tall recompression: m <= BRT_H is brcc_plan; above it the stage copies are always in the slot (the copy of left never competes for LDS), Wr,
-// J and G by brcc_plan's rule, and the slot is brtc_ws_elems
-template <typename R>
-BatchedPlan<BrccPlace> brtc_plan(int m, int n, int K) {
-    if (m <= BRT_H) return brcc_plan<R>(m, n, K);
-    const int pad = ((K + 15) / 32) * 32 + 16, odd = K | 1;
-    const BrccPlace places[] = {{false, true, true, true, pad},     {false, true, true, true, odd},    {false, false, true, true, pad},
-                                {false, false, true, true, odd},    {false, false, false, true, pad},  {false, false, false, true, odd},
-                                {false, false, false, false, K}};
-    return batched_first_fit(places, [&](BrccPlace p) { return brcc_lds_bytes<R>(m, n, K, p.ld, p.l, p.r, p.v, p.g); },
-        [&](BrccPlace p) { return brtc_ws_elems(m, n, K, p.ld, p.l, p.r, p.v, p.g) * sizeof(cplx<R>); }, "lowrank_recompress_tall_complex_batched");
-}
-
-// large recompression: n <= BRT_H is brtc_plan (the tall complex call's plan byte for byte); above it the right factor's stage copies are always
-// in the slot, the left factor's copy by brcc_plan's rule for m <= BRT_H and staged above it, J and G by brcc_plan's rule, and the slot is
-// brlc_ws_elems
-template <typename R>
-BatchedPlan<BrccPlace> brlc_plan(int m, int n, int K) {
-    if (n <= BRT_H) return brtc_plan<R>(m, n, K);
-    const int pad = ((K + 15) / 32) * 32 + 16, odd = K | 1;
-    const bool l = m <= BRT_H;  // the only copy that may sit in LDS (for m > BRT_H the first two places repeat the next two: first fit skips nothing)
-    const BrccPlace places[] = {{l, false, true, true, pad},       {l, false, true, true, odd},      {false, false, true, true, pad},
-                                {false, false, true, true, odd},   {false, false, false, true, pad}, {false, false, false, true, odd},
-                                {false, false, false, false, K}};
-    return batched_first_fit(places, [&](BrccPlace p) { return brcc_lds_bytes<R>(m, n, K, p.ld, p.l, p.r, p.v, p.g); },
-        [&](BrccPlace p) { return brlc_ws_elems(m, n, K, p.ld, p.l, p.r, p.v, p.g) * sizeof(cplx<R>); }, "lowrank_recompress_complex_large_batched");
-}
-
-// sketched column ID: W (l x n complex) in LDS when it fits next to the chunk images, else in the workgroup's slot
-template <typename R>
-BatchedPlan<bool> bscid_plan(int l, int n) {
-    return batched_lds_or_ws([&](bool w_lds) { return bsc_lds_bytes<R>(l, n, w_lds); }, (size_t)l * (size_t)n * sizeof(cplx<R>), "sketch_column_id_rank_batched");
-}
-
-// range step: the working copy of Y^T (n x l complex) in LDS when it fits next to the two pairs of chunk planes, else in the workgroup's slot
-// behind conj(Q), which is always there (the projection reads it through the chunk staging, as the sketch reads omega)
-template <typename R>
-BatchedPlan<bool> brsc_plan(int l, int n) {
-    const bool places[] = {true, false};
-    return batched_first_fit(places, [&](bool w_lds) { return brsc_lds_bytes<R>(l, n, w_lds); },
-        [&](bool w_lds) { return (size_t)(w_lds ? 1 : 2) * (size_t)l * (size_t)n * sizeof(cplx<R>); }, "sketch_range_step_complex_batched");
-}
+struct ComplexFamily {
+    using RecompressArgs = BrcCArgs<R>;
+    using SketchIdArgs = BscArgs<R>;
+    using RangeStepArgs = BrscArgs<R>;
+    static size_t svd_lds_bytes(int M, int N, BsvPlace p) { return bsc_lds_bytes<R>(M, N, p.ld, p.w, p.v, p.g); }
+    static size_t svd_ws_elems(int M, int N, BsvPlace p) { return bsc_ws_elems(M, N, p.ld, p.w, p.v, p.g); }
+    static auto svd_kernel(BsvPlace p) {
+        return p.w   ? k_batched_svd_c<R, true, true, true>
+               : p.v ? k_batched_svd_c<R, false, true, true>
+               : p.g ? k_batched_svd_c<R, false, false, true>
+                     : k_batched_svd_c<R, false, false, false>;
+    }
+    static size_t recompress_lds_bytes(int m, int n, int K, BrcPlace p) { return brcc_lds_bytes<R>(m, n, K, p.ld, p.l, p.r, p.v, p.g); }
+    static size_t recompress_ws_elems(int form, int m, int n, int K, BrcPlace p) {
+        return form == BRC_LARGE  ? brlc_ws_elems(m, n, K, p.ld, p.l, p.r, p.v, p.g)
+               : form == BRC_TALL ? brtc_ws_elems(m, n, K, p.ld, p.l, p.r, p.v, p.g)
+                                  : brcc_ws_elems(m, n, K, p.ld, p.l, p.r, p.v, p.g);
+    }
+    // m <= BRT_H under the tall call is the small instance, n <= BRT_H under the large call the tall call's: the same bits at the same rate
+    template <int FORM>
+    static auto recompress_kernel(int m, int n) {
+        constexpr bool TALL = FORM != BRC_SMALL, LARGE = FORM == BRC_LARGE;
+        return LARGE && n > BRT_H   ? k_batched_recompress_c<R, TALL, LARGE>
+               : TALL && m > BRT_H ? k_batched_recompress_c<R, TALL>
+                                   : k_batched_recompress_c<R, false>;
+    }
+    static size_t sketch_id_lds_bytes(int l, int n, bool w_lds) { return bsc_lds_bytes<R>(l, n, w_lds); }
+    static auto sketch_id_kernel(bool a_rows, bool o_rows) {
+        void (*const kerns[4])(BscArgs<R>) = {k_batched_sketch_id_c<R, false, false>, k_batched_sketch_id_c<R, false, true>, k_batched_sketch_id_c<R, true, false>,
+                                              k_batched_sketch_id_c<R, true, true>};
+        return kerns[(a_rows ? 2 : 0) + (o_rows ? 1 : 0)];
+    }
+    static size_t range_step_lds_bytes(int l, int n, bool w_lds) { return brsc_lds_bytes<R>(l, n, w_lds); }
+    static auto range_step_kernel(bool a_rows, bool o_rows) {
+        void (*const kerns[4])(BrscArgs<R>) = {k_batched_range_step_c<R, false, false>, k_batched_range_step_c<R, false, true>,
+                                               k_batched_range_step_c<R, true, false>, k_batched_range_step_c<R, true, true>};
+        return kerns[(a_rows ? 2 : 0) + (o_rows ? 1 : 0)];
+    }
+};
 
 }  // namespace
 
-template <typename R>
-void batched_column_id_c(rc_context *c, const rc_matrix &a_, int64_t abs, int32_t count, int64_t k, double tol, const rc_matrix &cm_, int64_t cbs,
-                         const rc_matrix &z_, int64_t zbs, int64_t *col_ind, int64_t *ranks) {
-    const CV<R> a = view_of<R>(a_), cm = view_of<R>(cm_), z = view_of<R>(z_);
-    bid_launch<cplx<R>>(c, a, abs, count, k, tol, cm, cbs, z, zbs, col_ind, ranks);
-}
+template <> struct BatchedFamily<cplx<double>> : ComplexFamily<double> {};
+template <> struct BatchedFamily<cplx<float>> : ComplexFamily<float> {};
 
-template <typename R>
-void batched_two_sided_id_c(rc_context *c, const rc_matrix &a_, int64_t abs, int32_t count, int64_t k, double tol, const rc_matrix &cm_, int64_t cbs,
-                            const rc_matrix &x_, int64_t xbs, const rc_matrix &z_, int64_t zbs, int64_t *row_ind, int64_t *col_ind, int64_t *ranks) {
-    const CV<R> a = view_of<R>(a_), cm = view_of<R>(cm_), x = view_of<R>(x_), z = view_of<R>(z_);
-    bts_launch<cplx<R>>(c, a, abs, count, k, tol, cm, cbs, x, xbs, z, zbs, row_ind, col_ind, ranks);
-}
-
-template <typename R>
-void batched_svd_c(rc_context *c, const rc_matrix &a_, int64_t abs, int32_t count, int64_t k, double tol, const rc_matrix &u_, int64_t ubs, R *s,
-                   const rc_matrix &vt_, int64_t vbs, int64_t *ranks) {
-    const CV<R> a = view_of<R>(a_), u = view_of<R>(u_), vt = view_of<R>(vt_);
-    const int m = (int)a.rows, n = (int)a.cols;
-    if (count <= 0) return;
-    const bool wide = m < n;
-    const auto plan = bsc_plan<R>(m, n);
-    const BscPlace at = plan.at;
-    const auto lch = batched_prepare(c,
-                                     at.w   ? k_batched_svd_c<R, true, true, true>
-                                     : at.v ? k_batched_svd_c<R, false, true, true>
-                                     : at.g ? k_batched_svd_c<R, false, false, true>
-                                            : k_batched_svd_c<R, false, false, false>,
-                                     "svd_rank_batched", plan.lds, plan.ws, count);
-    ProfScope ps(c, "op:batched_svd<complex> %dx%d k=%lld count=%d grid=%lld slots=%lld plan=W:%s,V:%s,G:%s,ld=%d", m, n, (long long)k, (int)count,
-                 (long long)lch.grid, (long long)lch.slots, at.w ? "lds" : "ws", at.v ? "lds" : "ws", at.g ? "lds" : "ws", at.ld);
-    // the work orientation's U (M x k) and V^H (k x N): u and vt, or for a wide matrix the plain transposed views vt^T and u^T
-    const CV<R> uo = wide ? vt.t() : u, vo = wide ? u.t() : vt;
-    const int64_t uobs = wide ? vbs : ubs, vobs = wide ? ubs : vbs;
-    lch.launch(a, abs, (int)count, (int)k, tol, uo, uobs, vo, vobs, s, ranks, lch.template workspace<cplx<R>>(), c->health_word(), at.ld);
-}
-
-// The plan only moves base pointers and pitches, and no sum depends on a pitch, so it cannot change a block's bits.
-// TALL (rc_lowrank_recompress_tall_complex_batched_*): the same arguments and, for m <= 512, the same plan and the same kernel instance, so the
-// same bits at the same rate.  Above it the TALL instance runs and a slot holds every stage's copy (173 MiB at 65536 x 128 in c64), so the grid
-// is bounded a second time, by brt_grid_cap: few workgroups run there.  LARGE (rc_lowrank_recompress_complex_large_batched_*): for n <= 512 the
-// tall complex call's plan and instances (brlc_plan returns that plan), so its bits at its rate; above it the LARGE instance, the slot holds the
-// right factor's stages too and the same bound applies to the whole slot.
-template <typename R, bool TALL, bool LARGE = false>
-void brcc_launch(rc_context *c, const rc_matrix &left_, int64_t lbs, const rc_matrix &mid_, int64_t mbs, const R *s, int64_t s_stride, const rc_matrix &right_,
-                 int64_t rbs, const int64_t *in_ranks, int32_t count, int64_t k, double tol, const rc_matrix &u_, int64_t ubs, R *s_out, const rc_matrix &vt_,
-                 int64_t vbs, int64_t *ranks) {
-    const CV<R> left = view_of<R>(left_), mid = view_of<R>(mid_), right = view_of<R>(right_), u = view_of<R>(u_), vt = view_of<R>(vt_);
-    const int m = (int)left.rows, n = (int)right.cols, K = (int)left.cols;
-    if (count <= 0) return;
-    const auto plan = LARGE ? brlc_plan<R>(m, n, K) : TALL ? brtc_plan<R>(m, n, K) : brcc_plan<R>(m, n, K);
-    const BrccPlace at = plan.at;
-    void (*const kern)(BrcCArgs<R>) = LARGE && n > BRT_H       ? k_batched_recompress_c<R, TALL, LARGE>
-                                      : TALL && m > BRT_H ? k_batched_recompress_c<R, TALL>
-                                                          : k_batched_recompress_c<R, false>;
-    auto lch = batched_prepare(c, kern,
-                               LARGE  ? "lowrank_recompress_complex_large_batched"
-                               : TALL ? "lowrank_recompress_tall_complex_batched"
-                                      : "lowrank_recompress_batched",
-                               plan.lds, plan.ws, count);
-    char stages[48] = "";
-    if constexpr (TALL) {
-        lch.grid = brt_grid_cap(lch.grid, plan.ws);
-        lch.slots = brt_grid_cap(lch.slots, plan.ws);
-        // inside plan=: the label keeps the family's fields
-        if (LARGE) snprintf(stages, sizeof stages, "stages=%d,rstages=%d,", brt_stages(m, K), brt_stages(n, K));
-        else snprintf(stages, sizeof stages, "stages=%d,", brt_stages(m, K));
-    }
-    ProfScope ps(c, "op:batched_recompress%s<complex> %dx%d k=%d count=%d grid=%lld slots=%lld plan=%sL:%s,R:%s,V:%s,G:%s,ld=%d,kk=%d%s%s",
-                 LARGE ? "_large" : TALL ? "_tall" : "", m, n, K, (int)count, (long long)lch.grid, (long long)lch.slots, stages, at.l ? "lds" : "ws",
-                 at.r ? "lds" : "ws", at.v ? "lds" : "ws", at.g ? "lds" : "ws", at.ld, (int)std::min<int64_t>(k, K), mid.p ? ",mid" : "", s ? ",s" : "");
-    BrcCArgs<R> a;
-    a.left = left; a.mid = mid; a.right = right; a.u = u; a.vt = vt;
-    a.lbs = lbs; a.mbs = mbs; a.rbs = rbs; a.ubs = ubs; a.vbs = vbs; a.s_stride = s_stride;
-    a.s = s; a.in_ranks = in_ranks; a.s_out = s_out; a.ranks = ranks;
-    a.ws = lch.template workspace<cplx<R>>();
-    a.health = c->health_word();
-    a.tol = tol; a.count = (int)count; a.k = (int)std::min<int64_t>(k, K); a.ldg = at.ld;
-    a.l_lds = at.l; a.r_lds = at.r; a.v_lds = at.v; a.g_lds = at.g;
-    lch.launch(a);
-}
-template <typename R>
-void batched_lowrank_recompress_c(rc_context *c, const rc_matrix &left, int64_t lbs, const rc_matrix &mid, int64_t mbs, const R *s, int64_t s_stride,
-                                  const rc_matrix &right, int64_t rbs, const int64_t *in_ranks, int32_t count, int64_t k, double tol, const rc_matrix &u,
-                                  int64_t ubs, R *s_out, const rc_matrix &vt, int64_t vbs, int64_t *ranks) {
-    brcc_launch<R, false>(c, left, lbs, mid, mbs, s, s_stride, right, rbs, in_ranks, count, k, tol, u, ubs, s_out, vt, vbs, ranks);
-}
-template <typename R>
-void batched_lowrank_recompress_tall_c(rc_context *c, const rc_matrix &left, int64_t lbs, const rc_matrix &mid, int64_t mbs, const R *s, int64_t s_stride,
-                                       const rc_matrix &right, int64_t rbs, const int64_t *in_ranks, int32_t count, int64_t k, double tol, const rc_matrix &u,
-                                       int64_t ubs, R *s_out, const rc_matrix &vt, int64_t vbs, int64_t *ranks) {
-    brcc_launch<R, true>(c, left, lbs, mid, mbs, s, s_stride, right, rbs, in_ranks, count, k, tol, u, ubs, s_out, vt, vbs, ranks);
-}
-
-template <typename R>
-void batched_lowrank_recompress_large_c(rc_context *c, const rc_matrix &left, int64_t lbs, const rc_matrix &mid, int64_t mbs, const R *s, int64_t s_stride,
-                                        const rc_matrix &right, int64_t rbs, const int64_t *in_ranks, int32_t count, int64_t k, double tol, const rc_matrix &u,
-                                        int64_t ubs, R *s_out, const rc_matrix &vt, int64_t vbs, int64_t *ranks) {
-    brcc_launch<R, true, true>(c, left, lbs, mid, mbs, s, s_stride, right, rbs, in_ranks, count, k, tol, u, ubs, s_out, vt, vbs, ranks);
-}
-
-// the complex large launcher's plan as numbers (rc_lowrank_recompress_complex_large_batched_plan): the stages of both factors at inner width K,
-// bytes of one slot, and the grid brt_grid_cap leaves of `resident` workgroups
-void batched_lowrank_recompress_large_c_plan(int64_t m, int64_t n, int64_t K, bool c64, int64_t resident, int64_t *stages_left, int64_t *stages_right,
-                                             int64_t *slot_bytes, int64_t *grid) {
-    const size_t ws = c64 ? brlc_plan<double>((int)m, (int)n, (int)K).ws : brlc_plan<float>((int)m, (int)n, (int)K).ws;
-    *stages_left = brt_stages((int)m, (int)K);
-    *stages_right = brt_stages((int)n, (int)K);
-    *slot_bytes = (int64_t)ws;
-    *grid = brt_grid_cap(resident, ws);
-}
-
-// the complex tall launcher's plan as numbers (rc_lowrank_recompress_tall_complex_batched_plan): stages at inner width K, bytes of one slot, and
-// the grid brt_grid_cap leaves of `resident` workgroups
-void batched_lowrank_recompress_tall_c_plan(int64_t m, int64_t n, int64_t K, bool c64, int64_t resident, int64_t *stages, int64_t *slot_bytes, int64_t *grid) {
-    const size_t ws = c64 ? brtc_plan<double>((int)m, (int)n, (int)K).ws : brtc_plan<float>((int)m, (int)n, (int)K).ws;
-    *stages = brt_stages((int)m, (int)K);
-    *slot_bytes = (int64_t)ws;
-    *grid = brt_grid_cap(resident, ws);
-}
-
-// The plan only moves W's base pointer and pitch, so it cannot change a block's bits.  Four instances of the kernel, by the index of a and of
-// omega that the staging loads' lanes run along; each component of Y is summed in the same order in all four.  The label carries the launched
-// instance's scratch bytes per thread (a compiler that starts to spill shows up in every profile and in tools/batched_sketch_id_bench.py --complex).
-template <typename R>
-void batched_sketch_column_id_c(rc_context *c, const rc_matrix &a_, int64_t abs, const rc_matrix &omega_, int64_t obs, int32_t count, int64_t kk, double tol,
-                                const rc_matrix &y_, int64_t ybs, const rc_matrix &cm_, int64_t cbs, const rc_matrix &z_, int64_t zbs, int64_t *col_ind,
-                                int64_t *ranks) {
-    const CV<R> a = view_of<R>(a_), omega = view_of<R>(omega_), y = view_of<R>(y_), cm = view_of<R>(cm_), z = view_of<R>(z_);
-    const int m = (int)a.rows, n = (int)a.cols, l = (int)omega.rows;
-    if (count <= 0) return;
-    const auto plan = bscid_plan<R>(l, n);
-    // the lanes of the staging loads along the smaller stride of a and of omega (the real call's rule)
-    const bool a_rows = a.rs <= a.cs, o_rows = omega.rs < omega.cs;
-    void (*const kerns[4])(BscArgs<R>) = {k_batched_sketch_id_c<R, false, false>, k_batched_sketch_id_c<R, false, true>, k_batched_sketch_id_c<R, true, false>,
-                                          k_batched_sketch_id_c<R, true, true>};
-    const auto lch = batched_prepare(c, kerns[(a_rows ? 2 : 0) + (o_rows ? 1 : 0)], "sketch_column_id_rank_batched", plan.lds, plan.ws, count);
-    ProfScope ps(c, "op:batched_sketch_id_c %dx%d k=%lld count=%d grid=%lld slots=%lld plan=W:%s,l=%d,rows=%d,cols=%d,scratch=%d", m, n, (long long)kk,
-                 (int)count, (long long)lch.grid, (long long)lch.slots, plan.at ? "lds" : "ws", l, BSI_ROWS, BSI_COLS, lch.scratch);
-    BscArgs<R> g;
-    g.a = a; g.omega = omega; g.y = y; g.c = cm; g.z = z;
-    g.abs = abs; g.obs = obs; g.ybs = ybs; g.cbs = cbs; g.zbs = zbs;
-    g.col_ind = col_ind; g.ranks = ranks;
-    g.ws = lch.template workspace<cplx<R>>();
-    g.tol = tol; g.count = (int)count; g.kk = (int)kk; g.w_lds = plan.at;
-    lch.launch(g);
-}
-
-// The plan only moves the working copy's base pointer and pitch, and the four instances (by the index of a and of omega that the sketch's
-// staging loads run along; the projection's run along the other index of a and along n in conj(Q)) sum every component in the same order,
-// so neither can change a block's bits.  The label carries the scratch bytes per thread like the sketched ID's.
-template <typename R>
-void batched_sketch_range_step_c(rc_context *c, const rc_matrix &a_, int64_t abs, const rc_matrix &omega_, int64_t obs, int32_t count, const rc_matrix &y_,
-                                 int64_t ybs, const rc_matrix &q_, int64_t qbs, const rc_matrix &p_, int64_t pbs, int64_t *ranks, bool p_conj) {
-    const CV<R> a = view_of<R>(a_), omega = view_of<R>(omega_), y = view_of<R>(y_), q = view_of<R>(q_), p = view_of<R>(p_);
-    const int m = (int)a.rows, n = (int)a.cols, l = (int)omega.rows;
-    if (count <= 0) return;
-    const auto plan = brsc_plan<R>(l, n);
-    const bool a_rows = a.rs <= a.cs, o_rows = omega.rs < omega.cs;
-    void (*const kerns[4])(BrscArgs<R>) = {k_batched_range_step_c<R, false, false>, k_batched_range_step_c<R, false, true>,
-                                           k_batched_range_step_c<R, true, false>, k_batched_range_step_c<R, true, true>};
-    const auto lch = batched_prepare(c, kerns[(a_rows ? 2 : 0) + (o_rows ? 1 : 0)], "sketch_range_step_complex_batched", plan.lds, plan.ws, count);
-    ProfScope ps(c, "op:batched_range_step_c %dx%d l=%d count=%d grid=%lld slots=%lld plan=W:%s,Q:ws,rows=%d,cols=%d,conj=%d,scratch=%d", m, n, l, (int)count,
-                 (long long)lch.grid, (long long)lch.slots, plan.at ? "lds" : "ws", BSI_ROWS, BSI_COLS, p_conj ? 1 : 0, lch.scratch);
-    BrscArgs<R> g;
-    g.a = a; g.omega = omega; g.y = y; g.q = q; g.p = p;
-    g.abs = abs; g.obs = obs; g.ybs = ybs; g.qbs = qbs; g.pbs = pbs;
-    g.ranks = ranks;
-    g.ws = lch.template workspace<cplx<R>>();
-    g.slot = plan.ws / sizeof(cplx<R>);
-    g.count = (int)count; g.w_lds = plan.at; g.p_conj = p_conj;
-    lch.launch(g);
-}
-
-template void batched_sketch_range_step_c<double>(rc_context *, const rc_matrix &, int64_t, const rc_matrix &, int64_t, int32_t, const rc_matrix &, int64_t,
-                                                  const rc_matrix &, int64_t, const rc_matrix &, int64_t, int64_t *, bool);
-template void batched_sketch_range_step_c<float>(rc_context *, const rc_matrix &, int64_t, const rc_matrix &, int64_t, int32_t, const rc_matrix &, int64_t,
-                                                 const rc_matrix &, int64_t, const rc_matrix &, int64_t, int64_t *, bool);
-
-template void batched_sketch_column_id_c<double>(rc_context *, const rc_matrix &, int64_t, const rc_matrix &, int64_t, int32_t, int64_t, double, const rc_matrix &,
-                                                 int64_t, const rc_matrix &, int64_t, const rc_matrix &, int64_t, int64_t *, int64_t *);
-template void batched_sketch_column_id_c<float>(rc_context *, const rc_matrix &, int64_t, const rc_matrix &, int64_t, int32_t, int64_t, double, const rc_matrix &,
-                                                int64_t, const rc_matrix &, int64_t, const rc_matrix &, int64_t, int64_t *, int64_t *);
-
-template void batched_column_id_c<double>(rc_context *, const rc_matrix &, int64_t, int32_t, int64_t, double, const rc_matrix &, int64_t, const rc_matrix &,
-                                          int64_t, int64_t *, int64_t *);
-template void batched_column_id_c<float>(rc_context *, const rc_matrix &, int64_t, int32_t, int64_t, double, const rc_matrix &, int64_t, const rc_matrix &,
-                                         int64_t, int64_t *, int64_t *);
-template void batched_two_sided_id_c<double>(rc_context *, const rc_matrix &, int64_t, int32_t, int64_t, double, const rc_matrix &, int64_t,
-                                             const rc_matrix &, int64_t, const rc_matrix &, int64_t, int64_t *, int64_t *, int64_t *);
-template void batched_two_sided_id_c<float>(rc_context *, const rc_matrix &, int64_t, int32_t, int64_t, double, const rc_matrix &, int64_t,
-                                            const rc_matrix &, int64_t, const rc_matrix &, int64_t, int64_t *, int64_t *, int64_t *);
-
-template void batched_svd_c<double>(rc_context *, const rc_matrix &, int64_t, int32_t, int64_t, double, const rc_matrix &, int64_t, double *,
-                                    const rc_matrix &, int64_t, int64_t *);
-template void batched_svd_c<float>(rc_context *, const rc_matrix &, int64_t, int32_t, int64_t, double, const rc_matrix &, int64_t, float *,
-                                   const rc_matrix &, int64_t, int64_t *);
-
-template void batched_lowrank_recompress_c<double>(rc_context *, const rc_matrix &, int64_t, const rc_matrix &, int64_t, const double *, int64_t,
-                                                   const rc_matrix &, int64_t, const int64_t *, int32_t, int64_t, double, const rc_matrix &, int64_t, double *,
-                                                   const rc_matrix &, int64_t, int64_t *);
-template void batched_lowrank_recompress_c<float>(rc_context *, const rc_matrix &, int64_t, const rc_matrix &, int64_t, const float *, int64_t,
-                                                  const rc_matrix &, int64_t, const int64_t *, int32_t, int64_t, double, const rc_matrix &, int64_t, float *,
-                                                  const rc_matrix &, int64_t, int64_t *);
-template void batched_lowrank_recompress_tall_c<double>(rc_context *, const rc_matrix &, int64_t, const rc_matrix &, int64_t, const double *, int64_t,
-                                                        const rc_matrix &, int64_t, const int64_t *, int32_t, int64_t, double, const rc_matrix &, int64_t,
-                                                        double *, const rc_matrix &, int64_t, int64_t *);
-template void batched_lowrank_recompress_tall_c<float>(rc_context *, const rc_matrix &, int64_t, const rc_matrix &, int64_t, const float *, int64_t,
-                                                       const rc_matrix &, int64_t, const int64_t *, int32_t, int64_t, double, const rc_matrix &, int64_t, float *,
-                                                       const rc_matrix &, int64_t, int64_t *);
-template void batched_lowrank_recompress_large_c<double>(rc_context *, const rc_matrix &, int64_t, const rc_matrix &, int64_t, const double *, int64_t,
-                                                         const rc_matrix &, int64_t, const int64_t *, int32_t, int64_t, double, const rc_matrix &, int64_t,
-                                                         double *, const rc_matrix &, int64_t, int64_t *);
-template void batched_lowrank_recompress_large_c<float>(rc_context *, const rc_matrix &, int64_t, const rc_matrix &, int64_t, const float *, int64_t,
-                                                        const rc_matrix &, int64_t, const int64_t *, int32_t, int64_t, double, const rc_matrix &, int64_t, float *,
-                                                        const rc_matrix &, int64_t, int64_t *);
+// (the launchers: batched_launchers.hpp)
+RC_INSTANTIATE_BATCHED_SKETCH(cplx<double>, cplx<float>)
+RC_INSTANTIATE_BATCHED_ID_SVD(cplx<double>, cplx<float>)
+RC_INSTANTIATE_BATCHED_RECOMPRESS(cplx<double>, cplx<float>)
 
 }  // namespace rc

@@ -292,10 +292,11 @@ BatchedPlan<bool> br_plan(int K, int n, bool has_mid, bool has_s) {
 
 }  // namespace
 
-// The plan only moves base pointers, so it cannot change a block's bits.  One kernel per scalar type.
+// The plan only moves base pointers, so it cannot change a block's bits.  One kernel per scalar type.  (T real: the complex elements'
+// launcher is specialised in kernels_batched_residual_c.hip.)
 template <typename T>
-void batched_lowrank_residual(rc_context *c, Mat<T> a, int64_t abs, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride, Mat<T> right,
-                              int64_t rbs, const int64_t *ranks, int32_t count, Mat<T> e, int64_t ebs, T *err, T *nrm) {
+void batched_lowrank_residual(rc_context *c, Mat<T> a, int64_t abs, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const real_t<T> *s, int64_t s_stride,
+                              Mat<T> right, int64_t rbs, const int64_t *ranks, int32_t count, Mat<T> e, int64_t ebs, real_t<T> *err, real_t<T> *nrm) {
     const int m = (int)a.rows, n = (int)a.cols, K = (int)left.cols;
     if (count <= 0) return;
     const bool has_mid = mid.p != nullptr;

@@ -18,8 +18,8 @@
 //      elements (32-lane groups, rows 16 modulo 32 elements apart) and as 16-byte elements (the 16-lane groups of ds_read_b128, rows
 //      0 modulo 16 elements apart).  They live in LDS when they fit BID_MAX_LDS next to the chunk images, else in the workgroup's slot
 //      of the grid-bounded workspace; the plan only moves base pointers, so it cannot change a bit.
-//   2. Row chunks of BRC_ROWS = 32 rows against the resident W; left's chunk (32 x 4 ceil(r / 4), zeros past m and past r) is staged
-//      once per chunk and a's chunk streams through LDS in tiles of BRC_COLS = 64 columns, both with the lanes along the operand's
+//   2. Row chunks of BREC_ROWS = 32 rows against the resident W; left's chunk (32 x 4 ceil(r / 4), zeros past m and past r) is staged
+//      once per chunk and a's chunk streams through LDS in tiles of BREC_COLS = 64 columns, both with the lanes along the operand's
 //      smaller stride and that index fastest in the image.  Per tile each wave owns a 16-column strip and both 16-row tiles.  The
 //      rebuild runs on v_mfma_f64_16x16x4_f64 / v_mfma_f32_16x16x4_f32 (Acc<R> of rc_gemm.hpp) with the real and imaginary parts as
 //      separate real operands: per output element each of Re Ah and Im Ah is one accumulator chain from zero over the ascending
@@ -51,11 +51,11 @@ namespace rc {
 
 namespace {
 
-constexpr int BRC_THREADS = BATCHED_THREADS;
-constexpr int BRC_ROWS = 32;  // rows of a and of left per chunk: two 16-row MFMA tiles
-constexpr int BRC_COLS = 64;  // columns of a per tile: one 16-column strip per wave
-constexpr int BRC_PER = BRC_ROWS * BRC_COLS / BRC_THREADS;  // 8 complex elements of a tile per thread, staged and computed
-constexpr int BRC_PAR = BRC_ROWS + 2;  // pitch of a's image with the row index fastest (2 modulo 16: no conflict for 16-byte elements)
+constexpr int BREC_THREADS = BATCHED_THREADS;
+constexpr int BREC_ROWS = 32;  // rows of a and of left per chunk: two 16-row MFMA tiles
+constexpr int BREC_COLS = 64;  // columns of a per tile: one 16-column strip per wave
+constexpr int BREC_PER = BREC_ROWS * BREC_COLS / BREC_THREADS;  // 8 complex elements of a tile per thread, staged and computed
+constexpr int BREC_PAR = BREC_ROWS + 2;  // pitch of a's image with the row index fastest (2 modulo 16: no conflict for 16-byte elements)
 
 // an element of the LDS and workspace images: a cplx<R> over-aligned to one 8- or 16-byte load (the caller's memory holds cplx<R>,
 // aligned as R)
@@ -66,39 +66,39 @@ struct alignas(2 * sizeof(R)) img_cx {
 
 // pitch of left's image with the row index fastest: 16 modulo 32 elements (8-byte elements), 0 modulo 16 (16-byte elements)
 template <typename R>
-__host__ __device__ constexpr int brc_plr() { return sizeof(R) == 8 ? BRC_ROWS : BRC_ROWS + 16; }
+__host__ __device__ constexpr int brec_plr() { return sizeof(R) == 8 ? BREC_ROWS : BREC_ROWS + 16; }
 // pitch of a's image with the column index fastest: the accumulator-layout read has lanes 16 columns x 4 rows, the rows 1 (f64) or 4 (f32) apart
 template <typename R>
-__host__ __device__ constexpr int brc_pac() { return sizeof(R) == 8 ? 80 : 68; }
+__host__ __device__ constexpr int brec_pac() { return sizeof(R) == 8 ? 80 : 68; }
 template <typename R>
-__host__ __device__ constexpr int brc_a_elems() { return BRC_ROWS * brc_pac<R>() > BRC_COLS * BRC_PAR ? BRC_ROWS * brc_pac<R>() : BRC_COLS * BRC_PAR; }
-__host__ __device__ constexpr int brc_k4(int k) { return (k + 3) & ~3; }
+__host__ __device__ constexpr int brec_a_elems() { return BREC_ROWS * brec_pac<R>() > BREC_COLS * BREC_PAR ? BREC_ROWS * brec_pac<R>() : BREC_COLS * BREC_PAR; }
+__host__ __device__ constexpr int brec_k4(int k) { return (k + 3) & ~3; }
 // pitch of left's image with the inner index fastest (2 modulo 32: the A-operand read, 16 rows x 4 inner indices, is free of conflicts)
-__host__ __device__ constexpr int brc_plk(int k) { return ((k + 31) & ~31) + 2; }
+__host__ __device__ constexpr int brec_plk(int k) { return ((k + 31) & ~31) + 2; }
 template <typename R>
-__host__ __device__ constexpr int brc_l_elems(int k) {
-    return BRC_ROWS * brc_plk(k) > brc_k4(k) * brc_plr<R>() ? BRC_ROWS * brc_plk(k) : brc_k4(k) * brc_plr<R>();
+__host__ __device__ constexpr int brec_l_elems(int k) {
+    return BREC_ROWS * brec_plk(k) > brec_k4(k) * brec_plr<R>() ? BREC_ROWS * brec_plk(k) : brec_k4(k) * brec_plr<R>();
 }
-__host__ __device__ constexpr int brc_np(int n) { return (n + BRC_COLS - 1) & ~(BRC_COLS - 1); }
-__host__ __device__ constexpr int brc_pw(int n) { return brc_np(n) + 16; }  // pitch of W's image
-__host__ __device__ constexpr size_t brc_w_elems(int k, int n, bool has_mid) { return (size_t)(has_mid ? 2 : 1) * brc_k4(k) * brc_pw(n); }
+__host__ __device__ constexpr int brec_np(int n) { return (n + BREC_COLS - 1) & ~(BREC_COLS - 1); }
+__host__ __device__ constexpr int brec_pw(int n) { return brec_np(n) + 16; }  // pitch of W's image
+__host__ __device__ constexpr size_t brec_w_elems(int k, int n, bool has_mid) { return (size_t)(has_mid ? 2 : 1) * brec_k4(k) * brec_pw(n); }
 
 // dynamic LDS: red[8] (f64) | [W0 [W1, with mid]: K4 x pw(n), LDS plan only] a's tile image | left's chunk image (complex elements)
 template <typename R>
-size_t brc_lds_bytes(int k, int n, bool has_mid, bool w_lds) {
-    return 64 + ((w_lds ? brc_w_elems(k, n, has_mid) : 0) + (size_t)brc_a_elems<R>() + (size_t)brc_l_elems<R>(k)) * sizeof(img_cx<R>);
+size_t brec_lds_bytes(int k, int n, bool has_mid, bool w_lds) {
+    return 64 + ((w_lds ? brec_w_elems(k, n, has_mid) : 0) + (size_t)brec_a_elems<R>() + (size_t)brec_l_elems<R>(k)) * sizeof(img_cx<R>);
 }
 
-// strided view of block 0 of one operand (in complex elements); the shapes travel once, in BrcArgs, not per operand as in CV<R>
+// strided view of block 0 of one operand (in complex elements); the shapes travel once, in BrecArgs, not per operand as in CV<R>
 template <typename R>
-struct BrcView {
+struct BrecView {
     cplx<R> *p;
     int64_t rs, cs;
 };
 
 template <typename R>
-struct BrcArgs {
-    BrcView<R> a, left, mid, right, e;  // mid.p == nullptr: none; e.p == nullptr: the residual is not written
+struct BrecArgs {
+    BrecView<R> a, left, mid, right, e;  // mid.p == nullptr: none; e.p == nullptr: the residual is not written
     int64_t abs, lbs, mbs, rbs, ebs, s_stride;
     const R *s;
     const int64_t *ranks;
@@ -110,7 +110,7 @@ struct BrcArgs {
 };
 
 template <typename R>
-__global__ __launch_bounds__(BRC_THREADS) void k_batched_residual_c(BrcArgs<R> g) {
+__global__ __launch_bounds__(BREC_THREADS) void k_batched_residual_c(BrecArgs<R> g) {
     using C = img_cx<R>;
     using G = cplx<R>;
     typedef typename Acc<R>::type acc_t;
@@ -119,25 +119,25 @@ __global__ __launch_bounds__(BRC_THREADS) void k_batched_residual_c(BrcArgs<R> g
     constexpr bool WIDE = sizeof(R) == 8;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int m = g.m, n = g.n, K = g.k;
-    const int np = brc_np(n), pw = brc_pw(n);
+    const int np = brec_np(n), pw = brec_pw(n);
     const bool has_mid = g.mid.p != nullptr;
-    const size_t wel = (size_t)brc_k4(K) * pw;
+    const size_t wel = (size_t)brec_k4(K) * pw;
     double *red = reinterpret_cast<double *>(smem_raw);
     C *lds = reinterpret_cast<C *>(smem_raw + 64);
-    C *W0 = g.w_lds ? lds : g.direct ? lds : g.ws + (size_t)blockIdx.x * brc_w_elems(K, n, has_mid);  // unused when direct
+    C *W0 = g.w_lds ? lds : g.direct ? lds : g.ws + (size_t)blockIdx.x * brec_w_elems(K, n, has_mid);  // unused when direct
     C *W1 = W0 + wel;
-    C *As = lds + (g.w_lds ? brc_w_elems(K, n, has_mid) : 0);
-    C *Ls = As + brc_a_elems<R>();
+    C *As = lds + (g.w_lds ? brec_w_elems(K, n, has_mid) : 0);
+    C *Ls = As + brec_a_elems<R>();
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r16 = lane & 15, k4 = lane >> 4;
     // the lanes of every staging loop run along the operand's smaller stride, and that index is the fastest one of the LDS image
     const bool a_rows = g.a.rs <= g.a.cs, l_rows = g.left.rs <= g.left.cs, r_rows = g.right.rs <= g.right.cs, e_rows = g.e.rs <= g.e.cs;
-    const int as_sr = a_rows ? 1 : brc_pac<R>(), as_sc = a_rows ? BRC_PAR : 1;    // As[row * as_sr + col * as_sc]
-    const int ls_sr = l_rows ? 1 : brc_plk(K), ls_sk = l_rows ? brc_plr<R>() : 1;  // Ls[row * ls_sr + k * ls_sk]
-    // this thread's BRC_PER elements of a tile when staging a (row0 + drow * q, col0 + dcol * q) and when storing e
-    const int a_row0 = a_rows ? (tid & (BRC_ROWS - 1)) : (tid / BRC_COLS), a_col0 = a_rows ? (tid / BRC_ROWS) : (tid & (BRC_COLS - 1));
-    const int a_drow = a_rows ? 0 : BRC_THREADS / BRC_COLS, a_dcol = a_rows ? BRC_THREADS / BRC_ROWS : 0;
-    const int e_row0 = e_rows ? (tid & (BRC_ROWS - 1)) : (tid / BRC_COLS), e_col0 = e_rows ? (tid / BRC_ROWS) : (tid & (BRC_COLS - 1));
-    const int e_drow = e_rows ? 0 : BRC_THREADS / BRC_COLS, e_dcol = e_rows ? BRC_THREADS / BRC_ROWS : 0;
+    const int as_sr = a_rows ? 1 : brec_pac<R>(), as_sc = a_rows ? BREC_PAR : 1;    // As[row * as_sr + col * as_sc]
+    const int ls_sr = l_rows ? 1 : brec_plk(K), ls_sk = l_rows ? brec_plr<R>() : 1;  // Ls[row * ls_sr + k * ls_sk]
+    // this thread's BREC_PER elements of a tile when staging a (row0 + drow * q, col0 + dcol * q) and when storing e
+    const int a_row0 = a_rows ? (tid & (BREC_ROWS - 1)) : (tid / BREC_COLS), a_col0 = a_rows ? (tid / BREC_ROWS) : (tid & (BREC_COLS - 1));
+    const int a_drow = a_rows ? 0 : BREC_THREADS / BREC_COLS, a_dcol = a_rows ? BREC_THREADS / BREC_ROWS : 0;
+    const int e_row0 = e_rows ? (tid & (BREC_ROWS - 1)) : (tid / BREC_COLS), e_col0 = e_rows ? (tid / BREC_ROWS) : (tid & (BREC_COLS - 1));
+    const int e_drow = e_rows ? 0 : BREC_THREADS / BREC_COLS, e_dcol = e_rows ? BREC_THREADS / BREC_ROWS : 0;
     // and in the accumulator layout: rows i * 16 + Acc<R>::row(lane, reg) of column wv * 16 + r16
     const C *ls_ld = Ls + r16 * ls_sr + k4 * ls_sk;
     C *as_acc = As + (wv * 16 + r16) * as_sc;
@@ -150,7 +150,7 @@ __global__ __launch_bounds__(BRC_THREADS) void k_batched_residual_c(BrcArgs<R> g
             r = rv < 0 ? 0 : rv > K ? K : (int)rv;
         }
         r = __builtin_amdgcn_readfirstlane(r);  // one value per block, uniform by construction: the loop bounds stay in scalar registers
-        const int r4 = brc_k4(r);
+        const int r4 = brec_k4(r);
         const G *__restrict__ A = g.a.p + (int64_t)b * g.abs;
         const G *__restrict__ Lf = g.left.p + (int64_t)b * g.lbs;
         const G *__restrict__ Rt = g.right.p + (int64_t)b * g.rbs;
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(BRC_THREADS) void k_batched_residual_c(BrcArgs<R> g
 
         // ---- phase 1: W0 = diag(s[:r]) right[:r, :], zero rows r .. r4 - 1 and zero columns n .. np - 1 ----------------------------------
         const int wtot = g.direct ? 0 : r4 * np;  // without mid and s there is nothing to produce
-        for (int idx = tid; idx < wtot; idx += BRC_THREADS) {
+        for (int idx = tid; idx < wtot; idx += BREC_THREADS) {
             int k, j;
             if (r_rows) { k = idx % r4; j = idx / r4; } else { j = idx % np; k = idx / np; }
             C v = czero;
@@ -179,7 +179,7 @@ __global__ __launch_bounds__(BRC_THREADS) void k_batched_residual_c(BrcArgs<R> g
         const C *Wp = W0;
         if (has_mid) {  // W1 = mid[:r, :r] W0: the 64 lanes of a wave share the row l (np is a multiple of 64) and read one element of mid
             const G *__restrict__ Md = g.mid.p + (int64_t)b * g.mbs;
-            for (int idx = tid; idx < wtot; idx += BRC_THREADS) {
+            for (int idx = tid; idx < wtot; idx += BREC_THREADS) {
                 const int j = idx % np, l = idx / np;
                 C acc = czero;
                 if (l < r && j < n) {
@@ -202,11 +202,11 @@ __global__ __launch_bounds__(BRC_THREADS) void k_batched_residual_c(BrcArgs<R> g
 
         // ---- phase 2: row chunks of a and left against W ------------------------------------------------------------------------------
         SumSq3 se{0.0, 0.0, 0.0}, sa{0.0, 0.0, 0.0};  // c32: med alone
-        for (int m0 = 0; m0 < m; m0 += BRC_ROWS) {
-            const int ltot = BRC_ROWS * r4;
-            for (int idx = tid; idx < ltot; idx += BRC_THREADS) {
+        for (int m0 = 0; m0 < m; m0 += BREC_ROWS) {
+            const int ltot = BREC_ROWS * r4;
+            for (int idx = tid; idx < ltot; idx += BREC_THREADS) {
                 int row, k;
-                if (l_rows) { row = idx & (BRC_ROWS - 1); k = idx / BRC_ROWS; } else { k = idx % r4; row = idx / r4; }
+                if (l_rows) { row = idx & (BREC_ROWS - 1); k = idx / BREC_ROWS; } else { k = idx % r4; row = idx / r4; }
                 C v = czero;
                 if (m0 + row < m && k < r) {
                     const G x = Lf[(int64_t)(m0 + row) * g.left.rs + (int64_t)k * g.left.cs];
@@ -215,16 +215,16 @@ __global__ __launch_bounds__(BRC_THREADS) void k_batched_residual_c(BrcArgs<R> g
                 }
                 Ls[row * ls_sr + k * ls_sk] = v;
             }
-            for (int c0 = 0; c0 < n; c0 += BRC_COLS) {
-                G av[BRC_PER];
+            for (int c0 = 0; c0 < n; c0 += BREC_COLS) {
+                G av[BREC_PER];
 #pragma unroll
-                for (int q = 0; q < BRC_PER; ++q) {
+                for (int q = 0; q < BREC_PER; ++q) {
                     const int row = a_row0 + a_drow * q, col = a_col0 + a_dcol * q;
                     const bool ok = m0 + row < m && c0 + col < n;
                     av[q] = ok ? A[(int64_t)(m0 + row) * g.a.rs + (int64_t)(c0 + col) * g.a.cs] : G{(R)0, (R)0};
                 }
 #pragma unroll
-                for (int q = 0; q < BRC_PER; ++q) As[(a_row0 + a_drow * q) * as_sr + (a_col0 + a_dcol * q) * as_sc] = C{av[q].re, av[q].im};
+                for (int q = 0; q < BREC_PER; ++q) As[(a_row0 + a_drow * q) * as_sr + (a_col0 + a_dcol * q) * as_sc] = C{av[q].re, av[q].im};
                 __syncthreads();
                 acc_t are[2], aim[2];
                 [[maybe_unused]] const double se0 = se.med, sa0 = sa.med;
@@ -308,7 +308,7 @@ __global__ __launch_bounds__(BRC_THREADS) void k_batched_residual_c(BrcArgs<R> g
                 if (E) {  // uniform over the grid
                     __syncthreads();
 #pragma unroll
-                    for (int q = 0; q < BRC_PER; ++q) {
+                    for (int q = 0; q < BREC_PER; ++q) {
                         const int row = e_row0 + e_drow * q, col = e_col0 + e_dcol * q;
                         if (m0 + row < m && c0 + col < n) {
                             const C v = As[row * as_sr + col * as_sc];
@@ -358,34 +358,33 @@ __global__ __launch_bounds__(BRC_THREADS) void k_batched_residual_c(BrcArgs<R> g
 }
 
 template <typename R>
-BrcView<R> brc_view(const rc_matrix &v) { return BrcView<R>{static_cast<cplx<R> *>(v.data), v.row_stride, v.col_stride}; }
+BrecView<R> brec_view(Mat<cplx<R>> v) { return BrecView<R>{v.p, v.rs, v.cs}; }
 
 // the plan (at: W's images in LDS): the real kernel's rule (br_plan) on the over-aligned image elements
 template <typename R>
-BatchedPlan<bool> brc_plan(int K, int n, bool has_mid, bool has_s) {
-    if (!has_mid && !has_s) return {false, brc_lds_bytes<R>(K, n, false, false), 0};
-    return batched_lds_or_ws([&](bool w_lds) { return brc_lds_bytes<R>(K, n, has_mid, w_lds); }, brc_w_elems(K, n, has_mid) * sizeof(img_cx<R>),
+BatchedPlan<bool> brec_plan(int K, int n, bool has_mid, bool has_s) {
+    if (!has_mid && !has_s) return {false, brec_lds_bytes<R>(K, n, false, false), 0};
+    return batched_lds_or_ws([&](bool w_lds) { return brec_lds_bytes<R>(K, n, has_mid, w_lds); }, brec_w_elems(K, n, has_mid) * sizeof(img_cx<R>),
                              "lowrank_residual_batched");
 }
 
-}  // namespace
-
-// The plan only moves base pointers, so it cannot change a block's bits.  One kernel per scalar type.
+// The plan only moves base pointers, so it cannot change a block's bits.  One kernel per scalar type.  A body of its own, not the real
+// launcher's (kernels_batched_residual.hip): the Args and the image element differ.  It stands inside this file's namespace, and
+// batched_lowrank_residual<cplx<R>> below are explicit specialisations that call it.
 template <typename R>
-void batched_lowrank_residual_c(rc_context *c, const rc_matrix &a, int64_t abs, const rc_matrix &left, int64_t lbs, const rc_matrix &mid, int64_t mbs, const R *s,
-                                int64_t s_stride, const rc_matrix &right, int64_t rbs, const int64_t *ranks, int32_t count, const rc_matrix &e, int64_t ebs,
-                                R *err, R *nrm) {
+void brec_launch(rc_context *c, Mat<cplx<R>> a, int64_t abs, Mat<cplx<R>> left, int64_t lbs, Mat<cplx<R>> mid, int64_t mbs, const R *s, int64_t s_stride,
+                 Mat<cplx<R>> right, int64_t rbs, const int64_t *ranks, int32_t count, Mat<cplx<R>> e, int64_t ebs, R *err, R *nrm) {
     const int m = (int)a.rows, n = (int)a.cols, K = (int)left.cols;
     if (count <= 0) return;
-    const bool has_mid = mid.data != nullptr;
+    const bool has_mid = mid.p != nullptr;
     const bool direct = !has_mid && !s;
-    const auto plan = brc_plan<R>(K, n, has_mid, s != nullptr);
+    const auto plan = brec_plan<R>(K, n, has_mid, s != nullptr);
     const auto lch = batched_prepare(c, k_batched_residual_c<R>, "lowrank_residual_batched", plan.lds, plan.ws, count);
     ProfScope ps(c, "op:batched_residual<complex> %dx%d k=%d count=%d grid=%lld slots=%lld plan=W:%s,rows=%d,cols=%d%s%s%s%s", m, n, K, (int)count,
-                 (long long)lch.grid, (long long)lch.slots, direct ? "right" : plan.at ? "lds" : "ws", BRC_ROWS, BRC_COLS, has_mid ? ",mid" : "", s ? ",s" : "",
-                 e.data ? ",e" : "", nrm ? ",nrm" : "");
-    BrcArgs<R> g;
-    g.a = brc_view<R>(a); g.left = brc_view<R>(left); g.mid = brc_view<R>(mid); g.right = brc_view<R>(right); g.e = brc_view<R>(e);
+                 (long long)lch.grid, (long long)lch.slots, direct ? "right" : plan.at ? "lds" : "ws", BREC_ROWS, BREC_COLS, has_mid ? ",mid" : "", s ? ",s" : "",
+                 e.p ? ",e" : "", nrm ? ",nrm" : "");
+    BrecArgs<R> g;
+    g.a = brec_view<R>(a); g.left = brec_view<R>(left); g.mid = brec_view<R>(mid); g.right = brec_view<R>(right); g.e = brec_view<R>(e);
     g.abs = abs; g.lbs = lbs; g.mbs = mbs; g.rbs = rbs; g.ebs = ebs; g.s_stride = s_stride;
     g.s = s; g.ranks = ranks; g.err = err; g.nrm = nrm;
     g.ws = lch.template workspace<img_cx<R>>();
@@ -393,9 +392,16 @@ void batched_lowrank_residual_c(rc_context *c, const rc_matrix &a, int64_t abs, 
     lch.launch(g);
 }
 
-template void batched_lowrank_residual_c<double>(rc_context *, const rc_matrix &, int64_t, const rc_matrix &, int64_t, const rc_matrix &, int64_t, const double *,
-                                                 int64_t, const rc_matrix &, int64_t, const int64_t *, int32_t, const rc_matrix &, int64_t, double *, double *);
-template void batched_lowrank_residual_c<float>(rc_context *, const rc_matrix &, int64_t, const rc_matrix &, int64_t, const rc_matrix &, int64_t, const float *,
-                                                int64_t, const rc_matrix &, int64_t, const int64_t *, int32_t, const rc_matrix &, int64_t, float *, float *);
+}  // namespace
+
+#define RC_DEFINE_RESIDUAL(R)                                                                                                                   \
+    template <>                                                                                                                                 \
+    void batched_lowrank_residual<cplx<R>>(rc_context *c, Mat<cplx<R>> a, int64_t abs, Mat<cplx<R>> left, int64_t lbs, Mat<cplx<R>> mid, int64_t mbs, \
+                                           const R *s, int64_t s_stride, Mat<cplx<R>> right, int64_t rbs, const int64_t *ranks, int32_t count,      \
+                                           Mat<cplx<R>> e, int64_t ebs, R *err, R *nrm) {                                                           \
+        brec_launch<R>(c, a, abs, left, lbs, mid, mbs, s, s_stride, right, rbs, ranks, count, e, ebs, err, nrm);                                    \
+    }
+RC_DEFINE_RESIDUAL(double)
+RC_DEFINE_RESIDUAL(float)
 
 }  // namespace rc

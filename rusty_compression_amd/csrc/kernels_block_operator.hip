@@ -196,40 +196,27 @@ void bop_pattern(rc_context *c, BopArgs<E, S> &a, const BlockPattern &pat, Block
 
 }  // namespace
 
-template <typename T>
-void block_operator_apply(rc_context *c, Mat<T> left, int64_t lbs, Mat<T> mid, int64_t mbs, const T *s, int64_t s_stride, Mat<T> right, int64_t rbs,
-                          const int64_t *ranks, int32_t count, Mat<T> dense, int64_t dbs, int32_t dense_count, const BlockPattern &pat, BlockShape shape,
-                          Mat<T> x, Mat<T> y, bool accumulate) {
-    BopArgs<T> a;
-    a.left = bop_view<const T>(left.p, left.rs, left.cs, lbs);
-    a.mid = bop_view<const T>(count > 0 ? mid.p : nullptr, mid.rs, mid.cs, mbs);
-    a.right = bop_view<const T>(right.p, right.rs, right.cs, rbs);
-    a.dense = bop_view<const T>(dense.p, dense.rs, dense.cs, dbs);
+template <typename E>
+void block_operator_apply(rc_context *c, Mat<E> left, int64_t lbs, Mat<E> mid, int64_t mbs, const real_t<E> *s, int64_t s_stride, Mat<E> right, int64_t rbs,
+                          const int64_t *ranks, int32_t count, Mat<E> dense, int64_t dbs, int32_t dense_count, const BlockPattern &pat, BlockShape shape,
+                          Mat<E> x, Mat<E> y, bool accumulate, bool conj) {
+    BopArgs<E> a;
+    a.left = bop_view<const E>(left.p, left.rs, left.cs, lbs);
+    a.mid = bop_view<const E>(count > 0 ? mid.p : nullptr, mid.rs, mid.cs, mbs);
+    a.right = bop_view<const E>(right.p, right.rs, right.cs, rbs);
+    a.dense = bop_view<const E>(dense.p, dense.rs, dense.cs, dbs);
     a.s = count > 0 ? s : nullptr; a.s_stride = s_stride; a.ranks = ranks;
     a.x = x.p; a.xrs = x.rs; a.xcs = x.cs; a.xrows = x.rows;
     a.y = y.p; a.yrs = y.rs; a.ycs = y.cs; a.yrows = y.rows;
     a.ncols = (int)y.cols;
     bop_pattern(c, a, pat, shape, count, dense_count, accumulate);
-    bop_launch<T, false, T>(c, a, "", false);
-}
-
-template <typename R>
-void block_operator_apply_c(rc_context *c, const rc_matrix &left, int64_t lbs, const rc_matrix &mid, int64_t mbs, const R *s, int64_t s_stride,
-                            const rc_matrix &right, int64_t rbs, const int64_t *ranks, int32_t count, const rc_matrix &dense, int64_t dbs, int32_t dense_count,
-                            const BlockPattern &pat, BlockShape shape, const rc_matrix &x, const rc_matrix &y, bool accumulate, bool conj) {
-    using E = cplx<R>;
-    BopArgs<E> a;
-    a.left = bop_view<const E>(left.data, left.row_stride, left.col_stride, lbs);
-    a.mid = bop_view<const E>(count > 0 ? mid.data : nullptr, mid.row_stride, mid.col_stride, mbs);
-    a.right = bop_view<const E>(right.data, right.row_stride, right.col_stride, rbs);
-    a.dense = bop_view<const E>(dense.data, dense.row_stride, dense.col_stride, dbs);
-    a.s = count > 0 ? s : nullptr; a.s_stride = s_stride; a.ranks = ranks;
-    a.x = static_cast<const E *>(x.data); a.xrs = x.row_stride; a.xcs = x.col_stride; a.xrows = x.rows;
-    a.y = static_cast<E *>(y.data); a.yrs = y.row_stride; a.ycs = y.col_stride; a.yrows = y.rows;
-    a.ncols = (int)y.cols;
-    bop_pattern(c, a, pat, shape, count, dense_count, accumulate);
-    if (conj) bop_launch<E, true, E>(c, a, "<complex>", true);
-    else bop_launch<E, false, E>(c, a, "<complex>", false);
+    // conjugation is the identity on real elements: they have no conjugating instance and ignore the flag
+    if constexpr (std::is_same<E, real_t<E>>::value) {
+        bop_launch<E, false, E>(c, a, "", false);
+    } else {
+        if (conj) bop_launch<E, true, E>(c, a, "<complex>", true);
+        else bop_launch<E, false, E>(c, a, "<complex>", false);
+    }
 }
 
 // the mixed calls: factor views of S (strides in elements of S), dense, x and y of E, s double
@@ -265,15 +252,12 @@ void block_operator_apply_mixed(rc_context *c, bool complex_data, const rc_matri
     else bop_launch<E, false, S>(c, a, "<complex,mixed>", false);
 }
 
-template void block_operator_apply<double>(rc_context *, Mat<double>, int64_t, Mat<double>, int64_t, const double *, int64_t, Mat<double>, int64_t,
-                                           const int64_t *, int32_t, Mat<double>, int64_t, int32_t, const BlockPattern &, BlockShape, Mat<double>, Mat<double>, bool);
-template void block_operator_apply<float>(rc_context *, Mat<float>, int64_t, Mat<float>, int64_t, const float *, int64_t, Mat<float>, int64_t,
-                                          const int64_t *, int32_t, Mat<float>, int64_t, int32_t, const BlockPattern &, BlockShape, Mat<float>, Mat<float>, bool);
-template void block_operator_apply_c<double>(rc_context *, const rc_matrix &, int64_t, const rc_matrix &, int64_t, const double *, int64_t,
-                                             const rc_matrix &, int64_t, const int64_t *, int32_t, const rc_matrix &, int64_t, int32_t, const BlockPattern &,
-                                             BlockShape, const rc_matrix &, const rc_matrix &, bool, bool);
-template void block_operator_apply_c<float>(rc_context *, const rc_matrix &, int64_t, const rc_matrix &, int64_t, const float *, int64_t,
-                                            const rc_matrix &, int64_t, const int64_t *, int32_t, const rc_matrix &, int64_t, int32_t, const BlockPattern &,
-                                            BlockShape, const rc_matrix &, const rc_matrix &, bool, bool);
+#define RC_INSTANTIATE_BLOCK_OPERATOR(E)                                                                                                    \
+    template void block_operator_apply<E>(rc_context *, Mat<E>, int64_t, Mat<E>, int64_t, const real_t<E> *, int64_t, Mat<E>, int64_t, const int64_t *, \
+                                          int32_t, Mat<E>, int64_t, int32_t, const BlockPattern &, BlockShape, Mat<E>, Mat<E>, bool, bool);
+RC_INSTANTIATE_BLOCK_OPERATOR(double)
+RC_INSTANTIATE_BLOCK_OPERATOR(float)
+RC_INSTANTIATE_BLOCK_OPERATOR(cplx<double>)
+RC_INSTANTIATE_BLOCK_OPERATOR(cplx<float>)
 
 }  // namespace rc

@@ -1,10 +1,12 @@
 // The host layer of the batched family: the argument checks and every rc_*_batched_* / rc_block_operator_apply_* entry point of the C ABI, defined
-// once for f64, f32, c64 and c32.  No kernel is defined or instantiated here: the launchers live in the kernels_*.hip files (rc_batched.hpp), real
-// and complex as twins, and an entry point is "check, return when there is nothing to do, launch" under the call guard (rc_common.hpp).
+// once for f64, f32, c64 and c32.  No kernel is defined or instantiated here: the launchers live in the kernels_*.hip files, each declared
+// once over the element type of its typed views (rc_batched.hpp), and an entry point is "check, return when there is nothing to do, launch on
+// from_c<E> views" under the call guard (rc_common.hpp).
 #include "rc_common.hpp"
 
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 
 using namespace rc;
 
@@ -257,58 +259,28 @@ void check_convert_batched(const char *who, const rc_matrix &src, int32_t count,
 
 namespace {
 
-// One scalar type of the family, as its entry points see it: what its launchers take for an rc_matrix (the real ones a typed view, the complex
-// twins the rc_matrix itself) and the launchers by one name.  The differences between real and complex stay differences: the complex
-// recompressions take their tolerance in the real type and check the tall form under a name of their own, conjugation is the identity on real
-// data (the real block operator and range step ignore the flag).
-template <typename R>
-struct Real {
-    using recompress_tol = double;
-    static constexpr bool complex = false;
-    static constexpr int tall = RC_TALL;
-    static Mat<R> view(const rc_matrix &m) { return from_c<R>(m); }
-    template <typename... A> static void column_id(const A &...a) { batched_column_id<R>(a...); }
-    template <typename... A> static void two_sided_id(const A &...a) { batched_two_sided_id<R>(a...); }
-    template <typename... A> static void svd(const A &...a) { batched_svd<R>(a...); }
-    template <typename... A> static void lowrank_apply(const A &...a) { batched_lowrank_apply<R>(a...); }
-    template <typename... A> static void block_operator(bool, const A &...a) { block_operator_apply<R>(a...); }
-    template <typename... A> static void recompress(const A &...a) { batched_lowrank_recompress<R>(a...); }
-    template <typename... A> static void recompress_tall(const A &...a) { batched_lowrank_recompress_tall<R>(a...); }
-    template <typename... A> static void recompress_large(const A &...a) { batched_lowrank_recompress_large<R>(a...); }
-    template <typename... A> static void sketch_column_id(const A &...a) { batched_sketch_column_id<R>(a...); }
-    template <typename... A> static void range_step(bool, const A &...a) { batched_sketch_range_step<R>(a...); }
-    template <typename... A> static void residual(const A &...a) { batched_lowrank_residual<R>(a...); }
-};
-template <typename R>
-struct Cplx {
-    using recompress_tol = R;
-    static constexpr bool complex = true;
-    static constexpr int tall = RC_TALL_COMPLEX;
-    static const rc_matrix &view(const rc_matrix &m) { return m; }
-    template <typename... A> static void column_id(const A &...a) { batched_column_id_c<R>(a...); }
-    template <typename... A> static void two_sided_id(const A &...a) { batched_two_sided_id_c<R>(a...); }
-    template <typename... A> static void svd(const A &...a) { batched_svd_c<R>(a...); }
-    template <typename... A> static void lowrank_apply(const A &...a) { batched_lowrank_apply_c<R>(a...); }
-    template <typename... A> static void block_operator(bool conj, const A &...a) { block_operator_apply_c<R>(a..., conj); }
-    template <typename... A> static void recompress(const A &...a) { batched_lowrank_recompress_c<R>(a...); }
-    template <typename... A> static void recompress_tall(const A &...a) { batched_lowrank_recompress_tall_c<R>(a...); }
-    template <typename... A> static void recompress_large(const A &...a) { batched_lowrank_recompress_large_c<R>(a...); }
-    template <typename... A> static void sketch_column_id(const A &...a) { batched_sketch_column_id_c<R>(a...); }
-    template <typename... A> static void range_step(bool p_conj, const A &...a) { batched_sketch_range_step_c<R>(a..., p_conj); }
-    template <typename... A> static void residual(const A &...a) { batched_lowrank_residual_c<R>(a...); }
+// One scalar type of the family, as its entry points see it: the element E of its views (from_c<E>) and what really differs between the
+// real and the complex entry points: the complex recompressions take their tolerance in the real type and check the tall form under a name
+// of their own.  Conjugation is the identity on real data (the real block operator and range step ignore the flag).
+template <typename E>
+struct Scalar {
+    static constexpr bool complex = !std::is_same<E, real_t<E>>::value;
+    using recompress_tol = std::conditional_t<complex, real_t<E>, double>;
+    static constexpr int tall = complex ? RC_TALL_COMPLEX : RC_TALL;
 };
 
 // One range step of a power iteration on every block of a batch (sample_range_power_iteration, src/random_sampling.rs:131-158): the sketch
 // y = omega a, an orthonormal basis q of its rows by a pivoted Householder QR of y^H and the projection p = a q^H (or its conjugate, p_conj), in
 // one launch; p is orthonormalised by the tall recompression with right = I before its transpose is the next omega.  Only the complex entry
 // points carry p_conj, so they are written out below this body instead of in RC_DEFINE_BATCHED.
-template <typename S>
+template <typename E>
 rc_status sketch_range_step(rc_context *ctx, const rc_matrix &a, int64_t abs, const rc_matrix &omega, int64_t obs, int32_t count, const rc_matrix &y,
                             int64_t ybs, const rc_matrix &q, int64_t qbs, const rc_matrix &p, int64_t pbs, int64_t *ranks, bool p_conj) {
     return guarded(ctx, [&] {
-        check_sketch_range_step_batched(a, omega, count, y, ybs, q, qbs, p, pbs, ranks, S::complex);
+        check_sketch_range_step_batched(a, omega, count, y, ybs, q, qbs, p, pbs, ranks, Scalar<E>::complex);
         if (count == 0) return;
-        S::range_step(p_conj, ctx, S::view(a), abs, S::view(omega), obs, count, S::view(y), ybs, S::view(q), qbs, S::view(p), pbs, ranks);
+        batched_sketch_range_step<E>(ctx, from_c<E>(a), abs, from_c<E>(omega), obs, count, from_c<E>(y), ybs, from_c<E>(q), qbs, from_c<E>(p), pbs, ranks,
+                                     p_conj);
     });
 }
 
@@ -319,8 +291,10 @@ rc_status recompress_tall_plan(bool complex, int64_t m, int64_t n, int64_t inner
         resident < 1 || !stages || !slot_bytes || !grid)
         return RC_INVALID_ARGUMENT;
     try {
-        (complex ? batched_lowrank_recompress_tall_c_plan : batched_lowrank_recompress_tall_plan)(m, n, inner, real_bytes == 8, resident, stages, slot_bytes,
-                                                                                                  grid);
+        const bool wide = real_bytes == 8;
+        (complex ? (wide ? batched_lowrank_recompress_tall_plan<cplx<double>> : batched_lowrank_recompress_tall_plan<cplx<float>>)
+                 : (wide ? batched_lowrank_recompress_tall_plan<double> : batched_lowrank_recompress_tall_plan<float>))(m, n, inner, resident, stages,
+                                                                                                                        slot_bytes, grid);
         return RC_OK;
     } catch (const Error &e) {
         return e.code;
@@ -334,8 +308,10 @@ rc_status recompress_large_plan(bool complex, int64_t m, int64_t n, int64_t inne
         resident < 1 || !stages_left || !stages_right || !slot_bytes || !grid)
         return RC_INVALID_ARGUMENT;
     try {
-        (complex ? batched_lowrank_recompress_large_c_plan : batched_lowrank_recompress_large_plan)(m, n, inner, elem_bytes == 8, resident, stages_left,
-                                                                                                    stages_right, slot_bytes, grid);
+        const bool wide = elem_bytes == 8;
+        (complex ? (wide ? batched_lowrank_recompress_large_plan<cplx<double>> : batched_lowrank_recompress_large_plan<cplx<float>>)
+                 : (wide ? batched_lowrank_recompress_large_plan<double> : batched_lowrank_recompress_large_plan<float>))(m, n, inner, resident, stages_left,
+                                                                                                                          stages_right, slot_bytes, grid);
         return RC_OK;
     } catch (const Error &e) {
         return e.code;
@@ -347,22 +323,22 @@ rc_status recompress_large_plan(bool complex, int64_t m, int64_t n, int64_t inne
 // ================================================================================================ extern "C"
 extern "C" {
 
-// The regular entry points of one scalar type: SUF its suffix, R its real type, S its adapter (Real or Cplx), CX empty or `complex_` for the
+// The regular entry points of one scalar type: SUF its suffix, R its real type, E its element, CX empty or `complex_` for the
 // four stems that carry the word.  Every body is the same three steps; the rank rule (tol, 0: fixed rank k) runs on the device, without a host
 // round trip; one path, stream-ordered, capturable.
-#define RC_DEFINE_BATCHED(SUF, R, S, CX)                                                                                                     \
-    /* rank-revealing column IDs of many small same-shaped matrices (the unit of rc_column_id_rank_*) in one launch */                      \
+#define RC_DEFINE_BATCHED(SUF, R, E, CX)                                                                                                     \
+    /* rank-revealing column IDs of many small same-shaped matrices (the unit of rc_column_id_rank_*) in one launch */                       \
     rc_status rc_column_id_rank_batched_##SUF(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol,    \
                                               rc_matrix c, int64_t c_batch_stride, rc_matrix z, int64_t z_batch_stride, int64_t *col_ind,    \
                                               int64_t *ranks) {                                                                              \
         return guarded(ctx, [&] {                                                                                                            \
             k = check_column_id_rank_batched(a, count, k, tol, c, c_batch_stride, z, z_batch_stride, col_ind, ranks);                        \
             if (count == 0) return;                                                                                                          \
-            S<R>::column_id(ctx, S<R>::view(a), a_batch_stride, count, k, tol, S<R>::view(c), c_batch_stride, S<R>::view(z), z_batch_stride, \
-                            col_ind, ranks);                                                                                                 \
+            batched_column_id<E>(ctx, from_c<E>(a), a_batch_stride, count, k, tol, from_c<E>(c), c_batch_stride, from_c<E>(z),               \
+                                 z_batch_stride, col_ind, ranks);                                                                            \
         });                                                                                                                                  \
     }                                                                                                                                        \
-    /* the two-sided ID A ~ C X R of the same batch (ColumnID::two_sided_id after the column ID), in the same one launch */                 \
+    /* the two-sided ID A ~ C X R of the same batch (ColumnID::two_sided_id after the column ID), in the same one launch */                  \
     rc_status rc_two_sided_id_rank_batched_##SUF(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol, \
                                                  rc_matrix c, int64_t c_batch_stride, rc_matrix x, int64_t x_batch_stride, rc_matrix r,      \
                                                  int64_t r_batch_stride, int64_t *row_ind, int64_t *col_ind, int64_t *ranks) {               \
@@ -370,22 +346,22 @@ extern "C" {
             k = check_two_sided_id_rank_batched(a, count, k, tol, c, c_batch_stride, x, x_batch_stride, r, r_batch_stride, row_ind, col_ind, \
                                                 ranks);                                                                                      \
             if (count == 0) return;                                                                                                          \
-            S<R>::two_sided_id(ctx, S<R>::view(a), a_batch_stride, count, k, tol, S<R>::view(c), c_batch_stride, S<R>::view(x),              \
-                               x_batch_stride, S<R>::view(r), r_batch_stride, row_ind, col_ind, ranks);                                      \
+            batched_two_sided_id<E>(ctx, from_c<E>(a), a_batch_stride, count, k, tol, from_c<E>(c), c_batch_stride, from_c<E>(x),            \
+                                    x_batch_stride, from_c<E>(r), r_batch_stride, row_ind, col_ind, ranks);                                  \
         });                                                                                                                                  \
     }                                                                                                                                        \
-    /* truncated SVDs of the same batch (SVD::compute_from -> compress(.) per matrix), rank chosen per matrix on the singular values, */    \
-    /* which are real for every scalar type; u (m x k), vt = V^H (k x n) */                                                                 \
+    /* truncated SVDs of the same batch (SVD::compute_from -> compress(.) per matrix), rank chosen per matrix on the singular values, */     \
+    /* which are real for every scalar type; u (m x k), vt = V^H (k x n) */                                                                  \
     rc_status rc_svd_rank_batched_##SUF(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, int32_t count, int64_t k, double tol,          \
                                         rc_matrix u, int64_t u_batch_stride, R *s, rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks) {  \
         return guarded(ctx, [&] {                                                                                                            \
             k = check_svd_rank_batched(a, count, k, tol, u, u_batch_stride, s, vt, vt_batch_stride, ranks);                                  \
             if (count == 0) return;                                                                                                          \
-            S<R>::svd(ctx, S<R>::view(a), a_batch_stride, count, k, tol, S<R>::view(u), u_batch_stride, s, S<R>::view(vt), vt_batch_stride,  \
-                      ranks);                                                                                                                \
+            batched_svd<E>(ctx, from_c<E>(a), a_batch_stride, count, k, tol, from_c<E>(u), u_batch_stride, s, from_c<E>(vt),                 \
+                           vt_batch_stride, ranks);                                                                                          \
         });                                                                                                                                  \
     }                                                                                                                                        \
-    /* apply (b given) or rebuild (b.data == nullptr) every block of a batch from its factors, reading the ranks on the device: one */      \
+    /* apply (b given) or rebuild (b.data == nullptr) every block of a batch from its factors, reading the ranks on the device: one */       \
     /* launch, no workspace */                                                                                                               \
     rc_status rc_lowrank_apply_batched_##SUF(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid,                      \
                                              int64_t mid_batch_stride, const R *s, int64_t s_stride, rc_matrix right,                        \
@@ -394,12 +370,13 @@ extern "C" {
         return guarded(ctx, [&] {                                                                                                            \
             check_lowrank_apply_batched(left, mid, right, count, b, y, y_batch_stride);                                                      \
             if (count == 0) return;                                                                                                          \
-            S<R>::lowrank_apply(ctx, S<R>::view(left), left_batch_stride, S<R>::view(mid), mid_batch_stride, s, s_stride, S<R>::view(right), \
-                                right_batch_stride, ranks, count, S<R>::view(b), b_batch_stride, S<R>::view(y), y_batch_stride);             \
+            batched_lowrank_apply<E>(ctx, from_c<E>(left), left_batch_stride, from_c<E>(mid), mid_batch_stride, s, s_stride,                 \
+                                     from_c<E>(right), right_batch_stride, ranks, count, from_c<E>(b), b_batch_stride, from_c<E>(y),         \
+                                     y_batch_stride);                                                                                        \
         });                                                                                                                                  \
     }                                                                                                                                        \
-    /* y = H x for the block-sparse operator made of a low-rank batch and a dense batch placed by a block-CSR pattern on the device: */     \
-    /* one launch, no workspace; conj is ignored on real data, where conjugation is the identity */                                         \
+    /* y = H x for the block-sparse operator made of a low-rank batch and a dense batch placed by a block-CSR pattern on the device: */      \
+    /* one launch, no workspace; conj is ignored on real data, where conjugation is the identity */                                          \
     rc_status rc_block_operator_apply_##SUF(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid,                       \
                                             int64_t mid_batch_stride, const R *s, int64_t s_stride, rc_matrix right,                         \
                                             int64_t right_batch_stride, const int64_t *ranks, int32_t count, rc_matrix dense,                \
@@ -410,46 +387,46 @@ extern "C" {
             const BlockPattern pat{group_ptr, group_row, entry_block, entry_col, groups};                                                    \
             const BlockShape sh = check_block_operator_apply(left, mid, right, count, dense, &dense_count, pat, x, y);                       \
             if (groups == 0) return;                                                                                                         \
-            S<R>::block_operator(conj != 0, ctx, S<R>::view(left), left_batch_stride, S<R>::view(mid), mid_batch_stride, s, s_stride,        \
-                                 S<R>::view(right), right_batch_stride, ranks, count, S<R>::view(dense), dense_batch_stride, dense_count,    \
-                                 pat, sh, S<R>::view(x), S<R>::view(y), accumulate != 0);                                                    \
+            block_operator_apply<E>(ctx, from_c<E>(left), left_batch_stride, from_c<E>(mid), mid_batch_stride, s, s_stride,                  \
+                                    from_c<E>(right), right_batch_stride, ranks, count, from_c<E>(dense), dense_batch_stride, dense_count,   \
+                                    pat, sh, from_c<E>(x), from_c<E>(y), accumulate != 0, conj != 0);                                        \
         });                                                                                                                                  \
     }                                                                                                                                        \
-    /* recompress every factor pair left (m x K) [mid (K x K)] [diag(s)] right (K x n) of a batch to a truncated SVD of rank */             \
-    /* <= min(k, K) without forming the m x n blocks (SVD::to_qr / compute_from_range_estimate's scheme, src/svd.rs:150-163, :171-, */      \
-    /* with compress's rank rule, :60-101): one launch; s, s_out (and the complex call's tol) in the real type, vt = V^H */                 \
+    /* recompress every factor pair left (m x K) [mid (K x K)] [diag(s)] right (K x n) of a batch to a truncated SVD of rank */              \
+    /* <= min(k, K) without forming the m x n blocks (SVD::to_qr / compute_from_range_estimate's scheme, src/svd.rs:150-163, :171-, */       \
+    /* with compress's rank rule, :60-101): one launch; s, s_out (and the complex call's tol) in the real type, vt = V^H */                  \
     rc_status rc_lowrank_recompress_##CX##batched_##SUF(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid,           \
                                                         int64_t mid_batch_stride, const R *s, int64_t s_stride, rc_matrix right,             \
                                                         int64_t right_batch_stride, const int64_t *in_ranks, int32_t count, int64_t k,       \
-                                                        S<R>::recompress_tol tol, rc_matrix u, int64_t u_batch_stride, R *s_out,             \
+                                                        Scalar<E>::recompress_tol tol, rc_matrix u, int64_t u_batch_stride, R *s_out,        \
                                                         rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks) {                             \
         return guarded(ctx, [&] {                                                                                                            \
             check_lowrank_recompress_batched(left, mid, right, count, k, tol, u, u_batch_stride, s_out, vt, vt_batch_stride, ranks);         \
             if (count == 0) return;                                                                                                          \
-            S<R>::recompress(ctx, S<R>::view(left), left_batch_stride, S<R>::view(mid), mid_batch_stride, s, s_stride, S<R>::view(right),    \
-                             right_batch_stride, in_ranks, count, k, (double)tol, S<R>::view(u), u_batch_stride, s_out, S<R>::view(vt),      \
-                             vt_batch_stride, ranks);                                                                                        \
+            batched_lowrank_recompress<E>(ctx, from_c<E>(left), left_batch_stride, from_c<E>(mid), mid_batch_stride, s, s_stride,            \
+                                          from_c<E>(right), right_batch_stride, in_ranks, count, k, (double)tol, from_c<E>(u),               \
+                                          u_batch_stride, s_out, from_c<E>(vt), vt_batch_stride, ranks);                                     \
         });                                                                                                                                  \
     }                                                                                                                                        \
-    /* the same for a tall left factor (m <= 65536): the same checks with that bound under the call's own name, the left factor by a */     \
+    /* the same for a tall left factor (m <= 65536): the same checks with that bound under the call's own name, the left factor by a */      \
     /* flat Householder TSQR inside the launch */                                                                                            \
     rc_status rc_lowrank_recompress_tall_##CX##batched_##SUF(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid,      \
                                                              int64_t mid_batch_stride, const R *s, int64_t s_stride, rc_matrix right,        \
                                                              int64_t right_batch_stride, const int64_t *in_ranks, int32_t count, int64_t k,  \
-                                                             S<R>::recompress_tol tol, rc_matrix u, int64_t u_batch_stride, R *s_out,        \
+                                                             Scalar<E>::recompress_tol tol, rc_matrix u, int64_t u_batch_stride, R *s_out,   \
                                                              rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks) {                        \
         return guarded(ctx, [&] {                                                                                                            \
             check_lowrank_recompress_batched(left, mid, right, count, k, tol, u, u_batch_stride, s_out, vt, vt_batch_stride, ranks,          \
-                                             S<R>::tall);                                                                                    \
+                                             Scalar<E>::tall);                                                                               \
             if (count == 0) return;                                                                                                          \
-            S<R>::recompress_tall(ctx, S<R>::view(left), left_batch_stride, S<R>::view(mid), mid_batch_stride, s, s_stride,                  \
-                                  S<R>::view(right), right_batch_stride, in_ranks, count, k, (double)tol, S<R>::view(u), u_batch_stride,     \
-                                  s_out, S<R>::view(vt), vt_batch_stride, ranks);                                                            \
+            batched_lowrank_recompress_tall<E>(ctx, from_c<E>(left), left_batch_stride, from_c<E>(mid), mid_batch_stride, s, s_stride,       \
+                                               from_c<E>(right), right_batch_stride, in_ranks, count, k, (double)tol, from_c<E>(u),          \
+                                               u_batch_stride, s_out, from_c<E>(vt), vt_batch_stride, ranks);                                \
         });                                                                                                                                  \
     }                                                                                                                                        \
-    /* the one-pass randomized column ID of every block of a batch: the sketch y = omega a (l x n, nothing conjugated) and the column */    \
-    /* ID of y in one launch, c gathered from a (sample_range_by_rank's projection, src/random_sampling.rs, then */                         \
-    /* QR::compute_from_range_estimate + column_id, src/qr.rs:311-323, per block) */                                                        \
+    /* the one-pass randomized column ID of every block of a batch: the sketch y = omega a (l x n, nothing conjugated) and the column */     \
+    /* ID of y in one launch, c gathered from a (sample_range_by_rank's projection, src/random_sampling.rs, then */                          \
+    /* QR::compute_from_range_estimate + column_id, src/qr.rs:311-323, per block) */                                                         \
     rc_status rc_sketch_column_id_rank_##CX##batched_##SUF(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega,            \
                                                            int64_t omega_batch_stride, int32_t count, int64_t k, double tol, rc_matrix y,    \
                                                            int64_t y_batch_stride, rc_matrix c, int64_t c_batch_stride, rc_matrix z,         \
@@ -458,12 +435,13 @@ extern "C" {
             const int64_t kk = check_sketch_column_id_rank_batched(a, omega, count, k, tol, y, y_batch_stride, c, c_batch_stride, z,         \
                                                                    z_batch_stride, col_ind, ranks);                                          \
             if (count == 0) return;                                                                                                          \
-            S<R>::sketch_column_id(ctx, S<R>::view(a), a_batch_stride, S<R>::view(omega), omega_batch_stride, count, kk, tol, S<R>::view(y), \
-                                   y_batch_stride, S<R>::view(c), c_batch_stride, S<R>::view(z), z_batch_stride, col_ind, ranks);            \
+            batched_sketch_column_id<E>(ctx, from_c<E>(a), a_batch_stride, from_c<E>(omega), omega_batch_stride, count, kk, tol,             \
+                                        from_c<E>(y), y_batch_stride, from_c<E>(c), c_batch_stride, from_c<E>(z), z_batch_stride, col_ind,   \
+                                        ranks);                                                                                              \
         });                                                                                                                                  \
     }                                                                                                                                        \
-    /* ||a_i - left_i mid_i diag(s_i) right_i||_F at each block's rank, ||a_i||_F and optionally the residual blocks, for the factors */    \
-    /* of any batched compressor: the reference's rel_diff_fro(x.to_mat(), a) per block (src/lib.rs), in one launch and on the */           \
+    /* ||a_i - left_i mid_i diag(s_i) right_i||_F at each block's rank, ||a_i||_F and optionally the residual blocks, for the factors */     \
+    /* of any batched compressor: the reference's rel_diff_fro(x.to_mat(), a) per block (src/lib.rs), in one launch and on the */            \
     /* sketched ID's domain; s, err and nrm in the real type */                                                                              \
     rc_status rc_lowrank_residual_batched_##SUF(rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix left,                        \
                                                 int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const R *s,              \
@@ -472,55 +450,39 @@ extern "C" {
         return guarded(ctx, [&] {                                                                                                            \
             check_lowrank_residual_batched(a, left, mid, right, count, e, e_batch_stride, err);                                              \
             if (count == 0) return;                                                                                                          \
-            S<R>::residual(ctx, S<R>::view(a), a_batch_stride, S<R>::view(left), left_batch_stride, S<R>::view(mid), mid_batch_stride, s,    \
-                           s_stride, S<R>::view(right), right_batch_stride, ranks, count, S<R>::view(e), e_batch_stride, err, nrm);          \
+            batched_lowrank_residual<E>(ctx, from_c<E>(a), a_batch_stride, from_c<E>(left), left_batch_stride, from_c<E>(mid),               \
+                                        mid_batch_stride, s, s_stride, from_c<E>(right), right_batch_stride, ranks, count, from_c<E>(e),     \
+                                        e_batch_stride, err, nrm);                                                                           \
         });                                                                                                                                  \
     }
 
-RC_DEFINE_BATCHED(f64, double, Real, )
-RC_DEFINE_BATCHED(f32, float, Real, )
-RC_DEFINE_BATCHED(c64, double, Cplx, complex_)
-RC_DEFINE_BATCHED(c32, float, Cplx, complex_)
+RC_DEFINE_BATCHED(f64, double, double, )
+RC_DEFINE_BATCHED(f32, float, float, )
+RC_DEFINE_BATCHED(c64, double, cplx<double>, complex_)
+RC_DEFINE_BATCHED(c32, float, cplx<float>, complex_)
 
-// the recompression with both factors tall (m, n <= 65536): the pair's checks with those bounds under the call's own name, both factors by a
-// flat Householder TSQR inside the launch.  The real pair; the complex twin's stem is spelled differently (below), so both stanzas stand outside RC_DEFINE_BATCHED.
-#define RC_DEFINE_RECOMPRESS_LARGE(SUF, R)                                                                                                   \
-    rc_status rc_lowrank_recompress_large_batched_##SUF(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid,           \
-                                                        int64_t mid_batch_stride, const R *s, int64_t s_stride, rc_matrix right,             \
-                                                        int64_t right_batch_stride, const int64_t *in_ranks, int32_t count, int64_t k,       \
-                                                        double tol, rc_matrix u, int64_t u_batch_stride, R *s_out, rc_matrix vt,             \
-                                                        int64_t vt_batch_stride, int64_t *ranks) {                                           \
+// the recompression with both factors tall (m, n <= 65536): the tall call's signature (the complex tol in the real type) and the pair's checks
+// with those bounds under the call's own name (MODE), both factors by a flat Householder TSQR inside the launch.  The complex stem is
+// rc_lowrank_recompress_complex_large_batched_, "complex" before "large", so the stanza stands outside RC_DEFINE_BATCHED: the names the real
+// pair's section proposed for a complex twin (..._large_batched_c64 / _c32, ..._large_complex_batched_c64 / _c32) are pinned as absent by
+// that pair's ABI test and stay absent.
+#define RC_DEFINE_RECOMPRESS_LARGE(STEM, SUF, R, E, MODE)                                                                                    \
+    rc_status STEM##SUF(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid, int64_t mid_batch_stride, const R *s,     \
+                        int64_t s_stride, rc_matrix right, int64_t right_batch_stride, const int64_t *in_ranks, int32_t count, int64_t k,    \
+                        Scalar<E>::recompress_tol tol, rc_matrix u, int64_t u_batch_stride, R *s_out, rc_matrix vt, int64_t vt_batch_stride, \
+                        int64_t *ranks) {                                                                                                    \
         return guarded(ctx, [&] {                                                                                                            \
-            check_lowrank_recompress_batched(left, mid, right, count, k, tol, u, u_batch_stride, s_out, vt, vt_batch_stride, ranks,          \
-                                             RC_LARGE);                                                                                      \
+            check_lowrank_recompress_batched(left, mid, right, count, k, tol, u, u_batch_stride, s_out, vt, vt_batch_stride, ranks, MODE);   \
             if (count == 0) return;                                                                                                          \
-            Real<R>::recompress_large(ctx, Real<R>::view(left), left_batch_stride, Real<R>::view(mid), mid_batch_stride, s, s_stride,        \
-                                      Real<R>::view(right), right_batch_stride, in_ranks, count, k, tol, Real<R>::view(u), u_batch_stride,   \
-                                      s_out, Real<R>::view(vt), vt_batch_stride, ranks);                                                     \
+            batched_lowrank_recompress_large<E>(ctx, from_c<E>(left), left_batch_stride, from_c<E>(mid), mid_batch_stride, s, s_stride,      \
+                                                from_c<E>(right), right_batch_stride, in_ranks, count, k, (double)tol, from_c<E>(u),         \
+                                                u_batch_stride, s_out, from_c<E>(vt), vt_batch_stride, ranks);                               \
         });                                                                                                                                  \
     }
-RC_DEFINE_RECOMPRESS_LARGE(f64, double)
-RC_DEFINE_RECOMPRESS_LARGE(f32, float)
-
-// its complex twin: the tall complex call's signature (tol in the real type) and the same checks under this call's own name.  The stem is
-// rc_lowrank_recompress_complex_large_batched_, "complex" before "large": the names the real pair's section proposed for a complex twin
-// (..._large_batched_c64 / _c32, ..._large_complex_batched_c64 / _c32) are pinned as absent by that pair's ABI test and stay absent.
-#define RC_DEFINE_RECOMPRESS_COMPLEX_LARGE(SUF, R)                                                                                           \
-    rc_status rc_lowrank_recompress_complex_large_batched_##SUF(rc_context *ctx, rc_matrix left, int64_t left_batch_stride, rc_matrix mid,   \
-                                                                int64_t mid_batch_stride, const R *s, int64_t s_stride, rc_matrix right,     \
-                                                                int64_t right_batch_stride, const int64_t *in_ranks, int32_t count,          \
-                                                                int64_t k, R tol, rc_matrix u, int64_t u_batch_stride, R *s_out,             \
-                                                                rc_matrix vt, int64_t vt_batch_stride, int64_t *ranks) {                     \
-        return guarded(ctx, [&] {                                                                                                            \
-            check_lowrank_recompress_batched(left, mid, right, count, k, tol, u, u_batch_stride, s_out, vt, vt_batch_stride, ranks,          \
-                                             RC_LARGE_COMPLEX);                                                                              \
-            if (count == 0) return;                                                                                                          \
-            Cplx<R>::recompress_large(ctx, left, left_batch_stride, mid, mid_batch_stride, s, s_stride, right, right_batch_stride, in_ranks, \
-                                      count, k, (double)tol, u, u_batch_stride, s_out, vt, vt_batch_stride, ranks);                          \
-        });                                                                                                                                  \
-    }
-RC_DEFINE_RECOMPRESS_COMPLEX_LARGE(c64, double)
-RC_DEFINE_RECOMPRESS_COMPLEX_LARGE(c32, float)
+RC_DEFINE_RECOMPRESS_LARGE(rc_lowrank_recompress_large_batched_, f64, double, double, RC_LARGE)
+RC_DEFINE_RECOMPRESS_LARGE(rc_lowrank_recompress_large_batched_, f32, float, float, RC_LARGE)
+RC_DEFINE_RECOMPRESS_LARGE(rc_lowrank_recompress_complex_large_batched_, c64, double, cplx<double>, RC_LARGE_COMPLEX)
+RC_DEFINE_RECOMPRESS_LARGE(rc_lowrank_recompress_complex_large_batched_, c32, float, cplx<float>, RC_LARGE_COMPLEX)
 
 // the sketch y = omega a of every block of a batch and nothing else, for blocks of up to 65536 columns: the front end of a randomized SVD of
 // wide or square blocks, and, on transposed views, its projection p = a q^T.  Real scalars only, like the large recompression.
@@ -541,13 +503,13 @@ RC_DEFINE_SKETCH_PRODUCT(f32, float)
     rc_context *ctx, rc_matrix a, int64_t a_batch_stride, rc_matrix omega, int64_t omega_batch_stride, int32_t count, rc_matrix y, int64_t y_batch_stride, \
         rc_matrix q, int64_t q_batch_stride, rc_matrix p, int64_t p_batch_stride, int64_t *ranks
 #define RC_RANGE_STEP_ARGS ctx, a, a_batch_stride, omega, omega_batch_stride, count, y, y_batch_stride, q, q_batch_stride, p, p_batch_stride, ranks
-rc_status rc_sketch_range_step_batched_f64(RC_RANGE_STEP_PARAMS) { return sketch_range_step<Real<double>>(RC_RANGE_STEP_ARGS, false); }
-rc_status rc_sketch_range_step_batched_f32(RC_RANGE_STEP_PARAMS) { return sketch_range_step<Real<float>>(RC_RANGE_STEP_ARGS, false); }
+rc_status rc_sketch_range_step_batched_f64(RC_RANGE_STEP_PARAMS) { return sketch_range_step<double>(RC_RANGE_STEP_ARGS, false); }
+rc_status rc_sketch_range_step_batched_f32(RC_RANGE_STEP_PARAMS) { return sketch_range_step<float>(RC_RANGE_STEP_ARGS, false); }
 rc_status rc_sketch_range_step_complex_batched_c64(RC_RANGE_STEP_PARAMS, int32_t p_conj) {
-    return sketch_range_step<Cplx<double>>(RC_RANGE_STEP_ARGS, p_conj != 0);
+    return sketch_range_step<cplx<double>>(RC_RANGE_STEP_ARGS, p_conj != 0);
 }
 rc_status rc_sketch_range_step_complex_batched_c32(RC_RANGE_STEP_PARAMS, int32_t p_conj) {
-    return sketch_range_step<Cplx<float>>(RC_RANGE_STEP_ARGS, p_conj != 0);
+    return sketch_range_step<cplx<float>>(RC_RANGE_STEP_ARGS, p_conj != 0);
 }
 
 rc_status rc_lowrank_recompress_tall_batched_plan(int64_t m, int64_t n, int64_t inner, int32_t elem_bytes, int64_t resident, int64_t *stages,
@@ -578,7 +540,7 @@ rc_status rc_lowrank_recompress_complex_large_batched_plan(int64_t m, int64_t n,
         return guarded(ctx, [&] {                                                                                                            \
             check_lowrank_apply_batched(left, mid, right, count, b, y, y_batch_stride);                                                      \
             if (count == 0) return;                                                                                                          \
-            batched_lowrank_apply_mixed(ctx, COMPLEX, left, left_batch_stride, mid, mid_batch_stride, s, s_stride, right, right_batch_stride, \
+            batched_lowrank_apply_mixed(ctx, COMPLEX, left, left_batch_stride, mid, mid_batch_stride, s, s_stride, right, right_batch_stride,\
                                         ranks, count, b, b_batch_stride, y, y_batch_stride);                                                 \
         });                                                                                                                                  \
     }                                                                                                                                        \

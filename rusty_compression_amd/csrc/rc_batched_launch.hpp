@@ -1,9 +1,9 @@
 // The launch path of the persistent batched kernels (host only, but for the tall recompressions' stage arithmetic): every launcher of kernels_batched_id.hip, kernels_batched_id_c.hip,
 // kernels_batched_apply.hip, kernels_block_operator.hip, kernels_batched_residual.hip and kernels_batched_residual_c.hip goes
 //     plan (a pure function of the shapes, in its own file)  ->  batched_prepare  ->  ProfScope  ->  workspace()  ->  launch(...)
-// so that the LDS cap, the grid rule, the workspace unit (bytes) and the launch check live here once.  The plans and launcher bodies of the
-// column and two-sided IDs are written once for all four element types in batched_stages.hpp, with the device stages the real and complex
-// kernels share.
+// so that the LDS cap, the grid rule, the workspace unit (bytes) and the launch check live here once.  The plans and launcher bodies of
+// kernels_batched_id.hip and kernels_batched_id_c.hip are written once for all four element types: those of the column and two-sided IDs in
+// batched_stages.hpp, with the device stages the real and complex kernels share, the others in batched_launchers.hpp.
 #pragma once
 #include <algorithm>
 
@@ -44,13 +44,17 @@ struct BatchedPlan {
     size_t lds, ws;
 };
 
-// the first of the candidate places, in the list's order, whose LDS need lds(place) is at most BID_MAX_LDS; ws(place) is its workspace
+// the first of the n candidate places, in the list's order, whose LDS need lds(place) is at most BID_MAX_LDS; ws(place) is its workspace
+template <typename Place, typename Lds, typename Ws>
+BatchedPlan<Place> batched_first_fit(const Place *places, size_t n, Lds lds, Ws ws, const char *what) {
+    size_t i = 0;
+    while (i < n && (size_t)lds(places[i]) > BID_MAX_LDS) ++i;
+    RC_REQUIRE(i < n, RC_RUNTIME_ERROR, "%s: %zu bytes of LDS", what, (size_t)lds(places[n - 1]));
+    return {places[i], (size_t)lds(places[i]), (size_t)ws(places[i])};
+}
 template <typename Place, size_t N, typename Lds, typename Ws>
 BatchedPlan<Place> batched_first_fit(const Place (&places)[N], Lds lds, Ws ws, const char *what) {
-    size_t i = 0;
-    while (i < N && (size_t)lds(places[i]) > BID_MAX_LDS) ++i;
-    RC_REQUIRE(i < N, RC_RUNTIME_ERROR, "%s: %zu bytes of LDS", what, (size_t)lds(places[N - 1]));
-    return {places[i], (size_t)lds(places[i]), (size_t)ws(places[i])};
+    return batched_first_fit(places, N, lds, ws, what);
 }
 // the launchers with one movable buffer W of w_bytes: in LDS when lds(true) fits, else in the workspace
 template <typename Lds>

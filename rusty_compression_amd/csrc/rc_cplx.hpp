@@ -1,5 +1,6 @@
 // The complex element of every complex kernel (rc_complex.hip, kernels_batched_id_c.hip, batched_stages.hpp, batched_apply.hpp and the
-// two kernels built on it, kernels_batched_residual_c.hip) and the strided complex view of an rc_matrix.  Complex data is interleaved (re, im) -- the
+// two kernels built on it, kernels_batched_residual_c.hip), which rc_batched.hpp declares for the launchers' signatures, and the strided complex
+// view of an rc_matrix.  Complex data is interleaved (re, im) -- the
 // layout of ndarray's Complex<T> / numpy complex -- and aligned as its real type, so a view may start at any element of a caller's array.
 #pragma once
 #include "rc_common.hpp"
@@ -7,12 +8,14 @@
 
 namespace rc {
 
-namespace {
-
+// one type in every translation unit (rc_batched.hpp declares it), so that Mat<cplx<R>> crosses them; its operations stay internal to each
 template <typename R>
 struct cplx {
     R re, im;
 };
+
+namespace {
+
 template <typename R> __host__ __device__ __forceinline__ cplx<R> mk(R a, R b) { return cplx<R>{a, b}; }
 template <typename R> __host__ __device__ __forceinline__ cplx<R> czero() { return {(R)0, (R)0}; }
 template <typename R> __host__ __device__ __forceinline__ cplx<R> cone() { return {(R)1, (R)0}; }
@@ -40,12 +43,12 @@ template <typename R> __device__ __forceinline__ void cfma(cplx<R> a, cplx<R> b,
 }
 
 // The complex side of the element operations the shared batched stages are written in (batched_stages.hpp, where the real side and the
-// primary elem<E> stand): the real type with zero and one, division (Smith's), the larger pow2_key of the two parts, scaling by a
-// real, and the back substitution's acc -= a b in the complex kernels' spelling.  abs2 and cj above are shared as they are.
+// primary elem<E> stand): zero and one, division (Smith's), the larger pow2_key of the two parts, scaling by a real, and the back
+// substitution's acc -= a b in the complex kernels' spelling.  abs2 and cj above are shared as they are; the real type is real_t<E>
+// (rc_batched.hpp).
 template <typename E> struct elem;
 template <typename R>
 struct elem<cplx<R>> {
-    using real = R;
     static __host__ __device__ __forceinline__ cplx<R> zero() { return czero<R>(); }
     static __host__ __device__ __forceinline__ cplx<R> one() { return cone<R>(); }
 };

@@ -1,5 +1,5 @@
 // The host code the dense real API (rc_api.hip: f64 / f32) and the dense complex API (rc_complex.hip: c64 / c32) have in common, written once
-// over the element type E (double, float, cplx<double>, cplx<float>); real_t<E> is the type of norms and tolerances.  Host templates only:
+// over the element type E (double, float, cplx<double>, cplx<float>); real_t<E> (rc_batched.hpp) is the type of norms and tolerances.  Host templates only:
 // no kernel stands here, and nothing here is exported.  Each of the two files includes this header AFTER its own primitives, inside its
 // `using namespace rc`, and expands RC_DEFINE_DENSE_SHARED for its two suffixes.
 //
@@ -24,10 +24,6 @@
 #include "rc_cplx.hpp"
 
 namespace {
-
-template <typename E> struct real_of { using type = E; };
-template <typename R> struct real_of<cplx<R>> { using type = R; };
-template <typename E> using real_t = typename real_of<E>::type;
 
 // The operator the range finders sample: the reference implements them for ANY `Op: MatMat` / `Op: ConjMatMat`
 // (/root/reference/src/random_sampling.rs:102, :130, :222; trait contract src/types.rs:40-51, :77-81, products :58-71, :88-101; all four
