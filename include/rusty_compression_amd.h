@@ -140,6 +140,10 @@ rc_status rc_graph_destroy(rc_context *ctx, void *graph_exec);
  * (iii) RC_OPT_FUSED_CONSUMERS selects the order and the launches of the two consumers of B in rc_rsvd_id_*; bits are promised per
  * setting like the others (today the two settings agree bit for bit -- tests/test_gpu_fused_consumers.py -- because neither
  * factorization changes its arithmetic, but only the per-setting promise is API).
+ * Across RELEASES bits are not promised.  Since the small products of the tall-skinny QR (R2 R1, R2^-1 Q2, Q1[:k, :] W, R2^-1 Vc) are
+ * formed inside the kernels next to them, each entry in one ascending order instead of a two-slab GEMM, results move at rounding
+ * level wherever the second CholeskyQR pass does not reduce to the identity (first-pass defect above 2.5e-14 in f64, 1e-6 in f32);
+ * where it does (well-conditioned sketches, the cfg3 workload) they are the bits of the GEMM order.
  * Environment switches that select between implementations (measurement aids, read once per process) change rounding the same
  * way and are NOT part of the promise: RC_TSQR_FOLD (order of the small factors of the tall-skinny QR), RC_QRCP_CAND_MB (which
  * columns of a blocked panel are updated reflector by reflector and which through the block update: last bits of R12 / Z),

@@ -771,12 +771,16 @@ __global__ __launch_bounds__(256) void k_id_z(Mat<T> w, const int64_t *jpvt, int
 // matrix wf, its pivots and tau, and none reads what another writes (Z is solved from wf, not from R: k_id_z<T, false>, the same
 // bits).  Workgroups take a role by blockIdx.x range; the roles exchange nothing (no flags, no atomics, no waits):
 //   [0, nz)            Z role: the body of k_id_z<T, false>, first so that its workgroups (the longest) are dispatched first
-//   [nz, nz + nq)      Q_b role: the body of k_form_q_small<T, NE>, 32 output columns per workgroup, reflectors in its own LDS
-//   [nz + nq, grid)    R role: the body of k_extract_r, grid-stride over its workgroups
-// Dynamic LDS is what the Q_b role needs; the other roles ignore it.
+//   [nz, nz + ns)      small role (ns may be 0): small = r2i x for svd_finish, the body of small_tri_product (rc_device.hpp),
+//                      kSmallProductCols columns per workgroup.  Not a tail of wf: r2i and x (the right vectors of the core)
+//                      were complete before the launch, small is written here alone, and the role is over long before Z's
+//   [nz + ns, + nq)    Q_b role: the body of k_form_q_small<T, NE>, 32 output columns per workgroup, reflectors in its own LDS
+//   [nz + ns + nq, grid)  R role: the body of k_extract_r, grid-stride over its workgroups
+// Dynamic LDS is what the Q_b role needs (the small role's columns fit in it); the other roles ignore it.
 // ---------------------------------------------------------------------------
 template <typename T, int NE>
-__global__ __launch_bounds__(256) void k_rsvd_id_tails(Mat<T> w, const int64_t *jpvt, const T *tau, int k, Mat<T> z, Mat<T> qw, Mat<T> r, int nz, int nq) {
+__global__ __launch_bounds__(256) void k_rsvd_id_tails(Mat<T> w, const int64_t *jpvt, const T *tau, int k, Mat<T> z, Mat<T> qw, Mat<T> r, int nz, int nq, Mat<T> r2i,
+                                                       Mat<T> x, Mat<T> small, int ns) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     __shared__ T tile[kIdzNB][kIdzNB + 1];
     __shared__ int64_t jtri[8 * NE];  // (k <= 8 NE: the rows a column of the Q_b role holds)
@@ -786,29 +790,36 @@ __global__ __launch_bounds__(256) void k_rsvd_id_tails(Mat<T> w, const int64_t *
         __syncthreads();
         id_z_body<T, false, false>(w, jpvt, jtri, k, z, IdzCheck<false>{}, tile, wg, tid, 256);
     }
-    else if (wg < nz + nq) form_q_small_body<T, NE>(w, jpvt, tau, k, qw, smem_raw, wg - nz, tid, 256);
-    else extract_r_body<T>(w, jpvt, r, wg - nz - nq, (int64_t)gridDim.x - nz - nq, tid, 256);
+    else if (wg < nz + ns) {
+        const int c0 = (wg - nz) * kSmallProductCols;
+        small_product_tri<T, NE>(r2i, x, small, c0, min(kSmallProductCols, (int)x.cols - c0), reinterpret_cast<T *>(smem_raw), tid, 256);
+    }
+    else if (wg < nz + ns + nq) form_q_small_body<T, NE>(w, jpvt, tau, k, qw, smem_raw, wg - nz - ns, tid, 256);
+    else extract_r_body<T>(w, jpvt, r, wg - nz - ns - nq, (int64_t)gridDim.x - nz - ns - nq, tid, 256);
 }
 // wf: k x n in the ?geqp3 format (column-major, k steps done), 64 < k <= 128 < n; qb: k x k column-major; r: k x n; z: k x n or
-// empty (then the launch has no Z role)
+// empty (then the launch has no Z role); r2i, x, small: k x k or all empty (then it has no small role)
 template <typename T>
-void rsvd_id_tails(rc_context *c, Mat<T> wf, const int64_t *jpvt, const T *tau, Mat<T> qb, Mat<T> r, Mat<T> z) {
+void rsvd_id_tails(rc_context *c, Mat<T> wf, const int64_t *jpvt, const T *tau, Mat<T> qb, Mat<T> r, Mat<T> z, Mat<T> r2i, Mat<T> x, Mat<T> small) {
     const int64_t k = wf.rows, n = wf.cols;
+    RC_REQUIRE(small.empty() || (r2i.rows == k && r2i.cols == k && x.rows == k && x.cols == k && small.rows == k && small.cols == k), RC_INVALID_ARGUMENT,
+               "rsvd_id_tails: shape mismatch of the small product");
     RC_REQUIRE(wf.rs == 1 && qb.rs == 1 && qb.rows == k && qb.cols == k && r.rows == k && r.cols == n && k > 64 && k <= 8 * 16 && k < n &&
                    (z.empty() || (z.rows == k && z.cols == n)),
                RC_INVALID_ARGUMENT, "rsvd_id_tails: shape mismatch");
     constexpr int NE = 16, CPW = 256 / 8;
     const int nz = z.empty() ? 0 : (int)cdiv(n, 256), nq = (int)cdiv(qb.cols, CPW);
     const int nr = (int)std::min<int64_t>(cdiv(k * n, 256), 192);
-    const size_t lds = ((size_t)k * 8 * NE + (size_t)k) * sizeof(T);
-    ProfScope ps(c, "op:rsvd_id_tails k=%lld n=%lld wgs=%d+%d+%d", (long long)k, (long long)n, nz, nq, nr);
+    const int ns = small.empty() ? 0 : (int)cdiv(k, kSmallProductCols);
+    const size_t lds = ((size_t)k * 8 * NE + (size_t)k) * sizeof(T);  // (>= kSmallProductCols * (k | 1) words: k > 64)
+    ProfScope ps(c, "op:rsvd_id_tails k=%lld n=%lld wgs=%d+%d+%d+%d", (long long)k, (long long)n, nz, ns, nq, nr);
     auto kern = k_rsvd_id_tails<T, NE>;
     static bool attr_set[64] = {};
     if (!attr_set[c->device & 63]) {
         RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096));
         attr_set[c->device & 63] = true;
     }
-    hipLaunchKernelGGL(kern, dim3((unsigned)(nz + nq + nr)), dim3(256), lds, c->stream, wf, jpvt, tau, (int)k, z, qb, r, nz, nq);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(nz + ns + nq + nr)), dim3(256), lds, c->stream, wf, jpvt, tau, (int)k, z, qb, r, nz, nq, r2i, x, small, ns);
 }
 // a: the original m x n matrix (any layout); w: its factorization in the ?geqp3 format (column-major, columns in place, k steps);
 // jpvt: position -> physical column; cm: m x k, z: k x n
@@ -845,7 +856,7 @@ void id_z_from_r_checked(rc_context *c, Mat<T> r, int64_t k, const int64_t *ind,
     template void id_z_from_r_checked<T>(rc_context *, Mat<T>, int64_t, const int64_t *, const int64_t *, Mat<T>); \
     template void geqp3_inplace<T>(rc_context *, Mat<T>, int64_t, bool, int64_t *, T *, T *);             \
     template void extract_r<T>(rc_context *, Mat<T>, const int64_t *, Mat<T>);                             \
-    template void rsvd_id_tails<T>(rc_context *, Mat<T>, const int64_t *, const T *, Mat<T>, Mat<T>, Mat<T>); \
+    template void rsvd_id_tails<T>(rc_context *, Mat<T>, const int64_t *, const T *, Mat<T>, Mat<T>, Mat<T>, Mat<T>, Mat<T>, Mat<T>); \
     template void form_q<T>(rc_context *, Mat<T>, const int64_t *, const T *, int64_t, Mat<T>);           \
     template void trsm_upper<T>(rc_context *, Mat<T>, Mat<T>);
 RC_INST(double)

@@ -47,9 +47,13 @@ __device__ inline T row_sum16(T v) {  // sum over an aligned group of 16 lanes
 // Cholesky G = R^T R (R upper) + R^{-1}, n x n in the LDS of one workgroup.
 //   flag bit 0: non-positive pivot (G not numerically SPD)
 //   flag bit 1: check_identity && max|G - I| > ident_tol  (first pass left Q1 too far from orthonormal)
+// r1 (empty on the first pass of CholeskyQR2): the first pass's factor.  The second pass then leaves the factor of the whole
+// matrix, r_out = R r1, instead of its own R: no caller wants R2 by itself, and the product was a GEMM and a reduction launch
+// behind this kernel.  Each entry is one sum over the inner index, ascending from the diagonal of R to that of r1.
+// FOLD says whether r1 is given: the first pass keeps the instance it had (its n dependent steps are a tenth of the chain).
 // ---------------------------------------------------------------------------
-template <typename T, int NT>
-__global__ __launch_bounds__(1024) void k_chol_inv(Mat<T> g, Mat<T> r_out, Mat<T> rinv_out, int check_identity, T ident_tol, T skip_tol, int *flag) {
+template <typename T, int NT, bool FOLD>
+__global__ __launch_bounds__(1024) void k_chol_inv(Mat<T> g, Mat<T> r_out, Mat<T> rinv_out, Mat<T> r1, int check_identity, T ident_tol, T skip_tol, int *flag) {
     // Register-tiled right-looking Cholesky: thread (ti, tc) of the 32 x 32 thread grid owns
     // the entries (ti + 32 a, tc + 32 b), a, b < NT, in registers; per step only pivot row j
     // goes through LDS (double buffered: ONE barrier per step).
@@ -77,6 +81,20 @@ __global__ __launch_bounds__(1024) void k_chol_inv(Mat<T> g, Mat<T> r_out, Mat<T
             }
             reg[a][b] = v;
         }
+    // r1's upper triangle is fetched behind g, before anything waits for g, and parked in A (free until the loop below): if the
+    // pass turns out to be the identity, r_out = I r1 is this copy, and neither its load nor its layout stands behind the decision
+    // (only where the decision is taken: its barrier is what separates these writes from the loop's use of A)
+    if constexpr (FOLD) {
+        if (check_identity) {
+#pragma unroll
+            for (int a = 0; a < NT; ++a)
+#pragma unroll
+                for (int b = 0; b < NT; ++b) {
+                    const int i = ti + 32 * a, c = tc + 32 * b;
+                    if (i < n && c < n) A[i * ld + c] = c >= i ? r1.at(i, c) : (T)0;
+                }
+        }
+    }
     if (check_identity) {
         dev = wave_max_dpp(dev);
         if (lane == 0) red[wv] = dev;
@@ -86,7 +104,7 @@ __global__ __launch_bounds__(1024) void k_chol_inv(Mat<T> g, Mat<T> r_out, Mat<T
         if (tid == 0 && !(mx <= ident_tol)) atomicOr(flag, 2);
         // The first pass already delivered orthonormal columns to working accuracy (well-conditioned input:
         // max |Q1^T Q1 - I| <= skip_tol): the second pass would change nothing above that level, so R2 = R2^-1 = I
-        // and the 2 n dependent column steps below are skipped.
+        // and the 2 n dependent column steps below are skipped (r_out = I r1 is r1's upper triangle, exactly).
         if (mx <= skip_tol) {
 #pragma unroll
             for (int a = 0; a < NT; ++a)
@@ -95,8 +113,13 @@ __global__ __launch_bounds__(1024) void k_chol_inv(Mat<T> g, Mat<T> r_out, Mat<T
                     const int i = ti + 32 * a, c = tc + 32 * b;
                     if (i < n && c < n) {
                         const T e = (i == c) ? (T)1 : (T)0;
-                        r_out.at(i, c) = e;
+                        if constexpr (!FOLD) r_out.at(i, c) = e;
                         rinv_out.at(i, c) = e;
+                        if constexpr (FOLD) {  // (from A, behind the barrier above: written along r_out's contiguous index whichever that is)
+                            const bool rows_fast = r_out.rs < r_out.cs;
+                            const int io = rows_fast ? tc + 32 * b : i, co = rows_fast ? ti + 32 * a : c;
+                            if (io < n && co < n) r_out.at(io, co) = A[io * ld + co];
+                        }
                     }
                 }
             return;
@@ -181,8 +204,32 @@ __global__ __launch_bounds__(1024) void k_chol_inv(Mat<T> g, Mat<T> r_out, Mat<T
         for (int b = 0; b < NT; ++b) {
             const int i = ti + 32 * a, c = tc + 32 * b;
             if (i < n && c < n) {
-                r_out.at(i, c) = (b >= a && c >= i) ? reg[a][b] : (T)0;
+                if constexpr (!FOLD) r_out.at(i, c) = (b >= a && c >= i) ? reg[a][b] : (T)0;
                 rinv_out.at(i, c) = (b >= a && c >= i) ? xr[a][b] : (T)0;
+            }
+        }
+    if constexpr (!FOLD) return;
+    // r_out = R r1: R goes into A (the last step's readers of colbuf are past the barrier below).  r1 is read where it lies, in
+    // memory, up to n loads per entry: deliberate -- LDS does not hold a second n x n matrix at the n of the flagship workload,
+    // and this path (a second pass that does factor) costs its n dependent steps first: 220 us against about 35 for the product.
+    __syncthreads();
+#pragma unroll
+    for (int a = 0; a < NT; ++a)
+#pragma unroll
+        for (int b = a; b < NT; ++b) {
+            const int i = ti + 32 * a, c = tc + 32 * b;
+            if (i < n && c < n && c >= i) A[i * ld + c] = reg[a][b];
+        }
+    __syncthreads();
+#pragma unroll
+    for (int a = 0; a < NT; ++a)
+#pragma unroll
+        for (int b = 0; b < NT; ++b) {
+            const int i = ti + 32 * a, c = tc + 32 * b;
+            if (i < n && c < n) {
+                T acc = 0;
+                for (int l = i; l <= c; ++l) acc = fma(A[i * ld + l], r1.at(l, c), acc);
+                r_out.at(i, c) = acc;
             }
         }
 }
@@ -190,24 +237,31 @@ __global__ __launch_bounds__(1024) void k_chol_inv(Mat<T> g, Mat<T> r_out, Mat<T
 template <typename T>
 static size_t chol_lds(int64_t n) { return ((size_t)n * (n | 1) + 3 * (size_t)n + 16) * sizeof(T); }
 
-template <typename T, int NT>
-static void chol_inv_launch(rc_context *c, Mat<T> g, Mat<T> r, Mat<T> rinv, bool check_identity, T ident_tol, T skip_tol, int *flag) {
-    auto kern = k_chol_inv<T, NT>;
+template <typename T, int NT, bool FOLD>
+static void chol_inv_launch(rc_context *c, Mat<T> g, Mat<T> r, Mat<T> rinv, Mat<T> r1, bool check_identity, T ident_tol, T skip_tol, int *flag) {
+    auto kern = k_chol_inv<T, NT, FOLD>;
     static bool attr_set[64] = {};
     if (!attr_set[c->device & 63]) {
         RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
         attr_set[c->device & 63] = true;
     }
-    hipLaunchKernelGGL(kern, dim3(1), dim3(1024), chol_lds<T>(g.rows), c->stream, g, r, rinv, check_identity ? 1 : 0, ident_tol, skip_tol, flag);
+    hipLaunchKernelGGL(kern, dim3(1), dim3(1024), chol_lds<T>(g.rows), c->stream, g, r, rinv, r1, check_identity ? 1 : 0, ident_tol, skip_tol, flag);
 }
+// r1 empty: r = R, g = R^T R.  r1 given (n x n upper triangular): r = R r1
 template <typename T>
-static void chol_inv(rc_context *c, Mat<T> g, Mat<T> r, Mat<T> rinv, bool check_identity, T ident_tol, T skip_tol, int *flag) {
+static void chol_inv(rc_context *c, Mat<T> g, Mat<T> r, Mat<T> rinv, Mat<T> r1, bool check_identity, T ident_tol, T skip_tol, int *flag) {
     const int64_t n = g.rows;
     RC_REQUIRE(n <= 224 && chol_lds<T>(n) <= 160 * 1024 - 1024, RC_INVALID_ARGUMENT, "chol_inv: n = %lld does not fit LDS", (long long)n);
     ProfScope ps(c, "op:chol_inv n=%lld", (long long)n);
-    if (n <= 64) chol_inv_launch<T, 2>(c, g, r, rinv, check_identity, ident_tol, skip_tol, flag);
-    else if (n <= 160) chol_inv_launch<T, 5>(c, g, r, rinv, check_identity, ident_tol, skip_tol, flag);
-    else chol_inv_launch<T, 7>(c, g, r, rinv, check_identity, ident_tol, skip_tol, flag);
+#define RC_CI(NT_)                                                                                          \
+    do {                                                                                                    \
+        if (r1.empty()) chol_inv_launch<T, NT_, false>(c, g, r, rinv, r1, check_identity, ident_tol, skip_tol, flag); \
+        else chol_inv_launch<T, NT_, true>(c, g, r, rinv, r1, check_identity, ident_tol, skip_tol, flag);    \
+    } while (0)
+    if (n <= 64) RC_CI(2);
+    else if (n <= 160) RC_CI(5);
+    else if constexpr (sizeof(T) == 4) RC_CI(7);  // (f64: n > 160 does not fit LDS and has failed the check above)
+#undef RC_CI
 }
 
 template <typename T>
@@ -220,6 +274,7 @@ bool tsqr_supported(int64_t m, int64_t n) {
 // for coalesced GEMM epilogues), r2i: n x n, r: n x n (upper, any strides).  *flag (device int) gets bits OR-ed in on failure.
 // Callers fold r2i into whatever small matrix multiplies Q next (Q2 of the small QRCP, U_c / V_c of the small SVD), so the
 // tall matrix is read by two Gram products and written / read by two applications instead of three (four with the sign pass).
+// Five launches: two Gram products, one application and the two k_chol_inv; r = R2 R1 is formed inside the second of those.
 template <typename T>
 void tsqr_cholqr2_factored(rc_context *c, Mat<T> y, Mat<T> q1, Mat<T> r2i, Mat<T> r, int *flag) {
     const int64_t m = y.rows, n = y.cols;
@@ -227,16 +282,14 @@ void tsqr_cholqr2_factored(rc_context *c, Mat<T> y, Mat<T> q1, Mat<T> r2i, Mat<T
     ArenaMark mark(c);
     Mat<T> g = rowmajor(c->alloc<T>((size_t)n * even_ld(n)), n, n, even_ld(n));
     Mat<T> r1 = rowmajor(c->alloc<T>((size_t)n * even_ld(n)), n, n, even_ld(n)), r1i = rowmajor(c->alloc<T>((size_t)n * even_ld(n)), n, n, even_ld(n));
-    Mat<T> r2 = rowmajor(c->alloc<T>((size_t)n * even_ld(n)), n, n, even_ld(n));
     gemm<T>(c, 1, y.t(), y, 0, g);
-    chol_inv<T>(c, g, r1, r1i, false, 0, 0, flag);
+    chol_inv<T>(c, g, r1, r1i, Mat<T>(), false, 0, 0, flag);
     gemm<T>(c, 1, y, r1i, 0, q1);
     gemm<T>(c, 1, q1.t(), q1, 0, g);
     // after one pass ||Q1^T Q1 - I|| ~ cond(Y)^2 eps; the second pass is only accurate while that is << 1
     static const int skip_ok = env_int("RC_CHOLQR_SKIP", 1);
     const T skip_tol = skip_ok ? (sizeof(T) == 8 ? (T)2.5e-14 : (T)1e-6) : (T)-1;
-    chol_inv<T>(c, g, r2, r2i, true, (T)1e-2, skip_tol, flag);
-    gemm<T>(c, 1, r2, r1, 0, r);
+    chol_inv<T>(c, g, r, r2i, r1, true, (T)1e-2, skip_tol, flag);  // r = R2 r1
 }
 
 // Y = Q R with Q formed: q m x n (any strides)
@@ -383,8 +436,9 @@ __device__ __forceinline__ void qrcp_small_reflect_flat(T (&x)[NE], const T *vco
 }
 
 // Column cq of Q2 by one LPP-lane group: apply H_min(cq,kmax-1) ... H_0 to e_cq (A, tau, jp: the factored LDS image, read-only)
+// (xkeep, FLAT only: the caller's registers get the column as well, rows ll + LPP e)
 template <typename T, int NE, int LPP, bool FLAT = false>
-__device__ __forceinline__ void qrcp_small_q2_column(const T *A, int ld, int n, int kmax, const T *tau, const int *jp, int cq, int ll, Mat<T> q2) {
+__device__ __forceinline__ void qrcp_small_q2_column(const T *A, int ld, int n, int kmax, const T *tau, const int *jp, int cq, int ll, Mat<T> q2, T *xkeep = nullptr) {
     T x[NE];
 #pragma unroll
     for (int e = 0; e < NE; ++e) x[e] = (ll + LPP * e == cq) ? (T)1 : (T)0;
@@ -421,6 +475,7 @@ __device__ __forceinline__ void qrcp_small_q2_column(const T *A, int ld, int n, 
     for (int e = 0; e < NE; ++e) {
         int i = ll + LPP * e;
         if (i < n) q2.at(i, cq) = x[e];
+        if constexpr (FLAT) xkeep[e] = x[e];
     }
 }
 
@@ -531,8 +586,11 @@ __global__ __launch_bounds__(NTHR) void k_qrcp_small(Mat<T> rin, int kmax, int p
 // group per column with the steps of the in-kernel formation in its order (qrcp_small_q2_column, loads issued together).
 // Columns are independent, so a CU holds cpw / 8 waves of them instead of sixteen and the phase is bound by the longest
 // column's dependent chain.
+// w not empty: the workgroup goes on to its own columns of  w = r2i q2  and  top = q1top w  (small_product_w_top, rc_device.hpp):
+// the columns of Q2 are in registers and the LDS image is dead by then, so they take its place (cpw <= kQ2FoldCols then).
+constexpr int kQ2FoldCols = 32;  // 2 * 32 columns of n | 1 words fit where the n columns of the image (n > 64) stood
 template <typename T, int NE>
-__global__ __launch_bounds__(1024) void k_qrcp_small_q2(const T *img, int n, int kmax, Mat<T> q2, int cpw) {
+__global__ __launch_bounds__(1024) void k_qrcp_small_q2(const T *img, int n, int kmax, Mat<T> q2, int cpw, Mat<T> r2i, Mat<T> q1top, Mat<T> w, Mat<T> top) {
     constexpr int LPP = 8;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int ld = n | 1;
@@ -555,13 +613,67 @@ __global__ __launch_bounds__(1024) void k_qrcp_small_q2(const T *img, int n, int
     __syncthreads();
     const int ll = tid % LPP, grp = tid / LPP;
     const int cq = (int)blockIdx.x * cpw + grp;
-    if (grp < cpw && cq < (int)q2.cols) qrcp_small_q2_column<T, NE, LPP, true>(A, ld, n, kmax, tau, jp, cq, ll, q2);
+    const bool mine = grp < cpw && cq < (int)q2.cols;
+    T x[NE];
+    if (mine) qrcp_small_q2_column<T, NE, LPP, true>(A, ld, n, kmax, tau, jp, cq, ll, q2, x);
+    if (w.empty()) return;
+    const int c0 = (int)blockIdx.x * cpw, nc = min(cpw, (int)q2.cols - c0);
+    T *Qs = A, *Ws = A + kQ2FoldCols * ld;
+    __syncthreads();  // every group has read the image for the last time
+    if (mine) {
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            const int i = ll + LPP * e;
+            if (i < n) Qs[grp * ld + i] = x[e];
+        }
+    }
+    __syncthreads();
+    small_product_w_top<T, NE>(r2i, q1top, w, top, c0, nc, Qs, Ws, ld, tid, 1024);
 }
 
+// The same columns where Q2 was formed inside k_qrcp_small (q2 is read from memory), and out = r2i x alone (top empty) for
+// svd_finish: kSmallProductCols columns per workgroup.
+template <typename T, int NT8>
+__global__ __launch_bounds__(256) void k_small_products(Mat<T> r2i, Mat<T> x, Mat<T> q1top, Mat<T> w, Mat<T> top) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const int n = (int)r2i.rows, ldx = n | 1;
+    T *Xs = reinterpret_cast<T *>(smem_raw), *Ws = Xs + kSmallProductCols * ldx;
+    const int tid = threadIdx.x;
+    const int c0 = (int)blockIdx.x * kSmallProductCols, nc = min(kSmallProductCols, (int)x.cols - c0);
+    if (top.empty()) { small_product_tri<T, NT8>(r2i, x, w, c0, nc, Xs, tid, 256); return; }
+    small_product_load_cols<T>(x, c0, nc, Xs, ldx, tid, 256);
+    __syncthreads();
+    small_product_w_top<T, NT8>(r2i, q1top, w, top, c0, nc, Xs, Ws, ldx, tid, 256);
+}
 template <typename T>
-void qrcp_small(rc_context *c, Mat<T> rin, int64_t kmax, bool pivot, int64_t *jpvt, Mat<T> rout, Mat<T> q2) {
+static void small_products_launch(rc_context *c, Mat<T> r2i, Mat<T> x, Mat<T> q1top, Mat<T> w, Mat<T> top) {
+    const int64_t n = r2i.rows;
+    RC_REQUIRE(r2i.cols == n && x.rows == n && w.rows == n && w.cols == x.cols && (top.empty() || (q1top.cols == n && top.rows == q1top.rows && top.cols == x.cols)),
+               RC_INVALID_ARGUMENT, "small products: shape mismatch");
+    if (x.cols == 0) return;
+    const size_t lds = 2 * (size_t)kSmallProductCols * (n | 1) * sizeof(T);
+    RC_REQUIRE(n <= 8 * 26 && lds <= 64 * 1024, RC_INVALID_ARGUMENT, "small products: n = %lld is too large", (long long)n);
+    const dim3 grid((unsigned)cdiv(x.cols, kSmallProductCols));
+    if (n <= 8 * 8) hipLaunchKernelGGL((k_small_products<T, 8>), grid, dim3(256), lds, c->stream, r2i, x, q1top, w, top);
+    else if (n <= 8 * 18) hipLaunchKernelGGL((k_small_products<T, 18>), grid, dim3(256), lds, c->stream, r2i, x, q1top, w, top);
+    else hipLaunchKernelGGL((k_small_products<T, 26>), grid, dim3(256), lds, c->stream, r2i, x, q1top, w, top);
+}
+// out = r2i x: r2i n x n upper triangular, x and out n x nc (any strides)
+template <typename T>
+void small_tri_product(rc_context *c, Mat<T> r2i, Mat<T> x, Mat<T> out) {
+    ProfScope ps(c, "op:small_tri_product n=%lld cols=%lld", (long long)r2i.rows, (long long)x.cols);
+    small_products_launch<T>(c, r2i, x, Mat<T>(), out, Mat<T>());
+}
+
+// w not empty (then q2 is not either): w = r2i q2 (n x q2.cols) and top = q1top w (q1top: rows x n) are formed as well, by the
+// workgroups that form Q2 where it is spread, by one more launch of the same body where it is not.
+template <typename T>
+void qrcp_small(rc_context *c, Mat<T> rin, int64_t kmax, bool pivot, int64_t *jpvt, Mat<T> rout, Mat<T> q2, Mat<T> r2i, Mat<T> q1top, Mat<T> w, Mat<T> top) {
     const int64_t n = rin.rows;
     RC_REQUIRE(rin.rows == rin.cols, RC_INVALID_ARGUMENT, "qrcp_small: square input required");
+    RC_REQUIRE(w.empty() || (!q2.empty() && !top.empty() && r2i.rows == n && r2i.cols == n && w.rows == n && w.cols == q2.cols && q1top.cols == n &&
+                             top.rows == q1top.rows && top.cols == q2.cols),
+               RC_INVALID_ARGUMENT, "qrcp_small: shape mismatch of the folded products");
     const size_t lds = ((size_t)n * (n | 1) + 3 * (size_t)n) * sizeof(T) + (size_t)n * sizeof(int) + 64;
     RC_REQUIRE(lds <= 160 * 1024 - 1024 && n <= 208, RC_INVALID_ARGUMENT, "qrcp_small: n = %lld does not fit LDS", (long long)n);
     ProfScope ps(c, "op:qrcp_small n=%lld k=%lld", (long long)n, (long long)kmax);
@@ -593,9 +705,10 @@ void qrcp_small(rc_context *c, Mat<T> rin, int64_t kmax, bool pivot, int64_t *jp
         }
         hipLaunchKernelGGL(kf, dim3(1), dim3(1024), lds, c->stream, rin, (int)kmax, pivot ? 1 : 0, jpvt, rout, q2, img);
         // whole waves of columns per workgroup (8 columns a wave), at most the 128 column groups of a workgroup
-        const int cpw = (int)std::min<int64_t>(cdiv(cdiv(q2.cols, q2_wgs), 8) * 8, 128);
+        // (with the products behind the columns at most kQ2FoldCols: both sets of columns stand in LDS where the image was)
+        const int cpw = (int)std::min<int64_t>(cdiv(cdiv(q2.cols, q2_wgs), 8) * 8, w.empty() ? 128 : kQ2FoldCols);
         ProfScope pq(c, "op:qrcp_small_q2 n=%lld cols=%lld wgs=%d", (long long)n, (long long)q2.cols, (int)cdiv(q2.cols, cpw));
-        hipLaunchKernelGGL(kq, dim3((unsigned)cdiv(q2.cols, cpw)), dim3(1024), lds, c->stream, (const T *)img, (int)n, (int)kmax, q2, cpw);
+        hipLaunchKernelGGL(kq, dim3((unsigned)cdiv(q2.cols, cpw)), dim3(1024), lds, c->stream, (const T *)img, (int)n, (int)kmax, q2, cpw, r2i, q1top, w, top);
         return;
     }
     if (n <= 64) RC_QS(8, 512);
@@ -603,6 +716,7 @@ void qrcp_small(rc_context *c, Mat<T> rin, int64_t kmax, bool pivot, int64_t *jp
     else if (n <= 144) RC_QS(18, 512);
     else RC_QS(26, 512);
 #undef RC_QS
+    if (!w.empty()) small_products_launch<T>(c, r2i, q2, q1top, w, top);
 }
 
 // ---------------------------------------------------------------------------
@@ -706,9 +820,9 @@ void qrcp_tall_fast(rc_context *c, Mat<T> y, int64_t k, bool pivot, Mat<T> q, Ma
     else tsqr_cholqr2<T>(c, y, q1, r1, flag);
     Mat<T> q2 = colmajor(c->alloc<T>((size_t)even_ld(n) * k), n, k, even_ld(n));
     Mat<T> rr = r.empty() ? rowmajor(c->alloc<T>((size_t)k * even_ld(n)), k, n, even_ld(n)) : r;
-    qrcp_small<T>(c, r1, k, pivot, ind, rr, q2);
     Mat<T> qq = q.empty() ? rowmajor(c->alloc<T>((size_t)m * even_ld(k)), m, k, even_ld(k)) : q;
     if (!fold) {
+        qrcp_small<T>(c, r1, k, pivot, ind, rr, q2, Mat<T>(), Mat<T>(), Mat<T>(), Mat<T>());
         gemm<T>(c, 1, q1, q2, 0, qq);
         householder_sign_fix<T>(c, qq, rr);
         return;
@@ -716,8 +830,7 @@ void qrcp_tall_fast(rc_context *c, Mat<T> y, int64_t k, bool pivot, Mat<T> q, Ma
     Mat<T> w = colmajor(c->alloc<T>((size_t)even_ld(n) * k), n, k, even_ld(n));
     Mat<T> top = colmajor(c->alloc<T>((size_t)even_ld(k) * k), k, k, even_ld(k));
     T *d = c->alloc<T>((size_t)k);
-    gemm<T>(c, 1, r2i, q2, 0, w);
-    gemm<T>(c, 1, q1.sub(0, k, 0, n), w, 0, top);
+    qrcp_small<T>(c, r1, k, pivot, ind, rr, q2, r2i, q1.sub(0, k, 0, n), w, top);  // ... and w = r2i q2, top = q1[:k, :] w
     householder_signs<T>(c, top, d);
     scale_cols_rows<T>(c, w, rr, d);
     gemm<T>(c, 1, q1, w, 0, qq);
@@ -727,7 +840,8 @@ void qrcp_tall_fast(rc_context *c, Mat<T> y, int64_t k, bool pivot, Mat<T> q, Ma
     template bool tsqr_supported<T>(int64_t, int64_t);                                                           \
     template void tsqr_cholqr2<T>(rc_context *, Mat<T>, Mat<T>, Mat<T>, int *);                                  \
     template void tsqr_cholqr2_factored<T>(rc_context *, Mat<T>, Mat<T>, Mat<T>, Mat<T>, int *);                 \
-    template void qrcp_small<T>(rc_context *, Mat<T>, int64_t, bool, int64_t *, Mat<T>, Mat<T>);                 \
+    template void qrcp_small<T>(rc_context *, Mat<T>, int64_t, bool, int64_t *, Mat<T>, Mat<T>, Mat<T>, Mat<T>, Mat<T>, Mat<T>); \
+    template void small_tri_product<T>(rc_context *, Mat<T>, Mat<T>, Mat<T>);                                   \
     template void householder_sign_fix<T>(rc_context *, Mat<T>, Mat<T>);                                         \
     template void qrcp_tall_fast<T>(rc_context *, Mat<T>, int64_t, bool, Mat<T>, Mat<T>, int64_t *, int *);
 RC_INST(double)

@@ -396,16 +396,16 @@ void lapack_orgqr(rc_context *c, Mat<T> a, const T *tau, int64_t k, Mat<T> q) {
 
 // The tail of svd_core: from the SVD of the core (uc, s, vc) and the orthogonal factor of the tall QR -- qw, or q1 r2i when it
 // stayed factored -- to the factors of the matrix itself.  u_in_place (transposed only): the caller had the SVD of the core write
-// uc into u's storage, so u = uc needs no copy.
+// uc into u's storage, so u = uc needs no copy.  small (factored only): r2i vc (transposed) or r2i uc where a launch before this
+// has formed it already (rsvd_id_tails); empty: formed here, by the same body.
 template <typename T>
 void svd_finish(rc_context *c, bool transposed, bool factored, Mat<T> qw, Mat<T> q1, Mat<T> r2i, Mat<T> uc, Mat<T> vc, const T *s, Mat<T> u, Mat<T> vt,
-                bool u_in_place = false) {
+                bool u_in_place = false, Mat<T> small = Mat<T>()) {
     const int64_t r = uc.rows;
     complete_left_basis(c, uc, s);  // (?gesdd: U stays orthonormal when singular values are zero; no-op otherwise)
-    Mat<T> small;
-    if (factored) {
+    if (factored && small.empty()) {
         small = tmp_colmajor<T>(c, r, r);
-        gemm<T>(c, 1, r2i, transposed ? vc : uc, 0, small);
+        small_tri_product<T>(c, r2i, transposed ? vc : uc, small);
     }
     if (!transposed) {
         // a = Q_w R = (Q_w Uc) S Vc^T
@@ -668,12 +668,13 @@ bool rsvd_id_consumers_fused(rc_context *c, Mat<T> range, Mat<T> b, const rc_rsv
     // (ub: the Jacobi writes the left vectors of the core where U = range ub reads them -- no copy in svd_finish)
     Mat<T> ub = tmp_colmajor<T>(c, k, k), vc = tmp_colmajor<T>(c, k, k);
     Mat<T> qb = tmp_colmajor<T>(c, k, k);
+    Mat<T> small = tmp_colmajor<T>(c, k, k);  // r2i vc for svd_finish
     Mat<T> r = o.qr_r.data ? from_c<T>(o.qr_r) : tmp_rowmajor<T>(c, k, n);
     int64_t *ind = o.qr_ind ? o.qr_ind : c->alloc<int64_t>((size_t)n);
     T *tau = c->alloc<T>((size_t)k);
     Mat<T> wf = tmp_colmajor<T>(c, k, n);
     T *s = static_cast<T *>(o.s);
-    bool qr_done;
+    bool qr_done, small_done = false;
     {
         ProfScope ps(c, "stage:qrcp of B | svd of the core");
         qr_done = run_certified(c, [&](int *flag) { geqp3_wide_coop_jacobi<T>(c, b, wf, k, ind, tau, flag, core, ub, s, vc); });
@@ -688,7 +689,9 @@ bool rsvd_id_consumers_fused(rc_context *c, Mat<T> range, Mat<T> b, const rc_rsv
             if (want_cz)
                 RC_REQUIRE(cm.rows == m && cm.cols == k && z.rows == k && z.cols == n, RC_INVALID_ARGUMENT, "column_id: c %lld x %lld, z %lld x %lld",
                            (long long)cm.rows, (long long)cm.cols, (long long)z.rows, (long long)z.cols);
-            rsvd_id_tails(c, wf, ind, tau, qb, r, want_cz ? z : Mat<T>());
+            // (and r2i vc of the SVD branch: both operands are complete, and the launch is as long as its Z role either way)
+            rsvd_id_tails(c, wf, ind, tau, qb, r, want_cz ? z : Mat<T>(), r2i, vc, small);
+            small_done = true;
         } else if (qr_done) {
             extract_r(c, wf, ind, r);
             form_q(c, wf, ind, tau, k, qb);
@@ -704,7 +707,7 @@ bool rsvd_id_consumers_fused(rc_context *c, Mat<T> range, Mat<T> b, const rc_rsv
     }
     {
         ProfScope ps(c, "stage:svd of B + U=Q Ub");
-        svd_finish(c, /*transposed=*/true, /*factored=*/true, Mat<T>(), q1, r2i, ub, vc, s, ub, from_c<T>(o.vt), /*u_in_place=*/true);
+        svd_finish(c, /*transposed=*/true, /*factored=*/true, Mat<T>(), q1, r2i, ub, vc, s, ub, from_c<T>(o.vt), /*u_in_place=*/true, small_done ? small : Mat<T>());
         gemm<T>(c, 1, range, ub, 0, from_c<T>(o.u));
     }
     return true;

@@ -368,7 +368,8 @@ void coop_gate_launch(rc_context *c, unsigned need, unsigned *sync, unsigned lon
 // r(i, p) = (i <= p) ? w(i, jpvt[p]) : 0  for i < r.rows
 template <typename T> void extract_r(rc_context *c, Mat<T> w, const int64_t *jpvt, Mat<T> r);
 // R, Q_b and Z (may be empty) from the factored k x n wf of the fused QRCP/Jacobi launch in one launch (kernels_qr.hip)
-template <typename T> void rsvd_id_tails(rc_context *c, Mat<T> wf, const int64_t *jpvt, const T *tau, Mat<T> qb, Mat<T> r, Mat<T> z);
+// small not empty: small = r2i x (k x k, small_tri_product's bits) by a fourth role of the launch
+template <typename T> void rsvd_id_tails(rc_context *c, Mat<T> wf, const int64_t *jpvt, const T *tau, Mat<T> qb, Mat<T> r, Mat<T> z, Mat<T> r2i, Mat<T> x, Mat<T> small);
 // qw (m x kq column-major) = H_0 ... H_{k-1} [I ; 0], reflector j stored in column jpvt[j] of w
 template <typename T> void form_q(rc_context *c, Mat<T> w, const int64_t *jpvt, const T *tau, int64_t k, Mat<T> qw);
 // solve T X = B in place; t: k x k upper triangular view (any strides), b: k x nrhs view
@@ -378,7 +379,10 @@ template <typename T> bool tsqr_supported(int64_t m, int64_t n);
 int tsqr_fold();  // RC_TSQR_FOLD: Q of the CholeskyQR2 stays factored (Q1 R2^-1); one read (kernels_tsqr.hip) for its callers there and in rc_api.hip, which must agree
 template <typename T> void tsqr_cholqr2(rc_context *c, Mat<T> y, Mat<T> q, Mat<T> r, int *flag);
 template <typename T> void tsqr_cholqr2_factored(rc_context *c, Mat<T> y, Mat<T> q1, Mat<T> r2i, Mat<T> r, int *flag);
-template <typename T> void qrcp_small(rc_context *c, Mat<T> rin, int64_t kmax, bool pivot, int64_t *jpvt, Mat<T> rout, Mat<T> q2);
+// (r2i, q1top, w, top: empty, or w = r2i q2 and top = q1top w are formed with Q2)
+template <typename T> void qrcp_small(rc_context *c, Mat<T> rin, int64_t kmax, bool pivot, int64_t *jpvt, Mat<T> rout, Mat<T> q2, Mat<T> r2i, Mat<T> q1top, Mat<T> w, Mat<T> top);
+// out = r2i x with r2i upper triangular, in the one summation order of small_product_cols (rc_device.hpp)
+template <typename T> void small_tri_product(rc_context *c, Mat<T> r2i, Mat<T> x, Mat<T> out);
 template <typename T> void householder_sign_fix(rc_context *c, Mat<T> q, Mat<T> r);
 template <typename T> void qrcp_tall_fast(rc_context *c, Mat<T> y, int64_t k, bool pivot, Mat<T> q, Mat<T> r, int64_t *ind, int *flag);
 // one-sided Jacobi SVD of the square column-major n x n matrix g (destroyed):

@@ -255,4 +255,81 @@ __device__ __forceinline__ bool jacobi_rotation_was_large(T app, T aqq, double a
 // Sweep budget of the LDS-resident Jacobi; the fused launch of k_jacobi_lds hands the sweep count over in the 8-bit payload of a tagged word.
 constexpr int kMaxSweeps = 30;
 
+// ---- the chain's small products, inside the kernels next to them ("The small products folded") ----
+// out(i, c0 + cc) = sum_l a(i, l) X[cc * ldx + l], i < rows, cc < nc, l < n: the nc columns of the right factor stand in LDS, one
+// 8-lane group forms one row of eight of them.  Lane ll takes l = ll + 8 t with t ascending (UPPER: a is upper triangular and no
+// term left of the diagonal is taken), then the eight partial sums go through group_sum_dpp<8>.
+// That is ONE order per entry: it depends on neither the workgroup size, nor the columns a workgroup holds, nor the launch the
+// body runs in, so two paths that call it on the same operands give the same bits.  xout (LDS, may be null) gets the result as
+// well, xout[cc * ldx + i].  M: Mat<T>.  Whole 8-lane groups must enter.  NT8 >= cdiv(n, 8): a lane's entries of the row are
+// loaded together, one round trip to memory per item.  Every fma reads its operand of the right factor from LDS, so the CU's
+// one LDS pipe is the bound of the body (profiles/r08_small_products_ab.txt).
+template <typename T, bool UPPER, int NT8, typename M>
+__device__ __forceinline__ void small_product_cols(M a, int rows, int n, const T *X, int ldx, int nc, M out, int c0, T *xout, int tid, int nthr) {
+    constexpr int LPP = 8, CW = 8;
+    const int ll = tid % LPP, ngrp = nthr / LPP;
+    const int ncg = (nc + CW - 1) / CW;
+    for (int item = tid / LPP; item < rows * ncg; item += ngrp) {
+        const int i = item % rows, cb = (item / rows) * CW;
+        const T *xc[CW];
+#pragma unroll
+        for (int u = 0; u < CW; ++u) xc[u] = X + (cb + u < nc ? cb + u : nc - 1) * ldx;
+        T acc[CW], av[NT8];
+#pragma unroll
+        for (int u = 0; u < CW; ++u) acc[u] = 0;
+        const T *arow = &a.at(i, 0);
+#pragma unroll
+        for (int t = 0; t < NT8; ++t) {
+            const int l = ll + LPP * t;
+            av[t] = (l < n && (!UPPER || l >= i)) ? arow[l * a.cs] : (T)0;
+        }
+#pragma unroll
+        for (int t = 0; t < NT8; ++t) {
+            const int l = ll + LPP * t;
+            if (l < n && (!UPPER || l >= i)) {  // (no term where there is none: LDS past a column's end is not read)
+#pragma unroll
+                for (int u = 0; u < CW; ++u) acc[u] = fma(av[t], xc[u][l], acc[u]);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < CW; ++u) acc[u] = group_sum_dpp<LPP>(acc[u]);
+        if (ll == 0) {
+#pragma unroll
+            for (int u = 0; u < CW; ++u)
+                if (cb + u < nc) {
+                    out.at(i, c0 + cb + u) = acc[u];
+                    if (xout) xout[(cb + u) * ldx + i] = acc[u];
+                }
+        }
+    }
+}
+// columns [c0, c0 + nc) of x to LDS, X[cc * ldx + i]
+template <typename T, typename M>
+__device__ __forceinline__ void small_product_load_cols(M x, int c0, int nc, T *X, int ldx, int tid, int nthr) {
+    const int rows = (int)x.rows;
+    for (int e = tid; e < nc * rows; e += nthr) {
+        const int cc = e / rows, i = e - cc * rows;
+        X[cc * ldx + i] = x.at(i, c0 + cc);
+    }
+}
+// Columns [c0, c0 + nc) of  w = r2i q2  (r2i: n x n upper triangular, the columns of q2 in LDS at Qs) and of  top = q1top w
+// (q1top: k x n), for qrcp_tall_fast.  Ws: LDS for the same columns of w.  Called by every thread of the workgroup.
+template <typename T, int NT8, typename M>
+__device__ __forceinline__ void small_product_w_top(M r2i, M q1top, M w, M top, int c0, int nc, const T *Qs, T *Ws, int ldx, int tid, int nthr) {
+    const int n = (int)r2i.rows;
+    small_product_cols<T, true, NT8>(r2i, n, n, Qs, ldx, nc, w, c0, Ws, tid, nthr);
+    __syncthreads();
+    small_product_cols<T, false, NT8>(q1top, (int)q1top.rows, n, Ws, ldx, nc, top, c0, (T *)nullptr, tid, nthr);
+}
+// Columns [c0, c0 + nc) of  out = r2i x  (x read from memory), for svd_finish.  X: LDS, nc * (n | 1) words.  Called by every
+// thread of the workgroup.
+template <typename T, int NT8, typename M>
+__device__ __forceinline__ void small_product_tri(M r2i, M x, M out, int c0, int nc, T *X, int tid, int nthr) {
+    const int n = (int)r2i.rows, ldx = n | 1;
+    small_product_load_cols<T>(x, c0, nc, X, ldx, tid, nthr);
+    __syncthreads();
+    small_product_cols<T, true, NT8>(r2i, n, n, X, ldx, nc, out, c0, (T *)nullptr, tid, nthr);
+}
+constexpr int kSmallProductCols = 8;  // columns per workgroup where the body has a launch, or a role of one, to itself
+
 }  // namespace rc
