@@ -149,7 +149,9 @@ rc_status rc_graph_destroy(rc_context *ctx, void *graph_exec);
  * columns of a blocked panel are updated reflector by reflector and which through the block update: last bits of R12 / Z),
  * RC_GEMM_LANES_TARGET, RC_GEMM_SLOTS_TARGET, RC_GEMM_SMALL_TARGET (split-K counts).
  * Schedules that only change WHEN or WHERE the same arithmetic is issued -- RC_WQ_STAGES, RC_QRCP_OPTIMISTIC, RC_BATCH_OPTIMISTIC,
- * RC_QRCP_KEEP_DIRECT, RC_ID_FUSED -- give identical bits (tested for the staged k_wq_coop and the optimistic blocked QRCP). */
+ * RC_QRCP_KEEP_DIRECT, RC_ID_FUSED -- give identical bits (tested for the staged k_wq_coop and the optimistic blocked QRCP).
+ * RC_GEMM_SPREAD changes scheduling only: which workgroup computes an entry of the Gram and shallow products of the tall-skinny
+ * chain, never its K slabs or the order of its sum (tests/test_gpu_spread_switch.py compares the two settings bit for bit). */
 /* RC_OPT_POWER_ITERATION_FIXED (default 0): rc_sample_range_power_iteration_* performs it_count power steps
  * (Y <- A orth(A^H orth(Y))) as the reference documents; 0 reproduces the reference's behaviour, where a shadowed
  * loop variable leaves exactly one step (src/random_sampling.rs:145-153). */

@@ -479,13 +479,10 @@ static int wide_target(const rc_context *c, int many, int lone) {
     return n >= 8 ? many : n >= 2 ? target_slots : lone;
 }
 
-// The tail shared by launch_cfg and launch_f64q: K split until `target` workgroups exist (each at least min_ksteps K tiles deep;
-// 0 = 16 for a product of >= 32 output tiles, 4 otherwise), the slabs, the product on the tiles x splits grid -- `kern`, unless
-// `pipe` launches it on the pipelined main loop of kernels_gemm_pipe.hip -- and the deterministic slab reduction
-template <typename T, int BK, class Pipe>
-static void launch_split(rc_context *c, GemmArgs<T> g, int target, int min_ksteps, void (*kern)(GemmArgs<T>), int nt, size_t lds,
-                         bool (&attr_set)[64], const char *name, Pipe &&pipe) {
-    const int64_t tiles = (int64_t)g.tiles_m * g.tiles_n;
+// The K slabs of a product of `tiles` output tiles: K split until `target` workgroups exist (each at least min_ksteps K tiles deep;
+// 0 = 16 for a product of >= 32 output tiles, 4 otherwise).  Fills g.kchunk and g.splits.
+template <typename T, int BK>
+static void plan_split(GemmArgs<T> &g, int64_t tiles, int target, int min_ksteps) {
     int splits = 1;
     const int64_t ksteps = cdiv(g.K, BK);
     const int min_ks = min_ksteps > 0 ? min_ksteps : (tiles >= 32 ? 16 : 4);
@@ -494,6 +491,15 @@ static void launch_split(rc_context *c, GemmArgs<T> g, int target, int min_kstep
     splits = (int)cdiv(g.K, g.kchunk);
     if (splits < 1) splits = 1;
     g.splits = splits;
+}
+
+// The tail shared by launch_cfg and launch_f64q for a planned product (tiles_m, tiles_n, kchunk, splits filled in): the slabs, the
+// product on the tiles x splits grid -- `kern`, unless `pipe` launches it on the pipelined main loop of kernels_gemm_pipe.hip --
+// and the deterministic slab reduction
+template <typename T, class Pipe>
+static void launch_split(rc_context *c, GemmArgs<T> g, void (*kern)(GemmArgs<T>), int nt, size_t lds, bool (&attr_set)[64], const char *name, Pipe &&pipe) {
+    const int64_t tiles = (int64_t)g.tiles_m * g.tiles_n;
+    const int splits = g.splits;
     ArenaMark mark(c);
     if (splits > 1) g.partial = c->alloc<T>((size_t)splits * g.M * g.N);
     if (lds > 48 * 1024 && !attr_set[c->device & 63]) {
@@ -535,11 +541,13 @@ static void launch_cfg(rc_context *c, GemmArgs<T> g, int target_wgs = 0, int min
     static bool attr_set[64] = {};
     char nm[128];
     snprintf(nm, sizeof(nm), "k_gemm_mfma<%s,%d,%d,%d,%d,%d,%d,%d,%d,%d>", sizeof(T) == 8 ? "double" : "float", ALAY, BLAY, BM, BN, BK, WM, WN, VEC, NBUF);
-    launch_split<T, BK>(c, g, target, min_ksteps, k_gemm_mfma<T, ALAY, BLAY, BM, BN, BK, WM, WN, VEC, NBUF>, NT, lds, attr_set, nm,
-                        [](const GemmArgs<T> &) { return false; });
+    plan_split<T, BK>(g, tiles, target, min_ksteps);
+    launch_split<T>(c, g, k_gemm_mfma<T, ALAY, BLAY, BM, BN, BK, WM, WN, VEC, NBUF>, NT, lds, attr_set, nm, [](const GemmArgs<T> &) { return false; });
 }
 
-template <int ALAY, int BLAY, int BM, int BN, int BK, int WM, int WN, int VEC, int ORIENT, int GLDS = 0>
+// PBM x PBN: the tile the K slabs are planned for.  It is the launched tile, except in the spread forms of gemm_chain, which cut the
+// planned tile into smaller workgroups and keep its slabs.
+template <int ALAY, int BLAY, int BM, int BN, int BK, int WM, int WN, int VEC, int ORIENT, int GLDS = 0, int PBM = BM, int PBN = BN>
 static void launch_f64q(rc_context *c, GemmArgs<double> g, int target_wgs = 0, int min_ksteps = 0) {
     typedef double T;
     constexpr int NT = WM * WN * 64;
@@ -547,9 +555,10 @@ static void launch_f64q(rc_context *c, GemmArgs<double> g, int target_wgs = 0, i
     typedef TileStager<T, BLAY == 1 ? 0 : 1, BN, BK, NT, VEC> StB;
     constexpr size_t lds = 2 * (size_t)(StA::ELEMS + StB::ELEMS) * sizeof(T);
     static_assert(lds <= 160 * 1024, "tile does not fit LDS");
+    static_assert(PBM % BM == 0 && PBN % BN == 0, "the launched tiles cut the planned one");
     g.tiles_m = (int)cdiv(g.M, BM);
     g.tiles_n = (int)cdiv(g.N, BN);
-    const int64_t tiles = (int64_t)g.tiles_m * g.tiles_n;
+    const int64_t tiles = cdiv(g.M, PBM) * cdiv(g.N, PBN);
     // the split targets of launch_cfg, except that target_wgs replaces only the one of a lone wide product
     static const int target_big = env_int("RC_GEMM_TARGET_WGS", 256), target_small = env_int("RC_GEMM_SMALL_TARGET", 32);
     // (RC_GEMM_LANES_TARGET=64: ONE K split in flight -- CUs come free twice as often, which shortens the cooperative kernels' wait for
@@ -562,8 +571,9 @@ static void launch_f64q(rc_context *c, GemmArgs<double> g, int target_wgs = 0, i
     char nm[128];
     snprintf(nm, sizeof(nm), "k_gemm_f64q<%d,%d,%d,%d,%d,%d,%d,%d,%d,%d>", ALAY, BLAY, BM, BN, BK, WM, WN, VEC, ORIENT, GLDS);
     // the software-pipelined main loop (kernels_gemm_pipe.hip) where it has an instantiation for this tile shape
-    launch_split<T, BK>(c, g, target, min_ksteps, k_gemm_f64q<ALAY, BLAY, BM, BN, BK, WM, WN, VEC, ORIENT, GLDS>, NT, lds, attr_set, nm,
-                        [&](const GemmArgs<T> &gs) { return gemm_f64p_launch(c, gs, ALAY, BLAY, BM, BN, BK, WM, WN, ORIENT, VEC == 2); });
+    plan_split<T, BK>(g, tiles, target, min_ksteps);
+    launch_split<T>(c, g, k_gemm_f64q<ALAY, BLAY, BM, BN, BK, WM, WN, VEC, ORIENT, GLDS>, NT, lds, attr_set, nm,
+                    [&](const GemmArgs<T> &gs) { return gemm_f64p_launch(c, gs, ALAY, BLAY, BM, BN, BK, WM, WN, ORIENT, VEC == 2); });
 }
 
 // f64 shapes on the 4x4x4 MFMA
@@ -606,9 +616,36 @@ static void launch_shape_f64q(rc_context *c, const GemmArgs<double> &g) {
     else launch_f64q<ALAY, BLAY, 128, 128, 16, 2, 2, VEC, 0>(c, g);
 }
 
+// The spread forms of gemm_chain: the Gram products and the shallow products of a compression's chain on more and smaller
+// workgroups, with smaller wave tiles.  Both keep the K slabs of the tile launch_shape_f64q launches (PBM x PBN of launch_f64q),
+// and an entry's sum does not depend on the tile it sits in: it is the same chain of MFMAs, one per four k ascending from its
+// slab's first k, and only the wave that computes it changes.  Tiles by measurement (profiles/r09_spread_products_ab.txt).
+// Returns false where launch_shape_f64q would take another arm, or the pipelined loop would refuse the Gram product.
+template <int ALAY, int BLAY, int VEC>
+static bool launch_spread_f64q(rc_context *c, const GemmArgs<double> &g) {
+    if (g.M <= 144 && g.N <= 144 && g.M > 80 && g.N > 80) {
+        // 9 tiles of 48 x 48 on four waves of 12 x 48 each (one 144 x 144 tile on nine waves of 48 x 48): 24 / 27 KB of LDS
+        if constexpr (VEC == 2 && ALAY != BLAY) {
+            if (!gemm_f64p_accepts(g, 144, 144, 16)) return false;
+            launch_f64q<ALAY, BLAY, 48, 48, 16, 4, 1, VEC, 0, 0, 144, 144>(c, g);
+            return true;
+        }
+        return false;
+    }
+    if (g.N <= 144 || g.M <= 80) return false;
+    if (g.M <= 136 && g.K <= 160 && g.N >= 2048) {
+        // 128 x 32 tiles on eight waves of 32 x 16 (128 x 128 on eight of 128 x 16); 136 x 64 on eight of 68 x 16 (136 x 128 on eight of 68 x 32)
+        if (g.M <= 128) launch_f64q<ALAY, BLAY, 128, 32, 16, 4, 2, VEC, 1, 0, 128, 128>(c, g);
+        else launch_f64q<ALAY, BLAY, 136, 64, 16, 2, 4, VEC, 0, 0, 136, 128>(c, g);
+        return true;
+    }
+    return false;
+}
+
 template <typename T, int ALAY, int BLAY, int VEC>
-static void launch_shape(rc_context *c, const GemmArgs<T> &g) {
+static void launch_shape(rc_context *c, const GemmArgs<T> &g, bool spread) {
     if constexpr (std::is_same_v<T, double>) {
+        if (spread && launch_spread_f64q<ALAY, BLAY, VEC>(c, g)) return;
         launch_shape_f64q<ALAY, BLAY, VEC>(c, g);
     } else {
         // Skinny outputs (the sketch Y = A Omega has N = k + p ~ 69..133; the range
@@ -631,7 +668,7 @@ static void launch_shape(rc_context *c, const GemmArgs<T> &g) {
 }
 
 template <typename T, int ALAY, int BLAY>
-static void launch_vec(rc_context *c, const GemmArgs<T> &g) {
+static void launch_vec(rc_context *c, const GemmArgs<T> &g, bool spread) {
     // 2-element vector staging needs the contiguous stride to be 1, the other stride even and
     // the base 2-element aligned, for BOTH operands (odd leading dimensions take the scalar path)
     auto ok = [](const T *p, int64_t s_contig, int64_t s_other) {
@@ -639,8 +676,8 @@ static void launch_vec(rc_context *c, const GemmArgs<T> &g) {
     };
     const bool va = ALAY == 0 ? ok(g.a, g.sak, g.sam) : ok(g.a, g.sam, g.sak);
     const bool vb = BLAY == 0 ? ok(g.b, g.sbn, g.sbk) : ok(g.b, g.sbk, g.sbn);
-    if (va && vb) launch_shape<T, ALAY, BLAY, 2>(c, g);
-    else launch_shape<T, ALAY, BLAY, 1>(c, g);
+    if (va && vb) launch_shape<T, ALAY, BLAY, 2>(c, g, spread);
+    else launch_shape<T, ALAY, BLAY, 1>(c, g, spread);
 }
 
 // C = beta C (BLAS with an empty inner dimension; beta != 0 -- beta = 0 writes zeros and never reads C)
@@ -653,8 +690,9 @@ __global__ __launch_bounds__(256) void k_scale_c(Mat<T> cm, T beta) {
     }
 }
 
+// spread: a product of gemm_chain, which may take a spread form
 template <typename T>
-void gemm(rc_context *c, T alpha, Mat<T> a, Mat<T> b, T beta, Mat<T> cm) {
+static void gemm_run(rc_context *c, T alpha, Mat<T> a, Mat<T> b, T beta, Mat<T> cm, bool spread) {
     RC_REQUIRE(a.cols == b.rows && a.rows == cm.rows && b.cols == cm.cols, RC_INVALID_ARGUMENT,
                "gemm: shapes (%lld x %lld) * (%lld x %lld) -> (%lld x %lld)", (long long)a.rows, (long long)a.cols,
                (long long)b.rows, (long long)b.cols, (long long)cm.rows, (long long)cm.cols);
@@ -696,13 +734,34 @@ void gemm(rc_context *c, T alpha, Mat<T> a, Mat<T> b, T beta, Mat<T> cm) {
     const bool a_kc = (a.cs == 1);
     const bool b_nc = (b.cs == 1);
     if (a_kc) {
-        if (b_nc) launch_vec<T, 0, 0>(c, g); else launch_vec<T, 0, 1>(c, g);
+        if (b_nc) launch_vec<T, 0, 0>(c, g, spread); else launch_vec<T, 0, 1>(c, g, spread);
     } else {
-        if (b_nc) launch_vec<T, 1, 0>(c, g); else launch_vec<T, 1, 1>(c, g);
+        if (b_nc) launch_vec<T, 1, 0>(c, g, spread); else launch_vec<T, 1, 1>(c, g, spread);
     }
+}
+
+template <typename T>
+void gemm(rc_context *c, T alpha, Mat<T> a, Mat<T> b, T beta, Mat<T> cm) {
+    gemm_run<T>(c, alpha, a, b, beta, cm, false);
+}
+
+// The products on a compression's dependent chain.  With fewer than 8 compressions side by side a launch costs its duration
+// however little of the chip it fills, so the f64 Gram and shallow products go out on more and smaller
+// workgroups (launch_spread_f64q); at 8 and more the chip is the bound and gemm's fewer, fatter workgroups are right.  Same bits
+// and same slabs either way.  RC_GEMM_SPREAD=0: always gemm.
+template <typename T>
+void gemm_chain(rc_context *c, T alpha, Mat<T> a, Mat<T> b, T beta, Mat<T> cm) {
+    bool spread = false;
+    if constexpr (std::is_same_v<T, double>) {
+        static const int on = env_int("RC_GEMM_SPREAD", 1);
+        spread = on != 0 && c->lanes_in_flight() < 8;
+    }
+    gemm_run<T>(c, alpha, a, b, beta, cm, spread);
 }
 
 template void gemm<double>(rc_context *, double, Mat<double>, Mat<double>, double, Mat<double>);
 template void gemm<float>(rc_context *, float, Mat<float>, Mat<float>, float, Mat<float>);
+template void gemm_chain<double>(rc_context *, double, Mat<double>, Mat<double>, double, Mat<double>);
+template void gemm_chain<float>(rc_context *, float, Mat<float>, Mat<float>, float, Mat<float>);
 
 }  // namespace rc

@@ -533,6 +533,17 @@ static bool launch_r(rc_context *c, const GemmArgs<double> &g) {
     return true;
 }
 
+// 32-bit byte offsets from a workgroup's first element over a K chunk of `kchunk`
+static bool pipe_spans_ok(const GemmArgs<double> &g, int bm, int bn, int64_t kchunk) {
+    const int64_t a_span = ((int64_t)bm * g.sam + kchunk * g.sak + 2) * 8;
+    const int64_t b_span = ((int64_t)bn * g.sbn + kchunk * g.sbk + 2) * 8;
+    return a_span < (1ll << 31) && b_span < (1ll << 31) && g.sam >= 0 && g.sak >= 0 && g.sbn >= 0 && g.sbk >= 0;
+}
+
+bool gemm_f64p_accepts(const GemmArgs<double> &g, int bm, int bn, int bk) {
+    return bk == 16 && g.K % bk == 0 && g.K >= bk && pipe_spans_ok(g, bm, bn, g.K);
+}
+
 template <int ALAY, int BLAY, int BM, int BN, int BK, int WM, int WN, int ORIENT>
 static bool launch_p(rc_context *c, const GemmArgs<double> &g) {
     constexpr int NT = WM * WN * 64;
@@ -540,10 +551,7 @@ static bool launch_p(rc_context *c, const GemmArgs<double> &g) {
     typedef PipeStage<BLAY == 1 ? 0 : 1, BN, BK, NT> SB;
     constexpr size_t lds = 2 * (size_t)(SA::ELEMS + SB::ELEMS) * sizeof(double);
     static_assert(lds <= 160 * 1024, "tile does not fit LDS");
-    // 32-bit byte offsets from a workgroup's first element over its whole K chunk
-    const int64_t a_span = ((int64_t)BM * g.sam + g.kchunk * g.sak + 2) * 8;
-    const int64_t b_span = ((int64_t)BN * g.sbn + g.kchunk * g.sbk + 2) * 8;
-    if (a_span >= (1ll << 31) || b_span >= (1ll << 31) || g.sam < 0 || g.sak < 0 || g.sbn < 0 || g.sbk < 0) return false;
+    if (!pipe_spans_ok(g, BM, BN, g.kchunk)) return false;
     auto kern = k_gemm_f64p<ALAY, BLAY, BM, BN, BK, WM, WN, ORIENT>;
     static bool attr_set[64] = {};
     if (lds > 48 * 1024 && !attr_set[c->device & 63]) {
@@ -574,6 +582,9 @@ bool gemm_f64p_launch(rc_context *c, const GemmArgs<double> &g, int alay, int bl
     // K tile on them (load -> LDS -> MFMA in sequence), this one keeps the next tile's loads in flight
     RC_PIPE_CASE(0, 1, 144, 144, 3, 3, 0)
     RC_PIPE_CASE(1, 0, 144, 144, 3, 3, 0)
+    // the same products for gemm_chain's spread form: nine 48 x 48 tiles, each on four waves of 12 x 48, 24 / 27 KB of LDS
+    RC_PIPE_CASE(0, 1, 48, 48, 4, 1, 0)
+    RC_PIPE_CASE(1, 0, 48, 48, 4, 1, 0)
     // (the K = 128 shallow products -- Q = range Q_b, C = Q R11, U = range U_b -- through this loop on 128 x 128 tiles measured
     // neutral to slightly slower in the headline, 1072 / 1083 against 1084 / 1084: eight K tiles do not amortise the prologue)
     // the sketch and the projection where the ring refuses them (the sketch with N not a multiple of 256; spans of 2 GiB and more)

@@ -282,10 +282,10 @@ void tsqr_cholqr2_factored(rc_context *c, Mat<T> y, Mat<T> q1, Mat<T> r2i, Mat<T
     ArenaMark mark(c);
     Mat<T> g = rowmajor(c->alloc<T>((size_t)n * even_ld(n)), n, n, even_ld(n));
     Mat<T> r1 = rowmajor(c->alloc<T>((size_t)n * even_ld(n)), n, n, even_ld(n)), r1i = rowmajor(c->alloc<T>((size_t)n * even_ld(n)), n, n, even_ld(n));
-    gemm<T>(c, 1, y.t(), y, 0, g);
+    gemm_chain<T>(c, 1, y.t(), y, 0, g);
     chol_inv<T>(c, g, r1, r1i, Mat<T>(), false, 0, 0, flag);
-    gemm<T>(c, 1, y, r1i, 0, q1);
-    gemm<T>(c, 1, q1.t(), q1, 0, g);
+    gemm_chain<T>(c, 1, y, r1i, 0, q1);
+    gemm_chain<T>(c, 1, q1.t(), q1, 0, g);
     // after one pass ||Q1^T Q1 - I|| ~ cond(Y)^2 eps; the second pass is only accurate while that is << 1
     static const int skip_ok = env_int("RC_CHOLQR_SKIP", 1);
     const T skip_tol = skip_ok ? (sizeof(T) == 8 ? (T)2.5e-14 : (T)1e-6) : (T)-1;
@@ -833,7 +833,7 @@ void qrcp_tall_fast(rc_context *c, Mat<T> y, int64_t k, bool pivot, Mat<T> q, Ma
     qrcp_small<T>(c, r1, k, pivot, ind, rr, q2, r2i, q1.sub(0, k, 0, n), w, top);  // ... and w = r2i q2, top = q1[:k, :] w
     householder_signs<T>(c, top, d);
     scale_cols_rows<T>(c, w, rr, d);
-    gemm<T>(c, 1, q1, w, 0, qq);
+    gemm_chain<T>(c, 1, q1, w, 0, qq);
 }
 
 #define RC_INST(T)                                                                                               \

@@ -415,7 +415,7 @@ void svd_finish(rc_context *c, bool transposed, bool factored, Mat<T> qw, Mat<T>
     } else {
         // a = L Q_w^T = Uc S (Q_w Vc)^T
         if (!u_in_place) copy_mat(c, uc, u);
-        if (factored) gemm<T>(c, 1, small.t(), q1.t(), 0, vt);
+        if (factored) gemm_chain<T>(c, 1, small.t(), q1.t(), 0, vt);
         else gemm<T>(c, 1, vc.t(), qw.t(), 0, vt);
     }
 }
@@ -701,14 +701,14 @@ bool rsvd_id_consumers_fused(rc_context *c, Mat<T> range, Mat<T> b, const rc_rsv
             qrcp_core(c, b, k, true, qb, r, ind);
         }
         Mat<T> q = o.qr_q.data ? from_c<T>(o.qr_q) : tmp_colmajor<T>(c, m, k);
-        gemm<T>(c, 1, range, qb, 0, q);
-        if (want_cz && tails) gemm<T>(c, 1, q, r.sub(0, k, 0, k), 0, cm);  // C = Q R11, as qr_column_id has it
+        gemm_chain<T>(c, 1, range, qb, 0, q);
+        if (want_cz && tails) gemm_chain<T>(c, 1, q, r.sub(0, k, 0, k), 0, cm);  // C = Q R11, as qr_column_id has it
         else if (want_cz) qr_column_id(c, q, r, ind, cm, z, /*own_ind=*/true);
     }
     {
         ProfScope ps(c, "stage:svd of B + U=Q Ub");
         svd_finish(c, /*transposed=*/true, /*factored=*/true, Mat<T>(), q1, r2i, ub, vc, s, ub, from_c<T>(o.vt), /*u_in_place=*/true, small_done ? small : Mat<T>());
-        gemm<T>(c, 1, range, ub, 0, from_c<T>(o.u));
+        gemm_chain<T>(c, 1, range, ub, 0, from_c<T>(o.u));
     }
     return true;
 }

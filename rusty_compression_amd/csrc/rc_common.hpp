@@ -292,6 +292,9 @@ template <typename T> void adaptive_residual_update(rc_context *c, Mat<T> y, Mat
 
 // C = alpha * A * B + beta * C on views (transposes are expressed through strides)
 template <typename T> void gemm(rc_context *c, T alpha, Mat<T> a, Mat<T> b, T beta, Mat<T> cmat);
+// the same product, bit for bit, for the f64 Gram and shallow products of a compression's chain: on many small workgroups when fewer
+// than 8 compressions run side by side (kernels_gemm.hip, RC_GEMM_SPREAD)
+template <typename T> void gemm_chain(rc_context *c, T alpha, Mat<T> a, Mat<T> b, T beta, Mat<T> cmat);
 template <typename T> void complete_left_basis(rc_context *c, Mat<T> uc, const T *s);  // kernels_svd.hip: orthonormal vectors for zero singular values
 
 // Householder QR with optional column pivoting (LAPACK ?geqp3 / ?laqp2 semantics).

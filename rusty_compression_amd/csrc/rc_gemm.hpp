@@ -61,5 +61,8 @@ struct GemmArgs {
 // tiles_n, kchunk, splits, partial filled in by the caller) if an instantiation for this tile shape exists and the operands
 // meet its preconditions (16-byte vector staging, K chunks that are multiples of the K tile); returns false otherwise.
 bool gemm_f64p_launch(rc_context *c, const GemmArgs<double> &g, int alay, int blay, int bm, int bn, int bk, int wm, int wn, int orient, bool vec2);
+// Whether an instantiation of bm x bn tiles takes a product of 16-byte vector operands however its K is split (whole K tiles, 32-bit
+// spans over all of K): gemm_chain asks this of the tile gemm would launch before it cuts that tile up.
+bool gemm_f64p_accepts(const GemmArgs<double> &g, int bm, int bn, int bk);
 
 }  // namespace rc
