@@ -301,7 +301,9 @@ struct QR {  // src/qr.rs:31-40
     int64_t ncols() const { return r.ncols(); }
     int64_t rank() const { return q.ncols(); }
 
-    static QR compute_from(const DeviceMatrix<T> &a) {  // src/qr.rs:251-253
+    // src/qr.rs:251-253.  Input scale: the paragraph at rc_pivoted_qr_* (rusty_compression_amd.h) holds for compute_from here, in LQ and
+    // in SVD; compute_from_range_estimate promises no input-scale domain yet.
+    static QR compute_from(const DeviceMatrix<T> &a) {
         const int64_t m = a.nrows(), n = a.ncols(), k = m < n ? m : n;
         QR out{DeviceMatrix<T>(a.ctx(), m, k), DeviceMatrix<T>(a.ctx(), k, n), DeviceIndex(a.ctx(), (std::size_t)n)};
         a.ctx().check(Api<T>::pivoted_qr(a.ctx().raw(), a.view(), out.q.view(), out.r.view(), out.ind.data()));

@@ -271,7 +271,20 @@ rc_status rc_apply_permutation_vector_f32(rc_context *ctx, int32_t mode, rc_matr
  * k = q.cols = r.rows.  k == min(m, n) reproduces the reference exactly.
  * k <  min(m, n) is the TRUNCATED factorization (stops after k Householder
  * steps): q, r[:k] and ind[:k] equal the full factorization's, ind[k:] lists
- * the remaining columns in the order the swaps left them. */
+ * the remaining columns in the order the swaps left them.
+ * Input scale.  The domain and the equivariance statement of the "Input scale" paragraph at rc_column_id_rank_batched_* hold for
+ * this call in all four scalar types: with the largest finite real or imaginary part of a within [2^-100, 2^100] (f32 / c32) or
+ * [2^-900, 2^900] (f64 / c64) the call factors 2^-e a, e the exponent of that part (taken on the device, no host read), and R takes
+ * 2^e back; the result for 2^t A is the result for A with R times 2^t and q, ind unchanged, bit for bit while nothing leaves the
+ * normal range.  A zero matrix and one with a non-finite entry are not normalised.  Inside the domain in the same way (the factor
+ * that carries the scale in brackets): rc_pivoted_lq_* (l), rc_geqp3_* (R and, for kmax < min(m, n), the trailing block; tau and the
+ * reflectors carry none), rc_compute_svd_* (s), rc_column_id_two_sided_* and rc_row_id_two_sided_*, rc_max_col_norm_* (the norm) and
+ * rc_rel_diff_fro_* (none: both operands are read times 2^-e, e taken over both).  The calls that take such factors (rc_qr_column_id_*,
+ * rc_lq_row_id_*, rc_*_to_mat_*, rc_rank_by_tolerance_*) form no squares of them.
+ * NOT inside it -- no input-scale domain is promised yet: rc_sample_range_*, rc_qr_from_range_estimate_*, rc_svd_from_range_estimate_*
+ * and rc_rsvd_id_*, their _op_ forms and the row-sharded call (they factor the sketch A Omega and the projection Q^H A on the timed
+ * chain without normalising them), and rc_column_id_rank_* with rc_batch_column_id_* (the lone call restores from a and reads C
+ * from it, and the batch promises the lone call's bits). */
 rc_status rc_pivoted_qr_f64(rc_context *ctx, rc_matrix a, rc_matrix q, rc_matrix r, int64_t *ind);
 rc_status rc_pivoted_qr_f32(rc_context *ctx, rc_matrix a, rc_matrix q, rc_matrix r, int64_t *ind);
 /* PivotedQR::pivoted_lq (src/pivoted_qr.rs:32-41), LQ::compute_from (src/qr.rs:354-362):

@@ -303,11 +303,13 @@ void max_sqrt(rc_context *c, const T *v, int64_t n, T *out) {
     hipLaunchKernelGGL(k_max_sqrt<T>, dim3(1), dim3(256), 0, c->stream, v, n, out);
 }
 
-// Frobenius pieces, deterministic two-stage: per-block partials then one block.
+// Frobenius pieces, deterministic two-stage: per-block partials then one block.  Both operands are read times 2^-e, e the device word
+// of input_exponent(a, b): no square leaves the range, and the quotient the caller takes is free of e.
 // /root/reference/src/types.rs:182-188
 template <typename T>
-__global__ __launch_bounds__(256) void k_fro_partial(Mat<T> a, Mat<T> b, T *partial) {
+__global__ __launch_bounds__(256) void k_fro_partial(Mat<T> a, Mat<T> b, T *partial, const int *e) {
     __shared__ T sh[4];
+    const int down = -*e;
     const bool col_fast = (b.cs <= b.rs);
     const int64_t total = a.rows * a.cols;
     T d2 = 0, b2 = 0;
@@ -315,7 +317,7 @@ __global__ __launch_bounds__(256) void k_fro_partial(Mat<T> a, Mat<T> b, T *part
         int64_t i, j;
         if (col_fast) { i = e / a.cols; j = e - i * a.cols; }
         else { j = e / a.rows; i = e - j * a.rows; }
-        T x = a.at(i, j), y = b.at(i, j);
+        T x = ldexp(a.at(i, j), down), y = ldexp(b.at(i, j), down);
         d2 += (x - y) * (x - y);
         b2 += y * y;
     }
@@ -335,10 +337,11 @@ __global__ __launch_bounds__(256) void k_fro_final(const T *partial, int nblocks
 template <typename T>
 void fro_diff(rc_context *c, Mat<T> a, Mat<T> b, T *out2) {
     RC_REQUIRE(a.rows == b.rows && a.cols == b.cols, RC_INVALID_ARGUMENT, "rel_diff_fro: shape mismatch");
+    const int *e = input_exponent(c, a, b);
     int grid = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(a.rows * a.cols, 256 * 8), 1024));
     ArenaMark mark(c);
     T *partial = c->alloc<T>(2 * (size_t)grid);
-    hipLaunchKernelGGL(k_fro_partial<T>, dim3(grid), dim3(256), 0, c->stream, a, b, partial);
+    hipLaunchKernelGGL(k_fro_partial<T>, dim3(grid), dim3(256), 0, c->stream, a, b, partial, e);
     hipLaunchKernelGGL(k_fro_final<T>, dim3(1), dim3(256), 0, c->stream, partial, grid, out2);
 }
 

@@ -338,8 +338,11 @@ void pivoted_qr(rc_context *c, Mat<T> a, Mat<T> q, Mat<T> r, int64_t *ind) {
     if (n == 0) return;
     ArenaMark mark(c);
     Mat<T> w = tmp_colmajor<T>(c, m, n);  // the reference's F-order working copy (pivoted_qr.rs:28-29)
-    copy_mat(c, a, w);
+    // input scale: the copy is 2^-e a, e the exponent of a's largest entry (a device word); R takes 2^e back
+    const int *e = input_exponent(c, a);
+    copy_mat_scaled(c, a, w, e);
     qrcp_core(c, w, k, true, q, r, ind);
+    rescale(c, r, e, 1);
 }
 
 // ---- LAPACK granularity (for a maintainer who swaps only the `$qrf` call at /root/reference/src/pivoted_qr.rs:139-172
@@ -357,7 +360,8 @@ void lapack_geqp3(rc_context *c, Mat<T> a, int64_t kmax, int64_t *jpvt, T *tau) 
     if (kmax == 0 || m == 0) { iota_i64(c, jpvt, n); return; }
     ArenaMark mark(c);
     Mat<T> w = tmp_colmajor<T>(c, m, n);
-    copy_mat(c, a, w);
+    const int *e = input_exponent(c, a);  // (input scale, as pivoted_qr)
+    copy_mat_scaled(c, a, w, e);
     Mat<T> src = w;
     bool done = false;
     if (c->opt_wide_coop && wide_coop_supported<T>(m, n, c->device)) {
@@ -373,6 +377,7 @@ void lapack_geqp3(rc_context *c, Mat<T> a, int64_t kmax, int64_t *jpvt, T *tau) 
         geqp3_inplace(c, w, kmax, true, jpvt, tau, vn);
     }
     gather_cols(c, src, jpvt, a);  // a[:, p] = factored column jpvt[p]
+    rescale(c, a, e, 1, kmax);     // R (and, kmax < min(m, n), the trailing block) carries 2^e; the reflectors and tau do not
 }
 // ?orgqr: q (m x k) = H_0 ... H_{k-1} [I; 0] from the reflectors below the diagonal of the first k columns of a (LAPACK format) and tau
 template <typename T>
@@ -469,8 +474,10 @@ void compute_svd(rc_context *c, Mat<T> a, Mat<T> u, T *s, Mat<T> vt) {
     const bool transposed = m < n;
     Mat<T> src = transposed ? a.t() : a;
     Mat<T> wt = tmp_colmajor<T>(c, src.rows, src.cols);
-    copy_mat(c, src, wt);
+    const int *e = input_exponent(c, a);  // (input scale, as pivoted_qr: s takes 2^e back)
+    copy_mat_scaled(c, src, wt, e);
     svd_core(c, wt, transposed, u, s, vt);
+    rescale(c, Mat<T>(s, r, 1, 1, 1), e, 1);
 }
 
 // Z of a column / row ID in one launch (RC_ID_FUSED)

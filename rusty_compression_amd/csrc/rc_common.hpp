@@ -287,8 +287,15 @@ void iota_i64(rc_context *c, int64_t *p, int64_t n);
 template <typename T> void col_sumsq(rc_context *c, Mat<T> a, T *out);
 // device scalar reductions; results land in device memory `out`
 template <typename T> void max_sqrt(rc_context *c, const T *v, int64_t n, T *out);           // out = sqrt(max v)
-template <typename T> void fro_diff(rc_context *c, Mat<T> a, Mat<T> b, T *out2);             // out2[0]=|a-b|_F^2, out2[1]=|b|_F^2
+template <typename T> void fro_diff(rc_context *c, Mat<T> a, Mat<T> b, T *out2);             // out2[0]=|a-b|_F^2, out2[1]=|b|_F^2, both times 4^-e of input_exponent(a, b)
 template <typename T> void adaptive_residual_update(rc_context *c, Mat<T> y, Mat<T> corr);   // y -= corr
+// Input scale of the dense entry points (kernels_scale.hip; E: f64, f32 and their complex elements).
+// input_exponent: a device word with ilogb of the largest finite magnitude of a (and b), clamped to the normal exponents; 0 for zero
+// data and for data with an inf or a NaN.  copy_mat_scaled: dst = 2^-e src.  rescale: x *= 2^(sign e) in place, the entries below the
+// diagonal of the first refl_k columns left as they are.
+template <typename E> int *input_exponent(rc_context *c, Mat<E> a, Mat<E> b = Mat<E>());
+template <typename E> void copy_mat_scaled(rc_context *c, Mat<E> src, Mat<E> dst, const int *e);
+template <typename E> void rescale(rc_context *c, Mat<E> x, const int *e, int sign, int64_t refl_k = 0);
 
 // C = alpha * A * B + beta * C on views (transposes are expressed through strides)
 template <typename T> void gemm(rc_context *c, T alpha, Mat<T> a, Mat<T> b, T beta, Mat<T> cmat);

@@ -133,15 +133,19 @@ __global__ __launch_bounds__(256) void k_c_col_sumsq(CV<R> a, R *out) {
         if (lane == 0) out[j] = acc;
     }
 }
-// out2[0] = ||a - b||_F^2, out2[1] = ||b||_F^2 : one workgroup, fixed order (small matrices only on this path)
+// out2[0] = ||a - b||_F^2, out2[1] = ||b||_F^2 : one workgroup, fixed order (small matrices only on this path); both operands are read
+// times 2^-e, e the device word of input_exponent(a, b) (as k_fro_partial, kernels_util.hip)
 template <typename R>
-__global__ __launch_bounds__(1024) void k_c_fro(CV<R> a, CV<R> b, R *out2) {
+__global__ __launch_bounds__(1024) void k_c_fro(CV<R> a, CV<R> b, R *out2, const int *e) {
     __shared__ R sh[32];
+    const int down = -*e;
     R d2 = 0, b2 = 0;
     const int64_t total = a.rows * a.cols;
     for (int64_t e = threadIdx.x; e < total; e += 1024) {
         const int64_t j = e / a.rows, i = e - j * a.rows;
-        const cplx<R> x = a.at(i, j), y = b.at(i, j);
+        cplx<R> x = a.at(i, j), y = b.at(i, j);
+        x = {ldexp(x.re, down), ldexp(x.im, down)};
+        y = {ldexp(y.re, down), ldexp(y.im, down)};
         d2 += abs2(x - y);
         b2 += abs2(y);
     }
@@ -413,9 +417,11 @@ void c_lapack_geqp3(rc_context *c, CV<R> a, int64_t kmax, int64_t *jpvt, cplx<R>
     if (kmax == 0 || m == 0) { iota_i64(c, jpvt, n); return; }
     ArenaMark mark(c);
     CV<R> w = tmp_colmajor<cplx<R>>(c, m, n);
-    copy_mat(c, a, w);
+    const int *e = input_exponent(c, a);  // input scale: factor 2^-e a; R takes 2^e back, the reflectors and tau carry none
+    copy_mat_scaled(c, a, w, e);
     c_geqp3(c, w, kmax, jpvt, tau);
     gather_cols(c, w, jpvt, a);
+    rescale(c, a, e, 1, kmax);
 }
 template <typename R>
 void c_lapack_ungqr(rc_context *c, CV<R> a, const cplx<R> *tau, int64_t k, CV<R> q) {
@@ -743,6 +749,36 @@ void c_pivoted_lq(rc_context *c, CV<R> a, CV<R> l, CV<R> q, int64_t *ind, int64_
     copy_mat(c, rp.t(), l, true);
     copy_mat(c, qp.t(), q, true);
 }
+// ---- the input scale of rc_pivoted_qr_c*, rc_pivoted_lq_c*, rc_compute_svd_c* and the two-sided IDs: the call
+// runs on 2^-e a, e the exponent of a's largest component (a device word), and R, L and s take 2^e back.  The functions above stay as
+// they are for the range finders, rc_rsvd_id_c* and the column IDs by rank, which promise no input-scale domain yet.
+template <typename R>
+CV<R> c_normalised(rc_context *c, CV<R> a, const int *e) {
+    CV<R> an = tmp_colmajor<cplx<R>>(c, a.rows, a.cols);
+    copy_mat_scaled(c, a, an, e);
+    return an;
+}
+template <typename R>
+void c_pivoted_qr_scaled(rc_context *c, CV<R> a, CV<R> q, CV<R> r, int64_t *ind, int64_t k) {
+    ArenaMark mark(c);
+    const int *e = input_exponent(c, a);
+    c_pivoted_qr(c, c_normalised(c, a, e), q, r, ind, k);
+    rescale(c, r, e, 1);
+}
+template <typename R>
+void c_pivoted_lq_scaled(rc_context *c, CV<R> a, CV<R> l, CV<R> q, int64_t *ind, int64_t k) {
+    ArenaMark mark(c);
+    const int *e = input_exponent(c, a);
+    c_pivoted_lq(c, c_normalised(c, a, e), l, q, ind, k);
+    rescale(c, l, e, 1);
+}
+template <typename R>
+void c_compute_svd_scaled(rc_context *c, CV<R> a, CV<R> u, R *s, CV<R> vt) {
+    ArenaMark mark(c);
+    const int *e = input_exponent(c, a);
+    c_compute_svd(c, c_normalised(c, a, e), u, s, vt);
+    rescale(c, Mat<R>(s, std::min(a.rows, a.cols), 1, 1, 1), e, 1);
+}
 template <typename R>
 void fill_gaussian(rc_context *c, CV<R> out, uint64_t seed, uint64_t offset) {
     // element (i, j): re = normal number 2 (i cols + j), im = the next one (src/random_matrix.rs:136-143), row-major order
@@ -881,7 +917,7 @@ extern "C" {
             CV<R> A = view_of<R>(first), B = view_of<R>(second);                                                                          \
             RC_REQUIRE(A.rows == B.rows && A.cols == B.cols, RC_INVALID_ARGUMENT, "rel_diff_fro: shape mismatch");                        \
             R *d = ctx->alloc<R>(2);                                                                                                      \
-            hipLaunchKernelGGL(k_c_fro<R>, dim3(1), dim3(1024), 0, ctx->stream, A, B, d);                                                 \
+            hipLaunchKernelGGL(k_c_fro<R>, dim3(1), dim3(1024), 0, ctx->stream, A, B, d, input_exponent(ctx, A, B));                      \
             R h[2];                                                                                                                       \
             read_back(ctx, d, h, 2);                                                                                                      \
             *out = std::sqrt(h[0]) / std::sqrt(h[1]);                                                                                     \
@@ -891,7 +927,7 @@ extern "C" {
         return guarded(ctx, [&] {                                                                                                         \
             CV<R> A = view_of<R>(a), Q = view_of<R>(q), Rr = view_of<R>(r);                                                               \
             RC_REQUIRE(Q.rows == A.rows && Rr.cols == A.cols && Rr.rows == Q.cols, RC_INVALID_ARGUMENT, "pivoted_qr: output shapes");     \
-            c_pivoted_qr<R>(ctx, A, Q, Rr, ind, Q.cols);                                                                                  \
+            c_pivoted_qr_scaled<R>(ctx, A, Q, Rr, ind, Q.cols);                                                                           \
         });                                                                                                                               \
     }                                                                                                                                     \
     rc_status rc_geqp3_##SUF(rc_context *ctx, rc_matrix a, int64_t kmax, int64_t *jpvt, CT *tau) {                                        \
@@ -912,11 +948,11 @@ extern "C" {
         return guarded(ctx, [&] {                                                                                                         \
             CV<R> A = view_of<R>(a), L = view_of<R>(l), Q = view_of<R>(q);                                                                \
             RC_REQUIRE(L.rows == A.rows && Q.cols == A.cols && Q.rows == L.cols, RC_INVALID_ARGUMENT, "pivoted_lq: output shapes");       \
-            c_pivoted_lq<R>(ctx, A, L, Q, ind, L.cols);                                                                                   \
+            c_pivoted_lq_scaled<R>(ctx, A, L, Q, ind, L.cols);                                                                            \
         });                                                                                                                               \
     }                                                                                                                                     \
     rc_status rc_compute_svd_##SUF(rc_context *ctx, rc_matrix a, rc_matrix u, R *s, rc_matrix vt) {                                       \
-        return guarded(ctx, [&] { c_compute_svd<R>(ctx, view_of<R>(a), view_of<R>(u), s, view_of<R>(vt)); });                             \
+        return guarded(ctx, [&] { c_compute_svd_scaled<R>(ctx, view_of<R>(a), view_of<R>(u), s, view_of<R>(vt)); });                      \
     }                                                                                                                                     \
     rc_status rc_qr_to_mat_##SUF(rc_context *ctx, rc_matrix q, rc_matrix r, const int64_t *ind, rc_matrix out) {                          \
         return guarded(ctx, [&] {                                                                                                         \
@@ -966,7 +1002,7 @@ extern "C" {
             CV<R> C = view_of<R>(c);                                                                                                      \
             const int64_t m = C.rows, k = C.cols, kk = std::min(m, k);                                                                    \
             CV<R> l = tmp_colmajor<cplx<R>>(ctx, m, kk), ql = tmp_colmajor<cplx<R>>(ctx, kk, k);                                          \
-            c_pivoted_lq<R>(ctx, C, l, ql, row_ind, kk); /* LQ::compute_from, qr.rs:354-362 */                                            \
+            c_pivoted_lq_scaled<R>(ctx, C, l, ql, row_ind, kk); /* LQ::compute_from, qr.rs:354-362 */                                     \
             c_lq_row_id<R>(ctx, l, ql, row_ind, view_of<R>(c_out), view_of<R>(x));                                                        \
         });                                                                                                                               \
     }                                                                                                                                     \
@@ -975,7 +1011,7 @@ extern "C" {
             CV<R> Rr = view_of<R>(r);                                                                                                     \
             const int64_t k = Rr.rows, n = Rr.cols, kk = std::min(k, n);                                                                  \
             CV<R> q = tmp_colmajor<cplx<R>>(ctx, k, kk), rr = tmp_colmajor<cplx<R>>(ctx, kk, n);                                          \
-            c_pivoted_qr<R>(ctx, Rr, q, rr, col_ind, kk);                                                                                 \
+            c_pivoted_qr_scaled<R>(ctx, Rr, q, rr, col_ind, kk);                                                                          \
             c_qr_column_id<R>(ctx, q, rr, col_ind, view_of<R>(x), view_of<R>(r_out));                                                     \
         });                                                                                                                               \
     }                                                                                                                                     \

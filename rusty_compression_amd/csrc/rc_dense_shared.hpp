@@ -294,8 +294,13 @@ void apply_perm_matrix(rc_context *c, int mode, Mat<E> in, const int64_t *perm, 
     }                                                                                                                                    \
     rc_status rc_max_col_norm_##SUF(rc_context *ctx, rc_matrix y, R *out) {                                                              \
         return guarded(ctx, [&] {                                                                                                        \
+            /* input scale: the norms of 2^-e y, which no square leaves the range of, times 2^e */              \
+            Mat<E> Y = from_c<E>(y), w = tmp_colmajor<E>(ctx, Y.rows, Y.cols);                                                           \
             R *d = ctx->alloc<R>(1);                                                                                                     \
-            max_col_norm_dev(ctx, from_c<E>(y), d);                                                                                      \
+            const int *e = input_exponent(ctx, Y);                                                                                       \
+            copy_mat_scaled(ctx, Y, w, e);                                                                                               \
+            max_col_norm_dev(ctx, w, d);                                                                                                 \
+            rescale(ctx, Mat<R>(d, 1, 1, 1, 1), e, 1);                                                                                   \
             read_back(ctx, d, out, 1);                                                                                                   \
         });                                                                                                                              \
     }                                                                                                                                    \

@@ -13,7 +13,7 @@ BOUNDS = {
     np.dtype(np.float32): dict(sval=2e-5, orth=1e-4, recon=5e-5),
 }
 # Powers of four: the scaling is exact in f32.  The smallest keeps every squared column norm of a converged core above the smallest
-# normal f32 (sigma_0 >~ 2^-16 * 10, noise >~ 2^-40 sigma_0: squares >~ 2^-105); smaller scales are another subject.
+# normal f32 (sigma_0 >~ 2^-16 * 10, noise >~ 2^-40 sigma_0: squares >~ 2^-105); smaller and larger scales: tests/dense_scale_cases.py.
 SCALES = (1.0, 4.0 ** -5, 4.0 ** -8)
 
 

@@ -12,12 +12,11 @@ import torch
 
 import rusty_compression_amd as rc
 from oracle import ref_lapack as o
-from tests.helpers import agreed_pivot_prefix, is_permutation, npy, rel, stable_prefix
+from tests.dense_scale_cases import TOLC, check_complex_svd, check_pivoted_lq_complex, check_pivoted_qr_complex
+from tests.helpers import npy, rel, stable_prefix
 
 pytestmark = pytest.mark.gpu
 CT = rc.CompressionType
-TOLC = {np.dtype(np.complex128): dict(factor=1e-10, sval=1e-12, orth=1e-12, recon=1e-12, real=np.float64),
-        np.dtype(np.complex64): dict(factor=1e-4, sval=1e-5, orth=2e-5, recon=2e-5, real=np.float32)}
 CASES = [(np.complex128, (100, 50)), (np.complex64, (100, 50)), (np.complex128, (50, 100)), (np.complex64, (50, 100))]
 
 
@@ -69,25 +68,10 @@ def test_complex_pivoted_qr_lq_match_zgeqp3(dtype, shape):
     """src/pivoted_qr.rs:296-316 (c64 / c32 rows) + oracle parity: identical pivots, R and Q to tolerance."""
     t = TOLC[np.dtype(dtype)]
     a = _mat(dtype, shape, 1e-5, 100 + shape[0])
-    k = min(shape)
     q, r, ind = (npy(x) for x in rc.pivoted_qr(a))
-    oq, orr, oind = o.pivoted_qr(a)
-    assert is_permutation(ind, shape[1])
-    ns = agreed_pivot_prefix(ind[:k], r, oind[:k], orr, t["real"])
-    assert ns == min(k, stable_prefix(orr, t["real"]))
-    assert np.abs(q.conj().T @ q - np.eye(k)).max() <= t["orth"] * 10           # reference: 1e-6
-    assert rel(q @ r, a[:, ind]) <= t["recon"] * 10
-    assert np.abs(np.diag(r).imag).max() <= 1e-6 * np.abs(r[0, 0])               # ?geqp3: real diagonal
-    assert rel(r[:ns], orr[:ns]) <= t["factor"] * 3
-    lead = min(ns, int((np.abs(np.diag(orr)) > np.abs(orr[0, 0]) * 1e-2).sum()))
-    assert rel(q[:, :lead], oq[:, :lead]) <= t["factor"] * 10
+    check_pivoted_qr_complex(a, q, r, ind, o.pivoted_qr(a), t)
     l, ql, indl = (npy(x) for x in rc.pivoted_lq(a))
-    ol, oql, oindl = o.pivoted_lq(a)
-    nl = agreed_pivot_prefix(indl[:k], l.conj().T, oindl[:k], ol.conj().T, t["real"])
-    assert nl == min(k, stable_prefix(ol.conj().T, t["real"]))
-    assert np.abs(ql @ ql.conj().T - np.eye(k)).max() <= t["orth"] * 10
-    assert rel(l @ ql, a[indl, :]) <= t["recon"] * 10
-    assert rel(l[:, :nl], ol[:, :nl]) <= t["factor"] * 3
+    check_pivoted_lq_complex(a, l, ql, indl, o.pivoted_lq(a), t)
 
 
 @pytest.mark.parametrize("dtype,shape", CASES)
@@ -98,14 +82,7 @@ def test_complex_svd_matches_zgesdd_and_reference_properties(dtype, shape):
     svd = rc.SVD.compute_from(a)
     u, s, vt = npy(svd.u), npy(svd.s), npy(svd.vt)
     so = o.compute_svd(a)[1]
-    r = min(shape)
-    assert s.dtype == t["real"] and np.all(s[:-1] >= s[1:])
-    assert np.abs(s - so).max() <= t["sval"] * so[0]
-    assert rel((u * s) @ vt, a) <= t["recon"] * 10
-    lead = int((so > so[0] * (1e-6 if dtype == np.complex128 else 1e-2)).sum())
-    assert np.abs(u[:, :lead].conj().T @ u[:, :lead] - np.eye(lead)).max() <= t["orth"] * 10
-    assert np.abs(vt[:lead] @ vt[:lead].conj().T - np.eye(lead)).max() <= t["orth"] * 10
-    assert r == s.shape[0]
+    check_complex_svd(a, u, s, vt, so, t)
     assert rc.rel_diff_fro(svd.to_qr().to_mat(), a) < (1e-12 if dtype == np.complex128 else 1e-5)     # test_svd_to_qr_*
     c = svd.compress(CT.RANK(20))
     assert c.u.shape[1] == 20 and c.vt.shape[0] == 20 and rc.rel_diff_fro(c.to_mat(), a) < 1e-4       # test_svd_compression_by_rank_*

@@ -11,13 +11,10 @@ import pytest
 
 import rusty_compression_amd as rc
 from oracle import ref_lapack as o
+from tests.dense_scale_cases import FACTOR, RECON, REAL_OF as REAL, check_geqp3
 from tests.helpers import TOL, agreed_pivot_prefix, is_permutation, npy, rel
 
 pytestmark = pytest.mark.gpu
-FACTOR = {np.dtype(np.float64): 1e-10, np.dtype(np.complex128): 1e-10, np.dtype(np.float32): 1e-4, np.dtype(np.complex64): 1e-4}
-# A[:, jpvt] = Q R and Q^H Q = I of our own factors (backward error; the c32 Householder chain accumulates ~k eps over k steps)
-RECON = {np.dtype(np.float64): 1e-12, np.dtype(np.complex128): 1e-12, np.dtype(np.float32): 1e-5, np.dtype(np.complex64): 1e-4}
-REAL = {np.dtype(np.float64): np.float64, np.dtype(np.complex128): np.float64, np.dtype(np.float32): np.float32, np.dtype(np.complex64): np.float32}
 # tall (Householder chain / blocked panels), square, short-wide (the cooperative register-resident kernel), tiny
 SHAPES = [(300, 60), (200, 200), (96, 4096), (64, 700), (5, 3), (1, 7)]
 DTYPES = [np.float64, np.float32, np.complex128, np.complex64]
@@ -38,22 +35,10 @@ def test_geqp3_and_orgqr_match_lapack_output_format(dtype, shape):
     f, jp, tau = rc.geqp3(a)
     f, jp, tau = npy(f), npy(jp), npy(tau)
     fo, jpo, tauo = o.geqp3_raw(a)
-    assert is_permutation(jp, n) and tau.shape == (k,)
-    r, ro = np.triu(f[:k]), np.triu(fo[:k])
-    ns = agreed_pivot_prefix(jp, r, jpo, ro, REAL[dt])
-    assert ns >= min(k, 3), f"only {ns} pivots agree"
+    # R, the reflectors and tau entry for entry on the prefix both sides pivoted alike, and A[:, jpvt] = Q R with Q from OUR
+    # reflectors through OUR ?orgqr (tests/dense_scale_cases.py, which runs the same check at far-from-unit scales)
+    check_geqp3(a, f, jp, tau, npy(rc.orgqr(f, tau)), (fo, jpo, tauo), FACTOR[dt], RECON[dt], REAL[dt])
     tol = FACTOR[dt]
-    # R, the reflectors and tau, entry for entry, on the columns both sides factored in the same order
-    assert rel(r[:ns, :ns], ro[:ns, :ns]) <= tol
-    assert rel(np.abs(np.diag(r))[:ns], np.abs(np.diag(ro))[:ns]) <= tol
-    assert rel(np.tril(f[:, :ns], -1), np.tril(fo[:, :ns], -1)) <= 50 * tol   # v = x / (alpha - beta): one division more than R
-    assert rel(tau[:ns], tauo[:ns]) <= 50 * tol
-    # the factorization itself: A[:, jpvt] = Q R with Q from OUR reflectors through OUR ?orgqr
-    q = npy(rc.orgqr(f, tau))
-    assert q.shape == (m, k)
-    wide = np.complex128 if dt.kind == "c" else np.float64
-    assert rel(q.astype(wide) @ r.astype(wide), a[:, jp]) <= RECON[dt]
-    assert rel(q.conj().T.astype(wide) @ q.astype(wide), np.eye(k)) <= RECON[dt]
     # ?orgqr alone: LAPACK's reflectors in, LAPACK's Q out
     assert rel(npy(rc.orgqr(fo, tauo)), o.orgqr_raw(fo, tauo)) <= tol
     # fewer columns than reflectors stored in a: the first kk reflectors only

@@ -17,6 +17,7 @@ import torch
 
 import rusty_compression_amd as rc
 from oracle import ref_lapack as o
+from tests.dense_scale_cases import check_pivoted_qr_real, check_truncated_qr_real
 from tests.gemm_cases import GEMM_DISPATCH, gemm_operand, last_gemm_kernel
 from tests.helpers import TOL, agreed_pivot_prefix, golden, greedy_pivot_slack, is_permutation, npy, rel, sign_normalise, stable_prefix
 
@@ -223,16 +224,8 @@ def test_pivoted_qr_and_lq_match_golden(name):
 def test_pivoted_qr_shapes_against_live_oracle(dtype, shape):
     rng = np.random.default_rng(shape[0] * 7 + shape[1])
     a = o.random_approximate_low_rank_matrix(shape, 1.0, 1e-5, rng, dtype) if min(shape) > 1 else rng.standard_normal(shape).astype(dtype)
-    tol = TOL[a.dtype]
-    q, r, ind = o.pivoted_qr(a)
     gq, gr, gi = (npy(t) for t in rc.pivoted_qr(a))
-    ns = agreed_pivot_prefix(gi, gr, ind, r, dtype)
-    assert is_permutation(gi, shape[1])
-    if dtype == np.float64:
-        assert ns == stable_prefix(r, dtype)
-    assert rel(gr[:ns, :ns], r[:ns, :ns]) <= tol["factor"]
-    assert rel(gq @ gr, a[:, gi]) <= (1e-13 if dtype == np.float64 else 5e-6)
-    assert np.abs(gq.T @ gq - np.eye(gq.shape[1])).max() <= (1e-13 if dtype == np.float64 else 1e-5)
+    check_pivoted_qr_real(a, gq, gr, gi, o.pivoted_qr(a))
 
 
 @pytest.mark.parametrize("n", [8, 33, 64, 65, 100, 133, 160, 161, 224])
@@ -268,12 +261,8 @@ def test_truncated_pivoted_qr_equals_the_leading_part_of_the_full_one():
     rng = np.random.default_rng(12)
     for dtype in (np.float64, np.float32):
         a = o.random_approximate_low_rank_matrix((200, 120), 1.0, 1e-5, rng, dtype)
-        q, r, ind = o.pivoted_qr(a)
         gq, gr, gi = (npy(t) for t in rc.pivoted_qr(a, rank=30))
-        tol = TOL[a.dtype]
-        assert np.array_equal(gi[:30], ind[:30]) and is_permutation(gi, 120)
-        assert rel(gq, q[:, :30]) <= (1e-9 if dtype == np.float64 else 5e-2)
-        assert rel(o.apply_permutation_matrix(gr, gi, "COLINV"), o.apply_permutation_matrix(r[:30], ind, "COLINV")) <= tol["factor"]
+        check_truncated_qr_real(a, gq, gr, gi, 30, o.pivoted_qr(a))
 
 
 def test_pivot_ties_take_the_first_maximum_like_idamax():
