@@ -3,6 +3,7 @@
 #pragma once
 #include "rc_common.hpp"
 #include "rc_device.hpp"
+#include "rc_launch.hpp"
 
 namespace rc {
 
@@ -60,8 +61,7 @@ static_assert(kMaxSweeps < 255, "sweep count must fit a tagged word");
 // Column pitch of the core in LDS and the dynamic LDS of a launch.  A 32-lane half of a wave holds the groups of two neighbouring
 // pair slots, whose columns are neighbours too (p, p + 1 and q, q - 1): with a pitch of 16 elements modulo 32 the two 16-lane groups
 // read opposite halves of the bank row (ds_read_b64: 64 banks, f32 ds_read_b32: 32 banks) -- conflict-free, where the odd pitch n | 1
-// made every such read two-way conflicted.  The padded pitch is used whenever it fits the CU's LDS.
-constexpr size_t kJacobiLdsCap = 160 * 1024 - 2048 - 64;
+// made every such read two-way conflicted.  The padded pitch is used whenever it fits the CU's LDS (kJacobiLdsCap, rc_launch.hpp).
 template <typename T>
 inline size_t jacobi_lds_bytes(int n, int pitch) { return ((size_t)pitch * n + n) * sizeof(T) + (size_t)n * sizeof(int) + 64; }
 template <typename T>

@@ -44,11 +44,7 @@
 // The launchers follow rc_batched_launch.hpp: a plan function per entry point, then prepare, label, workspace, launch.  All but the sketch
 // product's are written once for all four element types in batched_launchers.hpp; the file ends with what they take from this family
 // (RealFamily: the Args structs, the LDS and workspace sizes and the instance to launch) and their instantiation for double and float.
-// bid_grid and the first-use LDS cap of the whole batched family are defined here.
-#include <map>
-#include <mutex>
-#include <utility>
-
+// bid_grid and the first-use LDS cap of the whole batched family are defined in rc_launch.hip.
 #include "batched_launchers.hpp"
 #include "batched_stages.hpp"
 #include "rc_batched_launch.hpp"
@@ -1242,38 +1238,6 @@ struct RealFamily {
 
 template <> struct BatchedFamily<double> : RealFamily<double> {};
 template <> struct BatchedFamily<float> : RealFamily<float> {};
-
-// the persistent grid of the whole batched family (the rule: rc_batched_launch.hpp)
-int64_t bid_grid(rc_context *c, const void *kern, size_t lds, size_t ws_per, int32_t count, int64_t *slots) {
-    static int cus_of[64] = {};
-    int &cus = cus_of[c->device & 63];
-    if (!cus && (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus <= 0)) cus = 256;
-    int per_cu = 0;
-    RC_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, BID_THREADS, lds));
-    int64_t grid = (int64_t)cus * std::max(per_cu, 1);
-    if (ws_per) grid = std::min<int64_t>(grid, std::max<int64_t>(cus, (int64_t)((size_t)256 << 20) / (int64_t)ws_per));
-    *slots = grid;
-    return std::min<int64_t>(grid, count);
-}
-
-int batched_kernel_cap(int device, const void *kern) {
-    // the calling thread's last answer first: a loop over one entry point takes neither the lock nor the lookup
-    thread_local int last_device = -1, last_scratch = 0;
-    thread_local const void *last_kern = nullptr;
-    if (device == last_device && kern == last_kern) return last_scratch;
-    static std::mutex mu;
-    static std::map<std::pair<int, const void *>, int> scratch_of;
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = scratch_of.find({device, kern});
-    if (it == scratch_of.end()) {
-        RC_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BID_MAX_LDS));
-        hipFuncAttributes fa;
-        RC_HIP(hipFuncGetAttributes(&fa, kern));
-        it = scratch_of.emplace(std::make_pair(device, kern), (int)fa.localSizeBytes).first;
-    }
-    last_device = device; last_kern = kern;
-    return last_scratch = it->second;
-}
 
 // (the launchers of the two IDs, the SVD, the recompressions, the sketched column ID and the range step: batched_launchers.hpp)
 

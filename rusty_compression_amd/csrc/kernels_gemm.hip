@@ -495,17 +495,15 @@ static void plan_split(GemmArgs<T> &g, int64_t tiles, int target, int min_ksteps
 
 // The tail shared by launch_cfg and launch_f64q for a planned product (tiles_m, tiles_n, kchunk, splits filled in): the slabs, the
 // product on the tiles x splits grid -- `kern`, unless `pipe` launches it on the pipelined main loop of kernels_gemm_pipe.hip --
-// and the deterministic slab reduction
+// and the deterministic slab reduction.  first_use: the guard of the launching instance (kern stays a run-time argument here: naming it as
+// a template argument would move the instance in front of the reduction kernels in the code object)
 template <typename T, class Pipe>
-static void launch_split(rc_context *c, GemmArgs<T> g, void (*kern)(GemmArgs<T>), int nt, size_t lds, bool (&attr_set)[64], const char *name, Pipe &&pipe) {
+static void launch_split(rc_context *c, GemmArgs<T> g, void (*kern)(GemmArgs<T>), int nt, size_t lds, FirstUse &first_use, const char *name, Pipe &&pipe) {
     const int64_t tiles = (int64_t)g.tiles_m * g.tiles_n;
     const int splits = g.splits;
     ArenaMark mark(c);
     if (splits > 1) g.partial = c->alloc<T>((size_t)splits * g.M * g.N);
-    if (lds > 48 * 1024 && !attr_set[c->device & 63]) {
-        RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set[c->device & 63] = true;
-    }
+    if (lds > 48 * 1024) first_use(c->device, [&] { set_dynamic_lds_limit(reinterpret_cast<const void *>(kern), lds); });
     c->last_gemm_kernel = name;
     if (!pipe(g)) {
         ProfScope ps(c, "kernel:k_gemm_mfma<%s> M=%lld N=%lld K=%lld", sizeof(T) == 8 ? "f64" : "f32", (long long)g.M, (long long)g.N, (long long)g.K);
@@ -529,7 +527,7 @@ static void launch_cfg(rc_context *c, GemmArgs<T> g, int target_wgs = 0, int min
     typedef TileStager<T, ALAY, BM, BK, NT, VEC> StA;
     typedef TileStager<T, BLAY == 1 ? 0 : 1, BN, BK, NT, VEC> StB;
     constexpr size_t lds = NBUF * (size_t)(StA::ELEMS + StB::ELEMS) * sizeof(T);
-    static_assert(lds <= 160 * 1024, "tile does not fit LDS");
+    static_assert(lds <= kCuLdsBytes, "tile does not fit LDS");
     g.tiles_m = (int)cdiv(g.M, BM);
     g.tiles_n = (int)cdiv(g.N, BN);
     const int64_t tiles = (int64_t)g.tiles_m * g.tiles_n;
@@ -538,11 +536,11 @@ static void launch_cfg(rc_context *c, GemmArgs<T> g, int target_wgs = 0, int min
     // amortise its prologue / slab write, and the reduction reads 4x less than with 128 slabs
     static const int target_big = env_int("RC_GEMM_TARGET_WGS", 256), target_small = env_int("RC_GEMM_SMALL_TARGET", 32);
     const int target = target_wgs > 0 ? target_wgs : tiles >= 8 ? (tiles >= 32 ? wide_target(c, 1, target_big) : target_big) : target_small;
-    static bool attr_set[64] = {};
+    static FirstUse first_use;
     char nm[128];
     snprintf(nm, sizeof(nm), "k_gemm_mfma<%s,%d,%d,%d,%d,%d,%d,%d,%d,%d>", sizeof(T) == 8 ? "double" : "float", ALAY, BLAY, BM, BN, BK, WM, WN, VEC, NBUF);
     plan_split<T, BK>(g, tiles, target, min_ksteps);
-    launch_split<T>(c, g, k_gemm_mfma<T, ALAY, BLAY, BM, BN, BK, WM, WN, VEC, NBUF>, NT, lds, attr_set, nm, [](const GemmArgs<T> &) { return false; });
+    launch_split<T>(c, g, k_gemm_mfma<T, ALAY, BLAY, BM, BN, BK, WM, WN, VEC, NBUF>, NT, lds, first_use, nm, [](const GemmArgs<T> &) { return false; });
 }
 
 // PBM x PBN: the tile the K slabs are planned for.  It is the launched tile, except in the spread forms of gemm_chain, which cut the
@@ -554,7 +552,7 @@ static void launch_f64q(rc_context *c, GemmArgs<double> g, int target_wgs = 0, i
     typedef TileStager<T, ALAY, BM, BK, NT, VEC> StA;
     typedef TileStager<T, BLAY == 1 ? 0 : 1, BN, BK, NT, VEC> StB;
     constexpr size_t lds = 2 * (size_t)(StA::ELEMS + StB::ELEMS) * sizeof(T);
-    static_assert(lds <= 160 * 1024, "tile does not fit LDS");
+    static_assert(lds <= kCuLdsBytes, "tile does not fit LDS");
     static_assert(PBM % BM == 0 && PBN % BN == 0, "the launched tiles cut the planned one");
     g.tiles_m = (int)cdiv(g.M, BM);
     g.tiles_n = (int)cdiv(g.N, BN);
@@ -567,12 +565,12 @@ static void launch_f64q(rc_context *c, GemmArgs<double> g, int target_wgs = 0, i
     static const int target_lanes = env_int("RC_GEMM_LANES_TARGET", 1);
     const int lone = target_wgs > 0 ? target_wgs : target_big;
     const int target = tiles >= 8 ? (tiles >= 32 ? wide_target(c, target_lanes, lone) : lone) : target_small;
-    static bool attr_set[64] = {};
+    static FirstUse first_use;
     char nm[128];
     snprintf(nm, sizeof(nm), "k_gemm_f64q<%d,%d,%d,%d,%d,%d,%d,%d,%d,%d>", ALAY, BLAY, BM, BN, BK, WM, WN, VEC, ORIENT, GLDS);
     // the software-pipelined main loop (kernels_gemm_pipe.hip) where it has an instantiation for this tile shape
     plan_split<T, BK>(g, tiles, target, min_ksteps);
-    launch_split<T>(c, g, k_gemm_f64q<ALAY, BLAY, BM, BN, BK, WM, WN, VEC, ORIENT, GLDS>, NT, lds, attr_set, nm,
+    launch_split<T>(c, g, k_gemm_f64q<ALAY, BLAY, BM, BN, BK, WM, WN, VEC, ORIENT, GLDS>, NT, lds, first_use, nm,
                     [&](const GemmArgs<T> &gs) { return gemm_f64p_launch(c, gs, ALAY, BLAY, BM, BN, BK, WM, WN, ORIENT, VEC == 2); });
 }
 

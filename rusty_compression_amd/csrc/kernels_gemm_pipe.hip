@@ -513,18 +513,14 @@ template <int BLAY, int ORIENT, int BM, int BN, int WM, int WN, bool MASKTAIL>
 static bool launch_r(rc_context *c, const GemmArgs<double> &g) {
     constexpr int NT = WM * WN * 64;
     constexpr size_t lds = 3 * (size_t)(DirectRows<BM, 16, NT, MASKTAIL>::ELEMS + (BLAY == 0 ? DirectRows<BN, 16, NT>::ELEMS : DirectK<BN, 16, NT>::ELEMS)) * sizeof(double);
-    static_assert(lds <= 160 * 1024, "ring does not fit LDS");
+    static_assert(lds <= kCuLdsBytes, "ring does not fit LDS");
     if (g.sam != 1) return false;
     if (BLAY == 0 ? g.sbn != 1 : (g.sbk != 1 || g.N % BN != 0)) return false;
     const int64_t a_span = ((int64_t)256 * g.sam + g.kchunk * g.sak + 2) * 8;
     const int64_t b_span = ((int64_t)BN * g.sbn + g.kchunk * g.sbk + 2) * 8;
     if (a_span >= (1ll << 31) || b_span >= (1ll << 31) || g.sak < 0 || g.sbn < 0 || g.sbk < 0) return false;
-    auto kern = k_gemm_f64r<BLAY, ORIENT, BM, BN, WM, WN, MASKTAIL>;
-    static bool attr_set[64] = {};
-    if (!attr_set[c->device & 63]) {
-        RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set[c->device & 63] = true;
-    }
+    constexpr auto kern = k_gemm_f64r<BLAY, ORIENT, BM, BN, WM, WN, MASKTAIL>;
+    raise_lds_limit<kern>(c->device, lds);
     char nm[128];
     snprintf(nm, sizeof(nm), "k_gemm_f64r<%d,%d,%d,%d,%d,%d,%s,0>", BLAY, ORIENT, BM, BN, WM, WN, MASKTAIL ? "true" : "false");  // as rocprofv3 prints it
     c->last_gemm_kernel = nm;
@@ -550,14 +546,10 @@ static bool launch_p(rc_context *c, const GemmArgs<double> &g) {
     typedef PipeStage<ALAY, BM, BK, NT> SA;
     typedef PipeStage<BLAY == 1 ? 0 : 1, BN, BK, NT> SB;
     constexpr size_t lds = 2 * (size_t)(SA::ELEMS + SB::ELEMS) * sizeof(double);
-    static_assert(lds <= 160 * 1024, "tile does not fit LDS");
+    static_assert(lds <= kCuLdsBytes, "tile does not fit LDS");
     if (!pipe_spans_ok(g, BM, BN, g.kchunk)) return false;
-    auto kern = k_gemm_f64p<ALAY, BLAY, BM, BN, BK, WM, WN, ORIENT>;
-    static bool attr_set[64] = {};
-    if (lds > 48 * 1024 && !attr_set[c->device & 63]) {
-        RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set[c->device & 63] = true;
-    }
+    constexpr auto kern = k_gemm_f64p<ALAY, BLAY, BM, BN, BK, WM, WN, ORIENT>;
+    if (lds > 48 * 1024) raise_lds_limit<kern>(c->device, lds);
     char nm[128];
     snprintf(nm, sizeof(nm), "k_gemm_f64p<%d,%d,%d,%d,%d,%d,%d,%d>", ALAY, BLAY, BM, BN, BK, WM, WN, ORIENT);
     c->last_gemm_kernel = nm;

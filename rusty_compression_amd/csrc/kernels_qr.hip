@@ -22,6 +22,7 @@
 // generation.
 #include "rc_common.hpp"
 #include "rc_device.hpp"
+#include "rc_launch.hpp"
 
 namespace rc {
 
@@ -561,7 +562,7 @@ void form_q(rc_context *c, Mat<T> w, const int64_t *jpvt, const T *tau, int64_t 
     const unsigned grid = (unsigned)qw.cols;
     if (k <= 0) { fill_identity(c, qw); return; }
     ProfScope ps(c, "op:form_q %lldx%lld k=%lld", (long long)m, (long long)qw.cols, (long long)k);
-    if (m >= 2048 && k >= 16 && ((size_t)k + (size_t)k * (k | 1)) * sizeof(T) <= 160 * 1024 - 1024) {
+    if (m >= 2048 && k >= 16 && ((size_t)k + (size_t)k * (k | 1)) * sizeof(T) <= kLdsCap) {
         // tall: three MFMA GEMMs instead of k dependent reflector applications per column
         ArenaMark mark(c);
         const int64_t kq = qw.cols;
@@ -572,14 +573,9 @@ void form_q(rc_context *c, Mat<T> w, const int64_t *jpvt, const T *tau, int64_t 
         Mat<T> tm = colmajor(c->alloc<T>((size_t)even_ld(k) * k), k, k, even_ld(k));
         {
             const size_t lds = ((size_t)k + (size_t)k * (k | 1)) * sizeof(T);
-            RC_REQUIRE(lds <= 160 * 1024 - 1024, RC_INVALID_ARGUMENT, "form_q: block of %lld reflectors does not fit the LDS T-builder", (long long)k);
-            auto kern = k_build_t<T>;
-            static bool attr_set[64] = {};
-            if (!attr_set[c->device & 63]) {
-                RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-                attr_set[c->device & 63] = true;
-            }
-            hipLaunchKernelGGL(kern, dim3(1), dim3(1024), lds, c->stream, sg, tau, tm);
+            RC_REQUIRE(lds <= kLdsCap, RC_INVALID_ARGUMENT, "form_q: block of %lld reflectors does not fit the LDS T-builder", (long long)k);
+            raise_lds_limit<k_build_t<T>>(c->device, kLdsCap);
+            hipLaunchKernelGGL(k_build_t<T>, dim3(1), dim3(1024), lds, c->stream, sg, tau, tm);
         }
         Mat<T> w2 = rowmajor(c->alloc<T>((size_t)k * even_ld(kq)), k, kq, even_ld(kq));
         gemm<T>(c, 1, tm, vm.sub(0, std::min(kq, m), 0, k).t(), 0, w2);
@@ -591,16 +587,10 @@ void form_q(rc_context *c, Mat<T> w, const int64_t *jpvt, const T *tau, int64_t 
         const unsigned threads = (unsigned)std::max<int64_t>(256, ((qw.cols * 8 + 63) / 64) * 64);
         const int ne = m <= 64 ? 8 : 16;
         const size_t lds = ((size_t)k * 8 * ne + (size_t)k) * sizeof(T);
-        auto k8 = k_form_q_small<T, 8>;
-        auto k16 = k_form_q_small<T, 16>;
-        static bool attr_set[64] = {};
-        if (!attr_set[c->device & 63]) {
-            RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k8), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-            RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k16), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-            attr_set[c->device & 63] = true;
-        }
-        if (ne == 8) hipLaunchKernelGGL(k8, dim3(1), dim3(threads), lds, c->stream, w, jpvt, tau, (int)k, qw);
-        else hipLaunchKernelGGL(k16, dim3(1), dim3(threads), lds, c->stream, w, jpvt, tau, (int)k, qw);
+        raise_lds_limit<k_form_q_small<T, 8>>(c->device, kLdsCap);
+        raise_lds_limit<k_form_q_small<T, 16>>(c->device, kLdsCap);
+        if (ne == 8) hipLaunchKernelGGL((k_form_q_small<T, 8>), dim3(1), dim3(threads), lds, c->stream, w, jpvt, tau, (int)k, qw);
+        else hipLaunchKernelGGL((k_form_q_small<T, 16>), dim3(1), dim3(threads), lds, c->stream, w, jpvt, tau, (int)k, qw);
         return;
     }
     if (m <= 256 * 2) hipLaunchKernelGGL((k_form_q<T, 2>), dim3(grid), dim3(256), 0, c->stream, w, jpvt, tau, k, qw);
@@ -813,13 +803,8 @@ void rsvd_id_tails(rc_context *c, Mat<T> wf, const int64_t *jpvt, const T *tau, 
     const int ns = small.empty() ? 0 : (int)cdiv(k, kSmallProductCols);
     const size_t lds = ((size_t)k * 8 * NE + (size_t)k) * sizeof(T);  // (>= kSmallProductCols * (k | 1) words: k > 64)
     ProfScope ps(c, "op:rsvd_id_tails k=%lld n=%lld wgs=%d+%d+%d+%d", (long long)k, (long long)n, nz, ns, nq, nr);
-    auto kern = k_rsvd_id_tails<T, NE>;
-    static bool attr_set[64] = {};
-    if (!attr_set[c->device & 63]) {
-        RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096));
-        attr_set[c->device & 63] = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)(nz + ns + nq + nr)), dim3(256), lds, c->stream, wf, jpvt, tau, (int)k, z, qb, r, nz, nq, r2i, x, small, ns);
+    raise_lds_limit<k_rsvd_id_tails<T, NE>>(c->device, kLdsCapTails);
+    hipLaunchKernelGGL((k_rsvd_id_tails<T, NE>), dim3((unsigned)(nz + ns + nq + nr)), dim3(256), lds, c->stream, wf, jpvt, tau, (int)k, z, qb, r, nz, nq, r2i, x, small, ns);
 }
 // a: the original m x n matrix (any layout); w: its factorization in the ?geqp3 format (column-major, columns in place, k steps);
 // jpvt: position -> physical column; cm: m x k, z: k x n
@@ -1109,7 +1094,7 @@ __global__ __launch_bounds__(256) void k_wq_extract(Mat<T> rphys, const int64_t 
 template <typename T>
 static size_t wq_pivot_lds(int64_t m) { return ((size_t)m * (m | 1) + 4 * (size_t)m + 16) * sizeof(T) + 16 * sizeof(long long); }
 template <typename T>
-bool wide_lazy_supported(int64_t m, int64_t n) { return m >= 2 && m <= 256 && n >= 4 * m && n >= 256 && wq_pivot_lds<T>(m) <= 160 * 1024 - 1024; }
+bool wide_lazy_supported(int64_t m, int64_t n) { return m >= 2 && m <= 256 && n >= 4 * m && n >= 256 && wq_pivot_lds<T>(m) <= kLdsCap; }
 
 // b: m x n column-major (NOT modified); q: m x kq (any strides, may be empty); r: kmax x n (may be empty)
 template <typename T>
@@ -1126,12 +1111,8 @@ void geqp3_wide_lazy(rc_context *c, Mat<T> b, int64_t kmax, int64_t *jpvt, Mat<T
     T *vn1 = vn, *vn2 = vn + n;
     hipLaunchKernelGGL(k_qr_init<T>, dim3((unsigned)std::min<int64_t>(n, 65535)), dim3(256), 0, c->stream, b, 1, jpvt, vn1, vn2);
     hipLaunchKernelGGL(k_wq_init<T>, dim3((unsigned)std::min<int64_t>(cdiv(m * m + kmax * n, 256), 4096)), dim3(256), 0, c->stream, qacc, rphys);
-    auto pk = k_wq_pivot<T>;
-    static bool attr_set[64] = {};
-    if (!attr_set[c->device & 63]) {
-        RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(pk), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-        attr_set[c->device & 63] = true;
-    }
+    constexpr auto pk = k_wq_pivot<T>;
+    raise_lds_limit<pk>(c->device, kLdsCap);
     for (int64_t j = 0; j < kmax; ++j) {
         hipLaunchKernelGGL(pk, dim3(1), dim3(1024), wq_pivot_lds<T>(m), c->stream, b, qacc, rphys, j, jpvt, vn1, vn2, tau);
         const int64_t rem = n - j - 1;

@@ -208,12 +208,8 @@ static void launch_lds_impl(rc_context *c, Mat<T> g, Mat<T> uc, T *s, Mat<T> vc,
     Rot<T> *log = c->alloc<Rot<T>>((size_t)kMaxSweeps * (N - 1) * (N / 2));
     int *sweeps = c->alloc<int>(1);
     int *order = c->alloc<int>((size_t)n);
-    auto kern = k_jacobi_lds<T, NE, FULL>;
-    static bool attr_set[64] = {};
-    if (!attr_set[c->device & 63]) {
-        RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048));
-        attr_set[c->device & 63] = true;
-    }
+    constexpr auto kern = k_jacobi_lds<T, NE, FULL>;
+    raise_lds_limit<kern>(c->device, kLdsCapWide);
     // one 16-lane group per pair, rounded up to whole waves
     const int threads = std::min(1024, std::max(64, (((N / 2) * kLPP + 63) / 64) * 64));
     // fused right vectors: a second workgroup applies the rotations to V as they are published (no replay kernel

@@ -22,6 +22,7 @@
 // from src/random_sampling.rs:114) and the QR/LQ reduction inside ?gesdd (src/compute_svd.rs:19).
 #include "rc_common.hpp"
 #include "rc_device.hpp"
+#include "rc_launch.hpp"
 
 namespace rc {
 
@@ -239,19 +240,14 @@ static size_t chol_lds(int64_t n) { return ((size_t)n * (n | 1) + 3 * (size_t)n 
 
 template <typename T, int NT, bool FOLD>
 static void chol_inv_launch(rc_context *c, Mat<T> g, Mat<T> r, Mat<T> rinv, Mat<T> r1, bool check_identity, T ident_tol, T skip_tol, int *flag) {
-    auto kern = k_chol_inv<T, NT, FOLD>;
-    static bool attr_set[64] = {};
-    if (!attr_set[c->device & 63]) {
-        RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-        attr_set[c->device & 63] = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(1), dim3(1024), chol_lds<T>(g.rows), c->stream, g, r, rinv, r1, check_identity ? 1 : 0, ident_tol, skip_tol, flag);
+    raise_lds_limit<k_chol_inv<T, NT, FOLD>>(c->device, kLdsCap);
+    hipLaunchKernelGGL((k_chol_inv<T, NT, FOLD>), dim3(1), dim3(1024), chol_lds<T>(g.rows), c->stream, g, r, rinv, r1, check_identity ? 1 : 0, ident_tol, skip_tol, flag);
 }
 // r1 empty: r = R, g = R^T R.  r1 given (n x n upper triangular): r = R r1
 template <typename T>
 static void chol_inv(rc_context *c, Mat<T> g, Mat<T> r, Mat<T> rinv, Mat<T> r1, bool check_identity, T ident_tol, T skip_tol, int *flag) {
     const int64_t n = g.rows;
-    RC_REQUIRE(n <= 224 && chol_lds<T>(n) <= 160 * 1024 - 1024, RC_INVALID_ARGUMENT, "chol_inv: n = %lld does not fit LDS", (long long)n);
+    RC_REQUIRE(n <= 224 && chol_lds<T>(n) <= kLdsCap, RC_INVALID_ARGUMENT, "chol_inv: n = %lld does not fit LDS", (long long)n);
     ProfScope ps(c, "op:chol_inv n=%lld", (long long)n);
 #define RC_CI(NT_)                                                                                          \
     do {                                                                                                    \
@@ -267,7 +263,7 @@ static void chol_inv(rc_context *c, Mat<T> g, Mat<T> r, Mat<T> rinv, Mat<T> r1, 
 template <typename T>
 bool tsqr_supported(int64_t m, int64_t n) {
     const size_t small_lds = ((size_t)n * (n | 1) + 4 * (size_t)n) * sizeof(T) + (size_t)n * sizeof(int) + 256;
-    return n >= 2 && m >= 4 * n && m >= 1024 && small_lds <= 160 * 1024 - 2048;
+    return n >= 2 && m >= 4 * n && m >= 1024 && small_lds <= kLdsCapWide;
 }
 
 // Y = Q R by CholeskyQR2 with Q left in factored form: Q = q1 r2i.  y: m x n (any strides, not modified), q1: m x n (row-major
@@ -675,17 +671,12 @@ void qrcp_small(rc_context *c, Mat<T> rin, int64_t kmax, bool pivot, int64_t *jp
                              top.rows == q1top.rows && top.cols == q2.cols),
                RC_INVALID_ARGUMENT, "qrcp_small: shape mismatch of the folded products");
     const size_t lds = ((size_t)n * (n | 1) + 3 * (size_t)n) * sizeof(T) + (size_t)n * sizeof(int) + 64;
-    RC_REQUIRE(lds <= 160 * 1024 - 1024 && n <= 208, RC_INVALID_ARGUMENT, "qrcp_small: n = %lld does not fit LDS", (long long)n);
+    RC_REQUIRE(lds <= kLdsCap && n <= 208, RC_INVALID_ARGUMENT, "qrcp_small: n = %lld does not fit LDS", (long long)n);
     ProfScope ps(c, "op:qrcp_small n=%lld k=%lld", (long long)n, (long long)kmax);
 #define RC_QS(NE, NT_)                                                                                                 \
     do {                                                                                                               \
-        auto kern = k_qrcp_small<T, NE, NT_>;                                                                          \
-        static bool attr_set[64] = {};                                                                                 \
-        if (!attr_set[c->device & 63]) {                                                                               \
-            RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024)); \
-            attr_set[c->device & 63] = true;                                                                           \
-        }                                                                                                              \
-        hipLaunchKernelGGL(kern, dim3(1), dim3(NT_), lds, c->stream, rin, (int)kmax, pivot ? 1 : 0, jpvt, rout, q2, (T *)nullptr); \
+        raise_lds_limit<k_qrcp_small<T, NE, NT_>>(c->device, kLdsCap);                                                 \
+        hipLaunchKernelGGL((k_qrcp_small<T, NE, NT_>), dim3(1), dim3(NT_), lds, c->stream, rin, (int)kmax, pivot ? 1 : 0, jpvt, rout, q2, (T *)nullptr); \
     } while (0)
     static const int wide = env_int("RC_QRCP_SMALL_1024", 1);
     // workgroups of the separate Q2 launch (0: Q2 stays inside k_qrcp_small).  With fewer than 8 compressions side by side the
@@ -695,20 +686,14 @@ void qrcp_small(rc_context *c, Mat<T> rin, int64_t kmax, bool pivot, int64_t *jp
         ArenaMark mark(c);
         const size_t nt = (size_t)n * (n | 1) + 3 * (size_t)n;
         T *img = c->alloc<T>(nt + (size_t)n);  // (n ints behind nt words of T)
-        auto kf = k_qrcp_small<T, 18, 1024, true>;
-        auto kq = k_qrcp_small_q2<T, 18>;
-        static bool attr_set[64] = {};
-        if (!attr_set[c->device & 63]) {
-            RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kf), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-            RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kq), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-            attr_set[c->device & 63] = true;
-        }
-        hipLaunchKernelGGL(kf, dim3(1), dim3(1024), lds, c->stream, rin, (int)kmax, pivot ? 1 : 0, jpvt, rout, q2, img);
+        raise_lds_limit<k_qrcp_small<T, 18, 1024, true>>(c->device, kLdsCap);
+        raise_lds_limit<k_qrcp_small_q2<T, 18>>(c->device, kLdsCap);
+        hipLaunchKernelGGL((k_qrcp_small<T, 18, 1024, true>), dim3(1), dim3(1024), lds, c->stream, rin, (int)kmax, pivot ? 1 : 0, jpvt, rout, q2, img);
         // whole waves of columns per workgroup (8 columns a wave), at most the 128 column groups of a workgroup
         // (with the products behind the columns at most kQ2FoldCols: both sets of columns stand in LDS where the image was)
         const int cpw = (int)std::min<int64_t>(cdiv(cdiv(q2.cols, q2_wgs), 8) * 8, w.empty() ? 128 : kQ2FoldCols);
         ProfScope pq(c, "op:qrcp_small_q2 n=%lld cols=%lld wgs=%d", (long long)n, (long long)q2.cols, (int)cdiv(q2.cols, cpw));
-        hipLaunchKernelGGL(kq, dim3((unsigned)cdiv(q2.cols, cpw)), dim3(1024), lds, c->stream, (const T *)img, (int)n, (int)kmax, q2, cpw, r2i, q1top, w, top);
+        hipLaunchKernelGGL((k_qrcp_small_q2<T, 18>), dim3((unsigned)cdiv(q2.cols, cpw)), dim3(1024), lds, c->stream, (const T *)img, (int)n, (int)kmax, q2, cpw, r2i, q1top, w, top);
         return;
     }
     if (n <= 64) RC_QS(8, 512);
@@ -770,14 +755,9 @@ template <typename T>
 static void householder_signs(rc_context *c, Mat<T> top, T *d) {
     const int64_t k = top.cols;
     const size_t lds = (size_t)k * (k | 1) * sizeof(T);
-    RC_REQUIRE(top.rows >= k && lds <= 160 * 1024 - 1024, RC_INVALID_ARGUMENT, "sign fix: k = %lld does not fit LDS", (long long)k);
-    auto kern = k_householder_signs<T>;
-    static bool attr_set[64] = {};
-    if (!attr_set[c->device & 63]) {
-        RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-        attr_set[c->device & 63] = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(1), dim3(1024), lds, c->stream, top, d);
+    RC_REQUIRE(top.rows >= k && lds <= kLdsCap, RC_INVALID_ARGUMENT, "sign fix: k = %lld does not fit LDS", (long long)k);
+    raise_lds_limit<k_householder_signs<T>>(c->device, kLdsCap);
+    hipLaunchKernelGGL(k_householder_signs<T>, dim3(1), dim3(1024), lds, c->stream, top, d);
 }
 template <typename T>
 static void scale_cols_rows(rc_context *c, Mat<T> q, Mat<T> r, const T *d) {

@@ -35,6 +35,7 @@
 #include <cstdlib>
 #include "rc_device.hpp"
 #include "jacobi_lds.hpp"
+#include "rc_launch.hpp"
 
 #include <chrono>
 #include <mutex>
@@ -631,8 +632,7 @@ unsigned coop_budget_units(int device) {
     std::lock_guard<std::mutex> lk(mu);
     unsigned &b = total[device & 63];
     if (!b) {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
+        const int cus = device_cus(device);
         static const int v = env_int("RC_COOP_BUDGET", 0);  // in CUs (experiments)
         b = (unsigned)(v >= 32 && v <= cus ? 2 * v : 2 * cus * 3 / 4);
     }
@@ -791,12 +791,8 @@ void geqp3_wide_coop_jacobi(rc_context *c, Mat<T> w, Mat<T> wf, int64_t kmax, in
         unsigned *vsync = c->alloc<unsigned>((size_t)nc + 1);
         unsigned long long *chk = c->alloc<unsigned long long>(nrec);
         const JacobiLdsArgs<T> ja{core, log, sweeps, uc, s, order, kMaxSweeps, 1, vsync, chk, c->epoch_word(), vc, c->health_word(), ld};
-        auto kern = k_wq_jacobi_fused<T>;
-        static bool attr_set[64] = {};
-        if (!attr_set[c->device & 63]) {
-            RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048));
-            attr_set[c->device & 63] = true;
-        }
+        constexpr auto kern = k_wq_jacobi_fused<T>;
+        raise_lds_limit<kern>(c->device, kLdsCapWide);
         coop_gate_launch(c, a.units, a.sync, a.hdr, 2 * g * 5, nullptr, vsync, nc + 1);  // (vsync: J4)
         hipLaunchKernelGGL(kern, dim3((unsigned)g + 2), dim3(8 * kFusedGroups), lds, c->stream, a, ja, g);
     }

@@ -8,21 +8,20 @@
 #include <algorithm>
 
 #include "rc_common.hpp"
+#include "rc_launch.hpp"
 
 namespace rc {
 
-// the workgroup of every batched kernel, the dynamic-LDS cap they share, and the persistent grid (kernels_batched_id.hip): the resident
-// workgroups of BATCHED_THREADS threads on every CU, fewer when the workspace (ws_per bytes per workgroup, 0 without one) would pass
-// 256 MiB unless that leaves less than one workgroup per CU; never more than count.  *slots receives the grid before that last bound
-// (slots= in the profile label)
-constexpr int BATCHED_THREADS = 256;
-constexpr size_t BID_MAX_LDS = 160 * 1024 - 1024;
-int64_t bid_grid(rc_context *c, const void *kern, size_t lds, size_t ws_per, int32_t count, int64_t *slots);
-
-// first use of kern on the device (process-wide, behind a mutex; kernels_batched_id.hip): its dynamic-LDS limit is raised to
-// BID_MAX_LDS and its scratch bytes per thread are read.  Every call returns the latter; a thread that asks for the kernel it asked for
-// last gets the answer without the lock.
-int batched_kernel_cap(int device, const void *kern);
+// Declared in rc_launch.hpp and defined in rc_launch.hip, beside the dense launch sites' first-use guard:
+//
+// BATCHED_THREADS, BID_MAX_LDS, bid_grid: the workgroup of every batched kernel, the dynamic-LDS cap they share, and the persistent
+// grid: the resident workgroups of BATCHED_THREADS threads on every CU, fewer when the workspace (ws_per bytes per workgroup, 0 without
+// one) would pass 256 MiB unless that leaves less than one workgroup per CU; never more than count.  *slots receives the grid before
+// that last bound (slots= in the profile label)
+//
+// batched_kernel_cap: first use of kern on the device (process-wide, behind a mutex): its dynamic-LDS limit is raised to BID_MAX_LDS
+// and its scratch bytes per thread are read.  Every call returns the latter; a thread that asks for the kernel it asked for last gets
+// the answer without the lock.
 
 // the tall recompressions (k_batched_recompress<T, true>, k_batched_recompress_c<R, true>): the stage height of their flat Householder TSQR,
 // the stages of an m-row left factor of inner rank q, one stage in the workgroup's slot in elements of the kernel's scalar (the copy, H x K at

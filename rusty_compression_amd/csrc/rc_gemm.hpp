@@ -2,6 +2,7 @@
 // kernels_gemm_pipe.hip: the software-pipelined f64 main loop of the two big products).
 #pragma once
 #include "rc_common.hpp"
+#include "rc_launch.hpp"
 
 namespace rc {
 
